@@ -191,6 +191,29 @@ def a_steps_in_profile(root, ptag):
     return None
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # every file of a dump together, .npy headers included
+
+
+def dump_outputs(out_dir: str, events: np.ndarray) -> dict:
+    """The events of one drain as DIR/events_<field>.npy, one row per event in drain order (stream, slot, seq): every integer
+    field as float64 (exact below 2^53), rdata as float32 [n, 64].  Past DUMP_LIMIT_BYTES a fixed sample of rows (seed 0) is
+    written, in drain order, with its row numbers in events_row.npy."""
+    n = len(events)
+    scalars = [f for f in events.dtype.names if f != "rdata"]
+    row_bytes = 8 * (len(scalars) + 1) + 4 * events.dtype["rdata"].shape[0]
+    keep = max(1, (DUMP_LIMIT_BYTES - 16 * 1024) // row_bytes)
+    rows = np.arange(n) if n <= keep else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    sel = events[rows]
+    os.makedirs(out_dir, exist_ok=True)
+    for f in scalars:
+        col = sel[f].astype(np.int64)
+        assert np.all(np.abs(col) < (1 << 53)), "events_%s: not exact in float64" % f
+        np.save(os.path.join(out_dir, "events_%s.npy" % f), col.astype(np.float64))
+    np.save(os.path.join(out_dir, "events_rdata.npy"), sel["rdata"].astype(np.float32))
+    np.save(os.path.join(out_dir, "events_row.npy"), rows.astype(np.float64))
+    return {"dir": out_dir, "events": n, "events_written": len(rows), "sampled": len(rows) < n}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -200,7 +223,8 @@ def main():
     ap.add_argument("--blocks", type=int, default=48, help="65536-byte blocks per stream per step")
     ap.add_argument("--types", type=lambda x: int(x, 16), default=0x2F)
     ap.add_argument("--thresh", type=int, default=500)
-    ap.add_argument("--unique", type=int, default=0, help="distinct synthetic streams to generate per GPU (0 = auto)")
+    ap.add_argument("--unique", type=int, default=0,
+                    help="distinct synthetic streams to generate per GPU, tiled over the batch (0 = every stream distinct)")
     ap.add_argument("--cpu-budget", type=float, default=12.0,
                     help="upper bound in seconds for each single-thread leg of the CPU baseline (0 = skip)")
     ap.add_argument("--parity-streams", type=int, default=-1,
@@ -230,7 +254,12 @@ def main():
     ap.add_argument("--input-10x", action="store_true",
                     help="BASELINE config 5 instead of config 2: 15.36 MS/s input through the 10:1 front end "
                          "(secondary measurement; the default line stays config 2)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the flush events the last timed step drained (rank 0) to DIR/events_<field>.npy "
+                         "(float64; rdata float32), at most 64 MB in all: the outputs of two builds can be compared file by file")
     a = ap.parse_args()
+    if a.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
     rate = 10 if a.input_10x else 1
 
     if a.gpus < 1:
@@ -273,8 +302,8 @@ def main():
     n_streams, n_blocks = a.streams, a.blocks
     row = n_blocks * api.BLOCK_BYTES * rate
     # ---- synthetic input: distinct seeds per rank; generate `unique` streams and tile them over the batch
-    ncpu = os.cpu_count() or 1
-    unique = a.unique if a.unique > 0 else (n_streams if ncpu >= 32 else min(n_streams, max(16, 8 * ncpu)))
+    # (the input depends on the arguments alone, never on the host: the same command line gives the same batches everywhere)
+    unique = a.unique if a.unique > 0 else n_streams
     t0 = time.perf_counter()
     n_distinct = max(1, a.distinct_batches)
     if rate != 1:
@@ -374,6 +403,8 @@ def main():
         else:
             host_ms["gc_pauses"].append([info.get("generation"), round((time.perf_counter() - gc_t[0]) * 1e3, 3)])
 
+    last_ev = [None]  # the events the most recent drain returned: what a caller of the path receives for its last step
+
     def run(n_steps, collect, src=None, stamps=None):
         n_ev = 0
         queued = 0
@@ -391,7 +422,8 @@ def main():
                         bg[1].copy_(bg[0], non_blocking=True)
             if stamps is not None and t_ret is not None:
                 host_ms["between_drains_max"] = max(host_ms["between_drains_max"], (time.perf_counter() - t_ret) * 1e3)
-            n_ev += len(r.drain())
+            last_ev[0] = r.drain()
+            n_ev += len(last_ev[0])
             t_ret = time.perf_counter()
             if stamps is not None:
                 stamps.append(time.perf_counter())
@@ -417,6 +449,7 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     elapsed = shard.max_over_ranks(elapsed, red_dev)
+    dumped = dump_outputs(a.dump_outputs, last_ev[0]) if a.dump_outputs and rank == 0 else None
 
     # ---- parity of the state the timed region ran in (carried decoder / biquad / slicer / FIR state, FIFO `depth` deep): one
     # more batch through the same context, a spread of its streams against the oracle CONTINUED over every repetition of
@@ -811,6 +844,8 @@ def main():
             out["utilisation"] = utilisation
         if extra:
             out["other_configs"] = extra
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         print(json.dumps(out), flush=True)
     r.close()
     if rank == 0 and fm["undecidable"]:

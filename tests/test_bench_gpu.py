@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -84,18 +85,45 @@ def test_bench_gpus_2_launches_its_own_ranks():
     assert len(j["config"]["rank_input_crc32"]) == 2
 
 
-def test_bench_gpus_8_same_device():
-    """BASELINE configs[3] dry run: EIGHT ranks of bench.py (64 streams x 8 blocks each) on one device, gloo for the barrier and
-    the scalar reduces -- rendezvous of 8, per-rank seeding, the barrier + MAX-reduce bracket, 8 contexts' memory and the
-    whole-job value at N = 8, before an 8-GPU node ever runs it.  No scaling figure is taken from this."""
+def test_bench_gpus_4_same_device():
+    """BASELINE configs[3] dry run: FOUR ranks of bench.py (64 streams x 8 blocks each) on one device, gloo for the barrier and
+    the scalar reduces -- rendezvous of N > 2, per-rank seeding, the barrier + MAX-reduce bracket, several contexts' memory and
+    the whole-job value, before an 8-GPU node ever runs it.  Four ranks, not eight: together with this process no more than
+    six processes may have one device open.  The rendezvous of eight ranks is covered without a GPU in test_sharding_gloo.py.
+    No scaling figure is taken from this."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--same-device", "--dist-backend",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--same-device", "--dist-backend",
                           "gloo"] + COMMON, capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     j = _line(out.stdout)
-    assert j["n_gpus"] == 8 and j["scaling"] == "weak" and j["value"] > 0
+    assert j["n_gpus"] == 4 and j["scaling"] == "weak" and j["value"] > 0
     c = j["config"]
     assert c["parity_ok"] is True and c["parity_after_timed"] is True and c["atan_host_mismatch"] == 0
-    assert len(set(c["rank_input_crc32"])) == 8  # eight distinct sets of streams
-    assert c["events_all_ranks"] > 4 * c["events_per_step"] * j["steps"]
-    assert abs(j["value"] - 8 * 64 * 8 * 32768 * j["steps"] / (j["ms_per_step"] * j["steps"] * 1e-3) / 1e6) / j["value"] < 1e-3
+    assert len(set(c["rank_input_crc32"])) == 4  # four distinct sets of streams
+    assert c["events_all_ranks"] > 2 * c["events_per_step"] * j["steps"]
+    assert abs(j["value"] - 4 * 64 * 8 * 32768 * j["steps"] / (j["ms_per_step"] * j["steps"] * 1e-3) / 1e6) / j["value"] < 1e-3
+
+
+def test_bench_dump_outputs_are_the_same_run_to_run(tmp_path):
+    """--dump-outputs: the events of the last timed step, written after the timed region; the same command line gives the same
+    input and therefore the same files, and --steps sets the number of timed steps."""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--h2d-steps", "0", "--dump-outputs", str(d)] + COMMON,
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        j = _line(out.stdout)
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and len(j["step_ms"]) == 3
+        assert j["dump_outputs"]["events"] > 0 and j["dump_outputs"]["sampled"] is False
+        files = sorted(os.listdir(d))
+        assert "events_stream.npy" in files and "events_rdata.npy" in files
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 * 10 ** 6
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert all(len(a) == j["dump_outputs"]["events"] for a in arrs.values())
+        assert arrs["events_stream"].min() >= 0 and arrs["events_stream"].max() < 64
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f

@@ -16,7 +16,7 @@ from tfrec_amd import shard, synth
 from oracle import oracle as O
 dist.init_process_group("gloo")
 rank, world = dist.get_rank(), dist.get_world_size()
-N, NB = 6, 8
+N, NB = int(os.environ["SHARD_TEST_STREAMS"]), 8
 a, b = shard.shard_range(rank, world, N)
 lines = []
 for s in range(a, b):
@@ -42,7 +42,7 @@ def _free_port():
     return p
 
 
-def test_two_rank_sharding_matches_single_process(tmp_path):
+def _sharded_run(tmp_path, world, n_streams):
     import json
     from oracle import oracle as O
     from tfrec_amd import synth
@@ -51,18 +51,28 @@ def test_two_rank_sharding_matches_single_process(tmp_path):
     script.write_text(WORKER % ROOT)
     port = _free_port()
     procs = []
-    for r in range(2):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port))
+    for r in range(world):
+        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
+                   MASTER_PORT=str(port), SHARD_TEST_STREAMS=str(n_streams))
         procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE,
                                       stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=300) for p in procs]
     assert all(p.returncode == 0 for p in procs), outs
     res = json.loads(outs[0][0].strip().splitlines()[-1])
     want = []
-    for s in range(6):
+    for s in range(n_streams):
         o = O.Oracle(0x2F, 500)
         o.process(synth.gen_stream(21, s, 8))
         want += ["%d %s" % (s, ln) for ln in o.text().splitlines()]
     assert res["lines"] == sorted(want) and res["total"] == len(want) and len(want) > 0
-    assert res["slowest"] == 2.0
+    assert res["slowest"] == float(world)
+
+
+def test_two_rank_sharding_matches_single_process(tmp_path):
+    _sharded_run(tmp_path, 2, 6)
+
+
+def test_eight_rank_sharding_matches_single_process(tmp_path):
+    """The job size of BASELINE configs[3]: a rendezvous of eight ranks, streams sharded by index (some ranks hold none),
+    the scalar reduces over all eight."""
+    _sharded_run(tmp_path, 8, 6)
