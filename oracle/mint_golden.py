@@ -11,8 +11,10 @@ fixtures the CPU tests replay on any machine:
   tests/golden/config5.json       the same for BASELINE config 5 (15.36 MS/s input, 10:1 stage, int16 entry)
   tests/golden/iq_*.npz           small raw IQ captures with the reference's outputs (generator-independent)
   tests/golden/unit_probes.npz    fm_dev / fm_dev_nrzs / iir2::step probes of the reference functions
+  tests/golden/scenes.json        scene specs (oracle/scenes.py) + hashes + the reference's events/data/text/bit log
 
-Usage:  python oracle/mint_golden.py [--campaign N]   (N extra random streams compared, not stored)
+Usage:  python oracle/mint_golden.py [--campaign N] [--only NAME ...]   (N extra random streams compared, not stored;
+        --only mints just the named sets: kats kat_debug unit_probes streams config5 iq_fixtures scenes)
 """
 from __future__ import annotations
 
@@ -239,6 +241,48 @@ def mint_iq_fixtures(tmp):
                                                                     len(ref["events"]), ref["text"].strip()[:60]))
 
 
+def scene_cases():
+    """The scenes pinned in scenes.json: every row of the families but the dense ones, which are pinned at 4 blocks (their
+    full 24-block form is checked for packing on the oracle by tests/test_scenes_cpu.py); the level rows also with the
+    auto threshold and the wide filter."""
+    from oracle import scenes as S
+
+    cases = []
+    for fam in S.FAMILIES:
+        for row in S.family(fam):
+            if fam == "dense":
+                if not row["name"].endswith("_pm2") and row["name"] != "dense_w356_exact":
+                    continue
+                row = dict(row, n_blocks=4)
+            settings = [(0x2F, 500, 0)] + ([(0x2F, 0, 0), (0x2F, 500, 1)] if fam == "levels" else [])
+            for types, thresh, wide in settings:
+                cases.append(dict(family=fam, spec=row, types=types, thresh=thresh, wide=wide))
+    return cases
+
+
+def mint_scenes(tmp):
+    from oracle import scenes as S
+
+    out = []
+    for c in scene_cases():
+        iq = S.render(c["spec"])
+        tag = "scene %s (%s thresh %d wide %d)" % (c["spec"]["name"], c["family"], c["thresh"], c["wide"])
+        ref = compare_stream(iq, c["types"], c["thresh"], c["wide"], tmp, tag)
+        d = dict(c)
+        d.update(iq_sha256=sha(iq), dec_sha256=sha(ref["dec"]), flushes=S.flush_counts(ref["events"]),
+                 events_sha256=S.events_digest(ref["events"]), data=data_to_json(ref["data"]), text=ref["text"],
+                 bits_sha256=hashlib.sha256(ref["bits"].encode()).hexdigest())
+        out.append(d)
+    # one case per line; the events and the store_bit log as digests (oracle/scenes.py events_digest): the IQ, the events and
+    # the bits are all reproduced from the spec, so hashes pin them as tightly as copies would
+    with open(os.path.join(GOLD, "scenes.json"), "w") as f:
+        f.write('{"source": "oracle/_ref/ref_driver run (real reference hot path) on oracle/scenes.py rows",\n"cases": [\n')
+        f.write(",\n".join(json.dumps(d, sort_keys=True, separators=(",", ":")) for d in out))
+        f.write("\n]}\n")
+    print("scenes: %d cases, %d flushes, %d text lines" % (len(out), sum(sum(c["flushes"]) for c in out),
+                                                          sum(len(c["text"].splitlines()) for c in out)))
+
+
 def mint_unit_probes():
     rng = np.random.default_rng(12345)
     # discriminators: random int16-range quads + exact octant/axis cases (SURVEY App. E.3)
@@ -300,6 +344,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--campaign", type=int, default=0)
     ap.add_argument("--no-mint", action="store_true")
+    ap.add_argument("--only", nargs="+", default=None,
+                    choices=["kats", "kat_debug", "unit_probes", "streams", "config5", "iq_fixtures", "scenes"])
     a = ap.parse_args()
     if not os.path.isdir(O.REFERENCE_DIR):
         print("no /root/reference here: nothing to mint")
@@ -308,12 +354,12 @@ def main():
     os.makedirs(GOLD, exist_ok=True)
     with tempfile.TemporaryDirectory() as tmp:
         if not a.no_mint:
-            mint_kats(tmp)
-            mint_kat_debug(tmp)
-            mint_unit_probes()
-            mint_streams(tmp)
-            mint_config5(tmp)
-            mint_iq_fixtures(tmp)
+            steps = dict(kats=lambda: mint_kats(tmp), kat_debug=lambda: mint_kat_debug(tmp), unit_probes=mint_unit_probes,
+                         streams=lambda: mint_streams(tmp), config5=lambda: mint_config5(tmp),
+                         iq_fixtures=lambda: mint_iq_fixtures(tmp), scenes=lambda: mint_scenes(tmp))
+            for name, step in steps.items():
+                if a.only is None or name in a.only:
+                    step()
         if a.campaign:
             campaign(a.campaign, tmp)
     print("OK")

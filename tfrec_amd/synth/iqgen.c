@@ -273,18 +273,14 @@ static int corrupt_frame(int proto, uint8_t *f, int nbytes, int mode)
 	return nbytes;
 }
 
-static int64_t synth_burst(rng_t *r, work_t *w, int proto, int64_t start, int64_t total, int32_t *si, int32_t *sq,
-			   iqgen_truth_t *tr, int64_t fs, int corrupt)
+/* the on-air bits of one burst (preamble, frame, tail; WHB scrambled); the frame is drawn from r unless given
+ * (given: frame[0..nbytes) already holds it, sync and checksum included).  Returns the frame length after the fault. */
+static int burst_bits(rng_t *r, int proto, int corrupt, int given, uint8_t *frame, int nbytes, uint8_t *bits, size_t *pnb)
 {
-	const int64_t FS = fs;
-	uint8_t frame[64];
-	uint8_t bits[1024];
 	size_t nb = 0;
-	int nbytes;
-	memset(frame, 0, sizeof(frame));
 	switch (proto) {
 	case 0:
-		nbytes = corrupt_frame(proto, frame, frame_tfa1(r, frame), corrupt);
+		nbytes = corrupt_frame(proto, frame, given ? nbytes : frame_tfa1(r, frame), corrupt);
 		for (int i = 0; i < 200; i++) bits[nb++] = 0;
 		put_bits_lsb(bits, &nb, frame, nbytes);
 		for (int i = 0; i < 48; i++) bits[nb++] = 0;
@@ -292,7 +288,8 @@ static int64_t synth_burst(rng_t *r, work_t *w, int proto, int64_t start, int64_
 	case 1:
 	case 2:
 	case 3: {
-		nbytes = corrupt_frame(proto, frame, proto == 3 ? frame_tx22(r, frame) : frame_tfa23(r, frame), corrupt);
+		nbytes = corrupt_frame(proto, frame, given ? nbytes : (proto == 3 ? frame_tx22(r, frame) : frame_tfa23(r, frame)),
+				       corrupt);
 		int pre = proto == 1 ? 4 : (proto == 2 ? 12 : 8);
 		for (int i = 0; i < pre; i++) { bits[nb++] = 1; bits[nb++] = 0; }
 		put_bits_msb(bits, &nb, frame, nbytes);
@@ -300,7 +297,7 @@ static int64_t synth_burst(rng_t *r, work_t *w, int proto, int64_t start, int64_
 		break;
 	}
 	default: {
-		nbytes = corrupt_frame(proto, frame, frame_whb(r, frame), corrupt);
+		nbytes = corrupt_frame(proto, frame, given ? nbytes : frame_whb(r, frame), corrupt);
 		uint8_t d[1024];
 		size_t nd = 0;
 		for (int i = 0; i < 200; i++) d[nd++] = 1;
@@ -317,14 +314,28 @@ static int64_t synth_burst(rng_t *r, work_t *w, int proto, int64_t start, int64_
 		break;
 	}
 	}
+	*pnb = nb;
+	return nbytes;
+}
+
+/* bit clock: bit b ends at input sample floor((b+1) * FS * 1e6 / (baud * (1e6 + ppm))) -- ppm > 0 is a faster clock;
+ * ppm 0 is exactly (b+1) * FS / baud */
+static int64_t bit_end(int64_t b1, int64_t FS, int baud, int ppm)
+{
+	return (b1 * FS * 1000000) / ((int64_t)baud * (1000000 + ppm));
+}
+
+static int64_t burst_len(size_t nb, int64_t FS, int baud, int ppm)
+{
+	const int64_t den = (int64_t)baud * (1000000 + ppm);
+	return ((int64_t)nb * FS * 1000000 + den - 1) / den;
+}
+
+/* ADDS the Q16 signal of bits[0..nb) into si/sq[start..start+len) */
+static void modulate(work_t *w, int proto, const uint8_t *bits, size_t nb, int64_t start, int64_t len, int32_t *si,
+		     int32_t *sq, int64_t FS, int ppm, int32_t amp_q4, int32_t f0, uint32_t ph, int32_t fdev)
+{
 	int baud = baud_tab[proto];
-	int64_t len = ((int64_t)nb * FS + baud - 1) / baud;
-	if (start + len > total)
-		return -1;
-	int32_t amp_q4 = (int32_t)rng_range(r, 30 * 16, 110 * 16);
-	int32_t f0 = (int32_t)rng_range(r, 0, 20000) - 10000;
-	uint32_t ph = (uint32_t)rng_next(r);
-	int32_t fdev = (int32_t)rng_range(r, 30000, 60000);
 	work_reserve(w, (size_t)len);
 	int psk = (proto == 0 || proto == 4);
 	if (psk) {
@@ -333,7 +344,7 @@ static int64_t synth_burst(rng_t *r, work_t *w, int proto, int64_t start, int64_
 		int64_t n = 0;
 		for (size_t b = 0; b < nb; b++) {
 			if (!bits[b]) lv = -lv;
-			int64_t end = ((int64_t)(b + 1) * FS) / baud;
+			int64_t end = bit_end((int64_t)b + 1, FS, baud, ppm);
 			for (; n < end && n < len; n++) w->lvl[n] = lv * 4096;
 		}
 		for (; n < len; n++) w->lvl[n] = lv * 4096;
@@ -342,15 +353,15 @@ static int64_t synth_burst(rng_t *r, work_t *w, int proto, int64_t start, int64_
 		uint32_t dph = (uint32_t)(int32_t)(((int64_t)f0 << 32) / FS);
 		for (int64_t k = 0; k < len; k++) {
 			int64_t a = (int64_t)amp_q4 * w->lvl[k]; /* Q4 * Q12 = Q16 */
-			si[start + k] = (int32_t)((a * sin_q15(ph + 0x40000000u)) >> 15);
-			sq[start + k] = (int32_t)((a * sin_q15(ph)) >> 15);
+			si[start + k] += (int32_t)((a * sin_q15(ph + 0x40000000u)) >> 15);
+			sq[start + k] += (int32_t)((a * sin_q15(ph)) >> 15);
 			ph += dph;
 		}
 	} else {
 		/* CPFSK: instantaneous frequency f0 +- fdev, lightly smoothed (BT ~0.5) */
 		int64_t n = 0;
 		for (size_t b = 0; b < nb; b++) {
-			int64_t end = ((int64_t)(b + 1) * FS) / baud;
+			int64_t end = bit_end((int64_t)b + 1, FS, baud, ppm);
 			for (; n < end && n < len; n++) w->lvl[n] = bits[b] ? 4096 : -4096;
 		}
 		for (; n < len; n++) w->lvl[n] = 0;
@@ -359,11 +370,30 @@ static int64_t synth_burst(rng_t *r, work_t *w, int proto, int64_t start, int64_
 		int64_t a = (int64_t)amp_q4 << 12; /* Q16 */
 		int64_t w0 = ((int64_t)f0 << 32) / FS, wd = ((int64_t)fdev << 32) / FS;
 		for (int64_t k = 0; k < len; k++) {
-			si[start + k] = (int32_t)((a * sin_q15(ph + 0x40000000u)) >> 15);
-			sq[start + k] = (int32_t)((a * sin_q15(ph)) >> 15);
+			si[start + k] += (int32_t)((a * sin_q15(ph + 0x40000000u)) >> 15);
+			sq[start + k] += (int32_t)((a * sin_q15(ph)) >> 15);
 			ph += (uint32_t)(int32_t)(w0 + ((wd * w->lvl[k]) >> 12));
 		}
 	}
+}
+
+/* returns burst length in samples; adds the Q16 signal into si/sq[start..start+len) */
+static int64_t synth_burst(rng_t *r, work_t *w, int proto, int64_t start, int64_t total, int32_t *si, int32_t *sq,
+			   iqgen_truth_t *tr, int64_t fs, int corrupt)
+{
+	uint8_t frame[64];
+	uint8_t bits[1024];
+	size_t nb = 0;
+	memset(frame, 0, sizeof(frame));
+	int nbytes = burst_bits(r, proto, corrupt, 0, frame, 0, bits, &nb);
+	int64_t len = burst_len(nb, fs, baud_tab[proto], 0);
+	if (start + len > total)
+		return -1;
+	int32_t amp_q4 = (int32_t)rng_range(r, 30 * 16, 110 * 16);
+	int32_t f0 = (int32_t)rng_range(r, 0, 20000) - 10000;
+	uint32_t ph = (uint32_t)rng_next(r);
+	int32_t fdev = (int32_t)rng_range(r, 30000, 60000);
+	modulate(w, proto, bits, nb, start, len, si, sq, fs, 0, amp_q4, f0, ph, fdev);
 	if (tr) {
 		tr->proto = proto;
 		tr->nbytes = nbytes;
@@ -377,7 +407,7 @@ static int64_t synth_burst(rng_t *r, work_t *w, int proto, int64_t start, int64_
 }
 
 /* noise + quantisation of [n0,n1): si/sq may be NULL (pure silence) */
-static void quantise(rng_t *r, const int32_t *si, const int32_t *sq, int64_t n, int noise_q8, uint8_t *out)
+static void quantise(rng_t *r, const int32_t *si, const int32_t *sq, int64_t n, int noise_q8, int dc_i, int dc_q, uint8_t *out)
 {
 	/* Irwin-Hall(4) over bytes: mean 510, sigma sqrt(4*(256^2-1)/12) = 147.80; scale to Q16 LSB */
 	const int64_t k = ((int64_t)noise_q8 * 65536 * 1000) / (256 * 147802LL);
@@ -385,8 +415,8 @@ static void quantise(rng_t *r, const int32_t *si, const int32_t *sq, int64_t n, 
 		uint64_t u = rng_next(r);
 		int32_t n1 = (int32_t)((u & 0xff) + ((u >> 8) & 0xff) + ((u >> 16) & 0xff) + ((u >> 24) & 0xff)) - 510;
 		int32_t n2 = (int32_t)(((u >> 32) & 0xff) + ((u >> 40) & 0xff) + ((u >> 48) & 0xff) + ((u >> 56) & 0xff)) - 510;
-		int64_t vi = (si ? si[i] : 0) + n1 * k + (128LL << 16) + 32768;
-		int64_t vq = (sq ? sq[i] : 0) + n2 * k + (128LL << 16) + 32768;
+		int64_t vi = (si ? si[i] : 0) + n1 * k + ((128LL + dc_i) << 16) + 32768;
+		int64_t vq = (sq ? sq[i] : 0) + n2 * k + ((128LL + dc_q) << 16) + 32768;
 		vi >>= 16;
 		vq >>= 16;
 		out[2 * i] = (uint8_t)(vi < 0 ? 0 : (vi > 255 ? 255 : vi));
@@ -440,7 +470,7 @@ int iqgen_stream_ex(uint64_t seed, uint32_t stream, int n_blocks, int proto_mask
 			proto = (proto + 1) % 5;
 		}
 	}
-	quantise(&rn, si, sq, total, noise_q8, out);
+	quantise(&rn, si, sq, total, noise_q8, 0, 0, out);
 	free(si);
 	free(sq);
 	free(w.lvl);
@@ -452,6 +482,80 @@ int iqgen_stream(uint64_t seed, uint32_t stream, int n_blocks, int proto_mask, i
 		 iqgen_truth_t *truth, int truth_cap)
 {
 	return iqgen_stream_rate(seed, stream, n_blocks, proto_mask, noise_q8, out, truth, truth_cap, 1);
+}
+
+/* ---- scenes: an explicit list of bursts (tests of dense windows, repeats, collisions, clock offsets, levels) */
+
+typedef struct {
+	int32_t proto;        /* 0 TFA_1, 1 TFA_2, 2 TFA_3, 3 TX22, 4 WHB */
+	int32_t corrupt;      /* planted fault of corrupt_frame (0 none) */
+	int64_t start;        /* first input sample of the first copy */
+	int32_t amp_q4;       /* amplitude in 1/16 LSB */
+	int32_t f0_hz;        /* carrier offset */
+	int32_t baud_ppm;     /* bit clock offset: the bit rate is baud * (1 + ppm / 1e6) */
+	int32_t fdev_hz;      /* FSK deviation (TFA_2 / TFA_3 / TX22) */
+	int32_t repeats;      /* copies of the same frame (< 1 counts as 1) */
+	int32_t repeat_gap;   /* input samples from the end of one copy to the start of the next */
+	int32_t nbytes;       /* > 0: frame[0..nbytes) is the frame, sync and checksum included; 0: drawn from payload_seed */
+	int32_t pad;
+	uint64_t payload_seed;
+	uint8_t frame[64];
+} iqgen_burst_t;
+
+/* One stream of n_blocks*65536*rate_mult bytes holding the given bursts: overlapping bursts add up before the
+ * quantiser clips them; dc_i / dc_q shift the rails by whole LSB.  Only the noise draws random numbers besides the
+ * payloads (from payload_seed) and the start phases (from seed and the burst's index).  One truth record per copy
+ * that fits (a copy that would run past the end is left out); returns the number of copies planted. */
+int iqgen_scene(uint64_t seed, int n_blocks, const iqgen_burst_t *bursts, int n_bursts, int noise_q8, int dc_i, int dc_q,
+		int rate_mult, uint8_t *out, iqgen_truth_t *truth, int truth_cap)
+{
+	rng_t rn;
+	rng_seed(&rn, seed ^ 0x5851F42D4C957F2DULL, 0x5CE7E5u);
+	const int64_t fs = (int64_t)FS_BASE * rate_mult;
+	const int64_t total = (int64_t)n_blocks * BLOCK_SAMPLES * rate_mult;
+	int32_t *si = (int32_t *)calloc((size_t)total, sizeof(int32_t));
+	int32_t *sq = (int32_t *)calloc((size_t)total, sizeof(int32_t));
+	work_t w = { 0, 0, 0 };
+	int nt = 0;
+	for (int k = 0; k < n_bursts; k++) {
+		const iqgen_burst_t *b = &bursts[k];
+		if (b->proto < 0 || b->proto > 4 || b->nbytes < 0 || b->nbytes > 64 || b->baud_ppm <= -500000)
+			continue;
+		rng_t rp, rs;
+		rng_seed(&rp, b->payload_seed, 0xF4A3u);
+		rng_seed(&rs, seed, 0x10000u + (uint32_t)k);
+		uint8_t frame[64];
+		uint8_t bits[1024];
+		size_t nb = 0;
+		memcpy(frame, b->frame, 64);
+		int nbytes = burst_bits(&rp, b->proto, b->corrupt, b->nbytes > 0, frame, b->nbytes, bits, &nb);
+		int64_t len = burst_len(nb, fs, baud_tab[b->proto], b->baud_ppm);
+		int64_t pos = b->start;
+		for (int c = 0; c < (b->repeats < 1 ? 1 : b->repeats); c++) {
+			uint32_t ph = (uint32_t)rng_next(&rs);
+			if (pos >= 0 && pos + len <= total) {
+				modulate(&w, b->proto, bits, nb, pos, len, si, sq, fs, b->baud_ppm, b->amp_q4, b->f0_hz, ph, b->fdev_hz);
+				if (truth && nt < truth_cap) {
+					iqgen_truth_t *tr = &truth[nt];
+					tr->proto = b->proto;
+					tr->nbytes = nbytes;
+					tr->start = pos;
+					tr->length = len;
+					tr->amp_q4 = b->amp_q4;
+					tr->f0_hz = b->f0_hz;
+					memcpy(tr->frame, frame, 64);
+				}
+				nt++;
+			}
+			pos += len + b->repeat_gap;
+		}
+	}
+	quantise(&rn, si, sq, total, noise_q8, dc_i, dc_q, out);
+	free(si);
+	free(sq);
+	free(w.lvl);
+	free(w.tmp);
+	return nt;
 }
 
 /* Batch: streams first_stream .. first_stream+n_streams-1, contiguous in out. OpenMP over streams. */
