@@ -28,9 +28,9 @@ def test_library_exports_every_declared_symbol():
     assert C.sizeof(api.Config) == 32 and api.EVENT_DTYPE.itemsize == 96
 
 
-def test_product_library_has_no_environment_knobs_and_the_experiments_build_exports_the_same_abi():
+def test_product_library_has_no_knobs_and_the_experiments_build_has_only_the_kept_ones_and_the_same_abi():
     """csrc/knobs.h: the library bench.py and the adapter load is built without TFREC_AMD_EXPERIMENTS -- no getenv import, no knob
-    name, no what-if switch or test hook in the binary; libtfrec_amd_exp.so (same sources) has them and the same C ABI."""
+    name, no test hook in the binary; libtfrec_amd_exp.so (same sources) has them and the same C ABI, and no retired knob."""
     import subprocess
     from tfrec_amd import _build
 
@@ -43,7 +43,13 @@ def test_product_library_has_no_environment_knobs_and_the_experiments_build_expo
     for knob in (b"TFREC_AMD_SKIP", b"TFREC_AMD_WHB_FORCE_FAIL", b"TFREC_AMD_WHB_TEST_PERTURB", b"TFREC_AMD_LANES_", b"_DIV",
                  b"TFREC_AMD_LDS_PAD", b"TFREC_AMD_DEEP", b"TFREC_AMD_"):
         assert knob not in prod, knob
-    assert b"TFREC_AMD_SKIP" in expl and b"TFREC_AMD_WHB_FORCE_FAIL" in expl
+    assert b"TFREC_AMD_DEEP" in expl and b"TFREC_AMD_WHB_FORCE_FAIL" in expl
+    # the A/B variants of rounds 1-6 are retired (profiles/NOTES.md, "retired knobs"): not even the experiments build reads them
+    for knob in (b"TFREC_AMD_SKIP", b"TFREC_AMD_LANES_", b"_DIV", b"TFREC_AMD_LDS_PAD", b"TFREC_AMD_FE_LDS_PAD", b"TFREC_AMD_WHB_LDS",
+                 b"TFREC_AMD_COOP_", b"TFREC_AMD_HEAD_CHUNKS", b"TFREC_AMD_FMDEV_", b"TFREC_AMD_WHB_EXACT",
+                 b"TFREC_AMD_WHB_CHECK_ROWS", b"TFREC_AMD_T1_EARLY", b"TFREC_AMD_SCAN_KW", b"TFREC_AMD_SPEC_OWN", b"TFREC_AMD_COPY_OWN",
+                 b"TFREC_AMD_PRIO", b"TFREC_AMD_FS_CU", b"TFREC_AMD_COPY_KERNEL", b"TFREC_AMD_COPY_BLOCKS", b"TFREC_AMD_FE_PERSIST"):
+        assert knob not in expl, knob
     # ... and it does not import getenv at all
     syms = subprocess.run(["nm", "-D", "--undefined-only", _build.LIB_SO], capture_output=True, text=True, check=True).stdout
     assert "getenv" not in syms

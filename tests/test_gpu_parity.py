@@ -659,7 +659,8 @@ def test_event_buffer_overflow_is_reported_and_the_context_goes_on():
 @pytest.mark.parametrize("deep", ["1", "0"])
 @pytest.mark.parametrize("every", [1, 3])
 def test_whb_speculation_failures_are_redone_exactly(every, deep, monkeypatch):
-    """WHB stage 2 speculates its decision levels and whb_verify_kernel checks them against the exact recurrence; a stream
+    """WHB stage 2 speculates its decision levels and whb_chain_kernel + whb_check_kernel check them against the exact
+    recurrence (a stream per lane); a stream
     that fails is redone by the exact kernel from the state the submit started from, its speculative events retracted, and
     every later submit that was speculated from the superseded state is redone too.  TFREC_AMD_WHB_FORCE_FAIL declares
     every N-th (stream + submit) failed: the events must still be the oracle's -- with four submits in flight (a failed
@@ -691,8 +692,8 @@ def test_whb_speculation_failures_are_redone_exactly(every, deep, monkeypatch):
 
 
 def test_whb_speculation_is_verified_and_rarely_fails():
-    """Without forced failures: the speculative WHB stage reproduces the exact kernel's events (TFREC_AMD_WHB_EXACT=1 is the
-    wave-per-stream recurrence, exact by itself) and the verification accepts practically every stream."""
+    """Without forced failures: the speculative WHB stage reproduces the oracle's events and the check accepts practically
+    every stream."""
     n_streams, n_blocks = 64, 24
     iq = synth.gen_batch(92, 0, n_streams, n_blocks)
     with api.Receiver(n_streams, 0x20, 500, 0, max_blocks=n_blocks, all_flushes=True) as r:

@@ -1,7 +1,7 @@
 """In-tree build of the native libraries (hipcc cross-compiles gfx950 without a GPU).
 
 Two builds of the same HIP sources (tfrec_amd/csrc/knobs.h):
-  libtfrec_amd.so      the product: no environment knobs, no what-if branches, no test hooks in the binary;
+  libtfrec_amd.so      the product: no environment knobs, no test hooks in the binary;
   libtfrec_amd_exp.so  -DTFREC_AMD_EXPERIMENTS: the knobs read from the environment (tests that drive a hook, A/B sessions).
 
 Staleness is decided by CONTENT, not by time stamps: every object and library has a side file `<target>.stamp` holding the

@@ -87,15 +87,13 @@ struct tfrec_amd_ctx {
 	// high-priority streams, and cp (with k2 / kw in the deep layout) has normal priority -- no pool holds more than
 	// four streams, whatever GPU_MAX_HW_QUEUES is.
 	hipStream_t cp = nullptr;
-	bool deep = false;
-	bool scan_on_kw = false;                      // deep layout: the window scan runs at the head of kw, not on fs
-	bool fmdev_k2 = false;                        // the discriminator pass runs at the head of k2, not behind the front end
+	bool deep = false;                            // deep layout: the window scan runs at the head of kw, not on fs
+	bool fmdev_k2 = false;                        // the discriminator pass runs ahead of k2 (on fq), not behind the front end
 	hipEvent_t ev_in[kSets] = {}, ev_front[kSets] = {};
-	hipEvent_t ev_pipe[kSets][8] = {};
-	hipStream_t fq = nullptr;                    // PipeCtl::fq (TFREC_AMD_FMDEV_OWN)
-	hipStream_t ks = nullptr;                    // PipeCtl::ks (TFREC_AMD_SPEC_OWN)
-	hipStream_t cq = nullptr;                    // the drain's copies, when not on cp (TFREC_AMD_COPY_OWN)
-	hipStream_t cz = nullptr;                    // PipeCtl::cz (TFREC_AMD_COOP_STREAM)                // per set: window scan done, TFA_1 fork, TFA_2 / WHB biquads done
+	hipEvent_t ev_pipe[kSets][6] = {};            // per set: PipeCtl's ev_win, ev_fork, ev_k2, ev_kw, ev_fm, ev_spec
+	hipStream_t fq = nullptr;                     // PipeCtl::fq (deep layout, fmdev_k2), low priority
+	hipStream_t ks = nullptr;                     // PipeCtl::ks (when fq exists), low priority
+	hipStream_t cq = nullptr;                     // the drain's copies (deep layout; else on cp), low priority
 	int last_set = 0;
 	// one set per submit in flight, like the front-end outputs: the window scan and the biquads of submit k+1 fill
 	// theirs while the slicers of submit k still read the other
@@ -112,7 +110,7 @@ struct tfrec_amd_ctx {
 	int whb_test_perturb = 0;                    // TFREC_AMD_WHB_TEST_PERTURB (tests)
 	int whb_force_fail = 0;                      // TFREC_AMD_WHB_FORCE_FAIL (tests)
 	int submit_seq = 0;
-	hipStream_t vx = nullptr;                    // whb_verify_kernel: an alias of cp (deep layout) or of aux
+	hipStream_t vx = nullptr;                    // the WHB check: an alias of cp (deep layout) or of aux
 	hipEvent_t ev_aux[kSets] = {};               // whb_demod_kernel of the set's submit done
 	FskState *d_fsk = nullptr;  // auto-threshold mode only
 	int wmax = 0;
@@ -325,8 +323,6 @@ int tfrec_amd_destroy(tfrec_amd_ctx *c)
 				(void)hipEventDestroy(e);
 	}
 	(void)hipFree(c->d_tcarry);
-	if (c->cz)
-		(void)hipStreamDestroy(c->cz);
 	if (c->fq)
 		(void)hipStreamDestroy(c->fq);
 	if (c->ks)
@@ -700,30 +696,11 @@ int tfrec_amd_create(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
 	// Every pipeline stream except the biquad stages runs at high priority.  With the front end at low priority
 	// ("fill what the latency-bound chains leave free") its kernel stretched from 3 to 11 ms beside the chains and,
 	// with three submits in flight, became the longest stage of all: 13.4 ms per batch instead of 11.7.
+	// (The biquad stages and cp run at normal priority, 0; the discriminator pass, the TFA_2 family's speculative pass and the
+	// drain's copies, when they have streams of their own, at low priority.)
 	int prio_lo = 0, prio_hi = 0;
 	(void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-	const int prio_fs = TFREC_KNOB_STR("PRIO_FS") ? atoi(TFREC_KNOB_STR("PRIO_FS")) : prio_hi;
-	// (experiments: TFREC_AMD_PRIO = one letter h / n / l per stream in the order fs cp cs t1 aux k2 kw, default "hnhhhnn")
-	const char *prio_env = TFREC_KNOB_STR("PRIO");
-	auto prio_of = [&](int k, int dflt) {
-		if (!prio_env || strlen(prio_env) <= (size_t)k)
-			return dflt;
-		return prio_env[k] == 'h' ? prio_hi : (prio_env[k] == 'l' ? prio_lo : 0);
-	};
-	auto mkstream = [&](hipStream_t *st, int k, int dflt) { return hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio_of(k, dflt)); };
-	// (experiment, TFREC_AMD_FS_CUS=n: the front end's stream confined to n of the chip's compute units (a CU mask; such a stream has
-	// normal priority) -- at high priority its 196 k workgroups hold the workgroup dispatcher for their whole duration and nothing else
-	// STARTS meanwhile: profiles/r06_final_steps.txt)
-	auto mk_fs = [&]() -> hipError_t {
-		const int ncu = TFREC_KNOB_INT("FS_CUS", 0, 0, 256);
-		if (ncu <= 0)
-			return mkstream(&c->fs, 0, prio_fs);
-		uint32_t mask[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-		const int stride = TFREC_KNOB_INT("FS_CU_STRIDE", 1, 1, 8);  // 1: the lowest n bits; k: every k-th bit
-		for (int i = 0, set = 0; i < 256 && set < ncu; i += stride, set++)
-			mask[i >> 5] |= 1u << (i & 31);
-		return hipExtStreamCreateWithCUMask(&c->fs, 8, mask);
-	};
+	auto mkstream = [](hipStream_t *st, int prio) { return hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio); };
 	if (rc == TFREC_AMD_OK) {
 		// zero FIR history == u8 value 128 (decimate::decimate zeroes hist0, dsp_stuff.cpp:145-152)
 		EventBuf eb;
@@ -736,10 +713,9 @@ int tfrec_amd_create(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
 				  hipMemset(c->d_tail10[1], 0x80, n * 112) != hipSuccess)) ||
 		    hipMemset(c->d_eb_fresh, 0, kEvFreshBytes) != hipSuccess ||
 		    hipMemcpy(c->d_eb_fresh, &eb, sizeof(eb), hipMemcpyHostToDevice) != hipSuccess ||
-		    mk_fs() != hipSuccess ||
-		    mkstream(&c->cp, 1, 0) != hipSuccess ||
-		    mkstream(&c->cs, 2, prio_hi) != hipSuccess ||
-		    false)
+		    mkstream(&c->fs, prio_hi) != hipSuccess ||
+		    mkstream(&c->cp, 0) != hipSuccess ||
+		    mkstream(&c->cs, prio_hi) != hipSuccess)
 			rc = TFREC_AMD_E_HIP;
 		for (int k = 0; k < kSets && rc == TFREC_AMD_OK; k++) {
 			for (auto &e : c->done[k])
@@ -756,7 +732,7 @@ int tfrec_amd_create(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
 		}
 	}
 	if (rc == TFREC_AMD_OK && !(cfg->flags & TFREC_AMD_F_SERIAL_CHAINS)) {
-		if (mkstream(&c->t1, 3, prio_hi) != hipSuccess || mkstream(&c->aux, 4, prio_hi) != hipSuccess)
+		if (mkstream(&c->t1, prio_hi) != hipSuccess || mkstream(&c->aux, prio_hi) != hipSuccess)
 			rc = TFREC_AMD_E_HIP;
 		// deep layout (default; TFREC_AMD_DEEP=0 selects the shallow one): the biquad stages get streams of their own
 		const char *dp = TFREC_KNOB_STR("DEEP");
@@ -767,52 +743,32 @@ int tfrec_amd_create(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
 		bool has_whb = false;
 		for (int a = 0; a < c->launch.n_active; a++)
 			has_whb = has_whb || c->launch.params[a].kind == 2;
-		c->scan_on_kw = TFREC_KNOB_INT("SCAN_KW", 1, 0, 1) != 0;
-		c->fmdev_k2 = TFREC_KNOB_INT("FMDEV_K2", has_whb ? 1 : 0, 0, 1) != 0;
+		c->fmdev_k2 = has_whb;
 		c->k2 = c->cs;
 		c->kw = c->aux;
 		c->vx = c->aux;
 		if (c->deep && rc == TFREC_AMD_OK &&
-		    (mkstream(&c->k2, 5, 0) != hipSuccess || mkstream(&c->kw, 6, 0) != hipSuccess))
+		    (mkstream(&c->k2, 0) != hipSuccess || mkstream(&c->kw, 0) != hipSuccess))
 			rc = TFREC_AMD_E_HIP;
-		// TFREC_AMD_COOP_STREAM=1: a stream for the TFA_2 family's cooperative slicers (PipeCtl::cz).  It is the fifth of high
-		// priority: with the HIP default of four hardware queues per priority it shares one (GPU_MAX_HW_QUEUES >= 8 wanted).
-		if (c->deep && rc == TFREC_AMD_OK && TFREC_KNOB_INT("COOP_STREAM", 0, 0, 2) != 0 &&
-		    hipStreamCreateWithPriority(&c->cz, hipStreamNonBlocking, TFREC_KNOB_INT("COOP_STREAM", 0, 0, 2) == 2 ? 0 : prio_hi) != hipSuccess)
+		// The discriminator pass on a LOW-priority stream of its own when a WHB demodulator is registered.  It needs the front
+		// end only, not the window scan; at the head of k2 it made that stream (discriminator + five biquad kernels) the one that
+		// set the batch period: 6.98 -> 6.60 ms per batch over 100 steps (profiles/r04_ab_fmdev_stream.txt).  The low-priority
+		// pool's hardware queues are otherwise unused, so the stream shares none (a fifth normal-priority stream would).
+		if (c->deep && rc == TFREC_AMD_OK && c->need_fmdev && c->fmdev_k2 && mkstream(&c->fq, prio_lo) != hipSuccess)
 			rc = TFREC_AMD_E_HIP;
-		// The discriminator pass on a LOW-priority stream of its own (TFREC_AMD_FMDEV_OWN: 0 = at the head of k2, 1 = low
-		// (default when a WHB demodulator is registered), 2 = normal, 3 = high priority).  It needs the front end only, not
-		// the window scan; at the head of k2 it made that stream (discriminator + five biquad kernels) the one that set the
-		// batch period: 6.98 -> 6.60 ms per batch over 100 steps (profiles/r04_ab_fmdev_stream.txt).  The low-priority pool's
-		// hardware queues are otherwise unused, so the stream shares none (a fifth normal-priority stream would).
-		{
-			const int m = TFREC_KNOB_INT("FMDEV_OWN", c->fmdev_k2 ? 1 : 0, 0, 3);
-			if (c->deep && rc == TFREC_AMD_OK && m > 0 && c->need_fmdev && c->fmdev_k2 &&
-			    hipStreamCreateWithPriority(&c->fq, hipStreamNonBlocking, m == 1 ? prio_lo : (m == 2 ? 0 : prio_hi)) != hipSuccess)
-				rc = TFREC_AMD_E_HIP;
-		}
-		// The speculative biquad pass of the TFA_2 family on a stream of its own (TFREC_AMD_SPEC_OWN: 0 = at the head of k2,
-		// 1 = low priority (default when the discriminator pass has its stream), 2 = normal, 3 = high): it needs nothing of the
-		// submit before (chains2.hip K3a), so it runs beside that submit's repair passes and chain walk on k2.  The third
-		// stream of the low-priority pool (with fq and cq): no shared hardware queue.
-		{
-			const int m = TFREC_KNOB_INT("SPEC_OWN", 1, 0, 3);
-			if (c->deep && rc == TFREC_AMD_OK && m > 0 && c->fq &&
-			    hipStreamCreateWithPriority(&c->ks, hipStreamNonBlocking, m == 1 ? prio_lo : (m == 2 ? 0 : prio_hi)) != hipSuccess)
-				rc = TFREC_AMD_E_HIP;
-		}
-		// The drain's copy on a low-priority stream of its own (TFREC_AMD_COPY_OWN=0: on cp).  On cp it sat between the WHB
-		// checks of consecutive submits and waits for ALL chains of its submit: the check of submit k + 1 could not start
-		// before the TFA chains of submit k had ended.  6.32 -> 6.21 ms per batch over 100 steps
-		// (profiles/r04_ab_copy_stream.txt); the low pool's hardware queues hold only this stream and the discriminator's.
-		{  // (TFREC_AMD_COPY_OWN: 0 = on cp, 1 = low priority (default), 2 = normal, 3 = high)
-			const int m = TFREC_KNOB_INT("COPY_OWN", 1, 0, 3);
-			if (c->deep && rc == TFREC_AMD_OK && m > 0 &&
-			    hipStreamCreateWithPriority(&c->cq, hipStreamNonBlocking, m == 1 ? prio_lo : (m == 2 ? 0 : prio_hi)) != hipSuccess)
-				rc = TFREC_AMD_E_HIP;
-		}
-		// whb_verify_kernel runs on the copy stream, ahead of its submit's device-to-host copies (they wait for it anyway).
-		// A stream of its own would be the FIFTH of normal priority in the process (k2, kw, cp and the caller's): it shared a
+		// The speculative biquad pass of the TFA_2 family on a low-priority stream of its own (when the discriminator pass has
+		// its stream): it needs nothing of the submit before (chains2.hip K3a), so it runs beside that submit's repair passes and
+		// chain walk on k2.  The third stream of the low-priority pool (with fq and cq): no shared hardware queue.
+		if (c->deep && rc == TFREC_AMD_OK && c->fq && mkstream(&c->ks, prio_lo) != hipSuccess)
+			rc = TFREC_AMD_E_HIP;
+		// The drain's copy on a low-priority stream of its own (the shallow layout: on cp).  On cp it sat between the WHB checks
+		// of consecutive submits and waits for ALL chains of its submit: the check of submit k + 1 could not start before the TFA
+		// chains of submit k had ended.  6.32 -> 6.21 ms per batch over 100 steps (profiles/r04_ab_copy_stream.txt);
+		// the low pool's hardware queues hold only this stream and the discriminator's.
+		if (c->deep && rc == TFREC_AMD_OK && mkstream(&c->cq, prio_lo) != hipSuccess)
+			rc = TFREC_AMD_E_HIP;
+		// The WHB check (whb_chain_kernel, whb_check_kernel, the redo) runs on cp, where the drain's copies were until they
+		// moved to cq.  A stream of its own would be the FIFTH of normal priority in the process (k2, kw, cp and the caller's): it shared a
 		// hardware queue with kw, and the 6 ms verification of submit k held up the WHB biquads of submit k + 2.
 		if (c->deep)
 			c->vx = c->cp;
@@ -883,11 +839,6 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		fin = (const uint8_t *)c->d_in16[set];
 		fstride = c->in16_stride * sizeof(uint32_t);
 	}
-	// (TFREC_AMD_SKIP bit 512, WHAT-IF timing only: after the first 12 submits the front end is left out and the chains run
-	// on what the buffer set holds from four submits ago -- what the front end costs the batch period)
-	static const bool whatif_no_fe = (TFREC_KNOB_INT("SKIP", 0, 0, 1 << 16) & 512) != 0;
-	static int whatif_submits = 0;
-	if (!(whatif_no_fe && ++whatif_submits > 12))
 	HIPCHK(launch_frontend(fs, fin, fstride, c->cfg.n_streams, n_blocks, c->d_tail[c->tail_sel],
 			       c->d_tail[c->tail_sel ^ 1], c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride,
 			       c->d_prevdec[set], c->cfg.thresh ? c->cfg.thresh : 500, c->taps, c->in10x));
@@ -915,7 +866,7 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	} else {
 		PipeCtl P;
 		P.fs = fs;
-		P.ws = (c->deep && c->scan_on_kw) ? c->kw : fs;
+		P.ws = c->deep ? c->kw : fs;
 		P.ev_front = c->ev_front[set];
 		P.k2 = c->k2;
 		P.kw = c->kw;
@@ -930,12 +881,9 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		P.ev_k2 = c->ev_pipe[set][2];
 		P.ev_kw = c->ev_pipe[set][3];
 		P.ev_fm = c->ev_pipe[set][4];
-		P.cz = c->cz;
 		P.fq = c->fq;
 		P.ks = c->ks;
-		P.ev_spec = c->ev_pipe[set][7];
-		P.ev_heads = c->ev_pipe[set][5];
-		P.ev_coop = c->ev_pipe[set][6];
+		P.ev_spec = c->ev_pipe[set][5];
 		for (int k = 0; k < 3; k++)
 			P.done[k] = c->done[set][k];
 		P.tev = (timing && c->tev[set][0]) ? c->tev[set] : nullptr;
@@ -1045,17 +993,11 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	{  // header, overflow flag and the first copied_n events in one go
 		static_assert(kEvHeader % 16 == 0 && sizeof(tfrec_amd_event) % 16 == 0, "drain_copy_kernel moves 16 bytes per lane");
 		const size_t bytes = kEvHeader + (size_t)c->copied_n[set] * sizeof(tfrec_amd_event);
-		static const int copy_kernel = TFREC_KNOB_INT("COPY_KERNEL", 1, 0, 1);  // (0: hipMemcpyAsync, as until round 6)
-		if (copy_kernel) {
-			const size_t n16 = bytes / 16;
-			static const int copy_blocks = TFREC_KNOB_INT("COPY_BLOCKS", 256, 1, 4096);
-			const unsigned blocks = (unsigned)std::min<size_t>((size_t)copy_blocks, (n16 + 255) / 256);
-			hipLaunchKernelGGL(tfrec::drain_copy_kernel, dim3(blocks), dim3(256), 0, cpy, (const uint4 *)c->d_evblock[set],
-					   (uint4 *)c->h_evblock_dev[set], n16);
-			HIPCHK(hipGetLastError());
-		} else {
-			HIPCHK(hipMemcpyAsync(c->h_evblock[set], c->d_evblock[set], bytes, hipMemcpyDeviceToHost, cpy));
-		}
+		const size_t n16 = bytes / 16;
+		const unsigned blocks = (unsigned)std::min<size_t>(256, (n16 + 255) / 256);
+		hipLaunchKernelGGL(tfrec::drain_copy_kernel, dim3(blocks), dim3(256), 0, cpy, (const uint4 *)c->d_evblock[set],
+				   (uint4 *)c->h_evblock_dev[set], n16);
+		HIPCHK(hipGetLastError());
 	}
 	HIPCHK(hipEventRecord(c->copied[set], cpy));
 	if (timing)
@@ -1136,7 +1078,7 @@ int tfrec_amd_sync(tfrec_amd_ctx *c)
 	if (!c)
 		return TFREC_AMD_E_INVAL;
 	HIPCHK(hipSetDevice(c->cfg.device));
-	for (hipStream_t st : { c->fs, c->k2, c->kw, c->cs, c->cz, c->fq, c->ks, c->cq, c->aux, c->vx, c->t1, c->cp })
+	for (hipStream_t st : { c->fs, c->k2, c->kw, c->cs, c->fq, c->ks, c->cq, c->aux, c->vx, c->t1, c->cp })
 		if (st)
 			HIPCHK(hipStreamSynchronize(st));
 	return TFREC_AMD_OK;
@@ -1445,8 +1387,6 @@ int tfrec_amd_get_timings(tfrec_amd_ctx *c, tfrec_amd_timings *out)
 			HIPCHK(hipEventElapsedTime(k2_ms[k], tev[1 + k], tev[2 + k]));
 		HIPCHK(hipEventElapsedTime(&out->slicer_ms, tev[23], tev[5]));
 		HIPCHK(hipEventElapsedTime(&out->coop_slicer_ms, tev[5], tev[6]));
-		if (c->cz)  // (split off cs: its own marks)
-			HIPCHK(hipEventElapsedTime(&out->coop_slicer_ms, tev[28], tev[29]));
 		HIPCHK(hipEventElapsedTime(&out->decode_ms, tev[6], tev[7]));
 		HIPCHK(hipEventElapsedTime(&out->commit_ms, tev[7], tev[8]));
 	}

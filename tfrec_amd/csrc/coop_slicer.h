@@ -974,7 +974,6 @@ __global__ __launch_bounds__(64) void coop_slicer_kernel(const uint32_t *__restr
 {
 	__shared__ int lds_m[64];
 	__shared__ uint32_t t1_stage[kCoopStageWords];
-	latency_prio();
 	const int M = n_blocks * kBlockDec;
 	const size_t total = (size_t)L.n_active * n_streams * T.cap;
 	const int q = 2 * kind;  // the long windows of this kind

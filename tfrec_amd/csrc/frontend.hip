@@ -31,7 +31,6 @@
 #include <stdlib.h>
 
 #include "dsp_dev.h"
-#include "knobs.h"
 #include <algorithm>
 
 namespace tfrec {
@@ -69,10 +68,7 @@ __global__ __launch_bounds__(kFrontThreads) void frontend_kernel(
 	// MODE.FP_ROUND (fp32) = 2, round toward -inf: see stage 1.  Every fp32 operation of this kernel is either one of
 	// those FMAs or exact.
 	__builtin_amdgcn_s_setreg(1 | (0 << 6) | (1 << 11), 2);
-#ifdef TFREC_AMD_FE_PRIO
-	__builtin_amdgcn_s_setprio(TFREC_AMD_FE_PRIO);
-#endif
-	// A workgroup per tile (persist = 0: grid = tiles x streams), or -- TFREC_AMD_FE_PERSIST=n -- n workgroups that take the
+	// A workgroup per tile (persist = 0: grid = tiles x streams), or -- persist = n -- n workgroups that take the
 	// tiles in turn: the stream's queue is then empty as soon as they are placed, and other streams' kernels can START beside a
 	// running front end (its 196 k workgroups at high priority hold the dispatcher for their whole duration otherwise)
 	const int ntiles = m_total / kTileDec;
@@ -345,7 +341,7 @@ __global__ __launch_bounds__(kFmThreads) void fmdev_kernel(const uint32_t *__res
 							      int ntiles, int n_streams, int persist)
 {
 	// kFmPersist workgroups that take the tiles in turn, like the front end's (393 k workgroups on a low-priority stream were placed
-	// only when every other queue was empty: 3.3 ms inside the batch for 0.8 ms of work; TFREC_AMD_FMDEV_PERSIST=0: a workgroup per tile)
+	// only when every other queue was empty: 3.3 ms inside the batch for 0.8 ms of work)
 	const int n_work = persist ? ntiles * n_streams : 1;
 	for (int wi = persist ? (int)blockIdx.x : 0; wi < n_work; wi += persist ? (int)gridDim.x : 1) {
 	const int s = persist ? wi / ntiles : (int)blockIdx.y, tile = persist ? wi - (wi / ntiles) * ntiles : (int)blockIdx.x;
@@ -356,10 +352,7 @@ __global__ __launch_bounds__(kFmThreads) void fmdev_kernel(const uint32_t *__res
 	// Wave priority 1: the pass heads the TFA_2 family's biquad stream, one of the two chains that end at the period.  At
 	// priority 0 the pipeline has two stable states -- this pass 1.8 ms inside the batch and the batch 6.6 ms, or 2.7 and
 	// 7.3 (two runs in five) --, at priority 1 or 2 only the first (nine runs of nine).
-#ifndef TFREC_AMD_FMDEV_PRIO
-#define TFREC_AMD_FMDEV_PRIO 1
-#endif
-	__builtin_amdgcn_s_setprio(TFREC_AMD_FMDEV_PRIO);
+	__builtin_amdgcn_s_setprio(1);
 	// A sample is read by a demodulator only inside a trigger window, i.e. if a trigger lies at most wmax - 1 samples
 	// before it (the first wmax samples of a submit may belong to a window left open by the previous one).  Decided
 	// per wave = per 256 samples: the mask words of [first - wmax, last], one per lane, one ballot.
@@ -556,17 +549,14 @@ hipError_t launch_frontend(hipStream_t st, const uint8_t *iq, size_t stride, int
 			   bool in16)
 {
 	const int m_total = n_blocks * kBlockDec;
-	// experiment knobs: extra dynamic LDS per workgroup (caps the front end's workgroups per CU); a fixed number of workgroups
-	static const int pad = TFREC_KNOB_INT("FE_LDS_PAD", 0, 0, 64 << 10);
 	// (config 5's int16 entry keeps a workgroup per tile: behind the 10:1 stage, which it waits for, the persistent form measured 4 % slower)
-	static const int persist_u8 = TFREC_KNOB_INT("FE_PERSIST", kFrontPersist, 0, 1 << 20);
-	const int persist = in16 ? 0 : persist_u8;
+	const int persist = in16 ? 0 : kFrontPersist;
 	const dim3 grid = persist ? dim3((unsigned)std::min<long>(persist, (long)(m_total / kTileDec) * n_streams)) : dim3(m_total / kTileDec, n_streams);
 	if (in16)
-		hipLaunchKernelGGL(frontend_kernel<true>, grid, dim3(kFrontThreads), pad, st, iq, stride, m_total, tail_in, tail_out,
+		hipLaunchKernelGGL(frontend_kernel<true>, grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
 				   dec, dec_stride, mask, mask_stride, prevdec, thresh, taps, n_streams, persist);
 	else
-		hipLaunchKernelGGL(frontend_kernel<false>, grid, dim3(kFrontThreads), pad, st, iq, stride, m_total, tail_in, tail_out,
+		hipLaunchKernelGGL(frontend_kernel<false>, grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
 				   dec, dec_stride, mask, mask_stride, prevdec, thresh, taps, n_streams, persist);
 	return hipGetLastError();
 }
@@ -658,10 +648,9 @@ hipError_t launch_fmdev(hipStream_t st, const uint32_t *dec, size_t dec_stride, 
 			int n_streams, int n_blocks, int wmax, double flag_eps)
 {
 	const int m_total = n_blocks * kBlockDec;
-	static const int fm_persist = TFREC_KNOB_INT("FMDEV_PERSIST", kFmPersist, 0, 1 << 20);
-	const dim3 grid = fm_persist ? dim3((unsigned)std::min<long>(fm_persist, (long)(m_total / kFmTile) * n_streams)) : dim3(m_total / kFmTile, n_streams);
+	const dim3 grid((unsigned)std::min<long>(kFmPersist, (long)(m_total / kFmTile) * n_streams));
 	hipLaunchKernelGGL(fmdev_kernel, grid, dim3(kFmThreads), 0, st, dec, dec_stride, mask, mask_stride, prevdec, fmdev,
-			   fmdev_stride, eb, wmax, flag_eps, m_total / kFmTile, n_streams, fm_persist);
+			   fmdev_stride, eb, wmax, flag_eps, m_total / kFmTile, n_streams, kFmPersist);
 	// one-wave workgroups: the kernel normally has nothing to do, and a 256-thread workgroup waits until a CU has four
 	// wave slots and their registers free at once -- up to a millisecond on the stream that sets the batch period
 	hipLaunchKernelGGL(fm_resolve_kernel, dim3(512), dim3(64), 0, st, dec, dec_stride, prevdec, fmdev, fmdev_stride, eb,

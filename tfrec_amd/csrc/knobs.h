@@ -1,13 +1,18 @@
-// Experiment and test knobs of the library.
+// Test and instrumentation knobs of the library.
 //
 // TWO builds of the same sources (tfrec_amd/_build.py):
 //   libtfrec_amd.so      the product -- what bench.py, the adapter and the parity tests load.  Built WITHOUT
-//                        TFREC_AMD_EXPERIMENTS: every knob below is its default as a compile-time constant, the what-if
-//                        branches ("leave kernel group k out", results wrong) and the test hooks (forced WHB failures, a
-//                        perturbed frozen average) fold away, and neither a getenv call nor a knob's name is in the binary
-//                        (`strings libtfrec_amd.so | grep -c TFREC_AMD_SKIP` = 0; tests/test_cabi_cpu.py checks it).
+//                        TFREC_AMD_EXPERIMENTS: every knob below is its default as a compile-time constant, the test hooks
+//                        fold away, and neither a getenv call nor a knob's name is in the binary
+//                        (`strings libtfrec_amd.so | grep -c TFREC_AMD_DEEP` = 0; tests/test_cabi_cpu.py checks it).
 //   libtfrec_amd_exp.so  -DTFREC_AMD_EXPERIMENTS: the knobs are read from the environment.  Loaded only by the tests that
-//                        drive a hook (tests/: api.Receiver(..., experiments=True)) and by the A/B sessions under profiles/.
+//                        drive a hook (tests/: api.Receiver(..., experiments=True)) and by sessions under profiles/.
+// What the knobs are still for (every other A/B variant of rounds 1-6 is retired: profiles/NOTES.md, "retired knobs"):
+//   test hooks        WHB_FORCE_FAIL, WHB_TEST_PERTURB (WHB check failures and redos), FM_FLAG_EPS (the discriminator's exact
+//                     slow path), COPY_GUESS_MIN (the drain's fetch-the-rest path);
+//   stream layout     DEEP=0: the shallow layout (tests and tests/stress_gpu.py run it);
+//   vectorised walks  TFA1_VEC, TFA2_VEC: =0 selects the cooperative slicers' scalar walk (read by the kernels from WinTables);
+//   instrumentation   HOST_PROF (host time per submit / drain), DEBUG_WINHIST, DEBUG_CONVHIST (distributions of one submit).
 // The macros take the knob's name WITHOUT its TFREC_AMD_ prefix; in the product build the name is not expanded at all.
 #pragma once
 

@@ -326,7 +326,7 @@ __device__ __forceinline__ void window_task(int c, int j, int n_streams, int M, 
 // windows are sliced completely.  Of the long TFA_2-family windows only the head, where the thresholds still
 // adapt sample by sample (tfa2.cpp:363 "bitcnt < 10"; cheap per window when 64 windows share a wave, expensive
 // for a whole wave) -- the rest, and the long TFA_1 windows, belong to coop_slicer_kernel.
-__global__ __launch_bounds__(64) TFREC_LAT_VGPR_ATTR void slicer_kernel(const uint32_t *__restrict__ dec, size_t dec_stride,
+__global__ __launch_bounds__(64) void slicer_kernel(const uint32_t *__restrict__ dec, size_t dec_stride,
 						    const int16_t *__restrict__ ld16, int n_streams, int n_blocks, ChainLaunch L,
 						    WinTables T, int lanes, int head_chunks, int kind, int qsel)
 {
@@ -335,10 +335,6 @@ __global__ __launch_bounds__(64) TFREC_LAT_VGPR_ATTR void slicer_kernel(const ui
 	// Dynamic, so that the TFA_2-family launch holds half: these waves live for milliseconds, six of them per CU, and the
 	// front end beside them needs 16.6 KB per workgroup of what the CU's 160 KB have left (profiles/NOTES.md round 3)
 	extern __shared__ uint4 slot_lds[];
-	latency_prio();
-#ifdef TFREC_AMD_SLICER_CLAIM  // (sensitivity experiment: -DTFREC_AMD_SLICER_CLAIM='"v175"' makes the kernel hold that many registers)
-	asm volatile("" ::: TFREC_AMD_SLICER_CLAIM);
-#endif
 	uint4 *my_lds = slot_lds + threadIdx.x;
 	if ((int)threadIdx.x >= lanes)
 		return;
@@ -372,14 +368,13 @@ __global__ __launch_bounds__(64) TFREC_LAT_VGPR_ATTR void slicer_kernel(const ui
 // start == the true value bit for bit when it reaches the piece, and otherwise recomputes the piece itself:
 // exactness does not rest on the warm-up, only speed does.  16 lane-instructions per sample for 64 pieces at once
 // instead of 7 wave-instructions per sample.
-__global__ __launch_bounds__(256) TFREC_LAT_VGPR_ATTR void mark_kernel(const uint32_t *__restrict__ dec, size_t dec_stride, int n_streams,
+__global__ __launch_bounds__(256) void mark_kernel(const uint32_t *__restrict__ dec, size_t dec_stride, int n_streams,
 						  int n_blocks, ChainLaunch L, WinTables T)
 {
-	latency_prio();
 	const int M = n_blocks * kBlockDec;
 	const size_t total = (size_t)L.n_active * n_streams * T.cap;
 	const uint32_t count = T.queue[7].count;
-	// (four independent waves per workgroup, one on each SIMD of a CU: see whb_verify_kernel)
+	// (four independent waves per workgroup, one on each SIMD of a CU)
 	const uint32_t tid = blockIdx.x * 256 + threadIdx.x, nthreads = gridDim.x * 256;
 	for (uint32_t idx = tid; idx < count; idx += nthreads) {
 		const uint2 it = T.items[(size_t)7 * total + idx];

@@ -186,7 +186,7 @@ struct WhbStart {
 };
 
 // One record per 64-sample step in which whb_demod_kernel<false> ran the decision-level average (and one per window that
-// began with the decoder locked, and an end mark): everything whb_verify_kernel needs to walk a stream's submit as ONE
+// began with the decoder locked, and an end mark): everything whb_check_kernel needs to walk a stream's submit as ONE
 // flat sequence with its loads queued several steps ahead -- where the step's stage-1 outputs are, on how many of them the
 // filter ran, the speculated decisions, and what the window froze if the decoder locked in this step.
 struct WhbStepRec {
@@ -201,10 +201,10 @@ constexpr uint32_t kWhbRecAmb = 1u << 29;       // a candidate test of the windo
 constexpr uint32_t kWhbRecClosed = 1u << 30;    // the window's flush fired in this submit
 constexpr uint32_t kWhbRecPseudo = 1u << 31;    // no filter step: a window that began (and stayed) locked
 constexpr uint32_t kWhbRecEnd = 0xffffffffu;    // no more records
-constexpr int kWhbRecSlack = 16;               // records whb_verify_kernel may read past the end mark (never interpreted)
+constexpr int kWhbRecSlack = 16;               // records a check may read past the end mark (never interpreted)
 static_assert(sizeof(WhbStepRec) == 16, "one 16-byte load per record");
 
-// iir_avg of whb_demod (whb.cpp:611, 654) as whb_verify_kernel carries it: the last two outputs, bit for bit, and the
+// iir_avg of whb_demod (whb.cpp:611, 654) as the check carries it: the last two outputs, bit for bit, and the
 // last two inputs (0.5 * a stage-1 output each) as the integers
 struct WhbExact {
 	double y1, y2;
@@ -275,14 +275,14 @@ struct WinTables {
 	                        // shared by the two table sets: the scan of submit k+1 must not wait for the chains of k)
 	// WHB stage 2, speculate + verify (chains2.hip K4'): per 64-sample step in which the decision-level average ran,
 	// the decisions "dev < (int)avg" the demodulator kernel took from its lane-parallel evaluation of the filter
-	WhbStepRec *whbrec;          // [n_streams * whbrec_stride], in the order whb_verify_kernel walks them
+	WhbStepRec *whbrec;          // [n_streams * whbrec_stride], in the order whb_check_kernel walks them
 	int32_t whbrec_stride;       // records a stream can have in one submit (filter steps M / 64 + cap, one per window that
-	                             // begins locked, the end mark) + the slack whb_verify_kernel's prefetch reads ahead
-	WhbExact *whbx;              // [n_streams] the filter's exact state, carried by whb_verify_kernel (ONE array per context)
-	int32_t *whbfail;            // [n_streams] set by whb_verify_kernel: the stream's speculation failed in this submit
+	                             // begins locked, the end mark) + the slack a check's prefetch may read ahead
+	WhbExact *whbx;              // [n_streams] the filter's exact state, carried by the check (ONE array per context)
+	int32_t *whbfail;            // [n_streams] set by whb_check_kernel: the stream's speculation failed in this submit
 	// ... and what the exact kernel needs to do such a stream's submit again:
 	ChainState *whbsnap;         // [n_streams] the WHB chain state whb_demod_kernel<false> started this submit from
-	WhbExact *whbx0;             // [n_streams] the exact filter state whb_verify_kernel started this submit from
+	WhbExact *whbx0;             // [n_streams] the exact filter state the check started this submit from
 	uint32_t *whbseen;           // [n_streams] whbgen[s] as whb_demod_kernel<false> saw it before it read the state
 	uint32_t *whbgen;            // [n_streams] redone submits of the stream so far (ONE array per context)
 	ChainState *whbX;            // [n_streams] the chain state after the stream's last redone submit (ONE array per context)
@@ -322,20 +322,16 @@ struct PipeCtl {
 	hipEvent_t ev_front;       // front end done (fs)
 	hipStream_t k2, kw;        // stage A: biquads of the TFA_2 family / of WHB
 	hipStream_t cs, aux, t1;   // stage B: TFA_2 family, WHB, TFA_1 (no stage A)
-	hipStream_t vx;            // stage C of WHB: whb_verify_kernel (== aux in the shallow layout)
+	hipStream_t vx;            // stage C of WHB: whb_chain_kernel + whb_check_kernel + the redo (== aux in the shallow layout)
 	hipEvent_t ev_aux;         // whb_demod_kernel done (aux)
-	int *whb_carry;            // [n_streams] whb_verify_kernel: exact minus speculated frozen average of a window still open
+	int *whb_carry;            // [n_streams] whb_check_kernel: exact minus speculated frozen average of a window still open
 	hipEvent_t ev_win;         // window scan done (fs)
 	hipEvent_t ev_fork;        // first TFA_2 biquad pass done (k2): TFA_1 starts
 	hipEvent_t ev_k2, ev_kw;   // stage A done
-	hipEvent_t ev_fm;          // the discriminator pass done, when it runs at the head of kw instead of k2
-	// TFA_2 family, stage B split: once the long windows' heads are sliced (cs), the cooperative slicers of their tails
-	// run on cz beside the short windows' slicers on cs (nullptr: one after the other on cs)
-	hipStream_t cz;
-	hipStream_t fq;            // the discriminator pass's own stream (TFREC_AMD_FMDEV_OWN), or nullptr: at the head of k2
-	hipStream_t ks;            // the speculative pass of the TFA_2 family's biquads (TFREC_AMD_SPEC_OWN), or nullptr: at the head of k2
+	hipEvent_t ev_fm;          // the discriminator pass done (fq)
+	hipStream_t fq;            // the discriminator pass's own stream, or nullptr: at the head of k2
+	hipStream_t ks;            // the speculative pass of the TFA_2 family's biquads (needs fq), or nullptr: at the head of k2
 	hipEvent_t ev_spec;        // ... done (ks): the repair passes on k2 start
-	hipEvent_t ev_heads, ev_coop;
 	hipEvent_t done[3];        // end of the submit on cs / aux / t1
 	hipEvent_t *tev;           // optional timing marks (kTimingMarks)
 	// the FM discriminator pass, when it runs at the head of stage A of the TFA_2 family (k2) instead of behind the
@@ -345,7 +341,7 @@ struct PipeCtl {
 	int16_t *fmdev_out;
 	const uint32_t *prevdec;
 };
-constexpr int kTimingMarks = 30;
+constexpr int kTimingMarks = 28;
 
 constexpr int kNQueues = 8;
 // one more counter after the work queues, with a (stream, slot) list behind the queues' items: the TFA_2-family
@@ -358,7 +354,7 @@ constexpr int kSegSlots = TFREC_AMD_SEG_SLOTS;  // biquad segments: 256 in-windo
                                                 // (profiles/r05_ab_segments.txt): 128 -> 256 with the same number of waves = a quarter fewer repair
                                                 // slots, the batch 2.5 % shorter; 512: no better (the passes stretch), 1024: 17 % worse
 constexpr int kSegConverged = 0x40000000, kSegRan = 0x20000000;
-constexpr int kLongWindow = 1024;  // samples; longer windows go to the wave-cooperative slicers (default; TFREC_AMD_COOP_MIN).
+constexpr int kLongWindow = 1024;  // samples; longer windows go to the wave-cooperative slicers (half of it below 1024 chains).
                                    // Until round 5 the cooperative slicers were scalar walks (51 scalar instructions per
                                    // accepted edge) and 4096 measured 4-8 % better than 2048; with a step per lane they cost
                                    // less per window than a lane of the lane-per-window kernels, whose longest window sets

@@ -1,11 +1,11 @@
 // tfrec_amd/csrc/whb_check.h -- WHB stage 2, the check of the speculated decisions as an exact chain PER LANE (round 6).
-// Included by chains2.hip (inside namespace tfrec, behind whb_demod.h and whb_verify.h).
+// Included by chains2.hip (inside namespace tfrec, behind whb_demod.h).
 //
 // whb_demod_kernel<false> speculates the decisions "dev < (int)avg_of" (whb.cpp:654, 662) from a lane-parallel evaluation of
 // iir_avg.  The reference's own recurrence -- iir2::step in its normative association, y = ((B2 + a1 y1) + P) + a2 y2 with
 // P = fma(2, t1, t0), B2 = t2, t = fl((b0 / 2) dev), dsp_dev.h: iir_step_t -- is serial per stream.  Rounds 3-5 ran it with a
-// stream per ROW of 16 lanes (whb_verify_kernel: the feed-forward terms enter through DPP broadcasts): six vector instructions per
-// sample for FOUR streams, 279 M of the batch's 1.95 G vector instructions.  Here a stream is a LANE:
+// stream per ROW of 16 lanes (the feed-forward terms entered through DPP broadcasts): six vector instructions per sample for
+// FOUR streams, 279 M of the batch's 1.95 G vector instructions.  Here a stream is a LANE:
 //
 //   * whb_demod_kernel<false> writes the filter's INPUT SEQUENCE of every stream (WinTables::whbdense): the filter knows neither
 //     windows nor steps -- it pauses while the decoder is locked and goes on where it stopped --, so the sequence is simply every
@@ -19,7 +19,11 @@
 //   * whb_check_kernel (a wave per stream, throughput work): the rest of the sequence (< 64 inputs) serially, the records'
 //     decisions against the exact ones (a prefix sum of the records' lengths gives each its place in the sequence), and for
 //     every lock the frozen integer against (int) of the exact average there -- recomputed from the state the chain kernel left at
-//     the round before, a lane per lock.  Rules, carried state and failure flags are whb_verify_kernel's.
+//     the round before, a lane per lock.  The rule: where the decoder locked, the average was frozen as an integer
+//     (whb.cpp:653-654), and (int) of the speculated double is the exact one's neighbour once in ~200 locks; that is accepted
+//     iff no candidate test of the window could tell the two apart (kWhbRecAmb in the lock's record, set by the demodulator kernel).
+//     All equal: what whb_demod_kernel<false> emitted is the reference's result, and the exact filter state is carried on in
+//     T.whbx.  Otherwise T.whbfail[s] is set: the stream's submit is redone by the exact kernel.
 #pragma once
 
 #ifndef TFREC_AMD_CHK_STREAMS
@@ -62,12 +66,6 @@ __global__ __launch_bounds__(64 * (1 + kChkProducers)) void whb_chain_kernel(int
 		return;
 	if (wave == 0) {
 		// ---------------------------------------------------------------- consumer: a stream per lane
-#ifdef TFREC_AMD_CHK_CLAIM  // the whole register file of its SIMD: no other wave beside the chain (experiment)
-		asm volatile("" ::: "v255", "a255");
-#endif
-#ifdef TFREC_AMD_CHK_PRIO  // (experiment)
-		__builtin_amdgcn_s_setprio(TFREC_AMD_CHK_PRIO);
-#endif
 		double y1 = 0.0, y2 = 0.0;
 		if (my_on) {
 			const WhbExact st = T.whbx[my_s];
@@ -110,11 +108,7 @@ __global__ __launch_bounds__(64 * (1 + kChkProducers)) void whb_chain_kernel(int
 						// |0.5 dev| <= 6.6e8 and the low-pass has an L1 gain of 1.09: (int) never saturates (= x86's cvttsd2si)
 						const int yi = (int)y;
 						// acc = 2 acc + (dev < (int)avg): the compare's bit enters as the carry of acc + acc
-#ifndef TFREC_AMD_CHK_WHATIF_NOCMP  // (timing experiment: the chain without its decisions -- results wrong)
 						asm("v_cmp_lt_i32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(acc[g8 >> 2]) : "v"(dv[j]), "v"(yi) : "vcc");
-#else
-						if (j == 7) acc[g8 >> 2] += (uint32_t)yi + (uint32_t)dv[j];
-#endif
 					}
 				}
 				// (the first input of a half sits in the top bit)
@@ -141,16 +135,10 @@ __global__ __launch_bounds__(64 * (1 + kChkProducers)) void whb_chain_kernel(int
 			h2[q] = __builtin_amdgcn_readfirstlane(st.fd2);
 		}
 		int cur[kChkPerProducer], nxt[kChkPerProducer];  // the lane's input of the round being laid out / of the one after it
-#ifdef TFREC_AMD_CHK_PF3  // (experiment: loads three rounds ahead)
-		int nx2[kChkPerProducer];
-#endif
 #pragma unroll
 		for (int q = 0; q < kChkPerProducer; q++) {
 			cur[q] = rounds[q] > 0 ? row[q][ln] : 0;
 			nxt[q] = rounds[q] > 1 ? row[q][64 + ln] : 0;
-#ifdef TFREC_AMD_CHK_PF3
-			nx2[q] = rounds[q] > 2 ? row[q][128 + ln] : 0;
-#endif
 		}
 		auto lay_out = [&](ChkBuf &b, int r) {  // round r from cur[] (h1, h2: the inputs 64 r - 1, 64 r - 2)
 #pragma unroll
@@ -175,31 +163,17 @@ __global__ __launch_bounds__(64 * (1 + kChkProducers)) void whb_chain_kernel(int
 		for (int r = 0; r < rmax; r++) {
 			// round r + 1 is in nxt[]; the loads of round r + 2 go out before it is laid out
 			int far[kChkPerProducer];
-#ifdef TFREC_AMD_CHK_PF3
-#pragma unroll
-			for (int q = 0; q < kChkPerProducer; q++)
-				far[q] = r + 3 < rounds[q] ? row[q][64 * (r + 3) + ln] : 0;
-#else
 #pragma unroll
 			for (int q = 0; q < kChkPerProducer; q++)
 				far[q] = r + 2 < rounds[q] ? row[q][64 * (r + 2) + ln] : 0;
-#endif
 #pragma unroll
 			for (int q = 0; q < kChkPerProducer; q++)
 				cur[q] = nxt[q];
 			if (r + 1 < rmax)
 				lay_out(buf[(r + 1) & 1], r + 1);
-#ifdef TFREC_AMD_CHK_PF3
-#pragma unroll
-			for (int q = 0; q < kChkPerProducer; q++) {
-				nxt[q] = nx2[q];
-				nx2[q] = far[q];
-			}
-#else
 #pragma unroll
 			for (int q = 0; q < kChkPerProducer; q++)
 				nxt[q] = far[q];
-#endif
 			__syncthreads();
 		}
 	}

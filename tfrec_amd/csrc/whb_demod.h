@@ -74,7 +74,7 @@ __device__ __forceinline__ double row_shr_f64(double v)
 //     y(k) = u(k) + R(k+1) . (y1, y2) + sum_{q < k/16} R(k - 16 q - 15) . E_q,     R(n) = first row of M^n.
 // ~60 vector instructions per step instead of the 6 x 64 of the serial recurrence -- but in another order of
 // operations, so not the reference's bits: the result only SPECULATES the decisions "dev < (int)avg";
-// whb_verify_kernel checks them against the exact recurrence.
+// the check (whb_check.h) compares them with the exact recurrence.
 struct WhbScan {
 	double m2[4], m4[4], m8[4];   // M^2, M^4, M^8 (m11, m12, m21, m22), wave-uniform
 	double cy1, cy2;              // R(k + 1)
@@ -146,7 +146,7 @@ __device__ __forceinline__ double whb_scan_step(const WhbScan &w, double x, doub
 	return y;
 }
 
-// REDO (EXACT only): launched behind whb_verify_kernel over all streams, does the submit of those it failed again.
+// REDO (EXACT only): launched behind whb_check_kernel over all streams, does the submit of those it failed again.
 template <bool EXACT, bool REDO>
 __global__ __launch_bounds__(64) void whb_demod_kernel(const uint32_t *__restrict__ dec, size_t dec_stride,
 						       const int32_t *__restrict__ dev32, int n_streams, int n_blocks,
@@ -159,19 +159,14 @@ __global__ __launch_bounds__(64) void whb_demod_kernel(const uint32_t *__restric
 	// Wave priority 1: since the check stopped being the longest kernel of the batch (round 4) this one is, and its 1024
 	// statically placed waves end with the slowest: 5.5 -> 5.1 ms inside the batch, the batch 1 % shorter
 	// (profiles/r04_ab_whb_prio.txt; priority 2: the same).
-#ifndef TFREC_AMD_WHB_PRIO
-#define TFREC_AMD_WHB_PRIO 1
-#endif
-	__builtin_amdgcn_s_setprio(TFREC_AMD_WHB_PRIO);
+	__builtin_amdgcn_s_setprio(1);
 	// One of these waves per SIMD, never two: the kernel claims 264 of a SIMD's 512 registers (256 + 8 accumulation
 	// registers it never touches).  Its one-wave workgroups are dispatched while the other chains' kernels fill the chip
 	// and land wherever a wave slot is free; two of them on one SIMD share its VALU (the recurrence alone wants 3/4 of
 	// it) and run at half speed, and the kernel ends with its slowest stream: a third of the streams ran doubled up,
 	// the slowest took 2.2x the average (profiles/ubench/whb_cycles.py span); with the claim 8.7 -> 6.7 ms in the batch.
-#ifndef TFREC_AMD_WHB_THIN
 	if (EXACT && !REDO)  // (the redo launch: a thousand workgroups that return at once must not wait for half a SIMD each)
 		asm volatile("" ::: "v255", "a7");
-#endif
 	constexpr int kStep = 64;  // samples per iteration: one per lane
 	const int ln = threadIdx.x;
 	// one wave per stream (the body returns where the stream has nothing more to do)
@@ -183,7 +178,7 @@ __global__ __launch_bounds__(64) void whb_demod_kernel(const uint32_t *__restric
 	constexpr int kStateChunks = (int)(sizeof(ChainState) / 16);
 	static_assert(kStateChunks <= 64, "a wave copies a ChainState in one go");
 	if (!EXACT) {
-		// what a redo of this submit would start from (whb_verify_kernel decides): the generation first, then the state
+		// what a redo of this submit would start from (whb_check_kernel decides): the generation first, then the state
 		const uint32_t gen = __atomic_load_n(&T.whbgen[s], __ATOMIC_RELAXED);
 		__threadfence();
 		if (ln < kStateChunks)
@@ -277,7 +272,7 @@ __global__ __launch_bounds__(64) void whb_demod_kernel(const uint32_t *__restric
 		int sc = sgpr(st.sr_cnt), bc = sgpr(st.byte_cnt);
 		const bool cont = T.cont[c] != 0;
 		// EXACT = false: the filter's steps are evaluated lane-parallel (whb_scan_step) and their decisions recorded for
-		// whb_verify_kernel: one word per step in which the filter ran, numbered through the submit
+		// the check (whb_check.h): one word per step in which the filter ran, numbered through the submit
 		WhbScan scan;
 		if (!EXACT)
 			whb_scan_init(scan, a1, a2, ln);
@@ -624,9 +619,9 @@ __global__ __launch_bounds__(64) void whb_demod_kernel(const uint32_t *__restric
 			res.offset = (int32_t)(uint32_t)((unsigned long long)rssi_out >> 32);
 			res.lbi_out = 0;
 			res.first_cand_g = -1;
-			// for whb_verify_kernel: the filter steps of this window (their records start at mark_lvl), where the decoder
-			// locked (window-relative sample, -1: it did not), the average it froze there, and (last_bit) whether a candidate
-			// test of this window would change with that average off by one
+			// the filter steps of this window (their records start at mark_lvl), where the decoder locked (window-relative
+			// sample, -1: it did not), the average it froze there, and (last_bit) whether a candidate test of this window would
+			// change with that average off by one (the check itself reads the same from the records)
 			res.bitcnt = vstep - vbase;
 			res.dmax = lock_pos;
 			res.dmin = avg_frozen;
@@ -636,7 +631,7 @@ __global__ __launch_bounds__(64) void whb_demod_kernel(const uint32_t *__restric
 			if (ln == 0)
 				T.result[(size_t)c * T.cap + j] = res;
 			if (!EXACT) {
-				// whb_verify_kernel's view of the window's end: the filter's run ended with a lock (the step's record says on
+				// the check's view of the window's end: the filter's run ended with a lock (the step's record says on
 				// which sample, what was frozen, and whether the rest of the window could tell it from its neighbours), or the
 				// window never ran the filter (it began locked: one record without a step)
 				const uint32_t wfl = (amb ? kWhbRecAmb : 0u) | (res.closed ? kWhbRecClosed : 0u);
