@@ -65,7 +65,8 @@ enum {
 #define TFREC_AMD_F_BITS 16u        /* parity/debug: besides the flush events, report every bit the demodulators hand to
 				      decoder::store_bit (decoder.h:39; tfa1.cpp:120, tfa2.cpp:281, whb.cpp:566) as BITS events: status
 				      = TFREC_AMD_STATUS_BITS, byte_cnt = bits in this chunk (<= 512), rdata = the bits, LSB first,
-				      seq = ordinal of the flush they precede, (end_sample, offset) = their order within that flush.
+				      seq = ordinal of the flush they precede, end_sample = the first sample of their trigger window (counted like a
+				      flush's), offset = the chunk's index: (end_sample, offset) is their order within that flush.
 				      Window-parallel pipeline only. */
 #define TFREC_AMD_F_SERIAL_CHAINS 4u /* run the demodulators as one serial lane per (stream, slot) -- the simple
 				      GPU formulation kept as a cross-check of the window-parallel pipeline */
@@ -91,8 +92,8 @@ typedef struct {
 	uint8_t status;     /* 1 = passes the decoder's CRC + sanity checks (a telegram), 2 = rejected, 0 = shorter than a telegram */
 	uint16_t byte_cnt;  /* decoder byte_cnt at flush (saturated at 65535) */
 	int32_t offset;     /* second flush() argument (tfa2.cpp:434; 0 for TFA_1 and WHB) */
-	uint32_t seq;       /* ordinal of this flush within (stream, slot) since context creation */
-	int64_t end_sample; /* decimated sample index (since stream start) at which flush fired */
+	uint32_t seq;       /* ordinal of this flush within (stream, slot) since context creation (or the stream's last reset) */
+	int64_t end_sample; /* decimated sample index (since stream start or its last reset) at which flush fired */
 	int64_t rssi_raw;   /* raw RSSI accumulator: tfa1.cpp:161, tfa2.cpp:373, whb.cpp:678 (an exact integer) */
 	uint8_t rdata[64];  /* decoder rdata[0..64) at flush, before the decoder clears anything */
 } tfrec_amd_event;
@@ -150,6 +151,28 @@ int tfrec_amd_submit_host(tfrec_amd_ctx *ctx, const uint8_t *h_iq, size_t stream
 /* Page-locked host memory for tfrec_amd_submit_host (NULL on failure). */
 void *tfrec_amd_host_alloc(size_t bytes);
 void tfrec_amd_host_free(void *p);
+
+/* Mark streams[0..n) to restart as fresh receivers at the start of the NEXT submit -- what replugging or retuning one stick
+ * of the reference means: restarting that one tfrec process.  Every other stream carries on untouched.
+ *   - The reset falls between the last submit already queued and the next one.  Events of submits still in the FIFO are
+ *     drained unchanged (old seq, old end_sample).  Calls made before one submit accumulate; duplicate indices are allowed;
+ *     n == 0 is a no-op.
+ *   - From the next submit on, a reset stream's events are exactly those of a fresh receiver (tfrec_amd_create with the
+ *     context's types_mask, thresh, filter_type and flags) fed only the input that follows: seq restarts at 0 per slot and
+ *     end_sample counts from the first sample after the reset.
+ *   - A trigger window open at the reset point is dropped without a flush, as the reference drops it at the end of a dump
+ *     (the process exits, engine.cpp:72-76): the events before the reset are those of a fresh receiver run on the old
+ *     input truncated at the cut.
+ *   - Auto threshold (thresh == 0): the stream restarts at 500 (fm_demod.cpp:23-27); tfrec_amd_read_thresh shows it once
+ *     the next submit has run.
+ *   - Context-wide counters (tfrec_amd_get_stats, tfrec_amd_get_fm_stats, timings) are not reset.
+ *   - Every mode: both pipeline layouts, TFREC_AMD_F_SERIAL_CHAINS, _INPUT_10X, _BITS, _ALL_FLUSHES.
+ *   - Cost: a submit that carries resets starts its front end only once every stage of the submit before it has ended (it
+ *     does not overlap it: about twice the period at the benchmark size, however few streams it resets); a
+ *     submit without one runs exactly as before.
+ * Errors: an index outside [0, n_streams), n < 0, or streams == NULL with n > 0: TFREC_AMD_E_INVAL, and nothing is
+ * marked.  A poisoned context: TFREC_AMD_E_STATE. */
+int tfrec_amd_reset_streams(tfrec_amd_ctx *ctx, const int32_t *streams, int n);
 
 /* Wait for submitted work. */
 int tfrec_amd_sync(tfrec_amd_ctx *ctx);

@@ -90,7 +90,7 @@ EXPORTS = (
     "tfrec_amd_pending_events", "tfrec_amd_rssi_db", "tfrec_amd_read_decimated", "tfrec_amd_atan_uncertain",
     "tfrec_amd_get_timings", "tfrec_amd_read_thresh", "tfrec_amd_get_stats", "tfrec_amd_get_layout", "tfrec_amd_host_alloc",
     "tfrec_amd_host_free", "tfrec_amd_read_stage0", "tfrec_amd_get_fm_stats", "tfrec_amd_fm_dev_probe",
-    "tfrec_amd_fifo_depth", "tfrec_amd_get_memory", "tfrec_amd_iir_probe",
+    "tfrec_amd_fifo_depth", "tfrec_amd_get_memory", "tfrec_amd_iir_probe", "tfrec_amd_reset_streams",
 )
 
 _libs = {}
@@ -148,6 +148,7 @@ def load_library(build: bool = True, experiments: bool = False):
     L.tfrec_amd_get_fm_stats.argtypes = [C.c_void_p, C.POINTER(FmStats)]
     L.tfrec_amd_fm_dev_probe.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(FmStats)]
     L.tfrec_amd_iir_probe.argtypes = [C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.tfrec_amd_reset_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.tfrec_amd_fifo_depth.restype = C.c_int
     if L.tfrec_amd_fifo_depth() != FIFO_DEPTH:
         raise RuntimeError("libtfrec_amd.so was built with FIFO depth %d, this binding expects %d" % (
@@ -230,6 +231,15 @@ class Receiver:
 
     def sync(self):
         _check(self.L, self.L.tfrec_amd_sync(self.h))
+
+    def reset_streams(self, streams):
+        """Restart the given streams as fresh receivers from the next submit on (tfrec_amd_reset_streams): submits already
+        queued drain unchanged; afterwards seq restarts at 0 and end_sample counts from the reset."""
+        idx = [int(s) for s in streams]
+        if any(s < 0 or s >= self.n_streams for s in idx):  # (refused before int32 could wrap an index into range)
+            raise TfrecAmdError(E_INVAL, "stream index outside [0, %d)" % self.n_streams)
+        a = np.ascontiguousarray(idx, dtype=np.int32)
+        _check(self.L, self.L.tfrec_amd_reset_streams(self.h, a.ctypes.data if len(a) else None, len(a)))
 
     def drain(self, allow_overflow: bool = False) -> np.ndarray:
         out = np.empty(self.max_events, dtype=EVENT_DTYPE)

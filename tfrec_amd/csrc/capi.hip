@@ -145,6 +145,18 @@ struct tfrec_amd_ctx {
 	size_t stage_bytes[kSets] = {};
 	long long sample_base = 0;
 	int last_blocks = 0;
+	// tfrec_amd_reset_streams: streams marked since the last submit (each once), and the per-stream sample origin -- the
+	// sample_base at the stream's last reset -- that the drain subtracts from end_sample.  A submit records the origins it
+	// ran with (set_origin), so that the drain of an older submit still in the FIFO uses the older ones.
+	std::vector<int32_t> reset_pending;
+	std::vector<uint8_t> reset_marked;
+	std::vector<long long> origin;
+	std::vector<long long> set_origin[kSets];  // empty: no submit before the set's one carried a reset
+	int32_t *d_reset[kSets] = {};  // the submit's reset list on the device (stream_reset_kernel)
+	int32_t *h_reset[kSets] = {};  // ... and its page-locked source
+	ChainState *d_chain_init = nullptr;  // the constructor ChainState (create), source of every reset
+	bool submitted = false;              // done[last_set] has been recorded
+	bool any_reset = false;              // a submit has carried a reset: set_origin is kept from then on
 	hipEvent_t ev[kSets][4] = {};  // start, after the front end, end of the submit, after the discriminator pass
 	hipStream_t aux = nullptr;  // second stream: WHB stage 2 runs beside the TFA slicers
 	hipEvent_t tev[kSets][kTimingMarks] = {};
@@ -177,6 +189,58 @@ __global__ __launch_bounds__(256) void drain_copy_kernel(const uint4 *__restrict
 {
 	for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256)
 		dst[i] = src[i];
+}
+
+// tfrec_amd_reset_streams: every piece of state a submit carries to the next one, back to what tfrec_amd_create made of it,
+// for the streams list[0 .. n_list) (distinct, < n_streams).  A workgroup per listed stream.  See DESIGN.md, "Stream reset".
+struct StreamReset {
+	const int32_t *list;
+	int32_t n_list, n_streams;
+	uint8_t *tail;      // front-end FIR history the NEXT front end reads: tail_bytes per stream, filled with tail_fill
+	int32_t tail_bytes, tail_fill;
+	uint8_t *tail10;    // TFREC_AMD_F_INPUT_10X: the 10:1 stage's raw history (112 bytes per stream of 0x80), or nullptr
+	FskState *fsk;      // auto threshold, or nullptr
+	int32_t n_active;
+	ChainState *states[kNSlots];
+	const ChainState *chain_init;
+	int32_t *tcarry;    // [n_active * n_streams] window scan's timeout carry (window-parallel pipeline), or nullptr
+	WhbExact *whbx;     // WHB check's exact filter state, its carry and the redo's chain state (WHB registered), or nullptr
+	int *whbcarry;
+	ChainState *whbX;
+};
+
+__global__ __launch_bounds__(64) void stream_reset_kernel(StreamReset R)
+{
+	if ((int)blockIdx.x >= R.n_list)
+		return;
+	const int s = R.list[blockIdx.x];
+	if (s < 0 || s >= R.n_streams)
+		return;
+	const int ln = threadIdx.x;
+	for (int i = ln; i < R.tail_bytes; i += 64)
+		R.tail[(size_t)s * R.tail_bytes + i] = (uint8_t)R.tail_fill;
+	if (R.tail10)
+		for (int i = ln; i < 112; i += 64)
+			R.tail10[(size_t)s * 112 + i] = 0x80;
+	constexpr int kChunks = (int)(sizeof(ChainState) / 16);
+	const uint4 *init = reinterpret_cast<const uint4 *>(R.chain_init);
+	for (int a = 0; a < R.n_active; a++)
+		for (int i = ln; i < kChunks; i += 64)
+			reinterpret_cast<uint4 *>(&R.states[a][s])[i] = init[i];
+	if (R.whbX)
+		for (int i = ln; i < kChunks; i += 64)
+			reinterpret_cast<uint4 *>(&R.whbX[s])[i] = init[i];
+	if (ln == 0) {
+		if (R.fsk)
+			R.fsk[s] = FskState{ 500, 0, 0, -(1 << 28) };  // fm_demod.cpp:23-27, as tfrec_amd_create
+		if (R.tcarry)
+			for (int a = 0; a < R.n_active; a++)
+				R.tcarry[(size_t)a * R.n_streams + s] = 0;
+		if (R.whbx) {
+			R.whbx[s] = WhbExact{ 0.0, 0.0, 0, 0, 0, 0 };
+			R.whbcarry[s] = 0;
+		}
+	}
 }
 }  // namespace tfrec
 
@@ -361,6 +425,12 @@ int tfrec_amd_destroy(tfrec_amd_ctx *c)
 				(void)hipEventDestroy(e);
 	}
 	(void)hipFree(c->d_eb_fresh);
+	(void)hipFree(c->d_chain_init);
+	for (int k = 0; k < kSets; k++) {
+		(void)hipFree(c->d_reset[k]);
+		if (c->h_reset[k])
+			(void)hipHostFree(c->h_reset[k]);
+	}
 	for (int k = 0; k < kSets; k++) {
 		if (c->h_evblock[k])
 			(void)hipHostFree(c->h_evblock[k]);
@@ -681,6 +751,19 @@ int tfrec_amd_create(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
 		}
 	}
 	ALLOC(c->d_eb_fresh, kEvFreshBytes);
+	// tfrec_amd_reset_streams: a list of at most n_streams indices per set, and the constructor state it restores
+	ALLOC(c->d_chain_init, sizeof(ChainState));
+	for (int k = 0; k < kSets; k++)
+		ALLOC(c->d_reset[k], n * sizeof(int32_t));
+	if (rc == TFREC_AMD_OK) {
+		ChainState init;
+		memset(&init, 0, sizeof(init));
+		init.sr_cnt = -1;
+		init.dmin = 32767;
+		init.dmax = -32767;
+		if (hipMemcpy(c->d_chain_init, &init, sizeof(init), hipMemcpyHostToDevice) != hipSuccess)
+			rc = TFREC_AMD_E_HIP;
+	}
 #undef ALLOC
 	for (int k = 0; k < kSets && rc == TFREC_AMD_OK; k++) {
 		if (hipHostMalloc((void **)&c->h_evblock[k], kEvHeader + (size_t)cfg->max_events * sizeof(tfrec_amd_event), hipHostMallocDefault) != hipSuccess ||
@@ -692,6 +775,15 @@ int tfrec_amd_create(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
 		c->pinned_bytes += kEvHeader + (size_t)cfg->max_events * sizeof(tfrec_amd_event);
 		c->h_eb[k] = (EventBuf *)c->h_evblock[k];
 		c->h_events[k] = (tfrec_amd_event *)(c->h_evblock[k] + kEvHeader);
+		if (hipHostMalloc((void **)&c->h_reset[k], n * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
+			rc = TFREC_AMD_E_NOMEM;
+			break;
+		}
+		c->pinned_bytes += n * sizeof(int32_t);
+	}
+	if (rc == TFREC_AMD_OK) {
+		c->reset_marked.assign(n, 0);
+		c->origin.assign(n, 0);
 	}
 	// Every pipeline stream except the biquad stages runs at high priority.  With the front end at low priority
 	// ("fill what the latency-bound chains leave free") its kernel stretched from 3 to 11 ms beside the chains and,
@@ -797,6 +889,44 @@ int tfrec_amd_create(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
 	return TFREC_AMD_OK;
 }
 
+// The resets marked since the last submit, at the head of this submit's front end (fs).  Carried state is written by several
+// stages on several streams (a ChainState by the biquad stage, the slicers, the decoders' commit and the WHB check's redo), and
+// in the deep layout those of the submit before may still run while this one's front end does: the front-end stream first
+// waits for the end of every chain of the last submit (done[last_set]: every stage of it and of all earlier submits is behind
+// one of them), then one kernel restores the state of the listed streams.  Every stage of this submit is ordered after its
+// front end, so it reads the restored state.  A submit without a pending reset launches nothing of this.
+static int launch_resets(tfrec_amd_ctx *c, int set)
+{
+	hipStream_t fs = c->fs;
+	if (c->submitted)
+		for (hipEvent_t e : c->done[c->last_set])
+			HIPCHK(hipStreamWaitEvent(fs, e, 0));
+	const int nl = (int)c->reset_pending.size();
+	memcpy(c->h_reset[set], c->reset_pending.data(), (size_t)nl * sizeof(int32_t));  // (the set's last copy was drained)
+	HIPCHK(hipMemcpyAsync(c->d_reset[set], c->h_reset[set], (size_t)nl * sizeof(int32_t), hipMemcpyHostToDevice, fs));
+	StreamReset R;
+	memset(&R, 0, sizeof(R));
+	R.list = c->d_reset[set];
+	R.n_list = nl;
+	R.n_streams = c->cfg.n_streams;
+	R.tail = c->d_tail[c->tail_sel];  // the buffer this submit's front end reads (the history flips per submit)
+	R.tail_bytes = c->in10x ? 2 * kTailBytes : kTailBytes;
+	R.tail_fill = c->in10x ? 0 : 0x80;  // as tfrec_amd_create: int16 zero, or u8 128
+	R.tail10 = c->in10x ? c->d_tail10[c->tail_sel] : nullptr;
+	R.fsk = c->d_fsk;
+	R.n_active = c->launch.n_active;
+	for (int a = 0; a < c->launch.n_active; a++)
+		R.states[a] = c->launch.states[a];
+	R.chain_init = c->d_chain_init;
+	R.tcarry = c->d_tcarry;
+	R.whbx = c->d_whbx;
+	R.whbcarry = c->d_whbcarry;
+	R.whbX = c->d_whbX;
+	hipLaunchKernelGGL(tfrec::stream_reset_kernel, dim3(nl), dim3(64), 0, fs, R);
+	HIPCHK(hipGetLastError());
+	return TFREC_AMD_OK;
+}
+
 // in_stream_is_fs: the input was produced on the front-end stream itself (staged host input): no event needed
 static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int n_blocks, void *hip_stream, bool input_on_fs)
 {
@@ -831,6 +961,12 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	HIPCHK(hipMemcpyAsync(c->d_eb[set], c->d_eb_fresh, kEvFreshBytes, hipMemcpyDeviceToDevice, fs));  // (+ the overflow flag)
 	if (timing)
 		HIPCHK(hipEventRecord(c->ev[set][0], fs));
+	const bool resets = !c->reset_pending.empty();
+	if (resets) {
+		const int rr = launch_resets(c, set);
+		if (rr)
+			return rr;
+	}
 	const uint8_t *fin = (const uint8_t *)d_iq;
 	size_t fstride = stride;
 	if (c->in10x) {  // 15.36 MS/s u8 -> 1.536 MS/s int16 pairs, then the standard cascade on int16 input
@@ -1002,6 +1138,18 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	HIPCHK(hipEventRecord(c->copied[set], cpy));
 	if (timing)
 		c->timed = true;
+	if (resets) {
+		for (int32_t r : c->reset_pending) {
+			c->origin[r] = c->sample_base;
+			c->reset_marked[r] = 0;
+		}
+		c->reset_pending.clear();
+	}
+	// (until the first reset the origins are all zero: nothing is recorded, and the drain subtracts nothing)
+	c->any_reset = c->any_reset || resets;
+	if (c->any_reset)
+		c->set_origin[set] = c->origin;
+	c->submitted = true;
 	c->inflight++;
 	c->last_set = set;
 	c->tail_sel ^= 1;
@@ -1133,6 +1281,12 @@ int tfrec_amd_drain_events(tfrec_amd_ctx *c, tfrec_amd_event *out, int cap, int 
 			if (tmp[i].status != kStatusDead)
 				tmp[live++] = tmp[i];
 	}
+	if (!c->set_origin[set].empty()) {  // end_sample counts from the stream's last reset: flushes and BITS chunks (window opens) alike
+		const std::vector<long long> &org = c->set_origin[set];
+		for (uint32_t i = 0; i < live; i++)
+			if (tmp[i].stream < org.size())
+				tmp[i].end_sample -= org[tmp[i].stream];
+	}
 	c->head = (c->head + 1) % kSets;
 	c->inflight--;
 	c->last_drained = set;
@@ -1191,6 +1345,27 @@ int tfrec_amd_drain_events(tfrec_amd_ctx *c, tfrec_amd_event *out, int cap, int 
 	c->hp_sort += std::chrono::duration<double>(hp3 - hp2).count();
 	c->hp_n++;
 	return overflow ? TFREC_AMD_E_OVERFLOW : TFREC_AMD_OK;
+}
+
+int tfrec_amd_reset_streams(tfrec_amd_ctx *c, const int32_t *streams, int n)
+{
+	if (!c || n < 0 || (n > 0 && !streams))
+		return TFREC_AMD_E_INVAL;
+	for (int i = 0; i < n; i++)
+		if (streams[i] < 0 || streams[i] >= c->cfg.n_streams) {
+			snprintf(g_err, sizeof(g_err), "stream index %d outside [0, %d)", (int)streams[i], c->cfg.n_streams);
+			return TFREC_AMD_E_INVAL;
+		}
+	if (c->poisoned) {
+		snprintf(g_err, sizeof(g_err), "an earlier submit failed half way: the context must be recreated");
+		return TFREC_AMD_E_STATE;
+	}
+	for (int i = 0; i < n; i++)
+		if (!c->reset_marked[streams[i]]) {
+			c->reset_marked[streams[i]] = 1;
+			c->reset_pending.push_back(streams[i]);
+		}
+	return TFREC_AMD_OK;
 }
 
 int tfrec_amd_read_stage0(tfrec_amd_ctx *c, int stream, int16_t *out, size_t n_pairs)

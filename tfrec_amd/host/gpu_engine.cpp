@@ -28,7 +28,7 @@ void tfrec_handler_args(const sensordata_t &d, sensor_e dec_type, char *out, siz
 gpu_engine::gpu_engine(const std::vector<std::string> &dumpfiles, int _types, int _thresh, int _filter, int _dbg,
 		       const std::vector<int> &_devices, int blocks_per_submit)
 	: files(dumpfiles), types(_types), thresh(_thresh), filter(_filter), dbg(_dbg), bps(blocks_per_submit),
-	  devices(_devices), n_telegrams(0), sink(NULL), psink(NULL), out_mode(0), bits_replay(false)
+	  devices(_devices), n_telegrams(0), sink(NULL), psink(NULL), out_mode(0), bits_replay(false), slots(0)
 {
 	if (devices.empty())
 		devices.push_back(0);
@@ -125,6 +125,58 @@ void gpu_engine::replay(const tfrec_amd_event &ev)
 
 namespace {
 
+// One batch of a device context: the blocks every stream gets, the dump file each stream (slot) reads (-1: none, silence),
+// and the streams reset before it is submitted (their previous file ended in the batch before)
+struct batch_plan {
+	int nb;
+	std::vector<int> file;
+	std::vector<int32_t> reset;
+};
+
+// The batches that push the files [s0, s1) through nslots streams of bps blocks (file_blocks: blocks of every file of the job).
+// Files take free streams in order; a file's last batch may be partial (padded with silence, its events cut by the engine).
+// A batch has bps blocks unless no stream needs that many.  With one stream per file this is the plan of a run without -n:
+// every file starts in the first batch and no stream is ever reset.
+std::vector<batch_plan> plan_batches(const std::vector<size_t> &file_blocks, size_t s0, size_t s1, size_t nslots, int bps)
+{
+	std::vector<batch_plan> plan;
+	std::vector<int> cur(nslots, -1);
+	std::vector<size_t> left(nslots, 0);    // blocks of the stream's file still to submit
+	std::vector<bool> used(nslots, false);  // the stream has carried a file: reset it before the next one
+	size_t next = s0;
+	for (;;) {
+		batch_plan b;
+		for (size_t j = 0; j < nslots; j++) {
+			while (cur[j] < 0 && next < s1) {
+				const size_t f = next++;
+				if (file_blocks[f] == 0)
+					continue;  // (no block, no event)
+				cur[j] = (int)f;
+				left[j] = file_blocks[f];
+				if (used[j])
+					b.reset.push_back((int32_t)j);
+				used[j] = true;
+			}
+		}
+		size_t most = 0;
+		for (size_t j = 0; j < nslots; j++)
+			if (cur[j] >= 0)
+				most = std::max(most, left[j]);
+		if (most == 0)
+			break;
+		b.nb = (int)std::min<size_t>((size_t)bps, most);
+		b.file = cur;
+		for (size_t j = 0; j < nslots; j++)
+			if (cur[j] >= 0) {
+				left[j] -= std::min<size_t>(left[j], (size_t)b.nb);
+				if (left[j] == 0)
+					cur[j] = -1;
+			}
+		plan.push_back(std::move(b));
+	}
+	return plan;
+}
+
 // engine::run (engine.cpp:63-93) for the dump files [s0, s1) on ONE device, as a three-stage pipeline over batches of
 // bps blocks:
 //   reader thread : fread batch k+2 of every file into a pinned host buffer (three buffers in rotation)
@@ -137,7 +189,9 @@ struct device_worker {
 	size_t s0, s1;
 	int device, types, thresh, filter, bps;
 	uint32_t flags;     // TFREC_AMD_F_* of the context
-	size_t max_blocks;  // of ALL files: every device runs the same number of batches
+	size_t nslots;      // streams of the context
+	const std::vector<size_t> *file_blocks;  // blocks of every file of the job
+	std::vector<batch_plan> plan;             // plan_batches
 	int rc;
 	std::atomic<bool> *abort;  // set by the engine when any worker failed: stop instead of running the whole job
 	std::mutex mu;
@@ -146,7 +200,7 @@ struct device_worker {
 	bool done;
 	std::thread th;
 
-	device_worker() : files(NULL), s0(0), s1(0), device(0), types(0), thresh(0), filter(0), bps(1), flags(0), max_blocks(0), rc(0), abort(NULL), done(false) {}
+	device_worker() : files(NULL), s0(0), s1(0), device(0), types(0), thresh(0), filter(0), bps(1), flags(0), nslots(0), file_blocks(NULL), rc(0), abort(NULL), done(false) {}
 
 	void push(std::vector<tfrec_amd_event> &&ev)
 	{
@@ -183,17 +237,13 @@ struct device_worker {
 
 	int work()
 	{
-		const size_t n = s1 - s0;
-		std::vector<FILE *> fd(n, (FILE *)NULL);
-		for (size_t s = 0; s < n; s++) {
-			fd[s] = fopen((*files)[s0 + s].c_str(), "rb");
-			if (!fd[s]) {
-				perror((*files)[s0 + s].c_str());
-				for (size_t q = 0; q < s; q++)
-					fclose(fd[q]);
-				return TFREC_AMD_E_INVAL;
-			}
-		}
+		const size_t n = nslots;
+		// a file is opened when its first batch is read and closed after its last one (a queue of thousands of files)
+		std::vector<FILE *> fd(s1 - s0, (FILE *)NULL);
+		std::vector<size_t> fleft(s1 - s0);
+		for (size_t f = s0; f < s1; f++)
+			fleft[f - s0] = (*file_blocks)[f];
+		bool read_failed = false;
 		tfrec_amd_config cfg;
 		memset(&cfg, 0, sizeof(cfg));
 		cfg.n_streams = (int32_t)n;
@@ -209,12 +259,10 @@ struct device_worker {
 		int r = tfrec_amd_create(&cfg, &ctx);
 		if (r) {
 			fprintf(stderr, "tfrec_amd_create (device %d): %s (%s)\n", device, tfrec_amd_strerror(r), tfrec_amd_last_error());
-			for (size_t s = 0; s < n; s++)
-				fclose(fd[s]);
 			return r;
 		}
 		const size_t row = (size_t)bps * TFREC_AMD_BLOCK_BYTES;
-		const size_t n_batches = (max_blocks + bps - 1) / bps;
+		const size_t n_batches = plan.size();
 		const int depth = std::max(1, std::min(tfrec_amd_fifo_depth(), TFREC_AMD_FIFO_DEPTH));
 		constexpr int kBufs = TFREC_AMD_FIFO_DEPTH + 1;
 		uint8_t *host[kBufs];
@@ -235,13 +283,30 @@ struct device_worker {
 					std::unique_lock<std::mutex> lk(rmu);
 					rcv.wait(lk, [&]() { return k < drained + kBufs; });
 				}
-				const int nb = (int)std::min<size_t>(bps, max_blocks - k * bps);
+				const batch_plan &b = plan[k];
 				uint8_t *buf = host[k % kBufs];
 				for (size_t s = 0; s < n; s++) {
 					uint8_t *dst = buf + s * row;
-					const size_t want = (size_t)nb * TFREC_AMD_BLOCK_BYTES;
-					size_t got = fread(dst, 1, want, fd[s]);
-					got -= got % TFREC_AMD_BLOCK_BYTES;
+					const size_t want = (size_t)b.nb * TFREC_AMD_BLOCK_BYTES;
+					const int f = b.file[s];
+					size_t got = 0;
+					if (f >= 0) {
+						FILE *&fp = fd[f - s0];
+						if (!fp && !read_failed && !(fp = fopen((*files)[f].c_str(), "rb"))) {
+							perror((*files)[f].c_str());
+							read_failed = true;
+						}
+						if (fp) {
+							got = fread(dst, 1, want, fp);
+							got -= got % TFREC_AMD_BLOCK_BYTES;
+							size_t &left = fleft[f - s0];
+							left -= std::min<size_t>(left, (size_t)b.nb);
+							if (left == 0) {
+								fclose(fp);
+								fp = NULL;
+							}
+						}
+					}
 					memset(dst + got, 0x80, want - got);  // a shorter file is padded with silence (its events are cut by the engine)
 				}
 				{
@@ -256,8 +321,13 @@ struct device_worker {
 				std::unique_lock<std::mutex> lk(rmu);
 				rcv.wait(lk, [&]() { return filled > k; });
 			}
-			const int nb = (int)std::min<size_t>(bps, max_blocks - k * bps);
-			return tfrec_amd_submit_host(ctx, host[k % kBufs], row, nb);
+			const batch_plan &b = plan[k];
+			if (!b.reset.empty()) {  // the streams whose file ended in the batch before: fresh receivers for the next files
+				const int rr = tfrec_amd_reset_streams(ctx, b.reset.data(), (int)b.reset.size());
+				if (rr)
+					return rr;
+			}
+			return tfrec_amd_submit_host(ctx, host[k % kBufs], row, b.nb);
 		};
 		size_t queued = 0;
 		for (size_t k = 0; k < n_batches && r == 0; k++) {
@@ -283,9 +353,15 @@ struct device_worker {
 				drained = k + 1;  // batch k's host buffer may be refilled
 			}
 			rcv.notify_all();
-			ev.resize(nev);
+			// stream -> the index of the file it carried in this batch, within the whole job (none: silence, dropped)
+			const std::vector<int> &file = plan[k].file;
+			int kept = 0;
 			for (int q = 0; q < nev; q++)
-				ev[q].stream += (uint32_t)s0;  // index within the whole job
+				if (ev[q].stream < file.size() && file[ev[q].stream] >= 0) {
+					ev[kept] = ev[q];
+					ev[kept++].stream = (uint32_t)file[ev[q].stream];
+				}
+			ev.resize(kept);
 			push(std::move(ev));
 		}
 		if (r)
@@ -303,8 +379,11 @@ struct device_worker {
 			else
 				free(host[b]);
 		}
-		for (size_t s = 0; s < n; s++)
-			fclose(fd[s]);
+		for (FILE *fp : fd)
+			if (fp)
+				fclose(fp);
+		if (!r && read_failed)
+			r = TFREC_AMD_E_INVAL;
 		return r;
 	}
 };
@@ -317,7 +396,7 @@ struct device_worker {
 int gpu_engine::run()
 {
 	const size_t n = files.size();
-	size_t max_blocks = 0;
+	std::vector<size_t> file_blocks(n, 0);
 	stream_samples.assign(n, 0);
 	for (size_t s = 0; s < n; s++) {
 		FILE *f = fopen(files[s].c_str(), "rb");
@@ -329,9 +408,9 @@ int gpu_engine::run()
 		const size_t blocks = (size_t)ftell(f) / TFREC_AMD_BLOCK_BYTES;  // trailing partial block dropped, engine.cpp:72-76
 		fclose(f);
 		stream_samples[s] = (long long)blocks * TFREC_AMD_BLOCK_DEC;
-		max_blocks = std::max(max_blocks, blocks);
+		file_blocks[s] = blocks;
 	}
-	const size_t n_batches = (max_blocks + bps - 1) / bps;
+	size_t n_batches = 0;  // of the device with the most
 	const size_t nd = std::min(devices.size(), n);  // never more workers than streams
 	std::vector<device_worker> workers(nd);
 	for (size_t d = 0; d < nd; d++) {
@@ -346,7 +425,12 @@ int gpu_engine::run()
 		w.filter = filter;
 		w.bps = bps;
 		w.flags = bits_replay ? (TFREC_AMD_F_BITS | TFREC_AMD_F_ALL_FLUSHES) : 0u;
-		w.max_blocks = max_blocks;
+		w.nslots = w.s1 - w.s0;
+		if (slots > 0)
+			w.nslots = std::min(w.nslots, (size_t)slots);
+		w.file_blocks = &file_blocks;
+		w.plan = plan_batches(file_blocks, w.s0, w.s1, w.nslots, bps);
+		n_batches = std::max(n_batches, w.plan.size());
 	}
 	std::atomic<bool> abort(false);
 	for (size_t d = 0; d < nd; d++) {
@@ -357,6 +441,8 @@ int gpu_engine::run()
 	std::vector<tfrec_amd_event> ev;
 	for (size_t k = 0; k < n_batches && rc == 0; k++) {
 		for (size_t d = 0; d < nd && rc == 0; d++) {
+			if (k >= workers[d].plan.size())
+				continue;  // (this device's queue has run out)
 			if (!workers[d].pop(ev)) {
 				rc = workers[d].rc ? workers[d].rc : TFREC_AMD_E_STATE;
 				break;

@@ -97,6 +97,11 @@ public:
 	// inside the reference -- including what store_bit itself prints (tfa2.cpp:294-300 "Inverted SYNC").  Default off:
 	// the byte-level replay (store_bytes + flush) moves 64 bytes per window instead of every bit.
 	void set_bits_replay(bool on) { bits_replay = on; }
+	// -n: at most n streams per device context.  The dump files of a device go through them as a queue, in command-line order:
+	// when a file's last block has been submitted its stream is reset (tfrec_amd_reset_streams) and the next file starts
+	// there with the next batch.  0 (default): one stream per file for the whole job.  A batch that carries a reset does not
+	// overlap the batch before it on the GPU: a queue of mixed-length files runs at about half the throughput.
+	void set_slots(int n) { slots = n; }
 	// returns 0 on success, a TFREC_AMD_E_* code otherwise
 	int run();
 	// decoders of stream s in slot order (NULL for slots not registered)
@@ -115,6 +120,7 @@ private:
 	pipe_sink *psink;
 	int out_mode;
 	bool bits_replay;
+	int slots;
 };
 
 #endif

@@ -1,7 +1,7 @@
 // tfrec_amd/host/main.cpp -- tfrec_gpu: the reference's file-replay CLI on the GPU path.
 //
-//   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-q] [-D] [-B] [-d device[,device...]] [-b blocks] [-e handler | -E handler] [-m mode]
-//             -L dump.iq [-L more.iq ...]
+//   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-q] [-D] [-B] [-d device[,device...]] [-b blocks] [-n streams]
+//             [-e handler | -E handler] [-m mode] -L dump.iq [-L more.iq ...]
 //   tfrec_gpu [-T hexmask] -X telegrams.txt
 //
 // Flags keep the reference's meaning (main.cpp:63-88, 107-164): -T sensor type bit mask (hex), -t trigger
@@ -13,6 +13,8 @@
 // (gpu_engine.h), so that stdout also carries what store_bit prints ("Inverted SYNC", tfa2.cpp:294-300).
 // -E handler (not in the reference): the handler is started ONCE and receives the records of all
 // streams on stdin, "<stream> <id> <temp> <hum> <seq> <alarm> <rssi> <flags> <ts>" per line, one write per batch.
+// -n streams (not in the reference): at most this many streams per device; the -L files queue for them in order, and a
+// stream whose file has ended is reset and takes the next file (gpu_engine.h).  <stream> of -E is then the file's index.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -66,9 +68,10 @@ int main(int argc, char **argv)
 	std::vector<std::string> dumps;
 	const char *hexfile = NULL, *exec = NULL;
 	bool batched = false, bits = false;
-	int mode = 0;
+	int mode = 0, slots = 0;
+	bool have_slots = false;
 	int c;
-	while ((c = getopt(argc, argv, "T:t:WqDBd:b:L:X:e:E:m:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:WqDBd:b:n:L:X:e:E:m:h")) != -1) {
 		switch (c) {
 		case 'T': types = (int)strtol(optarg, NULL, 16); break;
 		case 't': thresh = atoi(optarg); break;
@@ -81,15 +84,21 @@ int main(int argc, char **argv)
 				devices.push_back(atoi(tok));
 			break;
 		case 'b': blocks = atoi(optarg); break;
+		case 'n': slots = atoi(optarg); have_slots = true; break;
 		case 'L': dumps.push_back(optarg); break;
 		case 'X': hexfile = optarg; break;
 		case 'e': exec = optarg; batched = false; break;
 		case 'E': exec = optarg; batched = true; break;
 		case 'm': mode = atoi(optarg); break;
 		default:
-			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-q] [-D] [-B] [-d dev] [-b blocks] -L dump [-L dump ...] | -X hexfile\n");
+			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] -L dump [-L dump ...] | -X hexfile\n"
+					"  -n streams  at most this many streams per device: the -L files queue for them in order\n");
 			return c == 'h' ? 0 : 1;
 		}
+	}
+	if (have_slots && slots < 1) {
+		fprintf(stderr, "tfrec_gpu: -n must be >= 1\n");
+		return 1;
 	}
 	setvbuf(stdout, NULL, _IOFBF, 1 << 16);
 	if (hexfile)
@@ -106,6 +115,7 @@ int main(int argc, char **argv)
 	if (exec || mode)
 		e.set_handler(exec, batched, mode);
 	e.set_bits_replay(bits);
+	e.set_slots(slots);
 	int rc = e.run();
 	fflush(stdout);
 	return rc ? 2 : 0;
