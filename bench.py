@@ -10,14 +10,20 @@ Workload (BASELINE.json configs[2], the configuration the "batched streams" metr
 fixed threshold -t 500, per GPU.  With N GPUs every rank gets its own 1024 streams (configs[3] at N=8:
 8192 streams, weak scaling, no collective on the data path -- streams are independent).
 
+A plain run does what its headline figure needs: it sets up, warms up, times the steps, writes --dump-outputs and prints
+the line.  `--full` adds everything else the benchmark measures or checks: the oracle parity gates before and after the
+timed region, the CPU baseline, the PCIe-inclusive leg and the other configurations.  Both runs submit the same batches in
+the same order (the gate's batch included), so their timed steps and dumped outputs are the same.
+
 Rank 0 prints ONE JSON line with the contract fields plus
   "roofline":     dominant kernel (longest live HIP-event span) vs the HBM roofline (algorithmic bytes = 2 B per complex input
                   sample), the whole path's fraction; from the builder's committed rocprofv3 runs of this command (named in the
                   block): that kernel's average in the kernel trace, HBM traffic, and "valu" = the batch's VALU instruction mix
                   against the measured issue cost per class ("state both numbers"),
-  "cpu_baseline": the reference CPU path timed on this box's host cores (1 thread) on a bounded sample,
-  "h2d_included": the same batches fed from page-locked HOST memory through the submit/drain FIFO (PCIe-inclusive rate;
-                  never `value`),
+  "cpu_baseline": (--full) the reference CPU path timed on this box's host cores (1 thread) on a bounded sample,
+  "h2d_included": (--full) the same batches fed from page-locked HOST memory through the submit/drain FIFO (PCIe-inclusive
+                  rate; never `value`),
+  "other_configs": (--full) short measurements of the other single-GPU configurations of BASELINE.json,
   "ms_min/ms_median/ms_max": per-step dispersion (time between consecutive drains inside the timed region);
   "ms_per_step_steady": the same without the steps in which the FIFO fills and drains.
   "host_ms":      the host's side of the timed region: every submit's duration, the longest gap between two drains, pauses of
@@ -32,11 +38,12 @@ Rank 0 prints ONE JSON line with the contract fields plus
 The steps ROTATE through config.distinct_batches (3) distinct synthetic batches of their own seeds -- A, B, C, A, ... -- so that
 no stream is given the same block twice in a row (engine.cpp:63-93) and every one of the library's four buffer sets holds
 every batch in turn.
-Parity gates: BEFORE the timed region, on fresh state, EVERY stream of the batch at N=1 (128 spread over the batch per
+Parity gates (--full): BEFORE the timed region, on fresh state, EVERY stream of the batch at N=1 (128 spread over the batch per
 rank at N>1) against the CPU oracle; AFTER it one more batch through the same context (carried decoder / biquad / slicer
 state, FIFO four deep) with 64-256 streams against the oracle run over the TRUE concatenation of all batches the context has
-seen, in their order (config.parity_after_timed*); and the discriminator's self-check counters (config.atan_*: samples decided by the
-exact slow path / differing from this host's libm).  A mismatch in any of them fails the run.
+seen, in their order (config.parity_after_timed*).  In every run: the discriminator's self-check counters (config.atan_*:
+samples decided by the exact slow path / differing from this host's libm; the library compares them at every drain).  A
+mismatch in any of them fails the run.
 """
 from __future__ import annotations
 
@@ -226,20 +233,20 @@ def main():
     ap.add_argument("--unique", type=int, default=0,
                     help="distinct synthetic streams to generate per GPU, tiled over the batch (0 = every stream distinct)")
     ap.add_argument("--cpu-budget", type=float, default=12.0,
-                    help="upper bound in seconds for each single-thread leg of the CPU baseline (0 = skip)")
+                    help="--full: upper bound in seconds for each single-thread leg of the CPU baseline (0 = skip)")
     ap.add_argument("--parity-streams", type=int, default=-1,
-                    help="streams of the first batch checked against the CPU oracle: -1 = all at N=1, 128 spread over the "
-                         "batch per rank at N>1; 0 = none")
+                    help="--full: streams of the first batch checked against the CPU oracle: -1 = all at N=1, 128 spread over "
+                         "the batch per rank at N>1; 0 = none.  Unless 0, every run submits that batch before the warm-up")
     ap.add_argument("--parity-after-streams", type=int, default=0,
-                    help="streams of the batch AFTER the timed region checked against the oracle continued over all "
+                    help="--full: streams of the batch AFTER the timed region checked against the oracle continued over all "
                          "repetitions of the input (0 = 256 on runs of up to 32 batches, down to 64 on long ones; a quarter of "
                          "it per rank at N>1; needs --parity-streams != 0)")
     ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl",
                     help="backend of the barrier / scalar reduces at N>1 (the data path has no collective)")
     ap.add_argument("--same-device", action="store_true", help="tests: every rank uses cuda:0")
-    ap.add_argument("--h2d-steps", type=int, default=4, help="batches of the PCIe-inclusive leg (0 = skip; N=1 only)")
+    ap.add_argument("--h2d-steps", type=int, default=4, help="--full: batches of the PCIe-inclusive leg (0 = skip; N=1 only)")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the short secondary measurements of BASELINE configs[1] and configs[4] (N=1 only)")
+                    help="--full: skip the short secondary measurements of the other BASELINE configs (N=1 only)")
     ap.add_argument("--depth", type=int, default=4, help="batches kept in the submit/drain FIFO (1..4)")
     ap.add_argument("--bg-traffic-gb", type=float, default=0.0,
                     help="EXPERIMENT (what binds?): beside every batch, a device-to-device copy of this many GB of HBM traffic (half read, "
@@ -257,6 +264,9 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the flush events the last timed step drained (rank 0) to DIR/events_<field>.npy "
                          "(float64; rdata float32), at most 64 MB in all: the outputs of two builds can be compared file by file")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the parity gates against the CPU oracle before and "
+                         "after the timed region, the CPU baseline, the PCIe-inclusive leg and the other configurations")
     a = ap.parse_args()
     if a.steps < 1:
         sys.exit("bench.py: --steps must be >= 1")
@@ -340,13 +350,15 @@ def main():
     r = api.Receiver(n_streams, a.types, a.thresh, 0, device=dev_index, max_blocks=n_blocks, timing=True,
                      max_events=max(4096, n_streams * 256), input_10x=a.input_10x, experiments=a.experiments)
 
-    # ---- parity gate (fresh context state): GPU events of the first batch == oracle events, stream by stream
+    # ---- parity gate (fresh context state): GPU events of the first batch == oracle events, stream by stream.  A plain run
+    # submits and drains the same batch without the comparison: the warm-up and the timed steps start from the same state
     parity_ok = None
     parity_n = 0
     if a.parity_streams != 0:
-        from oracle import oracle as O
         r.submit(next_batch())  # batch 0 of the rotation = hosts[0]
         first = r.drain()
+    if a.parity_streams != 0 and a.full:
+        from oracle import oracle as O
         want_n = a.parity_streams if a.parity_streams > 0 else (n_streams if world == 1 else 128)
         want_n = min(want_n, n_streams)
         # spread over the batch: first, middle, last (stream s of the batch is distinct stream s % unique)
@@ -457,7 +469,7 @@ def main():
     # whb.cpp:616-623 carry state from block to block exactly like this
     parity_after = None
     parity_after_n = 0
-    if a.parity_streams != 0 and rate == 1:
+    if a.full and a.parity_streams != 0 and rate == 1:
         from oracle import oracle as O
         reps_before = seq[0]  # gate + warm-up + timed steps
         assert reps_before == (1 if parity_ok is not None else 0) + a.warmup + a.steps
@@ -503,7 +515,7 @@ def main():
     mem_tables = r.memory()  # before the PCIe leg: tfrec_amd_submit_host grows one input staging buffer per FIFO set on demand
     # ---- PCIe-inclusive leg: the same batch from page-locked host memory through the FIFO (never `value`)
     h2d = None
-    if a.h2d_steps > 0 and world == 1:
+    if a.full and a.h2d_steps > 0 and world == 1:
         try:
             import ctypes as C
             L = r.L
@@ -532,7 +544,7 @@ def main():
     # ---- secondary, short measurements of the other single-GPU configurations of BASELINE.json (never `value`): same
     # method (input resident in HBM, FIFO of depth 4, parity gate on fresh state against the oracle)
     extra = {}
-    if world == 1 and not a.no_extra_configs and not a.input_10x and (n_streams, n_blocks, a.types) == (1024, 48, 0x2F):
+    if a.full and world == 1 and not a.no_extra_configs and not a.input_10x and (n_streams, n_blocks, a.types) == (1024, 48, 0x2F):
         from oracle import oracle as O
 
         def side(name, xs, xb, xt, x10, steps, xthresh=None, gen=None, cpu_ref=False, want_kernels=()):
@@ -836,7 +848,7 @@ def main():
                 "context_memory": dict(mem_tables, device_bytes_with_host_staging=r.memory()["device_bytes"]),
             },
         }
-        if a.cpu_budget > 0 and world == 1 and rate == 1:
+        if a.full and a.cpu_budget > 0 and world == 1 and rate == 1:
             out["cpu_baseline"] = cpu_baseline(host[: min(unique, 256)], a.types, a.thresh, a.cpu_budget)
         if h2d is not None:
             out["h2d_included"] = h2d

@@ -8,7 +8,7 @@ cd $R
 rounds=${1:-3}
 shift
 run() {  # $1 = label, $2 = env assignments, $3 = steps
-	env $2 python bench.py --cpu-budget 0 --h2d-steps 0 --parity-streams 8 --steps $3 --warmup 5 --no-extra-configs 2>/dev/null | python -c "
+	env $2 python bench.py --full --cpu-budget 0 --h2d-steps 0 --parity-streams 8 --steps $3 --warmup 5 --no-extra-configs 2>/dev/null | python -c "
 import sys, json
 j = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = j['roofline']['kernels_ms']

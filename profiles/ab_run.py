@@ -22,7 +22,7 @@ for a in sys.argv[5:]:
            else os.path.join(R, "tfrec_amd", "ab", parts[0] + ".so"))
     env = dict(p.split("=", 1) for p in parts[1:])
     specs.append((label, lib, env))
-extra = os.environ.get("AB_BENCH_ARGS", "--cpu-budget 0 --h2d-steps 0 --parity-streams 8 --no-extra-configs").split()
+extra = os.environ.get("AB_BENCH_ARGS", "--full --cpu-budget 0 --h2d-steps 0 --parity-streams 8 --no-extra-configs").split()
 with open(out_path, "a") as fo:
     for r in range(rounds):
         for label, lib, env in specs:

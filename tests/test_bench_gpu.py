@@ -30,8 +30,8 @@ COMMON = ["--steps", "3", "--warmup", "1", "--streams", "64", "--blocks", "8", "
 
 
 def test_bench_single_rank_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + COMMON + ["--h2d-steps", "2"], capture_output=True,
-                         text=True, timeout=600, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + COMMON + ["--h2d-steps", "2"],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     j = _line(out.stdout)
     assert j["n_gpus"] == 1 and j["value"] > 0 and j["unit"] == "MSamples/s"
@@ -57,8 +57,8 @@ def test_bench_two_ranks_gloo_on_one_device():
     for r in range(2):
         env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-                                       "--same-device"] + COMMON, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                                      text=True, cwd=ROOT))
+                                       "--same-device", "--full"] + COMMON, env=env, stdout=subprocess.PIPE,
+                                      stderr=subprocess.PIPE, text=True, cwd=ROOT))
     outs = [p.communicate(timeout=900) for p in procs]
     assert all(p.returncode == 0 for p in procs), [o[1][-1500:] for o in outs]
     assert not [ln for ln in outs[1][0].splitlines() if ln.startswith('{"metric"')]  # only rank 0 prints
@@ -78,7 +78,7 @@ def test_bench_gpus_2_launches_its_own_ranks():
     print n_gpus 1)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--same-device", "--dist-backend",
-                          "gloo"] + COMMON, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "gloo", "--full"] + COMMON, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     j = _line(out.stdout)
     assert j["n_gpus"] == 2 and j["config"]["parity_ok"] is True
@@ -93,7 +93,7 @@ def test_bench_gpus_4_same_device():
     No scaling figure is taken from this."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--same-device", "--dist-backend",
-                          "gloo"] + COMMON, capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
+                          "gloo", "--full"] + COMMON, capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     j = _line(out.stdout)
     assert j["n_gpus"] == 4 and j["scaling"] == "weak" and j["value"] > 0
@@ -127,3 +127,30 @@ def test_bench_dump_outputs_are_the_same_run_to_run(tmp_path):
     assert dumps[0].keys() == dumps[1].keys()
     for f in dumps[0]:
         assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
+def test_bench_plain_run_leaves_the_checks_to_full_and_dumps_the_same(tmp_path):
+    """A plain run times the steps and prints the line without the oracle gates, the CPU baseline or the PCIe leg; it still
+    submits the gate's batch first, so the timed steps see the same state as under --full and write the same outputs."""
+    lines, dumps = {}, {}
+    for mode in ("plain", "full"):
+        d = tmp_path / mode
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", str(d), "--h2d-steps", "2",
+                              "--steps", "3", "--warmup", "1", "--streams", "64", "--blocks", "8", "--cpu-budget", "1"]
+                             + (["--full"] if mode == "full" else []), capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines[mode] = _line(out.stdout)
+        dumps[mode] = {f: np.load(d / f) for f in sorted(os.listdir(d))}
+    p, f = lines["plain"], lines["full"]
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert p[k] == f[k], k
+    assert p["value"] > 0 and p["ms_per_step"] > 0 and len(p["step_ms"]) == 3
+    assert p["config"]["parity_ok"] is None and p["config"]["parity_after_timed"] is None
+    assert p["config"]["atan_host_mismatch"] == 0
+    assert not {"cpu_baseline", "h2d_included", "other_configs"} & p.keys()
+    assert f["config"]["parity_ok"] is True and f["config"]["parity_after_timed"] is True
+    assert {"cpu_baseline", "h2d_included"} <= f.keys()
+    assert p["config"]["events_per_step"] == f["config"]["events_per_step"]
+    assert p["dump_outputs"]["events"] > 0 and dumps["plain"].keys() == dumps["full"].keys()
+    for name in dumps["plain"]:
+        assert np.array_equal(dumps["plain"][name], dumps["full"][name]), name

@@ -578,7 +578,7 @@ def test_config1_single_stream_tfa123_48_blocks():
 
 def test_quarter_of_config2_every_stream_against_the_oracle():
     """256 streams x 48 blocks x all five protocols (a quarter of BASELINE configs[2]; bench.py's gate checks all 1024 on
-    every run): EVERY stream's complete flush log against the oracle, two submits (24 + 24 blocks) in flight."""
+    every --full run): EVERY stream's complete flush log against the oracle, two submits (24 + 24 blocks) in flight."""
     n_streams, n_blocks = 256, 48
     iq = synth.gen_batch(1000, 0, n_streams, n_blocks)
     with api.Receiver(n_streams, 0x2F, 500, 0, max_blocks=24, all_flushes=True, max_events=n_streams * 24 * 40) as r:
