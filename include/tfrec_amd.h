@@ -158,8 +158,9 @@ void tfrec_amd_host_free(void *p);
  *     drained unchanged (old seq, old end_sample).  Calls made before one submit accumulate; duplicate indices are allowed;
  *     n == 0 is a no-op.
  *   - From the next submit on, a reset stream's events are exactly those of a fresh receiver (tfrec_amd_create with the
- *     context's types_mask, thresh, filter_type and flags) fed only the input that follows: seq restarts at 0 per slot and
- *     end_sample counts from the first sample after the reset.
+ *     stream's own current types_mask, thresh and filter_type -- the context's, unless tfrec_amd_configure_streams changed
+ *     them -- and the context's flags) fed only the input that follows: seq restarts at 0 per slot and end_sample counts
+ *     from the first sample after the reset.
  *   - A trigger window open at the reset point is dropped without a flush, as the reference drops it at the end of a dump
  *     (the process exits, engine.cpp:72-76): the events before the reset are those of a fresh receiver run on the old
  *     input truncated at the cut.
@@ -173,6 +174,29 @@ void tfrec_amd_host_free(void *p);
  * Errors: an index outside [0, n_streams), n < 0, or streams == NULL with n > 0: TFREC_AMD_E_INVAL, and nothing is
  * marked.  A poisoned context: TFREC_AMD_E_STATE. */
 int tfrec_amd_reset_streams(tfrec_amd_ctx *ctx, const int32_t *streams, int n);
+
+/* Settings of one stream: what -T, -t and -W are to one tfrec process of the reference. */
+typedef struct {
+	int32_t types_mask;  /* demodulators of this stream: a non-empty subset of the context's types_mask */
+	int32_t thresh;      /* trigger threshold >= 0; 0 = the reference's auto mode, starting at 500 */
+	int32_t filter_type; /* 0 narrow, 1 wide (-W) */
+	int32_t reserved;    /* must be 0 */
+} tfrec_amd_stream_config;
+
+/* Give streams[i] the settings cfgs[i] (i < n), as a fresh receiver from the NEXT submit on.  The context's types_mask is the
+ * set of demodulators it builds; its thresh and filter_type are every stream's initial settings.
+ *   - The restart is exactly that of tfrec_amd_reset_streams (the same cut, the dropped open window, seq and end_sample
+ *     restarting, other streams untouched), but the stream comes back with its new settings.  A later reset keeps them.
+ *   - Before the first submit this only sets the settings.  Duplicate indices are allowed: the last one wins.  A reset and a
+ *     configure of one stream before one submit are one restart, with the latest settings.  n == 0 is a no-op.
+ *   - Flags stay context-wide (TFREC_AMD_F_BITS, _ALL_FLUSHES, _INPUT_10X, _SERIAL_CHAINS, _TIMING).
+ *   - A context in which no stream was ever configured runs exactly as before.  Cost: that of a reset.
+ * Errors: an index outside [0, n_streams), n < 0, streams or cfgs NULL with n > 0, a types_mask that is empty or names a
+ * demodulator outside the context's types_mask, thresh < 0, filter_type not 0 or 1, reserved != 0: TFREC_AMD_E_INVAL, and
+ * nothing is marked.  A poisoned context: TFREC_AMD_E_STATE. */
+int tfrec_amd_configure_streams(tfrec_amd_ctx *ctx, const int32_t *streams, const tfrec_amd_stream_config *cfgs, int n);
+/* The settings the next submit will use for one stream. */
+int tfrec_amd_get_stream_config(tfrec_amd_ctx *ctx, int stream, tfrec_amd_stream_config *out);
 
 /* Wait for submitted work. */
 int tfrec_amd_sync(tfrec_amd_ctx *ctx);
@@ -262,7 +286,8 @@ int tfrec_amd_get_layout(tfrec_amd_ctx *ctx, int *n_streams);
  * submit that may be in flight) and the page-locked host memory of its drain buffers, in bytes.  The caller's input
  * batches are not counted.  No reference counterpart. */
 int tfrec_amd_get_memory(tfrec_amd_ctx *ctx, uint64_t *device_bytes, uint64_t *pinned_host_bytes);
-/* Current trigger threshold of one stream (auto mode, fm_demod.cpp:58-73, moves it; fixed mode returns cfg.thresh). */
+/* Current trigger threshold of one stream (auto mode, fm_demod.cpp:58-73, moves it; a fixed stream returns its own thresh).
+ * Per stream: the settings the last submit ran with (tfrec_amd_configure_streams takes effect with the next submit). */
 int tfrec_amd_read_thresh(tfrec_amd_ctx *ctx, int stream, int *thresh);
 
 #ifdef __cplusplus

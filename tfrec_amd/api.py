@@ -63,6 +63,11 @@ class Stats(C.Structure):
                 ("tfa1_vector_groups", C.c_uint64), ("tfa2_vector_groups", C.c_uint64)]
 
 
+class StreamConfig(C.Structure):
+    """tfrec_amd_stream_config: one stream's -T, -t and -W (tfrec_amd_configure_streams)."""
+    _fields_ = [("types_mask", C.c_int32), ("thresh", C.c_int32), ("filter_type", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FmStats(C.Structure):
     _fields_ = [("resolved", C.c_uint64), ("host_verified", C.c_uint64), ("host_mismatch", C.c_uint64),
                 ("undecidable", C.c_uint64), ("reserved", C.c_uint64 * 4)]
@@ -91,6 +96,7 @@ EXPORTS = (
     "tfrec_amd_get_timings", "tfrec_amd_read_thresh", "tfrec_amd_get_stats", "tfrec_amd_get_layout", "tfrec_amd_host_alloc",
     "tfrec_amd_host_free", "tfrec_amd_read_stage0", "tfrec_amd_get_fm_stats", "tfrec_amd_fm_dev_probe",
     "tfrec_amd_fifo_depth", "tfrec_amd_get_memory", "tfrec_amd_iir_probe", "tfrec_amd_reset_streams",
+    "tfrec_amd_configure_streams", "tfrec_amd_get_stream_config",
 )
 
 _libs = {}
@@ -149,6 +155,8 @@ def load_library(build: bool = True, experiments: bool = False):
     L.tfrec_amd_fm_dev_probe.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(FmStats)]
     L.tfrec_amd_iir_probe.argtypes = [C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
     L.tfrec_amd_reset_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.tfrec_amd_configure_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.tfrec_amd_get_stream_config.argtypes = [C.c_void_p, C.c_int, C.POINTER(StreamConfig)]
     L.tfrec_amd_fifo_depth.restype = C.c_int
     if L.tfrec_amd_fifo_depth() != FIFO_DEPTH:
         raise RuntimeError("libtfrec_amd.so was built with FIFO depth %d, this binding expects %d" % (
@@ -240,6 +248,40 @@ class Receiver:
             raise TfrecAmdError(E_INVAL, "stream index outside [0, %d)" % self.n_streams)
         a = np.ascontiguousarray(idx, dtype=np.int32)
         _check(self.L, self.L.tfrec_amd_reset_streams(self.h, a.ctypes.data if len(a) else None, len(a)))
+
+    def configure_streams(self, streams, types_mask=None, thresh=None, filter_type=None):
+        """Give the listed streams their own settings (tfrec_amd_configure_streams): each of types_mask, thresh and filter_type
+        is one value for all of them or one per listed stream; None keeps each stream's current value.  The streams restart
+        as fresh receivers with these settings at the next submit, exactly as after reset_streams."""
+        idx = [int(s) for s in streams]
+        if any(s < 0 or s >= self.n_streams for s in idx):  # (refused before int32 could wrap an index into range)
+            raise TfrecAmdError(E_INVAL, "stream index outside [0, %d)" % self.n_streams)
+
+        def per_stream(v):
+            if v is None or np.ndim(v) == 0:
+                return [v] * len(idx)
+            v = list(v)
+            if len(v) != len(idx):
+                raise ValueError("%d values for %d streams" % (len(v), len(idx)))
+            return v
+
+        cur = {}
+        cfgs = (StreamConfig * max(1, len(idx)))()
+        for i, (s, t, th, w) in enumerate(zip(idx, per_stream(types_mask), per_stream(thresh), per_stream(filter_type))):
+            c = cur[s] if s in cur else self.stream_config(s)  # (a duplicate index builds on the value before it)
+            c = {"types_mask": c["types_mask"] if t is None else int(t), "thresh": c["thresh"] if th is None else int(th),
+                 "filter_type": c["filter_type"] if w is None else int(w)}
+            cur[s] = c
+            cfgs[i] = StreamConfig(c["types_mask"], c["thresh"], c["filter_type"], 0)
+        a = np.ascontiguousarray(idx, dtype=np.int32)
+        _check(self.L, self.L.tfrec_amd_configure_streams(self.h, a.ctypes.data if len(a) else None,
+                                                          C.cast(cfgs, C.c_void_p) if len(a) else None, len(a)))
+
+    def stream_config(self, stream: int) -> dict:
+        """The settings the next submit uses for one stream (tfrec_amd_get_stream_config)."""
+        c = StreamConfig()
+        _check(self.L, self.L.tfrec_amd_get_stream_config(self.h, int(stream), C.byref(c)))
+        return {"types_mask": c.types_mask, "thresh": c.thresh, "filter_type": c.filter_type}
 
     def drain(self, allow_overflow: bool = False) -> np.ndarray:
         out = np.empty(self.max_events, dtype=EVENT_DTYPE)

@@ -16,7 +16,7 @@ hipError_t launch_decim10(hipStream_t st, const uint8_t *iq, size_t stride, int 
 			  const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride);
 hipError_t launch_frontend(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks,
 			   const uint8_t *tail_in, uint8_t *tail_out, uint32_t *dec, size_t dec_stride,
-			   unsigned long long *mask, size_t mask_stride, uint32_t *prevdec, int thresh, const FrontTaps &taps,
+			   unsigned long long *mask, size_t mask_stride, uint32_t *prevdec, int thresh, const FrontTapsCfg &taps,
 			   bool in16);
 hipError_t launch_fmdev(hipStream_t st, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask,
 			size_t mask_stride, const uint32_t *prevdec, int16_t *fmdev, size_t fmdev_stride, EventBuf *eb,
@@ -28,7 +28,7 @@ hipError_t launch_pipeline(const PipeCtl &P, const uint32_t *dec, size_t dec_str
 hipError_t launch_fm_probe(hipStream_t st, const int32_t *quads, size_t n, int32_t *out, EventBuf *eb, int kind);
 hipError_t launch_iir_probe(hipStream_t st, const double *in, size_t n, const BiquadCoef &c, double *out, int form);
 hipError_t launch_threshold(hipStream_t st, const uint32_t *dec, size_t dec_stride, unsigned long long *mask,
-			    size_t mask_stride, int n_streams, int n_blocks, FskState *fsk, int wmax);
+			    size_t mask_stride, int n_streams, int n_blocks, FskState *fsk, int wmax, const StreamCfg *scfg);
 hipError_t launch_chains(hipStream_t st, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask,
 			 size_t mask_stride, int n_streams, int n_blocks, long long sample_base, const ChainLaunch &L,
 			 tfrec_amd_event *events, EventBuf *eb, uint32_t flags);
@@ -66,7 +66,9 @@ struct FmTotals {
 struct tfrec_amd_ctx {
 	tfrec_amd_config cfg;
 	ChainLaunch launch;
-	FrontTaps taps;
+	// stage-2 taps of the front end: the context's (f2, scfg == nullptr) until a stream is configured, then narrow (f2) and
+	// wide (w) with scfg = d_scfg
+	FrontTapsCfg taps;
 	// front-end outputs, one set per submit in flight like the event buffers: the front end of submit k+2 (its own stream)
 	// runs beside the demodulator chains of submit k
 	uint32_t *d_dec[kSets] = {};
@@ -112,8 +114,18 @@ struct tfrec_amd_ctx {
 	int submit_seq = 0;
 	hipStream_t vx = nullptr;                    // the WHB check: an alias of cp (deep layout) or of aux
 	hipEvent_t ev_aux[kSets] = {};               // whb_demod_kernel of the set's submit done
-	FskState *d_fsk = nullptr;  // auto-threshold mode only
+	FskState *d_fsk = nullptr;  // auto threshold (every context has it: a stream can be configured to auto)
 	int wmax = 0;
+	// tfrec_amd_configure_streams: every stream's settings as the next submit uses them (scfg, the host's copy), their device
+	// copy as the last submit used them (d_scfg: written only by stream_reset_kernel, in the entries of its list), and the
+	// settings that travel with a submit's reset list (d_rcfg / h_rcfg).  per_stream: a stream was configured -- from then on
+	// the kernels read d_scfg (launch.scfg, taps.scfg); before, the uniform kernels run.  n_auto: streams of scfg in auto mode.
+	std::vector<StreamCfg> scfg;
+	std::vector<tfrec_amd_stream_config> scfg_api;
+	StreamCfg *d_scfg = nullptr;
+	StreamCfg *d_rcfg[kSets] = {}, *h_rcfg[kSets] = {};
+	bool per_stream = false;
+	int n_auto = 0;
 	uint8_t *d_tail[kSets] = {};
 	int tail_sel = 0;
 	// TFREC_AMD_F_INPUT_10X: output of the 10:1 stage (1.536 MS/s int16 pairs, one buffer per set) and its raw history
@@ -199,7 +211,9 @@ struct StreamReset {
 	uint8_t *tail;      // front-end FIR history the NEXT front end reads: tail_bytes per stream, filled with tail_fill
 	int32_t tail_bytes, tail_fill;
 	uint8_t *tail10;    // TFREC_AMD_F_INPUT_10X: the 10:1 stage's raw history (112 bytes per stream of 0x80), or nullptr
-	FskState *fsk;      // auto threshold, or nullptr
+	FskState *fsk;      // auto threshold
+	const StreamCfg *cfgs;  // [n_list] the listed streams' settings from this submit on ...
+	StreamCfg *scfg;        // ... written over their entries here
 	int32_t n_active;
 	ChainState *states[kNSlots];
 	const ChainState *chain_init;
@@ -231,8 +245,10 @@ __global__ __launch_bounds__(64) void stream_reset_kernel(StreamReset R)
 		for (int i = ln; i < kChunks; i += 64)
 			reinterpret_cast<uint4 *>(&R.whbX[s])[i] = init[i];
 	if (ln == 0) {
-		if (R.fsk)
-			R.fsk[s] = FskState{ 500, 0, 0, -(1 << 28) };  // fm_demod.cpp:23-27, as tfrec_amd_create
+		// In place: every kernel of the submits before this one that reads scfg has ended (launch_resets)
+		const StreamCfg sc = R.cfgs[blockIdx.x];
+		R.scfg[s] = sc;
+		R.fsk[s] = FskState{ sc.thresh, 0, 0, -(1 << 28) };  // auto: 500, fm_demod.cpp:23-27, as tfrec_amd_create
 		if (R.tcarry)
 			for (int a = 0; a < R.n_active; a++)
 				R.tcarry[(size_t)a * R.n_streams + s] = 0;
@@ -426,10 +442,14 @@ int tfrec_amd_destroy(tfrec_amd_ctx *c)
 	}
 	(void)hipFree(c->d_eb_fresh);
 	(void)hipFree(c->d_chain_init);
+	(void)hipFree(c->d_scfg);
 	for (int k = 0; k < kSets; k++) {
 		(void)hipFree(c->d_reset[k]);
+		(void)hipFree(c->d_rcfg[k]);
 		if (c->h_reset[k])
 			(void)hipHostFree(c->h_reset[k]);
+		if (c->h_rcfg[k])
+			(void)hipHostFree(c->h_rcfg[k]);
 	}
 	for (int k = 0; k < kSets; k++) {
 		if (c->h_evblock[k])
@@ -445,6 +465,29 @@ int tfrec_amd_destroy(tfrec_amd_ctx *c)
 		(void)hipStreamDestroy(c->t1);
 	delete c;
 	return TFREC_AMD_OK;
+}
+
+// A stream's settings as the kernels read them: the active slots (launch order) of its types, its threshold (auto: 500, where
+// its FskState starts), its longest window, its taps
+// second-stage taps: dsp_stuff.cpp:61-88 (narrow) / :91-117 (wide, -W)
+static const int16_t kNarrowTaps[20] = { -1087, -1082, -1065, -451, 912, 2997, 5556, 8157, 10285, 11484,
+					 11484, 10285, 8157, 5556, 2997, 912, -451, -1065, -1082, -1087 };
+static const int16_t kWideTaps[20] = { 546, 451, -317, -1844, -3198, -2817, 494, 6469, 13074, 17421,
+				       17421, 13074, 6469, 494, -2817, -3198, -1844, -317, 451, 546 };
+
+static StreamCfg device_cfg(const tfrec_amd_ctx *c, const tfrec_amd_stream_config &sc)
+{
+	StreamCfg d;
+	memset(&d, 0, sizeof(d));
+	for (int a = 0; a < c->launch.n_active; a++)
+		if (sc.types_mask & (1 << c->launch.params[a].sensor_type)) {
+			d.amask |= 1u << a;
+			d.wmax = std::max(d.wmax, (int32_t)c->launch.params[a].window);
+		}
+	d.thresh = sc.thresh ? sc.thresh : 500;
+	d.autoth = sc.thresh == 0;
+	d.wide = (uint16_t)sc.filter_type;
+	return d;
 }
 
 int tfrec_amd_create(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
@@ -482,13 +525,12 @@ int tfrec_amd_create(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
 	memset(&c->launch, 0, sizeof(c->launch));
 	memset(&c->win, 0, sizeof(c->win));
 
-	// second-stage taps: dsp_stuff.cpp:61-88 (narrow) / :91-117 (wide, -W), as h / 65536
-	static const int16_t narrow[20] = { -1087, -1082, -1065, -451, 912, 2997, 5556, 8157, 10285, 11484,
-					    11484, 10285, 8157, 5556, 2997, 912, -451, -1065, -1082, -1087 };
-	static const int16_t wide[20] = { 546, 451, -317, -1844, -3198, -2817, 494, 6469, 13074, 17421,
-					  17421, 13074, 6469, 494, -2817, -3198, -1844, -317, 451, 546 };
-	for (int n = 0; n < 20; n++)
-		c->taps.f2[n][0] = c->taps.f2[n][1] = (float)(cfg->filter_type ? wide[n] : narrow[n]) / 65536.0f;
+	// second-stage taps (kNarrowTaps / kWideTaps), as h / 65536
+	for (int n = 0; n < 20; n++) {
+		c->taps.f2[n][0] = c->taps.f2[n][1] = (float)(cfg->filter_type ? kWideTaps[n] : kNarrowTaps[n]) / 65536.0f;
+		c->taps.w[n][0] = c->taps.w[n][1] = (float)kWideTaps[n] / 65536.0f;
+	}
+	c->taps.scfg = nullptr;
 
 	// registration order, types and samples-per-bit of main.cpp:173-218
 	static const struct {
@@ -574,13 +616,18 @@ int tfrec_amd_create(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
 	}
 	for (int a = 0; a < c->launch.n_active; a++)
 		c->wmax = std::max(c->wmax, (int)c->launch.params[a].window);
-	if (cfg->thresh == 0) {  // fm_demod.cpp:23-27: 0 selects the adaptive mode starting at 500
-		ALLOC(c->d_fsk, n * sizeof(FskState));
-		if (rc == TFREC_AMD_OK) {
-			std::vector<FskState> init(n, FskState{ 500, 0, 0, -(1 << 28) });
-			if (hipMemcpy(c->d_fsk, init.data(), n * sizeof(FskState), hipMemcpyHostToDevice) != hipSuccess)
-				rc = TFREC_AMD_E_HIP;
-		}
+	// fm_demod.cpp:23-27: thresh 0 selects the adaptive mode starting at 500.  Every stream starts with the context's settings.
+	ALLOC(c->d_fsk, n * sizeof(FskState));
+	ALLOC(c->d_scfg, n * sizeof(StreamCfg));
+	if (rc == TFREC_AMD_OK) {
+		const tfrec_amd_stream_config sc0 = { cfg->types_mask, cfg->thresh, cfg->filter_type, 0 };
+		c->scfg_api.assign(n, sc0);
+		c->scfg.assign(n, device_cfg(c, sc0));
+		c->n_auto = cfg->thresh == 0 ? (int)n : 0;
+		std::vector<FskState> init(n, FskState{ c->scfg[0].thresh, 0, 0, -(1 << 28) });
+		if (hipMemcpy(c->d_fsk, init.data(), n * sizeof(FskState), hipMemcpyHostToDevice) != hipSuccess ||
+		    hipMemcpy(c->d_scfg, c->scfg.data(), n * sizeof(StreamCfg), hipMemcpyHostToDevice) != hipSuccess)
+			rc = TFREC_AMD_E_HIP;
 	}
 	for (int k = 0; k < kSets; k++) {
 		ALLOC(c->d_fmdev[k], n * m_max * sizeof(int16_t) + 256);  // + slack: K3 reads whole dwords past an odd tail
@@ -753,8 +800,10 @@ int tfrec_amd_create(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
 	ALLOC(c->d_eb_fresh, kEvFreshBytes);
 	// tfrec_amd_reset_streams: a list of at most n_streams indices per set, and the constructor state it restores
 	ALLOC(c->d_chain_init, sizeof(ChainState));
-	for (int k = 0; k < kSets; k++)
+	for (int k = 0; k < kSets; k++) {
 		ALLOC(c->d_reset[k], n * sizeof(int32_t));
+		ALLOC(c->d_rcfg[k], n * sizeof(StreamCfg));
+	}
 	if (rc == TFREC_AMD_OK) {
 		ChainState init;
 		memset(&init, 0, sizeof(init));
@@ -775,11 +824,12 @@ int tfrec_amd_create(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
 		c->pinned_bytes += kEvHeader + (size_t)cfg->max_events * sizeof(tfrec_amd_event);
 		c->h_eb[k] = (EventBuf *)c->h_evblock[k];
 		c->h_events[k] = (tfrec_amd_event *)(c->h_evblock[k] + kEvHeader);
-		if (hipHostMalloc((void **)&c->h_reset[k], n * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
+		if (hipHostMalloc((void **)&c->h_reset[k], n * sizeof(int32_t), hipHostMallocDefault) != hipSuccess ||
+		    hipHostMalloc((void **)&c->h_rcfg[k], n * sizeof(StreamCfg), hipHostMallocDefault) != hipSuccess) {
 			rc = TFREC_AMD_E_NOMEM;
 			break;
 		}
-		c->pinned_bytes += n * sizeof(int32_t);
+		c->pinned_bytes += n * (sizeof(int32_t) + sizeof(StreamCfg));
 	}
 	if (rc == TFREC_AMD_OK) {
 		c->reset_marked.assign(n, 0);
@@ -903,7 +953,10 @@ static int launch_resets(tfrec_amd_ctx *c, int set)
 			HIPCHK(hipStreamWaitEvent(fs, e, 0));
 	const int nl = (int)c->reset_pending.size();
 	memcpy(c->h_reset[set], c->reset_pending.data(), (size_t)nl * sizeof(int32_t));  // (the set's last copy was drained)
+	for (int i = 0; i < nl; i++)  // a reset stream restarts with its own current settings
+		c->h_rcfg[set][i] = c->scfg[c->reset_pending[i]];
 	HIPCHK(hipMemcpyAsync(c->d_reset[set], c->h_reset[set], (size_t)nl * sizeof(int32_t), hipMemcpyHostToDevice, fs));
+	HIPCHK(hipMemcpyAsync(c->d_rcfg[set], c->h_rcfg[set], (size_t)nl * sizeof(StreamCfg), hipMemcpyHostToDevice, fs));
 	StreamReset R;
 	memset(&R, 0, sizeof(R));
 	R.list = c->d_reset[set];
@@ -914,6 +967,8 @@ static int launch_resets(tfrec_amd_ctx *c, int set)
 	R.tail_fill = c->in10x ? 0 : 0x80;  // as tfrec_amd_create: int16 zero, or u8 128
 	R.tail10 = c->in10x ? c->d_tail10[c->tail_sel] : nullptr;
 	R.fsk = c->d_fsk;
+	R.cfgs = c->d_rcfg[set];
+	R.scfg = c->d_scfg;
 	R.n_active = c->launch.n_active;
 	for (int a = 0; a < c->launch.n_active; a++)
 		R.states[a] = c->launch.states[a];
@@ -978,9 +1033,9 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	HIPCHK(launch_frontend(fs, fin, fstride, c->cfg.n_streams, n_blocks, c->d_tail[c->tail_sel],
 			       c->d_tail[c->tail_sel ^ 1], c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride,
 			       c->d_prevdec[set], c->cfg.thresh ? c->cfg.thresh : 500, c->taps, c->in10x));
-	if (c->d_fsk)  // auto threshold: per-block thresholds rewrite the trigger mask (fm_demod.cpp:58-73)
+	if (c->n_auto)  // auto threshold: per-block thresholds rewrite the trigger mask (fm_demod.cpp:58-73)
 		HIPCHK(launch_threshold(fs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams,
-					n_blocks, c->d_fsk, c->wmax));
+					n_blocks, c->d_fsk, c->wmax, c->per_stream ? c->d_scfg : nullptr));
 	if (timing)
 		HIPCHK(hipEventRecord(c->ev[set][3], fs));
 	const bool fmdev_k2 = c->need_fmdev && c->fmdev_k2 && !(c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS);
@@ -1368,6 +1423,62 @@ int tfrec_amd_reset_streams(tfrec_amd_ctx *c, const int32_t *streams, int n)
 	return TFREC_AMD_OK;
 }
 
+int tfrec_amd_configure_streams(tfrec_amd_ctx *c, const int32_t *streams, const tfrec_amd_stream_config *cfgs, int n)
+{
+	if (!c || n < 0 || (n > 0 && (!streams || !cfgs)))
+		return TFREC_AMD_E_INVAL;
+	for (int i = 0; i < n; i++) {
+		const tfrec_amd_stream_config &sc = cfgs[i];
+		if (streams[i] < 0 || streams[i] >= c->cfg.n_streams) {
+			snprintf(g_err, sizeof(g_err), "stream index %d outside [0, %d)", (int)streams[i], c->cfg.n_streams);
+			return TFREC_AMD_E_INVAL;
+		}
+		if (sc.types_mask == 0 || (sc.types_mask & ~c->cfg.types_mask) != 0 || sc.thresh < 0 || sc.filter_type < 0 ||
+		    sc.filter_type > 1 || sc.reserved != 0) {
+			snprintf(g_err, sizeof(g_err), "bad stream config (types_mask 0x%x of the context's 0x%x, thresh %d, filter_type %d, "
+				 "reserved %d)", (unsigned)sc.types_mask, (unsigned)c->cfg.types_mask, (int)sc.thresh, (int)sc.filter_type,
+				 (int)sc.reserved);
+			return TFREC_AMD_E_INVAL;
+		}
+	}
+	if (c->poisoned) {
+		snprintf(g_err, sizeof(g_err), "an earlier submit failed half way: the context must be recreated");
+		return TFREC_AMD_E_STATE;
+	}
+	if (n == 0)
+		return TFREC_AMD_OK;
+	// a configure is a reset with new settings: the stream restarts at the next submit (before the first one that restores
+	// nothing but the settings)
+	for (int i = 0; i < n; i++) {
+		const int s = streams[i];
+		c->scfg_api[s] = cfgs[i];
+		c->scfg[s] = device_cfg(c, cfgs[i]);
+		if (!c->reset_marked[s]) {
+			c->reset_marked[s] = 1;
+			c->reset_pending.push_back(s);
+		}
+	}
+	c->n_auto = 0;
+	for (const StreamCfg &d : c->scfg)
+		c->n_auto += d.autoth;
+	if (!c->per_stream) {  // from the next submit on the kernels read every stream's own settings
+		c->per_stream = true;
+		c->launch.scfg = c->d_scfg;
+		c->taps.scfg = c->d_scfg;
+		for (int k = 0; k < 20; k++)  // f2: the narrow taps from now on (w: the wide ones)
+			c->taps.f2[k][0] = c->taps.f2[k][1] = (float)kNarrowTaps[k] / 65536.0f;
+	}
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_get_stream_config(tfrec_amd_ctx *c, int stream, tfrec_amd_stream_config *out)
+{
+	if (!c || !out || stream < 0 || stream >= c->cfg.n_streams)
+		return TFREC_AMD_E_INVAL;
+	*out = c->scfg_api[stream];
+	return TFREC_AMD_OK;
+}
+
 int tfrec_amd_read_stage0(tfrec_amd_ctx *c, int stream, int16_t *out, size_t n_pairs)
 {
 	if (!c || !out || !c->in10x || stream < 0 || stream >= c->cfg.n_streams ||
@@ -1489,7 +1600,7 @@ int tfrec_amd_read_thresh(tfrec_amd_ctx *c, int stream, int *thresh)
 {
 	if (!c || !thresh || stream < 0 || stream >= c->cfg.n_streams)
 		return TFREC_AMD_E_INVAL;
-	if (!c->d_fsk) {
+	if (!c->per_stream && c->cfg.thresh) {  // (a configured stream's FskState holds its fixed threshold: stream_reset_kernel)
 		*thresh = c->cfg.thresh;
 		return TFREC_AMD_OK;
 	}

@@ -276,6 +276,11 @@ __global__ __launch_bounds__(64) void chains_kernel(const uint32_t *__restrict__
 {
 	const int a = blockIdx.y;
 	const ChainParams &p = L.params[a];
+	if (L.scfg) {  // tfrec_amd_configure_streams: a slot outside the stream's own types does not run on it
+		const int s = blockIdx.x * 64 + threadIdx.x;
+		if (s < n_streams && !((L.scfg[s].amask >> a) & 1))
+			return;
+	}
 	if (p.kind == 0)
 		chain_body<0>(dec, dec_stride, mask, mask_stride, n_streams, n_blocks, sample_base, L.states[a], p, L.slot[a],
 			      events, eb, flags);

@@ -32,6 +32,7 @@
 
 #include "dsp_dev.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace tfrec {
 
@@ -51,12 +52,16 @@ typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(4)));  // 16
 // begins in the moment the front end ends).  At lower priority the front end starves instead (rounds 4 and 6).  With a few
 // workgroups per CU placed at once its queue is empty, the others start beside it: -3 % (profiles/r06_ab_front_end_dispatch.txt).
 constexpr int kFrontPersist = 2048;
-template <bool IN16>
+// PER = false: every stream has the context's `thresh` and stage-2 `taps` (FrontTaps).  PER = true (a context in which
+// tfrec_amd_configure_streams was called): `taps` is a FrontTapsCfg, and a stream's own StreamCfg picks its threshold and its
+// narrow or wide taps -- s is wave-uniform per tile, so that is a scalar load and a select per tap and tile.  (The PER = false
+// code is exactly the kernel it was before the per-stream settings: `if constexpr` keeps them out of it.)
+template <bool IN16, bool PER>
 __global__ __launch_bounds__(kFrontThreads) void frontend_kernel(
 	const uint8_t *__restrict__ iq, size_t stride, int m_total, const uint8_t *__restrict__ tail_in,
 	uint8_t *__restrict__ tail_out, uint32_t *__restrict__ dec, size_t dec_stride,
-	unsigned long long *__restrict__ mask, size_t mask_stride, uint32_t *__restrict__ prevdec, int thresh, FrontTaps taps,
-	int n_streams, int persist)
+	unsigned long long *__restrict__ mask, size_t mask_stride, uint32_t *__restrict__ prevdec, int thresh,
+	std::conditional_t<PER, FrontTapsCfg, FrontTaps> taps, int n_streams, int persist)
 {
 	constexpr int kB = IN16 ? 2 : 1;             // bytes per rail sample
 	constexpr int kTail = kTailBytes * kB;      // history bytes (56 complex samples)
@@ -76,6 +81,12 @@ __global__ __launch_bounds__(kFrontThreads) void frontend_kernel(
 	for (int w = persist ? (int)blockIdx.x : 0; w < n_work; w += persist ? (int)gridDim.x : 1) {
 	const int s = persist ? w / ntiles : (int)blockIdx.y;
 	const int tile = persist ? w - s * ntiles : (int)blockIdx.x;
+	int thresh_s = thresh;
+	bool wide_s = false;
+	if constexpr (PER) {
+		thresh_s = taps.scfg[s].thresh;
+		wide_s = taps.scfg[s].wide != 0;
+	}
 	// (the lane index laundered per tile: what the tile derives from it is computed again instead of being kept alive across the
 	// whole loop -- with everything hoisted the kernel needed 153 registers instead of 97, three waves per SIMD instead of five)
 	int tid = threadIdx.x;
@@ -255,11 +266,21 @@ __global__ __launch_bounds__(kFrontThreads) void frontend_kernel(
 	// the floats -- exact integers below 2^17 --, as the sign of (thresh + 0.5) - (|I| + |Q|) (never zero: x - x would be -0
 	// in this kernel's rounding mode).  5 instructions per sample instead of 9 and no compare / select pairs with their
 	// wait states; the 16-bit halves are packed by one v_perm_b32.
-	const float thresh_h = (float)thresh + 0.5f;
+	const float thresh_h = (float)thresh_s + 0.5f;
 	f32x2 accs[R];
 #pragma unroll
 	for (int o = 0; o < R; o++)
 		accs[o] = f32x2{ kMagic, kMagic };
+	if constexpr (PER) {
+#pragma unroll
+		for (int n = 0; n < 20; n++) {
+			const f32x2 h = wide_s ? f32x2{ taps.w[n][0], taps.w[n][1] } : f32x2{ taps.f2[n][0], taps.f2[n][1] };
+#pragma unroll
+			for (int o = 0; o < R; o++)
+				accs[o] = __builtin_elementwise_fma(y[2 * o + n], h, accs[o]);
+			__builtin_amdgcn_sched_barrier(0);
+		}
+	} else {
 #pragma unroll
 	for (int n = 0; n < 20; n++) {
 #pragma unroll
@@ -269,13 +290,14 @@ __global__ __launch_bounds__(kFrontThreads) void frontend_kernel(
 		// needs a wait state before its successor)
 		__builtin_amdgcn_sched_barrier(0);
 	}
+	}
 #pragma unroll
 	for (int o = 0; o < R; o++) {
 		const f32x2 acc = accs[o];
 		if (IN16) {  // int16 input: the reference's int16 store can wrap (dsp_stuff.cpp:196): integer path
 			const int oI = (int)(int16_t)(__float_as_uint(acc.x) & 0xffffu), oQ = (int)(int16_t)(__float_as_uint(acc.y) & 0xffffu);
 			outw[o] = ((uint32_t)oI & 0xffffu) | ((uint32_t)oQ << 16);
-			nib |= (uint32_t)((abs(oI) + abs(oQ)) > thresh) << o;
+			nib |= (uint32_t)((abs(oI) + abs(oQ)) > thresh_s) << o;
 		} else {
 			const f32x2 d = acc - f32x2{ kMagic, kMagic };
 			const float r = thresh_h - (__builtin_fabsf(d.x) + __builtin_fabsf(d.y));
@@ -317,9 +339,15 @@ __global__ __launch_bounds__(kFrontThreads) void frontend_kernel(
 	// at stream start): the FM discriminator pass needs it for sample 0
 	if (tile == 0 && tid == 0) {
 		f32x2 acc = { kMagic, kMagic };
+		if constexpr (PER) {
+			for (int n = 0; n < 20; n++)
+				acc = __builtin_elementwise_fma(y1[y1_phys(2 + n)], wide_s ? f32x2{ taps.w[n][0], taps.w[n][1] } :
+											     f32x2{ taps.f2[n][0], taps.f2[n][1] }, acc);
+		} else {
 #pragma unroll
 		for (int n = 0; n < 20; n++)
 			acc = __builtin_elementwise_fma(y1[y1_phys(2 + n)], f32x2{ taps.f2[n][0], taps.f2[n][1] }, acc);
+		}
 		prevdec[s] = (__float_as_uint(acc.x) & 0xffffu) | (__float_as_uint(acc.y) << 16);
 	}
 	if (persist)
@@ -545,19 +573,26 @@ hipError_t launch_decim10(hipStream_t st, const uint8_t *iq, size_t stride, int 
 
 hipError_t launch_frontend(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks,
 			   const uint8_t *tail_in, uint8_t *tail_out, uint32_t *dec, size_t dec_stride,
-			   unsigned long long *mask, size_t mask_stride, uint32_t *prevdec, int thresh, const FrontTaps &taps,
+			   unsigned long long *mask, size_t mask_stride, uint32_t *prevdec, int thresh, const FrontTapsCfg &taps,
 			   bool in16)
 {
 	const int m_total = n_blocks * kBlockDec;
 	// (config 5's int16 entry keeps a workgroup per tile: behind the 10:1 stage, which it waits for, the persistent form measured 4 % slower)
 	const int persist = in16 ? 0 : kFrontPersist;
 	const dim3 grid = persist ? dim3((unsigned)std::min<long>(persist, (long)(m_total / kTileDec) * n_streams)) : dim3(m_total / kTileDec, n_streams);
-	if (in16)
-		hipLaunchKernelGGL(frontend_kernel<true>, grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
+	const FrontTaps &narrow = taps;  // taps.scfg == nullptr: no stream was ever configured, the uniform kernel
+	if (taps.scfg && in16)
+		hipLaunchKernelGGL((frontend_kernel<true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
 				   dec, dec_stride, mask, mask_stride, prevdec, thresh, taps, n_streams, persist);
+	else if (taps.scfg)
+		hipLaunchKernelGGL((frontend_kernel<false, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
+				   dec, dec_stride, mask, mask_stride, prevdec, thresh, taps, n_streams, persist);
+	else if (in16)
+		hipLaunchKernelGGL((frontend_kernel<true, false>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
+				   dec, dec_stride, mask, mask_stride, prevdec, thresh, narrow, n_streams, persist);
 	else
-		hipLaunchKernelGGL(frontend_kernel<false>, grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
-				   dec, dec_stride, mask, mask_stride, prevdec, thresh, taps, n_streams, persist);
+		hipLaunchKernelGGL((frontend_kernel<false, false>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
+				   dec, dec_stride, mask, mask_stride, prevdec, thresh, narrow, n_streams, persist);
 	return hipGetLastError();
 }
 

@@ -56,6 +56,12 @@ constexpr int kFmThreads = 256, kFmTile = 1024;
 struct FrontTaps {
 	float f2[20][2];  // stage-2 taps / 65536, each twice: the (I, Q) operand of a packed FMA as it sits in a scalar register pair
 };
+struct StreamCfg;
+// the per-stream front end (tfrec_amd_configure_streams): f2 = the narrow taps, w = the wide ones, chosen by StreamCfg::wide
+struct FrontTapsCfg : FrontTaps {
+	float w[20][2];
+	const StreamCfg *scfg;  // nullptr: no stream was ever configured (the uniform front end, f2 = the context's taps)
+};
 
 // ---- biquad (dsp_stuff.cpp:28-56); state as the reference's members, coefficients in FrontParams
 struct Biquad {
@@ -110,12 +116,23 @@ __host__ __device__ inline int tfa2_numbits_mul(int tdiff, uint64_t nb_mul)
 	return (int)(((uint64_t)(uint32_t)(tdiff >> 1) * nb_mul + (1ull << 39)) >> 40);
 }
 
+// per-stream settings (tfrec_amd_configure_streams), one entry per stream on the device; written only by stream_reset_kernel
+struct StreamCfg {
+	uint32_t amask;   // bit a: active slot a (launch order) runs on this stream
+	int32_t thresh;   // trigger threshold; auto streams: 500, where their FskState restarts
+	int32_t wmax;     // the longest window of the stream's slots (the auto threshold's "some demodulator in its window")
+	uint16_t autoth;  // auto threshold (fm_demod.cpp:23-27)
+	uint16_t wide;    // -W stage-2 taps
+};
+static_assert(sizeof(StreamCfg) == 16, "StreamCfg");
+
 // everything one chains launch needs, passed by value as kernel argument
 struct ChainLaunch {
 	int32_t n_active;
 	int32_t slot[kNSlots];
 	ChainState *states[kNSlots];
 	ChainParams params[kNSlots];
+	const StreamCfg *scfg;  // per-stream settings, or nullptr: every stream runs every active slot
 };
 
 // fsk_demod state of one stream in auto-threshold mode (fm_demod.h:23-30, fm_demod.cpp:18-32)

@@ -11,12 +11,20 @@
 // the same trigger test, so "some demodulator is in its window" = "within Wmax samples after a trigger" with Wmax
 // the largest window of the registered demodulators.  One wave per stream: 64 samples per step (coalesced),
 // ballot -> mask word, wave-uniform bookkeeping.  Rewrites the trigger mask the front end produced.
+// scfg (tfrec_amd_configure_streams; nullptr: every stream is auto with the context's wmax): the demodulators registered
+// are the stream's own, so Wmax is its own; a stream with a fixed threshold keeps the front end's mask and its FskState.
 __global__ __launch_bounds__(64) void threshold_kernel(const uint32_t *__restrict__ dec, size_t dec_stride,
 						       unsigned long long *__restrict__ mask, size_t mask_stride, int n_blocks,
-						       FskState *__restrict__ fsk, int wmax)
+						       FskState *__restrict__ fsk, int wmax, const StreamCfg *__restrict__ scfg)
 {
 	const int s = blockIdx.x;
 	const int lane = threadIdx.x;
+	if (scfg) {
+		const StreamCfg sc = scfg[s];
+		if (!sc.autoth)
+			return;
+		wmax = sc.wmax;
+	}
 	const uint32_t *drow = dec + (size_t)s * dec_stride;
 	unsigned long long *mrow = mask + (size_t)s * mask_stride;
 	FskState st = fsk[s];
@@ -56,10 +64,10 @@ __global__ __launch_bounds__(64) void threshold_kernel(const uint32_t *__restric
 }
 
 hipError_t launch_threshold(hipStream_t st, const uint32_t *dec, size_t dec_stride, unsigned long long *mask,
-			    size_t mask_stride, int n_streams, int n_blocks, FskState *fsk, int wmax)
+			    size_t mask_stride, int n_streams, int n_blocks, FskState *fsk, int wmax, const StreamCfg *scfg)
 {
 	hipLaunchKernelGGL(threshold_kernel, dim3(n_streams), dim3(64), 0, st, dec, dec_stride, mask, mask_stride, n_blocks, fsk,
-			   wmax);
+			   wmax, scfg);
 	return hipGetLastError();
 }
 
@@ -83,12 +91,15 @@ __global__ __launch_bounds__(64) void windows_kernel(const unsigned long long *_
 	const int nwords = M >> 6;
 	const unsigned long long *mrow = mask + (size_t)s * mask_stride;
 	const size_t total = (size_t)L.n_active * n_streams * T.cap;
+	// the stream's own slots (tfrec_amd_configure_streams): an excluded slot is inactive here -- it opens no window, queues
+	// no work, and its tables say so (no windows, timeout carry 0)
+	const uint32_t amask = L.scfg ? L.scfg[s].amask : ~0u;
 	// per active slot, wave-uniform
 	int W[kNSlots], t0[kNSlots], open_g[kNSlots], last_trig[kNSlots], count[kNSlots], vs[kNSlots];
 	bool open[kNSlots], overflow = false;
 #pragma unroll
 	for (int a = 0; a < kNSlots; a++) {
-		const bool act = a < L.n_active;
+		const bool act = a < L.n_active && ((amask >> a) & 1);
 		W[a] = act ? L.params[a].window : 400;
 		t0[a] = act ? T.timeout_carry[a * n_streams + s] : 0;
 		open[a] = t0[a] > 0;
@@ -173,7 +184,7 @@ __global__ __launch_bounds__(64) void windows_kernel(const unsigned long long *_
 			const int lastt = ((w0 + l2) << 6) + __builtin_amdgcn_readlane(last_bit, l2);
 #pragma unroll
 			for (int a = 0; a < kNSlots; a++) {
-				if (a < L.n_active) {
+				if (a < L.n_active && ((amask >> a) & 1)) {
 					if (open[a] && first > last_trig[a] + W[a] - 1) {
 						emit(a, open_g[a], last_trig[a] + W[a] - 1);
 						count[a]++;

@@ -26,14 +26,17 @@ void tfrec_handler_args(const sensordata_t &d, sensor_e dec_type, char *out, siz
 }
 
 gpu_engine::gpu_engine(const std::vector<std::string> &dumpfiles, int _types, int _thresh, int _filter, int _dbg,
-		       const std::vector<int> &_devices, int blocks_per_submit)
-	: files(dumpfiles), types(_types), thresh(_thresh), filter(_filter), dbg(_dbg), bps(blocks_per_submit),
+		       const std::vector<int> &_devices, int blocks_per_submit, const std::vector<file_settings> &per_file)
+	: files(dumpfiles), settings(per_file), types(_types), thresh(_thresh), filter(_filter), dbg(_dbg), bps(blocks_per_submit),
 	  devices(_devices), n_telegrams(0), sink(NULL), psink(NULL), out_mode(0), bits_replay(false), slots(0)
 {
 	if (devices.empty())
 		devices.push_back(0);
-	// one set of protocol handlers per stream, registered like main.cpp:173-218
+	if (settings.size() != files.size())
+		settings.assign(files.size(), file_settings{ types, thresh, filter });
+	// one set of protocol handlers per stream, registered like main.cpp:173-218 (with the file's own -T)
 	for (size_t s = 0; s < files.size(); s++) {
+		const int types = settings[s].types;
 		std::vector<decoder *> d(TFREC_AMD_NSLOTS, (decoder *)NULL);
 		if (types & (1 << TFA_1)) d[TFREC_AMD_SLOT_TFA1] = new sinked_decoder<tfa1_decoder>(TFA_1, &sink, (int)s);
 		if (types & (1 << TFA_2)) d[TFREC_AMD_SLOT_TFA2] = new sinked_decoder<tfa2_decoder>(TFA_2, &sink, (int)s);
@@ -126,20 +129,26 @@ void gpu_engine::replay(const tfrec_amd_event &ev)
 namespace {
 
 // One batch of a device context: the blocks every stream gets, the dump file each stream (slot) reads (-1: none, silence),
-// and the streams reset before it is submitted (their previous file ended in the batch before)
+// the streams reset before it is submitted (their previous file ended in the batch before), and the streams configured
+// before it (their next file's settings differ from the stream's current ones: a configure is a reset with new settings)
 struct batch_plan {
 	int nb;
 	std::vector<int> file;
 	std::vector<int32_t> reset;
+	std::vector<int32_t> conf;
+	std::vector<tfrec_amd_stream_config> conf_cfg;
 };
 
 // The batches that push the files [s0, s1) through nslots streams of bps blocks (file_blocks: blocks of every file of the job).
 // Files take free streams in order; a file's last batch may be partial (padded with silence, its events cut by the engine).
 // A batch has bps blocks unless no stream needs that many.  With one stream per file this is the plan of a run without -n:
 // every file starts in the first batch and no stream is ever reset.
-std::vector<batch_plan> plan_batches(const std::vector<size_t> &file_blocks, size_t s0, size_t s1, size_t nslots, int bps)
+// settings: every file's; dflt: the context's.
+std::vector<batch_plan> plan_batches(const std::vector<size_t> &file_blocks, const std::vector<file_settings> &settings,
+				     const file_settings &dflt, size_t s0, size_t s1, size_t nslots, int bps)
 {
 	std::vector<batch_plan> plan;
+	std::vector<file_settings> has(nslots, dflt);  // the settings each stream runs with
 	std::vector<int> cur(nslots, -1);
 	std::vector<size_t> left(nslots, 0);    // blocks of the stream's file still to submit
 	std::vector<bool> used(nslots, false);  // the stream has carried a file: reset it before the next one
@@ -153,8 +162,13 @@ std::vector<batch_plan> plan_batches(const std::vector<size_t> &file_blocks, siz
 					continue;  // (no block, no event)
 				cur[j] = (int)f;
 				left[j] = file_blocks[f];
-				if (used[j])
+				if (settings[f] != has[j]) {
+					has[j] = settings[f];
+					b.conf.push_back((int32_t)j);
+					b.conf_cfg.push_back(tfrec_amd_stream_config{ has[j].types, has[j].thresh, has[j].filter, 0 });
+				} else if (used[j]) {
 					b.reset.push_back((int32_t)j);
+				}
 				used[j] = true;
 			}
 		}
@@ -327,6 +341,11 @@ struct device_worker {
 				if (rr)
 					return rr;
 			}
+			if (!b.conf.empty()) {  // ... with the settings of their next file
+				const int rr = tfrec_amd_configure_streams(ctx, b.conf.data(), b.conf_cfg.data(), (int)b.conf.size());
+				if (rr)
+					return rr;
+			}
 			return tfrec_amd_submit_host(ctx, host[k % kBufs], row, b.nb);
 		};
 		size_t queued = 0;
@@ -420,7 +439,9 @@ int gpu_engine::run()
 		w.s1 = w.s0 + base + (d < rem ? 1 : 0);
 		w.files = &files;
 		w.device = devices[d];
-		w.types = types;
+		w.types = 0;  // the union of the device's files' types
+		for (size_t s = w.s0; s < w.s1; s++)
+			w.types |= settings[s].types;
 		w.thresh = thresh;
 		w.filter = filter;
 		w.bps = bps;
@@ -429,7 +450,7 @@ int gpu_engine::run()
 		if (slots > 0)
 			w.nslots = std::min(w.nslots, (size_t)slots);
 		w.file_blocks = &file_blocks;
-		w.plan = plan_batches(file_blocks, w.s0, w.s1, w.nslots, bps);
+		w.plan = plan_batches(file_blocks, settings, file_settings{ w.types, thresh, filter }, w.s0, w.s1, w.nslots, bps);
 		n_batches = std::max(n_batches, w.plan.size());
 	}
 	std::atomic<bool> abort(false);

@@ -81,13 +81,25 @@ private:
 	long n_records;
 };
 
+// -T, -t and -W of one dump file (tfrec_gpu -p)
+struct file_settings {
+	int types, thresh, filter;
+	bool operator==(const file_settings &o) const { return types == o.types && thresh == o.thresh && filter == o.filter; }
+	bool operator!=(const file_settings &o) const { return !(*this == o); }
+};
+
 class gpu_engine {
 public:
 	// types: -T bit mask; thresh: -t; filter: -W; dbg: -1 quiet, 0 normal, >=1 debug (main.cpp:97).
 	// devices: HIP device ordinals; the streams (dump files) are sharded over them by index, contiguous ranges, no
 	// exchange between devices; an ordinal may appear more than once (several contexts on one GPU).
+	// per_file (tfrec_gpu -p): each file's own settings, one per file, or empty: (types, thresh, filter) for every file.  A
+	// device's context builds the union of its files' types and has (thresh, filter) as defaults; each file's decoders are
+	// its own types', and a stream whose file's settings differ from the context's is configured
+	// (tfrec_amd_configure_streams) before the file's first batch.
 	gpu_engine(const std::vector<std::string> &dumpfiles, int types, int thresh, int filter, int dbg,
-		   const std::vector<int> &devices, int blocks_per_submit);
+		   const std::vector<int> &devices, int blocks_per_submit,
+		   const std::vector<file_settings> &per_file = std::vector<file_settings>());
 	~gpu_engine();
 	// exec: per-telegram handler as the reference's -e (system() per record); batched: the same command started
 	// once, records on its stdin (pipe_sink); mode: the reference's -m (1 = summary at the end)
@@ -98,9 +110,10 @@ public:
 	// the byte-level replay (store_bytes + flush) moves 64 bytes per window instead of every bit.
 	void set_bits_replay(bool on) { bits_replay = on; }
 	// -n: at most n streams per device context.  The dump files of a device go through them as a queue, in command-line order:
-	// when a file's last block has been submitted its stream is reset (tfrec_amd_reset_streams) and the next file starts
-	// there with the next batch.  0 (default): one stream per file for the whole job.  A batch that carries a reset does not
-	// overlap the batch before it on the GPU: a queue of mixed-length files runs at about half the throughput.
+	// when a file's last block has been submitted its stream is reset (tfrec_amd_reset_streams) -- or configured for the next
+	// file, when that one's settings differ -- and the next file starts there with the next batch.  0 (default): one stream
+	// per file for the whole job.  A batch that carries a reset does not overlap the batch before it on the GPU (DESIGN.md
+	// 6b): a queue of mixed-length files runs at about half the throughput.
 	void set_slots(int n) { slots = n; }
 	// returns 0 on success, a TFREC_AMD_E_* code otherwise
 	int run();
@@ -111,6 +124,7 @@ public:
 private:
 	void replay(const tfrec_amd_event &ev);
 	std::vector<std::string> files;
+	std::vector<file_settings> settings;  // per file
 	int types, thresh, filter, dbg, bps;
 	std::vector<int> devices;
 	std::vector<std::vector<decoder *> > decs;

@@ -1,7 +1,7 @@
 // tfrec_amd/host/main.cpp -- tfrec_gpu: the reference's file-replay CLI on the GPU path.
 //
 //   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-q] [-D] [-B] [-d device[,device...]] [-b blocks] [-n streams]
-//             [-e handler | -E handler] [-m mode] -L dump.iq [-L more.iq ...]
+//             [-e handler | -E handler] [-m mode] [-p settings] -L dump.iq [[-p settings] -L more.iq ...]
 //   tfrec_gpu [-T hexmask] -X telegrams.txt
 //
 // Flags keep the reference's meaning (main.cpp:63-88, 107-164): -T sensor type bit mask (hex), -t trigger
@@ -15,6 +15,9 @@
 // streams on stdin, "<stream> <id> <temp> <hum> <seq> <alarm> <rssi> <flags> <ts>" per line, one write per batch.
 // -n streams (not in the reference): at most this many streams per device; the -L files queue for them in order, and a
 // stream whose file has ended is reset and takes the next file (gpu_engine.h).  <stream> of -E is then the file's index.
+// -p T=<hex>,t=<n>,W=<0|1> (not in the reference; any of the three fields, in any order): -T, -t and -W of the -L files that
+// follow it, up to the next -p -- what they would be to separate tfrec processes.  Fields left out, and files before any -p,
+// take the global -T / -t / -W.  The files share one context per device (tfrec_amd_configure_streams).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -24,6 +27,39 @@
 #include <vector>
 
 #include "gpu_engine.h"
+
+// one -p spec: the fields it sets (-1: left out, the global value)
+struct spec {
+	int types = -1, thresh = -1, filter = -1;
+};
+
+static bool parse_spec(const char *arg, spec &out)
+{
+	std::string a(arg);
+	size_t pos = 0;
+	for (;;) {
+		const size_t e = a.find(',', pos);
+		const std::string f = a.substr(pos, e == std::string::npos ? std::string::npos : e - pos);
+		if (f.size() < 3 || f[1] != '=')
+			return false;
+		const char *v = f.c_str() + 2;
+		char *end = NULL;
+		const long x = strtol(v, &end, f[0] == 'T' ? 16 : 10);
+		if (*end || end == v)
+			return false;
+		if (f[0] == 'T' && out.types < 0 && x > 0 && (x & ~0x2fL) == 0)
+			out.types = (int)x;
+		else if (f[0] == 't' && out.thresh < 0 && x >= 0 && x <= 0x7fffffff)
+			out.thresh = (int)x;
+		else if (f[0] == 'W' && out.filter < 0 && (x == 0 || x == 1))
+			out.filter = (int)x;
+		else
+			return false;  // unknown field, one given twice, or a value out of range (a mask outside 0x2f)
+		if (e == std::string::npos)
+			return true;
+		pos = e + 1;
+	}
+}
 
 static int replay_hex(int types, int dbg, const char *fn, const char *exec, bool batched)
 {
@@ -70,8 +106,11 @@ int main(int argc, char **argv)
 	bool batched = false, bits = false;
 	int mode = 0, slots = 0;
 	bool have_slots = false;
+	spec cur;  // the -p in force
+	std::vector<spec> dump_spec;  // per -L file
+	bool have_spec = false;
 	int c;
-	while ((c = getopt(argc, argv, "T:t:WqDBd:b:n:L:X:e:E:m:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:WqDBd:b:n:L:X:e:E:m:p:h")) != -1) {
 		switch (c) {
 		case 'T': types = (int)strtol(optarg, NULL, 16); break;
 		case 't': thresh = atoi(optarg); break;
@@ -85,19 +124,35 @@ int main(int argc, char **argv)
 			break;
 		case 'b': blocks = atoi(optarg); break;
 		case 'n': slots = atoi(optarg); have_slots = true; break;
-		case 'L': dumps.push_back(optarg); break;
+		case 'L':
+			dumps.push_back(optarg);
+			dump_spec.push_back(cur);
+			break;
+		case 'p':
+			cur = spec();
+			have_spec = true;
+			if (!parse_spec(optarg, cur)) {
+				fprintf(stderr, "tfrec_gpu: bad -p '%s': want T=<hex mask within 2f>,t=<thresh >= 0>,W=<0|1>\n", optarg);
+				return 1;
+			}
+			break;
 		case 'X': hexfile = optarg; break;
 		case 'e': exec = optarg; batched = false; break;
 		case 'E': exec = optarg; batched = true; break;
 		case 'm': mode = atoi(optarg); break;
 		default:
-			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] -L dump [-L dump ...] | -X hexfile\n"
-					"  -n streams  at most this many streams per device: the -L files queue for them in order\n");
+			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-p settings] -L dump [[-p settings] -L dump ...] | -X hexfile\n"
+					"  -n streams  at most this many streams per device: the -L files queue for them in order\n"
+					"  -p T=<hex>,t=<n>,W=<0|1>  -T / -t / -W of the -L files that follow, up to the next -p (fields left out: the global ones)\n");
 			return c == 'h' ? 0 : 1;
 		}
 	}
 	if (have_slots && slots < 1) {
 		fprintf(stderr, "tfrec_gpu: -n must be >= 1\n");
+		return 1;
+	}
+	if (have_spec && hexfile) {
+		fprintf(stderr, "tfrec_gpu: -p applies to -L files, not to -X\n");
 		return 1;
 	}
 	setvbuf(stdout, NULL, _IOFBF, 1 << 16);
@@ -111,7 +166,12 @@ int main(int argc, char **argv)
 		fprintf(stderr, "tfrec_gpu: -t must be >= 0 (0 = auto)\n");
 		return 1;
 	}
-	gpu_engine e(dumps, types, thresh, filter, dbg, devices, blocks);
+	std::vector<file_settings> per_file;
+	if (have_spec)
+		for (const spec &p : dump_spec)
+			per_file.push_back(file_settings{ p.types >= 0 ? p.types : types, p.thresh >= 0 ? p.thresh : thresh,
+							  p.filter >= 0 ? p.filter : filter });
+	gpu_engine e(dumps, types, thresh, filter, dbg, devices, blocks, per_file);
 	if (exec || mode)
 		e.set_handler(exec, batched, mode);
 	e.set_bits_replay(bits);
