@@ -157,6 +157,27 @@ def test_device_resident_input_and_timings():
             check_stream(ev, s, oracle_events(iq[s], 0x2F, 500))
 
 
+def test_whb_contexts_on_two_devices():
+    """One process, a WHB context on device 0 and one on device 1, submits to both in flight at once: whb_chain_kernel's
+    dynamic-LDS opt-in is a per-device attribute, set by each context's create."""
+    import torch
+
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two GPUs")
+    n_streams, n_blocks = 8, 8
+    iq = [synth.gen_batch(19 + d, 0, n_streams, n_blocks) for d in range(2)]
+    rs = [api.Receiver(n_streams, 0x2F, 500, 0, device=d, max_blocks=n_blocks, all_flushes=True) for d in range(2)]
+    try:
+        for d in range(2):
+            rs[d].submit(iq[d])
+        evs = [r.drain() for r in rs]
+    finally:
+        for r in rs:
+            r.close()
+    for d in range(2):
+        assert sum(check_stream(evs[d], s, oracle_events(iq[d][s], 0x2F, 500)) for s in range(n_streams)) > 0
+
+
 def _stress_batch():
     """Inputs that open and close trigger windows as often as possible (noise hovering around the threshold),
     saturate them (uniform random bytes), or pack bursts tightly: exercises window tables at their limits,

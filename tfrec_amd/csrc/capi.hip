@@ -25,6 +25,7 @@ hipError_t launch_pipeline(const PipeCtl &P, const uint32_t *dec, size_t dec_str
 			   size_t mask_stride, const int16_t *fmdev, size_t fmdev_stride, int n_streams, int n_blocks,
 			   long long sample_base, const ChainLaunch &L, const WinTables &T, int16_t *ld16, int32_t *dev32,
 			   tfrec_amd_event *events, EventBuf *eb, uint32_t flags);
+hipError_t whb_chain_lds_optin();
 hipError_t launch_fm_probe(hipStream_t st, const int32_t *quads, size_t n, int32_t *out, EventBuf *eb, int kind);
 hipError_t launch_iir_probe(hipStream_t st, const double *in, size_t n, const BiquadCoef &c, double *out, int form);
 hipError_t launch_threshold(hipStream_t st, const uint32_t *dec, size_t dec_stride, unsigned long long *mask,
@@ -58,9 +59,25 @@ static int hip_fail(hipError_t e, const char *what)
 		if (e_ != hipSuccess)                  \
 			return hip_fail(e_, #call);    \
 	} while (0)
+// a step that returns a TFREC_AMD_* status
+#define TRY(call)                                      \
+	do {                                           \
+		const int rc_ = (call);                \
+		if (rc_ != TFREC_AMD_OK)               \
+			return rc_;                    \
+	} while (0)
 
 struct FmTotals {
 	unsigned long long resolved = 0, verified = 0, mismatch = 0, undecidable = 0;
+};
+
+// TFREC_AMD_F_TIMING: a set's marks on the front-end stream (every layout) and the end of the serial chains
+enum HostMark {
+	kEvSubmit,      // the submit starts (fs)
+	kEvFmdevDone,   // the discriminator pass behind the front end is done (fs): the chains start
+	kEvSerialDone,  // the serial chains are done (cs)
+	kEvFrontDone,   // the front end and the threshold pass are done (fs)
+	kHostMarks
 };
 
 struct tfrec_amd_ctx {
@@ -69,36 +86,54 @@ struct tfrec_amd_ctx {
 	// stage-2 taps of the front end: the context's (f2, scfg == nullptr) until a stream is configured, then narrow (f2) and
 	// wide (w) with scfg = d_scfg
 	FrontTapsCfg taps;
-	// front-end outputs, one set per submit in flight like the event buffers: the front end of submit k+2 (its own stream)
-	// runs beside the demodulator chains of submit k
+	// Every device buffer, page-locked block, stream and event the context owns, in the order tfrec_amd_create made them
+	// (own_*): release_all frees them in reverse.  Aliased streams are not recorded (make_streams).
+	struct Owned {
+		enum Kind { kDevice, kPinned, kStream, kEvent } kind;
+		void *h;
+	};
+	std::vector<Owned> owned;
+	size_t dev_bytes = 0, pinned_bytes = 0;  // tfrec_amd_get_memory
+	// ---- streams and events (make_streams: the layout and why; make_pipes)
+	// per set: what launch_pipeline takes for a submit of that set (the streams, the set's events and buffers); the serial
+	// layout uses its fs, cs, ev_front and done
+	PipeCtl pipe[kSets] = {};
+	hipStream_t cpy = nullptr;  // the drain's device-to-host copies
+	bool deep = false;          // deep layout
+	bool fmdev_k2 = false;      // the discriminator pass runs in the pipeline (PipeCtl::fmdev_wmax), not behind the front end
+	hipEvent_t ev_in[kSets] = {};              // the caller's stream has produced the input
+	hipEvent_t ev[kSets][kHostMarks] = {};     // TFREC_AMD_F_TIMING
+	hipEvent_t tev[kSets][kTimingMarks] = {};  // TFREC_AMD_F_TIMING, window-parallel pipeline: PipeCtl::tev
+	int last_set = 0;
+	// ---- front end (make_front_buffers).  Outputs, one set per submit in flight like the event buffers: the front end of
+	// submit k+2 (its own stream) runs beside the demodulator chains of submit k
 	uint32_t *d_dec[kSets] = {};
 	size_t dec_stride = 0;  // uint32 units
 	unsigned long long *d_mask[kSets] = {};
 	size_t mask_stride = 0;
 	int16_t *d_fmdev[kSets] = {};  // [n_streams][m_max] fm_dev of the decimated samples (computed near windows)
 	uint32_t *d_prevdec[kSets] = {};  // [n_streams] the decimated sample before the submit's first one
-	bool need_fmdev = false;                      // a TFA_2-family demodulator is registered
-	// HIP multiplexes the streams of one priority onto GPU_MAX_HW_QUEUES hardware queues (default 4), and two streams
-	// that share a queue serialise (profiles/ubench/queues.hip).  The deep layout (stage A of submit k+1 beside stage B
-	// of submit k) has six streams in two priority classes (see cp below); the shallow one has k2 = cs and kw = aux.
-	hipStream_t fs = nullptr;                     // front-end stream + window scan (+ the drain's device-to-host copies)
-	hipStream_t cs = nullptr;                     // TFA_2-family slicers and decoders (the caller's stream only orders the input)
-	hipStream_t k2 = nullptr, kw = nullptr;       // biquad stages (deep layout only: else aliases of cs / aux)
-	// The drain's device-to-host copies must not queue behind the work of younger submits, so they need a hardware
-	// queue of their own.  The runtime keeps one pool of hardware queues PER PRIORITY: fs / cs / aux / t1 are the
-	// high-priority streams, and cp (with k2 / kw in the deep layout) has normal priority -- no pool holds more than
-	// four streams, whatever GPU_MAX_HW_QUEUES is.
-	hipStream_t cp = nullptr;
-	bool deep = false;                            // deep layout: the window scan runs at the head of kw, not on fs
-	bool fmdev_k2 = false;                        // the discriminator pass runs ahead of k2 (on fq), not behind the front end
-	hipEvent_t ev_in[kSets] = {}, ev_front[kSets] = {};
-	hipEvent_t ev_pipe[kSets][6] = {};            // per set: PipeCtl's ev_win, ev_fork, ev_k2, ev_kw, ev_fm, ev_spec
-	hipStream_t fq = nullptr;                     // PipeCtl::fq (deep layout, fmdev_k2), low priority
-	hipStream_t ks = nullptr;                     // PipeCtl::ks (when fq exists), low priority
-	hipStream_t cq = nullptr;                     // the drain's copies (deep layout; else on cp), low priority
-	int last_set = 0;
-	// one set per submit in flight, like the front-end outputs: the window scan and the biquads of submit k+1 fill
-	// theirs while the slicers of submit k still read the other
+	FskState *d_fsk = nullptr;  // auto threshold (every context has it: a stream can be configured to auto)
+	int wmax = 0;
+	// tfrec_amd_configure_streams: every stream's settings as the next submit uses them (scfg, the host's copy), their device
+	// copy as the last submit used them (d_scfg: written only by stream_reset_kernel, in the entries of its list), and the
+	// settings that travel with a submit's reset list (d_rcfg / h_rcfg).  per_stream: a stream was configured -- from then on
+	// the kernels read d_scfg (launch.scfg, taps.scfg); before, the uniform kernels run.  n_auto: streams of scfg in auto mode.
+	std::vector<StreamCfg> scfg;
+	std::vector<tfrec_amd_stream_config> scfg_api;
+	StreamCfg *d_scfg = nullptr;
+	StreamCfg *d_rcfg[kSets] = {}, *h_rcfg[kSets] = {};
+	bool per_stream = false;
+	int n_auto = 0;
+	uint8_t *d_tail[kSets] = {};  // FIR history: [tail_sel] is read by the next front end, [tail_sel ^ 1] written
+	int tail_sel = 0;
+	// TFREC_AMD_F_INPUT_10X: output of the 10:1 stage (1.536 MS/s int16 pairs, one buffer per set) and its raw history
+	uint32_t *d_in16[kSets] = {};
+	size_t in16_stride = 0;  // uint32 units
+	uint8_t *d_tail10[kSets] = {};
+	bool in10x = false;
+	// ---- window-parallel pipeline (make_window_state).  One set per submit in flight, like the front-end outputs: the window
+	// scan and the biquads of submit k+1 fill theirs while the slicers of submit k still read the other
 	int16_t *d_ld16[kSets] = {};   // [chains][m_max] tfa2-family biquad outputs
 	int32_t *d_dev32[kSets] = {};  // [n_streams][m_max] WHB stage-1 outputs
 	WinTables win[kSets] = {};
@@ -112,35 +147,14 @@ struct tfrec_amd_ctx {
 	int whb_test_perturb = 0;                    // TFREC_AMD_WHB_TEST_PERTURB (tests)
 	int whb_force_fail = 0;                      // TFREC_AMD_WHB_FORCE_FAIL (tests)
 	int submit_seq = 0;
-	hipStream_t vx = nullptr;                    // the WHB check: an alias of cp (deep layout) or of aux
-	hipEvent_t ev_aux[kSets] = {};               // whb_demod_kernel of the set's submit done
-	FskState *d_fsk = nullptr;  // auto threshold (every context has it: a stream can be configured to auto)
-	int wmax = 0;
-	// tfrec_amd_configure_streams: every stream's settings as the next submit uses them (scfg, the host's copy), their device
-	// copy as the last submit used them (d_scfg: written only by stream_reset_kernel, in the entries of its list), and the
-	// settings that travel with a submit's reset list (d_rcfg / h_rcfg).  per_stream: a stream was configured -- from then on
-	// the kernels read d_scfg (launch.scfg, taps.scfg); before, the uniform kernels run.  n_auto: streams of scfg in auto mode.
-	std::vector<StreamCfg> scfg;
-	std::vector<tfrec_amd_stream_config> scfg_api;
-	StreamCfg *d_scfg = nullptr;
-	StreamCfg *d_rcfg[kSets] = {}, *h_rcfg[kSets] = {};
-	bool per_stream = false;
-	int n_auto = 0;
-	uint8_t *d_tail[kSets] = {};
-	int tail_sel = 0;
-	// TFREC_AMD_F_INPUT_10X: output of the 10:1 stage (1.536 MS/s int16 pairs, one buffer per set) and its raw history
-	uint32_t *d_in16[kSets] = {};
-	size_t in16_stride = 0;  // uint32 units
-	uint8_t *d_tail10[kSets] = {};
-	bool in10x = false;
-	// One event buffer set per submit in flight (FIFO of depth TFREC_AMD_FIFO_DEPTH): submits may be queued while the
-	// host still drains an older one
+	// ---- event buffers (make_event_blocks).  One set per submit in flight (FIFO of depth TFREC_AMD_FIFO_DEPTH): submits may
+	// be queued while the host still drains an older one
 	tfrec_amd_event *d_events[kSets] = {};
 	EventBuf *d_eb[kSets] = {};
 	uint8_t *d_evblock[kSets] = {}, *h_evblock[kSets] = {};  // what d_eb / d_events and h_eb / h_events point into
 	uint8_t *h_evblock_dev[kSets] = {};                      // the page-locked blocks as the device addresses them (drain_copy_kernel)
 	EventBuf *d_eb_fresh = nullptr;       // { 0, max_events, 0 }: copied over a set's EventBuf when a submit starts
-	// Pinned staging for the drain, one per set: the device-to-host copies of a submit's event buffer are queued on cp
+	// Pinned staging for the drain, one per set: the device-to-host copies of a submit's event buffer are queued on cpy
 	// when the submit is made (behind its three end-of-chain events), so they are done when the host comes to drain it.
 	// The number of events is not known then: `copy_guess` of them are copied ahead (twice the last submit's count), the
 	// drain fetches the rest if there are more.
@@ -150,10 +164,9 @@ struct tfrec_amd_ctx {
 	uint32_t copied_n[kSets] = {};
 	uint32_t copy_guess = 4096, copy_guess_min = 4096;  // TFREC_AMD_COPY_GUESS_MIN (tests: exercise the fetch-the-rest path)
 	std::vector<uint32_t> sort_idx, sort_start;
-	hipEvent_t done[kSets][3] = {};  // end of the submit that owns the set, on the cs / aux / t1 stream
 	int head = 0, inflight = 0;           // oldest undrained set, submits not yet drained (0..TFREC_AMD_FIFO_DEPTH)
 	int last_drained = -1;
-	uint8_t *d_stage[kSets] = {};  // tfrec_amd_submit_host: device staging, one per buffer set
+	uint8_t *d_stage[kSets] = {};  // tfrec_amd_submit_host: device staging, one per buffer set, grown on demand
 	size_t stage_bytes[kSets] = {};
 	long long sample_base = 0;
 	int last_blocks = 0;
@@ -166,14 +179,9 @@ struct tfrec_amd_ctx {
 	std::vector<long long> set_origin[kSets];  // empty: no submit before the set's one carried a reset
 	int32_t *d_reset[kSets] = {};  // the submit's reset list on the device (stream_reset_kernel)
 	int32_t *h_reset[kSets] = {};  // ... and its page-locked source
-	ChainState *d_chain_init = nullptr;  // the constructor ChainState (create), source of every reset
-	bool submitted = false;              // done[last_set] has been recorded
+	ChainState *d_chain_init = nullptr;  // the constructor ChainState (chain_init_state), source of every reset
+	bool submitted = false;              // pipe[last_set].done has been recorded
 	bool any_reset = false;              // a submit has carried a reset: set_origin is kept from then on
-	hipEvent_t ev[kSets][4] = {};  // start, after the front end, end of the submit, after the discriminator pass
-	hipStream_t aux = nullptr;  // second stream: WHB stage 2 runs beside the TFA slicers
-	hipEvent_t tev[kSets][kTimingMarks] = {};
-	hipStream_t t1 = nullptr;  // TFA_1 slicer chain (needs no biquad stage: runs beside the TFA_2-family biquads)
-	bool whb_active = false;
 	bool timed = false;
 	// fm_dev samples decided by the exact slow path: all / checked against this host's libm at drain / differing from
 	// it / closer to a rounding midpoint than glibc's error bound
@@ -186,7 +194,6 @@ struct tfrec_amd_ctx {
 	// state, the FIFO's bookkeeping), so the context cannot continue exactly.  Every later submit / drain returns
 	// TFREC_AMD_E_STATE; destroy and recreate.
 	bool poisoned = false;
-	size_t dev_bytes = 0, pinned_bytes = 0;  // tfrec_amd_get_memory
 	// TFREC_AMD_HOST_PROF=1: host-side time of the submit / drain calls, printed when the context is destroyed
 	double hp_submit = 0, hp_wait = 0, hp_copy = 0, hp_sort = 0, hp_gap = 0, hp_lat = 0, hp_s2s = 0;
 	long hp_n = 0, hp_gap_n = 0;
@@ -333,6 +340,585 @@ static void account_fm_log(FmTotals *t, const EventBuf &eb)
 	}
 }
 
+// ---- checks shared by the entry points
+static int check_live(const tfrec_amd_ctx *c)
+{
+	if (!c->poisoned)
+		return TFREC_AMD_OK;
+	snprintf(g_err, sizeof(g_err), "an earlier submit failed half way: the context must be recreated");
+	return TFREC_AMD_E_STATE;
+}
+
+static int check_stream(const tfrec_amd_ctx *c, int32_t s)
+{
+	if (s >= 0 && s < c->cfg.n_streams)
+		return TFREC_AMD_OK;
+	snprintf(g_err, sizeof(g_err), "stream index %d outside [0, %d)", (int)s, c->cfg.n_streams);
+	return TFREC_AMD_E_INVAL;
+}
+
+static int check_fifo(const tfrec_amd_ctx *c)
+{
+	if (c->inflight < kSets)
+		return TFREC_AMD_OK;
+	snprintf(g_err, sizeof(g_err), "%d submits are waiting to be drained: call tfrec_amd_drain_events first", kSets);
+	return TFREC_AMD_E_STATE;
+}
+
+// ---- what a context owns: every buffer, stream and event of tfrec_amd_create is made by one of these, which record it
+template <class T>
+static int own_device(tfrec_amd_ctx *c, T *&p, size_t bytes)
+{
+	void *h = nullptr;
+	if (hipMalloc(&h, bytes) != hipSuccess) {
+		snprintf(g_err, sizeof(g_err), "hipMalloc(%zu) failed", bytes);
+		return TFREC_AMD_E_NOMEM;
+	}
+	c->owned.push_back({ tfrec_amd_ctx::Owned::kDevice, h });
+	c->dev_bytes += bytes;
+	p = static_cast<T *>(h);
+	return TFREC_AMD_OK;
+}
+
+template <class T>
+static int own_pinned(tfrec_amd_ctx *c, T *&p, size_t bytes)
+{
+	void *h = nullptr;
+	if (hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess) {
+		snprintf(g_err, sizeof(g_err), "hipHostMalloc(%zu) failed", bytes);
+		return TFREC_AMD_E_NOMEM;
+	}
+	c->owned.push_back({ tfrec_amd_ctx::Owned::kPinned, h });
+	c->pinned_bytes += bytes;
+	p = static_cast<T *>(h);
+	return TFREC_AMD_OK;
+}
+
+static int own_stream(tfrec_amd_ctx *c, hipStream_t &st, int prio)
+{
+	HIPCHK(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, prio));
+	c->owned.push_back({ tfrec_amd_ctx::Owned::kStream, st });
+	return TFREC_AMD_OK;
+}
+
+static int own_event(tfrec_amd_ctx *c, hipEvent_t &e, unsigned flags)
+{
+	HIPCHK(hipEventCreateWithFlags(&e, flags));
+	c->owned.push_back({ tfrec_amd_ctx::Owned::kEvent, e });
+	return TFREC_AMD_OK;
+}
+
+// everything recorded, newest first, and tfrec_amd_submit_host's staging
+static void release_all(tfrec_amd_ctx *c)
+{
+	for (auto it = c->owned.rbegin(); it != c->owned.rend(); ++it)
+		switch (it->kind) {
+		case tfrec_amd_ctx::Owned::kDevice: (void)hipFree(it->h); break;
+		case tfrec_amd_ctx::Owned::kPinned: (void)hipHostFree(it->h); break;
+		case tfrec_amd_ctx::Owned::kStream: (void)hipStreamDestroy(static_cast<hipStream_t>(it->h)); break;
+		case tfrec_amd_ctx::Owned::kEvent: (void)hipEventDestroy(static_cast<hipEvent_t>(it->h)); break;
+		}
+	c->owned.clear();
+	for (uint8_t *&p : c->d_stage) {
+		(void)hipFree(p);
+		p = nullptr;
+	}
+}
+
+// constructor state of a chain: tfa1.cpp:136-141, tfa2.cpp:316-334, whb.cpp:605-623, decoders :36-45/:54-62/:77-107
+static ChainState chain_init_state()
+{
+	ChainState st;
+	memset(&st, 0, sizeof(st));
+	st.sr_cnt = -1;
+	st.dmin = 32767;
+	st.dmax = -32767;
+	return st;
+}
+
+// A stream's settings as the kernels read them: the active slots (launch order) of its types, its threshold (auto: 500, where
+// its FskState starts), its longest window, its taps
+// second-stage taps: dsp_stuff.cpp:61-88 (narrow) / :91-117 (wide, -W)
+static const int16_t kNarrowTaps[20] = { -1087, -1082, -1065, -451, 912, 2997, 5556, 8157, 10285, 11484,
+					 11484, 10285, 8157, 5556, 2997, 912, -451, -1065, -1082, -1087 };
+static const int16_t kWideTaps[20] = { 546, 451, -317, -1844, -3198, -2817, 494, 6469, 13074, 17421,
+				       17421, 13074, 6469, 494, -2817, -3198, -1844, -317, 451, 546 };
+
+static StreamCfg device_cfg(const tfrec_amd_ctx *c, const tfrec_amd_stream_config &sc)
+{
+	StreamCfg d;
+	memset(&d, 0, sizeof(d));
+	for (int a = 0; a < c->launch.n_active; a++)
+		if (sc.types_mask & (1 << c->launch.params[a].sensor_type)) {
+			d.amask |= 1u << a;
+			d.wmax = std::max(d.wmax, (int32_t)c->launch.params[a].window);
+		}
+	d.thresh = sc.thresh ? sc.thresh : 500;
+	d.autoth = sc.thresh == 0;
+	d.wide = (uint16_t)sc.filter_type;
+	return d;
+}
+
+// ================================================================================ tfrec_amd_create, step by step
+static int validate(const tfrec_amd_config *cfg)
+{
+	if (cfg->n_streams < 1 || cfg->n_streams > 65535 || cfg->max_blocks < 1 || cfg->max_blocks > 4096 ||
+	    cfg->max_events < 1 || (cfg->types_mask & 0x2f) == 0 || (cfg->types_mask & ~0x2f) != 0 ||
+	    cfg->filter_type < 0 || cfg->filter_type > 1) {
+		snprintf(g_err, sizeof(g_err), "bad config");
+		return TFREC_AMD_E_INVAL;
+	}
+	if (cfg->thresh < 0) {
+		snprintf(g_err, sizeof(g_err), "thresh must be >= 0 (0 = the reference's auto mode)");
+		return TFREC_AMD_E_INVAL;
+	}
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+		snprintf(g_err, sizeof(g_err), "no HIP device available");
+		return TFREC_AMD_E_HIP;
+	}
+	if (cfg->device < 0 || cfg->device >= ndev)
+		return TFREC_AMD_E_INVAL;
+	return TFREC_AMD_OK;
+}
+
+// the parameters of a chain of protocol kind `kind` (0 TFA_1, 1 TFA_2 family, 2 WHB) at `baud`
+static int chain_params(ChainParams &p, int kind, double baud)
+{
+	if (kind == 0) {
+		p.window = 400;  // 40*BITPERIOD, tfa1.cpp:34, 148
+		p.spb = 10;
+		return TFREC_AMD_OK;
+	}
+	p.spb = (1536000 / 4.0) / baud;
+	if (kind == 1) {
+		p.window = d2i_host(16 * p.spb);  // tfa2.cpp:355
+		// multiplier form of numbits (ChainParams::nb_mul), accepted only if it reproduces the fp64 expression
+		// for every argument the slicer can form
+		const int hmax = (int)(16 * p.spb) + 2;
+		const uint64_t a0 = (uint64_t)((double)(1ull << 40) / p.spb);
+		for (uint64_t a_try : { a0, a0 + 1, a0 - 1 }) {
+			bool ok = true;
+			for (int h = 0; h <= hmax && ok; h++)
+				ok = tfa2_numbits_mul(2 * h, a_try) == (int)(((double)h + p.spb / 2) / p.spb);
+			if (ok) {
+				p.nb_mul = a_try;
+				break;
+			}
+		}
+		p.td_lo = (int)floor(p.spb / 4) + 1;
+		p.td_hi = (int)ceil(32 * p.spb) - 1;
+		p.iir = biquad_coef(0.5 / p.spb);  // tfa2.cpp:321
+		return TFREC_AMD_OK;
+	}
+	// whb_demod_kernel's candidate walk has the reference's 64 samples per bit (main.cpp:217) built in (chains2.hip: kWhbSpb)
+	if (p.spb != 64.0) {
+		snprintf(g_err, sizeof(g_err), "WHB chain with %.3f samples per bit: only 64 is built", p.spb);
+		return TFREC_AMD_E_INVAL;
+	}
+	p.window = d2i_host(8 * p.spb);         // whb.cpp:641
+	p.iir = biquad_coef(2.0 / p.spb);       // whb.cpp:610
+	p.iir_avg = biquad_coef(0.0025 / p.spb); // whb.cpp:611
+	return TFREC_AMD_OK;
+}
+
+// the chains of cfg->types_mask in registration order (types and samples-per-bit of main.cpp:173-218), their state arrays
+static int register_chains(tfrec_amd_ctx *c)
+{
+	static const struct {
+		int sensor_type, kind, min_bytes;
+		double baud;
+	} reg[kNSlots] = { { 0, 0, 10, 0 }, { 1, 1, 7, 17240 }, { 2, 1, 7, 9600 }, { 3, 1, 7, 8842 }, { 5, 2, 11, 6000 } };
+	const size_t n = (size_t)c->cfg.n_streams;
+	const std::vector<ChainState> init(n, chain_init_state());
+	for (int s = 0; s < kNSlots; s++) {
+		if (!(c->cfg.types_mask & (1 << reg[s].sensor_type)))
+			continue;
+		const int a = c->launch.n_active++;
+		c->launch.slot[a] = s;
+		ChainParams &p = c->launch.params[a];
+		memset(&p, 0, sizeof(p));
+		p.kind = reg[s].kind;
+		p.sensor_type = reg[s].sensor_type;
+		p.min_bytes = reg[s].min_bytes;
+		TRY(chain_params(p, p.kind, reg[s].baud));
+		TRY(own_device(c, c->launch.states[a], n * sizeof(ChainState)));
+		HIPCHK(hipMemcpy(c->launch.states[a], init.data(), n * sizeof(ChainState), hipMemcpyHostToDevice));
+		c->wmax = std::max(c->wmax, (int)p.window);
+	}
+	return TFREC_AMD_OK;
+}
+
+// the front end: its taps, outputs (one set per submit in flight), FIR history, the auto threshold and every stream's settings
+static int make_front_buffers(tfrec_amd_ctx *c)
+{
+	const tfrec_amd_config &cfg = c->cfg;
+	const size_t m_max = (size_t)cfg.max_blocks * kBlockDec;
+	const size_t n = (size_t)cfg.n_streams;
+	// second-stage taps (kNarrowTaps / kWideTaps), as h / 65536
+	for (int k = 0; k < 20; k++) {
+		c->taps.f2[k][0] = c->taps.f2[k][1] = (float)(cfg.filter_type ? kWideTaps[k] : kNarrowTaps[k]) / 65536.0f;
+		c->taps.w[k][0] = c->taps.w[k][1] = (float)kWideTaps[k] / 65536.0f;
+	}
+	c->taps.scfg = nullptr;
+	c->dec_stride = m_max;
+	c->mask_stride = m_max / 64;
+	for (int k = 0; k < kSets; k++) {
+		TRY(own_device(c, c->d_dec[k], n * c->dec_stride * sizeof(uint32_t) + 256));  // + slack: K3 loads whole 32-sample chunks at window tails
+		TRY(own_device(c, c->d_mask[k], n * c->mask_stride * sizeof(unsigned long long)));
+	}
+	// fm_demod.cpp:23-27: thresh 0 selects the adaptive mode starting at 500.  Every stream starts with the context's settings.
+	TRY(own_device(c, c->d_fsk, n * sizeof(FskState)));
+	TRY(own_device(c, c->d_scfg, n * sizeof(StreamCfg)));
+	const tfrec_amd_stream_config sc0 = { cfg.types_mask, cfg.thresh, cfg.filter_type, 0 };
+	c->scfg_api.assign(n, sc0);
+	c->scfg.assign(n, device_cfg(c, sc0));
+	c->n_auto = cfg.thresh == 0 ? (int)n : 0;
+	const std::vector<FskState> fsk(n, FskState{ c->scfg[0].thresh, 0, 0, -(1 << 28) });
+	HIPCHK(hipMemcpy(c->d_fsk, fsk.data(), n * sizeof(FskState), hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(c->d_scfg, c->scfg.data(), n * sizeof(StreamCfg), hipMemcpyHostToDevice));
+	for (int k = 0; k < kSets; k++) {
+		TRY(own_device(c, c->d_fmdev[k], n * m_max * sizeof(int16_t) + 256));  // + slack: K3 reads whole dwords past an odd tail
+		TRY(own_device(c, c->d_prevdec[k], n * sizeof(uint32_t)));
+	}
+	c->in10x = (cfg.flags & TFREC_AMD_F_INPUT_10X) != 0;
+	const size_t tail_bytes = c->in10x ? 2 * (size_t)kTailBytes : (size_t)kTailBytes;  // int16 history is twice as wide
+	// zero FIR history == u8 value 128 (decimate::decimate zeroes hist0, dsp_stuff.cpp:145-152); int16 history of the 10x
+	// path: zero, raw u8 history of its 10:1 stage: 128
+	for (int k = 0; k < 2; k++) {
+		TRY(own_device(c, c->d_tail[k], n * tail_bytes));
+		HIPCHK(hipMemset(c->d_tail[k], c->in10x ? 0 : 0x80, n * tail_bytes));
+	}
+	if (c->in10x) {
+		c->in16_stride = 4 * m_max;  // complex samples at 1.536 MS/s per stream and submit
+		for (int k = 0; k < kSets; k++) {
+			TRY(own_device(c, c->d_in16[k], n * c->in16_stride * sizeof(uint32_t)));
+			TRY(own_device(c, c->d_tail10[k], n * 112));
+		}
+		for (int k = 0; k < 2; k++)
+			HIPCHK(hipMemset(c->d_tail10[k], 0x80, n * 112));
+	}
+	return TFREC_AMD_OK;
+}
+
+// One set's window tables (chains2.hip): the rows and counters of every chain carved out of one block
+static int make_win_tables(tfrec_amd_ctx *c, int set)
+{
+	const size_t m_max = (size_t)c->cfg.max_blocks * kBlockDec;
+	const size_t n = (size_t)c->cfg.n_streams;
+	const size_t chains = (size_t)c->launch.n_active * n;
+	const bool whb = has_kind(c->launch, 2);
+	WinTables &T = c->win[set];
+	T.cap = (int32_t)(m_max / 356 + 2);  // windows of one chain are > W-1 >= 355 samples apart
+	T.slots = (int32_t)(m_max / 32 + (size_t)T.cap + 2);  // window-relative 32-sample slots per chain row
+	if ((size_t)T.slots > (size_t)kWhbRecOffMask) {  // WhbStepRec::meta packs a slot index into kWhbRecOffMask's bits
+		snprintf(g_err, sizeof(g_err), "max_blocks too large for the WHB step records");
+		return TFREC_AMD_E_INVAL;
+	}
+	// rows only for the chains that use them: ld16 for the TFA_2 family (its slots are adjacent in registration order),
+	// checkpoints for the chains with a biquad stage (all but TFA_1, which is registered first)
+	int a_ld0 = -1, n_ld = 0, a_ck0 = -1;
+	for (int a = 0; a < c->launch.n_active; a++) {
+		if (c->launch.params[a].kind == 1) {
+			if (a_ld0 < 0)
+				a_ld0 = a;
+			n_ld = a - a_ld0 + 1;
+		}
+		if (c->launch.params[a].kind != 0 && a_ck0 < 0)
+			a_ck0 = a;
+	}
+	T.ld_c0 = (int32_t)((a_ld0 < 0 ? 0 : a_ld0) * n);
+	T.ck_c0 = (int32_t)((a_ck0 < 0 ? 0 : a_ck0) * n);
+	const size_t ck_chains = a_ck0 < 0 ? 0 : chains - (size_t)a_ck0 * n;
+	TRY(own_device(c, c->d_ld16[set], std::max<size_t>(1, (size_t)n_ld * n) * (size_t)T.slots * 32 * sizeof(int16_t)));
+	if (whb)  // + slack: whb_demod_kernel keeps three 64-sample steps in flight past a row's last window (whb_demod.h)
+		TRY(own_device(c, c->d_dev32[set], n * (size_t)T.slots * 32 * sizeof(int32_t) + 4096));
+	T.bit_words = (int32_t)(m_max / 64 + 3 * (size_t)T.cap + 8);
+	const size_t wins = chains * (size_t)T.cap;
+	size_t off = 0;
+	auto carve = [&](size_t bytes) {
+		const size_t o = off;
+		off += (bytes + 255) & ~(size_t)255;
+		return o;
+	};
+	const size_t o_count = carve(chains * 4), o_cont = carve(chains * 4), o_tnext = carve(chains * 4);
+	const size_t o_open = carve(wins * 4), o_close = carve(wins * 4), o_res = carve(wins * sizeof(WinResult));
+	const size_t o_dcd = carve(wins * sizeof(WinDecode)), o_wst = carve(whb ? n * (size_t)T.cap * sizeof(WhbStart) : 0);
+	const size_t o_bits = carve(chains * (size_t)T.bit_words * 4), o_items = carve((kNQueues * wins + chains) * sizeof(uint2));
+	const size_t o_queue = carve((kNQueues + 1) * sizeof(WorkQueue)), o_stats = carve(128);
+	T.segcap = (int32_t)((m_max / 32 + (size_t)T.cap) / kSegSlots + 2);
+	const size_t segs = chains * (size_t)T.segcap;
+	const size_t o_ckpt = carve(ck_chains * (size_t)T.slots * sizeof(double2));
+	const size_t o_sstart = carve(segs * sizeof(uint2)), o_vtotal = carve(chains * 4);
+	const size_t o_se1 = carve(segs * sizeof(BiquadEnd)), o_se2 = carve(segs * sizeof(BiquadEnd)), o_sfix = carve(segs * 4);
+	const size_t o_se3 = carve(segs * sizeof(BiquadEnd)), o_sfix2 = carve(segs * 4);
+	const size_t o_cand = carve(n * (size_t)T.slots * 4), o_mark = carve(n * (size_t)T.slots * sizeof(MarkPiece));
+	T.whbrec_stride = (int32_t)(m_max / 64 + 2 * (size_t)T.cap + 2 + kWhbRecSlack);
+	const size_t o_wrec = carve(whb ? n * (size_t)T.whbrec_stride * sizeof(WhbStepRec) : 0), o_wfail = carve(whb ? n * 4 : 0);
+	const size_t o_wsnap = carve(whb ? n * sizeof(ChainState) : 0), o_wx0 = carve(whb ? n * sizeof(WhbExact) : 0);
+	const size_t o_wseen = carve(whb ? n * 4 : 0);
+	T.whbdense_stride = (int32_t)(m_max + 64);
+	T.whbx_stride = (int32_t)(m_max / 64 + 2);
+	const size_t o_wdn = carve(whb ? n * 4 : 0), o_wxb = carve(whb ? n * (size_t)T.whbx_stride * 8 : 0);
+	const size_t o_wxs = carve(whb ? n * (size_t)T.whbx_stride * sizeof(double2) : 0);
+	const size_t o_wdense = carve(whb ? n * (size_t)T.whbdense_stride * 4 : 0);
+	TRY(own_device(c, c->win_block[set], off));
+	uint8_t *b = (uint8_t *)c->win_block[set];
+	T.count = (int32_t *)(b + o_count);
+	T.cont = (int32_t *)(b + o_cont);
+	T.timeout_next = (int32_t *)(b + o_tnext);
+	T.open = (int32_t *)(b + o_open);
+	T.close = (int32_t *)(b + o_close);
+	T.result = (WinResult *)(b + o_res);
+	T.decode = (WinDecode *)(b + o_dcd);
+	T.whbstart = (WhbStart *)(b + o_wst);
+	T.bits = (uint32_t *)(b + o_bits);
+	T.items = (uint2 *)(b + o_items);
+	T.queue = (WorkQueue *)(b + o_queue);
+	T.overflow = nullptr;  // lives in the set's event block (kEvOverflowOff): make_event_blocks, reset by every submit
+	T.stats = (unsigned long long *)(b + o_stats);
+	T.ckpt = (double2 *)(b + o_ckpt);
+	T.segstart = (uint2 *)(b + o_sstart);
+	T.vtotal = (int32_t *)(b + o_vtotal);
+	T.segend1 = (BiquadEnd *)(b + o_se1);
+	T.segend2 = (BiquadEnd *)(b + o_se2);
+	T.segfix = (int32_t *)(b + o_sfix);
+	T.segend3 = (BiquadEnd *)(b + o_se3);
+	T.segfix2 = (int32_t *)(b + o_sfix2);
+	T.cand = (uint32_t *)(b + o_cand);
+	T.mark = (MarkPiece *)(b + o_mark);
+	T.whbrec = (WhbStepRec *)(b + o_wrec);
+	T.whbfail = (int32_t *)(b + o_wfail);
+	T.whbsnap = (ChainState *)(b + o_wsnap);
+	T.whbx0 = (WhbExact *)(b + o_wx0);
+	T.whbseen = (uint32_t *)(b + o_wseen);
+	T.whbdense = (int32_t *)(b + o_wdense);
+	T.whbdense_n = (int32_t *)(b + o_wdn);
+	T.whbxbits = (unsigned long long *)(b + o_wxb);
+	T.whbxsnap = (double2 *)(b + o_wxs);
+	T.whbgen = c->d_whbgen;
+	T.whbX = c->d_whbX;
+	T.whbscr = c->d_whbscr;
+	T.whbpub = nullptr;
+	T.whb_test_perturb = c->whb_test_perturb;
+	T.tfa1_vec = TFREC_KNOB_INT("TFA1_VEC", 1, 0, 1) != 0;
+	T.tfa2_vec = TFREC_KNOB_INT("TFA2_VEC", 1, 0, 1) != 0;
+	T.whb_force_fail = c->whb_force_fail;
+	T.whbx = c->d_whbx;
+	T.timeout_carry = c->d_tcarry;
+	T.prevdec = c->d_prevdec[set];
+	HIPCHK(hipMemset(T.queue, 0, (kNQueues + 1) * sizeof(WorkQueue)));
+	HIPCHK(hipMemset(T.stats, 0, 128));
+	return TFREC_AMD_OK;
+}
+
+// the window-parallel pipeline's carried state (the window scan's timeout carry, the WHB check's) and every set's window tables
+static int make_window_state(tfrec_amd_ctx *c)
+{
+	const size_t n = (size_t)c->cfg.n_streams;
+	const size_t chains = (size_t)c->launch.n_active * n;
+	TRY(own_device(c, c->d_tcarry, chains * 4));
+	HIPCHK(hipMemset(c->d_tcarry, 0, chains * 4));
+	if (has_kind(c->launch, 2)) {  // iir_avg starts from zero like every iir2 (dsp_stuff.cpp:28-34)
+		TRY(own_device(c, c->d_whbx, n * sizeof(WhbExact)));
+		TRY(own_device(c, c->d_whbcarry, n * sizeof(int)));
+		TRY(own_device(c, c->d_whbgen, n * sizeof(uint32_t)));
+		TRY(own_device(c, c->d_whbX, n * sizeof(ChainState)));
+		TRY(own_device(c, c->d_whbscr, n * sizeof(ChainState)));
+		HIPCHK(hipMemset(c->d_whbgen, 0, n * sizeof(uint32_t)));
+		HIPCHK(hipMemset(c->d_whbx, 0, n * sizeof(WhbExact)));
+		HIPCHK(hipMemset(c->d_whbcarry, 0, n * sizeof(int)));
+		// TEST hooks (results stay exact under both: the check's tolerance and the ambiguity rule widen with D, and a forced
+		// failure is only a redo) -- clamped, and never silent: a stray variable changes the redo rate, i.e. the speed
+		if (const char *tp = TFREC_KNOB_STR("WHB_TEST_PERTURB"))
+			c->whb_test_perturb = std::max(-1000000, std::min(1000000, atoi(tp)));
+		if (const char *ff = TFREC_KNOB_STR("WHB_FORCE_FAIL"))
+			c->whb_force_fail = std::max(0, atoi(ff));
+#if TFREC_KNOBS_BUILT
+		if (c->whb_test_perturb || c->whb_force_fail)
+			fprintf(stderr, "tfrec_amd: TEST hook active (TFREC_AMD_WHB_TEST_PERTURB=%d, TFREC_AMD_WHB_FORCE_FAIL=%d): WHB streams are "
+					"redone on purpose, results unchanged, throughput lower\n", c->whb_test_perturb, c->whb_force_fail);
+#endif
+		HIPCHK(whb_chain_lds_optin());  // (a per-device attribute: this context's device is the current one)
+	}
+	for (int set = 0; set < kSets; set++)
+		TRY(make_win_tables(c, set));
+	return TFREC_AMD_OK;
+}
+
+// One event block per set: [EventBuf | the window tables' overflow flag, 16 B | pad to 256 | events] on the device and a
+// page-locked copy (the drain's device-to-host copy of a submit is ONE copy on the stream that sets the batch period: three
+// copies were 0.45 ms of it with their gaps); the fresh header every submit starts from; the reset lists
+static int make_event_blocks(tfrec_amd_ctx *c)
+{
+	const size_t n = (size_t)c->cfg.n_streams;
+	const size_t block = kEvHeader + (size_t)c->cfg.max_events * sizeof(tfrec_amd_event);
+	EventBuf eb;
+	memset(&eb, 0, sizeof(eb));
+	eb.capacity = (uint32_t)c->cfg.max_events;
+	for (int k = 0; k < kSets; k++) {
+		TRY(own_device(c, c->d_evblock[k], block));
+		c->d_eb[k] = (EventBuf *)c->d_evblock[k];
+		c->d_events[k] = (tfrec_amd_event *)(c->d_evblock[k] + kEvHeader);
+		if (c->win[k].count)  // (window-parallel pipeline: its overflow flag lives behind the EventBuf)
+			c->win[k].overflow = (int32_t *)(c->d_evblock[k] + kEvOverflowOff);
+		HIPCHK(hipMemset(c->d_evblock[k], 0, kEvHeader));
+		HIPCHK(hipMemcpy(c->d_eb[k], &eb, sizeof(eb), hipMemcpyHostToDevice));
+	}
+	TRY(own_device(c, c->d_eb_fresh, kEvFreshBytes));
+	HIPCHK(hipMemset(c->d_eb_fresh, 0, kEvFreshBytes));
+	HIPCHK(hipMemcpy(c->d_eb_fresh, &eb, sizeof(eb), hipMemcpyHostToDevice));
+	// tfrec_amd_reset_streams: a list of at most n_streams indices per set, and the constructor state it restores
+	TRY(own_device(c, c->d_chain_init, sizeof(ChainState)));
+	const ChainState init = chain_init_state();
+	HIPCHK(hipMemcpy(c->d_chain_init, &init, sizeof(init), hipMemcpyHostToDevice));
+	for (int k = 0; k < kSets; k++) {
+		TRY(own_device(c, c->d_reset[k], n * sizeof(int32_t)));
+		TRY(own_device(c, c->d_rcfg[k], n * sizeof(StreamCfg)));
+	}
+	for (int k = 0; k < kSets; k++) {
+		TRY(own_pinned(c, c->h_evblock[k], block));
+		HIPCHK(hipHostGetDevicePointer((void **)&c->h_evblock_dev[k], c->h_evblock[k], 0));
+		c->h_eb[k] = (EventBuf *)c->h_evblock[k];
+		c->h_events[k] = (tfrec_amd_event *)(c->h_evblock[k] + kEvHeader);
+		TRY(own_pinned(c, c->h_reset[k], n * sizeof(int32_t)));
+		TRY(own_pinned(c, c->h_rcfg[k], n * sizeof(StreamCfg)));
+	}
+	c->reset_marked.assign(n, 0);
+	c->origin.assign(n, 0);
+	return TFREC_AMD_OK;
+}
+
+// The stream layout: which streams exist, at which priority, and which are aliases -- into S (every set's PipeCtl starts
+// from it) and c->cpy.
+//   serial (TFREC_AMD_F_SERIAL_CHAINS): fs, cs, and cp for the drain's copies.
+//   shallow (TFREC_AMD_DEEP=0): + t1, aux; the biquad stages and the WHB check are aliases (k2 = cs, kw = aux, vx = aux).
+//   deep (the default): + k2, kw of their own, fq and ks (discriminator and speculative pass) when a WHB and a TFA_2-family
+//     chain are registered, cq for the drain's copies; the window scan runs at the head of kw (ws) and the WHB check on cp
+//     (vx).  Stage A of submit k+1 runs beside stage B of submit k.
+// Why (measured):
+// - HIP multiplexes the streams of one priority onto GPU_MAX_HW_QUEUES hardware queues (default 4), and two streams that
+//   share a queue serialise (profiles/ubench/queues.hip).  The runtime keeps one pool of hardware queues PER PRIORITY:
+//   fs / cs / aux / t1 are the high-priority streams, and cp (with k2 / kw in the deep layout) has normal priority -- no pool
+//   holds more than four streams, whatever GPU_MAX_HW_QUEUES is.
+// - Every pipeline stream except the biquad stages runs at high priority.  With the front end at low priority ("fill what
+//   the latency-bound chains leave free") its kernel stretched from 3 to 11 ms beside the chains and, with three submits in
+//   flight, became the longest stage of all: 13.4 ms per batch instead of 11.7.  (The biquad stages and cp run at normal
+//   priority, 0; the discriminator pass, the TFA_2 family's speculative pass and the drain's copies, when they have streams
+//   of their own, at low priority.)
+// - The window scan at the head of kw, not behind the front end: the front-end stream is the busiest of all (0.3-1.1 ms less
+//   on it per batch).
+// - The discriminator pass moves from the front-end stream into the pipeline (the head of the TFA_2-family biquad stage, or
+//   fq) when a WHB demodulator is registered: then the WHB chain is the longest and the front-end stream the busiest
+//   (measured 12.2 -> 11.8 ms per batch; without WHB the TFA_2 chain is the longest and the move costs 7.7 -> 8.5 ms).
+// - fq: the discriminator pass on a LOW-priority stream of its own.  It needs the front end only, not the window scan; at the
+//   head of k2 it made that stream (discriminator + five biquad kernels) the one that set the batch period: 6.98 -> 6.60 ms
+//   per batch over 100 steps (profiles/r04_ab_fmdev_stream.txt).  The low-priority pool's hardware queues are otherwise
+//   unused, so the stream shares none (a fifth normal-priority stream would).
+// - ks: the speculative biquad pass of the TFA_2 family on a low-priority stream of its own (when the discriminator pass has
+//   its stream): it needs nothing of the submit before (chains2.hip K3a), so it runs beside that submit's repair passes and
+//   chain walk on k2.  The third stream of the low-priority pool (with fq and cq): no shared hardware queue.
+// - cq: the drain's copies must not queue behind the work of younger submits, so they need a hardware queue of their own.
+//   On cp they sat between the WHB checks of consecutive submits and waited for ALL chains of their submit: the check of
+//   submit k + 1 could not start before the TFA chains of submit k had ended.  6.32 -> 6.21 ms per batch over
+//   100 steps (profiles/r04_ab_copy_stream.txt); the low pool's hardware queues hold only this stream and the
+//   discriminator's.
+// - vx = cp: the WHB check (whb_chain_kernel, whb_check_kernel, the redo) runs where the drain's copies were until they
+//   moved to cq.  A stream of its own would be the FIFTH of normal priority in the process (k2, kw, cp and the caller's): it
+//   shared a hardware queue with kw, and the 6 ms verification of submit k held up the WHB biquads of submit k + 2.
+static int make_streams(tfrec_amd_ctx *c, PipeCtl &S)
+{
+	int prio_lo = 0, prio_hi = 0;
+	(void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+	hipStream_t cp = nullptr;
+	TRY(own_stream(c, S.fs, prio_hi));
+	TRY(own_stream(c, cp, 0));
+	TRY(own_stream(c, S.cs, prio_hi));
+	S.ws = S.fs;
+	c->cpy = cp;
+	if (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS)
+		return TFREC_AMD_OK;
+	TRY(own_stream(c, S.t1, prio_hi));
+	TRY(own_stream(c, S.aux, prio_hi));
+	const char *dp = TFREC_KNOB_STR("DEEP");
+	c->deep = dp ? atoi(dp) != 0 : true;
+	c->fmdev_k2 = has_kind(c->launch, 1) && has_kind(c->launch, 2);
+	S.k2 = S.cs;
+	S.kw = S.aux;
+	S.vx = S.aux;
+	if (!c->deep)
+		return TFREC_AMD_OK;
+	TRY(own_stream(c, S.k2, 0));
+	TRY(own_stream(c, S.kw, 0));
+	S.ws = S.kw;
+	if (c->fmdev_k2) {
+		TRY(own_stream(c, S.fq, prio_lo));
+		TRY(own_stream(c, S.ks, prio_lo));
+	}
+	TRY(own_stream(c, c->cpy, prio_lo));
+	S.vx = cp;
+	return TFREC_AMD_OK;
+}
+
+// every set's PipeCtl (the layout's streams, the set's events and buffers) and the set's other events
+static int make_pipes(tfrec_amd_ctx *c, const PipeCtl &S)
+{
+	const bool serial = (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) != 0;
+	const bool timing = (c->cfg.flags & TFREC_AMD_F_TIMING) != 0;
+	for (int k = 0; k < kSets; k++) {
+		PipeCtl &P = c->pipe[k];
+		P = S;
+		for (hipEvent_t *e : { &P.done[0], &P.done[1], &P.done[2], &P.ev_win, &P.ev_fork, &P.ev_k2, &P.ev_kw, &P.ev_fm,
+				       &P.ev_spec, &c->ev_in[k], &P.ev_front, &c->copied[k] })
+			TRY(own_event(c, *e, hipEventDisableTiming));
+		if (!serial)
+			TRY(own_event(c, P.ev_aux, hipEventDisableTiming));
+		if (timing) {
+			for (hipEvent_t &e : c->ev[k])
+				TRY(own_event(c, e, hipEventDefault));
+			if (!serial) {
+				for (hipEvent_t &e : c->tev[k])
+					TRY(own_event(c, e, hipEventDefault));
+				P.tev = c->tev[k];
+			}
+		}
+		P.whb_carry = c->d_whbcarry;
+		P.fmdev_wmax = c->fmdev_k2 ? c->wmax : 0;
+		P.fm_flag_eps = c->fm_flag_eps;
+		P.fmdev_out = c->d_fmdev[k];
+		P.prevdec = c->d_prevdec[k];
+	}
+	return TFREC_AMD_OK;
+}
+
+static int init_context(tfrec_amd_ctx *c)
+{
+	if (const char *fe = TFREC_KNOB_STR("FM_FLAG_EPS"))
+		c->fm_flag_eps = std::max(1e-9, atof(fe));
+	if (const char *cg = TFREC_KNOB_STR("COPY_GUESS_MIN"))
+		c->copy_guess = c->copy_guess_min = (uint32_t)std::max(1, atoi(cg));
+	TRY(register_chains(c));
+	TRY(make_front_buffers(c));
+	if (!(c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS))
+		TRY(make_window_state(c));
+	TRY(make_event_blocks(c));
+	PipeCtl streams = {};
+	TRY(make_streams(c, streams));
+	TRY(make_pipes(c, streams));
+	return TFREC_AMD_OK;
+}
+
+static void print_host_prof(const tfrec_amd_ctx *c)
+{
+	if (TFREC_KNOB_STR("HOST_PROF") && c->hp_n)
+		fprintf(stderr, "tfrec_amd host time per batch: submit %.0f us, drain: wait %.0f + copy %.0f + sort %.0f us (%ld batches)\n",
+			1e6 * c->hp_submit / c->hp_n, 1e6 * c->hp_wait / c->hp_n, 1e6 * c->hp_copy / c->hp_n, 1e6 * c->hp_sort / c->hp_n,
+			c->hp_n);
+	if (TFREC_KNOB_STR("HOST_PROF") && c->hp_gap_n)
+		fprintf(stderr, "tfrec_amd front-end stream: %.3f ms between one submit's front end and the next one's; front-end start -> TFA_1 chain end %.2f ms; front-end start to start %.3f ms (%ld batches)\n",
+			c->hp_gap / c->hp_gap_n, c->hp_lat / c->hp_gap_n, c->hp_s2s / c->hp_gap_n, c->hp_gap_n);
+}
+
 extern "C" {
 
 const char *tfrec_amd_version(void) { return "tfrec_amd 0.1 (gfx950)"; }
@@ -366,128 +952,12 @@ int tfrec_amd_destroy(tfrec_amd_ctx *c)
 {
 	if (!c)
 		return TFREC_AMD_OK;
-	if (TFREC_KNOB_STR("HOST_PROF") && c->hp_n)
-		fprintf(stderr, "tfrec_amd host time per batch: submit %.0f us, drain: wait %.0f + copy %.0f + sort %.0f us (%ld batches)\n",
-			1e6 * c->hp_submit / c->hp_n, 1e6 * c->hp_wait / c->hp_n, 1e6 * c->hp_copy / c->hp_n, 1e6 * c->hp_sort / c->hp_n,
-			c->hp_n);
-	if (TFREC_KNOB_STR("HOST_PROF") && c->hp_gap_n)
-		fprintf(stderr, "tfrec_amd front-end stream: %.3f ms between one submit's front end and the next one's; front-end start -> TFA_1 chain end %.2f ms; front-end start to start %.3f ms (%ld batches)\n",
-			c->hp_gap / c->hp_gap_n, c->hp_lat / c->hp_gap_n, c->hp_s2s / c->hp_gap_n, c->hp_gap_n);
 	(void)hipSetDevice(c->cfg.device);
 	(void)hipDeviceSynchronize();
-	for (int a = 0; a < kNSlots; a++)
-		if (c->launch.states[a])
-			(void)hipFree(c->launch.states[a]);
-	for (int k = 0; k < kSets; k++) {
-		(void)hipFree(c->d_dec[k]);
-		(void)hipFree(c->d_mask[k]);
-		(void)hipFree(c->d_fmdev[k]);
-		(void)hipFree(c->d_prevdec[k]);
-		if (c->ev_in[k])
-			(void)hipEventDestroy(c->ev_in[k]);
-		if (c->ev_front[k])
-			(void)hipEventDestroy(c->ev_front[k]);
-	}
-	if (c->fs)
-		(void)hipStreamDestroy(c->fs);
-	if (c->cp)
-		(void)hipStreamDestroy(c->cp);
-	if (c->cs)
-		(void)hipStreamDestroy(c->cs);
-	for (int k = 0; k < kSets; k++) {
-		(void)hipFree(c->d_ld16[k]);
-		(void)hipFree(c->d_dev32[k]);
-		(void)hipFree(c->win_block[k]);
-		for (auto &e : c->ev_pipe[k])
-			if (e)
-				(void)hipEventDestroy(e);
-	}
-	(void)hipFree(c->d_tcarry);
-	if (c->fq)
-		(void)hipStreamDestroy(c->fq);
-	if (c->ks)
-		(void)hipStreamDestroy(c->ks);
-	if (c->cq)
-		(void)hipStreamDestroy(c->cq);
-	(void)hipFree(c->d_whbx);
-	(void)hipFree(c->d_whbcarry);
-	(void)hipFree(c->d_whbgen);
-	(void)hipFree(c->d_whbX);
-	(void)hipFree(c->d_whbscr);
-	for (auto &e : c->ev_aux)
-		if (e)
-			(void)hipEventDestroy(e);
-	if (c->deep && c->k2)
-		(void)hipStreamDestroy(c->k2);
-	if (c->deep && c->kw)
-		(void)hipStreamDestroy(c->kw);
-	(void)hipFree(c->d_fsk);
-	(void)hipFree(c->d_tail[0]);
-	(void)hipFree(c->d_tail[1]);
-	for (int k = 0; k < kSets; k++) {
-		(void)hipFree(c->d_in16[k]);
-		(void)hipFree(c->d_tail10[k]);
-	}
-	for (int k = 0; k < kSets; k++) {
-		(void)hipFree(c->d_evblock[k]);
-		for (auto &e : c->done[k])
-			if (e)
-				(void)hipEventDestroy(e);
-		for (auto &e : c->ev[k])
-			if (e)
-				(void)hipEventDestroy(e);
-		for (auto &e : c->tev[k])
-			if (e)
-				(void)hipEventDestroy(e);
-	}
-	(void)hipFree(c->d_eb_fresh);
-	(void)hipFree(c->d_chain_init);
-	(void)hipFree(c->d_scfg);
-	for (int k = 0; k < kSets; k++) {
-		(void)hipFree(c->d_reset[k]);
-		(void)hipFree(c->d_rcfg[k]);
-		if (c->h_reset[k])
-			(void)hipHostFree(c->h_reset[k]);
-		if (c->h_rcfg[k])
-			(void)hipHostFree(c->h_rcfg[k]);
-	}
-	for (int k = 0; k < kSets; k++) {
-		if (c->h_evblock[k])
-			(void)hipHostFree(c->h_evblock[k]);
-		if (c->copied[k])
-			(void)hipEventDestroy(c->copied[k]);
-	}
-	for (auto &p : c->d_stage)
-		(void)hipFree(p);
-	if (c->aux)
-		(void)hipStreamDestroy(c->aux);
-	if (c->t1)
-		(void)hipStreamDestroy(c->t1);
+	print_host_prof(c);
+	release_all(c);
 	delete c;
 	return TFREC_AMD_OK;
-}
-
-// A stream's settings as the kernels read them: the active slots (launch order) of its types, its threshold (auto: 500, where
-// its FskState starts), its longest window, its taps
-// second-stage taps: dsp_stuff.cpp:61-88 (narrow) / :91-117 (wide, -W)
-static const int16_t kNarrowTaps[20] = { -1087, -1082, -1065, -451, 912, 2997, 5556, 8157, 10285, 11484,
-					 11484, 10285, 8157, 5556, 2997, 912, -451, -1065, -1082, -1087 };
-static const int16_t kWideTaps[20] = { 546, 451, -317, -1844, -3198, -2817, 494, 6469, 13074, 17421,
-				       17421, 13074, 6469, 494, -2817, -3198, -1844, -317, 451, 546 };
-
-static StreamCfg device_cfg(const tfrec_amd_ctx *c, const tfrec_amd_stream_config &sc)
-{
-	StreamCfg d;
-	memset(&d, 0, sizeof(d));
-	for (int a = 0; a < c->launch.n_active; a++)
-		if (sc.types_mask & (1 << c->launch.params[a].sensor_type)) {
-			d.amask |= 1u << a;
-			d.wmax = std::max(d.wmax, (int32_t)c->launch.params[a].window);
-		}
-	d.thresh = sc.thresh ? sc.thresh : 500;
-	d.autoth = sc.thresh == 0;
-	d.wide = (uint16_t)sc.filter_type;
-	return d;
 }
 
 int tfrec_amd_create(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
@@ -495,442 +965,13 @@ int tfrec_amd_create(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
 	if (!cfg || !out)
 		return TFREC_AMD_E_INVAL;
 	*out = nullptr;
-	if (cfg->n_streams < 1 || cfg->n_streams > 65535 || cfg->max_blocks < 1 || cfg->max_blocks > 4096 ||
-	    cfg->max_events < 1 || (cfg->types_mask & 0x2f) == 0 || (cfg->types_mask & ~0x2f) != 0 ||
-	    cfg->filter_type < 0 || cfg->filter_type > 1) {
-		snprintf(g_err, sizeof(g_err), "bad config");
-		return TFREC_AMD_E_INVAL;
-	}
-	if (cfg->thresh < 0) {
-		snprintf(g_err, sizeof(g_err), "thresh must be >= 0 (0 = the reference's auto mode)");
-		return TFREC_AMD_E_INVAL;
-	}
-	int ndev = 0;
-	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-		snprintf(g_err, sizeof(g_err), "no HIP device available");
-		return TFREC_AMD_E_HIP;
-	}
-	if (cfg->device < 0 || cfg->device >= ndev)
-		return TFREC_AMD_E_INVAL;
+	TRY(validate(cfg));
 	HIPCHK(hipSetDevice(cfg->device));
-
 	tfrec_amd_ctx *c = new (std::nothrow) tfrec_amd_ctx();
 	if (!c)
 		return TFREC_AMD_E_NOMEM;
 	c->cfg = *cfg;
-	if (const char *fe = TFREC_KNOB_STR("FM_FLAG_EPS"))
-		c->fm_flag_eps = std::max(1e-9, atof(fe));
-	if (const char *cg = TFREC_KNOB_STR("COPY_GUESS_MIN"))
-		c->copy_guess = c->copy_guess_min = (uint32_t)std::max(1, atoi(cg));
-	memset(&c->launch, 0, sizeof(c->launch));
-	memset(&c->win, 0, sizeof(c->win));
-
-	// second-stage taps (kNarrowTaps / kWideTaps), as h / 65536
-	for (int n = 0; n < 20; n++) {
-		c->taps.f2[n][0] = c->taps.f2[n][1] = (float)(cfg->filter_type ? kWideTaps[n] : kNarrowTaps[n]) / 65536.0f;
-		c->taps.w[n][0] = c->taps.w[n][1] = (float)kWideTaps[n] / 65536.0f;
-	}
-	c->taps.scfg = nullptr;
-
-	// registration order, types and samples-per-bit of main.cpp:173-218
-	static const struct {
-		int sensor_type, kind, min_bytes;
-		double baud;
-	} reg[kNSlots] = { { 0, 0, 10, 0 }, { 1, 1, 7, 17240 }, { 2, 1, 7, 9600 }, { 3, 1, 7, 8842 }, { 5, 2, 11, 6000 } };
-	const size_t m_max = (size_t)cfg->max_blocks * kBlockDec;
-	const size_t n = (size_t)cfg->n_streams;
-	int rc = TFREC_AMD_OK;
-#define ALLOC(ptr, bytes)                                                     \
-	do {                                                                  \
-		if (rc == TFREC_AMD_OK && hipMalloc((void **)&(ptr), (bytes)) != hipSuccess) { \
-			snprintf(g_err, sizeof(g_err), "hipMalloc(%zu) failed", (size_t)(bytes)); \
-			rc = TFREC_AMD_E_NOMEM;                               \
-		} else if (rc == TFREC_AMD_OK) {                              \
-			c->dev_bytes += (size_t)(bytes);                      \
-		}                                                             \
-	} while (0)
-	for (int s = 0; s < kNSlots && rc == TFREC_AMD_OK; s++) {
-		if (!(cfg->types_mask & (1 << reg[s].sensor_type)))
-			continue;
-		const int a = c->launch.n_active++;
-		c->launch.slot[a] = s;
-		ChainParams &p = c->launch.params[a];
-		memset(&p, 0, sizeof(p));
-		p.kind = reg[s].kind;
-		p.sensor_type = reg[s].sensor_type;
-		p.min_bytes = reg[s].min_bytes;
-		if (p.kind == 0) {
-			p.window = 400;  // 40*BITPERIOD, tfa1.cpp:34, 148
-			p.spb = 10;
-		} else {
-			p.spb = (1536000 / 4.0) / reg[s].baud;
-			if (p.kind == 1) {
-				p.window = d2i_host(16 * p.spb);  // tfa2.cpp:355
-				// multiplier form of numbits (ChainParams::nb_mul), accepted only if it reproduces the fp64 expression
-				// for every argument the slicer can form
-				const int hmax = (int)(16 * p.spb) + 2;
-				const uint64_t a0 = (uint64_t)((double)(1ull << 40) / p.spb);
-				for (uint64_t a_try : { a0, a0 + 1, a0 - 1 }) {
-					bool ok = true;
-					for (int h = 0; h <= hmax && ok; h++)
-						ok = tfa2_numbits_mul(2 * h, a_try) == (int)(((double)h + p.spb / 2) / p.spb);
-					if (ok) {
-						p.nb_mul = a_try;
-						break;
-					}
-				}
-				p.td_lo = (int)floor(p.spb / 4) + 1;
-				p.td_hi = (int)ceil(32 * p.spb) - 1;
-				p.iir = biquad_coef(0.5 / p.spb);  // tfa2.cpp:321
-			} else {
-				// whb_demod_kernel's candidate walk has the reference's 64 samples per bit (main.cpp:217) built in (chains2.hip: kWhbSpb)
-				if (p.spb != 64.0) {
-					snprintf(g_err, sizeof(g_err), "WHB chain with %.3f samples per bit: only 64 is built", p.spb);
-					rc = TFREC_AMD_E_INVAL;
-					break;
-				}
-				p.window = d2i_host(8 * p.spb);         // whb.cpp:641
-				p.iir = biquad_coef(2.0 / p.spb);       // whb.cpp:610
-				p.iir_avg = biquad_coef(0.0025 / p.spb); // whb.cpp:611
-			}
-		}
-		ALLOC(c->launch.states[a], n * sizeof(ChainState));
-		if (rc != TFREC_AMD_OK)
-			break;
-		// constructor state: tfa1.cpp:136-141, tfa2.cpp:316-334, whb.cpp:605-623, decoders :36-45/:54-62/:77-107
-		std::vector<ChainState> init(n);
-		memset(init.data(), 0, n * sizeof(ChainState));
-		for (auto &st : init) {
-			st.sr_cnt = -1;
-			st.dmin = 32767;
-			st.dmax = -32767;
-		}
-		if (hipMemcpy(c->launch.states[a], init.data(), n * sizeof(ChainState), hipMemcpyHostToDevice) != hipSuccess)
-			rc = TFREC_AMD_E_HIP;
-	}
-	c->dec_stride = m_max;
-	c->mask_stride = m_max / 64;
-	for (int k = 0; k < kSets; k++) {
-		ALLOC(c->d_dec[k], n * c->dec_stride * sizeof(uint32_t) + 256);  // + slack: K3 loads whole 32-sample chunks at window tails
-		ALLOC(c->d_mask[k], n * c->mask_stride * sizeof(unsigned long long));
-	}
-	for (int a = 0; a < c->launch.n_active; a++)
-		c->wmax = std::max(c->wmax, (int)c->launch.params[a].window);
-	// fm_demod.cpp:23-27: thresh 0 selects the adaptive mode starting at 500.  Every stream starts with the context's settings.
-	ALLOC(c->d_fsk, n * sizeof(FskState));
-	ALLOC(c->d_scfg, n * sizeof(StreamCfg));
-	if (rc == TFREC_AMD_OK) {
-		const tfrec_amd_stream_config sc0 = { cfg->types_mask, cfg->thresh, cfg->filter_type, 0 };
-		c->scfg_api.assign(n, sc0);
-		c->scfg.assign(n, device_cfg(c, sc0));
-		c->n_auto = cfg->thresh == 0 ? (int)n : 0;
-		std::vector<FskState> init(n, FskState{ c->scfg[0].thresh, 0, 0, -(1 << 28) });
-		if (hipMemcpy(c->d_fsk, init.data(), n * sizeof(FskState), hipMemcpyHostToDevice) != hipSuccess ||
-		    hipMemcpy(c->d_scfg, c->scfg.data(), n * sizeof(StreamCfg), hipMemcpyHostToDevice) != hipSuccess)
-			rc = TFREC_AMD_E_HIP;
-	}
-	for (int k = 0; k < kSets; k++) {
-		ALLOC(c->d_fmdev[k], n * m_max * sizeof(int16_t) + 256);  // + slack: K3 reads whole dwords past an odd tail
-		ALLOC(c->d_prevdec[k], n * sizeof(uint32_t));
-	}
-	for (int a = 0; a < c->launch.n_active; a++)
-		c->need_fmdev = c->need_fmdev || c->launch.params[a].kind == 1;
-	if (!(cfg->flags & TFREC_AMD_F_SERIAL_CHAINS)) {
-		// window-parallel pipeline buffers (chains2.hip)
-		const size_t chains = (size_t)c->launch.n_active * n;
-		bool whb = false;
-		for (int a = 0; a < c->launch.n_active; a++)
-			whb = whb || c->launch.params[a].kind == 2;
-		ALLOC(c->d_tcarry, chains * 4);
-		if (rc == TFREC_AMD_OK && hipMemset(c->d_tcarry, 0, chains * 4) != hipSuccess)
-			rc = TFREC_AMD_E_HIP;
-		if (whb) {  // iir_avg starts from zero like every iir2 (dsp_stuff.cpp:28-34)
-			ALLOC(c->d_whbx, n * sizeof(WhbExact));
-			ALLOC(c->d_whbcarry, n * sizeof(int));
-			ALLOC(c->d_whbgen, n * sizeof(uint32_t));
-			ALLOC(c->d_whbX, n * sizeof(ChainState));
-			ALLOC(c->d_whbscr, n * sizeof(ChainState));
-			// TEST hooks (results stay exact under both: the check's tolerance and the ambiguity rule widen with D, and a forced
-			// failure is only a redo) -- clamped, and never silent: a stray variable changes the redo rate, i.e. the speed
-			if (const char *tp = TFREC_KNOB_STR("WHB_TEST_PERTURB"))
-				c->whb_test_perturb = std::max(-1000000, std::min(1000000, atoi(tp)));
-			if (rc == TFREC_AMD_OK && hipMemset(c->d_whbgen, 0, n * sizeof(uint32_t)) != hipSuccess)
-				rc = TFREC_AMD_E_HIP;
-			if (const char *ff = TFREC_KNOB_STR("WHB_FORCE_FAIL"))
-				c->whb_force_fail = std::max(0, atoi(ff));
-#if TFREC_KNOBS_BUILT
-			if (c->whb_test_perturb || c->whb_force_fail)
-				fprintf(stderr, "tfrec_amd: TEST hook active (TFREC_AMD_WHB_TEST_PERTURB=%d, TFREC_AMD_WHB_FORCE_FAIL=%d): WHB streams are "
-						"redone on purpose, results unchanged, throughput lower\n", c->whb_test_perturb, c->whb_force_fail);
-#endif
-			if (rc == TFREC_AMD_OK && (hipMemset(c->d_whbx, 0, n * sizeof(WhbExact)) != hipSuccess ||
-						   hipMemset(c->d_whbcarry, 0, n * sizeof(int)) != hipSuccess))
-				rc = TFREC_AMD_E_HIP;
-		}
-		for (int set = 0; set < kSets; set++) {
-		WinTables &T = c->win[set];
-		T.cap = (int32_t)(m_max / 356 + 2);  // windows of one chain are > W-1 >= 355 samples apart
-		T.slots = (int32_t)(m_max / 32 + (size_t)T.cap + 2);  // window-relative 32-sample slots per chain row
-		if ((size_t)T.slots > (size_t)kWhbRecOffMask) {  // WhbStepRec::meta packs a slot index into kWhbRecOffMask's bits
-			snprintf(g_err, sizeof(g_err), "max_blocks too large for the WHB step records");
-			rc = TFREC_AMD_E_INVAL;
-			break;
-		}
-		// rows only for the chains that use them: ld16 for the TFA_2 family (its slots are adjacent in registration order),
-		// checkpoints for the chains with a biquad stage (all but TFA_1, which is registered first)
-		int a_ld0 = -1, n_ld = 0, a_ck0 = -1;
-		for (int a = 0; a < c->launch.n_active; a++) {
-			if (c->launch.params[a].kind == 1) {
-				if (a_ld0 < 0)
-					a_ld0 = a;
-				n_ld = a - a_ld0 + 1;
-			}
-			if (c->launch.params[a].kind != 0 && a_ck0 < 0)
-				a_ck0 = a;
-		}
-		T.ld_c0 = (int32_t)((a_ld0 < 0 ? 0 : a_ld0) * n);
-		T.ck_c0 = (int32_t)((a_ck0 < 0 ? 0 : a_ck0) * n);
-		const size_t ck_chains = a_ck0 < 0 ? 0 : chains - (size_t)a_ck0 * n;
-		ALLOC(c->d_ld16[set], std::max<size_t>(1, (size_t)n_ld * n) * (size_t)T.slots * 32 * sizeof(int16_t));
-		if (whb)
-			ALLOC(c->d_dev32[set], n * (size_t)T.slots * 32 * sizeof(int32_t) + 4096);  // + slack: whb_demod_kernel keeps two 64-sample steps in flight past a row's last window
-		T.bit_words = (int32_t)(m_max / 64 + 3 * (size_t)T.cap + 8);
-		const size_t wins = chains * (size_t)T.cap;
-		size_t off = 0;
-		auto carve = [&](size_t bytes) {
-			const size_t o = off;
-			off += (bytes + 255) & ~(size_t)255;
-			return o;
-		};
-		const size_t o_count = carve(chains * 4), o_cont = carve(chains * 4), o_tnext = carve(chains * 4);
-		const size_t o_open = carve(wins * 4), o_close = carve(wins * 4), o_res = carve(wins * sizeof(WinResult));
-		const size_t o_dcd = carve(wins * sizeof(WinDecode)), o_wst = carve(whb ? n * (size_t)T.cap * sizeof(WhbStart) : 0);
-		const size_t o_bits = carve(chains * (size_t)T.bit_words * 4), o_items = carve((kNQueues * wins + chains) * sizeof(uint2));
-		const size_t o_queue = carve((kNQueues + 1) * sizeof(WorkQueue)), o_stats = carve(128);
-		T.segcap = (int32_t)((m_max / 32 + (size_t)T.cap) / kSegSlots + 2);
-		const size_t segs = chains * (size_t)T.segcap;
-		const size_t o_ckpt = carve(ck_chains * (size_t)T.slots * sizeof(double2));
-		const size_t o_sstart = carve(segs * sizeof(uint2)), o_vtotal = carve(chains * 4);
-		const size_t o_se1 = carve(segs * sizeof(BiquadEnd)), o_se2 = carve(segs * sizeof(BiquadEnd)), o_sfix = carve(segs * 4);
-		const size_t o_se3 = carve(segs * sizeof(BiquadEnd)), o_sfix2 = carve(segs * 4);
-		const size_t o_cand = carve(n * (size_t)T.slots * 4), o_mark = carve(n * (size_t)T.slots * sizeof(MarkPiece));
-		T.whbrec_stride = (int32_t)(m_max / 64 + 2 * (size_t)T.cap + 2 + kWhbRecSlack);
-		const size_t o_wrec = carve(whb ? n * (size_t)T.whbrec_stride * sizeof(WhbStepRec) : 0), o_wfail = carve(whb ? n * 4 : 0);
-		const size_t o_wsnap = carve(whb ? n * sizeof(ChainState) : 0), o_wx0 = carve(whb ? n * sizeof(WhbExact) : 0);
-		const size_t o_wseen = carve(whb ? n * 4 : 0);
-		T.whbdense_stride = (int32_t)(m_max + 64);
-		T.whbx_stride = (int32_t)(m_max / 64 + 2);
-		const size_t o_wdn = carve(whb ? n * 4 : 0), o_wxb = carve(whb ? n * (size_t)T.whbx_stride * 8 : 0);
-		const size_t o_wxs = carve(whb ? n * (size_t)T.whbx_stride * sizeof(double2) : 0);
-		const size_t o_wdense = carve(whb ? n * (size_t)T.whbdense_stride * 4 : 0);
-		ALLOC(c->win_block[set], off);
-		if (rc == TFREC_AMD_OK) {
-			uint8_t *b = (uint8_t *)c->win_block[set];
-			T.count = (int32_t *)(b + o_count);
-			T.cont = (int32_t *)(b + o_cont);
-			T.timeout_next = (int32_t *)(b + o_tnext);
-			T.open = (int32_t *)(b + o_open);
-			T.close = (int32_t *)(b + o_close);
-			T.result = (WinResult *)(b + o_res);
-			T.decode = (WinDecode *)(b + o_dcd);
-			T.whbstart = (WhbStart *)(b + o_wst);
-			T.bits = (uint32_t *)(b + o_bits);
-			T.items = (uint2 *)(b + o_items);
-			T.queue = (WorkQueue *)(b + o_queue);
-			T.overflow = nullptr;  // lives in the set's event block (kEvOverflowOff): set below, reset by every submit
-			T.stats = (unsigned long long *)(b + o_stats);
-			T.ckpt = (double2 *)(b + o_ckpt);
-			T.segstart = (uint2 *)(b + o_sstart);
-			T.vtotal = (int32_t *)(b + o_vtotal);
-			T.segend1 = (BiquadEnd *)(b + o_se1);
-			T.segend2 = (BiquadEnd *)(b + o_se2);
-			T.segfix = (int32_t *)(b + o_sfix);
-			T.segend3 = (BiquadEnd *)(b + o_se3);
-			T.segfix2 = (int32_t *)(b + o_sfix2);
-			T.cand = (uint32_t *)(b + o_cand);
-			T.mark = (MarkPiece *)(b + o_mark);
-			T.whbrec = (WhbStepRec *)(b + o_wrec);
-			T.whbfail = (int32_t *)(b + o_wfail);
-			T.whbsnap = (ChainState *)(b + o_wsnap);
-			T.whbx0 = (WhbExact *)(b + o_wx0);
-			T.whbseen = (uint32_t *)(b + o_wseen);
-			T.whbdense = (int32_t *)(b + o_wdense);
-			T.whbdense_n = (int32_t *)(b + o_wdn);
-			T.whbxbits = (unsigned long long *)(b + o_wxb);
-			T.whbxsnap = (double2 *)(b + o_wxs);
-			T.whbgen = c->d_whbgen;
-			T.whbX = c->d_whbX;
-			T.whbscr = c->d_whbscr;
-			T.whbpub = nullptr;
-			T.whb_test_perturb = c->whb_test_perturb;
-			T.tfa1_vec = TFREC_KNOB_INT("TFA1_VEC", 1, 0, 1) != 0;
-			T.tfa2_vec = TFREC_KNOB_INT("TFA2_VEC", 1, 0, 1) != 0;
-			T.whb_force_fail = c->whb_force_fail;
-			T.whbx = c->d_whbx;
-			T.timeout_carry = c->d_tcarry;
-			T.prevdec = c->d_prevdec[set];
-			if (hipMemset(T.queue, 0, (kNQueues + 1) * sizeof(WorkQueue)) != hipSuccess ||
-			    hipMemset(T.stats, 0, 128) != hipSuccess)
-				rc = TFREC_AMD_E_HIP;
-		}
-		}
-	}
-	c->in10x = (cfg->flags & TFREC_AMD_F_INPUT_10X) != 0;
-	const size_t tail_bytes = c->in10x ? 2 * (size_t)kTailBytes : (size_t)kTailBytes;  // int16 history is twice as wide
-	ALLOC(c->d_tail[0], n * tail_bytes);
-	ALLOC(c->d_tail[1], n * tail_bytes);
-	if (c->in10x) {
-		c->in16_stride = 4 * m_max;  // complex samples at 1.536 MS/s per stream and submit
-		for (int k = 0; k < kSets; k++) {
-			ALLOC(c->d_in16[k], n * c->in16_stride * sizeof(uint32_t));
-			ALLOC(c->d_tail10[k], n * 112);
-		}
-	}
-	// One block per set: [EventBuf | the window tables' overflow flag, 16 B | pad to 256 | events]: the drain's device-to-host
-	// copy of a submit is ONE copy on the stream that sets the batch period (three copies were 0.45 ms of it with their gaps)
-	for (int k = 0; k < kSets; k++) {
-		ALLOC(c->d_evblock[k], kEvHeader + (size_t)cfg->max_events * sizeof(tfrec_amd_event));
-		if (rc == TFREC_AMD_OK) {
-			c->d_eb[k] = (EventBuf *)c->d_evblock[k];
-			c->d_events[k] = (tfrec_amd_event *)(c->d_evblock[k] + kEvHeader);
-			if (c->win[k].count)  // (window-parallel pipeline: its overflow flag lives behind the EventBuf)
-				c->win[k].overflow = (int32_t *)(c->d_evblock[k] + kEvOverflowOff);
-		}
-	}
-	ALLOC(c->d_eb_fresh, kEvFreshBytes);
-	// tfrec_amd_reset_streams: a list of at most n_streams indices per set, and the constructor state it restores
-	ALLOC(c->d_chain_init, sizeof(ChainState));
-	for (int k = 0; k < kSets; k++) {
-		ALLOC(c->d_reset[k], n * sizeof(int32_t));
-		ALLOC(c->d_rcfg[k], n * sizeof(StreamCfg));
-	}
-	if (rc == TFREC_AMD_OK) {
-		ChainState init;
-		memset(&init, 0, sizeof(init));
-		init.sr_cnt = -1;
-		init.dmin = 32767;
-		init.dmax = -32767;
-		if (hipMemcpy(c->d_chain_init, &init, sizeof(init), hipMemcpyHostToDevice) != hipSuccess)
-			rc = TFREC_AMD_E_HIP;
-	}
-#undef ALLOC
-	for (int k = 0; k < kSets && rc == TFREC_AMD_OK; k++) {
-		if (hipHostMalloc((void **)&c->h_evblock[k], kEvHeader + (size_t)cfg->max_events * sizeof(tfrec_amd_event), hipHostMallocDefault) != hipSuccess ||
-		    hipHostGetDevicePointer((void **)&c->h_evblock_dev[k], c->h_evblock[k], 0) != hipSuccess ||
-		    hipEventCreateWithFlags(&c->copied[k], hipEventDisableTiming) != hipSuccess) {
-			rc = TFREC_AMD_E_NOMEM;
-			break;
-		}
-		c->pinned_bytes += kEvHeader + (size_t)cfg->max_events * sizeof(tfrec_amd_event);
-		c->h_eb[k] = (EventBuf *)c->h_evblock[k];
-		c->h_events[k] = (tfrec_amd_event *)(c->h_evblock[k] + kEvHeader);
-		if (hipHostMalloc((void **)&c->h_reset[k], n * sizeof(int32_t), hipHostMallocDefault) != hipSuccess ||
-		    hipHostMalloc((void **)&c->h_rcfg[k], n * sizeof(StreamCfg), hipHostMallocDefault) != hipSuccess) {
-			rc = TFREC_AMD_E_NOMEM;
-			break;
-		}
-		c->pinned_bytes += n * (sizeof(int32_t) + sizeof(StreamCfg));
-	}
-	if (rc == TFREC_AMD_OK) {
-		c->reset_marked.assign(n, 0);
-		c->origin.assign(n, 0);
-	}
-	// Every pipeline stream except the biquad stages runs at high priority.  With the front end at low priority
-	// ("fill what the latency-bound chains leave free") its kernel stretched from 3 to 11 ms beside the chains and,
-	// with three submits in flight, became the longest stage of all: 13.4 ms per batch instead of 11.7.
-	// (The biquad stages and cp run at normal priority, 0; the discriminator pass, the TFA_2 family's speculative pass and the
-	// drain's copies, when they have streams of their own, at low priority.)
-	int prio_lo = 0, prio_hi = 0;
-	(void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-	auto mkstream = [](hipStream_t *st, int prio) { return hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio); };
-	if (rc == TFREC_AMD_OK) {
-		// zero FIR history == u8 value 128 (decimate::decimate zeroes hist0, dsp_stuff.cpp:145-152)
-		EventBuf eb;
-		memset(&eb, 0, sizeof(eb));
-		eb.capacity = (uint32_t)cfg->max_events;
-		// (int16 history of the 10x path: zero; raw u8 history of its 10:1 stage: 128)
-		if (hipMemset(c->d_tail[0], c->in10x ? 0 : 0x80, n * tail_bytes) != hipSuccess ||
-		    hipMemset(c->d_tail[1], c->in10x ? 0 : 0x80, n * tail_bytes) != hipSuccess ||
-		    (c->in10x && (hipMemset(c->d_tail10[0], 0x80, n * 112) != hipSuccess ||
-				  hipMemset(c->d_tail10[1], 0x80, n * 112) != hipSuccess)) ||
-		    hipMemset(c->d_eb_fresh, 0, kEvFreshBytes) != hipSuccess ||
-		    hipMemcpy(c->d_eb_fresh, &eb, sizeof(eb), hipMemcpyHostToDevice) != hipSuccess ||
-		    mkstream(&c->fs, prio_hi) != hipSuccess ||
-		    mkstream(&c->cp, 0) != hipSuccess ||
-		    mkstream(&c->cs, prio_hi) != hipSuccess)
-			rc = TFREC_AMD_E_HIP;
-		for (int k = 0; k < kSets && rc == TFREC_AMD_OK; k++) {
-			for (auto &e : c->done[k])
-				if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess)
-					rc = TFREC_AMD_E_HIP;
-			for (auto &e : c->ev_pipe[k])
-				if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess)
-					rc = TFREC_AMD_E_HIP;
-			if (hipEventCreateWithFlags(&c->ev_in[k], hipEventDisableTiming) != hipSuccess ||
-			    hipEventCreateWithFlags(&c->ev_front[k], hipEventDisableTiming) != hipSuccess ||
-			    hipMemset(c->d_evblock[k], 0, kEvHeader) != hipSuccess ||
-			    hipMemcpy(c->d_eb[k], &eb, sizeof(eb), hipMemcpyHostToDevice) != hipSuccess)
-				rc = TFREC_AMD_E_HIP;
-		}
-	}
-	if (rc == TFREC_AMD_OK && !(cfg->flags & TFREC_AMD_F_SERIAL_CHAINS)) {
-		if (mkstream(&c->t1, prio_hi) != hipSuccess || mkstream(&c->aux, prio_hi) != hipSuccess)
-			rc = TFREC_AMD_E_HIP;
-		// deep layout (default; TFREC_AMD_DEEP=0 selects the shallow one): the biquad stages get streams of their own
-		const char *dp = TFREC_KNOB_STR("DEEP");
-		c->deep = dp ? atoi(dp) != 0 : true;
-		// The discriminator pass moves from the front-end stream to the head of the TFA_2-family biquad stage when a WHB
-		// demodulator is registered: then the WHB chain is the longest and the front-end stream the busiest (measured
-		// 12.2 -> 11.8 ms per batch; without WHB the TFA_2 chain is the longest and the move costs 7.7 -> 8.5 ms)
-		bool has_whb = false;
-		for (int a = 0; a < c->launch.n_active; a++)
-			has_whb = has_whb || c->launch.params[a].kind == 2;
-		c->fmdev_k2 = has_whb;
-		c->k2 = c->cs;
-		c->kw = c->aux;
-		c->vx = c->aux;
-		if (c->deep && rc == TFREC_AMD_OK &&
-		    (mkstream(&c->k2, 0) != hipSuccess || mkstream(&c->kw, 0) != hipSuccess))
-			rc = TFREC_AMD_E_HIP;
-		// The discriminator pass on a LOW-priority stream of its own when a WHB demodulator is registered.  It needs the front
-		// end only, not the window scan; at the head of k2 it made that stream (discriminator + five biquad kernels) the one that
-		// set the batch period: 6.98 -> 6.60 ms per batch over 100 steps (profiles/r04_ab_fmdev_stream.txt).  The low-priority
-		// pool's hardware queues are otherwise unused, so the stream shares none (a fifth normal-priority stream would).
-		if (c->deep && rc == TFREC_AMD_OK && c->need_fmdev && c->fmdev_k2 && mkstream(&c->fq, prio_lo) != hipSuccess)
-			rc = TFREC_AMD_E_HIP;
-		// The speculative biquad pass of the TFA_2 family on a low-priority stream of its own (when the discriminator pass has
-		// its stream): it needs nothing of the submit before (chains2.hip K3a), so it runs beside that submit's repair passes and
-		// chain walk on k2.  The third stream of the low-priority pool (with fq and cq): no shared hardware queue.
-		if (c->deep && rc == TFREC_AMD_OK && c->fq && mkstream(&c->ks, prio_lo) != hipSuccess)
-			rc = TFREC_AMD_E_HIP;
-		// The drain's copy on a low-priority stream of its own (the shallow layout: on cp).  On cp it sat between the WHB checks
-		// of consecutive submits and waits for ALL chains of its submit: the check of submit k + 1 could not start before the TFA
-		// chains of submit k had ended.  6.32 -> 6.21 ms per batch over 100 steps (profiles/r04_ab_copy_stream.txt);
-		// the low pool's hardware queues hold only this stream and the discriminator's.
-		if (c->deep && rc == TFREC_AMD_OK && mkstream(&c->cq, prio_lo) != hipSuccess)
-			rc = TFREC_AMD_E_HIP;
-		// The WHB check (whb_chain_kernel, whb_check_kernel, the redo) runs on cp, where the drain's copies were until they
-		// moved to cq.  A stream of its own would be the FIFTH of normal priority in the process (k2, kw, cp and the caller's): it shared a
-		// hardware queue with kw, and the 6 ms verification of submit k held up the WHB biquads of submit k + 2.
-		if (c->deep)
-			c->vx = c->cp;
-		for (int k = 0; k < kSets && rc == TFREC_AMD_OK; k++)
-			if (hipEventCreateWithFlags(&c->ev_aux[k], hipEventDisableTiming) != hipSuccess)
-				rc = TFREC_AMD_E_HIP;
-	}
-	if (rc == TFREC_AMD_OK && (cfg->flags & TFREC_AMD_F_TIMING)) {
-		for (int k = 0; k < kSets; k++) {
-			for (auto &e : c->ev[k])
-				if (hipEventCreate(&e) != hipSuccess)
-					rc = TFREC_AMD_E_HIP;
-			if (!(cfg->flags & TFREC_AMD_F_SERIAL_CHAINS))
-				for (auto &e : c->tev[k])
-					if (hipEventCreate(&e) != hipSuccess)
-						rc = TFREC_AMD_E_HIP;
-		}
-	}
-	for (int a = 0; a < c->launch.n_active; a++)
-		c->whb_active = c->whb_active || c->launch.params[a].kind == 2;
+	const int rc = init_context(c);
 	if (rc != TFREC_AMD_OK) {
 		tfrec_amd_destroy(c);
 		return rc;
@@ -942,14 +983,14 @@ int tfrec_amd_create(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
 // The resets marked since the last submit, at the head of this submit's front end (fs).  Carried state is written by several
 // stages on several streams (a ChainState by the biquad stage, the slicers, the decoders' commit and the WHB check's redo), and
 // in the deep layout those of the submit before may still run while this one's front end does: the front-end stream first
-// waits for the end of every chain of the last submit (done[last_set]: every stage of it and of all earlier submits is behind
+// waits for the end of every chain of the last submit (its set's done: every stage of it and of all earlier submits is behind
 // one of them), then one kernel restores the state of the listed streams.  Every stage of this submit is ordered after its
 // front end, so it reads the restored state.  A submit without a pending reset launches nothing of this.
 static int launch_resets(tfrec_amd_ctx *c, int set)
 {
-	hipStream_t fs = c->fs;
+	hipStream_t fs = c->pipe[set].fs;
 	if (c->submitted)
-		for (hipEvent_t e : c->done[c->last_set])
+		for (hipEvent_t e : c->pipe[c->last_set].done)
 			HIPCHK(hipStreamWaitEvent(fs, e, 0));
 	const int nl = (int)c->reset_pending.size();
 	memcpy(c->h_reset[set], c->reset_pending.data(), (size_t)nl * sizeof(int32_t));  // (the set's last copy was drained)
@@ -964,7 +1005,7 @@ static int launch_resets(tfrec_amd_ctx *c, int set)
 	R.n_streams = c->cfg.n_streams;
 	R.tail = c->d_tail[c->tail_sel];  // the buffer this submit's front end reads (the history flips per submit)
 	R.tail_bytes = c->in10x ? 2 * kTailBytes : kTailBytes;
-	R.tail_fill = c->in10x ? 0 : 0x80;  // as tfrec_amd_create: int16 zero, or u8 128
+	R.tail_fill = c->in10x ? 0 : 0x80;  // as make_front_buffers: int16 zero, or u8 128
 	R.tail10 = c->in10x ? c->d_tail10[c->tail_sel] : nullptr;
 	R.fsk = c->d_fsk;
 	R.cfgs = c->d_rcfg[set];
@@ -982,111 +1023,9 @@ static int launch_resets(tfrec_amd_ctx *c, int set)
 	return TFREC_AMD_OK;
 }
 
-// in_stream_is_fs: the input was produced on the front-end stream itself (staged host input): no event needed
-static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int n_blocks, void *hip_stream, bool input_on_fs)
+// Instrumentation builds and knobs: statistics of the third submit, printed to stderr (the host waits for the device first)
+static void report_debug_stats(tfrec_amd_ctx *c, int set, int n_blocks)
 {
-	if (!c || !d_iq || n_blocks < 1 || n_blocks > c->cfg.max_blocks)
-		return TFREC_AMD_E_INVAL;
-	const size_t block_bytes = c->in10x ? TFREC_AMD_BLOCK_BYTES_10X : TFREC_AMD_BLOCK_BYTES;
-	if ((stride % 16) != 0 || ((uintptr_t)d_iq % 16) != 0 ||
-	    (c->cfg.n_streams > 1 && stride < (size_t)n_blocks * block_bytes)) {
-		snprintf(g_err, sizeof(g_err), "IQ base and stream stride must be 16-byte aligned and >= one stream");
-		return TFREC_AMD_E_INVAL;
-	}
-	if (c->inflight >= kSets) {
-		snprintf(g_err, sizeof(g_err), "%d submits are waiting to be drained: call tfrec_amd_drain_events first", kSets);
-		return TFREC_AMD_E_STATE;
-	}
-	if (c->poisoned) {
-		snprintf(g_err, sizeof(g_err), "an earlier submit failed half way: the context must be recreated");
-		return TFREC_AMD_E_STATE;
-	}
-	HIPCHK(hipSetDevice(c->cfg.device));
-	PoisonGuard guard(c);  // from here on work is enqueued: a failure leaves the carried state undefined
-	const bool timing = (c->cfg.flags & TFREC_AMD_F_TIMING) != 0;
-	const int set = (c->head + c->inflight) % kSets;  // this submit's event buffers and timing events
-	// Front end on its own stream: it starts when the caller's stream has produced the input, and may overlap the
-	// chains of the previous submit (different buffer set; the set's previous user was drained, see the FIFO rule)
-	hipStream_t fs = c->fs;
-	hipStream_t st = c->cs;  // the chains run on an internal stream: nothing of ours is queued on the caller's
-	if (!input_on_fs) {
-		HIPCHK(hipEventRecord(c->ev_in[set], (hipStream_t)hip_stream));
-		HIPCHK(hipStreamWaitEvent(fs, c->ev_in[set], 0));
-	}
-	HIPCHK(hipMemcpyAsync(c->d_eb[set], c->d_eb_fresh, kEvFreshBytes, hipMemcpyDeviceToDevice, fs));  // (+ the overflow flag)
-	if (timing)
-		HIPCHK(hipEventRecord(c->ev[set][0], fs));
-	const bool resets = !c->reset_pending.empty();
-	if (resets) {
-		const int rr = launch_resets(c, set);
-		if (rr)
-			return rr;
-	}
-	const uint8_t *fin = (const uint8_t *)d_iq;
-	size_t fstride = stride;
-	if (c->in10x) {  // 15.36 MS/s u8 -> 1.536 MS/s int16 pairs, then the standard cascade on int16 input
-		HIPCHK(launch_decim10(fs, (const uint8_t *)d_iq, stride, c->cfg.n_streams, n_blocks, c->d_tail10[c->tail_sel],
-				      c->d_tail10[c->tail_sel ^ 1], c->d_in16[set], c->in16_stride));
-		fin = (const uint8_t *)c->d_in16[set];
-		fstride = c->in16_stride * sizeof(uint32_t);
-	}
-	HIPCHK(launch_frontend(fs, fin, fstride, c->cfg.n_streams, n_blocks, c->d_tail[c->tail_sel],
-			       c->d_tail[c->tail_sel ^ 1], c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride,
-			       c->d_prevdec[set], c->cfg.thresh ? c->cfg.thresh : 500, c->taps, c->in10x));
-	if (c->n_auto)  // auto threshold: per-block thresholds rewrite the trigger mask (fm_demod.cpp:58-73)
-		HIPCHK(launch_threshold(fs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams,
-					n_blocks, c->d_fsk, c->wmax, c->per_stream ? c->d_scfg : nullptr));
-	if (timing)
-		HIPCHK(hipEventRecord(c->ev[set][3], fs));
-	const bool fmdev_k2 = c->need_fmdev && c->fmdev_k2 && !(c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS);
-	if (c->need_fmdev && !fmdev_k2)  // FM discriminator of the samples near trigger windows (after the mask is final)
-		HIPCHK(launch_fmdev(fs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->d_prevdec[set],
-				    c->d_fmdev[set], c->dec_stride, c->d_eb[set], c->cfg.n_streams, n_blocks, c->wmax,
-				    c->fm_flag_eps));
-	if (timing)
-		HIPCHK(hipEventRecord(c->ev[set][1], fs));
-	HIPCHK(hipEventRecord(c->ev_front[set], fs));
-	if (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) {
-		HIPCHK(hipStreamWaitEvent(st, c->ev_front[set], 0));
-		HIPCHK(launch_chains(st, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams, n_blocks,
-				     c->sample_base, c->launch, c->d_events[set], c->d_eb[set], c->cfg.flags));
-		if (timing)
-			HIPCHK(hipEventRecord(c->ev[set][2], st));
-		for (auto &e : c->done[set])
-			HIPCHK(hipEventRecord(e, st));
-	} else {
-		PipeCtl P;
-		P.fs = fs;
-		P.ws = c->deep ? c->kw : fs;
-		P.ev_front = c->ev_front[set];
-		P.k2 = c->k2;
-		P.kw = c->kw;
-		P.cs = c->cs;
-		P.aux = c->aux;
-		P.t1 = c->t1;
-		P.vx = c->vx;
-		P.ev_aux = c->ev_aux[set];
-		P.whb_carry = c->d_whbcarry;
-		P.ev_win = c->ev_pipe[set][0];
-		P.ev_fork = c->ev_pipe[set][1];
-		P.ev_k2 = c->ev_pipe[set][2];
-		P.ev_kw = c->ev_pipe[set][3];
-		P.ev_fm = c->ev_pipe[set][4];
-		P.fq = c->fq;
-		P.ks = c->ks;
-		P.ev_spec = c->ev_pipe[set][5];
-		for (int k = 0; k < 3; k++)
-			P.done[k] = c->done[set][k];
-		P.tev = (timing && c->tev[set][0]) ? c->tev[set] : nullptr;
-		P.fmdev_wmax = fmdev_k2 ? c->wmax : 0;
-		P.fm_flag_eps = c->fm_flag_eps;
-		P.fmdev_out = c->d_fmdev[set];
-		P.prevdec = c->d_prevdec[set];
-		c->win[set].whb_submit_seq = c->submit_seq++;
-		HIPCHK(launch_pipeline(P, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->d_fmdev[set], c->dec_stride,
-				       c->cfg.n_streams, n_blocks, c->sample_base, c->launch, c->win[set], c->d_ld16[set],
-				       c->d_dev32[set], c->d_events[set], c->d_eb[set], c->cfg.flags));
-	}
 #ifdef TFREC_AMD_VECSTAT
 	if (c->submit_seq == 3) {
 		(void)hipDeviceSynchronize();
@@ -1176,21 +1115,93 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 			fprintf(stderr, "\n");
 		}
 	}
+}
+
+// input_on_fs: the input was produced on the front-end stream itself (staged host input): no event needed
+static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int n_blocks, void *hip_stream, bool input_on_fs)
+{
+	if (!c || !d_iq || n_blocks < 1 || n_blocks > c->cfg.max_blocks)
+		return TFREC_AMD_E_INVAL;
+	const size_t block_bytes = c->in10x ? TFREC_AMD_BLOCK_BYTES_10X : TFREC_AMD_BLOCK_BYTES;
+	if ((stride % 16) != 0 || ((uintptr_t)d_iq % 16) != 0 ||
+	    (c->cfg.n_streams > 1 && stride < (size_t)n_blocks * block_bytes)) {
+		snprintf(g_err, sizeof(g_err), "IQ base and stream stride must be 16-byte aligned and >= one stream");
+		return TFREC_AMD_E_INVAL;
+	}
+	TRY(check_fifo(c));
+	TRY(check_live(c));
+	HIPCHK(hipSetDevice(c->cfg.device));
+	PoisonGuard guard(c);  // from here on work is enqueued: a failure leaves the carried state undefined
+	const bool timing = (c->cfg.flags & TFREC_AMD_F_TIMING) != 0;
+	const int set = (c->head + c->inflight) % kSets;  // this submit's buffer set, events and timing events
+	const PipeCtl &P = c->pipe[set];
+	hipEvent_t *ev = c->ev[set];
+	// Front end on its own stream: it starts when the caller's stream has produced the input, and may overlap the
+	// chains of the previous submit (different buffer set; the set's previous user was drained, see the FIFO rule).
+	// The chains run on internal streams: nothing of ours is queued on the caller's.
+	hipStream_t fs = P.fs;
+	if (!input_on_fs) {
+		HIPCHK(hipEventRecord(c->ev_in[set], (hipStream_t)hip_stream));
+		HIPCHK(hipStreamWaitEvent(fs, c->ev_in[set], 0));
+	}
+	HIPCHK(hipMemcpyAsync(c->d_eb[set], c->d_eb_fresh, kEvFreshBytes, hipMemcpyDeviceToDevice, fs));  // (+ the overflow flag)
+	if (timing)
+		HIPCHK(hipEventRecord(ev[kEvSubmit], fs));
+	const bool resets = !c->reset_pending.empty();
+	if (resets)
+		TRY(launch_resets(c, set));
+	const uint8_t *fin = (const uint8_t *)d_iq;
+	size_t fstride = stride;
+	if (c->in10x) {  // 15.36 MS/s u8 -> 1.536 MS/s int16 pairs, then the standard cascade on int16 input
+		HIPCHK(launch_decim10(fs, (const uint8_t *)d_iq, stride, c->cfg.n_streams, n_blocks, c->d_tail10[c->tail_sel],
+				      c->d_tail10[c->tail_sel ^ 1], c->d_in16[set], c->in16_stride));
+		fin = (const uint8_t *)c->d_in16[set];
+		fstride = c->in16_stride * sizeof(uint32_t);
+	}
+	HIPCHK(launch_frontend(fs, fin, fstride, c->cfg.n_streams, n_blocks, c->d_tail[c->tail_sel],
+			       c->d_tail[c->tail_sel ^ 1], c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride,
+			       c->d_prevdec[set], c->cfg.thresh ? c->cfg.thresh : 500, c->taps, c->in10x));
+	if (c->n_auto)  // auto threshold: per-block thresholds rewrite the trigger mask (fm_demod.cpp:58-73)
+		HIPCHK(launch_threshold(fs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams,
+					n_blocks, c->d_fsk, c->wmax, c->per_stream ? c->d_scfg : nullptr));
+	if (timing)
+		HIPCHK(hipEventRecord(ev[kEvFrontDone], fs));
+	if (has_kind(c->launch, 1) && !c->fmdev_k2)  // FM discriminator of the samples near trigger windows (after the mask is final)
+		HIPCHK(launch_fmdev(fs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->d_prevdec[set],
+				    c->d_fmdev[set], c->dec_stride, c->d_eb[set], c->cfg.n_streams, n_blocks, c->wmax,
+				    c->fm_flag_eps));
+	if (timing)
+		HIPCHK(hipEventRecord(ev[kEvFmdevDone], fs));
+	HIPCHK(hipEventRecord(P.ev_front, fs));
+	if (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) {
+		HIPCHK(hipStreamWaitEvent(P.cs, P.ev_front, 0));
+		HIPCHK(launch_chains(P.cs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams, n_blocks,
+				     c->sample_base, c->launch, c->d_events[set], c->d_eb[set], c->cfg.flags));
+		if (timing)
+			HIPCHK(hipEventRecord(ev[kEvSerialDone], P.cs));
+		for (hipEvent_t e : P.done)
+			HIPCHK(hipEventRecord(e, P.cs));
+	} else {
+		c->win[set].whb_submit_seq = c->submit_seq++;
+		HIPCHK(launch_pipeline(P, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->d_fmdev[set], c->dec_stride,
+				       c->cfg.n_streams, n_blocks, c->sample_base, c->launch, c->win[set], c->d_ld16[set],
+				       c->d_dev32[set], c->d_events[set], c->d_eb[set], c->cfg.flags));
+	}
+	report_debug_stats(c, set, n_blocks);
 	// the drain's copies, queued now
-	hipStream_t cpy = c->cq ? c->cq : c->cp;
-	for (auto &e : c->done[set])
-		HIPCHK(hipStreamWaitEvent(cpy, e, 0));
+	for (hipEvent_t e : P.done)
+		HIPCHK(hipStreamWaitEvent(c->cpy, e, 0));
 	c->copied_n[set] = std::min<uint32_t>(c->copy_guess, (uint32_t)c->cfg.max_events);
 	{  // header, overflow flag and the first copied_n events in one go
 		static_assert(kEvHeader % 16 == 0 && sizeof(tfrec_amd_event) % 16 == 0, "drain_copy_kernel moves 16 bytes per lane");
 		const size_t bytes = kEvHeader + (size_t)c->copied_n[set] * sizeof(tfrec_amd_event);
 		const size_t n16 = bytes / 16;
 		const unsigned blocks = (unsigned)std::min<size_t>(256, (n16 + 255) / 256);
-		hipLaunchKernelGGL(tfrec::drain_copy_kernel, dim3(blocks), dim3(256), 0, cpy, (const uint4 *)c->d_evblock[set],
+		hipLaunchKernelGGL(tfrec::drain_copy_kernel, dim3(blocks), dim3(256), 0, c->cpy, (const uint4 *)c->d_evblock[set],
 				   (uint4 *)c->h_evblock_dev[set], n16);
 		HIPCHK(hipGetLastError());
 	}
-	HIPCHK(hipEventRecord(c->copied[set], cpy));
+	HIPCHK(hipEventRecord(c->copied[set], c->cpy));
 	if (timing)
 		c->timed = true;
 	if (resets) {
@@ -1241,10 +1252,7 @@ static int submit_host_impl(tfrec_amd_ctx *c, const uint8_t *h_iq, size_t stride
 	const size_t row = (size_t)n_blocks * (c->in10x ? TFREC_AMD_BLOCK_BYTES_10X : TFREC_AMD_BLOCK_BYTES);
 	if (c->cfg.n_streams > 1 && stride < row)
 		return TFREC_AMD_E_INVAL;
-	if (c->inflight >= kSets) {
-		snprintf(g_err, sizeof(g_err), "%d submits are waiting to be drained: call tfrec_amd_drain_events first", kSets);
-		return TFREC_AMD_E_STATE;
-	}
+	TRY(check_fifo(c));
 	HIPCHK(hipSetDevice(c->cfg.device));
 	const int set = (c->head + c->inflight) % kSets;  // the set's previous user has been drained: its staging buffer is free
 	const size_t need = row * (size_t)c->cfg.n_streams;
@@ -1258,7 +1266,7 @@ static int submit_host_impl(tfrec_amd_ctx *c, const uint8_t *h_iq, size_t stride
 	}
 	// asynchronous on the front-end stream when h_iq is pinned (tfrec_amd_host_alloc); pageable memory is staged
 	// by the runtime before the call returns
-	HIPCHK(hipMemcpy2DAsync(c->d_stage[set], row, h_iq, stride, row, (size_t)c->cfg.n_streams, hipMemcpyHostToDevice, c->fs));
+	HIPCHK(hipMemcpy2DAsync(c->d_stage[set], row, h_iq, stride, row, (size_t)c->cfg.n_streams, hipMemcpyHostToDevice, c->pipe[set].fs));
 	return submit_common(c, c->d_stage[set], row, n_blocks, nullptr, true);
 }
 
@@ -1281,9 +1289,9 @@ int tfrec_amd_sync(tfrec_amd_ctx *c)
 	if (!c)
 		return TFREC_AMD_E_INVAL;
 	HIPCHK(hipSetDevice(c->cfg.device));
-	for (hipStream_t st : { c->fs, c->k2, c->kw, c->cs, c->fq, c->ks, c->cq, c->aux, c->vx, c->t1, c->cp })
-		if (st)
-			HIPCHK(hipStreamSynchronize(st));
+	for (const tfrec_amd_ctx::Owned &o : c->owned)
+		if (o.kind == tfrec_amd_ctx::Owned::kStream)
+			HIPCHK(hipStreamSynchronize(static_cast<hipStream_t>(o.h)));
 	return TFREC_AMD_OK;
 }
 
@@ -1292,10 +1300,7 @@ int tfrec_amd_pending_events(tfrec_amd_ctx *c, int *n)
 	if (!c || !n)
 		return TFREC_AMD_E_INVAL;
 	*n = 0;
-	if (c->poisoned) {  // (copied[head] may never have been recorded: synchronising on it would succeed at once)
-		snprintf(g_err, sizeof(g_err), "an earlier submit failed half way: the context must be recreated");
-		return TFREC_AMD_E_STATE;
-	}
+	TRY(check_live(c));  // (copied[head] may never have been recorded: synchronising on it would succeed at once)
 	if (c->inflight == 0)
 		return TFREC_AMD_OK;
 	HIPCHK(hipSetDevice(c->cfg.device));
@@ -1310,10 +1315,7 @@ int tfrec_amd_drain_events(tfrec_amd_ctx *c, tfrec_amd_event *out, int cap, int 
 	if (!c || !n_out || cap < 0 || (cap > 0 && !out))
 		return TFREC_AMD_E_INVAL;
 	*n_out = 0;
-	if (c->poisoned) {
-		snprintf(g_err, sizeof(g_err), "an earlier submit failed half way: the context must be recreated");
-		return TFREC_AMD_E_STATE;
-	}
+	TRY(check_live(c));
 	if (c->inflight == 0)
 		return TFREC_AMD_OK;
 	HIPCHK(hipSetDevice(c->cfg.device));
@@ -1407,14 +1409,8 @@ int tfrec_amd_reset_streams(tfrec_amd_ctx *c, const int32_t *streams, int n)
 	if (!c || n < 0 || (n > 0 && !streams))
 		return TFREC_AMD_E_INVAL;
 	for (int i = 0; i < n; i++)
-		if (streams[i] < 0 || streams[i] >= c->cfg.n_streams) {
-			snprintf(g_err, sizeof(g_err), "stream index %d outside [0, %d)", (int)streams[i], c->cfg.n_streams);
-			return TFREC_AMD_E_INVAL;
-		}
-	if (c->poisoned) {
-		snprintf(g_err, sizeof(g_err), "an earlier submit failed half way: the context must be recreated");
-		return TFREC_AMD_E_STATE;
-	}
+		TRY(check_stream(c, streams[i]));
+	TRY(check_live(c));
 	for (int i = 0; i < n; i++)
 		if (!c->reset_marked[streams[i]]) {
 			c->reset_marked[streams[i]] = 1;
@@ -1429,10 +1425,7 @@ int tfrec_amd_configure_streams(tfrec_amd_ctx *c, const int32_t *streams, const 
 		return TFREC_AMD_E_INVAL;
 	for (int i = 0; i < n; i++) {
 		const tfrec_amd_stream_config &sc = cfgs[i];
-		if (streams[i] < 0 || streams[i] >= c->cfg.n_streams) {
-			snprintf(g_err, sizeof(g_err), "stream index %d outside [0, %d)", (int)streams[i], c->cfg.n_streams);
-			return TFREC_AMD_E_INVAL;
-		}
+		TRY(check_stream(c, streams[i]));
 		if (sc.types_mask == 0 || (sc.types_mask & ~c->cfg.types_mask) != 0 || sc.thresh < 0 || sc.filter_type < 0 ||
 		    sc.filter_type > 1 || sc.reserved != 0) {
 			snprintf(g_err, sizeof(g_err), "bad stream config (types_mask 0x%x of the context's 0x%x, thresh %d, filter_type %d, "
@@ -1441,10 +1434,7 @@ int tfrec_amd_configure_streams(tfrec_amd_ctx *c, const int32_t *streams, const 
 			return TFREC_AMD_E_INVAL;
 		}
 	}
-	if (c->poisoned) {
-		snprintf(g_err, sizeof(g_err), "an earlier submit failed half way: the context must be recreated");
-		return TFREC_AMD_E_STATE;
-	}
+	TRY(check_live(c));
 	if (n == 0)
 		return TFREC_AMD_OK;
 	// a configure is a reset with new settings: the stream restarts at the next submit (before the first one that restores
@@ -1622,16 +1612,17 @@ int tfrec_amd_get_timings(tfrec_amd_ctx *c, tfrec_amd_timings *out)
 	// the most recently drained submit; before the first drain: the oldest one in flight
 	const int set = c->last_drained >= 0 ? c->last_drained : c->head;
 	hipEvent_t *ev = c->ev[set], *tev = c->tev[set];
-	for (auto &e : c->done[set])
+	for (hipEvent_t e : c->pipe[set].done)
 		HIPCHK(hipEventSynchronize(e));
-	HIPCHK(hipEventElapsedTime(&out->frontend_ms, ev[0], ev[3]));
+	HIPCHK(hipEventElapsedTime(&out->frontend_ms, ev[kEvSubmit], ev[kEvFrontDone]));
 	if (TFREC_KNOB_STR("HOST_PROF") && c->hp_n > 2) {  // idle time of the front-end stream between two submits' front ends
 		float gap = 0, total = 0;
 		const int next = (set + 1) % kSets;  // (in flight: its front end started long ago)
-		if (hipEventElapsedTime(&gap, ev[3], c->ev[next][0]) == hipSuccess && hipEventElapsedTime(&total, ev[0], tev[20]) == hipSuccess &&
+		if (hipEventElapsedTime(&gap, ev[kEvFrontDone], c->ev[next][kEvSubmit]) == hipSuccess &&
+		    hipEventElapsedTime(&total, ev[kEvSubmit], tev[kMarkTfa1End]) == hipSuccess &&
 		    gap > -1000 && gap < 1000) {
 			float s2s = 0;
-			if (hipEventElapsedTime(&s2s, ev[0], c->ev[next][0]) == hipSuccess)
+			if (hipEventElapsedTime(&s2s, ev[kEvSubmit], c->ev[next][kEvSubmit]) == hipSuccess)
 				c->hp_s2s += s2s;
 			c->hp_gap += gap;
 			c->hp_lat += total;
@@ -1639,52 +1630,54 @@ int tfrec_amd_get_timings(tfrec_amd_ctx *c, tfrec_amd_timings *out)
 		}
 		(void)hipGetLastError();
 	}
-	HIPCHK(hipEventElapsedTime(&out->fmdev_ms, ev[3], ev[1]));
-	if (c->need_fmdev && c->fmdev_k2 && !(c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS))
-		HIPCHK(hipEventElapsedTime(&out->fmdev_ms, tev[24], tev[25]));
+	HIPCHK(hipEventElapsedTime(&out->fmdev_ms, ev[kEvFrontDone], ev[kEvFmdevDone]));
+	if (c->fmdev_k2)  // (the discriminator pass ran in the pipeline)
+		HIPCHK(hipEventElapsedTime(&out->fmdev_ms, tev[kMarkFmdev], tev[kMarkFmdevEnd]));
 	out->windows_ms = out->spec_biquad_ms = out->repair_biquad_ms = out->fix_biquad_ms = out->slicer_ms = 0;
 	out->coop_slicer_ms = out->decode_ms = out->commit_ms = 0;
 	out->whb_biquad_ms = out->whb_demod_ms = out->whb_decode_ms = out->whb_commit_ms = 0;
 	out->tfa1_slicer_ms = out->tfa1_coop_slicer_ms = out->tfa1_decode_commit_ms = 0;
 	out->whb_verify_ms = 0;
 	if (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) {
-		HIPCHK(hipEventElapsedTime(&out->chains_ms, ev[1], ev[2]));
-		HIPCHK(hipEventElapsedTime(&out->total_ms, ev[0], ev[2]));
+		HIPCHK(hipEventElapsedTime(&out->chains_ms, ev[kEvFmdevDone], ev[kEvSerialDone]));
+		HIPCHK(hipEventElapsedTime(&out->total_ms, ev[kEvSubmit], ev[kEvSerialDone]));
 		return TFREC_AMD_OK;
 	}
 	// the submit ends when the last of its three chains does
 	out->chains_ms = out->total_ms = 0;
-	bool has[3] = { false, false, false };  // TFA_2 family, WHB, TFA_1
-	for (int a = 0; a < c->launch.n_active; a++)
-		has[c->launch.params[a].kind == 1 ? 0 : (c->launch.params[a].kind == 2 ? 1 : 2)] = true;
-	const int last_mark[3] = { 8, 15, 20 };
-	for (int k = 0; k < 3; k++)
-		if (has[k]) {
+	const bool has_tfa2 = has_kind(c->launch, 1), has_whb = has_kind(c->launch, 2), has_tfa1 = has_kind(c->launch, 0);
+	const struct {
+		bool has;
+		int end;
+	} chain_end[3] = { { has_tfa2, kMarkTfa2End }, { has_whb, kMarkWhbCommitEnd }, { has_tfa1, kMarkTfa1End } };
+	for (const auto &ce : chain_end)
+		if (ce.has) {
 			float t = 0;
-			HIPCHK(hipEventElapsedTime(&t, ev[1], tev[last_mark[k]]));
+			HIPCHK(hipEventElapsedTime(&t, ev[kEvFmdevDone], tev[ce.end]));
 			out->chains_ms = std::max(out->chains_ms, t);
-			HIPCHK(hipEventElapsedTime(&t, ev[0], tev[last_mark[k]]));
+			HIPCHK(hipEventElapsedTime(&t, ev[kEvSubmit], tev[ce.end]));
 			out->total_ms = std::max(out->total_ms, t);
 		}
-	HIPCHK(hipEventElapsedTime(&out->windows_ms, tev[0], tev[21]));
-	if (has[0]) {
-		float *k2_ms[3] = { &out->spec_biquad_ms, &out->repair_biquad_ms, &out->fix_biquad_ms };
-		for (int k = 0; k < 3; k++)
-			HIPCHK(hipEventElapsedTime(k2_ms[k], tev[1 + k], tev[2 + k]));
-		HIPCHK(hipEventElapsedTime(&out->slicer_ms, tev[23], tev[5]));
-		HIPCHK(hipEventElapsedTime(&out->coop_slicer_ms, tev[5], tev[6]));
-		HIPCHK(hipEventElapsedTime(&out->decode_ms, tev[6], tev[7]));
-		HIPCHK(hipEventElapsedTime(&out->commit_ms, tev[7], tev[8]));
+	HIPCHK(hipEventElapsedTime(&out->windows_ms, tev[kMarkWindows], tev[kMarkWindowsEnd]));
+	if (has_tfa2) {
+		HIPCHK(hipEventElapsedTime(&out->spec_biquad_ms, tev[kMarkTfa2Spec], tev[kMarkTfa2Repair]));
+		HIPCHK(hipEventElapsedTime(&out->repair_biquad_ms, tev[kMarkTfa2Repair], tev[kMarkTfa2Fix]));
+		HIPCHK(hipEventElapsedTime(&out->fix_biquad_ms, tev[kMarkTfa2Fix], tev[kMarkTfa2BiquadEnd]));
+		HIPCHK(hipEventElapsedTime(&out->slicer_ms, tev[kMarkTfa2Slicer], tev[kMarkTfa2Coop]));
+		HIPCHK(hipEventElapsedTime(&out->coop_slicer_ms, tev[kMarkTfa2Coop], tev[kMarkTfa2Decode]));
+		HIPCHK(hipEventElapsedTime(&out->decode_ms, tev[kMarkTfa2Decode], tev[kMarkTfa2Commit]));
+		HIPCHK(hipEventElapsedTime(&out->commit_ms, tev[kMarkTfa2Commit], tev[kMarkTfa2End]));
 	}
-	if (has[2]) {
-		HIPCHK(hipEventElapsedTime(&out->tfa1_slicer_ms, tev[16], tev[17]));
-		HIPCHK(hipEventElapsedTime(&out->tfa1_coop_slicer_ms, tev[17], tev[18]));
-		HIPCHK(hipEventElapsedTime(&out->tfa1_decode_commit_ms, tev[18], tev[20]));
+	if (has_tfa1) {
+		HIPCHK(hipEventElapsedTime(&out->tfa1_slicer_ms, tev[kMarkTfa1Slicer], tev[kMarkTfa1Coop]));
+		HIPCHK(hipEventElapsedTime(&out->tfa1_coop_slicer_ms, tev[kMarkTfa1Coop], tev[kMarkTfa1Decode]));
+		HIPCHK(hipEventElapsedTime(&out->tfa1_decode_commit_ms, tev[kMarkTfa1Decode], tev[kMarkTfa1End]));
 	}
-	if (has[1]) {
-		HIPCHK(hipEventElapsedTime(&out->whb_biquad_ms, tev[9], tev[12]));
-		HIPCHK(hipEventElapsedTime(&out->whb_demod_ms, tev[22], tev[13]));
-		if (hipEventQuery(tev[27]) == hipSuccess && hipEventElapsedTime(&out->whb_verify_ms, tev[26], tev[27]) != hipSuccess)
+	if (has_whb) {
+		HIPCHK(hipEventElapsedTime(&out->whb_biquad_ms, tev[kMarkWhbSpec], tev[kMarkWhbBiquadEnd]));
+		HIPCHK(hipEventElapsedTime(&out->whb_demod_ms, tev[kMarkWhbDemod], tev[kMarkWhbDemodEnd]));
+		if (hipEventQuery(tev[kMarkWhbCheckEnd]) == hipSuccess &&
+		    hipEventElapsedTime(&out->whb_verify_ms, tev[kMarkWhbCheck], tev[kMarkWhbCheckEnd]) != hipSuccess)
 			out->whb_verify_ms = 0;
 		(void)hipGetLastError();
 		// whb_decode_ms / whb_commit_ms stay 0: those stages run in the tail of whb_demod_kernel

@@ -177,13 +177,7 @@ hipError_t launch_pipeline(const PipeCtl &P, const uint32_t *dec, size_t dec_str
 			   long long sample_base, const ChainLaunch &L, const WinTables &T, int16_t *ld16, int32_t *dev32,
 			   tfrec_amd_event *events, EventBuf *eb, uint32_t flags)
 {
-	// P.tev (optional, kTimingMarks events), one interval per kernel:
-	//   ws : 0 | windows | 21
-	//   k2 : 1 | spec | 2 | repair | 3 | fix | 4(k2)        cs : 23 | slicer | 5 | coop_slicer | 6 | decode | 7 | commit | 8
-	//   kw : 9 | spec | 10 | repair | 11 | fix | 12          aux: 22 | whb_demod (+ decoder tail) | 13 = 14 = 15
-	//   fq : 24 | fmdev | 25  (k2 when the discriminator pass has no stream of its own)
-	//   t1 : 16 | mark + slicer | 17 | coop_slicer | 18 | decode | 19 | commit | 20
-	//   vx : 26 | whb_chain + whb_check + redo | 27
+	// P.tev (optional): one interval per kernel, TimingMark (tfrec_dev.h)
 	auto mark = [&](int k, hipStream_t s_) {
 		if (P.tev)
 			(void)hipEventRecord(P.tev[k], s_);
@@ -228,22 +222,17 @@ hipError_t launch_pipeline(const PipeCtl &P, const uint32_t *dec, size_t dec_str
 	const int coop_blocks = std::min(32768, std::max(1, (int)std::min<size_t>((size_t)L.n_active * n_streams *
 								((size_t)n_blocks * kBlockDec / (size_t)long_window + 1), 1u << 30)));
 	const int dec_blocks = std::min(16384, std::max(1, win_blocks));
-	bool has_whb = false, has_tfa2 = false, has_tfa1 = false;
-	for (int a = 0; a < L.n_active; a++) {
-		has_whb = has_whb || L.params[a].kind == 2;
-		has_tfa2 = has_tfa2 || L.params[a].kind == 1;
-		has_tfa1 = has_tfa1 || L.params[a].kind == 0;
-	}
+	const bool has_whb = has_kind(L, 2), has_tfa2 = has_kind(L, 1), has_tfa1 = has_kind(L, 0);
 	// ---- window scan: behind the front end on its stream, or -- deep layout -- at the head of the WHB biquad stream
 	// (the front-end stream is the busiest of all: 0.3-1.1 ms less on it per batch); consecutive scans stay in order
 	// on one stream either way (timeout_carry)
 	if (P.ws != P.fs)
 		TRY(hipStreamWaitEvent(P.ws, P.ev_front, 0));
 	TRY(hipMemsetAsync(T.queue, 0, (kNQueues + 1) * sizeof(WorkQueue), P.ws));
-	mark(0, P.ws);
+	mark(kMarkWindows, P.ws);
 	hipLaunchKernelGGL(windows_kernel, dim3(n_streams), block, 0, P.ws, mask, mask_stride, n_streams, n_blocks, L, T,
 			   long_window);
-	mark(21, P.ws);
+	mark(kMarkWindowsEnd, P.ws);
 	TRY(hipEventRecord(P.ev_win, P.ws));
 	// Independent kernel chains after the scan (they touch disjoint state):
 	//   kw -> aux: WHB          spec -> repair -> fix (biquad) | whb_demod -> whb_decode -> whb_commit
@@ -253,21 +242,21 @@ hipError_t launch_pipeline(const PipeCtl &P, const uint32_t *dec, size_t dec_str
 	int whb_spec = -1;  // the WHB slot, when its speculative stage 2 ran
 	if (has_whb) {
 		TRY(hipStreamWaitEvent(P.kw, P.ev_win, 0));
-		mark(9, P.kw);
+		mark(kMarkWhbSpec, P.kw);
 		hipLaunchKernelGGL((spec_biquad_kernel<true, 0>), dim3(spec_blocks), block, K3Tile<true>::kSize, P.kw, dec, dec_stride, fmdev, fmdev_stride,
 				   n_streams, n_blocks, L, T, ld16, dev32, lanes);
-		mark(10, P.kw);
+		mark(kMarkWhbRepair, P.kw);
 		hipLaunchKernelGGL((spec_biquad_kernel<true, 1>), dim3(repair_blocks), block, K3Tile<true>::kSize, P.kw, dec, dec_stride, fmdev, fmdev_stride,
 				   n_streams, n_blocks, L, T, ld16, dev32, lanes);
 		hipLaunchKernelGGL((spec_biquad_kernel<true, 2>), dim3(repair_blocks), block, K3Tile<true>::kSize, P.kw, dec, dec_stride, fmdev, fmdev_stride,
 				   n_streams, n_blocks, L, T, ld16, dev32, lanes);
-		mark(11, P.kw);
+		mark(kMarkWhbFix, P.kw);
 		hipLaunchKernelGGL(fix_biquad_kernel, dim3(n_streams, L.n_active), block, 0, P.kw, dec, dec_stride, fmdev, fmdev_stride,
 				   n_streams, n_blocks, L, T, ld16, dev32, 2);
-		mark(12, P.kw);
+		mark(kMarkWhbBiquadEnd, P.kw);
 		TRY(hipEventRecord(P.ev_kw, P.kw));
 		TRY(hipStreamWaitEvent(P.aux, P.ev_kw, 0));
-		mark(22, P.aux);
+		mark(kMarkWhbDemod, P.aux);
 		for (int a = 0; a < L.n_active; a++)
 			if (L.params[a].kind == 2) {
 				// 4 KB of dynamic LDS for the decoder tail (64 lanes x rdata[0 .. 64)).  The kernel is launched while the other
@@ -285,9 +274,9 @@ hipError_t launch_pipeline(const PipeCtl &P, const uint32_t *dec, size_t dec_str
 							   n_blocks, sample_base, L, a, T, events, eb, flags);
 					whb_spec = a;
 				}
-				mark(13, P.aux);
-				mark(14, P.aux);
-				mark(15, P.aux);
+				mark(kMarkWhbDemodEnd, P.aux);
+				mark(kMarkWhbDecodeEnd, P.aux);
+				mark(kMarkWhbCommitEnd, P.aux);
 			}
 	}
 	if (whb_spec >= 0) {  // stage C of WHB: a serial chain per lane, a few dozen waves
@@ -295,12 +284,8 @@ hipError_t launch_pipeline(const PipeCtl &P, const uint32_t *dec, size_t dec_str
 			TRY(hipEventRecord(P.ev_aux, P.aux));
 			TRY(hipStreamWaitEvent(P.vx, P.ev_aux, 0));
 		}
-		mark(26, P.vx);
+		mark(kMarkWhbCheck, P.vx);
 		// The check: the exact chain a stream per LANE over the filter's input sequence, then the records against it (whb_check.h)
-		static const hipError_t lds_ok = hipFuncSetAttribute(reinterpret_cast<const void *>(&whb_chain_kernel),
-								     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kChkLdsBytes);
-		if (lds_ok != hipSuccess)
-			return lds_ok;
 		hipLaunchKernelGGL(whb_chain_kernel, dim3((n_streams + kChkStreams - 1) / kChkStreams), dim3(64 * (1 + kChkProducers)), kChkLdsBytes,
 				   P.vx, n_streams, L, whb_spec, T);
 		hipLaunchKernelGGL(whb_check_kernel, dim3(n_streams), block, 0, P.vx, n_streams, L, whb_spec, T, P.whb_carry);
@@ -312,12 +297,13 @@ hipError_t launch_pipeline(const PipeCtl &P, const uint32_t *dec, size_t dec_str
 		Lr.states[whb_spec] = T.whbscr;
 		hipLaunchKernelGGL((whb_demod_kernel<true, true>), dim3((n_streams + 63) / 64), block, 64 * 64, P.vx, dec, dec_stride, dev32, n_streams,
 				   n_blocks, sample_base, Lr, whb_spec, Tr, events, eb, flags);
-		mark(27, P.vx);
+		mark(kMarkWhbCheckEnd, P.vx);
 		TRY(hipEventRecord(P.done[1], P.vx));
 	} else {
 		TRY(hipEventRecord(P.done[1], P.aux));
 	}
-	// the slicer -> decoder chain of one protocol kind (0: TFA_1, 1: TFA_2 family) on stream s_
+	// the slicer -> decoder chain of one protocol kind (0: TFA_1, 1: TFA_2 family) on stream s_; m0: its Coop mark
+	static_assert(kMarkTfa2End == kMarkTfa2Coop + 3 && kMarkTfa1End == kMarkTfa1Coop + 3, "a slicer chain's marks are consecutive");
 	auto slicer_chain = [&](int kind, hipStream_t s_, int m0) {
 		if (kind == 0)
 			hipLaunchKernelGGL(mark_kernel, dim3(std::max(1, win_blocks / 16)), dim3(256), 0, s_, dec, dec_stride, n_streams,
@@ -327,18 +313,18 @@ hipError_t launch_pipeline(const PipeCtl &P, const uint32_t *dec, size_t dec_str
 		const size_t slds = (kind == 0 ? 8 : 4) * 64 * sizeof(uint4);
 		hipLaunchKernelGGL(slicer_kernel, dim3(std::max(64, win_blocks)), block, slds, s_, dec, dec_stride, ld16, n_streams, n_blocks, L, T,
 				   lanes, head_chunks, kind, 0);
-		mark(m0 + 1, s_);
+		mark(m0, s_);
 		hipLaunchKernelGGL(coop_slicer_kernel, dim3(coop_blocks), block, 0, s_, dec, dec_stride, ld16, n_streams, n_blocks, L,
 				   T, kind);
-		mark(m0 + 2, s_);
+		mark(m0 + 1, s_);
 		hipLaunchKernelGGL(decode_kernel, dim3(dec_blocks), block, 0, s_, n_streams, L, T, kind);
-		mark(m0 + 3, s_);
+		mark(m0 + 2, s_);
 		hipLaunchKernelGGL(commit_kernel, grid, block, 0, s_, dec, dec_stride, ld16, n_streams, n_blocks, sample_base, L, T,
 				   events, eb, flags, lanes, kind);
 		if (kind == 1)  // the few chains (normally none) with a window to slice again
 			hipLaunchKernelGGL(commit_wave_kernel, dim3(256), block, 0, s_, dec, dec_stride, ld16, n_streams, n_blocks,
 					   sample_base, L, T, events, eb, flags);
-		mark(m0 + 4, s_);
+		mark(m0 + 3, s_);
 	};
 	// ---- TFA_2 family
 	if (has_tfa2) {
@@ -347,17 +333,17 @@ hipError_t launch_pipeline(const PipeCtl &P, const uint32_t *dec, size_t dec_str
 			// the discriminator pass on a stream of its own: it needs the front end only, not the window scan, and k2 --
 			// discriminator + five biquad kernels -- is the stream that sets the period
 			TRY(hipStreamWaitEvent(P.fq, P.ev_front, 0));
-			mark(24, P.fq);
+			mark(kMarkFmdev, P.fq);
 			TRY(launch_fmdev(P.fq, dec, dec_stride, mask, mask_stride, P.prevdec, P.fmdev_out, fmdev_stride, eb, n_streams,
 					 n_blocks, P.fmdev_wmax, P.fm_flag_eps));
-			mark(25, P.fq);
+			mark(kMarkFmdevEnd, P.fq);
 			TRY(hipEventRecord(P.ev_fm, P.fq));
 			TRY(hipStreamWaitEvent(P.k2, P.ev_fm, 0));
 		} else if (P.fmdev_wmax > 0) {
-			mark(24, P.k2);
+			mark(kMarkFmdev, P.k2);
 			TRY(launch_fmdev(P.k2, dec, dec_stride, mask, mask_stride, P.prevdec, P.fmdev_out, fmdev_stride, eb, n_streams,
 					 n_blocks, P.fmdev_wmax, P.fm_flag_eps));
-			mark(25, P.k2);
+			mark(kMarkFmdevEnd, P.k2);
 		}
 		// The speculative pass needs the discriminator pass and the window scan of ITS submit only (every segment starts from
 		// zero): on a stream of its own (ks) it runs beside the repair passes and the chain walk of the submit before, which
@@ -367,10 +353,10 @@ hipError_t launch_pipeline(const PipeCtl &P, const uint32_t *dec, size_t dec_str
 			TRY(hipStreamWaitEvent(sp, P.ev_win, 0));
 			TRY(hipStreamWaitEvent(sp, P.ev_fm, 0));
 		}
-		mark(1, sp);
+		mark(kMarkTfa2Spec, sp);
 		hipLaunchKernelGGL((spec_biquad_kernel<false, 0>), dim3(spec_blocks), block, K3Tile<false>::kSize, sp, dec, dec_stride, fmdev, fmdev_stride,
 				   n_streams, n_blocks, L, T, ld16, dev32, lanes);
-		mark(2, sp);
+		mark(kMarkTfa2Repair, sp);
 		if (sp != P.k2) {
 			TRY(hipEventRecord(P.ev_spec, sp));
 			TRY(hipStreamWaitEvent(P.k2, P.ev_spec, 0));
@@ -385,26 +371,34 @@ hipError_t launch_pipeline(const PipeCtl &P, const uint32_t *dec, size_t dec_str
 				   n_streams, n_blocks, L, T, ld16, dev32, lanes);
 		hipLaunchKernelGGL((spec_biquad_kernel<false, 2>), dim3(repair_blocks), block, K3Tile<false>::kSize, P.k2, dec, dec_stride, fmdev, fmdev_stride,
 				   n_streams, n_blocks, L, T, ld16, dev32, lanes);
-		mark(3, P.k2);
+		mark(kMarkTfa2Fix, P.k2);
 		hipLaunchKernelGGL(fix_biquad_kernel, dim3(n_streams, L.n_active), block, 0, P.k2, dec, dec_stride, fmdev, fmdev_stride,
 				   n_streams, n_blocks, L, T, ld16, dev32, 1);
-		mark(4, P.k2);
+		mark(kMarkTfa2BiquadEnd, P.k2);
 		TRY(hipEventRecord(P.ev_k2, P.k2));
 		TRY(hipStreamWaitEvent(P.cs, P.ev_k2, 0));
-		mark(23, P.cs);
-		slicer_chain(1, P.cs, 4);  // marks 5..8
+		mark(kMarkTfa2Slicer, P.cs);
+		slicer_chain(1, P.cs, kMarkTfa2Coop);
 	}
 	TRY(hipEventRecord(P.done[0], P.cs));
 	// ---- TFA_1
 	if (has_tfa1) {
 		if (!has_tfa2)  // (else it waits for the speculative pass: above)
 			TRY(hipStreamWaitEvent(P.t1, P.ev_win, 0));
-		mark(16, P.t1);
-		slicer_chain(0, P.t1, 16);  // marks 17..20
+		mark(kMarkTfa1Slicer, P.t1);
+		slicer_chain(0, P.t1, kMarkTfa1Coop);
 	}
 	TRY(hipEventRecord(P.done[2], P.t1));
 #undef TRY
 	return hipGetLastError();
+}
+
+// whb_chain_kernel's dynamic LDS (kChkLdsBytes) is above the default limit: the opt-in is a function attribute of the current
+// device, so tfrec_amd_create sets it for each context after hipSetDevice
+hipError_t whb_chain_lds_optin()
+{
+	return hipFuncSetAttribute(reinterpret_cast<const void *>(&whb_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+				   (int)kChkLdsBytes);
 }
 
 }  // namespace tfrec

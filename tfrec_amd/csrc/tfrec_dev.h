@@ -350,7 +350,7 @@ struct PipeCtl {
 	hipStream_t ks;            // the speculative pass of the TFA_2 family's biquads (needs fq), or nullptr: at the head of k2
 	hipEvent_t ev_spec;        // ... done (ks): the repair passes on k2 start
 	hipEvent_t done[3];        // end of the submit on cs / aux / t1
-	hipEvent_t *tev;           // optional timing marks (kTimingMarks)
+	hipEvent_t *tev;           // optional timing marks (TimingMark)
 	// the FM discriminator pass, when it runs at the head of stage A of the TFA_2 family (k2) instead of behind the
 	// front end (its only consumer is that stage): wmax > 0
 	int fmdev_wmax;
@@ -358,7 +358,36 @@ struct PipeCtl {
 	int16_t *fmdev_out;
 	const uint32_t *prevdec;
 };
-constexpr int kTimingMarks = 28;
+// PipeCtl::tev: launch_pipeline's timing marks, one interval per kernel (tfrec_amd_get_timings reads them), stream by stream:
+//   ws : Windows | windows | WindowsEnd
+//   k2 : Tfa2Spec | spec | Tfa2Repair | repair | Tfa2Fix | fix | Tfa2BiquadEnd      (spec on ks when it has that stream)
+//   cs : Tfa2Slicer | slicer | Tfa2Coop | coop_slicer | Tfa2Decode | decode | Tfa2Commit | commit | Tfa2End
+//   kw : WhbSpec | spec | WhbRepair | repair | WhbFix | fix | WhbBiquadEnd
+//   aux: WhbDemod | whb_demod (+ decoder tail) | WhbDemodEnd = WhbDecodeEnd = WhbCommitEnd
+//   fq : Fmdev | fmdev | FmdevEnd  (k2 when the discriminator pass has no stream of its own)
+//   t1 : Tfa1Slicer | mark + slicer | Tfa1Coop | coop_slicer | Tfa1Decode | decode | Tfa1Commit | commit | Tfa1End
+//   vx : WhbCheck | whb_chain + whb_check + redo | WhbCheckEnd
+// The values are the event slots: Coop .. End of a slicer chain are consecutive (launch_pipeline's slicer_chain).
+enum TimingMark : int {
+	kMarkWindows = 0,
+	kMarkTfa2Spec = 1, kMarkTfa2Repair = 2, kMarkTfa2Fix = 3, kMarkTfa2BiquadEnd = 4,
+	kMarkTfa2Coop = 5, kMarkTfa2Decode = 6, kMarkTfa2Commit = 7, kMarkTfa2End = 8,
+	kMarkWhbSpec = 9, kMarkWhbRepair = 10, kMarkWhbFix = 11, kMarkWhbBiquadEnd = 12,
+	kMarkWhbDemodEnd = 13, kMarkWhbDecodeEnd = 14, kMarkWhbCommitEnd = 15,
+	kMarkTfa1Slicer = 16, kMarkTfa1Coop = 17, kMarkTfa1Decode = 18, kMarkTfa1Commit = 19, kMarkTfa1End = 20,
+	kMarkWindowsEnd = 21, kMarkWhbDemod = 22, kMarkTfa2Slicer = 23, kMarkFmdev = 24, kMarkFmdevEnd = 25,
+	kMarkWhbCheck = 26, kMarkWhbCheckEnd = 27,
+	kTimingMarks = 28
+};
+
+// a chain of protocol kind `kind` (ChainParams::kind) is registered
+inline bool has_kind(const ChainLaunch &L, int kind)
+{
+	for (int a = 0; a < L.n_active; a++)
+		if (L.params[a].kind == kind)
+			return true;
+	return false;
+}
 
 constexpr int kNQueues = 8;
 // one more counter after the work queues, with a (stream, slot) list behind the queues' items: the TFA_2-family
