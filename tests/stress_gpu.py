@@ -7,7 +7,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from oracle import oracle as O  # noqa: E402
+import parity  # noqa: E402
 from tfrec_amd import api, synth  # noqa: E402
 
 
@@ -40,8 +40,8 @@ def _round(rng, rnd, verbose):
             evs = []
             k = 0
             pend = 0
-            for a, b in zip(cuts, cuts[1:]):
-                r.submit(np.ascontiguousarray(iq[:, a * 65536:b * 65536]))
+            for p in parity.cut(iq, np.diff(cuts)):
+                r.submit(p)
                 pend += 1
                 if pend == api.FIFO_DEPTH or rng.integers(0, 2):  # sometimes several submits in flight
                     keep = int(rng.integers(0, pend))              # ... and sometimes the younger ones stay in flight
@@ -54,9 +54,7 @@ def _round(rng, rnd, verbose):
             ev = np.concatenate(evs) if evs else np.zeros(0, api.EVENT_DTYPE)
             ok = True
             for s in range(n_streams):
-                o = O.Oracle(types, thresh, wide)
-                o.process(iq[s])
-                want = sorted(o.events_full())
+                want = sorted(parity.fresh_oracle(iq[s], types, thresh, wide).events_full())
                 got = sorted(api.event_tuples_full(ev, s))
                 if got != want:
                     ok = False

@@ -8,38 +8,13 @@ import os
 import numpy as np
 import pytest
 
+import parity
 from oracle import oracle as O
 from tfrec_amd import api, synth
 
 pytestmark = pytest.mark.gpu
 
-
-def oracle_events(iq, types, thresh, wide=0):
-    o = O.Oracle(types, thresh, wide, keep_dec=True)
-    o.process(iq)
-    return o
-
-
-def by_slot(evs):
-    d = {}
-    for e in evs:
-        d.setdefault(e[0], []).append(e)
-    return d
-
-
-def check_stream(gpu_events, stream, orc, min_bytes_only=False):
-    # full tuples: ..., rssi_raw (the accumulator itself, not only its dB value: BASELINE.md 3 "raw RSSI and offset integers
-    # identical"), status (the decoder's CRC / sanity verdict of every event, computed on the GPU)
-    g = by_slot(api.event_tuples_full(gpu_events, stream))
-    oe = orc.events_full()
-    if min_bytes_only:
-        minb = {0: 10, 1: 7, 2: 7, 3: 7, 4: 11}
-        oe = [e for e in oe if e[2] >= minb[e[0]] and not (e[0] == 3 and e[2] >= 64) and not (e[0] == 4 and e[2] > 60)]
-    o = by_slot(oe)
-    assert sorted(g.keys()) == sorted(o.keys())
-    for slot in o:
-        assert g[slot] == o[slot], "stream %d slot %d" % (stream, slot)
-    return sum(len(v) for v in o.values())
+_all_streams_equal = parity.assert_all_streams  # (profiles/ubench/fullsize_check.py imports it from here)
 
 
 @pytest.mark.parametrize("wide", [0, 1])
@@ -70,7 +45,7 @@ def test_all_flush_events_match_oracle(serial):
         ev = r.drain()
         total = 0
         for s in range(n_streams):
-            total += check_stream(ev, s, oracle_events(iq[s], 0x2F, 500))
+            total += parity.assert_stream(ev, s, parity.fresh_oracle(iq[s], 0x2F, 500))
         assert total > 20 * n_streams
         assert r.fm_stats()["host_mismatch"] == 0
 
@@ -82,8 +57,8 @@ def test_default_mode_reports_candidates_with_verdict():
         r.submit(iq)
         ev = r.drain()
         for s in range(n_streams):
-            orc = oracle_events(iq[s], 0x2F, 500)
-            check_stream(ev, s, orc, min_bytes_only=True)
+            orc = parity.fresh_oracle(iq[s], 0x2F, 500)
+            parity.assert_stream(ev, s, orc, default_mode=True)
             # status==1 events are exactly the flushes that produced telegram text in the reference
             n_ok = int(np.sum((ev["stream"] == s) & (ev["status"] == 1)))
             lines = [ln for ln in orc.text().splitlines() if not ln.startswith("Inverted") and not ln.startswith("WHB:")]
@@ -104,7 +79,7 @@ def test_planted_crc_and_sanity_failures_status_per_event(serial, all_flushes):
         r.submit(iq)
         ev = r.drain()
         for s in range(n_streams):
-            check_stream(ev, s, oracle_events(iq[s], 0x2F, 500), min_bytes_only=not all_flushes)
+            parity.assert_stream(ev, s, parity.fresh_oracle(iq[s], 0x2F, 500), default_mode=not all_flushes)
         for st in seen:
             seen[st] = int(np.sum(ev["status"] == st))
     # planted: rejected telegrams of every protocol next to accepted ones
@@ -118,16 +93,9 @@ def test_state_carries_across_submits(serial):
     n_streams = 5
     iq = synth.gen_batch(11, 7, n_streams, 24)
     with api.Receiver(n_streams, 0x2F, 500, 0, max_blocks=16, all_flushes=True, serial_chains=serial) as r:
-        evs = []
-        pos = 0
-        for nb in (1, 7, 3, 13):
-            r.submit(np.ascontiguousarray(iq[:, pos * 65536:(pos + nb) * 65536]))
-            evs.append(r.drain())
-            pos += nb
-        ev = np.concatenate(evs)
-        ev = ev[np.lexsort((ev["seq"], ev["slot"], ev["stream"]))]
+        ev = parity.sort_events(np.concatenate(parity.run_fifo(r, parity.cut(iq, (1, 7, 3, 13)), depth=1)))
         for s in range(n_streams):
-            check_stream(ev, s, oracle_events(iq[s], 0x2F, 500))
+            parity.assert_stream(ev, s, parity.fresh_oracle(iq[s], 0x2F, 500))
 
 
 @SERIAL
@@ -139,7 +107,7 @@ def test_type_masks_and_thresholds(types, thresh, serial):
         r.submit(iq)
         ev = r.drain()
         for s in range(n_streams):
-            check_stream(ev, s, oracle_events(iq[s], types, thresh))
+            parity.assert_stream(ev, s, parity.fresh_oracle(iq[s], types, thresh))
 
 
 def test_device_resident_input_and_timings():
@@ -154,7 +122,7 @@ def test_device_resident_input_and_timings():
         t = r.timings()
         assert t["frontend_ms"] > 0 and t["chains_ms"] > 0
         for s in range(n_streams):
-            check_stream(ev, s, oracle_events(iq[s], 0x2F, 500))
+            parity.assert_stream(ev, s, parity.fresh_oracle(iq[s], 0x2F, 500))
 
 
 def test_whb_contexts_on_two_devices():
@@ -175,7 +143,7 @@ def test_whb_contexts_on_two_devices():
         for r in rs:
             r.close()
     for d in range(2):
-        assert sum(check_stream(evs[d], s, oracle_events(iq[d][s], 0x2F, 500)) for s in range(n_streams)) > 0
+        assert sum(parity.assert_stream(evs[d], s, parity.fresh_oracle(iq[d][s], 0x2F, 500)) for s in range(n_streams)) > 0
 
 
 def _stress_batch():
@@ -204,15 +172,10 @@ def test_stress_sporadic_triggers(serial, thresh):
     with api.Receiver(n_streams, 0x2F, thresh, 0, max_blocks=n_blocks, all_flushes=True, serial_chains=serial,
                       max_events=400000) as r:
         # two submits so that windows straddle the submit boundary as well
-        r.submit(np.ascontiguousarray(iq[:, : 5 * 65536]))
-        e1 = r.drain()
-        r.submit(np.ascontiguousarray(iq[:, 5 * 65536:]))
-        e2 = r.drain()
-        ev = np.concatenate([e1, e2])
-        ev = ev[np.lexsort((ev["seq"], ev["slot"], ev["stream"]))]
+        ev = parity.sort_events(np.concatenate(parity.run_fifo(r, parity.cut(iq, (5, n_blocks - 5)), depth=1)))
         total = 0
         for s in range(n_streams):
-            total += check_stream(ev, s, oracle_events(iq[s], 0x2F, thresh))
+            total += parity.assert_stream(ev, s, parity.fresh_oracle(iq[s], 0x2F, thresh))
         assert total > 500
 
 
@@ -227,16 +190,12 @@ def test_auto_threshold_matches_oracle(serial):
     iq = np.stack(rows)
     with api.Receiver(iq.shape[0], 0x2F, 0, 0, max_blocks=20, all_flushes=True, serial_chains=serial,
                       max_events=200000) as r:
-        evs = []
-        for a, b in ((0, 20), (20, 33), (33, 48)):  # thresholds must carry across submits
-            r.submit(np.ascontiguousarray(iq[:, a * 65536:b * 65536]))
-            evs.append(r.drain())
-        ev = np.concatenate(evs)
-        ev = ev[np.lexsort((ev["seq"], ev["slot"], ev["stream"]))]
+        # thresholds must carry across submits
+        ev = parity.sort_events(np.concatenate(parity.run_fifo(r, parity.cut(iq, (20, 13, 15)), depth=1)))
         moved = 0
         for s in range(iq.shape[0]):
-            o = oracle_events(iq[s], 0x2F, 0)
-            check_stream(ev, s, o)
+            o = parity.fresh_oracle(iq[s], 0x2F, 0)
+            parity.assert_stream(ev, s, o)
             assert r.thresh(s) == o.thresh(), "stream %d" % s
             moved += int(o.thresh() != 500)
         assert moved >= 2
@@ -246,15 +205,12 @@ def test_submits_in_flight_fifo():
     """Submits k+1 .. k+3 may be queued before submit k is drained (FIFO of depth four); a fifth one is refused."""
     n_streams = 6
     iq = synth.gen_batch(23, 5, n_streams, 40)
-    parts = [np.ascontiguousarray(iq[:, a * 65536:b * 65536]) for a, b in ((0, 8), (8, 16), (16, 24), (24, 32), (32, 40))]
+    parts = parity.cut(iq, (8,) * 5)
     with api.Receiver(n_streams, 0x2F, 500, 0, max_blocks=10, all_flushes=True) as r:
-        ref = []
-        for p in parts:
-            r.submit(p)
-            ref.append(r.drain())
+        ref = parity.run_fifo(r, parts, depth=1)
     with api.Receiver(n_streams, 0x2F, 500, 0, max_blocks=10, all_flushes=True) as r:
         import torch
-        dev = [torch.from_numpy(p).cuda() for p in parts]
+        dev = [torch.from_numpy(np.ascontiguousarray(p)).cuda() for p in parts]
         got = []
         assert api.FIFO_DEPTH == 4
         for k in range(4):
@@ -276,21 +232,20 @@ def test_drain_fetches_events_beyond_the_copy_queued_at_submit(monkeypatch):
     with more events than that must still deliver all of them, in the same order."""
     n_streams = 6
     iq = synth.gen_batch(29, 11, n_streams, 24)
-    parts = [np.ascontiguousarray(iq[:, a * 65536:b * 65536]) for a, b in ((0, 2), (2, 14), (14, 24))]
+    parts = parity.cut(iq, (2, 12, 10))
     out = {}
     for guess in (None, "1"):
         if guess:
             monkeypatch.setenv("TFREC_AMD_COPY_GUESS_MIN", guess)
         with api.Receiver(n_streams, 0x2F, 500, 0, max_blocks=12, all_flushes=True, experiments=True) as r:
-            for p in parts:  # queued together: the guesses of the 2nd and 3rd submit come from before the 1st drain
-                r.submit(p)
-            out[guess] = [r.drain() for _ in parts]
+            # queued together: the guesses of the 2nd and 3rd submit come from before the 1st drain
+            out[guess] = parity.run_fifo(r, parts, depth=len(parts))
     assert sum(len(e) for e in out[None]) > 50
     for a, b in zip(out[None], out["1"]):
         assert a.tobytes() == b.tobytes()
-    ev = np.concatenate(out["1"])
+    ev = parity.sort_events(np.concatenate(out["1"]))
     for s in range(n_streams):
-        check_stream(ev[np.lexsort((ev["seq"], ev["slot"], ev["stream"]))], s, oracle_events(iq[s], 0x2F, 500))
+        parity.assert_stream(ev, s, parity.fresh_oracle(iq[s], 0x2F, 500))
 
 
 def test_config5_10x_front_end():
@@ -308,13 +263,10 @@ def test_config5_10x_front_end():
                 want = O.decim10(iq[s, : b * 655360])[2 * a * 32768:]
                 got = r.stage0(s, (b - a) * 32768)
                 assert np.array_equal(got, want), "10:1 stage, stream %d" % s
-        ev = np.concatenate(evs)
-        ev = ev[np.lexsort((ev["seq"], ev["slot"], ev["stream"]))]
+        ev = parity.sort_events(np.concatenate(evs))
         total = 0
         for s in range(n_streams):
-            o = O.Oracle(0x2F, 500, 0)
-            o.process_s16(O.decim10(iq[s]))
-            total += check_stream(ev, s, o)
+            total += parity.assert_stream(ev, s, parity.fresh_oracle(iq[s], 0x2F, 500, in10x=True))
         assert total >= 10
 
 
@@ -331,7 +283,7 @@ def test_config5_full_length_batch_of_64_streams():
         ev = r.drain()
         assert r.fm_stats()["host_mismatch"] == 0
         stage0 = [r.stage0(s, n_blocks * 32768) for s in range(n_unique)]
-    ev = ev[np.lexsort((ev["seq"], ev["slot"], ev["stream"]))]
+    ev = parity.sort_events(ev)
     total = 0
     for s in range(n_unique):
         want = O.decim10(base[s])
@@ -339,7 +291,7 @@ def test_config5_full_length_batch_of_64_streams():
         o = O.Oracle(0x2F, 500, 0)
         o.process_s16(want)
         for k in range(copies):
-            total += check_stream(ev, s + k * n_unique, o)
+            total += parity.assert_stream(ev, s + k * n_unique, o)
     assert total >= 40 * copies
 
 
@@ -369,7 +321,7 @@ def test_full_size_pipeline_equals_serial_chains_and_replicas():
         rep["stream"] -= k * n_unique
         assert rep.tobytes() == first.tobytes()
     for s in (0, 17, 47):
-        check_stream(a, s, oracle_events(base[s], 0x2F, 500))
+        parity.assert_stream(a, s, parity.fresh_oracle(base[s], 0x2F, 500))
 
 
 def test_tfa2_edge_timing_speculation_failure_is_resliced_exactly():
@@ -380,15 +332,10 @@ def test_tfa2_edge_timing_speculation_failure_is_resliced_exactly():
     n_blocks = 12
     iq = np.concatenate([synth.gen_batch(1000, s, 1, n_blocks) for s in (2387, 3079)])
     with api.Receiver(2, 0x2F, 500, 0, max_blocks=n_blocks, all_flushes=True) as r:
-        evs = []
-        for _ in range(2):
-            r.submit(iq)
-            evs.append(r.drain())
+        ev = parity.sort_events(np.concatenate(parity.run_fifo(r, [iq, iq], depth=1)))
         assert r.stats()["tfa2_resliced"] > 0
-        ev = np.concatenate(evs)
-        ev = ev[np.lexsort((ev["seq"], ev["slot"], ev["stream"]))]
     for s in range(2):
-        check_stream(ev, s, oracle_events(np.concatenate([iq[s], iq[s]]), 0x2F, 500))
+        parity.assert_stream(ev, s, parity.fresh_oracle(np.concatenate([iq[s], iq[s]]), 0x2F, 500))
 
 
 def test_deep_and_shallow_layouts_agree_across_submits(monkeypatch):
@@ -402,22 +349,10 @@ def test_deep_and_shallow_layouts_agree_across_submits(monkeypatch):
         monkeypatch.setenv("TFREC_AMD_DEEP", deep)
         with api.Receiver(n_streams, 0x2F, 500, 0, max_blocks=max(cuts), all_flushes=True, experiments=True) as r:
             assert r.layout() == (6 if deep == "1" else 4)
-            evs, pos, pending = [], 0, 0
-            for nb in cuts:
-                r.submit(np.ascontiguousarray(iq[:, pos * 65536:(pos + nb) * 65536]))
-                pos += nb
-                pending += 1
-                if pending == api.FIFO_DEPTH:
-                    evs.append(r.drain())
-                    pending -= 1
-            while pending:
-                evs.append(r.drain())
-                pending -= 1
-            ev = np.concatenate(evs)
-            got[deep] = ev[np.lexsort((ev["seq"], ev["slot"], ev["stream"]))]
+            got[deep] = parity.sort_events(np.concatenate(parity.run_fifo(r, parity.cut(iq, cuts))))
     assert got["1"].tobytes() == got["0"].tobytes()
     for s in range(n_streams):
-        check_stream(got["1"], s, oracle_events(iq[s], 0x2F, 500))
+        parity.assert_stream(got["1"], s, parity.fresh_oracle(iq[s], 0x2F, 500))
 
 
 def test_randomised_campaign():
@@ -471,11 +406,10 @@ def test_fm_dev_slow_path_through_the_pipeline(eps, monkeypatch):
     n_streams, n_blocks = 4, 16
     iq = synth.gen_batch(31, 7, n_streams, n_blocks)
     with api.Receiver(n_streams, 0x2F, 500, 0, max_blocks=n_blocks, all_flushes=True, experiments=True) as r:
-        for h in range(2):  # two submits: the carried state after a patched submit
-            r.submit(np.ascontiguousarray(iq[:, h * (n_blocks // 2) * 65536:(h + 1) * (n_blocks // 2) * 65536]))
-        ev = np.concatenate([r.drain(), r.drain()])
+        # two submits: the carried state after a patched submit
+        ev = np.concatenate(parity.run_fifo(r, parity.cut(iq, (n_blocks // 2,) * 2)))
         for s in range(n_streams):
-            check_stream(ev, s, oracle_events(iq[s], 0x2F, 500))
+            parity.assert_stream(ev, s, parity.fresh_oracle(iq[s], 0x2F, 500))
         st = r.fm_stats()
         assert st["resolved"] > 30 and st["host_verified"] > 30 and st["host_mismatch"] == 0
         assert st["undecidable"] == 0
@@ -491,26 +425,13 @@ def test_bits_mode_every_store_bit_equals_the_oracle(splits):
     iq = synth.gen_batch(43, 3, n_streams, n_blocks)
     cut = n_blocks // splits
     with api.Receiver(n_streams, 0x2F, 500, 0, max_blocks=cut, all_flushes=True, bits=True, max_events=1 << 17) as r:
-        evs = []
-        for k in range(splits):
-            r.submit(np.ascontiguousarray(iq[:, k * cut * 65536:(k + 1) * cut * 65536]))
-            evs.append(r.drain())
-        ev = np.concatenate(evs)
+        ev = np.concatenate(parity.run_fifo(r, parity.cut(iq, (cut,) * splits), depth=1))
     n_bits = 0
     for s in range(n_streams):
-        o = O.Oracle(0x2F, 500, 0, log_bits=True)
-        o.process(iq[s])
-        want = {}
-        for ln in o.bits_text().splitlines():  # "W slot nbits bits": one record per flush, in flush order
-            p = ln.split()
-            want.setdefault(int(p[1]), []).append(p[3] if len(p) > 3 else "")
-        got = api.bits_by_flush(ev, s)
-        check_stream(ev, s, o)  # the flush events themselves are unchanged by the mode
-        for slot, recs in want.items():
-            for seq, bits in enumerate(recs):
-                assert got.get((slot, seq), "") == bits, "stream %d slot %d flush %d" % (s, slot, seq)
-                n_bits += len(bits)
-        assert sorted(want.keys()) == [0, 1, 2, 3, 4]
+        o = parity.fresh_oracle(iq[s], 0x2F, 500, log_bits=True)
+        parity.assert_stream(ev, s, o)  # the flush events themselves are unchanged by the mode
+        n_bits += parity.assert_bits(ev, s, o, "stream %d" % s)
+        assert sorted(parity.oracle_bits(o)) == [0, 1, 2, 3, 4]
     assert n_bits > 20000
 
 
@@ -528,11 +449,7 @@ def test_cooperative_slicers_step_per_lane_and_scalar_walk_emit_the_same_bits(ve
     iq = np.concatenate([iq, noisy[None, :]])
     n_streams += 1
     with api.Receiver(n_streams, 0x2F, 500, 0, max_blocks=cut, all_flushes=True, bits=True, max_events=1 << 18, experiments=True) as r:
-        evs = []
-        for k in range(n_blocks // cut):
-            r.submit(np.ascontiguousarray(iq[:, k * cut * 65536:(k + 1) * cut * 65536]))
-            evs.append(r.drain())
-        ev = np.concatenate(evs)
+        ev = np.concatenate(parity.run_fifo(r, parity.cut(iq, (cut,) * (n_blocks // cut)), depth=1))
         st = r.stats()
     if vec == "0":
         # (the counters describe the lane-per-step form: nothing to count when it is switched off)
@@ -547,43 +464,10 @@ def test_cooperative_slicers_step_per_lane_and_scalar_walk_emit_the_same_bits(ve
         assert st["tfa1_scalar_groups"] + st["tfa2_scalar_groups"] > 0, st
     n_bits = 0
     for s in range(n_streams):
-        o = O.Oracle(0x2F, 500, 0, log_bits=True)
-        o.process(iq[s])
-        want = {}
-        for ln in o.bits_text().splitlines():
-            p = ln.split()
-            want.setdefault(int(p[1]), []).append(p[3] if len(p) > 3 else "")
-        got = api.bits_by_flush(ev, s)
-        check_stream(ev, s, o)
-        for slot, recs in want.items():
-            for seq, bits in enumerate(recs):
-                assert got.get((slot, seq), "") == bits, "stream %d slot %d flush %d" % (s, slot, seq)
-                n_bits += len(bits)
+        o = parity.fresh_oracle(iq[s], 0x2F, 500, log_bits=True)
+        parity.assert_stream(ev, s, o)
+        n_bits += parity.assert_bits(ev, s, o, "stream %d" % s)
     assert n_bits > 30000
-
-
-def _all_streams_equal(ev, iq, types, thresh, all_flushes=True, wide=0, orc=None):
-    """every stream of the batch against the oracle (OpenMP, one receiver per stream): vectorised comparison.
-    orc: the oracle's events if they were computed already (one ORC_EVENT_DTYPE array per stream)"""
-    if orc is None:
-        orc = O.process_many(iq, types, thresh, wide)
-    gs, gm = api.events_canon(ev)
-    order = np.argsort(gs, kind="stable")  # (several drains concatenated: each is ordered by stream)
-    gs, gm = gs[order], gm[order]
-    bounds = np.searchsorted(gs, np.arange(len(orc) + 1))
-    minb = np.array([10, 7, 7, 7, 11])
-    total = 0
-    for s in range(len(orc)):
-        e = orc[s]
-        if not all_flushes:
-            e = e[(e["byte_cnt"] >= minb[e["slot"]]) & ~((e["slot"] == 3) & (e["byte_cnt"] >= 64)) & ~((e["slot"] == 4) & (e["byte_cnt"] > 60))]
-        wm = O.canon(e)
-        wm = wm[np.lexsort((wm[:, 1], wm[:, 0]))]
-        g = gm[bounds[s]:bounds[s + 1]]
-        g = g[np.lexsort((g[:, 1], g[:, 0]))]
-        assert g.shape == wm.shape and np.array_equal(g, wm), "stream %d" % s
-        total += len(wm)
-    return total
 
 
 def test_config1_single_stream_tfa123_48_blocks():
@@ -592,7 +476,7 @@ def test_config1_single_stream_tfa123_48_blocks():
     with api.Receiver(1, 0x07, 500, 0, max_blocks=48, all_flushes=True) as r:
         r.submit(iq)
         ev = r.drain()
-        assert _all_streams_equal(ev, iq, 0x07, 500) > 30
+        assert parity.assert_all_streams(ev, iq, 0x07, 500) > 30
         assert sorted(set(ev["slot"].tolist())) == [0, 1, 2]
         assert r.fm_stats()["host_mismatch"] == 0
 
@@ -603,10 +487,8 @@ def test_quarter_of_config2_every_stream_against_the_oracle():
     n_streams, n_blocks = 256, 48
     iq = synth.gen_batch(1000, 0, n_streams, n_blocks)
     with api.Receiver(n_streams, 0x2F, 500, 0, max_blocks=24, all_flushes=True, max_events=n_streams * 24 * 40) as r:
-        r.submit(np.ascontiguousarray(iq[:, :24 * 65536]))
-        r.submit(np.ascontiguousarray(iq[:, 24 * 65536:]))
-        ev = np.concatenate([r.drain(), r.drain()])
-        total = _all_streams_equal(ev, iq, 0x2F, 500)
+        ev = np.concatenate(parity.run_fifo(r, parity.cut(iq, (24, 24))))
+        total = parity.assert_all_streams(ev, iq, 0x2F, 500)
         assert total > 80 * n_streams
         assert r.fm_stats()["host_mismatch"] == 0
 
@@ -619,7 +501,7 @@ def test_config2_full_size_every_stream():
     with api.Receiver(n_streams, 0x2F, 500, 0, max_blocks=n_blocks, all_flushes=True, max_events=n_streams * n_blocks * 40) as r:
         r.submit(iq)
         ev = r.drain()
-        total = _all_streams_equal(ev, iq, 0x2F, 500)
+        total = parity.assert_all_streams(ev, iq, 0x2F, 500)
         assert total > 80 * n_streams
         assert r.fm_stats()["host_mismatch"] == 0
         assert r.stats()["biquad_segments"] > 40 * n_streams  # (256-slot segments: ~46 per stream and submit)
@@ -640,16 +522,10 @@ def test_hostile_and_degenerate_inputs_over_ragged_submits():
             good[0], good[1].copy()]
     rows[6][n // 2:] = 0x80
     iq = np.stack(rows)
-    cuts = [0, 1, 3, 8, 11]
     with api.Receiver(len(iq), 0x2F, 500, 0, max_blocks=5, all_flushes=True, max_events=1 << 16) as r:
-        evs = []
-        for a, b in zip(cuts, cuts[1:]):
-            r.submit(np.ascontiguousarray(iq[:, a * 65536:b * 65536]))
-            evs.append(r.drain())
-        ev = np.concatenate(evs)
+        ev = np.concatenate(parity.run_fifo(r, parity.cut(iq, (1, 2, 5, 3)), depth=1))
         for s in range(len(iq)):
-            o = oracle_events(iq[s], 0x2F, 500)
-            check_stream(ev, s, o)
+            parity.assert_stream(ev, s, parity.fresh_oracle(iq[s], 0x2F, 500))
         assert len(api.event_tuples(ev, 0)) == 0  # silence: nothing at all
         assert r.fm_stats()["host_mismatch"] == 0
 
@@ -670,11 +546,9 @@ def test_event_buffer_overflow_is_reported_and_the_context_goes_on():
         assert len(first) == 16
     # (a context with room: the reference for the second half's events)
     with api.Receiver(n_streams, 0x2F, 500, 0, max_blocks=8, all_flushes=True) as r:
-        r.submit(np.ascontiguousarray(iq[:, :8 * 65536]))
-        r.submit(np.ascontiguousarray(iq[:, 8 * 65536:]))
-        ev = np.concatenate([r.drain(), r.drain()])
+        ev = np.concatenate(parity.run_fifo(r, parity.cut(iq, (8, 8))))
         for s in range(n_streams):
-            check_stream(ev, s, oracle_events(iq[s], 0x2F, 500))
+            parity.assert_stream(ev, s, parity.fresh_oracle(iq[s], 0x2F, 500))
 
 
 @pytest.mark.parametrize("deep", ["1", "0"])
@@ -690,26 +564,17 @@ def test_whb_speculation_failures_are_redone_exactly(every, deep, monkeypatch):
     monkeypatch.setenv("TFREC_AMD_DEEP", deep)
     n_streams, n_blocks = 24, 40
     iq = synth.gen_batch(91, 3, n_streams, n_blocks)
-    parts = [np.ascontiguousarray(iq[:, a * 65536:b * 65536]) for a, b in ((0, 6), (6, 9), (9, 20), (20, 28), (28, 33), (33, 40))]
+    parts = parity.cut(iq, (6, 3, 11, 8, 5, 7))
     for types in (0x2F, 0x20):
         with api.Receiver(n_streams, types, 500, 0, max_blocks=11, all_flushes=True, experiments=True) as r:
-            evs, q = [], 0
-            for k in range(len(parts)):
-                while q < len(parts) and q - k < api.FIFO_DEPTH:
-                    r.submit(parts[q])
-                    q += 1
-                evs.append(r.drain())
-            ev = np.concatenate(evs)
+            ev = np.concatenate(parity.run_fifo(r, parts))
             assert not (ev["status"] == 0xFF).any()
-            assert _all_streams_equal(ev, iq, types, 500) > (10 if types == 0x2F else 2) * n_streams
+            assert parity.assert_all_streams(ev, iq, types, 500) > (10 if types == 0x2F else 2) * n_streams
             redone = r.stats()["whb_respeculated"]
             assert redone >= n_streams * len(parts) // every // 2, redone
         with api.Receiver(n_streams, types, 500, 0, max_blocks=11, all_flushes=False, experiments=True) as r:  # default mode, one in flight
-            evs = []
-            for p in parts:
-                r.submit(p)
-                evs.append(r.drain())
-            assert _all_streams_equal(np.concatenate(evs), iq, types, 500, all_flushes=False) > n_streams
+            ev = np.concatenate(parity.run_fifo(r, parts, depth=1))
+            assert parity.assert_all_streams(ev, iq, types, 500, all_flushes=False) > n_streams
 
 
 def test_whb_speculation_is_verified_and_rarely_fails():
@@ -720,7 +585,7 @@ def test_whb_speculation_is_verified_and_rarely_fails():
     with api.Receiver(n_streams, 0x20, 500, 0, max_blocks=n_blocks, all_flushes=True) as r:
         r.submit(iq)
         ev = r.drain()
-        assert _all_streams_equal(ev, iq, 0x20, 500) > n_streams
+        assert parity.assert_all_streams(ev, iq, 0x20, 500) > n_streams
         assert r.stats()["whb_respeculated"] <= 1
 
 
@@ -770,15 +635,9 @@ def test_config2_steady_state_five_batches_vs_oracle(force_fail, monkeypatch):
     n_streams, n_blocks = 1024, 48
     dev = [torch.from_numpy(np.ascontiguousarray(b)).to("cuda:0") for b in batches]
     with api.Receiver(n_streams, 0x2F, 500, 0, max_blocks=n_blocks, all_flushes=True, max_events=n_streams * n_blocks * 40, experiments=True) as r:
-        evs, q = [], 0
-        for k in range(len(dev)):
-            while q < len(dev) and q - k < api.FIFO_DEPTH:
-                r.submit(dev[q])
-                q += 1
-            evs.append(r.drain())
-        ev = np.concatenate(evs)
+        ev = np.concatenate(parity.run_fifo(r, dev))
         assert not (ev["status"] == 0xFF).any()
-        total = _all_streams_equal(ev, None, 0x2F, 500, orc=orc)
+        total = parity.assert_all_streams(ev, None, 0x2F, 500, orc=orc)
         assert total > 5 * 80 * n_streams
         assert r.fm_stats()["host_mismatch"] == 0
         redone = r.stats()["whb_respeculated"]
@@ -800,10 +659,8 @@ def test_wide_filter_events_match_oracle():
     n_streams, n_blocks = 24, 24
     iq = synth.gen_batch(314, 0, n_streams, n_blocks)
     with api.Receiver(n_streams, 0x2F, 500, 1, max_blocks=16, all_flushes=True) as r:
-        r.submit(np.ascontiguousarray(iq[:, :16 * 65536]))
-        r.submit(np.ascontiguousarray(iq[:, 16 * 65536:]))
-        ev = np.concatenate([r.drain(), r.drain()])
-        total = _all_streams_equal(ev, iq, 0x2F, 500, wide=1)
+        ev = np.concatenate(parity.run_fifo(r, parity.cut(iq, (16, 8))))
+        total = parity.assert_all_streams(ev, iq, 0x2F, 500, wide=1)
         assert total > 40 * n_streams
         assert sorted(set(ev["slot"].tolist())) == [0, 1, 2, 3, 4]
         assert r.fm_stats()["host_mismatch"] == 0
@@ -829,15 +686,9 @@ def test_whb_frozen_average_off_by_some_is_carried_into_a_redo(perturb, monkeypa
     rng = np.random.default_rng(11)
     while cuts[-1] < n_blocks:
         cuts.append(min(n_blocks, cuts[-1] + int(rng.integers(1, 4))))
-    parts = [np.ascontiguousarray(iq[:, a * 65536:b * 65536]) for a, b in zip(cuts, cuts[1:])]
+    parts = parity.cut(iq, np.diff(cuts))
     with api.Receiver(n_streams, 0x20, 500, 0, max_blocks=3, all_flushes=True, experiments=True) as r:
-        evs, q = [], 0
-        for k in range(len(parts)):
-            while q < len(parts) and q - k < api.FIFO_DEPTH:
-                r.submit(parts[q])
-                q += 1
-            evs.append(r.drain())
-        ev = np.concatenate(evs)
+        ev = np.concatenate(parity.run_fifo(r, parts))
         assert not (ev["status"] == 0xFF).any()
-        assert _all_streams_equal(ev, iq, 0x20, 500) > 2 * n_streams
+        assert parity.assert_all_streams(ev, iq, 0x20, 500) > 2 * n_streams
         assert r.stats()["whb_respeculated"] >= n_streams * len(parts) // 4

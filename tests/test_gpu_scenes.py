@@ -9,14 +9,12 @@ import os
 import numpy as np
 import pytest
 
-from oracle import oracle as O
+import parity
 from oracle import scenes as S
 from tfrec_amd import api, synth
 
 pytestmark = pytest.mark.gpu
 
-MINB = {0: 10, 1: 7, 2: 7, 3: 7, 4: 11}
-PREFIX = {0: "TFA1 ", 1: "TFA2 ", 2: "TFA3 ", 3: "TX22 ", 4: "WHB"}
 # submit cuts per family (blocks); tests/test_scenes_cpu.py checked the tables for exactly these
 CUTS = dict(dense=[24], edges=[1, 2, 5, 4], repeats=[24], collisions=[7, 25], drift=[32], levels=[16])
 # fallbacks each family reaches in the pipeline (stats() counters, observed on an MI355X for these fixed inputs; only "> 0"
@@ -34,47 +32,13 @@ def _run(iq, cuts, thresh=500, wide=0, **kw):
     """Submit the batch cut into `cuts` blocks, up to four submits in flight, and drain; events in per-(stream, slot) order
     plus the context's counters."""
     with api.Receiver(len(iq), 0x2F, thresh, wide, max_blocks=max(cuts), max_events=1 << 18, **kw) as r:
-        evs, pos, inflight = [], 0, 0
-        for nb in cuts:
-            if inflight == api.FIFO_DEPTH:
-                evs.append(r.drain())
-                inflight -= 1
-            r.submit(np.ascontiguousarray(iq[:, pos * 65536:(pos + nb) * 65536]))
-            pos += nb
-            inflight += 1
-        for _ in range(inflight):
-            evs.append(r.drain())
-        ev = np.concatenate(evs)
+        ev = np.concatenate(parity.run_fifo(r, parity.cut(iq, cuts)))
         stats, fm = r.stats(), r.fm_stats()
-    ev = ev[np.lexsort((ev["seq"], ev["slot"], ev["stream"]))] if not kw.get("bits") else ev
-    return ev, stats, fm
-
-
-def _by_slot(evs):
-    d = {}
-    for e in evs:
-        d.setdefault(e[0], []).append(e)
-    return d
-
-
-def _check(ev, s, orc, all_flushes, name):
-    oe = orc.events_full()
-    if not all_flushes:
-        oe = [e for e in oe if e[2] >= MINB[e[0]] and not (e[0] == 3 and e[2] >= 64) and not (e[0] == 4 and e[2] > 60)]
-    g, o = _by_slot(api.event_tuples_full(ev, s)), _by_slot(oe)
-    assert sorted(g) == sorted(o), name
-    for slot in o:
-        assert g[slot] == o[slot], "%s slot %d" % (name, slot)
-    return sum(len(v) for v in o.values())
+    return (ev if kw.get("bits") else parity.sort_events(ev)), stats, fm
 
 
 def _oracles(iq, thresh=500, wide=0, log_bits=False):
-    out = []
-    for row in iq:
-        o = O.Oracle(0x2F, thresh, wide, log_bits=log_bits)
-        o.process(row)
-        out.append(o)
-    return out
+    return [parity.fresh_oracle(row, 0x2F, thresh, wide, log_bits=log_bits) for row in iq]
 
 
 def _family(fam):
@@ -95,7 +59,7 @@ def test_dense_windows_fill_the_window_table(serial):
     ev, st, fm = _run(iq, CUTS["dense"], all_flushes=True, serial_chains=serial)
     orcs = _oracles(iq)
     for s, row in enumerate(rows):
-        _check(ev, s, orcs[s], True, row["name"])
+        parity.assert_stream(ev, s, orcs[s], row["name"])
     per_chain = {slot: max(int(np.sum((ev["stream"] == s) & (ev["slot"] == slot))) for s in range(len(rows)))
                  for slot in range(4)}
     assert per_chain[1] >= 0.98 * cap, per_chain
@@ -111,7 +75,7 @@ def test_scene_family_all_flushes(fam, serial):
     rows, iq = _family(fam)
     ev, st, fm = _run(iq, CUTS[fam], all_flushes=True, serial_chains=serial)
     orcs = _oracles(iq)
-    total = sum(_check(ev, s, orcs[s], True, row["name"]) for s, row in enumerate(rows))
+    total = sum(parity.assert_stream(ev, s, orcs[s], row["name"]) for s, row in enumerate(rows))
     assert total > len(rows)
     assert fm["host_mismatch"] == 0
     if not serial:
@@ -124,7 +88,7 @@ def test_scene_family_default_mode(fam):
     ev, st, fm = _run(iq, CUTS[fam])
     orcs = _oracles(iq)
     for s, row in enumerate(rows):
-        _check(ev, s, orcs[s], False, row["name"])
+        parity.assert_stream(ev, s, orcs[s], row["name"], default_mode=True)
         n_ok = int(np.sum((ev["stream"] == s) & (ev["status"] == 1)))
         lines = [ln for ln in orcs[s].text().splitlines() if not ln.startswith("Inverted") and not ln.startswith("WHB:")]
         assert n_ok == len(lines), row["name"]
@@ -137,7 +101,7 @@ def test_levels_with_auto_threshold_and_wide_filter(thresh, wide):
     ev, st, fm = _run(iq, [5, 11], thresh=thresh, wide=wide, all_flushes=True)
     orcs = _oracles(iq, thresh, wide)
     for s, row in enumerate(rows):
-        _check(ev, s, orcs[s], True, row["name"])
+        parity.assert_stream(ev, s, orcs[s], row["name"])
     assert fm["host_mismatch"] == 0
 
 
@@ -150,15 +114,7 @@ def test_scene_bits_equal_the_oracle_flush_by_flush(fam):
     orcs = _oracles(iq, log_bits=True)
     n_bits = 0
     for s, row in enumerate(rows):
-        want = {}
-        for ln in orcs[s].bits_text().splitlines():
-            p = ln.split()
-            want.setdefault(int(p[1]), []).append(p[3] if len(p) > 3 else "")
-        got = api.bits_by_flush(ev, s)
-        for slot, recs in want.items():
-            for seq, bits in enumerate(recs):
-                assert got.get((slot, seq), "") == bits, "%s slot %d flush %d" % (row["name"], slot, seq)
-                n_bits += len(bits)
+        n_bits += parity.assert_bits(ev, s, orcs[s], row["name"])
     assert n_bits > 1000 * len(rows)
 
 
@@ -173,40 +129,23 @@ def test_minted_scenes_equal_the_reference_directly(golden_dir):
         iq = np.stack([S.render(c["spec"]) for c in cs])
         for row, c in zip(iq, cs):
             assert _sha(row) == c["iq_sha256"], c["spec"]["name"]
-        cut = [n_blocks // 2, n_blocks - n_blocks // 2] if n_blocks > 1 else [1]
-        with api.Receiver(len(cs), types, thresh, wide, max_blocks=max(cut), all_flushes=True, max_events=1 << 17) as r:
-            evs = []
-            pos = 0
-            for nb in cut:
-                r.submit(np.ascontiguousarray(iq[:, pos * 65536:(pos + nb) * 65536]))
-                evs.append(r.drain())
-                pos += nb
-            ev = np.concatenate(evs)
-            ev = ev[np.lexsort((ev["seq"], ev["slot"], ev["stream"]))]
+        sizes = [n_blocks // 2, n_blocks - n_blocks // 2] if n_blocks > 1 else [1]
+        with api.Receiver(len(cs), types, thresh, wide, max_blocks=max(sizes), all_flushes=True, max_events=1 << 17) as r:
+            ev = parity.sort_events(np.concatenate(parity.run_fifo(r, parity.cut(iq, sizes), depth=1)))
             assert r.fm_stats()["host_mismatch"] == 0
         for s, c in enumerate(cs):
             full = api.event_tuples_full(ev, s)
             name = c["spec"]["name"]
             assert S.flush_counts(full) == c["flushes"], name
             assert S.events_digest([e[:6] for e in full]) == c["events_sha256"], name
-            _status_pinned_by_text(full, c["text"], name)
+            parity.status_pinned_by_text(full, c["text"], name)
 
 
 def _golden_events(ev, s, golden_events, text, name):
     full = api.event_tuples_full(ev, s)
     want = [(e[0], e[1], e[2], e[3], e[4], bytes.fromhex(e[5])) for e in golden_events]
     assert sorted(e[:6] for e in full) == sorted(want), name
-    _status_pinned_by_text(full, text, name)
-
-
-def _status_pinned_by_text(full, text, name):
-    lines = text.splitlines()
-    for slot, prefix in PREFIX.items():
-        n = len([ln for ln in lines if ln.startswith(prefix) and not ln.startswith("WHB:")])
-        assert sum(1 for e in full if e[0] == slot and e[7] == 1) == n, (name, prefix)
-    for e in full:
-        too_short = e[2] < MINB[e[0]] or (e[0] == 3 and e[2] >= 64) or (e[0] == 4 and e[2] > 60)
-        assert (e[7] == 0) == too_short, name
+    parity.status_pinned_by_text(full, text, name)
 
 
 @pytest.mark.parametrize("name", ["tfa_1", "tfa_2", "tfa_3", "tx22", "whb"])

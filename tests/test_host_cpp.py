@@ -5,20 +5,16 @@ import json
 import os
 import subprocess
 
-import numpy as np
 import pytest
 
+import parity
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "tfrec_amd", "host")
-CLI = os.path.join(HOST, "tfrec_gpu")
 
 
 @pytest.fixture(scope="module")
 def cli():
-    from tfrec_amd import _build
-    _build.build_device_lib()
-    subprocess.check_call(["make", "-s", "-C", HOST])
-    return CLI
+    return parity.build_cli()
 
 
 def test_byte_level_telegrams_like_reference_dash_X(cli, golden_dir, tmp_path):
@@ -99,10 +95,7 @@ def test_batched_sink_on_dump_replay(cli, golden_dir, tmp_path):
         p = tmp_path / ("s%d.iq" % k)
         iq.tofile(p)
         files += ["-L", str(p)]
-    sink = tmp_path / "sink.out"
-    out = subprocess.run([cli, "-T", "%x" % c["types"], "-t", str(c["thresh"]), "-b", "16", "-E", "cat > %s" % sink] + files,
-                         capture_output=True, text=True, check=True).stdout
-    recs = [ln.split() for ln in sink.read_text().splitlines()]
+    out, recs = parity.cli(["-T", "%x" % c["types"], "-t", str(c["thresh"]), "-b", "16"] + files, tmp_path / "sink.out")
     assert len(recs) >= 20 and {r[0] for r in recs} == {"0", "1", "2"}
     # every record corresponds to a printed telegram (TX22 / WHB telegrams expand to several records)
     assert len(recs) >= len([ln for ln in out.splitlines() if ln.strip()])
@@ -128,16 +121,14 @@ def test_handler_records_equal_the_real_reference(cli, golden_dir, tmp_path):
     -m 1: the summary of flush_storage (:98-109) in the reference's order.  Goldens: oracle/mint_handler_records.py."""
     g, c, files = _three_streams(golden_dir, tmp_path)
     largs = sum((["-L", f] for f in files), [])
-    base = [cli, "-T", "%x" % c["types"], "-t", str(c["thresh"]), "-q", "-b", "16"]
+    base = ["-T", "%x" % c["types"], "-t", str(c["thresh"]), "-q", "-b", "16"]
     for mode in (0, 1):
-        sink = tmp_path / ("sink%d.out" % mode)
-        subprocess.run(base + ["-m", str(mode), "-E", "cat > %s" % sink] + largs, check=True)
-        recs = [ln.split() for ln in sink.read_text().splitlines()]
+        _, recs = parity.cli(base + ["-m", str(mode)] + largs, tmp_path / ("sink%d.out" % mode))
         for k in range(3):
-            got = [" ".join(r[1:-1]) for r in recs if r[0] == str(k)]  # minus the stream tag and ts
+            got = [" ".join(r[1:]) for r in recs if r[0] == str(k)]  # minus the stream tag
             assert got == g["streams"][k]["mode%d" % mode], (mode, k)
     # the reference's own one-exec-per-record path on one stream
-    out = subprocess.run(base + ["-e", "echo REC", "-L", files[1]], capture_output=True, text=True, check=True).stdout
+    out = subprocess.run([cli] + base + ["-e", "echo REC", "-L", files[1]], capture_output=True, text=True, check=True).stdout
     assert [" ".join(ln.split()[1:-1]) for ln in out.splitlines() if ln.startswith("REC ")] == g["streams"][1]["mode0"]
 
 
@@ -147,12 +138,9 @@ def test_streams_sharded_over_several_device_contexts(cli, golden_dir, tmp_path)
     concatenated on the host: stdout and the sink are those of a single-context run (two contexts on device 0 here)."""
     g, c, files = _three_streams(golden_dir, tmp_path)
     largs = sum((["-L", f] for f in files), [])
-    base = [cli, "-T", "%x" % c["types"], "-t", str(c["thresh"]), "-b", "7"]
-    outs = []
-    for dev in ("0", "0,0", "0,0,0"):
-        sink = tmp_path / ("sink_%s.out" % dev.replace(",", "_"))
-        o = subprocess.run(base + ["-d", dev, "-E", "cat > %s" % sink] + largs, capture_output=True, text=True, check=True).stdout
-        outs.append((o, [ln.split()[:-1] for ln in sink.read_text().splitlines()]))
+    base = ["-T", "%x" % c["types"], "-t", str(c["thresh"]), "-b", "7"]
+    outs = [parity.cli(base + ["-d", dev] + largs, tmp_path / ("sink_%s.out" % dev.replace(",", "_")))
+            for dev in ("0", "0,0", "0,0,0")]
     assert len(outs[0][0].splitlines()) > 50
     assert outs[1] == outs[0] and outs[2] == outs[0]
 

@@ -13,9 +13,8 @@ from oracle import oracle as O
 from oracle import scenes as S
 from tfrec_amd import synth
 
-from test_oracle_golden import _data, _sha, _status_pinned_by_text
-
-PREFIX = {0: "TFA1 ", 1: "TFA2 ", 2: "TFA3 ", 3: "TX22 ", 4: "WHB"}
+import parity
+from test_oracle_golden import _data, _sha
 
 
 @pytest.fixture(scope="module")
@@ -28,7 +27,7 @@ def test_scene_goldens_cover_every_family_and_protocol(cases):
     assert fams == set(S.FAMILIES)
     for fam in ("repeats", "collisions", "drift", "levels"):
         text = "".join(c["text"] for c in cases if c["family"] == fam)
-        for slot, p in PREFIX.items():
+        for slot, p in parity.PREFIX.items():
             assert any(ln.startswith(p) and not ln.startswith("WHB:") for ln in text.splitlines()), (fam, p)
     assert any(c["thresh"] == 0 for c in cases) and any(c["wide"] == 1 for c in cases)
 
@@ -46,7 +45,7 @@ def test_scenes_against_reference_outputs(cases):
         assert o.data() == _data(c["data"]), tag
         assert o.text() == c["text"], tag
         assert hashlib.sha256(o.bits_text().encode()).hexdigest() == c["bits_sha256"], tag
-        _status_pinned_by_text(o, c["text"].splitlines())
+        parity.status_pinned_by_text(o.events_full(), c["text"], tag)
 
 
 def test_repeats_put_several_frames_in_one_window(cases):
@@ -57,7 +56,7 @@ def test_repeats_put_several_frames_in_one_window(cases):
         name = synth.PROTO_NAMES[proto].lower()
         one, split = by["repeat_%s_one_window" % name], by["repeat_%s_split" % name]
         assert one["flushes"][proto] == 1
-        assert len([ln for ln in split["text"].splitlines() if ln.startswith(PREFIX[proto])]) == 3
+        assert len([ln for ln in split["text"].splitlines() if ln.startswith(parity.PREFIX[proto])]) == 3
     for name in ("repeat_whb_tight", "repeat_tfa1_tight", "repeat_tx22_tight"):
         o = O.Oracle(0x2F, 500, 0, log_bits=True)
         o.process(S.render(by[name]["spec"]))  # (the bit log itself is pinned by test_scenes_against_reference_outputs)

@@ -8,18 +8,15 @@ import subprocess
 
 import pytest
 
-from tfrec_amd import _build, api
+import parity
+from tfrec_amd import api
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "tfrec_amd", "host")
-CLI = os.path.join(HOST, "tfrec_gpu")
 
 
 @pytest.fixture(scope="module")
 def cli():
-    _build.build_device_lib()
-    subprocess.check_call(["make", "-s", "-C", HOST])
-    return CLI
+    return parity.build_cli()
 
 
 def test_header_declares_and_library_exports_the_stream_config_calls():

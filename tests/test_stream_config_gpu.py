@@ -5,18 +5,15 @@ A configured stream restarts at the next submit exactly as after a reset, but as
 -W: its events equal those of oracle.Oracle(types_mask, thresh, wide) fed the input after the cut, while the streams
 beside it, with other settings, carry on with theirs.  Compared in every field: slot, end_sample, byte_cnt, rssi, offset,
 rdata, rssi_raw, status and seq; read_thresh against Oracle.thresh() after every submit."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import parity
 from oracle import oracle as O
 from tfrec_amd import api, synth
 
 pytestmark = pytest.mark.gpu
 
-B = api.BLOCK_BYTES
 SIZES = (3, 2, 3)  # blocks of the three submits
 
 
@@ -39,14 +36,6 @@ def make_input(seed, n_streams, n_blocks, rate_mult=1):
         else:
             rows.append(synth.gen_stream(seed, s, n_blocks, rate_mult=rate_mult))
     return np.stack(rows)
-
-
-def split(iq, sizes, block=B):
-    parts, pos = [], 0
-    for nb in sizes:
-        parts.append(iq[:, pos * block:(pos + nb) * block])
-        pos += nb
-    return parts
 
 
 # A mix for a 0x2f context: each slot alone, pairs and all five; auto and fixed thresholds; both filters; None = the defaults
@@ -72,8 +61,8 @@ def run_and_check(r, parts, ops, dflt, in10x=False, bits=False):
     n = parts[0].shape[0]
     cur = [dflt] * n
     segs = [[] for _ in range(n)]  # per stream: [first submit, settings, oracle] of each segment
-    evs, pending = [], 0
-    for k, p in enumerate(parts):
+
+    def before(k):
         restart = set()
         for op in ops.get(k, ()):
             apply(r, [op])
@@ -86,55 +75,26 @@ def run_and_check(r, parts, ops, dflt, in10x=False, bits=False):
             if k == 0 or s in restart:
                 c = cur[s]
                 segs[s].append([k, c, O.Oracle(c[0], c[1], c[2], log_bits=bits)])
-        if pending == api.FIFO_DEPTH:
-            evs.append(r.drain())
-            pending -= 1
-        r.submit(np.ascontiguousarray(p))
-        pending += 1
+
+    def after(k):
         for s in range(n):  # the oracles follow submit by submit: the threshold each stream has after it
             orc = segs[s][-1][2]
             if in10x:
-                orc.process_s16(O.decim10(np.asarray(p[s])))
+                orc.process_s16(O.decim10(np.asarray(parts[k][s])))
             else:
-                orc.process(np.asarray(p[s]))
+                orc.process(np.asarray(parts[k][s]))
             assert r.thresh(s) == orc.thresh(), "stream %d submit %d threshold" % (s, k)
-    while pending:
-        evs.append(r.drain())
-        pending -= 1
+
+    evs = parity.run_fifo(r, parts, before=before, after=after)
     total = 0
     for s in range(n):
         bounds = [g[0] for g in segs[s]] + [len(parts)]
         for g, (_, c, orc) in enumerate(segs[s]):
             ev = np.concatenate([e[e["stream"] == s] for e in evs[bounds[g]:bounds[g + 1]]])
-            want = by_slot(orc.events_full())
-            have = by_slot(api.event_tuples_full(ev, s))
-            assert sorted(have) == sorted(want), "stream %d segment %d settings %s" % (s, g, c)
-            for slot in want:
-                assert have[slot] == want[slot], "stream %d segment %d slot %d" % (s, g, slot)
-                total += len(want[slot])
-            flushes = ev[ev["status"] != api.STATUS_BITS]
-            for slot in want:  # seq: the flush ordinal since the restart
-                seq = flushes[flushes["slot"] == slot]["seq"]
-                assert np.array_equal(seq, np.arange(len(seq))), "stream %d segment %d slot %d seq" % (s, g, slot)
+            total += parity.assert_segment(ev, s, orc, "stream %d segment %d settings %s" % (s, g, c), bits)
             own = {i for i in range(5) if c[0] & (1 << (i if i < 4 else 5))}
             assert set(np.unique(ev["slot"]).tolist()) <= own, "stream %d: a slot outside its types" % s
-            if bits:
-                want_bits = {}
-                for ln in orc.bits_text().splitlines():
-                    f = ln.split()
-                    want_bits.setdefault(int(f[1]), []).append(f[3] if len(f) > 3 else "")
-                have_bits = api.bits_by_flush(ev, s)
-                for slot, recs in want_bits.items():
-                    for q, b in enumerate(recs):
-                        assert have_bits.get((slot, q), "") == b, "stream %d segment %d slot %d flush %d" % (s, g, slot, q)
     return total
-
-
-def by_slot(evs):
-    d = {}
-    for e in evs:
-        d.setdefault(e[0], []).append(e)
-    return d
 
 
 def test_inputs_discriminate():
@@ -159,7 +119,7 @@ def test_inputs_discriminate():
 @pytest.mark.parametrize("dflt", [(0x2F, 500, 0), (0x2F, 0, 1)], ids=["fixed-narrow", "auto-wide"])
 def test_mixed_context(dflt):
     iq = make_input(11, len(MIX), sum(SIZES))
-    parts = split(iq, SIZES)
+    parts = parity.cut(iq, SIZES)
     table = [c for c in MIX]
     if dflt[1] == 0:  # the auto context: some streams fixed, the rest left at the defaults
         table = [c if c is None or c[1] else None for c in MIX]
@@ -178,7 +138,7 @@ def test_modes(mode):
     rate = 10 if mode == "input_10x" else 1
     sizes = (2, 1, 2) if rate == 10 else SIZES
     iq = make_input(12, MODE_N, sum(sizes), rate_mult=rate)
-    parts = split(iq, sizes, B * rate)
+    parts = parity.cut(iq, sizes, api.BLOCK_BYTES * rate)
     # (every mode with all flushes: the oracle reports every decoder::flush, and seq counts them all)
     kw = dict(max_blocks=max(sizes), all_flushes=True, serial_chains=(mode == "serial_chains"),
               input_10x=(mode == "input_10x"), bits=(mode == "bits"), max_events=1 << 17)
@@ -199,7 +159,7 @@ def test_reconfigure_mid_run():
     n_streams = 10
     sizes = (2, 1, 2, 2, 1, 2)
     iq = make_input(13, n_streams, sum(sizes))
-    parts = split(iq, sizes)
+    parts = parity.cut(iq, sizes)
     ops = {0: [("conf", [0], [(0x01, 0, 0)])],  # before the first submit
            2: [("conf", [1, 2, 2], [(0x21, 900, 1), (0x2F, 500, 0), (0x01, 0, 0)]),  # (duplicate: the last wins)
                ("reset", [4])],
@@ -210,10 +170,7 @@ def test_reconfigure_mid_run():
         run_and_check(r, parts, ops, dflt)
         assert r.stream_config(2) == {"types_mask": 0x01, "thresh": 0, "filter_type": 0}
     with api.Receiver(n_streams, *dflt, max_blocks=max(sizes), all_flushes=True) as r:  # untouched streams: as without calls
-        ev_plain = []
-        for p in parts:
-            r.submit(np.ascontiguousarray(p))
-            ev_plain.append(r.drain())
+        ev_plain = parity.run_fifo(r, parts, depth=1)
     with api.Receiver(n_streams, *dflt, max_blocks=max(sizes), all_flushes=True) as r:
         ev_conf = []
         for k, p in enumerate(parts):
@@ -230,17 +187,14 @@ def test_reconfigure_mid_run():
 def test_configuring_the_context_settings_changes_nothing(dflt):
     n_streams = 8
     iq = make_input(14, n_streams, sum(SIZES))
-    parts = split(iq, SIZES)
+    parts = parity.cut(iq, SIZES)
     out = []
     for conf in (False, True):
         with api.Receiver(n_streams, *dflt, max_blocks=max(SIZES), all_flushes=True) as r:
             if conf:
                 r.configure_streams(range(n_streams), *dflt)
-            ev = []
-            for p in parts:
-                r.submit(np.ascontiguousarray(p))
-                ev.append(r.drain())
-            out.append((np.concatenate(ev), [r.thresh(s) for s in range(n_streams)]))
+            ev = np.concatenate(parity.run_fifo(r, parts, depth=1))
+            out.append((ev, [r.thresh(s) for s in range(n_streams)]))
     assert len(out[0][0]) > 2 * n_streams
     assert out[0][0].tobytes() == out[1][0].tobytes()
     assert out[0][1] == out[1][1]
@@ -249,7 +203,7 @@ def test_configuring_the_context_settings_changes_nothing(dflt):
 def test_argument_errors_mark_nothing():
     n_streams = 4
     iq = make_input(15, n_streams, 6)
-    parts = split(iq, (3, 3))
+    parts = parity.cut(iq, (3, 3))
 
     def run(calls):
         with api.Receiver(n_streams, 0x23, 500, 0, max_blocks=3, all_flushes=True) as r:
@@ -292,8 +246,6 @@ def test_argument_errors_mark_nothing():
 
 
 # ---- tfrec_gpu -p
-HOST = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tfrec_amd", "host")
-CLI = os.path.join(HOST, "tfrec_gpu")
 FILES = [  # (blocks, -p spec, the same as global options)
     (5, "T=1,t=0", ["-T", "1", "-t", "0"]),
     (7, None, ["-T", "2f", "-t", "500"]),
@@ -305,9 +257,7 @@ FILES = [  # (blocks, -p spec, the same as global options)
 
 @pytest.fixture(scope="module")
 def dumps(tmp_path_factory):
-    from tfrec_amd import _build
-    _build.build_device_lib()
-    subprocess.check_call(["make", "-s", "-C", HOST])
+    parity.build_cli()
     d = tmp_path_factory.mktemp("pdumps")
     files = []
     for k, (nb, _, _) in enumerate(FILES):
@@ -315,12 +265,6 @@ def dumps(tmp_path_factory):
         p.write_bytes((pulse_stream(70 + k, nb) if k % 2 else synth.gen_stream(70, k, nb)).tobytes())
         files.append(str(p))
     return d, files
-
-
-def cli(args, sink):
-    out = subprocess.run([CLI, "-b", "4"] + args + ["-E", "cat > %s" % sink], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr
-    return out.stdout, [ln.split()[:-1] for ln in open(sink).read().splitlines()]  # (minus the time stamp)
 
 
 def p_args(files):
@@ -333,10 +277,10 @@ def p_args(files):
 @pytest.mark.parametrize("extra", [[], ["-n", "1"], ["-n", "2"], ["-m", "1"]], ids=["default", "n1", "n2", "summary"])
 def test_tfrec_gpu_per_file_settings(dumps, extra):
     d, files = dumps
-    out, recs = cli(["-T", "2f", "-t", "500"] + extra + p_args(files), d / "p.out")
+    out, recs = parity.cli(["-b", "4", "-T", "2f", "-t", "500"] + extra + p_args(files), d / "p.out")
     n = 0
     for k, f in enumerate(files):
-        _, alone = cli(FILES[k][2] + extra + ["-L", f], d / ("a%d.out" % k))
+        _, alone = parity.cli(["-b", "4"] + FILES[k][2] + extra + ["-L", f], d / ("a%d.out" % k))
         got = [r[1:] for r in recs if r[0] == str(k)]
         assert got == [r[1:] for r in alone], "file %d" % k
         n += len(got)
@@ -346,5 +290,5 @@ def test_tfrec_gpu_per_file_settings(dumps, extra):
 def test_tfrec_gpu_without_p_is_unchanged(dumps):
     d, files = dumps
     largs = sum((["-L", f] for f in files), [])
-    base = cli(["-T", "2f", "-t", "500"] + largs, d / "b0.out")
-    assert base == cli(["-T", "2f", "-t", "500", "-p", "T=2f,t=500,W=0"] + largs, d / "b1.out")
+    base = parity.cli(["-b", "4", "-T", "2f", "-t", "500"] + largs, d / "b0.out")
+    assert base == parity.cli(["-b", "4", "-T", "2f", "-t", "500", "-p", "T=2f,t=500,W=0"] + largs, d / "b1.out")

@@ -11,7 +11,7 @@ import os
 import numpy as np
 import pytest
 
-from oracle import oracle as O
+import parity
 from tfrec_amd import api, synth
 
 pytestmark = pytest.mark.gpu
@@ -20,21 +20,11 @@ B = api.BLOCK_BYTES
 
 
 def run_gpu(r, parts, resets):
-    """Submit parts[k] ([n_streams, bytes], one per submit) with up to FIFO_DEPTH submits in flight; resets[k] = the streams
-    reset before submit k (called while older submits are still queued).  -> one event array per submit, in order."""
-    out, pending = [], 0
-    for k, p in enumerate(parts):
+    """parity.run_fifo with resets[k] = the streams reset before submit k (called while older submits are still queued)."""
+    def before(k):
         if k in resets:
             r.reset_streams(resets[k])
-        if pending == api.FIFO_DEPTH:
-            out.append(r.drain())
-            pending -= 1
-        r.submit(np.ascontiguousarray(p))
-        pending += 1
-    while pending:
-        out.append(r.drain())
-        pending -= 1
-    return out
+    return parity.run_fifo(r, parts, before=before)
 
 
 def segments(parts, resets, s):
@@ -48,22 +38,6 @@ def segments(parts, resets, s):
     return [np.concatenate(x) for x in segs], seg_of
 
 
-def fresh_oracle(seg, types, thresh, wide, in10x=False, log_bits=False):
-    o = O.Oracle(types, thresh, wide, log_bits=log_bits)
-    if in10x:
-        o.process_s16(O.decim10(seg))
-    else:
-        o.process(seg)
-    return o
-
-
-def by_slot(evs):
-    d = {}
-    for e in evs:
-        d.setdefault(e[0], []).append(e)
-    return d
-
-
 def check_all(evs, parts, resets, n_streams, types=0x2F, thresh=500, wide=0, in10x=False, bits=False, r=None):
     """Every stream, segment by segment, against a fresh oracle per segment.  -> events compared."""
     total = 0
@@ -72,29 +46,9 @@ def check_all(evs, parts, resets, n_streams, types=0x2F, thresh=500, wide=0, in1
         got = [[] for _ in segs]
         for k, ev in enumerate(evs):
             got[seg_of[k]].append(ev[ev["stream"] == s])
-        orc = None
         for g, seg in enumerate(segs):
-            ev = np.concatenate(got[g])
-            orc = fresh_oracle(seg, types, thresh, wide, in10x, log_bits=bits)
-            want = by_slot(orc.events_full())
-            have = by_slot(api.event_tuples_full(ev, s))
-            assert sorted(have) == sorted(want), "stream %d segment %d" % (s, g)
-            for slot in want:
-                assert have[slot] == want[slot], "stream %d segment %d slot %d" % (s, g, slot)
-                total += len(want[slot])
-            flushes = ev[ev["status"] != api.STATUS_BITS]
-            for slot in want:  # all flushes are reported: seq is the flush ordinal since the reset
-                seq = flushes[flushes["slot"] == slot]["seq"]
-                assert np.array_equal(seq, np.arange(len(seq))), "stream %d segment %d slot %d seq" % (s, g, slot)
-            if bits:
-                want_bits = {}
-                for ln in orc.bits_text().splitlines():
-                    p = ln.split()
-                    want_bits.setdefault(int(p[1]), []).append(p[3] if len(p) > 3 else "")
-                have_bits = api.bits_by_flush(ev, s)
-                for slot, recs in want_bits.items():
-                    for seq, b in enumerate(recs):
-                        assert have_bits.get((slot, seq), "") == b, "stream %d segment %d slot %d flush %d" % (s, g, slot, seq)
+            orc = parity.fresh_oracle(seg, types, thresh, wide, in10x, log_bits=bits)
+            total += parity.assert_segment(np.concatenate(got[g]), s, orc, "stream %d segment %d" % (s, g), bits)
         if r is not None and thresh == 0:  # auto threshold: the stream's last segment started from 500
             assert r.thresh(s) == orc.thresh(), "stream %d threshold" % s
     return total
@@ -103,14 +57,6 @@ def check_all(evs, parts, resets, n_streams, types=0x2F, thresh=500, wide=0, in1
 N_STREAMS = 8
 SIZES = (3, 2, 4, 3, 2)  # blocks of the five submits
 RESETS = {2: [1, 4, 6]}  # before the 3rd submit
-
-
-def split(iq, sizes, block=B):
-    parts, pos = [], 0
-    for nb in sizes:
-        parts.append(iq[:, pos * block:(pos + nb) * block])
-        pos += nb
-    return parts
 
 
 LAYOUTS = pytest.mark.parametrize("layout", ["deep", "shallow", "serial"])
@@ -131,7 +77,7 @@ def make_receiver(layout, monkeypatch, **kw):
 @pytest.mark.parametrize("thresh", [500, 0])
 def test_reset_some_streams(layout, thresh, monkeypatch):
     iq = synth.gen_batch(71, 0, N_STREAMS, sum(SIZES))
-    parts = split(iq, SIZES)
+    parts = parity.cut(iq, SIZES)
     with make_receiver(layout, monkeypatch, thresh=thresh, max_blocks=max(SIZES), all_flushes=True) as r:
         evs = run_gpu(r, parts, RESETS)
         n = check_all(evs, parts, RESETS, N_STREAMS, thresh=thresh, r=r)
@@ -141,7 +87,7 @@ def test_reset_some_streams(layout, thresh, monkeypatch):
 @pytest.mark.parametrize("layout", ["deep", "serial"])
 def test_reset_some_streams_wide_filter(layout, monkeypatch):
     iq = synth.gen_batch(72, 0, N_STREAMS, sum(SIZES))
-    parts = split(iq, SIZES)
+    parts = parity.cut(iq, SIZES)
     with make_receiver(layout, monkeypatch, thresh=0, filter_type=1, max_blocks=max(SIZES), all_flushes=True) as r:
         evs = run_gpu(r, parts, RESETS)
         check_all(evs, parts, RESETS, N_STREAMS, thresh=0, wide=1, r=r)
@@ -149,7 +95,7 @@ def test_reset_some_streams_wide_filter(layout, monkeypatch):
 
 def test_reset_some_streams_bits_mode():
     iq = synth.gen_batch(73, 0, N_STREAMS, sum(SIZES))
-    parts = split(iq, SIZES)
+    parts = parity.cut(iq, SIZES)
     with api.Receiver(N_STREAMS, max_blocks=max(SIZES), all_flushes=True, bits=True, max_events=1 << 17) as r:
         evs = run_gpu(r, parts, RESETS)
         check_all(evs, parts, RESETS, N_STREAMS, bits=True)
@@ -163,7 +109,7 @@ def test_reset_with_whb_check_forced_to_fail(layout, monkeypatch):
     if layout == "shallow":
         monkeypatch.setenv("TFREC_AMD_DEEP", "0")
     iq = synth.gen_batch(74, 0, N_STREAMS, sum(SIZES))
-    parts = split(iq, SIZES)
+    parts = parity.cut(iq, SIZES)
     with api.Receiver(N_STREAMS, max_blocks=max(SIZES), all_flushes=True, experiments=True) as r:
         evs = run_gpu(r, parts, RESETS)
         check_all(evs, parts, RESETS, N_STREAMS)
@@ -174,7 +120,7 @@ def test_reset_on_the_10x_input():
     sizes = (2, 1, 2, 1, 2)
     bb = 10 * B
     iq = np.stack([synth.gen_stream(75, s, sum(sizes), rate_mult=10) for s in range(N_STREAMS)])
-    parts = split(iq, sizes, bb)
+    parts = parity.cut(iq, sizes, bb)
     with api.Receiver(N_STREAMS, max_blocks=max(sizes), all_flushes=True, input_10x=True) as r:
         evs = run_gpu(r, parts, RESETS)
         n = check_all(evs, parts, RESETS, N_STREAMS, in10x=True)
@@ -196,16 +142,16 @@ def test_windows_open_at_the_cut_are_dropped():
         rows.append(synth.gen_scene(80 + p, n_blocks, bursts))
     rows.append(synth.gen_batch(81, 0, 1, n_blocks)[0])
     iq = np.stack(rows)
-    parts = split(iq, (cut_blocks, n_blocks - cut_blocks))
+    parts = parity.cut(iq, (cut_blocks, n_blocks - cut_blocks))
     resets = {1: [0, 1, 2, 3, 4]}
     with api.Receiver(len(rows), max_blocks=cut_blocks, all_flushes=True) as r:
         evs = run_gpu(r, parts, resets)
         check_all(evs, parts, resets, len(rows))
     m = cut // 4  # decimated samples before the cut
     for s in range(5):  # the cut matters: one receiver over the whole row flushes the straddling burst's window
-        whole = sorted(fresh_oracle(iq[s], 0x2F, 500, 0).events_full())
-        before = fresh_oracle(iq[s, :2 * cut], 0x2F, 500, 0).events_full()
-        after = [(e[0], e[1] + m) + e[2:] for e in fresh_oracle(iq[s, 2 * cut:], 0x2F, 500, 0).events_full()]
+        whole = sorted(parity.fresh_oracle(iq[s], 0x2F, 500, 0).events_full())
+        before = parity.fresh_oracle(iq[s, :2 * cut], 0x2F, 500, 0).events_full()
+        after = [(e[0], e[1] + m) + e[2:] for e in parity.fresh_oracle(iq[s, 2 * cut:], 0x2F, 500, 0).events_full()]
         assert whole != sorted(before + after), "stream %d: no window open at the cut" % s
 
 
@@ -214,7 +160,7 @@ def test_reset_every_stream_equals_a_new_context(bits):
     """After every stream is reset, the drained events equal those of a new context fed the same input in every field, BITS
     chunks included (their end_sample is the first sample of their window, counted from the reset like a flush's)."""
     iq = synth.gen_batch(76, 0, N_STREAMS, 9)
-    parts = split(iq, (3, 3, 3))
+    parts = parity.cut(iq, (3, 3, 3))
     kw = dict(max_blocks=3, all_flushes=True, bits=bits, max_events=1 << 16)
     with api.Receiver(N_STREAMS, **kw) as r:
         evs = run_gpu(r, parts, {1: list(range(N_STREAMS))})
@@ -255,7 +201,7 @@ def test_reset_stream_reproduces_the_real_reference_fixture(proto, golden_dir):
 
 def test_api_edge_cases():
     iq = synth.gen_batch(79, 0, 4, 6)
-    parts = split(iq, (3, 3))
+    parts = parity.cut(iq, (3, 3))
 
     def run(calls):
         with api.Receiver(4, max_blocks=3, all_flushes=True) as r:

@@ -3,26 +3,19 @@ stream when its file has ended).  Every file's records, -m 1 summary and -q outp
 with at least one stream per file the output is byte for byte that of a run without -n.  -B (BITS replay) checks that the
 BITS chunks of a file in a recycled stream count their samples from the file's start, like its flushes: the engine cuts
 and orders both by end_sample."""
-import os
-import subprocess
-
 import pytest
 
+import parity
 from tfrec_amd import synth
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "tfrec_amd", "host")
-CLI = os.path.join(HOST, "tfrec_gpu")
 BLOCKS = (5, 9, 3, 8, 6)  # blocks per dump: some not a multiple of -b 4
 
 
 @pytest.fixture(scope="module")
 def dumps(tmp_path_factory):
-    from tfrec_amd import _build
-    _build.build_device_lib()
-    subprocess.check_call(["make", "-s", "-C", HOST])
+    parity.build_cli()
     d = tmp_path_factory.mktemp("dumps")
     files = []
     for k, nb in enumerate(BLOCKS):
@@ -35,12 +28,7 @@ def dumps(tmp_path_factory):
 
 
 def run(args, files, sink):
-    largs = sum((["-L", f] for f in files), [])
-    out = subprocess.run([CLI, "-T", "2f", "-t", "500", "-b", "4"] + args + ["-E", "cat > %s" % sink] + largs,
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr
-    recs = [ln.split() for ln in open(sink).read().splitlines()]
-    return out.stdout, [r[:-1] for r in recs]  # (minus the time stamp)
+    return parity.cli(["-T", "2f", "-t", "500", "-b", "4"] + args + sum((["-L", f] for f in files), []), sink)
 
 
 @pytest.mark.parametrize("extra", [[], ["-m", "1"], ["-q"], ["-B"]], ids=["default", "summary", "quiet", "bits"])
