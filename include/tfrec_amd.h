@@ -198,6 +198,30 @@ int tfrec_amd_configure_streams(tfrec_amd_ctx *ctx, const int32_t *streams, cons
 /* The settings the next submit will use for one stream. */
 int tfrec_amd_get_stream_config(tfrec_amd_ctx *ctx, int stream, tfrec_amd_stream_config *out);
 
+/* Tune streams[i] to tune_hz[i] (i < n): what -f, the receive frequency, is to one tfrec process of the reference, applied to
+ * recorded IQ.  tune_hz is the offset of the wanted channel from the centre of the recording (f - f_recorded, in Hz), and
+ * |tune_hz| < 768000.  No reference counterpart: the stage is defined here and pinned by a CPU restatement
+ * (tfrec_amd/tune.py).  It acts on the 1.536 MS/s int16 (I, Q) stream that enters downconvert::process_iq -- the default
+ * input x = (u8 - 128) << 6, with TFREC_AMD_F_INPUT_10X the output of the 10:1 stage:
+ *     inc  = floor((tune_hz * 2^33 + 1536000) / 3072000) mod 2^32       (exact 64-bit integers, floor division)
+ *     p    = (n * inc) mod 2^32,  k = p >> 20                          (n: the sample's index since the stream's start or
+ *                                                                        last restart; the FIR history before it is silence)
+ *     C[k] = round(32767 * cos(2 pi k / 4096)),  S[k] = C[(k - 1024) mod 4096]
+ *     I'   = sat16((I * C[k] + Q * S[k] + 2^14) >> 15),  Q' = sat16((Q * C[k] - I * S[k] + 2^14) >> 15)   (int32, arithmetic >>)
+ * A signal at +tune_hz in the recording is moved to DC.  tune_hz = 0 means no mixing: the stream is bit for bit what it is
+ * untuned.  The rest of the path is the reference's process_iq on int16 input.
+ *   - A tune is a restart with exactly the semantics of tfrec_amd_configure_streams: the same cut and dropped open window,
+ *     seq and end_sample restarting, other streams untouched.  Before the first submit it only sets the value.  Duplicate
+ *     indices: the last one wins.  A reset, a configure and a tune of one stream before one submit are one restart with the
+ *     latest values; later resets and configures keep the tune.  n == 0 is a no-op.
+ *   - A context in which no stream has a tune other than 0 launches the kernels of an untuned context.  Cost: that of a reset
+ *     for the restart, and the rotation in the front end while a stream is tuned.
+ * Errors: an index outside [0, n_streams), n < 0, streams or tune_hz NULL with n > 0, |tune_hz| >= 768000:
+ * TFREC_AMD_E_INVAL, and nothing is marked.  A poisoned context: TFREC_AMD_E_STATE. */
+int tfrec_amd_tune_streams(tfrec_amd_ctx *ctx, const int32_t *streams, const int32_t *tune_hz, int n);
+/* The tune the next submit will use for one stream (0: untuned). */
+int tfrec_amd_get_stream_tune(tfrec_amd_ctx *ctx, int stream, int32_t *tune_hz);
+
 /* Wait for submitted work. */
 int tfrec_amd_sync(tfrec_amd_ctx *ctx);
 

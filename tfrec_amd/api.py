@@ -96,7 +96,7 @@ EXPORTS = (
     "tfrec_amd_get_timings", "tfrec_amd_read_thresh", "tfrec_amd_get_stats", "tfrec_amd_get_layout", "tfrec_amd_host_alloc",
     "tfrec_amd_host_free", "tfrec_amd_read_stage0", "tfrec_amd_get_fm_stats", "tfrec_amd_fm_dev_probe",
     "tfrec_amd_fifo_depth", "tfrec_amd_get_memory", "tfrec_amd_iir_probe", "tfrec_amd_reset_streams",
-    "tfrec_amd_configure_streams", "tfrec_amd_get_stream_config",
+    "tfrec_amd_configure_streams", "tfrec_amd_get_stream_config", "tfrec_amd_tune_streams", "tfrec_amd_get_stream_tune",
 )
 
 _libs = {}
@@ -157,6 +157,8 @@ def load_library(build: bool = True, experiments: bool = False):
     L.tfrec_amd_reset_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.tfrec_amd_configure_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tfrec_amd_get_stream_config.argtypes = [C.c_void_p, C.c_int, C.POINTER(StreamConfig)]
+    L.tfrec_amd_tune_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.tfrec_amd_get_stream_tune.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
     L.tfrec_amd_fifo_depth.restype = C.c_int
     if L.tfrec_amd_fifo_depth() != FIFO_DEPTH:
         raise RuntimeError("libtfrec_amd.so was built with FIFO depth %d, this binding expects %d" % (
@@ -282,6 +284,29 @@ class Receiver:
         c = StreamConfig()
         _check(self.L, self.L.tfrec_amd_get_stream_config(self.h, int(stream), C.byref(c)))
         return {"types_mask": c.types_mask, "thresh": c.thresh, "filter_type": c.filter_type}
+
+    def tune_streams(self, streams, tune_hz):
+        """Tune the listed streams (tfrec_amd_tune_streams): tune_hz is one value for all of them or one per listed stream, the
+        offset in Hz of the wanted channel from the recording's centre (|tune_hz| < 768000; 0 = untuned; see tune.py).  The
+        streams restart as fresh receivers at the next submit, exactly as after reset_streams."""
+        idx = [int(s) for s in streams]
+        if any(s < 0 or s >= self.n_streams for s in idx):  # (refused before int32 could wrap an index into range)
+            raise TfrecAmdError(E_INVAL, "stream index outside [0, %d)" % self.n_streams)
+        hz = [int(tune_hz)] * len(idx) if np.ndim(tune_hz) == 0 else [int(v) for v in tune_hz]
+        if len(hz) != len(idx):
+            raise ValueError("%d values for %d streams" % (len(hz), len(idx)))
+        if any(not -2 ** 31 <= v < 2 ** 31 for v in hz):  # (refused before int32 could wrap a value into range)
+            raise TfrecAmdError(E_INVAL, "tune_hz outside int32")
+        a = np.ascontiguousarray(idx, dtype=np.int32)
+        t = np.ascontiguousarray(hz, dtype=np.int32)
+        _check(self.L, self.L.tfrec_amd_tune_streams(self.h, a.ctypes.data if len(a) else None,
+                                                     t.ctypes.data if len(t) else None, len(a)))
+
+    def stream_tune(self, stream: int) -> int:
+        """The tune in Hz the next submit uses for one stream (tfrec_amd_get_stream_tune)."""
+        v = C.c_int32(0)
+        _check(self.L, self.L.tfrec_amd_get_stream_tune(self.h, int(stream), C.byref(v)))
+        return int(v.value)
 
     def drain(self, allow_overflow: bool = False) -> np.ndarray:
         out = np.empty(self.max_events, dtype=EVENT_DTYPE)

@@ -17,7 +17,7 @@ hipError_t launch_decim10(hipStream_t st, const uint8_t *iq, size_t stride, int 
 hipError_t launch_frontend(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks,
 			   const uint8_t *tail_in, uint8_t *tail_out, uint32_t *dec, size_t dec_stride,
 			   unsigned long long *mask, size_t mask_stride, uint32_t *prevdec, int thresh, const FrontTapsCfg &taps,
-			   bool in16);
+			   bool in16, const uint2 *tune);
 hipError_t launch_fmdev(hipStream_t st, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask,
 			size_t mask_stride, const uint32_t *prevdec, int16_t *fmdev, size_t fmdev_stride, EventBuf *eb,
 			int n_streams, int n_blocks, int wmax, double flag_eps);
@@ -36,6 +36,8 @@ hipError_t launch_chains(hipStream_t st, const uint32_t *dec, size_t dec_stride,
 }  // namespace tfrec
 
 using namespace tfrec;
+
+constexpr int kTuneLimit = 768000;  // |tune_hz| < half the 1.536 MS/s sample rate
 
 // Buffer / table sets = submits that may be in flight (the FIFO depth): front end of submit k+2, biquad stage of
 // k+1 and slicer stage of k run beside each other in the deep layout
@@ -125,6 +127,13 @@ struct tfrec_amd_ctx {
 	StreamCfg *d_rcfg[kSets] = {}, *h_rcfg[kSets] = {};
 	bool per_stream = false;
 	int n_auto = 0;
+	// tfrec_amd_tune_streams: every stream's tune as the next submit uses it (tune_hz, and its phase increment tune_inc), and per
+	// set the {inc, phase of the submit's first sample} the set's front end reads (h_tune -> d_tune, filled by the submit).
+	// n_tuned: streams with inc != 0 -- while there is one, the tuned front end runs; before, the kernels of an untuned context.
+	std::vector<int32_t> tune_hz;
+	std::vector<uint32_t> tune_inc;
+	uint2 *d_tune[kSets] = {}, *h_tune[kSets] = {};
+	int n_tuned = 0;
 	uint8_t *d_tail[kSets] = {};  // FIR history: [tail_sel] is read by the next front end, [tail_sel ^ 1] written
 	int tail_sel = 0;
 	// TFREC_AMD_F_INPUT_10X: output of the 10:1 stage (1.536 MS/s int16 pairs, one buffer per set) and its raw history
@@ -775,6 +784,7 @@ static int make_event_blocks(tfrec_amd_ctx *c)
 	for (int k = 0; k < kSets; k++) {
 		TRY(own_device(c, c->d_reset[k], n * sizeof(int32_t)));
 		TRY(own_device(c, c->d_rcfg[k], n * sizeof(StreamCfg)));
+		TRY(own_device(c, c->d_tune[k], n * sizeof(uint2)));
 	}
 	for (int k = 0; k < kSets; k++) {
 		TRY(own_pinned(c, c->h_evblock[k], block));
@@ -783,7 +793,10 @@ static int make_event_blocks(tfrec_amd_ctx *c)
 		c->h_events[k] = (tfrec_amd_event *)(c->h_evblock[k] + kEvHeader);
 		TRY(own_pinned(c, c->h_reset[k], n * sizeof(int32_t)));
 		TRY(own_pinned(c, c->h_rcfg[k], n * sizeof(StreamCfg)));
+		TRY(own_pinned(c, c->h_tune[k], n * sizeof(uint2)));
 	}
+	c->tune_hz.assign(n, 0);
+	c->tune_inc.assign(n, 0u);
 	c->reset_marked.assign(n, 0);
 	c->origin.assign(n, 0);
 	return TFREC_AMD_OK;
@@ -1117,6 +1130,22 @@ static void report_debug_stats(tfrec_amd_ctx *c, int set, int n_blocks)
 	}
 }
 
+// The tuned front end's per-stream {inc, phase} of this submit, queued on the front-end stream ahead of it.  The
+// phase of the submit's first 1.536 MS/s sample n0 (4 per decimated sample, counted from the stream's start or restart --
+// 0 for a stream that restarts with this submit) is (n0 * inc) mod 2^32, in 64-bit integers.  h_tune[set] is free: the
+// set's previous submit, whose copy read it, has been drained.
+static int stage_tune(tfrec_amd_ctx *c, int set)
+{
+	for (int s = 0; s < c->cfg.n_streams; s++) {
+		const uint32_t inc = c->tune_inc[s];
+		const long long n0 = c->reset_marked[s] ? 0 : 4 * (c->sample_base - c->origin[s]);
+		c->h_tune[set][s] = make_uint2(inc, (uint32_t)((uint64_t)n0 * inc));
+	}
+	HIPCHK(hipMemcpyAsync(c->d_tune[set], c->h_tune[set], (size_t)c->cfg.n_streams * sizeof(uint2), hipMemcpyHostToDevice,
+			      c->pipe[set].fs));
+	return TFREC_AMD_OK;
+}
+
 // input_on_fs: the input was produced on the front-end stream itself (staged host input): no event needed
 static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int n_blocks, void *hip_stream, bool input_on_fs)
 {
@@ -1158,9 +1187,12 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		fin = (const uint8_t *)c->d_in16[set];
 		fstride = c->in16_stride * sizeof(uint32_t);
 	}
+	if (c->n_tuned)
+		TRY(stage_tune(c, set));
 	HIPCHK(launch_frontend(fs, fin, fstride, c->cfg.n_streams, n_blocks, c->d_tail[c->tail_sel],
 			       c->d_tail[c->tail_sel ^ 1], c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride,
-			       c->d_prevdec[set], c->cfg.thresh ? c->cfg.thresh : 500, c->taps, c->in10x));
+			       c->d_prevdec[set], c->cfg.thresh ? c->cfg.thresh : 500, c->taps, c->in10x,
+			       c->n_tuned ? c->d_tune[set] : nullptr));
 	if (c->n_auto)  // auto threshold: per-block thresholds rewrite the trigger mask (fm_demod.cpp:58-73)
 		HIPCHK(launch_threshold(fs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams,
 					n_blocks, c->d_fsk, c->wmax, c->per_stream ? c->d_scfg : nullptr));
@@ -1419,6 +1451,27 @@ int tfrec_amd_reset_streams(tfrec_amd_ctx *c, const int32_t *streams, int n)
 	return TFREC_AMD_OK;
 }
 
+// a configure or a tune: from the next submit on the kernels read every stream's own settings
+static void use_per_stream(tfrec_amd_ctx *c)
+{
+	if (c->per_stream)
+		return;
+	c->per_stream = true;
+	c->launch.scfg = c->d_scfg;
+	c->taps.scfg = c->d_scfg;
+	for (int k = 0; k < 20; k++)  // f2: the narrow taps from now on (w: the wide ones)
+		c->taps.f2[k][0] = c->taps.f2[k][1] = (float)kNarrowTaps[k] / 65536.0f;
+}
+
+// mark stream s to restart at the next submit (once per submit)
+static void mark_restart(tfrec_amd_ctx *c, int32_t s)
+{
+	if (!c->reset_marked[s]) {
+		c->reset_marked[s] = 1;
+		c->reset_pending.push_back(s);
+	}
+}
+
 int tfrec_amd_configure_streams(tfrec_amd_ctx *c, const int32_t *streams, const tfrec_amd_stream_config *cfgs, int n)
 {
 	if (!c || n < 0 || (n > 0 && (!streams || !cfgs)))
@@ -1443,21 +1496,12 @@ int tfrec_amd_configure_streams(tfrec_amd_ctx *c, const int32_t *streams, const 
 		const int s = streams[i];
 		c->scfg_api[s] = cfgs[i];
 		c->scfg[s] = device_cfg(c, cfgs[i]);
-		if (!c->reset_marked[s]) {
-			c->reset_marked[s] = 1;
-			c->reset_pending.push_back(s);
-		}
+		mark_restart(c, s);
 	}
 	c->n_auto = 0;
 	for (const StreamCfg &d : c->scfg)
 		c->n_auto += d.autoth;
-	if (!c->per_stream) {  // from the next submit on the kernels read every stream's own settings
-		c->per_stream = true;
-		c->launch.scfg = c->d_scfg;
-		c->taps.scfg = c->d_scfg;
-		for (int k = 0; k < 20; k++)  // f2: the narrow taps from now on (w: the wide ones)
-			c->taps.f2[k][0] = c->taps.f2[k][1] = (float)kNarrowTaps[k] / 65536.0f;
-	}
+	use_per_stream(c);
 	return TFREC_AMD_OK;
 }
 
@@ -1466,6 +1510,52 @@ int tfrec_amd_get_stream_config(tfrec_amd_ctx *c, int stream, tfrec_amd_stream_c
 	if (!c || !out || stream < 0 || stream >= c->cfg.n_streams)
 		return TFREC_AMD_E_INVAL;
 	*out = c->scfg_api[stream];
+	return TFREC_AMD_OK;
+}
+
+// inc = floor((tune_hz * 2^33 + 1536000) / 3072000) mod 2^32: the phase step per 1.536 MS/s sample in 2^-32 turns
+static uint32_t tune_inc(int32_t tune_hz)
+{
+	const long long num = (long long)tune_hz * (1LL << 33) + 1536000, den = 3072000;
+	long long q = num / den;
+	if (num % den != 0 && num < 0)
+		q--;  // (floor, not C's truncation)
+	return (uint32_t)(uint64_t)q;
+}
+
+int tfrec_amd_tune_streams(tfrec_amd_ctx *c, const int32_t *streams, const int32_t *tune_hz, int n)
+{
+	if (!c || n < 0 || (n > 0 && (!streams || !tune_hz)))
+		return TFREC_AMD_E_INVAL;
+	for (int i = 0; i < n; i++) {
+		TRY(check_stream(c, streams[i]));
+		if (tune_hz[i] <= -kTuneLimit || tune_hz[i] >= kTuneLimit) {
+			snprintf(g_err, sizeof(g_err), "tune_hz %d outside (-%d, %d)", (int)tune_hz[i], kTuneLimit, kTuneLimit);
+			return TFREC_AMD_E_INVAL;
+		}
+	}
+	TRY(check_live(c));
+	if (n == 0)
+		return TFREC_AMD_OK;
+	// a tune is a reset with a new tune, exactly as a configure is one with new settings
+	for (int i = 0; i < n; i++) {
+		const int s = streams[i];
+		c->tune_hz[s] = tune_hz[i];
+		c->tune_inc[s] = tune_inc(tune_hz[i]);
+		mark_restart(c, s);
+	}
+	c->n_tuned = 0;
+	for (const uint32_t inc : c->tune_inc)
+		c->n_tuned += inc != 0;
+	use_per_stream(c);
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_get_stream_tune(tfrec_amd_ctx *c, int stream, int32_t *tune_hz)
+{
+	if (!c || !tune_hz || stream < 0 || stream >= c->cfg.n_streams)
+		return TFREC_AMD_E_INVAL;
+	*tune_hz = c->tune_hz[stream];
 	return TFREC_AMD_OK;
 }
 

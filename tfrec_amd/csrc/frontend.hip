@@ -31,6 +31,7 @@
 #include <stdlib.h>
 
 #include "dsp_dev.h"
+#include "tune_table.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -42,6 +43,10 @@ __device__ __constant__ double kAtanPolyFront[16] = TFREC_ATAN_POLY;  // see dsp
 __device__ __constant__ const int kS1[8] = { 2443, 6339, 11036, 14254, 14254, 11036, 6339, 2443 };
 
 typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(4)));  // 16-byte load, dword aligned
+
+// digital tuning: C[k] = round(32767 cos(2 pi k / 4096)); S[k] = C[(k - 1024) mod 4096]
+__device__ __constant__ const int16_t kTuneCos[1 << TFREC_TUNE_BITS] = { TFREC_TUNE_COS_TABLE };
+constexpr int kTuneN = 1 << TFREC_TUNE_BITS;
 
 // IN16 = false: raw input is u8 IQ, x = (u8 - 128) << 6 (engine.cpp:77-78).  IN16 = true: the input already is
 // int16 (I,Q) pairs at 1.536 MS/s (what decim10_kernel produces for BASELINE config 5): 4 bytes per complex
@@ -56,13 +61,19 @@ constexpr int kFrontPersist = 2048;
 // tfrec_amd_configure_streams was called): `taps` is a FrontTapsCfg, and a stream's own StreamCfg picks its threshold and its
 // narrow or wide taps -- s is wave-uniform per tile, so that is a scalar load and a select per tap and tile.  (The PER = false
 // code is exactly the kernel it was before the per-stream settings: `if constexpr` keeps them out of it.)
-template <bool IN16, bool PER>
+// TUNE = true (a stream has a tune, tfrec_amd_tune_streams; implies PER): `taps` is a FrontTapsTune, and every raw sample of a
+// tuned stream is rotated as it is loaded: p = phase + n * inc, k = p >> 20, (C[k], S[k]) from a packed table
+// in LDS (16 KB), I' = (I C + Q S + 2^14) >> 15 and Q' = (Q C - I S + 2^14) >> 15 as v_dot2_i32_i16 -- (-S, C) is entry
+// k + 1024 --, then stage 1 in its int16 form.  The FIR history keeps the unrotated input.  An untuned stream of a tuned
+// context takes x = (u8 - 128) << 6 unrotated through the same int16 form (inc = 0: a scalar branch per tile).
+template <bool IN16, bool PER, bool TUNE = false>
 __global__ __launch_bounds__(kFrontThreads) void frontend_kernel(
 	const uint8_t *__restrict__ iq, size_t stride, int m_total, const uint8_t *__restrict__ tail_in,
 	uint8_t *__restrict__ tail_out, uint32_t *__restrict__ dec, size_t dec_stride,
 	unsigned long long *__restrict__ mask, size_t mask_stride, uint32_t *__restrict__ prevdec, int thresh,
-	std::conditional_t<PER, FrontTapsCfg, FrontTaps> taps, int n_streams, int persist)
+	std::conditional_t<TUNE, FrontTapsTune, std::conditional_t<PER, FrontTapsCfg, FrontTaps>> taps, int n_streams, int persist)
 {
+	static_assert(!TUNE || PER, "tuning implies the per-stream front end");
 	constexpr int kB = IN16 ? 2 : 1;             // bytes per rail sample
 	constexpr int kTail = kTailBytes * kB;      // history bytes (56 complex samples)
 	typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -73,6 +84,12 @@ __global__ __launch_bounds__(kFrontThreads) void frontend_kernel(
 	// MODE.FP_ROUND (fp32) = 2, round toward -inf: see stage 1.  Every fp32 operation of this kernel is either one of
 	// those FMAs or exact.
 	__builtin_amdgcn_s_setreg(1 | (0 << 6) | (1 << 11), 2);
+	__shared__ uint32_t cs_tab[TUNE ? kTuneN : 1];  // (C[k], S[k]) as int16 halves
+	if constexpr (TUNE) {
+		for (int i = threadIdx.x; i < kTuneN; i += kFrontThreads)
+			cs_tab[i] = (uint32_t)(uint16_t)kTuneCos[i] | ((uint32_t)(uint16_t)kTuneCos[(i - kTuneN / 4) & (kTuneN - 1)] << 16);
+		__syncthreads();
+	}
 	// A workgroup per tile (persist = 0: grid = tiles x streams), or -- persist = n -- n workgroups that take the
 	// tiles in turn: the stream's queue is then empty as soon as they are placed, and other streams' kernels can START beside a
 	// running front end (its 196 k workgroups at high priority hold the dispatcher for their whole duration otherwise)
@@ -86,6 +103,12 @@ __global__ __launch_bounds__(kFrontThreads) void frontend_kernel(
 	if constexpr (PER) {
 		thresh_s = taps.scfg[s].thresh;
 		wide_s = taps.scfg[s].wide != 0;
+	}
+	uint32_t tinc = 0, tph = 0;  // TUNE: the stream's phase increment and the phase of the submit's first sample
+	if constexpr (TUNE) {
+		const uint2 t = taps.tune[s];
+		tinc = t.x;
+		tph = t.y;
 	}
 	// (the lane index laundered per tile: what the tile derives from it is computed again instead of being kept alive across the
 	// whole loop -- with everything hoisted the kernel needed 153 registers instead of 97, three waves per SIMD instead of five)
@@ -106,6 +129,44 @@ __global__ __launch_bounds__(kFrontThreads) void frontend_kernel(
 		if (bo < 0)
 			return *reinterpret_cast<const uint32_t *>(tail_in + (size_t)s * kTail + (kTail + bo));
 		return silence;
+	};
+	// TUNE: raw dwords -> stage-1 input x (floats) of `ns` consecutive complex samples, the first of them sample n (from the
+	// submit's start; history samples are negative).  u8: the dword's two samples as packed int16 (b << 8) -- 4x the
+	// (u8 - 128) << 6 of the definition, which the shift by 17 instead of 15 takes back exactly --; int16: one sample.
+	auto tuned_x = [&](const uint32_t *rp, int ns, int n, auto *x) {
+		if (tinc == 0) {
+#pragma unroll
+			for (int i = 0; i < ns; i++) {
+				if (IN16) {
+					x[i] = f32x2{ (float)(int)(int16_t)(rp[i] & 0xffff), (float)((int)rp[i] >> 16) };
+				} else {
+					const uint32_t w = rp[i / 2] ^ 0x80808080u;
+					x[i] = f32x2{ (float)(signed char)(w >> (16 * (i & 1))) * 64.0f, (float)(signed char)(w >> (16 * (i & 1) + 8)) * 64.0f };
+				}
+			}
+			return;
+		}
+		typedef short s16x2 __attribute__((ext_vector_type(2)));
+		const uint32_t p0 = tph + (uint32_t)n * tinc;
+#pragma unroll
+		for (int i = 0; i < ns; i++) {
+			const uint32_t p = p0 + (uint32_t)i * tinc;
+			const uint32_t cs = cs_tab[p >> (32 - TFREC_TUNE_BITS)];                // (C, S)
+			const uint32_t sc = cs_tab[(p + (1u << 30)) >> (32 - TFREC_TUNE_BITS)];  // (-S, C): entry k + 1024
+			uint32_t xiq;
+			if (IN16)
+				xiq = rp[i];
+			else  // bytes b0 b1 (sample 2j) or b2 b3 (2j + 1) of the dword, two's complement, into the high bytes of the halves
+				xiq = __builtin_amdgcn_perm(0u, rp[i / 2] ^ 0x80808080u, (i & 1) ? 0x030c020cu : 0x010c000cu);
+			constexpr int kSh = IN16 ? 15 : 17;
+			int vi = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, xiq), __builtin_bit_cast(s16x2, cs), 1 << (kSh - 1), false) >> kSh;
+			int vq = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, xiq), __builtin_bit_cast(s16x2, sc), 1 << (kSh - 1), false) >> kSh;
+			if (IN16) {  // (|I'|, |Q'| <= 11585 with u8 input)
+				vi = min(max(vi, -32768), 32767);
+				vq = min(max(vq, -32768), 32767);
+			}
+			x[i] = f32x2{ (float)vi, (float)vq };
+		}
 	};
 	// history for the next submit: the last 56 raw complex samples of this one
 	if (tile == ntiles - 1 && tid < kTail / 16)
@@ -152,14 +213,18 @@ __global__ __launch_bounds__(kFrontThreads) void frontend_kernel(
 			}
 		}
 		f32x2 oy[kG1];
-		if (IN16) {
+		if (IN16 || TUNE) {
 			// int16 input: the same FMA form (below) with x * (h / 65536); x * h has up to 30 bits, which the FMA does not
 			// care about (it rounds once, after the exact product), the 8 terms sum to less than 2^16 in magnitude, and
 			// the int16 store of the reference (dsp_stuff.cpp:222) -- it can wrap here -- is the low half of the mantissa
 			f32x2 x[2 * kG1 + 6];
+			if constexpr (TUNE) {
+				tuned_x(rp, 2 * kG1 + 6, 4 * m0 - 50 + 2 * kG1 * grp, x);
+			} else {
 #pragma unroll
 			for (int i = 0; i < 2 * kG1 + 6; i++)
 				x[i] = f32x2{ (float)(int)(int16_t)(rp[i] & 0xffff), (float)((int)rp[i] >> 16) };
+			}
 			f32x2 acc[kG1];
 #pragma unroll
 			for (int n = 0; n < 8; n++) {
@@ -225,7 +290,14 @@ __global__ __launch_bounds__(kFrontThreads) void frontend_kernel(
 				rp[q] = raw_dword(base + off + 4 * q);
 		}
 		f32x2 acc = { kMagic, kMagic };
-		if (IN16) {
+		if constexpr (TUNE) {
+			f32x2 x[8];
+			tuned_x(rp, 8, 4 * m0 - 50 + 2 * slot, x);
+#pragma unroll
+			for (int n = 0; n < 8; n++)
+				acc = __builtin_elementwise_fma(x[n], f32x2{ (float)kS1[n] * (1.0f / 65536.0f), (float)kS1[n] * (1.0f / 65536.0f) }, acc);
+			y1[y1_phys(slot)] = f32x2{ (float)(int)(int16_t)(__float_as_uint(acc.x) & 0xffffu), (float)(int)(int16_t)(__float_as_uint(acc.y) & 0xffffu) };
+		} else if (IN16) {
 #pragma unroll
 			for (int n = 0; n < 8; n++) {
 				const float hs = (float)kS1[n] * (1.0f / 65536.0f);
@@ -261,8 +333,8 @@ __global__ __launch_bounds__(kFrontThreads) void frontend_kernel(
 	}
 	uint32_t outw[R];
 	uint32_t nib = 0;  // trigger bits of the lane's R samples
-	// u8 input: the sums stay below 2^14 in magnitude (|y1| <= 8526, |y2| <= 12153 with the wide taps), so the int16 store
-	// changes nothing and acc - 2^23 - 2^22 IS the sample: |I| + |Q| > thresh (fm_demod.cpp:45, tfa1.cpp:147) is evaluated on
+	// u8 input: the sums stay below 2^14 in magnitude (|y1| <= 8526, |y2| <= 12153 with the wide taps; tuned, below 2^15, as
+	// the rotated samples are at most 11585 in magnitude), so the int16 store changes nothing and acc - 2^23 - 2^22 IS the sample: |I| + |Q| > thresh (fm_demod.cpp:45, tfa1.cpp:147) is evaluated on
 	// the floats -- exact integers below 2^17 --, as the sign of (thresh + 0.5) - (|I| + |Q|) (never zero: x - x would be -0
 	// in this kernel's rounding mode).  5 instructions per sample instead of 9 and no compare / select pairs with their
 	// wait states; the 16-bit halves are packed by one v_perm_b32.
@@ -574,14 +646,23 @@ hipError_t launch_decim10(hipStream_t st, const uint8_t *iq, size_t stride, int 
 hipError_t launch_frontend(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks,
 			   const uint8_t *tail_in, uint8_t *tail_out, uint32_t *dec, size_t dec_stride,
 			   unsigned long long *mask, size_t mask_stride, uint32_t *prevdec, int thresh, const FrontTapsCfg &taps,
-			   bool in16)
+			   bool in16, const uint2 *tune)
 {
 	const int m_total = n_blocks * kBlockDec;
 	// (config 5's int16 entry keeps a workgroup per tile: behind the 10:1 stage, which it waits for, the persistent form measured 4 % slower)
 	const int persist = in16 ? 0 : kFrontPersist;
 	const dim3 grid = persist ? dim3((unsigned)std::min<long>(persist, (long)(m_total / kTileDec) * n_streams)) : dim3(m_total / kTileDec, n_streams);
 	const FrontTaps &narrow = taps;  // taps.scfg == nullptr: no stream was ever configured, the uniform kernel
-	if (taps.scfg && in16)
+	FrontTapsTune tt;  // tune != nullptr (a stream is tuned; implies scfg): the tuned kernels
+	static_cast<FrontTapsCfg &>(tt) = taps;
+	tt.tune = tune;
+	if (tune && in16)
+		hipLaunchKernelGGL((frontend_kernel<true, true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
+				   dec, dec_stride, mask, mask_stride, prevdec, thresh, tt, n_streams, persist);
+	else if (tune)
+		hipLaunchKernelGGL((frontend_kernel<false, true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
+				   dec, dec_stride, mask, mask_stride, prevdec, thresh, tt, n_streams, persist);
+	else if (taps.scfg && in16)
 		hipLaunchKernelGGL((frontend_kernel<true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
 				   dec, dec_stride, mask, mask_stride, prevdec, thresh, taps, n_streams, persist);
 	else if (taps.scfg)

@@ -62,6 +62,11 @@ struct FrontTapsCfg : FrontTaps {
 	float w[20][2];
 	const StreamCfg *scfg;  // nullptr: no stream was ever configured (the uniform front end, f2 = the context's taps)
 };
+// the tuned front end (tfrec_amd_tune_streams): per stream {inc, (n0 * inc) mod 2^32} with n0 the submit's first
+// 1.536 MS/s sample since the stream's start or restart -- the host's, one array per buffer set; inc = 0: not tuned
+struct FrontTapsTune : FrontTapsCfg {
+	const uint2 *tune;
+};
 
 // ---- biquad (dsp_stuff.cpp:28-56); state as the reference's members, coefficients in FrontParams
 struct Biquad {

@@ -33,7 +33,7 @@ gpu_engine::gpu_engine(const std::vector<std::string> &dumpfiles, int _types, in
 	if (devices.empty())
 		devices.push_back(0);
 	if (settings.size() != files.size())
-		settings.assign(files.size(), file_settings{ types, thresh, filter });
+		settings.assign(files.size(), file_settings{ types, thresh, filter, 0 });
 	// one set of protocol handlers per stream, registered like main.cpp:173-218 (with the file's own -T)
 	for (size_t s = 0; s < files.size(); s++) {
 		const int types = settings[s].types;
@@ -130,13 +130,16 @@ namespace {
 
 // One batch of a device context: the blocks every stream gets, the dump file each stream (slot) reads (-1: none, silence),
 // the streams reset before it is submitted (their previous file ended in the batch before), and the streams configured
-// before it (their next file's settings differ from the stream's current ones: a configure is a reset with new settings)
+// or tuned before it (their next file's settings or tune differ from the stream's current ones: a configure or a tune is a
+// reset with new settings)
 struct batch_plan {
 	int nb;
 	std::vector<int> file;
 	std::vector<int32_t> reset;
 	std::vector<int32_t> conf;
 	std::vector<tfrec_amd_stream_config> conf_cfg;
+	std::vector<int32_t> tune;
+	std::vector<int32_t> tune_hz;
 };
 
 // The batches that push the files [s0, s1) through nslots streams of bps blocks (file_blocks: blocks of every file of the job).
@@ -163,9 +166,15 @@ std::vector<batch_plan> plan_batches(const std::vector<size_t> &file_blocks, con
 				cur[j] = (int)f;
 				left[j] = file_blocks[f];
 				if (settings[f] != has[j]) {
+					if (!settings[f].same_config(has[j])) {
+						b.conf.push_back((int32_t)j);
+						b.conf_cfg.push_back(tfrec_amd_stream_config{ settings[f].types, settings[f].thresh, settings[f].filter, 0 });
+					}
+					if (settings[f].tune != has[j].tune) {
+						b.tune.push_back((int32_t)j);
+						b.tune_hz.push_back(settings[f].tune);
+					}
 					has[j] = settings[f];
-					b.conf.push_back((int32_t)j);
-					b.conf_cfg.push_back(tfrec_amd_stream_config{ has[j].types, has[j].thresh, has[j].filter, 0 });
 				} else if (used[j]) {
 					b.reset.push_back((int32_t)j);
 				}
@@ -346,6 +355,11 @@ struct device_worker {
 				if (rr)
 					return rr;
 			}
+			if (!b.tune.empty()) {  // ... and tunes
+				const int rr = tfrec_amd_tune_streams(ctx, b.tune.data(), b.tune_hz.data(), (int)b.tune.size());
+				if (rr)
+					return rr;
+			}
 			return tfrec_amd_submit_host(ctx, host[k % kBufs], row, b.nb);
 		};
 		size_t queued = 0;
@@ -450,7 +464,7 @@ int gpu_engine::run()
 		if (slots > 0)
 			w.nslots = std::min(w.nslots, (size_t)slots);
 		w.file_blocks = &file_blocks;
-		w.plan = plan_batches(file_blocks, settings, file_settings{ w.types, thresh, filter }, w.s0, w.s1, w.nslots, bps);
+		w.plan = plan_batches(file_blocks, settings, file_settings{ w.types, thresh, filter, 0 }, w.s0, w.s1, w.nslots, bps);
 		n_batches = std::max(n_batches, w.plan.size());
 	}
 	std::atomic<bool> abort(false);

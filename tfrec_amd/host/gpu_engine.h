@@ -81,10 +81,12 @@ private:
 	long n_records;
 };
 
-// -T, -t and -W of one dump file (tfrec_gpu -p)
+// -T, -t, -W and the tune of one dump file (tfrec_gpu -p; tune: -f minus -c, in Hz, tfrec_amd_tune_streams)
 struct file_settings {
 	int types, thresh, filter;
-	bool operator==(const file_settings &o) const { return types == o.types && thresh == o.thresh && filter == o.filter; }
+	int tune;  // Hz
+	bool same_config(const file_settings &o) const { return types == o.types && thresh == o.thresh && filter == o.filter; }
+	bool operator==(const file_settings &o) const { return same_config(o) && tune == o.tune; }
 	bool operator!=(const file_settings &o) const { return !(*this == o); }
 };
 
@@ -96,7 +98,7 @@ public:
 	// per_file (tfrec_gpu -p): each file's own settings, one per file, or empty: (types, thresh, filter) for every file.  A
 	// device's context builds the union of its files' types and has (thresh, filter) as defaults; each file's decoders are
 	// its own types', and a stream whose file's settings differ from the context's is configured
-	// (tfrec_amd_configure_streams) before the file's first batch.
+	// (tfrec_amd_configure_streams) before the file's first batch -- and tuned (tfrec_amd_tune_streams) when its tune is not 0.
 	gpu_engine(const std::vector<std::string> &dumpfiles, int types, int thresh, int filter, int dbg,
 		   const std::vector<int> &devices, int blocks_per_submit,
 		   const std::vector<file_settings> &per_file = std::vector<file_settings>());
@@ -110,8 +112,8 @@ public:
 	// the byte-level replay (store_bytes + flush) moves 64 bytes per window instead of every bit.
 	void set_bits_replay(bool on) { bits_replay = on; }
 	// -n: at most n streams per device context.  The dump files of a device go through them as a queue, in command-line order:
-	// when a file's last block has been submitted its stream is reset (tfrec_amd_reset_streams) -- or configured for the next
-	// file, when that one's settings differ -- and the next file starts there with the next batch.  0 (default): one stream
+	// when a file's last block has been submitted its stream is reset (tfrec_amd_reset_streams) -- or configured and / or tuned
+	// for the next file, when that one's settings or tune differ -- and the next file starts there with the next batch.  0 (default): one stream
 	// per file for the whole job.  A batch that carries a reset does not overlap the batch before it on the GPU (DESIGN.md
 	// 6b): a queue of mixed-length files runs at about half the throughput.
 	void set_slots(int n) { slots = n; }

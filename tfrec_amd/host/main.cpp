@@ -1,11 +1,11 @@
 // tfrec_amd/host/main.cpp -- tfrec_gpu: the reference's file-replay CLI on the GPU path.
 //
-//   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-q] [-D] [-B] [-d device[,device...]] [-b blocks] [-n streams]
-//             [-e handler | -E handler] [-m mode] [-p settings] -L dump.iq [[-p settings] -L more.iq ...]
+//   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-q] [-D] [-B] [-d device[,device...]] [-b blocks]
+//             [-n streams] [-e handler | -E handler] [-m mode] [-p settings] -L dump.iq [[-p settings] -L more.iq ...]
 //   tfrec_gpu [-T hexmask] -X telegrams.txt
 //
 // Flags keep the reference's meaning (main.cpp:63-88, 107-164): -T sensor type bit mask (hex), -t trigger
-// threshold (0 = auto, the default), -W wide filter, -q quiet, -D debug,
+// threshold (0 = auto, the default), -W wide filter, -f receive frequency in kHz, -q quiet, -D debug,
 // -e handler executed for every message, -m 1 summary at exit,
 // -L raw 8-bit IQ dump as written by "tfrec -S", -X hex telegrams for the byte-level test entry
 // (main.cpp:24-53).  Several -L files are processed as one batch, one stream each.
@@ -18,6 +18,10 @@
 // -p T=<hex>,t=<n>,W=<0|1> (not in the reference; any of the three fields, in any order): -T, -t and -W of the -L files that
 // follow it, up to the next -p -- what they would be to separate tfrec processes.  Fields left out, and files before any -p,
 // take the global -T / -t / -W.  The files share one context per device (tfrec_amd_configure_streams).
+// -f kHz keeps the reference's meaning, the receive frequency; -c kHz (not in the reference) is the frequency the dumps were
+// recorded at, by default 868250 (the reference's default -f).  A dump cannot be retuned: the difference is applied as a
+// digital shift of the recorded IQ (tfrec_amd_tune_streams), within +-767 kHz.  -p f=<kHz> sets it per file; one
+// file given twice with two f= runs as two streams.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -31,7 +35,19 @@
 // one -p spec: the fields it sets (-1: left out, the global value)
 struct spec {
 	int types = -1, thresh = -1, filter = -1;
+	long freq = -1;  // kHz
 };
+
+// a frequency in kHz: a decimal integer > 0 -> false if it is not one
+static bool parse_khz(const char *v, long &out)
+{
+	char *end = NULL;
+	const long x = strtol(v, &end, 10);
+	if (end == v || *end || x <= 0 || x > 100000000L)
+		return false;
+	out = x;
+	return true;
+}
 
 static bool parse_spec(const char *arg, spec &out)
 {
@@ -43,6 +59,14 @@ static bool parse_spec(const char *arg, spec &out)
 		if (f.size() < 3 || f[1] != '=')
 			return false;
 		const char *v = f.c_str() + 2;
+		if (f[0] == 'f') {
+			if (out.freq >= 0 || !parse_khz(v, out.freq))
+				return false;
+			if (e == std::string::npos)
+				return true;
+			pos = e + 1;
+			continue;
+		}
 		char *end = NULL;
 		const long x = strtol(v, &end, f[0] == 'T' ? 16 : 10);
 		if (*end || end == v)
@@ -109,12 +133,20 @@ int main(int argc, char **argv)
 	spec cur;  // the -p in force
 	std::vector<spec> dump_spec;  // per -L file
 	bool have_spec = false;
+	long freq = -1, center = 868250;  // -f (unset: the dumps' own frequency), -c: kHz
 	int c;
-	while ((c = getopt(argc, argv, "T:t:WqDBd:b:n:L:X:e:E:m:p:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:qDBd:b:n:L:X:e:E:m:p:h")) != -1) {
 		switch (c) {
 		case 'T': types = (int)strtol(optarg, NULL, 16); break;
 		case 't': thresh = atoi(optarg); break;
 		case 'W': filter = 1; break;
+		case 'f':
+		case 'c':
+			if (!parse_khz(optarg, c == 'f' ? freq : center)) {
+				fprintf(stderr, "tfrec_gpu: bad -%c '%s': want a frequency in kHz\n", c, optarg);
+				return 1;
+			}
+			break;
 		case 'q': dbg = -1; break;
 		case 'D': dbg++; break;
 		case 'B': bits = true; break;
@@ -132,7 +164,7 @@ int main(int argc, char **argv)
 			cur = spec();
 			have_spec = true;
 			if (!parse_spec(optarg, cur)) {
-				fprintf(stderr, "tfrec_gpu: bad -p '%s': want T=<hex mask within 2f>,t=<thresh >= 0>,W=<0|1>\n", optarg);
+				fprintf(stderr, "tfrec_gpu: bad -p '%s': want T=<hex mask within 2f>,t=<thresh >= 0>,W=<0|1>,f=<kHz>\n", optarg);
 				return 1;
 			}
 			break;
@@ -141,9 +173,11 @@ int main(int argc, char **argv)
 		case 'E': exec = optarg; batched = true; break;
 		case 'm': mode = atoi(optarg); break;
 		default:
-			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-p settings] -L dump [[-p settings] -L dump ...] | -X hexfile\n"
+			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-p settings] -L dump [[-p settings] -L dump ...] | -X hexfile\n"
+					"  -f kHz      receive frequency (default: the dumps' own, -c)\n"
+					"  -c kHz      frequency the dumps were recorded at (default 868250); -f within 767 kHz of it\n"
 					"  -n streams  at most this many streams per device: the -L files queue for them in order\n"
-					"  -p T=<hex>,t=<n>,W=<0|1>  -T / -t / -W of the -L files that follow, up to the next -p (fields left out: the global ones)\n");
+					"  -p T=<hex>,t=<n>,W=<0|1>,f=<kHz>  -T / -t / -W / -f of the -L files that follow, up to the next -p (fields left out: the global ones)\n");
 			return c == 'h' ? 0 : 1;
 		}
 	}
@@ -166,11 +200,26 @@ int main(int argc, char **argv)
 		fprintf(stderr, "tfrec_gpu: -t must be >= 0 (0 = auto)\n");
 		return 1;
 	}
+	// every file's tune, checked before any device is opened
+	std::vector<int> tunes;
+	bool tuned = false;
+	for (const spec &p : dump_spec) {
+		const long f = p.freq >= 0 ? p.freq : (freq >= 0 ? freq : center);
+		if (f - center <= -768 || f - center >= 768) {
+			fprintf(stderr, "tfrec_gpu: receive frequency %ld kHz (-f / -p f=) is %ld kHz from the dumps' %ld kHz (-c): at most "
+					"767 kHz, half the 1.536 MS/s band, can be tuned\n", f, f - center, center);
+			return 1;
+		}
+		tunes.push_back((int)((f - center) * 1000));
+		tuned = tuned || tunes.back() != 0;
+	}
 	std::vector<file_settings> per_file;
-	if (have_spec)
-		for (const spec &p : dump_spec)
+	if (have_spec || tuned)
+		for (size_t i = 0; i < dump_spec.size(); i++) {
+			const spec &p = dump_spec[i];
 			per_file.push_back(file_settings{ p.types >= 0 ? p.types : types, p.thresh >= 0 ? p.thresh : thresh,
-							  p.filter >= 0 ? p.filter : filter });
+							  p.filter >= 0 ? p.filter : filter, tunes[i] });
+		}
 	gpu_engine e(dumps, types, thresh, filter, dbg, devices, blocks, per_file);
 	if (exec || mode)
 		e.set_handler(exec, batched, mode);

@@ -1,0 +1,58 @@
+"""Digital tuning (tfrec_amd_tune_streams): the numpy restatement of the frequency shift the front end applies
+to a tuned stream's 1.536 MS/s int16 (I, Q) input before the decimating FIR.
+
+    inc   = floor((tune_hz * 2^33 + 1536000) / 3072000) mod 2^32
+    p     = (n * inc) mod 2^32,  k = p >> 20            (n: complex sample since the stream's start or last restart)
+    C[k]  = round(32767 * cos(2 pi k / 4096)),  S[k] = C[(k - 1024) mod 4096]
+    I'    = sat16((I * C[k] + Q * S[k] + 2^14) >> 15)
+    Q'    = sat16((Q * C[k] - I * S[k] + 2^14) >> 15)
+
+A signal at +tune_hz in the recording ends up at DC; tune_hz = 0 leaves the stream untouched."""
+from __future__ import annotations
+
+import numpy as np
+
+RATE = 1536000  # complex samples per second entering downconvert::process_iq
+TABLE_BITS = 12
+TUNE_MAX = RATE // 2  # |tune_hz| < TUNE_MAX
+
+
+def table():
+    """(C, S) as int32 arrays of 4096 entries: C[k] = round(32767 cos(2 pi k / 4096)), S[k] = C[(k - 1024) mod 4096]."""
+    k = np.arange(1 << TABLE_BITS)
+    c = np.round(32767.0 * np.cos(2.0 * np.pi * k / (1 << TABLE_BITS))).astype(np.int32)
+    s = c[(k - (1 << (TABLE_BITS - 2))) % (1 << TABLE_BITS)]
+    return c, s
+
+
+def inc(tune_hz: int) -> int:
+    """The phase increment per complex sample, in units of 2^-32 turns (exact integers, floor division)."""
+    t = int(tune_hz)
+    if not -TUNE_MAX < t < TUNE_MAX:
+        raise ValueError("tune_hz %d outside (-%d, %d)" % (t, TUNE_MAX, TUNE_MAX))
+    return ((t << 33) + RATE) // (2 * RATE) % (1 << 32)
+
+
+def mix_s16(x16, tune_hz: int, n0: int = 0) -> np.ndarray:
+    """Interleaved int16 (I, Q) samples x16, the first of them sample n0 of its stream -> the tuned samples (int16, same
+    layout).  tune_hz = 0: a copy of x16."""
+    x = np.ascontiguousarray(x16, dtype=np.int16).reshape(-1)
+    assert x.size % 2 == 0
+    step = inc(tune_hz)
+    if step == 0:
+        return x.copy()
+    n = (np.arange(x.size // 2, dtype=np.uint64) + np.uint64(int(n0) % (1 << 32))) & np.uint64(0xFFFFFFFF)
+    p = (n * np.uint64(step)) & np.uint64(0xFFFFFFFF)
+    k = (p >> np.uint64(32 - TABLE_BITS)).astype(np.int64)
+    c, s = table()
+    ck, sk = c[k].astype(np.int64), s[k].astype(np.int64)
+    i, q = x[0::2].astype(np.int64), x[1::2].astype(np.int64)
+    out = np.empty_like(x)
+    out[0::2] = np.clip((i * ck + q * sk + (1 << 14)) >> 15, -32768, 32767)
+    out[1::2] = np.clip((q * ck - i * sk + (1 << 14)) >> 15, -32768, 32767)
+    return out
+
+
+def s16_of_u8(iq) -> np.ndarray:
+    """The default input as the front end sees it: x = (u8 - 128) << 6 (engine.cpp:77-78), interleaved int16."""
+    return ((np.asarray(iq, dtype=np.int16) - 128) << 6).astype(np.int16)
