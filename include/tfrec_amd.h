@@ -222,6 +222,45 @@ int tfrec_amd_tune_streams(tfrec_amd_ctx *ctx, const int32_t *streams, const int
 /* The tune the next submit will use for one stream (0: untuned). */
 int tfrec_amd_get_stream_tune(tfrec_amd_ctx *ctx, int stream, int32_t *tune_hz);
 
+/* Shared inputs: stream streams[i] reads input row inputs[i] (0 <= inputs[i] < n_streams) from the NEXT submit on:
+ * its samples start at iq + inputs[i] * stream_stride_bytes.  Default: the identity (stream s reads row s).  Several streams may
+ * read one row: K receivers of one wide recording (each with its own tune and settings) need the recording in the batch once.
+ *   - A map is a restart with exactly the semantics of tfrec_amd_configure_streams / tfrec_amd_tune_streams: the same cut and
+ *     dropped open window, seq and end_sample restarting, other streams untouched.  Before the first submit it only sets the
+ *     value.  Duplicate indices: the last one wins.  A reset, configure, tune and map of one stream before one submit are ONE
+ *     restart with the latest values; later resets keep the map.  Mapping a stream to the row it reads already is still a
+ *     restart.  n == 0 is a no-op.
+ *   - Only the address a stream's samples are loaded from changes.  Everything a receiver carries stays its own, the FIR
+ *     history included: two streams on one row that restarted at different times have different histories.
+ *   - A submit must provide rows 0 .. R-1, R = 1 + the highest row a stream reads.  tfrec_amd_submit_device reads only those;
+ *     tfrec_amd_submit_host stages and copies only those (this is the saving: K receivers of one row cost one row of PCIe).
+ *     The stride rules of the submits are unchanged.
+ *   - A context in which no stream was ever mapped launches the kernels it launched before.  A mapped context of the default
+ *     input runs the per-stream tuned front end (the cost of tfrec_amd_tune_streams); with
+ *     TFREC_AMD_F_INPUT_10X the 10:1 stage's tuned kernel looks the row up and the front end is unchanged.
+ * Errors: a stream index or an input outside [0, n_streams), n < 0, streams or inputs NULL with n > 0: TFREC_AMD_E_INVAL, and
+ * nothing is marked.  A poisoned context: TFREC_AMD_E_STATE. */
+int tfrec_amd_map_streams(tfrec_amd_ctx *ctx, const int32_t *streams, const int32_t *inputs, int n);
+/* The input row the next submit will read for one stream. */
+int tfrec_amd_get_stream_input(tfrec_amd_ctx *ctx, int stream, int32_t *input);
+
+/* Wideband tune (TFREC_AMD_F_INPUT_10X contexts only): a frequency shift AHEAD of the 10:1 stage, so that a
+ * receiver can sit anywhere in the 15.36 MS/s input.  |tune_hz| < 7680000.  It is tfrec_amd_tune_streams' mixer at the input
+ * rate, on the int16 stream x = (u8 - 128) << 6 the 10:1 stage is defined on (same table C, S and the same rounding):
+ *     inc10 = floor((tune_hz * 2^33 + 15360000) / 30720000) mod 2^32
+ *     p     = (n * inc10) mod 2^32,  k = p >> 20        (n: the INPUT sample's index since the stream's start or last restart;
+ *                                                         the history before a restart is silence)
+ *     I'    = sat16((I * C[k] + Q * S[k] + 2^14) >> 15),  Q' = sat16((Q * C[k] - I * S[k] + 2^14) >> 15)
+ *     y0[m] = int16( sum_{n<60} ( x'[10 m - 50 + n] * h10[n] ) >> 16 )                           (the 10:1 stage, unchanged)
+ * tune_hz = 0 is no mixing: bit for bit the stage as it is.  tfrec_amd_tune_streams composes: it acts on y0.
+ * tfrec_amd_read_stage0 returns the shifted, decimated y0.  Pinned by tfrec_amd/tune.py (inc10, mix10_s16, decim10_s16).
+ *   - A wide tune is a restart, with the semantics, the "last wins" and the composition rules of tfrec_amd_map_streams.
+ *   - A context without a wide tune and without a map launches the 10:1 kernel it launched before.
+ * Errors: as tfrec_amd_tune_streams with the limit above; a context without TFREC_AMD_F_INPUT_10X: TFREC_AMD_E_INVAL. */
+int tfrec_amd_tune_streams_wide(tfrec_amd_ctx *ctx, const int32_t *streams, const int32_t *tune_hz, int n);
+/* The wide tune the next submit will use for one stream (0: none). */
+int tfrec_amd_get_stream_tune_wide(tfrec_amd_ctx *ctx, int stream, int32_t *tune_hz);
+
 /* Wait for submitted work. */
 int tfrec_amd_sync(tfrec_amd_ctx *ctx);
 

@@ -97,6 +97,7 @@ EXPORTS = (
     "tfrec_amd_host_free", "tfrec_amd_read_stage0", "tfrec_amd_get_fm_stats", "tfrec_amd_fm_dev_probe",
     "tfrec_amd_fifo_depth", "tfrec_amd_get_memory", "tfrec_amd_iir_probe", "tfrec_amd_reset_streams",
     "tfrec_amd_configure_streams", "tfrec_amd_get_stream_config", "tfrec_amd_tune_streams", "tfrec_amd_get_stream_tune",
+    "tfrec_amd_map_streams", "tfrec_amd_get_stream_input", "tfrec_amd_tune_streams_wide", "tfrec_amd_get_stream_tune_wide",
 )
 
 _libs = {}
@@ -159,6 +160,10 @@ def load_library(build: bool = True, experiments: bool = False):
     L.tfrec_amd_get_stream_config.argtypes = [C.c_void_p, C.c_int, C.POINTER(StreamConfig)]
     L.tfrec_amd_tune_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tfrec_amd_get_stream_tune.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
+    L.tfrec_amd_map_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.tfrec_amd_get_stream_input.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
+    L.tfrec_amd_tune_streams_wide.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.tfrec_amd_get_stream_tune_wide.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
     L.tfrec_amd_fifo_depth.restype = C.c_int
     if L.tfrec_amd_fifo_depth() != FIFO_DEPTH:
         raise RuntimeError("libtfrec_amd.so was built with FIFO depth %d, this binding expects %d" % (
@@ -203,6 +208,7 @@ class Receiver:
         self.n_streams = n_streams
         self.max_events = max_events
         self._keep = ()
+        self._rows = None  # map_streams: every stream's input row (None: the identity)
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -224,13 +230,14 @@ class Receiver:
     def submit(self, iq, n_blocks: int | None = None, stream=None):
         """iq: torch uint8 CUDA tensor [n_streams, n_bytes] (resident in HBM) or a numpy/host array."""
         if isinstance(iq, np.ndarray):
-            a = np.ascontiguousarray(iq, dtype=np.uint8).reshape(self.n_streams, -1)
+            a = np.ascontiguousarray(iq, dtype=np.uint8)
+            a = a.reshape(a.shape[0] if a.ndim == 2 and self.rows_in_use <= a.shape[0] <= self.n_streams else self.n_streams, -1)
             nb = a.shape[1] // self.block_bytes if n_blocks is None else n_blocks
             _check(self.L, self.L.tfrec_amd_submit_host(self.h, a.ctypes.data, a.strides[0], nb))
             return nb
         import torch
 
-        assert iq.is_cuda and iq.dtype == torch.uint8 and iq.dim() == 2 and iq.shape[0] == self.n_streams
+        assert iq.is_cuda and iq.dtype == torch.uint8 and iq.dim() == 2 and self.rows_in_use <= iq.shape[0] <= self.n_streams
         assert iq.stride(1) == 1
         nb = iq.shape[1] // self.block_bytes if n_blocks is None else n_blocks
         st = torch.cuda.current_stream(iq.device) if stream is None else stream
@@ -306,6 +313,54 @@ class Receiver:
         """The tune in Hz the next submit uses for one stream (tfrec_amd_get_stream_tune)."""
         v = C.c_int32(0)
         _check(self.L, self.L.tfrec_amd_get_stream_tune(self.h, int(stream), C.byref(v)))
+        return int(v.value)
+
+    def _pairs(self, fn, streams, values, what, name):
+        idx = [int(s) for s in streams]
+        if any(s < 0 or s >= self.n_streams for s in idx):  # (refused before int32 could wrap an index into range)
+            raise TfrecAmdError(E_INVAL, "stream index outside [0, %d)" % self.n_streams)
+        v = [int(values)] * len(idx) if np.ndim(values) == 0 else [int(x) for x in values]
+        if len(v) != len(idx):
+            raise ValueError("%d values for %d streams" % (len(v), len(idx)))
+        if any(not -2 ** 31 <= x < 2 ** 31 for x in v):  # (refused before int32 could wrap a value into range)
+            raise TfrecAmdError(E_INVAL, "%s outside int32" % name)
+        a = np.ascontiguousarray(idx, dtype=np.int32)
+        t = np.ascontiguousarray(v, dtype=np.int32)
+        _check(self.L, fn(self.h, a.ctypes.data if len(a) else None, t.ctypes.data if len(t) else None, len(a)))
+        return idx, v
+
+    def map_streams(self, streams, inputs):
+        """Let the listed streams read the given input rows (tfrec_amd_map_streams): `inputs` is one row for all of them or one
+        per listed stream.  Several streams may share a row; a submit then needs rows 0 .. rows_in_use - 1 only.  The streams
+        restart as fresh receivers at the next submit, exactly as after reset_streams."""
+        idx, rows = self._pairs(self.L.tfrec_amd_map_streams, streams, inputs, "map", "input row")
+        if idx:
+            if self._rows is None:
+                self._rows = list(range(self.n_streams))
+            for s, r in zip(idx, rows):
+                self._rows[s] = r
+
+    def stream_input(self, stream: int) -> int:
+        """The input row the next submit reads for one stream (tfrec_amd_get_stream_input)."""
+        v = C.c_int32(0)
+        _check(self.L, self.L.tfrec_amd_get_stream_input(self.h, int(stream), C.byref(v)))
+        return int(v.value)
+
+    @property
+    def rows_in_use(self) -> int:
+        """Rows of the input batch a submit must provide: n_streams, or 1 + the highest row mapped."""
+        return self.n_streams if self._rows is None else 1 + max(self._rows)
+
+    def tune_streams_wide(self, streams, tune_hz):
+        """Wideband tune of the listed streams (tfrec_amd_tune_streams_wide, input_10x contexts): the offset in Hz of the wanted
+        channel from the centre of the 15.36 MS/s input (|tune_hz| < 7680000; 0 = none; see tune.py: mix10_s16).  The streams
+        restart as fresh receivers at the next submit, exactly as after reset_streams."""
+        self._pairs(self.L.tfrec_amd_tune_streams_wide, streams, tune_hz, "tune", "tune_hz")
+
+    def stream_tune_wide(self, stream: int) -> int:
+        """The wide tune in Hz the next submit uses for one stream (tfrec_amd_get_stream_tune_wide)."""
+        v = C.c_int32(0)
+        _check(self.L, self.L.tfrec_amd_get_stream_tune_wide(self.h, int(stream), C.byref(v)))
         return int(v.value)
 
     def drain(self, allow_overflow: bool = False) -> np.ndarray:

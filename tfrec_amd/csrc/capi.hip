@@ -13,11 +13,11 @@
 
 namespace tfrec {
 hipError_t launch_decim10(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks,
-			  const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride);
+			  const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride, const uint4 *chan);
 hipError_t launch_frontend(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks,
 			   const uint8_t *tail_in, uint8_t *tail_out, uint32_t *dec, size_t dec_stride,
 			   unsigned long long *mask, size_t mask_stride, uint32_t *prevdec, int thresh, const FrontTapsCfg &taps,
-			   bool in16, const uint2 *tune);
+			   bool in16, const uint2 *tune, const uint4 *chan);
 hipError_t launch_fmdev(hipStream_t st, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask,
 			size_t mask_stride, const uint32_t *prevdec, int16_t *fmdev, size_t fmdev_stride, EventBuf *eb,
 			int n_streams, int n_blocks, int wmax, double flag_eps);
@@ -38,6 +38,7 @@ hipError_t launch_chains(hipStream_t st, const uint32_t *dec, size_t dec_stride,
 using namespace tfrec;
 
 constexpr int kTuneLimit = 768000;  // |tune_hz| < half the 1.536 MS/s sample rate
+constexpr int kTuneWideLimit = 7680000;  // tfrec_amd_tune_streams_wide: half the 15.36 MS/s input rate
 
 // Buffer / table sets = submits that may be in flight (the FIFO depth): front end of submit k+2, biquad stage of
 // k+1 and slicer stage of k run beside each other in the deep layout
@@ -134,6 +135,16 @@ struct tfrec_amd_ctx {
 	std::vector<uint32_t> tune_inc;
 	uint2 *d_tune[kSets] = {}, *h_tune[kSets] = {};
 	int n_tuned = 0;
+	// tfrec_amd_map_streams / tfrec_amd_tune_streams_wide: the input row every stream reads from the next submit
+	// on (the identity until a stream is mapped: `mapped`), every stream's wide tune and its phase increment per 15.36 MS/s
+	// sample (n_wide: streams with wide_inc != 0), and per set the {inc10, phase10, row, 0} the set's 10:1 stage -- in a context
+	// of the default input the front end, for the row -- reads (h_chan -> d_chan, filled by the submit).
+	std::vector<int32_t> row;
+	bool mapped = false;
+	std::vector<int32_t> wide_hz;
+	std::vector<uint32_t> wide_inc;
+	int n_wide = 0;
+	uint4 *d_chan[kSets] = {}, *h_chan[kSets] = {};
 	uint8_t *d_tail[kSets] = {};  // FIR history: [tail_sel] is read by the next front end, [tail_sel ^ 1] written
 	int tail_sel = 0;
 	// TFREC_AMD_F_INPUT_10X: output of the 10:1 stage (1.536 MS/s int16 pairs, one buffer per set) and its raw history
@@ -785,6 +796,7 @@ static int make_event_blocks(tfrec_amd_ctx *c)
 		TRY(own_device(c, c->d_reset[k], n * sizeof(int32_t)));
 		TRY(own_device(c, c->d_rcfg[k], n * sizeof(StreamCfg)));
 		TRY(own_device(c, c->d_tune[k], n * sizeof(uint2)));
+		TRY(own_device(c, c->d_chan[k], n * sizeof(uint4)));
 	}
 	for (int k = 0; k < kSets; k++) {
 		TRY(own_pinned(c, c->h_evblock[k], block));
@@ -794,9 +806,15 @@ static int make_event_blocks(tfrec_amd_ctx *c)
 		TRY(own_pinned(c, c->h_reset[k], n * sizeof(int32_t)));
 		TRY(own_pinned(c, c->h_rcfg[k], n * sizeof(StreamCfg)));
 		TRY(own_pinned(c, c->h_tune[k], n * sizeof(uint2)));
+		TRY(own_pinned(c, c->h_chan[k], n * sizeof(uint4)));
 	}
 	c->tune_hz.assign(n, 0);
 	c->tune_inc.assign(n, 0u);
+	c->wide_hz.assign(n, 0);
+	c->wide_inc.assign(n, 0u);
+	c->row.resize(n);
+	for (size_t s = 0; s < n; s++)
+		c->row[s] = (int32_t)s;
 	c->reset_marked.assign(n, 0);
 	c->origin.assign(n, 0);
 	return TFREC_AMD_OK;
@@ -1146,6 +1164,28 @@ static int stage_tune(tfrec_amd_ctx *c, int set)
 	return TFREC_AMD_OK;
 }
 
+// The per-stream {inc10, phase10, input row, 0} of this submit, staged like stage_tune's.  phase10 is the phase of
+// the submit's first INPUT sample n0 (40 per decimated sample with TFREC_AMD_F_INPUT_10X): (n0 * inc10) mod 2^32.
+static int stage_chan(tfrec_amd_ctx *c, int set)
+{
+	for (int s = 0; s < c->cfg.n_streams; s++) {
+		const uint32_t inc = c->wide_inc[s];
+		const long long n0 = c->reset_marked[s] ? 0 : 40 * (c->sample_base - c->origin[s]);
+		c->h_chan[set][s] = make_uint4(inc, (uint32_t)((uint64_t)n0 * inc), (uint32_t)c->row[s], 0u);
+	}
+	HIPCHK(hipMemcpyAsync(c->d_chan[set], c->h_chan[set], (size_t)c->cfg.n_streams * sizeof(uint4), hipMemcpyHostToDevice,
+			      c->pipe[set].fs));
+	return TFREC_AMD_OK;
+}
+
+// rows of the input batch the streams read: 1 + the highest one mapped
+static int rows_in_use(const tfrec_amd_ctx *c)
+{
+	if (!c->mapped)
+		return c->cfg.n_streams;
+	return 1 + *std::max_element(c->row.begin(), c->row.end());
+}
+
 // input_on_fs: the input was produced on the front-end stream itself (staged host input): no event needed
 static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int n_blocks, void *hip_stream, bool input_on_fs)
 {
@@ -1153,7 +1193,7 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		return TFREC_AMD_E_INVAL;
 	const size_t block_bytes = c->in10x ? TFREC_AMD_BLOCK_BYTES_10X : TFREC_AMD_BLOCK_BYTES;
 	if ((stride % 16) != 0 || ((uintptr_t)d_iq % 16) != 0 ||
-	    (c->cfg.n_streams > 1 && stride < (size_t)n_blocks * block_bytes)) {
+	    (rows_in_use(c) > 1 && stride < (size_t)n_blocks * block_bytes)) {  // (one row in use: the stride is never applied)
 		snprintf(g_err, sizeof(g_err), "IQ base and stream stride must be 16-byte aligned and >= one stream");
 		return TFREC_AMD_E_INVAL;
 	}
@@ -1181,18 +1221,22 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		TRY(launch_resets(c, set));
 	const uint8_t *fin = (const uint8_t *)d_iq;
 	size_t fstride = stride;
+	// a mapped or wide-tuned context: the 10:1 stage's tuned kernel, or -- default input -- the front end that looks up the rows
+	const bool chan10 = c->in10x && (c->mapped || c->n_wide), chan_front = !c->in10x && c->mapped;
+	if (chan10 || chan_front)
+		TRY(stage_chan(c, set));
 	if (c->in10x) {  // 15.36 MS/s u8 -> 1.536 MS/s int16 pairs, then the standard cascade on int16 input
 		HIPCHK(launch_decim10(fs, (const uint8_t *)d_iq, stride, c->cfg.n_streams, n_blocks, c->d_tail10[c->tail_sel],
-				      c->d_tail10[c->tail_sel ^ 1], c->d_in16[set], c->in16_stride));
+				      c->d_tail10[c->tail_sel ^ 1], c->d_in16[set], c->in16_stride, chan10 ? c->d_chan[set] : nullptr));
 		fin = (const uint8_t *)c->d_in16[set];
 		fstride = c->in16_stride * sizeof(uint32_t);
 	}
-	if (c->n_tuned)
+	if (c->n_tuned || chan_front)
 		TRY(stage_tune(c, set));
 	HIPCHK(launch_frontend(fs, fin, fstride, c->cfg.n_streams, n_blocks, c->d_tail[c->tail_sel],
 			       c->d_tail[c->tail_sel ^ 1], c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride,
 			       c->d_prevdec[set], c->cfg.thresh ? c->cfg.thresh : 500, c->taps, c->in10x,
-			       c->n_tuned ? c->d_tune[set] : nullptr));
+			       (c->n_tuned || chan_front) ? c->d_tune[set] : nullptr, chan_front ? c->d_chan[set] : nullptr));
 	if (c->n_auto)  // auto threshold: per-block thresholds rewrite the trigger mask (fm_demod.cpp:58-73)
 		HIPCHK(launch_threshold(fs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams,
 					n_blocks, c->d_fsk, c->wmax, c->per_stream ? c->d_scfg : nullptr));
@@ -1282,12 +1326,13 @@ static int submit_host_impl(tfrec_amd_ctx *c, const uint8_t *h_iq, size_t stride
 	if (!c || !h_iq || n_blocks < 1 || n_blocks > c->cfg.max_blocks)
 		return TFREC_AMD_E_INVAL;
 	const size_t row = (size_t)n_blocks * (c->in10x ? TFREC_AMD_BLOCK_BYTES_10X : TFREC_AMD_BLOCK_BYTES);
-	if (c->cfg.n_streams > 1 && stride < row)
+	if (rows_in_use(c) > 1 && stride < row)
 		return TFREC_AMD_E_INVAL;
 	TRY(check_fifo(c));
 	HIPCHK(hipSetDevice(c->cfg.device));
 	const int set = (c->head + c->inflight) % kSets;  // the set's previous user has been drained: its staging buffer is free
-	const size_t need = row * (size_t)c->cfg.n_streams;
+	const size_t rows = (size_t)rows_in_use(c);  // (a mapped context: only the rows a stream reads are staged and copied)
+	const size_t need = row * rows;
 	if (c->stage_bytes[set] < need) {
 		(void)hipFree(c->d_stage[set]);
 		c->d_stage[set] = nullptr;
@@ -1298,7 +1343,7 @@ static int submit_host_impl(tfrec_amd_ctx *c, const uint8_t *h_iq, size_t stride
 	}
 	// asynchronous on the front-end stream when h_iq is pinned (tfrec_amd_host_alloc); pageable memory is staged
 	// by the runtime before the call returns
-	HIPCHK(hipMemcpy2DAsync(c->d_stage[set], row, h_iq, stride, row, (size_t)c->cfg.n_streams, hipMemcpyHostToDevice, c->pipe[set].fs));
+	HIPCHK(hipMemcpy2DAsync(c->d_stage[set], row, h_iq, stride, row, rows, hipMemcpyHostToDevice, c->pipe[set].fs));
 	return submit_common(c, c->d_stage[set], row, n_blocks, nullptr, true);
 }
 
@@ -1556,6 +1601,87 @@ int tfrec_amd_get_stream_tune(tfrec_amd_ctx *c, int stream, int32_t *tune_hz)
 	if (!c || !tune_hz || stream < 0 || stream >= c->cfg.n_streams)
 		return TFREC_AMD_E_INVAL;
 	*tune_hz = c->tune_hz[stream];
+	return TFREC_AMD_OK;
+}
+
+// a map is a restart that changes the row the stream's tiles are loaded from -- also when it names the row the stream reads already
+int tfrec_amd_map_streams(tfrec_amd_ctx *c, const int32_t *streams, const int32_t *inputs, int n)
+{
+	if (!c || n < 0 || (n > 0 && (!streams || !inputs)))
+		return TFREC_AMD_E_INVAL;
+	for (int i = 0; i < n; i++) {
+		TRY(check_stream(c, streams[i]));
+		if (inputs[i] < 0 || inputs[i] >= c->cfg.n_streams) {
+			snprintf(g_err, sizeof(g_err), "input row %d outside [0, %d)", (int)inputs[i], c->cfg.n_streams);
+			return TFREC_AMD_E_INVAL;
+		}
+	}
+	TRY(check_live(c));
+	if (n == 0)
+		return TFREC_AMD_OK;
+	for (int i = 0; i < n; i++) {
+		c->row[streams[i]] = inputs[i];
+		mark_restart(c, streams[i]);
+	}
+	c->mapped = true;
+	if (!c->in10x)  // (the mapped front end is a per-stream variant; with the 10x input the 10:1 stage maps)
+		use_per_stream(c);
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_get_stream_input(tfrec_amd_ctx *c, int stream, int32_t *input)
+{
+	if (!c || !input || stream < 0 || stream >= c->cfg.n_streams)
+		return TFREC_AMD_E_INVAL;
+	*input = c->row[stream];
+	return TFREC_AMD_OK;
+}
+
+// inc10 = floor((tune_hz * 2^33 + 15360000) / 30720000) mod 2^32: the phase step per 15.36 MS/s sample
+static uint32_t tune_inc10(int32_t tune_hz)
+{
+	const long long num = (long long)tune_hz * (1LL << 33) + 15360000, den = 30720000;
+	long long q = num / den;
+	if (num % den != 0 && num < 0)
+		q--;  // (floor, not C's truncation)
+	return (uint32_t)(uint64_t)q;
+}
+
+int tfrec_amd_tune_streams_wide(tfrec_amd_ctx *c, const int32_t *streams, const int32_t *tune_hz, int n)
+{
+	if (!c || n < 0 || (n > 0 && (!streams || !tune_hz)))
+		return TFREC_AMD_E_INVAL;
+	if (!c->in10x) {
+		snprintf(g_err, sizeof(g_err), "the wide tune acts ahead of the 10:1 stage: the context needs the 15.36 MS/s input flag");
+		return TFREC_AMD_E_INVAL;
+	}
+	for (int i = 0; i < n; i++) {
+		TRY(check_stream(c, streams[i]));
+		if (tune_hz[i] <= -kTuneWideLimit || tune_hz[i] >= kTuneWideLimit) {
+			snprintf(g_err, sizeof(g_err), "tune_hz %d outside (-%d, %d)", (int)tune_hz[i], kTuneWideLimit, kTuneWideLimit);
+			return TFREC_AMD_E_INVAL;
+		}
+	}
+	TRY(check_live(c));
+	if (n == 0)
+		return TFREC_AMD_OK;
+	for (int i = 0; i < n; i++) {
+		const int s = streams[i];
+		c->wide_hz[s] = tune_hz[i];
+		c->wide_inc[s] = tune_inc10(tune_hz[i]);
+		mark_restart(c, s);
+	}
+	c->n_wide = 0;
+	for (const uint32_t inc : c->wide_inc)
+		c->n_wide += inc != 0;
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_get_stream_tune_wide(tfrec_amd_ctx *c, int stream, int32_t *tune_hz)
+{
+	if (!c || !tune_hz || stream < 0 || stream >= c->cfg.n_streams)
+		return TFREC_AMD_E_INVAL;
+	*tune_hz = c->wide_hz[stream];
 	return TFREC_AMD_OK;
 }
 

@@ -66,14 +66,19 @@ constexpr int kFrontPersist = 2048;
 // in LDS (16 KB), I' = (I C + Q S + 2^14) >> 15 and Q' = (Q C - I S + 2^14) >> 15 as v_dot2_i32_i16 -- (-S, C) is entry
 // k + 1024 --, then stage 1 in its int16 form.  The FIR history keeps the unrotated input.  An untuned stream of a tuned
 // context takes x = (u8 - 128) << 6 unrotated through the same int16 form (inc = 0: a scalar branch per tile).
-template <bool IN16, bool PER, bool TUNE = false>
+// MAP = true (a stream reads another stream's input row, tfrec_amd_map_streams; default input only -- with
+// TFREC_AMD_F_INPUT_10X the 10:1 stage does the mapping; implies TUNE): `taps` is a FrontTapsMap, and the stream's tile is loaded
+// from row chan[s].z of the batch.  Everything else, the FIR history included, stays the stream's own.
+template <bool IN16, bool PER, bool TUNE = false, bool MAP = false>
 __global__ __launch_bounds__(kFrontThreads) void frontend_kernel(
 	const uint8_t *__restrict__ iq, size_t stride, int m_total, const uint8_t *__restrict__ tail_in,
 	uint8_t *__restrict__ tail_out, uint32_t *__restrict__ dec, size_t dec_stride,
 	unsigned long long *__restrict__ mask, size_t mask_stride, uint32_t *__restrict__ prevdec, int thresh,
-	std::conditional_t<TUNE, FrontTapsTune, std::conditional_t<PER, FrontTapsCfg, FrontTaps>> taps, int n_streams, int persist)
+	std::conditional_t<MAP, FrontTapsMap, std::conditional_t<TUNE, FrontTapsTune, std::conditional_t<PER, FrontTapsCfg, FrontTaps>>> taps,
+	int n_streams, int persist)
 {
 	static_assert(!TUNE || PER, "tuning implies the per-stream front end");
+	static_assert(!MAP || (TUNE && !IN16), "mapping implies the tuned front end on the default input");
 	constexpr int kB = IN16 ? 2 : 1;             // bytes per rail sample
 	constexpr int kTail = kTailBytes * kB;      // history bytes (56 complex samples)
 	typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -116,6 +121,8 @@ __global__ __launch_bounds__(kFrontThreads) void frontend_kernel(
 	asm volatile("" : "+v"(tid));
 	const int m0 = tile * kTileDec;
 	const uint8_t *src = iq + (size_t)s * stride;
+	if constexpr (MAP)
+		src = iq + (size_t)taps.chan[s].z * stride;
 	// The tile reads raw bytes [8*m0 - 112, 8*m0 + 8*T + 16) (x kB) straight from global memory: a lane's 76 bytes per
 	// stage-1 group overlap its neighbours' (64-byte stride), so the last load of a group hits what the first one of
 	// the next lane brought in; the 112 bytes before the submit come from the previous one's tail, what lies behind its
@@ -547,16 +554,48 @@ __device__ __constant__ const int kTaps10[60] = {
 	-668, -511, -343, -185, -53,  44,   104,  132,  135,  121,  98,   72,   48,   27,   9,
 };
 
+// TUNE = true (a stream of the context has a wide tune, tfrec_amd_tune_streams_wide, or reads another stream's
+// input row, tfrec_amd_map_streams): `chan` holds per stream {inc10, phase of the submit's first input sample, input row, 0}.
+// The tile is staged into LDS as an int16 (I, Q) image, one dword per complex sample, and every sample of a tuned stream is
+// rotated ONCE while it is staged (6d's mixer at the input rate: p = phase + n * inc10, k = p >> 20, the u8 sample as
+// packed b << 8 = 4 x, two v_dot2_i32_i16 with a shift by 17 instead of 15; |I'|, |Q'| <= 11585: nothing saturates), an
+// untuned one (inc10 = 0) is widened to x = (u8 - 128) << 6.  The taps then run in their int16 form, (x' * h) >> 16 per
+// tap: the same FMA onto the same accumulator, the product exact whatever its width.  The history (tail) stays raw u8:
+// a history sample is rotated with its own n (negative from the tile's phase), and 0x80 -- silence after a restart --
+// rotates to 0.  A lane's 80 dwords are followed by one pad dword (stride 81: 64 lanes, 64 banks); the cosine table
+// sits beside the image as 4096 int16 (8 KB; S[k] is C[k - 1024]).  TUNE = false is the kernel as it was: `chan` is an
+// empty parameter pack there (a parameter of any type would move the hidden kernel arguments), one `const uint4 *` with TUNE.
+constexpr int kImg10 = kTail10 / 2 + 10 * kT10;  // TUNE: complex samples of a tile's image (sample 0 = input sample 10 m0 - 56)
+constexpr int kLaneS10 = 10 * kR10;             // 80: a lane's stride in samples, = the pad interval
+static_assert(kLaneS10 % 8 == 0, "a staged chunk of 8 samples never straddles a pad");
+__device__ __forceinline__ constexpr int pad10t(int d) { return d + d / kLaneS10; }
+
+template <bool TUNE, class... Chan>
 __global__ __launch_bounds__(kThreads10) void decim10_kernel(const uint8_t *__restrict__ iq, size_t stride, long n_out,
 							     const uint8_t *__restrict__ tail_in, uint8_t *__restrict__ tail_out,
-							     uint32_t *__restrict__ out, size_t out_stride)
+							     uint32_t *__restrict__ out, size_t out_stride,
+							     Chan... chan)
 {
-	__shared__ uint32_t raw[pad10(kRawDw10) + 4];
+	static_assert(sizeof...(Chan) == (TUNE ? 1 : 0), "TUNE: one const uint4 *");
+	__shared__ uint32_t raw[TUNE ? pad10t(kImg10) : pad10(kRawDw10) + 4];
+	__shared__ int16_t ctab[TUNE ? kTuneN : 1];
 	const int s = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
 	const long m0 = (long)tile * kT10;
 	__builtin_amdgcn_s_setreg(1 | (0 << 6) | (1 << 11), 2);  // fp32 rounding toward -inf (see frontend_kernel, stage 1)
 	const long nbytes = 20L * n_out;
 	const uint8_t *src = iq + (size_t)s * stride;
+	uint32_t tinc = 0, tph = 0;
+	if constexpr (TUNE) {
+		const uint4 ch = (chan, ...)[s];
+		tinc = ch.x;
+		tph = ch.y;
+		src = iq + (size_t)ch.z * stride;
+		if (tinc != 0)  // (uniform for the workgroup; the barrier behind the staging loop covers the table too)
+			for (int i = tid; i < kTuneN / 2; i += kThreads10)
+				reinterpret_cast<uint32_t *>(ctab)[i] = (uint32_t)(uint16_t)kTuneCos[2 * i] | ((uint32_t)(uint16_t)kTuneCos[2 * i + 1] << 16);
+		if (tinc != 0)
+			__syncthreads();
+	}
 	// ---- stage the tile: chunk c = logical dwords 4c .. 4c + 3 = stream bytes 20 m0 - 112 + 16 c ..; the submit's first
 	// tile takes its first seven chunks from the previous submit's tail
 	const long base = 20L * m0 - kTail10;
@@ -568,8 +607,36 @@ __global__ __launch_bounds__(kThreads10) void decim10_kernel(const uint8_t *__re
 			const long bo = base + 16L * c;
 			const uint4 v = bo >= 0 ? *reinterpret_cast<const uint4 *>(src + bo)
 						: *reinterpret_cast<const uint4 *>(tail_in + (size_t)s * kTail10 + (kTail10 + bo));
+			if constexpr (TUNE) {
+				// the chunk's 8 samples = image dwords 8c .. 8c + 7; the first is input sample 10 m0 - 56 + 8c of the submit
+				typedef short s16x2 __attribute__((ext_vector_type(2)));
+				uint32_t *d = raw + 8 * c + c / (kLaneS10 / 8);
+				const uint32_t w4[4] = { v.x ^ 0x80808080u, v.y ^ 0x80808080u, v.z ^ 0x80808080u, v.w ^ 0x80808080u };
+				if (tinc == 0) {
+#pragma unroll
+					for (int i = 0; i < 8; i++) {  // (b << 8) >> 2 per half = b << 6
+						const uint32_t x4 = __builtin_amdgcn_perm(0u, w4[i / 2], (i & 1) ? 0x030c020cu : 0x010c000cu);
+						d[i] = ((uint32_t)((int)(int16_t)(x4 & 0xffffu) >> 2) & 0xffffu) | ((uint32_t)((int)x4 >> 18) << 16);
+					}
+				} else {
+					const uint32_t p0 = tph + (uint32_t)(10 * (int)m0 - kTail10 / 2 + 8 * c) * tinc;
+#pragma unroll
+					for (int i = 0; i < 8; i++) {
+						const uint32_t p = p0 + (uint32_t)i * tinc;
+						const uint32_t k = p >> (32 - TFREC_TUNE_BITS);
+						const int C = ctab[k], S = ctab[(k - kTuneN / 4) & (kTuneN - 1)];
+						const uint32_t cs = ((uint32_t)C & 0xffffu) | ((uint32_t)S << 16);   // (C, S)
+						const uint32_t sc = ((uint32_t)-S & 0xffffu) | ((uint32_t)C << 16);  // (-S, C)
+						const uint32_t x4 = __builtin_amdgcn_perm(0u, w4[i / 2], (i & 1) ? 0x030c020cu : 0x010c000cu);
+						const int vi = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, x4), __builtin_bit_cast(s16x2, cs), 1 << 16, false) >> 17;
+						const int vq = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, x4), __builtin_bit_cast(s16x2, sc), 1 << 16, false) >> 17;
+						d[i] = ((uint32_t)vi & 0xffffu) | ((uint32_t)vq << 16);
+					}
+				}
+			} else {
 			uint32_t *d = raw + 4 * c + c / (kLaneDw10 / 4);
 			d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+			}
 		}
 	}
 	if (tile == (int)gridDim.x - 1 && tid < kTail10 / 16)
@@ -577,7 +644,8 @@ __global__ __launch_bounds__(kThreads10) void decim10_kernel(const uint8_t *__re
 			*reinterpret_cast<const uint4 *>(src + nbytes - kTail10 + 16 * tid);
 	__syncthreads();
 	// ---- the lane's outputs m0 + 8 tid + o: raw samples [10 m - 50, 10 m + 80) = logical dwords 40 tid + 3 + w, w < 65
-	const uint32_t *lp = raw + (kLaneDw10 + 1) * tid;  // physical dword of logical 40 tid
+	// (TUNE: image dwords 80 tid + 6 + w, w < 130)
+	const uint32_t *lp = raw + (TUNE ? kLaneS10 + 1 : kLaneDw10 + 1) * tid;  // physical dword of logical 40 tid (80 tid)
 	// (d*h) >> 10 per tap as one fp32 FMA in round-toward-minus-infinity mode, both rails per v_pk_fma_f32: see stage 1 of
 	// frontend_kernel.  The 60 taps' terms sum to less than 2^14.  The raw dwords come from LDS eight at a time, one group
 	// ahead of the one being consumed (all 65 up front cost 130 registers).
@@ -587,31 +655,34 @@ __global__ __launch_bounds__(kThreads10) void decim10_kernel(const uint8_t *__re
 #pragma unroll
 	for (int o = 0; o < kR10; o++)
 		acc[o] = f32x2{ kMagic, kMagic };
-	constexpr int kGrp = 8, kGroups10 = (kD10 + kGrp - 1) / kGrp;
+	constexpr int kD = TUNE ? 2 * kD10 : kD10;  // dwords a lane reads
+	constexpr int kGrp = 8, kGroups10 = (kD + kGrp - 1) / kGrp;
+	auto lds = [&](int w) -> uint32_t { return TUNE ? lp[pad10t(6 + w)] : lp[pad10(3 + w)]; };
 	uint32_t cur[kGrp], nxt[kGrp];
 #pragma unroll
 	for (int k = 0; k < kGrp; k++)
-		cur[k] = lp[pad10(3 + k)];
+		cur[k] = lds(k);
 #pragma unroll
 	for (int g = 0; g < kGroups10; g++) {
 #pragma unroll
 		for (int k = 0; k < kGrp; k++)
-			nxt[k] = kGrp * (g + 1) + k < kD10 ? lp[pad10(3 + kGrp * (g + 1) + k)] : 0u;
+			nxt[k] = kGrp * (g + 1) + k < kD ? lds(kGrp * (g + 1) + k) : 0u;
 #pragma unroll
 		for (int k = 0; k < kGrp; k++) {
-			const int w = kGrp * g + k;  // one dword = two complex samples
-			if (w < kD10) {
-				const uint32_t v = cur[k] ^ 0x80808080u;  // bytes become two's complement (u8 - 128)
-				const f32x2 x[2] = { f32x2{ (float)(signed char)(v), (float)(signed char)(v >> 8) },
+			const int w = kGrp * g + k;  // one dword = two complex samples (TUNE: one)
+			if (w < kD) {
+				const uint32_t v = TUNE ? cur[k] : cur[k] ^ 0x80808080u;  // bytes become two's complement (u8 - 128)
+				const f32x2 x[2] = { TUNE ? f32x2{ (float)(int)(int16_t)(v & 0xffffu), (float)((int)v >> 16) }
+							  : f32x2{ (float)(signed char)(v), (float)(signed char)(v >> 8) },
 						     f32x2{ (float)(signed char)(v >> 16), (float)((int)v >> 24) } };
 #pragma unroll
-				for (int h = 0; h < 2; h++) {
-					const int c = 2 * w + h;  // sample index relative to 10 m - 50
+				for (int h = 0; h < (TUNE ? 1 : 2); h++) {
+					const int c = TUNE ? w : 2 * w + h;  // sample index relative to 10 m - 50
 #pragma unroll
 					for (int o = 0; o < kR10; o++) {
 						const int n = c - 10 * o;
 						if (n >= 0 && n < 60) {
-							const float hs = (float)kTaps10[n] * (1.0f / 1024.0f);
+							const float hs = (float)kTaps10[n] * (TUNE ? 1.0f / 65536.0f : 1.0f / 1024.0f);
 							acc[o] = __builtin_elementwise_fma(x[h], f32x2{ hs, hs }, acc[o]);
 						}
 					}
@@ -633,20 +704,24 @@ __global__ __launch_bounds__(kThreads10) void decim10_kernel(const uint8_t *__re
 		dst[q] = make_uint4(ow[4 * q], ow[4 * q + 1], ow[4 * q + 2], ow[4 * q + 3]);
 }
 
+// chan != nullptr: the tuned / mapped kernel (per stream {inc10, phase10, input row, 0})
 hipError_t launch_decim10(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks,
-			  const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride)
+			  const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride, const uint4 *chan)
 {
 	const long n_out = (long)n_blocks * (TFREC_AMD_BLOCK_BYTES / 2);  // complex samples at 1.536 MS/s
 	static_assert(kBlockDec * 4 % kT10 == 0, "decim10_kernel has no partial tiles: a block is a whole number of them");
 	dim3 grid((unsigned)(n_out / kT10), n_streams);
-	hipLaunchKernelGGL(decim10_kernel, grid, dim3(kThreads10), 0, st, iq, stride, n_out, tail_in, tail_out, out, out_stride);
+	if (chan)
+		hipLaunchKernelGGL((decim10_kernel<true, const uint4 *>), grid, dim3(kThreads10), 0, st, iq, stride, n_out, tail_in, tail_out, out, out_stride, chan);
+	else
+		hipLaunchKernelGGL(decim10_kernel<false>, grid, dim3(kThreads10), 0, st, iq, stride, n_out, tail_in, tail_out, out, out_stride);
 	return hipGetLastError();
 }
 
 hipError_t launch_frontend(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks,
 			   const uint8_t *tail_in, uint8_t *tail_out, uint32_t *dec, size_t dec_stride,
 			   unsigned long long *mask, size_t mask_stride, uint32_t *prevdec, int thresh, const FrontTapsCfg &taps,
-			   bool in16, const uint2 *tune)
+			   bool in16, const uint2 *tune, const uint4 *chan)
 {
 	const int m_total = n_blocks * kBlockDec;
 	// (config 5's int16 entry keeps a workgroup per tile: behind the 10:1 stage, which it waits for, the persistent form measured 4 % slower)
@@ -656,7 +731,13 @@ hipError_t launch_frontend(hipStream_t st, const uint8_t *iq, size_t stride, int
 	FrontTapsTune tt;  // tune != nullptr (a stream is tuned; implies scfg): the tuned kernels
 	static_cast<FrontTapsCfg &>(tt) = taps;
 	tt.tune = tune;
-	if (tune && in16)
+	if (chan && tune && !in16) {  // a mapped context (default input): the tuned kernel that looks up every stream's input row
+		FrontTapsMap tm;
+		static_cast<FrontTapsTune &>(tm) = tt;
+		tm.chan = chan;
+		hipLaunchKernelGGL((frontend_kernel<false, true, true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
+				   dec, dec_stride, mask, mask_stride, prevdec, thresh, tm, n_streams, persist);
+	} else if (tune && in16)
 		hipLaunchKernelGGL((frontend_kernel<true, true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
 				   dec, dec_stride, mask, mask_stride, prevdec, thresh, tt, n_streams, persist);
 	else if (tune)

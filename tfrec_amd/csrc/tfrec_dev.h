@@ -67,6 +67,11 @@ struct FrontTapsCfg : FrontTaps {
 struct FrontTapsTune : FrontTapsCfg {
 	const uint2 *tune;
 };
+// the mapped front end (tfrec_amd_map_streams): per stream {inc10, phase10, input row, 0} -- the array the 10:1
+// stage's tuned kernel reads with TFREC_AMD_F_INPUT_10X; the front end uses the row
+struct FrontTapsMap : FrontTapsTune {
+	const uint4 *chan;
+};
 
 // ---- biquad (dsp_stuff.cpp:28-56); state as the reference's members, coefficients in FrontParams
 struct Biquad {

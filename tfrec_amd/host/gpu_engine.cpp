@@ -28,7 +28,7 @@ void tfrec_handler_args(const sensordata_t &d, sensor_e dec_type, char *out, siz
 gpu_engine::gpu_engine(const std::vector<std::string> &dumpfiles, int _types, int _thresh, int _filter, int _dbg,
 		       const std::vector<int> &_devices, int blocks_per_submit, const std::vector<file_settings> &per_file)
 	: files(dumpfiles), settings(per_file), types(_types), thresh(_thresh), filter(_filter), dbg(_dbg), bps(blocks_per_submit),
-	  devices(_devices), n_telegrams(0), sink(NULL), psink(NULL), out_mode(0), bits_replay(false), slots(0)
+	  devices(_devices), n_telegrams(0), sink(NULL), psink(NULL), out_mode(0), bits_replay(false), slots(0), wide(false)
 {
 	if (devices.empty())
 		devices.push_back(0);
@@ -215,6 +215,8 @@ struct device_worker {
 	size_t nslots;      // streams of the context
 	const std::vector<size_t> *file_blocks;  // blocks of every file of the job
 	std::vector<batch_plan> plan;             // plan_batches
+	bool wide;          // -x: 15.36 MS/s dumps (TFREC_AMD_F_INPUT_10X in flags), the files' tunes are wide tunes
+	bool share;         // one stream per file for the whole job (no -n): a path given several times is read once, into one row
 	int rc;
 	std::atomic<bool> *abort;  // set by the engine when any worker failed: stop instead of running the whole job
 	std::mutex mu;
@@ -223,7 +225,7 @@ struct device_worker {
 	bool done;
 	std::thread th;
 
-	device_worker() : files(NULL), s0(0), s1(0), device(0), types(0), thresh(0), filter(0), bps(1), flags(0), nslots(0), file_blocks(NULL), rc(0), abort(NULL), done(false) {}
+	device_worker() : files(NULL), s0(0), s1(0), device(0), types(0), thresh(0), filter(0), bps(1), flags(0), nslots(0), file_blocks(NULL), wide(false), share(false), rc(0), abort(NULL), done(false) {}
 
 	void push(std::vector<tfrec_amd_event> &&ev)
 	{
@@ -284,17 +286,56 @@ struct device_worker {
 			fprintf(stderr, "tfrec_amd_create (device %d): %s (%s)\n", device, tfrec_amd_strerror(r), tfrec_amd_last_error());
 			return r;
 		}
-		const size_t row = (size_t)bps * TFREC_AMD_BLOCK_BYTES;
+		const size_t block_bytes = wide ? TFREC_AMD_BLOCK_BYTES_10X : TFREC_AMD_BLOCK_BYTES;
+		const size_t row = (size_t)bps * block_bytes;
 		const size_t n_batches = plan.size();
+		// Shared inputs (tfrec_amd_map_streams): without -n a stream carries one file for the whole job, and the streams whose
+		// files are one path share that path's input row -- the file is opened and read once, staged and copied once.  Decoders,
+		// stream indices and the order of the output stay per -L occurrence.  (A stream without a file reads row 0; its events
+		// are dropped.)
+		std::vector<int32_t> in_row(n, 0);
+		std::vector<bool> reads(n, true);  // the stream's file is read into its row (the first stream of the row)
+		size_t n_rows = n;
+		if (share && n_batches) {
+			std::vector<std::string> paths;
+			for (size_t s = 0; s < n; s++) {
+				const int f = plan[0].file[s];
+				if (f < 0)
+					continue;
+				const size_t r = std::find(paths.begin(), paths.end(), (*files)[f]) - paths.begin();
+				reads[s] = r == paths.size();
+				if (reads[s])
+					paths.push_back((*files)[f]);
+				in_row[s] = (int32_t)r;
+			}
+			if (paths.size() < n) {
+				std::vector<int32_t> all(n);
+				for (size_t s = 0; s < n; s++)
+					all[s] = (int32_t)s;
+				r = tfrec_amd_map_streams(ctx, all.data(), in_row.data(), (int)n);
+				if (r) {
+					fprintf(stderr, "tfrec_amd_map_streams (device %d): %s (%s)\n", device, tfrec_amd_strerror(r), tfrec_amd_last_error());
+					tfrec_amd_destroy(ctx);
+					return r;
+				}
+				n_rows = std::max<size_t>(1, paths.size());
+			} else {
+				for (size_t s = 0; s < n; s++)
+					in_row[s] = (int32_t)s;
+			}
+		} else {
+			for (size_t s = 0; s < n; s++)
+				in_row[s] = (int32_t)s;
+		}
 		const int depth = std::max(1, std::min(tfrec_amd_fifo_depth(), TFREC_AMD_FIFO_DEPTH));
 		constexpr int kBufs = TFREC_AMD_FIFO_DEPTH + 1;
 		uint8_t *host[kBufs];
 		bool pinned[kBufs];  // per buffer: each is released by the allocator it came from
 		for (int b = 0; b < kBufs; b++) {
-			host[b] = (uint8_t *)tfrec_amd_host_alloc(n * row);
+			host[b] = (uint8_t *)tfrec_amd_host_alloc(n_rows * row);
 			pinned[b] = host[b] != NULL;
 			if (!host[b])  // no page-locked memory: this buffer's copies become synchronous, results are the same
-				host[b] = (uint8_t *)malloc(n * row);
+				host[b] = (uint8_t *)malloc(n_rows * row);
 		}
 		// ---- reader thread: batch k goes to host[k % kBufs]; it may run at most kBufs batches ahead of the drain
 		std::mutex rmu;
@@ -309,8 +350,10 @@ struct device_worker {
 				const batch_plan &b = plan[k];
 				uint8_t *buf = host[k % kBufs];
 				for (size_t s = 0; s < n; s++) {
-					uint8_t *dst = buf + s * row;
-					const size_t want = (size_t)b.nb * TFREC_AMD_BLOCK_BYTES;
+					if (n_rows < n && (!reads[s] || b.file[s] < 0))
+						continue;  // (a shared row is filled by its first stream)
+					uint8_t *dst = buf + (size_t)in_row[s] * row;
+					const size_t want = (size_t)b.nb * block_bytes;
 					const int f = b.file[s];
 					size_t got = 0;
 					if (f >= 0) {
@@ -321,7 +364,7 @@ struct device_worker {
 						}
 						if (fp) {
 							got = fread(dst, 1, want, fp);
-							got -= got % TFREC_AMD_BLOCK_BYTES;
+							got -= got % block_bytes;
 							size_t &left = fleft[f - s0];
 							left -= std::min<size_t>(left, (size_t)b.nb);
 							if (left == 0) {
@@ -356,7 +399,8 @@ struct device_worker {
 					return rr;
 			}
 			if (!b.tune.empty()) {  // ... and tunes
-				const int rr = tfrec_amd_tune_streams(ctx, b.tune.data(), b.tune_hz.data(), (int)b.tune.size());
+				const int rr = wide ? tfrec_amd_tune_streams_wide(ctx, b.tune.data(), b.tune_hz.data(), (int)b.tune.size())
+						    : tfrec_amd_tune_streams(ctx, b.tune.data(), b.tune_hz.data(), (int)b.tune.size());
 				if (rr)
 					return rr;
 			}
@@ -438,7 +482,7 @@ int gpu_engine::run()
 			return TFREC_AMD_E_INVAL;
 		}
 		fseek(f, 0, SEEK_END);
-		const size_t blocks = (size_t)ftell(f) / TFREC_AMD_BLOCK_BYTES;  // trailing partial block dropped, engine.cpp:72-76
+		const size_t blocks = (size_t)ftell(f) / (wide ? TFREC_AMD_BLOCK_BYTES_10X : TFREC_AMD_BLOCK_BYTES);  // trailing partial block dropped, engine.cpp:72-76
 		fclose(f);
 		stream_samples[s] = (long long)blocks * TFREC_AMD_BLOCK_DEC;
 		file_blocks[s] = blocks;
@@ -459,7 +503,9 @@ int gpu_engine::run()
 		w.thresh = thresh;
 		w.filter = filter;
 		w.bps = bps;
-		w.flags = bits_replay ? (TFREC_AMD_F_BITS | TFREC_AMD_F_ALL_FLUSHES) : 0u;
+		w.flags = (bits_replay ? (TFREC_AMD_F_BITS | TFREC_AMD_F_ALL_FLUSHES) : 0u) | (wide ? TFREC_AMD_F_INPUT_10X : 0u);
+		w.wide = wide;
+		w.share = slots <= 0;
 		w.nslots = w.s1 - w.s0;
 		if (slots > 0)
 			w.nslots = std::min(w.nslots, (size_t)slots);

@@ -117,6 +117,11 @@ public:
 	// per file for the whole job.  A batch that carries a reset does not overlap the batch before it on the GPU (DESIGN.md
 	// 6b): a queue of mixed-length files runs at about half the throughput.
 	void set_slots(int n) { slots = n; }
+	// -x: the dump files are 15.36 MS/s u8 dumps (TFREC_AMD_F_INPUT_10X, blocks of TFREC_AMD_BLOCK_BYTES_10X), and a file's tune
+	// is a wide tune (tfrec_amd_tune_streams_wide, up to +-7679 kHz) ahead of the 10:1 stage.
+	// In both modes, without -n: a path given to several -L is opened and read once and occupies one input row of the batch; its
+	// streams are mapped to it (tfrec_amd_map_streams).  Decoders, stream indices and output order stay per -L occurrence.
+	void set_wide(bool on) { wide = on; }
 	// returns 0 on success, a TFREC_AMD_E_* code otherwise
 	int run();
 	// decoders of stream s in slot order (NULL for slots not registered)
@@ -137,6 +142,7 @@ private:
 	int out_mode;
 	bool bits_replay;
 	int slots;
+	bool wide;
 };
 
 #endif

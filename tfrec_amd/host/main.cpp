@@ -1,6 +1,6 @@
 // tfrec_amd/host/main.cpp -- tfrec_gpu: the reference's file-replay CLI on the GPU path.
 //
-//   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-q] [-D] [-B] [-d device[,device...]] [-b blocks]
+//   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x] [-q] [-D] [-B] [-d device[,device...]] [-b blocks]
 //             [-n streams] [-e handler | -E handler] [-m mode] [-p settings] -L dump.iq [[-p settings] -L more.iq ...]
 //   tfrec_gpu [-T hexmask] -X telegrams.txt
 //
@@ -22,6 +22,11 @@
 // recorded at, by default 868250 (the reference's default -f).  A dump cannot be retuned: the difference is applied as a
 // digital shift of the recorded IQ (tfrec_amd_tune_streams), within +-767 kHz.  -p f=<kHz> sets it per file; one
 // file given twice with two f= runs as two streams.
+// -x (not in the reference): the -L files are 15.36 MS/s u8 dumps (ten times the rate: TFREC_AMD_F_INPUT_10X), and the whole
+// difference f - c is a shift AHEAD of the 10:1 stage (tfrec_amd_tune_streams_wide), within +-7679 kHz: a receiver
+// can sit anywhere in the wide dump.  With or without -x, and without -n: a path given to several -L is opened and read once and
+// occupies one input row of the batch (tfrec_amd_map_streams); decoders, the -E stream index and the order of the output stay
+// per -L occurrence.  With -n a repeated file is read once per occurrence, as before.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -127,7 +132,7 @@ int main(int argc, char **argv)
 	std::vector<int> devices;
 	std::vector<std::string> dumps;
 	const char *hexfile = NULL, *exec = NULL;
-	bool batched = false, bits = false;
+	bool batched = false, bits = false, wide = false;
 	int mode = 0, slots = 0;
 	bool have_slots = false;
 	spec cur;  // the -p in force
@@ -135,7 +140,7 @@ int main(int argc, char **argv)
 	bool have_spec = false;
 	long freq = -1, center = 868250;  // -f (unset: the dumps' own frequency), -c: kHz
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:qDBd:b:n:L:X:e:E:m:p:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xqDBd:b:n:L:X:e:E:m:p:h")) != -1) {
 		switch (c) {
 		case 'T': types = (int)strtol(optarg, NULL, 16); break;
 		case 't': thresh = atoi(optarg); break;
@@ -147,6 +152,7 @@ int main(int argc, char **argv)
 				return 1;
 			}
 			break;
+		case 'x': wide = true; break;
 		case 'q': dbg = -1; break;
 		case 'D': dbg++; break;
 		case 'B': bits = true; break;
@@ -173,9 +179,11 @@ int main(int argc, char **argv)
 		case 'E': exec = optarg; batched = true; break;
 		case 'm': mode = atoi(optarg); break;
 		default:
-			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-p settings] -L dump [[-p settings] -L dump ...] | -X hexfile\n"
+			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-p settings] -L dump [[-p settings] -L dump ...] | -X hexfile\n"
 					"  -f kHz      receive frequency (default: the dumps' own, -c)\n"
 					"  -c kHz      frequency the dumps were recorded at (default 868250); -f within 767 kHz of it\n"
+					"  -x          the dumps are 15.36 MS/s u8 dumps (10x the rate); -f within 7679 kHz of -c, shifted ahead of the 10:1 stage\n"
+					"              (a file given to several -L is read once and shared by its streams; with -n it is read per -L, as before)\n"
 					"  -n streams  at most this many streams per device: the -L files queue for them in order\n"
 					"  -p T=<hex>,t=<n>,W=<0|1>,f=<kHz>  -T / -t / -W / -f of the -L files that follow, up to the next -p (fields left out: the global ones)\n");
 			return c == 'h' ? 0 : 1;
@@ -205,9 +213,11 @@ int main(int argc, char **argv)
 	bool tuned = false;
 	for (const spec &p : dump_spec) {
 		const long f = p.freq >= 0 ? p.freq : (freq >= 0 ? freq : center);
-		if (f - center <= -768 || f - center >= 768) {
+		const long lim = wide ? 7680 : 768;
+		if (f - center <= -lim || f - center >= lim) {
 			fprintf(stderr, "tfrec_gpu: receive frequency %ld kHz (-f / -p f=) is %ld kHz from the dumps' %ld kHz (-c): at most "
-					"767 kHz, half the 1.536 MS/s band, can be tuned\n", f, f - center, center);
+					"%ld kHz, half the %s band, can be tuned%s\n", f, f - center, center, lim - 1,
+				wide ? "15.36 MS/s" : "1.536 MS/s", wide ? "" : " (-x: 15.36 MS/s dumps, 7679 kHz)");
 			return 1;
 		}
 		tunes.push_back((int)((f - center) * 1000));
@@ -225,6 +235,7 @@ int main(int argc, char **argv)
 		e.set_handler(exec, batched, mode);
 	e.set_bits_replay(bits);
 	e.set_slots(slots);
+	e.set_wide(wide);
 	int rc = e.run();
 	fflush(stdout);
 	return rc ? 2 : 0;
