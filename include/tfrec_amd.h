@@ -261,6 +261,44 @@ int tfrec_amd_tune_streams_wide(tfrec_amd_ctx *ctx, const int32_t *streams, cons
 /* The wide tune the next submit will use for one stream (0: none). */
 int tfrec_amd_get_stream_tune_wide(tfrec_amd_ctx *ctx, int stream, int32_t *tune_hz);
 
+/* Other input rates: a context for u8 IQ at fs_in = 1536000 * rate_p / rate_q samples per second -- 2.048 MS/s is
+ * 4/3, 2.4 MS/s 25/16, 1.92 MS/s 5/4 -- which a resampling stage on the GPU brings to the 1.536 MS/s int16 (I, Q) stream that
+ * enters downconvert::process_iq; the rest of the path is unchanged.  No reference counterpart: like the 10:1 stage and the
+ * tuners the stage is defined here, in the reference's FIR style, and pinned by a CPU restatement (tfrec_amd/resample.py).
+ *   Rates:   gcd(P, Q) = 1, 1 <= Q <= 64, 1 < P/Q < 10.  r = P/Q is the number of input samples per output sample.
+ *   Filter:  T = 2 * ceil(3 r) taps per phase (even, <= 60; 8 at 2.048 MS/s, 10 at 2.4 MS/s).  For output sample m, counted since
+ *            the stream's start or last restart:  a = m P,  i0 = floor(a / Q),  phi = a mod Q   (exact 64-bit integers)
+ *   Output:  y0[m] = int16( sum_{n<T} ( x[i0 - (T-1) + n] * h[phi][n] ) >> 16 )   per rail, int32 arithmetic, arithmetic shifts,
+ *            x = (u8 - 128) << 6, x[<0] = 0 (the history before a start or restart is silence, u8 128).  Causal: the newest
+ *            sample used is i0, so a submit never reads past its own input.
+ *   Taps:    d = n - T/2 + 1 - phi/Q  (in (-T/2, T/2]),  g = sinc(d / r) (0.54 + 0.46 cos(2 pi d / T)),  sinc(u) = sin(pi u)/(pi u),
+ *            sinc(0) = 1;  v = g * 65536 / sum_n g;  h[phi][n] = round(v); the residual 65536 - sum_n h is added to the tap with
+ *            the largest v (the lowest n among equals): every phase sums to exactly 65536, unity DC gain as for the 10:1 taps.
+ *            Computed in double.  (A tap reaches about 65536 / r: the table is int32, not int16.)
+ *   Refused: a rate where any v lies within 1e-9 of a rounding tie (the table must not depend on the host's libm), or where
+ *            max_phi sum_n |h[phi][n]| * 8192 >> 16 >= 32768 (so the int16 store never wraps for u8 input): TFREC_AMD_E_INVAL.
+ *   Submits: n_blocks blocks (TFREC_AMD_BLOCK_DEC decimated samples each, as always) consume exactly
+ *            n_in = n_blocks * 32768 * P / Q complex input samples per stream, n_in * 2 bytes per input row; n_blocks must make
+ *            that a whole number -- any value when Q is a power of two, otherwise a multiple of Q's odd part --, or the submit
+ *            returns TFREC_AMD_E_INVAL and nothing is queued.  Every submit therefore begins at phase 0 on its own first input
+ *            sample, and results do not depend on how a stream is cut into submits.
+ * cfg->flags must not contain TFREC_AMD_F_INPUT_10X (TFREC_AMD_E_INVAL).  On such a context tfrec_amd_submit_device / _host take
+ * n_in * 2 bytes per row (submit_host stages exactly that, rows 0 .. R-1), tfrec_amd_read_stage0 returns y0, tfrec_amd_get_memory
+ * counts the stage's buffers, tfrec_amd_tune_streams_wide returns TFREC_AMD_E_INVAL (a wide tune ahead of this stage is not
+ * built), and everything else keeps its meaning, because nothing behind stage 0 changes: reset, configure, tune (it acts on y0)
+ * and map (the stage looks the row up), both pipeline layouts, _SERIAL_CHAINS, _BITS, _ALL_FLUSHES, _TIMING.  A context made by
+ * tfrec_amd_create launches the kernels it launched before. */
+int tfrec_amd_create_rate(const tfrec_amd_config *cfg, int32_t rate_p, int32_t rate_q, tfrec_amd_ctx **out);
+/* The context's input rate as P/Q of 1.536 MS/s: 1/1 for tfrec_amd_create, 10/1 with TFREC_AMD_F_INPUT_10X. */
+int tfrec_amd_get_input_rate(tfrec_amd_ctx *ctx, int32_t *p, int32_t *q);
+/* Bytes one input row of a submit of n_blocks blocks holds (every kind of context); TFREC_AMD_E_INVAL when n_blocks < 1 or
+ * breaks the divisibility rule above. */
+int tfrec_amd_input_bytes(tfrec_amd_ctx *ctx, int n_blocks, size_t *bytes_per_stream);
+/* The tap table of a rate: taps[phi * T + n], Q * T values (cap: the room in `taps`, in values), T to *n_taps_per_phase.  taps may
+ * be NULL with cap 0 (only T, or only the verdict, is wanted).  Needs no context and no GPU.  TFREC_AMD_E_INVAL: a rate outside
+ * the rules above or refused by them, or cap too small. */
+int tfrec_amd_resample_taps(int32_t rate_p, int32_t rate_q, int32_t *taps, int cap, int *n_taps_per_phase);
+
 /* Wait for submitted work. */
 int tfrec_amd_sync(tfrec_amd_ctx *ctx);
 
@@ -285,7 +323,8 @@ int tfrec_amd_pending_events(tfrec_amd_ctx *ctx, int *n);
  * reference's host expressions (tfa1.cpp:180, tfa2.cpp:434, whb.cpp:696) including (int)(10*log10(0)). */
 int tfrec_amd_rssi_db(int slot, int64_t rssi_raw);
 
-/* Parity/debug (TFREC_AMD_F_INPUT_10X): the 1.536 MS/s int16 IQ the 10:1 stage produced for the last submit. */
+/* Parity/debug (TFREC_AMD_F_INPUT_10X or tfrec_amd_create_rate): the 1.536 MS/s int16 IQ the 10:1 or the resampling stage produced
+ * for the last submit. */
 int tfrec_amd_read_stage0(tfrec_amd_ctx *ctx, int stream, int16_t *out, size_t n_pairs);
 /* Parity/debug: copy the decimated int16 IQ of the last submit for one stream (n_pairs*2 int16). */
 int tfrec_amd_read_decimated(tfrec_amd_ctx *ctx, int stream, int16_t *out, size_t n_pairs);

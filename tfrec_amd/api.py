@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from fractions import Fraction
 
 import numpy as np
 
@@ -98,6 +99,7 @@ EXPORTS = (
     "tfrec_amd_fifo_depth", "tfrec_amd_get_memory", "tfrec_amd_iir_probe", "tfrec_amd_reset_streams",
     "tfrec_amd_configure_streams", "tfrec_amd_get_stream_config", "tfrec_amd_tune_streams", "tfrec_amd_get_stream_tune",
     "tfrec_amd_map_streams", "tfrec_amd_get_stream_input", "tfrec_amd_tune_streams_wide", "tfrec_amd_get_stream_tune_wide",
+    "tfrec_amd_create_rate", "tfrec_amd_get_input_rate", "tfrec_amd_input_bytes", "tfrec_amd_resample_taps",
 )
 
 _libs = {}
@@ -164,6 +166,10 @@ def load_library(build: bool = True, experiments: bool = False):
     L.tfrec_amd_get_stream_input.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
     L.tfrec_amd_tune_streams_wide.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tfrec_amd_get_stream_tune_wide.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
+    L.tfrec_amd_create_rate.argtypes = [C.POINTER(Config), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.tfrec_amd_get_input_rate.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.tfrec_amd_input_bytes.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]
+    L.tfrec_amd_resample_taps.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.tfrec_amd_fifo_depth.restype = C.c_int
     if L.tfrec_amd_fifo_depth() != FIFO_DEPTH:
         raise RuntimeError("libtfrec_amd.so was built with FIFO depth %d, this binding expects %d" % (
@@ -177,6 +183,19 @@ def _check(L, rc: int, ok=(E_OK,)):
         detail = L.tfrec_amd_last_error().decode() if rc == E_HIP or rc == E_INVAL or rc == E_NOMEM else ""
         raise TfrecAmdError(rc, L.tfrec_amd_strerror(rc).decode() + (" (" + detail + ")" if detail else ""))
     return rc
+
+
+def resample_taps(p: int, q: int) -> np.ndarray:
+    """The library's tap table of the input rate 1536000 P / Q (tfrec_amd_resample_taps) as int32 [Q, T]; TfrecAmdError(E_INVAL) for
+    a rate outside the rules or refused by them.  Needs no GPU.  (tfrec_amd/resample.py: taps is the independent restatement.)"""
+    L = load_library()
+    if not all(-2 ** 31 <= int(v) < 2 ** 31 for v in (p, q)):
+        raise TfrecAmdError(E_INVAL, "rate outside int32")
+    t = C.c_int(0)
+    _check(L, L.tfrec_amd_resample_taps(int(p), int(q), None, 0, C.byref(t)))
+    out = np.empty((int(q), t.value), dtype=np.int32)
+    _check(L, L.tfrec_amd_resample_taps(int(p), int(q), out.ctypes.data, out.size, C.byref(t)))
+    return out
 
 
 def rssi_db(slot: int, rssi_raw: int) -> int:
@@ -193,7 +212,7 @@ class Receiver:
     def __init__(self, n_streams: int, types_mask: int = 0x2F, thresh: int = 500, filter_type: int = 0,
                  device: int = 0, max_blocks: int = 48, max_events: int | None = None, all_flushes: bool = False,
                  timing: bool = False, serial_chains: bool = False, input_10x: bool = False, bits: bool = False,
-                 experiments: bool = False):
+                 experiments: bool = False, input_rate=None):
         # experiments=True: the build that reads the TFREC_AMD_* knobs / test hooks from the environment (csrc/knobs.h);
         # the default is the product library, which has none
         self.L = load_library(experiments=experiments)
@@ -201,10 +220,22 @@ class Receiver:
             max_events = max(4096, n_streams * max_blocks * 4 * (8 if all_flushes else 2))
         flags = ((F_ALL_FLUSHES if all_flushes else 0) | (F_TIMING if timing else 0)
                  | (F_SERIAL_CHAINS if serial_chains else 0) | (F_INPUT_10X if input_10x else 0) | (F_BITS if bits else 0))
-        self.block_bytes = BLOCK_BYTES * (10 if input_10x else 1)
+        # input_rate=(P, Q): u8 IQ at 1536000 P / Q samples per second, resampled on the GPU (tfrec_amd_create_rate, resample.py).
+        # block_bytes: the bytes of one block of one input row -- a fraction when Q does not divide 65536 P; input_bytes(n_blocks)
+        # is what a submit takes
+        self.input_rate = (10, 1) if input_10x else (1, 1)
         self.cfg = Config(n_streams, types_mask, thresh, filter_type, device, max_blocks, max_events, flags)
         self.h = C.c_void_p()
-        _check(self.L, self.L.tfrec_amd_create(C.byref(self.cfg), C.byref(self.h)))
+        if input_rate is None:
+            _check(self.L, self.L.tfrec_amd_create(C.byref(self.cfg), C.byref(self.h)))
+        else:
+            p, q = (int(v) for v in input_rate)
+            if not all(-2 ** 31 <= v < 2 ** 31 for v in (p, q)):  # (refused before int32 could wrap a value into range)
+                raise TfrecAmdError(E_INVAL, "input_rate outside int32")
+            _check(self.L, self.L.tfrec_amd_create_rate(C.byref(self.cfg), p, q, C.byref(self.h)))
+            self.input_rate = (p, q)
+        bb = Fraction(BLOCK_BYTES * self.input_rate[0], self.input_rate[1])
+        self.block_bytes = int(bb) if bb.denominator == 1 else bb
         self.n_streams = n_streams
         self.max_events = max_events
         self._keep = ()
@@ -245,6 +276,13 @@ class Receiver:
         _check(self.L, self.L.tfrec_amd_submit_device(self.h, C.c_void_p(iq.data_ptr()), iq.stride(0), nb,
                                                       C.c_void_p(st.cuda_stream)))
         return nb
+
+    def input_bytes(self, n_blocks: int) -> int:
+        """Bytes one input row of a submit of n_blocks blocks holds (tfrec_amd_input_bytes); E_INVAL for a block count the
+        context's input rate does not permit."""
+        v = C.c_size_t(0)
+        _check(self.L, self.L.tfrec_amd_input_bytes(self.h, int(n_blocks), C.byref(v)))
+        return int(v.value)
 
     def sync(self):
         _check(self.L, self.L.tfrec_amd_sync(self.h))
@@ -371,7 +409,7 @@ class Receiver:
         return out[: n.value]
 
     def stage0(self, stream: int, n_pairs: int) -> np.ndarray:
-        """input_10x: the 1.536 MS/s int16 IQ the 10:1 stage produced for the last submit."""
+        """input_10x or input_rate: the 1.536 MS/s int16 IQ the 10:1 or the resampling stage produced for the last submit."""
         out = np.empty(2 * n_pairs, dtype=np.int16)
         _check(self.L, self.L.tfrec_amd_read_stage0(self.h, stream, out.ctypes.data, n_pairs))
         return out

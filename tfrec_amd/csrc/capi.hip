@@ -14,6 +14,9 @@
 namespace tfrec {
 hipError_t launch_decim10(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks,
 			  const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride, const uint4 *chan);
+hipError_t launch_resample(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, int p, int q, int t,
+			   const float *taps, const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride,
+			   const uint4 *chan);
 hipError_t launch_frontend(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks,
 			   const uint8_t *tail_in, uint8_t *tail_out, uint32_t *dec, size_t dec_stride,
 			   unsigned long long *mask, size_t mask_stride, uint32_t *prevdec, int thresh, const FrontTapsCfg &taps,
@@ -39,6 +42,8 @@ using namespace tfrec;
 
 constexpr int kTuneLimit = 768000;  // |tune_hz| < half the 1.536 MS/s sample rate
 constexpr int kTuneWideLimit = 7680000;  // tfrec_amd_tune_streams_wide: half the 15.36 MS/s input rate
+constexpr int kRateQMax = 64;  // tfrec_amd_create_rate: the largest Q
+constexpr int kRateTail = 128;  // ... and its raw history per stream in bytes (resample_kernel: kRsTail)
 
 // Buffer / table sets = submits that may be in flight (the FIFO depth): front end of submit k+2, biquad stage of
 // k+1 and slicer stage of k run beside each other in the deep layout
@@ -152,6 +157,13 @@ struct tfrec_amd_ctx {
 	size_t in16_stride = 0;  // uint32 units
 	uint8_t *d_tail10[kSets] = {};
 	bool in10x = false;
+	// tfrec_amd_create_rate: the input rate is 1536000 rate_p / rate_q; the resampling stage writes d_in16 as the
+	// 10:1 stage does, from a tap table [rate_q][rate_t] (h / 1024 as floats) and its raw history (d_tailR: two buffers that flip
+	// with tail_sel).  in16: a pre-stage writes stage 0 and the front end reads int16 (in10x or resamp).
+	int32_t rate_p = 1, rate_q = 1, rate_t = 0;
+	bool resamp = false, in16 = false;
+	float *d_rtaps = nullptr;
+	uint8_t *d_tailR[2] = {};
 	// ---- window-parallel pipeline (make_window_state).  One set per submit in flight, like the front-end outputs: the window
 	// scan and the biquads of submit k+1 fill theirs while the slicers of submit k still read the other
 	int16_t *d_ld16[kSets] = {};   // [chains][m_max] tfa2-family biquad outputs
@@ -238,6 +250,7 @@ struct StreamReset {
 	uint8_t *tail;      // front-end FIR history the NEXT front end reads: tail_bytes per stream, filled with tail_fill
 	int32_t tail_bytes, tail_fill;
 	uint8_t *tail10;    // TFREC_AMD_F_INPUT_10X: the 10:1 stage's raw history (112 bytes per stream of 0x80), or nullptr
+	uint8_t *tailR;     // tfrec_amd_create_rate: the resampling stage's raw history (kRateTail bytes per stream of 0x80), or nullptr
 	FskState *fsk;      // auto threshold
 	const StreamCfg *cfgs;  // [n_list] the listed streams' settings from this submit on ...
 	StreamCfg *scfg;        // ... written over their entries here
@@ -263,6 +276,9 @@ __global__ __launch_bounds__(64) void stream_reset_kernel(StreamReset R)
 	if (R.tail10)
 		for (int i = ln; i < 112; i += 64)
 			R.tail10[(size_t)s * 112 + i] = 0x80;
+	if (R.tailR)
+		for (int i = ln; i < kRateTail; i += 64)
+			R.tailR[(size_t)s * kRateTail + i] = 0x80;
 	constexpr int kChunks = (int)(sizeof(ChainState) / 16);
 	const uint4 *init = reinterpret_cast<const uint4 *>(R.chain_init);
 	for (int a = 0; a < R.n_active; a++)
@@ -464,6 +480,55 @@ static const int16_t kNarrowTaps[20] = { -1087, -1082, -1065, -451, 912, 2997, 5
 static const int16_t kWideTaps[20] = { 546, 451, -317, -1844, -3198, -2817, 494, 6469, 13074, 17421,
 				       17421, 13074, 6469, 494, -2817, -3198, -1844, -317, 451, 546 };
 
+// The resampling stage's tap table (tfrec_amd/resample.py restates it): h[phi][n], phi < q, n < t = 2 ceil(3 p / q).
+// With dn = (n - t/2 + 1) q - phi the tap offset is d = dn / q and d / r = dn / p:
+//   g = sinc(dn / p) (0.54 + 0.46 cos(2 pi dn / (q t))),  v = g 65536 / sum g,  h = round(v), and the residual 65536 - sum h goes to
+//   the tap with the largest v (the lowest n among equals).
+// false: the rate is outside 1 < p/q < 10, q <= 64, gcd = 1, or refused -- a v within 1e-9 of a rounding tie (the table must not
+// depend on the host's libm), or max_phi sum |h| * 8192 >> 16 >= 32768 (the int16 store could wrap).
+static bool resample_table(int32_t p, int32_t q, std::vector<int32_t> &h, int &t)
+{
+	if (p <= 0 || q <= 0 || q > kRateQMax || p <= q || (long long)p >= 10LL * q)
+		return false;
+	for (int a = p, b = q; b;) {  // gcd
+		const int r = a % b;
+		a = b;
+		b = r;
+		if (!b && a != 1)
+			return false;
+	}
+	t = 2 * ((3 * p + q - 1) / q);
+	h.assign((size_t)q * t, 0);
+	std::vector<double> v((size_t)t);
+	for (int phi = 0; phi < q; phi++) {
+		double total = 0.0;
+		for (int n = 0; n < t; n++) {
+			const double dn = (double)((n - t / 2 + 1) * q - phi);
+			const double u = M_PI * dn / p;
+			v[n] = (dn == 0.0 ? 1.0 : sin(u) / u) * (0.54 + 0.46 * cos(2.0 * M_PI * dn / ((double)q * t)));
+			total += v[n];
+		}
+		long long sum = 0, sum_abs = 0;
+		int best = 0;
+		for (int n = 0; n < t; n++) {
+			v[n] = v[n] * 65536.0 / total;
+			if (fabs(fabs(v[n] - floor(v[n])) - 0.5) < 1e-9)
+				return false;
+			const int32_t r = (int32_t)floor(v[n] + 0.5);
+			h[(size_t)phi * t + n] = r;
+			sum += r;
+			if (v[n] > v[best])
+				best = n;
+		}
+		h[(size_t)phi * t + best] += (int32_t)(65536 - sum);
+		for (int n = 0; n < t; n++)
+			sum_abs += llabs((long long)h[(size_t)phi * t + n]);
+		if (((sum_abs * 8192) >> 16) >= 32768)
+			return false;
+	}
+	return true;
+}
+
 static StreamCfg device_cfg(const tfrec_amd_ctx *c, const tfrec_amd_stream_config &sc)
 {
 	StreamCfg d;
@@ -602,12 +667,13 @@ static int make_front_buffers(tfrec_amd_ctx *c)
 		TRY(own_device(c, c->d_prevdec[k], n * sizeof(uint32_t)));
 	}
 	c->in10x = (cfg.flags & TFREC_AMD_F_INPUT_10X) != 0;
-	const size_t tail_bytes = c->in10x ? 2 * (size_t)kTailBytes : (size_t)kTailBytes;  // int16 history is twice as wide
+	c->in16 = c->in10x || c->resamp;
+	const size_t tail_bytes = c->in16 ? 2 * (size_t)kTailBytes : (size_t)kTailBytes;  // int16 history is twice as wide
 	// zero FIR history == u8 value 128 (decimate::decimate zeroes hist0, dsp_stuff.cpp:145-152); int16 history of the 10x
-	// path: zero, raw u8 history of its 10:1 stage: 128
+	// path: zero, raw u8 history of its 10:1 stage (or of the resampling stage): 128
 	for (int k = 0; k < 2; k++) {
 		TRY(own_device(c, c->d_tail[k], n * tail_bytes));
-		HIPCHK(hipMemset(c->d_tail[k], c->in10x ? 0 : 0x80, n * tail_bytes));
+		HIPCHK(hipMemset(c->d_tail[k], c->in16 ? 0 : 0x80, n * tail_bytes));
 	}
 	if (c->in10x) {
 		c->in16_stride = 4 * m_max;  // complex samples at 1.536 MS/s per stream and submit
@@ -617,6 +683,25 @@ static int make_front_buffers(tfrec_amd_ctx *c)
 		}
 		for (int k = 0; k < 2; k++)
 			HIPCHK(hipMemset(c->d_tail10[k], 0x80, n * 112));
+	}
+	if (c->resamp) {
+		c->in16_stride = 4 * m_max;
+		for (int k = 0; k < kSets; k++)
+			TRY(own_device(c, c->d_in16[k], n * c->in16_stride * sizeof(uint32_t)));
+		for (int k = 0; k < 2; k++) {
+			TRY(own_device(c, c->d_tailR[k], n * kRateTail));
+			HIPCHK(hipMemset(c->d_tailR[k], 0x80, n * kRateTail));
+		}
+		std::vector<int32_t> h;
+		int t = 0;
+		if (!resample_table(c->rate_p, c->rate_q, h, t))  // (tfrec_amd_create_rate checked it already)
+			return TFREC_AMD_E_INVAL;
+		c->rate_t = t;
+		std::vector<float> hf(h.size());
+		for (size_t i = 0; i < h.size(); i++)
+			hf[i] = (float)h[i] * (1.0f / 1024.0f);  // exact: |h| < 2^17
+		TRY(own_device(c, c->d_rtaps, hf.size() * sizeof(float)));
+		HIPCHK(hipMemcpy(c->d_rtaps, hf.data(), hf.size() * sizeof(float), hipMemcpyHostToDevice));
 	}
 	return TFREC_AMD_OK;
 }
@@ -1011,6 +1096,61 @@ int tfrec_amd_create(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
 	return TFREC_AMD_OK;
 }
 
+int tfrec_amd_resample_taps(int32_t rate_p, int32_t rate_q, int32_t *taps, int cap, int *n_taps_per_phase)
+{
+	std::vector<int32_t> h;
+	int t = 0;
+	if (cap < 0 || (cap > 0 && !taps) || !resample_table(rate_p, rate_q, h, t)) {
+		snprintf(g_err, sizeof(g_err), "input rate %d/%d: unsupported or refused", (int)rate_p, (int)rate_q);
+		return TFREC_AMD_E_INVAL;
+	}
+	if (n_taps_per_phase)
+		*n_taps_per_phase = t;
+	if (taps) {
+		if ((size_t)cap < h.size())
+			return TFREC_AMD_E_INVAL;
+		memcpy(taps, h.data(), h.size() * sizeof(int32_t));
+	}
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_create_rate(const tfrec_amd_config *cfg, int32_t rate_p, int32_t rate_q, tfrec_amd_ctx **out)
+{
+	if (!cfg || !out)
+		return TFREC_AMD_E_INVAL;
+	*out = nullptr;
+	if (cfg->flags & TFREC_AMD_F_INPUT_10X) {
+		snprintf(g_err, sizeof(g_err), "an input rate and the 15.36 MS/s input flag exclude each other");
+		return TFREC_AMD_E_INVAL;
+	}
+	TRY(tfrec_amd_resample_taps(rate_p, rate_q, nullptr, 0, nullptr));
+	TRY(validate(cfg));
+	HIPCHK(hipSetDevice(cfg->device));
+	tfrec_amd_ctx *c = new (std::nothrow) tfrec_amd_ctx();
+	if (!c)
+		return TFREC_AMD_E_NOMEM;
+	c->cfg = *cfg;
+	c->rate_p = rate_p;
+	c->rate_q = rate_q;
+	c->resamp = true;
+	const int rc = init_context(c);
+	if (rc != TFREC_AMD_OK) {
+		tfrec_amd_destroy(c);
+		return rc;
+	}
+	*out = c;
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_get_input_rate(tfrec_amd_ctx *c, int32_t *p, int32_t *q)
+{
+	if (!c || !p || !q)
+		return TFREC_AMD_E_INVAL;
+	*p = c->in10x ? 10 : c->rate_p;
+	*q = c->in10x ? 1 : c->rate_q;
+	return TFREC_AMD_OK;
+}
+
 // The resets marked since the last submit, at the head of this submit's front end (fs).  Carried state is written by several
 // stages on several streams (a ChainState by the biquad stage, the slicers, the decoders' commit and the WHB check's redo), and
 // in the deep layout those of the submit before may still run while this one's front end does: the front-end stream first
@@ -1035,9 +1175,10 @@ static int launch_resets(tfrec_amd_ctx *c, int set)
 	R.n_list = nl;
 	R.n_streams = c->cfg.n_streams;
 	R.tail = c->d_tail[c->tail_sel];  // the buffer this submit's front end reads (the history flips per submit)
-	R.tail_bytes = c->in10x ? 2 * kTailBytes : kTailBytes;
-	R.tail_fill = c->in10x ? 0 : 0x80;  // as make_front_buffers: int16 zero, or u8 128
+	R.tail_bytes = c->in16 ? 2 * kTailBytes : kTailBytes;
+	R.tail_fill = c->in16 ? 0 : 0x80;  // as make_front_buffers: int16 zero, or u8 128
 	R.tail10 = c->in10x ? c->d_tail10[c->tail_sel] : nullptr;
+	R.tailR = c->resamp ? c->d_tailR[c->tail_sel] : nullptr;
 	R.fsk = c->d_fsk;
 	R.cfgs = c->d_rcfg[set];
 	R.scfg = c->d_scfg;
@@ -1186,14 +1327,31 @@ static int rows_in_use(const tfrec_amd_ctx *c)
 	return 1 + *std::max_element(c->row.begin(), c->row.end());
 }
 
+// Bytes of one input row of a submit of n_blocks blocks: n_blocks * 32768 * P / Q complex u8 samples, which must be a whole
+// number (any n_blocks when Q is a power of two, otherwise a multiple of Q's odd part).
+static int input_bytes(const tfrec_amd_ctx *c, int n_blocks, size_t *bytes)
+{
+	if (n_blocks < 1)
+		return TFREC_AMD_E_INVAL;
+	const long long p = c->in10x ? 10 : c->rate_p, q = c->in10x ? 1 : c->rate_q;
+	const long long num = (long long)n_blocks * (TFREC_AMD_BLOCK_BYTES / 2) * p;
+	if (num % q != 0) {
+		snprintf(g_err, sizeof(g_err), "%d blocks at the input rate %lld/%lld are not a whole number of input samples", n_blocks, p, q);
+		return TFREC_AMD_E_INVAL;
+	}
+	*bytes = (size_t)(num / q) * 2;
+	return TFREC_AMD_OK;
+}
+
 // input_on_fs: the input was produced on the front-end stream itself (staged host input): no event needed
 static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int n_blocks, void *hip_stream, bool input_on_fs)
 {
 	if (!c || !d_iq || n_blocks < 1 || n_blocks > c->cfg.max_blocks)
 		return TFREC_AMD_E_INVAL;
-	const size_t block_bytes = c->in10x ? TFREC_AMD_BLOCK_BYTES_10X : TFREC_AMD_BLOCK_BYTES;
+	size_t row_bytes = 0;
+	TRY(input_bytes(c, n_blocks, &row_bytes));
 	if ((stride % 16) != 0 || ((uintptr_t)d_iq % 16) != 0 ||
-	    (rows_in_use(c) > 1 && stride < (size_t)n_blocks * block_bytes)) {  // (one row in use: the stride is never applied)
+	    (rows_in_use(c) > 1 && stride < row_bytes)) {  // (one row in use: the stride is never applied)
 		snprintf(g_err, sizeof(g_err), "IQ base and stream stride must be 16-byte aligned and >= one stream");
 		return TFREC_AMD_E_INVAL;
 	}
@@ -1222,7 +1380,8 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	const uint8_t *fin = (const uint8_t *)d_iq;
 	size_t fstride = stride;
 	// a mapped or wide-tuned context: the 10:1 stage's tuned kernel, or -- default input -- the front end that looks up the rows
-	const bool chan10 = c->in10x && (c->mapped || c->n_wide), chan_front = !c->in10x && c->mapped;
+	// (a rate context: the resampling stage looks the row up, as the 10:1 stage does)
+	const bool chan10 = c->in16 && (c->mapped || c->n_wide), chan_front = !c->in16 && c->mapped;
 	if (chan10 || chan_front)
 		TRY(stage_chan(c, set));
 	if (c->in10x) {  // 15.36 MS/s u8 -> 1.536 MS/s int16 pairs, then the standard cascade on int16 input
@@ -1231,11 +1390,18 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		fin = (const uint8_t *)c->d_in16[set];
 		fstride = c->in16_stride * sizeof(uint32_t);
 	}
+	if (c->resamp) {  // 1536000 P / Q S/s u8 -> 1.536 MS/s int16 pairs, then the same cascade on int16 input
+		HIPCHK(launch_resample(fs, (const uint8_t *)d_iq, stride, c->cfg.n_streams, n_blocks, c->rate_p, c->rate_q, c->rate_t,
+				       c->d_rtaps, c->d_tailR[c->tail_sel], c->d_tailR[c->tail_sel ^ 1], c->d_in16[set], c->in16_stride,
+				       chan10 ? c->d_chan[set] : nullptr));
+		fin = (const uint8_t *)c->d_in16[set];
+		fstride = c->in16_stride * sizeof(uint32_t);
+	}
 	if (c->n_tuned || chan_front)
 		TRY(stage_tune(c, set));
 	HIPCHK(launch_frontend(fs, fin, fstride, c->cfg.n_streams, n_blocks, c->d_tail[c->tail_sel],
 			       c->d_tail[c->tail_sel ^ 1], c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride,
-			       c->d_prevdec[set], c->cfg.thresh ? c->cfg.thresh : 500, c->taps, c->in10x,
+			       c->d_prevdec[set], c->cfg.thresh ? c->cfg.thresh : 500, c->taps, c->in16,
 			       (c->n_tuned || chan_front) ? c->d_tune[set] : nullptr, chan_front ? c->d_chan[set] : nullptr));
 	if (c->n_auto)  // auto threshold: per-block thresholds rewrite the trigger mask (fm_demod.cpp:58-73)
 		HIPCHK(launch_threshold(fs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams,
@@ -1325,7 +1491,8 @@ static int submit_host_impl(tfrec_amd_ctx *c, const uint8_t *h_iq, size_t stride
 {
 	if (!c || !h_iq || n_blocks < 1 || n_blocks > c->cfg.max_blocks)
 		return TFREC_AMD_E_INVAL;
-	const size_t row = (size_t)n_blocks * (c->in10x ? TFREC_AMD_BLOCK_BYTES_10X : TFREC_AMD_BLOCK_BYTES);
+	size_t row = 0;
+	TRY(input_bytes(c, n_blocks, &row));
 	if (rows_in_use(c) > 1 && stride < row)
 		return TFREC_AMD_E_INVAL;
 	TRY(check_fifo(c));
@@ -1345,6 +1512,13 @@ static int submit_host_impl(tfrec_amd_ctx *c, const uint8_t *h_iq, size_t stride
 	// by the runtime before the call returns
 	HIPCHK(hipMemcpy2DAsync(c->d_stage[set], row, h_iq, stride, row, rows, hipMemcpyHostToDevice, c->pipe[set].fs));
 	return submit_common(c, c->d_stage[set], row, n_blocks, nullptr, true);
+}
+
+int tfrec_amd_input_bytes(tfrec_amd_ctx *c, int n_blocks, size_t *bytes_per_stream)
+{
+	if (!c || !bytes_per_stream)
+		return TFREC_AMD_E_INVAL;
+	return input_bytes(c, n_blocks, bytes_per_stream);
 }
 
 void *tfrec_amd_host_alloc(size_t bytes)
@@ -1624,7 +1798,7 @@ int tfrec_amd_map_streams(tfrec_amd_ctx *c, const int32_t *streams, const int32_
 		mark_restart(c, streams[i]);
 	}
 	c->mapped = true;
-	if (!c->in10x)  // (the mapped front end is a per-stream variant; with the 10x input the 10:1 stage maps)
+	if (!c->in16)  // (the mapped front end is a per-stream variant; with the 10x input or a rate the pre-stage maps)
 		use_per_stream(c);
 	return TFREC_AMD_OK;
 }
@@ -1652,7 +1826,8 @@ int tfrec_amd_tune_streams_wide(tfrec_amd_ctx *c, const int32_t *streams, const 
 	if (!c || n < 0 || (n > 0 && (!streams || !tune_hz)))
 		return TFREC_AMD_E_INVAL;
 	if (!c->in10x) {
-		snprintf(g_err, sizeof(g_err), "the wide tune acts ahead of the 10:1 stage: the context needs the 15.36 MS/s input flag");
+		snprintf(g_err, sizeof(g_err), "the wide tune acts ahead of the 10:1 stage: the context needs the 15.36 MS/s input flag%s",
+			 c->resamp ? " (a wide tune ahead of the resampling stage is not built)" : "");
 		return TFREC_AMD_E_INVAL;
 	}
 	for (int i = 0; i < n; i++) {
@@ -1687,7 +1862,7 @@ int tfrec_amd_get_stream_tune_wide(tfrec_amd_ctx *c, int stream, int32_t *tune_h
 
 int tfrec_amd_read_stage0(tfrec_amd_ctx *c, int stream, int16_t *out, size_t n_pairs)
 {
-	if (!c || !out || !c->in10x || stream < 0 || stream >= c->cfg.n_streams ||
+	if (!c || !out || !c->in16 || stream < 0 || stream >= c->cfg.n_streams ||
 	    n_pairs > (size_t)c->last_blocks * 4 * kBlockDec)
 		return TFREC_AMD_E_INVAL;
 	int rc = tfrec_amd_sync(c);

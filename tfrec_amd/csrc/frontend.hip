@@ -855,4 +855,6 @@ hipError_t launch_fmdev(hipStream_t st, const uint32_t *dec, size_t dec_stride, 
 	return hipGetLastError();
 }
 
+#include "resample.h"  // resample_kernel, launch_resample
+
 }  // namespace tfrec

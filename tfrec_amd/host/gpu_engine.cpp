@@ -28,7 +28,7 @@ void tfrec_handler_args(const sensordata_t &d, sensor_e dec_type, char *out, siz
 gpu_engine::gpu_engine(const std::vector<std::string> &dumpfiles, int _types, int _thresh, int _filter, int _dbg,
 		       const std::vector<int> &_devices, int blocks_per_submit, const std::vector<file_settings> &per_file)
 	: files(dumpfiles), settings(per_file), types(_types), thresh(_thresh), filter(_filter), dbg(_dbg), bps(blocks_per_submit),
-	  devices(_devices), n_telegrams(0), sink(NULL), psink(NULL), out_mode(0), bits_replay(false), slots(0), wide(false)
+	  devices(_devices), n_telegrams(0), sink(NULL), psink(NULL), out_mode(0), bits_replay(false), slots(0), wide(false), rate_p(1), rate_q(1), unit(1)
 {
 	if (devices.empty())
 		devices.push_back(0);
@@ -80,6 +80,15 @@ void pipe_sink::flush()
 		fflush(pipe);
 	}
 	pending.clear();
+}
+
+void gpu_engine::set_rate(int p, int q)
+{
+	rate_p = p;
+	rate_q = q;
+	unit = q;
+	while (unit % 2 == 0)
+		unit /= 2;
 }
 
 void gpu_engine::set_handler(const char *exec, bool batched, int mode)
@@ -217,6 +226,9 @@ struct device_worker {
 	std::vector<batch_plan> plan;             // plan_batches
 	bool wide;          // -x: 15.36 MS/s dumps (TFREC_AMD_F_INPUT_10X in flags), the files' tunes are wide tunes
 	bool share;         // one stream per file for the whole job (no -n): a path given several times is read once, into one row
+	int rate_p, rate_q;  // -r: the input rate as p / q of 1.536 MS/s (1 / 1: none)
+	size_t block_bytes;  // bytes of one block of a file: 65536 p / q (x `unit` blocks when q does not divide it), 655360 with -x
+	int unit;            // blocks a block_bytes piece holds: every batch carries a multiple of it
 	int rc;
 	std::atomic<bool> *abort;  // set by the engine when any worker failed: stop instead of running the whole job
 	std::mutex mu;
@@ -225,7 +237,7 @@ struct device_worker {
 	bool done;
 	std::thread th;
 
-	device_worker() : files(NULL), s0(0), s1(0), device(0), types(0), thresh(0), filter(0), bps(1), flags(0), nslots(0), file_blocks(NULL), wide(false), share(false), rc(0), abort(NULL), done(false) {}
+	device_worker() : files(NULL), s0(0), s1(0), device(0), types(0), thresh(0), filter(0), bps(1), flags(0), nslots(0), file_blocks(NULL), wide(false), share(false), rate_p(1), rate_q(1), block_bytes(TFREC_AMD_BLOCK_BYTES), unit(1), rc(0), abort(NULL), done(false) {}
 
 	void push(std::vector<tfrec_amd_event> &&ev)
 	{
@@ -281,13 +293,12 @@ struct device_worker {
 		cfg.max_events = (int32_t)std::max<size_t>(4096, n * (size_t)bps * ((flags & TFREC_AMD_F_BITS) ? 256 : 64));
 		cfg.flags = flags;
 		tfrec_amd_ctx *ctx = NULL;
-		int r = tfrec_amd_create(&cfg, &ctx);
+		int r = (rate_p != 1 || rate_q != 1) ? tfrec_amd_create_rate(&cfg, rate_p, rate_q, &ctx) : tfrec_amd_create(&cfg, &ctx);
 		if (r) {
 			fprintf(stderr, "tfrec_amd_create (device %d): %s (%s)\n", device, tfrec_amd_strerror(r), tfrec_amd_last_error());
 			return r;
 		}
-		const size_t block_bytes = wide ? TFREC_AMD_BLOCK_BYTES_10X : TFREC_AMD_BLOCK_BYTES;
-		const size_t row = (size_t)bps * block_bytes;
+		const size_t row = (size_t)(bps / unit) * block_bytes;
 		const size_t n_batches = plan.size();
 		// Shared inputs (tfrec_amd_map_streams): without -n a stream carries one file for the whole job, and the streams whose
 		// files are one path share that path's input row -- the file is opened and read once, staged and copied once.  Decoders,
@@ -353,7 +364,7 @@ struct device_worker {
 					if (n_rows < n && (!reads[s] || b.file[s] < 0))
 						continue;  // (a shared row is filled by its first stream)
 					uint8_t *dst = buf + (size_t)in_row[s] * row;
-					const size_t want = (size_t)b.nb * block_bytes;
+					const size_t want = (size_t)(b.nb / unit) * block_bytes;
 					const int f = b.file[s];
 					size_t got = 0;
 					if (f >= 0) {
@@ -475,6 +486,9 @@ int gpu_engine::run()
 	const size_t n = files.size();
 	std::vector<size_t> file_blocks(n, 0);
 	stream_samples.assign(n, 0);
+	// bytes of a piece of `unit` blocks of a file (unit = 1 without -r): 65536 p / q x unit is a whole number
+	// (q is unit times a power of two <= 64)
+	const size_t block_bytes = wide ? (size_t)TFREC_AMD_BLOCK_BYTES_10X : (size_t)TFREC_AMD_BLOCK_BYTES * rate_p * unit / rate_q;
 	for (size_t s = 0; s < n; s++) {
 		FILE *f = fopen(files[s].c_str(), "rb");
 		if (!f) {
@@ -482,13 +496,15 @@ int gpu_engine::run()
 			return TFREC_AMD_E_INVAL;
 		}
 		fseek(f, 0, SEEK_END);
-		const size_t blocks = (size_t)ftell(f) / (wide ? TFREC_AMD_BLOCK_BYTES_10X : TFREC_AMD_BLOCK_BYTES);  // trailing partial block dropped, engine.cpp:72-76
+		// trailing partial block dropped, engine.cpp:72-76 (-r: a trailing partial piece of `unit` blocks)
+		const size_t blocks = (size_t)ftell(f) / block_bytes * (size_t)unit;
 		fclose(f);
 		stream_samples[s] = (long long)blocks * TFREC_AMD_BLOCK_DEC;
 		file_blocks[s] = blocks;
 	}
 	size_t n_batches = 0;  // of the device with the most
 	const size_t nd = std::min(devices.size(), n);  // never more workers than streams
+	bps = (bps + unit - 1) / unit * unit;
 	std::vector<device_worker> workers(nd);
 	for (size_t d = 0; d < nd; d++) {
 		device_worker &w = workers[d];
@@ -506,6 +522,10 @@ int gpu_engine::run()
 		w.flags = (bits_replay ? (TFREC_AMD_F_BITS | TFREC_AMD_F_ALL_FLUSHES) : 0u) | (wide ? TFREC_AMD_F_INPUT_10X : 0u);
 		w.wide = wide;
 		w.share = slots <= 0;
+		w.rate_p = rate_p;
+		w.rate_q = rate_q;
+		w.block_bytes = block_bytes;
+		w.unit = unit;
 		w.nslots = w.s1 - w.s0;
 		if (slots > 0)
 			w.nslots = std::min(w.nslots, (size_t)slots);

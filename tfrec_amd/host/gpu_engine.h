@@ -122,6 +122,11 @@ public:
 	// In both modes, without -n: a path given to several -L is opened and read once and occupies one input row of the batch; its
 	// streams are mapped to it (tfrec_amd_map_streams).  Decoders, stream indices and output order stay per -L occurrence.
 	void set_wide(bool on) { wide = on; }
+	// -r: the dump files are u8 dumps at 1536000 p / q samples per second (tfrec_amd_create_rate).  A submit then
+	// carries a multiple of `unit` blocks, the odd part of q (the caller rounds blocks_per_submit up to one), a file is read in
+	// pieces of that many blocks and its trailing partial piece is dropped; everything else -- the tail of a file, -n, -d,
+	// shared paths, tunes and settings -- is as without it.  Excludes set_wide.
+	void set_rate(int p, int q);
 	// returns 0 on success, a TFREC_AMD_E_* code otherwise
 	int run();
 	// decoders of stream s in slot order (NULL for slots not registered)
@@ -143,6 +148,7 @@ private:
 	bool bits_replay;
 	int slots;
 	bool wide;
+	int rate_p, rate_q, unit;  // set_rate (1, 1, 1: none)
 };
 
 #endif

@@ -1,6 +1,6 @@
 // tfrec_amd/host/main.cpp -- tfrec_gpu: the reference's file-replay CLI on the GPU path.
 //
-//   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x] [-q] [-D] [-B] [-d device[,device...]] [-b blocks]
+//   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-q] [-D] [-B] [-d device[,device...]] [-b blocks]
 //             [-n streams] [-e handler | -E handler] [-m mode] [-p settings] -L dump.iq [[-p settings] -L more.iq ...]
 //   tfrec_gpu [-T hexmask] -X telegrams.txt
 //
@@ -27,6 +27,10 @@
 // can sit anywhere in the wide dump.  With or without -x, and without -n: a path given to several -L is opened and read once and
 // occupies one input row of the batch (tfrec_amd_map_streams); decoders, the -E stream index and the order of the output stay
 // per -L occurrence.  With -n a repeated file is read once per occurrence, as before.
+// -r Hz (not in the reference): the sample rate of the -L files, for dumps that were not recorded at 1.536 MS/s -- rtl_sdr's
+// default 2048000, 2400000, 1920000 ... --: the rate is reduced to P / Q of 1536000 and the dumps are resampled on the GPU
+// (tfrec_amd_create_rate; 1 < P/Q < 10, Q <= 64).  -f / -c / -p f= act behind the resampler, within +-767 kHz.  A
+// submit must hold a whole number of input samples: -b is rounded up to the next multiple of Q's odd part.  Excludes -x.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -139,8 +143,9 @@ int main(int argc, char **argv)
 	std::vector<spec> dump_spec;  // per -L file
 	bool have_spec = false;
 	long freq = -1, center = 868250;  // -f (unset: the dumps' own frequency), -c: kHz
+	long rate = 0;  // -r: Hz (0: 1536000)
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xqDBd:b:n:L:X:e:E:m:p:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:qDBd:b:n:L:X:e:E:m:p:h")) != -1) {
 		switch (c) {
 		case 'T': types = (int)strtol(optarg, NULL, 16); break;
 		case 't': thresh = atoi(optarg); break;
@@ -153,6 +158,15 @@ int main(int argc, char **argv)
 			}
 			break;
 		case 'x': wide = true; break;
+		case 'r': {
+			char *end = NULL;
+			rate = strtol(optarg, &end, 10);
+			if (end == optarg || *end || rate <= 0 || rate > 100000000L) {
+				fprintf(stderr, "tfrec_gpu: bad -r '%s': want the dumps' sample rate in Hz\n", optarg);
+				return 1;
+			}
+			break;
+		}
 		case 'q': dbg = -1; break;
 		case 'D': dbg++; break;
 		case 'B': bits = true; break;
@@ -179,11 +193,13 @@ int main(int argc, char **argv)
 		case 'E': exec = optarg; batched = true; break;
 		case 'm': mode = atoi(optarg); break;
 		default:
-			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-p settings] -L dump [[-p settings] -L dump ...] | -X hexfile\n"
+			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-p settings] -L dump [[-p settings] -L dump ...] | -X hexfile\n"
 					"  -f kHz      receive frequency (default: the dumps' own, -c)\n"
 					"  -c kHz      frequency the dumps were recorded at (default 868250); -f within 767 kHz of it\n"
 					"  -x          the dumps are 15.36 MS/s u8 dumps (10x the rate); -f within 7679 kHz of -c, shifted ahead of the 10:1 stage\n"
 					"              (a file given to several -L is read once and shared by its streams; with -n it is read per -L, as before)\n"
+					"  -r Hz       sample rate of the dumps (default 1536000), e.g. 2048000 or 2400000: resampled on the GPU; -b is rounded up\n"
+					"              to a block count that holds a whole number of input samples; not with -x\n"
 					"  -n streams  at most this many streams per device: the -L files queue for them in order\n"
 					"  -p T=<hex>,t=<n>,W=<0|1>,f=<kHz>  -T / -t / -W / -f of the -L files that follow, up to the next -p (fields left out: the global ones)\n");
 			return c == 'h' ? 0 : 1;
@@ -207,6 +223,38 @@ int main(int argc, char **argv)
 	if (thresh < 0) {
 		fprintf(stderr, "tfrec_gpu: -t must be >= 0 (0 = auto)\n");
 		return 1;
+	}
+	// -r: the rate as P / Q of 1536000, checked by the library's own rules (no device needed); -b up to a permitted block count
+	int rate_p = 1, rate_q = 1;
+	if (rate && wide) {
+		fprintf(stderr, "tfrec_gpu: -r and -x exclude each other (-x is the fixed rate 15360000)\n");
+		return 1;
+	}
+	if (rate && rate != 1536000) {
+		long a = rate, b = 1536000;
+		while (b) {
+			const long t = a % b;
+			a = b;
+			b = t;
+		}
+		const long p = rate / a, q = 1536000 / a;
+		if (p > 0x7fffffffL || tfrec_amd_resample_taps((int32_t)p, (int32_t)q, NULL, 0, NULL) != TFREC_AMD_OK) {
+			fprintf(stderr, "tfrec_gpu: -r %ld: the rate is %ld/%ld of 1536000 S/s, which the resampler does not take (it needs "
+					"1536000 < rate < 15360000 and a denominator of at most 64, and refuses a few rates whose filter would "
+					"be ambiguous or could overflow)\n", rate, p, q);
+			return 1;
+		}
+		rate_p = (int)p;
+		rate_q = (int)q;
+		int unit = rate_q;
+		while (unit % 2 == 0)
+			unit /= 2;
+		if (blocks >= 1 && blocks % unit) {
+			const int up = (blocks + unit - 1) / unit * unit;
+			fprintf(stderr, "tfrec_gpu: -b %d rounded up to %d: at %ld S/s a submit holds a multiple of %d blocks\n", blocks, up,
+				rate, unit);
+			blocks = up;
+		}
 	}
 	// every file's tune, checked before any device is opened
 	std::vector<int> tunes;
@@ -236,6 +284,8 @@ int main(int argc, char **argv)
 	e.set_bits_replay(bits);
 	e.set_slots(slots);
 	e.set_wide(wide);
+	if (rate_p != 1 || rate_q != 1)
+		e.set_rate(rate_p, rate_q);
 	int rc = e.run();
 	fflush(stdout);
 	return rc ? 2 : 0;
