@@ -284,11 +284,39 @@ int tfrec_amd_get_stream_tune_wide(tfrec_amd_ctx *ctx, int stream, int32_t *tune
  *            sample, and results do not depend on how a stream is cut into submits.
  * cfg->flags must not contain TFREC_AMD_F_INPUT_10X (TFREC_AMD_E_INVAL).  On such a context tfrec_amd_submit_device / _host take
  * n_in * 2 bytes per row (submit_host stages exactly that, rows 0 .. R-1), tfrec_amd_read_stage0 returns y0, tfrec_amd_get_memory
- * counts the stage's buffers, tfrec_amd_tune_streams_wide returns TFREC_AMD_E_INVAL (a wide tune ahead of this stage is not
- * built), and everything else keeps its meaning, because nothing behind stage 0 changes: reset, configure, tune (it acts on y0)
+ * counts the stage's buffers, tfrec_amd_tune_streams_wide returns TFREC_AMD_E_INVAL (the tune ahead of this stage is
+ * tfrec_amd_tune_streams_input, below), and everything else keeps its meaning, because nothing behind stage 0 changes: reset, configure, tune (it acts on y0)
  * and map (the stage looks the row up), both pipeline layouts, _SERIAL_CHAINS, _BITS, _ALL_FLUSHES, _TIMING.  A context made by
  * tfrec_amd_create launches the kernels it launched before. */
 int tfrec_amd_create_rate(const tfrec_amd_config *cfg, int32_t rate_p, int32_t rate_q, tfrec_amd_ctx **out);
+/* Input-rate tune: a frequency shift at the context's input rate fs_in = 1536000 * P / Q (what
+ * tfrec_amd_get_input_rate reports), AHEAD of the resampling stage, so that a receiver can sit anywhere in a recording made at
+ * that rate -- not only within the +-768 kHz that tfrec_amd_tune_streams, which acts behind the stage, can reach.  It is
+ * tfrec_amd_tune_streams' mixer at the input rate, on x = (u8 - 128) << 6 (same table C, S and the same rounding):
+ *     inc_in = floor((tune_hz * 2^33 * Q + 1536000 * P) / (2 * 1536000 * P)) mod 2^32          (exact 64-bit integers, floor division)
+ *     p      = (n * inc_in) mod 2^32,  k = p >> 20      (n: the INPUT sample's index since the stream's start or last restart)
+ *     I'     = sat16((I * C[k] + Q * S[k] + 2^14) >> 15),  Q' = sat16((Q * C[k] - I * S[k] + 2^14) >> 15)
+ *     y0[m]  = int16( sum_{n<T} ( x'[i0 - (T-1) + n] * h[phi][n] ) >> 16 )                  (the resampling stage, unchanged)
+ * Limit: 2 * |tune_hz| * Q < 1536000 * P, that is |tune_hz| < fs_in / 2, tested in integers (the numerator of inc_in stays below
+ * 2^63 for every permitted rate).  With P/Q = 10/1 the formula is inc10, with 1/1 tfrec_amd_tune_streams' inc: one definition
+ * for every rate.  tune_hz = 0 is no mixing: bit for bit the stage as it is.  The history before a start or restart is silence; a
+ * history sample from the previous submit is rotated with its own (earlier) n.  The phase of a submit's first input sample is
+ * (n0 * inc_in) mod 2^32, n0 = 4 * (decimated samples since the stream's origin) * P / Q, whole because every submit is.
+ * tfrec_amd_tune_streams composes: it acts on y0.  tfrec_amd_read_stage0 returns the shifted, resampled y0.  Pinned by
+ * tfrec_amd/tune.py (inc_in, mix_in_s16) and tfrec_amd/resample.py (resample_x16).
+ *   No wrap: the mixer's output of u8 input is at most 11585 per rail, and the largest max_phi sum_n |h| of any accepted rate is
+ *   108112 (at 65/64), so |y0| <= 108112 * 11585 >> 16 = 19111.  A guard stays: on a rate where
+ *   max_phi sum_n |h[phi][n]| * 11585 >> 16 >= 32768 the call returns TFREC_AMD_E_INVAL.
+ *   - An input tune is a restart, with the semantics, the "last wins" and the composition rules of tfrec_amd_map_streams /
+ *     tfrec_amd_tune_streams_wide: reset + configure + tune + map + input tune before one submit are ONE restart; later resets
+ *     keep the tune.
+ *   - A context in which no stream has an input tune launches the kernels it launched before, and holds no more memory with one.
+ *   - A TFREC_AMD_F_INPUT_10X context: the call IS tfrec_amd_tune_streams_wide (the same state; both getters return the same value).
+ *     A context of the default input: TFREC_AMD_E_INVAL (its tune is tfrec_amd_tune_streams).
+ * Errors: as tfrec_amd_tune_streams_wide, with the limit above. */
+int tfrec_amd_tune_streams_input(tfrec_amd_ctx *ctx, const int32_t *streams, const int32_t *tune_hz, int n);
+/* The input-rate tune the next submit will use for one stream (0: none). */
+int tfrec_amd_get_stream_tune_input(tfrec_amd_ctx *ctx, int stream, int32_t *tune_hz);
 /* The context's input rate as P/Q of 1.536 MS/s: 1/1 for tfrec_amd_create, 10/1 with TFREC_AMD_F_INPUT_10X. */
 int tfrec_amd_get_input_rate(tfrec_amd_ctx *ctx, int32_t *p, int32_t *q);
 /* Bytes one input row of a submit of n_blocks blocks holds (every kind of context); TFREC_AMD_E_INVAL when n_blocks < 1 or

@@ -1,6 +1,7 @@
-"""Cost of the resampling stage: kernel time of resample_kernel at P/Q = 4/3 (2.048 MS/s) and 25/16 (2.4 MS/s)
-for 1024 streams x 48 blocks, and -- for scale, on the same machine in the same run -- of the plain front end of an
-unresampled context at the same size.
+"""Cost of the resampling stage and of the input-rate tune ahead of it (6g): kernel time of resample_kernel at
+P/Q = 4/3 (2.048 MS/s) and 25/16 (2.4 MS/s) for 1024 streams x 48 blocks, untuned (resample_kernel<false>) and with every stream
+tuned at the input rate (resample_kernel<true>), and -- for scale, on the same machine in the same run -- of the plain front end
+of an unresampled context at the same size.
 
     python profiles/ubench/resample_cost.py [--out DIR] [--streams 1024] [--blocks 48] [--submits 12]
 
@@ -35,9 +36,13 @@ def workload(n_streams: int, n_blocks: int, submits: int) -> None:
 
     from tfrec_amd import api
 
-    for rate in RATES + [None]:
+    # per rate an untuned context, then one with every stream tuned at the input rate; the plain context last
+    for rate, tuned in [(r, t) for r in RATES for t in (False, True)] + [(None, False)]:
         kw = {} if rate is None else {"input_rate": rate}
         with api.Receiver(n_streams, 0x2F, 500, 0, max_blocks=n_blocks, **kw) as r:
+            if tuned:
+                half = 768000 * rate[0] // rate[1]
+                r.tune_streams_input(range(n_streams), [((s % 13) - 6) * (half // 7) + 30000 for s in range(n_streams)])
             nbytes = r.input_bytes(n_blocks)
             iq = torch.randint(124, 133, (n_streams, nbytes), dtype=torch.uint8, device="cuda:0")
             torch.cuda.synchronize()
@@ -74,11 +79,18 @@ def report(trace_dir: str, n_streams: int, n_blocks: int, submits: int) -> str:
         names = [k for k in d if sub in k]
         return sum((d[k] for k in sorted(names)), []) if names else []
 
-    rs = pick("resample_kernel")
+    def variant(tuned):
+        tag = ("<true>", "ILb1E") if tuned else ("<false>", "ILb0E")
+        names = [k for k in d if "resample_kernel" in k and any(t in k.replace(" ", "") for t in tag)]
+        return sum((d[k] for k in sorted(names)), [])
+
     per = WARMUP + submits
     rows = []
-    for i, (p, q) in enumerate(RATES):
-        rows.append(("resample_kernel %d/%d" % (p, q), rs[i * per + WARMUP:(i + 1) * per], n_streams * n_blocks * 65536 * p // q))
+    for tuned in (False, True):
+        rs = variant(tuned)
+        for i, (p, q) in enumerate(RATES):
+            rows.append(("resample_kernel<%s> %d/%d" % ("true" if tuned else "false", p, q), rs[i * per + WARMUP:(i + 1) * per],
+                         n_streams * n_blocks * 65536 * p // q))
     # the plain context's front end: the u8 instantiation (the rate contexts run the int16 one)
     fe = [k for k in d if "frontend_kernel" in k and "Lb0ELb0" in k.replace(" ", "")] or [k for k in d if "frontend_kernel<false, false" in k]
     plain = sum((d[k] for k in fe), [])
@@ -86,7 +98,7 @@ def report(trace_dir: str, n_streams: int, n_blocks: int, submits: int) -> str:
     fe16 = [k for k in d if "frontend_kernel" in k and k not in fe]
     in16 = sum((d[k] for k in fe16), [])
     for i, (p, q) in enumerate(RATES):
-        rows.append(("frontend_kernel behind %d/%d (int16 input)" % (p, q), in16[i * per + WARMUP:(i + 1) * per],
+        rows.append(("frontend_kernel behind %d/%d (int16 input)" % (p, q), in16[2 * i * per + WARMUP:(2 * i + 1) * per],
                      n_streams * n_blocks * 32768 * 4))
     for name, t, nbytes in rows:
         if not t:

@@ -100,6 +100,7 @@ EXPORTS = (
     "tfrec_amd_configure_streams", "tfrec_amd_get_stream_config", "tfrec_amd_tune_streams", "tfrec_amd_get_stream_tune",
     "tfrec_amd_map_streams", "tfrec_amd_get_stream_input", "tfrec_amd_tune_streams_wide", "tfrec_amd_get_stream_tune_wide",
     "tfrec_amd_create_rate", "tfrec_amd_get_input_rate", "tfrec_amd_input_bytes", "tfrec_amd_resample_taps",
+    "tfrec_amd_tune_streams_input", "tfrec_amd_get_stream_tune_input",
 )
 
 _libs = {}
@@ -166,6 +167,8 @@ def load_library(build: bool = True, experiments: bool = False):
     L.tfrec_amd_get_stream_input.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
     L.tfrec_amd_tune_streams_wide.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tfrec_amd_get_stream_tune_wide.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
+    L.tfrec_amd_tune_streams_input.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.tfrec_amd_get_stream_tune_input.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
     L.tfrec_amd_create_rate.argtypes = [C.POINTER(Config), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
     L.tfrec_amd_get_input_rate.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.tfrec_amd_input_bytes.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]
@@ -399,6 +402,18 @@ class Receiver:
         """The wide tune in Hz the next submit uses for one stream (tfrec_amd_get_stream_tune_wide)."""
         v = C.c_int32(0)
         _check(self.L, self.L.tfrec_amd_get_stream_tune_wide(self.h, int(stream), C.byref(v)))
+        return int(v.value)
+
+    def tune_streams_input(self, streams, tune_hz):
+        """Input-rate tune of the listed streams (tfrec_amd_tune_streams_input, input_rate and input_10x contexts): the offset in
+        Hz of the wanted channel from the centre of the recording, applied ahead of the resampling stage (|tune_hz| < half the
+        input rate; 0 = none; see tune.py: mix_in_s16).  The streams restart as fresh receivers at the next submit."""
+        self._pairs(self.L.tfrec_amd_tune_streams_input, streams, tune_hz, "tune", "tune_hz")
+
+    def stream_tune_input(self, stream: int) -> int:
+        """The input-rate tune in Hz the next submit uses for one stream (tfrec_amd_get_stream_tune_input)."""
+        v = C.c_int32(0)
+        _check(self.L, self.L.tfrec_amd_get_stream_tune_input(self.h, int(stream), C.byref(v)))
         return int(v.value)
 
     def drain(self, allow_overflow: bool = False) -> np.ndarray:

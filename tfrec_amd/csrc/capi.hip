@@ -16,7 +16,7 @@ hipError_t launch_decim10(hipStream_t st, const uint8_t *iq, size_t stride, int 
 			  const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride, const uint4 *chan);
 hipError_t launch_resample(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, int p, int q, int t,
 			   const float *taps, const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride,
-			   const uint4 *chan);
+			   const uint4 *chan, bool tuned);
 hipError_t launch_frontend(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks,
 			   const uint8_t *tail_in, uint8_t *tail_out, uint32_t *dec, size_t dec_stride,
 			   unsigned long long *mask, size_t mask_stride, uint32_t *prevdec, int thresh, const FrontTapsCfg &taps,
@@ -160,7 +160,10 @@ struct tfrec_amd_ctx {
 	// tfrec_amd_create_rate: the input rate is 1536000 rate_p / rate_q; the resampling stage writes d_in16 as the
 	// 10:1 stage does, from a tap table [rate_q][rate_t] (h / 1024 as floats) and its raw history (d_tailR: two buffers that flip
 	// with tail_sel).  in16: a pre-stage writes stage 0 and the front end reads int16 (in10x or resamp).
+	// rate_abs: max_phi sum_n |h[phi][n]| of that table, for the guard of tfrec_amd_tune_streams_input (6g), whose per-stream
+	// tune and increment per input sample live in wide_hz / wide_inc as the 10x context's wide tune does.
 	int32_t rate_p = 1, rate_q = 1, rate_t = 0;
+	long long rate_abs = 0;
 	bool resamp = false, in16 = false;
 	float *d_rtaps = nullptr;
 	uint8_t *d_tailR[2] = {};
@@ -697,6 +700,12 @@ static int make_front_buffers(tfrec_amd_ctx *c)
 		if (!resample_table(c->rate_p, c->rate_q, h, t))  // (tfrec_amd_create_rate checked it already)
 			return TFREC_AMD_E_INVAL;
 		c->rate_t = t;
+		for (int phi = 0; phi < c->rate_q; phi++) {
+			long long a = 0;
+			for (int k = 0; k < t; k++)
+				a += llabs((long long)h[(size_t)phi * t + k]);
+			c->rate_abs = std::max(c->rate_abs, a);
+		}
 		std::vector<float> hf(h.size());
 		for (size_t i = 0; i < h.size(); i++)
 			hf[i] = (float)h[i] * (1.0f / 1024.0f);  // exact: |h| < 2^17
@@ -1306,12 +1315,14 @@ static int stage_tune(tfrec_amd_ctx *c, int set)
 }
 
 // The per-stream {inc10, phase10, input row, 0} of this submit, staged like stage_tune's.  phase10 is the phase of
-// the submit's first INPUT sample n0 (40 per decimated sample with TFREC_AMD_F_INPUT_10X): (n0 * inc10) mod 2^32.
+// the submit's first INPUT sample n0 (40 per decimated sample with TFREC_AMD_F_INPUT_10X): (n0 * inc10) mod 2^32.  A rate
+// context (6g): {inc_in, ...} with n0 = 4 P / Q input samples per decimated sample -- whole, because every submit is.
 static int stage_chan(tfrec_amd_ctx *c, int set)
 {
 	for (int s = 0; s < c->cfg.n_streams; s++) {
 		const uint32_t inc = c->wide_inc[s];
-		const long long n0 = c->reset_marked[s] ? 0 : 40 * (c->sample_base - c->origin[s]);
+		const long long rp = c->in10x ? 10 : c->rate_p, rq = c->in10x ? 1 : c->rate_q;
+		const long long n0 = c->reset_marked[s] ? 0 : 4 * (c->sample_base - c->origin[s]) * rp / rq;
 		c->h_chan[set][s] = make_uint4(inc, (uint32_t)((uint64_t)n0 * inc), (uint32_t)c->row[s], 0u);
 	}
 	HIPCHK(hipMemcpyAsync(c->d_chan[set], c->h_chan[set], (size_t)c->cfg.n_streams * sizeof(uint4), hipMemcpyHostToDevice,
@@ -1393,7 +1404,7 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	if (c->resamp) {  // 1536000 P / Q S/s u8 -> 1.536 MS/s int16 pairs, then the same cascade on int16 input
 		HIPCHK(launch_resample(fs, (const uint8_t *)d_iq, stride, c->cfg.n_streams, n_blocks, c->rate_p, c->rate_q, c->rate_t,
 				       c->d_rtaps, c->d_tailR[c->tail_sel], c->d_tailR[c->tail_sel ^ 1], c->d_in16[set], c->in16_stride,
-				       chan10 ? c->d_chan[set] : nullptr));
+				       chan10 ? c->d_chan[set] : nullptr, c->n_wide != 0));
 		fin = (const uint8_t *)c->d_in16[set];
 		fstride = c->in16_stride * sizeof(uint32_t);
 	}
@@ -1827,7 +1838,7 @@ int tfrec_amd_tune_streams_wide(tfrec_amd_ctx *c, const int32_t *streams, const 
 		return TFREC_AMD_E_INVAL;
 	if (!c->in10x) {
 		snprintf(g_err, sizeof(g_err), "the wide tune acts ahead of the 10:1 stage: the context needs the 15.36 MS/s input flag%s",
-			 c->resamp ? " (a wide tune ahead of the resampling stage is not built)" : "");
+			 c->resamp ? " (the tune ahead of the resampling stage is tfrec_amd_tune_streams_input)" : "");
 		return TFREC_AMD_E_INVAL;
 	}
 	for (int i = 0; i < n; i++) {
@@ -1858,6 +1869,63 @@ int tfrec_amd_get_stream_tune_wide(tfrec_amd_ctx *c, int stream, int32_t *tune_h
 		return TFREC_AMD_E_INVAL;
 	*tune_hz = c->wide_hz[stream];
 	return TFREC_AMD_OK;
+}
+
+// inc_in = floor((tune_hz * 2^33 * Q + 1536000 P) / (2 * 1536000 P)) mod 2^32: the phase step per input sample at
+// 1536000 P / Q samples per second.  |tune_hz| < 7680000 and Q <= 64: the numerator stays below 2^63.
+static uint32_t tune_inc_in(int32_t tune_hz, long long p, long long q)
+{
+	const long long num = (long long)tune_hz * (1LL << 33) * q + 1536000LL * p, den = 2 * 1536000LL * p;
+	long long v = num / den;
+	if (num % den != 0 && num < 0)
+		v--;  // (floor, not C's truncation)
+	return (uint32_t)(uint64_t)v;
+}
+
+// The tune at the input rate, ahead of the resampling stage (6g); a 10x context's wide tune under another name
+int tfrec_amd_tune_streams_input(tfrec_amd_ctx *c, const int32_t *streams, const int32_t *tune_hz, int n)
+{
+	if (!c || n < 0 || (n > 0 && (!streams || !tune_hz)))
+		return TFREC_AMD_E_INVAL;
+	if (c->in10x)
+		return tfrec_amd_tune_streams_wide(c, streams, tune_hz, n);
+	if (!c->resamp) {
+		snprintf(g_err, sizeof(g_err), "the input-rate tune acts ahead of a resampling or 10:1 stage, and this context has none: "
+					       "tfrec_amd_tune_streams tunes its 1.536 MS/s input");
+		return TFREC_AMD_E_INVAL;
+	}
+	const long long p = c->rate_p, q = c->rate_q;
+	if (((c->rate_abs * 11585) >> 16) >= 32768) {  // (no accepted rate comes near: 19111 at most)
+		snprintf(g_err, sizeof(g_err), "input rate %lld/%lld: the int16 store of a tuned stream could wrap", p, q);
+		return TFREC_AMD_E_INVAL;
+	}
+	for (int i = 0; i < n; i++) {
+		TRY(check_stream(c, streams[i]));
+		const long long a = 2 * llabs((long long)tune_hz[i]) * q;
+		if (a >= 1536000LL * p) {  // |tune_hz| < fs_in / 2, in integers
+			snprintf(g_err, sizeof(g_err), "tune_hz %d outside half the input rate 1536000 * %lld / %lld (|tune_hz| < %lld)", (int)tune_hz[i],
+				 p, q, (1536000LL * p + 2 * q - 1) / (2 * q));
+			return TFREC_AMD_E_INVAL;
+		}
+	}
+	TRY(check_live(c));
+	if (n == 0)
+		return TFREC_AMD_OK;
+	for (int i = 0; i < n; i++) {
+		const int s = streams[i];
+		c->wide_hz[s] = tune_hz[i];
+		c->wide_inc[s] = tune_inc_in(tune_hz[i], p, q);
+		mark_restart(c, s);
+	}
+	c->n_wide = 0;
+	for (const uint32_t inc : c->wide_inc)
+		c->n_wide += inc != 0;
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_get_stream_tune_input(tfrec_amd_ctx *c, int stream, int32_t *tune_hz)
+{
+	return tfrec_amd_get_stream_tune_wide(c, stream, tune_hz);
 }
 
 int tfrec_amd_read_stage0(tfrec_amd_ctx *c, int stream, int16_t *out, size_t n_pairs)

@@ -393,6 +393,7 @@ struct device_worker {
 				rcv.notify_all();
 			}
 		});
+		std::vector<bool> in_tune(n, false), narrow_tune(n, false);  // -r: the stream has an input-rate tune / a tune behind the resampler
 		auto submit = [&](size_t k) -> int {
 			{
 				std::unique_lock<std::mutex> lk(rmu);
@@ -409,7 +410,31 @@ struct device_worker {
 				if (rr)
 					return rr;
 			}
-			if (!b.tune.empty()) {  // ... and tunes
+			if (!b.tune.empty() && (rate_p != 1 || rate_q != 1)) {
+				// ... and tunes, -r: an offset within +-767 kHz is a tune behind the resampler, as it always was; a larger one is
+				// the input-rate tune ahead of it (tfrec_amd_tune_streams_input).  A stream that goes from one kind to the other
+				// (-n) has the other kind cleared; all of it is one restart.
+				std::vector<int32_t> ns, nhz, is, ihz;
+				for (size_t i = 0; i < b.tune.size(); i++) {
+					const int32_t s = b.tune[i], hz = b.tune_hz[i];
+					const bool far = hz <= -768000 || hz >= 768000;
+					if (far || in_tune[s]) {
+						is.push_back(s);
+						ihz.push_back(far ? hz : 0);
+						in_tune[s] = far;
+					}
+					if (!far || narrow_tune[s]) {
+						ns.push_back(s);
+						nhz.push_back(far ? 0 : hz);
+						narrow_tune[s] = !far && hz != 0;
+					}
+				}
+				int rr = ns.empty() ? 0 : tfrec_amd_tune_streams(ctx, ns.data(), nhz.data(), (int)ns.size());
+				if (!rr && !is.empty())
+					rr = tfrec_amd_tune_streams_input(ctx, is.data(), ihz.data(), (int)is.size());
+				if (rr)
+					return rr;
+			} else if (!b.tune.empty()) {  // ... and tunes
 				const int rr = wide ? tfrec_amd_tune_streams_wide(ctx, b.tune.data(), b.tune_hz.data(), (int)b.tune.size())
 						    : tfrec_amd_tune_streams(ctx, b.tune.data(), b.tune_hz.data(), (int)b.tune.size());
 				if (rr)

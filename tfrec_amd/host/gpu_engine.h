@@ -125,7 +125,8 @@ public:
 	// -r: the dump files are u8 dumps at 1536000 p / q samples per second (tfrec_amd_create_rate).  A submit then
 	// carries a multiple of `unit` blocks, the odd part of q (the caller rounds blocks_per_submit up to one), a file is read in
 	// pieces of that many blocks and its trailing partial piece is dropped; everything else -- the tail of a file, -n, -d,
-	// shared paths, tunes and settings -- is as without it.  Excludes set_wide.
+	// shared paths, tunes and settings -- is as without it, and a file's tune beyond +-767 kHz (up to half the rate) becomes the
+	// input-rate tune ahead of the resampler (tfrec_amd_tune_streams_input).  Excludes set_wide.
 	void set_rate(int p, int q);
 	// returns 0 on success, a TFREC_AMD_E_* code otherwise
 	int run();

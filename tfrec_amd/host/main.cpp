@@ -29,8 +29,10 @@
 // per -L occurrence.  With -n a repeated file is read once per occurrence, as before.
 // -r Hz (not in the reference): the sample rate of the -L files, for dumps that were not recorded at 1.536 MS/s -- rtl_sdr's
 // default 2048000, 2400000, 1920000 ... --: the rate is reduced to P / Q of 1536000 and the dumps are resampled on the GPU
-// (tfrec_amd_create_rate; 1 < P/Q < 10, Q <= 64).  -f / -c / -p f= act behind the resampler, within +-767 kHz.  A
-// submit must hold a whole number of input samples: -b is rounded up to the next multiple of Q's odd part.  Excludes -x.
+// (tfrec_amd_create_rate; 1 < P/Q < 10, Q <= 64).  -f / -c / -p f= reach the whole recording, |f - c| below half the
+// rate: within +-767 kHz the shift acts behind the resampler (tfrec_amd_tune_streams), a larger one ahead of it, at the input
+// rate (tfrec_amd_tune_streams_input).  A path given to several -L is read once, as without -r.  A submit must
+// hold a whole number of input samples: -b is rounded up to the next multiple of Q's odd part.  Excludes -x.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -199,7 +201,8 @@ int main(int argc, char **argv)
 					"  -x          the dumps are 15.36 MS/s u8 dumps (10x the rate); -f within 7679 kHz of -c, shifted ahead of the 10:1 stage\n"
 					"              (a file given to several -L is read once and shared by its streams; with -n it is read per -L, as before)\n"
 					"  -r Hz       sample rate of the dumps (default 1536000), e.g. 2048000 or 2400000: resampled on the GPU; -b is rounded up\n"
-					"              to a block count that holds a whole number of input samples; not with -x\n"
+					"              to a block count that holds a whole number of input samples; -f less than half the rate from -c (beyond\n"
+					"              767 kHz it is shifted ahead of the resampler); not with -x\n"
 					"  -n streams  at most this many streams per device: the -L files queue for them in order\n"
 					"  -p T=<hex>,t=<n>,W=<0|1>,f=<kHz>  -T / -t / -W / -f of the -L files that follow, up to the next -p (fields left out: the global ones)\n");
 			return c == 'h' ? 0 : 1;
@@ -262,7 +265,13 @@ int main(int argc, char **argv)
 	for (const spec &p : dump_spec) {
 		const long f = p.freq >= 0 ? p.freq : (freq >= 0 ? freq : center);
 		const long lim = wide ? 7680 : 768;
-		if (f - center <= -lim || f - center >= lim) {
+		if (rate_p != 1 || rate_q != 1) {  // -r: |f - c| < fs_in / 2, that is 2 |f - c| Q < 1536 P in kHz
+			if (2 * labs(f - center) * rate_q >= 1536L * rate_p) {
+				fprintf(stderr, "tfrec_gpu: receive frequency %ld kHz (-f / -p f=) is %ld kHz from the dumps' %ld kHz (-c): less than "
+						"%.1f kHz, half the %ld S/s band (-r), can be tuned\n", f, f - center, center, rate / 2000.0, rate);
+				return 1;
+			}
+		} else if (f - center <= -lim || f - center >= lim) {
 			fprintf(stderr, "tfrec_gpu: receive frequency %ld kHz (-f / -p f=) is %ld kHz from the dumps' %ld kHz (-c): at most "
 					"%ld kHz, half the %s band, can be tuned%s\n", f, f - center, center, lim - 1,
 				wide ? "15.36 MS/s" : "1.536 MS/s", wide ? "" : " (-x: 15.36 MS/s dumps, 7679 kHz)");

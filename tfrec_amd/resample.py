@@ -9,6 +9,7 @@ Written from the definition alone: nothing here calls the C library.
     T = 2 * ceil(3 r) taps per phase
     output m (since the stream's start or last restart):  a = m P,  i0 = a div Q,  phi = a mod Q
     y0[m] = int16( sum_{n<T} ( x[i0 - (T-1) + n] * h[phi][n] ) >> 16 )   per rail, x = (u8 - 128) << 6, x[<0] = 0
+    on int16 input x' (the input-rate tune of DESIGN.md 6g ahead of the stage): the same sum over x' -- resample_x16
     h[phi][n]: d = n - T/2 + 1 - phi/Q, g = sinc(d / r) (0.54 + 0.46 cos(2 pi d / T)), v = g 65536 / sum_n g, h = round(v),
                the residual 65536 - sum_n h added to the tap with the largest v (the lowest n among equals)
 """
@@ -80,20 +81,20 @@ def input_samples(n_blocks: int, p: int, q: int) -> int:
     return num // int(q)
 
 
-def resample_s16(iq_u8, p: int, q: int, hist=None) -> np.ndarray:
-    """u8 IQ (interleaved) at 1536000 P / Q -> interleaved int16 (I, Q) at 1.536 MS/s: the whole input as one stream from
-    zero history (hist = None), or -- the input of a submit that follows a permitted boundary -- from `hist`, the (at least
-    T - 1) raw u8 complex samples before it (interleaved); phase 0 falls on the first sample either way."""
+def resample_x16(x16, p: int, q: int, hist=None) -> np.ndarray:
+    """The stage on int16 input (what the input-rate tune feeds it): interleaved int16 (I, Q) at 1536000 P / Q ->
+    interleaved int16 (I, Q) at 1.536 MS/s.  The whole input as one stream from zero history (hist = None), or -- the input of a
+    submit that follows a permitted boundary -- from `hist`, the (at least T - 1) int16 complex samples before it
+    (interleaved); phase 0 falls on the first sample either way."""
     h = taps(p, q).astype(np.int64)
     t = h.shape[1]
-    raw = np.ascontiguousarray(iq_u8, dtype=np.uint8).reshape(-1, 2)
-    n_in = len(raw)
-    x = (raw.astype(np.int64) - 128) << 6
+    x = np.ascontiguousarray(x16, dtype=np.int16).reshape(-1, 2).astype(np.int64)
+    n_in = len(x)
     lead = np.zeros((t - 1, 2), dtype=np.int64)
     if hist is not None:
-        hr = np.ascontiguousarray(hist, dtype=np.uint8).reshape(-1, 2)
+        hr = np.ascontiguousarray(hist, dtype=np.int16).reshape(-1, 2)
         assert len(hr) >= t - 1
-        lead = (hr[len(hr) - (t - 1):].astype(np.int64) - 128) << 6
+        lead = hr[len(hr) - (t - 1):].astype(np.int64)
     xp = np.concatenate([lead, x])  # xp[k] = x[k - (T - 1)]
     n_out = (n_in * q + p - 1) // p  # outputs whose newest sample i0 lies inside the input
     out = np.empty((n_out, 2), dtype=np.int16)
@@ -107,3 +108,19 @@ def resample_s16(iq_u8, p: int, q: int, hist=None) -> np.ndarray:
             acc = ((xp[idx, rail] * hh) >> 16).sum(axis=1)
             out[m0:m0 + len(a), rail] = acc.astype(np.int16)  # (never wraps: taps() refuses a rate where it could)
     return out.reshape(-1)
+
+
+def _widen(iq_u8) -> np.ndarray:
+    return ((np.ascontiguousarray(iq_u8, dtype=np.uint8).astype(np.int16) - 128) << 6).astype(np.int16)
+
+
+def resample_s16(iq_u8, p: int, q: int, hist=None) -> np.ndarray:
+    """u8 IQ (interleaved) at 1536000 P / Q -> interleaved int16 (I, Q) at 1.536 MS/s: the whole input as one stream from
+    zero history (hist = None), or -- the input of a submit that follows a permitted boundary -- from `hist`, the (at least
+    T - 1) raw u8 complex samples before it (interleaved); phase 0 falls on the first sample either way."""
+    return resample_x16(_widen(iq_u8), p, q, None if hist is None else _widen(hist))
+
+
+def abs_sum_max(p: int, q: int) -> int:
+    """max_phi sum_n |h[phi][n]|: what bounds |y0|.  The input-rate tune (6g) is refused where this * 11585 >> 16 >= 32768."""
+    return int(np.abs(taps(p, q).astype(np.int64)).sum(axis=1).max())

@@ -13,7 +13,12 @@ Wideband tune (tfrec_amd_tune_streams_wide): the same mixer at the
 of TFREC_AMD_F_INPUT_10X -- inc10, mix10_s16 -- and that stage itself on int16 input, decim10_s16:
 
     inc10 = floor((tune_hz * 2^33 + 15360000) / 30720000) mod 2^32
-    y0[m] = int16( sum_{n<60} ( x'[10 m - 50 + n] * h10[n] ) >> 16 )       (x' = 0 before the stream's start)"""
+    y0[m] = int16( sum_{n<60} ( x'[10 m - 50 + n] * h10[n] ) >> 16 )       (x' = 0 before the stream's start)
+
+Input-rate tune (tfrec_amd_tune_streams_input): the same mixer at the input rate 1536000 P / Q of a rate context,
+ahead of the resampling stage -- inc_in, mix_in_s16; the stage on int16 input is resample.resample_x16:
+
+    inc_in = floor((tune_hz * 2^33 * Q + 1536000 P) / (2 * 1536000 P)) mod 2^32,    2 |tune_hz| Q < 1536000 P"""
 from __future__ import annotations
 
 import numpy as np
@@ -77,6 +82,21 @@ def inc10(tune_hz: int) -> int:
 def mix10_s16(x16, tune_hz: int, n0: int = 0) -> np.ndarray:
     """mix_s16 at the input rate: x16 are 15.36 MS/s samples, the first of them INPUT sample n0 of its stream."""
     return _mix(x16, inc10(tune_hz), n0)
+
+
+def inc_in(tune_hz: int, p: int, q: int) -> int:
+    """The input-rate tune's phase increment per sample at 1536000 p / q samples per second, in units of 2^-32 turns."""
+    t, p, q = int(tune_hz), int(p), int(q)
+    if p <= 0 or q <= 0:
+        raise ValueError("rate %d/%d" % (p, q))
+    if not 2 * abs(t) * q < RATE * p:
+        raise ValueError("tune_hz %d outside half the input rate %d * %d / %d" % (t, RATE, p, q))
+    return ((t << 33) * q + RATE * p) // (2 * RATE * p) % (1 << 32)
+
+
+def mix_in_s16(x16, tune_hz: int, p: int, q: int, n0: int = 0) -> np.ndarray:
+    """mix_s16 at the input rate 1536000 p / q: x16 are samples at that rate, the first of them INPUT sample n0 of its stream."""
+    return _mix(x16, inc_in(tune_hz, p, q), n0)
 
 
 def taps10() -> np.ndarray:
