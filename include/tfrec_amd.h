@@ -326,6 +326,39 @@ int tfrec_amd_input_bytes(tfrec_amd_ctx *ctx, int n_blocks, size_t *bytes_per_st
  * be NULL with cap 0 (only T, or only the verdict, is wanted).  Needs no context and no GPU.  TFREC_AMD_E_INVAL: a rate outside
  * the rules above or refused by them, or cap too small. */
 int tfrec_amd_resample_taps(int32_t rate_p, int32_t rate_q, int32_t *taps, int cap, int *n_taps_per_phase);
+/* Sample formats: a context whose input rows are not the RTL-SDR's offset-binary u8 but what other recorders write --
+ * signed int8 (hackrf_transfer), int16 (Airspy, SDRplay, USRP, rx_sdr) or float32 (GNU Radio, SDR++, GQRX, SigMF cf32_le) --, at
+ * any rate tfrec_amd_create_rate accepts or at the base rate 1/1 (1.536 MS/s).  A format maps one stored component (I or Q,
+ * little-endian, interleaved I, Q) to x, the int16 value every stage is defined on, -8192 <= x <= 8191; full scale maps to full
+ * scale, so the trigger threshold and the auto threshold keep their meaning:
+ *     format                bytes per complex sample   x
+ *     TFREC_AMD_FMT_U8  0   2                          (u8 - 128) << 6   (as always)
+ *     TFREC_AMD_FMT_S8  1   2                          s8 << 6           (the u8 value of byte ^ 0x80)
+ *     TFREC_AMD_FMT_S16 2   4                          s16 >> 2, arithmetic shift
+ *     TFREC_AMD_FMT_F32 3   8                          v = f * 8192 in fp32 (exact unless it overflows); x = clamp(rint(v), -8192, 8191),
+ *                                                      rint ties to even; NaN gives 0; +-inf and overflow clamp
+ * Everything after x is the text above: the input-rate tune's mixer acts on x at the input rate, the resampling stage
+ * y0[m] = int16( sum_{n<T} ( x'[i0 - (T-1) + n] * h[phi][n] ) >> 16 ) follows, then tfrec_amd_tune_streams and process_iq on int16
+ * input.  The history before a start or restart is x = 0.  The no-wrap arguments of the resampling stage and of the input-rate
+ * tune hold unchanged, because |x| <= 8192 as for u8.  At 1/1 no resampler runs and no delay is introduced: stage 0 is x itself,
+ * and an S8 context on bytes ^ 0x80 equals a tfrec_amd_create context on the bytes, bit for bit.  Pinned by tfrec_amd/formats.py
+ * (to_x) ahead of resample.py (resample_x16) and tune.py (mix_in_s16).
+ *   - TFREC_AMD_FMT_U8 IS tfrec_amd_create_rate, or tfrec_amd_create at 1/1: the same kernels, memory and behaviour.
+ *   - Refused with TFREC_AMD_E_INVAL: an unknown format; TFREC_AMD_F_INPUT_10X with a format other than U8; a rate that is neither
+ *     1/1 nor accepted by tfrec_amd_create_rate.
+ *   - Rows: tfrec_amd_input_bytes returns n_in * bytes per complex sample, and tfrec_amd_submit_device / _host take that many bytes
+ *     per row (submit_host's staging buffer grows with it).  The 16-byte alignment rules for base and stride are unchanged -- n_in
+ *     is a multiple of 8 for every permitted submit, so every row size is a 16-byte multiple --, and so is the block-count rule.
+ *   - Everything that works on a rate context works: reset, configure, tfrec_amd_tune_streams, tfrec_amd_map_streams,
+ *     tfrec_amd_tune_streams_input, both layouts, _SERIAL_CHAINS, _BITS, _ALL_FLUSHES, _TIMING; tfrec_amd_read_stage0 returns y0 (at
+ *     1/1: x); tfrec_amd_get_memory counts what the context holds.  At 1/1 the input-rate tune returns TFREC_AMD_E_INVAL, as on a
+ *     tfrec_amd_create context (the tune there is tfrec_amd_tune_streams); tfrec_amd_tune_streams_wide returns TFREC_AMD_E_INVAL, as
+ *     on any rate context.
+ * Contexts made by tfrec_amd_create, tfrec_amd_create_rate or with TFREC_AMD_F_INPUT_10X launch the kernels they launched before. */
+enum { TFREC_AMD_FMT_U8 = 0, TFREC_AMD_FMT_S8 = 1, TFREC_AMD_FMT_S16 = 2, TFREC_AMD_FMT_F32 = 3 };
+int tfrec_amd_create_format(const tfrec_amd_config *cfg, int32_t format, int32_t rate_p, int32_t rate_q, tfrec_amd_ctx **out);
+/* The context's input format (TFREC_AMD_FMT_U8 for every context of the older constructors). */
+int tfrec_amd_get_input_format(tfrec_amd_ctx *ctx, int32_t *format);
 
 /* Wait for submitted work. */
 int tfrec_amd_sync(tfrec_amd_ctx *ctx);

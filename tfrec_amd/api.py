@@ -100,7 +100,7 @@ EXPORTS = (
     "tfrec_amd_configure_streams", "tfrec_amd_get_stream_config", "tfrec_amd_tune_streams", "tfrec_amd_get_stream_tune",
     "tfrec_amd_map_streams", "tfrec_amd_get_stream_input", "tfrec_amd_tune_streams_wide", "tfrec_amd_get_stream_tune_wide",
     "tfrec_amd_create_rate", "tfrec_amd_get_input_rate", "tfrec_amd_input_bytes", "tfrec_amd_resample_taps",
-    "tfrec_amd_tune_streams_input", "tfrec_amd_get_stream_tune_input",
+    "tfrec_amd_tune_streams_input", "tfrec_amd_get_stream_tune_input", "tfrec_amd_create_format", "tfrec_amd_get_input_format",
 )
 
 _libs = {}
@@ -173,6 +173,8 @@ def load_library(build: bool = True, experiments: bool = False):
     L.tfrec_amd_get_input_rate.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.tfrec_amd_input_bytes.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]
     L.tfrec_amd_resample_taps.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.tfrec_amd_create_format.argtypes = [C.POINTER(Config), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.tfrec_amd_get_input_format.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.tfrec_amd_fifo_depth.restype = C.c_int
     if L.tfrec_amd_fifo_depth() != FIFO_DEPTH:
         raise RuntimeError("libtfrec_amd.so was built with FIFO depth %d, this binding expects %d" % (
@@ -215,7 +217,7 @@ class Receiver:
     def __init__(self, n_streams: int, types_mask: int = 0x2F, thresh: int = 500, filter_type: int = 0,
                  device: int = 0, max_blocks: int = 48, max_events: int | None = None, all_flushes: bool = False,
                  timing: bool = False, serial_chains: bool = False, input_10x: bool = False, bits: bool = False,
-                 experiments: bool = False, input_rate=None):
+                 experiments: bool = False, input_rate=None, input_format=None):
         # experiments=True: the build that reads the TFREC_AMD_* knobs / test hooks from the environment (csrc/knobs.h);
         # the default is the product library, which has none
         self.L = load_library(experiments=experiments)
@@ -229,7 +231,24 @@ class Receiver:
         self.input_rate = (10, 1) if input_10x else (1, 1)
         self.cfg = Config(n_streams, types_mask, thresh, filter_type, device, max_blocks, max_events, flags)
         self.h = C.c_void_p()
-        if input_rate is None:
+        # input_format="s8" | "s16" | "f32" (or a TFREC_AMD_FMT_* number; "u8", the default, is the context as it always was): what
+        # the input rows hold (tfrec_amd_create_format, formats.py), at input_rate or -- without one -- at 1.536 MS/s.  Rows stay
+        # uint8 arrays or tensors, of input_bytes(n_blocks) bytes.
+        self.input_format = "u8"
+        if input_format is not None:
+            from . import formats
+
+            p, q = (int(v) for v in (input_rate if input_rate is not None else (1, 1)))
+            fmt = formats.FORMATS.get(input_format, input_format) if isinstance(input_format, str) else input_format
+            if not isinstance(fmt, int) or not all(-2 ** 31 <= v < 2 ** 31 for v in (p, q, fmt)):
+                raise TfrecAmdError(E_INVAL, "input_format or input_rate: unknown name or outside int32")
+            _check(self.L, self.L.tfrec_amd_create_format(C.byref(self.cfg), fmt, p, q, C.byref(self.h)))
+            if not input_10x:
+                self.input_rate = (p, q)
+            got = C.c_int32(-1)
+            _check(self.L, self.L.tfrec_amd_get_input_format(self.h, C.byref(got)))
+            self.input_format = formats.NAMES[got.value]
+        elif input_rate is None:
             _check(self.L, self.L.tfrec_amd_create(C.byref(self.cfg), C.byref(self.h)))
         else:
             p, q = (int(v) for v in input_rate)
@@ -237,7 +256,7 @@ class Receiver:
                 raise TfrecAmdError(E_INVAL, "input_rate outside int32")
             _check(self.L, self.L.tfrec_amd_create_rate(C.byref(self.cfg), p, q, C.byref(self.h)))
             self.input_rate = (p, q)
-        bb = Fraction(BLOCK_BYTES * self.input_rate[0], self.input_rate[1])
+        bb = Fraction(BLOCK_BYTES * self.input_rate[0] * {"s16": 2, "f32": 4}.get(self.input_format, 1), self.input_rate[1])
         self.block_bytes = int(bb) if bb.denominator == 1 else bb
         self.n_streams = n_streams
         self.max_events = max_events

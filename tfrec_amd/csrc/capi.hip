@@ -17,6 +17,11 @@ hipError_t launch_decim10(hipStream_t st, const uint8_t *iq, size_t stride, int 
 hipError_t launch_resample(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, int p, int q, int t,
 			   const float *taps, const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride,
 			   const uint4 *chan, bool tuned);
+hipError_t launch_resample_fmt(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, int p, int q, int t,
+			       const float *taps, const uint32_t *tail_in, uint32_t *tail_out, uint32_t *out, size_t out_stride,
+			       const uint4 *chan, bool tuned);
+hipError_t launch_ingest(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, uint32_t *out,
+			 size_t out_stride, const uint4 *chan);
 hipError_t launch_frontend(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks,
 			   const uint8_t *tail_in, uint8_t *tail_out, uint32_t *dec, size_t dec_stride,
 			   unsigned long long *mask, size_t mask_stride, uint32_t *prevdec, int thresh, const FrontTapsCfg &taps,
@@ -44,6 +49,7 @@ constexpr int kTuneLimit = 768000;  // |tune_hz| < half the 1.536 MS/s sample ra
 constexpr int kTuneWideLimit = 7680000;  // tfrec_amd_tune_streams_wide: half the 15.36 MS/s input rate
 constexpr int kRateQMax = 64;  // tfrec_amd_create_rate: the largest Q
 constexpr int kRateTail = 128;  // ... and its raw history per stream in bytes (resample_kernel: kRsTail)
+constexpr int kFmtTail = 256;   // tfrec_amd_create_format: the history per stream in bytes, 64 complex samples of x (formats.h: kFmtTailDw)
 
 // Buffer / table sets = submits that may be in flight (the FIFO depth): front end of submit k+2, biquad stage of
 // k+1 and slicer stage of k run beside each other in the deep layout
@@ -167,6 +173,12 @@ struct tfrec_amd_ctx {
 	bool resamp = false, in16 = false;
 	float *d_rtaps = nullptr;
 	uint8_t *d_tailR[2] = {};
+	// tfrec_amd_create_format: fmt is the TFREC_AMD_FMT_* of the input rows, 0 (U8) in every context of the older
+	// constructors.  A rate context with another format runs resample_fmt_kernel from a history of canonical x (d_tailX, in place
+	// of d_tailR); at the base rate (ingest: rate 1/1, no resampler) ingest_kernel converts the rows into d_in16.
+	int32_t fmt = TFREC_AMD_FMT_U8;
+	bool ingest = false;
+	uint32_t *d_tailX[2] = {};
 	// ---- window-parallel pipeline (make_window_state).  One set per submit in flight, like the front-end outputs: the window
 	// scan and the biquads of submit k+1 fill theirs while the slicers of submit k still read the other
 	int16_t *d_ld16[kSets] = {};   // [chains][m_max] tfa2-family biquad outputs
@@ -254,6 +266,7 @@ struct StreamReset {
 	int32_t tail_bytes, tail_fill;
 	uint8_t *tail10;    // TFREC_AMD_F_INPUT_10X: the 10:1 stage's raw history (112 bytes per stream of 0x80), or nullptr
 	uint8_t *tailR;     // tfrec_amd_create_rate: the resampling stage's raw history (kRateTail bytes per stream of 0x80), or nullptr
+	uint32_t *tailX;    // tfrec_amd_create_format: its history of x (kFmtTail bytes per stream of zero), or nullptr
 	FskState *fsk;      // auto threshold
 	const StreamCfg *cfgs;  // [n_list] the listed streams' settings from this submit on ...
 	StreamCfg *scfg;        // ... written over their entries here
@@ -282,6 +295,9 @@ __global__ __launch_bounds__(64) void stream_reset_kernel(StreamReset R)
 	if (R.tailR)
 		for (int i = ln; i < kRateTail; i += 64)
 			R.tailR[(size_t)s * kRateTail + i] = 0x80;
+	if (R.tailX)
+		for (int i = ln; i < kFmtTail / 4; i += 64)
+			R.tailX[(size_t)s * (kFmtTail / 4) + i] = 0u;
 	constexpr int kChunks = (int)(sizeof(ChainState) / 16);
 	const uint4 *init = reinterpret_cast<const uint4 *>(R.chain_init);
 	for (int a = 0; a < R.n_active; a++)
@@ -670,7 +686,7 @@ static int make_front_buffers(tfrec_amd_ctx *c)
 		TRY(own_device(c, c->d_prevdec[k], n * sizeof(uint32_t)));
 	}
 	c->in10x = (cfg.flags & TFREC_AMD_F_INPUT_10X) != 0;
-	c->in16 = c->in10x || c->resamp;
+	c->in16 = c->in10x || c->resamp || c->ingest;
 	const size_t tail_bytes = c->in16 ? 2 * (size_t)kTailBytes : (size_t)kTailBytes;  // int16 history is twice as wide
 	// zero FIR history == u8 value 128 (decimate::decimate zeroes hist0, dsp_stuff.cpp:145-152); int16 history of the 10x
 	// path: zero, raw u8 history of its 10:1 stage (or of the resampling stage): 128
@@ -687,11 +703,21 @@ static int make_front_buffers(tfrec_amd_ctx *c)
 		for (int k = 0; k < 2; k++)
 			HIPCHK(hipMemset(c->d_tail10[k], 0x80, n * 112));
 	}
+	if (c->ingest) {  // the base rate in another format: stage 0 is the converted input
+		c->in16_stride = 4 * m_max;
+		for (int k = 0; k < kSets; k++)
+			TRY(own_device(c, c->d_in16[k], n * c->in16_stride * sizeof(uint32_t)));
+	}
 	if (c->resamp) {
 		c->in16_stride = 4 * m_max;
 		for (int k = 0; k < kSets; k++)
 			TRY(own_device(c, c->d_in16[k], n * c->in16_stride * sizeof(uint32_t)));
 		for (int k = 0; k < 2; k++) {
+			if (c->fmt != TFREC_AMD_FMT_U8) {  // the history of x: silence is zero
+				TRY(own_device(c, c->d_tailX[k], n * kFmtTail));
+				HIPCHK(hipMemset(c->d_tailX[k], 0, n * kFmtTail));
+				continue;
+			}
 			TRY(own_device(c, c->d_tailR[k], n * kRateTail));
 			HIPCHK(hipMemset(c->d_tailR[k], 0x80, n * kRateTail));
 		}
@@ -1151,6 +1177,52 @@ int tfrec_amd_create_rate(const tfrec_amd_config *cfg, int32_t rate_p, int32_t r
 	return TFREC_AMD_OK;
 }
 
+int tfrec_amd_create_format(const tfrec_amd_config *cfg, int32_t format, int32_t rate_p, int32_t rate_q, tfrec_amd_ctx **out)
+{
+	if (!cfg || !out)
+		return TFREC_AMD_E_INVAL;
+	*out = nullptr;
+	const bool base = rate_p == 1 && rate_q == 1;
+	if (format < TFREC_AMD_FMT_U8 || format > TFREC_AMD_FMT_F32) {
+		snprintf(g_err, sizeof(g_err), "unknown input format %d", (int)format);
+		return TFREC_AMD_E_INVAL;
+	}
+	if (format == TFREC_AMD_FMT_U8)  // exactly the older constructors
+		return base ? tfrec_amd_create(cfg, out) : tfrec_amd_create_rate(cfg, rate_p, rate_q, out);
+	if (cfg->flags & TFREC_AMD_F_INPUT_10X) {
+		snprintf(g_err, sizeof(g_err), "the 15.36 MS/s input flag takes u8 input only");
+		return TFREC_AMD_E_INVAL;
+	}
+	if (!base)
+		TRY(tfrec_amd_resample_taps(rate_p, rate_q, nullptr, 0, nullptr));
+	TRY(validate(cfg));
+	HIPCHK(hipSetDevice(cfg->device));
+	tfrec_amd_ctx *c = new (std::nothrow) tfrec_amd_ctx();
+	if (!c)
+		return TFREC_AMD_E_NOMEM;
+	c->cfg = *cfg;
+	c->fmt = format;
+	c->rate_p = rate_p;
+	c->rate_q = rate_q;
+	c->resamp = !base;
+	c->ingest = base;
+	const int rc = init_context(c);
+	if (rc != TFREC_AMD_OK) {
+		tfrec_amd_destroy(c);
+		return rc;
+	}
+	*out = c;
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_get_input_format(tfrec_amd_ctx *c, int32_t *format)
+{
+	if (!c || !format)
+		return TFREC_AMD_E_INVAL;
+	*format = c->fmt;
+	return TFREC_AMD_OK;
+}
+
 int tfrec_amd_get_input_rate(tfrec_amd_ctx *c, int32_t *p, int32_t *q)
 {
 	if (!c || !p || !q)
@@ -1187,7 +1259,8 @@ static int launch_resets(tfrec_amd_ctx *c, int set)
 	R.tail_bytes = c->in16 ? 2 * kTailBytes : kTailBytes;
 	R.tail_fill = c->in16 ? 0 : 0x80;  // as make_front_buffers: int16 zero, or u8 128
 	R.tail10 = c->in10x ? c->d_tail10[c->tail_sel] : nullptr;
-	R.tailR = c->resamp ? c->d_tailR[c->tail_sel] : nullptr;
+	R.tailR = (c->resamp && c->fmt == TFREC_AMD_FMT_U8) ? c->d_tailR[c->tail_sel] : nullptr;
+	R.tailX = (c->resamp && c->fmt != TFREC_AMD_FMT_U8) ? c->d_tailX[c->tail_sel] : nullptr;
 	R.fsk = c->d_fsk;
 	R.cfgs = c->d_rcfg[set];
 	R.scfg = c->d_scfg;
@@ -1338,8 +1411,10 @@ static int rows_in_use(const tfrec_amd_ctx *c)
 	return 1 + *std::max_element(c->row.begin(), c->row.end());
 }
 
-// Bytes of one input row of a submit of n_blocks blocks: n_blocks * 32768 * P / Q complex u8 samples, which must be a whole
-// number (any n_blocks when Q is a power of two, otherwise a multiple of Q's odd part).
+// Bytes of one input row of a submit of n_blocks blocks: n_blocks * 32768 * P / Q complex samples, which must be a whole
+// number (any n_blocks when Q is a power of two, otherwise a multiple of Q's odd part), of 2, 4 or 8 bytes each.
+static size_t sample_bytes(int32_t fmt) { return fmt == TFREC_AMD_FMT_F32 ? 8 : fmt == TFREC_AMD_FMT_S16 ? 4 : 2; }
+
 static int input_bytes(const tfrec_amd_ctx *c, int n_blocks, size_t *bytes)
 {
 	if (n_blocks < 1)
@@ -1350,7 +1425,7 @@ static int input_bytes(const tfrec_amd_ctx *c, int n_blocks, size_t *bytes)
 		snprintf(g_err, sizeof(g_err), "%d blocks at the input rate %lld/%lld are not a whole number of input samples", n_blocks, p, q);
 		return TFREC_AMD_E_INVAL;
 	}
-	*bytes = (size_t)(num / q) * 2;
+	*bytes = (size_t)(num / q) * sample_bytes(c->fmt);
 	return TFREC_AMD_OK;
 }
 
@@ -1401,7 +1476,19 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		fin = (const uint8_t *)c->d_in16[set];
 		fstride = c->in16_stride * sizeof(uint32_t);
 	}
-	if (c->resamp) {  // 1536000 P / Q S/s u8 -> 1.536 MS/s int16 pairs, then the same cascade on int16 input
+	if (c->ingest) {  // 1.536 MS/s in another format -> x as int16 pairs, then the same cascade on int16 input
+		HIPCHK(launch_ingest(fs, c->fmt, (const uint8_t *)d_iq, stride, c->cfg.n_streams, n_blocks, c->d_in16[set], c->in16_stride,
+				     chan10 ? c->d_chan[set] : nullptr));
+		fin = (const uint8_t *)c->d_in16[set];
+		fstride = c->in16_stride * sizeof(uint32_t);
+	}
+	if (c->resamp && c->fmt != TFREC_AMD_FMT_U8) {  // 1536000 P / Q S/s in another format: the format-aware resampling stage
+		HIPCHK(launch_resample_fmt(fs, c->fmt, (const uint8_t *)d_iq, stride, c->cfg.n_streams, n_blocks, c->rate_p, c->rate_q,
+					   c->rate_t, c->d_rtaps, c->d_tailX[c->tail_sel], c->d_tailX[c->tail_sel ^ 1], c->d_in16[set],
+					   c->in16_stride, chan10 ? c->d_chan[set] : nullptr, c->n_wide != 0));
+		fin = (const uint8_t *)c->d_in16[set];
+		fstride = c->in16_stride * sizeof(uint32_t);
+	} else if (c->resamp) {  // 1536000 P / Q S/s u8 -> 1.536 MS/s int16 pairs, then the same cascade on int16 input
 		HIPCHK(launch_resample(fs, (const uint8_t *)d_iq, stride, c->cfg.n_streams, n_blocks, c->rate_p, c->rate_q, c->rate_t,
 				       c->d_rtaps, c->d_tailR[c->tail_sel], c->d_tailR[c->tail_sel ^ 1], c->d_in16[set], c->in16_stride,
 				       chan10 ? c->d_chan[set] : nullptr, c->n_wide != 0));

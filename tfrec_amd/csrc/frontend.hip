@@ -856,5 +856,6 @@ hipError_t launch_fmdev(hipStream_t st, const uint32_t *dec, size_t dec_stride, 
 }
 
 #include "resample.h"  // resample_kernel, launch_resample
+#include "formats.h"   // resample_fmt_kernel, ingest_kernel and their launchers
 
 }  // namespace tfrec

@@ -28,7 +28,7 @@ void tfrec_handler_args(const sensordata_t &d, sensor_e dec_type, char *out, siz
 gpu_engine::gpu_engine(const std::vector<std::string> &dumpfiles, int _types, int _thresh, int _filter, int _dbg,
 		       const std::vector<int> &_devices, int blocks_per_submit, const std::vector<file_settings> &per_file)
 	: files(dumpfiles), settings(per_file), types(_types), thresh(_thresh), filter(_filter), dbg(_dbg), bps(blocks_per_submit),
-	  devices(_devices), n_telegrams(0), sink(NULL), psink(NULL), out_mode(0), bits_replay(false), slots(0), wide(false), rate_p(1), rate_q(1), unit(1)
+	  devices(_devices), n_telegrams(0), sink(NULL), psink(NULL), out_mode(0), bits_replay(false), slots(0), wide(false), rate_p(1), rate_q(1), unit(1), fmt(TFREC_AMD_FMT_U8)
 {
 	if (devices.empty())
 		devices.push_back(0);
@@ -227,6 +227,7 @@ struct device_worker {
 	bool wide;          // -x: 15.36 MS/s dumps (TFREC_AMD_F_INPUT_10X in flags), the files' tunes are wide tunes
 	bool share;         // one stream per file for the whole job (no -n): a path given several times is read once, into one row
 	int rate_p, rate_q;  // -r: the input rate as p / q of 1.536 MS/s (1 / 1: none)
+	int fmt;             // -F: TFREC_AMD_FMT_* of the files (U8: none)
 	size_t block_bytes;  // bytes of one block of a file: 65536 p / q (x `unit` blocks when q does not divide it), 655360 with -x
 	int unit;            // blocks a block_bytes piece holds: every batch carries a multiple of it
 	int rc;
@@ -237,7 +238,7 @@ struct device_worker {
 	bool done;
 	std::thread th;
 
-	device_worker() : files(NULL), s0(0), s1(0), device(0), types(0), thresh(0), filter(0), bps(1), flags(0), nslots(0), file_blocks(NULL), wide(false), share(false), rate_p(1), rate_q(1), block_bytes(TFREC_AMD_BLOCK_BYTES), unit(1), rc(0), abort(NULL), done(false) {}
+	device_worker() : files(NULL), s0(0), s1(0), device(0), types(0), thresh(0), filter(0), bps(1), flags(0), nslots(0), file_blocks(NULL), wide(false), share(false), rate_p(1), rate_q(1), fmt(TFREC_AMD_FMT_U8), block_bytes(TFREC_AMD_BLOCK_BYTES), unit(1), rc(0), abort(NULL), done(false) {}
 
 	void push(std::vector<tfrec_amd_event> &&ev)
 	{
@@ -293,7 +294,9 @@ struct device_worker {
 		cfg.max_events = (int32_t)std::max<size_t>(4096, n * (size_t)bps * ((flags & TFREC_AMD_F_BITS) ? 256 : 64));
 		cfg.flags = flags;
 		tfrec_amd_ctx *ctx = NULL;
-		int r = (rate_p != 1 || rate_q != 1) ? tfrec_amd_create_rate(&cfg, rate_p, rate_q, &ctx) : tfrec_amd_create(&cfg, &ctx);
+		int r = fmt != TFREC_AMD_FMT_U8	       ? tfrec_amd_create_format(&cfg, fmt, rate_p, rate_q, &ctx)
+			: (rate_p != 1 || rate_q != 1) ? tfrec_amd_create_rate(&cfg, rate_p, rate_q, &ctx)
+						       : tfrec_amd_create(&cfg, &ctx);
 		if (r) {
 			fprintf(stderr, "tfrec_amd_create (device %d): %s (%s)\n", device, tfrec_amd_strerror(r), tfrec_amd_last_error());
 			return r;
@@ -384,7 +387,8 @@ struct device_worker {
 							}
 						}
 					}
-					memset(dst + got, 0x80, want - got);  // a shorter file is padded with silence (its events are cut by the engine)
+					// a shorter file is padded with silence (its events are cut by the engine): u8 128, zero in every other format
+					memset(dst + got, fmt != TFREC_AMD_FMT_U8 ? 0 : 0x80, want - got);
 				}
 				{
 					std::lock_guard<std::mutex> lk(rmu);
@@ -512,8 +516,10 @@ int gpu_engine::run()
 	std::vector<size_t> file_blocks(n, 0);
 	stream_samples.assign(n, 0);
 	// bytes of a piece of `unit` blocks of a file (unit = 1 without -r): 65536 p / q x unit is a whole number
-	// (q is unit times a power of two <= 64)
-	const size_t block_bytes = wide ? (size_t)TFREC_AMD_BLOCK_BYTES_10X : (size_t)TFREC_AMD_BLOCK_BYTES * rate_p * unit / rate_q;
+	// (q is unit times a power of two <= 64); -F: times the format's bytes per complex sample / 2
+	const size_t sample_bytes = fmt == TFREC_AMD_FMT_F32 ? 8 : fmt == TFREC_AMD_FMT_S16 ? 4 : 2;
+	const size_t block_bytes =
+		wide ? (size_t)TFREC_AMD_BLOCK_BYTES_10X : (size_t)TFREC_AMD_BLOCK_BYTES * rate_p * unit / rate_q * sample_bytes / 2;
 	for (size_t s = 0; s < n; s++) {
 		FILE *f = fopen(files[s].c_str(), "rb");
 		if (!f) {
@@ -524,6 +530,8 @@ int gpu_engine::run()
 		// trailing partial block dropped, engine.cpp:72-76 (-r: a trailing partial piece of `unit` blocks)
 		const size_t blocks = (size_t)ftell(f) / block_bytes * (size_t)unit;
 		fclose(f);
+		if (dbg > 0 && fmt != TFREC_AMD_FMT_U8)  // -D with -F: how the file is cut
+			fprintf(stderr, "%s: %zu blocks, %zu bytes per %d\n", files[s].c_str(), blocks, block_bytes, unit);
 		stream_samples[s] = (long long)blocks * TFREC_AMD_BLOCK_DEC;
 		file_blocks[s] = blocks;
 	}
@@ -549,6 +557,7 @@ int gpu_engine::run()
 		w.share = slots <= 0;
 		w.rate_p = rate_p;
 		w.rate_q = rate_q;
+		w.fmt = fmt;
 		w.block_bytes = block_bytes;
 		w.unit = unit;
 		w.nslots = w.s1 - w.s0;

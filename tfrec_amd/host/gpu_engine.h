@@ -128,6 +128,10 @@ public:
 	// shared paths, tunes and settings -- is as without it, and a file's tune beyond +-767 kHz (up to half the rate) becomes the
 	// input-rate tune ahead of the resampler (tfrec_amd_tune_streams_input).  Excludes set_wide.
 	void set_rate(int p, int q);
+	// -F: the dump files hold TFREC_AMD_FMT_* samples instead of u8 (tfrec_amd_create_format), at the rate of
+	// set_rate or -- without one -- at 1.536 MS/s.  A block of a file is 65536 p / q * bytes per complex sample / 2 bytes, and a
+	// shorter file is padded with the format's silence (zero); everything else is as with u8.  Excludes set_wide.
+	void set_format(int format) { fmt = format; }
 	// returns 0 on success, a TFREC_AMD_E_* code otherwise
 	int run();
 	// decoders of stream s in slot order (NULL for slots not registered)
@@ -150,6 +154,7 @@ private:
 	int slots;
 	bool wide;
 	int rate_p, rate_q, unit;  // set_rate (1, 1, 1: none)
+	int fmt;                   // set_format (TFREC_AMD_FMT_U8: none)
 };
 
 #endif

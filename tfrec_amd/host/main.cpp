@@ -1,6 +1,6 @@
 // tfrec_amd/host/main.cpp -- tfrec_gpu: the reference's file-replay CLI on the GPU path.
 //
-//   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-q] [-D] [-B] [-d device[,device...]] [-b blocks]
+//   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-q] [-D] [-B] [-d device[,device...]] [-b blocks]
 //             [-n streams] [-e handler | -E handler] [-m mode] [-p settings] -L dump.iq [[-p settings] -L more.iq ...]
 //   tfrec_gpu [-T hexmask] -X telegrams.txt
 //
@@ -33,6 +33,11 @@
 // rate: within +-767 kHz the shift acts behind the resampler (tfrec_amd_tune_streams), a larger one ahead of it, at the input
 // rate (tfrec_amd_tune_streams_input).  A path given to several -L is read once, as without -r.  A submit must
 // hold a whole number of input samples: -b is rounded up to the next multiple of Q's odd part.  Excludes -x.
+// -F u8|s8|s16|f32 (not in the reference; also cu8, cs8, cs16, cf32): what the -L files hold -- rtl_sdr's offset-binary u8 (the
+// default), hackrf_transfer's signed int8, the int16 of Airspy, SDRplay, USRP and rx_sdr, or the float32 of GNU Radio, SDR++, GQRX
+// and SigMF cf32_le; little-endian, interleaved I, Q, without a header (tfrec_amd_create_format).  With -r the files
+// are at that rate, without it at 1.536 MS/s.  A block of a file is 65536 * P / Q * bytes per complex sample / 2 bytes; -b, -n, -d,
+// shared paths and -f / -c / -p f= are as with -r.  A format other than u8 excludes -x.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -146,8 +151,9 @@ int main(int argc, char **argv)
 	bool have_spec = false;
 	long freq = -1, center = 868250;  // -f (unset: the dumps' own frequency), -c: kHz
 	long rate = 0;  // -r: Hz (0: 1536000)
+	int format = TFREC_AMD_FMT_U8;  // -F
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:qDBd:b:n:L:X:e:E:m:p:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:h")) != -1) {
 		switch (c) {
 		case 'T': types = (int)strtol(optarg, NULL, 16); break;
 		case 't': thresh = atoi(optarg); break;
@@ -165,6 +171,22 @@ int main(int argc, char **argv)
 			rate = strtol(optarg, &end, 10);
 			if (end == optarg || *end || rate <= 0 || rate > 100000000L) {
 				fprintf(stderr, "tfrec_gpu: bad -r '%s': want the dumps' sample rate in Hz\n", optarg);
+				return 1;
+			}
+			break;
+		}
+		case 'F': {
+			static const struct {
+				const char *name;
+				int fmt;
+			} names[] = { { "u8", TFREC_AMD_FMT_U8 }, { "cu8", TFREC_AMD_FMT_U8 }, { "s8", TFREC_AMD_FMT_S8 }, { "cs8", TFREC_AMD_FMT_S8 },
+				      { "s16", TFREC_AMD_FMT_S16 }, { "cs16", TFREC_AMD_FMT_S16 }, { "f32", TFREC_AMD_FMT_F32 }, { "cf32", TFREC_AMD_FMT_F32 } };
+			format = -1;
+			for (const auto &nm : names)
+				if (!strcmp(optarg, nm.name))
+					format = nm.fmt;
+			if (format < 0) {
+				fprintf(stderr, "tfrec_gpu: bad -F '%s': want u8, s8, s16 or f32 (cu8, cs8, cs16, cf32)\n", optarg);
 				return 1;
 			}
 			break;
@@ -195,7 +217,7 @@ int main(int argc, char **argv)
 		case 'E': exec = optarg; batched = true; break;
 		case 'm': mode = atoi(optarg); break;
 		default:
-			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-p settings] -L dump [[-p settings] -L dump ...] | -X hexfile\n"
+			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-p settings] -L dump [[-p settings] -L dump ...] | -X hexfile\n"
 					"  -f kHz      receive frequency (default: the dumps' own, -c)\n"
 					"  -c kHz      frequency the dumps were recorded at (default 868250); -f within 767 kHz of it\n"
 					"  -x          the dumps are 15.36 MS/s u8 dumps (10x the rate); -f within 7679 kHz of -c, shifted ahead of the 10:1 stage\n"
@@ -203,6 +225,8 @@ int main(int argc, char **argv)
 					"  -r Hz       sample rate of the dumps (default 1536000), e.g. 2048000 or 2400000: resampled on the GPU; -b is rounded up\n"
 					"              to a block count that holds a whole number of input samples; -f less than half the rate from -c (beyond\n"
 					"              767 kHz it is shifted ahead of the resampler); not with -x\n"
+					"  -F format   what the dumps hold: u8 (default), s8, s16 or f32 (cu8, cs8, cs16, cf32): little-endian interleaved I, Q without a\n"
+					"              header, at the rate of -r or at 1536000; a format other than u8 not with -x\n"
 					"  -n streams  at most this many streams per device: the -L files queue for them in order\n"
 					"  -p T=<hex>,t=<n>,W=<0|1>,f=<kHz>  -T / -t / -W / -f of the -L files that follow, up to the next -p (fields left out: the global ones)\n");
 			return c == 'h' ? 0 : 1;
@@ -231,6 +255,10 @@ int main(int argc, char **argv)
 	int rate_p = 1, rate_q = 1;
 	if (rate && wide) {
 		fprintf(stderr, "tfrec_gpu: -r and -x exclude each other (-x is the fixed rate 15360000)\n");
+		return 1;
+	}
+	if (format != TFREC_AMD_FMT_U8 && wide) {
+		fprintf(stderr, "tfrec_gpu: -F and -x exclude each other (15.36 MS/s dumps are u8)\n");
 		return 1;
 	}
 	if (rate && rate != 1536000) {
@@ -295,6 +323,7 @@ int main(int argc, char **argv)
 	e.set_wide(wide);
 	if (rate_p != 1 || rate_q != 1)
 		e.set_rate(rate_p, rate_q);
+	e.set_format(format);
 	int rc = e.run();
 	fflush(stdout);
 	return rc ? 2 : 0;
