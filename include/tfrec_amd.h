@@ -68,6 +68,8 @@ enum {
 				      seq = ordinal of the flush they precede, end_sample = the first sample of their trigger window (counted like a
 				      flush's), offset = the chunk's index: (end_sample, offset) is their order within that flush.
 				      Window-parallel pipeline only. */
+#define TFREC_AMD_F_LEVELS 32u       /* level meter: one tfrec_amd_level per stream and block of every submit (tfrec_amd_read_levels,
+				      below).  A context without it launches exactly what it launched before */
 #define TFREC_AMD_F_SERIAL_CHAINS 4u /* run the demodulators as one serial lane per (stream, slot) -- the simple
 				      GPU formulation kept as a cross-check of the window-parallel pipeline */
 
@@ -379,6 +381,43 @@ int tfrec_amd_drain_events(tfrec_amd_ctx *ctx, tfrec_amd_event *out, int cap, in
 
 /* Number of events of the oldest undrained submit (waits for it). */
 int tfrec_amd_pending_events(tfrec_amd_ctx *ctx, int *n);
+
+/* Level meter (TFREC_AMD_F_LEVELS): what a receiver saw, whether or not it decoded anything -- per stream s and per
+ * block b (TFREC_AMD_BLOCK_DEC decimated samples) of a submit one record of exact integers.  I, Q are the decimated int16 samples
+ * tfrec_amd_read_decimated returns; pwr = |I| + |Q| is fsk_demod::process's trigger quantity (fm_demod.cpp:45). */
+typedef struct {            /* 32 bytes */
+	uint64_t energy;        /* sum over the block's 8192 decimated samples of I*I + Q*Q  (<= 2^44) */
+	uint32_t pwr_sum;       /* sum of pwr (<= 2^29) */
+	int32_t  pwr_max;       /* largest pwr in the block */
+	int32_t  n_over;        /* samples with pwr > thresh (tfa1.cpp:147, tfa2.cpp:351, whb.cpp:636), thresh = the field below */
+	int32_t  triggered;     /* fm_demod.cpp:52: samples at which at least one registered demodulator of this stream returned non-zero */
+	int32_t  thresh;        /* the trigger threshold in force DURING this block */
+	int32_t  triggered_avg; /* fm_demod.cpp:58, after this block */
+} tfrec_amd_level;
+/*   triggered: a demodulator returns non-zero while its timeout counter runs -- set to its window W at every sample with
+ *     pwr > thresh, counted, then decremented (tfa1.cpp:147-164, tfa2.cpp:351-375, whb.cpp:636-657).  All demodulators of a stream
+ *     share the trigger test, so sample n counts iff some sample n' of this stream has n - W < n' <= n, pwr[n'] > the thresh in
+ *     force at n', and n' at or after the stream's start or last restart; W is the LARGEST window of the stream's own registered
+ *     demodulators: 400 for TFA_1, (int)(16 * 384000 / baud) for TFA_2 (356), TFA_3 (640) and TX22 (694), 512 for WHB.  A trigger
+ *     carries over block and submit boundaries.  The same quantity drives the auto threshold.
+ *   triggered_avg, thresh: the recurrence of fm_demod.cpp:58-73 from triggered_avg = 0, runs = 0 and thresh = the stream's setting
+ *     (500 in auto mode): per block runs++, triggered_avg = (31 * triggered_avg + triggered) / 32 -- in BOTH modes, as the reference
+ *     computes it unconditionally --, and in auto mode only, when runs % 4 == 0: triggered_avg >= 512 raises thresh by 2, else
+ *     triggered_avg <= 256 with thresh > 50 lowers it by 2.  On an auto stream the last record's thresh, stepped once more, is
+ *     what tfrec_amd_read_thresh returns.
+ *   A restart (reset, configure, tune, map, wide tune, input tune) returns the stream's level state to those starting values at
+ *     the cut, and no trigger is carried over it.  Results do not depend on how a stream is cut into submits.
+ *   Valid on every kind of context and in every mode (both layouts, _SERIAL_CHAINS, _BITS, _ALL_FLUSHES, _TIMING, _INPUT_10X, rate
+ *     and format contexts): the records are defined on the decimated samples and the final trigger mask alone.  The two kernels that
+ *     compute them run behind the front end on a low-priority stream of their own; the events do not depend on them.
+ *   Memory: n_streams * max_blocks * 32 bytes of device memory per FIFO slot (TFREC_AMD_FIFO_DEPTH of them) and 16 bytes per stream
+ *     of carried state; no page-locked host copy (the call below copies into `out`).  Pinned by tfrec_amd/levels.py.
+ * tfrec_amd_read_levels: the levels of the OLDEST undrained submit (waits for it, like tfrec_amd_pending_events; call it BEFORE
+ * tfrec_amd_drain_events pops that submit): out[s * n_blocks + b], n_streams * n_blocks records (cap: the room in `out`, in
+ * records); *n_blocks_out = that submit's n_blocks.
+ * Errors: a context without TFREC_AMD_F_LEVELS: TFREC_AMD_E_INVAL; nothing undrained: TFREC_AMD_E_STATE; cap too small or a NULL
+ * pointer: TFREC_AMD_E_INVAL, and nothing is written; a poisoned context: TFREC_AMD_E_STATE. */
+int tfrec_amd_read_levels(tfrec_amd_ctx *ctx, tfrec_amd_level *out, size_t cap, int *n_blocks_out);
 
 /* The dB value the reference demodulator passes to decoder::flush for this slot, computed with the
  * reference's host expressions (tfa1.cpp:180, tfa2.cpp:434, whb.cpp:696) including (int)(10*log10(0)). */

@@ -13,6 +13,7 @@ from fractions import Fraction
 import numpy as np
 
 from . import _build
+from .levels import LEVEL_DTYPE  # tfrec_amd_level
 
 BLOCK_BYTES = 65536
 BLOCK_DEC = 8192
@@ -25,6 +26,7 @@ F_TIMING = 2
 F_SERIAL_CHAINS = 4
 F_INPUT_10X = 8
 F_BITS = 16
+F_LEVELS = 32
 STATUS_BITS = 0x80
 
 E_OK, E_INVAL, E_NOMEM, E_HIP, E_OVERFLOW, E_STATE = 0, -1, -2, -3, -4, -5
@@ -101,6 +103,7 @@ EXPORTS = (
     "tfrec_amd_map_streams", "tfrec_amd_get_stream_input", "tfrec_amd_tune_streams_wide", "tfrec_amd_get_stream_tune_wide",
     "tfrec_amd_create_rate", "tfrec_amd_get_input_rate", "tfrec_amd_input_bytes", "tfrec_amd_resample_taps",
     "tfrec_amd_tune_streams_input", "tfrec_amd_get_stream_tune_input", "tfrec_amd_create_format", "tfrec_amd_get_input_format",
+    "tfrec_amd_read_levels",
 )
 
 _libs = {}
@@ -175,6 +178,7 @@ def load_library(build: bool = True, experiments: bool = False):
     L.tfrec_amd_resample_taps.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.tfrec_amd_create_format.argtypes = [C.POINTER(Config), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
     L.tfrec_amd_get_input_format.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    L.tfrec_amd_read_levels.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
     L.tfrec_amd_fifo_depth.restype = C.c_int
     if L.tfrec_amd_fifo_depth() != FIFO_DEPTH:
         raise RuntimeError("libtfrec_amd.so was built with FIFO depth %d, this binding expects %d" % (
@@ -217,14 +221,15 @@ class Receiver:
     def __init__(self, n_streams: int, types_mask: int = 0x2F, thresh: int = 500, filter_type: int = 0,
                  device: int = 0, max_blocks: int = 48, max_events: int | None = None, all_flushes: bool = False,
                  timing: bool = False, serial_chains: bool = False, input_10x: bool = False, bits: bool = False,
-                 experiments: bool = False, input_rate=None, input_format=None):
+                 experiments: bool = False, input_rate=None, input_format=None, levels: bool = False):
         # experiments=True: the build that reads the TFREC_AMD_* knobs / test hooks from the environment (csrc/knobs.h);
         # the default is the product library, which has none
         self.L = load_library(experiments=experiments)
         if max_events is None:
             max_events = max(4096, n_streams * max_blocks * 4 * (8 if all_flushes else 2))
         flags = ((F_ALL_FLUSHES if all_flushes else 0) | (F_TIMING if timing else 0)
-                 | (F_SERIAL_CHAINS if serial_chains else 0) | (F_INPUT_10X if input_10x else 0) | (F_BITS if bits else 0))
+                 | (F_SERIAL_CHAINS if serial_chains else 0) | (F_INPUT_10X if input_10x else 0) | (F_BITS if bits else 0)
+                 | (F_LEVELS if levels else 0))  # levels: the level meter (read_levels; levels.py)
         # input_rate=(P, Q): u8 IQ at 1536000 P / Q samples per second, resampled on the GPU (tfrec_amd_create_rate, resample.py).
         # block_bytes: the bytes of one block of one input row -- a fraction when Q does not divide 65536 P; input_bytes(n_blocks)
         # is what a submit takes
@@ -441,6 +446,15 @@ class Receiver:
         rc = self.L.tfrec_amd_drain_events(self.h, out.ctypes.data, self.max_events, C.byref(n))
         _check(self.L, rc, ok=(E_OK, E_OVERFLOW) if allow_overflow else (E_OK,))
         return out[: n.value]
+
+    def read_levels(self) -> np.ndarray:
+        """levels=True: the level records of the OLDEST undrained submit (tfrec_amd_read_levels; call it before the drain that pops
+        that submit) as a LEVEL_DTYPE array [n_streams, n_blocks].  TfrecAmdError(E_INVAL) on a context without levels,
+        (E_STATE) when nothing is waiting to be drained."""
+        out = np.empty(self.n_streams * self.cfg.max_blocks, dtype=LEVEL_DTYPE)
+        nb = C.c_int(0)
+        _check(self.L, self.L.tfrec_amd_read_levels(self.h, out.ctypes.data, len(out), C.byref(nb)))
+        return out[: self.n_streams * nb.value].reshape(self.n_streams, nb.value).copy()
 
     def stage0(self, stream: int, n_pairs: int) -> np.ndarray:
         """input_10x or input_rate: the 1.536 MS/s int16 IQ the 10:1 or the resampling stage produced for the last submit."""

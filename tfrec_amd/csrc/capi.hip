@@ -41,6 +41,8 @@ hipError_t launch_threshold(hipStream_t st, const uint32_t *dec, size_t dec_stri
 hipError_t launch_chains(hipStream_t st, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask,
 			 size_t mask_stride, int n_streams, int n_blocks, long long sample_base, const ChainLaunch &L,
 			 tfrec_amd_event *events, EventBuf *eb, uint32_t flags);
+hipError_t launch_levels(hipStream_t st, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask, size_t mask_stride,
+			 int n_streams, int n_blocks, LevelState *lev, const StreamCfg *scfg, tfrec_amd_level *out);
 }  // namespace tfrec
 
 using namespace tfrec;
@@ -128,6 +130,14 @@ struct tfrec_amd_ctx {
 	int16_t *d_fmdev[kSets] = {};  // [n_streams][m_max] fm_dev of the decimated samples (computed near windows)
 	uint32_t *d_prevdec[kSets] = {};  // [n_streams] the decimated sample before the submit's first one
 	FskState *d_fsk = nullptr;  // auto threshold (every context has it: a stream can be configured to auto)
+	// TFREC_AMD_F_LEVELS (make_levels): the level meter's carried state, one record buffer per set
+	// ([n_streams][the submit's n_blocks]), its low-priority stream, the set's "records written" event and the set's block count
+	bool levels = false;
+	LevelState *d_lev = nullptr;
+	tfrec_amd_level *d_levels[kSets] = {};
+	hipStream_t lv = nullptr;
+	hipEvent_t ev_lev[kSets] = {};
+	int set_blocks[kSets] = {};
 	int wmax = 0;
 	// tfrec_amd_configure_streams: every stream's settings as the next submit uses them (scfg, the host's copy), their device
 	// copy as the last submit used them (d_scfg: written only by stream_reset_kernel, in the entries of its list), and the
@@ -268,6 +278,7 @@ struct StreamReset {
 	uint8_t *tailR;     // tfrec_amd_create_rate: the resampling stage's raw history (kRateTail bytes per stream of 0x80), or nullptr
 	uint32_t *tailX;    // tfrec_amd_create_format: its history of x (kFmtTail bytes per stream of zero), or nullptr
 	FskState *fsk;      // auto threshold
+	LevelState *lev;    // TFREC_AMD_F_LEVELS: the level meter's carried state, or nullptr
 	const StreamCfg *cfgs;  // [n_list] the listed streams' settings from this submit on ...
 	StreamCfg *scfg;        // ... written over their entries here
 	int32_t n_active;
@@ -311,6 +322,8 @@ __global__ __launch_bounds__(64) void stream_reset_kernel(StreamReset R)
 		const StreamCfg sc = R.cfgs[blockIdx.x];
 		R.scfg[s] = sc;
 		R.fsk[s] = FskState{ sc.thresh, 0, 0, -(1 << 28) };  // auto: 500, fm_demod.cpp:23-27, as tfrec_amd_create
+		if (R.lev)
+			R.lev[s] = LevelState{ sc.thresh, 0, 0, -(1 << 28) };
 		if (R.tcarry)
 			for (int a = 0; a < R.n_active; a++)
 				R.tcarry[(size_t)a * R.n_streams + s] = 0;
@@ -940,6 +953,26 @@ static int make_event_blocks(tfrec_amd_ctx *c)
 	return TFREC_AMD_OK;
 }
 
+// TFREC_AMD_F_LEVELS: the level meter's state (every stream starts like its FskState), records, stream and events
+static int make_levels(tfrec_amd_ctx *c)
+{
+	c->levels = (c->cfg.flags & TFREC_AMD_F_LEVELS) != 0;
+	if (!c->levels)
+		return TFREC_AMD_OK;
+	const size_t n = (size_t)c->cfg.n_streams;
+	TRY(own_device(c, c->d_lev, n * sizeof(LevelState)));
+	const std::vector<LevelState> lev(n, LevelState{ c->scfg[0].thresh, 0, 0, -(1 << 28) });
+	HIPCHK(hipMemcpy(c->d_lev, lev.data(), n * sizeof(LevelState), hipMemcpyHostToDevice));
+	for (int k = 0; k < kSets; k++) {
+		TRY(own_device(c, c->d_levels[k], n * (size_t)c->cfg.max_blocks * sizeof(tfrec_amd_level)));
+		TRY(own_event(c, c->ev_lev[k], hipEventDisableTiming));
+	}
+	int prio_lo = 0, prio_hi = 0;
+	(void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+	TRY(own_stream(c, c->lv, prio_lo));
+	return TFREC_AMD_OK;
+}
+
 // The stream layout: which streams exist, at which priority, and which are aliases -- into S (every set's PipeCtl starts
 // from it) and c->cpy.
 //   serial (TFREC_AMD_F_SERIAL_CHAINS): fs, cs, and cp for the drain's copies.
@@ -1056,6 +1089,7 @@ static int init_context(tfrec_amd_ctx *c)
 	PipeCtl streams = {};
 	TRY(make_streams(c, streams));
 	TRY(make_pipes(c, streams));
+	TRY(make_levels(c));
 	return TFREC_AMD_OK;
 }
 
@@ -1244,6 +1278,8 @@ static int launch_resets(tfrec_amd_ctx *c, int set)
 	if (c->submitted)
 		for (hipEvent_t e : c->pipe[c->last_set].done)
 			HIPCHK(hipStreamWaitEvent(fs, e, 0));
+	if (c->submitted && c->levels)  // (the level meter of the last submit reads d_scfg and owns d_lev)
+		HIPCHK(hipStreamWaitEvent(fs, c->ev_lev[c->last_set], 0));
 	const int nl = (int)c->reset_pending.size();
 	memcpy(c->h_reset[set], c->reset_pending.data(), (size_t)nl * sizeof(int32_t));  // (the set's last copy was drained)
 	for (int i = 0; i < nl; i++)  // a reset stream restarts with its own current settings
@@ -1262,6 +1298,7 @@ static int launch_resets(tfrec_amd_ctx *c, int set)
 	R.tailR = (c->resamp && c->fmt == TFREC_AMD_FMT_U8) ? c->d_tailR[c->tail_sel] : nullptr;
 	R.tailX = (c->resamp && c->fmt != TFREC_AMD_FMT_U8) ? c->d_tailX[c->tail_sel] : nullptr;
 	R.fsk = c->d_fsk;
+	R.lev = c->d_lev;
 	R.cfgs = c->d_rcfg[set];
 	R.scfg = c->d_scfg;
 	R.n_active = c->launch.n_active;
@@ -1513,6 +1550,13 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	if (timing)
 		HIPCHK(hipEventRecord(ev[kEvFmdevDone], fs));
 	HIPCHK(hipEventRecord(P.ev_front, fs));
+	if (c->levels) {  // the level meter: behind the front end (the mask is final), beside the chains, on its own low-priority stream
+		HIPCHK(hipStreamWaitEvent(c->lv, P.ev_front, 0));
+		HIPCHK(launch_levels(c->lv, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams, n_blocks,
+				     c->d_lev, c->d_scfg, c->d_levels[set]));
+		HIPCHK(hipEventRecord(c->ev_lev[set], c->lv));
+		c->set_blocks[set] = n_blocks;
+	}
 	if (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) {
 		HIPCHK(hipStreamWaitEvent(P.cs, P.ev_front, 0));
 		HIPCHK(launch_chains(P.cs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams, n_blocks,
@@ -1531,6 +1575,8 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	// the drain's copies, queued now
 	for (hipEvent_t e : P.done)
 		HIPCHK(hipStreamWaitEvent(c->cpy, e, 0));
+	if (c->levels)  // copied[set] then also says "the records are written" (tfrec_amd_read_levels, and the set's reuse)
+		HIPCHK(hipStreamWaitEvent(c->cpy, c->ev_lev[set], 0));
 	c->copied_n[set] = std::min<uint32_t>(c->copy_guess, (uint32_t)c->cfg.max_events);
 	{  // header, overflow flag and the first copied_n events in one go
 		static_assert(kEvHeader % 16 == 0 && sizeof(tfrec_amd_event) % 16 == 0, "drain_copy_kernel moves 16 bytes per lane");
@@ -1657,6 +1703,32 @@ int tfrec_amd_pending_events(tfrec_amd_ctx *c, int *n)
 	const EventBuf eb = *c->h_eb[c->head];
 	*n = (int)(std::min(eb.count, eb.capacity) - std::min(eb.dead, std::min(eb.count, eb.capacity)));  // (retracted events are not reported)
 	return eb.count > eb.capacity ? TFREC_AMD_E_OVERFLOW : TFREC_AMD_OK;
+}
+
+int tfrec_amd_read_levels(tfrec_amd_ctx *c, tfrec_amd_level *out, size_t cap, int *n_blocks_out)
+{
+	if (!c || !out || !n_blocks_out)
+		return TFREC_AMD_E_INVAL;
+	if (!c->levels) {
+		snprintf(g_err, sizeof(g_err), "the context was made without the level meter's flag");
+		return TFREC_AMD_E_INVAL;
+	}
+	TRY(check_live(c));
+	if (c->inflight == 0) {
+		snprintf(g_err, sizeof(g_err), "no undrained submit: the levels are read before tfrec_amd_drain_events");
+		return TFREC_AMD_E_STATE;
+	}
+	const int set = c->head;
+	const size_t n = (size_t)c->cfg.n_streams * (size_t)c->set_blocks[set];
+	if (cap < n) {
+		snprintf(g_err, sizeof(g_err), "room for %zu level records, the submit has %zu", cap, n);
+		return TFREC_AMD_E_INVAL;
+	}
+	HIPCHK(hipSetDevice(c->cfg.device));
+	HIPCHK(hipEventSynchronize(c->copied[set]));  // (behind ev_lev[set])
+	HIPCHK(hipMemcpy(out, c->d_levels[set], n * sizeof(tfrec_amd_level), hipMemcpyDeviceToHost));
+	*n_blocks_out = c->set_blocks[set];
+	return TFREC_AMD_OK;
 }
 
 int tfrec_amd_drain_events(tfrec_amd_ctx *c, tfrec_amd_event *out, int cap, int *n_out)

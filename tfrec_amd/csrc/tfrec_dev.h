@@ -153,6 +153,15 @@ struct FskState {
 	int32_t last_trig;      // last sample with pwr > thresh, relative to the start of the current submit
 };
 
+// The level meter's carried state (TFREC_AMD_F_LEVELS, levels.h: level_trig_kernel): FskState's fields, kept apart from it --
+// threshold_kernel owns FskState, and the meter recomputes the recurrence on its own
+struct LevelState {
+	int32_t thresh;         // trigger threshold of the next block
+	int32_t triggered_avg;  // fm_demod.cpp:58
+	int32_t runs;           // blocks since the stream's start or last restart (fm_demod.cpp:37)
+	int32_t last_trig;      // last sample with pwr > thresh, relative to the start of the next submit (very negative: none)
+};
+
 // fm_dev samples decided by the exact slow path (fm_resolve.h): logged so that the host can check them against its
 // own libm when the batch is drained (capi.hip)
 struct FmLogEntry {

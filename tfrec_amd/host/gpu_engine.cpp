@@ -235,22 +235,24 @@ struct device_worker {
 	std::mutex mu;
 	std::condition_variable cv;
 	std::deque<std::vector<tfrec_amd_event> > out;  // batches drained, oldest first
+	std::deque<std::vector<tfrec_amd_level> > out_levels;  // -s: their level records, [stream][the batch's blocks]
 	bool done;
 	std::thread th;
 
 	device_worker() : files(NULL), s0(0), s1(0), device(0), types(0), thresh(0), filter(0), bps(1), flags(0), nslots(0), file_blocks(NULL), wide(false), share(false), rate_p(1), rate_q(1), fmt(TFREC_AMD_FMT_U8), block_bytes(TFREC_AMD_BLOCK_BYTES), unit(1), rc(0), abort(NULL), done(false) {}
 
-	void push(std::vector<tfrec_amd_event> &&ev)
+	void push(std::vector<tfrec_amd_event> &&ev, std::vector<tfrec_amd_level> &&lv)
 	{
 		{
 			std::unique_lock<std::mutex> lk(mu);
 			cv.wait(lk, [&]() { return out.size() < 2; });  // the engine's thread is at most two batches behind
 			out.push_back(std::move(ev));
+			out_levels.push_back(std::move(lv));
 		}
 		cv.notify_all();
 	}
-	// next batch's events (false: the worker ended -- rc says why)
-	bool pop(std::vector<tfrec_amd_event> &ev)
+	// next batch's events and (-s) level records (false: the worker ended -- rc says why)
+	bool pop(std::vector<tfrec_amd_event> &ev, std::vector<tfrec_amd_level> &lv)
 	{
 		std::unique_lock<std::mutex> lk(mu);
 		cv.wait(lk, [&]() { return !out.empty() || done; });
@@ -258,6 +260,8 @@ struct device_worker {
 			return false;
 		ev = std::move(out.front());
 		out.pop_front();
+		lv = std::move(out_levels.front());
+		out_levels.pop_front();
 		lk.unlock();
 		cv.notify_all();
 		return true;
@@ -456,6 +460,15 @@ struct device_worker {
 				r = TFREC_AMD_E_STATE;
 				break;
 			}
+			std::vector<tfrec_amd_level> lv;
+			if (flags & TFREC_AMD_F_LEVELS) {  // -s: the batch's level records, before the drain pops it
+				int nb = 0;
+				lv.resize(n * (size_t)bps);
+				r = tfrec_amd_read_levels(ctx, lv.data(), lv.size(), &nb);
+				if (r)
+					break;
+				lv.resize(n * (size_t)nb);
+			}
 			std::vector<tfrec_amd_event> ev(cfg.max_events);
 			int nev = 0;
 			r = tfrec_amd_drain_events(ctx, ev.data(), (int)ev.size(), &nev);
@@ -479,7 +492,7 @@ struct device_worker {
 					ev[kept++].stream = (uint32_t)file[ev[q].stream];
 				}
 			ev.resize(kept);
-			push(std::move(ev));
+			push(std::move(ev), std::move(lv));
 		}
 		if (r)
 			fprintf(stderr, "tfrec_amd (device %d): %s (%s)\n", device, tfrec_amd_strerror(r), tfrec_amd_last_error());
@@ -535,6 +548,15 @@ int gpu_engine::run()
 		stream_samples[s] = (long long)blocks * TFREC_AMD_BLOCK_DEC;
 		file_blocks[s] = blocks;
 	}
+	if (scan) {  // -s: the channel list, before a device is opened
+		fprintf(stderr, "scan: %zu channels, input rate %ld S/s\n", n, wide ? 15360000L : 1536000L * rate_p / rate_q);
+		for (size_t s = 0; s < n; s++) {
+			const int hz = settings[s].tune;
+			const bool far = !wide && (hz <= -768000 || hz >= 768000);
+			fprintf(stderr, "scan channel %ld kHz: tune %d Hz %s\n", scan_khz[s], hz,
+				hz == 0 ? "(none)" : wide ? "ahead of the 10:1 stage" : far ? "ahead of the resampler" : (rate_p != 1 || rate_q != 1) ? "behind the resampler" : "in the front end");
+		}
+	}
 	size_t n_batches = 0;  // of the device with the most
 	const size_t nd = std::min(devices.size(), n);  // never more workers than streams
 	bps = (bps + unit - 1) / unit * unit;
@@ -552,7 +574,8 @@ int gpu_engine::run()
 		w.thresh = thresh;
 		w.filter = filter;
 		w.bps = bps;
-		w.flags = (bits_replay ? (TFREC_AMD_F_BITS | TFREC_AMD_F_ALL_FLUSHES) : 0u) | (wide ? TFREC_AMD_F_INPUT_10X : 0u);
+		w.flags = (bits_replay ? (TFREC_AMD_F_BITS | TFREC_AMD_F_ALL_FLUSHES) : 0u) | (wide ? TFREC_AMD_F_INPUT_10X : 0u) |
+			  (scan ? TFREC_AMD_F_LEVELS : 0u);
 		w.wide = wide;
 		w.share = slots <= 0;
 		w.rate_p = rate_p;
@@ -574,13 +597,44 @@ int gpu_engine::run()
 	}
 	int rc = 0;
 	std::vector<tfrec_amd_event> ev;
+	std::vector<tfrec_amd_level> lv;
+	// -s: per channel (file) the sums of its level records, its telegrams, and with -D every record
+	struct channel_sum {
+		unsigned long long blocks = 0, pwr_sum = 0, over = 0, triggered = 0, telegrams = 0;
+		int peak = 0, thresh = 0;
+		std::vector<tfrec_amd_level> rec;
+	};
+	std::vector<channel_sum> chan(scan ? n : 0);
 	for (size_t k = 0; k < n_batches && rc == 0; k++) {
 		for (size_t d = 0; d < nd && rc == 0; d++) {
 			if (k >= workers[d].plan.size())
 				continue;  // (this device's queue has run out)
-			if (!workers[d].pop(ev)) {
+			if (!workers[d].pop(ev, lv)) {
 				rc = workers[d].rc ? workers[d].rc : TFREC_AMD_E_STATE;
 				break;
+			}
+			if (scan) {  // no replay: the table is the product
+				const batch_plan &b = workers[d].plan[k];
+				for (size_t s = 0; s < b.file.size(); s++) {
+					if (b.file[s] < 0)
+						continue;
+					channel_sum &c = chan[b.file[s]];
+					for (int j = 0; j < b.nb && c.blocks < file_blocks[b.file[s]]; j++) {  // (not the padding behind the file's end)
+						const tfrec_amd_level &r = lv[s * (size_t)b.nb + j];
+						c.blocks++;
+						c.pwr_sum += r.pwr_sum;
+						c.over += (unsigned long long)r.n_over;
+						c.triggered += (unsigned long long)r.triggered;
+						c.peak = std::max(c.peak, (int)r.pwr_max);
+						c.thresh = r.thresh;
+						if (dbg > 0)
+							c.rec.push_back(r);
+					}
+				}
+				for (size_t q = 0; q < ev.size(); q++)
+					if (ev[q].status == 1 && ev[q].end_sample < stream_samples[ev[q].stream])
+						chan[ev[q].stream].telegrams++;
+				continue;
 			}
 			// per stream in time order, slots in registration order like the reference's dispatch loop (fm_demod.cpp:48-49).
 			// BITS chunks carry the first sample of their trigger window (a chunk has no per-bit time): a window's bits
@@ -605,12 +659,21 @@ int gpu_engine::run()
 	if (rc)
 		abort.store(true);
 	for (size_t d = 0; d < nd; d++) {
-		while (workers[d].pop(ev)) {
+		while (workers[d].pop(ev, lv)) {
 		}
 		workers[d].th.join();
 		if (!rc)
 			rc = workers[d].rc;
 	}
+	if (scan && !rc)
+		for (size_t s = 0; s < n; s++) {
+			const channel_sum &c = chan[s];
+			for (const tfrec_amd_level &r : c.rec)  // fm_demod.cpp:61, per channel
+				printf("%ld Trigger ratio %d/%d, avg %d\n", scan_khz[s], (int)r.triggered, TFREC_AMD_BLOCK_DEC, (int)r.triggered_avg);
+			printf("scan %ld blocks=%llu mean_pwr=%llu peak=%d over=%llu triggered=%llu thresh=%d telegrams=%llu\n", scan_khz[s], c.blocks,
+			       c.blocks ? c.pwr_sum / ((unsigned long long)TFREC_AMD_BLOCK_DEC * c.blocks) : 0ull, c.peak, c.over, c.triggered,
+			       c.blocks ? c.thresh : (settings[s].thresh ? settings[s].thresh : 500), c.telegrams);
+		}
 	if (out_mode)  // -m 1: summary at the end (decoder.cpp:98-109)
 		for (size_t s = 0; s < decs.size(); s++)
 			for (size_t k2 = 0; k2 < decs[s].size(); k2++)

@@ -132,6 +132,16 @@ public:
 	// set_rate or -- without one -- at 1.536 MS/s.  A block of a file is 65536 p / q * bytes per complex sample / 2 bytes, and a
 	// shorter file is padded with the format's silence (zero); everything else is as with u8.  Excludes set_wide.
 	void set_format(int format) { fmt = format; }
+	// -s: scan mode.  The dump files are ONE recording given once per channel, khz[i] the receive frequency of
+	// file i (ascending; the files' tunes place them): the streams share the recording's input row as repeated paths always do,
+	// the context runs with TFREC_AMD_F_LEVELS, and instead of replaying telegrams into the decoders run() sums every channel's
+	// level records (tfrec_amd_read_levels, the blocks the file really holds) and counts its events with status 1.  It prints
+	// the channel list to stderr before a device is opened and the table to stdout at the end: per channel
+	//   scan <kHz> blocks=<n> mean_pwr=<sum pwr_sum / (8192 n)> peak=<max pwr_max> over=<sum n_over> triggered=<sum triggered>
+	//        thresh=<the last block's> telegrams=<events with status 1>
+	// preceded, with dbg > 0, by the reference's per-block line "<kHz> Trigger ratio <triggered>/8192, avg <triggered_avg>"
+	// (fm_demod.cpp:61) for every block.  One device, no -n.
+	void set_scan(const std::vector<long> &khz) { scan = true; scan_khz = khz; }
 	// returns 0 on success, a TFREC_AMD_E_* code otherwise
 	int run();
 	// decoders of stream s in slot order (NULL for slots not registered)
@@ -155,6 +165,8 @@ private:
 	bool wide;
 	int rate_p, rate_q, unit;  // set_rate (1, 1, 1: none)
 	int fmt;                   // set_format (TFREC_AMD_FMT_U8: none)
+	bool scan = false;         // set_scan
+	std::vector<long> scan_khz;
 };
 
 #endif

@@ -2,6 +2,7 @@
 //
 //   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-q] [-D] [-B] [-d device[,device...]] [-b blocks]
 //             [-n streams] [-e handler | -E handler] [-m mode] [-p settings] -L dump.iq [[-p settings] -L more.iq ...]
+//   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-c kHz] [-x | -r Hz] [-F format] [-D] [-d device] [-b blocks] -s step_kHz -L dump.iq
 //   tfrec_gpu [-T hexmask] -X telegrams.txt
 //
 // Flags keep the reference's meaning (main.cpp:63-88, 107-164): -T sensor type bit mask (hex), -t trigger
@@ -38,6 +39,14 @@
 // and SigMF cf32_le; little-endian, interleaved I, Q, without a header (tfrec_amd_create_format).  With -r the files
 // are at that rate, without it at 1.536 MS/s.  A block of a file is 65536 * P / Q * bytes per complex sample / 2 bytes; -b, -n, -d,
 // shared paths and -f / -c / -p f= are as with -r.  A format other than u8 excludes -x.
+// -s step_kHz (not in the reference): scan ONE recording -- at 1.536 MS/s, or given with -x, or with -r / -F -- for where the energy
+// and the telegrams are.  A receiver sits on every channel c + k * step (k any integer) that lies at least 192 kHz,
+// half the band behind the 4:1 stage, inside the recording: |k * step * 1000| <= fs_in / 2 - 192000; at most 4096 of them.  All
+// read the file once, through one input row, each with the tune -f would give it; the context runs the level meter
+// (TFREC_AMD_F_LEVELS).  Telegram text is suppressed; stdout carries one line per channel in ascending frequency,
+//   scan <kHz> blocks=<n> mean_pwr=<..> peak=<..> over=<..> triggered=<..> thresh=<..> telegrams=<..>
+// and with -D, ahead of it, the reference's "Trigger ratio" line (fm_demod.cpp:61) of each of its blocks, prefixed with <kHz>;
+// stderr lists the channels before a device is opened.  Not with -n, -p, -f, -e / -E, -X, several -L or several devices.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -152,9 +161,21 @@ int main(int argc, char **argv)
 	long freq = -1, center = 868250;  // -f (unset: the dumps' own frequency), -c: kHz
 	long rate = 0;  // -r: Hz (0: 1536000)
 	int format = TFREC_AMD_FMT_U8;  // -F
+	long scan_step = 0;  // -s: kHz
+	bool have_scan = false;
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:h")) != -1) {
 		switch (c) {
+		case 's': {
+			char *end = NULL;
+			scan_step = strtol(optarg, &end, 10);
+			have_scan = true;
+			if (end == optarg || *end || scan_step < 1 || scan_step > 100000000L) {
+				fprintf(stderr, "tfrec_gpu: bad -s '%s': want the channel step in kHz, >= 1\n", optarg);
+				return 1;
+			}
+			break;
+		}
 		case 'T': types = (int)strtol(optarg, NULL, 16); break;
 		case 't': thresh = atoi(optarg); break;
 		case 'W': filter = 1; break;
@@ -217,7 +238,8 @@ int main(int argc, char **argv)
 		case 'E': exec = optarg; batched = true; break;
 		case 'm': mode = atoi(optarg); break;
 		default:
-			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-p settings] -L dump [[-p settings] -L dump ...] | -X hexfile\n"
+			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -X hexfile\n"
+					"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
 					"  -f kHz      receive frequency (default: the dumps' own, -c)\n"
 					"  -c kHz      frequency the dumps were recorded at (default 868250); -f within 767 kHz of it\n"
 					"  -x          the dumps are 15.36 MS/s u8 dumps (10x the rate); -f within 7679 kHz of -c, shifted ahead of the 10:1 stage\n"
@@ -234,6 +256,10 @@ int main(int argc, char **argv)
 	}
 	if (have_slots && slots < 1) {
 		fprintf(stderr, "tfrec_gpu: -n must be >= 1\n");
+		return 1;
+	}
+	if (have_scan && (have_slots || have_spec || freq >= 0 || exec || hexfile || dumps.size() > 1 || devices.size() > 1)) {
+		fprintf(stderr, "tfrec_gpu: -s scans one -L file on one device: not with -n, -p, -f, -e, -E, -X, several -L or several -d\n");
 		return 1;
 	}
 	if (have_spec && hexfile) {
@@ -287,6 +313,31 @@ int main(int argc, char **argv)
 			blocks = up;
 		}
 	}
+	// -s: the file once per channel c + k * step, |k * step * 1000| <= fs_in / 2 - 192000 (in integers: 2000 |k| step <= fs_in - 384000)
+	std::vector<long> scan_khz;
+	if (have_scan) {
+		const long fs_in = wide ? 15360000L : (rate ? rate : 1536000L);
+		const long kmax = (fs_in - 384000) / (2000 * scan_step);
+		if (2 * kmax + 1 > 4096) {
+			fprintf(stderr, "tfrec_gpu: -s %ld: %ld channels across the %ld S/s recording, at most 4096 are scanned at once\n", scan_step,
+				2 * kmax + 1, fs_in);
+			return 1;
+		}
+		const std::string path = dumps[0];
+		dumps.clear();
+		dump_spec.clear();
+		for (long k = -kmax; k <= kmax; k++) {
+			spec p;
+			p.freq = center + k * scan_step;
+			if (p.freq <= 0) {
+				fprintf(stderr, "tfrec_gpu: -s: channel %ld kHz below zero: -c %ld is not the recording's frequency\n", p.freq, center);
+				return 1;
+			}
+			dumps.push_back(path);
+			dump_spec.push_back(p);
+			scan_khz.push_back(p.freq);
+		}
+	}
 	// every file's tune, checked before any device is opened
 	std::vector<int> tunes;
 	bool tuned = false;
@@ -309,7 +360,7 @@ int main(int argc, char **argv)
 		tuned = tuned || tunes.back() != 0;
 	}
 	std::vector<file_settings> per_file;
-	if (have_spec || tuned)
+	if (have_spec || tuned || have_scan)
 		for (size_t i = 0; i < dump_spec.size(); i++) {
 			const spec &p = dump_spec[i];
 			per_file.push_back(file_settings{ p.types >= 0 ? p.types : types, p.thresh >= 0 ? p.thresh : thresh,
@@ -324,6 +375,8 @@ int main(int argc, char **argv)
 	if (rate_p != 1 || rate_q != 1)
 		e.set_rate(rate_p, rate_q);
 	e.set_format(format);
+	if (have_scan)
+		e.set_scan(scan_khz);
 	int rc = e.run();
 	fflush(stdout);
 	return rc ? 2 : 0;
