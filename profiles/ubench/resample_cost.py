@@ -1,6 +1,6 @@
 """Cost of the resampling stage and of the input-rate tune ahead of it (6g): kernel time of resample_kernel at
-P/Q = 4/3 (2.048 MS/s) and 25/16 (2.4 MS/s) for 1024 streams x 48 blocks, untuned (resample_kernel<false>) and with every stream
-tuned at the input rate (resample_kernel<true>), and -- for scale, on the same machine in the same run -- of the plain front end
+P/Q = 4/3 (2.048 MS/s) and 25/16 (2.4 MS/s) for 1024 streams x 48 blocks, untuned (resample_kernel) and with every stream
+tuned at the input rate (resample_fmt_kernel<kFmtU8>, the format kernel's U8 instantiation), and -- for scale, on the same machine in the same run -- of the plain front end
 of an unresampled context at the same size.
 
     python profiles/ubench/resample_cost.py [--out DIR] [--streams 1024] [--blocks 48] [--submits 12]
@@ -80,8 +80,10 @@ def report(trace_dir: str, n_streams: int, n_blocks: int, submits: int) -> str:
         return sum((d[k] for k in sorted(names)), []) if names else []
 
     def variant(tuned):
-        tag = ("<true>", "ILb1E") if tuned else ("<false>", "ILb0E")
-        names = [k for k in d if "resample_kernel" in k and any(t in k.replace(" ", "") for t in tag)]
+        if tuned:  # the template argument 0 = kFmtU8, whether the trace names the kernel mangled or not
+            names = [k for k in d if "resample_fmt_kernelILi0E" in k or "resample_fmt_kernel<0>" in k]
+        else:
+            names = [k for k in d if "resample_kernel" in k]
         return sum((d[k] for k in sorted(names)), [])
 
     per = WARMUP + submits
@@ -89,7 +91,8 @@ def report(trace_dir: str, n_streams: int, n_blocks: int, submits: int) -> str:
     for tuned in (False, True):
         rs = variant(tuned)
         for i, (p, q) in enumerate(RATES):
-            rows.append(("resample_kernel<%s> %d/%d" % ("true" if tuned else "false", p, q), rs[i * per + WARMUP:(i + 1) * per],
+            rows.append(("%s %d/%d" % ("resample_fmt_kernel<U8> tuned" if tuned else "resample_kernel", p, q),
+                         rs[i * per + WARMUP:(i + 1) * per],
                          n_streams * n_blocks * 65536 * p // q))
     # the plain context's front end: the u8 instantiation (the rate contexts run the int16 one)
     fe = [k for k in d if "frontend_kernel" in k and "Lb0ELb0" in k.replace(" ", "")] or [k for k in d if "frontend_kernel<false, false" in k]

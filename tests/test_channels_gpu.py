@@ -181,6 +181,33 @@ def test_wideband_receivers_of_one_row():
     assert total > n
 
 
+def test_an_untuned_stream_keeps_its_history_while_the_10x_kernels_change_around_it():
+    """A 10x context runs the plain 10:1 kernel while no stream has a wide tune and the tuned one while one has.  Stream 0 is tuned
+    before the second submit and untuned again before the third -- each a restart of stream 0 alone --, so stream 1, never tuned
+    and never restarted, has its history written by one kernel and read by the other, in both directions: its stage 0 is that of
+    the uninterrupted input.  (Near-silence with full-scale stretches at the start and across the two boundaries.)"""
+    block = 10 * api.BLOCK_BYTES
+    rng = np.random.default_rng(53)
+    iq = rng.integers(125, 132, (2, 3 * block), dtype=np.uint8)
+    for pos in (0, block, 2 * block):
+        lo, hi = max(0, pos - 3000), pos + 3000
+        iq[:, lo:hi] = rng.integers(0, 256, (2, hi - lo), dtype=np.uint8)
+    devs, _ = device_parts(iq, (1, 1, 1), block)
+    y = []
+    with api.Receiver(2, DFLT[0], DFLT[1], DFLT[2], max_blocks=1, all_flushes=True, input_10x=True) as r:
+        for k, d in enumerate(devs):
+            if k == 1:
+                r.tune_streams_wide([0], [3300000])
+            if k == 2:
+                r.tune_streams_wide([0], [0])
+            r.submit(d, 1)
+            r.drain()
+            y.append([r.stage0(s, 4 * api.BLOCK_DEC) for s in range(2)])
+    assert np.array_equal(np.concatenate([v[1] for v in y]), tune.decim10_s16(tune.s16_of_u8(iq[1])))
+    want0 = tune.decim10_s16(tune.mix10_s16(tune.s16_of_u8(iq[0][block:2 * block]), 3300000))
+    assert np.array_equal(y[1][0], want0)  # (the tuned kernel did run in between)
+
+
 def test_wide_tune_needs_the_10x_input_and_argument_errors_change_nothing():
     with api.Receiver(2, DFLT[0], DFLT[1], DFLT[2], max_blocks=1, all_flushes=True) as r:
         with pytest.raises(api.TfrecAmdError) as e:

@@ -92,8 +92,8 @@ def full_scale_row(fmt, n, seed):
 @pytest.mark.parametrize("fmt", ["s8", "s16", "f32"])
 def test_stage0_of_the_large_rates(fmt, p, q):
     """One stream, two submits of one block, full-scale input.  639/64: the tap table, the int16 image of a whole tile and the
-    cosine table exceed the LDS limit, so the kernel runs tiles of 512 outputs (the half tile), as resample_kernel<true> does at
-    this rate.  29/4 = 7.25 input samples per output has 44 taps per phase and a tile's image of 30 KB: the largest image among
+    cosine table exceed the LDS limit, so the kernel runs tiles of 512 outputs (the half tile), as its U8
+    instantiation (the tuned u8 resampler) does at this rate.  29/4 = 7.25 input samples per output has 44 taps per phase and a tile's image of 30 KB: the largest image among
     the rates with a small Q, still in whole tiles."""
     sizes = (1, 1)
     rows = full_scale_row(fmt, resample.input_samples(2, p, q), 29)

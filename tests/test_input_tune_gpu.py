@@ -72,6 +72,28 @@ def test_stage0_equals_the_restatement(p, q, sizes):
         assert pos == len(want)
 
 
+@pytest.mark.parametrize("p,q", [(25, 16), (639, 64)])
+def test_an_untuned_stream_keeps_its_history_while_the_kernels_change_around_it(p, q):
+    """A u8 rate context runs the plain resampler while no stream is tuned and the format kernel's U8 instantiation while one is.
+    Stream 0 is tuned before the second submit and untuned again before the third -- each a restart of stream 0 alone --, so
+    stream 1, never tuned and never restarted, has its history written by one kernel and read by the other, in both directions:
+    its stage 0 is that of the uninterrupted input.  25/16 takes the whole tile, 639/64 the half tile."""
+    sizes = (1, 1, 1)
+    hz = 300000
+    iq = loud_and_quiet(p, q, sizes, 2, 7000 * p + q)
+
+    def before(r, k):
+        if k == 1:
+            r.tune_streams_input([0], [hz])
+        if k == 2:
+            r.tune_streams_input([0], [0])
+
+    _, y0 = run(iq, sizes, p, q, before=before, all_flushes=True, max_events=1 << 16)
+    assert np.array_equal(np.concatenate([y[1] for y in y0]), resample.resample_s16(iq[1], p, q))
+    c1 = 2 * resample.input_samples(1, p, q)
+    assert np.array_equal(y0[1][0], stage0_of(iq[0][c1:], p, q, hz)[:len(y0[1][0])])  # (the tuned kernel did run in between)
+
+
 @pytest.mark.parametrize("p,q", sorted(WIDE_SCENES))
 @pytest.mark.parametrize("mode", ["deep", "shallow", "serial_chains", "default_mode", "bits", "host"])
 def test_events_equal_the_oracle_behind_the_restatement(mode, p, q, monkeypatch):

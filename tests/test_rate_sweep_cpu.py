@@ -66,7 +66,7 @@ def tuned_lds(p, q, t, tile):
 
 
 def plain_lds(p, q, t):
-    """... and of resample_kernel<false>: the table and the raw image (4 dwords per chunk), always a whole tile."""
+    """... and of resample_kernel: the table and the raw image (4 dwords per chunk), always a whole tile."""
     return (((q * t + 3) & ~3) + 4 * raw_chunks(p, q, t, 1024)) * 4
 
 

@@ -1,4 +1,4 @@
-"""The resampling kernels on the GPU across the rate range, bit for bit: resample_kernel<false>, resample_kernel<true> and
+"""The resampling kernels on the GPU across the rate range, bit for bit: resample_kernel, resample_fmt_kernel<U8> (the tuned u8 kernel) and
 resample_fmt_kernel<S8 | S16 | F32> at the rates of test_rate_sweep_cpu.SWEEP_RATES (the edges of T, Q, the LDS and the
 whole-tile / half-tile decision; that module asserts what each rate is there for and that the expectations are consistent in
 themselves), and ingest_kernel's row lookup.
@@ -76,13 +76,13 @@ def sweep(fmt, p, q, tuned):
 
 @pytest.mark.parametrize("p,q", RATES, ids=SWEEP_IDS)
 def test_u8_untuned(p, q):
-    """(a) resample_kernel<false>: the kernel tfrec_gpu -r uses by default."""
+    """(a) resample_kernel: the kernel tfrec_gpu -r uses by default."""
     sweep("u8", p, q, False)
 
 
 @pytest.mark.parametrize("p,q", RATES, ids=SWEEP_IDS)
 def test_u8_mixed_tunes_in_one_launch(p, q):
-    """(b) resample_kernel<true>: stream 0 tuned 1234 Hz inside the limit, stream 1 untuned, stream 2 tuned to -123457 Hz."""
+    """(b) resample_fmt_kernel<U8>, the tuned u8 kernel: stream 0 tuned 1234 Hz inside the limit, stream 1 untuned, stream 2 tuned to -123457 Hz."""
     sweep("u8", p, q, True)
 
 

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <functional>
 #include <new>
 #include <vector>
 
@@ -18,7 +19,7 @@ hipError_t launch_resample(hipStream_t st, const uint8_t *iq, size_t stride, int
 			   const float *taps, const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride,
 			   const uint4 *chan, bool tuned);
 hipError_t launch_resample_fmt(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, int p, int q, int t,
-			       const float *taps, const uint32_t *tail_in, uint32_t *tail_out, uint32_t *out, size_t out_stride,
+			       const float *taps, const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride,
 			       const uint4 *chan, bool tuned);
 hipError_t launch_ingest(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, uint32_t *out,
 			 size_t out_stride, const uint4 *chan);
@@ -50,7 +51,8 @@ using namespace tfrec;
 constexpr int kTuneLimit = 768000;  // |tune_hz| < half the 1.536 MS/s sample rate
 constexpr int kTuneWideLimit = 7680000;  // tfrec_amd_tune_streams_wide: half the 15.36 MS/s input rate
 constexpr int kRateQMax = 64;  // tfrec_amd_create_rate: the largest Q
-constexpr int kRateTail = 128;  // ... and its raw history per stream in bytes (resample_kernel: kRsTail)
+constexpr int k10xTail = 112;   // TFREC_AMD_F_INPUT_10X: the 10:1 stage's raw history per stream in bytes (decim10_kernel: kTail10)
+constexpr int kRateTail = 128;  // tfrec_amd_create_rate: the resampling stage's raw history per stream in bytes (resample.h: kRsTail)
 constexpr int kFmtTail = 256;   // tfrec_amd_create_format: the history per stream in bytes, 64 complex samples of x (formats.h: kFmtTailDw)
 
 // Buffer / table sets = submits that may be in flight (the FIFO depth): front end of submit k+2, biquad stage of
@@ -168,27 +170,27 @@ struct tfrec_amd_ctx {
 	uint4 *d_chan[kSets] = {}, *h_chan[kSets] = {};
 	uint8_t *d_tail[kSets] = {};  // FIR history: [tail_sel] is read by the next front end, [tail_sel ^ 1] written
 	int tail_sel = 0;
-	// TFREC_AMD_F_INPUT_10X: output of the 10:1 stage (1.536 MS/s int16 pairs, one buffer per set) and its raw history
+	// in16: a pre-stage (launch_prestage: the 10:1 stage, the resampling stage or the format conversion) writes stage 0, 1.536 MS/s
+	// int16 pairs, one buffer per set, and the front end reads int16.  Its history of the input, if it keeps one: pre_bytes per
+	// stream, pre_fill after a start or restart, [tail_sel] read and [tail_sel ^ 1] written like d_tail (make_front_buffers).
 	uint32_t *d_in16[kSets] = {};
 	size_t in16_stride = 0;  // uint32 units
-	uint8_t *d_tail10[kSets] = {};
-	bool in10x = false;
+	uint8_t *d_pre[kSets] = {};
+	int pre_bytes = 0, pre_fill = 0;
+	bool in10x = false;  // TFREC_AMD_F_INPUT_10X
 	// tfrec_amd_create_rate: the input rate is 1536000 rate_p / rate_q; the resampling stage writes d_in16 as the
-	// 10:1 stage does, from a tap table [rate_q][rate_t] (h / 1024 as floats) and its raw history (d_tailR: two buffers that flip
-	// with tail_sel).  in16: a pre-stage writes stage 0 and the front end reads int16 (in10x or resamp).
+	// 10:1 stage does, from a tap table [rate_q][rate_t] (h / 1024 as floats).
 	// rate_abs: max_phi sum_n |h[phi][n]| of that table, for the guard of tfrec_amd_tune_streams_input (6g), whose per-stream
 	// tune and increment per input sample live in wide_hz / wide_inc as the 10x context's wide tune does.
 	int32_t rate_p = 1, rate_q = 1, rate_t = 0;
 	long long rate_abs = 0;
 	bool resamp = false, in16 = false;
 	float *d_rtaps = nullptr;
-	uint8_t *d_tailR[2] = {};
 	// tfrec_amd_create_format: fmt is the TFREC_AMD_FMT_* of the input rows, 0 (U8) in every context of the older
-	// constructors.  A rate context with another format runs resample_fmt_kernel from a history of canonical x (d_tailX, in place
-	// of d_tailR); at the base rate (ingest: rate 1/1, no resampler) ingest_kernel converts the rows into d_in16.
+	// constructors.  A rate context with another format runs resample_fmt_kernel from a history of canonical x instead
+	// of the raw one; at the base rate (ingest: rate 1/1, no resampler) ingest_kernel converts the rows into d_in16.
 	int32_t fmt = TFREC_AMD_FMT_U8;
 	bool ingest = false;
-	uint32_t *d_tailX[2] = {};
 	// ---- window-parallel pipeline (make_window_state).  One set per submit in flight, like the front-end outputs: the window
 	// scan and the biquads of submit k+1 fill theirs while the slicers of submit k still read the other
 	int16_t *d_ld16[kSets] = {};   // [chains][m_max] tfa2-family biquad outputs
@@ -274,9 +276,8 @@ struct StreamReset {
 	int32_t n_list, n_streams;
 	uint8_t *tail;      // front-end FIR history the NEXT front end reads: tail_bytes per stream, filled with tail_fill
 	int32_t tail_bytes, tail_fill;
-	uint8_t *tail10;    // TFREC_AMD_F_INPUT_10X: the 10:1 stage's raw history (112 bytes per stream of 0x80), or nullptr
-	uint8_t *tailR;     // tfrec_amd_create_rate: the resampling stage's raw history (kRateTail bytes per stream of 0x80), or nullptr
-	uint32_t *tailX;    // tfrec_amd_create_format: its history of x (kFmtTail bytes per stream of zero), or nullptr
+	uint8_t *pre;       // the pre-stage's history the NEXT one reads (pre_bytes per stream, filled with pre_fill), or nullptr
+	int32_t pre_bytes, pre_fill;
 	FskState *fsk;      // auto threshold
 	LevelState *lev;    // TFREC_AMD_F_LEVELS: the level meter's carried state, or nullptr
 	const StreamCfg *cfgs;  // [n_list] the listed streams' settings from this submit on ...
@@ -300,15 +301,8 @@ __global__ __launch_bounds__(64) void stream_reset_kernel(StreamReset R)
 	const int ln = threadIdx.x;
 	for (int i = ln; i < R.tail_bytes; i += 64)
 		R.tail[(size_t)s * R.tail_bytes + i] = (uint8_t)R.tail_fill;
-	if (R.tail10)
-		for (int i = ln; i < 112; i += 64)
-			R.tail10[(size_t)s * 112 + i] = 0x80;
-	if (R.tailR)
-		for (int i = ln; i < kRateTail; i += 64)
-			R.tailR[(size_t)s * kRateTail + i] = 0x80;
-	if (R.tailX)
-		for (int i = ln; i < kFmtTail / 4; i += 64)
-			R.tailX[(size_t)s * (kFmtTail / 4) + i] = 0u;
+	for (int i = ln; i < R.pre_bytes; i += 64)  // (0 without a history)
+		R.pre[(size_t)s * R.pre_bytes + i] = (uint8_t)R.pre_fill;
 	constexpr int kChunks = (int)(sizeof(ChainState) / 16);
 	const uint4 *init = reinterpret_cast<const uint4 *>(R.chain_init);
 	for (int a = 0; a < R.n_active; a++)
@@ -707,33 +701,19 @@ static int make_front_buffers(tfrec_amd_ctx *c)
 		TRY(own_device(c, c->d_tail[k], n * tail_bytes));
 		HIPCHK(hipMemset(c->d_tail[k], c->in16 ? 0 : 0x80, n * tail_bytes));
 	}
-	if (c->in10x) {
+	if (c->in16) {  // stage 0 and the pre-stage's history: raw u8 (silence is 128) or, a rate context in another format, x
 		c->in16_stride = 4 * m_max;  // complex samples at 1.536 MS/s per stream and submit
-		for (int k = 0; k < kSets; k++) {
-			TRY(own_device(c, c->d_in16[k], n * c->in16_stride * sizeof(uint32_t)));
-			TRY(own_device(c, c->d_tail10[k], n * 112));
-		}
-		for (int k = 0; k < 2; k++)
-			HIPCHK(hipMemset(c->d_tail10[k], 0x80, n * 112));
-	}
-	if (c->ingest) {  // the base rate in another format: stage 0 is the converted input
-		c->in16_stride = 4 * m_max;
 		for (int k = 0; k < kSets; k++)
 			TRY(own_device(c, c->d_in16[k], n * c->in16_stride * sizeof(uint32_t)));
+		const bool raw = c->fmt == TFREC_AMD_FMT_U8;
+		c->pre_bytes = c->in10x ? k10xTail : c->ingest ? 0 : raw ? kRateTail : kFmtTail;
+		c->pre_fill = raw ? 0x80 : 0;
+		for (int k = 0; c->pre_bytes && k < (c->in10x ? kSets : 2); k++) {  // (the 10x context has always owned one per set)
+			TRY(own_device(c, c->d_pre[k], n * c->pre_bytes));
+			HIPCHK(hipMemset(c->d_pre[k], c->pre_fill, n * c->pre_bytes));
+		}
 	}
 	if (c->resamp) {
-		c->in16_stride = 4 * m_max;
-		for (int k = 0; k < kSets; k++)
-			TRY(own_device(c, c->d_in16[k], n * c->in16_stride * sizeof(uint32_t)));
-		for (int k = 0; k < 2; k++) {
-			if (c->fmt != TFREC_AMD_FMT_U8) {  // the history of x: silence is zero
-				TRY(own_device(c, c->d_tailX[k], n * kFmtTail));
-				HIPCHK(hipMemset(c->d_tailX[k], 0, n * kFmtTail));
-				continue;
-			}
-			TRY(own_device(c, c->d_tailR[k], n * kRateTail));
-			HIPCHK(hipMemset(c->d_tailR[k], 0x80, n * kRateTail));
-		}
 		std::vector<int32_t> h;
 		int t = 0;
 		if (!resample_table(c->rate_p, c->rate_q, h, t))  // (tfrec_amd_create_rate checked it already)
@@ -1294,9 +1274,9 @@ static int launch_resets(tfrec_amd_ctx *c, int set)
 	R.tail = c->d_tail[c->tail_sel];  // the buffer this submit's front end reads (the history flips per submit)
 	R.tail_bytes = c->in16 ? 2 * kTailBytes : kTailBytes;
 	R.tail_fill = c->in16 ? 0 : 0x80;  // as make_front_buffers: int16 zero, or u8 128
-	R.tail10 = c->in10x ? c->d_tail10[c->tail_sel] : nullptr;
-	R.tailR = (c->resamp && c->fmt == TFREC_AMD_FMT_U8) ? c->d_tailR[c->tail_sel] : nullptr;
-	R.tailX = (c->resamp && c->fmt != TFREC_AMD_FMT_U8) ? c->d_tailX[c->tail_sel] : nullptr;
+	R.pre = c->d_pre[c->tail_sel];
+	R.pre_bytes = c->pre_bytes;
+	R.pre_fill = c->pre_fill;
 	R.fsk = c->d_fsk;
 	R.lev = c->d_lev;
 	R.cfgs = c->d_rcfg[set];
@@ -1450,8 +1430,6 @@ static int rows_in_use(const tfrec_amd_ctx *c)
 
 // Bytes of one input row of a submit of n_blocks blocks: n_blocks * 32768 * P / Q complex samples, which must be a whole
 // number (any n_blocks when Q is a power of two, otherwise a multiple of Q's odd part), of 2, 4 or 8 bytes each.
-static size_t sample_bytes(int32_t fmt) { return fmt == TFREC_AMD_FMT_F32 ? 8 : fmt == TFREC_AMD_FMT_S16 ? 4 : 2; }
-
 static int input_bytes(const tfrec_amd_ctx *c, int n_blocks, size_t *bytes)
 {
 	if (n_blocks < 1)
@@ -1462,7 +1440,29 @@ static int input_bytes(const tfrec_amd_ctx *c, int n_blocks, size_t *bytes)
 		snprintf(g_err, sizeof(g_err), "%d blocks at the input rate %lld/%lld are not a whole number of input samples", n_blocks, p, q);
 		return TFREC_AMD_E_INVAL;
 	}
-	*bytes = (size_t)(num / q) * sample_bytes(c->fmt);
+	*bytes = (size_t)(num / q) * fmt_sample_bytes(c->fmt);
+	return TFREC_AMD_OK;
+}
+
+// The submit's input -> stage 0 (d_in16[set]) on the set's front-end stream.  chan: the set's {inc, phase, row, 0} per stream
+// where a stream is mapped or has an input-rate tune (stage_chan), or nullptr.
+static int launch_prestage(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, size_t stride, int n_blocks, const uint4 *chan)
+{
+	hipStream_t fs = c->pipe[set].fs;
+	const int n = c->cfg.n_streams;
+	const uint8_t *hin = c->d_pre[c->tail_sel];
+	uint8_t *hout = c->d_pre[c->tail_sel ^ 1];
+	uint32_t *out = c->d_in16[set];
+	if (c->in10x)  // 15.36 MS/s u8 -> 1.536 MS/s int16 pairs
+		HIPCHK(launch_decim10(fs, d_iq, stride, n, n_blocks, hin, hout, out, c->in16_stride, chan));
+	else if (c->ingest)  // 1.536 MS/s in another format -> x as int16 pairs
+		HIPCHK(launch_ingest(fs, c->fmt, d_iq, stride, n, n_blocks, out, c->in16_stride, chan));
+	else if (c->fmt != TFREC_AMD_FMT_U8)  // 1536000 P / Q S/s in another format: the format-aware resampling stage
+		HIPCHK(launch_resample_fmt(fs, c->fmt, d_iq, stride, n, n_blocks, c->rate_p, c->rate_q, c->rate_t, c->d_rtaps, hin, hout, out,
+					   c->in16_stride, chan, c->n_wide != 0));
+	else  // 1536000 P / Q S/s u8 -> 1.536 MS/s int16 pairs
+		HIPCHK(launch_resample(fs, d_iq, stride, n, n_blocks, c->rate_p, c->rate_q, c->rate_t, c->d_rtaps, hin, hout, out, c->in16_stride,
+				       chan, c->n_wide != 0));
 	return TFREC_AMD_OK;
 }
 
@@ -1507,28 +1507,8 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	const bool chan10 = c->in16 && (c->mapped || c->n_wide), chan_front = !c->in16 && c->mapped;
 	if (chan10 || chan_front)
 		TRY(stage_chan(c, set));
-	if (c->in10x) {  // 15.36 MS/s u8 -> 1.536 MS/s int16 pairs, then the standard cascade on int16 input
-		HIPCHK(launch_decim10(fs, (const uint8_t *)d_iq, stride, c->cfg.n_streams, n_blocks, c->d_tail10[c->tail_sel],
-				      c->d_tail10[c->tail_sel ^ 1], c->d_in16[set], c->in16_stride, chan10 ? c->d_chan[set] : nullptr));
-		fin = (const uint8_t *)c->d_in16[set];
-		fstride = c->in16_stride * sizeof(uint32_t);
-	}
-	if (c->ingest) {  // 1.536 MS/s in another format -> x as int16 pairs, then the same cascade on int16 input
-		HIPCHK(launch_ingest(fs, c->fmt, (const uint8_t *)d_iq, stride, c->cfg.n_streams, n_blocks, c->d_in16[set], c->in16_stride,
-				     chan10 ? c->d_chan[set] : nullptr));
-		fin = (const uint8_t *)c->d_in16[set];
-		fstride = c->in16_stride * sizeof(uint32_t);
-	}
-	if (c->resamp && c->fmt != TFREC_AMD_FMT_U8) {  // 1536000 P / Q S/s in another format: the format-aware resampling stage
-		HIPCHK(launch_resample_fmt(fs, c->fmt, (const uint8_t *)d_iq, stride, c->cfg.n_streams, n_blocks, c->rate_p, c->rate_q,
-					   c->rate_t, c->d_rtaps, c->d_tailX[c->tail_sel], c->d_tailX[c->tail_sel ^ 1], c->d_in16[set],
-					   c->in16_stride, chan10 ? c->d_chan[set] : nullptr, c->n_wide != 0));
-		fin = (const uint8_t *)c->d_in16[set];
-		fstride = c->in16_stride * sizeof(uint32_t);
-	} else if (c->resamp) {  // 1536000 P / Q S/s u8 -> 1.536 MS/s int16 pairs, then the same cascade on int16 input
-		HIPCHK(launch_resample(fs, (const uint8_t *)d_iq, stride, c->cfg.n_streams, n_blocks, c->rate_p, c->rate_q, c->rate_t,
-				       c->d_rtaps, c->d_tailR[c->tail_sel], c->d_tailR[c->tail_sel ^ 1], c->d_in16[set], c->in16_stride,
-				       chan10 ? c->d_chan[set] : nullptr, c->n_wide != 0));
+	if (c->in16) {  // ... then the standard cascade on int16 input
+		TRY(launch_prestage(c, set, (const uint8_t *)d_iq, stride, n_blocks, chan10 ? c->d_chan[set] : nullptr));
 		fin = (const uint8_t *)c->d_in16[set];
 		fstride = c->in16_stride * sizeof(uint32_t);
 	}
@@ -1902,41 +1882,59 @@ int tfrec_amd_get_stream_config(tfrec_amd_ctx *c, int stream, tfrec_amd_stream_c
 	return TFREC_AMD_OK;
 }
 
-// inc = floor((tune_hz * 2^33 + 1536000) / 3072000) mod 2^32: the phase step per 1.536 MS/s sample in 2^-32 turns
-static uint32_t tune_inc(int32_t tune_hz)
+// The phase step per sample, in 2^-32 turns, of a tune of tune_hz at 1536000 P / Q samples per second:
+//   inc = floor((tune_hz * 2^33 * Q + 1536000 P) / (2 * 1536000 P)) mod 2^32
+// (DESIGN.md 6d at 1/1, 6e at 10/1, 6g at the input rate).  |tune_hz| < 7680000 and Q <= 64: the numerator stays below 2^63.
+static uint32_t phase_inc(int32_t tune_hz, long long p, long long q)
 {
-	const long long num = (long long)tune_hz * (1LL << 33) + 1536000, den = 3072000;
-	long long q = num / den;
+	const long long num = (long long)tune_hz * (1LL << 33) * q + 1536000LL * p, den = 2 * 1536000LL * p;
+	long long v = num / den;
 	if (num % den != 0 && num < 0)
-		q--;  // (floor, not C's truncation)
-	return (uint32_t)(uint64_t)q;
+		v--;  // (floor, not C's truncation)
+	return (uint32_t)(uint64_t)v;
+}
+
+// What the three tunes share, behind their own preconditions: every stream and tune checked (out_of_range(tune_hz) writes the
+// message) before anything changes; then hz / inc of the listed streams, their restart -- a tune is a reset with a new tune,
+// exactly as a configure is one with new settings -- and the count of tuned streams.
+static int tune_common(tfrec_amd_ctx *c, const int32_t *streams, const int32_t *tune_hz, int n, long long p, long long q,
+		       const std::function<bool(int32_t)> &out_of_range, std::vector<int32_t> &hz, std::vector<uint32_t> &inc, int &n_tuned)
+{
+	for (int i = 0; i < n; i++) {
+		TRY(check_stream(c, streams[i]));
+		if (out_of_range(tune_hz[i]))
+			return TFREC_AMD_E_INVAL;
+	}
+	TRY(check_live(c));
+	for (int i = 0; i < n; i++) {
+		const int s = streams[i];
+		hz[s] = tune_hz[i];
+		inc[s] = phase_inc(tune_hz[i], p, q);
+		mark_restart(c, s);
+	}
+	n_tuned = 0;
+	for (const uint32_t v : inc)
+		n_tuned += v != 0;
+	return TFREC_AMD_OK;
+}
+
+// |tune_hz| < limit, the message of the base and the wide tune
+static bool outside_limit(int32_t tune_hz, int limit)
+{
+	if (tune_hz > -limit && tune_hz < limit)
+		return false;
+	snprintf(g_err, sizeof(g_err), "tune_hz %d outside (-%d, %d)", (int)tune_hz, limit, limit);
+	return true;
 }
 
 int tfrec_amd_tune_streams(tfrec_amd_ctx *c, const int32_t *streams, const int32_t *tune_hz, int n)
 {
 	if (!c || n < 0 || (n > 0 && (!streams || !tune_hz)))
 		return TFREC_AMD_E_INVAL;
-	for (int i = 0; i < n; i++) {
-		TRY(check_stream(c, streams[i]));
-		if (tune_hz[i] <= -kTuneLimit || tune_hz[i] >= kTuneLimit) {
-			snprintf(g_err, sizeof(g_err), "tune_hz %d outside (-%d, %d)", (int)tune_hz[i], kTuneLimit, kTuneLimit);
-			return TFREC_AMD_E_INVAL;
-		}
-	}
-	TRY(check_live(c));
-	if (n == 0)
-		return TFREC_AMD_OK;
-	// a tune is a reset with a new tune, exactly as a configure is one with new settings
-	for (int i = 0; i < n; i++) {
-		const int s = streams[i];
-		c->tune_hz[s] = tune_hz[i];
-		c->tune_inc[s] = tune_inc(tune_hz[i]);
-		mark_restart(c, s);
-	}
-	c->n_tuned = 0;
-	for (const uint32_t inc : c->tune_inc)
-		c->n_tuned += inc != 0;
-	use_per_stream(c);
+	TRY(tune_common(c, streams, tune_hz, n, 1, 1, [](int32_t hz) { return outside_limit(hz, kTuneLimit); }, c->tune_hz, c->tune_inc,
+			c->n_tuned));
+	if (n > 0)
+		use_per_stream(c);
 	return TFREC_AMD_OK;
 }
 
@@ -1981,16 +1979,6 @@ int tfrec_amd_get_stream_input(tfrec_amd_ctx *c, int stream, int32_t *input)
 	return TFREC_AMD_OK;
 }
 
-// inc10 = floor((tune_hz * 2^33 + 15360000) / 30720000) mod 2^32: the phase step per 15.36 MS/s sample
-static uint32_t tune_inc10(int32_t tune_hz)
-{
-	const long long num = (long long)tune_hz * (1LL << 33) + 15360000, den = 30720000;
-	long long q = num / den;
-	if (num % den != 0 && num < 0)
-		q--;  // (floor, not C's truncation)
-	return (uint32_t)(uint64_t)q;
-}
-
 int tfrec_amd_tune_streams_wide(tfrec_amd_ctx *c, const int32_t *streams, const int32_t *tune_hz, int n)
 {
 	if (!c || n < 0 || (n > 0 && (!streams || !tune_hz)))
@@ -2000,26 +1988,8 @@ int tfrec_amd_tune_streams_wide(tfrec_amd_ctx *c, const int32_t *streams, const 
 			 c->resamp ? " (the tune ahead of the resampling stage is tfrec_amd_tune_streams_input)" : "");
 		return TFREC_AMD_E_INVAL;
 	}
-	for (int i = 0; i < n; i++) {
-		TRY(check_stream(c, streams[i]));
-		if (tune_hz[i] <= -kTuneWideLimit || tune_hz[i] >= kTuneWideLimit) {
-			snprintf(g_err, sizeof(g_err), "tune_hz %d outside (-%d, %d)", (int)tune_hz[i], kTuneWideLimit, kTuneWideLimit);
-			return TFREC_AMD_E_INVAL;
-		}
-	}
-	TRY(check_live(c));
-	if (n == 0)
-		return TFREC_AMD_OK;
-	for (int i = 0; i < n; i++) {
-		const int s = streams[i];
-		c->wide_hz[s] = tune_hz[i];
-		c->wide_inc[s] = tune_inc10(tune_hz[i]);
-		mark_restart(c, s);
-	}
-	c->n_wide = 0;
-	for (const uint32_t inc : c->wide_inc)
-		c->n_wide += inc != 0;
-	return TFREC_AMD_OK;
+	return tune_common(c, streams, tune_hz, n, 10, 1, [](int32_t hz) { return outside_limit(hz, kTuneWideLimit); }, c->wide_hz,
+			   c->wide_inc, c->n_wide);
 }
 
 int tfrec_amd_get_stream_tune_wide(tfrec_amd_ctx *c, int stream, int32_t *tune_hz)
@@ -2028,17 +1998,6 @@ int tfrec_amd_get_stream_tune_wide(tfrec_amd_ctx *c, int stream, int32_t *tune_h
 		return TFREC_AMD_E_INVAL;
 	*tune_hz = c->wide_hz[stream];
 	return TFREC_AMD_OK;
-}
-
-// inc_in = floor((tune_hz * 2^33 * Q + 1536000 P) / (2 * 1536000 P)) mod 2^32: the phase step per input sample at
-// 1536000 P / Q samples per second.  |tune_hz| < 7680000 and Q <= 64: the numerator stays below 2^63.
-static uint32_t tune_inc_in(int32_t tune_hz, long long p, long long q)
-{
-	const long long num = (long long)tune_hz * (1LL << 33) * q + 1536000LL * p, den = 2 * 1536000LL * p;
-	long long v = num / den;
-	if (num % den != 0 && num < 0)
-		v--;  // (floor, not C's truncation)
-	return (uint32_t)(uint64_t)v;
 }
 
 // The tune at the input rate, ahead of the resampling stage (6g); a 10x context's wide tune under another name
@@ -2058,28 +2017,14 @@ int tfrec_amd_tune_streams_input(tfrec_amd_ctx *c, const int32_t *streams, const
 		snprintf(g_err, sizeof(g_err), "input rate %lld/%lld: the int16 store of a tuned stream could wrap", p, q);
 		return TFREC_AMD_E_INVAL;
 	}
-	for (int i = 0; i < n; i++) {
-		TRY(check_stream(c, streams[i]));
-		const long long a = 2 * llabs((long long)tune_hz[i]) * q;
-		if (a >= 1536000LL * p) {  // |tune_hz| < fs_in / 2, in integers
-			snprintf(g_err, sizeof(g_err), "tune_hz %d outside half the input rate 1536000 * %lld / %lld (|tune_hz| < %lld)", (int)tune_hz[i],
-				 p, q, (1536000LL * p + 2 * q - 1) / (2 * q));
-			return TFREC_AMD_E_INVAL;
-		}
-	}
-	TRY(check_live(c));
-	if (n == 0)
-		return TFREC_AMD_OK;
-	for (int i = 0; i < n; i++) {
-		const int s = streams[i];
-		c->wide_hz[s] = tune_hz[i];
-		c->wide_inc[s] = tune_inc_in(tune_hz[i], p, q);
-		mark_restart(c, s);
-	}
-	c->n_wide = 0;
-	for (const uint32_t inc : c->wide_inc)
-		c->n_wide += inc != 0;
-	return TFREC_AMD_OK;
+	const auto outside = [p, q](int32_t hz) {  // |tune_hz| < fs_in / 2, in integers
+		if (2 * llabs((long long)hz) * q < 1536000LL * p)
+			return false;
+		snprintf(g_err, sizeof(g_err), "tune_hz %d outside half the input rate 1536000 * %lld / %lld (|tune_hz| < %lld)", (int)hz, p, q,
+			 (1536000LL * p + 2 * q - 1) / (2 * q));
+		return true;
+	};
+	return tune_common(c, streams, tune_hz, n, p, q, outside, c->wide_hz, c->wide_inc, c->n_wide);
 }
 
 int tfrec_amd_get_stream_tune_input(tfrec_amd_ctx *c, int stream, int32_t *tune_hz)

@@ -3,20 +3,26 @@
 //
 // A format maps one stored component (I or Q; little-endian, interleaved I, Q) to x, the int16 value every stage is defined on,
 // -8192 <= x <= 8191 (include/tfrec_amd.h: tfrec_amd_create_format the normative text, tfrec_amd/formats.py the CPU restatement):
-//   S8   x = s8 << 6                      S16  x = s16 >> 2 (arithmetic)
-//   F32  v = f * 8192 in fp32, x = clamp(rint(v), -8192, 8191), ties to even, NaN -> 0
-// U8 never comes here: a U8 context is tfrec_amd_create_rate's or tfrec_amd_create's, with the kernels those launch.
-//   * resample_fmt_kernel<FMT> is resample_kernel<true> (resample.h) with the chunk load and the conversion to x in front: the
+//   U8   x = (u8 - 128) << 6              S8   x = s8 << 6
+//   S16  x = s16 >> 2 (arithmetic)        F32  v = f * 8192 in fp32, x = clamp(rint(v), -8192, 8191), ties to even, NaN -> 0
+//   * resample_fmt_kernel<FMT> is the resampling stage (resample.h) with the chunk load and the conversion to x in front: the
 //     tile is staged into LDS as the int16 (I, Q) image, one dword per complex sample; a chunk of 8 complex samples is 16, 32 or
-//     64 bytes of input; a tuned stream's samples are rotated once while they are staged (4 x as the int16 halves, two
-//     v_dot2_i32_i16, + 2^16 >> 17: |4 x| <= 32768, and |C| + |S| < 2^15.6 keeps the dot product in int32); the taps run as
-//     fma(x', h / 65536, acc) on the 2^23 + 2^22 accumulator in round-toward-minus-infinity mode.  The history is 64 complex
-//     samples per stream of canonical x (256 bytes; x = 0 after a start or restart), so one kernel reads the history of every
-//     format alike.  The cosine table is staged, and its 8 KB of LDS asked for, only by a launch with a tuned stream.
-//   * ingest_kernel<FMT> (base rate, 1/1) converts each stream's row into the stage-0 buffer frontend_kernel<true, ...> reads.
-constexpr int kFmtU8 = 0, kFmtS8 = 1, kFmtS16 = 2, kFmtF32 = 3;
+//     64 bytes of input; a tuned stream's samples (6g: chan[s].x = inc_in != 0) are rotated once while they are staged (mixer.h),
+//     with the phase of their own n -- negative for a history sample -- and the history keeps the unrotated input; an untuned
+//     stream of the launch comes out as an untuned launch makes it.  The taps run as fma(x', h / 65536, acc) on the 2^23 + 2^22
+//     accumulator in round-toward-minus-infinity mode: |h| < 2^17, so h / 65536 is exact in fp32; the FMA rounds once after the
+//     exact product and the accumulator is integer-valued, so each tap floors its own term; and every partial sum is at most
+//     max_phi sum |h| * 11585 >> 16 <= 19111 (108112 at 65/64 is the largest sum |h| of any accepted rate; the tune is refused
+//     where the bound reaches 32768), which keeps the accumulator in [2^23, 2^24) and the int16 store from wrapping.
+//     The history is 64 complex samples per stream: of canonical x (256 bytes; x = 0 after a start or restart) for S8, S16 and
+//     F32, so one loop reads the history of those formats alike -- and the RAW 128 bytes (0x80 after a start or restart) for U8,
+//     read through the format's own loader.  A U8 context runs this kernel only while a stream is tuned and resample_kernel
+//     otherwise: both read and write that one history, so an untuned stream's survives the change in both directions.
+//     The cosine table is staged, and its 8 KB of LDS asked for, only by a launch with a tuned stream.
+//   * ingest_kernel<FMT> (base rate, 1/1; never U8, whose rows the front end reads as they are) converts each stream's row into
+//     the stage-0 buffer frontend_kernel<true, ...> reads.
 constexpr int kFmtTailDw = 64;  // history per stream: 64 complex samples of x, one dword each (T - 1 <= 59 needed)
-__host__ __device__ constexpr int fmt_sample_bytes(int fmt) { return fmt == kFmtF32 ? 8 : fmt == kFmtS16 ? 4 : 2; }
+static_assert(kRsTail == 2 * kFmtTailDw, "the raw u8 history holds the same 64 samples");
 
 // One fp32 component -> x in the low 16 bits.  None of this depends on the fp32 rounding mode the tap loop sets: a product with a
 // power of two is exact (where it overflows, every mode gives a value beyond the clamp), v_rndne_f32 rounds to the nearest
@@ -28,55 +34,60 @@ __device__ __forceinline__ uint32_t fmt_f32_x(float f)
 	return (uint32_t)(v != v ? 0 : (int)r) & 0xffffu;
 }
 
-// 8 complex samples at src (16-byte aligned) -> x as 8 dwords, I in the low half and Q in the high one
-template <int FMT>
+// 8 complex samples at src (16-byte aligned) -> x as 8 dwords, I in the low half and Q in the high one; X4: 4 x instead, the form
+// mixer_rotate takes (what the 8-bit formats' permute makes anyway)
+template <int FMT, bool X4 = false>
 __device__ __forceinline__ void fmt_load8(const uint8_t *__restrict__ src, uint32_t (&o)[8])
 {
 	const uint4 *p = reinterpret_cast<const uint4 *>(src);
-	if constexpr (FMT == kFmtS8) {
+	if constexpr (FMT == kFmtU8 || FMT == kFmtS8) {
+		constexpr uint32_t kFlip = FMT == kFmtU8 ? 0x80808080u : 0u;  // u8 - 128 as two's complement
 		const uint4 v = p[0];
-		const uint32_t w[4] = { v.x, v.y, v.z, v.w };
+		const uint32_t w[4] = { v.x ^ kFlip, v.y ^ kFlip, v.z ^ kFlip, v.w ^ kFlip };
 #pragma unroll
-		for (int i = 0; i < 8; i++) {  // (b << 8) >> 2 per half = b << 6
-			const uint32_t x4 = __builtin_amdgcn_perm(0u, w[i / 2], (i & 1) ? 0x030c020cu : 0x010c000cu);
-			o[i] = ((uint32_t)((int)(int16_t)(x4 & 0xffffu) >> 2) & 0xffffu) | ((uint32_t)((int)x4 >> 18) << 16);
-		}
+		for (int i = 0; i < 8; i++)  // (b << 8) >> 2 per half = b << 6
+			o[i] = X4 ? mixer_b8(w[i / 2], i & 1) : mixer_x(mixer_b8(w[i / 2], i & 1));
 	} else if constexpr (FMT == kFmtS16) {
 		const uint4 a = p[0], b = p[1];
 		const uint32_t w[8] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
 #pragma unroll
 		for (int i = 0; i < 8; i++)
-			o[i] = ((uint32_t)((int)(int16_t)(w[i] & 0xffffu) >> 2) & 0xffffu) | ((uint32_t)((int)w[i] >> 18) << 16);
+			o[i] = X4 ? w[i] & 0xfffcfffcu : mixer_x(w[i]);
 	} else {
-		static_assert(FMT == kFmtF32, "U8 has kernels of its own");
+		static_assert(FMT == kFmtF32, "four formats");
 #pragma unroll
 		for (int k = 0; k < 4; k++) {
 			const uint4 v = p[k];
-			o[2 * k] = fmt_f32_x(__uint_as_float(v.x)) | (fmt_f32_x(__uint_as_float(v.y)) << 16);
-			o[2 * k + 1] = fmt_f32_x(__uint_as_float(v.z)) | (fmt_f32_x(__uint_as_float(v.w)) << 16);
+			const uint32_t x0 = fmt_f32_x(__uint_as_float(v.x)) | (fmt_f32_x(__uint_as_float(v.y)) << 16);
+			const uint32_t x1 = fmt_f32_x(__uint_as_float(v.z)) | (fmt_f32_x(__uint_as_float(v.w)) << 16);
+			o[2 * k] = X4 ? mixer_x4(x0) : x0;
+			o[2 * k + 1] = X4 ? mixer_x4(x1) : x1;
 		}
 	}
 }
 
 // `chan` (nullptr: stream s reads row s, nothing is tuned): {inc_in, phase of the submit's first input sample, input row, 0} per
-// stream, as resample_kernel<true> reads it; `tuned`: a stream of the launch has inc_in != 0 and the launch's LDS holds the table.
+// stream; `tuned`: a stream of the launch has inc_in != 0 and the launch's LDS holds the table.  The history: kFmtTailDw dwords of
+// x per stream, or -- U8 -- kRsTail raw bytes.
 template <int FMT>
 __global__ __launch_bounds__(kRsThreads) void resample_fmt_kernel(const uint8_t *__restrict__ iq, size_t stride, long n_in, int p, int q,
-								  int t, const float *__restrict__ taps, const uint32_t *__restrict__ tail_in,
-								  uint32_t *__restrict__ tail_out, uint32_t *__restrict__ out, size_t out_stride,
+								  int t, const float *__restrict__ taps, const uint8_t *__restrict__ tail_in,
+								  uint8_t *__restrict__ tail_out, uint32_t *__restrict__ out, size_t out_stride,
 								  const uint4 *__restrict__ chan, int tuned)
 {
 	constexpr int kBps = fmt_sample_bytes(FMT);
+	constexpr bool kRawHist = FMT == kFmtU8;
+	constexpr int kHistBps = kRawHist ? kBps : 4;  // bytes per complex sample of the history
 	extern __shared__ __attribute__((aligned(16))) uint32_t fmt_lds[];
 	float *htab = reinterpret_cast<float *>(fmt_lds);
 	uint32_t *raw = fmt_lds + rs_taps_dw(q, t);
 	typedef float f32x2 __attribute__((ext_vector_type(2)));
-	typedef short s16x2 __attribute__((ext_vector_type(2)));
 	const int s = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
 	const int nthreads = (int)blockDim.x, tile_n = kRsOut * (int)blockDim.x;
 	__builtin_amdgcn_s_setreg(1 | (0 << 6) | (1 << 11), 2);  // fp32 rounding toward -inf (see frontend_kernel, stage 1)
 	const long m0 = (long)tile * tile_n;
 	const uint8_t *src = iq + (size_t)(chan ? chan[s].z : (uint32_t)s) * stride;
+	const uint8_t *hist = tail_in + (size_t)s * (kFmtTailDw * kHistBps);
 	for (int i = tid; i < q * t; i += nthreads)
 		htab[i] = taps[i] * (1.0f / 64.0f);  // (h / 1024 -> h / 65536: exact)
 	// ---- the tile's first output: a = m0 P in 64 bits
@@ -90,46 +101,60 @@ __global__ __launch_bounds__(kRsThreads) void resample_fmt_kernel(const uint8_t 
 	const uint32_t tinc = (tuned && chan) ? chan[s].x : 0u, tph = chan ? chan[s].y : 0u;
 	int16_t *ctab = reinterpret_cast<int16_t *>(raw + 8 * rs_raw_chunks(p, q, t, tile_n));
 	if (tinc != 0) {  // (uniform for the workgroup)
-		for (int i = tid; i < kTuneN / 2; i += nthreads)
-			reinterpret_cast<uint32_t *>(ctab)[i] = (uint32_t)(uint16_t)kTuneCos[2 * i] | ((uint32_t)(uint16_t)kTuneCos[2 * i + 1] << 16);
+		mixer_stage_table(ctab, tid, nthreads);
 		__syncthreads();
 	}
-	for (int c = tid; c < nchunks; c += nthreads) {
-		const long so = b0 + 8L * c;  // a chunk lies wholly in the history or wholly in the submit (both are multiples of 8 samples)
-		uint32_t o8[8] = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u };
+	// the chunk at sample `so` of the submit as x (or 4 x): it lies wholly in the history or wholly in the submit (both are multiples
+	// of 8 samples); silence elsewhere
+	auto chunk = [&](auto x4, long so, uint32_t (&o8)[8]) {
+		constexpr bool kX4 = decltype(x4)::value;
 		if (so >= 0 && so + 8 <= n_in) {
-			fmt_load8<FMT>(src + (size_t)so * kBps, o8);
+			fmt_load8<FMT, kX4>(src + (size_t)so * kBps, o8);
 		} else if (so < 0 && so >= -kFmtTailDw) {
-			const uint4 *h = reinterpret_cast<const uint4 *>(tail_in + (size_t)s * kFmtTailDw + (kFmtTailDw + so));
-			const uint4 a = h[0], b = h[1];
-			o8[0] = a.x, o8[1] = a.y, o8[2] = a.z, o8[3] = a.w, o8[4] = b.x, o8[5] = b.y, o8[6] = b.z, o8[7] = b.w;
+			const uint8_t *h = hist + (kFmtTailDw + so) * kHistBps;
+			if constexpr (kRawHist) {
+				fmt_load8<FMT, kX4>(h, o8);
+			} else {
+				const uint4 a = reinterpret_cast<const uint4 *>(h)[0], b = reinterpret_cast<const uint4 *>(h)[1];
+				const uint32_t w[8] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
+#pragma unroll
+				for (int i = 0; i < 8; i++)
+					o8[i] = kX4 ? mixer_x4(w[i]) : w[i];
+			}
+		} else {
+#pragma unroll
+			for (int i = 0; i < 8; i++)
+				o8[i] = 0u;
 		}
+	};
+	for (int c = tid; c < nchunks; c += nthreads) {
+		const long so = b0 + 8L * c;
+		uint32_t o8[8];
 		if (tinc != 0) {  // the chunk's first sample is input sample so of the submit
+			chunk(std::true_type{}, so, o8);
 			const uint32_t p0 = tph + (uint32_t)(int)so * tinc;
 #pragma unroll
-			for (int i = 0; i < 8; i++) {
-				const uint32_t ph = p0 + (uint32_t)i * tinc;
-				const uint32_t k = ph >> (32 - TFREC_TUNE_BITS);
-				const int C = ctab[k], S = ctab[(k - kTuneN / 4) & (kTuneN - 1)];
-				const uint32_t cs = ((uint32_t)C & 0xffffu) | ((uint32_t)S << 16);   // (C, S)
-				const uint32_t sc = ((uint32_t)-S & 0xffffu) | ((uint32_t)C << 16);  // (-S, C)
-				const uint32_t x4 = (o8[i] << 2) & 0xfffcfffcu;                      // (4 I, 4 Q)
-				const int vi = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, x4), __builtin_bit_cast(s16x2, cs), 1 << 16, false) >> 17;
-				const int vq = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, x4), __builtin_bit_cast(s16x2, sc), 1 << 16, false) >> 17;
-				o8[i] = ((uint32_t)vi & 0xffffu) | ((uint32_t)vq << 16);
-			}
+			for (int i = 0; i < 8; i++)
+				o8[i] = mixer_rotate(ctab, o8[i], p0 + (uint32_t)i * tinc);
+		} else {
+			chunk(std::false_type{}, so, o8);
 		}
 		uint32_t *d = raw + 8 * c;
 		reinterpret_cast<uint4 *>(d)[0] = make_uint4(o8[0], o8[1], o8[2], o8[3]);
 		reinterpret_cast<uint4 *>(d)[1] = make_uint4(o8[4], o8[5], o8[6], o8[7]);
 	}
-	// history for the next submit: the last 64 complex samples of this one as x, unrotated (n_in >= 32768, a multiple of 8)
+	// history for the next submit: the last 64 complex samples of this one, unrotated (n_in >= 32768, a multiple of 8)
 	if (tile == (int)gridDim.x - 1 && tid < kFmtTailDw / 8) {
-		uint32_t o8[8];
-		fmt_load8<FMT>(src + (size_t)(n_in - kFmtTailDw + 8 * tid) * kBps, o8);
-		uint4 *d = reinterpret_cast<uint4 *>(tail_out + (size_t)s * kFmtTailDw + 8 * tid);
-		d[0] = make_uint4(o8[0], o8[1], o8[2], o8[3]);
-		d[1] = make_uint4(o8[4], o8[5], o8[6], o8[7]);
+		const uint8_t *last = src + (size_t)(n_in - kFmtTailDw + 8 * tid) * kBps;
+		uint4 *d = reinterpret_cast<uint4 *>(tail_out + (size_t)s * (kFmtTailDw * kHistBps) + 8 * kHistBps * tid);
+		if constexpr (kRawHist) {
+			d[0] = *reinterpret_cast<const uint4 *>(last);
+		} else {
+			uint32_t o8[8];
+			fmt_load8<FMT>(last, o8);
+			d[0] = make_uint4(o8[0], o8[1], o8[2], o8[3]);
+			d[1] = make_uint4(o8[4], o8[5], o8[6], o8[7]);
+		}
 	}
 	__syncthreads();
 	// ---- the lane's outputs m0 + 8 tid + o: sample i0 - (T-1) + n is dword sh + (i0 - i00) + n of the image
@@ -192,10 +217,32 @@ __global__ __launch_bounds__(kIngestThreads) void ingest_kernel(const uint8_t *_
 	d[1] = make_uint4(o8[4], o8[5], o8[6], o8[7]);
 }
 
-// fmt: kFmtS8, kFmtS16 or kFmtF32; the rest as launch_resample, with the history in dwords of x.  One geometry per rate, tuned
-// or not: half the tile where the image of a whole one and the cosine table exceed the LDS limit (resample.h).
+// fmt -> f(std::integral_constant<int, fmt>{}); false: no such format (U8: only where the caller has a U8 instantiation)
+template <bool U8, class F>
+bool fmt_dispatch(int fmt, F f)
+{
+	switch (fmt) {
+	case kFmtU8:
+		if constexpr (U8)
+			f(std::integral_constant<int, kFmtU8>{});
+		return U8;
+	case kFmtS8:
+		f(std::integral_constant<int, kFmtS8>{});
+		return true;
+	case kFmtS16:
+		f(std::integral_constant<int, kFmtS16>{});
+		return true;
+	case kFmtF32:
+		f(std::integral_constant<int, kFmtF32>{});
+		return true;
+	}
+	return false;
+}
+
+// The arguments of launch_resample with the format in front; the history is the format's (above).  One geometry per rate, tuned or
+// not: half the tile where the image of a whole one and the cosine table exceed the LDS limit (resample.h).
 hipError_t launch_resample_fmt(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, int p, int q, int t,
-			       const float *taps, const uint32_t *tail_in, uint32_t *tail_out, uint32_t *out, size_t out_stride,
+			       const float *taps, const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride,
 			       const uint4 *chan, bool tuned)
 {
 	const long n_out = (long)n_blocks * (TFREC_AMD_BLOCK_BYTES / 2);  // complex samples at 1.536 MS/s
@@ -205,21 +252,11 @@ hipError_t launch_resample_fmt(hipStream_t st, int fmt, const uint8_t *iq, size_
 	const int tile = rs_tuned_lds(p, q, t, kRsTile) <= kRsLdsMax ? kRsTile : kRsTile / 2;
 	const size_t lds = (size_t)rs_tuned_lds(p, q, t, tile) - (tuned ? 0 : 2 * kTuneN);
 	const dim3 grid((unsigned)(n_out / tile), n_streams), block(tile / kRsOut);
-	const int tn = tuned ? 1 : 0;
-	switch (fmt) {
-	case kFmtS8:
-		hipLaunchKernelGGL(resample_fmt_kernel<kFmtS8>, grid, block, lds, st, iq, stride, n_in, p, q, t, taps, tail_in, tail_out, out, out_stride, chan, tn);
-		break;
-	case kFmtS16:
-		hipLaunchKernelGGL(resample_fmt_kernel<kFmtS16>, grid, block, lds, st, iq, stride, n_in, p, q, t, taps, tail_in, tail_out, out, out_stride, chan, tn);
-		break;
-	case kFmtF32:
-		hipLaunchKernelGGL(resample_fmt_kernel<kFmtF32>, grid, block, lds, st, iq, stride, n_in, p, q, t, taps, tail_in, tail_out, out, out_stride, chan, tn);
-		break;
-	default:
-		return hipErrorInvalidValue;
-	}
-	return hipGetLastError();
+	const bool known = fmt_dispatch<true>(fmt, [&](auto f) {
+		hipLaunchKernelGGL(resample_fmt_kernel<decltype(f)::value>, grid, block, lds, st, iq, stride, n_in, p, q, t, taps, tail_in, tail_out,
+				   out, out_stride, chan, tuned ? 1 : 0);
+	});
+	return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_ingest(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, uint32_t *out,
@@ -227,18 +264,8 @@ hipError_t launch_ingest(hipStream_t st, int fmt, const uint8_t *iq, size_t stri
 {
 	const long n_chunks = (long)n_blocks * (TFREC_AMD_BLOCK_BYTES / 2) / 8;
 	const dim3 grid((unsigned)((n_chunks + kIngestThreads - 1) / kIngestThreads), n_streams), block(kIngestThreads);
-	switch (fmt) {
-	case kFmtS8:
-		hipLaunchKernelGGL(ingest_kernel<kFmtS8>, grid, block, 0, st, iq, stride, n_chunks, out, out_stride, chan);
-		break;
-	case kFmtS16:
-		hipLaunchKernelGGL(ingest_kernel<kFmtS16>, grid, block, 0, st, iq, stride, n_chunks, out, out_stride, chan);
-		break;
-	case kFmtF32:
-		hipLaunchKernelGGL(ingest_kernel<kFmtF32>, grid, block, 0, st, iq, stride, n_chunks, out, out_stride, chan);
-		break;
-	default:
-		return hipErrorInvalidValue;
-	}
-	return hipGetLastError();
+	const bool known = fmt_dispatch<false>(fmt, [&](auto f) {
+		hipLaunchKernelGGL(ingest_kernel<decltype(f)::value>, grid, block, 0, st, iq, stride, n_chunks, out, out_stride, chan);
+	});
+	return known ? hipGetLastError() : hipErrorInvalidValue;
 }

@@ -47,6 +47,7 @@ typedef uint32_t u32x4_u __attribute__((ext_vector_type(4), aligned(4)));  // 16
 // digital tuning: C[k] = round(32767 cos(2 pi k / 4096)); S[k] = C[(k - 1024) mod 4096]
 __device__ __constant__ const int16_t kTuneCos[1 << TFREC_TUNE_BITS] = { TFREC_TUNE_COS_TABLE };
 constexpr int kTuneN = 1 << TFREC_TUNE_BITS;
+#include "mixer.h"  // the pre-stages' phase mixer (decim10_kernel<true>, resample_fmt_kernel)
 
 // IN16 = false: raw input is u8 IQ, x = (u8 - 128) << 6 (engine.cpp:77-78).  IN16 = true: the input already is
 // int16 (I,Q) pairs at 1.536 MS/s (what decim10_kernel produces for BASELINE config 5): 4 bytes per complex
@@ -557,7 +558,7 @@ __device__ __constant__ const int kTaps10[60] = {
 // TUNE = true (a stream of the context has a wide tune, tfrec_amd_tune_streams_wide, or reads another stream's
 // input row, tfrec_amd_map_streams): `chan` holds per stream {inc10, phase of the submit's first input sample, input row, 0}.
 // The tile is staged into LDS as an int16 (I, Q) image, one dword per complex sample, and every sample of a tuned stream is
-// rotated ONCE while it is staged (6d's mixer at the input rate: p = phase + n * inc10, k = p >> 20, the u8 sample as
+// rotated ONCE while it is staged (mixer.h -- 6d's mixer at the input rate: p = phase + n * inc10, k = p >> 20, the u8 sample as
 // packed b << 8 = 4 x, two v_dot2_i32_i16 with a shift by 17 instead of 15; |I'|, |Q'| <= 11585: nothing saturates), an
 // untuned one (inc10 = 0) is widened to x = (u8 - 128) << 6.  The taps then run in their int16 form, (x' * h) >> 16 per
 // tap: the same FMA onto the same accumulator, the product exact whatever its width.  The history (tail) stays raw u8:
@@ -590,11 +591,10 @@ __global__ __launch_bounds__(kThreads10) void decim10_kernel(const uint8_t *__re
 		tinc = ch.x;
 		tph = ch.y;
 		src = iq + (size_t)ch.z * stride;
-		if (tinc != 0)  // (uniform for the workgroup; the barrier behind the staging loop covers the table too)
-			for (int i = tid; i < kTuneN / 2; i += kThreads10)
-				reinterpret_cast<uint32_t *>(ctab)[i] = (uint32_t)(uint16_t)kTuneCos[2 * i] | ((uint32_t)(uint16_t)kTuneCos[2 * i + 1] << 16);
-		if (tinc != 0)
+		if (tinc != 0) {  // (uniform for the workgroup)
+			mixer_stage_table(ctab, tid, kThreads10);
 			__syncthreads();
+		}
 	}
 	// ---- stage the tile: chunk c = logical dwords 4c .. 4c + 3 = stream bytes 20 m0 - 112 + 16 c ..; the submit's first
 	// tile takes its first seven chunks from the previous submit's tail
@@ -609,29 +609,17 @@ __global__ __launch_bounds__(kThreads10) void decim10_kernel(const uint8_t *__re
 						: *reinterpret_cast<const uint4 *>(tail_in + (size_t)s * kTail10 + (kTail10 + bo));
 			if constexpr (TUNE) {
 				// the chunk's 8 samples = image dwords 8c .. 8c + 7; the first is input sample 10 m0 - 56 + 8c of the submit
-				typedef short s16x2 __attribute__((ext_vector_type(2)));
 				uint32_t *d = raw + 8 * c + c / (kLaneS10 / 8);
 				const uint32_t w4[4] = { v.x ^ 0x80808080u, v.y ^ 0x80808080u, v.z ^ 0x80808080u, v.w ^ 0x80808080u };
 				if (tinc == 0) {
 #pragma unroll
-					for (int i = 0; i < 8; i++) {  // (b << 8) >> 2 per half = b << 6
-						const uint32_t x4 = __builtin_amdgcn_perm(0u, w4[i / 2], (i & 1) ? 0x030c020cu : 0x010c000cu);
-						d[i] = ((uint32_t)((int)(int16_t)(x4 & 0xffffu) >> 2) & 0xffffu) | ((uint32_t)((int)x4 >> 18) << 16);
-					}
+					for (int i = 0; i < 8; i++)
+						d[i] = mixer_x(mixer_b8(w4[i / 2], i & 1));
 				} else {
 					const uint32_t p0 = tph + (uint32_t)(10 * (int)m0 - kTail10 / 2 + 8 * c) * tinc;
 #pragma unroll
-					for (int i = 0; i < 8; i++) {
-						const uint32_t p = p0 + (uint32_t)i * tinc;
-						const uint32_t k = p >> (32 - TFREC_TUNE_BITS);
-						const int C = ctab[k], S = ctab[(k - kTuneN / 4) & (kTuneN - 1)];
-						const uint32_t cs = ((uint32_t)C & 0xffffu) | ((uint32_t)S << 16);   // (C, S)
-						const uint32_t sc = ((uint32_t)-S & 0xffffu) | ((uint32_t)C << 16);  // (-S, C)
-						const uint32_t x4 = __builtin_amdgcn_perm(0u, w4[i / 2], (i & 1) ? 0x030c020cu : 0x010c000cu);
-						const int vi = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, x4), __builtin_bit_cast(s16x2, cs), 1 << 16, false) >> 17;
-						const int vq = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, x4), __builtin_bit_cast(s16x2, sc), 1 << 16, false) >> 17;
-						d[i] = ((uint32_t)vi & 0xffffu) | ((uint32_t)vq << 16);
-					}
+					for (int i = 0; i < 8; i++)
+						d[i] = mixer_rotate(ctab, mixer_b8(w4[i / 2], i & 1), p0 + (uint32_t)i * tinc);
 				}
 			} else {
 			uint32_t *d = raw + 4 * c + c / (kLaneDw10 / 4);

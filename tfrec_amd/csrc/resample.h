@@ -22,6 +22,8 @@
 //     from it (the offset is below 2^20), and the lane steps (i0, phi) by (P div Q, P mod Q) from there;
 //   * a lane makes kRsOut = 8 consecutive outputs, tap by tap: the eight FMAs of a tap go to eight accumulators.
 // `chan` (nullptr: stream s reads row s): the {.., .., input row, ..} of tfrec_amd_map_streams, as decim10_kernel<true> reads it.
+// resample_kernel is the kernel of a u8 context in which no stream has an input-rate tune (6g).  While one has, the context runs
+// resample_fmt_kernel<kFmtU8> (formats.h) on the same raw history instead: it rotates the tuned streams as it stages them.
 constexpr int kRsOut = 8;                      // outputs per lane
 constexpr int kRsTile = 1024;                  // outputs per workgroup
 constexpr int kRsThreads = kRsTile / kRsOut;   // 128
@@ -33,27 +35,13 @@ constexpr int kRsQMax = 64, kRsTMax = 60;
 __host__ __device__ constexpr int rs_taps_dw(int q, int t) { return (q * t + 3) & ~3; }
 __host__ __device__ constexpr int rs_raw_chunks(int p, int q, int t, int tile = kRsTile) { return (2 * ((q - 1 + (tile - 1) * p) / q + t) + 14 + 15) / 16; }
 static_assert((rs_taps_dw(kRsQMax, kRsTMax) + 4 * rs_raw_chunks(10 * kRsQMax - 1, kRsQMax, kRsTMax)) * 4 <= 48 * 1024, "fits the default LDS limit");
-// ... and of a tuned launch (resample_kernel<true>): the table, the int16 image (8 dwords per chunk) and the cosine table
+// ... and of the format-aware launch (formats.h: resample_fmt_kernel, which also is the tuned kernel of a u8 context): the table, the
+// int16 image (8 dwords per chunk) and the cosine table.  Where that exceeds 48 KB with a tile of 1024 outputs (the large rates)
+// the launch uses 64-thread workgroups and tiles of 512: at most 44.3 KB (639/64), so no rate needs more than the default LDS limit.
 constexpr int kRsLdsMax = 48 * 1024;
 __host__ __device__ constexpr int rs_tuned_lds(int p, int q, int t, int tile) { return (rs_taps_dw(q, t) + 8 * rs_raw_chunks(p, q, t, tile)) * 4 + 2 * kTuneN; }
 static_assert(rs_tuned_lds(10 * kRsQMax - 1, kRsQMax, kRsTMax, kRsTile / 2) <= kRsLdsMax, "the half tile serves the largest rate");
 
-// TUNE = true (a stream of the context has an input-rate tune, tfrec_amd_tune_streams_input): `chan` holds per
-// stream {inc_in, phase of the submit's first input sample, input row, 0}.  As in decim10_kernel<true> the tile is staged into
-// LDS as an int16 (I, Q) image, one dword per complex sample, and every sample of a tuned stream is rotated ONCE while it is
-// staged (6d's mixer at the input rate: p = phase + n * inc_in, k = p >> 20, the u8 sample as packed b << 8 = 4 x, two
-// v_dot2_i32_i16 with a shift by 17 instead of 15; |I'|, |Q'| <= 11585: nothing saturates); an untuned stream of the launch
-// (inc_in = 0) is widened to x = (u8 - 128) << 6 and comes out as the untuned kernel makes it.  The history stays raw u8: a
-// history sample is rotated with its own n (negative from the submit's phase), and 0x80 -- silence after a restart -- rotates
-// to 0.  The taps run in their int16 form, fma(x', h / 65536, acc) in the same rounding mode on the same accumulator:
-// |h| < 2^17, so h / 65536 is exact in fp32; the FMA rounds once after the exact product and the accumulator is
-// integer-valued, so each tap floors its own term; and every partial sum is at most max_phi sum |h| * 11585 >> 16 <= 19111
-// (108112 at 65/64 is the largest sum |h| of any accepted rate; the call is refused where the bound reaches 32768), which keeps
-// the accumulator in [2^23, 2^24) and the int16 store from wrapping.  LDS of a launch: the table (h / 65536), the image --
-// twice the raw one -- and the cosine table as 4096 int16 (8 KB; S[k] is C[k - 1024]) behind it.  Where that exceeds 48 KB
-// with a tile of 1024 outputs (the large rates) the launch uses 64-thread workgroups and tiles of 512: at most 44.3 KB
-// (639/64), so no rate needs more than the default LDS limit.  TUNE = false is the kernel as it was.
-template <bool TUNE>
 __global__ __launch_bounds__(kRsThreads) void resample_kernel(const uint8_t *__restrict__ iq, size_t stride, long n_in, int p, int q,
 							      int t, const float *__restrict__ taps, const uint8_t *__restrict__ tail_in,
 							      uint8_t *__restrict__ tail_out, uint32_t *__restrict__ out, size_t out_stride,
@@ -64,13 +52,13 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(const uint8_t *__r
 	uint32_t *raw = rs_lds + rs_taps_dw(q, t);
 	typedef float f32x2 __attribute__((ext_vector_type(2)));
 	const int s = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
-	const int nthreads = TUNE ? (int)blockDim.x : kRsThreads, tile_n = TUNE ? kRsOut * (int)blockDim.x : kRsTile;
+	const int nthreads = kRsThreads, tile_n = kRsTile;
 	__builtin_amdgcn_s_setreg(1 | (0 << 6) | (1 << 11), 2);  // fp32 rounding toward -inf (see frontend_kernel, stage 1)
 	const long m0 = (long)tile * tile_n;
 	const long nbytes = 2 * n_in;
 	const uint8_t *src = iq + (size_t)(chan ? chan[s].z : (uint32_t)s) * stride;
 	for (int i = tid; i < q * t; i += nthreads)
-		htab[i] = TUNE ? taps[i] * (1.0f / 64.0f) : taps[i];  // (h / 1024 -> h / 65536: exact)
+		htab[i] = taps[i];
 	// ---- the tile's first output: a = m0 P in 64 bits
 	const unsigned long long a0 = (unsigned long long)m0 * (unsigned)p;
 	const long i00 = (long)(a0 / (unsigned)q);
@@ -79,18 +67,6 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(const uint8_t *__r
 	const long b0 = (2 * lo) & ~15L;  // ... and the 16-byte boundary at or below it
 	const long hi = i00 + (long)((phi0 + (unsigned)(tile_n - 1) * (unsigned)p) / (unsigned)q);  // its last sample: i0(m0 + 1023) < n_in
 	const int nchunks = min((int)((2 * (hi + 1) - b0 + 15) >> 4), rs_raw_chunks(p, q, t, tile_n));
-	uint32_t tinc = 0, tph = 0;
-	int16_t *ctab = nullptr;
-	if constexpr (TUNE) {
-		tinc = chan[s].x;
-		tph = chan[s].y;
-		ctab = reinterpret_cast<int16_t *>(raw + 8 * rs_raw_chunks(p, q, t, tile_n));
-		if (tinc != 0) {  // (uniform for the workgroup)
-			for (int i = tid; i < kTuneN / 2; i += nthreads)
-				reinterpret_cast<uint32_t *>(ctab)[i] = (uint32_t)(uint16_t)kTuneCos[2 * i] | ((uint32_t)(uint16_t)kTuneCos[2 * i + 1] << 16);
-			__syncthreads();
-		}
-	}
 	for (int c = tid; c < nchunks; c += nthreads) {
 		const long bo = b0 + 16L * c;  // a chunk lies wholly in the history or wholly in the submit (both are 16-byte multiples)
 		uint4 v = make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
@@ -98,38 +74,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(const uint8_t *__r
 			v = *reinterpret_cast<const uint4 *>(src + bo);
 		else if (bo < 0 && bo >= -kRsTail)
 			v = *reinterpret_cast<const uint4 *>(tail_in + (size_t)s * kRsTail + (kRsTail + bo));
-		if constexpr (TUNE) {
-			// the chunk's 8 samples = image dwords 8c .. 8c + 7; the first is input sample bo / 2 of the submit
-			typedef short s16x2 __attribute__((ext_vector_type(2)));
-			uint32_t *d = raw + 8 * c;
-			const uint32_t w4[4] = { v.x ^ 0x80808080u, v.y ^ 0x80808080u, v.z ^ 0x80808080u, v.w ^ 0x80808080u };
-			uint32_t o8[8];
-			if (tinc == 0) {
-#pragma unroll
-				for (int i = 0; i < 8; i++) {  // (b << 8) >> 2 per half = b << 6
-					const uint32_t x4 = __builtin_amdgcn_perm(0u, w4[i / 2], (i & 1) ? 0x030c020cu : 0x010c000cu);
-					o8[i] = ((uint32_t)((int)(int16_t)(x4 & 0xffffu) >> 2) & 0xffffu) | ((uint32_t)((int)x4 >> 18) << 16);
-				}
-			} else {
-				const uint32_t p0 = tph + (uint32_t)(int)(bo >> 1) * tinc;
-#pragma unroll
-				for (int i = 0; i < 8; i++) {
-					const uint32_t ph = p0 + (uint32_t)i * tinc;
-					const uint32_t k = ph >> (32 - TFREC_TUNE_BITS);
-					const int C = ctab[k], S = ctab[(k - kTuneN / 4) & (kTuneN - 1)];
-					const uint32_t cs = ((uint32_t)C & 0xffffu) | ((uint32_t)S << 16);   // (C, S)
-					const uint32_t sc = ((uint32_t)-S & 0xffffu) | ((uint32_t)C << 16);  // (-S, C)
-					const uint32_t x4 = __builtin_amdgcn_perm(0u, w4[i / 2], (i & 1) ? 0x030c020cu : 0x010c000cu);
-					const int vi = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, x4), __builtin_bit_cast(s16x2, cs), 1 << 16, false) >> 17;
-					const int vq = __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, x4), __builtin_bit_cast(s16x2, sc), 1 << 16, false) >> 17;
-					o8[i] = ((uint32_t)vi & 0xffffu) | ((uint32_t)vq << 16);
-				}
-			}
-			reinterpret_cast<uint4 *>(d)[0] = make_uint4(o8[0], o8[1], o8[2], o8[3]);
-			reinterpret_cast<uint4 *>(d)[1] = make_uint4(o8[4], o8[5], o8[6], o8[7]);
-		} else {
-			*reinterpret_cast<uint4 *>(raw + 4 * c) = v;
-		}
+		*reinterpret_cast<uint4 *>(raw + 4 * c) = v;
 	}
 	// history for the next submit: the last 64 raw complex samples of this one (n_in >= 32768)
 	if (tile == (int)gridDim.x - 1 && tid < kRsTail / 16)
@@ -137,7 +82,6 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(const uint8_t *__r
 			*reinterpret_cast<const uint4 *>(src + nbytes - kRsTail + 16 * tid);
 	__syncthreads();
 	// ---- the lane's outputs m0 + 8 tid + o: sample i0 - (T-1) + n sits at byte sh + 2 (i0 - i00) + 2 n of the image
-	// (TUNE: at twice that, one dword per sample)
 	const int sh = (int)(2 * lo - b0);
 	const unsigned ar = phi0 + (unsigned)(kRsOut * tid) * (unsigned)p;  // a - i00 Q of the lane's first output, < 2^20
 	unsigned di = ar / (unsigned)q, phi = ar % (unsigned)q;
@@ -149,7 +93,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(const uint8_t *__r
 	f32x2 acc[kRsOut];
 #pragma unroll
 	for (int o = 0; o < kRsOut; o++) {
-		xp[o] = TUNE ? rb + 2 * sh + 4 * di : rb + sh + 2 * di;
+		xp[o] = rb + sh + 2 * di;
 		hp[o] = htab + phi * (unsigned)t;
 		acc[o] = f32x2{ kMagic, kMagic };
 		phi += pr;
@@ -163,14 +107,8 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(const uint8_t *__r
 	for (int n = 0; n < t; n++) {  // (T is even)
 #pragma unroll
 		for (int o = 0; o < kRsOut; o++) {
-			f32x2 d;
-			if constexpr (TUNE) {
-				const uint32_t w = *reinterpret_cast<const uint32_t *>(xp[o] + 4 * n);
-				d = f32x2{ (float)(int)(int16_t)(w & 0xffffu), (float)((int)w >> 16) };  // exact
-			} else {
-				const uint32_t w = *reinterpret_cast<const uint16_t *>(xp[o] + 2 * n);
-				d = f32x2{ (float)(w & 0xffu), (float)(w >> 8) } - f32x2{ 128.0f, 128.0f };  // exact
-			}
+			const uint32_t w = *reinterpret_cast<const uint16_t *>(xp[o] + 2 * n);
+			const f32x2 d = f32x2{ (float)(w & 0xffu), (float)(w >> 8) } - f32x2{ 128.0f, 128.0f };  // exact
 			const float hs = hp[o][n];
 			acc[o] = __builtin_elementwise_fma(d, f32x2{ hs, hs }, acc[o]);
 		}
@@ -185,26 +123,24 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(const uint8_t *__r
 		dst[k] = make_uint4(ow[4 * k], ow[4 * k + 1], ow[4 * k + 2], ow[4 * k + 3]);
 }
 
+hipError_t launch_resample_fmt(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, int p, int q, int t,
+			       const float *taps, const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride,
+			       const uint4 *chan, bool tuned);  // formats.h
+
 // taps: [q][t] floats on the device, h / 1024; n_blocks * 32768 * p is a multiple of q (the caller checked)
-// tuned: a stream has an input-rate tune (6g; chan != nullptr then): the tuned kernel, with half the tile where the int16
-// image of a whole one does not fit
+// tuned: a stream has an input-rate tune (6g; chan != nullptr then): the format kernel's U8 instantiation, which reads and writes
+// the same raw history -- an untuned stream's survives the change of kernels around it in both directions
 hipError_t launch_resample(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, int p, int q, int t,
 			   const float *taps, const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride,
 			   const uint4 *chan, bool tuned)
 {
+	if (tuned)
+		return launch_resample_fmt(st, kFmtU8, iq, stride, n_streams, n_blocks, p, q, t, taps, tail_in, tail_out, out, out_stride, chan, true);
 	const long n_out = (long)n_blocks * (TFREC_AMD_BLOCK_BYTES / 2);  // complex samples at 1.536 MS/s
 	const long n_in = n_out * p / q;
 	static_assert((TFREC_AMD_BLOCK_BYTES / 2) % kRsTile == 0, "resample_kernel has no partial tiles");
-	if (tuned) {
-		if (!chan)
-			return hipErrorInvalidValue;
-		const int tile = rs_tuned_lds(p, q, t, kRsTile) <= kRsLdsMax ? kRsTile : kRsTile / 2;
-		hipLaunchKernelGGL(resample_kernel<true>, dim3((unsigned)(n_out / tile), n_streams), dim3(tile / kRsOut),
-				   (size_t)rs_tuned_lds(p, q, t, tile), st, iq, stride, n_in, p, q, t, taps, tail_in, tail_out, out, out_stride, chan);
-		return hipGetLastError();
-	}
 	const size_t lds = (size_t)(rs_taps_dw(q, t) + 4 * rs_raw_chunks(p, q, t)) * 4;
-	hipLaunchKernelGGL(resample_kernel<false>, dim3((unsigned)(n_out / kRsTile), n_streams), dim3(kRsThreads), lds, st, iq, stride, n_in, p, q,
+	hipLaunchKernelGGL(resample_kernel, dim3((unsigned)(n_out / kRsTile), n_streams), dim3(kRsThreads), lds, st, iq, stride, n_in, p, q,
 			   t, taps, tail_in, tail_out, out, out_stride, chan);
 	return hipGetLastError();
 }
