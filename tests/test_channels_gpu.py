@@ -2,17 +2,14 @@
 6e), against the oracle, bit for bit.
 
 A receiver's events (every field, seq included), decimated samples and threshold equal those of a fresh oracle fed the input of
-the ROW the receiver reads, from the receiver's own restart on -- test_tune_gpu.py's segment scheme with the row looked up
+the ROW the receiver reads, from the receiver's own restart on -- segments.py's scheme with the row looked up
 through the map.  With the 10x input the oracle is fed tune.decim10_s16(tune.mix10_s16(...)) of the segment, and stage0() equals
 it too."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import parity
-from oracle import oracle as O
+import segments
 from tfrec_amd import api, synth, tune
 from test_channels_cpu import EMPTY_HZ, WIDE_BLOCKS, WIDE_BURSTS, wide_scene
 
@@ -38,97 +35,16 @@ def make_rows(seed, n_blocks, rows=ROWS):
     return np.stack(out)
 
 
-class Seg:
-    """One segment of a receiver (from its start or a restart on): settings, tunes, the row it reads, its oracle."""
-
-    def __init__(self, k, cfg, tune_hz, wide_hz, row, bits, in10x):
-        self.k, self.cfg, self.tune, self.wide, self.row, self.in10x = k, cfg, tune_hz, wide_hz, row, in10x
-        self.orc = O.Oracle(cfg[0], cfg[1], cfg[2], log_bits=bits, keep_dec=True)
-        self.n = 0       # 1.536 MS/s samples fed
-        self.hist = None  # in10x: the last 50 mixed input samples
-        self.y0 = None
-
-    def feed(self, part):
-        x16 = tune.s16_of_u8(np.asarray(part))
-        if self.in10x:
-            xm = tune.mix10_s16(x16, self.wide, 10 * self.n)
-            x16 = self.y0 = tune.decim10_s16(xm, hist=self.hist)
-            self.hist = xm[-100:]
-        self.orc.process_s16(tune.mix_s16(x16, self.tune, self.n))
-        self.n += len(x16) // 2
-
-
-def run_and_check(r, parts, ops, n, in10x=False, bits=False, rows0=None):
-    """parts[k]: [rows, bytes] of submit k (numpy or device tensors; hosts[k] the numpy copy).  ops[k]: ("map", streams, rows) |
-    ("tune", ..) | ("wide", ..) | ("conf", streams, cfgs) | ("reset", streams), applied before submit k."""
-    parts, hosts = parts
-    cfg, tn, wd = [DFLT] * n, [0] * n, [0] * n
-    row = list(range(n)) if rows0 is None else list(rows0)
-    segs = [[] for _ in range(n)]
-
-    def before(k):
-        restart = set()
-        for op in ops.get(k, ()):
-            if op[0] == "map":
-                r.map_streams(op[1], op[2])
-                for s, v in zip(op[1], op[2]):
-                    row[s] = v
-            elif op[0] == "tune":
-                r.tune_streams(op[1], op[2])
-                for s, v in zip(op[1], op[2]):
-                    tn[s] = v
-            elif op[0] == "wide":
-                r.tune_streams_wide(op[1], op[2])
-                for s, v in zip(op[1], op[2]):
-                    wd[s] = v
-            elif op[0] == "conf":
-                r.configure_streams(op[1], types_mask=[c[0] for c in op[2]], thresh=[c[1] for c in op[2]],
-                                    filter_type=[c[2] for c in op[2]])
-                for s, c in zip(op[1], op[2]):
-                    cfg[s] = c
-            else:
-                r.reset_streams(op[1])
-            restart |= set(op[1])
-        for s in range(n):
-            assert (r.stream_input(s), r.stream_tune(s), r.stream_tune_wide(s)) == (row[s], tn[s], wd[s]), "stream %d" % s
-            if k == 0 or s in restart:
-                segs[s].append(Seg(k, cfg[s], tn[s], wd[s], row[s], bits, in10x))
-        assert r.rows_in_use == (1 + max(row) if any(op[0] == "map" for j in range(k + 1) for op in ops.get(j, ())) else n)
-
-    def after(k):
-        for s in range(n):
-            segs[s][-1].feed(hosts[k][row[s]])
-            assert r.thresh(s) == segs[s][-1].orc.thresh(), "stream %d submit %d threshold" % (s, k)
-            if in10x:
-                y0 = segs[s][-1].y0
-                assert np.array_equal(r.stage0(s, len(y0) // 2), y0), "stream %d submit %d stage 0" % (s, k)
-
-    evs = parity.run_fifo(r, parts, before=before, after=after)
-    m = hosts[-1].shape[1] // r.block_bytes * api.BLOCK_DEC
-    total = 0
-    for s in range(n):
-        assert np.array_equal(r.decimated(s, m), segs[s][-1].orc.dec()[-2 * m:]), "stream %d decimated" % s
-        bounds = [g.k for g in segs[s]] + [len(hosts)]
-        for i, g in enumerate(segs[s]):
-            ev = np.concatenate([e[e["stream"] == s] for e in evs[bounds[i]:bounds[i + 1]]])
-            label = "stream %d segment %d row %d settings %s tune %d wide %d" % (s, i, g.row, g.cfg, g.tune, g.wide)
-            total += parity.assert_segment(ev, s, g.orc, label, bits)
-    return total, segs
-
-
 def device_parts(iq, sizes, block=api.BLOCK_BYTES):
-    import torch
-
     hosts = [np.ascontiguousarray(p) for p in parity.cut(iq, sizes, block)]
-    return [torch.from_numpy(h).to("cuda:0") for h in hosts], hosts
+    return parity.to_device(hosts), hosts
 
 
 @pytest.mark.parametrize("mode", ["deep", "shallow", "serial_chains", "bits"])
 def test_shared_rows(mode, monkeypatch):
     """24 receivers on 6 rows with mixed tunes and settings, ragged submits through the full FIFO; remaps, resets, retunes and
     reconfigures between the submits.  The batch holds the 6 rows only."""
-    if mode == "shallow":
-        monkeypatch.setenv("TFREC_AMD_DEEP", "0")
+    kw, layout, flags = parity.mode_kwargs(mode, monkeypatch)
     n = 24
     sizes = (3, 2, 1, 3, 2)
     iq = make_rows(51, sum(sizes))
@@ -141,12 +57,10 @@ def test_shared_rows(mode, monkeypatch):
            # one restart out of a reset, a configure, a tune and a map
            3: [("reset", [2]), ("conf", [2], [(0x2F, 500, 0)]), ("tune", [2], [0]), ("map", [2], [4]), ("tune", [16], [31])],
            4: [("reset", [3, 20]), ("map", [0], [5])]}
-    kw = dict(bits=mode == "bits", serial_chains=mode == "serial_chains")
-    # (TFREC_AMD_DEEP is read by the experiments build of the library only)
-    with api.Receiver(n, DFLT[0], DFLT[1], DFLT[2], max_blocks=max(sizes), all_flushes=True, experiments=mode == "shallow",
-                      **kw) as r:
-        assert r.layout() == {"deep": 6, "shallow": 4, "serial_chains": 2, "bits": 6}[mode]
-        total, segs = run_and_check(r, device_parts(iq, sizes), ops, n, bits=mode == "bits", rows0=None)
+    with api.Receiver(n, DFLT[0], DFLT[1], DFLT[2], max_blocks=max(sizes), **kw) as r:
+        assert r.layout() == layout
+        parts, hosts = device_parts(iq, sizes)
+        total, segs = segments.run_segments(r, parts, ops, DFLT, hosts=hosts, bits=flags["bits"])
         assert [r.stream_input(s) for s in (0, 2, 3, 6, 9)] == [5, 4, 5, 0, 1]
     assert [len(segs[s]) for s in (0, 2, 3, 6, 9, 11, 16, 20, 1)] == [2, 2, 3, 2, 2, 2, 2, 2, 1]
     assert total > 5 * n
@@ -168,11 +82,11 @@ def test_wideband_receivers_of_one_row():
     n = len(wides)
     tunes = [0] * n
     tunes[6] = 200000  # 3.1 MHz + 200 kHz: the burst at 3.3 MHz
-    _, parts = wide_parts(sizes)
+    _, (parts, hosts) = wide_parts(sizes)
     ops = {0: [("map", list(range(n)), [0] * n), ("wide", list(range(n)), wides), ("tune", [6], [200000])],
            2: [("wide", [1, 4], [-1100000, 6900000]), ("reset", [2])]}  # (stream 1: the same tune again is a restart too)
     with api.Receiver(n, DFLT[0], DFLT[1], DFLT[2], max_blocks=max(sizes), all_flushes=True, input_10x=True) as r:
-        total, segs = run_and_check(r, parts, ops, n, in10x=True)
+        total, segs = segments.run_segments(r, parts, ops, DFLT, hosts=hosts, in10x=True)
     assert [len(g) for g in segs] == [1, 2, 2, 1, 2, 1, 1, 1, 1]
     tel = [[e[0] for e in g[0].orc.events_full() if e[7] == 1] for g in segs]  # telegrams of every receiver's first segment
     # a telegram per planted burst (receivers 1 and 2 restart behind theirs), none on the empty frequency, untuned, at the limits

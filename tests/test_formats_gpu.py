@@ -11,7 +11,7 @@ import pytest
 
 import parity
 from oracle import oracle as O
-from tfrec_amd import api, formats, resample, synth, tune
+from tfrec_amd import api, formats, resample, tune
 from test_formats_cpu import KINDS, scene, scene_oracle, scene_stage0, scene_u8, stage0_of
 from test_resample_cpu import SCENE_BLOCKS, THRESH, TYPES
 
@@ -20,51 +20,7 @@ pytestmark = pytest.mark.gpu
 FOUR = (3, 3, 3, 3)
 
 
-def cut_rows(rows, sizes, fmt, p, q):
-    """rows[rows, bytes] -> consecutive parts of sizes[k] blocks each at the input rate p / q in the format."""
-    parts, pos = [], 0
-    for nb in sizes:
-        n = formats.bytes_per_sample(fmt) * resample.input_samples(nb, p, q)
-        parts.append(np.ascontiguousarray(rows[:, pos:pos + n]))
-        pos += n
-    assert pos == rows.shape[1]
-    return parts
-
-
-def run(fmt, rows, sizes, p, q, host=False, before=None, n_streams=None, stage0=True, **kw):
-    """A format receiver over the rows cut into `sizes` -> (one drained array per submit, the receiver's stage 0 per submit and
-    stream).  fmt None: the receiver of the older constructors (u8).  stage0=False: nothing is read back between the submits."""
-    parts = cut_rows(rows, sizes, fmt or "u8", p, q)
-    n = len(rows) if n_streams is None else n_streams
-    y0 = []
-    if fmt is not None:
-        kw["input_format"] = fmt
-        kw["input_rate"] = (p, q)
-    elif (p, q) != (1, 1):
-        kw["input_rate"] = (p, q)
-    with api.Receiver(n, TYPES, THRESH, 0, max_blocks=max(sizes), **kw) as r:
-        assert r.input_rate == (p, q) and r.input_format == (fmt or "u8")
-        for k, nb in enumerate(sizes):
-            assert r.input_bytes(nb) == parts[k].shape[1] and parts[k].shape[1] % 16 == 0
-
-        def after(k):
-            y0.append([r.stage0(s, sizes[k] * 4 * api.BLOCK_DEC) for s in range(n)])
-
-        if not host:
-            import torch
-
-            parts = [torch.from_numpy(h).to("cuda:0") for h in parts]
-        evs = parity.run_fifo(r, parts, before=(lambda k: before(r, k)) if before else None, after=after if stage0 else None)
-    return evs, y0
-
-
-def assert_stage0(y0, sizes, want, s, label=""):
-    pos = 0
-    for k, nb in enumerate(sizes):
-        n = 2 * nb * 4 * api.BLOCK_DEC
-        assert np.array_equal(y0[k][s], want[pos:pos + n]), "%s stream %d submit %d" % (label, s, k)
-        pos += n
-    assert pos == len(want)
+run_input = functools.partial(parity.run_input, types=TYPES, thresh=THRESH)
 
 
 # ---- stage 0 equals the restatement
@@ -73,19 +29,9 @@ def assert_stage0(y0, sizes, want, s, label=""):
 def test_stage0_equals_the_restatement(kind, p, q):
     """The first submit and three following ones: the history carry and both history buffers; at 1/1 stage 0 is x itself."""
     rows = scene(kind, p, q)
-    _, y0 = run(KINDS[kind], rows, FOUR, p, q, all_flushes=True)
+    _, y0 = run_input(rows, FOUR, p, q, KINDS[kind], all_flushes=True)
     for s in range(len(rows)):
-        assert_stage0(y0, FOUR, scene_stage0(kind, p, q, s), s, kind)
-
-
-def full_scale_row(fmt, n, seed):
-    """[1, bytes]: n complex samples that use the format's whole range (f32: beyond it, so that the clamp works)."""
-    rng = np.random.default_rng(seed)
-    if fmt == "s8":
-        return rng.integers(0, 256, (1, 2 * n), dtype=np.uint8)
-    if fmt == "s16":
-        return rng.integers(-32768, 32768, (1, 2 * n)).astype("<i2").view(np.uint8)
-    return (rng.random((1, 2 * n), dtype=np.float32) * np.float32(2.4) - np.float32(1.2)).astype("<f4").view(np.uint8)
+        parity.assert_stage0(y0, FOUR, scene_stage0(kind, p, q, s), s, kind)
 
 
 @pytest.mark.parametrize("p,q", [(29, 4), (639, 64)])
@@ -96,9 +42,9 @@ def test_stage0_of_the_large_rates(fmt, p, q):
     instantiation (the tuned u8 resampler) does at this rate.  29/4 = 7.25 input samples per output has 44 taps per phase and a tile's image of 30 KB: the largest image among
     the rates with a small Q, still in whole tiles."""
     sizes = (1, 1)
-    rows = full_scale_row(fmt, resample.input_samples(2, p, q), 29)
-    _, y0 = run(fmt, rows, sizes, p, q, all_flushes=True, max_events=1 << 16)
-    assert_stage0(y0, sizes, stage0_of(fmt, rows[0], p, q), 0, fmt)
+    rows = parity.full_scale_row(fmt, resample.input_samples(2, p, q), 29)
+    _, y0 = run_input(rows, sizes, p, q, fmt, all_flushes=True, max_events=1 << 16)
+    parity.assert_stage0(y0, sizes, stage0_of(fmt, rows[0], p, q), 0, fmt)
 
 
 EDGES = [np.nan, np.inf, -np.inf, 2.0, -2.0, 1.0, -1.0, 0.99993896, -0.99993896, 0.5 / 8192, 1.5 / 8192, 2.5 / 8192, -0.5 / 8192,
@@ -119,8 +65,8 @@ def test_f32_edge_values(p, q, nb):
     rows = v.view(np.uint8).reshape(1, -1)
     x = formats.to_x("f32", rows[0])
     assert np.isnan(v).any() and x.min() == -8192 and x.max() == 8191
-    _, y0 = run("f32", rows, (nb,), p, q, all_flushes=True, max_events=1 << 16)
-    assert_stage0(y0, (nb,), stage0_of("f32", rows[0], p, q), 0)
+    _, y0 = run_input(rows, (nb,), p, q, "f32", all_flushes=True, max_events=1 << 16)
+    parity.assert_stage0(y0, (nb,), stage0_of("f32", rows[0], p, q), 0)
 
 
 # ---- events equal the oracle behind the restatement
@@ -132,20 +78,18 @@ EVENT_RUNS = ([("deep", k, 4, 3) for k in ("s8", "s16", "f32")]
 
 @pytest.mark.parametrize("mode,kind,p,q", EVENT_RUNS)
 def test_events_equal_the_oracle_behind_the_restatement(mode, kind, p, q, monkeypatch):
-    if mode == "shallow":
-        monkeypatch.setenv("TFREC_AMD_DEEP", "0")
+    kw, layout, flags = parity.mode_kwargs(mode, monkeypatch)
     rows = scene(kind, p, q)
-    kw = dict(all_flushes=mode != "default_mode", bits=mode == "bits", serial_chains=mode == "serial_chains",
-              experiments=mode == "shallow")
     layouts = []
-    evs, _ = run(KINDS[kind], rows, FOUR, p, q, host=mode == "host", stage0=False, before=lambda r, k: layouts.append(r.layout()), **kw)
-    assert layouts[0] == {"shallow": 4, "serial_chains": 2}.get(mode, 6)
+    evs, _ = run_input(rows, FOUR, p, q, KINDS[kind], host=flags["host"], stage0=False, before=lambda r, k: layouts.append(r.layout()),
+                       **kw)
+    assert layouts[0] == layout
     ev = np.concatenate(evs)
     total = telegrams = 0
     for s in range(len(rows)):
-        orc = scene_oracle(kind, p, q, s, mode == "bits")
-        total += parity.assert_stream(ev, s, orc, default_mode=mode == "default_mode")
-        if mode == "bits":
+        orc = scene_oracle(kind, p, q, s, flags["bits"])
+        total += parity.assert_stream(ev, s, orc, default_mode=flags["default_mode"])
+        if flags["bits"]:
             assert parity.assert_bits(ev, s, orc, "stream %d" % s) > 1000
         telegrams += sum(1 for e in orc.events_full() if e[7] == 1)
     assert total >= 8 and telegrams >= 8
@@ -156,7 +100,7 @@ def test_events_equal_the_oracle_behind_the_restatement(mode, kind, p, q, monkey
 def sorted_events(fmt, kind, p, q):
     """The sorted event bytes of a receiver of the format (None: the older constructors') over a scene's rows."""
     rows = scene_u8(p, q) if kind == "u8" else scene(kind, p, q)
-    evs, _ = run(fmt, rows, FOUR, p, q, stage0=False, all_flushes=True)
+    evs, _ = run_input(rows, FOUR, p, q, fmt, stage0=False, all_flushes=True)
     ev = parity.sort_events(np.concatenate(evs))
     assert len(ev) > 20
     return ev.tobytes()
@@ -178,8 +122,8 @@ def test_s8_of_flipped_bytes_equals_the_u8_context(p, q):
 
 @pytest.mark.parametrize("p,q", [(4, 3), (1, 1)])
 def test_s16_and_f32_of_the_same_x_give_the_same_events(p, q):
-    s16 = run("s16", encoded("s16", p, q), FOUR, p, q, stage0=False, all_flushes=True)[0]
-    f32 = run("f32", encoded("f32", p, q), FOUR, p, q, stage0=False, all_flushes=True)[0]
+    s16 = run_input(encoded("s16", p, q), FOUR, p, q, "s16", stage0=False, all_flushes=True)[0]
+    f32 = run_input(encoded("f32", p, q), FOUR, p, q, "f32", stage0=False, all_flushes=True)[0]
     s16, f32 = parity.sort_events(np.concatenate(s16)), parity.sort_events(np.concatenate(f32))
     assert len(s16) > 20 and s16.tobytes() == f32.tobytes() == sorted_events(None, "u8", p, q)
 
@@ -188,7 +132,7 @@ def test_s16_and_f32_of_the_same_x_give_the_same_events(p, q):
 def test_reset_in_mid_stream_equals_a_fresh_receiver():
     p, q, kind = 4, 3, "s16"
     rows = scene(kind, p, q)
-    evs, y0 = run("s16", rows, FOUR, p, q, all_flushes=True, before=lambda r, k: r.reset_streams([1]) if k == 2 else None)
+    evs, y0 = run_input(rows, FOUR, p, q, "s16", all_flushes=True, before=lambda r, k: r.reset_streams([1]) if k == 2 else None)
     cut = 4 * resample.input_samples(6, p, q)
     after = stage0_of("s16", rows[1][cut:], p, q)  # zero history behind the cut
     whole = scene_stage0(kind, p, q, 1)
@@ -203,7 +147,7 @@ def test_reset_in_mid_stream_equals_a_fresh_receiver():
     assert np.array_equal(y0[2][1], after[:len(y0[2][1])])
     assert not np.array_equal(y0[2][1][:16], whole[2 * 6 * 4 * api.BLOCK_DEC:][:16])
     assert np.array_equal(y0[3][1], after[len(y0[2][1]):])
-    assert_stage0(y0, FOUR, scene_stage0(kind, p, q, 0), 0)
+    parity.assert_stage0(y0, FOUR, scene_stage0(kind, p, q, 0), 0)
 
 
 def test_configure_works():
@@ -215,7 +159,7 @@ def test_configure_works():
         if k == 0:
             r.configure_streams([1], types_mask=0x01, thresh=700)
 
-    evs, _ = run("s16", rows, FOUR, p, q, stage0=False, all_flushes=True, before=before)
+    evs, _ = run_input(rows, FOUR, p, q, "s16", stage0=False, all_flushes=True, before=before)
     ev = np.concatenate(evs)
     o = O.Oracle(0x01, 700, 0)
     o.process_s16(scene_stage0(kind, p, q, 1))
@@ -226,38 +170,12 @@ def test_configure_works():
 TUNES = (200000, -200000)
 
 
-@functools.lru_cache(maxsize=None)
-def tuned_row(p, q, freqs, n_blocks=6):
-    """[1, bytes]: one s16 recording at 1536000 p / q with a burst of its own protocol at each of freqs (Hz from the centre)."""
-    n = n_blocks * api.BLOCK_BYTES // 2 * p
-    bursts = [dict(proto=j, start=(40000 * p + j * (n - 100000 * p) // len(freqs)) // q * q, payload_seed=21 + j, f0_hz=f, amp=50)
-              for j, f in enumerate(freqs)]
-    u = synth.gen_scene(77, n_blocks, bursts, rate_mult=p).reshape(-1, 2)[::q].reshape(-1)
-    v = ((u.astype(np.int32) - 128) << 8) + np.random.default_rng(9).integers(-128, 128, u.shape)
-    row = np.clip(v, -32768, 32767).astype("<i2").view(np.uint8).reshape(1, -1)
-    row.setflags(write=False)
-    return row
-
-
-@functools.lru_cache(maxsize=None)
-def tuned_oracle(p, q, freqs, input_hz, narrow_hz):
-    """The oracle behind the restatement of one receiver on tuned_row: the mixer at the input rate, the stage, the tune behind it."""
-    x = formats.to_x("s16", tuned_row(p, q, freqs)[0])
-    o = O.Oracle(TYPES, THRESH, 0)
-    o.process_s16(tune.mix_s16(resample.resample_x16(tune.mix_in_s16(x, input_hz, p, q), p, q), narrow_hz, 0))
-    return o
-
-
-def decoded(o):
-    return [e[0] for e in o.events_full() if e[7] == 1]
-
-
 @pytest.mark.parametrize("shared", [False, True])
 def test_tunes_and_a_shared_row(shared):
     """tune_streams at +-200 kHz acts on y0: the oracle behind tune.mix_s16 of the restatement.  shared: the two streams are mapped
     to row 0 and the submit carries one row; otherwise each reads its own copy."""
     p, q, sizes = 4, 3, (3, 3)
-    row = tuned_row(p, q, TUNES)
+    row = parity.tuned_row(p, q, TUNES, "s16")
 
     def before(r, k):
         if k == 0:
@@ -266,38 +184,38 @@ def test_tunes_and_a_shared_row(shared):
             r.tune_streams([0, 1], TUNES)
             assert r.rows_in_use == (1 if shared else 2)
 
-    evs, y0 = run("s16", row if shared else np.repeat(row, 2, axis=0), sizes, p, q, n_streams=2, before=before, all_flushes=True)
+    evs, y0 = run_input(row if shared else np.repeat(row, 2, axis=0), sizes, p, q, "s16", n_streams=2, before=before, all_flushes=True)
     ev = np.concatenate(evs)
     for s, hz in enumerate(TUNES):
-        orc = tuned_oracle(p, q, TUNES, 0, hz)
+        orc = parity.tuned_oracle(p, q, TUNES, "s16", 0, hz, types=TYPES, thresh=THRESH)
         assert parity.assert_segment(ev, s, orc, "stream %d tune %d" % (s, hz)) > 0
-        assert decoded(orc) == [s]  # each receiver decodes the burst it is tuned to
-        assert_stage0(y0, sizes, stage0_of("s16", row[0], p, q), s)  # stage 0 is ahead of the tune
+        assert parity.decoded(orc) == [s]  # each receiver decodes the burst it is tuned to
+        parity.assert_stage0(y0, sizes, stage0_of("s16", row[0], p, q), s)  # stage 0 is ahead of the tune
 
 
 def test_input_tune_beside_an_untuned_stream():
     """tune_streams_input at +900 kHz on a 25/16 context, an untuned stream in the same launch."""
     p, q, sizes, freqs = 25, 16, (1, 2, 2, 1), (0, 900000)
-    row = tuned_row(p, q, freqs)
+    row = parity.tuned_row(p, q, freqs, "s16")
 
     def before(r, k):
         if k == 0:
             r.tune_streams_input([1], [900000])
             assert r.stream_tune_input(1) == 900000 and r.stream_tune_input(0) == 0
 
-    evs, y0 = run("s16", np.repeat(row, 2, axis=0), sizes, p, q, before=before, all_flushes=True)
+    evs, y0 = run_input(np.repeat(row, 2, axis=0), sizes, p, q, "s16", before=before, all_flushes=True)
     ev = np.concatenate(evs)
     x = formats.to_x("s16", row[0])
     for s, hz in enumerate(freqs):
-        orc = tuned_oracle(p, q, freqs, hz, 0)
+        orc = parity.tuned_oracle(p, q, freqs, "s16", hz, 0, types=TYPES, thresh=THRESH)
         assert parity.assert_segment(ev, s, orc, "stream %d input tune %d" % (s, hz)) > 0
-        assert decoded(orc) == [s]
-        assert_stage0(y0, sizes, resample.resample_x16(tune.mix_in_s16(x, hz, p, q), p, q), s)
+        assert parity.decoded(orc) == [s]
+        parity.assert_stage0(y0, sizes, resample.resample_x16(tune.mix_in_s16(x, hz, p, q), p, q), s)
 
 
 def test_results_do_not_depend_on_the_cut():
     p, q = 4, 3
-    one, _ = run("s16", scene("s16", p, q), (SCENE_BLOCKS,), p, q, stage0=False, all_flushes=True)
+    one, _ = run_input(scene("s16", p, q), (SCENE_BLOCKS,), p, q, "s16", stage0=False, all_flushes=True)
     a = parity.sort_events(np.concatenate(one))
     assert len(a) > 20 and a.tobytes() == sorted_events("s16", "s16", p, q)
 

@@ -49,10 +49,6 @@ def input_oracle(x, p, q, input_hz, narrow_hz=0, log_bits=False):
     return o
 
 
-def decoded(o):
-    return [e[0] for e in o.events_full() if e[7] == 1]
-
-
 # ---- inc_in
 CORNERS = (0, 1, -1, 1000, -1000, 250000, -250000, 767999, -767999)
 
@@ -198,9 +194,9 @@ def test_every_burst_decodes_for_exactly_the_receiver_tuned_to_it(p, q):
     freqs = WIDE_SCENES[p, q]
     assert freqs[0] == 0 and any(0 < abs(f) < 768000 for f in freqs) and any(abs(f) > 768000 for f in freqs)
     for j, f in enumerate(freqs):
-        assert decoded(input_oracle(x, p, q, f)) == [j], (j, f)
+        assert parity.decoded(input_oracle(x, p, q, f)) == [j], (j, f)
         if abs(f) < 768000:  # within the narrow tune's reach both tunes decode it
-            assert decoded(input_oracle(x, p, q, 0, f)) == [j], (j, f)
+            assert parity.decoded(input_oracle(x, p, q, 0, f)) == [j], (j, f)
         else:
             # the tune behind the resampler does not reach it: neither as near as that tune gets, nor at the frequency the
             # burst would alias to at 1.536 MS/s -- the resampler's low-pass has removed it
@@ -208,4 +204,4 @@ def test_every_burst_decodes_for_exactly_the_receiver_tuned_to_it(p, q):
             alias = f - 1536000 if f > 0 else f + 1536000
             assert abs(alias) < 768000
             for hz in (edge, alias):
-                assert j not in decoded(input_oracle(x, p, q, 0, hz)), (j, f, hz)
+                assert j not in parity.decoded(input_oracle(x, p, q, 0, hz)), (j, f, hz)

@@ -3,18 +3,20 @@
 Stage 0 is pinned by the restatement (tune.mix_in_s16, resample.resample_x16), everything behind it by the oracle's process_s16 fed
 that restatement's output.  The scenes are the recordings of test_input_tune_cpu.py at 2.4 MS/s (25/16) and 3.2 MS/s (25/12),
 which asserts that the oracle decodes each burst for exactly the receiver tuned to it."""
+import functools
+
 import numpy as np
 import pytest
 
 import parity
-from tfrec_amd import api, resample, tune
+from tfrec_amd import api, resample
 from test_channels_cpu import WIDE_BURSTS, wide_scene
-from test_input_tune_cpu import THRESH, TYPES, WIDE_BLOCKS, WIDE_SCENES, decoded, input_oracle, stage0_of, wide_row
+from test_input_tune_cpu import THRESH, TYPES, WIDE_BLOCKS, WIDE_SCENES, input_oracle, stage0_of, wide_row
 from test_resample_cpu import oracle_of
-from test_resample_gpu import run
 
 pytestmark = pytest.mark.gpu
 
+run_input = functools.partial(parity.run_input, types=TYPES, thresh=THRESH)
 SIZES = {(25, 16): (1, 2, 2, 1), (25, 12): (3, 3)}  # the scenes' WIDE_BLOCKS blocks cut into submits
 
 
@@ -32,44 +34,24 @@ def receivers(p, q):
     return freqs, before
 
 
-def loud_and_quiet(p, q, sizes, n_streams, seed):
-    """[streams, bytes] for the stage-0 test: near-silence with stretches of full-scale random bytes at the start and across
-    every boundary between two submits, so that the history carry moves samples that matter and every rail value occurs."""
-    rng = np.random.default_rng(seed)
-    n = resample.input_samples(sum(sizes), p, q)
-    x = rng.integers(125, 132, (n_streams, 2 * n), dtype=np.uint8)
-    pos = 0
-    for nb in (0,) + tuple(sizes[:-1]):
-        pos += 2 * resample.input_samples(nb, p, q) if nb else 0
-        lo, hi = max(0, pos - 3000), min(2 * n, pos + 3000)
-        x[:, lo:hi] = rng.integers(0, 256, (n_streams, hi - lo), dtype=np.uint8)
-    x[:, 2 * n - 400:] = rng.integers(0, 256, (n_streams, 400), dtype=np.uint8)
-    return x
-
-
 @pytest.mark.parametrize("p,q,sizes", [(4, 3, (3, 3, 3, 3)), (25, 16, (1, 2, 1, 2)), (25, 12, (3, 3, 3, 3)), (639, 64, (1, 1, 1, 1))])
 def test_stage0_equals_the_restatement(p, q, sizes):
     """Four submits: the history carry, both history buffers and the phase carry; a tuned stream near the limit, an untuned one and
     a second tuned one in one launch.  639/64 takes the kernel's half tile."""
     top = (1536000 * p + 2 * q - 1) // (2 * q) - 1
     hz = (top - 1234, 0, -123457)
-    iq = loud_and_quiet(p, q, sizes, 3, 1000 * p + q)
+    iq = parity.loud_and_quiet(p, q, sizes, 3, 1000 * p + q)
 
     def before(r, k):
         if k == 0:
             r.tune_streams_input([0, 1, 2], hz)
 
-    _, y0 = run(iq, sizes, p, q, before=before, all_flushes=True, max_events=1 << 16)
+    _, y0 = run_input(iq, sizes, p, q, before=before, all_flushes=True, max_events=1 << 16)
     for s in range(3):
         want = stage0_of(iq[s], p, q, hz[s])
         if hz[s] == 0:
             assert np.array_equal(want, resample.resample_s16(iq[s], p, q))
-        pos = 0
-        for k, nb in enumerate(sizes):
-            n = 2 * nb * 4 * api.BLOCK_DEC
-            assert np.array_equal(y0[k][s], want[pos:pos + n]), "stream %d submit %d" % (s, k)
-            pos += n
-        assert pos == len(want)
+        parity.assert_stage0(y0, sizes, want, s)
 
 
 @pytest.mark.parametrize("p,q", [(25, 16), (639, 64)])
@@ -80,7 +62,7 @@ def test_an_untuned_stream_keeps_its_history_while_the_kernels_change_around_it(
     its stage 0 is that of the uninterrupted input.  25/16 takes the whole tile, 639/64 the half tile."""
     sizes = (1, 1, 1)
     hz = 300000
-    iq = loud_and_quiet(p, q, sizes, 2, 7000 * p + q)
+    iq = parity.loud_and_quiet(p, q, sizes, 2, 7000 * p + q)
 
     def before(r, k):
         if k == 1:
@@ -88,7 +70,7 @@ def test_an_untuned_stream_keeps_its_history_while_the_kernels_change_around_it(
         if k == 2:
             r.tune_streams_input([0], [0])
 
-    _, y0 = run(iq, sizes, p, q, before=before, all_flushes=True, max_events=1 << 16)
+    _, y0 = run_input(iq, sizes, p, q, before=before, all_flushes=True, max_events=1 << 16)
     assert np.array_equal(np.concatenate([y[1] for y in y0]), resample.resample_s16(iq[1], p, q))
     c1 = 2 * resample.input_samples(1, p, q)
     assert np.array_equal(y0[1][0], stage0_of(iq[0][c1:], p, q, hz)[:len(y0[1][0])])  # (the tuned kernel did run in between)
@@ -97,21 +79,18 @@ def test_an_untuned_stream_keeps_its_history_while_the_kernels_change_around_it(
 @pytest.mark.parametrize("p,q", sorted(WIDE_SCENES))
 @pytest.mark.parametrize("mode", ["deep", "shallow", "serial_chains", "default_mode", "bits", "host"])
 def test_events_equal_the_oracle_behind_the_restatement(mode, p, q, monkeypatch):
-    if mode == "shallow":
-        monkeypatch.setenv("TFREC_AMD_DEEP", "0")
+    kw, _, flags = parity.mode_kwargs(mode, monkeypatch)
     row = wide_row(p, q)
     freqs, before = receivers(p, q)
-    kw = dict(all_flushes=mode != "default_mode", bits=mode == "bits", serial_chains=mode == "serial_chains",
-              experiments=mode == "shallow")
-    evs, _ = run(row, SIZES[p, q], p, q, host=mode == "host", stage0=False, n_streams=len(freqs), before=before, **kw)
+    evs, _ = run_input(row, SIZES[p, q], p, q, host=flags["host"], stage0=False, n_streams=len(freqs), before=before, **kw)
     ev = np.concatenate(evs)
     total = 0
     for s, f in enumerate(freqs):
-        orc = input_oracle(row[0], p, q, f, log_bits=mode == "bits")
-        total += parity.assert_stream(ev, s, orc, "stream %d tune %d" % (s, f), default_mode=mode == "default_mode")
-        if mode == "bits":
+        orc = input_oracle(row[0], p, q, f, log_bits=flags["bits"])
+        total += parity.assert_stream(ev, s, orc, "stream %d tune %d" % (s, f), default_mode=flags["default_mode"])
+        if flags["bits"]:
             assert parity.assert_bits(ev, s, orc, "stream %d" % s) > 50
-        assert decoded(orc) == [s]  # a telegram per tuned receiver: its own burst
+        assert parity.decoded(orc) == [s]  # a telegram per tuned receiver: its own burst
         assert [t[0] for t in api.event_tuples_full(ev, s) if t[7] == 1] == [s]
     assert total >= len(freqs)
 
@@ -120,8 +99,8 @@ def test_events_equal_the_oracle_behind_the_restatement(mode, p, q, monkeypatch)
 def test_results_do_not_depend_on_the_cut(p, q):
     row = wide_row(p, q)
     freqs, before = receivers(p, q)
-    one, _ = run(row, (WIDE_BLOCKS,), p, q, n_streams=len(freqs), before=before, all_flushes=True)
-    cut, _ = run(row, SIZES[p, q], p, q, n_streams=len(freqs), before=before, all_flushes=True)
+    one, _ = run_input(row, (WIDE_BLOCKS,), p, q, n_streams=len(freqs), before=before, all_flushes=True)
+    cut, _ = run_input(row, SIZES[p, q], p, q, n_streams=len(freqs), before=before, all_flushes=True)
     a, b = parity.sort_events(np.concatenate(one)), parity.sort_events(np.concatenate(cut))
     assert len(a) >= len(freqs) and a.tobytes() == b.tobytes()
 
@@ -143,7 +122,7 @@ def test_a_tune_and_a_reset_in_mid_stream_equal_fresh_receivers():
             r.reset_streams([1])
             assert r.stream_tune_input(1) == f1
 
-    evs, y0 = run(np.stack([x, x]), sizes, p, q, before=before, all_flushes=True)
+    evs, y0 = run_input(np.stack([x, x]), sizes, p, q, before=before, all_flushes=True)
     c1, c2 = 2 * resample.input_samples(2, p, q), 2 * resample.input_samples(4, p, q)
     parity.assert_segment(np.concatenate(evs[:1]), 0, oracle_of(x[:c1], p, q), "stream 0 before its tune")
     n = parity.assert_segment(np.concatenate(evs[1:]), 0, input_oracle(x[c1:], p, q, f0), "stream 0 after its tune")
@@ -175,14 +154,14 @@ def test_receivers_of_one_row_equal_receivers_of_copies(p, q):
             r.tune_streams_input([0, 1, 2], hz)
             assert r.rows_in_use == 3
 
-    ev_shared, y0 = run(row, SIZES[p, q], p, q, n_streams=3, before=one_row, all_flushes=True)
-    ev_copies, y0c = run(np.repeat(row, 3, axis=0), SIZES[p, q], p, q, before=copies, all_flushes=True)
+    ev_shared, y0 = run_input(row, SIZES[p, q], p, q, n_streams=3, before=one_row, all_flushes=True)
+    ev_copies, y0c = run_input(np.repeat(row, 3, axis=0), SIZES[p, q], p, q, before=copies, all_flushes=True)
     a, b = parity.sort_events(np.concatenate(ev_shared)), parity.sort_events(np.concatenate(ev_copies))
     assert a.tobytes() == b.tobytes()
     for s in range(3):
         orc = input_oracle(row[0], p, q, hz[s])
         parity.assert_segment(a, s, orc, "stream %d tune %d" % (s, hz[s]))
-        assert decoded(orc) == [k3[s]]  # each receiver decodes only its own burst
+        assert parity.decoded(orc) == [k3[s]]  # each receiver decodes only its own burst
         assert [t[0] for t in api.event_tuples_full(a, s) if t[7] == 1] == [k3[s]]
         for k in range(len(y0)):
             assert np.array_equal(y0[k][s], y0c[k][s])
@@ -203,12 +182,12 @@ def test_the_tune_behind_the_resampler_composes():
             r.tune_streams_input([0, 1, 2], [a for a, _ in pairs])
             assert [r.stream_tune(s) for s in range(3)] == [b for _, b in pairs]
 
-    evs, y0 = run(row, SIZES[p, q], p, q, n_streams=3, before=before, all_flushes=True)
+    evs, y0 = run_input(row, SIZES[p, q], p, q, n_streams=3, before=before, all_flushes=True)
     ev = np.concatenate(evs)
     for s, (a, b) in enumerate(pairs):
         orc = input_oracle(row[0], p, q, a, b)
         parity.assert_segment(ev, s, orc, "stream %d" % s)
-        assert decoded(orc) == [want[s]]
+        assert parity.decoded(orc) == [want[s]]
         assert np.array_equal(y0[0][s], stage0_of(row[0], p, q, a)[:len(y0[0][s])])  # stage 0 is ahead of that tune
 
 
@@ -289,10 +268,6 @@ def test_memory_is_what_it_was_with_and_without_a_tune():
         assert r.memory() == rate
 
 
-def telegram_lines(text):
-    return [ln for ln in text.splitlines() if ln.startswith(tuple(parity.PREFIX.values())) and not ln.startswith("WHB:")]
-
-
 @pytest.fixture(scope="module")
 def cli():
     return parity.build_cli()
@@ -317,5 +292,5 @@ def test_cli_one_2400000_dump_given_three_times(cli, tmp_path):
     assert rec == [[str(i)] + r[1:] for i, s in enumerate(singles) for r in s[1]] and len(rec) >= 3
     for i, f in enumerate(WIDE_SCENES[p, q][:3]):  # ... and each is the oracle's text behind the restatement
         o = input_oracle(wide_row(p, q)[0], p, q, f) if abs(f) >= 768000 else input_oracle(wide_row(p, q)[0], p, q, 0, f)
-        want, got = telegram_lines(o.text()), telegram_lines(singles[i][0])
+        want, got = parity.telegram_lines(o.text()), parity.telegram_lines(singles[i][0])
         assert got == want and len(want) >= 1, i

@@ -1,13 +1,16 @@
-"""CPU tests of the shared GPU parity harness (tests/parity.py): the parts the GPU suite can check only indirectly -- the
-order in which run_fifo submits and drains, the cuts, the default-mode rule and the parse of the oracle's bit log."""
+"""CPU tests of the shared GPU parity harness (tests/parity.py, tests/segments.py): the parts the GPU suite can check only
+indirectly -- the order in which run_fifo submits and drains, the cuts, the default-mode rule, the parse of the oracle's bit
+log, a segment's oracle fed part by part, the stage-0 comparison and the table of modes."""
+import os
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
 import parity
+import segments
 from oracle import oracle as O
-from tfrec_amd import api, synth
+from tfrec_amd import api, formats, resample, synth, tune
 
 
 class FakeReceiver:
@@ -111,3 +114,92 @@ def test_oracle_bits_of_a_real_run():
         assert [len(b) for b in recs] == [int(p[2]) for p in mine]
         assert "".join(recs) == "".join(p[3] for p in mine if len(p) > 3) and set("".join(recs)) <= {"0", "1"}
     assert sum(len(b) for recs in got.values() for b in recs) > 5000
+
+
+# ---- segments.Segment
+SEGMENT_CASES = {"default": (False, 0, 0), "input_10x": (True, 0, 0), "tuned": (False, -200000, 0),
+                 "input_10x-wide-tuned": (True, 25000, 2500000)}  # (10x input, tune, wide tune)
+
+
+@pytest.mark.parametrize("case", sorted(SEGMENT_CASES))
+def test_segment_fed_in_ragged_parts_equals_the_oracle_fed_the_whole(case):
+    """The history of the 10:1 stage and the phases of both mixers carry from part to part: the events, the decimated samples
+    and the (auto) threshold are those of one oracle behind the restatement of the whole input -- without a tune, of
+    parity.fresh_oracle, which on 10x is oracle.decim10 of the whole."""
+    in10x, hz, wide = SEGMENT_CASES[case]
+    sizes, mult = ((2, 1, 2), 10) if in10x else ((3, 2, 3), 1)
+    n = sum(sizes) * api.BLOCK_BYTES // 2 * mult
+    bursts = [dict(proto=j, start=(20000 * mult + j * (n - 40000 * mult) // 3) // mult * mult, payload_seed=7 + 11 * j,
+                   f0_hz=wide + hz, amp=50 + 10 * j) for j in range(3)]  # test_tune_gpu.make_input's bursts, at the tune
+    x = synth.gen_scene(2100, sum(sizes), bursts, rate_mult=mult)
+    cfg = (0x2F, 0, 0)
+    seg = segments.Segment(0, cfg, hz, wide, in10x=in10x)
+    for part in parity.cut(x[None, :], sizes, api.BLOCK_BYTES * mult):
+        seg.feed(part[0])
+    if hz == 0 and wide == 0:
+        want = parity.fresh_oracle(x, *cfg, in10x=in10x, keep_dec=True)
+    else:
+        x16 = tune.s16_of_u8(x)
+        want = O.Oracle(*cfg, keep_dec=True)
+        want.process_s16(tune.mix_s16(tune.decim10_s16(tune.mix10_s16(x16, wide)) if in10x else x16, hz))
+    assert seg.n == sum(sizes) * 4 * api.BLOCK_DEC
+    assert len(want.events_full()) > 0 and parity.decoded(want) != []
+    assert seg.orc.events_full() == want.events_full()
+    assert np.array_equal(seg.orc.dec(), want.dec()) and len(want.dec()) == 2 * sum(sizes) * api.BLOCK_DEC
+    assert seg.orc.thresh() == want.thresh()
+
+
+# ---- the input runner's parts
+@pytest.mark.parametrize("p,q,sizes", [(1, 1, (3, 3, 3, 3)), (4, 3, (3, 3, 3, 3)), (25, 16, (3, 3, 3, 3)), (25, 16, (1, 2, 1, 2))])
+@pytest.mark.parametrize("fmt", ["u8", "s8", "s16", "f32"])
+def test_cut_input_reproduces_the_byte_slices(fmt, p, q, sizes):
+    lens = [formats.bytes_per_sample(fmt) * resample.input_samples(nb, p, q) for nb in sizes]
+    rows = np.random.default_rng(4).integers(0, 256, (2, sum(lens)), dtype=np.uint8)
+    parts = parity.cut_input(rows, sizes, fmt, p, q)
+    assert [part.shape for part in parts] == [(2, n) for n in lens] and all(part.flags["C_CONTIGUOUS"] for part in parts)
+    bounds = np.cumsum([0] + lens)
+    for part, a, b in zip(parts, bounds, bounds[1:]):
+        assert np.array_equal(part, rows[:, a:b])
+    assert np.array_equal(np.concatenate(parts, axis=1), rows)
+    if (fmt, p, q) == ("u8", 1, 1):
+        assert all(np.array_equal(a, b) for a, b in zip(parts, parity.cut(rows, sizes)))
+        assert all(np.array_equal(a, b) for a, b in zip(parity.cut_input(rows, sizes), parts))  # (the defaults)
+    with pytest.raises(AssertionError):
+        parity.cut_input(np.concatenate([rows, rows[:, :1]], axis=1), sizes, fmt, p, q)
+
+
+def test_assert_stage0_names_the_stream_and_the_submit():
+    sizes = (1, 2, 1)
+    per = 2 * 4 * api.BLOCK_DEC
+    want = np.random.default_rng(6).integers(-8192, 8192, (2, sum(sizes) * per)).astype(np.int16)
+    bounds = np.cumsum((0,) + sizes) * per
+    y0 = [[want[s, a:b].copy() for s in range(2)] for a, b in zip(bounds, bounds[1:])]
+    for s in range(2):
+        parity.assert_stage0(y0, sizes, want[s], s)
+        parity.assert_stage0(y0, sizes, want[s], s, "label", tile=512)
+    y0[2][1][-3] ^= 1  # one value of stream 1's last submit
+    parity.assert_stage0(y0, sizes, want[0], 0)
+    with pytest.raises(AssertionError, match=r"4/3 stream 1 submit 2$"):
+        parity.assert_stage0(y0, sizes, want[1], 1, "4/3")
+    with pytest.raises(AssertionError, match=r"stream 1 submit 2: first differing output %d \(mod 512: %d, mod 8: %d\), 1 values" % (
+            per // 2 - 2, (per // 2 - 2) % 512, (per // 2 - 2) % 8)):
+        parity.assert_stage0(y0, sizes, want[1], 1, tile=512)
+    with pytest.raises(AssertionError, match=r"stream 0: 5 values expected behind submit 2"):  # `want` goes on behind the submits
+        parity.assert_stage0(y0, sizes, np.concatenate([want[0], want[0][:5]]), 0)
+    y0[0][1][0] ^= 1
+    parity.assert_stage0(y0[:2] + [[y0[2][0], want[1, bounds[2]:]]], sizes, want[1, per:], 1, first=1)  # first=1 skips submit 0
+    with pytest.raises(AssertionError, match=r"stream 1 submit 0"):
+        parity.assert_stage0(y0, sizes, want[1], 1)
+
+
+@pytest.mark.parametrize("mode", ["deep", "shallow", "serial_chains", "default_mode", "bits", "host"])
+def test_mode_kwargs_is_the_table_the_modules_spelt_out(mode, monkeypatch):
+    monkeypatch.delenv("TFREC_AMD_DEEP", raising=False)
+    kw, layout, flags = parity.mode_kwargs(mode, monkeypatch)
+    assert sorted(parity.MODES) == sorted(["deep", "shallow", "serial_chains", "default_mode", "bits", "host"])
+    assert kw == dict(all_flushes=mode != "default_mode", bits=mode == "bits", serial_chains=mode == "serial_chains",
+                      experiments=mode == "shallow")
+    assert layout == {"shallow": 4, "serial_chains": 2}.get(mode, 6)
+    assert layout == {"deep": 6, "shallow": 4, "serial_chains": 2, "default_mode": 6, "bits": 6, "host": 6}[mode]
+    assert flags == dict(bits=mode == "bits", default_mode=mode == "default_mode", host=mode == "host")
+    assert os.environ.get("TFREC_AMD_DEEP") == ("0" if mode == "shallow" else None)

@@ -9,8 +9,8 @@ import math
 import numpy as np
 import pytest
 
+import parity
 from tfrec_amd import api, formats, resample, tune
-from test_formats_gpu import full_scale_row
 from test_input_tune_cpu import stage0_of as tuned_stage0_of
 
 # ---- the rates of the GPU sweep: (P, Q, T, block unit, tile of the tuned and the format launches, format of case (d)).
@@ -166,7 +166,7 @@ def sweep_rows(fmt, p, q):
     if fmt == "u8":
         rows = np.random.default_rng(1000 * p + q).integers(0, 256, (SWEEP_STREAMS, 2 * n), dtype=np.uint8)
     else:
-        rows = np.concatenate([full_scale_row(fmt, n, 1000 * p + q + 7 * s + 1) for s in range(SWEEP_STREAMS)])
+        rows = np.concatenate([parity.full_scale_row(fmt, n, 1000 * p + q + 7 * s + 1) for s in range(SWEEP_STREAMS)])
     assert rows.shape == (SWEEP_STREAMS, n * formats.bytes_per_sample(fmt)) and not np.array_equal(rows[0], rows[1])
     rows.setflags(write=False)
     return rows

@@ -10,12 +10,10 @@ buffers.  Stage 0 is read back after each submit and compared per stream and sub
 import numpy as np
 import pytest
 
-import test_formats_gpu
-import test_resample_gpu
+import parity
 from tfrec_amd import api, formats, resample, tune
 from test_formats_cpu import stage0_of as fmt_stage0_of
-from test_formats_gpu import full_scale_row
-from test_input_tune_gpu import loud_and_quiet
+from test_resample_cpu import THRESH, TYPES
 from test_rate_sweep_cpu import (SWEEP_FORMAT, SWEEP_IDS, SWEEP_RATES, SWEEP_STREAMS, sweep_rows, sweep_sizes, sweep_stage0,
                                  sweep_tunes, tile_of)
 
@@ -24,33 +22,11 @@ pytestmark = pytest.mark.gpu
 RATES = [r[:2] for r in SWEEP_RATES]
 
 
-def run(fmt, rows, sizes, p, q, before=None, n_streams=None):
-    """test_resample_gpu's run for u8 (tfrec_amd_create_rate) or test_formats_gpu's for a format -> stage 0 per submit and
-    stream.  max_blocks is the largest submit."""
-    kw = dict(before=before, n_streams=n_streams, all_flushes=True, max_events=1 << 16)
-    if fmt == "u8":
-        return test_resample_gpu.run(rows, sizes, p, q, **kw)[1]
-    return test_formats_gpu.run(fmt, rows, sizes, p, q, **kw)[1]
-
-
-def first_difference(got, want, tile):
-    """Where two stage-0 arrays first differ, as the output index and its place in the tile and in the lane's eight outputs."""
-    d = np.nonzero(got != want)[0]
-    if not len(d):
-        return "lengths %d and %d" % (len(got), len(want))
-    m = int(d[0]) // 2
-    return "first differing output %d (mod %d: %d, mod 8: %d), %d values differ" % (m, tile, m % tile, m % 8, len(d))
-
-
-def assert_stage0(y0, sizes, want, s, label, tile=1024, first=0):
-    """Submits first .. of stream s against `want`, the restatement from submit `first` on."""
-    pos = 0
-    for k in range(first, len(sizes)):
-        n = 2 * sizes[k] * 4 * api.BLOCK_DEC
-        got, w = y0[k][s], want[pos:pos + n]
-        assert np.array_equal(got, w), "%s stream %d submit %d: %s" % (label, s, k, first_difference(got, w, tile))
-        pos += n
-    assert pos == len(want)
+def stage0_run(fmt, rows, sizes, p, q, before=None, n_streams=None):
+    """A u8 rate receiver (the older constructor) or a format receiver over the rows -> stage 0 per submit and stream.
+    max_blocks is the largest submit."""
+    return parity.run_input(rows, sizes, p, q, None if fmt == "u8" else fmt, types=TYPES, thresh=THRESH, before=before,
+                            n_streams=n_streams, all_flushes=True, max_events=1 << 16)[1]
 
 
 def tune_first(p, q):
@@ -66,12 +42,12 @@ def tune_first(p, q):
 
 def sweep(fmt, p, q, tuned):
     sizes = sweep_sizes(q)
-    y0 = run(fmt, sweep_rows(fmt, p, q), sizes, p, q, before=tune_first(p, q) if tuned else None)
+    y0 = stage0_run(fmt, sweep_rows(fmt, p, q), sizes, p, q, before=tune_first(p, q) if tuned else None)
     want = sweep_stage0(fmt, p, q, tuned)
     label = "%d/%d %s%s" % (p, q, fmt, " tuned" if tuned else "")
     tile = 1024 if fmt == "u8" and not tuned else tile_of(p, q, resample.n_taps(p, q))
     for s in range(SWEEP_STREAMS):
-        assert_stage0(y0, sizes, want[s], s, label, tile)
+        parity.assert_stage0(y0, sizes, want[s], s, label, tile)
 
 
 @pytest.mark.parametrize("p,q", RATES, ids=SWEEP_IDS)
@@ -106,18 +82,18 @@ def test_base_rate_format_context_reads_mapped_rows(fmt):
     to_x of its row; a map back to the identity before the second submit takes effect."""
     sizes, rows_of = (1, 1), ([1, 1, 0], [0, 1, 2])
     n = resample.input_samples(sum(sizes), 1, 1)
-    rows = np.concatenate([full_scale_row(fmt, n, 11 + s) for s in range(3)])
+    rows = np.concatenate([parity.full_scale_row(fmt, n, 11 + s) for s in range(3)])
 
     def before(r, k):
         r.map_streams([0, 1, 2], rows_of[k])
         assert [r.stream_input(s) for s in range(3)] == rows_of[k] and r.rows_in_use == (2, 3)[k]
 
-    y0 = run(fmt, rows, sizes, 1, 1, before=before)
+    y0 = stage0_run(fmt, rows, sizes, 1, 1, before=before)
     half = rows.shape[1] // 2
     for k in range(2):
         for s in range(3):
             want = fmt_stage0_of(fmt, rows[rows_of[k][s], k * half:(k + 1) * half], 1, 1)
-            assert np.array_equal(y0[k][s], want), "%s submit %d stream %d: %s" % (fmt, k, s, first_difference(y0[k][s], want, 2048))
+            assert np.array_equal(y0[k][s], want), "%s submit %d stream %d: %s" % (fmt, k, s, parity.first_difference(y0[k][s], want, 2048))
     assert not np.array_equal(y0[0][0], y0[0][2]) and not np.array_equal(y0[1][0], y0[1][1])
 
 
@@ -133,11 +109,11 @@ def test_shared_row_at_a_half_tile_rate():
             r.tune_streams_input([0, 1, 2], hz)
             assert r.rows_in_use == 1
 
-    y0 = run(fmt, row, sizes, p, q, before=before, n_streams=3)
+    y0 = stage0_run(fmt, row, sizes, p, q, before=before, n_streams=3)
     x = formats.to_x(fmt, row[0])
     for s in range(3):
         want = sweep_stage0(fmt, p, q, True)[0] if s == 0 else resample.resample_x16(tune.mix_in_s16(x, hz[s], p, q), p, q)
-        assert_stage0(y0, sizes, want, s, "39/4 f32 shared row", 512)
+        parity.assert_stage0(y0, sizes, want, s, "39/4 f32 shared row", 512)
 
 
 @pytest.mark.parametrize("fmt,p,q", [("u8", 65, 64), ("s16", 39, 4)])
@@ -146,19 +122,19 @@ def test_reset_at_an_edge_rate(fmt, p, q):
     history and phase 0; stream 0 carries on."""
     sizes = sweep_sizes(q)
     if fmt == "u8":
-        rows = loud_and_quiet(p, q, sizes, 2, 1000 * p + q)
+        rows = parity.loud_and_quiet(p, q, sizes, 2, 1000 * p + q)
     else:
-        rows = np.concatenate([full_scale_row(fmt, resample.input_samples(sum(sizes), p, q), 31 + s) for s in range(2)])
-    y0 = run(fmt, rows, sizes, p, q, before=lambda r, k: r.reset_streams([1]) if k == 1 else None)
+        rows = np.concatenate([parity.full_scale_row(fmt, resample.input_samples(sum(sizes), p, q), 31 + s) for s in range(2)])
+    y0 = stage0_run(fmt, rows, sizes, p, q, before=lambda r, k: r.reset_streams([1]) if k == 1 else None)
 
     def restated(row):
         return resample.resample_s16(row, p, q) if fmt == "u8" else fmt_stage0_of(fmt, row, p, q)
 
     tile = 1024 if fmt == "u8" else tile_of(p, q, resample.n_taps(p, q))
     cut = formats.bytes_per_sample(fmt) * resample.input_samples(sizes[0], p, q)
-    assert_stage0(y0, sizes, restated(rows[0]), 0, "%d/%d %s beside a reset" % (p, q, fmt), tile)
+    parity.assert_stage0(y0, sizes, restated(rows[0]), 0, "%d/%d %s beside a reset" % (p, q, fmt), tile)
     whole = restated(rows[1])
     n0 = 2 * sizes[0] * 4 * api.BLOCK_DEC
     assert np.array_equal(y0[0][1], whole[:n0])
-    assert_stage0(y0, sizes, restated(rows[1][cut:]), 1, "%d/%d %s after the reset" % (p, q, fmt), tile, first=1)
+    parity.assert_stage0(y0, sizes, restated(rows[1][cut:]), 1, "%d/%d %s after the reset" % (p, q, fmt), tile, first=1)
     assert not np.array_equal(y0[1][1][:16], whole[n0:][:16])  # the history is silence, not the carried stream's

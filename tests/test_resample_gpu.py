@@ -3,53 +3,20 @@
 Stage 0 is pinned by the restatement tfrec_amd/resample.py, everything behind it by the oracle's process_s16 fed that
 restatement's output.  The scenes are recordings at 2.048 MS/s (4/3) and 2.4 MS/s (25/16); test_resample_cpu.py asserts that
 the oracle decodes a telegram of every protocol from them."""
+import functools
 import subprocess
 
 import numpy as np
 import pytest
 
 import parity
-from oracle import oracle as O
-from tfrec_amd import api, resample, synth, tune
+from tfrec_amd import api, resample
 from test_resample_cpu import SCENE_BLOCKS, SCENE_RATES, THRESH, TYPES, oracle_of, rate_scene
 
 pytestmark = pytest.mark.gpu
 
 
-def cut_rate(iq, sizes, p, q):
-    """iq[rows, bytes] -> consecutive parts of sizes[k] blocks each at the input rate p / q."""
-    parts, pos = [], 0
-    for nb in sizes:
-        n = 2 * resample.input_samples(nb, p, q)
-        parts.append(np.ascontiguousarray(iq[:, pos:pos + n]))
-        pos += n
-    assert pos == iq.shape[1]
-    return parts
-
-
-def to_device(parts):
-    import torch
-
-    return [torch.from_numpy(h).to("cuda:0") for h in parts]
-
-
-def run(iq, sizes, p, q, host=False, before=None, n_streams=None, stage0=True, **kw):
-    """A rate receiver over the scene cut into `sizes` -> (one drained array per submit, the receiver's stage 0 per submit
-    and stream).  stage0=False: nothing is read back between the submits, and they queue up to the FIFO's depth."""
-    parts = cut_rate(iq, sizes, p, q)
-    n = len(iq) if n_streams is None else n_streams
-    y0 = []
-    with api.Receiver(n, TYPES, THRESH, 0, max_blocks=max(sizes), input_rate=(p, q), **kw) as r:
-        assert r.input_rate == (p, q)
-        for k, nb in enumerate(sizes):
-            assert r.input_bytes(nb) == parts[k].shape[1]
-
-        def after(k):
-            y0.append([r.stage0(s, sizes[k] * 4 * api.BLOCK_DEC) for s in range(n)])
-
-        evs = parity.run_fifo(r, parts if host else to_device(parts), before=(lambda k: before(r, k)) if before else None,
-                              after=after if stage0 else None)
-    return evs, y0
+run_input = functools.partial(parity.run_input, types=TYPES, thresh=THRESH)
 
 
 @pytest.mark.parametrize("p,q", SCENE_RATES)
@@ -57,34 +24,27 @@ def test_stage0_equals_the_restatement(p, q):
     """The first submit and three following ones: the history carry and both history buffers."""
     iq = rate_scene(p, q)
     sizes = (3, 3, 3, 3)
-    _, y0 = run(iq, sizes, p, q, all_flushes=True)
+    _, y0 = run_input(iq, sizes, p, q, all_flushes=True)
     for s in range(len(iq)):
         want = resample.resample_s16(iq[s], p, q)
         assert len(want) == 2 * SCENE_BLOCKS * 4 * api.BLOCK_DEC
-        pos = 0
-        for k, nb in enumerate(sizes):
-            n = 2 * nb * 4 * api.BLOCK_DEC
-            assert np.array_equal(y0[k][s], want[pos:pos + n]), "stream %d submit %d" % (s, k)
-            pos += n
+        parity.assert_stage0(y0, sizes, want, s)
 
 
 @pytest.mark.parametrize("p,q", SCENE_RATES)
 @pytest.mark.parametrize("mode", ["deep", "shallow", "serial_chains", "default_mode", "bits", "host"])
 def test_events_equal_the_oracle_behind_the_restatement(mode, p, q, monkeypatch):
-    if mode == "shallow":
-        monkeypatch.setenv("TFREC_AMD_DEEP", "0")
+    kw, layout, flags = parity.mode_kwargs(mode, monkeypatch)
     iq = rate_scene(p, q)
-    kw = dict(all_flushes=mode != "default_mode", bits=mode == "bits", serial_chains=mode == "serial_chains",
-              experiments=mode == "shallow")
     layouts = []
-    evs, _ = run(iq, (3, 3, 3, 3), p, q, host=mode == "host", stage0=False, before=lambda r, k: layouts.append(r.layout()), **kw)
-    assert layouts[0] == {"shallow": 4, "serial_chains": 2}.get(mode, 6)
+    evs, _ = run_input(iq, (3, 3, 3, 3), p, q, host=flags["host"], stage0=False, before=lambda r, k: layouts.append(r.layout()), **kw)
+    assert layouts[0] == layout
     ev = np.concatenate(evs)
     total = telegrams = 0
     for s in range(len(iq)):
-        orc = oracle_of(iq[s], p, q, log_bits=mode == "bits")
-        total += parity.assert_stream(ev, s, orc, default_mode=mode == "default_mode")
-        if mode == "bits":
+        orc = oracle_of(iq[s], p, q, log_bits=flags["bits"])
+        total += parity.assert_stream(ev, s, orc, default_mode=flags["default_mode"])
+        if flags["bits"]:
             assert parity.assert_bits(ev, s, orc, "stream %d" % s) > 1000
         telegrams += sum(1 for e in orc.events_full() if e[7] == 1)
     assert total >= 8 and telegrams >= 8  # four protocols or more per stream decode
@@ -93,8 +53,8 @@ def test_events_equal_the_oracle_behind_the_restatement(mode, p, q, monkeypatch)
 @pytest.mark.parametrize("p,q", SCENE_RATES)
 def test_results_do_not_depend_on_the_cut(p, q):
     iq = rate_scene(p, q)
-    one, _ = run(iq, (12,), p, q, all_flushes=True)
-    four, _ = run(iq, (3, 3, 3, 3), p, q, all_flushes=True)
+    one, _ = run_input(iq, (12,), p, q, all_flushes=True)
+    four, _ = run_input(iq, (3, 3, 3, 3), p, q, all_flushes=True)
     a, b = parity.sort_events(np.concatenate(one)), parity.sort_events(np.concatenate(four))
     assert len(a) > 20 and a.tobytes() == b.tobytes()
 
@@ -103,7 +63,7 @@ def test_reset_in_mid_stream_equals_a_fresh_receiver():
     p, q = 4, 3
     iq = rate_scene(p, q)
     sizes = (3, 3, 3, 3)
-    evs, y0 = run(iq, sizes, p, q, all_flushes=True, before=lambda r, k: r.reset_streams([1]) if k == 2 else None)
+    evs, y0 = run_input(iq, sizes, p, q, all_flushes=True, before=lambda r, k: r.reset_streams([1]) if k == 2 else None)
     cut = 2 * resample.input_samples(6, p, q)
     # stream 0 carries on; stream 1 is a receiver on the input before the cut, then a fresh one on the input after it
     parity.assert_segment(np.concatenate(evs), 0, oracle_of(iq[0], p, q), "stream 0")
@@ -118,28 +78,13 @@ def test_reset_in_mid_stream_equals_a_fresh_receiver():
 TUNES = (200000, -250000)
 
 
-def tuned_row(p, q, n_blocks=6):
-    """One recording at 1536000 p / q with a burst at each of TUNES (and one at the centre)."""
-    n = n_blocks * api.BLOCK_BYTES // 2 * p
-    bursts = [dict(proto=j, start=(40000 * p + j * (n - 100000 * p) // 3) // q * q, payload_seed=21 + j, f0_hz=f, amp=50)
-              for j, f in enumerate((0,) + TUNES)]
-    x = synth.gen_scene(77, n_blocks, bursts, rate_mult=p).reshape(-1, 2)[::q]
-    return np.ascontiguousarray(x).reshape(1, -1)
-
-
-def tuned_oracle(x, p, q, hz):
-    o = O.Oracle(TYPES, THRESH, 0)
-    o.process_s16(tune.mix_s16(resample.resample_s16(x, p, q), hz, 0))
-    return o
-
-
 @pytest.mark.parametrize("p,q", SCENE_RATES)
 def test_tunes_and_shared_rows_compose(p, q):
     """tune_streams acts on y0: the oracle on tune.py's mixer applied to the restatement's output.  Three streams mapped to one
     row with different tunes equal three receivers fed copies of it."""
-    row = tuned_row(p, q)
-    sizes = (3, 3)
     hz = (0,) + TUNES
+    row = parity.tuned_row(p, q, hz)
+    sizes = (3, 3)
 
     def shared(r, k):
         if k == 0:
@@ -151,14 +96,14 @@ def test_tunes_and_shared_rows_compose(p, q):
         if k == 0:
             r.tune_streams([0, 1, 2], hz)
 
-    ev_shared, y0 = run(row, sizes, p, q, n_streams=3, before=shared, all_flushes=True)
-    ev_copies, _ = run(np.repeat(row, 3, axis=0), sizes, p, q, before=copies, all_flushes=True)
+    ev_shared, y0 = run_input(row, sizes, p, q, n_streams=3, before=shared, all_flushes=True)
+    ev_copies, _ = run_input(np.repeat(row, 3, axis=0), sizes, p, q, before=copies, all_flushes=True)
     a, b = parity.sort_events(np.concatenate(ev_shared)), parity.sort_events(np.concatenate(ev_copies))
     assert a.tobytes() == b.tobytes()
     for s in range(3):
-        orc = tuned_oracle(row[0], p, q, hz[s])
+        orc = parity.tuned_oracle(p, q, hz, narrow_hz=hz[s], types=TYPES, thresh=THRESH)
         parity.assert_segment(a, s, orc, "stream %d tune %d" % (s, hz[s]))
-        assert [e[0] for e in orc.events_full() if e[7] == 1] == [s], s  # each receiver decodes the burst it is tuned to
+        assert parity.decoded(orc) == [s], s  # each receiver decodes the burst it is tuned to
         assert np.array_equal(y0[0][s], resample.resample_s16(row[0], p, q)[:len(y0[0][s])])  # stage 0 is ahead of the tune
 
 

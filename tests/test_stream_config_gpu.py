@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import parity
+import segments
 from oracle import oracle as O
 from tfrec_amd import api, synth
 
@@ -44,59 +45,6 @@ MIX = [(0x04, 300, 1), (0x02, 500, 0), (0x01, 0, 0), (0x08, 900, 0), (0x20, 0, 1
        None, (0x28, 300, 0), (0x01, 500, 0), (0x2F, 900, 0), (0x21, 0, 1), None, (0x02, 0, 1), (0x2E, 500, 0), (0x01, 300, 0)]
 
 
-def apply(r, ops):
-    """ops: [("conf", streams, [(types_mask, thresh, filter_type), ...]) | ("reset", streams)], in order."""
-    for op in ops:
-        if op[0] == "conf":
-            r.configure_streams(op[1], types_mask=[c[0] for c in op[2]], thresh=[c[1] for c in op[2]],
-                                filter_type=[c[2] for c in op[2]])
-        else:
-            r.reset_streams(op[1])
-
-
-def run_and_check(r, parts, ops, dflt, in10x=False, bits=False):
-    """Submit parts[k] with up to FIFO_DEPTH submits in flight, ops[k] applied before submit k (while older submits are still
-    queued).  Every stream, segment by segment (a segment starts at a restart), against a fresh oracle with the segment's
-    settings; read_thresh against the oracle after every submit.  -> events compared."""
-    n = parts[0].shape[0]
-    cur = [dflt] * n
-    segs = [[] for _ in range(n)]  # per stream: [first submit, settings, oracle] of each segment
-
-    def before(k):
-        restart = set()
-        for op in ops.get(k, ()):
-            apply(r, [op])
-            for i, s in enumerate(op[1]):
-                restart.add(s)
-                if op[0] == "conf":
-                    cur[s] = op[2][i]
-        for s in range(n):
-            assert r.stream_config(s) == dict(zip(("types_mask", "thresh", "filter_type"), cur[s])), "stream %d" % s
-            if k == 0 or s in restart:
-                c = cur[s]
-                segs[s].append([k, c, O.Oracle(c[0], c[1], c[2], log_bits=bits)])
-
-    def after(k):
-        for s in range(n):  # the oracles follow submit by submit: the threshold each stream has after it
-            orc = segs[s][-1][2]
-            if in10x:
-                orc.process_s16(O.decim10(np.asarray(parts[k][s])))
-            else:
-                orc.process(np.asarray(parts[k][s]))
-            assert r.thresh(s) == orc.thresh(), "stream %d submit %d threshold" % (s, k)
-
-    evs = parity.run_fifo(r, parts, before=before, after=after)
-    total = 0
-    for s in range(n):
-        bounds = [g[0] for g in segs[s]] + [len(parts)]
-        for g, (_, c, orc) in enumerate(segs[s]):
-            ev = np.concatenate([e[e["stream"] == s] for e in evs[bounds[g]:bounds[g + 1]]])
-            total += parity.assert_segment(ev, s, orc, "stream %d segment %d settings %s" % (s, g, c), bits)
-            own = {i for i in range(5) if c[0] & (1 << (i if i < 4 else 5))}
-            assert set(np.unique(ev["slot"]).tolist()) <= own, "stream %d: a slot outside its types" % s
-    return total
-
-
 def test_inputs_discriminate():
     """On the oracle alone: the pulse train ends a TFA_1-only auto stream at another threshold than an all-types one (a
     context-wide Wmax would be caught), and the two filters give different events on the test input."""
@@ -126,7 +74,7 @@ def test_mixed_context(dflt):
     idx = [s for s, c in enumerate(table) if c is not None]
     ops = {0: [("conf", idx, [table[s] for s in idx])]}
     with api.Receiver(len(MIX), dflt[0], dflt[1], dflt[2], max_blocks=max(SIZES), all_flushes=True) as r:
-        n = run_and_check(r, parts, ops, dflt)
+        n, _ = segments.run_segments(r, parts, ops, dflt)
     assert n > 10 * len(MIX)
 
 
@@ -148,7 +96,7 @@ def test_modes(mode):
     ops = {0: [("conf", idx, [table[s] for s in idx])],
            2: [("conf", [1, 5, 8], [(0x2F, 0, 0), (0x01, 500, 1), (0x20, 300, 0)]), ("reset", [3])]}
     with api.Receiver(MODE_N, 0x2F, 0, 0, **kw) as r:
-        n = run_and_check(r, parts, ops, (0x2F, 0, 0), in10x=(rate == 10), bits=(mode == "bits"))
+        n, _ = segments.run_segments(r, parts, ops, (0x2F, 0, 0), in10x=(rate == 10), bits=(mode == "bits"))
     assert n > 0
 
 
@@ -167,14 +115,18 @@ def test_reconfigure_mid_run():
            4: [("conf", [5], [(0x06, 300, 1)]), ("reset", [5]), ("reset", [6]), ("conf", [6], [(0x20, 0, 0)])]}
     dflt = (0x2F, 500, 0)
     with api.Receiver(n_streams, *dflt, max_blocks=max(sizes), all_flushes=True) as r:
-        run_and_check(r, parts, ops, dflt)
+        segments.run_segments(r, parts, ops, dflt)
         assert r.stream_config(2) == {"types_mask": 0x01, "thresh": 0, "filter_type": 0}
     with api.Receiver(n_streams, *dflt, max_blocks=max(sizes), all_flushes=True) as r:  # untouched streams: as without calls
         ev_plain = parity.run_fifo(r, parts, depth=1)
     with api.Receiver(n_streams, *dflt, max_blocks=max(sizes), all_flushes=True) as r:
         ev_conf = []
         for k, p in enumerate(parts):
-            apply(r, ops.get(k, ()))
+            for op in ops.get(k, ()):
+                if op[0] == "conf":
+                    r.configure_streams(op[1], *zip(*op[2]))
+                else:
+                    r.reset_streams(op[1])
             r.submit(np.ascontiguousarray(p))
             ev_conf.append(r.drain())
     for s in (3, 7, 8, 9):

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import parity
+import segments
 from tfrec_amd import api, synth
 
 pytestmark = pytest.mark.gpu
@@ -19,39 +20,11 @@ pytestmark = pytest.mark.gpu
 B = api.BLOCK_BYTES
 
 
-def run_gpu(r, parts, resets):
-    """parity.run_fifo with resets[k] = the streams reset before submit k (called while older submits are still queued)."""
-    def before(k):
-        if k in resets:
-            r.reset_streams(resets[k])
-    return parity.run_fifo(r, parts, before=before)
-
-
-def segments(parts, resets, s):
-    """Stream s's input cut at its resets -> (list of byte arrays, segment index of every submit)."""
-    segs, seg_of = [[]], []
-    for k, p in enumerate(parts):
-        if s in set(resets.get(k, ())) and k > 0:
-            segs.append([])
-        segs[-1].append(np.asarray(p[s]))
-        seg_of.append(len(segs) - 1)
-    return [np.concatenate(x) for x in segs], seg_of
-
-
-def check_all(evs, parts, resets, n_streams, types=0x2F, thresh=500, wide=0, in10x=False, bits=False, r=None):
-    """Every stream, segment by segment, against a fresh oracle per segment.  -> events compared."""
-    total = 0
-    for s in range(n_streams):
-        segs, seg_of = segments(parts, resets, s)
-        got = [[] for _ in segs]
-        for k, ev in enumerate(evs):
-            got[seg_of[k]].append(ev[ev["stream"] == s])
-        for g, seg in enumerate(segs):
-            orc = parity.fresh_oracle(seg, types, thresh, wide, in10x, log_bits=bits)
-            total += parity.assert_segment(np.concatenate(got[g]), s, orc, "stream %d segment %d" % (s, g), bits)
-        if r is not None and thresh == 0:  # auto threshold: the stream's last segment started from 500
-            assert r.thresh(s) == orc.thresh(), "stream %d threshold" % s
-    return total
+def check_resets(r, parts, resets, types=0x2F, thresh=500, wide=0, **kw):
+    """resets[k]: the streams reset before submit k.  Nothing is read from the receiver between the submits: the resets arrive
+    with the FIFO full.  -> events compared."""
+    ops = {k: [("reset", streams)] for k, streams in resets.items()}
+    return segments.run_segments(r, parts, ops, (types, thresh, wide), read_between=False, **kw)[0]
 
 
 N_STREAMS = 8
@@ -63,13 +36,9 @@ LAYOUTS = pytest.mark.parametrize("layout", ["deep", "shallow", "serial"])
 
 
 def make_receiver(layout, monkeypatch, **kw):
-    if layout == "shallow":
-        monkeypatch.setenv("TFREC_AMD_DEEP", "0")
-        r = api.Receiver(N_STREAMS, experiments=True, **kw)
-        assert r.layout() == 4
-        return r
-    r = api.Receiver(N_STREAMS, serial_chains=(layout == "serial"), **kw)
-    assert r.layout() == (2 if layout == "serial" else 6)
+    mode, want, _ = parity.mode_kwargs("serial_chains" if layout == "serial" else layout, monkeypatch)
+    r = api.Receiver(N_STREAMS, **dict(mode, **kw))
+    assert r.layout() == want
     return r
 
 
@@ -79,8 +48,7 @@ def test_reset_some_streams(layout, thresh, monkeypatch):
     iq = synth.gen_batch(71, 0, N_STREAMS, sum(SIZES))
     parts = parity.cut(iq, SIZES)
     with make_receiver(layout, monkeypatch, thresh=thresh, max_blocks=max(SIZES), all_flushes=True) as r:
-        evs = run_gpu(r, parts, RESETS)
-        n = check_all(evs, parts, RESETS, N_STREAMS, thresh=thresh, r=r)
+        n = check_resets(r, parts, RESETS, thresh=thresh)
     assert n > 20 * N_STREAMS
 
 
@@ -89,16 +57,14 @@ def test_reset_some_streams_wide_filter(layout, monkeypatch):
     iq = synth.gen_batch(72, 0, N_STREAMS, sum(SIZES))
     parts = parity.cut(iq, SIZES)
     with make_receiver(layout, monkeypatch, thresh=0, filter_type=1, max_blocks=max(SIZES), all_flushes=True) as r:
-        evs = run_gpu(r, parts, RESETS)
-        check_all(evs, parts, RESETS, N_STREAMS, thresh=0, wide=1, r=r)
+        check_resets(r, parts, RESETS, thresh=0, wide=1)
 
 
 def test_reset_some_streams_bits_mode():
     iq = synth.gen_batch(73, 0, N_STREAMS, sum(SIZES))
     parts = parity.cut(iq, SIZES)
     with api.Receiver(N_STREAMS, max_blocks=max(SIZES), all_flushes=True, bits=True, max_events=1 << 17) as r:
-        evs = run_gpu(r, parts, RESETS)
-        check_all(evs, parts, RESETS, N_STREAMS, bits=True)
+        check_resets(r, parts, RESETS, bits=True)
 
 
 @pytest.mark.parametrize("layout", ["deep", "shallow"])
@@ -111,8 +77,7 @@ def test_reset_with_whb_check_forced_to_fail(layout, monkeypatch):
     iq = synth.gen_batch(74, 0, N_STREAMS, sum(SIZES))
     parts = parity.cut(iq, SIZES)
     with api.Receiver(N_STREAMS, max_blocks=max(SIZES), all_flushes=True, experiments=True) as r:
-        evs = run_gpu(r, parts, RESETS)
-        check_all(evs, parts, RESETS, N_STREAMS)
+        check_resets(r, parts, RESETS)
         assert r.stats()["whb_respeculated"] > 0
 
 
@@ -122,8 +87,7 @@ def test_reset_on_the_10x_input():
     iq = np.stack([synth.gen_stream(75, s, sum(sizes), rate_mult=10) for s in range(N_STREAMS)])
     parts = parity.cut(iq, sizes, bb)
     with api.Receiver(N_STREAMS, max_blocks=max(sizes), all_flushes=True, input_10x=True) as r:
-        evs = run_gpu(r, parts, RESETS)
-        n = check_all(evs, parts, RESETS, N_STREAMS, in10x=True)
+        n = check_resets(r, parts, RESETS, in10x=True)
     assert n > 0
 
 
@@ -145,8 +109,7 @@ def test_windows_open_at_the_cut_are_dropped():
     parts = parity.cut(iq, (cut_blocks, n_blocks - cut_blocks))
     resets = {1: [0, 1, 2, 3, 4]}
     with api.Receiver(len(rows), max_blocks=cut_blocks, all_flushes=True) as r:
-        evs = run_gpu(r, parts, resets)
-        check_all(evs, parts, resets, len(rows))
+        check_resets(r, parts, resets)
     m = cut // 4  # decimated samples before the cut
     for s in range(5):  # the cut matters: one receiver over the whole row flushes the straddling burst's window
         whole = sorted(parity.fresh_oracle(iq[s], 0x2F, 500, 0).events_full())
@@ -163,9 +126,9 @@ def test_reset_every_stream_equals_a_new_context(bits):
     parts = parity.cut(iq, (3, 3, 3))
     kw = dict(max_blocks=3, all_flushes=True, bits=bits, max_events=1 << 16)
     with api.Receiver(N_STREAMS, **kw) as r:
-        evs = run_gpu(r, parts, {1: list(range(N_STREAMS))})
+        evs = parity.run_fifo(r, parts, before=lambda k: r.reset_streams(range(N_STREAMS)) if k == 1 else None)
     with api.Receiver(N_STREAMS, **kw) as r2:
-        evs2 = run_gpu(r2, parts[1:], {})
+        evs2 = parity.run_fifo(r2, parts[1:])
     got, want = np.concatenate(evs[1:]), np.concatenate(evs2)
     assert len(want) > 2 * N_STREAMS
     assert bool((want["status"] == api.STATUS_BITS).any()) == bits
@@ -177,8 +140,7 @@ def test_stream_recycled_before_every_submit():
     parts = [synth.gen_batch(90 + k, 10 * k, N_STREAMS, nb) for k, nb in enumerate((2, 1, 3, 2, 1, 2))]
     resets = {k: [2, 5] for k in range(1, len(parts))}
     with api.Receiver(N_STREAMS, thresh=0, max_blocks=3, all_flushes=True) as r:
-        evs = run_gpu(r, parts, resets)
-        check_all(evs, parts, resets, N_STREAMS, thresh=0, r=r)
+        check_resets(r, parts, resets, thresh=0)
 
 
 @pytest.mark.parametrize("proto", ["tfa_1", "tfa_2", "tfa_3", "tx22", "whb"])
@@ -193,7 +155,7 @@ def test_reset_stream_reproduces_the_real_reference_fixture(proto, golden_dir):
     second = synth.gen_batch(78, 0, 3, nb)
     second[1] = fx
     with api.Receiver(3, meta["types"], meta["thresh"], meta["wide"], max_blocks=max(4, nb), all_flushes=True) as r:
-        evs = run_gpu(r, [first, second], {1: [1]})
+        evs = parity.run_fifo(r, [first, second], before=lambda k: r.reset_streams([1]) if k == 1 else None)
     got = sorted(api.event_tuples(evs[1], 1))
     want = sorted((e[0], e[1], e[2], e[3], e[4], bytes.fromhex(e[5])) for e in meta["events"])
     assert got == want

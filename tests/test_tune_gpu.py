@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import parity
+import segments
 from oracle import oracle as O
 from tfrec_amd import api, synth, tune
 
@@ -40,75 +41,6 @@ def make_input(seed, tunes, n_blocks, rate_mult=1):
     return np.stack(rows)
 
 
-class Seg:
-    """One segment of a stream (from its start or a restart on): its settings, tune and oracle, and the input it has seen."""
-
-    def __init__(self, k, cfg, tune_hz, bits, in10x):
-        self.k, self.cfg, self.tune, self.in10x = k, cfg, tune_hz, in10x
-        self.orc = O.Oracle(cfg[0], cfg[1], cfg[2], log_bits=bits, keep_dec=True)
-        self.raw = []
-        self.n = 0  # 1.536 MS/s samples fed
-
-    def feed(self, part):
-        part = np.asarray(part)
-        if self.in10x:  # (the 10:1 stage carries its history: decimate the segment so far, feed what is new)
-            self.raw.append(part)
-            x16 = O.decim10(np.concatenate(self.raw))[2 * self.n:]
-        else:
-            x16 = tune.s16_of_u8(part)
-        self.orc.process_s16(tune.mix_s16(x16, self.tune, self.n))
-        self.n += len(x16) // 2
-
-
-def run_and_check(r, parts, ops, dflt, in10x=False, bits=False, default_mode=False):
-    """Submit parts[k] with the FIFO up to four deep; ops[k] (("tune", streams, hz) | ("conf", streams, cfgs) | ("reset",
-    streams)) are applied before submit k.  Every stream, segment by segment, against a fresh oracle of the segment's settings
-    and tune; read_thresh after every submit and read_decimated after the last.  -> events compared."""
-    n = parts[0].shape[0]
-    cfg, tn = [dflt] * n, [0] * n
-    segs = [[] for _ in range(n)]
-
-    def before(k):
-        restart = set()
-        for op in ops.get(k, ()):
-            if op[0] == "tune":
-                r.tune_streams(op[1], op[2])
-                for s, v in zip(op[1], op[2]):
-                    tn[s] = v
-            elif op[0] == "conf":
-                r.configure_streams(op[1], types_mask=[c[0] for c in op[2]], thresh=[c[1] for c in op[2]],
-                                    filter_type=[c[2] for c in op[2]])
-                for s, c in zip(op[1], op[2]):
-                    cfg[s] = c
-            else:
-                r.reset_streams(op[1])
-            restart |= set(op[1])
-        for s in range(n):
-            assert r.stream_tune(s) == tn[s], "stream %d" % s
-            if k == 0 or s in restart:
-                segs[s].append(Seg(k, cfg[s], tn[s], bits, in10x))
-
-    def after(k):
-        for s in range(n):
-            segs[s][-1].feed(parts[k][s])
-            assert r.thresh(s) == segs[s][-1].orc.thresh(), "stream %d submit %d threshold" % (s, k)
-
-    evs = parity.run_fifo(r, parts, before=before, after=after)
-    m = parts[-1].shape[1] // r.block_bytes * api.BLOCK_DEC
-    total = 0
-    for s in range(n):
-        assert np.array_equal(r.decimated(s, m), segs[s][-1].orc.dec()[-2 * m:]), "stream %d decimated" % s
-        bounds = [g.k for g in segs[s]] + [len(parts)]
-        for i, g in enumerate(segs[s]):
-            ev = np.concatenate([e[e["stream"] == s] for e in evs[bounds[i]:bounds[i + 1]]])
-            label = "stream %d segment %d settings %s tune %d" % (s, i, g.cfg, g.tune)
-            if default_mode:
-                total += parity.assert_stream(ev, s, g.orc, label, default_mode=True)
-            else:
-                total += parity.assert_segment(ev, s, g.orc, label, bits)
-    return total, segs
-
-
 def conf_op(idx, dflt):
     idx = [s for s in idx if CFGS[s] is not None]
     return ("conf", idx, [CFGS[s] for s in idx])
@@ -125,7 +57,7 @@ def test_tuned_context_parity(in10x):
     ops = {0: [conf_op(range(n), dflt), ("tune", list(range(n)), TUNES)],
            1: [("tune", [3, 8, 13], [-25000, 0, 767999]), ("reset", [5])]}  # a mid-run tune (and one back to 0) beside a reset
     with api.Receiver(n, dflt[0], dflt[1], dflt[2], max_blocks=max(sizes), all_flushes=True, input_10x=in10x) as r:
-        total, segs = run_and_check(r, parts, ops, dflt, in10x=in10x)
+        total, segs = segments.run_segments(r, parts, ops, dflt, in10x=in10x)
     assert total > 5 * n
     # the planted bursts at the tune offsets decode: a telegram in most tuned segments
     tuned = [g for s in range(n) for g in segs[s] if g.tune != 0]
@@ -133,16 +65,16 @@ def test_tuned_context_parity(in10x):
 
 
 @pytest.mark.parametrize("mode", ["bits", "default_mode", "serial_chains"])
-def test_tuned_modes(mode):
+def test_tuned_modes(mode, monkeypatch):
     n = 12
     tunes = TUNES[:n]
     iq = make_input(22, tunes, sum(SIZES))
     parts = parity.cut(iq, SIZES)
     dflt = (0x2F, 500, 0)
     ops = {0: [conf_op(range(n), dflt), ("tune", list(range(n)), tunes)], 2: [("tune", [1, 2], [-200000, 150000])]}
-    kw = dict(bits=mode == "bits", all_flushes=mode != "default_mode", serial_chains=mode == "serial_chains")
+    kw, _, flags = parity.mode_kwargs(mode, monkeypatch)
     with api.Receiver(n, dflt[0], dflt[1], dflt[2], max_blocks=max(SIZES), **kw) as r:
-        total, _ = run_and_check(r, parts, ops, dflt, bits=mode == "bits", default_mode=mode == "default_mode")
+        total, _ = segments.run_segments(r, parts, ops, dflt, bits=flags["bits"], default_mode=flags["default_mode"])
     assert total > n
 
 
@@ -160,7 +92,7 @@ def test_restart_semantics():
            2: [("tune", [2], [150000]), ("conf", [2], [(0x2F, 0, 1)]), ("reset", [2, 3]), ("conf", [4], [(0x03, 500, 1)])],
            3: [("reset", [0]), ("conf", [2], [(0x2F, 300, 0)])]}
     with api.Receiver(n, dflt[0], dflt[1], dflt[2], max_blocks=2, all_flushes=True) as r:
-        total, segs = run_and_check(r, parts, ops, dflt)
+        total, segs = segments.run_segments(r, parts, ops, dflt)
         assert [r.stream_tune(s) for s in range(n)] == [200000, -250000, 150000, -400000, 25000, -200000, 0, 0]
     assert [len(segs[s]) for s in range(n)] == [2, 2, 3, 3, 3, 1, 1, 1]
     assert total > 4 * n
@@ -231,10 +163,6 @@ def test_argument_errors_change_nothing():
 
 
 # ---- tfrec_gpu -f / -c / -p f=
-def telegram_lines(text):
-    return [ln for ln in text.splitlines() if ln.startswith(tuple(parity.PREFIX.values())) and not ln.startswith("WHB:")]
-
-
 @pytest.fixture(scope="module")
 def dump(tmp_path_factory):
     parity.build_cli()
@@ -245,23 +173,16 @@ def dump(tmp_path_factory):
     return d, str(p), x
 
 
-def cli_stdout(args):
-    import subprocess
-    out = subprocess.run([parity.CLI] + args, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr
-    return out.stdout
-
-
 def test_tfrec_gpu_receive_frequency(dump):
     d, path, x = dump
     o = O.Oracle(0x07, 0, 0)  # tfrec_gpu's defaults: -T 7, -t 0 (auto)
     o.process_s16(tune.mix_s16(tune.s16_of_u8(x), -200000))
-    want = telegram_lines(o.text())
+    want = parity.telegram_lines(o.text())
     assert len(want) == 1 and want[0].startswith("TFA2 ")
-    tuned = cli_stdout(["-f", "868050", "-L", path])
-    assert telegram_lines(tuned) == want
-    assert cli_stdout(["-c", "868300", "-f", "868100", "-L", path]) == tuned
-    assert telegram_lines(cli_stdout(["-L", path])) == []
+    tuned = parity.cli_stdout(["-f", "868050", "-L", path])
+    assert parity.telegram_lines(tuned) == want
+    assert parity.cli_stdout(["-c", "868300", "-f", "868100", "-L", path]) == tuned
+    assert parity.telegram_lines(parity.cli_stdout(["-L", path])) == []
     # the same file twice: tuned for the first stream only
     _, recs = parity.cli(["-p", "f=868050", "-L", path, "-p", "f=868250", "-L", path], d / "two.out")
     assert [r[0] for r in recs] == ["0"]
