@@ -419,6 +419,62 @@ typedef struct {            /* 32 bytes */
  * pointer: TFREC_AMD_E_INVAL, and nothing is written; a poisoned context: TFREC_AMD_E_STATE. */
 int tfrec_amd_read_levels(tfrec_amd_ctx *ctx, tfrec_amd_level *out, size_t cap, int *n_blocks_out);
 
+/* Squelched recorder (tfrec_amd_enable_capture): the IQ of every trigger window -- exactly the decimated samples the
+ * demodulators were run on, packed, with their positions.  Exact integers only; no new arithmetic.
+ *   Captured samples: for stream s, decimated sample n is counted since the stream's start or last restart, as end_sample is.
+ *     Sample n is captured iff it is `triggered` in the sense of tfrec_amd_level: some n' with n - W < n' <= n, at or after the
+ *     last restart, has pwr[n'] > the thresh in force at n'.  W is the largest window of the stream's own registered demodulators
+ *     (400 / 356 / 640 / 694 / 512).  These are the samples for which at least one demodulator::demod call of that stream ran with
+ *     its timeout counter live.  There is no pre-roll: the demodulators see none either -- a run begins AT the sample that
+ *     triggered, not before it.
+ *   Runs: a run is a maximal set of consecutive captured samples of one stream within one submit.  A trigger that carries over a
+ *     submit boundary gives two runs: the second starts at the submit's first sample and has TFREC_AMD_RUN_CONTINUES set (the sample
+ *     just before the submit was captured too, and no restart lies between).  A run that reaches the submit's last sample has
+ *     TFREC_AMD_RUN_OPEN set.
+ *   Outputs per submit: a run table ordered by (stream, start_sample), and a sample pool: the runs' int16 (I, Q) pairs, packed back
+ *     to back in table order, the values exactly those tfrec_amd_read_decimated returns.  pool_offset is therefore the exclusive
+ *     prefix sum of n_samples in table order: the layout is deterministic (no atomic decides an order).
+ *   Cutting: the set of (stream, n, I, Q) over all runs does not depend on how a stream is cut into submits; only the split of
+ *     runs at submit boundaries and the two flags do.
+ *   Restarts: any restart (reset, configure, tune, map, wide tune, input tune) drops the carried trigger at the cut, as for the
+ *     levels: no CONTINUES run follows a restart, and start_sample counts from 0 again.
+ *   Validity: every kind of context and every mode, as the level meter: it is defined on the decimated samples and the final
+ *     trigger mask alone.  Its three kernels run behind the front end on a low-priority stream of their own; events and levels do
+ *     not depend on them.  Pinned by tfrec_amd/capture.py. */
+#define TFREC_AMD_RUN_CONTINUES 1u
+#define TFREC_AMD_RUN_OPEN 2u
+typedef struct {            /* 32 bytes */
+	uint32_t stream;
+	uint32_t flags;         /* TFREC_AMD_RUN_CONTINUES 1, TFREC_AMD_RUN_OPEN 2 */
+	int64_t  start_sample;  /* first captured sample, counted like end_sample */
+	uint32_t n_samples;
+	int32_t  thresh;        /* the threshold in force at start_sample */
+	uint64_t pool_offset;   /* index of the run's first (I, Q) pair in the sample pool */
+} tfrec_amd_run;
+/* Turn the recorder on: allowed only before the first submit (after it: TFREC_AMD_E_STATE).  Allocates, per FIFO set
+ * (TFREC_AMD_FIFO_DEPTH of them), max_runs * 32 bytes for the table, max_samples * 4 bytes for the pool and a 16-byte header, and
+ * once per context 16 bytes of carried state, 24 bytes of counts and bases and (max_blocks * 8192 / 356 + 3) * 20 bytes of
+ * staging per stream (a stream cannot have more runs in a submit: all but its first and last are at least 356 samples long);
+ * tfrec_amd_get_memory counts all of it.  tfrec_amd_config has no spare field, so this is a call and not a flag.
+ * Errors: a NULL context, a zero argument or a second call: TFREC_AMD_E_INVAL; TFREC_AMD_E_NOMEM as elsewhere (the context stays
+ * usable, without the recorder); a poisoned context: TFREC_AMD_E_STATE.
+ * A context on which it was never called creates no stream, event or buffer for this and launches what it launched before. */
+int tfrec_amd_enable_capture(tfrec_amd_ctx *ctx, uint32_t max_runs, uint64_t max_samples);
+/* The captures of the OLDEST undrained submit (waits for it; like tfrec_amd_read_levels, call it BEFORE tfrec_amd_drain_events pops
+ * that submit; reading pops nothing).  runs[0 .. *n_runs), samples[2 * pool_offset ..] = I, Q of a run's pairs; cap_runs and
+ * cap_pairs are the room in runs (entries) and samples (pairs).  samples may be NULL with cap_pairs 0 to fetch only the table and
+ * the counts.
+ * Errors: capture not enabled, or a NULL ctx, runs (with cap_runs > 0), n_runs or n_pairs: TFREC_AMD_E_INVAL; nothing undrained or
+ * a poisoned context: TFREC_AMD_E_STATE; the caller's room too small: TFREC_AMD_E_INVAL, nothing written, but *n_runs / *n_pairs
+ * set, so that the caller can size and call again.
+ * Device-side overflow -- the submit has more runs than max_runs or more pairs than max_samples --: TFREC_AMD_E_OVERFLOW, *n_runs /
+ * *n_pairs are the TRUE totals, and the call delivers the longest prefix of the table that fits both limits, whole runs only
+ * (the room needed is that prefix's; where cap_runs exceeds it, the entry behind the prefix is zeroed: n_samples == 0 ends the
+ * table, as no run is empty).  Events, levels and carried state are unaffected: the next submit captures normally, and its
+ * CONTINUES flag is still correct. */
+int tfrec_amd_read_captures(tfrec_amd_ctx *ctx, tfrec_amd_run *runs, size_t cap_runs, uint32_t *n_runs, int16_t *samples,
+			    size_t cap_pairs, uint64_t *n_pairs);
+
 /* The dB value the reference demodulator passes to decoder::flush for this slot, computed with the
  * reference's host expressions (tfa1.cpp:180, tfa2.cpp:434, whb.cpp:696) including (int)(10*log10(0)). */
 int tfrec_amd_rssi_db(int slot, int64_t rssi_raw);

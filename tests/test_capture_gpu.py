@@ -1,0 +1,394 @@
+"""The squelched recorder on the GPU (tfrec_amd_enable_capture, tfrec_amd_read_captures, tfrec_gpu -S), bit for bit.
+
+The run table and the pool are compared with the restatement tfrec_amd/capture.py run on the context's OWN decimated samples
+(tfrec_amd_read_decimated), so the front end ahead of the recorder is whatever the context runs; the events still equal the
+oracle's.  The scene, eight streams of four blocks, is aimed on the CPU (the oracle's front end is the context's, bit for bit) at
+the layouts the kernels can get wrong; every aim is asserted again on what the context returned.
+
+  0  near-silence: no run, an empty entry in the scan over the streams
+  1  a burst whose run starts at bit 63 of a mask word, and crosses the boundary between blocks 1 and 2
+  2  TFA_2 alone (W = 356): a burst whose run ends at bit 0 of a mask word
+  3, 4, 5  a burst that begins 1, 3 and 5 samples ahead of the input's end: open runs of those lengths
+  6  auto threshold, noise loud enough to move it: triggered throughout
+  7  TFA_1 alone (W = 400) on stream 1's input
+"""
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import parity
+from oracle import oracle as O
+from tfrec_amd import api, capture, levels, resample, synth
+
+pytestmark = pytest.mark.gpu
+
+B = api.BLOCK_DEC
+NB = 4
+M = NB * B
+N = 8
+TYPES = [0x2F, 0x2F, 0x02, 0x2F, 0x2F, 0x2F, 0x2F, 0x01]
+THRESH = [500, 500, 500, 500, 500, 500, 0, 500]
+CTX_TYPES = 0x2F
+
+
+def oracle_runs(x, types, thresh):
+    o = O.Oracle(types, thresh, 0, keep_dec=True)
+    o.process(x)
+    return capture.captures(o.dec(), types, thresh)[0]
+
+
+def burst(x, first, last):
+    """raw complex samples [first, last) of the u8 stream x: a carrier at full scale on I."""
+    x[2 * first:2 * last:2] = 228
+    x[2 * first + 1:2 * last:2] = 128
+
+
+def aim(base, place, measure, target, types, thresh, modulo=None):
+    """Move a burst until measure(runs) == target (modulo: in that residue class).  The front end decimates by four and is time
+    invariant, so one decimated sample is four raw ones: a few rounds, the noise around the edge permitting."""
+    pos = 0
+    for _ in range(12):
+        x = base.copy()
+        place(x, pos)
+        got = measure(oracle_runs(x, types, thresh))
+        d = target - got
+        if modulo:
+            d = (d + modulo // 2) % modulo - modulo // 2
+        if d == 0:
+            return x
+        pos += 4 * d
+    raise AssertionError("the burst did not settle")
+
+
+@functools.lru_cache(maxsize=None)
+def scene():
+    rng = np.random.default_rng(17)
+    n = NB * api.BLOCK_BYTES
+    quiet = lambda: rng.integers(126, 131, n, dtype=np.uint8)  # noqa: E731
+    end = lambda r: int(r["start_sample"] + r["n_samples"])  # noqa: E731
+    rows = [quiet()]
+    # 1: 300 decimated samples of carrier that end 100 ahead of block 2 -- the run crosses into it -- starting at bit 63 of a word
+    rows.append(aim(quiet(), lambda x, p: burst(x, 4 * (2 * B - 400) + p, 4 * (2 * B - 400) + p + 1200),
+                    lambda r: int(r[0]["start_sample"]) % 64, 63, TYPES[1], THRESH[1], modulo=64))
+    # 2: the burst's end moves until the run's last sample is bit 0 of a word
+    rows.append(aim(quiet(), lambda x, p: burst(x, 4 * 5000, 4 * 5300 + p), lambda r: (end(r[0]) - 1) % 64, 0, TYPES[2], THRESH[2],
+                    modulo=64))
+    for k, length in ((3, 1), (4, 3), (5, 5)):
+        rows.append(aim(quiet(), lambda x, p: burst(x, 4 * (M - 40) + p, n // 2), lambda r: int(r[-1]["start_sample"]), M - length,
+                        TYPES[k], THRESH[k]))
+    rows.append(rng.integers(0, 256, n, dtype=np.uint8))
+    rows.append(rows[1].copy())
+    iq = np.stack(rows)
+    iq.setflags(write=False)
+    return iq
+
+
+def want_tables(decs, states):
+    """The restatement on one submit's decimated samples -> (table, pool); states: each stream's carried state, updated."""
+    per = []
+    for s, d in enumerate(decs):
+        runs, pool, states[s] = capture.captures(d, TYPES[s], THRESH[s], states[s])
+        per.append((runs, pool))
+    return capture.table(per)
+
+
+def receiver(max_blocks=NB, cap=(4096, N * M), **kw):
+    r = api.Receiver(N, CTX_TYPES, 500, 0, max_blocks=max_blocks, all_flushes=True, **kw)
+    r.configure_streams([2, 6, 7], types_mask=[TYPES[2], TYPES[6], TYPES[7]], thresh=[THRESH[2], THRESH[6], THRESH[7]])
+    if cap:
+        r.enable_capture(*cap)
+    return r
+
+
+def assert_tables(got, want, label=""):
+    (runs, pool), (wruns, wpool) = got, want
+    assert runs.dtype == capture.RUN_DTYPE and pool.dtype == np.int16
+    for f in capture.RUN_DTYPE.names:
+        assert np.array_equal(runs[f], wruns[f]), "%s %s: got %s want %s" % (label, f, runs[f].tolist(), wruns[f].tolist())
+    assert pool.shape == wpool.shape and np.array_equal(pool, wpool), "%s pool" % label
+
+
+@functools.lru_cache(maxsize=None)
+def one_submit(serial=False):
+    """-> ((table, pool), the restatement's, events, every stream's decimated samples, thresholds read back, the final states)."""
+    with receiver(serial_chains=serial) as r:
+        r.submit(scene())
+        decs = [r.decimated(s, M) for s in range(N)]
+        got = r.read_captures()
+        assert r.capture_totals == (len(got[0]), len(got[1])) and not r.capture_overflow
+        again = r.read_captures()  # reading pops nothing
+        assert again[0].tobytes() == got[0].tobytes() and again[1].tobytes() == got[1].tobytes()
+        ev = r.drain()
+        th = [r.thresh(s) for s in range(N)]
+    states = [None] * N
+    want = want_tables(decs, states)
+    return got, want, ev, decs, th, states
+
+
+def test_table_and_pool_equal_the_restatement():
+    got, want, ev, decs, th, states = one_submit()
+    assert_tables(got, want)
+    assert th == [st["thresh"] for st in states] and th[6] == 502 and th[:6] == [500] * 6  # the thresholds the front end ended with
+    iq = scene()
+    for s in range(N):
+        parity.assert_stream(ev, s, parity.fresh_oracle(iq[s], TYPES[s], THRESH[s]), "stream %d" % s)
+
+
+def test_the_scene_holds_the_layouts_it_is_aimed_at():
+    (runs, pool), _, _, decs, _, _ = one_submit()
+    of = lambda s: runs[runs["stream"] == s]  # noqa: E731
+    end = lambda r: int(r["start_sample"] + r["n_samples"])  # noqa: E731
+    assert len(of(0)) == 0 and len(of(1)) == 1 and runs["stream"].tolist() == sorted(runs["stream"].tolist())
+    assert np.array_equal(runs["pool_offset"], np.concatenate([[0], np.cumsum(runs["n_samples"])[:-1]]).astype(np.uint64))
+    r1, r2, r7 = of(1)[0], of(2)[0], of(7)[0]
+    assert r1["start_sample"] % 64 == 63 and r1["start_sample"] < 2 * B < end(r1) and r1["flags"] == 0
+    assert (end(r2) - 1) % 64 == 0 and len(of(2)) == 1
+    assert r7["start_sample"] == r1["start_sample"] and r1["n_samples"] - r7["n_samples"] == 694 - 400  # each stream's own W
+    for s, length in ((3, 1), (4, 3), (5, 5)):
+        r = of(s)[-1]
+        assert r["n_samples"] == length and end(r) == M and r["flags"] == capture.RUN_OPEN and len(of(s)) == 1
+        d = decs[s].reshape(-1, 2)
+        assert np.array_equal(pool[int(r["pool_offset"]):int(r["pool_offset"]) + length], d[M - length:])
+    r6 = of(6)
+    assert end(r6[-1]) == M and r6[-1]["flags"] == capture.RUN_OPEN and r6[-1]["n_samples"] >= M - 16 and r6[-1]["thresh"] == 500
+    assert len({int(o) % 4 for o in runs["pool_offset"]}) > 1
+
+
+@functools.lru_cache(maxsize=None)
+def queued(sizes):
+    """The scene cut into `sizes`, every submit queued before the first read -> [(table, pool)] per submit, events per submit."""
+    parts = parity.cut(scene(), sizes)
+    with receiver(max_blocks=max(sizes)) as r:
+        for p in parts:
+            r.submit(p)
+        last = [r.decimated(s, sizes[-1] * B) for s in range(N)]
+        got, evs = [], []
+        for _ in parts:
+            got.append(r.read_captures())
+            evs.append(r.drain())
+        with pytest.raises(api.TfrecAmdError) as e:
+            r.read_captures()
+        assert e.value.code == api.E_STATE
+    return got, evs, last
+
+
+def test_one_plus_three_queued_before_the_first_read():
+    got, evs, last = queued((1, 3))
+    whole, _, ev, decs, _, _ = one_submit()
+    for s in range(N):  # the front end does not depend on the cut: the restatement may run on the uncut context's samples
+        assert np.array_equal(last[s], decs[s][2 * B:])
+    states, pos = [None] * N, 0
+    for k, nb in enumerate((1, 3)):
+        want = want_tables([d[2 * pos * B:2 * (pos + nb) * B] for d in decs], states)
+        assert_tables(got[k], want, "submit %d" % k)
+        pos += nb
+
+    def samples(tabs):
+        out = set()
+        for runs, pool in tabs:
+            for r in runs:
+                o = int(r["pool_offset"])
+                out |= {(int(r["stream"]), int(r["start_sample"]) + i, int(pool[o + i][0]), int(pool[o + i][1]))
+                        for i in range(int(r["n_samples"]))}
+        return out
+
+    assert samples(got) == samples([whole])
+    first6 = got[0][0][got[0][0]["stream"] == 6][-1]
+    second6 = got[1][0][got[1][0]["stream"] == 6]
+    assert first6["flags"] & capture.RUN_OPEN
+    # stream 6 in the second submit: one run of the whole submit, continued and open
+    assert len(second6) == 1 and second6[0]["flags"] == capture.RUN_CONTINUES | capture.RUN_OPEN
+    assert second6[0]["start_sample"] == B and second6[0]["n_samples"] == 3 * B
+    cont = np.concatenate([t[0] for t in got])
+    assert (cont[cont["flags"] & capture.RUN_CONTINUES != 0]["stream"] == 6).all()
+    assert parity.sort_events(np.concatenate(evs)).tobytes() == parity.sort_events(ev).tobytes()
+
+
+def test_a_reset_between_submits_drops_the_carried_trigger():
+    parts = parity.cut(scene(), (2, 2))
+    states = [None] * N
+    with receiver(max_blocks=2) as r:
+        r.submit(parts[0])
+        want0 = want_tables([r.decimated(s, 2 * B) for s in range(N)], states)
+        got0 = r.read_captures()
+        r.drain()
+        r.reset_streams([1, 6])
+        states[1] = states[6] = None  # fresh streams on the input that follows
+        r.submit(parts[1])
+        want1 = want_tables([r.decimated(s, 2 * B) for s in range(N)], states)
+        got1 = r.read_captures()
+        r.drain()
+    assert_tables(got0, want0, "before the reset")
+    assert_tables(got1, want1, "after the reset")
+    runs0, runs1 = got0[0], got1[0]
+    for s in (1, 6, 7):  # the runs of 1, 6 and 7 were open at the cut ...
+        assert runs0[runs0["stream"] == s][-1]["flags"] & capture.RUN_OPEN
+    # ... 7 carries on; 1 lost its trigger (what is left of the burst is quiet) and 6 starts again, from sample 0, not continued
+    r7 = runs1[runs1["stream"] == 7][0]
+    assert r7["flags"] & capture.RUN_CONTINUES and r7["start_sample"] == 2 * B
+    assert len(runs1[runs1["stream"] == 1]) == 0
+    r6 = runs1[runs1["stream"] == 6]
+    assert not (r6["flags"] & capture.RUN_CONTINUES).any() and r6[0]["start_sample"] < 16 and r6[0]["thresh"] == 500
+    assert int(r6[-1]["start_sample"] + r6[-1]["n_samples"]) == 2 * B
+
+
+@pytest.mark.parametrize("short", ["runs", "samples"])
+def test_overflow_delivers_a_prefix_and_the_next_submit_is_exact(short):
+    (runs, pool), _, _, decs, _, _ = one_submit()
+    cap = (len(runs) - 1, len(pool)) if short == "runs" else (len(runs), len(pool) - 1)
+    states = [None] * N
+    with receiver(cap=cap) as r:
+        r.submit(scene())
+        want = want_tables([r.decimated(s, M) for s in range(N)], states)
+        with pytest.raises(api.TfrecAmdError) as e:
+            r.read_captures()
+        assert e.value.code == api.E_OVERFLOW
+        got = r.read_captures(allow_overflow=True)
+        assert r.capture_overflow and r.capture_totals == (len(want[0]), len(want[1])) == (len(runs), len(pool))
+        wr, wp, ov = capture.prefix(want[0], want[1], *cap)
+        assert ov and len(wr) == len(runs) - 1  # whole runs only: the last run is missing either way
+        assert_tables(got, (wr, wp), "the prefix")
+        ev = r.drain()
+        # the next submit -- one block, so that it fits -- captures normally, its CONTINUES flags included
+        r.submit(scene()[:, :api.BLOCK_BYTES])
+        want2 = want_tables([r.decimated(s, B) for s in range(N)], states)
+        got2 = r.read_captures()
+        assert not r.capture_overflow
+        r.drain()
+    assert_tables(got2, want2, "the submit behind the overflow")
+    assert (got2[0]["flags"] & capture.RUN_CONTINUES).any()
+    assert parity.sort_events(ev).tobytes() == parity.sort_events(one_submit()[2]).tobytes()  # the events do not notice
+
+
+def test_with_levels_captured_is_triggered_and_telegrams_lie_inside_runs():
+    n, nb = 4, 4
+    iq = synth.gen_batch(5, 0, n, nb)
+    with api.Receiver(n, CTX_TYPES, 500, 0, max_blocks=nb, all_flushes=True, levels=True) as r:
+        r.enable_capture(4096, n * nb * B)
+        r.submit(iq)
+        runs, pool = r.read_captures()
+        lv = r.read_levels()
+        ev = r.drain()
+    per_block = np.zeros((n, nb), dtype=np.int64)
+    for x in runs:
+        k = np.arange(int(x["start_sample"]), int(x["start_sample"] + x["n_samples"])) // B
+        per_block[int(x["stream"])] += np.bincount(k, minlength=nb)
+    assert per_block.tolist() == lv["triggered"].tolist() and per_block.sum() == len(pool) > 0
+    tele = ev[ev["status"] == 1]
+    assert len(tele) > 0
+    for e in tele:
+        mine = runs[runs["stream"] == e["stream"]]
+        at = int(e["end_sample"]) - 1
+        assert ((mine["start_sample"] <= at) & (at < mine["start_sample"] + mine["n_samples"])).any(), e
+    for s in range(n):
+        parity.assert_stream(ev, s, parity.fresh_oracle(iq[s], CTX_TYPES, 500), "stream %d" % s)
+
+
+def check_plain(r, parts, types, thresh):
+    """Submit by submit on a uniform context: the table against the restatement on its own samples -> pairs captured."""
+    states, total = [None] * r.n_streams, 0
+    for p in parts:
+        nb = r.submit(p)
+        per = []
+        for s in range(r.n_streams):
+            runs, pool, states[s] = capture.captures(r.decimated(s, nb * B), types, thresh, states[s])
+            per.append((runs, pool))
+        got = r.read_captures()
+        assert_tables(got, capture.table(per))
+        total += len(got[1])
+        r.drain()
+    return total
+
+
+def test_a_rate_context_a_10x_context_and_a_serial_one():
+    p, q, nb = 4, 3, 3
+    row = synth.gen_scene(41, nb, [dict(proto=1, start=5000 * p, payload_seed=5, f0_hz=0, amp=60)], rate_mult=p).reshape(-1, 2)[::q]
+    row = np.ascontiguousarray(row).reshape(1, -1)
+    assert row.shape[1] == 2 * resample.input_samples(nb, p, q)
+    with api.Receiver(1, CTX_TYPES, 500, 0, max_blocks=nb, input_rate=(p, q)) as r:
+        r.enable_capture(256, nb * B)
+        assert check_plain(r, [row], CTX_TYPES, 500) > 0
+    iq10 = np.stack([synth.gen_stream(9, s, 1, rate_mult=10) for s in range(2)])
+    with api.Receiver(2, CTX_TYPES, 100, 0, max_blocks=1, input_10x=True) as r:  # (-t 100: the block's noise floor triggers)
+        r.enable_capture(256, 2 * B)
+        assert check_plain(r, [iq10], CTX_TYPES, 100) > 0
+    ser, want, ev, _, th, _ = one_submit(True)
+    assert_tables(ser, want, "serial")
+    assert ser[0].tobytes() == one_submit()[0][0].tobytes() and ser[1].tobytes() == one_submit()[0][1].tobytes()
+    assert th == one_submit()[4]
+    assert parity.sort_events(ev).tobytes() == parity.sort_events(one_submit()[2]).tobytes()
+
+
+def test_without_the_call_nothing_is_held_and_the_read_is_refused():
+    n, mb = 3, 5
+    with api.Receiver(n, CTX_TYPES, 500, 0, max_blocks=mb) as r:
+        plain = r.memory()
+        for _ in range(2):
+            with pytest.raises(api.TfrecAmdError) as e:
+                r.read_captures()
+            assert e.value.code == api.E_INVAL
+            r.submit(scene()[:n])
+        assert r.memory()["pinned_host_bytes"] == plain["pinned_host_bytes"]
+        with pytest.raises(api.TfrecAmdError) as e:  # ... and after the first submit it cannot be turned on any more
+            r.enable_capture(16, 1024)
+        assert e.value.code == api.E_STATE
+        r.drain()
+        r.drain()
+    # the memory of a context that never enabled it is what it was: the level meter's share is still the whole difference
+    with api.Receiver(n, CTX_TYPES, 500, 0, max_blocks=mb, levels=True) as r:
+        assert r.memory()["device_bytes"] - plain["device_bytes"] == api.FIFO_DEPTH * n * mb * 32 + n * 16
+    with api.Receiver(n, CTX_TYPES, 500, 0, max_blocks=mb) as r:
+        assert r.memory() == plain
+        for bad in ((0, 1024), (16, 0)):
+            with pytest.raises(api.TfrecAmdError) as e:
+                r.enable_capture(*bad)
+            assert e.value.code == api.E_INVAL
+        r.enable_capture(16, 1024)
+        with pytest.raises(api.TfrecAmdError) as e:
+            r.enable_capture(16, 1024)
+        assert e.value.code == api.E_INVAL
+        m = r.memory()
+        # per set the table, the pool and the totals; once the state, counts, bases and staged runs of every stream
+        assert m["device_bytes"] - plain["device_bytes"] == api.FIFO_DEPTH * (16 * 32 + 1024 * 4 + 16) + n * (
+            16 + 8 + 16 + (mb * B // 356 + 3) * 20)
+        assert m["pinned_host_bytes"] == plain["pinned_host_bytes"]
+        with pytest.raises(api.TfrecAmdError) as e:
+            r.read_captures()
+        assert e.value.code == api.E_STATE  # nothing undrained
+        # the caller's room too small: E_INVAL, nothing written, the counts set
+        r.submit(scene()[:n, :api.BLOCK_BYTES])
+        nr, npairs = api.C.c_uint32(0), api.C.c_uint64(0)
+        buf = np.full(32, 0x55, dtype=np.uint8)
+        rc = r.L.tfrec_amd_read_captures(r.h, buf.ctypes.data, 0, api.C.byref(nr), None, 0, api.C.byref(npairs))
+        runs, pool = r.read_captures()
+        assert rc == api.E_INVAL and (buf == 0x55).all() and (nr.value, npairs.value) == (len(runs), len(pool)) and len(runs) == 1
+        r.drain()
+
+
+def test_cli_capture_of_the_golden_tfa_2_scene(tmp_path):
+    cli = parity.build_cli()
+    z = np.load(os.path.join(parity.ROOT, "tests", "golden", "iq_tfa_2.npz"))
+    nb = 3
+    x = np.ascontiguousarray(z["iq"][:nb * api.BLOCK_BYTES])
+    f = tmp_path / "tfa2.iq"
+    x.tofile(f)
+    pre = str(tmp_path / "cap")
+    args = ["-T", "2f", "-t", "500", "-b", "2", "-L", str(f)]
+    plain = subprocess.run([cli] + args, capture_output=True, text=True, timeout=300)
+    out = subprocess.run([cli, "-S", pre] + args, capture_output=True, text=True, timeout=300)
+    assert plain.returncode == 0 and out.returncode == 0, out.stderr
+    assert parity.telegram_lines(out.stdout) == parity.telegram_lines(plain.stdout) and len(parity.telegram_lines(out.stdout)) >= 1
+    # the restatement: the oracle's front end, then capture.py submit by submit (-b 2: two blocks, then one)
+    o = O.Oracle(0x2F, 500, 0, keep_dec=True)
+    o.process(x)
+    dec = o.dec().reshape(-1, 2)
+    lines, pools, st = [], [], None
+    for a, b in ((0, 2), (2, 3)):
+        runs, pool, st = capture.captures(dec[a * B:b * B], 0x2F, 500, st)
+        lines += [capture.idx_line(0, r) for r in runs]
+        pools.append(pool)
+    assert open(pre + ".idx").read().splitlines() == lines and len(lines) >= 1
+    assert np.array_equal(np.fromfile(pre + ".0.cs16", dtype="<i2").reshape(-1, 2), np.concatenate(pools))

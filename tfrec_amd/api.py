@@ -13,6 +13,7 @@ from fractions import Fraction
 import numpy as np
 
 from . import _build
+from .capture import RUN_DTYPE  # tfrec_amd_run
 from .levels import LEVEL_DTYPE  # tfrec_amd_level
 
 BLOCK_BYTES = 65536
@@ -103,7 +104,7 @@ EXPORTS = (
     "tfrec_amd_map_streams", "tfrec_amd_get_stream_input", "tfrec_amd_tune_streams_wide", "tfrec_amd_get_stream_tune_wide",
     "tfrec_amd_create_rate", "tfrec_amd_get_input_rate", "tfrec_amd_input_bytes", "tfrec_amd_resample_taps",
     "tfrec_amd_tune_streams_input", "tfrec_amd_get_stream_tune_input", "tfrec_amd_create_format", "tfrec_amd_get_input_format",
-    "tfrec_amd_read_levels",
+    "tfrec_amd_read_levels", "tfrec_amd_enable_capture", "tfrec_amd_read_captures",
 )
 
 _libs = {}
@@ -179,6 +180,9 @@ def load_library(build: bool = True, experiments: bool = False):
     L.tfrec_amd_create_format.argtypes = [C.POINTER(Config), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
     L.tfrec_amd_get_input_format.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.tfrec_amd_read_levels.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
+    L.tfrec_amd_enable_capture.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
+    L.tfrec_amd_read_captures.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
+                                          C.POINTER(C.c_uint64)]
     L.tfrec_amd_fifo_depth.restype = C.c_int
     if L.tfrec_amd_fifo_depth() != FIFO_DEPTH:
         raise RuntimeError("libtfrec_amd.so was built with FIFO depth %d, this binding expects %d" % (
@@ -455,6 +459,41 @@ class Receiver:
         nb = C.c_int(0)
         _check(self.L, self.L.tfrec_amd_read_levels(self.h, out.ctypes.data, len(out), C.byref(nb)))
         return out[: self.n_streams * nb.value].reshape(self.n_streams, nb.value).copy()
+
+    def enable_capture(self, max_runs: int, max_samples: int):
+        """Turn the squelched recorder on (tfrec_amd_enable_capture; before the first submit): per submit at most max_runs runs and
+        max_samples (I, Q) pairs are kept on the device.  read_captures returns them."""
+        if not (0 <= int(max_runs) < 2 ** 32 and 0 <= int(max_samples) < 2 ** 64):  # (refused before ctypes could wrap a value)
+            raise TfrecAmdError(E_INVAL, "max_runs or max_samples outside their types")
+        _check(self.L, self.L.tfrec_amd_enable_capture(self.h, int(max_runs), int(max_samples)))
+        self._capture = (int(max_runs), int(max_samples))
+
+    def read_captures(self, allow_overflow: bool = False):
+        """The captures of the OLDEST undrained submit (tfrec_amd_read_captures; call it before the drain that pops that submit)
+        -> (runs, samples): a RUN_DTYPE array ordered by (stream, start_sample) and the pool, int16 [n_pairs, 2]; run r's pairs are
+        samples[r.pool_offset : r.pool_offset + r.n_samples].  A device-side overflow (E_OVERFLOW) raises unless allow_overflow,
+        as for drain(); then the longest prefix of whole runs that fitted is returned.  capture_totals holds the submit's true
+        (n_runs, n_pairs) and capture_overflow whether it overflowed.  TfrecAmdError(E_INVAL) on a context without enable_capture,
+        (E_STATE) when nothing is waiting to be drained."""
+        ok = (E_OK, E_OVERFLOW) if allow_overflow else (E_OK,)
+        nr, npairs = C.c_uint32(0), C.c_uint64(0)
+        max_runs, max_samples = getattr(self, "_capture", (0, 0))
+        rc = self.L.tfrec_amd_read_captures(self.h, None, 0, C.byref(nr), None, 0, C.byref(npairs))  # the counts (no room: E_INVAL)
+        if max_runs == 0 or rc == E_STATE or (rc == E_INVAL and nr.value == 0):
+            _check(self.L, rc)
+        runs = np.zeros(min(nr.value, max_runs) + 1, dtype=RUN_DTYPE)  # (+ 1: the entry that ends an overflowed table)
+        samples = np.empty((min(npairs.value, max_samples) + 1, 2), dtype=np.int16)
+        rc = self.L.tfrec_amd_read_captures(self.h, runs.ctypes.data, len(runs), C.byref(nr), samples.ctypes.data, len(samples),
+                                            C.byref(npairs))
+        self.capture_totals = (int(nr.value), int(npairs.value))
+        self.capture_overflow = rc == E_OVERFLOW
+        _check(self.L, rc, ok=ok)
+        k = nr.value
+        if rc == E_OVERFLOW:
+            k = int(np.flatnonzero(runs["n_samples"] == 0)[0])
+        runs = runs[:k].copy()
+        n = int(runs["pool_offset"][-1] + runs["n_samples"][-1]) if k else 0
+        return runs, samples[:n].copy()
 
     def stage0(self, stream: int, n_pairs: int) -> np.ndarray:
         """input_10x or input_rate: the 1.536 MS/s int16 IQ the 10:1 or the resampling stage produced for the last submit."""

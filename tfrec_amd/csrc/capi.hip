@@ -44,6 +44,10 @@ hipError_t launch_chains(hipStream_t st, const uint32_t *dec, size_t dec_stride,
 			 tfrec_amd_event *events, EventBuf *eb, uint32_t flags);
 hipError_t launch_levels(hipStream_t st, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask, size_t mask_stride,
 			 int n_streams, int n_blocks, LevelState *lev, const StreamCfg *scfg, tfrec_amd_level *out);
+hipError_t launch_capture(hipStream_t st, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask, size_t mask_stride,
+			  int n_streams, int n_blocks, long long sample_base, CaptureState *cst, const StreamCfg *scfg, CaptureStage *stage,
+			  int stage_cap, uint2 *cnt, uint4 *base, CaptureHeader *hdr, tfrec_amd_run *runs, uint32_t max_runs, uint32_t *pool,
+			  unsigned long long max_samples);
 }  // namespace tfrec
 
 using namespace tfrec;
@@ -140,6 +144,23 @@ struct tfrec_amd_ctx {
 	hipStream_t lv = nullptr;
 	hipEvent_t ev_lev[kSets] = {};
 	int set_blocks[kSets] = {};
+	// tfrec_amd_enable_capture: the recorder's carried state, the working set its three kernels share (staged runs,
+	// counts and bases per stream: one, because the submits' recorder kernels follow each other on one stream), per set the run
+	// table, the sample pool and the header with the true totals, its low-priority stream and the set's "captures written" event
+	bool capture = false;
+	uint32_t cap_max_runs = 0;
+	uint64_t cap_max_samples = 0;
+	CaptureState *d_capst = nullptr;
+	CaptureStage *d_capstage = nullptr;
+	int cap_stage_cap = 0;
+	uint2 *d_capcnt = nullptr;
+	uint4 *d_capbase = nullptr;
+	CaptureHeader *d_caphdr[kSets] = {};
+	tfrec_amd_run *d_runs[kSets] = {};
+	uint32_t *d_pool[kSets] = {};
+	hipStream_t cap = nullptr;
+	hipEvent_t ev_cap[kSets] = {};
+	std::vector<tfrec_amd_run> cap_tmp;
 	int wmax = 0;
 	// tfrec_amd_configure_streams: every stream's settings as the next submit uses them (scfg, the host's copy), their device
 	// copy as the last submit used them (d_scfg: written only by stream_reset_kernel, in the entries of its list), and the
@@ -280,6 +301,7 @@ struct StreamReset {
 	int32_t pre_bytes, pre_fill;
 	FskState *fsk;      // auto threshold
 	LevelState *lev;    // TFREC_AMD_F_LEVELS: the level meter's carried state, or nullptr
+	CaptureState *cap;  // tfrec_amd_enable_capture: the recorder's carried state, or nullptr
 	const StreamCfg *cfgs;  // [n_list] the listed streams' settings from this submit on ...
 	StreamCfg *scfg;        // ... written over their entries here
 	int32_t n_active;
@@ -318,6 +340,8 @@ __global__ __launch_bounds__(64) void stream_reset_kernel(StreamReset R)
 		R.fsk[s] = FskState{ sc.thresh, 0, 0, -(1 << 28) };  // auto: 500, fm_demod.cpp:23-27, as tfrec_amd_create
 		if (R.lev)
 			R.lev[s] = LevelState{ sc.thresh, 0, 0, -(1 << 28) };
+		if (R.cap)
+			R.cap[s] = CaptureState{ sc.thresh, 0, 0, -(1 << 28) };
 		if (R.tcarry)
 			for (int a = 0; a < R.n_active; a++)
 				R.tcarry[(size_t)a * R.n_streams + s] = 0;
@@ -1260,6 +1284,8 @@ static int launch_resets(tfrec_amd_ctx *c, int set)
 			HIPCHK(hipStreamWaitEvent(fs, e, 0));
 	if (c->submitted && c->levels)  // (the level meter of the last submit reads d_scfg and owns d_lev)
 		HIPCHK(hipStreamWaitEvent(fs, c->ev_lev[c->last_set], 0));
+	if (c->submitted && c->capture)  // (so does the recorder: d_scfg and d_capst)
+		HIPCHK(hipStreamWaitEvent(fs, c->ev_cap[c->last_set], 0));
 	const int nl = (int)c->reset_pending.size();
 	memcpy(c->h_reset[set], c->reset_pending.data(), (size_t)nl * sizeof(int32_t));  // (the set's last copy was drained)
 	for (int i = 0; i < nl; i++)  // a reset stream restarts with its own current settings
@@ -1279,6 +1305,7 @@ static int launch_resets(tfrec_amd_ctx *c, int set)
 	R.pre_fill = c->pre_fill;
 	R.fsk = c->d_fsk;
 	R.lev = c->d_lev;
+	R.cap = c->d_capst;
 	R.cfgs = c->d_rcfg[set];
 	R.scfg = c->d_scfg;
 	R.n_active = c->launch.n_active;
@@ -1537,6 +1564,13 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		HIPCHK(hipEventRecord(c->ev_lev[set], c->lv));
 		c->set_blocks[set] = n_blocks;
 	}
+	if (c->capture) {  // the recorder: placed like the level meter, on a low-priority stream of its own
+		HIPCHK(hipStreamWaitEvent(c->cap, P.ev_front, 0));
+		HIPCHK(launch_capture(c->cap, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams, n_blocks,
+				      c->sample_base, c->d_capst, c->d_scfg, c->d_capstage, c->cap_stage_cap, c->d_capcnt, c->d_capbase,
+				      c->d_caphdr[set], c->d_runs[set], c->cap_max_runs, c->d_pool[set], c->cap_max_samples));
+		HIPCHK(hipEventRecord(c->ev_cap[set], c->cap));
+	}
 	if (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) {
 		HIPCHK(hipStreamWaitEvent(P.cs, P.ev_front, 0));
 		HIPCHK(launch_chains(P.cs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams, n_blocks,
@@ -1557,6 +1591,8 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		HIPCHK(hipStreamWaitEvent(c->cpy, e, 0));
 	if (c->levels)  // copied[set] then also says "the records are written" (tfrec_amd_read_levels, and the set's reuse)
 		HIPCHK(hipStreamWaitEvent(c->cpy, c->ev_lev[set], 0));
+	if (c->capture)  // ... and "the captures are written" (tfrec_amd_read_captures)
+		HIPCHK(hipStreamWaitEvent(c->cpy, c->ev_cap[set], 0));
 	c->copied_n[set] = std::min<uint32_t>(c->copy_guess, (uint32_t)c->cfg.max_events);
 	{  // header, overflow flag and the first copied_n events in one go
 		static_assert(kEvHeader % 16 == 0 && sizeof(tfrec_amd_event) % 16 == 0, "drain_copy_kernel moves 16 bytes per lane");
@@ -1709,6 +1745,108 @@ int tfrec_amd_read_levels(tfrec_amd_ctx *c, tfrec_amd_level *out, size_t cap, in
 	HIPCHK(hipMemcpy(out, c->d_levels[set], n * sizeof(tfrec_amd_level), hipMemcpyDeviceToHost));
 	*n_blocks_out = c->set_blocks[set];
 	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_enable_capture(tfrec_amd_ctx *c, uint32_t max_runs, uint64_t max_samples)
+{
+	if (!c)
+		return TFREC_AMD_E_INVAL;
+	if (max_runs == 0 || max_samples == 0 || c->capture) {
+		snprintf(g_err, sizeof(g_err), c->capture ? "the recorder is enabled already" : "max_runs and max_samples must not be 0");
+		return TFREC_AMD_E_INVAL;
+	}
+	TRY(check_live(c));
+	if (c->submitted) {
+		snprintf(g_err, sizeof(g_err), "the recorder is enabled before the first submit");
+		return TFREC_AMD_E_STATE;
+	}
+	if (max_samples > (uint64_t)SIZE_MAX / sizeof(uint32_t)) {
+		snprintf(g_err, sizeof(g_err), "max_samples too large");
+		return TFREC_AMD_E_NOMEM;
+	}
+	HIPCHK(hipSetDevice(c->cfg.device));
+	const size_t n = (size_t)c->cfg.n_streams;
+	// a stream's runs in one submit: all but the first and the last are at least 356 samples long, with a gap between them
+	c->cap_stage_cap = (int)((size_t)c->cfg.max_blocks * kBlockDec / 356 + 3);
+	TRY(own_device(c, c->d_capst, n * sizeof(CaptureState)));
+	TRY(own_device(c, c->d_capstage, n * (size_t)c->cap_stage_cap * sizeof(CaptureStage)));
+	TRY(own_device(c, c->d_capcnt, n * sizeof(uint2)));
+	TRY(own_device(c, c->d_capbase, n * sizeof(uint4)));
+	std::vector<CaptureState> st(n);
+	for (size_t s = 0; s < n; s++)  // every stream starts like its FskState (a configure ahead of the first submit is a restart)
+		st[s] = CaptureState{ c->scfg[s].thresh, 0, 0, -(1 << 28) };
+	HIPCHK(hipMemcpy(c->d_capst, st.data(), n * sizeof(CaptureState), hipMemcpyHostToDevice));
+	for (int k = 0; k < kSets; k++) {
+		TRY(own_device(c, c->d_runs[k], (size_t)max_runs * sizeof(tfrec_amd_run)));
+		TRY(own_device(c, c->d_pool[k], (size_t)max_samples * sizeof(uint32_t)));
+		TRY(own_device(c, c->d_caphdr[k], sizeof(CaptureHeader)));
+		TRY(own_event(c, c->ev_cap[k], hipEventDisableTiming));
+	}
+	int prio_lo = 0, prio_hi = 0;
+	(void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+	TRY(own_stream(c, c->cap, prio_lo));
+	c->cap_max_runs = max_runs;
+	c->cap_max_samples = max_samples;
+	c->capture = true;  // (only now: a context whose allocation failed half way runs on without the recorder)
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_read_captures(tfrec_amd_ctx *c, tfrec_amd_run *runs, size_t cap_runs, uint32_t *n_runs, int16_t *samples, size_t cap_pairs,
+			    uint64_t *n_pairs)
+{
+	if (!c || !n_runs || !n_pairs || (cap_runs > 0 && !runs) || (cap_pairs > 0 && !samples))
+		return TFREC_AMD_E_INVAL;
+	if (!c->capture) {
+		snprintf(g_err, sizeof(g_err), "tfrec_amd_enable_capture was not called on this context");
+		return TFREC_AMD_E_INVAL;
+	}
+	TRY(check_live(c));
+	if (c->inflight == 0) {
+		snprintf(g_err, sizeof(g_err), "no undrained submit: the captures are read before tfrec_amd_drain_events");
+		return TFREC_AMD_E_STATE;
+	}
+	const int set = c->head;
+	HIPCHK(hipSetDevice(c->cfg.device));
+	HIPCHK(hipEventSynchronize(c->copied[set]));  // (behind ev_cap[set])
+	CaptureHeader hdr;
+	HIPCHK(hipMemcpy(&hdr, c->d_caphdr[set], sizeof(hdr), hipMemcpyDeviceToHost));
+	const bool overflow = hdr.n_runs > c->cap_max_runs || hdr.n_pairs > c->cap_max_samples;
+	// the table as far as the device wrote it, then the prefix of whole runs whose pairs it wrote too
+	size_t have = (size_t)std::min<unsigned long long>(hdr.n_runs, c->cap_max_runs);
+	std::vector<tfrec_amd_run> &tmp = c->cap_tmp;
+	tmp.resize(have);
+	if (have)
+		HIPCHK(hipMemcpy(tmp.data(), c->d_runs[set], have * sizeof(tfrec_amd_run), hipMemcpyDeviceToHost));
+	uint64_t pairs = hdr.n_pairs;
+	if (overflow) {
+		size_t k = 0;
+		pairs = 0;
+		while (k < have && tmp[k].pool_offset + tmp[k].n_samples <= c->cap_max_samples) {
+			pairs = tmp[k].pool_offset + tmp[k].n_samples;
+			k++;
+		}
+		have = k;
+	}
+	*n_runs = (uint32_t)std::min<unsigned long long>(hdr.n_runs, 0xffffffffull);
+	*n_pairs = hdr.n_pairs;
+	if (cap_runs < have || (samples && cap_pairs < pairs)) {
+		snprintf(g_err, sizeof(g_err), "room for %zu runs and %zu pairs, the submit delivers %zu and %llu", cap_runs, cap_pairs, have,
+			 (unsigned long long)pairs);
+		return TFREC_AMD_E_INVAL;
+	}
+	if (!c->set_origin[set].empty()) {  // start_sample counts from the stream's last restart, as end_sample does
+		const std::vector<long long> &org = c->set_origin[set];
+		for (size_t i = 0; i < have; i++)
+			if (tmp[i].stream < org.size())
+				tmp[i].start_sample -= org[tmp[i].stream];
+	}
+	if (samples && pairs)
+		HIPCHK(hipMemcpy(samples, c->d_pool[set], (size_t)pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (have)
+		memcpy(runs, tmp.data(), have * sizeof(tfrec_amd_run));
+	if (overflow && cap_runs > have)
+		memset(&runs[have], 0, sizeof(tfrec_amd_run));
+	return overflow ? TFREC_AMD_E_OVERFLOW : TFREC_AMD_OK;
 }
 
 int tfrec_amd_drain_events(tfrec_amd_ctx *c, tfrec_amd_event *out, int cap, int *n_out)

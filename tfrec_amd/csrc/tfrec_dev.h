@@ -165,6 +165,28 @@ struct LevelState {
 	int32_t last_trig;      // last sample with pwr > thresh, relative to the start of the next submit (very negative: none)
 };
 
+// The squelched recorder's carried state (tfrec_amd_enable_capture, capture.h: capture_scan_kernel): LevelState's fields once
+// more, so that a context may run the meter, the recorder, both or neither
+struct CaptureState {
+	int32_t thresh;         // trigger threshold of the next block
+	int32_t triggered_avg;  // fm_demod.cpp:58
+	int32_t runs;           // blocks since the stream's start or last restart (fm_demod.cpp:37)
+	int32_t last_trig;      // last sample with pwr > thresh, relative to the start of the next submit (very negative: none)
+};
+
+// One run of one stream as capture_scan_kernel leaves it for capture_copy_kernel, relative to the submit and to the stream
+struct CaptureStage {
+	int32_t start, end;  // first captured sample, and the first one behind the run
+	int32_t thresh;      // the threshold in force at start
+	uint32_t flags;      // TFREC_AMD_RUN_CONTINUES or 0 (TFREC_AMD_RUN_OPEN follows from end)
+	uint32_t rank;       // captured pairs of the stream ahead of the run
+};
+
+// the true totals of a submit, whatever the table and the pool could hold
+struct CaptureHeader {
+	unsigned long long n_runs, n_pairs;
+};
+
 // fm_dev samples decided by the exact slow path (fm_resolve.h): logged so that the host can check them against its
 // own libm when the batch is drained (capi.hip)
 struct FmLogEntry {

@@ -216,6 +216,14 @@ std::vector<batch_plan> plan_batches(const std::vector<size_t> &file_blocks, con
 //   worker thread : drain batch k's flush events and queue them for the engine's thread
 // The C ABI's submit/drain FIFO (depth TFREC_AMD_FIFO_DEPTH = 4) is what lets batches k+1 .. k+3 be queued before batch
 // k is drained; this loop keeps the FIFO full (one pinned host buffer per submit in flight + one being read).
+// -S: the captures of one batch of one device: the runs that belong to a file (file[i]: its index in the job), cut at the file's
+// end, and the batch's sample pool, which their pool_offset indexes
+struct capture_batch {
+	std::vector<tfrec_amd_run> runs;
+	std::vector<int> file;
+	std::vector<int16_t> pool;
+};
+
 struct device_worker {
 	const std::vector<std::string> *files;
 	size_t s0, s1;
@@ -236,23 +244,26 @@ struct device_worker {
 	std::condition_variable cv;
 	std::deque<std::vector<tfrec_amd_event> > out;  // batches drained, oldest first
 	std::deque<std::vector<tfrec_amd_level> > out_levels;  // -s: their level records, [stream][the batch's blocks]
+	bool capture;  // -S: the contexts record (tfrec_amd_enable_capture)
+	std::deque<capture_batch> out_caps;  // -S: their runs (stream = the file's index in the job) and sample pool
 	bool done;
 	std::thread th;
 
-	device_worker() : files(NULL), s0(0), s1(0), device(0), types(0), thresh(0), filter(0), bps(1), flags(0), nslots(0), file_blocks(NULL), wide(false), share(false), rate_p(1), rate_q(1), fmt(TFREC_AMD_FMT_U8), block_bytes(TFREC_AMD_BLOCK_BYTES), unit(1), rc(0), abort(NULL), done(false) {}
+	device_worker() : files(NULL), s0(0), s1(0), device(0), types(0), thresh(0), filter(0), bps(1), flags(0), nslots(0), file_blocks(NULL), wide(false), share(false), rate_p(1), rate_q(1), fmt(TFREC_AMD_FMT_U8), block_bytes(TFREC_AMD_BLOCK_BYTES), unit(1), rc(0), abort(NULL), capture(false), done(false) {}
 
-	void push(std::vector<tfrec_amd_event> &&ev, std::vector<tfrec_amd_level> &&lv)
+	void push(std::vector<tfrec_amd_event> &&ev, std::vector<tfrec_amd_level> &&lv, capture_batch &&cb)
 	{
 		{
 			std::unique_lock<std::mutex> lk(mu);
 			cv.wait(lk, [&]() { return out.size() < 2; });  // the engine's thread is at most two batches behind
 			out.push_back(std::move(ev));
 			out_levels.push_back(std::move(lv));
+			out_caps.push_back(std::move(cb));
 		}
 		cv.notify_all();
 	}
 	// next batch's events and (-s) level records (false: the worker ended -- rc says why)
-	bool pop(std::vector<tfrec_amd_event> &ev, std::vector<tfrec_amd_level> &lv)
+	bool pop(std::vector<tfrec_amd_event> &ev, std::vector<tfrec_amd_level> &lv, capture_batch &cb)
 	{
 		std::unique_lock<std::mutex> lk(mu);
 		cv.wait(lk, [&]() { return !out.empty() || done; });
@@ -262,6 +273,8 @@ struct device_worker {
 		out.pop_front();
 		lv = std::move(out_levels.front());
 		out_levels.pop_front();
+		cb = std::move(out_caps.front());
+		out_caps.pop_front();
 		lk.unlock();
 		cv.notify_all();
 		return true;
@@ -344,6 +357,15 @@ struct device_worker {
 		} else {
 			for (size_t s = 0; s < n; s++)
 				in_row[s] = (int32_t)s;
+		}
+		if (capture) {  // -S, sized so that no submit overflows: every sample, and a stream's runs are >= 356 samples long but two
+			r = tfrec_amd_enable_capture(ctx, (uint32_t)(n * ((size_t)bps * TFREC_AMD_BLOCK_DEC / 356 + 3)),
+						     (uint64_t)n * (uint64_t)bps * TFREC_AMD_BLOCK_DEC);
+			if (r) {
+				fprintf(stderr, "tfrec_amd_enable_capture (device %d): %s (%s)\n", device, tfrec_amd_strerror(r), tfrec_amd_last_error());
+				tfrec_amd_destroy(ctx);
+				return r;
+			}
 		}
 		const int depth = std::max(1, std::min(tfrec_amd_fifo_depth(), TFREC_AMD_FIFO_DEPTH));
 		constexpr int kBufs = TFREC_AMD_FIFO_DEPTH + 1;
@@ -460,6 +482,41 @@ struct device_worker {
 				r = TFREC_AMD_E_STATE;
 				break;
 			}
+			capture_batch cb;
+			if (capture) {  // -S: the batch's captures, then its levels, then the drain that pops it
+				uint32_t nr = 0;
+				uint64_t np = 0;
+				r = tfrec_amd_read_captures(ctx, NULL, 0, &nr, NULL, 0, &np);  // (the counts: E_INVAL for want of room)
+				if (r == TFREC_AMD_E_INVAL && nr) {
+					cb.runs.resize((size_t)nr + 1);
+					cb.pool.resize(2 * (size_t)np + 2);
+					r = tfrec_amd_read_captures(ctx, cb.runs.data(), cb.runs.size(), &nr, cb.pool.data(), cb.pool.size() / 2, &np);
+				}
+				size_t have = nr;
+				if (r == TFREC_AMD_E_OVERFLOW) {  // the runs that fitted were returned (n_samples == 0 ends them); the job goes on
+					for (have = 0; have < cb.runs.size() && cb.runs[have].n_samples; have++) {
+					}
+					fprintf(stderr, "tfrec_amd: device %d batch %zu: capture overflow, %zu of %u runs kept\n", device, k, have, (unsigned)nr);
+					r = 0;
+				}
+				if (r)
+					break;
+				// stream -> file, as for the events below; a run is cut at its file's end
+				const std::vector<int> &file = plan[k].file;
+				size_t kept = 0;
+				for (size_t q = 0; q < have; q++) {
+					tfrec_amd_run x = cb.runs[q];
+					if (x.stream >= file.size() || file[x.stream] < 0)
+						continue;
+					const long long end = (long long)(*file_blocks)[file[x.stream]] * TFREC_AMD_BLOCK_DEC;
+					if (x.start_sample >= end)
+						continue;
+					x.n_samples = (uint32_t)std::min<long long>(x.n_samples, end - x.start_sample);
+					cb.file.push_back(file[x.stream]);
+					cb.runs[kept++] = x;
+				}
+				cb.runs.resize(kept);
+			}
 			std::vector<tfrec_amd_level> lv;
 			if (flags & TFREC_AMD_F_LEVELS) {  // -s: the batch's level records, before the drain pops it
 				int nb = 0;
@@ -492,7 +549,7 @@ struct device_worker {
 					ev[kept++].stream = (uint32_t)file[ev[q].stream];
 				}
 			ev.resize(kept);
-			push(std::move(ev), std::move(lv));
+			push(std::move(ev), std::move(lv), std::move(cb));
 		}
 		if (r)
 			fprintf(stderr, "tfrec_amd (device %d): %s (%s)\n", device, tfrec_amd_strerror(r), tfrec_amd_last_error());
@@ -576,6 +633,7 @@ int gpu_engine::run()
 		w.bps = bps;
 		w.flags = (bits_replay ? (TFREC_AMD_F_BITS | TFREC_AMD_F_ALL_FLUSHES) : 0u) | (wide ? TFREC_AMD_F_INPUT_10X : 0u) |
 			  (scan ? TFREC_AMD_F_LEVELS : 0u);
+		w.capture = capture;
 		w.wide = wide;
 		w.share = slots <= 0;
 		w.rate_p = rate_p;
@@ -598,6 +656,13 @@ int gpu_engine::run()
 	int rc = 0;
 	std::vector<tfrec_amd_event> ev;
 	std::vector<tfrec_amd_level> lv;
+	capture_batch cb;
+	FILE *cap_idx = NULL;  // -S: <prefix>.idx, and which files' <prefix>.<file>.cs16 exist already
+	std::vector<bool> cap_made(capture ? n : 0, false);
+	if (capture && !(cap_idx = fopen((cap_prefix + ".idx").c_str(), "w"))) {
+		perror((cap_prefix + ".idx").c_str());
+		return TFREC_AMD_E_INVAL;
+	}
 	// -s: per channel (file) the sums of its level records, its telegrams, and with -D every record
 	struct channel_sum {
 		unsigned long long blocks = 0, pwr_sum = 0, over = 0, triggered = 0, telegrams = 0;
@@ -609,10 +674,32 @@ int gpu_engine::run()
 		for (size_t d = 0; d < nd && rc == 0; d++) {
 			if (k >= workers[d].plan.size())
 				continue;  // (this device's queue has run out)
-			if (!workers[d].pop(ev, lv)) {
+			if (!workers[d].pop(ev, lv, cb)) {
 				rc = workers[d].rc ? workers[d].rc : TFREC_AMD_E_STATE;
 				break;
 			}
+			for (size_t q = 0; q < cb.runs.size() && rc == 0;) {  // -S: the runs of one file are adjacent (the table is ordered by stream)
+				const int f = cb.file[q];
+				const std::string path = cap_prefix + "." + std::to_string(f) + ".cs16";
+				FILE *fp = fopen(path.c_str(), cap_made[f] ? "ab" : "wb");
+				if (!fp) {
+					perror(path.c_str());
+					rc = TFREC_AMD_E_INVAL;
+					break;
+				}
+				cap_made[f] = true;
+				for (; q < cb.runs.size() && cb.file[q] == f; q++) {
+					const tfrec_amd_run &x = cb.runs[q];
+					fprintf(cap_idx, "%d %u %lld %u %d %u\n", f, (unsigned)x.stream, (long long)x.start_sample, (unsigned)x.n_samples, (int)x.thresh,
+						(unsigned)x.flags);
+					if (fwrite(cb.pool.data() + 2 * (size_t)x.pool_offset, 4, x.n_samples, fp) != x.n_samples)
+						rc = TFREC_AMD_E_INVAL;
+				}
+				if (fclose(fp))
+					rc = TFREC_AMD_E_INVAL;
+			}
+			if (rc)
+				break;
 			if (scan) {  // no replay: the table is the product
 				const batch_plan &b = workers[d].plan[k];
 				for (size_t s = 0; s < b.file.size(); s++) {
@@ -659,12 +746,14 @@ int gpu_engine::run()
 	if (rc)
 		abort.store(true);
 	for (size_t d = 0; d < nd; d++) {
-		while (workers[d].pop(ev, lv)) {
+		while (workers[d].pop(ev, lv, cb)) {
 		}
 		workers[d].th.join();
 		if (!rc)
 			rc = workers[d].rc;
 	}
+	if (cap_idx && fclose(cap_idx) && !rc)
+		rc = TFREC_AMD_E_INVAL;
 	if (scan && !rc)
 		for (size_t s = 0; s < n; s++) {
 			const channel_sum &c = chan[s];

@@ -142,6 +142,13 @@ public:
 	// preceded, with dbg > 0, by the reference's per-block line "<kHz> Trigger ratio <triggered>/8192, avg <triggered_avg>"
 	// (fm_demod.cpp:61) for every block.  One device, no -n.
 	void set_scan(const std::vector<long> &khz) { scan = true; scan_khz = khz; }
+	// -S: the squelched recorder (tfrec_amd_enable_capture).  Every context captures the IQ of its streams' trigger
+	// windows; run() writes <prefix>.idx -- text, one line "<file index> <stream> <start_sample> <n_samples> <thresh> <flags>" per run
+	// in submit order, stream = the file's stream on its device, start_sample counted within the file -- and, for every file with
+	// a run, <prefix>.<file index>.cs16: the file's captured samples appended submit by submit, 384 kS/s int16 interleaved I, Q.
+	// The capture is sized from the batch's blocks and the stream count so that no submit can overflow it; should one, a warning
+	// goes to stderr per submit and the run goes on.  Runs are cut at the file's end (the padding behind it is not the file's).
+	void set_capture(const std::string &prefix) { capture = true; cap_prefix = prefix; }
 	// returns 0 on success, a TFREC_AMD_E_* code otherwise
 	int run();
 	// decoders of stream s in slot order (NULL for slots not registered)
@@ -167,6 +174,8 @@ private:
 	int fmt;                   // set_format (TFREC_AMD_FMT_U8: none)
 	bool scan = false;         // set_scan
 	std::vector<long> scan_khz;
+	bool capture = false;      // set_capture
+	std::string cap_prefix;
 };
 
 #endif

@@ -47,6 +47,12 @@
 //   scan <kHz> blocks=<n> mean_pwr=<..> peak=<..> over=<..> triggered=<..> thresh=<..> telegrams=<..>
 // and with -D, ahead of it, the reference's "Trigger ratio" line (fm_demod.cpp:61) of each of its blocks, prefixed with <kHz>;
 // stderr lists the channels before a device is opened.  Not with -n, -p, -f, -e / -E, -X, several -L or several devices.
+// -S prefix (the reference's letter, main.cpp:77 "Save IQ-file for later debugging"; here of the trigger windows only): record the
+// decimated IQ of every sample at which a demodulator of the stream was triggered (tfrec_amd_enable_capture).
+// <prefix>.idx gets one text line "<file index> <stream> <start_sample> <n_samples> <thresh> <flags>" per run, in submit order;
+// <prefix>.<file index>.cs16 that file's captured samples, appended submit by submit: 384 kS/s int16 interleaved I, Q, which any
+// SDR viewer opens (a file without a run gets none).  Works with -s -- a channel that triggers and decodes nothing is the case
+// it is for -- and with everything else but -X.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -163,8 +169,9 @@ int main(int argc, char **argv)
 	int format = TFREC_AMD_FMT_U8;  // -F
 	long scan_step = 0;  // -s: kHz
 	bool have_scan = false;
+	const char *cap_prefix = NULL;  // -S
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:h")) != -1) {
 		switch (c) {
 		case 's': {
 			char *end = NULL;
@@ -176,6 +183,13 @@ int main(int argc, char **argv)
 			}
 			break;
 		}
+		case 'S':
+			cap_prefix = optarg;
+			if (!*cap_prefix) {
+				fprintf(stderr, "tfrec_gpu: bad -S '': want the prefix of the files to write\n");
+				return 1;
+			}
+			break;
 		case 'T': types = (int)strtol(optarg, NULL, 16); break;
 		case 't': thresh = atoi(optarg); break;
 		case 'W': filter = 1; break;
@@ -238,8 +252,9 @@ int main(int argc, char **argv)
 		case 'E': exec = optarg; batched = true; break;
 		case 'm': mode = atoi(optarg); break;
 		default:
-			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -X hexfile\n"
+			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -X hexfile\n"
 					"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
+					"  -S prefix   record the IQ of every trigger window: <prefix>.idx (a line per run) and <prefix>.<file>.cs16 (384 kS/s int16 I, Q)\n"
 					"  -f kHz      receive frequency (default: the dumps' own, -c)\n"
 					"  -c kHz      frequency the dumps were recorded at (default 868250); -f within 767 kHz of it\n"
 					"  -x          the dumps are 15.36 MS/s u8 dumps (10x the rate); -f within 7679 kHz of -c, shifted ahead of the 10:1 stage\n"
@@ -260,6 +275,10 @@ int main(int argc, char **argv)
 	}
 	if (have_scan && (have_slots || have_spec || freq >= 0 || exec || hexfile || dumps.size() > 1 || devices.size() > 1)) {
 		fprintf(stderr, "tfrec_gpu: -s scans one -L file on one device: not with -n, -p, -f, -e, -E, -X, several -L or several -d\n");
+		return 1;
+	}
+	if (cap_prefix && hexfile) {
+		fprintf(stderr, "tfrec_gpu: -S records the trigger windows of -L files: not with -X\n");
 		return 1;
 	}
 	if (have_spec && hexfile) {
@@ -377,6 +396,8 @@ int main(int argc, char **argv)
 	e.set_format(format);
 	if (have_scan)
 		e.set_scan(scan_khz);
+	if (cap_prefix)
+		e.set_capture(cap_prefix);
 	int rc = e.run();
 	fflush(stdout);
 	return rc ? 2 : 0;
