@@ -475,6 +475,52 @@ int tfrec_amd_enable_capture(tfrec_amd_ctx *ctx, uint32_t max_runs, uint64_t max
 int tfrec_amd_read_captures(tfrec_amd_ctx *ctx, tfrec_amd_run *runs, size_t cap_runs, uint32_t *n_runs, int16_t *samples,
 			    size_t cap_pairs, uint64_t *n_pairs);
 
+/* Power spectrum of the input rows (tfrec_amd_enable_spectrum): where in a recording there is energy, and where the
+ * short bursts are that an average hides -- before a receiver is placed.  It belongs to an input ROW of a submit, not to a stream: it
+ * is taken on x, the int16 value every format maps a stored component to (tfrec_amd_create_format; -8192 <= x <= 8191), at the
+ * context's input rate, ahead of every tune, resampler and FIR.  Valid on every kind of context (tfrec_amd_create,
+ * TFREC_AMD_F_INPUT_10X, rate and format contexts).  Exact integers only: a direct DFT with one rounding before it and one after it
+ * and nothing in between, so that the order of summation cannot matter.  No reference counterpart; pinned by tfrec_amd/spectrum.py.
+ *   Tables:  C[k] = round(32767 * cos(2 pi k / 4096)), S[k] = C[(k - 1024) mod 4096] -- tfrec_amd_tune_streams' table, no other.
+ *            N = n_bins, one of 64, 128, 256, 512, 1024;  step = 4096 / N.
+ *   Window:  w[n] = (32767 - C[(n * step) mod 4096]) >> 1,  n = 0 .. N-1  (periodic Hann; 0 <= w <= 32767, w[0] = 0, w[N/2] = 32767).
+ *   Sample:  xw = (x * w[n] + 2^14) >> 15  per rail (int32, arithmetic shift): |xw| <= 8192.
+ *   Frames:  frame f of a submit covers the row's input samples [f N, (f + 1) N), counted from the submit's first sample;
+ *            F = floor(n_in / N) frames, n_in = the submit's complex samples per row (tfrec_amd_input_bytes / bytes per sample).  A
+ *            tail shorter than N is not analysed.  Nothing is carried from submit to submit; a restart of a stream does not touch it.
+ *   DFT:     for bin k = 0 .. N-1 and t = (k * n * step) mod 4096:
+ *                X_re[k] = sum_n ( xwI * C[t] + xwQ * S[t] ),   X_im[k] = sum_n ( xwQ * C[t] - xwI * S[t] )
+ *            The sign is the mixer's: a tone at +f lands in bin round(f N / fs_in), one at -f in bin N - that.  Exact integers: a term
+ *            is at most 8192 * (|C[t]| + |S[t]|) <= 8192 * 46341 < 2^29 in magnitude, so |X| < 2^39 at N = 1024, and every partial sum
+ *            of every grouping stays far below 2^53: int64 -- or fp64 on these integer operands -- is exact in any order.
+ *   Power:   Y = (X + 2^14) >> 15 per component (arithmetic shift), p[k] = Y_re^2 + Y_im^2  (|Y| < 2^24, p < 2^49).
+ *   Records: G = frames_per_record consecutive frames form a record: record r of a submit holds frames [r G, min((r + 1) G, F)),
+ *            ceil(F / G) records, the last may be short.  Per record and bin: sum[k] = sum of p[k] over its frames (< 2^63),
+ *            peak[k] = the largest p[k] among them (the peak hold that keeps a 10 ms burst visible in a one-second record); per
+ *            record n_frames, the frames it holds.
+ *   Cutting: where N divides every submit's n_in and G every submit's F, the concatenated records do not depend on how the input is
+ *            cut into submits; otherwise they do (frames and records are counted from each submit's first sample).
+ * tfrec_amd_enable_spectrum: allowed only before the first submit (after it: TFREC_AMD_E_STATE).  Rows 0 .. min(R, max_rows) - 1 of
+ * each submit are analysed, R = the rows the submit provides (tfrec_amd_map_streams: 1 + the highest row a stream reads; n_streams
+ * on an unmapped context).  Per FIFO set (TFREC_AMD_FIFO_DEPTH of them) it allocates max_rows * max_records * N * 16 bytes for
+ * sums and peaks and max_rows * max_records * 4 bytes for the frame counts, max_records = ceil(floor(n_max / N) / G) with n_max =
+ * floor(max_blocks * 32768 * P / Q) (the context's input rate P / Q; 10 / 1 with TFREC_AMD_F_INPUT_10X); tfrec_amd_get_memory counts
+ * all of it.  The one kernel runs on a low-priority stream of its own, ordered behind the producer of the input only; events,
+ * levels and captures do not depend on it.
+ * Errors: n_bins outside the list, frames_per_record outside [1, 16384], max_rows outside [1, n_streams], a NULL context or a
+ * second call: TFREC_AMD_E_INVAL; TFREC_AMD_E_NOMEM leaves the context usable without the spectrum (and holding nothing for it); a
+ * poisoned context: TFREC_AMD_E_STATE.
+ * A context on which it was never called creates no stream, event or buffer for this and launches what it launched before. */
+int tfrec_amd_enable_spectrum(tfrec_amd_ctx *ctx, int32_t n_bins, int32_t frames_per_record, int32_t max_rows);
+/* The spectrum records of one input row of the OLDEST undrained submit (waits for it; like tfrec_amd_read_levels, call it BEFORE
+ * tfrec_amd_drain_events pops that submit; reading pops nothing): sum[r * N + k], peak[r * N + k], n_frames[r] for r < *n_records;
+ * cap_records is the room in records.  sum, peak and n_frames may be NULL with cap_records 0 to fetch only *n_records.
+ * Errors: the spectrum not enabled, a row the submit's spectrum does not cover (row < 0 or row >= min(R, max_rows)), n_records
+ * NULL: TFREC_AMD_E_INVAL; the room too small (or a NULL array with records to deliver): TFREC_AMD_E_INVAL, nothing is written, but
+ * *n_records is set; nothing undrained or a poisoned context: TFREC_AMD_E_STATE. */
+int tfrec_amd_read_spectrum(tfrec_amd_ctx *ctx, int32_t row, uint64_t *sum, uint64_t *peak, size_t cap_records, uint32_t *n_frames,
+			    int *n_records);
+
 /* The dB value the reference demodulator passes to decoder::flush for this slot, computed with the
  * reference's host expressions (tfa1.cpp:180, tfa2.cpp:434, whb.cpp:696) including (int)(10*log10(0)). */
 int tfrec_amd_rssi_db(int slot, int64_t rssi_raw);

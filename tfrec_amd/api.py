@@ -104,7 +104,8 @@ EXPORTS = (
     "tfrec_amd_map_streams", "tfrec_amd_get_stream_input", "tfrec_amd_tune_streams_wide", "tfrec_amd_get_stream_tune_wide",
     "tfrec_amd_create_rate", "tfrec_amd_get_input_rate", "tfrec_amd_input_bytes", "tfrec_amd_resample_taps",
     "tfrec_amd_tune_streams_input", "tfrec_amd_get_stream_tune_input", "tfrec_amd_create_format", "tfrec_amd_get_input_format",
-    "tfrec_amd_read_levels", "tfrec_amd_enable_capture", "tfrec_amd_read_captures",
+    "tfrec_amd_read_levels", "tfrec_amd_enable_capture", "tfrec_amd_read_captures", "tfrec_amd_enable_spectrum",
+    "tfrec_amd_read_spectrum",
 )
 
 _libs = {}
@@ -183,6 +184,8 @@ def load_library(build: bool = True, experiments: bool = False):
     L.tfrec_amd_enable_capture.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
     L.tfrec_amd_read_captures.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
                                           C.POINTER(C.c_uint64)]
+    L.tfrec_amd_enable_spectrum.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+    L.tfrec_amd_read_spectrum.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int)]
     L.tfrec_amd_fifo_depth.restype = C.c_int
     if L.tfrec_amd_fifo_depth() != FIFO_DEPTH:
         raise RuntimeError("libtfrec_amd.so was built with FIFO depth %d, this binding expects %d" % (
@@ -494,6 +497,36 @@ class Receiver:
         runs = runs[:k].copy()
         n = int(runs["pool_offset"][-1] + runs["n_samples"][-1]) if k else 0
         return runs, samples[:n].copy()
+
+    def enable_spectrum(self, n_bins: int, frames_per_record: int, max_rows: int | None = None):
+        """Turn the per-input power spectrum on (tfrec_amd_enable_spectrum; before the first submit): an exact integer DFT of
+        n_bins bins over rows 0 .. max_rows - 1 (default: every row) of each submit, frames_per_record frames per record
+        (spectrum.py).  read_spectrum returns the records."""
+        rows = self.n_streams if max_rows is None else int(max_rows)
+        if not all(-2 ** 31 <= int(v) < 2 ** 31 for v in (n_bins, frames_per_record, rows)):  # (refused before int32 could wrap)
+            raise TfrecAmdError(E_INVAL, "n_bins, frames_per_record or max_rows outside int32")
+        _check(self.L, self.L.tfrec_amd_enable_spectrum(self.h, int(n_bins), int(frames_per_record), rows))
+        self._spectrum_bins = int(n_bins)
+
+    def read_spectrum(self, row: int):
+        """The spectrum records of input row `row` of the OLDEST undrained submit (tfrec_amd_read_spectrum; call it before the drain
+        that pops that submit) -> (sum[n_records, N] uint64, peak[n_records, N] uint64, n_frames[n_records] uint32).
+        TfrecAmdError(E_INVAL) on a context without enable_spectrum or for a row the submit's spectrum does not cover, (E_STATE)
+        when nothing is waiting to be drained."""
+        if not -2 ** 31 <= int(row) < 2 ** 31:
+            raise TfrecAmdError(E_INVAL, "row outside int32")
+        nr = C.c_int(0)
+        rc = self.L.tfrec_amd_read_spectrum(self.h, int(row), None, None, 0, None, C.byref(nr))  # the count (no room: E_INVAL)
+        n = getattr(self, "_spectrum_bins", 0)
+        if n == 0 or rc == E_STATE or (rc == E_INVAL and nr.value == 0):
+            _check(self.L, rc)
+        s = np.zeros((nr.value, n), dtype=np.uint64)
+        p = np.zeros((nr.value, n), dtype=np.uint64)
+        f = np.zeros(nr.value, dtype=np.uint32)
+        if nr.value:
+            _check(self.L, self.L.tfrec_amd_read_spectrum(self.h, int(row), s.ctypes.data, p.ctypes.data, nr.value, f.ctypes.data,
+                                                          C.byref(nr)))
+        return s, p, f
 
     def stage0(self, stream: int, n_pairs: int) -> np.ndarray:
         """input_10x or input_rate: the 1.536 MS/s int16 IQ the 10:1 or the resampling stage produced for the last submit."""

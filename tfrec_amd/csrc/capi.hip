@@ -48,6 +48,8 @@ hipError_t launch_capture(hipStream_t st, const uint32_t *dec, size_t dec_stride
 			  int n_streams, int n_blocks, long long sample_base, CaptureState *cst, const StreamCfg *scfg, CaptureStage *stage,
 			  int stage_cap, uint2 *cnt, uint4 *base, CaptureHeader *hdr, tfrec_amd_run *runs, uint32_t max_runs, uint32_t *pool,
 			  unsigned long long max_samples);
+hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_rows, long n_in, int n_bins, int g,
+			   size_t max_records, unsigned long long *sum, unsigned long long *peak, uint32_t *nfr);
 }  // namespace tfrec
 
 using namespace tfrec;
@@ -161,6 +163,17 @@ struct tfrec_amd_ctx {
 	hipStream_t cap = nullptr;
 	hipEvent_t ev_cap[kSets] = {};
 	std::vector<tfrec_amd_run> cap_tmp;
+	// tfrec_amd_enable_spectrum: bins, frames per record, rows analysed at most and the records the largest submit
+	// can hold; per set the sums and peaks ([spec_rows][spec_max_records][spec_n]), the frame counts ([spec_rows][spec_max_records]),
+	// the "records written" event and what the set's submit held (rows analysed, records); the kernel's low-priority stream
+	bool spectrum = false;
+	int spec_n = 0, spec_g = 0, spec_rows = 0;
+	size_t spec_max_records = 0;
+	unsigned long long *d_spec_sum[kSets] = {}, *d_spec_peak[kSets] = {};
+	uint32_t *d_spec_nf[kSets] = {};
+	hipStream_t sp = nullptr;
+	hipEvent_t ev_spectrum[kSets] = {};
+	int spec_set_rows[kSets] = {}, spec_set_records[kSets] = {};
 	int wmax = 0;
 	// tfrec_amd_configure_streams: every stream's settings as the next submit uses them (scfg, the host's copy), their device
 	// copy as the last submit used them (d_scfg: written only by stream_reset_kernel, in the entries of its list), and the
@@ -1521,6 +1534,21 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		HIPCHK(hipEventRecord(c->ev_in[set], (hipStream_t)hip_stream));
 		HIPCHK(hipStreamWaitEvent(fs, c->ev_in[set], 0));
 	}
+	if (c->spectrum) {
+		// the spectrum: it reads the raw rows and nothing else, so it is ordered behind the input's producer alone -- the wait the
+		// front end makes, or (staged host input) the copy queued on fs just before -- and runs beside everything, on its own
+		// low-priority stream.  The set's records were read or dropped when its previous submit was drained.
+		if (input_on_fs)
+			HIPCHK(hipEventRecord(c->ev_in[set], fs));
+		HIPCHK(hipStreamWaitEvent(c->sp, c->ev_in[set], 0));
+		const int rows = std::min(rows_in_use(c), c->spec_rows);
+		const long n_in = (long)(row_bytes / fmt_sample_bytes(c->fmt));
+		HIPCHK(launch_spectrum(c->sp, c->fmt, (const uint8_t *)d_iq, stride, rows, n_in, c->spec_n, c->spec_g, c->spec_max_records,
+				       c->d_spec_sum[set], c->d_spec_peak[set], c->d_spec_nf[set]));
+		HIPCHK(hipEventRecord(c->ev_spectrum[set], c->sp));
+		c->spec_set_rows[set] = rows;
+		c->spec_set_records[set] = (int)((n_in / c->spec_n + c->spec_g - 1) / c->spec_g);
+	}
 	HIPCHK(hipMemcpyAsync(c->d_eb[set], c->d_eb_fresh, kEvFreshBytes, hipMemcpyDeviceToDevice, fs));  // (+ the overflow flag)
 	if (timing)
 		HIPCHK(hipEventRecord(ev[kEvSubmit], fs));
@@ -1593,6 +1621,8 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		HIPCHK(hipStreamWaitEvent(c->cpy, c->ev_lev[set], 0));
 	if (c->capture)  // ... and "the captures are written" (tfrec_amd_read_captures)
 		HIPCHK(hipStreamWaitEvent(c->cpy, c->ev_cap[set], 0));
+	if (c->spectrum)  // ... and "the spectrum's records are written" (tfrec_amd_read_spectrum; the staged input may be reused)
+		HIPCHK(hipStreamWaitEvent(c->cpy, c->ev_spectrum[set], 0));
 	c->copied_n[set] = std::min<uint32_t>(c->copy_guess, (uint32_t)c->cfg.max_events);
 	{  // header, overflow flag and the first copied_n events in one go
 		static_assert(kEvHeader % 16 == 0 && sizeof(tfrec_amd_event) % 16 == 0, "drain_copy_kernel moves 16 bytes per lane");
@@ -1847,6 +1877,113 @@ int tfrec_amd_read_captures(tfrec_amd_ctx *c, tfrec_amd_run *runs, size_t cap_ru
 	if (overflow && cap_runs > have)
 		memset(&runs[have], 0, sizeof(tfrec_amd_run));
 	return overflow ? TFREC_AMD_E_OVERFLOW : TFREC_AMD_OK;
+}
+
+// Give back what own_* recorded behind `mark` (an enable call that ran out of memory half way: the context goes on without it)
+static void release_from(tfrec_amd_ctx *c, size_t mark, size_t dev_bytes)
+{
+	while (c->owned.size() > mark) {
+		const tfrec_amd_ctx::Owned o = c->owned.back();
+		c->owned.pop_back();
+		switch (o.kind) {
+		case tfrec_amd_ctx::Owned::kDevice: (void)hipFree(o.h); break;
+		case tfrec_amd_ctx::Owned::kPinned: (void)hipHostFree(o.h); break;
+		case tfrec_amd_ctx::Owned::kStream: (void)hipStreamDestroy(static_cast<hipStream_t>(o.h)); break;
+		case tfrec_amd_ctx::Owned::kEvent: (void)hipEventDestroy(static_cast<hipEvent_t>(o.h)); break;
+		}
+	}
+	c->dev_bytes = dev_bytes;
+}
+
+static int make_spectrum(tfrec_amd_ctx *c, size_t rows, size_t records, size_t n)
+{
+	for (int k = 0; k < kSets; k++) {
+		TRY(own_device(c, c->d_spec_sum[k], rows * records * n * sizeof(unsigned long long)));
+		TRY(own_device(c, c->d_spec_peak[k], rows * records * n * sizeof(unsigned long long)));
+		TRY(own_device(c, c->d_spec_nf[k], rows * records * sizeof(uint32_t)));
+		TRY(own_event(c, c->ev_spectrum[k], hipEventDisableTiming));
+	}
+	int prio_lo = 0, prio_hi = 0;
+	(void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+	TRY(own_stream(c, c->sp, prio_lo));
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_enable_spectrum(tfrec_amd_ctx *c, int32_t n_bins, int32_t frames_per_record, int32_t max_rows)
+{
+	if (!c)
+		return TFREC_AMD_E_INVAL;
+	const bool bins_ok = n_bins == 64 || n_bins == 128 || n_bins == 256 || n_bins == 512 || n_bins == 1024;
+	if (!bins_ok || frames_per_record < 1 || frames_per_record > 16384 || max_rows < 1 || max_rows > c->cfg.n_streams || c->spectrum) {
+		snprintf(g_err, sizeof(g_err), c->spectrum ? "the spectrum is enabled already"
+				: "n_bins is 64, 128, 256, 512 or 1024, frames_per_record within [1, 16384], max_rows within [1, n_streams]");
+		return TFREC_AMD_E_INVAL;
+	}
+	TRY(check_live(c));
+	if (c->submitted) {
+		snprintf(g_err, sizeof(g_err), "the spectrum is enabled before the first submit");
+		return TFREC_AMD_E_STATE;
+	}
+	HIPCHK(hipSetDevice(c->cfg.device));
+	// the largest submit: floor(max_blocks * 32768 * P / Q) complex samples per row
+	const long long p = c->in10x ? 10 : c->rate_p, q = c->in10x ? 1 : c->rate_q;
+	const long long n_in = (long long)c->cfg.max_blocks * (TFREC_AMD_BLOCK_BYTES / 2) * p / q;
+	const long long frames = n_in / n_bins;
+	const size_t records = (size_t)((frames + frames_per_record - 1) / frames_per_record);
+	const size_t mark = c->owned.size(), bytes = c->dev_bytes;
+	const int rc = make_spectrum(c, (size_t)max_rows, records, (size_t)n_bins);
+	if (rc != TFREC_AMD_OK) {
+		release_from(c, mark, bytes);
+		for (int k = 0; k < kSets; k++) {
+			c->d_spec_sum[k] = c->d_spec_peak[k] = nullptr;
+			c->d_spec_nf[k] = nullptr;
+			c->ev_spectrum[k] = nullptr;
+		}
+		c->sp = nullptr;
+		return rc;
+	}
+	c->spec_n = n_bins;
+	c->spec_g = frames_per_record;
+	c->spec_rows = max_rows;
+	c->spec_max_records = records;
+	c->spectrum = true;
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_read_spectrum(tfrec_amd_ctx *c, int32_t row, uint64_t *sum, uint64_t *peak, size_t cap_records, uint32_t *n_frames,
+			    int *n_records)
+{
+	if (!c || !n_records)
+		return TFREC_AMD_E_INVAL;
+	if (!c->spectrum) {
+		snprintf(g_err, sizeof(g_err), "tfrec_amd_enable_spectrum was not called on this context");
+		return TFREC_AMD_E_INVAL;
+	}
+	TRY(check_live(c));
+	if (c->inflight == 0) {
+		snprintf(g_err, sizeof(g_err), "no undrained submit: the spectrum is read before tfrec_amd_drain_events");
+		return TFREC_AMD_E_STATE;
+	}
+	const int set = c->head;
+	if (row < 0 || row >= c->spec_set_rows[set]) {
+		snprintf(g_err, sizeof(g_err), "row %d: the submit's spectrum covers rows [0, %d)", (int)row, c->spec_set_rows[set]);
+		return TFREC_AMD_E_INVAL;
+	}
+	const size_t nr = (size_t)c->spec_set_records[set], n = (size_t)c->spec_n;
+	*n_records = (int)nr;
+	if (cap_records < nr || (nr > 0 && (!sum || !peak || !n_frames))) {
+		snprintf(g_err, sizeof(g_err), "room for %zu spectrum records, the submit has %zu", cap_records, nr);
+		return TFREC_AMD_E_INVAL;
+	}
+	if (nr == 0)
+		return TFREC_AMD_OK;
+	HIPCHK(hipSetDevice(c->cfg.device));
+	HIPCHK(hipEventSynchronize(c->copied[set]));  // (behind ev_spectrum[set])
+	const size_t r0 = (size_t)row * c->spec_max_records;
+	HIPCHK(hipMemcpy(sum, c->d_spec_sum[set] + r0 * n, nr * n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(peak, c->d_spec_peak[set] + r0 * n, nr * n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(n_frames, c->d_spec_nf[set] + r0, nr * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	return TFREC_AMD_OK;
 }
 
 int tfrec_amd_drain_events(tfrec_amd_ctx *c, tfrec_amd_event *out, int cap, int *n_out)

@@ -218,10 +218,13 @@ std::vector<batch_plan> plan_batches(const std::vector<size_t> &file_blocks, con
 // k is drained; this loop keeps the FIFO full (one pinned host buffer per submit in flight + one being read).
 // -S: the captures of one batch of one device: the runs that belong to a file (file[i]: its index in the job), cut at the file's
 // end, and the batch's sample pool, which their pool_offset indexes
+// -P travels with it: the batch's spectrum records of input row 0, [record][bin], and their frame counts
 struct capture_batch {
 	std::vector<tfrec_amd_run> runs;
 	std::vector<int> file;
 	std::vector<int16_t> pool;
+	std::vector<uint64_t> spec_sum, spec_peak;
+	std::vector<uint32_t> spec_frames;
 };
 
 struct device_worker {
@@ -245,11 +248,12 @@ struct device_worker {
 	std::deque<std::vector<tfrec_amd_event> > out;  // batches drained, oldest first
 	std::deque<std::vector<tfrec_amd_level> > out_levels;  // -s: their level records, [stream][the batch's blocks]
 	bool capture;  // -S: the contexts record (tfrec_amd_enable_capture)
+	int spec_n, spec_g;  // -P: bins and frames per record of the spectrum of row 0 (tfrec_amd_enable_spectrum); 0: none
 	std::deque<capture_batch> out_caps;  // -S: their runs (stream = the file's index in the job) and sample pool
 	bool done;
 	std::thread th;
 
-	device_worker() : files(NULL), s0(0), s1(0), device(0), types(0), thresh(0), filter(0), bps(1), flags(0), nslots(0), file_blocks(NULL), wide(false), share(false), rate_p(1), rate_q(1), fmt(TFREC_AMD_FMT_U8), block_bytes(TFREC_AMD_BLOCK_BYTES), unit(1), rc(0), abort(NULL), capture(false), done(false) {}
+	device_worker() : files(NULL), s0(0), s1(0), device(0), types(0), thresh(0), filter(0), bps(1), flags(0), nslots(0), file_blocks(NULL), wide(false), share(false), rate_p(1), rate_q(1), fmt(TFREC_AMD_FMT_U8), block_bytes(TFREC_AMD_BLOCK_BYTES), unit(1), rc(0), abort(NULL), capture(false), spec_n(0), spec_g(0), done(false) {}
 
 	void push(std::vector<tfrec_amd_event> &&ev, std::vector<tfrec_amd_level> &&lv, capture_batch &&cb)
 	{
@@ -363,6 +367,14 @@ struct device_worker {
 						     (uint64_t)n * (uint64_t)bps * TFREC_AMD_BLOCK_DEC);
 			if (r) {
 				fprintf(stderr, "tfrec_amd_enable_capture (device %d): %s (%s)\n", device, tfrec_amd_strerror(r), tfrec_amd_last_error());
+				tfrec_amd_destroy(ctx);
+				return r;
+			}
+		}
+		if (spec_n) {  // -P: the one file's row
+			r = tfrec_amd_enable_spectrum(ctx, spec_n, spec_g, 1);
+			if (r) {
+				fprintf(stderr, "tfrec_amd_enable_spectrum (device %d): %s (%s)\n", device, tfrec_amd_strerror(r), tfrec_amd_last_error());
 				tfrec_amd_destroy(ctx);
 				return r;
 			}
@@ -517,6 +529,18 @@ struct device_worker {
 				}
 				cb.runs.resize(kept);
 			}
+			if (spec_n) {  // -P: the batch's spectrum records, before the drain pops it
+				int nr = 0;
+				r = tfrec_amd_read_spectrum(ctx, 0, NULL, NULL, 0, NULL, &nr);  // (the count: E_INVAL for want of room)
+				if (r == TFREC_AMD_E_INVAL && nr > 0) {
+					cb.spec_sum.resize((size_t)nr * spec_n);
+					cb.spec_peak.resize((size_t)nr * spec_n);
+					cb.spec_frames.resize((size_t)nr);
+					r = tfrec_amd_read_spectrum(ctx, 0, cb.spec_sum.data(), cb.spec_peak.data(), (size_t)nr, cb.spec_frames.data(), &nr);
+				}
+				if (r)
+					break;
+			}
 			std::vector<tfrec_amd_level> lv;
 			if (flags & TFREC_AMD_F_LEVELS) {  // -s: the batch's level records, before the drain pops it
 				int nb = 0;
@@ -605,8 +629,21 @@ int gpu_engine::run()
 		stream_samples[s] = (long long)blocks * TFREC_AMD_BLOCK_DEC;
 		file_blocks[s] = blocks;
 	}
+	const long fs_in = wide ? 15360000L : 1536000L * rate_p / rate_q;
+	// -P: bin k lies at center + (k < N/2 ? k : k - N) fs_in / N; listed (and printed) in ascending frequency
+	std::vector<double> spec_khz(spectrum ? spec_n : 0);
+	std::vector<int> spec_order(spectrum ? spec_n : 0);
+	if (spectrum) {
+		fprintf(stderr, "spec: %d bins, %d frames per record, input rate %ld S/s\n", spec_n, spec_g, fs_in);
+		for (int i = 0; i < spec_n; i++) {
+			const int k = (i + spec_n / 2) % spec_n;
+			spec_order[i] = k;
+			spec_khz[k] = spec_center + (double)((long)(k < spec_n / 2 ? k : k - spec_n) * fs_in) / spec_n / 1000.0;
+			fprintf(stderr, "spec bin %.3f kHz\n", spec_khz[k]);
+		}
+	}
 	if (scan) {  // -s: the channel list, before a device is opened
-		fprintf(stderr, "scan: %zu channels, input rate %ld S/s\n", n, wide ? 15360000L : 1536000L * rate_p / rate_q);
+		fprintf(stderr, "scan: %zu channels, input rate %ld S/s\n", n, fs_in);
 		for (size_t s = 0; s < n; s++) {
 			const int hz = settings[s].tune;
 			const bool far = !wide && (hz <= -768000 || hz >= 768000);
@@ -634,6 +671,8 @@ int gpu_engine::run()
 		w.flags = (bits_replay ? (TFREC_AMD_F_BITS | TFREC_AMD_F_ALL_FLUSHES) : 0u) | (wide ? TFREC_AMD_F_INPUT_10X : 0u) |
 			  (scan ? TFREC_AMD_F_LEVELS : 0u);
 		w.capture = capture;
+		w.spec_n = spectrum ? spec_n : 0;
+		w.spec_g = spec_g;
 		w.wide = wide;
 		w.share = slots <= 0;
 		w.rate_p = rate_p;
@@ -670,6 +709,12 @@ int gpu_engine::run()
 		std::vector<tfrec_amd_level> rec;
 	};
 	std::vector<channel_sum> chan(scan ? n : 0);
+	// -P: per bin the sum over every record (a record's sum stays below 2^63, a long file's total need not), the peak, the frames;
+	// with -D every record as it came
+	std::vector<unsigned __int128> spec_total(spectrum ? spec_n : 0, 0);
+	std::vector<uint64_t> spec_peak(spectrum ? spec_n : 0, 0), rec_sum, rec_peak;
+	std::vector<uint32_t> rec_frames;
+	unsigned long long spec_frames = 0;
 	for (size_t k = 0; k < n_batches && rc == 0; k++) {
 		for (size_t d = 0; d < nd && rc == 0; d++) {
 			if (k >= workers[d].plan.size())
@@ -700,6 +745,18 @@ int gpu_engine::run()
 			}
 			if (rc)
 				break;
+			for (size_t q = 0; q < cb.spec_frames.size(); q++) {  // -P
+				spec_frames += cb.spec_frames[q];
+				for (int b = 0; b < spec_n; b++) {
+					spec_total[b] += cb.spec_sum[q * spec_n + b];
+					spec_peak[b] = std::max(spec_peak[b], cb.spec_peak[q * spec_n + b]);
+				}
+			}
+			if (spectrum && dbg > 0) {
+				rec_sum.insert(rec_sum.end(), cb.spec_sum.begin(), cb.spec_sum.end());
+				rec_peak.insert(rec_peak.end(), cb.spec_peak.begin(), cb.spec_peak.end());
+				rec_frames.insert(rec_frames.end(), cb.spec_frames.begin(), cb.spec_frames.end());
+			}
 			if (scan) {  // no replay: the table is the product
 				const batch_plan &b = workers[d].plan[k];
 				for (size_t s = 0; s < b.file.size(); s++) {
@@ -768,6 +825,15 @@ int gpu_engine::run()
 			for (size_t k2 = 0; k2 < decs[s].size(); k2++)
 				if (decs[s][k2])
 					decs[s][k2]->flush_storage();
+	if (spectrum && !rc) {  // -P: behind the telegram output
+		for (size_t q = 0; q < rec_frames.size(); q++)
+			for (int k : spec_order)
+				printf("spec-rec %zu %.3f sum=%llu peak=%llu frames=%u\n", q, spec_khz[k], (unsigned long long)rec_sum[q * spec_n + k],
+				       (unsigned long long)rec_peak[q * spec_n + k], (unsigned)rec_frames[q]);
+		for (int k : spec_order)
+			printf("spec %.3f mean=%llu peak=%llu\n", spec_khz[k],
+			       spec_frames ? (unsigned long long)(spec_total[k] / spec_frames) : 0ull, (unsigned long long)spec_peak[k]);
+	}
 	if (psink)
 		psink->flush();
 	return rc;

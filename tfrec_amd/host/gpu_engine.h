@@ -149,6 +149,19 @@ public:
 	// The capture is sized from the batch's blocks and the stream count so that no submit can overflow it; should one, a warning
 	// goes to stderr per submit and the run goes on.  Runs are cut at the file's end (the padding behind it is not the file's).
 	void set_capture(const std::string &prefix) { capture = true; cap_prefix = prefix; }
+	// -P: the power spectrum of the one -L file's input row (tfrec_amd_enable_spectrum on row 0): n_bins bins,
+	// frames_per_record frames per record, the file recorded at center_khz.  run() lists the bins' frequencies on stderr before a
+	// device is opened ("spec bin <kHz>", ascending) and prints, behind the telegram output and in ascending frequency, per bin
+	//   spec <kHz, 3 decimals> mean=<total sum / total frames> peak=<max over the records>
+	// preceded, with dbg > 0, by "spec-rec <record> <kHz> sum=<..> peak=<..> frames=<..>" per record (counted through the file) and bin.
+	// The bin's frequency is center + (k < N/2 ? k : k - N) fs_in / N.  One file, one device, no -n.
+	void set_spectrum(int n_bins, int frames_per_record, long center_khz)
+	{
+		spectrum = true;
+		spec_n = n_bins;
+		spec_g = frames_per_record;
+		spec_center = center_khz;
+	}
 	// returns 0 on success, a TFREC_AMD_E_* code otherwise
 	int run();
 	// decoders of stream s in slot order (NULL for slots not registered)
@@ -176,6 +189,9 @@ private:
 	std::vector<long> scan_khz;
 	bool capture = false;      // set_capture
 	std::string cap_prefix;
+	bool spectrum = false;     // set_spectrum
+	int spec_n = 0, spec_g = 0;
+	long spec_center = 0;
 };
 
 #endif

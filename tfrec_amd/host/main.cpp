@@ -2,6 +2,7 @@
 //
 //   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-q] [-D] [-B] [-d device[,device...]] [-b blocks]
 //             [-n streams] [-e handler | -E handler] [-m mode] [-p settings] -L dump.iq [[-p settings] -L more.iq ...]
+//   tfrec_gpu [receiver flags as above] [-c kHz] [-x | -r Hz] [-F format] [-D] -P bins[,frames_per_record] -L dump.iq
 //   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-c kHz] [-x | -r Hz] [-F format] [-D] [-d device] [-b blocks] -s step_kHz -L dump.iq
 //   tfrec_gpu [-T hexmask] -X telegrams.txt
 //
@@ -53,11 +54,21 @@
 // <prefix>.<file index>.cs16 that file's captured samples, appended submit by submit: 384 kS/s int16 interleaved I, Q, which any
 // SDR viewer opens (a file without a run gets none).  Works with -s -- a channel that triggers and decodes nothing is the case
 // it is for -- and with everything else but -X.
+// -P bins[,frames_per_record] (not in the reference): the power spectrum of ONE recording, beside its decoding: an
+// exact integer DFT of bins = 64, 128, 256, 512 or 1024 bins over the raw input -- at 1.536 MS/s, or given with -x, or with -r / -F --,
+// per record of frames_per_record frames (1 .. 16384; default: the frames one block's input holds, at least 1) the sum and the peak
+// hold of every bin's power (tfrec_amd_enable_spectrum).  The file runs as one stream and is decoded as usual; behind the telegram
+// output stdout carries one line per bin in ascending frequency,
+//   spec <kHz, 3 decimals> mean=<total sum / total frames> peak=<max over the records>
+// and with -D, ahead of that table, "spec-rec <record> <kHz> sum=<..> peak=<..> frames=<..>" per record and bin; bin k lies at
+// c + (k < N/2 ? k : k - N) fs_in / N.  stderr lists the bins before a device is opened.  Not with -s, -n, -p, -X, several -L or
+// several devices.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -170,9 +181,33 @@ int main(int argc, char **argv)
 	long scan_step = 0;  // -s: kHz
 	bool have_scan = false;
 	const char *cap_prefix = NULL;  // -S
+	int spec_bins = 0, spec_g = 0;  // -P (spec_g 0: the default)
+	bool have_spec_p = false;
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:P:h")) != -1) {
 		switch (c) {
+		case 'P': {
+			char *end = NULL;
+			const long nb = strtol(optarg, &end, 10);
+			long g = 0;
+			bool ok = end != optarg && (nb == 64 || nb == 128 || nb == 256 || nb == 512 || nb == 1024);
+			if (ok && *end == ',') {
+				const char *gs = end + 1;
+				g = strtol(gs, &end, 10);
+				ok = end != gs && !*end && g >= 1 && g <= 16384;
+			} else if (ok && *end) {
+				ok = false;
+			}
+			if (!ok) {
+				fprintf(stderr, "tfrec_gpu: bad -P '%s': want <bins>[,<frames per record>], bins one of 64, 128, 256, 512, 1024, frames "
+						"per record within 1 .. 16384\n", optarg);
+				return 1;
+			}
+			have_spec_p = true;
+			spec_bins = (int)nb;
+			spec_g = (int)g;
+			break;
+		}
 		case 's': {
 			char *end = NULL;
 			scan_step = strtol(optarg, &end, 10);
@@ -252,8 +287,10 @@ int main(int argc, char **argv)
 		case 'E': exec = optarg; batched = true; break;
 		case 'm': mode = atoi(optarg); break;
 		default:
-			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -X hexfile\n"
+			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -X hexfile\n"
 					"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
+					"  -P bins[,G] power spectrum of one dump beside its decoding: bins = 64 .. 1024 (a power of two), G frames per record; a\n"
+					"              line per bin behind the telegrams (-D: per record too)\n"
 					"  -S prefix   record the IQ of every trigger window: <prefix>.idx (a line per run) and <prefix>.<file>.cs16 (384 kS/s int16 I, Q)\n"
 					"  -f kHz      receive frequency (default: the dumps' own, -c)\n"
 					"  -c kHz      frequency the dumps were recorded at (default 868250); -f within 767 kHz of it\n"
@@ -275,6 +312,10 @@ int main(int argc, char **argv)
 	}
 	if (have_scan && (have_slots || have_spec || freq >= 0 || exec || hexfile || dumps.size() > 1 || devices.size() > 1)) {
 		fprintf(stderr, "tfrec_gpu: -s scans one -L file on one device: not with -n, -p, -f, -e, -E, -X, several -L or several -d\n");
+		return 1;
+	}
+	if (have_spec_p && (have_scan || have_slots || have_spec || hexfile || dumps.size() > 1 || devices.size() > 1)) {
+		fprintf(stderr, "tfrec_gpu: -P takes the spectrum of one -L file on one device: not with -s, -n, -p, -X, several -L or several -d\n");
 		return 1;
 	}
 	if (cap_prefix && hexfile) {
@@ -398,6 +439,10 @@ int main(int argc, char **argv)
 		e.set_scan(scan_khz);
 	if (cap_prefix)
 		e.set_capture(cap_prefix);
+	if (have_spec_p) {  // the default record: the frames one block's input holds
+		const long per_block = wide ? 327680L : 32768L * rate_p / rate_q;
+		e.set_spectrum(spec_bins, spec_g ? spec_g : (int)std::max(1L, per_block / spec_bins), center);
+	}
 	int rc = e.run();
 	fflush(stdout);
 	return rc ? 2 : 0;
