@@ -457,7 +457,8 @@ typedef struct {            /* 32 bytes */
  * staging per stream (a stream cannot have more runs in a submit: all but its first and last are at least 356 samples long);
  * tfrec_amd_get_memory counts all of it.  tfrec_amd_config has no spare field, so this is a call and not a flag.
  * Errors: a NULL context, a zero argument or a second call: TFREC_AMD_E_INVAL; TFREC_AMD_E_NOMEM as elsewhere (the context stays
- * usable, without the recorder); a poisoned context: TFREC_AMD_E_STATE.
+ * usable, without the recorder); a poisoned context: TFREC_AMD_E_STATE.  A call that fails leaves the context exactly as it was
+ * before it: it holds nothing for the recorder, tfrec_amd_get_memory reports what it reported, and a later call is a first one.
  * A context on which it was never called creates no stream, event or buffer for this and launches what it launched before. */
 int tfrec_amd_enable_capture(tfrec_amd_ctx *ctx, uint32_t max_runs, uint64_t max_samples);
 /* The captures of the OLDEST undrained submit (waits for it; like tfrec_amd_read_levels, call it BEFORE tfrec_amd_drain_events pops
@@ -509,7 +510,8 @@ int tfrec_amd_read_captures(tfrec_amd_ctx *ctx, tfrec_amd_run *runs, size_t cap_
  * levels and captures do not depend on it.
  * Errors: n_bins outside the list, frames_per_record outside [1, 16384], max_rows outside [1, n_streams], a NULL context or a
  * second call: TFREC_AMD_E_INVAL; TFREC_AMD_E_NOMEM leaves the context usable without the spectrum (and holding nothing for it); a
- * poisoned context: TFREC_AMD_E_STATE.
+ * poisoned context: TFREC_AMD_E_STATE.  A call that fails leaves the context exactly as it was before it: tfrec_amd_get_memory
+ * reports what it reported, and a later call is a first one.
  * A context on which it was never called creates no stream, event or buffer for this and launches what it launched before. */
 int tfrec_amd_enable_spectrum(tfrec_amd_ctx *ctx, int32_t n_bins, int32_t frames_per_record, int32_t max_rows);
 /* The spectrum records of one input row of the OLDEST undrained submit (waits for it; like tfrec_amd_read_levels, call it BEFORE

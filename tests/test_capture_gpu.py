@@ -368,6 +368,36 @@ def test_without_the_call_nothing_is_held_and_the_read_is_refused():
         r.drain()
 
 
+def test_a_failed_enable_leaves_the_context_as_it_was():
+    """tfrec_amd_enable_capture that runs out of memory half way -- a pool of 4 TiB per set, past the SIZE_MAX guard and beyond any
+    device's memory: hipMalloc returns its ordinary out-of-memory error -- gives back what it made: the memory totals are those
+    from before the call, the recorder is off, and a later enable is a first one, whose recorder works."""
+    def fresh():
+        return api.Receiver(1, CTX_TYPES, 500, 0, max_blocks=1, levels=True)
+
+    with fresh() as r:
+        plain = r.memory()
+        r.enable_capture(16, 1024)
+        one_enable = r.memory()["device_bytes"] - plain["device_bytes"]
+    assert one_enable > 0
+    with fresh() as r:
+        before = r.memory()
+        assert before == plain
+        with pytest.raises(api.TfrecAmdError) as e:
+            r.enable_capture(16, 1 << 40)
+        assert e.value.code == api.E_NOMEM
+        assert r.memory() == before
+        with pytest.raises(api.TfrecAmdError) as e:
+            r.read_captures()
+        assert e.value.code == api.E_INVAL
+        r.enable_capture(16, 1024)
+        m = r.memory()
+        assert m["device_bytes"] - before["device_bytes"] == one_enable and m["pinned_host_bytes"] == before["pinned_host_bytes"]
+        x = np.random.default_rng(23).integers(126, 131, api.BLOCK_BYTES, dtype=np.uint8)
+        burst(x, 4 * 3000, 4 * 3050)  # one run, the burst and the longest window behind it: it fits the pool
+        assert 0 < check_plain(r, [x.reshape(1, -1)], CTX_TYPES, 500) <= 1024
+
+
 def test_cli_capture_of_the_golden_tfa_2_scene(tmp_path):
     cli = parity.build_cli()
     z = np.load(os.path.join(parity.ROOT, "tests", "golden", "iq_tfa_2.npz"))

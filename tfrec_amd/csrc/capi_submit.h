@@ -1,0 +1,539 @@
+// tfrec_amd/csrc/capi_submit.h -- submit and drain: included by capi.hip, which lists what is where.
+#pragma once
+
+namespace tfrec {
+// The drain's device-to-host copy as a kernel of our own (16 bytes per lane into the page-locked block, which the device addresses
+// directly).  hipMemcpyAsync did the same with the runtime's copy kernel -- but two or three times after every synchronize (the 6th and
+// 7th submit of the driver's 20-step line) the CALL blocked the host for a whole batch period, now and then for two (13 ms: the pipeline
+// ran dry, 6.2 instead of 5.75 ms per step): profiles/r06_host_stalls.txt.
+__global__ __launch_bounds__(256) void drain_copy_kernel(const uint4 *__restrict__ src, uint4 *__restrict__ dst, size_t n16)
+{
+	for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256)
+		dst[i] = src[i];
+}
+
+// tfrec_amd_reset_streams: every piece of state a submit carries to the next one, back to what tfrec_amd_create made of it,
+// for the streams list[0 .. n_list) (distinct, < n_streams).  A workgroup per listed stream.  See DESIGN.md, "Stream reset".
+struct StreamReset {
+	const int32_t *list;
+	int32_t n_list, n_streams;
+	uint8_t *tail;      // front-end FIR history the NEXT front end reads: tail_bytes per stream, filled with tail_fill
+	int32_t tail_bytes, tail_fill;
+	uint8_t *pre;       // the pre-stage's history the NEXT one reads (pre_bytes per stream, filled with pre_fill), or nullptr
+	int32_t pre_bytes, pre_fill;
+	FskState *fsk;      // auto threshold
+	LevelState *lev;    // TFREC_AMD_F_LEVELS: the level meter's carried state, or nullptr
+	CaptureState *cap;  // tfrec_amd_enable_capture: the recorder's carried state, or nullptr
+	const StreamCfg *cfgs;  // [n_list] the listed streams' settings from this submit on ...
+	StreamCfg *scfg;        // ... written over their entries here
+	int32_t n_active;
+	ChainState *states[kNSlots];
+	const ChainState *chain_init;
+	int32_t *tcarry;    // [n_active * n_streams] window scan's timeout carry (window-parallel pipeline), or nullptr
+	WhbExact *whbx;     // WHB check's exact filter state, its carry and the redo's chain state (WHB registered), or nullptr
+	int *whbcarry;
+	ChainState *whbX;
+};
+
+__global__ __launch_bounds__(64) void stream_reset_kernel(StreamReset R)
+{
+	if ((int)blockIdx.x >= R.n_list)
+		return;
+	const int s = R.list[blockIdx.x];
+	if (s < 0 || s >= R.n_streams)
+		return;
+	const int ln = threadIdx.x;
+	for (int i = ln; i < R.tail_bytes; i += 64)
+		R.tail[(size_t)s * R.tail_bytes + i] = (uint8_t)R.tail_fill;
+	for (int i = ln; i < R.pre_bytes; i += 64)  // (0 without a history)
+		R.pre[(size_t)s * R.pre_bytes + i] = (uint8_t)R.pre_fill;
+	constexpr int kChunks = (int)(sizeof(ChainState) / 16);
+	const uint4 *init = reinterpret_cast<const uint4 *>(R.chain_init);
+	for (int a = 0; a < R.n_active; a++)
+		for (int i = ln; i < kChunks; i += 64)
+			reinterpret_cast<uint4 *>(&R.states[a][s])[i] = init[i];
+	if (R.whbX)
+		for (int i = ln; i < kChunks; i += 64)
+			reinterpret_cast<uint4 *>(&R.whbX[s])[i] = init[i];
+	if (ln == 0) {
+		// In place: every kernel of the submits before this one that reads scfg has ended (launch_resets)
+		const StreamCfg sc = R.cfgs[blockIdx.x];
+		R.scfg[s] = sc;
+		R.fsk[s] = FskState{ sc.thresh, 0, 0, -(1 << 28) };  // auto: 500, fm_demod.cpp:23-27, as tfrec_amd_create
+		if (R.lev)
+			R.lev[s] = LevelState{ sc.thresh, 0, 0, -(1 << 28) };
+		if (R.cap)
+			R.cap[s] = CaptureState{ sc.thresh, 0, 0, -(1 << 28) };
+		if (R.tcarry)
+			for (int a = 0; a < R.n_active; a++)
+				R.tcarry[(size_t)a * R.n_streams + s] = 0;
+		if (R.whbx) {
+			R.whbx[s] = WhbExact{ 0.0, 0.0, 0, 0, 0, 0 };
+			R.whbcarry[s] = 0;
+		}
+	}
+}
+}  // namespace tfrec
+
+// The resets marked since the last submit, at the head of this submit's front end (fs).  Carried state is written by several
+// stages on several streams (a ChainState by the biquad stage, the slicers, the decoders' commit and the WHB check's redo), and
+// in the deep layout those of the submit before may still run while this one's front end does: the front-end stream first
+// waits for the end of every chain of the last submit (its set's done: every stage of it and of all earlier submits is behind
+// one of them), then one kernel restores the state of the listed streams.  Every stage of this submit is ordered after its
+// front end, so it reads the restored state.  A submit without a pending reset launches nothing of this.
+static int launch_resets(tfrec_amd_ctx *c, int set)
+{
+	hipStream_t fs = c->pipe[set].fs;
+	if (c->submitted)
+		for (hipEvent_t e : c->pipe[c->last_set].done)
+			HIPCHK(hipStreamWaitEvent(fs, e, 0));
+	if (c->submitted)  // (the level meter and the recorder of the last submit read d_scfg and own their carried state)
+		for (const SideLane *l : { &c->lev.lane, &c->cap.lane })
+			if (l->on)
+				HIPCHK(hipStreamWaitEvent(fs, l->written[c->last_set], 0));
+	const int nl = (int)c->reset_pending.size();
+	memcpy(c->h_reset[set], c->reset_pending.data(), (size_t)nl * sizeof(int32_t));  // (the set's last copy was drained)
+	for (int i = 0; i < nl; i++)  // a reset stream restarts with its own current settings
+		c->h_rcfg[set][i] = c->scfg[c->reset_pending[i]];
+	HIPCHK(hipMemcpyAsync(c->d_reset[set], c->h_reset[set], (size_t)nl * sizeof(int32_t), hipMemcpyHostToDevice, fs));
+	HIPCHK(hipMemcpyAsync(c->d_rcfg[set], c->h_rcfg[set], (size_t)nl * sizeof(StreamCfg), hipMemcpyHostToDevice, fs));
+	StreamReset R;
+	memset(&R, 0, sizeof(R));
+	R.list = c->d_reset[set];
+	R.n_list = nl;
+	R.n_streams = c->cfg.n_streams;
+	R.tail = c->d_tail[c->tail_sel];  // the buffer this submit's front end reads (the history flips per submit)
+	R.tail_bytes = c->in16 ? 2 * kTailBytes : kTailBytes;
+	R.tail_fill = c->in16 ? 0 : 0x80;  // as make_front_buffers: int16 zero, or u8 128
+	R.pre = c->d_pre[c->tail_sel];
+	R.pre_bytes = c->pre_bytes;
+	R.pre_fill = c->pre_fill;
+	R.fsk = c->d_fsk;
+	R.lev = c->lev.d_state;
+	R.cap = c->cap.d_state;
+	R.cfgs = c->d_rcfg[set];
+	R.scfg = c->d_scfg;
+	R.n_active = c->launch.n_active;
+	for (int a = 0; a < c->launch.n_active; a++)
+		R.states[a] = c->launch.states[a];
+	R.chain_init = c->d_chain_init;
+	R.tcarry = c->d_tcarry;
+	R.whbx = c->d_whbx;
+	R.whbcarry = c->d_whbcarry;
+	R.whbX = c->d_whbX;
+	hipLaunchKernelGGL(tfrec::stream_reset_kernel, dim3(nl), dim3(64), 0, fs, R);
+	HIPCHK(hipGetLastError());
+	return TFREC_AMD_OK;
+}
+
+// The tuned front end's per-stream {inc, phase} of this submit, queued on the front-end stream ahead of it.  The
+// phase of the submit's first 1.536 MS/s sample n0 (4 per decimated sample, counted from the stream's start or restart --
+// 0 for a stream that restarts with this submit) is (n0 * inc) mod 2^32, in 64-bit integers.  h_tune[set] is free: the
+// set's previous submit, whose copy read it, has been drained.
+static int stage_tune(tfrec_amd_ctx *c, int set)
+{
+	for (int s = 0; s < c->cfg.n_streams; s++) {
+		const uint32_t inc = c->tune_inc[s];
+		const long long n0 = c->reset_marked[s] ? 0 : 4 * (c->sample_base - c->origin[s]);
+		c->h_tune[set][s] = make_uint2(inc, (uint32_t)((uint64_t)n0 * inc));
+	}
+	HIPCHK(hipMemcpyAsync(c->d_tune[set], c->h_tune[set], (size_t)c->cfg.n_streams * sizeof(uint2), hipMemcpyHostToDevice,
+			      c->pipe[set].fs));
+	return TFREC_AMD_OK;
+}
+
+// The per-stream {inc10, phase10, input row, 0} of this submit, staged like stage_tune's.  phase10 is the phase of
+// the submit's first INPUT sample n0 (40 per decimated sample with TFREC_AMD_F_INPUT_10X): (n0 * inc10) mod 2^32.  A rate
+// context (6g): {inc_in, ...} with n0 = 4 P / Q input samples per decimated sample -- whole, because every submit is.
+static int stage_chan(tfrec_amd_ctx *c, int set)
+{
+	for (int s = 0; s < c->cfg.n_streams; s++) {
+		const uint32_t inc = c->wide_inc[s];
+		const long long n0 = c->reset_marked[s] ? 0 : 4 * (c->sample_base - c->origin[s]) * c->in_p / c->in_q;
+		c->h_chan[set][s] = make_uint4(inc, (uint32_t)((uint64_t)n0 * inc), (uint32_t)c->row[s], 0u);
+	}
+	HIPCHK(hipMemcpyAsync(c->d_chan[set], c->h_chan[set], (size_t)c->cfg.n_streams * sizeof(uint4), hipMemcpyHostToDevice,
+			      c->pipe[set].fs));
+	return TFREC_AMD_OK;
+}
+
+// rows of the input batch the streams read: 1 + the highest one mapped
+static int rows_in_use(const tfrec_amd_ctx *c)
+{
+	if (!c->mapped)
+		return c->cfg.n_streams;
+	return 1 + *std::max_element(c->row.begin(), c->row.end());
+}
+
+// Bytes of one input row of a submit of n_blocks blocks: n_blocks * 32768 * P / Q complex samples, which must be a whole
+// number (any n_blocks when Q is a power of two, otherwise a multiple of Q's odd part), of 2, 4 or 8 bytes each.
+static int input_bytes(const tfrec_amd_ctx *c, int n_blocks, size_t *bytes)
+{
+	if (n_blocks < 1)
+		return TFREC_AMD_E_INVAL;
+	const long long p = c->in_p, q = c->in_q;
+	const long long num = (long long)n_blocks * (TFREC_AMD_BLOCK_BYTES / 2) * p;
+	if (num % q != 0) {
+		snprintf(g_err, sizeof(g_err), "%d blocks at the input rate %lld/%lld are not a whole number of input samples", n_blocks, p, q);
+		return TFREC_AMD_E_INVAL;
+	}
+	*bytes = (size_t)(num / q) * fmt_sample_bytes(c->fmt);
+	return TFREC_AMD_OK;
+}
+
+// The submit's input -> stage 0 (d_in16[set]) on the set's front-end stream.  chan: the set's {inc, phase, row, 0} per stream
+// where a stream is mapped or has an input-rate tune (stage_chan), or nullptr.
+static int launch_prestage(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, size_t stride, int n_blocks, const uint4 *chan)
+{
+	hipStream_t fs = c->pipe[set].fs;
+	const int n = c->cfg.n_streams;
+	const uint8_t *hin = c->d_pre[c->tail_sel];
+	uint8_t *hout = c->d_pre[c->tail_sel ^ 1];
+	uint32_t *out = c->d_in16[set];
+	if (c->in10x)  // 15.36 MS/s u8 -> 1.536 MS/s int16 pairs
+		HIPCHK(launch_decim10(fs, d_iq, stride, n, n_blocks, hin, hout, out, c->in16_stride, chan));
+	else if (c->ingest)  // 1.536 MS/s in another format -> x as int16 pairs
+		HIPCHK(launch_ingest(fs, c->fmt, d_iq, stride, n, n_blocks, out, c->in16_stride, chan));
+	else if (c->fmt != TFREC_AMD_FMT_U8)  // 1536000 P / Q S/s in another format: the format-aware resampling stage
+		HIPCHK(launch_resample_fmt(fs, c->fmt, d_iq, stride, n, n_blocks, c->in_p, c->in_q, c->rate_t, c->d_rtaps, hin, hout, out,
+					   c->in16_stride, chan, c->n_wide != 0));
+	else  // 1536000 P / Q S/s u8 -> 1.536 MS/s int16 pairs
+		HIPCHK(launch_resample(fs, d_iq, stride, n, n_blocks, c->in_p, c->in_q, c->rate_t, c->d_rtaps, hin, hout, out, c->in16_stride,
+				       chan, c->n_wide != 0));
+	return TFREC_AMD_OK;
+}
+
+// input_on_fs: the input was produced on the front-end stream itself (staged host input): no event needed
+static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int n_blocks, void *hip_stream, bool input_on_fs)
+{
+	if (!c || !d_iq || n_blocks < 1 || n_blocks > c->cfg.max_blocks)
+		return TFREC_AMD_E_INVAL;
+	size_t row_bytes = 0;
+	TRY(input_bytes(c, n_blocks, &row_bytes));
+	if ((stride % 16) != 0 || ((uintptr_t)d_iq % 16) != 0 ||
+	    (rows_in_use(c) > 1 && stride < row_bytes)) {  // (one row in use: the stride is never applied)
+		snprintf(g_err, sizeof(g_err), "IQ base and stream stride must be 16-byte aligned and >= one stream");
+		return TFREC_AMD_E_INVAL;
+	}
+	TRY(check_fifo(c));
+	TRY(check_live(c));
+	HIPCHK(hipSetDevice(c->cfg.device));
+	PoisonGuard guard(c);  // from here on work is enqueued: a failure leaves the carried state undefined
+	const bool timing = (c->cfg.flags & TFREC_AMD_F_TIMING) != 0;
+	const int set = (c->head + c->inflight) % kSets;  // this submit's buffer set, events and timing events
+	const PipeCtl &P = c->pipe[set];
+	hipEvent_t *ev = c->ev[set];
+	// Front end on its own stream: it starts when the caller's stream has produced the input, and may overlap the
+	// chains of the previous submit (different buffer set; the set's previous user was drained, see the FIFO rule).
+	// The chains run on internal streams: nothing of ours is queued on the caller's.
+	hipStream_t fs = P.fs;
+	if (!input_on_fs) {
+		HIPCHK(hipEventRecord(c->ev_in[set], (hipStream_t)hip_stream));
+		HIPCHK(hipStreamWaitEvent(fs, c->ev_in[set], 0));
+	}
+	if (c->spec.lane.on) {
+		// the spectrum: it reads the raw rows and nothing else, so it is ordered behind the input's producer alone -- the wait the
+		// front end makes, or (staged host input) the copy queued on fs just before -- and runs beside everything, on its own
+		// low-priority stream.  The set's records were read or dropped when its previous submit was drained.
+		if (input_on_fs)
+			HIPCHK(hipEventRecord(c->ev_in[set], fs));
+		HIPCHK(lane_after(c->spec.lane, c->ev_in[set]));
+		const int rows = std::min(rows_in_use(c), c->spec.rows);
+		const long n_in = (long)(row_bytes / fmt_sample_bytes(c->fmt));
+		HIPCHK(launch_spectrum(c->spec.lane.st, c->fmt, (const uint8_t *)d_iq, stride, rows, n_in, c->spec.n, c->spec.g, c->spec.max_records,
+				       c->spec.d_sum[set], c->spec.d_peak[set], c->spec.d_nf[set]));
+		HIPCHK(lane_written(c->spec.lane, set));
+		c->spec.set_rows[set] = rows;
+		c->spec.set_records[set] = (int)((n_in / c->spec.n + c->spec.g - 1) / c->spec.g);
+	}
+	HIPCHK(hipMemcpyAsync(c->d_eb[set], c->d_eb_fresh, kEvFreshBytes, hipMemcpyDeviceToDevice, fs));  // (+ the overflow flag)
+	if (timing)
+		HIPCHK(hipEventRecord(ev[kEvSubmit], fs));
+	const bool resets = !c->reset_pending.empty();
+	if (resets)
+		TRY(launch_resets(c, set));
+	const uint8_t *fin = (const uint8_t *)d_iq;
+	size_t fstride = stride;
+	// a mapped or wide-tuned context: the 10:1 stage's tuned kernel, or -- default input -- the front end that looks up the rows
+	// (a rate context: the resampling stage looks the row up, as the 10:1 stage does)
+	const bool chan10 = c->in16 && (c->mapped || c->n_wide), chan_front = !c->in16 && c->mapped;
+	if (chan10 || chan_front)
+		TRY(stage_chan(c, set));
+	if (c->in16) {  // ... then the standard cascade on int16 input
+		TRY(launch_prestage(c, set, (const uint8_t *)d_iq, stride, n_blocks, chan10 ? c->d_chan[set] : nullptr));
+		fin = (const uint8_t *)c->d_in16[set];
+		fstride = c->in16_stride * sizeof(uint32_t);
+	}
+	if (c->n_tuned || chan_front)
+		TRY(stage_tune(c, set));
+	HIPCHK(launch_frontend(fs, fin, fstride, c->cfg.n_streams, n_blocks, c->d_tail[c->tail_sel],
+			       c->d_tail[c->tail_sel ^ 1], c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride,
+			       c->d_prevdec[set], c->cfg.thresh ? c->cfg.thresh : 500, c->taps, c->in16,
+			       (c->n_tuned || chan_front) ? c->d_tune[set] : nullptr, chan_front ? c->d_chan[set] : nullptr));
+	if (c->n_auto)  // auto threshold: per-block thresholds rewrite the trigger mask (fm_demod.cpp:58-73)
+		HIPCHK(launch_threshold(fs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams,
+					n_blocks, c->d_fsk, c->wmax, c->per_stream ? c->d_scfg : nullptr));
+	if (timing)
+		HIPCHK(hipEventRecord(ev[kEvFrontDone], fs));
+	if (has_kind(c->launch, 1) && !c->fmdev_k2)  // FM discriminator of the samples near trigger windows (after the mask is final)
+		HIPCHK(launch_fmdev(fs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->d_prevdec[set],
+				    c->d_fmdev[set], c->dec_stride, c->d_eb[set], c->cfg.n_streams, n_blocks, c->wmax,
+				    c->fm_flag_eps));
+	if (timing)
+		HIPCHK(hipEventRecord(ev[kEvFmdevDone], fs));
+	HIPCHK(hipEventRecord(P.ev_front, fs));
+	if (c->lev.lane.on) {  // the level meter: behind the front end (the mask is final), beside the chains, on its own low-priority stream
+		HIPCHK(lane_after(c->lev.lane, P.ev_front));
+		HIPCHK(launch_levels(c->lev.lane.st, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams, n_blocks,
+				     c->lev.d_state, c->d_scfg, c->lev.d_records[set]));
+		HIPCHK(lane_written(c->lev.lane, set));
+		c->lev.set_blocks[set] = n_blocks;
+	}
+	if (c->cap.lane.on) {  // the recorder: placed like the level meter, on a low-priority stream of its own
+		HIPCHK(lane_after(c->cap.lane, P.ev_front));
+		HIPCHK(launch_capture(c->cap.lane.st, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams, n_blocks,
+				      c->sample_base, c->cap.d_state, c->d_scfg, c->cap.d_stage, c->cap.stage_cap, c->cap.d_cnt, c->cap.d_base,
+				      c->cap.d_hdr[set], c->cap.d_runs[set], c->cap.max_runs, c->cap.d_pool[set], c->cap.max_samples));
+		HIPCHK(lane_written(c->cap.lane, set));
+	}
+	if (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) {
+		HIPCHK(hipStreamWaitEvent(P.cs, P.ev_front, 0));
+		HIPCHK(launch_chains(P.cs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams, n_blocks,
+				     c->sample_base, c->launch, c->d_events[set], c->d_eb[set], c->cfg.flags));
+		if (timing)
+			HIPCHK(hipEventRecord(ev[kEvSerialDone], P.cs));
+		for (hipEvent_t e : P.done)
+			HIPCHK(hipEventRecord(e, P.cs));
+	} else {
+		c->win[set].whb_submit_seq = c->submit_seq++;
+		HIPCHK(launch_pipeline(P, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->d_fmdev[set], c->dec_stride,
+				       c->cfg.n_streams, n_blocks, c->sample_base, c->launch, c->win[set], c->d_ld16[set],
+				       c->d_dev32[set], c->d_events[set], c->d_eb[set], c->cfg.flags));
+	}
+	report_debug_stats(c, set, n_blocks);
+	// the drain's copies, queued now
+	for (hipEvent_t e : P.done)
+		HIPCHK(hipStreamWaitEvent(c->cpy, e, 0));
+	// copied[set] then also says "the set's levels, captures and spectrum records are written" (their reads, and the set's reuse)
+	for (const SideLane *l : { &c->lev.lane, &c->cap.lane, &c->spec.lane })
+		if (l->on)
+			HIPCHK(hipStreamWaitEvent(c->cpy, l->written[set], 0));
+	c->copied_n[set] = std::min<uint32_t>(c->copy_guess, (uint32_t)c->cfg.max_events);
+	{  // header, overflow flag and the first copied_n events in one go
+		static_assert(kEvHeader % 16 == 0 && sizeof(tfrec_amd_event) % 16 == 0, "drain_copy_kernel moves 16 bytes per lane");
+		const size_t bytes = kEvHeader + (size_t)c->copied_n[set] * sizeof(tfrec_amd_event);
+		const size_t n16 = bytes / 16;
+		const unsigned blocks = (unsigned)std::min<size_t>(256, (n16 + 255) / 256);
+		hipLaunchKernelGGL(tfrec::drain_copy_kernel, dim3(blocks), dim3(256), 0, c->cpy, (const uint4 *)c->d_evblock[set],
+				   (uint4 *)c->h_evblock_dev[set], n16);
+		HIPCHK(hipGetLastError());
+	}
+	HIPCHK(hipEventRecord(c->copied[set], c->cpy));
+	if (timing)
+		c->timed = true;
+	if (resets) {
+		for (int32_t r : c->reset_pending) {
+			c->origin[r] = c->sample_base;
+			c->reset_marked[r] = 0;
+		}
+		c->reset_pending.clear();
+	}
+	// (until the first reset the origins are all zero: nothing is recorded, and the drain subtracts nothing)
+	c->any_reset = c->any_reset || resets;
+	if (c->any_reset)
+		c->set_origin[set] = c->origin;
+	c->submitted = true;
+	c->inflight++;
+	c->last_set = set;
+	c->tail_sel ^= 1;
+	c->sample_base += (long long)n_blocks * kBlockDec;
+	c->last_blocks = n_blocks;
+	guard.ok = true;
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_submit_device(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int n_blocks, void *hip_stream)
+{
+	const auto t0 = std::chrono::steady_clock::now();
+	const int rc = submit_common(c, d_iq, stride, n_blocks, hip_stream, false);
+	if (c)
+		c->hp_submit += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+	return rc;
+}
+
+static int submit_host_impl(tfrec_amd_ctx *c, const uint8_t *h_iq, size_t stride, int n_blocks)
+{
+	if (!c || !h_iq || n_blocks < 1 || n_blocks > c->cfg.max_blocks)
+		return TFREC_AMD_E_INVAL;
+	size_t row = 0;
+	TRY(input_bytes(c, n_blocks, &row));
+	if (rows_in_use(c) > 1 && stride < row)
+		return TFREC_AMD_E_INVAL;
+	TRY(check_fifo(c));
+	HIPCHK(hipSetDevice(c->cfg.device));
+	const int set = (c->head + c->inflight) % kSets;  // the set's previous user has been drained: its staging buffer is free
+	const size_t rows = (size_t)rows_in_use(c);  // (a mapped context: only the rows a stream reads are staged and copied)
+	const size_t need = row * rows;
+	if (c->stage_bytes[set] < need) {
+		(void)hipFree(c->d_stage[set]);
+		c->d_stage[set] = nullptr;
+		c->stage_bytes[set] = 0;
+		if (hipMalloc((void **)&c->d_stage[set], need) != hipSuccess)
+			return TFREC_AMD_E_NOMEM;
+		c->stage_bytes[set] = need;
+	}
+	// asynchronous on the front-end stream when h_iq is pinned (tfrec_amd_host_alloc); pageable memory is staged
+	// by the runtime before the call returns
+	HIPCHK(hipMemcpy2DAsync(c->d_stage[set], row, h_iq, stride, row, rows, hipMemcpyHostToDevice, c->pipe[set].fs));
+	return submit_common(c, c->d_stage[set], row, n_blocks, nullptr, true);
+}
+
+int tfrec_amd_submit_host(tfrec_amd_ctx *c, const uint8_t *h_iq, size_t stride, int n_blocks)
+{
+	const auto t0 = std::chrono::steady_clock::now();
+	const int rc = submit_host_impl(c, h_iq, stride, n_blocks);
+	if (c)
+		c->hp_submit += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+	return rc;
+}
+
+int tfrec_amd_input_bytes(tfrec_amd_ctx *c, int n_blocks, size_t *bytes_per_stream)
+{
+	if (!c || !bytes_per_stream)
+		return TFREC_AMD_E_INVAL;
+	return input_bytes(c, n_blocks, bytes_per_stream);
+}
+
+void *tfrec_amd_host_alloc(size_t bytes)
+{
+	void *p = nullptr;
+	if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess)
+		return nullptr;
+	return p;
+}
+
+void tfrec_amd_host_free(void *p)
+{
+	if (p)
+		(void)hipHostFree(p);
+}
+
+int tfrec_amd_sync(tfrec_amd_ctx *c)
+{
+	if (!c)
+		return TFREC_AMD_E_INVAL;
+	HIPCHK(hipSetDevice(c->cfg.device));
+	for (const tfrec_amd_ctx::Owned &o : c->owned)
+		if (o.kind == tfrec_amd_ctx::Owned::kStream)
+			HIPCHK(hipStreamSynchronize(static_cast<hipStream_t>(o.h)));
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_pending_events(tfrec_amd_ctx *c, int *n)
+{
+	if (!c || !n)
+		return TFREC_AMD_E_INVAL;
+	*n = 0;
+	TRY(check_live(c));  // (copied[head] may never have been recorded: synchronising on it would succeed at once)
+	if (c->inflight == 0)
+		return TFREC_AMD_OK;
+	HIPCHK(hipSetDevice(c->cfg.device));
+	HIPCHK(hipEventSynchronize(c->copied[c->head]));  // the oldest submit not yet drained
+	const EventBuf eb = *c->h_eb[c->head];
+	*n = (int)(std::min(eb.count, eb.capacity) - std::min(eb.dead, std::min(eb.count, eb.capacity)));  // (retracted events are not reported)
+	return eb.count > eb.capacity ? TFREC_AMD_E_OVERFLOW : TFREC_AMD_OK;
+}
+
+int tfrec_amd_drain_events(tfrec_amd_ctx *c, tfrec_amd_event *out, int cap, int *n_out)
+{
+	if (!c || !n_out || cap < 0 || (cap > 0 && !out))
+		return TFREC_AMD_E_INVAL;
+	*n_out = 0;
+	TRY(check_live(c));
+	if (c->inflight == 0)
+		return TFREC_AMD_OK;
+	HIPCHK(hipSetDevice(c->cfg.device));
+	const int set = c->head;  // the oldest submit not yet drained; a younger one may still be running
+	const auto hp0 = std::chrono::steady_clock::now();
+	HIPCHK(hipEventSynchronize(c->copied[set]));  // the chains' ends and the copies queued by the submit
+	const auto hp1 = std::chrono::steady_clock::now();
+	const EventBuf eb = *c->h_eb[set];
+	const uint32_t have = std::min(eb.count, eb.capacity);
+	bool overflow = eb.count > eb.capacity;
+	tfrec_amd_event *tmp = c->h_events[set];
+	if (have > c->copied_n[set])  // more events than the submit guessed (not on cp: the copies of younger submits wait there)
+		HIPCHK(hipMemcpy(tmp + c->copied_n[set], c->d_events[set] + c->copied_n[set],
+				 (size_t)(have - c->copied_n[set]) * sizeof(tfrec_amd_event), hipMemcpyDeviceToHost));
+	c->copy_guess = std::max<uint32_t>(c->copy_guess_min, 2 * have);
+	uint32_t live = have;
+	if (eb.dead) {  // a WHB stream's speculative events that the exact kernel replaced (rare): never reported
+		live = 0;
+		for (uint32_t i = 0; i < have; i++)
+			if (tmp[i].status != kStatusDead)
+				tmp[live++] = tmp[i];
+	}
+	if (!c->set_origin[set].empty()) {  // end_sample counts from the stream's last reset: flushes and BITS chunks (window opens) alike
+		const std::vector<long long> &org = c->set_origin[set];
+		for (uint32_t i = 0; i < live; i++)
+			if (tmp[i].stream < org.size())
+				tmp[i].end_sample -= org[tmp[i].stream];
+	}
+	c->head = (c->head + 1) % kSets;
+	c->inflight--;
+	c->last_drained = set;
+	account_fm_log(&c->fm, eb);
+	{
+		int32_t wov = 0;
+		memcpy(&wov, c->h_evblock[set] + kEvOverflowOff, 4);
+		if (wov) {  // cannot happen (cap is the worst case); reported rather than ignored
+			snprintf(g_err, sizeof(g_err), "window table overflow");
+			return TFREC_AMD_E_STATE;
+		}
+	}
+	const auto hp2 = std::chrono::steady_clock::now();
+	// Order: (stream, slot, seq, BITS chunks before their flush, end_sample, offset).  The events of a stream are few:
+	// bucket by stream (counting sort on indices), then order each bucket.
+	auto before = [](const tfrec_amd_event &a, const tfrec_amd_event &b) {
+		if (a.slot != b.slot)
+			return a.slot < b.slot;
+		if (a.seq != b.seq)
+			return a.seq < b.seq;
+		// TFREC_AMD_F_BITS: the bit chunks of a flush come before it, in the order the bits were produced
+		const bool ab = a.status == TFREC_AMD_STATUS_BITS, bb = b.status == TFREC_AMD_STATUS_BITS;
+		if (ab != bb)
+			return ab;
+		if (a.end_sample != b.end_sample)
+			return a.end_sample < b.end_sample;
+		return a.offset < b.offset;
+	};
+	const uint32_t ns = (uint32_t)c->cfg.n_streams;
+	std::vector<uint32_t> &idx = c->sort_idx, &start = c->sort_start;
+	idx.resize(live);
+	start.assign(ns + 1, 0u);
+	for (uint32_t i = 0; i < live; i++)
+		start[std::min(tmp[i].stream, ns - 1) + 1]++;
+	for (uint32_t s = 0; s < ns; s++)
+		start[s + 1] += start[s];
+	{
+		std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+		for (uint32_t i = 0; i < live; i++)
+			idx[fill[std::min(tmp[i].stream, ns - 1)]++] = i;
+	}
+	for (uint32_t s = 0; s < ns; s++)
+		std::sort(idx.begin() + start[s], idx.begin() + start[s + 1],
+			  [&](uint32_t x, uint32_t y) { return before(tmp[x], tmp[y]); });
+	uint32_t ncopy = live;
+	if (ncopy > (uint32_t)cap) {
+		ncopy = (uint32_t)cap;
+		overflow = true;
+	}
+	for (uint32_t i = 0; i < ncopy; i++)
+		out[i] = tmp[idx[i]];
+	*n_out = (int)ncopy;
+	const auto hp3 = std::chrono::steady_clock::now();
+	c->hp_wait += std::chrono::duration<double>(hp1 - hp0).count();
+	c->hp_copy += std::chrono::duration<double>(hp2 - hp1).count();
+	c->hp_sort += std::chrono::duration<double>(hp3 - hp2).count();
+	c->hp_n++;
+	return overflow ? TFREC_AMD_E_OVERFLOW : TFREC_AMD_OK;
+}
