@@ -523,6 +523,54 @@ int tfrec_amd_enable_spectrum(tfrec_amd_ctx *ctx, int32_t n_bins, int32_t frames
 int tfrec_amd_read_spectrum(tfrec_amd_ctx *ctx, int32_t row, uint64_t *sum, uint64_t *peak, size_t cap_records, uint32_t *n_frames,
 			    int *n_records);
 
+/* Occupancy detector (tfrec_amd_enable_occupancy): which bins of a spectrum record hold a signal -- decided on the
+ * device, on the records of the spectrum above while they lie in device memory, so that a caller who only wants to know where the
+ * channels are reads 16 + N / 8 bytes per record instead of 16 N.  It sits on top of the spectrum: tfrec_amd_enable_spectrum comes
+ * first, and records, rows and the cutting rule are the spectrum's, unchanged.  Exact integers only, on a record's sum[k], peak[k]
+ * and n_frames with N = n_bins; no tolerance, no floating point.  No reference counterpart; pinned by tfrec_amd/occupancy.py.
+ *   Parameters: ratio within [2, 4096], rel within [1, 4096].
+ *   Mean:    m[k] = sum[k] / n_frames  (floor division of uint64; < 2^49).
+ *   Floor:   the LOWER MEDIAN of m: with the N values of m sorted ascending, the value at index N / 2 - 1.  A value, not a
+ *            position: ties cannot matter.
+ *   Top:     top = max over k of peak[k].
+ *   Hit:     hit[k] = peak[k] > max(floor, 1) * ratio  AND  peak[k] * rel >= top.  peak < 2^49 and the factors are at most 2^12:
+ *            both products stay below 2^61.  max(floor, 1) keeps a record whose median is 0 from hitting wherever a peak is not 0
+ *            by a factor of 0; in an all-zero record peak = 0 and nothing hits.
+ *   Why two tests: the first finds what stands above the noise; but a strong transmitter's window side lobes and clipping products
+ *            stand above the noise too, across hundreds of kHz, and the middle of that span is not the signal's frequency.  The
+ *            second keeps the bins within 1 / rel of the record's strongest (rel = 16: within 12 dB).  Its price: a weak burst in
+ *            the same RECORD as a much stronger one (more than rel times stronger in peak power) is not seen.  Shorter records
+ *            (frames_per_record) narrow that blind spot in time; a larger rel narrows it in level.
+ *   Outputs per (row, record): one tfrec_amd_occupancy and N / 32 bitmap words: bit (k & 31) of word (k >> 5) is hit[k].  n_hit is
+ *            the number of set bits, n_frames the record's.  top is not stored: 16 bytes keep the struct a power of two, and a caller
+ *            who wants it has peak[] from tfrec_amd_read_spectrum.
+ *   Nothing is carried between submits.  Grouping the hits of a whole recording into channels is host work: tfrec_gpu -A and
+ *            tfrec_amd/occupancy.py: channels() do it; DESIGN.md 6l states the rule.
+ *   Defaults: the library has none.  tfrec_gpu and the Python binding use ratio = 32 (a windowed noise bin's power is close to
+ *            exponentially distributed: P(p > 32 mean) = e^-32 per frame and bin) and rel = 16 (chosen on one synthetic recording);
+ *            neither is a measurement of real recordings.
+ * tfrec_amd_enable_occupancy: allowed only after tfrec_amd_enable_spectrum and before the first submit.  Per FIFO set
+ * (TFREC_AMD_FIFO_DEPTH of them) it allocates max_rows * max_records * (16 + N / 8) bytes of device memory, max_rows, max_records
+ * and N the spectrum's; tfrec_amd_get_memory counts it.  Its one kernel runs on the spectrum's stream, directly behind the
+ * spectrum's kernel: no stream or event of its own.
+ * Errors: a NULL context, ratio or rel outside its range, a context without the spectrum, or a second call: TFREC_AMD_E_INVAL;
+ * after the first submit: TFREC_AMD_E_STATE, as for a poisoned context; TFREC_AMD_E_NOMEM leaves the context exactly as it was before
+ * the call, the spectrum included.  A context on which it was never called launches what it launched before. */
+typedef struct {            /* 16 bytes */
+	uint64_t floor;         /* the lower median of m */
+	uint32_t n_hit;         /* bins hit */
+	uint32_t n_frames;      /* the record's frames (tfrec_amd_read_spectrum's n_frames) */
+} tfrec_amd_occupancy;
+int tfrec_amd_enable_occupancy(tfrec_amd_ctx *ctx, uint32_t ratio, uint32_t rel);
+/* The occupancy records of one input row of the OLDEST undrained submit, with the conventions of tfrec_amd_read_spectrum (waits for
+ * the submit; call it BEFORE tfrec_amd_drain_events pops it; reading pops nothing): recs[r], bitmap[r * (N / 32) + w] for r <
+ * *n_records; cap_records is the room in records.  recs and bitmap may be NULL with cap_records 0 to fetch only *n_records.
+ * Errors: the detector not enabled, a row the submit's spectrum does not cover, n_records NULL: TFREC_AMD_E_INVAL; the room too
+ * small (or a NULL array with records to deliver): TFREC_AMD_E_INVAL, nothing is written, but *n_records is set; nothing undrained
+ * or a poisoned context: TFREC_AMD_E_STATE. */
+int tfrec_amd_read_occupancy(tfrec_amd_ctx *ctx, int32_t row, tfrec_amd_occupancy *recs, uint32_t *bitmap, size_t cap_records,
+			     int *n_records);
+
 /* The dB value the reference demodulator passes to decoder::flush for this slot, computed with the
  * reference's host expressions (tfa1.cpp:180, tfa2.cpp:434, whb.cpp:696) including (int)(10*log10(0)). */
 int tfrec_amd_rssi_db(int slot, int64_t rssi_raw);

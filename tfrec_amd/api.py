@@ -15,6 +15,7 @@ import numpy as np
 from . import _build
 from .capture import RUN_DTYPE  # tfrec_amd_run
 from .levels import LEVEL_DTYPE  # tfrec_amd_level
+from .occupancy import OCC_DTYPE  # tfrec_amd_occupancy
 
 BLOCK_BYTES = 65536
 BLOCK_DEC = 8192
@@ -105,7 +106,7 @@ EXPORTS = (
     "tfrec_amd_create_rate", "tfrec_amd_get_input_rate", "tfrec_amd_input_bytes", "tfrec_amd_resample_taps",
     "tfrec_amd_tune_streams_input", "tfrec_amd_get_stream_tune_input", "tfrec_amd_create_format", "tfrec_amd_get_input_format",
     "tfrec_amd_read_levels", "tfrec_amd_enable_capture", "tfrec_amd_read_captures", "tfrec_amd_enable_spectrum",
-    "tfrec_amd_read_spectrum",
+    "tfrec_amd_read_spectrum", "tfrec_amd_enable_occupancy", "tfrec_amd_read_occupancy",
 )
 
 _libs = {}
@@ -186,6 +187,8 @@ def load_library(build: bool = True, experiments: bool = False):
                                           C.POINTER(C.c_uint64)]
     L.tfrec_amd_enable_spectrum.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     L.tfrec_amd_read_spectrum.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int)]
+    L.tfrec_amd_enable_occupancy.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+    L.tfrec_amd_read_occupancy.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
     L.tfrec_amd_fifo_depth.restype = C.c_int
     if L.tfrec_amd_fifo_depth() != FIFO_DEPTH:
         raise RuntimeError("libtfrec_amd.so was built with FIFO depth %d, this binding expects %d" % (
@@ -527,6 +530,33 @@ class Receiver:
             _check(self.L, self.L.tfrec_amd_read_spectrum(self.h, int(row), s.ctypes.data, p.ctypes.data, nr.value, f.ctypes.data,
                                                           C.byref(nr)))
         return s, p, f
+
+    def enable_occupancy(self, ratio: int = 32, rel: int = 16):
+        """Turn the occupancy detector on (tfrec_amd_enable_occupancy; after enable_spectrum, before the first submit): per
+        spectrum record a noise floor and a bitmap of the bins whose peak stands `ratio` times above it and within 1 / `rel` of the
+        record's strongest (occupancy.py).  read_occupancy returns them."""
+        if not all(0 <= int(v) < 2 ** 32 for v in (ratio, rel)):  # (refused before ctypes could wrap a value)
+            raise TfrecAmdError(E_INVAL, "ratio or rel outside uint32")
+        _check(self.L, self.L.tfrec_amd_enable_occupancy(self.h, int(ratio), int(rel)))
+        self._occupancy = True
+
+    def read_occupancy(self, row: int):
+        """The occupancy records of input row `row` of the OLDEST undrained submit (tfrec_amd_read_occupancy; call it before the
+        drain that pops that submit) -> (records: OCC_DTYPE [n_records], bitmap: uint32 [n_records, N / 32]); occupancy.unpack
+        turns the bitmap into booleans.  TfrecAmdError(E_INVAL) on a context without enable_occupancy or for a row the submit's
+        spectrum does not cover, (E_STATE) when nothing is waiting to be drained."""
+        if not -2 ** 31 <= int(row) < 2 ** 31:
+            raise TfrecAmdError(E_INVAL, "row outside int32")
+        nr = C.c_int(0)
+        rc = self.L.tfrec_amd_read_occupancy(self.h, int(row), None, None, 0, C.byref(nr))  # the count (no room: E_INVAL)
+        n = getattr(self, "_spectrum_bins", 0)
+        if not getattr(self, "_occupancy", False) or n == 0 or rc == E_STATE or (rc == E_INVAL and nr.value == 0):
+            _check(self.L, rc)
+        recs = np.zeros(nr.value, dtype=OCC_DTYPE)
+        bits = np.zeros((nr.value, n // 32), dtype=np.uint32)
+        if nr.value:
+            _check(self.L, self.L.tfrec_amd_read_occupancy(self.h, int(row), recs.ctypes.data, bits.ctypes.data, nr.value, C.byref(nr)))
+        return recs, bits
 
     def stage0(self, stream: int, n_pairs: int) -> np.ndarray:
         """input_10x or input_rate: the 1.536 MS/s int16 IQ the 10:1 or the resampling stage produced for the last submit."""

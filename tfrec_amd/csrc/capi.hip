@@ -51,6 +51,9 @@ hipError_t launch_capture(hipStream_t st, const uint32_t *dec, size_t dec_stride
 			  unsigned long long max_samples);
 hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_rows, long n_in, int n_bins, int g,
 			   size_t max_records, unsigned long long *sum, unsigned long long *peak, uint32_t *nfr);
+hipError_t launch_occupancy(hipStream_t st, int n_rows, long n_in, int n_bins, int g, size_t max_records, const unsigned long long *sum,
+			    const unsigned long long *peak, const uint32_t *nfr, uint32_t ratio, uint32_t rel, tfrec_amd_occupancy *recs,
+			    uint32_t *bits);
 }  // namespace tfrec
 
 using namespace tfrec;
@@ -59,7 +62,7 @@ using namespace tfrec;
 #include "capi_create.h"   // chain parameters, tap tables, the context's buffers, streams and events; constructors, destroy
 #include "capi_probe.h"    // the discriminator's host check, debug statistics; probes, read-backs, timings, memory, counters
 #include "capi_submit.h"   // the two kernels, a submit's resets and staging, submit_common, the submits, drain, sync, pending
-#include "capi_outputs.h"  // the level meter's, the recorder's and the spectrum's entry points
+#include "capi_outputs.h"  // the level meter's, the recorder's, the spectrum's and the occupancy detector's entry points
 #include "capi_streams.h"  // reset, configure, the three tunes, map, and their getters
 
 extern "C" {

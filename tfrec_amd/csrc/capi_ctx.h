@@ -90,6 +90,15 @@ struct SpectrumOut {
 	uint32_t *d_nf[kSets] = {};
 	int set_rows[kSets] = {}, set_records[kSets] = {};
 };
+// tfrec_amd_enable_occupancy: the detector on the spectrum's records.  It runs on the spectrum's lane, behind its
+// kernel (lane: only `on` is used; rows, records and what a set's submit held are the spectrum's); per set the records ([rows]
+// [max_records]) and the bitmap words ([rows][max_records][n / 32])
+struct OccupancyOut {
+	SideLane lane;
+	uint32_t ratio = 0, rel = 0;
+	tfrec_amd_occupancy *d_recs[kSets] = {};
+	uint32_t *d_bits[kSets] = {};
+};
 
 struct tfrec_amd_ctx {
 	tfrec_amd_config cfg;
@@ -128,6 +137,7 @@ struct tfrec_amd_ctx {
 	LevelsOut lev;  // ---- side outputs
 	CaptureOut cap;
 	SpectrumOut spec;
+	OccupancyOut occ;
 	int wmax = 0;
 	// tfrec_amd_configure_streams: every stream's settings as the next submit uses them (scfg, the host's copy), their device
 	// copy as the last submit used them (d_scfg: written only by stream_reset_kernel, in the entries of its list), and the
@@ -355,7 +365,7 @@ static void release_all(tfrec_amd_ctx *c)
 	}
 }
 
-// An enable call (tfrec_amd_enable_capture, _spectrum) that fails half way leaves the context as it was before the call: what it
+// An enable call (tfrec_amd_enable_capture, _spectrum, _occupancy) that fails half way leaves the context as it was before the call: what it
 // made is given back, the byte counts of tfrec_amd_get_memory are restored and the feature's members are reset as a whole.
 template <class Feature>
 struct EnableGuard {

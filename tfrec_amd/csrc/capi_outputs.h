@@ -201,3 +201,57 @@ int tfrec_amd_read_spectrum(tfrec_amd_ctx *c, int32_t row, uint64_t *sum, uint64
 	HIPCHK(hipMemcpy(n_frames, o.d_nf[set] + r0, nr * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	return TFREC_AMD_OK;
 }
+
+int tfrec_amd_enable_occupancy(tfrec_amd_ctx *c, uint32_t ratio, uint32_t rel)
+{
+	if (!c)
+		return TFREC_AMD_E_INVAL;
+	if (ratio < 2 || ratio > 4096 || rel < 1 || rel > 4096) {
+		snprintf(g_err, sizeof(g_err), "ratio within [2, 4096], rel within [1, 4096]");
+		return TFREC_AMD_E_INVAL;
+	}
+	if (!c->spec.lane.on) {
+		snprintf(g_err, sizeof(g_err), "the occupancy detector works on the spectrum: call tfrec_amd_enable_spectrum first");
+		return TFREC_AMD_E_INVAL;
+	}
+	TRY(begin_side_enable(c, c->occ.lane, "occupancy detector"));
+	HIPCHK(hipSetDevice(c->cfg.device));
+	EnableGuard<OccupancyOut> guard(c, c->occ);  // (the spectrum's members are not its to reset)
+	OccupancyOut &o = c->occ;
+	const size_t records = (size_t)c->spec.rows * c->spec.max_records;
+	for (int k = 0; k < kSets; k++) {
+		TRY(own_device(c, o.d_recs[k], records * sizeof(tfrec_amd_occupancy)));
+		TRY(own_device(c, o.d_bits[k], records * (size_t)(c->spec.n / 32) * sizeof(uint32_t)));
+	}
+	o.ratio = ratio;
+	o.rel = rel;
+	o.lane.on = guard.ok = true;
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_read_occupancy(tfrec_amd_ctx *c, int32_t row, tfrec_amd_occupancy *recs, uint32_t *bitmap, size_t cap_records, int *n_records)
+{
+	if (!c || !n_records)
+		return TFREC_AMD_E_INVAL;
+	int set = 0;
+	TRY(begin_side_read(c, c->occ.lane, "occupancy detector", "call tfrec_amd_enable_occupancy before the first submit", &set));
+	const SpectrumOut &sp = c->spec;
+	if (row < 0 || row >= sp.set_rows[set]) {
+		snprintf(g_err, sizeof(g_err), "row %d: the submit's spectrum covers rows [0, %d)", (int)row, sp.set_rows[set]);
+		return TFREC_AMD_E_INVAL;
+	}
+	const size_t nr = (size_t)sp.set_records[set], words = (size_t)(sp.n / 32);
+	*n_records = (int)nr;
+	if (cap_records < nr || (nr > 0 && (!recs || !bitmap))) {
+		snprintf(g_err, sizeof(g_err), "room for %zu occupancy records, the submit has %zu", cap_records, nr);
+		return TFREC_AMD_E_INVAL;
+	}
+	if (nr == 0)
+		return TFREC_AMD_OK;
+	HIPCHK(hipSetDevice(c->cfg.device));
+	HIPCHK(hipEventSynchronize(c->copied[set]));  // (behind the spectrum lane's written[set], recorded behind the detector's kernel)
+	const size_t r0 = (size_t)row * sp.max_records;
+	HIPCHK(hipMemcpy(recs, c->occ.d_recs[set] + r0, nr * sizeof(tfrec_amd_occupancy), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(bitmap, c->occ.d_bits[set] + r0 * words, nr * words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	return TFREC_AMD_OK;
+}

@@ -242,6 +242,9 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		const long n_in = (long)(row_bytes / fmt_sample_bytes(c->fmt));
 		HIPCHK(launch_spectrum(c->spec.lane.st, c->fmt, (const uint8_t *)d_iq, stride, rows, n_in, c->spec.n, c->spec.g, c->spec.max_records,
 				       c->spec.d_sum[set], c->spec.d_peak[set], c->spec.d_nf[set]));
+		if (c->occ.lane.on)  // the occupancy detector: on the records just queued, in stream order behind their kernel
+			HIPCHK(launch_occupancy(c->spec.lane.st, rows, n_in, c->spec.n, c->spec.g, c->spec.max_records, c->spec.d_sum[set],
+						c->spec.d_peak[set], c->spec.d_nf[set], c->occ.ratio, c->occ.rel, c->occ.d_recs[set], c->occ.d_bits[set]));
 		HIPCHK(lane_written(c->spec.lane, set));
 		c->spec.set_rows[set] = rows;
 		c->spec.set_records[set] = (int)((n_in / c->spec.n + c->spec.g - 1) / c->spec.g);

@@ -848,5 +848,6 @@ hipError_t launch_fmdev(hipStream_t st, const uint32_t *dec, size_t dec_stride, 
 #include "levels.h"    // level_sum_kernel, level_trig_kernel, launch_levels
 #include "capture.h"   // capture_scan_kernel, capture_offsets_kernel, capture_copy_kernel, launch_capture
 #include "spectrum.h"  // spectrum_kernel, launch_spectrum
+#include "occupancy.h"  // occupancy_kernel, launch_occupancy
 
 }  // namespace tfrec

@@ -82,6 +82,50 @@ void pipe_sink::flush()
 	pending.clear();
 }
 
+// floor(a / b) for b > 0
+static long long floor_div(long long a, long long b) { return a / b - (a % b < 0 ? 1 : 0); }
+
+std::vector<occ_channel> occupancy_channels(const std::vector<unsigned long long> &hits, unsigned long long records, int n_bins, long fs_in,
+					    long center_khz, long join_hz)
+{
+	struct item {
+		long long pos;  // twice the middle bin: the order of the list
+		occ_channel c;
+	};
+	std::vector<item> items;
+	int group = -1;  // index of the open group in items
+	for (int b = -n_bins / 2; b < n_bins / 2; b++) {
+		const unsigned long long h = hits[(size_t)(b < 0 ? b + n_bins : b)];
+		if (h < 1)
+			continue;
+		if (2 * h > records) {  // continuous, like a receiver's DC spike: listed, never scanned, and no part of a group
+			const long off = (long)floor_div(2LL * b * fs_in + 1000LL * n_bins, 2000LL * n_bins);
+			items.push_back(item{ 2LL * b, occ_channel{ true, center_khz + off, b, b, h, false } });
+			continue;
+		}
+		if (group >= 0 && (long long)(b - items[group].c.hi - 1) * fs_in <= (long long)join_hz * n_bins) {
+			items[group].c.hi = b;
+			items[group].c.hits = std::max(items[group].c.hits, h);
+			continue;
+		}
+		group = (int)items.size();
+		items.push_back(item{ 0, occ_channel{ false, 0, b, b, h, false } });
+	}
+	for (item &it : items) {
+		if (it.c.carrier)
+			continue;
+		const long off = (long)floor_div((long long)(it.c.lo + it.c.hi) * fs_in + 1000LL * n_bins, 2000LL * n_bins);
+		it.pos = it.c.lo + it.c.hi;
+		it.c.khz = center_khz + off;
+		it.c.in_range = 2000LL * (off < 0 ? -off : off) <= (long long)fs_in - 384000;
+	}
+	std::stable_sort(items.begin(), items.end(), [](const item &a, const item &b) { return a.pos < b.pos; });
+	std::vector<occ_channel> out;
+	for (const item &it : items)
+		out.push_back(it.c);
+	return out;
+}
+
 void gpu_engine::set_rate(int p, int q)
 {
 	rate_p = p;
@@ -225,6 +269,8 @@ struct capture_batch {
 	std::vector<int16_t> pool;
 	std::vector<uint64_t> spec_sum, spec_peak;
 	std::vector<uint32_t> spec_frames;
+	std::vector<tfrec_amd_occupancy> occ_recs;  // -A: the detector's records of row 0 and their bitmap words, [record][N / 32]
+	std::vector<uint32_t> occ_bits;
 };
 
 struct device_worker {
@@ -249,11 +295,12 @@ struct device_worker {
 	std::deque<std::vector<tfrec_amd_level> > out_levels;  // -s: their level records, [stream][the batch's blocks]
 	bool capture;  // -S: the contexts record (tfrec_amd_enable_capture)
 	int spec_n, spec_g;  // -P: bins and frames per record of the spectrum of row 0 (tfrec_amd_enable_spectrum); 0: none
+	int occ_ratio, occ_rel;  // -A: the occupancy detector on it (tfrec_amd_enable_occupancy); 0: none
 	std::deque<capture_batch> out_caps;  // -S: their runs (stream = the file's index in the job) and sample pool
 	bool done;
 	std::thread th;
 
-	device_worker() : files(NULL), s0(0), s1(0), device(0), types(0), thresh(0), filter(0), bps(1), flags(0), nslots(0), file_blocks(NULL), wide(false), share(false), rate_p(1), rate_q(1), fmt(TFREC_AMD_FMT_U8), block_bytes(TFREC_AMD_BLOCK_BYTES), unit(1), rc(0), abort(NULL), capture(false), spec_n(0), spec_g(0), done(false) {}
+	device_worker() : files(NULL), s0(0), s1(0), device(0), types(0), thresh(0), filter(0), bps(1), flags(0), nslots(0), file_blocks(NULL), wide(false), share(false), rate_p(1), rate_q(1), fmt(TFREC_AMD_FMT_U8), block_bytes(TFREC_AMD_BLOCK_BYTES), unit(1), rc(0), abort(NULL), capture(false), spec_n(0), spec_g(0), occ_ratio(0), occ_rel(0), done(false) {}
 
 	void push(std::vector<tfrec_amd_event> &&ev, std::vector<tfrec_amd_level> &&lv, capture_batch &&cb)
 	{
@@ -375,6 +422,14 @@ struct device_worker {
 			r = tfrec_amd_enable_spectrum(ctx, spec_n, spec_g, 1);
 			if (r) {
 				fprintf(stderr, "tfrec_amd_enable_spectrum (device %d): %s (%s)\n", device, tfrec_amd_strerror(r), tfrec_amd_last_error());
+				tfrec_amd_destroy(ctx);
+				return r;
+			}
+		}
+		if (spec_n && occ_ratio) {  // -A: the detector on its records
+			r = tfrec_amd_enable_occupancy(ctx, (uint32_t)occ_ratio, (uint32_t)occ_rel);
+			if (r) {
+				fprintf(stderr, "tfrec_amd_enable_occupancy (device %d): %s (%s)\n", device, tfrec_amd_strerror(r), tfrec_amd_last_error());
 				tfrec_amd_destroy(ctx);
 				return r;
 			}
@@ -529,7 +584,17 @@ struct device_worker {
 				}
 				cb.runs.resize(kept);
 			}
-			if (spec_n) {  // -P: the batch's spectrum records, before the drain pops it
+			if (spec_n && occ_ratio) {  // -A: the detector's records in place of the spectrum's, 16 + N / 8 bytes each
+				int nr = 0;
+				r = tfrec_amd_read_occupancy(ctx, 0, NULL, NULL, 0, &nr);  // (the count: E_INVAL for want of room)
+				if (r == TFREC_AMD_E_INVAL && nr > 0) {
+					cb.occ_recs.resize((size_t)nr);
+					cb.occ_bits.resize((size_t)nr * (spec_n / 32));
+					r = tfrec_amd_read_occupancy(ctx, 0, cb.occ_recs.data(), cb.occ_bits.data(), (size_t)nr, &nr);
+				}
+				if (r)
+					break;
+			} else if (spec_n) {  // -P: the batch's spectrum records, before the drain pops it
 				int nr = 0;
 				r = tfrec_amd_read_spectrum(ctx, 0, NULL, NULL, 0, NULL, &nr);  // (the count: E_INVAL for want of room)
 				if (r == TFREC_AMD_E_INVAL && nr > 0) {
@@ -642,6 +707,9 @@ int gpu_engine::run()
 			fprintf(stderr, "spec bin %.3f kHz\n", spec_khz[k]);
 		}
 	}
+	const bool occ = spectrum && occ_ratio;  // -A, pass 1
+	if (occ)
+		fprintf(stderr, "occ: ratio %d, rel %d, join %ld Hz\n", occ_ratio, occ_rel, occ_join);
 	if (scan) {  // -s: the channel list, before a device is opened
 		fprintf(stderr, "scan: %zu channels, input rate %ld S/s\n", n, fs_in);
 		for (size_t s = 0; s < n; s++) {
@@ -673,6 +741,8 @@ int gpu_engine::run()
 		w.capture = capture;
 		w.spec_n = spectrum ? spec_n : 0;
 		w.spec_g = spec_g;
+		w.occ_ratio = spectrum ? occ_ratio : 0;
+		w.occ_rel = occ_rel;
 		w.wide = wide;
 		w.share = slots <= 0;
 		w.rate_p = rate_p;
@@ -715,6 +785,10 @@ int gpu_engine::run()
 	std::vector<uint64_t> spec_peak(spectrum ? spec_n : 0, 0), rec_sum, rec_peak;
 	std::vector<uint32_t> rec_frames;
 	unsigned long long spec_frames = 0;
+	// -A: per bin the records of the file in which it was hit, the records, the file's blocks the batches so far held
+	std::vector<unsigned long long> occ_hits(occ ? spec_n : 0, 0);
+	unsigned long long occ_records = 0, occ_blocks = 0;
+	occ_found.clear();
 	for (size_t k = 0; k < n_batches && rc == 0; k++) {
 		for (size_t d = 0; d < nd && rc == 0; d++) {
 			if (k >= workers[d].plan.size())
@@ -751,6 +825,24 @@ int gpu_engine::run()
 					spec_total[b] += cb.spec_sum[q * spec_n + b];
 					spec_peak[b] = std::max(spec_peak[b], cb.spec_peak[q * spec_n + b]);
 				}
+			}
+			if (occ) {  // no replay: the channel list is the product
+				// the file's samples in this batch: a record that begins behind them lies in the padding and is not the file's
+				const unsigned long long nb = workers[d].plan[k].nb;
+				const unsigned long long real = std::min<unsigned long long>(nb, file_blocks[0] - std::min<unsigned long long>(file_blocks[0], occ_blocks));
+				const unsigned long long real_samples = wide ? real * 327680ull : real * 32768ull * rate_p / rate_q;
+				occ_blocks += nb;
+				for (size_t q = 0; q < cb.occ_recs.size(); q++) {
+					if ((unsigned long long)q * spec_g * spec_n >= real_samples)
+						break;
+					if (dbg > 0)
+						printf("occ-rec %llu floor=%llu hits=%u frames=%u\n", occ_records, (unsigned long long)cb.occ_recs[q].floor,
+						       (unsigned)cb.occ_recs[q].n_hit, (unsigned)cb.occ_recs[q].n_frames);
+					occ_records++;
+					for (int b = 0; b < spec_n; b++)
+						occ_hits[b] += (cb.occ_bits[q * (spec_n / 32) + (b >> 5)] >> (b & 31)) & 1u;
+				}
+				continue;
 			}
 			if (spectrum && dbg > 0) {
 				rec_sum.insert(rec_sum.end(), cb.spec_sum.begin(), cb.spec_sum.end());
@@ -825,7 +917,23 @@ int gpu_engine::run()
 			for (size_t k2 = 0; k2 < decs[s].size(); k2++)
 				if (decs[s][k2])
 					decs[s][k2]->flush_storage();
-	if (spectrum && !rc) {  // -P: behind the telegram output
+	if (occ && !rc) {  // -A: the channel list
+		const std::vector<occ_channel> ch = occupancy_channels(occ_hits, occ_records, spec_n, fs_in, spec_center, occ_join);
+		for (const occ_channel &c : ch) {
+			if (c.carrier) {
+				printf("carrier %ld hits=%llu/%llu\n", c.khz, c.hits, occ_records);
+				continue;
+			}
+			printf("found %ld bins=%d..%d hits=%llu/%llu%s\n", c.khz, c.lo, c.hi, c.hits, occ_records, c.in_range ? "" : " out-of-range");
+			if (c.in_range)
+				occ_found.push_back(c.khz);
+		}
+		if (occ_found.size() > 4096) {
+			fprintf(stderr, "tfrec_gpu: -A found %zu channels, at most 4096 are scanned at once\n", occ_found.size());
+			rc = TFREC_AMD_E_INVAL;
+		}
+	}
+	if (spectrum && !occ && !rc) {  // -P: behind the telegram output
 		for (size_t q = 0; q < rec_frames.size(); q++)
 			for (int k : spec_order)
 				printf("spec-rec %zu %.3f sum=%llu peak=%llu frames=%u\n", q, spec_khz[k], (unsigned long long)rec_sum[q * spec_n + k],

@@ -90,6 +90,20 @@ struct file_settings {
 	bool operator!=(const file_settings &o) const { return !(*this == o); }
 };
 
+// -A: one line of the channel list: a carrier (one bin, listed, never scanned) or a group of active bins lo .. hi (signed bins: b = k
+// for k < N/2, else k - N); hits: the carrier's, or the largest of the group's bins
+struct occ_channel {
+	bool carrier;
+	long khz;
+	int lo, hi;
+	unsigned long long hits;
+	bool in_range;  // a group the scan can reach: |khz - center| * 1000 <= fs_in / 2 - 192000
+};
+// Group the hit counts of a recording into channels (tfrec_amd/occupancy.py: channels()), exact integers: hits[k] of
+// `records` records, bin k; ascending frequency.
+std::vector<occ_channel> occupancy_channels(const std::vector<unsigned long long> &hits, unsigned long long records, int n_bins, long fs_in,
+					    long center_khz, long join_hz);
+
 class gpu_engine {
 public:
 	// types: -T bit mask; thresh: -t; filter: -W; dbg: -1 quiet, 0 normal, >=1 debug (main.cpp:97).
@@ -162,6 +176,22 @@ public:
 		spec_g = frames_per_record;
 		spec_center = center_khz;
 	}
+	// -A, pass 1: with set_spectrum, the occupancy detector on the file's spectrum records
+	// (tfrec_amd_enable_occupancy: ratio, rel).  run() reads the detector's records instead of the spectrum's, replays no telegram
+	// and prints no spectrum table: it counts, per bin, the records of the file in which the bin was hit (a record that begins
+	// behind the file's end, in the padding of its last batch, is not counted), groups them (occupancy_channels, join_hz) and
+	// prints, in ascending frequency,
+	//   found <kHz> bins=<lo>..<hi> hits=<max in group>/<records>[ out-of-range]
+	//   carrier <kHz> hits=<h>/<records>
+	// preceded, with dbg > 0, by "occ-rec <record> floor=<..> hits=<n_hit> frames=<..>" per record.  found_khz() then lists the
+	// channels a scan can reach, ascending.
+	void set_occupancy(int ratio, int rel, long join_hz)
+	{
+		occ_ratio = ratio;
+		occ_rel = rel;
+		occ_join = join_hz;
+	}
+	const std::vector<long> &found_khz() const { return occ_found; }
 	// returns 0 on success, a TFREC_AMD_E_* code otherwise
 	int run();
 	// decoders of stream s in slot order (NULL for slots not registered)
@@ -192,6 +222,9 @@ private:
 	bool spectrum = false;     // set_spectrum
 	int spec_n = 0, spec_g = 0;
 	long spec_center = 0;
+	int occ_ratio = 0, occ_rel = 0;  // set_occupancy (0: none)
+	long occ_join = 0;
+	std::vector<long> occ_found;
 };
 
 #endif

@@ -4,6 +4,8 @@
 //             [-n streams] [-e handler | -E handler] [-m mode] [-p settings] -L dump.iq [[-p settings] -L more.iq ...]
 //   tfrec_gpu [receiver flags as above] [-c kHz] [-x | -r Hz] [-F format] [-D] -P bins[,frames_per_record] -L dump.iq
 //   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-c kHz] [-x | -r Hz] [-F format] [-D] [-d device] [-b blocks] -s step_kHz -L dump.iq
+//   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-c kHz] [-x | -r Hz] [-F format] [-D] [-d device] [-b blocks] [-P bins[,frames]]
+//             -A [ratio[,rel[,join_kHz]]] -L dump.iq
 //   tfrec_gpu [-T hexmask] -X telegrams.txt
 //
 // Flags keep the reference's meaning (main.cpp:63-88, 107-164): -T sensor type bit mask (hex), -t trigger
@@ -63,6 +65,18 @@
 // and with -D, ahead of that table, "spec-rec <record> <kHz> sum=<..> peak=<..> frames=<..>" per record and bin; bin k lies at
 // c + (k < N/2 ? k : k - N) fs_in / N.  stderr lists the bins before a device is opened.  Not with -s, -n, -p, -X, several -L or
 // several devices.
+// -A [ratio[,rel[,join_kHz]]] (not in the reference): find the occupied channels of ONE recording, then scan exactly those (DESIGN.md
+// 6l).  Pass 1 runs the file as one stream with the spectrum (256 bins unless -P bins[,frames] is given too; a record is the frames of
+// one block's input, as -P's default) and the occupancy detector on the GPU (tfrec_amd_enable_occupancy: ratio 2 .. 4096, default 32;
+// rel 1 .. 4096, default 16), counts per bin the records in which it was hit and groups the bins: a bin hit in more than half of the
+// records is a carrier (continuous, like the RTL-SDR's DC spike), the others form a channel with their neighbours while the empty gap
+// between them is at most join_kHz (0 .. 100000, default 50) wide.  stdout carries, in ascending frequency,
+//   found <kHz> bins=<lo>..<hi> hits=<max in group>/<records>[ out-of-range]      (signed bins: k, or k - N from N/2 on)
+//   carrier <kHz> hits=<h>/<records>
+// (-D: per record "occ-rec <record> floor=<..> hits=<..> frames=<..>" ahead of them), where out-of-range marks a channel closer than
+// 192 kHz to the recording's edge, which -s would not scan either.  Pass 2 is -s on the found channels: its "scan ..." lines.  No
+// channel found: no scan.  Both passes run in this process, one after the other.  stderr lists the bins before a device is opened, as
+// -P does.  Not with -s, -n, -p, -f, -e / -E, -X, -S, several -L or several devices.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -183,9 +197,37 @@ int main(int argc, char **argv)
 	const char *cap_prefix = NULL;  // -S
 	int spec_bins = 0, spec_g = 0;  // -P (spec_g 0: the default)
 	bool have_spec_p = false;
+	bool have_auto = false;  // -A
+	long auto_ratio = 32, auto_rel = 16, auto_join = 50;  // (join: kHz)
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:P:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:P:A::h")) != -1) {
 		switch (c) {
+		case 'A': {
+			// the argument is optional: attached (-A32,16), or the next word where that starts with a digit
+			const char *a = optarg;
+			if (!a && optind < argc && argv[optind][0] >= '0' && argv[optind][0] <= '9')
+				a = argv[optind++];
+			have_auto = true;
+			long *field[3] = { &auto_ratio, &auto_rel, &auto_join };
+			const long lo[3] = { 2, 1, 0 }, hi[3] = { 4096, 4096, 100000 };
+			bool ok = true;
+			for (int i = 0; a && ok; i++) {
+				char *end = NULL;
+				const long v = strtol(a, &end, 10);
+				ok = i < 3 && end != a && (*end == ',' || !*end) && v >= lo[i] && v <= hi[i];
+				if (ok)
+					*field[i] = v;
+				a = ok && *end == ',' ? end + 1 : NULL;
+				if (ok && *end == ',' && !end[1])
+					ok = false;  // (a trailing comma)
+			}
+			if (!ok) {
+				fprintf(stderr, "tfrec_gpu: bad -A '%s': want [ratio[,rel[,join_kHz]]], ratio within 2 .. 4096, rel within 1 .. 4096, "
+						"join_kHz within 0 .. 100000\n", optarg ? optarg : argv[optind - 1]);
+				return 1;
+			}
+			break;
+		}
 		case 'P': {
 			char *end = NULL;
 			const long nb = strtol(optarg, &end, 10);
@@ -287,7 +329,9 @@ int main(int argc, char **argv)
 		case 'E': exec = optarg; batched = true; break;
 		case 'm': mode = atoi(optarg); break;
 		default:
-			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -X hexfile\n"
+			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
+					"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
+					"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
 					"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
 					"  -P bins[,G] power spectrum of one dump beside its decoding: bins = 64 .. 1024 (a power of two), G frames per record; a\n"
 					"              line per bin behind the telegrams (-D: per record too)\n"
@@ -316,6 +360,11 @@ int main(int argc, char **argv)
 	}
 	if (have_spec_p && (have_scan || have_slots || have_spec || hexfile || dumps.size() > 1 || devices.size() > 1)) {
 		fprintf(stderr, "tfrec_gpu: -P takes the spectrum of one -L file on one device: not with -s, -n, -p, -X, several -L or several -d\n");
+		return 1;
+	}
+	if (have_auto && (have_scan || have_slots || have_spec || freq >= 0 || exec || hexfile || cap_prefix || dumps.size() > 1 || devices.size() > 1)) {
+		fprintf(stderr, "tfrec_gpu: -A finds and scans the channels of one -L file on one device: not with -s, -n, -p, -f, -e, -E, -X, -S, "
+				"several -L or several -d\n");
 		return 1;
 	}
 	if (cap_prefix && hexfile) {
@@ -426,6 +475,41 @@ int main(int argc, char **argv)
 			per_file.push_back(file_settings{ p.types >= 0 ? p.types : types, p.thresh >= 0 ? p.thresh : thresh,
 							  p.filter >= 0 ? p.filter : filter, tunes[i] });
 		}
+	const long per_block = wide ? 327680L : 32768L * rate_p / rate_q;  // a block's input samples: the default record of -P and -A
+	if (have_auto) {
+		// pass 1: the file as one stream with the spectrum and the detector
+		const int n_bins = have_spec_p ? spec_bins : 256;
+		{
+			gpu_engine e1(dumps, types, thresh, filter, dbg, devices, blocks);
+			e1.set_wide(wide);
+			if (rate_p != 1 || rate_q != 1)
+				e1.set_rate(rate_p, rate_q);
+			e1.set_format(format);
+			e1.set_spectrum(n_bins, spec_g ? spec_g : (int)std::max(1L, per_block / n_bins), center);
+			e1.set_occupancy((int)auto_ratio, (int)auto_rel, auto_join * 1000);
+			const int rc1 = e1.run();
+			fflush(stdout);
+			if (rc1)
+				return 2;
+			scan_khz = e1.found_khz();
+		}
+		if (scan_khz.empty())
+			return 0;
+		// pass 2: the scan, on exactly those (each within the scan's own range, so within what can be tuned)
+		const std::string path = dumps[0];
+		dumps.clear();
+		per_file.clear();
+		for (long khz : scan_khz) {
+			if (khz <= 0) {
+				fprintf(stderr, "tfrec_gpu: -A: channel %ld kHz below zero: -c %ld is not the recording's frequency\n", khz, center);
+				return 1;
+			}
+			dumps.push_back(path);
+			per_file.push_back(file_settings{ types, thresh, filter, (int)((khz - center) * 1000) });
+		}
+		have_scan = true;
+		have_spec_p = false;
+	}
 	gpu_engine e(dumps, types, thresh, filter, dbg, devices, blocks, per_file);
 	if (exec || mode)
 		e.set_handler(exec, batched, mode);
@@ -440,7 +524,6 @@ int main(int argc, char **argv)
 	if (cap_prefix)
 		e.set_capture(cap_prefix);
 	if (have_spec_p) {  // the default record: the frames one block's input holds
-		const long per_block = wide ? 327680L : 32768L * rate_p / rate_q;
 		e.set_spectrum(spec_bins, spec_g ? spec_g : (int)std::max(1L, per_block / spec_bins), center);
 	}
 	int rc = e.run();
