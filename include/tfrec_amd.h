@@ -361,6 +361,53 @@ enum { TFREC_AMD_FMT_U8 = 0, TFREC_AMD_FMT_S8 = 1, TFREC_AMD_FMT_S16 = 2, TFREC_
 int tfrec_amd_create_format(const tfrec_amd_config *cfg, int32_t format, int32_t rate_p, int32_t rate_q, tfrec_amd_ctx **out);
 /* The context's input format (TFREC_AMD_FMT_U8 for every context of the older constructors). */
 int tfrec_amd_get_input_format(tfrec_amd_ctx *ctx, int32_t *format);
+/* DC blocker: a context that removes each input ROW's DC offset -- the constant a zero-IF front end adds to I and to
+ * Q -- ahead of everything else.  It belongs to an input row, as the spectrum does, not to a stream: a row is corrected once, however
+ * many streams read it.  It acts on x, the int16 value every format maps a stored component to (tfrec_amd_create_format), at the
+ * context's input rate, ahead of the input-rate tune, the resampling stage, tfrec_amd_tune_streams and process_iq.  Exact integers:
+ *   Windows.  L = 512 complex input samples; window w of a row covers its samples [512 w, 512 (w + 1)), counted from the row's first
+ *     submit or its last DC reset.  Every permitted submit holds n_in = n_blocks * 32768 * P / Q samples, a multiple of 512: with
+ *     Q = 2^a * o, o odd and 2^a <= 64, n_blocks is a multiple of o and 32768 / 2^a >= 512 is one of 512.  So no window straddles a
+ *     submit, and results do not depend on how a row is cut into submits.
+ *   Sums.  S_I[w], S_Q[w] = the window's sums of x_I and x_Q (|S| <= 2^22).
+ *   Estimate.  K = avg_windows, 1 <= K <= 4096; lo = max(0, w - K + 1), c = w - lo + 1, A = S[lo] + ... + S[w] per rail (window w's
+ *     own sum included: a row's first window is already corrected), and
+ *         d[w] = floor((2 A + 512 c) / (1024 c))
+ *     in 64-bit integers -- floor, not C's truncation, for a negative numerator: the mean of the last c windows rounded half up.
+ *     |2 A| < 2^36 and -8192 <= d <= 8191.
+ *   Apply.  x' = clamp(x - d[w], -8192, 8191) per rail.  Everything downstream is the text above applied to x'; its no-wrap arguments
+ *     hold because |x'| <= 8192.  The pre-stage's history after a stream restart stays x = 0.
+ *   State.  Per row the last K window sums and the window count, carried from submit to submit.  A stream restart (reset, configure,
+ *     tune, map, input tune) does not touch it; tfrec_amd_reset_dc_rows clears it at the next submit; a row that a submit does not
+ *     provide (rows at or beyond the submit's rows in use) keeps it.
+ * tfrec_amd_create_dc: `format` is any of the four, the rate 1/1 or any rate tfrec_amd_create_rate accepts; max_rows within
+ * [1, n_streams] is the most input rows a submit may use (n_streams, or 1 + the highest row mapped): a submit that uses more returns
+ * TFREC_AMD_E_INVAL and queues nothing.  TFREC_AMD_F_INPUT_10X is refused with TFREC_AMD_E_INVAL (no DC removal ahead of the 10:1
+ * stage), as are avg_windows or max_rows outside their ranges, an unknown format and a rate the older constructors refuse.  The
+ * context is a format context in every other respect: tfrec_amd_get_input_format, tfrec_amd_input_bytes, the submits and the
+ * spectrum (which keeps reading the caller's raw rows: it shows the offset) see the caller's format; reset, configure, the tunes,
+ * map, levels, capture, spectrum, occupancy, both layouts, _SERIAL_CHAINS, _BITS, _ALL_FLUSHES and _TIMING work; and
+ * tfrec_amd_read_stage0 returns the stage-0 samples of the CORRECTED input.  Memory (all in tfrec_amd_get_memory): per FIFO set the
+ * corrected rows, max_rows * n_max * 4 bytes (n_max: the largest submit's samples per row), and the table of d, 4 bytes per window;
+ * per context the ring of sums (max_rows * K * 8 bytes), a submit's sums and the counts.  Pinned by tfrec_amd/dcblock.py.
+ * Contexts of the older constructors launch what they launched before. */
+int tfrec_amd_create_dc(const tfrec_amd_config *cfg, int32_t format, int32_t rate_p, int32_t rate_q, int32_t avg_windows, int32_t max_rows,
+			tfrec_amd_ctx **out);
+/* avg_windows and max_rows of a tfrec_amd_create_dc context; 0 and 0 on every other context. */
+int tfrec_amd_get_dc(tfrec_amd_ctx *ctx, int32_t *avg_windows, int32_t *max_rows);
+/* d[w] of one input row of the OLDEST undrained submit, with the conventions of tfrec_amd_read_levels (waits for the submit; call it
+ * BEFORE tfrec_amd_drain_events pops it; reading pops nothing): d[2 * w] = the I rail's and d[2 * w + 1] = the Q rail's value of the
+ * submit's window w, for w < *n_windows = n_in / 512; cap_windows is the room in windows.  d may be NULL with cap_windows 0 to fetch
+ * only *n_windows.
+ * Errors: not a tfrec_amd_create_dc context, a row the submit did not use, n_windows NULL: TFREC_AMD_E_INVAL; the room too small
+ * (or d NULL): TFREC_AMD_E_INVAL, nothing is written, but *n_windows is set; nothing undrained or a poisoned context:
+ * TFREC_AMD_E_STATE. */
+int tfrec_amd_read_dc(tfrec_amd_ctx *ctx, int32_t row, int16_t *d, size_t cap_windows, int *n_windows);
+/* Clear the DC state of the listed rows (each within [0, max_rows); duplicates allowed; n == 0: nothing) at the NEXT submit: their
+ * window count restarts at 0 there.  Submits already queued are not affected; the streams that read the rows are not restarted.
+ * Errors as tfrec_amd_reset_streams: a NULL list with n > 0, n < 0, a row out of range or a context without the blocker:
+ * TFREC_AMD_E_INVAL, and nothing is marked; a poisoned context: TFREC_AMD_E_STATE. */
+int tfrec_amd_reset_dc_rows(tfrec_amd_ctx *ctx, const int32_t *rows, int n);
 
 /* Wait for submitted work. */
 int tfrec_amd_sync(tfrec_amd_ctx *ctx);

@@ -106,7 +106,8 @@ EXPORTS = (
     "tfrec_amd_create_rate", "tfrec_amd_get_input_rate", "tfrec_amd_input_bytes", "tfrec_amd_resample_taps",
     "tfrec_amd_tune_streams_input", "tfrec_amd_get_stream_tune_input", "tfrec_amd_create_format", "tfrec_amd_get_input_format",
     "tfrec_amd_read_levels", "tfrec_amd_enable_capture", "tfrec_amd_read_captures", "tfrec_amd_enable_spectrum",
-    "tfrec_amd_read_spectrum", "tfrec_amd_enable_occupancy", "tfrec_amd_read_occupancy",
+    "tfrec_amd_read_spectrum", "tfrec_amd_enable_occupancy", "tfrec_amd_read_occupancy", "tfrec_amd_create_dc", "tfrec_amd_get_dc",
+    "tfrec_amd_read_dc", "tfrec_amd_reset_dc_rows",
 )
 
 _libs = {}
@@ -189,6 +190,10 @@ def load_library(build: bool = True, experiments: bool = False):
     L.tfrec_amd_read_spectrum.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int)]
     L.tfrec_amd_enable_occupancy.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
     L.tfrec_amd_read_occupancy.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
+    L.tfrec_amd_create_dc.argtypes = [C.POINTER(Config), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.tfrec_amd_get_dc.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.tfrec_amd_read_dc.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
+    L.tfrec_amd_reset_dc_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.tfrec_amd_fifo_depth.restype = C.c_int
     if L.tfrec_amd_fifo_depth() != FIFO_DEPTH:
         raise RuntimeError("libtfrec_amd.so was built with FIFO depth %d, this binding expects %d" % (
@@ -231,7 +236,8 @@ class Receiver:
     def __init__(self, n_streams: int, types_mask: int = 0x2F, thresh: int = 500, filter_type: int = 0,
                  device: int = 0, max_blocks: int = 48, max_events: int | None = None, all_flushes: bool = False,
                  timing: bool = False, serial_chains: bool = False, input_10x: bool = False, bits: bool = False,
-                 experiments: bool = False, input_rate=None, input_format=None, levels: bool = False):
+                 experiments: bool = False, input_rate=None, input_format=None, levels: bool = False, dc_windows=None,
+                 dc_rows=None):
         # experiments=True: the build that reads the TFREC_AMD_* knobs / test hooks from the environment (csrc/knobs.h);
         # the default is the product library, which has none
         self.L = load_library(experiments=experiments)
@@ -250,7 +256,22 @@ class Receiver:
         # the input rows hold (tfrec_amd_create_format, formats.py), at input_rate or -- without one -- at 1.536 MS/s.  Rows stay
         # uint8 arrays or tensors, of input_bytes(n_blocks) bytes.
         self.input_format = "u8"
-        if input_format is not None:
+        # dc_windows=K (1 .. 4096): the DC blocker ahead of everything, averaging over K windows of 512 input samples, for at most
+        # dc_rows input rows (default: n_streams) -- with any input_format ("u8" included) and input_rate (tfrec_amd_create_dc,
+        # dcblock.py)
+        if dc_windows is not None:
+            from . import formats
+
+            p, q = (int(v) for v in (input_rate if input_rate is not None else (1, 1)))
+            fmt = "u8" if input_format is None else input_format
+            fmt = formats.FORMATS.get(fmt, fmt) if isinstance(fmt, str) else fmt
+            rows = n_streams if dc_rows is None else int(dc_rows)
+            if not isinstance(fmt, int) or not all(-2 ** 31 <= v < 2 ** 31 for v in (p, q, fmt, int(dc_windows), rows)):
+                raise TfrecAmdError(E_INVAL, "input_format, input_rate, dc_windows or dc_rows: unknown name or outside int32")
+            _check(self.L, self.L.tfrec_amd_create_dc(C.byref(self.cfg), fmt, p, q, int(dc_windows), rows, C.byref(self.h)))
+            self.input_rate = (p, q)
+            self.input_format = formats.NAMES[fmt]
+        elif input_format is not None:
             from . import formats
 
             p, q = (int(v) for v in (input_rate if input_rate is not None else (1, 1)))
@@ -557,6 +578,35 @@ class Receiver:
         if nr.value:
             _check(self.L, self.L.tfrec_amd_read_occupancy(self.h, int(row), recs.ctypes.data, bits.ctypes.data, nr.value, C.byref(nr)))
         return recs, bits
+
+    def dc(self) -> tuple:
+        """(avg_windows, max_rows) of a dc_windows context, (0, 0) of every other (tfrec_amd_get_dc)."""
+        k, rows = C.c_int32(-1), C.c_int32(-1)
+        _check(self.L, self.L.tfrec_amd_get_dc(self.h, C.byref(k), C.byref(rows)))
+        return int(k.value), int(rows.value)
+
+    def read_dc(self, row: int) -> np.ndarray:
+        """The DC estimates d[w] of input row `row` of the OLDEST undrained submit (tfrec_amd_read_dc; call it before the drain that
+        pops that submit) -> int16 [n_windows, 2], (I, Q).  TfrecAmdError(E_INVAL) on a context without the blocker or for a row the
+        submit did not use, (E_STATE) when nothing is waiting to be drained."""
+        if not -2 ** 31 <= int(row) < 2 ** 31:
+            raise TfrecAmdError(E_INVAL, "row outside int32")
+        nw = C.c_int(0)
+        rc = self.L.tfrec_amd_read_dc(self.h, int(row), None, 0, C.byref(nw))  # the count (no room: E_INVAL)
+        if rc != E_INVAL or nw.value == 0:
+            _check(self.L, rc)
+        d = np.zeros((nw.value, 2), dtype=np.int16)
+        if nw.value:
+            _check(self.L, self.L.tfrec_amd_read_dc(self.h, int(row), d.ctypes.data, nw.value, C.byref(nw)))
+        return d
+
+    def reset_dc_rows(self, rows):
+        """Clear the DC state of the listed input rows at the next submit (tfrec_amd_reset_dc_rows); the streams are not restarted."""
+        idx = [int(r) for r in rows]
+        if any(not -2 ** 31 <= r < 2 ** 31 for r in idx):  # (refused before int32 could wrap an index into range)
+            raise TfrecAmdError(E_INVAL, "row outside int32")
+        a = np.ascontiguousarray(idx, dtype=np.int32)
+        _check(self.L, self.L.tfrec_amd_reset_dc_rows(self.h, a.ctypes.data if len(a) else None, len(a)))
 
     def stage0(self, stream: int, n_pairs: int) -> np.ndarray:
         """input_10x or input_rate: the 1.536 MS/s int16 IQ the 10:1 or the resampling stage produced for the last submit."""

@@ -54,6 +54,8 @@ hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t st
 hipError_t launch_occupancy(hipStream_t st, int n_rows, long n_in, int n_bins, int g, size_t max_records, const unsigned long long *sum,
 			    const unsigned long long *peak, const uint32_t *nfr, uint32_t ratio, uint32_t rel, tfrec_amd_occupancy *recs,
 			    uint32_t *bits);
+hipError_t launch_dc(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_rows, long n_in, int k, int2 *sums, int win_stride,
+		     int2 *ring, int2 *state, uint32_t *d, uint8_t *out, size_t out_stride);
 }  // namespace tfrec
 
 using namespace tfrec;
@@ -63,6 +65,7 @@ using namespace tfrec;
 #include "capi_probe.h"    // the discriminator's host check, debug statistics; probes, read-backs, timings, memory, counters
 #include "capi_submit.h"   // the two kernels, a submit's resets and staging, submit_common, the submits, drain, sync, pending
 #include "capi_outputs.h"  // the level meter's, the recorder's, the spectrum's and the occupancy detector's entry points
+#include "capi_dc.h"       // the DC blocker's constructor, getter, read and reset
 #include "capi_streams.h"  // reset, configure, the three tunes, map, and their getters
 
 extern "C" {

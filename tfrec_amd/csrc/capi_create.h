@@ -262,7 +262,7 @@ static int make_front_buffers(tfrec_amd_ctx *c)
 		c->in16_stride = 4 * m_max;  // complex samples at 1.536 MS/s per stream and submit
 		for (int k = 0; k < kSets; k++)
 			TRY(own_device(c, c->d_in16[k], n * c->in16_stride * sizeof(uint32_t)));
-		const bool raw = c->fmt == TFREC_AMD_FMT_U8;
+		const bool raw = c->pre_fmt == TFREC_AMD_FMT_U8;
 		c->pre_bytes = c->in10x ? k10xTail : c->ingest ? 0 : raw ? kRateTail : kFmtTail;
 		c->pre_fill = raw ? 0x80 : 0;
 		for (int k = 0; c->pre_bytes && k < (c->in10x ? kSets : 2); k++) {  // (the 10x context has always owned one per set)
@@ -288,6 +288,29 @@ static int make_front_buffers(tfrec_amd_ctx *c)
 		TRY(own_device(c, c->d_rtaps, hf.size() * sizeof(float)));
 		HIPCHK(hipMemcpy(c->d_rtaps, hf.data(), hf.size() * sizeof(float), hipMemcpyHostToDevice));
 	}
+	return TFREC_AMD_OK;
+}
+
+// tfrec_amd_create_dc: the blocker's carried state (a row before its first submit: no window, m = head = 0) and every set's buffers
+static int make_dc(tfrec_amd_ctx *c)
+{
+	DcBlock &o = c->dc;
+	if (!o.on)
+		return TFREC_AMD_OK;
+	// the largest submit: floor(max_blocks * 32768 * P / Q) complex samples per row, up to a whole chunk; its whole windows
+	const long long n_max = ((long long)c->cfg.max_blocks * (TFREC_AMD_BLOCK_BYTES / 2) * c->in_p / c->in_q + 7) & ~7LL;
+	const size_t rows = (size_t)o.rows;
+	o.win_stride = (int)(n_max / 512);
+	o.x_stride = (size_t)n_max * 4;
+	TRY(own_device(c, o.d_sums, rows * (size_t)o.win_stride * sizeof(int2)));
+	TRY(own_device(c, o.d_ring, rows * (size_t)o.k * sizeof(int2)));
+	TRY(own_device(c, o.d_state, rows * sizeof(int2)));
+	HIPCHK(hipMemset(o.d_state, 0, rows * sizeof(int2)));
+	for (int k = 0; k < kSets; k++) {
+		TRY(own_device(c, o.d_d[k], rows * (size_t)o.win_stride * sizeof(uint32_t)));
+		TRY(own_device(c, o.d_x[k], rows * o.x_stride));
+	}
+	o.reset_marked.assign(rows, 0);
 	return TFREC_AMD_OK;
 }
 
@@ -615,6 +638,7 @@ static int init_context(tfrec_amd_ctx *c)
 		c->copy_guess = c->copy_guess_min = (uint32_t)std::max(1, atoi(cg));
 	TRY(register_chains(c));
 	TRY(make_front_buffers(c));
+	TRY(make_dc(c));
 	if (!(c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS))
 		TRY(make_window_state(c));
 	TRY(make_event_blocks(c));
@@ -650,7 +674,9 @@ int tfrec_amd_destroy(tfrec_amd_ctx *c)
 
 // What the three constructors share behind their own argument checks: the input's format, its rate p / q (resamp: through the
 // resampling stage; ingest: another format at the base rate) and the context made for it
-static int create_with(const tfrec_amd_config *cfg, int32_t fmt, int32_t p, int32_t q, bool resamp, bool ingest, tfrec_amd_ctx **out)
+// dc_k != 0: with the DC blocker over at most dc_rows rows (tfrec_amd_create_dc)
+static int create_with(const tfrec_amd_config *cfg, int32_t fmt, int32_t p, int32_t q, bool resamp, bool ingest, tfrec_amd_ctx **out,
+		       int32_t dc_k = 0, int32_t dc_rows = 0)
 {
 	TRY(validate(cfg));
 	HIPCHK(hipSetDevice(cfg->device));
@@ -658,7 +684,13 @@ static int create_with(const tfrec_amd_config *cfg, int32_t fmt, int32_t p, int3
 	if (!c)
 		return TFREC_AMD_E_NOMEM;
 	c->cfg = *cfg;
-	c->fmt = fmt;
+	c->fmt = c->pre_fmt = fmt;
+	if (dc_k) {  // the pre-stage reads the corrected rows
+		c->pre_fmt = TFREC_AMD_FMT_S16;
+		c->dc.on = true;
+		c->dc.k = dc_k;
+		c->dc.rows = dc_rows;
+	}
 	c->in10x = (cfg->flags & TFREC_AMD_F_INPUT_10X) != 0;
 	c->in_p = c->in10x ? 10 : p;
 	c->in_q = c->in10x ? 1 : q;

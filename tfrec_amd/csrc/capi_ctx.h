@@ -100,6 +100,22 @@ struct OccupancyOut {
 	uint32_t *d_bits[kSets] = {};
 };
 
+// tfrec_amd_create_dc: K, the rows a submit may use, the largest submit's samples per row and windows; per context
+// a submit's sums ([rows][win_stride]), the ring ([rows][K]) and the rows' {m, head}; per set the table of d ([rows][win_stride]) and
+// the corrected rows (x_stride bytes each, int16 x' << 2) the pre-stage reads, and what the set's submit held.  reset_*: the rows
+// tfrec_amd_reset_dc_rows marked since the last submit (each once).
+struct DcBlock {
+	bool on = false;
+	int k = 0, rows = 0, win_stride = 0;
+	size_t x_stride = 0;
+	int2 *d_sums = nullptr, *d_ring = nullptr, *d_state = nullptr;
+	uint32_t *d_d[kSets] = {};
+	uint8_t *d_x[kSets] = {};
+	int set_rows[kSets] = {}, set_windows[kSets] = {};
+	std::vector<int32_t> reset_pending;
+	std::vector<uint8_t> reset_marked;
+};
+
 struct tfrec_amd_ctx {
 	tfrec_amd_config cfg;
 	ChainLaunch launch;
@@ -188,8 +204,11 @@ struct tfrec_amd_ctx {
 	// tfrec_amd_create_format: fmt is the TFREC_AMD_FMT_* of the input rows, 0 (U8) in every context of the older
 	// constructors.  A rate context with another format runs resample_fmt_kernel from a history of canonical x instead
 	// of the raw one; at the base rate (ingest: rate 1/1, no resampler) ingest_kernel converts the rows into d_in16.
-	int32_t fmt = TFREC_AMD_FMT_U8;
+	// tfrec_amd_create_dc keeps two formats: fmt stays the caller's (input_bytes, submit_host's staging, the spectrum), pre_fmt is
+	// what the pre-stage reads -- S16, the corrected rows (dc) -- and what its history is kept in; everywhere else pre_fmt == fmt.
+	int32_t fmt = TFREC_AMD_FMT_U8, pre_fmt = TFREC_AMD_FMT_U8;
 	bool ingest = false;
+	DcBlock dc;
 	// ---- window-parallel pipeline (make_window_state).  One set per submit in flight, like the front-end outputs: the window
 	// scan and the biquads of submit k+1 fill theirs while the slicers of submit k still read the other
 	int16_t *d_ld16[kSets] = {};   // [chains][m_max] tfa2-family biquad outputs

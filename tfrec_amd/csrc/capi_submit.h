@@ -193,13 +193,42 @@ static int launch_prestage(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, size_
 	if (c->in10x)  // 15.36 MS/s u8 -> 1.536 MS/s int16 pairs
 		HIPCHK(launch_decim10(fs, d_iq, stride, n, n_blocks, hin, hout, out, c->in16_stride, chan));
 	else if (c->ingest)  // 1.536 MS/s in another format -> x as int16 pairs
-		HIPCHK(launch_ingest(fs, c->fmt, d_iq, stride, n, n_blocks, out, c->in16_stride, chan));
-	else if (c->fmt != TFREC_AMD_FMT_U8)  // 1536000 P / Q S/s in another format: the format-aware resampling stage
-		HIPCHK(launch_resample_fmt(fs, c->fmt, d_iq, stride, n, n_blocks, c->in_p, c->in_q, c->rate_t, c->d_rtaps, hin, hout, out,
+		HIPCHK(launch_ingest(fs, c->pre_fmt, d_iq, stride, n, n_blocks, out, c->in16_stride, chan));
+	else if (c->pre_fmt != TFREC_AMD_FMT_U8)  // 1536000 P / Q S/s in another format: the format-aware resampling stage
+		HIPCHK(launch_resample_fmt(fs, c->pre_fmt, d_iq, stride, n, n_blocks, c->in_p, c->in_q, c->rate_t, c->d_rtaps, hin, hout, out,
 					   c->in16_stride, chan, c->n_wide != 0));
 	else  // 1536000 P / Q S/s u8 -> 1.536 MS/s int16 pairs
 		HIPCHK(launch_resample(fs, d_iq, stride, n, n_blocks, c->in_p, c->in_q, c->rate_t, c->d_rtaps, hin, hout, out, c->in16_stride,
 				       chan, c->n_wide != 0));
+	return TFREC_AMD_OK;
+}
+
+// tfrec_amd_create_dc: a submit may use at most max_rows input rows (checked before anything is queued)
+static int check_dc_rows(const tfrec_amd_ctx *c)
+{
+	if (!c->dc.on || rows_in_use(c) <= c->dc.rows)
+		return TFREC_AMD_OK;
+	snprintf(g_err, sizeof(g_err), "the submit uses %d input rows, the DC blocker was made for %d", rows_in_use(c), c->dc.rows);
+	return TFREC_AMD_E_INVAL;
+}
+
+// The DC blocker on the set's front-end stream, ahead of the pre-stage: the rows marked by tfrec_amd_reset_dc_rows
+// start again (m = head = 0), then the three kernels correct the submit's rows into the set's buffer.  The context's sums, ring
+// and state are ordered from submit to submit by the stream.
+static int launch_dc_rows(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, size_t stride, long n_in)
+{
+	DcBlock &o = c->dc;
+	hipStream_t fs = c->pipe[set].fs;
+	for (int32_t r : o.reset_pending) {
+		HIPCHK(hipMemsetAsync(o.d_state + r, 0, sizeof(int2), fs));
+		o.reset_marked[r] = 0;
+	}
+	o.reset_pending.clear();
+	const int rows = rows_in_use(c);
+	HIPCHK(launch_dc(fs, c->fmt, d_iq, stride, rows, n_in, o.k, o.d_sums, o.win_stride, o.d_ring, o.d_state, o.d_d[set], o.d_x[set],
+			 o.x_stride));
+	o.set_rows[set] = rows;
+	o.set_windows[set] = (int)(n_in / 512);
 	return TFREC_AMD_OK;
 }
 
@@ -215,6 +244,7 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		snprintf(g_err, sizeof(g_err), "IQ base and stream stride must be 16-byte aligned and >= one stream");
 		return TFREC_AMD_E_INVAL;
 	}
+	TRY(check_dc_rows(c));
 	TRY(check_fifo(c));
 	TRY(check_live(c));
 	HIPCHK(hipSetDevice(c->cfg.device));
@@ -263,7 +293,14 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	if (chan10 || chan_front)
 		TRY(stage_chan(c, set));
 	if (c->in16) {  // ... then the standard cascade on int16 input
-		TRY(launch_prestage(c, set, (const uint8_t *)d_iq, stride, n_blocks, chan10 ? c->d_chan[set] : nullptr));
+		const uint8_t *pin = (const uint8_t *)d_iq;
+		size_t pstride = stride;
+		if (c->dc.on) {  // the DC blocker first: the pre-stage reads the corrected rows, an S16 input
+			TRY(launch_dc_rows(c, set, pin, stride, (long)(row_bytes / fmt_sample_bytes(c->fmt))));
+			pin = c->dc.d_x[set];
+			pstride = c->dc.x_stride;
+		}
+		TRY(launch_prestage(c, set, pin, pstride, n_blocks, chan10 ? c->d_chan[set] : nullptr));
 		fin = (const uint8_t *)c->d_in16[set];
 		fstride = c->in16_stride * sizeof(uint32_t);
 	}
@@ -372,6 +409,7 @@ static int submit_host_impl(tfrec_amd_ctx *c, const uint8_t *h_iq, size_t stride
 	TRY(input_bytes(c, n_blocks, &row));
 	if (rows_in_use(c) > 1 && stride < row)
 		return TFREC_AMD_E_INVAL;
+	TRY(check_dc_rows(c));
 	TRY(check_fifo(c));
 	HIPCHK(hipSetDevice(c->cfg.device));
 	const int set = (c->head + c->inflight) % kSets;  // the set's previous user has been drained: its staging buffer is free

@@ -271,6 +271,8 @@ struct capture_batch {
 	std::vector<uint32_t> spec_frames;
 	std::vector<tfrec_amd_occupancy> occ_recs;  // -A: the detector's records of row 0 and their bitmap words, [record][N / 32]
 	std::vector<uint32_t> occ_bits;
+	std::vector<int> dc_file;  // -z with -D: per file of the batch its index in the job and the last window's {d_I, d_Q} of its row
+	std::vector<int16_t> dc_last;
 };
 
 struct device_worker {
@@ -296,11 +298,13 @@ struct device_worker {
 	bool capture;  // -S: the contexts record (tfrec_amd_enable_capture)
 	int spec_n, spec_g;  // -P: bins and frames per record of the spectrum of row 0 (tfrec_amd_enable_spectrum); 0: none
 	int occ_ratio, occ_rel;  // -A: the occupancy detector on it (tfrec_amd_enable_occupancy); 0: none
+	int dc_windows;     // -z: the DC blocker's avg_windows (tfrec_amd_create_dc); 0: none
+	bool dc_report;     // ... with -D: the batches carry every file's last estimate
 	std::deque<capture_batch> out_caps;  // -S: their runs (stream = the file's index in the job) and sample pool
 	bool done;
 	std::thread th;
 
-	device_worker() : files(NULL), s0(0), s1(0), device(0), types(0), thresh(0), filter(0), bps(1), flags(0), nslots(0), file_blocks(NULL), wide(false), share(false), rate_p(1), rate_q(1), fmt(TFREC_AMD_FMT_U8), block_bytes(TFREC_AMD_BLOCK_BYTES), unit(1), rc(0), abort(NULL), capture(false), spec_n(0), spec_g(0), occ_ratio(0), occ_rel(0), done(false) {}
+	device_worker() : files(NULL), s0(0), s1(0), device(0), types(0), thresh(0), filter(0), bps(1), flags(0), nslots(0), file_blocks(NULL), wide(false), share(false), rate_p(1), rate_q(1), fmt(TFREC_AMD_FMT_U8), block_bytes(TFREC_AMD_BLOCK_BYTES), unit(1), rc(0), abort(NULL), capture(false), spec_n(0), spec_g(0), occ_ratio(0), occ_rel(0), dc_windows(0), dc_report(false), done(false) {}
 
 	void push(std::vector<tfrec_amd_event> &&ev, std::vector<tfrec_amd_level> &&lv, capture_batch &&cb)
 	{
@@ -362,13 +366,6 @@ struct device_worker {
 		cfg.max_events = (int32_t)std::max<size_t>(4096, n * (size_t)bps * ((flags & TFREC_AMD_F_BITS) ? 256 : 64));
 		cfg.flags = flags;
 		tfrec_amd_ctx *ctx = NULL;
-		int r = fmt != TFREC_AMD_FMT_U8	       ? tfrec_amd_create_format(&cfg, fmt, rate_p, rate_q, &ctx)
-			: (rate_p != 1 || rate_q != 1) ? tfrec_amd_create_rate(&cfg, rate_p, rate_q, &ctx)
-						       : tfrec_amd_create(&cfg, &ctx);
-		if (r) {
-			fprintf(stderr, "tfrec_amd_create (device %d): %s (%s)\n", device, tfrec_amd_strerror(r), tfrec_amd_last_error());
-			return r;
-		}
 		const size_t row = (size_t)(bps / unit) * block_bytes;
 		const size_t n_batches = plan.size();
 		// Shared inputs (tfrec_amd_map_streams): without -n a stream carries one file for the whole job, and the streams whose
@@ -378,6 +375,7 @@ struct device_worker {
 		std::vector<int32_t> in_row(n, 0);
 		std::vector<bool> reads(n, true);  // the stream's file is read into its row (the first stream of the row)
 		size_t n_rows = n;
+		bool map = false;  // streams share rows: the context's streams are mapped to them
 		if (share && n_batches) {
 			std::vector<std::string> paths;
 			for (size_t s = 0; s < n; s++) {
@@ -391,15 +389,7 @@ struct device_worker {
 				in_row[s] = (int32_t)r;
 			}
 			if (paths.size() < n) {
-				std::vector<int32_t> all(n);
-				for (size_t s = 0; s < n; s++)
-					all[s] = (int32_t)s;
-				r = tfrec_amd_map_streams(ctx, all.data(), in_row.data(), (int)n);
-				if (r) {
-					fprintf(stderr, "tfrec_amd_map_streams (device %d): %s (%s)\n", device, tfrec_amd_strerror(r), tfrec_amd_last_error());
-					tfrec_amd_destroy(ctx);
-					return r;
-				}
+				map = true;
 				n_rows = std::max<size_t>(1, paths.size());
 			} else {
 				for (size_t s = 0; s < n; s++)
@@ -408,6 +398,26 @@ struct device_worker {
 		} else {
 			for (size_t s = 0; s < n; s++)
 				in_row[s] = (int32_t)s;
+		}
+		// (the rows are known: -z sizes the blocker for them)
+		int r = dc_windows		       ? tfrec_amd_create_dc(&cfg, fmt, rate_p, rate_q, dc_windows, (int32_t)n_rows, &ctx)
+			: fmt != TFREC_AMD_FMT_U8      ? tfrec_amd_create_format(&cfg, fmt, rate_p, rate_q, &ctx)
+			: (rate_p != 1 || rate_q != 1) ? tfrec_amd_create_rate(&cfg, rate_p, rate_q, &ctx)
+						       : tfrec_amd_create(&cfg, &ctx);
+		if (r) {
+			fprintf(stderr, "tfrec_amd_create (device %d): %s (%s)\n", device, tfrec_amd_strerror(r), tfrec_amd_last_error());
+			return r;
+		}
+		if (map) {
+			std::vector<int32_t> all(n);
+			for (size_t s = 0; s < n; s++)
+				all[s] = (int32_t)s;
+			r = tfrec_amd_map_streams(ctx, all.data(), in_row.data(), (int)n);
+			if (r) {
+				fprintf(stderr, "tfrec_amd_map_streams (device %d): %s (%s)\n", device, tfrec_amd_strerror(r), tfrec_amd_last_error());
+				tfrec_amd_destroy(ctx);
+				return r;
+			}
 		}
 		if (capture) {  // -S, sized so that no submit overflows: every sample, and a stream's runs are >= 356 samples long but two
 			r = tfrec_amd_enable_capture(ctx, (uint32_t)(n * ((size_t)bps * TFREC_AMD_BLOCK_DEC / 356 + 3)),
@@ -497,6 +507,16 @@ struct device_worker {
 				rcv.wait(lk, [&]() { return filled > k; });
 			}
 			const batch_plan &b = plan[k];
+			if (dc_windows && !share) {
+				// -n with -z: a slot that starts a new file -- by a reset, or by the configure or tune its next file needs -- starts a new
+				// DC estimate too.  A stream's row is its own here (nothing is shared); duplicates are allowed.
+				std::vector<int32_t> rows(b.reset);
+				rows.insert(rows.end(), b.conf.begin(), b.conf.end());
+				rows.insert(rows.end(), b.tune.begin(), b.tune.end());
+				const int rd = tfrec_amd_reset_dc_rows(ctx, rows.data(), (int)rows.size());
+				if (rd)
+					return rd;
+			}
 			if (!b.reset.empty()) {  // the streams whose file ended in the batch before: fresh receivers for the next files
 				const int rr = tfrec_amd_reset_streams(ctx, b.reset.data(), (int)b.reset.size());
 				if (rr)
@@ -602,6 +622,26 @@ struct device_worker {
 					cb.spec_peak.resize((size_t)nr * spec_n);
 					cb.spec_frames.resize((size_t)nr);
 					r = tfrec_amd_read_spectrum(ctx, 0, cb.spec_sum.data(), cb.spec_peak.data(), (size_t)nr, cb.spec_frames.data(), &nr);
+				}
+				if (r)
+					break;
+			}
+			if (dc_windows && dc_report) {  // -z -D: the last estimate of every file's row, before the drain pops the batch
+				std::vector<int16_t> d;
+				for (size_t s = 0; s < n && r == 0; s++) {
+					if (plan[k].file[s] < 0 || !reads[s])
+						continue;
+					int nw = 0;
+					r = tfrec_amd_read_dc(ctx, in_row[s], NULL, 0, &nw);  // (the count: E_INVAL for want of room)
+					if (r == TFREC_AMD_E_INVAL && nw > 0) {
+						d.resize(2 * (size_t)nw);
+						r = tfrec_amd_read_dc(ctx, in_row[s], d.data(), (size_t)nw, &nw);
+						if (r == 0) {
+							cb.dc_file.push_back(plan[k].file[s]);
+							cb.dc_last.push_back(d[2 * (size_t)nw - 2]);
+							cb.dc_last.push_back(d[2 * (size_t)nw - 1]);
+						}
+					}
 				}
 				if (r)
 					break;
@@ -743,6 +783,8 @@ int gpu_engine::run()
 		w.spec_g = spec_g;
 		w.occ_ratio = spectrum ? occ_ratio : 0;
 		w.occ_rel = occ_rel;
+		w.dc_windows = dc_windows;
+		w.dc_report = dbg > 0;
 		w.wide = wide;
 		w.share = slots <= 0;
 		w.rate_p = rate_p;
@@ -819,6 +861,8 @@ int gpu_engine::run()
 			}
 			if (rc)
 				break;
+			for (size_t q = 0; q < cb.dc_file.size(); q++)  // -z -D
+				printf("dc %s I=%d Q=%d\n", files[cb.dc_file[q]].c_str(), (int)cb.dc_last[2 * q], (int)cb.dc_last[2 * q + 1]);
 			for (size_t q = 0; q < cb.spec_frames.size(); q++) {  // -P
 				spec_frames += cb.spec_frames[q];
 				for (int b = 0; b < spec_n; b++) {

@@ -192,6 +192,12 @@ public:
 		occ_join = join_hz;
 	}
 	const std::vector<long> &found_khz() const { return occ_found; }
+	// -z: the DC blocker (tfrec_amd_create_dc) over `windows` windows of 512 input samples, on every input row of every
+	// context: a file's row (a path shared by several streams: its one row) is corrected once, ahead of every tune.  With -n the
+	// row of a stream that starts a new file has its DC state reset with the stream (tfrec_amd_reset_dc_rows).  With dbg > 0 run()
+	// prints "dc <file> I=<d> Q=<d>" per submit and file: the estimate of the submit's last window of the file's row.  Under -A
+	// only pass 2 is given it: pass 1's spectrum reads the raw rows either way.  Excludes set_wide.
+	void set_dc(int windows) { dc_windows = windows; }
 	// returns 0 on success, a TFREC_AMD_E_* code otherwise
 	int run();
 	// decoders of stream s in slot order (NULL for slots not registered)
@@ -225,6 +231,7 @@ private:
 	int occ_ratio = 0, occ_rel = 0;  // set_occupancy (0: none)
 	long occ_join = 0;
 	std::vector<long> occ_found;
+	int dc_windows = 0;        // set_dc (0: none)
 };
 
 #endif

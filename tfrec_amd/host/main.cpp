@@ -1,6 +1,6 @@
 // tfrec_amd/host/main.cpp -- tfrec_gpu: the reference's file-replay CLI on the GPU path.
 //
-//   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-q] [-D] [-B] [-d device[,device...]] [-b blocks]
+//   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-q] [-D] [-B] [-d device[,device...]] [-b blocks]
 //             [-n streams] [-e handler | -E handler] [-m mode] [-p settings] -L dump.iq [[-p settings] -L more.iq ...]
 //   tfrec_gpu [receiver flags as above] [-c kHz] [-x | -r Hz] [-F format] [-D] -P bins[,frames_per_record] -L dump.iq
 //   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-c kHz] [-x | -r Hz] [-F format] [-D] [-d device] [-b blocks] -s step_kHz -L dump.iq
@@ -77,6 +77,13 @@
 // 192 kHz to the recording's edge, which -s would not scan either.  Pass 2 is -s on the found channels: its "scan ..." lines.  No
 // channel found: no scan.  Both passes run in this process, one after the other.  stderr lists the bins before a device is opened, as
 // -P does.  Not with -s, -n, -p, -f, -e / -E, -X, -S, several -L or several devices.
+// -z [windows] (not in the reference): remove every recording's DC offset on the GPU (tfrec_amd_create_dc) -- the few
+// LSB a zero-IF front end adds to each rail, which keep |I| + |Q| above the threshold of the receiver on the centre channel.  Per
+// rail the mean of the last `windows` windows of 512 input samples (1 .. 4096, default 2048) is subtracted, in exact integers, at
+// the input rate and ahead of every tune; a path shared by several -L is corrected once.  Works with -r, -F, -c, -f, -p, -s, -S, -P,
+// -A and -n (a slot that starts a new file starts a new estimate); the spectrum of -P and of -A's pass 1 stays that of the raw
+// input.  With -D stdout carries "dc <file> I=<d> Q=<d>" per submit and file: the estimate of the submit's last window, in units
+// of x (a u8 LSB is 64).  Not with -x or -X.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -199,9 +206,30 @@ int main(int argc, char **argv)
 	bool have_spec_p = false;
 	bool have_auto = false;  // -A
 	long auto_ratio = 32, auto_rel = 16, auto_join = 50;  // (join: kHz)
+	// -z: the DC blocker's averaging length in windows of 512 input samples (0: off).  The default, 2048 windows = 0.68 s at
+	// 1.536 MS/s, is derived from nothing but the burst lengths: an average much longer than any telegram (8 windows eat part of
+	// a burst and lose a telegram, 64 do not: DESIGN.md 6m); it has not been measured on real recordings.
+	long dc_windows = 0;
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:P:A::h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:P:A::z::h")) != -1) {
 		switch (c) {
+		case 'z': {
+			// the argument is optional: attached (-z64), or the next word where that starts with a digit
+			const char *a = optarg;
+			if (!a && optind < argc && argv[optind][0] >= '0' && argv[optind][0] <= '9')
+				a = argv[optind++];
+			dc_windows = 2048;
+			if (a) {
+				char *end = NULL;
+				dc_windows = strtol(a, &end, 10);
+				if (end == a || *end || dc_windows < 1 || dc_windows > 4096) {
+					fprintf(stderr, "tfrec_gpu: bad -z '%s': want the windows (of 512 input samples) the DC estimate averages over, within "
+							"1 .. 4096\n", a);
+					return 1;
+				}
+			}
+			break;
+		}
 		case 'A': {
 			// the argument is optional: attached (-A32,16), or the next word where that starts with a digit
 			const char *a = optarg;
@@ -329,7 +357,7 @@ int main(int argc, char **argv)
 		case 'E': exec = optarg; batched = true; break;
 		case 'm': mode = atoi(optarg); break;
 		default:
-			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
+			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
 					"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
 					"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
 					"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
@@ -345,6 +373,9 @@ int main(int argc, char **argv)
 					"              767 kHz it is shifted ahead of the resampler); not with -x\n"
 					"  -F format   what the dumps hold: u8 (default), s8, s16 or f32 (cu8, cs8, cs16, cf32): little-endian interleaved I, Q without a\n"
 					"              header, at the rate of -r or at 1536000; a format other than u8 not with -x\n"
+					"  -z [n]      remove every dump's DC offset on the GPU, ahead of every tune: the mean over the last n windows of 512 input\n"
+					"              samples (default 2048, within 1 .. 4096) is subtracted from I and from Q (-D: a 'dc' line per submit); not with\n"
+					"              -x or -X; under -A the spectrum of pass 1 stays raw\n"
 					"  -n streams  at most this many streams per device: the -L files queue for them in order\n"
 					"  -p T=<hex>,t=<n>,W=<0|1>,f=<kHz>  -T / -t / -W / -f of the -L files that follow, up to the next -p (fields left out: the global ones)\n");
 			return c == 'h' ? 0 : 1;
@@ -365,6 +396,10 @@ int main(int argc, char **argv)
 	if (have_auto && (have_scan || have_slots || have_spec || freq >= 0 || exec || hexfile || cap_prefix || dumps.size() > 1 || devices.size() > 1)) {
 		fprintf(stderr, "tfrec_gpu: -A finds and scans the channels of one -L file on one device: not with -s, -n, -p, -f, -e, -E, -X, -S, "
 				"several -L or several -d\n");
+		return 1;
+	}
+	if (dc_windows && (wide || hexfile)) {
+		fprintf(stderr, "tfrec_gpu: -z removes the DC offset of -L files at 1.536 MS/s or the rate of -r: not with -x or -X\n");
 		return 1;
 	}
 	if (cap_prefix && hexfile) {
@@ -519,6 +554,8 @@ int main(int argc, char **argv)
 	if (rate_p != 1 || rate_q != 1)
 		e.set_rate(rate_p, rate_q);
 	e.set_format(format);
+	if (dc_windows)
+		e.set_dc((int)dc_windows);
 	if (have_scan)
 		e.set_scan(scan_khz);
 	if (cap_prefix)
