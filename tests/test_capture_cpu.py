@@ -214,3 +214,15 @@ def test_cli_capture_usage_errors(tmp_path):
         out = run(args)
         assert out.returncode == 2 and "missing.iq" in out.stderr, args
     assert not os.path.exists(pre + ".idx")
+
+
+def test_cli_capture_index_that_cannot_be_written(tmp_path):
+    """<prefix>.idx is opened before a device is: a prefix in a directory that does not exist ends the run there, with the path on
+    stderr."""
+    cli = parity.build_cli()
+    f = tmp_path / "one.iq"
+    f.write_bytes(bytes([128]) * api.BLOCK_BYTES)
+    pre = str(tmp_path / "nowhere" / "cap")
+    out = subprocess.run([cli, "-S", pre, "-L", str(f)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2 and out.stderr.startswith(pre + ".idx: "), out.stderr
+    assert out.stdout == ""

@@ -422,3 +422,30 @@ def test_cli_capture_of_the_golden_tfa_2_scene(tmp_path):
         pools.append(pool)
     assert open(pre + ".idx").read().splitlines() == lines and len(lines) >= 1
     assert np.array_equal(np.fromfile(pre + ".0.cs16", dtype="<i2").reshape(-1, 2), np.concatenate(pools))
+
+
+def test_cli_capture_is_the_same_across_contexts_and_slots(tmp_path):
+    """-S of two files (the golden TFA_2 scene's first 3 blocks, and its first 2) with -b 2: as two streams of one context, as one
+    stream each of two contexts (-d 0,0) and through one recycled stream (-n 1).  Per file the .idx lines -- without the stream
+    column, which is the file's stream on its device -- and the .cs16 bytes are the same."""
+    cli = parity.build_cli()
+    z = np.load(os.path.join(parity.ROOT, "tests", "golden", "iq_tfa_2.npz"))
+    paths = []
+    for i, nb in enumerate((3, 2)):
+        paths.append(str(tmp_path / ("f%d.iq" % i)))
+        np.ascontiguousarray(z["iq"][:nb * api.BLOCK_BYTES]).tofile(paths[-1])
+    got = []
+    for name, extra in (("plain", []), ("two", ["-d", "0,0"]), ("slot", ["-n", "1"])):
+        pre = str(tmp_path / name)
+        out = subprocess.run([cli, "-S", pre, "-T", "2f", "-t", "500", "-b", "2"] + extra + ["-L", paths[0], "-L", paths[1]],
+                             capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr
+        idx = [ln.split() for ln in open(pre + ".idx").read().splitlines()]
+        per_file = {}
+        for f in (0, 1):
+            cs = pre + ".%d.cs16" % f
+            per_file[f] = ([ln[:1] + ln[2:] for ln in idx if ln[0] == str(f)], open(cs, "rb").read() if os.path.exists(cs) else None)
+        assert set(ln[0] for ln in idx) <= {"0", "1"}
+        got.append(per_file)
+    assert got[1] == got[0] and got[2] == got[0]
+    assert len(got[0][0][0]) >= 1 and got[0][0][1]

@@ -294,3 +294,24 @@ def test_cli_one_2400000_dump_given_three_times(cli, tmp_path):
         o = input_oracle(wide_row(p, q)[0], p, q, f) if abs(f) >= 768000 else input_oracle(wide_row(p, q)[0], p, q, 0, f)
         want, got = parity.telegram_lines(o.text()), parity.telegram_lines(singles[i][0])
         assert got == want and len(want) >= 1, i
+
+
+def test_cli_one_slot_changes_tune_kind_near_far_near(cli, tmp_path):
+    """tfrec_gpu -r 2400000 -n 1: the same file three times through ONE stream, tuned near, far, near -- the slot goes from the tune
+    behind the resampler to the input-rate tune and back, the other kind cleared each time.  Stdout is the three single-file runs
+    one after the other, and the sink's records are theirs with the file index as stream."""
+    p, q = 25, 16
+    w = tmp_path / "w.iq"
+    wide_row(p, q)[0].tofile(w)
+    c = 868250
+    fs = [c + f // 1000 for f in WIDE_SCENES[p, q][:3]]
+    fs = [fs[0], fs[2], fs[1]]
+    assert [abs(f - c) > 767 for f in fs] == [False, True, False]
+    base = ["-r", "2400000", "-c", str(c), "-T", "%x" % TYPES, "-t", str(THRESH), "-b", "2"]
+    singles = [parity.cli(base + ["-p", "f=%d" % f, "-L", str(w)], str(tmp_path / ("s%d.txt" % i))) for i, f in enumerate(fs)]
+    args = base + ["-n", "1"]
+    for f in fs:
+        args += ["-p", "f=%d" % f, "-L", str(w)]
+    out, rec = parity.cli(args, str(tmp_path / "all.txt"))
+    assert out == "".join(s[0] for s in singles) and len(out.splitlines()) >= 3
+    assert rec == [[str(i)] + r[1:] for i, s in enumerate(singles) for r in s[1]] and len(rec) >= 3

@@ -326,3 +326,31 @@ def test_cli_scan_finds_the_channel(tmp_path):
         assert field(ln, "blocks") == 3
         if abs(k - (c + 600)) > 100:
             assert field(ln, "telegrams") == 0, ln
+
+
+def test_cli_scan_with_capture(tmp_path):
+    """-S beside -s: the table is the one of the scan alone, the channel that carries the scene has its trigger windows in
+    <prefix>.<channel index>.cs16 -- as many samples as its .idx lines count -- and a channel that never triggered has no file."""
+    cli = parity.build_cli()
+    f = tmp_path / "scan.iq"
+    scan_file().tofile(f)
+    c = 868250
+    args = ["-s", "100", "-r", "2048000", "-c", str(c), "-T", "2f", "-t", "500", "-b", "3", "-L", str(f)]
+    pre = str(tmp_path / "cap")
+    plain = subprocess.run([cli] + args, capture_output=True, text=True, timeout=300)
+    out = subprocess.run([cli, "-S", pre] + args, capture_output=True, text=True, timeout=300)
+    assert plain.returncode == 0 and out.returncode == 0, out.stderr
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("scan ")]
+    chans = levels.scan_channels(c, 100, 2048000)
+    assert lines == [ln for ln in plain.stdout.splitlines() if ln.startswith("scan ")] and len(lines) == len(chans)
+    idx = [ln.split() for ln in open(pre + ".idx").read().splitlines()]
+    mine = chans.index(c + 600)
+    n_samples = sum(int(ln[3]) for ln in idx if int(ln[0]) == mine)
+    assert n_samples >= 1 and os.path.getsize(pre + ".%d.cs16" % mine) == 4 * n_samples
+    field = lambda ln, k: int(dict(p.split("=") for p in ln.split()[2:])[k])  # noqa: E731
+    quiet = [i for i, ln in enumerate(lines) if field(ln, "triggered") == 0]
+    assert quiet  # (the channels far from the scene never trigger at -t 500)
+    for i in quiet:
+        assert not os.path.exists(pre + ".%d.cs16" % i), lines[i]
+    # ... and a file exists exactly for the channels that have a run
+    assert [i for i in range(len(chans)) if os.path.exists(pre + ".%d.cs16" % i)] == sorted(set(int(ln[0]) for ln in idx))

@@ -199,6 +199,15 @@ def test_cli_usage_errors(cli, tmp_path):
     assert out.returncode == 1 and "need -L" in out.stderr
 
 
+def test_cli_a_bad_argument_is_echoed(cli, tmp_path):
+    """The diagnostic names the argument as it was given, attached to -A or as the next word."""
+    f = str(tmp_path / "missing.iq")
+    for bad in ("1", "32,16,5,1", "32,", "4097,2"):
+        for args in (["-A", bad], ["-A" + bad]):
+            out = run_cli(cli, args + ["-L", f])
+            assert out.returncode == 1 and out.stderr.startswith("tfrec_gpu: bad -A '%s': want [ratio[,rel[,join_kHz]]]" % bad), (args, out.stderr)
+
+
 @pytest.mark.parametrize("args,fs_in,n_bins,g,occ", [
     (["-r", "2048000", "-c", "868250", "-A"], 2048000, 256, 170, (32, 16, 50000)),
     (["-c", "868250", "-A", "64,8,25"], 1536000, 256, 128, (64, 8, 25000)),

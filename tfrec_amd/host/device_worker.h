@@ -1,0 +1,472 @@
+// tfrec_amd/host/device_worker.h -- one device context of a job and the host thread that drives it (see gpu_engine.h).
+// The class and, below it, its steps: a header of gpu_engine.cpp alone, so that gpu_engine.cpp + main.cpp stay the whole adapter
+// for whoever builds it (the host Makefile, and oracle/Makefile against the reference's decoders).
+//
+// engine::run (engine.cpp:63-93) for the dump files [s0, s1) on ONE device, as a three-stage pipeline over batches of
+// bps blocks:
+//   reader thread : fread batch k+2 of every file into a pinned host buffer (buffers in rotation)
+//   GPU           : H2D copy + hot path of batch k+1 (tfrec_amd_submit_host is asynchronous on pinned memory)
+//   worker thread : drain batch k's flush events and queue them for the engine's thread
+// The C ABI's submit/drain FIFO (depth TFREC_AMD_FIFO_DEPTH = 4) is what lets batches k+1 .. k+3 be queued before batch
+// k is drained; the worker keeps the FIFO full (one pinned host buffer per submit in flight + one being read).
+#ifndef TFREC_AMD_HOST_DEVICE_WORKER_H
+#define TFREC_AMD_HOST_DEVICE_WORKER_H
+
+#include <stdlib.h>
+#include <string.h>
+
+#include <atomic>
+#include <condition_variable>
+#include <deque>
+#include <mutex>
+#include <thread>
+
+#include "job.h"
+
+class device_worker {
+public:
+	// files, file_blocks (blocks of every file of the job), settings: the whole job's; dflt: the context's thresh and filter (its
+	// types are the union of the files' types); abort: set by the engine when any worker failed -- stop instead of running the
+	// whole job.  All of them outlive the worker.
+	device_worker(const job_settings &job, const std::vector<std::string> &files, const std::vector<size_t> &file_blocks,
+		      const std::vector<file_settings> &settings, file_settings dflt, int device, size_t s0, size_t s1, int bps,
+		      const std::atomic<bool> &abort);
+	void start() { th = std::thread([this]() { run(); }); }
+	// next batch's results (false: the worker ended -- rc says why)
+	bool pop(batch_result &b);
+	std::vector<batch_plan> plan;  // plan_batches
+	int rc;
+	std::thread th;
+
+private:
+	static constexpr int kBufs = TFREC_AMD_FIFO_DEPTH + 1;
+	void run();
+	int work();
+	void push(batch_result &&b);
+	void map_rows();
+	int open_context();
+	void read_batches();
+	int submit(size_t k);
+	int collect(size_t k, batch_result &b);
+	int read_captures(size_t k, batch_result &b);
+	int read_dc(size_t k, batch_result &b);
+	int close_context(int r);
+
+	const job_settings &job;
+	const std::vector<std::string> &files;
+	const std::vector<size_t> &file_blocks;
+	const std::atomic<bool> &abort;
+	const int device;
+	const size_t s0, s1;
+	file_settings dflt;  // the context's: the union of its files' types, thresh, filter
+	size_t n;            // streams of the context
+	const int bps;
+	// to the engine's thread: batches drained, oldest first
+	std::mutex mu;
+	std::condition_variable cv;
+	std::deque<batch_result> out;
+	bool done;
+	// the context (open_context .. close_context)
+	tfrec_amd_ctx *ctx;
+	int32_t max_events;
+	std::vector<int32_t> in_row;  // map_rows: the input row each stream reads
+	std::vector<bool> reads;      // the stream's file is read into its row (the first stream of the row)
+	size_t n_rows;
+	bool map;                     // streams share rows: the context's streams are mapped to them
+	std::vector<bool> in_tune, narrow_tune;  // -r: the stream has an input-rate tune / a tune behind the resampler (split_tunes)
+	// the reader thread: batch k goes to host[k % kBufs]; it may run at most kBufs batches ahead of the drain
+	size_t row;  // bytes of one input row of a batch
+	uint8_t *host[kBufs];
+	bool pinned[kBufs];
+	std::thread reader;
+	std::mutex rmu;
+	std::condition_variable rcv;
+	size_t filled, drained;  // batches read / batches whose buffer is free again
+	bool read_failed;
+};
+
+inline device_worker::device_worker(const job_settings &job_, const std::vector<std::string> &files_, const std::vector<size_t> &file_blocks_,
+			     const std::vector<file_settings> &settings, file_settings dflt_, int device_, size_t s0_, size_t s1_, int bps_,
+			     const std::atomic<bool> &abort_)
+	: rc(0), job(job_), files(files_), file_blocks(file_blocks_), abort(abort_), device(device_), s0(s0_), s1(s1_), dflt(dflt_),
+	  n(s1_ - s0_), bps(bps_), done(false), ctx(NULL), max_events(0), n_rows(0), map(false), row(0), filled(0), drained(0),
+	  read_failed(false)
+{
+	dflt.types = 0;
+	for (size_t s = s0; s < s1; s++)
+		dflt.types |= settings[s].types;
+	if (job.slots > 0)
+		n = std::min(n, (size_t)job.slots);
+	plan = plan_batches(file_blocks, settings, dflt, s0, s1, n, bps);
+}
+
+inline void device_worker::push(batch_result &&b)
+{
+	{
+		std::unique_lock<std::mutex> lk(mu);
+		cv.wait(lk, [&]() { return out.size() < 2; });  // the engine's thread is at most two batches behind
+		out.push_back(std::move(b));
+	}
+	cv.notify_all();
+}
+
+inline bool device_worker::pop(batch_result &b)
+{
+	std::unique_lock<std::mutex> lk(mu);
+	cv.wait(lk, [&]() { return !out.empty() || done; });
+	if (out.empty())
+		return false;
+	b = std::move(out.front());
+	out.pop_front();
+	lk.unlock();
+	cv.notify_all();
+	return true;
+}
+
+inline void device_worker::run()
+{
+	rc = work();
+	{
+		std::lock_guard<std::mutex> lk(mu);
+		done = true;
+	}
+	cv.notify_all();
+}
+
+inline int device_worker::work()
+{
+	map_rows();
+	int r = open_context();
+	if (r)
+		return r;
+	const int depth = std::max(1, std::min(tfrec_amd_fifo_depth(), TFREC_AMD_FIFO_DEPTH));
+	row = (size_t)(bps / job.unit()) * job.piece_bytes();
+	for (int b = 0; b < kBufs; b++) {
+		host[b] = (uint8_t *)tfrec_amd_host_alloc(n_rows * row);
+		pinned[b] = host[b] != NULL;  // per buffer: each is released by the allocator it came from
+		if (!host[b])  // no page-locked memory: this buffer's copies become synchronous, results are the same
+			host[b] = (uint8_t *)malloc(n_rows * row);
+	}
+	reader = std::thread([this]() { read_batches(); });
+	size_t queued = 0;
+	for (size_t k = 0; k < plan.size() && r == 0; k++) {
+		while (queued < plan.size() && queued < k + (size_t)depth && r == 0)
+			r = submit(queued++);
+		if (r)
+			break;
+		if (abort.load()) {
+			r = TFREC_AMD_E_STATE;
+			break;
+		}
+		batch_result b;
+		r = collect(k, b);
+		if (!r)
+			push(std::move(b));
+	}
+	return close_context(r);
+}
+
+// Which stream reads which input row.  Shared inputs (tfrec_amd_map_streams): without -n a stream carries one file for the whole
+// job, and the streams whose files are one path share that path's input row -- the file is opened and read once, staged and
+// copied once.  Decoders, stream indices and the order of the output stay per -L occurrence.  (A stream without a file reads
+// row 0; its events are dropped.)  Otherwise stream s reads row s.
+inline void device_worker::map_rows()
+{
+	in_row.assign(n, 0);
+	reads.assign(n, true);
+	std::vector<std::string> paths;
+	if (job.share() && !plan.empty())
+		for (size_t s = 0; s < n; s++) {
+			const int f = plan[0].file[s];
+			if (f < 0)
+				continue;
+			const size_t r = std::find(paths.begin(), paths.end(), files[f]) - paths.begin();
+			reads[s] = r == paths.size();
+			if (reads[s])
+				paths.push_back(files[f]);
+			in_row[s] = (int32_t)r;
+		}
+	map = job.share() && !plan.empty() && paths.size() < n;
+	n_rows = map ? std::max<size_t>(1, paths.size()) : n;
+	for (size_t s = 0; s < n && !map; s++)
+		in_row[s] = (int32_t)s;
+}
+
+// tfrec_amd_create*, then tfrec_amd_map_streams, then the enables the job asks for; a call that fails is named on stderr and
+// leaves no context behind
+inline int device_worker::open_context()
+{
+	tfrec_amd_config cfg;
+	memset(&cfg, 0, sizeof(cfg));
+	cfg.n_streams = (int32_t)n;
+	cfg.types_mask = dflt.types;
+	cfg.thresh = dflt.thresh;
+	cfg.filter_type = dflt.filter;
+	cfg.device = device;
+	cfg.max_blocks = bps;
+	// (BITS mode: every flush + a chunk per 512 bits, a slicer emits < 0.5 bit per decimated sample)
+	cfg.max_events = max_events = (int32_t)std::max<size_t>(4096, n * (size_t)bps * (job.bits_replay ? 256 : 64));
+	cfg.flags = job.ctx_flags();
+	in_tune.assign(n, false);
+	narrow_tune.assign(n, false);
+	const char *call = "tfrec_amd_create";
+	// (the rows are known: -z sizes the blocker for them)
+	int r = job.dc_windows		       ? tfrec_amd_create_dc(&cfg, job.fmt, job.rate_p, job.rate_q, job.dc_windows, (int32_t)n_rows, &ctx)
+		: job.fmt != TFREC_AMD_FMT_U8  ? tfrec_amd_create_format(&cfg, job.fmt, job.rate_p, job.rate_q, &ctx)
+		: job.resampled()	       ? tfrec_amd_create_rate(&cfg, job.rate_p, job.rate_q, &ctx)
+					       : tfrec_amd_create(&cfg, &ctx);
+	const bool created = r == 0;
+	if (!r && map) {
+		std::vector<int32_t> all(n);
+		for (size_t s = 0; s < n; s++)
+			all[s] = (int32_t)s;
+		call = "tfrec_amd_map_streams";
+		r = tfrec_amd_map_streams(ctx, all.data(), in_row.data(), (int)n);
+	}
+	if (!r && job.capture) {  // -S, sized so that no submit overflows: every sample, and a stream's runs are >= 356 samples long but two
+		call = "tfrec_amd_enable_capture";
+		r = tfrec_amd_enable_capture(ctx, (uint32_t)(n * ((size_t)bps * TFREC_AMD_BLOCK_DEC / 356 + 3)),
+					     (uint64_t)n * (uint64_t)bps * TFREC_AMD_BLOCK_DEC);
+	}
+	if (!r && job.spectrum) {  // -P: the one file's row
+		call = "tfrec_amd_enable_spectrum";
+		r = tfrec_amd_enable_spectrum(ctx, job.spec_n, job.spec_g, 1);
+	}
+	if (!r && job.occupancy()) {  // -A: the detector on its records
+		call = "tfrec_amd_enable_occupancy";
+		r = tfrec_amd_enable_occupancy(ctx, (uint32_t)job.occ_ratio, (uint32_t)job.occ_rel);
+	}
+	if (r) {
+		fprintf(stderr, "%s (device %d): %s (%s)\n", call, device, tfrec_amd_strerror(r), tfrec_amd_last_error());
+		if (created)
+			tfrec_amd_destroy(ctx);
+	}
+	return r;
+}
+
+// the reader thread: a file is opened when its first batch is read and closed after its last one (a queue of thousands of files)
+inline void device_worker::read_batches()
+{
+	std::vector<FILE *> fd(s1 - s0, (FILE *)NULL);
+	std::vector<size_t> fleft(file_blocks.begin() + s0, file_blocks.begin() + s1);
+	const size_t piece = job.piece_bytes();
+	for (size_t k = 0; k < plan.size(); k++) {
+		{
+			std::unique_lock<std::mutex> lk(rmu);
+			rcv.wait(lk, [&]() { return k < drained + kBufs; });
+		}
+		const batch_plan &b = plan[k];
+		uint8_t *buf = host[k % kBufs];
+		for (size_t s = 0; s < n; s++) {
+			if (n_rows < n && (!reads[s] || b.file[s] < 0))
+				continue;  // (a shared row is filled by its first stream)
+			uint8_t *dst = buf + (size_t)in_row[s] * row;
+			const size_t want = (size_t)(b.nb / job.unit()) * piece;
+			const int f = b.file[s];
+			size_t got = 0;
+			if (f >= 0) {
+				FILE *&fp = fd[f - s0];
+				if (!fp && !read_failed && !(fp = fopen(files[f].c_str(), "rb"))) {
+					perror(files[f].c_str());
+					read_failed = true;
+				}
+				if (fp) {
+					got = fread(dst, 1, want, fp);
+					got -= got % piece;
+					size_t &left = fleft[f - s0];
+					left -= std::min<size_t>(left, (size_t)b.nb);
+					if (left == 0) {
+						fclose(fp);
+						fp = NULL;
+					}
+				}
+			}
+			// a shorter file is padded with silence (its events are cut by the engine): u8 128, zero in every other format
+			memset(dst + got, job.fmt != TFREC_AMD_FMT_U8 ? 0 : 0x80, want - got);
+		}
+		{
+			std::lock_guard<std::mutex> lk(rmu);
+			filled = k + 1;
+		}
+		rcv.notify_all();
+	}
+	for (FILE *fp : fd)
+		if (fp)
+			fclose(fp);
+}
+
+// batch k, once the reader has filled its buffer: the resets, configures and tunes its plan asks for, then the submit
+inline int device_worker::submit(size_t k)
+{
+	{
+		std::unique_lock<std::mutex> lk(rmu);
+		rcv.wait(lk, [&]() { return filled > k; });
+	}
+	const batch_plan &b = plan[k];
+	int r = 0;
+	if (job.dc_windows && !job.share()) {
+		// -n with -z: a slot that starts a new file -- by a reset, or by the configure or tune its next file needs -- starts a new
+		// DC estimate too.  A stream's row is its own here (nothing is shared); duplicates are allowed.
+		std::vector<int32_t> rows(b.reset);
+		rows.insert(rows.end(), b.conf.begin(), b.conf.end());
+		rows.insert(rows.end(), b.tune.begin(), b.tune.end());
+		r = tfrec_amd_reset_dc_rows(ctx, rows.data(), (int)rows.size());
+	}
+	if (!r && !b.reset.empty())  // the streams whose file ended in the batch before: fresh receivers for the next files
+		r = tfrec_amd_reset_streams(ctx, b.reset.data(), (int)b.reset.size());
+	if (!r && !b.conf.empty())  // ... with the settings of their next file
+		r = tfrec_amd_configure_streams(ctx, b.conf.data(), b.conf_cfg.data(), (int)b.conf.size());
+	if (!r && !b.tune.empty() && job.resampled()) {  // ... and tunes, -r: behind the resampler and ahead of it (split_tunes)
+		const tune_calls c = split_tunes(b.tune, b.tune_hz, in_tune, narrow_tune);
+		if (!c.narrow.empty())
+			r = tfrec_amd_tune_streams(ctx, c.narrow.data(), c.narrow_hz.data(), (int)c.narrow.size());
+		if (!r && !c.input.empty())
+			r = tfrec_amd_tune_streams_input(ctx, c.input.data(), c.input_hz.data(), (int)c.input.size());
+	} else if (!r && !b.tune.empty()) {  // ... and tunes
+		r = job.wide ? tfrec_amd_tune_streams_wide(ctx, b.tune.data(), b.tune_hz.data(), (int)b.tune.size())
+			     : tfrec_amd_tune_streams(ctx, b.tune.data(), b.tune_hz.data(), (int)b.tune.size());
+	}
+	return r ? r : tfrec_amd_submit_host(ctx, host[k % kBufs], row, b.nb);
+}
+
+// -S: the batch's captures.  stream -> file, as for the events; a run is cut at its file's end
+inline int device_worker::read_captures(size_t k, batch_result &b)
+{
+	uint32_t nr = 0;
+	uint64_t np = 0;
+	int r = tfrec_amd_read_captures(ctx, NULL, 0, &nr, NULL, 0, &np);  // (the counts: E_INVAL for want of room)
+	if (r == TFREC_AMD_E_INVAL && nr) {
+		b.runs.resize((size_t)nr + 1);
+		b.pool.resize(2 * (size_t)np + 2);
+		r = tfrec_amd_read_captures(ctx, b.runs.data(), b.runs.size(), &nr, b.pool.data(), b.pool.size() / 2, &np);
+	}
+	size_t have = nr;
+	if (r == TFREC_AMD_E_OVERFLOW) {  // the runs that fitted were returned (n_samples == 0 ends them); the job goes on
+		for (have = 0; have < b.runs.size() && b.runs[have].n_samples; have++) {
+		}
+		fprintf(stderr, "tfrec_amd: device %d batch %zu: capture overflow, %zu of %u runs kept\n", device, k, have, (unsigned)nr);
+		r = 0;
+	}
+	if (r)
+		return r;
+	const std::vector<int> &file = plan[k].file;
+	size_t kept = 0;
+	for (size_t q = 0; q < have; q++) {
+		tfrec_amd_run x = b.runs[q];
+		if (x.stream >= file.size() || file[x.stream] < 0)
+			continue;
+		const long long end = (long long)file_blocks[file[x.stream]] * TFREC_AMD_BLOCK_DEC;
+		if (x.start_sample >= end)
+			continue;
+		x.n_samples = (uint32_t)std::min<long long>(x.n_samples, end - x.start_sample);
+		b.file.push_back(file[x.stream]);
+		b.runs[kept++] = x;
+	}
+	b.runs.resize(kept);
+	return 0;
+}
+
+// -z -D: the last estimate of every file's row
+inline int device_worker::read_dc(size_t k, batch_result &b)
+{
+	std::vector<int16_t> d;
+	int r = 0;
+	for (size_t s = 0; s < n && r == 0; s++) {
+		if (plan[k].file[s] < 0 || !reads[s])
+			continue;
+		int nw = 0;
+		r = tfrec_amd_read_dc(ctx, in_row[s], NULL, 0, &nw);  // (the count: E_INVAL for want of room)
+		if (r == TFREC_AMD_E_INVAL && nw > 0) {
+			d.resize(2 * (size_t)nw);
+			r = tfrec_amd_read_dc(ctx, in_row[s], d.data(), (size_t)nw, &nw);
+			if (r == 0) {
+				b.dc_file.push_back(plan[k].file[s]);
+				b.dc_last.push_back(d[2 * (size_t)nw - 2]);
+				b.dc_last.push_back(d[2 * (size_t)nw - 1]);
+			}
+		}
+	}
+	return r;
+}
+
+// batch k's results: its side outputs (captures, then occupancy or spectrum, then DC, then levels), then the drain that pops it
+// and frees its host buffer for the reader
+inline int device_worker::collect(size_t k, batch_result &b)
+{
+	int r = job.capture ? read_captures(k, b) : 0;
+	if (!r && job.occupancy()) {  // -A: the detector's records in place of the spectrum's, 16 + N / 8 bytes each
+		int nr = 0;
+		r = tfrec_amd_read_occupancy(ctx, 0, NULL, NULL, 0, &nr);  // (the count: E_INVAL for want of room)
+		if (r == TFREC_AMD_E_INVAL && nr > 0) {
+			b.occ_recs.resize((size_t)nr);
+			b.occ_bits.resize((size_t)nr * (job.spec_n / 32));
+			r = tfrec_amd_read_occupancy(ctx, 0, b.occ_recs.data(), b.occ_bits.data(), (size_t)nr, &nr);
+		}
+	} else if (!r && job.spectrum) {  // -P: the batch's spectrum records
+		int nr = 0;
+		r = tfrec_amd_read_spectrum(ctx, 0, NULL, NULL, 0, NULL, &nr);  // (the count: E_INVAL for want of room)
+		if (r == TFREC_AMD_E_INVAL && nr > 0) {
+			b.spec_sum.resize((size_t)nr * job.spec_n);
+			b.spec_peak.resize((size_t)nr * job.spec_n);
+			b.spec_frames.resize((size_t)nr);
+			r = tfrec_amd_read_spectrum(ctx, 0, b.spec_sum.data(), b.spec_peak.data(), (size_t)nr, b.spec_frames.data(), &nr);
+		}
+	}
+	if (!r && job.dc_windows && job.dbg > 0)
+		r = read_dc(k, b);
+	if (!r && job.scan) {  // -s: the batch's level records
+		int nb = 0;
+		b.lv.resize(n * (size_t)bps);
+		r = tfrec_amd_read_levels(ctx, b.lv.data(), b.lv.size(), &nb);
+		b.lv.resize(n * (size_t)nb);
+	}
+	if (r)
+		return r;
+	b.ev.resize(max_events);
+	int nev = 0;
+	r = tfrec_amd_drain_events(ctx, b.ev.data(), (int)b.ev.size(), &nev);
+	if (r == TFREC_AMD_E_OVERFLOW) {  // the events that fit were returned; the replay goes on (those beyond are lost)
+		fprintf(stderr, "tfrec_amd: device %d batch %zu: event buffer overflow, %d events kept\n", device, k, nev);
+		r = 0;
+	}
+	if (r)
+		return r;
+	{
+		std::lock_guard<std::mutex> lk(rmu);
+		drained = k + 1;  // batch k's host buffer may be refilled
+	}
+	rcv.notify_all();
+	// stream -> the index of the file it carried in this batch, within the whole job (none: silence, dropped)
+	const std::vector<int> &file = plan[k].file;
+	int kept = 0;
+	for (int q = 0; q < nev; q++)
+		if (b.ev[q].stream < file.size() && file[b.ev[q].stream] >= 0) {
+			b.ev[kept] = b.ev[q];
+			b.ev[kept++].stream = (uint32_t)file[b.ev[q].stream];
+		}
+	b.ev.resize(kept);
+	return 0;
+}
+
+// the end of work(), r: how the batches went -> the worker's result
+inline int device_worker::close_context(int r)
+{
+	if (r)
+		fprintf(stderr, "tfrec_amd (device %d): %s (%s)\n", device, tfrec_amd_strerror(r), tfrec_amd_last_error());
+	{
+		std::lock_guard<std::mutex> lk(rmu);
+		drained = plan.size() + kBufs;  // let the reader run out after an error
+	}
+	rcv.notify_all();
+	reader.join();
+	tfrec_amd_destroy(ctx);
+	for (int b = 0; b < kBufs; b++) {
+		if (pinned[b])
+			tfrec_amd_host_free(host[b]);
+		else
+			free(host[b]);
+	}
+	return !r && read_failed ? TFREC_AMD_E_INVAL : r;
+}
+
+#endif

@@ -19,7 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/tfrec_amd.h"
+#include "job.h"
 #ifdef TFREC_AMD_REFERENCE_PLUGINS
 #include "decoder.h"
 #include "tfa1.h"
@@ -81,28 +81,8 @@ private:
 	long n_records;
 };
 
-// -T, -t, -W and the tune of one dump file (tfrec_gpu -p; tune: -f minus -c, in Hz, tfrec_amd_tune_streams)
-struct file_settings {
-	int types, thresh, filter;
-	int tune;  // Hz
-	bool same_config(const file_settings &o) const { return types == o.types && thresh == o.thresh && filter == o.filter; }
-	bool operator==(const file_settings &o) const { return same_config(o) && tune == o.tune; }
-	bool operator!=(const file_settings &o) const { return !(*this == o); }
-};
-
-// -A: one line of the channel list: a carrier (one bin, listed, never scanned) or a group of active bins lo .. hi (signed bins: b = k
-// for k < N/2, else k - N); hits: the carrier's, or the largest of the group's bins
-struct occ_channel {
-	bool carrier;
-	long khz;
-	int lo, hi;
-	unsigned long long hits;
-	bool in_range;  // a group the scan can reach: |khz - center| * 1000 <= fs_in / 2 - 192000
-};
-// Group the hit counts of a recording into channels (tfrec_amd/occupancy.py: channels()), exact integers: hits[k] of
-// `records` records, bin k; ascending frequency.
-std::vector<occ_channel> occupancy_channels(const std::vector<unsigned long long> &hits, unsigned long long records, int n_bins, long fs_in,
-					    long center_khz, long join_hz);
+// The slot-indexed protocol handlers of one stream (NULL: the type is not in `types`), registered like main.cpp:173-218
+std::vector<decoder *> make_decoders(int types, batch_sink *const *sink, int stream);
 
 class gpu_engine {
 public:
@@ -124,28 +104,28 @@ public:
 	// the demodulators hand to decoder::store_bit (TFREC_AMD_F_BITS) and every flush; the decoders then run exactly as
 	// inside the reference -- including what store_bit itself prints (tfa2.cpp:294-300 "Inverted SYNC").  Default off:
 	// the byte-level replay (store_bytes + flush) moves 64 bytes per window instead of every bit.
-	void set_bits_replay(bool on) { bits_replay = on; }
+	void set_bits_replay(bool on) { job.bits_replay = on; }
 	// -n: at most n streams per device context.  The dump files of a device go through them as a queue, in command-line order:
 	// when a file's last block has been submitted its stream is reset (tfrec_amd_reset_streams) -- or configured and / or tuned
 	// for the next file, when that one's settings or tune differ -- and the next file starts there with the next batch.  0 (default): one stream
 	// per file for the whole job.  A batch that carries a reset does not overlap the batch before it on the GPU (DESIGN.md
 	// 6b): a queue of mixed-length files runs at about half the throughput.
-	void set_slots(int n) { slots = n; }
+	void set_slots(int n) { job.slots = n; }
 	// -x: the dump files are 15.36 MS/s u8 dumps (TFREC_AMD_F_INPUT_10X, blocks of TFREC_AMD_BLOCK_BYTES_10X), and a file's tune
 	// is a wide tune (tfrec_amd_tune_streams_wide, up to +-7679 kHz) ahead of the 10:1 stage.
 	// In both modes, without -n: a path given to several -L is opened and read once and occupies one input row of the batch; its
 	// streams are mapped to it (tfrec_amd_map_streams).  Decoders, stream indices and output order stay per -L occurrence.
-	void set_wide(bool on) { wide = on; }
+	void set_wide(bool on) { job.wide = on; }
 	// -r: the dump files are u8 dumps at 1536000 p / q samples per second (tfrec_amd_create_rate).  A submit then
 	// carries a multiple of `unit` blocks, the odd part of q (the caller rounds blocks_per_submit up to one), a file is read in
 	// pieces of that many blocks and its trailing partial piece is dropped; everything else -- the tail of a file, -n, -d,
 	// shared paths, tunes and settings -- is as without it, and a file's tune beyond +-767 kHz (up to half the rate) becomes the
 	// input-rate tune ahead of the resampler (tfrec_amd_tune_streams_input).  Excludes set_wide.
-	void set_rate(int p, int q);
+	void set_rate(int p, int q) { job.rate_p = p; job.rate_q = q; }
 	// -F: the dump files hold TFREC_AMD_FMT_* samples instead of u8 (tfrec_amd_create_format), at the rate of
 	// set_rate or -- without one -- at 1.536 MS/s.  A block of a file is 65536 p / q * bytes per complex sample / 2 bytes, and a
 	// shorter file is padded with the format's silence (zero); everything else is as with u8.  Excludes set_wide.
-	void set_format(int format) { fmt = format; }
+	void set_format(int format) { job.fmt = format; }
 	// -s: scan mode.  The dump files are ONE recording given once per channel, khz[i] the receive frequency of
 	// file i (ascending; the files' tunes place them): the streams share the recording's input row as repeated paths always do,
 	// the context runs with TFREC_AMD_F_LEVELS, and instead of replaying telegrams into the decoders run() sums every channel's
@@ -155,14 +135,14 @@ public:
 	//        thresh=<the last block's> telegrams=<events with status 1>
 	// preceded, with dbg > 0, by the reference's per-block line "<kHz> Trigger ratio <triggered>/8192, avg <triggered_avg>"
 	// (fm_demod.cpp:61) for every block.  One device, no -n.
-	void set_scan(const std::vector<long> &khz) { scan = true; scan_khz = khz; }
+	void set_scan(const std::vector<long> &khz) { job.scan = true; job.scan_khz = khz; }
 	// -S: the squelched recorder (tfrec_amd_enable_capture).  Every context captures the IQ of its streams' trigger
 	// windows; run() writes <prefix>.idx -- text, one line "<file index> <stream> <start_sample> <n_samples> <thresh> <flags>" per run
 	// in submit order, stream = the file's stream on its device, start_sample counted within the file -- and, for every file with
 	// a run, <prefix>.<file index>.cs16: the file's captured samples appended submit by submit, 384 kS/s int16 interleaved I, Q.
 	// The capture is sized from the batch's blocks and the stream count so that no submit can overflow it; should one, a warning
 	// goes to stderr per submit and the run goes on.  Runs are cut at the file's end (the padding behind it is not the file's).
-	void set_capture(const std::string &prefix) { capture = true; cap_prefix = prefix; }
+	void set_capture(const std::string &prefix) { job.capture = true; job.cap_prefix = prefix; }
 	// -P: the power spectrum of the one -L file's input row (tfrec_amd_enable_spectrum on row 0): n_bins bins,
 	// frames_per_record frames per record, the file recorded at center_khz.  run() lists the bins' frequencies on stderr before a
 	// device is opened ("spec bin <kHz>", ascending) and prints, behind the telegram output and in ascending frequency, per bin
@@ -171,10 +151,10 @@ public:
 	// The bin's frequency is center + (k < N/2 ? k : k - N) fs_in / N.  One file, one device, no -n.
 	void set_spectrum(int n_bins, int frames_per_record, long center_khz)
 	{
-		spectrum = true;
-		spec_n = n_bins;
-		spec_g = frames_per_record;
-		spec_center = center_khz;
+		job.spectrum = true;
+		job.spec_n = n_bins;
+		job.spec_g = frames_per_record;
+		job.spec_center = center_khz;
 	}
 	// -A, pass 1: with set_spectrum, the occupancy detector on the file's spectrum records
 	// (tfrec_amd_enable_occupancy: ratio, rel).  run() reads the detector's records instead of the spectrum's, replays no telegram
@@ -187,9 +167,9 @@ public:
 	// channels a scan can reach, ascending.
 	void set_occupancy(int ratio, int rel, long join_hz)
 	{
-		occ_ratio = ratio;
-		occ_rel = rel;
-		occ_join = join_hz;
+		job.occ_ratio = ratio;
+		job.occ_rel = rel;
+		job.occ_join = join_hz;
 	}
 	const std::vector<long> &found_khz() const { return occ_found; }
 	// -z: the DC blocker (tfrec_amd_create_dc) over `windows` windows of 512 input samples, on every input row of every
@@ -197,7 +177,7 @@ public:
 	// row of a stream that starts a new file has its DC state reset with the stream (tfrec_amd_reset_dc_rows).  With dbg > 0 run()
 	// prints "dc <file> I=<d> Q=<d>" per submit and file: the estimate of the submit's last window of the file's row.  Under -A
 	// only pass 2 is given it: pass 1's spectrum reads the raw rows either way.  Excludes set_wide.
-	void set_dc(int windows) { dc_windows = windows; }
+	void set_dc(int windows) { job.dc_windows = windows; }
 	// returns 0 on success, a TFREC_AMD_E_* code otherwise
 	int run();
 	// decoders of stream s in slot order (NULL for slots not registered)
@@ -208,30 +188,17 @@ private:
 	void replay(const tfrec_amd_event &ev);
 	std::vector<std::string> files;
 	std::vector<file_settings> settings;  // per file
-	int types, thresh, filter, dbg, bps;
+	file_settings dflt;                   // the constructor's types, thresh, filter
+	int bps;
 	std::vector<int> devices;
+	job_settings job;                     // the set_* calls' (job.h)
 	std::vector<std::vector<decoder *> > decs;
 	std::vector<long long> stream_samples;  // decimated samples each file really holds
 	long n_telegrams;
 	batch_sink *sink;  // (the decoders hold its address)
 	pipe_sink *psink;
 	int out_mode;
-	bool bits_replay;
-	int slots;
-	bool wide;
-	int rate_p, rate_q, unit;  // set_rate (1, 1, 1: none)
-	int fmt;                   // set_format (TFREC_AMD_FMT_U8: none)
-	bool scan = false;         // set_scan
-	std::vector<long> scan_khz;
-	bool capture = false;      // set_capture
-	std::string cap_prefix;
-	bool spectrum = false;     // set_spectrum
-	int spec_n = 0, spec_g = 0;
-	long spec_center = 0;
-	int occ_ratio = 0, occ_rel = 0;  // set_occupancy (0: none)
-	long occ_join = 0;
 	std::vector<long> occ_found;
-	int dc_windows = 0;        // set_dc (0: none)
 };
 
 #endif

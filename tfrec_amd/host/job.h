@@ -1,0 +1,363 @@
+// tfrec_amd/host/job.h -- the pure half of tfrec_gpu's engine: what a job is, how its files are cut into batches, and what
+// becomes of a batch's results.  Functions of small inputs only: nothing here opens a device, calls the C ABI or knows a
+// decoder -- include/tfrec_amd.h is included for its struct types -- so all of it runs in a CPU test (tests/host_engine_driver.cpp).
+// device_worker.h is the half that drives a context with these plans; gpu_engine.cpp puts the two together.
+#ifndef TFREC_AMD_HOST_JOB_H
+#define TFREC_AMD_HOST_JOB_H
+
+#include <stdint.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/tfrec_amd.h"
+
+// -T, -t, -W and the tune of one dump file (tfrec_gpu -p; tune: -f minus -c, in Hz, tfrec_amd_tune_streams)
+struct file_settings {
+	int types, thresh, filter;
+	int tune;  // Hz
+	bool same_config(const file_settings &o) const { return types == o.types && thresh == o.thresh && filter == o.filter; }
+	bool operator==(const file_settings &o) const { return same_config(o) && tune == o.tune; }
+	bool operator!=(const file_settings &o) const { return !(*this == o); }
+};
+
+// Everything gpu_engine's set_* calls store (gpu_engine.h says what each mode does), one copy for the engine and all its workers,
+// and the input geometry that follows from it.
+struct job_settings {
+	bool wide = false;             // set_wide
+	int rate_p = 1, rate_q = 1;    // set_rate (1 / 1: none)
+	int fmt = TFREC_AMD_FMT_U8;    // set_format
+	int slots = 0;                 // set_slots (0: one stream per file)
+	bool bits_replay = false;      // set_bits_replay
+	int dbg = 0;                   // the constructor's: -1 quiet, 0 normal, >= 1 debug
+	bool scan = false;             // set_scan
+	std::vector<long> scan_khz;
+	bool capture = false;          // set_capture
+	std::string cap_prefix;
+	bool spectrum = false;         // set_spectrum
+	int spec_n = 0, spec_g = 0;
+	long spec_center = 0;
+	int occ_ratio = 0, occ_rel = 0;  // set_occupancy (0: none)
+	long occ_join = 0;
+	int dc_windows = 0;            // set_dc (0: none)
+
+	bool resampled() const { return rate_p != 1 || rate_q != 1; }
+	bool occupancy() const { return spectrum && occ_ratio; }  // -A, pass 1
+	bool share() const { return slots <= 0; }  // one stream per file for the whole job: a path given several times is read once
+	// -r: the blocks a piece of a file holds, the odd part of q (1 without -r): every batch carries a multiple of it
+	int unit() const
+	{
+		int u = rate_q;
+		while (u % 2 == 0)
+			u /= 2;
+		return u;
+	}
+	// bytes of a piece of `unit` blocks of a file: 65536 p / q x unit is a whole number (q is unit times a power of two <= 64);
+	// -F: times the format's bytes per complex sample / 2; 655360 with -x
+	size_t piece_bytes() const
+	{
+		const size_t sample_bytes = fmt == TFREC_AMD_FMT_F32 ? 8 : fmt == TFREC_AMD_FMT_S16 ? 4 : 2;
+		return wide ? (size_t)TFREC_AMD_BLOCK_BYTES_10X : (size_t)TFREC_AMD_BLOCK_BYTES * rate_p * unit() / rate_q * sample_bytes / 2;
+	}
+	// input samples of `blocks` blocks (rounded down); of one block: the default record of -P and -A
+	unsigned long long input_samples(unsigned long long blocks) const
+	{
+		return wide ? blocks * 327680ull : blocks * 32768ull * rate_p / rate_q;
+	}
+	long fs_in() const { return wide ? 15360000L : 1536000L * rate_p / rate_q; }  // input samples per second
+	uint32_t ctx_flags() const  // TFREC_AMD_F_* of every context
+	{
+		return (bits_replay ? (TFREC_AMD_F_BITS | TFREC_AMD_F_ALL_FLUSHES) : 0u) | (wide ? TFREC_AMD_F_INPUT_10X : 0u) |
+		       (scan ? TFREC_AMD_F_LEVELS : 0u);
+	}
+};
+
+// The files [s0, s1) of device d of nd: contiguous ranges of the n files, as evenly as possible (tfrec_amd/shard.py)
+inline void shard_range(size_t n, size_t nd, size_t d, size_t &s0, size_t &s1)
+{
+	const size_t base = n / nd, rem = n % nd;
+	s0 = d * base + std::min(d, rem);
+	s1 = s0 + base + (d < rem ? 1 : 0);
+}
+
+// One batch of a device context: the blocks every stream gets, the dump file each stream (slot) reads (-1: none, silence),
+// the streams reset before it is submitted (their previous file ended in the batch before), and the streams configured
+// or tuned before it (their next file's settings or tune differ from the stream's current ones: a configure or a tune is a
+// reset with new settings)
+struct batch_plan {
+	int nb;
+	std::vector<int> file;
+	std::vector<int32_t> reset;
+	std::vector<int32_t> conf;
+	std::vector<tfrec_amd_stream_config> conf_cfg;
+	std::vector<int32_t> tune;
+	std::vector<int32_t> tune_hz;
+};
+
+// The batches that push the files [s0, s1) through nslots streams of bps blocks (file_blocks: blocks of every file of the job).
+// Files take free streams in order; a file's last batch may be partial (padded with silence, its events cut by the engine).
+// A batch has bps blocks unless no stream needs that many.  With one stream per file this is the plan of a run without -n:
+// every file starts in the first batch and no stream is ever reset.
+// settings: every file's; dflt: the context's.
+inline std::vector<batch_plan> plan_batches(const std::vector<size_t> &file_blocks, const std::vector<file_settings> &settings,
+					    const file_settings &dflt, size_t s0, size_t s1, size_t nslots, int bps)
+{
+	std::vector<batch_plan> plan;
+	std::vector<file_settings> has(nslots, dflt);  // the settings each stream runs with
+	std::vector<int> cur(nslots, -1);
+	std::vector<size_t> left(nslots, 0);    // blocks of the stream's file still to submit
+	std::vector<bool> used(nslots, false);  // the stream has carried a file: reset it before the next one
+	size_t next = s0;
+	for (;;) {
+		batch_plan b;
+		for (size_t j = 0; j < nslots; j++) {
+			while (cur[j] < 0 && next < s1) {
+				const size_t f = next++;
+				if (file_blocks[f] == 0)
+					continue;  // (no block, no event)
+				cur[j] = (int)f;
+				left[j] = file_blocks[f];
+				if (settings[f] != has[j]) {
+					if (!settings[f].same_config(has[j])) {
+						b.conf.push_back((int32_t)j);
+						b.conf_cfg.push_back(tfrec_amd_stream_config{ settings[f].types, settings[f].thresh, settings[f].filter, 0 });
+					}
+					if (settings[f].tune != has[j].tune) {
+						b.tune.push_back((int32_t)j);
+						b.tune_hz.push_back(settings[f].tune);
+					}
+					has[j] = settings[f];
+				} else if (used[j]) {
+					b.reset.push_back((int32_t)j);
+				}
+				used[j] = true;
+			}
+		}
+		size_t most = 0;
+		for (size_t j = 0; j < nslots; j++)
+			if (cur[j] >= 0)
+				most = std::max(most, left[j]);
+		if (most == 0)
+			break;
+		b.nb = (int)std::min<size_t>((size_t)bps, most);
+		b.file = cur;
+		for (size_t j = 0; j < nslots; j++)
+			if (cur[j] >= 0) {
+				left[j] -= std::min<size_t>(left[j], (size_t)b.nb);
+				if (left[j] == 0)
+					cur[j] = -1;
+			}
+		plan.push_back(std::move(b));
+	}
+	return plan;
+}
+
+// -r: a batch's tunes as the two calls they become.  An offset within +-767 kHz is a tune behind the resampler, as it always
+// was (tfrec_amd_tune_streams: narrow); a larger one is the input-rate tune ahead of it (tfrec_amd_tune_streams_input: input).
+// A stream that goes from one kind to the other (-n) has the other kind cleared to 0; all of it is one restart.  in_tune /
+// narrow_tune: per stream, whether it has a tune of that kind now -- a stream that never had one is never sent a clear for it.
+struct tune_calls {
+	std::vector<int32_t> narrow, narrow_hz, input, input_hz;
+};
+inline tune_calls split_tunes(const std::vector<int32_t> &tune, const std::vector<int32_t> &tune_hz, std::vector<bool> &in_tune,
+			      std::vector<bool> &narrow_tune)
+{
+	tune_calls c;
+	for (size_t i = 0; i < tune.size(); i++) {
+		const int32_t s = tune[i], hz = tune_hz[i];
+		const bool far = hz <= -768000 || hz >= 768000;
+		if (far || in_tune[s]) {
+			c.input.push_back(s);
+			c.input_hz.push_back(far ? hz : 0);
+			in_tune[s] = far;
+		}
+		if (!far || narrow_tune[s]) {
+			c.narrow.push_back(s);
+			c.narrow_hz.push_back(far ? 0 : hz);
+			narrow_tune[s] = !far && hz != 0;
+		}
+	}
+	return c;
+}
+
+// -A: one line of the channel list: a carrier (one bin, listed, never scanned) or a group of active bins lo .. hi (signed bins: b = k
+// for k < N/2, else k - N); hits: the carrier's, or the largest of the group's bins
+struct occ_channel {
+	bool carrier;
+	long khz;
+	int lo, hi;
+	unsigned long long hits;
+	bool in_range;  // a group the scan can reach: |khz - center| * 1000 <= fs_in / 2 - 192000
+};
+
+// floor(a / b) for b > 0
+inline long long floor_div(long long a, long long b) { return a / b - (a % b < 0 ? 1 : 0); }
+
+// Group the hit counts of a recording into channels (tfrec_amd/occupancy.py: channels()), exact integers: hits[k] of
+// `records` records, bin k; ascending frequency.
+inline std::vector<occ_channel> occupancy_channels(const std::vector<unsigned long long> &hits, unsigned long long records, int n_bins,
+						   long fs_in, long center_khz, long join_hz)
+{
+	struct item {
+		long long pos;  // twice the middle bin: the order of the list
+		occ_channel c;
+	};
+	std::vector<item> items;
+	int group = -1;  // index of the open group in items
+	for (int b = -n_bins / 2; b < n_bins / 2; b++) {
+		const unsigned long long h = hits[(size_t)(b < 0 ? b + n_bins : b)];
+		if (h < 1)
+			continue;
+		if (2 * h > records) {  // continuous, like a receiver's DC spike: listed, never scanned, and no part of a group
+			const long off = (long)floor_div(2LL * b * fs_in + 1000LL * n_bins, 2000LL * n_bins);
+			items.push_back(item{ 2LL * b, occ_channel{ true, center_khz + off, b, b, h, false } });
+			continue;
+		}
+		if (group >= 0 && (long long)(b - items[group].c.hi - 1) * fs_in <= (long long)join_hz * n_bins) {
+			items[group].c.hi = b;
+			items[group].c.hits = std::max(items[group].c.hits, h);
+			continue;
+		}
+		group = (int)items.size();
+		items.push_back(item{ 0, occ_channel{ false, 0, b, b, h, false } });
+	}
+	for (item &it : items) {
+		if (it.c.carrier)
+			continue;
+		const long off = (long)floor_div((long long)(it.c.lo + it.c.hi) * fs_in + 1000LL * n_bins, 2000LL * n_bins);
+		it.pos = it.c.lo + it.c.hi;
+		it.c.khz = center_khz + off;
+		it.c.in_range = 2000LL * (off < 0 ? -off : off) <= (long long)fs_in - 384000;
+	}
+	std::stable_sort(items.begin(), items.end(), [](const item &a, const item &b) { return a.pos < b.pos; });
+	std::vector<occ_channel> out;
+	for (const item &it : items)
+		out.push_back(it.c);
+	return out;
+}
+
+// What one batch of one device brings to the engine's thread: its flush events (stream = the file's index in the job), and
+// -s: its level records, [stream][the batch's blocks]
+// -S: the runs that belong to a file (file[i]: its index in the job), cut at the file's end, and the batch's sample pool, which
+//     their pool_offset indexes
+// -P: the spectrum records of input row 0, [record][bin], and their frame counts
+// -A: the detector's records of row 0 and their bitmap words, [record][N / 32]
+// -z with -D: per file of the batch its index in the job and the last window's {d_I, d_Q} of its row
+struct batch_result {
+	std::vector<tfrec_amd_event> ev;
+	std::vector<tfrec_amd_level> lv;
+	std::vector<tfrec_amd_run> runs;
+	std::vector<int> file;
+	std::vector<int16_t> pool;
+	std::vector<uint64_t> spec_sum, spec_peak;
+	std::vector<uint32_t> spec_frames;
+	std::vector<tfrec_amd_occupancy> occ_recs;
+	std::vector<uint32_t> occ_bits;
+	std::vector<int> dc_file;
+	std::vector<int16_t> dc_last;
+};
+
+// ---- the sums behind the output modes' tables, one consumer per mode: begin() prints what the mode says before a device is
+// opened, take() is given every batch in the order of the output, finish() prints what follows the last one.  take() only adds up
+// and is defined here; begin() and finish(), and the two consumers that do nothing but write (-S, -z -D), are gpu_engine.cpp's.
+
+// -P: the spectrum table (gpu_engine.h: set_spectrum).  Per bin the sum over every record (a record's sum stays below 2^63, a long
+// file's total need not), the peak, the frames; with -D every record as it came.  Under -A only begin() is used.
+struct spectrum_table {
+	int n;
+	bool keep;  // -D
+	std::vector<double> khz;  // bin k lies at center + (k < N/2 ? k : k - N) fs_in / N; listed (and printed) in ascending frequency
+	std::vector<int> order;
+	std::vector<unsigned __int128> total;
+	std::vector<uint64_t> peak, rec_sum, rec_peak;
+	std::vector<uint32_t> rec_frames;
+	unsigned long long frames;
+	spectrum_table() : n(0), keep(false), frames(0) {}
+	void begin(const job_settings &job);
+	void take(const batch_result &b)
+	{
+		for (size_t q = 0; q < b.spec_frames.size(); q++) {
+			frames += b.spec_frames[q];
+			for (int k = 0; k < n; k++) {
+				total[k] += b.spec_sum[q * n + k];
+				peak[k] = std::max(peak[k], b.spec_peak[q * n + k]);
+			}
+		}
+		if (keep) {
+			rec_sum.insert(rec_sum.end(), b.spec_sum.begin(), b.spec_sum.end());
+			rec_peak.insert(rec_peak.end(), b.spec_peak.begin(), b.spec_peak.end());
+			rec_frames.insert(rec_frames.end(), b.spec_frames.begin(), b.spec_frames.end());
+		}
+	}
+	void finish() const;
+};
+
+// -A, pass 1: the channel list (gpu_engine.h: set_occupancy).  Per bin the records of the file in which it was hit, the records, and
+// the file's blocks the batches so far held.
+struct occupancy_list {
+	const job_settings *job;
+	std::vector<unsigned long long> hits;
+	unsigned long long records, blocks;
+	std::vector<long> found;  // the channels a scan can reach, ascending
+	occupancy_list() : job(NULL), records(0), blocks(0) {}
+	void begin(const job_settings &j);
+	// a batch of nb blocks of the file of file_blocks blocks -> how many of its records, from the first on, are the file's
+	size_t take(const batch_result &b, unsigned long long nb, unsigned long long file_blocks)
+	{
+		// the file's samples in this batch: a record that begins behind them lies in the padding and is not the file's
+		const unsigned long long real_samples = job->input_samples(std::min(nb, file_blocks - std::min(file_blocks, blocks)));
+		const int n = job->spec_n;
+		blocks += nb;
+		size_t q = 0;
+		for (; q < b.occ_recs.size() && (unsigned long long)q * job->spec_g * n < real_samples; q++) {
+			records++;
+			for (int k = 0; k < n; k++)
+				hits[k] += (b.occ_bits[q * (n / 32) + (k >> 5)] >> (k & 31)) & 1u;
+		}
+		return q;
+	}
+	int finish();
+};
+
+// -s: the scan table (gpu_engine.h: set_scan).  Per channel (file) the sums of its level records, its telegrams, and with -D
+// every record.
+struct scan_table {
+	struct channel_sum {
+		unsigned long long blocks = 0, pwr_sum = 0, over = 0, triggered = 0, telegrams = 0;
+		int peak = 0, thresh = 0;
+		std::vector<tfrec_amd_level> rec;
+	};
+	const job_settings *job;
+	const std::vector<file_settings> *settings;
+	std::vector<channel_sum> chan;
+	scan_table() : job(NULL), settings(NULL) {}
+	// the channel list, before a device is opened
+	void begin(const job_settings &j, const std::vector<file_settings> &per_file);
+	// a batch with its plan; file_blocks: the blocks every file really holds
+	void take(const batch_result &b, const batch_plan &p, const std::vector<size_t> &file_blocks)
+	{
+		for (size_t s = 0; s < p.file.size(); s++) {
+			if (p.file[s] < 0)
+				continue;
+			channel_sum &c = chan[p.file[s]];
+			for (int j = 0; j < p.nb && c.blocks < file_blocks[p.file[s]]; j++) {  // (not the padding behind the file's end)
+				const tfrec_amd_level &r = b.lv[s * (size_t)p.nb + j];
+				c.blocks++;
+				c.pwr_sum += r.pwr_sum;
+				c.over += (unsigned long long)r.n_over;
+				c.triggered += (unsigned long long)r.triggered;
+				c.peak = std::max(c.peak, (int)r.pwr_max);
+				c.thresh = r.thresh;
+				if (job->dbg > 0)
+					c.rec.push_back(r);
+			}
+		}
+		for (size_t q = 0; q < b.ev.size(); q++)
+			if (b.ev[q].status == 1 && b.ev[q].end_sample < (int64_t)file_blocks[b.ev[q].stream] * TFREC_AMD_BLOCK_DEC)
+				chan[b.ev[q].stream].telegrams++;
+	}
+	void finish() const;
+};
+
+#endif

@@ -101,15 +101,35 @@ struct spec {
 	long freq = -1;  // kHz
 };
 
-// a frequency in kHz: a decimal integer > 0 -> false if it is not one
-static bool parse_khz(const char *v, long &out)
+// a decimal integer within lo .. hi that is the whole string -> false if it is not one (out is then untouched)
+static bool parse_long(const char *v, long lo, long hi, long &out)
 {
 	char *end = NULL;
 	const long x = strtol(v, &end, 10);
-	if (end == v || *end || x <= 0 || x > 100000000L)
+	if (end == v || *end || x < lo || x > hi)
 		return false;
 	out = x;
 	return true;
+}
+
+// a frequency in kHz: a decimal integer > 0 -> false if it is not one
+static bool parse_khz(const char *v, long &out) { return parse_long(v, 1, 100000000L, out); }
+
+// the optional argument of -A and -z: attached (-z64, -A32,16), or the next word where that starts with a digit; NULL: none
+static const char *optional_arg(int argc, char **argv)
+{
+	if (!optarg && optind < argc && argv[optind][0] >= '0' && argv[optind][0] <= '9')
+		return argv[optind++];
+	return optarg;
+}
+
+// the input settings (-x, -r, -F) of every engine of the run: the plain one and both passes of -A
+static void apply_input(gpu_engine &e, const job_settings &in)
+{
+	e.set_wide(in.wide);
+	if (in.resampled())
+		e.set_rate(in.rate_p, in.rate_q);
+	e.set_format(in.fmt);
 }
 
 static bool parse_spec(const char *arg, spec &out)
@@ -152,12 +172,8 @@ static int replay_hex(int types, int dbg, const char *fn, const char *exec, bool
 {
 	pipe_sink *psink = (batched && exec) ? new pipe_sink(exec) : NULL;
 	batch_sink *sink = psink;
-	std::vector<decoder *> decs;
-	if (types & (1 << TFA_1)) decs.push_back(new sinked_decoder<tfa1_decoder>(TFA_1, &sink, 0));
-	if (types & (1 << TFA_2)) decs.push_back(new sinked_decoder<tfa2_decoder>(TFA_2, &sink, 0));
-	if (types & (1 << TFA_3)) decs.push_back(new sinked_decoder<tfa2_decoder>(TFA_3, &sink, 0));
-	if (types & (1 << TX22)) decs.push_back(new sinked_decoder<tfa2_decoder>(TX22, &sink, 0));
-	if (types & (1 << TFA_WHB)) decs.push_back(new sinked_decoder<whb_decoder>(TFA_WHB, &sink, 0));
+	std::vector<decoder *> decs = make_decoders(types, &sink, 0);
+	decs.erase(std::remove(decs.begin(), decs.end(), (decoder *)NULL), decs.end());  // (the slots of types not asked for)
 	FILE *fd = fopen(fn, "r");
 	if (!fd) {
 		perror("Can't open message file");
@@ -184,8 +200,8 @@ static int replay_hex(int types, int dbg, const char *fn, const char *exec, bool
 	return 0;
 }
 
-int main(int argc, char **argv)
-{
+// The command line, and main()'s steps over it in their order.  A step returns the exit code, or -1 to go on.
+struct cli {
 	int types = 0x07, thresh = 0, filter = 0, dbg = 0, blocks = 16;  // defaults of main.cpp:97-105 (0 = auto)
 	std::vector<int> devices;
 	std::vector<std::string> dumps;
@@ -193,7 +209,7 @@ int main(int argc, char **argv)
 	bool batched = false, bits = false, wide = false;
 	int mode = 0, slots = 0;
 	bool have_slots = false;
-	spec cur;  // the -p in force
+	spec cur;                     // the -p in force
 	std::vector<spec> dump_spec;  // per -L file
 	bool have_spec = false;
 	long freq = -1, center = 868250;  // -f (unset: the dumps' own frequency), -c: kHz
@@ -210,84 +226,126 @@ int main(int argc, char **argv)
 	// 1.536 MS/s, is derived from nothing but the burst lengths: an average much longer than any telegram (8 windows eat part of
 	// a burst and lose a telegram, 64 do not: DESIGN.md 6m); it has not been measured on real recordings.
 	long dc_windows = 0;
+	job_settings in;                  // the input: -x, -r as P / Q, -F; it answers what follows from them (job.h)
+	std::vector<long> scan_khz;       // -s, -A: the channels
+	std::vector<file_settings> per_file;
+
+	int parse(int argc, char **argv);
+	bool parse_auto(const char *arg);
+	bool parse_spectrum(const char *arg);
+	bool parse_format(const char *arg);
+	int check() const;
+	int reduce_rate();
+	int scan_channels();
+	int tune_files();
+	int find_channels();
+	int run();
+};
+
+static void usage()
+{
+	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
+			"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
+			"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
+			"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
+			"  -P bins[,G] power spectrum of one dump beside its decoding: bins = 64 .. 1024 (a power of two), G frames per record; a\n"
+			"              line per bin behind the telegrams (-D: per record too)\n"
+			"  -S prefix   record the IQ of every trigger window: <prefix>.idx (a line per run) and <prefix>.<file>.cs16 (384 kS/s int16 I, Q)\n"
+			"  -f kHz      receive frequency (default: the dumps' own, -c)\n"
+			"  -c kHz      frequency the dumps were recorded at (default 868250); -f within 767 kHz of it\n"
+			"  -x          the dumps are 15.36 MS/s u8 dumps (10x the rate); -f within 7679 kHz of -c, shifted ahead of the 10:1 stage\n"
+			"              (a file given to several -L is read once and shared by its streams; with -n it is read per -L, as before)\n"
+			"  -r Hz       sample rate of the dumps (default 1536000), e.g. 2048000 or 2400000: resampled on the GPU; -b is rounded up\n"
+			"              to a block count that holds a whole number of input samples; -f less than half the rate from -c (beyond\n"
+			"              767 kHz it is shifted ahead of the resampler); not with -x\n"
+			"  -F format   what the dumps hold: u8 (default), s8, s16 or f32 (cu8, cs8, cs16, cf32): little-endian interleaved I, Q without a\n"
+			"              header, at the rate of -r or at 1536000; a format other than u8 not with -x\n"
+			"  -z [n]      remove every dump's DC offset on the GPU, ahead of every tune: the mean over the last n windows of 512 input\n"
+			"              samples (default 2048, within 1 .. 4096) is subtracted from I and from Q (-D: a 'dc' line per submit); not with\n"
+			"              -x or -X; under -A the spectrum of pass 1 stays raw\n"
+			"  -n streams  at most this many streams per device: the -L files queue for them in order\n"
+			"  -p T=<hex>,t=<n>,W=<0|1>,f=<kHz>  -T / -t / -W / -f of the -L files that follow, up to the next -p (fields left out: the global ones)\n");
+}
+
+bool cli::parse_auto(const char *arg)
+{
+	have_auto = true;
+	long *field[3] = { &auto_ratio, &auto_rel, &auto_join };
+	const long lo[3] = { 2, 1, 0 }, hi[3] = { 4096, 4096, 100000 };
+	bool ok = true;
+	const char *a = arg;
+	for (int i = 0; a && ok; i++) {  // the fields between the commas, each a whole number in its range
+		const char *comma = strchr(a, ',');
+		const std::string f(a, comma ? (size_t)(comma - a) : strlen(a));
+		ok = i < 3 && parse_long(f.c_str(), lo[i], hi[i], *field[i]);
+		a = comma ? comma + 1 : NULL;
+	}
+	if (!ok)
+		fprintf(stderr, "tfrec_gpu: bad -A '%s': want [ratio[,rel[,join_kHz]]], ratio within 2 .. 4096, rel within 1 .. 4096, "
+				"join_kHz within 0 .. 100000\n", arg);
+	return ok;
+}
+
+bool cli::parse_spectrum(const char *arg)
+{
+	const char *comma = strchr(arg, ',');
+	long nb = 0, g = 0;
+	have_spec_p = parse_long(std::string(arg, comma ? (size_t)(comma - arg) : strlen(arg)).c_str(), 64, 1024, nb) && (nb & (nb - 1)) == 0 &&
+		      (!comma || parse_long(comma + 1, 1, 16384, g));
+	spec_bins = (int)nb;
+	spec_g = (int)g;
+	if (!have_spec_p)
+		fprintf(stderr, "tfrec_gpu: bad -P '%s': want <bins>[,<frames per record>], bins one of 64, 128, 256, 512, 1024, frames "
+				"per record within 1 .. 16384\n", arg);
+	return have_spec_p;
+}
+
+bool cli::parse_format(const char *arg)
+{
+	static const struct {
+		const char *name;
+		int fmt;
+	} names[] = { { "u8", TFREC_AMD_FMT_U8 }, { "cu8", TFREC_AMD_FMT_U8 }, { "s8", TFREC_AMD_FMT_S8 }, { "cs8", TFREC_AMD_FMT_S8 },
+		      { "s16", TFREC_AMD_FMT_S16 }, { "cs16", TFREC_AMD_FMT_S16 }, { "f32", TFREC_AMD_FMT_F32 }, { "cf32", TFREC_AMD_FMT_F32 } };
+	format = -1;
+	for (const auto &nm : names)
+		if (!strcmp(arg, nm.name))
+			format = nm.fmt;
+	if (format < 0)
+		fprintf(stderr, "tfrec_gpu: bad -F '%s': want u8, s8, s16 or f32 (cu8, cs8, cs16, cf32)\n", arg);
+	return format >= 0;
+}
+
+int cli::parse(int argc, char **argv)
+{
 	int c;
 	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:P:A::z::h")) != -1) {
 		switch (c) {
 		case 'z': {
-			// the argument is optional: attached (-z64), or the next word where that starts with a digit
-			const char *a = optarg;
-			if (!a && optind < argc && argv[optind][0] >= '0' && argv[optind][0] <= '9')
-				a = argv[optind++];
+			const char *a = optional_arg(argc, argv);
 			dc_windows = 2048;
-			if (a) {
-				char *end = NULL;
-				dc_windows = strtol(a, &end, 10);
-				if (end == a || *end || dc_windows < 1 || dc_windows > 4096) {
-					fprintf(stderr, "tfrec_gpu: bad -z '%s': want the windows (of 512 input samples) the DC estimate averages over, within "
-							"1 .. 4096\n", a);
-					return 1;
-				}
-			}
-			break;
-		}
-		case 'A': {
-			// the argument is optional: attached (-A32,16), or the next word where that starts with a digit
-			const char *a = optarg;
-			if (!a && optind < argc && argv[optind][0] >= '0' && argv[optind][0] <= '9')
-				a = argv[optind++];
-			have_auto = true;
-			long *field[3] = { &auto_ratio, &auto_rel, &auto_join };
-			const long lo[3] = { 2, 1, 0 }, hi[3] = { 4096, 4096, 100000 };
-			bool ok = true;
-			for (int i = 0; a && ok; i++) {
-				char *end = NULL;
-				const long v = strtol(a, &end, 10);
-				ok = i < 3 && end != a && (*end == ',' || !*end) && v >= lo[i] && v <= hi[i];
-				if (ok)
-					*field[i] = v;
-				a = ok && *end == ',' ? end + 1 : NULL;
-				if (ok && *end == ',' && !end[1])
-					ok = false;  // (a trailing comma)
-			}
-			if (!ok) {
-				fprintf(stderr, "tfrec_gpu: bad -A '%s': want [ratio[,rel[,join_kHz]]], ratio within 2 .. 4096, rel within 1 .. 4096, "
-						"join_kHz within 0 .. 100000\n", optarg ? optarg : argv[optind - 1]);
+			if (a && !parse_long(a, 1, 4096, dc_windows)) {
+				fprintf(stderr, "tfrec_gpu: bad -z '%s': want the windows (of 512 input samples) the DC estimate averages over, within "
+						"1 .. 4096\n", a);
 				return 1;
 			}
 			break;
 		}
-		case 'P': {
-			char *end = NULL;
-			const long nb = strtol(optarg, &end, 10);
-			long g = 0;
-			bool ok = end != optarg && (nb == 64 || nb == 128 || nb == 256 || nb == 512 || nb == 1024);
-			if (ok && *end == ',') {
-				const char *gs = end + 1;
-				g = strtol(gs, &end, 10);
-				ok = end != gs && !*end && g >= 1 && g <= 16384;
-			} else if (ok && *end) {
-				ok = false;
-			}
-			if (!ok) {
-				fprintf(stderr, "tfrec_gpu: bad -P '%s': want <bins>[,<frames per record>], bins one of 64, 128, 256, 512, 1024, frames "
-						"per record within 1 .. 16384\n", optarg);
+		case 'A':
+			if (!parse_auto(optional_arg(argc, argv)))
 				return 1;
-			}
-			have_spec_p = true;
-			spec_bins = (int)nb;
-			spec_g = (int)g;
 			break;
-		}
-		case 's': {
-			char *end = NULL;
-			scan_step = strtol(optarg, &end, 10);
+		case 'P':
+			if (!parse_spectrum(optarg))
+				return 1;
+			break;
+		case 's':
 			have_scan = true;
-			if (end == optarg || *end || scan_step < 1 || scan_step > 100000000L) {
+			if (!parse_long(optarg, 1, 100000000L, scan_step)) {
 				fprintf(stderr, "tfrec_gpu: bad -s '%s': want the channel step in kHz, >= 1\n", optarg);
 				return 1;
 			}
 			break;
-		}
 		case 'S':
 			cap_prefix = optarg;
 			if (!*cap_prefix) {
@@ -306,31 +364,16 @@ int main(int argc, char **argv)
 			}
 			break;
 		case 'x': wide = true; break;
-		case 'r': {
-			char *end = NULL;
-			rate = strtol(optarg, &end, 10);
-			if (end == optarg || *end || rate <= 0 || rate > 100000000L) {
+		case 'r':
+			if (!parse_long(optarg, 1, 100000000L, rate)) {
 				fprintf(stderr, "tfrec_gpu: bad -r '%s': want the dumps' sample rate in Hz\n", optarg);
 				return 1;
 			}
 			break;
-		}
-		case 'F': {
-			static const struct {
-				const char *name;
-				int fmt;
-			} names[] = { { "u8", TFREC_AMD_FMT_U8 }, { "cu8", TFREC_AMD_FMT_U8 }, { "s8", TFREC_AMD_FMT_S8 }, { "cs8", TFREC_AMD_FMT_S8 },
-				      { "s16", TFREC_AMD_FMT_S16 }, { "cs16", TFREC_AMD_FMT_S16 }, { "f32", TFREC_AMD_FMT_F32 }, { "cf32", TFREC_AMD_FMT_F32 } };
-			format = -1;
-			for (const auto &nm : names)
-				if (!strcmp(optarg, nm.name))
-					format = nm.fmt;
-			if (format < 0) {
-				fprintf(stderr, "tfrec_gpu: bad -F '%s': want u8, s8, s16 or f32 (cu8, cs8, cs16, cf32)\n", optarg);
+		case 'F':
+			if (!parse_format(optarg))
 				return 1;
-			}
 			break;
-		}
 		case 'q': dbg = -1; break;
 		case 'D': dbg++; break;
 		case 'B': bits = true; break;
@@ -357,30 +400,16 @@ int main(int argc, char **argv)
 		case 'E': exec = optarg; batched = true; break;
 		case 'm': mode = atoi(optarg); break;
 		default:
-			fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
-					"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
-					"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
-					"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
-					"  -P bins[,G] power spectrum of one dump beside its decoding: bins = 64 .. 1024 (a power of two), G frames per record; a\n"
-					"              line per bin behind the telegrams (-D: per record too)\n"
-					"  -S prefix   record the IQ of every trigger window: <prefix>.idx (a line per run) and <prefix>.<file>.cs16 (384 kS/s int16 I, Q)\n"
-					"  -f kHz      receive frequency (default: the dumps' own, -c)\n"
-					"  -c kHz      frequency the dumps were recorded at (default 868250); -f within 767 kHz of it\n"
-					"  -x          the dumps are 15.36 MS/s u8 dumps (10x the rate); -f within 7679 kHz of -c, shifted ahead of the 10:1 stage\n"
-					"              (a file given to several -L is read once and shared by its streams; with -n it is read per -L, as before)\n"
-					"  -r Hz       sample rate of the dumps (default 1536000), e.g. 2048000 or 2400000: resampled on the GPU; -b is rounded up\n"
-					"              to a block count that holds a whole number of input samples; -f less than half the rate from -c (beyond\n"
-					"              767 kHz it is shifted ahead of the resampler); not with -x\n"
-					"  -F format   what the dumps hold: u8 (default), s8, s16 or f32 (cu8, cs8, cs16, cf32): little-endian interleaved I, Q without a\n"
-					"              header, at the rate of -r or at 1536000; a format other than u8 not with -x\n"
-					"  -z [n]      remove every dump's DC offset on the GPU, ahead of every tune: the mean over the last n windows of 512 input\n"
-					"              samples (default 2048, within 1 .. 4096) is subtracted from I and from Q (-D: a 'dc' line per submit); not with\n"
-					"              -x or -X; under -A the spectrum of pass 1 stays raw\n"
-					"  -n streams  at most this many streams per device: the -L files queue for them in order\n"
-					"  -p T=<hex>,t=<n>,W=<0|1>,f=<kHz>  -T / -t / -W / -f of the -L files that follow, up to the next -p (fields left out: the global ones)\n");
+			usage();
 			return c == 'h' ? 0 : 1;
 		}
 	}
+	return -1;
+}
+
+// what excludes what, before any file is looked at
+int cli::check() const
+{
 	if (have_slots && slots < 1) {
 		fprintf(stderr, "tfrec_gpu: -n must be >= 1\n");
 		return 1;
@@ -410,19 +439,14 @@ int main(int argc, char **argv)
 		fprintf(stderr, "tfrec_gpu: -p applies to -L files, not to -X\n");
 		return 1;
 	}
-	setvbuf(stdout, NULL, _IOFBF, 1 << 16);
-	if (hexfile)
-		return replay_hex(types, dbg, hexfile, exec, batched);
-	if (dumps.empty()) {
-		fprintf(stderr, "tfrec_gpu: need -L <dumpfile> or -X <hexfile>\n");
-		return 1;
-	}
-	if (thresh < 0) {
-		fprintf(stderr, "tfrec_gpu: -t must be >= 0 (0 = auto)\n");
-		return 1;
-	}
-	// -r: the rate as P / Q of 1536000, checked by the library's own rules (no device needed); -b up to a permitted block count
-	int rate_p = 1, rate_q = 1;
+	return -1;
+}
+
+// -r: the rate as P / Q of 1536000, checked by the library's own rules (no device needed); -b up to a permitted block count
+int cli::reduce_rate()
+{
+	in.wide = wide;
+	in.fmt = format;
 	if (rate && wide) {
 		fprintf(stderr, "tfrec_gpu: -r and -x exclude each other (-x is the fixed rate 15360000)\n");
 		return 1;
@@ -445,11 +469,9 @@ int main(int argc, char **argv)
 					"be ambiguous or could overflow)\n", rate, p, q);
 			return 1;
 		}
-		rate_p = (int)p;
-		rate_q = (int)q;
-		int unit = rate_q;
-		while (unit % 2 == 0)
-			unit /= 2;
+		in.rate_p = (int)p;
+		in.rate_q = (int)q;
+		const int unit = in.unit();
 		if (blocks >= 1 && blocks % unit) {
 			const int up = (blocks + unit - 1) / unit * unit;
 			fprintf(stderr, "tfrec_gpu: -b %d rounded up to %d: at %ld S/s a submit holds a multiple of %d blocks\n", blocks, up,
@@ -457,39 +479,46 @@ int main(int argc, char **argv)
 			blocks = up;
 		}
 	}
-	// -s: the file once per channel c + k * step, |k * step * 1000| <= fs_in / 2 - 192000 (in integers: 2000 |k| step <= fs_in - 384000)
-	std::vector<long> scan_khz;
-	if (have_scan) {
-		const long fs_in = wide ? 15360000L : (rate ? rate : 1536000L);
-		const long kmax = (fs_in - 384000) / (2000 * scan_step);
-		if (2 * kmax + 1 > 4096) {
-			fprintf(stderr, "tfrec_gpu: -s %ld: %ld channels across the %ld S/s recording, at most 4096 are scanned at once\n", scan_step,
-				2 * kmax + 1, fs_in);
+	return -1;
+}
+
+// -s: the file once per channel c + k * step, |k * step * 1000| <= fs_in / 2 - 192000 (in integers: 2000 |k| step <= fs_in - 384000)
+int cli::scan_channels()
+{
+	const long fs_in = in.fs_in();
+	const long kmax = (fs_in - 384000) / (2000 * scan_step);
+	if (2 * kmax + 1 > 4096) {
+		fprintf(stderr, "tfrec_gpu: -s %ld: %ld channels across the %ld S/s recording, at most 4096 are scanned at once\n", scan_step,
+			2 * kmax + 1, fs_in);
+		return 1;
+	}
+	const std::string path = dumps[0];
+	dumps.clear();
+	dump_spec.clear();
+	for (long k = -kmax; k <= kmax; k++) {
+		spec p;
+		p.freq = center + k * scan_step;
+		if (p.freq <= 0) {
+			fprintf(stderr, "tfrec_gpu: -s: channel %ld kHz below zero: -c %ld is not the recording's frequency\n", p.freq, center);
 			return 1;
 		}
-		const std::string path = dumps[0];
-		dumps.clear();
-		dump_spec.clear();
-		for (long k = -kmax; k <= kmax; k++) {
-			spec p;
-			p.freq = center + k * scan_step;
-			if (p.freq <= 0) {
-				fprintf(stderr, "tfrec_gpu: -s: channel %ld kHz below zero: -c %ld is not the recording's frequency\n", p.freq, center);
-				return 1;
-			}
-			dumps.push_back(path);
-			dump_spec.push_back(p);
-			scan_khz.push_back(p.freq);
-		}
+		dumps.push_back(path);
+		dump_spec.push_back(p);
+		scan_khz.push_back(p.freq);
 	}
-	// every file's tune, checked before any device is opened
+	return -1;
+}
+
+// every file's tune, checked before any device is opened, and the per-file settings the engine gets
+int cli::tune_files()
+{
 	std::vector<int> tunes;
 	bool tuned = false;
 	for (const spec &p : dump_spec) {
 		const long f = p.freq >= 0 ? p.freq : (freq >= 0 ? freq : center);
 		const long lim = wide ? 7680 : 768;
-		if (rate_p != 1 || rate_q != 1) {  // -r: |f - c| < fs_in / 2, that is 2 |f - c| Q < 1536 P in kHz
-			if (2 * labs(f - center) * rate_q >= 1536L * rate_p) {
+		if (in.resampled()) {  // -r: |f - c| < fs_in / 2, that is 2 |f - c| Q < 1536 P in kHz
+			if (2 * labs(f - center) * in.rate_q >= 1536L * in.rate_p) {
 				fprintf(stderr, "tfrec_gpu: receive frequency %ld kHz (-f / -p f=) is %ld kHz from the dumps' %ld kHz (-c): less than "
 						"%.1f kHz, half the %ld S/s band (-r), can be tuned\n", f, f - center, center, rate / 2000.0, rate);
 				return 1;
@@ -503,67 +532,91 @@ int main(int argc, char **argv)
 		tunes.push_back((int)((f - center) * 1000));
 		tuned = tuned || tunes.back() != 0;
 	}
-	std::vector<file_settings> per_file;
 	if (have_spec || tuned || have_scan)
 		for (size_t i = 0; i < dump_spec.size(); i++) {
 			const spec &p = dump_spec[i];
 			per_file.push_back(file_settings{ p.types >= 0 ? p.types : types, p.thresh >= 0 ? p.thresh : thresh,
 							  p.filter >= 0 ? p.filter : filter, tunes[i] });
 		}
-	const long per_block = wide ? 327680L : 32768L * rate_p / rate_q;  // a block's input samples: the default record of -P and -A
-	if (have_auto) {
-		// pass 1: the file as one stream with the spectrum and the detector
-		const int n_bins = have_spec_p ? spec_bins : 256;
-		{
-			gpu_engine e1(dumps, types, thresh, filter, dbg, devices, blocks);
-			e1.set_wide(wide);
-			if (rate_p != 1 || rate_q != 1)
-				e1.set_rate(rate_p, rate_q);
-			e1.set_format(format);
-			e1.set_spectrum(n_bins, spec_g ? spec_g : (int)std::max(1L, per_block / n_bins), center);
-			e1.set_occupancy((int)auto_ratio, (int)auto_rel, auto_join * 1000);
-			const int rc1 = e1.run();
-			fflush(stdout);
-			if (rc1)
-				return 2;
-			scan_khz = e1.found_khz();
-		}
-		if (scan_khz.empty())
-			return 0;
-		// pass 2: the scan, on exactly those (each within the scan's own range, so within what can be tuned)
-		const std::string path = dumps[0];
-		dumps.clear();
-		per_file.clear();
-		for (long khz : scan_khz) {
-			if (khz <= 0) {
-				fprintf(stderr, "tfrec_gpu: -A: channel %ld kHz below zero: -c %ld is not the recording's frequency\n", khz, center);
-				return 1;
-			}
-			dumps.push_back(path);
-			per_file.push_back(file_settings{ types, thresh, filter, (int)((khz - center) * 1000) });
-		}
-		have_scan = true;
-		have_spec_p = false;
+	return -1;
+}
+
+// -A: pass 1, the file as one stream with the spectrum and the detector; then the channels it found become the files of a scan
+int cli::find_channels()
+{
+	const int n_bins = have_spec_p ? spec_bins : 256;
+	{
+		gpu_engine e1(dumps, types, thresh, filter, dbg, devices, blocks);
+		apply_input(e1, in);
+		e1.set_spectrum(n_bins, spec_g ? spec_g : (int)std::max(1L, (long)in.input_samples(1) / n_bins), center);
+		e1.set_occupancy((int)auto_ratio, (int)auto_rel, auto_join * 1000);
+		const int rc1 = e1.run();
+		fflush(stdout);
+		if (rc1)
+			return 2;
+		scan_khz = e1.found_khz();
 	}
+	if (scan_khz.empty())
+		return 0;
+	// pass 2: the scan, on exactly those (each within the scan's own range, so within what can be tuned)
+	const std::string path = dumps[0];
+	dumps.clear();
+	per_file.clear();
+	for (long khz : scan_khz) {
+		if (khz <= 0) {
+			fprintf(stderr, "tfrec_gpu: -A: channel %ld kHz below zero: -c %ld is not the recording's frequency\n", khz, center);
+			return 1;
+		}
+		dumps.push_back(path);
+		per_file.push_back(file_settings{ types, thresh, filter, (int)((khz - center) * 1000) });
+	}
+	have_scan = true;
+	have_spec_p = false;
+	return -1;
+}
+
+int cli::run()
+{
 	gpu_engine e(dumps, types, thresh, filter, dbg, devices, blocks, per_file);
 	if (exec || mode)
 		e.set_handler(exec, batched, mode);
 	e.set_bits_replay(bits);
 	e.set_slots(slots);
-	e.set_wide(wide);
-	if (rate_p != 1 || rate_q != 1)
-		e.set_rate(rate_p, rate_q);
-	e.set_format(format);
+	apply_input(e, in);
 	if (dc_windows)
 		e.set_dc((int)dc_windows);
 	if (have_scan)
 		e.set_scan(scan_khz);
 	if (cap_prefix)
 		e.set_capture(cap_prefix);
-	if (have_spec_p) {  // the default record: the frames one block's input holds
-		e.set_spectrum(spec_bins, spec_g ? spec_g : (int)std::max(1L, per_block / spec_bins), center);
-	}
+	if (have_spec_p)  // the default record: the frames one block's input holds
+		e.set_spectrum(spec_bins, spec_g ? spec_g : (int)std::max(1L, (long)in.input_samples(1) / spec_bins), center);
 	int rc = e.run();
 	fflush(stdout);
 	return rc ? 2 : 0;
+}
+
+int main(int argc, char **argv)
+{
+	cli c;
+	int r = c.parse(argc, argv);
+	if (r < 0)
+		r = c.check();
+	if (r >= 0)
+		return r;
+	setvbuf(stdout, NULL, _IOFBF, 1 << 16);
+	if (c.hexfile)
+		return replay_hex(c.types, c.dbg, c.hexfile, c.exec, c.batched);
+	if (c.dumps.empty()) {
+		fprintf(stderr, "tfrec_gpu: need -L <dumpfile> or -X <hexfile>\n");
+		return 1;
+	}
+	if (c.thresh < 0) {
+		fprintf(stderr, "tfrec_gpu: -t must be >= 0 (0 = auto)\n");
+		return 1;
+	}
+	if ((r = c.reduce_rate()) >= 0 || (c.have_scan && (r = c.scan_channels()) >= 0) || (r = c.tune_files()) >= 0 ||
+	    (c.have_auto && (r = c.find_channels()) >= 0))
+		return r;
+	return c.run();
 }
