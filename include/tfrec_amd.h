@@ -523,6 +523,57 @@ int tfrec_amd_enable_capture(tfrec_amd_ctx *ctx, uint32_t max_runs, uint64_t max
 int tfrec_amd_read_captures(tfrec_amd_ctx *ctx, tfrec_amd_run *runs, size_t cap_runs, uint32_t *n_runs, int16_t *samples,
 			    size_t cap_pairs, uint64_t *n_pairs);
 
+/* Channel-rate input: a context whose input rows already hold what process_iq produces -- little-endian int16 (I, Q)
+ * pairs at 384 kS/s, from tfrec_amd_read_captures, tfrec_gpu -S or an upstream channeliser.  A block is 8192 pairs = 32768 bytes:
+ * tfrec_amd_input_bytes returns n_blocks * 32768, tfrec_amd_get_input_rate 1/4, tfrec_amd_get_input_format TFREC_AMD_FMT_DEC16
+ * (which tfrec_amd_create_format keeps refusing).  The stride and alignment rules of the submits are unchanged.
+ *   Definition.  Per component v' = max(v, -32767), so that I*I + Q*Q and every product downstream stays inside int32; dec[n] =
+ *     (I', Q') is what tfrec_amd_read_decimated returns and what enters fsk_demod::process; mask bit n = |I'| + |Q'| > thresh of the
+ *     stream (the context's or its tfrec_amd_stream_config's; an auto stream's mask is rewritten block by block as on every
+ *     context).  The sample ahead of a submit's first one is the stream's last pair of the submit before, (0, 0) at the start and
+ *     after any restart: 4 bytes of carried state per stream.
+ *   No filter stage: no FIR, no history, no pre-stage.  filter_type is accepted, in the config and per stream, and has no effect.
+ *   Parity is pinned for inputs the decimator can produce (what tfrec_amd_read_decimated returns of any other context: fed back,
+ *     they give that context's events bit for bit).  For other int16 input the definition is the reference's arithmetic on those
+ *     values.
+ *   Works: reset, configure, tfrec_amd_map_streams (the kernel looks the row up), levels, the recorder, both layouts,
+ *     _SERIAL_CHAINS, _BITS, _ALL_FLUSHES, _TIMING.  Refused with TFREC_AMD_E_INVAL: TFREC_AMD_F_INPUT_10X; the three tunes (they are
+ *     defined ahead of process_iq); tfrec_amd_enable_spectrum (its bounds assume |x| <= 8192); tfrec_amd_read_stage0.
+ * Contexts of the older constructors launch what they launched before, with the arguments they had. */
+#define TFREC_AMD_FMT_DEC16 16
+int tfrec_amd_create_decimated(const tfrec_amd_config *cfg, tfrec_amd_ctx **out);
+/* The recorder's missing sample: with it a capture holds everything its stream's flush events depend on.  Call after
+ * tfrec_amd_enable_capture and before the first submit; max_runs * 4 bytes of device memory per FIFO set, counted in
+ * tfrec_amd_get_memory.  Errors: no recorder or a second call: TFREC_AMD_E_INVAL; after the first submit or a poisoned context:
+ * TFREC_AMD_E_STATE; TFREC_AMD_E_NOMEM as elsewhere; a call that fails leaves the context exactly as it was.  A recorder on which
+ * it was never called holds and launches what it did. */
+int tfrec_amd_enable_capture_pre(tfrec_amd_ctx *ctx);
+/* pre[2 i], pre[2 i + 1] = the decimated (I, Q) just ahead of runs[i].start_sample of the table tfrec_amd_read_captures returns for
+ * the same submit: the sample before it inside the submit, for a run at the submit's first sample the stream's last sample of the
+ * submit before, and (0, 0) where nothing precedes -- a stream's start or restart.  Conventions of tfrec_amd_read_captures: the
+ * OLDEST undrained submit, read BEFORE the drain that pops it; cap_runs is the room in pairs; *n_runs the submit's true run count; on
+ * a device-side overflow TFREC_AMD_E_OVERFLOW and the same delivered prefix.  Errors: not enabled, NULL ctx / n_runs / pre (with
+ * cap_runs > 0), room too small (nothing written, *n_runs set): TFREC_AMD_E_INVAL; nothing undrained or poisoned: TFREC_AMD_E_STATE. */
+int tfrec_amd_read_capture_pre(tfrec_amd_ctx *ctx, int16_t *pre, size_t cap_runs, uint32_t *n_runs);
+/* Sparse submits on a channel-rate context: allowed only before the first submit.  Per FIFO set, on the device and page-locked on
+ * the host alike: max_runs * 20 bytes (table and pre), max_samples * 4 bytes (pool), (n_streams + 1) * 4 and n_streams * 8 bytes;
+ * tfrec_amd_get_memory counts all of it.  Errors: not a tfrec_amd_create_decimated context, a zero argument, max_runs >= 2^31 or a
+ * second call: TFREC_AMD_E_INVAL; after the first submit: TFREC_AMD_E_STATE; TFREC_AMD_E_NOMEM as elsewhere; a failed call leaves
+ * the context as it was. */
+int tfrec_amd_enable_runs_input(tfrec_amd_ctx *ctx, uint32_t max_runs, uint64_t max_samples);
+/* Exactly tfrec_amd_submit_host of the expanded rows, with M = n_blocks * 8192: every sample (0, 0); run i's pairs
+ * (samples[2 * pool_offset ..]) at [start_sample, start_sample + n_samples) of row runs[i].stream; pre[2 i], pre[2 i + 1] at
+ * start_sample - 1 when start_sample > 0; when start_sample == 0, pre[i] is that stream's "sample ahead of the submit" for this
+ * submit instead of the carried pair (a stream that restarts at this submit still gets (0, 0)).  Only the table, the pool and pre
+ * cross to the device (host memory, copied before the call returns).  FIFO, poisoning and the n_blocks rules are those of the other
+ * submits.  Rules, checked before anything is queued (a violation: TFREC_AMD_E_INVAL, nothing queued, no state changed):
+ * start_sample is submit-relative, within [0, M); n_samples >= 1 and start_sample + n_samples <= M; stream < n_streams; the table is
+ * ordered by (stream, start_sample); at least one sample lies between two runs of a row; pool_offset is the exclusive prefix sum of
+ * n_samples and n_pairs their total; n_runs <= max_runs and n_pairs <= max_samples; a mapped context is refused (the dense submit
+ * serves those).  flags and thresh of the entries are ignored.  tfrec_amd/decin.py (expand, check, rebase) restates all of it. */
+int tfrec_amd_submit_runs(tfrec_amd_ctx *ctx, const tfrec_amd_run *runs, uint32_t n_runs, const int16_t *samples, uint64_t n_pairs,
+			  const int16_t *pre, int n_blocks);
+
 /* Power spectrum of the input rows (tfrec_amd_enable_spectrum): where in a recording there is energy, and where the
  * short bursts are that an average hides -- before a receiver is placed.  It belongs to an input ROW of a submit, not to a stream: it
  * is taken on x, the int16 value every format maps a stored component to (tfrec_amd_create_format; -8192 <= x <= 8191), at the

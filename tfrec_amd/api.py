@@ -107,7 +107,8 @@ EXPORTS = (
     "tfrec_amd_tune_streams_input", "tfrec_amd_get_stream_tune_input", "tfrec_amd_create_format", "tfrec_amd_get_input_format",
     "tfrec_amd_read_levels", "tfrec_amd_enable_capture", "tfrec_amd_read_captures", "tfrec_amd_enable_spectrum",
     "tfrec_amd_read_spectrum", "tfrec_amd_enable_occupancy", "tfrec_amd_read_occupancy", "tfrec_amd_create_dc", "tfrec_amd_get_dc",
-    "tfrec_amd_read_dc", "tfrec_amd_reset_dc_rows",
+    "tfrec_amd_read_dc", "tfrec_amd_reset_dc_rows", "tfrec_amd_create_decimated", "tfrec_amd_enable_capture_pre",
+    "tfrec_amd_read_capture_pre", "tfrec_amd_enable_runs_input", "tfrec_amd_submit_runs",
 )
 
 _libs = {}
@@ -194,6 +195,11 @@ def load_library(build: bool = True, experiments: bool = False):
     L.tfrec_amd_get_dc.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.tfrec_amd_read_dc.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
     L.tfrec_amd_reset_dc_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.tfrec_amd_create_decimated.argtypes = [C.POINTER(Config), C.POINTER(C.c_void_p)]
+    L.tfrec_amd_enable_capture_pre.argtypes = [C.c_void_p]
+    L.tfrec_amd_read_capture_pre.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+    L.tfrec_amd_enable_runs_input.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
+    L.tfrec_amd_submit_runs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
     L.tfrec_amd_fifo_depth.restype = C.c_int
     if L.tfrec_amd_fifo_depth() != FIFO_DEPTH:
         raise RuntimeError("libtfrec_amd.so was built with FIFO depth %d, this binding expects %d" % (
@@ -237,7 +243,7 @@ class Receiver:
                  device: int = 0, max_blocks: int = 48, max_events: int | None = None, all_flushes: bool = False,
                  timing: bool = False, serial_chains: bool = False, input_10x: bool = False, bits: bool = False,
                  experiments: bool = False, input_rate=None, input_format=None, levels: bool = False, dc_windows=None,
-                 dc_rows=None):
+                 dc_rows=None, decimated: bool = False):
         # experiments=True: the build that reads the TFREC_AMD_* knobs / test hooks from the environment (csrc/knobs.h);
         # the default is the product library, which has none
         self.L = load_library(experiments=experiments)
@@ -259,7 +265,16 @@ class Receiver:
         # dc_windows=K (1 .. 4096): the DC blocker ahead of everything, averaging over K windows of 512 input samples, for at most
         # dc_rows input rows (default: n_streams) -- with any input_format ("u8" included) and input_rate (tfrec_amd_create_dc,
         # dcblock.py)
-        if dc_windows is not None:
+        # decimated=True: the rows hold int16 (I, Q) pairs at 384 kS/s, the decimated samples themselves (tfrec_amd_create_decimated,
+        # decin.py): 32768 bytes per block.  submit() takes them as uint8 rows like every input, or as int16 arrays.
+        self.is_decimated = bool(decimated)
+        if decimated:
+            if dc_windows is not None or input_format is not None or input_rate is not None:
+                raise TfrecAmdError(E_INVAL, "decimated input has no other format, rate or DC blocker")
+            _check(self.L, self.L.tfrec_amd_create_decimated(C.byref(self.cfg), C.byref(self.h)))
+            self.input_rate = (1, 4)
+            self.input_format = "dec16"
+        elif dc_windows is not None:
             from . import formats
 
             p, q = (int(v) for v in (input_rate if input_rate is not None else (1, 1)))
@@ -292,7 +307,7 @@ class Receiver:
                 raise TfrecAmdError(E_INVAL, "input_rate outside int32")
             _check(self.L, self.L.tfrec_amd_create_rate(C.byref(self.cfg), p, q, C.byref(self.h)))
             self.input_rate = (p, q)
-        bb = Fraction(BLOCK_BYTES * self.input_rate[0] * {"s16": 2, "f32": 4}.get(self.input_format, 1), self.input_rate[1])
+        bb = Fraction(BLOCK_BYTES * self.input_rate[0] * {"s16": 2, "f32": 4, "dec16": 2}.get(self.input_format, 1), self.input_rate[1])
         self.block_bytes = int(bb) if bb.denominator == 1 else bb
         self.n_streams = n_streams
         self.max_events = max_events
@@ -319,6 +334,8 @@ class Receiver:
     def submit(self, iq, n_blocks: int | None = None, stream=None):
         """iq: torch uint8 CUDA tensor [n_streams, n_bytes] (resident in HBM) or a numpy/host array."""
         if isinstance(iq, np.ndarray):
+            if self.is_decimated and iq.dtype == np.int16:  # [rows, M, 2] or [rows, 2 M] pairs: their bytes
+                iq = np.ascontiguousarray(iq).reshape(iq.shape[0], -1).astype("<i2", copy=False).view(np.uint8)
             a = np.ascontiguousarray(iq, dtype=np.uint8)
             a = a.reshape(a.shape[0] if a.ndim == 2 and self.rows_in_use <= a.shape[0] <= self.n_streams else self.n_streams, -1)
             nb = a.shape[1] // self.block_bytes if n_blocks is None else n_blocks
@@ -495,13 +512,17 @@ class Receiver:
         _check(self.L, self.L.tfrec_amd_enable_capture(self.h, int(max_runs), int(max_samples)))
         self._capture = (int(max_runs), int(max_samples))
 
-    def read_captures(self, allow_overflow: bool = False):
+    def read_captures(self, allow_overflow: bool = False, pre: bool = False):
         """The captures of the OLDEST undrained submit (tfrec_amd_read_captures; call it before the drain that pops that submit)
         -> (runs, samples): a RUN_DTYPE array ordered by (stream, start_sample) and the pool, int16 [n_pairs, 2]; run r's pairs are
         samples[r.pool_offset : r.pool_offset + r.n_samples].  A device-side overflow (E_OVERFLOW) raises unless allow_overflow,
         as for drain(); then the longest prefix of whole runs that fitted is returned.  capture_totals holds the submit's true
         (n_runs, n_pairs) and capture_overflow whether it overflowed.  TfrecAmdError(E_INVAL) on a context without enable_capture,
-        (E_STATE) when nothing is waiting to be drained."""
+        (E_STATE) when nothing is waiting to be drained.  pre=True (after enable_capture_pre): -> (runs, samples, pre), pre as
+        read_capture_pre returns it."""
+        if pre:
+            runs, samples = self.read_captures(allow_overflow)
+            return runs, samples, self.read_capture_pre(allow_overflow)[:len(runs)]
         ok = (E_OK, E_OVERFLOW) if allow_overflow else (E_OK,)
         nr, npairs = C.c_uint32(0), C.c_uint64(0)
         max_runs, max_samples = getattr(self, "_capture", (0, 0))
@@ -521,6 +542,49 @@ class Receiver:
         runs = runs[:k].copy()
         n = int(runs["pool_offset"][-1] + runs["n_samples"][-1]) if k else 0
         return runs, samples[:n].copy()
+
+    def enable_capture_pre(self):
+        """Let the recorder also keep the sample ahead of every run (tfrec_amd_enable_capture_pre; after enable_capture, before the
+        first submit).  read_capture_pre, or read_captures(pre=True), returns them."""
+        _check(self.L, self.L.tfrec_amd_enable_capture_pre(self.h))
+
+    def read_capture_pre(self, allow_overflow: bool = False) -> np.ndarray:
+        """The pair ahead of every run of the table read_captures returns for the same -- the OLDEST undrained -- submit
+        (tfrec_amd_read_capture_pre; decin.pre_samples) -> int16 [n_runs, 2].  Overflow as for read_captures."""
+        ok = (E_OK, E_OVERFLOW) if allow_overflow else (E_OK,)
+        nr = C.c_uint32(0)
+        rc = self.L.tfrec_amd_read_capture_pre(self.h, None, 0, C.byref(nr))  # the count (no room: E_INVAL)
+        if rc != E_INVAL or nr.value == 0:
+            _check(self.L, rc, ok=ok)
+            return np.zeros((0, 2), dtype=np.int16)
+        max_runs = getattr(self, "_capture", (0, 0))[0]
+        pre = np.zeros((min(nr.value, max_runs), 2), dtype=np.int16)
+        rc = self.L.tfrec_amd_read_capture_pre(self.h, pre.ctypes.data, len(pre), C.byref(nr))
+        _check(self.L, rc, ok=ok)
+        if rc == E_OVERFLOW:  # the delivered prefix is the table's
+            pre = pre[:len(self.read_captures(allow_overflow=True)[0])]
+        return pre
+
+    def enable_runs_input(self, max_runs: int, max_samples: int):
+        """Turn sparse submits on (tfrec_amd_enable_runs_input; decimated receivers, before the first submit): a submit_runs may
+        carry at most max_runs runs and max_samples pairs."""
+        if not (0 <= int(max_runs) < 2 ** 32 and 0 <= int(max_samples) < 2 ** 64):  # (refused before ctypes could wrap a value)
+            raise TfrecAmdError(E_INVAL, "max_runs or max_samples outside their types")
+        _check(self.L, self.L.tfrec_amd_enable_runs_input(self.h, int(max_runs), int(max_samples)))
+
+    def submit_runs(self, runs, samples, pre, n_blocks: int):
+        """One submit of n_blocks blocks given as a run table (RUN_DTYPE, start_sample relative to the submit), its pool and the
+        pair ahead of every run (tfrec_amd_submit_runs): exactly submit() of decin.expand(runs, samples, pre, ...)."""
+        t = np.ascontiguousarray(runs, dtype=RUN_DTYPE)
+        p = np.ascontiguousarray(samples, dtype="<i2").reshape(-1, 2)
+        q = np.ascontiguousarray(pre, dtype="<i2").reshape(-1, 2)
+        if len(q) != len(t):
+            raise ValueError("%d pre samples for %d runs" % (len(q), len(t)))
+        if not -2 ** 31 <= int(n_blocks) < 2 ** 31:
+            raise TfrecAmdError(E_INVAL, "n_blocks outside int32")
+        _check(self.L, self.L.tfrec_amd_submit_runs(self.h, t.ctypes.data if len(t) else None, len(t), p.ctypes.data if len(p) else None,
+                                                    len(p), q.ctypes.data if len(q) else None, int(n_blocks)))
+        return int(n_blocks)
 
     def enable_spectrum(self, n_bins: int, frames_per_record: int, max_rows: int | None = None):
         """Turn the per-input power spectrum on (tfrec_amd_enable_spectrum; before the first submit): an exact integer DFT of

@@ -56,6 +56,14 @@ hipError_t launch_occupancy(hipStream_t st, int n_rows, long n_in, int n_bins, i
 			    uint32_t *bits);
 hipError_t launch_dc(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_rows, long n_in, int k, int2 *sums, int win_stride,
 		     int2 *ring, int2 *state, uint32_t *d, uint8_t *out, size_t out_stride);
+hipError_t launch_decin(hipStream_t st, const uint8_t *in, size_t stride, int n_streams, int n_blocks, const uint4 *chan, uint32_t *dec,
+			size_t dec_stride, unsigned long long *mask, size_t mask_stride, uint32_t *prevdec, uint32_t *last, int thresh,
+			const StreamCfg *scfg);
+hipError_t launch_decin_runs(hipStream_t st, int n_streams, int n_blocks, const uint4 *tab, const uint32_t *pool, const uint32_t *pre,
+			     const int32_t *first, const uint2 *ov, uint32_t *dec, size_t dec_stride, unsigned long long *mask,
+			     size_t mask_stride, uint32_t *prevdec, uint32_t *last, int thresh, const StreamCfg *scfg);
+hipError_t launch_capture_pre(hipStream_t st, const tfrec_amd_run *runs, const CaptureHeader *hdr, uint32_t max_runs, long long sample_base,
+			      const uint32_t *dec, size_t dec_stride, const uint32_t *prevdec, uint32_t *pre);
 }  // namespace tfrec
 
 using namespace tfrec;
@@ -67,6 +75,7 @@ using namespace tfrec;
 #include "capi_outputs.h"  // the level meter's, the recorder's, the spectrum's and the occupancy detector's entry points
 #include "capi_dc.h"       // the DC blocker's constructor, getter, read and reset
 #include "capi_streams.h"  // reset, configure, the three tunes, map, and their getters
+#include "capi_decin.h"    // the channel-rate constructor, the recorder's pre samples, sparse submits
 
 extern "C" {
 

@@ -251,6 +251,10 @@ static int make_front_buffers(tfrec_amd_ctx *c)
 		TRY(own_device(c, c->d_prevdec[k], n * sizeof(uint32_t)));
 	}
 	c->in16 = c->in10x || c->resamp || c->ingest;
+	if (c->decin.on) {  // channel-rate input: no FIR, the carried state is every stream's last pair ((0, 0) at the start)
+		TRY(own_device(c, c->decin.d_last, n * sizeof(uint32_t)));
+		HIPCHK(hipMemset(c->decin.d_last, 0, n * sizeof(uint32_t)));
+	}
 	const size_t tail_bytes = c->in16 ? 2 * (size_t)kTailBytes : (size_t)kTailBytes;  // int16 history is twice as wide
 	// zero FIR history == u8 value 128 (decimate::decimate zeroes hist0, dsp_stuff.cpp:145-152); int16 history of the 10x
 	// path: zero, raw u8 history of its 10:1 stage (or of the resampling stage): 128
@@ -676,7 +680,7 @@ int tfrec_amd_destroy(tfrec_amd_ctx *c)
 // resampling stage; ingest: another format at the base rate) and the context made for it
 // dc_k != 0: with the DC blocker over at most dc_rows rows (tfrec_amd_create_dc)
 static int create_with(const tfrec_amd_config *cfg, int32_t fmt, int32_t p, int32_t q, bool resamp, bool ingest, tfrec_amd_ctx **out,
-		       int32_t dc_k = 0, int32_t dc_rows = 0)
+		       int32_t dc_k = 0, int32_t dc_rows = 0, bool decimated = false)
 {
 	TRY(validate(cfg));
 	HIPCHK(hipSetDevice(cfg->device));
@@ -696,6 +700,7 @@ static int create_with(const tfrec_amd_config *cfg, int32_t fmt, int32_t p, int3
 	c->in_q = c->in10x ? 1 : q;
 	c->resamp = resamp;
 	c->ingest = ingest;
+	c->decin.on = decimated;
 	const int rc = init_context(c);
 	if (rc != TFREC_AMD_OK) {
 		tfrec_amd_destroy(c);

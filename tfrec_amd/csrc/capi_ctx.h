@@ -80,6 +80,28 @@ struct CaptureOut {
 	uint32_t *d_pool[kSets] = {};
 	std::vector<tfrec_amd_run> tmp;
 };
+// tfrec_amd_enable_capture_pre: per set the pair ahead of every run of the set's table
+struct CapturePre {
+	bool on = false;
+	uint32_t *d_pre[kSets] = {};
+};
+// tfrec_amd_create_decimated: the carried last pair of every stream
+struct DecIn {
+	bool on = false;
+	uint32_t *d_last = nullptr;
+};
+// tfrec_amd_enable_runs_input: the limits and, per set, the sparse submit's table ({ start, end, pool offset low, high } per run),
+// pool, pre, first_run[n_streams + 1] and the prevdec overrides ({ use, pair } per stream) on the device, each with its page-locked
+// source
+struct RunsIn {
+	bool on = false;
+	uint32_t max_runs = 0;
+	uint64_t max_samples = 0;
+	uint4 *d_tab[kSets] = {}, *h_tab[kSets] = {};
+	uint32_t *d_pool[kSets] = {}, *h_pool[kSets] = {}, *d_pre[kSets] = {}, *h_pre[kSets] = {};
+	int32_t *d_first[kSets] = {}, *h_first[kSets] = {};
+	uint2 *d_ov[kSets] = {}, *h_ov[kSets] = {};
+};
 // tfrec_amd_enable_spectrum: bins, frames per record, rows at most, records of the largest submit; per set sums and
 // peaks ([rows][max_records][n]), frame counts ([rows][max_records]) and what the set's submit held (rows analysed, records)
 struct SpectrumOut {
@@ -152,6 +174,9 @@ struct tfrec_amd_ctx {
 	FskState *d_fsk = nullptr;  // auto threshold (every context has it: a stream can be configured to auto)
 	LevelsOut lev;  // ---- side outputs
 	CaptureOut cap;
+	CapturePre cap_pre;
+	DecIn decin;
+	RunsIn runs_in;
 	SpectrumOut spec;
 	OccupancyOut occ;
 	int wmax = 0;

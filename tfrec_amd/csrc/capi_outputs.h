@@ -150,6 +150,10 @@ int tfrec_amd_enable_spectrum(tfrec_amd_ctx *c, int32_t n_bins, int32_t frames_p
 			 "n_bins is 64, 128, 256, 512 or 1024, frames_per_record within [1, 16384], max_rows within [1, n_streams]");
 		return TFREC_AMD_E_INVAL;
 	}
+	if (c->decin.on) {
+		snprintf(g_err, sizeof(g_err), "the spectrum's bounds assume |x| <= 8192: a channel-rate context has none");
+		return TFREC_AMD_E_INVAL;
+	}
 	TRY(begin_side_enable(c, c->spec.lane, "spectrum"));
 	HIPCHK(hipSetDevice(c->cfg.device));
 	// the largest submit: floor(max_blocks * 32768 * P / Q) complex samples per row

@@ -124,6 +124,10 @@ int tfrec_amd_tune_streams(tfrec_amd_ctx *c, const int32_t *streams, const int32
 {
 	if (!c || n < 0 || (n > 0 && (!streams || !tune_hz)))
 		return TFREC_AMD_E_INVAL;
+	if (c->decin.on) {
+		snprintf(g_err, sizeof(g_err), "the tunes are defined ahead of process_iq: a channel-rate context has none");
+		return TFREC_AMD_E_INVAL;
+	}
 	TRY(tune_common(c, streams, tune_hz, n, 1, 1, [](int32_t hz) { return outside_limit(hz, kTuneLimit); }, c->tune_hz, c->tune_inc,
 			c->n_tuned));
 	if (n > 0)

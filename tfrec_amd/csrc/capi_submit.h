@@ -33,6 +33,7 @@ struct StreamReset {
 	WhbExact *whbx;     // WHB check's exact filter state, its carry and the redo's chain state (WHB registered), or nullptr
 	int *whbcarry;
 	ChainState *whbX;
+	uint32_t *last;     // tfrec_amd_create_decimated: the stream's carried last pair, or nullptr
 };
 
 __global__ __launch_bounds__(64) void stream_reset_kernel(StreamReset R)
@@ -71,6 +72,8 @@ __global__ __launch_bounds__(64) void stream_reset_kernel(StreamReset R)
 			R.whbx[s] = WhbExact{ 0.0, 0.0, 0, 0, 0, 0 };
 			R.whbcarry[s] = 0;
 		}
+		if (R.last)
+			R.last[s] = 0u;
 	}
 }
 }  // namespace tfrec
@@ -121,6 +124,7 @@ static int launch_resets(tfrec_amd_ctx *c, int set)
 	R.whbx = c->d_whbx;
 	R.whbcarry = c->d_whbcarry;
 	R.whbX = c->d_whbX;
+	R.last = c->decin.d_last;
 	hipLaunchKernelGGL(tfrec::stream_reset_kernel, dim3(nl), dim3(64), 0, fs, R);
 	HIPCHK(hipGetLastError());
 	return TFREC_AMD_OK;
@@ -232,15 +236,38 @@ static int launch_dc_rows(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, size_t
 	return TFREC_AMD_OK;
 }
 
+// The channel-rate front end in the place of the pre-stage and the front end: the dense kernel on the rows, or
+// -- runs: tfrec_amd_submit_runs staged this set's table -- the sparse one
+static int launch_decin_front(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, size_t stride, int n_blocks, bool runs)
+{
+	hipStream_t fs = c->pipe[set].fs;
+	const RunsIn &o = c->runs_in;
+	uint32_t *last = c->decin.d_last;
+	const int thresh = c->cfg.thresh ? c->cfg.thresh : 500;
+	const StreamCfg *scfg = c->per_stream ? c->d_scfg : nullptr;
+	if (runs) {
+		HIPCHK(launch_decin_runs(fs, c->cfg.n_streams, n_blocks, o.d_tab[set], o.d_pool[set], o.d_pre[set], o.d_first[set], o.d_ov[set],
+					 c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->d_prevdec[set], last, thresh, scfg));
+		return TFREC_AMD_OK;
+	}
+	if (c->mapped)  // the kernel looks the row up
+		TRY(stage_chan(c, set));
+	HIPCHK(launch_decin(fs, d_iq, stride, c->cfg.n_streams, n_blocks, c->mapped ? c->d_chan[set] : nullptr, c->d_dec[set], c->dec_stride,
+			    c->d_mask[set], c->mask_stride, c->d_prevdec[set], last, thresh, scfg));
+	return TFREC_AMD_OK;
+}
+
 // input_on_fs: the input was produced on the front-end stream itself (staged host input): no event needed
-static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int n_blocks, void *hip_stream, bool input_on_fs)
+// runs: a sparse submit (tfrec_amd_submit_runs, which checked and staged everything on the front-end stream): there are no rows
+static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int n_blocks, void *hip_stream, bool input_on_fs,
+			 bool runs = false)
 {
 	if (!c || !d_iq || n_blocks < 1 || n_blocks > c->cfg.max_blocks)
 		return TFREC_AMD_E_INVAL;
 	size_t row_bytes = 0;
 	TRY(input_bytes(c, n_blocks, &row_bytes));
-	if ((stride % 16) != 0 || ((uintptr_t)d_iq % 16) != 0 ||
-	    (rows_in_use(c) > 1 && stride < row_bytes)) {  // (one row in use: the stride is never applied)
+	if (!runs && ((stride % 16) != 0 || ((uintptr_t)d_iq % 16) != 0 ||
+		      (rows_in_use(c) > 1 && stride < row_bytes))) {  // (one row in use: the stride is never applied)
 		snprintf(g_err, sizeof(g_err), "IQ base and stream stride must be 16-byte aligned and >= one stream");
 		return TFREC_AMD_E_INVAL;
 	}
@@ -285,11 +312,13 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	const bool resets = !c->reset_pending.empty();
 	if (resets)
 		TRY(launch_resets(c, set));
+	if (c->decin.on)
+		TRY(launch_decin_front(c, set, (const uint8_t *)d_iq, stride, n_blocks, runs));
 	const uint8_t *fin = (const uint8_t *)d_iq;
 	size_t fstride = stride;
 	// a mapped or wide-tuned context: the 10:1 stage's tuned kernel, or -- default input -- the front end that looks up the rows
 	// (a rate context: the resampling stage looks the row up, as the 10:1 stage does)
-	const bool chan10 = c->in16 && (c->mapped || c->n_wide), chan_front = !c->in16 && c->mapped;
+	const bool chan10 = c->in16 && (c->mapped || c->n_wide), chan_front = !c->in16 && c->mapped && !c->decin.on;
 	if (chan10 || chan_front)
 		TRY(stage_chan(c, set));
 	if (c->in16) {  // ... then the standard cascade on int16 input
@@ -306,10 +335,11 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	}
 	if (c->n_tuned || chan_front)
 		TRY(stage_tune(c, set));
-	HIPCHK(launch_frontend(fs, fin, fstride, c->cfg.n_streams, n_blocks, c->d_tail[c->tail_sel],
-			       c->d_tail[c->tail_sel ^ 1], c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride,
-			       c->d_prevdec[set], c->cfg.thresh ? c->cfg.thresh : 500, c->taps, c->in16,
-			       (c->n_tuned || chan_front) ? c->d_tune[set] : nullptr, chan_front ? c->d_chan[set] : nullptr));
+	if (!c->decin.on)
+		HIPCHK(launch_frontend(fs, fin, fstride, c->cfg.n_streams, n_blocks, c->d_tail[c->tail_sel],
+				       c->d_tail[c->tail_sel ^ 1], c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride,
+				       c->d_prevdec[set], c->cfg.thresh ? c->cfg.thresh : 500, c->taps, c->in16,
+				       (c->n_tuned || chan_front) ? c->d_tune[set] : nullptr, chan_front ? c->d_chan[set] : nullptr));
 	if (c->n_auto)  // auto threshold: per-block thresholds rewrite the trigger mask (fm_demod.cpp:58-73)
 		HIPCHK(launch_threshold(fs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams,
 					n_blocks, c->d_fsk, c->wmax, c->per_stream ? c->d_scfg : nullptr));
@@ -334,6 +364,9 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		HIPCHK(launch_capture(c->cap.lane.st, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams, n_blocks,
 				      c->sample_base, c->cap.d_state, c->d_scfg, c->cap.d_stage, c->cap.stage_cap, c->cap.d_cnt, c->cap.d_base,
 				      c->cap.d_hdr[set], c->cap.d_runs[set], c->cap.max_runs, c->cap.d_pool[set], c->cap.max_samples));
+		if (c->cap_pre.on)  // the pair ahead of every run: behind the copy kernel, which wrote the table
+			HIPCHK(launch_capture_pre(c->cap.lane.st, c->cap.d_runs[set], c->cap.d_hdr[set], c->cap.max_runs, c->sample_base,
+						  c->d_dec[set], c->dec_stride, c->d_prevdec[set], c->cap_pre.d_pre[set]));
 		HIPCHK(lane_written(c->cap.lane, set));
 	}
 	if (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) {

@@ -850,5 +850,6 @@ hipError_t launch_fmdev(hipStream_t st, const uint32_t *dec, size_t dec_stride, 
 #include "capture.h"   // capture_scan_kernel, capture_offsets_kernel, capture_copy_kernel, launch_capture
 #include "spectrum.h"  // spectrum_kernel, launch_spectrum
 #include "occupancy.h"  // occupancy_kernel, launch_occupancy
+#include "decin.h"     // decin_kernel, capture_pre_kernel and their launchers
 
 }  // namespace tfrec

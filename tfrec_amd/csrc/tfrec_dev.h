@@ -29,7 +29,8 @@ constexpr int kTailBytes = 112;                 // raw bytes of history carried 
 constexpr int kNSlots = TFREC_AMD_NSLOTS;
 // sample formats of the input rows (formats.h) and the bytes of one complex sample
 constexpr int kFmtU8 = TFREC_AMD_FMT_U8, kFmtS8 = TFREC_AMD_FMT_S8, kFmtS16 = TFREC_AMD_FMT_S16, kFmtF32 = TFREC_AMD_FMT_F32;
-__host__ __device__ constexpr int fmt_sample_bytes(int fmt) { return fmt == kFmtF32 ? 8 : fmt == kFmtS16 ? 4 : 2; }
+constexpr int kFmtDec16 = TFREC_AMD_FMT_DEC16;  // tfrec_amd_create_decimated: int16 pairs at 384 kS/s (no kernel is templated on it)
+__host__ __device__ constexpr int fmt_sample_bytes(int fmt) { return fmt == kFmtF32 ? 8 : (fmt == kFmtS16 || fmt == kFmtDec16) ? 4 : 2; }
 
 // ---- front-end tile geometry: a 256-thread workgroup per tile, kFrontOut decimated outputs (and 2 * kFrontOut
 // stage-1 outputs) per thread.  8 per thread: the per-wave scalar work (addresses, taps, edge tests) and the 6 raw

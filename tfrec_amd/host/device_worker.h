@@ -47,6 +47,7 @@ private:
 	int open_context();
 	void read_batches();
 	int submit(size_t k);
+	int submit_runs(size_t k);
 	int collect(size_t k, batch_result &b);
 	int read_captures(size_t k, batch_result &b);
 	int read_dc(size_t k, batch_result &b);
@@ -83,6 +84,11 @@ private:
 	std::condition_variable rcv;
 	size_t filled, drained;  // batches read / batches whose buffer is free again
 	bool read_failed;
+	// -R: per file of this device the blocks submitted so far and the first run that may reach into the next submit; one submit's
+	// table, pool and pre
+	std::vector<size_t> replay_pos, replay_from;
+	std::vector<tfrec_amd_run> rtab;
+	std::vector<int16_t> rpool, rpre;
 };
 
 inline device_worker::device_worker(const job_settings &job_, const std::vector<std::string> &files_, const std::vector<size_t> &file_blocks_,
@@ -140,14 +146,15 @@ inline int device_worker::work()
 	if (r)
 		return r;
 	const int depth = std::max(1, std::min(tfrec_amd_fifo_depth(), TFREC_AMD_FIFO_DEPTH));
-	row = (size_t)(bps / job.unit()) * job.piece_bytes();
+	row = job.replay ? 0 : (size_t)(bps / job.unit()) * job.piece_bytes();  // (-R: nothing is read, the tables are in memory)
 	for (int b = 0; b < kBufs; b++) {
 		host[b] = (uint8_t *)tfrec_amd_host_alloc(n_rows * row);
 		pinned[b] = host[b] != NULL;  // per buffer: each is released by the allocator it came from
 		if (!host[b])  // no page-locked memory: this buffer's copies become synchronous, results are the same
 			host[b] = (uint8_t *)malloc(n_rows * row);
 	}
-	reader = std::thread([this]() { read_batches(); });
+	if (!job.replay)
+		reader = std::thread([this]() { read_batches(); });
 	size_t queued = 0;
 	for (size_t k = 0; k < plan.size() && r == 0; k++) {
 		while (queued < plan.size() && queued < k + (size_t)depth && r == 0)
@@ -211,7 +218,8 @@ inline int device_worker::open_context()
 	narrow_tune.assign(n, false);
 	const char *call = "tfrec_amd_create";
 	// (the rows are known: -z sizes the blocker for them)
-	int r = job.dc_windows		       ? tfrec_amd_create_dc(&cfg, job.fmt, job.rate_p, job.rate_q, job.dc_windows, (int32_t)n_rows, &ctx)
+	int r = job.replay		       ? tfrec_amd_create_decimated(&cfg, &ctx)
+		: job.dc_windows	       ? tfrec_amd_create_dc(&cfg, job.fmt, job.rate_p, job.rate_q, job.dc_windows, (int32_t)n_rows, &ctx)
 		: job.fmt != TFREC_AMD_FMT_U8  ? tfrec_amd_create_format(&cfg, job.fmt, job.rate_p, job.rate_q, &ctx)
 		: job.resampled()	       ? tfrec_amd_create_rate(&cfg, job.rate_p, job.rate_q, &ctx)
 					       : tfrec_amd_create(&cfg, &ctx);
@@ -227,6 +235,23 @@ inline int device_worker::open_context()
 		call = "tfrec_amd_enable_capture";
 		r = tfrec_amd_enable_capture(ctx, (uint32_t)(n * ((size_t)bps * TFREC_AMD_BLOCK_DEC / 356 + 3)),
 					     (uint64_t)n * (uint64_t)bps * TFREC_AMD_BLOCK_DEC);
+	}
+	if (!r && job.capture) {  // ... and the pair ahead of every run
+		call = "tfrec_amd_enable_capture_pre";
+		r = tfrec_amd_enable_capture_pre(ctx);
+	}
+	if (!r && job.replay) {  // -R, sized so that every submit fits: its files' runs (a cut adds one per stream), every sample at most
+		uint64_t runs = 0, pairs = 0;
+		for (size_t f = s0; f < s1; f++) {
+			runs += (*job.replay)[f].runs.size();
+			pairs += (*job.replay)[f].pool.size() / 2;
+		}
+		runs = std::min<uint64_t>(runs + n, (uint64_t)n * ((uint64_t)bps * TFREC_AMD_BLOCK_DEC / 2 + 1));
+		pairs = std::min<uint64_t>(pairs, (uint64_t)n * (uint64_t)bps * TFREC_AMD_BLOCK_DEC);
+		call = "tfrec_amd_enable_runs_input";
+		r = tfrec_amd_enable_runs_input(ctx, (uint32_t)std::max<uint64_t>(1, runs), std::max<uint64_t>(1, pairs));
+		replay_pos.assign(s1 - s0, 0);
+		replay_from.assign(s1 - s0, 0);
 	}
 	if (!r && job.spectrum) {  // -P: the one file's row
 		call = "tfrec_amd_enable_spectrum";
@@ -298,7 +323,7 @@ inline void device_worker::read_batches()
 // batch k, once the reader has filled its buffer: the resets, configures and tunes its plan asks for, then the submit
 inline int device_worker::submit(size_t k)
 {
-	{
+	if (!job.replay) {
 		std::unique_lock<std::mutex> lk(rmu);
 		rcv.wait(lk, [&]() { return filled > k; });
 	}
@@ -326,7 +351,28 @@ inline int device_worker::submit(size_t k)
 		r = job.wide ? tfrec_amd_tune_streams_wide(ctx, b.tune.data(), b.tune_hz.data(), (int)b.tune.size())
 			     : tfrec_amd_tune_streams(ctx, b.tune.data(), b.tune_hz.data(), (int)b.tune.size());
 	}
-	return r ? r : tfrec_amd_submit_host(ctx, host[k % kBufs], row, b.nb);
+	if (r)
+		return r;
+	return job.replay ? submit_runs(k) : tfrec_amd_submit_host(ctx, host[k % kBufs], row, b.nb);
+}
+
+// -R: batch k as a sparse submit -- every stream's part of its file's capture (the tables are ordered by stream)
+inline int device_worker::submit_runs(size_t k)
+{
+	const batch_plan &b = plan[k];
+	rtab.clear();
+	rpool.clear();
+	rpre.clear();
+	for (size_t s = 0; s < n; s++) {
+		const int f = b.file[s];
+		if (f < 0)
+			continue;
+		size_t &pos = replay_pos[f - s0];
+		rebase_runs((*job.replay)[f], (uint32_t)s, (long long)pos * TFREC_AMD_BLOCK_DEC, (long long)b.nb * TFREC_AMD_BLOCK_DEC, replay_from[f - s0],
+			    rtab, rpool, rpre);
+		pos += (size_t)b.nb;
+	}
+	return tfrec_amd_submit_runs(ctx, rtab.data(), (uint32_t)rtab.size(), rpool.data(), rpool.size() / 2, rpre.data(), b.nb);
 }
 
 // -S: the batch's captures.  stream -> file, as for the events; a run is cut at its file's end
@@ -339,6 +385,13 @@ inline int device_worker::read_captures(size_t k, batch_result &b)
 		b.runs.resize((size_t)nr + 1);
 		b.pool.resize(2 * (size_t)np + 2);
 		r = tfrec_amd_read_captures(ctx, b.runs.data(), b.runs.size(), &nr, b.pool.data(), b.pool.size() / 2, &np);
+		if (r == 0 || r == TFREC_AMD_E_OVERFLOW) {  // the pair ahead of every run delivered
+			uint32_t npre = 0;
+			b.pre.resize(2 * ((size_t)nr + 1));
+			const int rp = tfrec_amd_read_capture_pre(ctx, b.pre.data(), b.pre.size() / 2, &npre);
+			if (rp != 0 && rp != TFREC_AMD_E_OVERFLOW)
+				r = rp;
+		}
 	}
 	size_t have = nr;
 	if (r == TFREC_AMD_E_OVERFLOW) {  // the runs that fitted were returned (n_samples == 0 ends them); the job goes on
@@ -360,9 +413,12 @@ inline int device_worker::read_captures(size_t k, batch_result &b)
 			continue;
 		x.n_samples = (uint32_t)std::min<long long>(x.n_samples, end - x.start_sample);
 		b.file.push_back(file[x.stream]);
+		b.pre[2 * kept] = b.pre[2 * q];
+		b.pre[2 * kept + 1] = b.pre[2 * q + 1];
 		b.runs[kept++] = x;
 	}
 	b.runs.resize(kept);
+	b.pre.resize(2 * kept);
 	return 0;
 }
 
@@ -458,7 +514,8 @@ inline int device_worker::close_context(int r)
 		drained = plan.size() + kBufs;  // let the reader run out after an error
 	}
 	rcv.notify_all();
-	reader.join();
+	if (reader.joinable())
+		reader.join();
 	tfrec_amd_destroy(ctx);
 	for (int b = 0; b < kBufs; b++) {
 		if (pinned[b])

@@ -131,7 +131,7 @@ void gpu_engine::replay(const tfrec_amd_event &ev)
 
 // ---- the output modes' consumers (job.h): what they print and write
 
-// -S: <prefix>.idx and the files' <prefix>.<file>.cs16 (gpu_engine.h: set_capture)
+// -S: <prefix>.idx and the files' <prefix>.<file>.cs16 and .pre (gpu_engine.h: set_capture)
 struct capture_writer {
 	std::string prefix;
 	FILE *idx;
@@ -157,15 +157,25 @@ struct capture_writer {
 				perror(path.c_str());
 				return TFREC_AMD_E_INVAL;
 			}
+			const std::string pre_path = prefix + "." + std::to_string(f) + ".pre";
+			FILE *pp = fopen(pre_path.c_str(), made[f] ? "ab" : "wb");
+			if (!pp) {
+				perror(pre_path.c_str());
+				fclose(fp);
+				return TFREC_AMD_E_INVAL;
+			}
 			made[f] = true;
 			for (; q < b.runs.size() && b.file[q] == f; q++) {
 				const tfrec_amd_run &x = b.runs[q];
 				fprintf(idx, "%d %u %lld %u %d %u\n", f, (unsigned)x.stream, (long long)x.start_sample, (unsigned)x.n_samples, (int)x.thresh,
 					(unsigned)x.flags);
-				if (fwrite(b.pool.data() + 2 * (size_t)x.pool_offset, 4, x.n_samples, fp) != x.n_samples)
+				if (fwrite(b.pool.data() + 2 * (size_t)x.pool_offset, 4, x.n_samples, fp) != x.n_samples ||
+				    fwrite(b.pre.data() + 2 * q, 4, 1, pp) != 1)
 					rc = TFREC_AMD_E_INVAL;
 			}
 			if (fclose(fp))
+				rc = TFREC_AMD_E_INVAL;
+			if (fclose(pp))
 				rc = TFREC_AMD_E_INVAL;
 		}
 		return rc;
@@ -292,7 +302,11 @@ int gpu_engine::run()
 	stream_samples.assign(n, 0);
 	const size_t piece = job.piece_bytes();
 	const int unit = job.unit();
-	for (size_t s = 0; s < n; s++) {
+	for (size_t s = 0; s < n && job.replay; s++) {  // -R: a capture is as long as its last run reaches
+		file_blocks[s] = (*job.replay)[s].blocks();
+		stream_samples[s] = (long long)file_blocks[s] * TFREC_AMD_BLOCK_DEC;
+	}
+	for (size_t s = 0; s < n && !job.replay; s++) {
 		FILE *f = fopen(files[s].c_str(), "rb");
 		if (!f) {
 			perror(files[s].c_str());

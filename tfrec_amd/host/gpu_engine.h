@@ -140,6 +140,8 @@ public:
 	// windows; run() writes <prefix>.idx -- text, one line "<file index> <stream> <start_sample> <n_samples> <thresh> <flags>" per run
 	// in submit order, stream = the file's stream on its device, start_sample counted within the file -- and, for every file with
 	// a run, <prefix>.<file index>.cs16: the file's captured samples appended submit by submit, 384 kS/s int16 interleaved I, Q.
+	// <prefix>.<file index>.pre holds one int16 (I, Q) per .idx line of the file, in .idx order: the decimated sample just ahead of
+	// the run (tfrec_amd_enable_capture_pre) -- with it set_replay reproduces the recording's events.
 	// The capture is sized from the batch's blocks and the stream count so that no submit can overflow it; should one, a warning
 	// goes to stderr per submit and the run goes on.  Runs are cut at the file's end (the padding behind it is not the file's).
 	void set_capture(const std::string &prefix) { job.capture = true; job.cap_prefix = prefix; }
@@ -178,6 +180,11 @@ public:
 	// prints "dc <file> I=<d> Q=<d>" per submit and file: the estimate of the submit's last window of the file's row.  Under -A
 	// only pass 2 is given it: pass 1's spectrum reads the raw rows either way.  Excludes set_wide.
 	void set_dc(int windows) { job.dc_windows = windows; }
+	// -R: replay a capture.  The engine's files are the capture's -- captures[i] is file i of the job, read back whole,
+	// and a file's length is its last run's end rounded up to blocks --; every context takes channel-rate input
+	// (tfrec_amd_create_decimated) and is fed sparse submits (tfrec_amd_submit_runs) cut by the batch plan, so -b, -n and -d work as
+	// with dumps.  captures outlives the engine.  Excludes every set_* that concerns the input.
+	void set_replay(const std::vector<replay_file> &captures) { job.replay = &captures; }
 	// returns 0 on success, a TFREC_AMD_E_* code otherwise
 	int run();
 	// decoders of stream s in slot order (NULL for slots not registered)

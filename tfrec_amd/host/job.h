@@ -22,6 +22,20 @@ struct file_settings {
 	bool operator!=(const file_settings &o) const { return !(*this == o); }
 };
 
+// -R: one file of a capture (tfrec_gpu -S), read back whole: its .idx lines in order -- start_sample counted within the file,
+// pool_offset into `pool` --, its .cs16 pairs and its .pre pairs, one per line
+struct replay_file {
+	int index;  // the file index of the .idx lines
+	std::vector<tfrec_amd_run> runs;
+	std::vector<int16_t> pool, pre;
+	// the last run's end rounded up to blocks
+	size_t blocks() const
+	{
+		const long long end = runs.empty() ? 0 : runs.back().start_sample + (long long)runs.back().n_samples;
+		return (size_t)((end + TFREC_AMD_BLOCK_DEC - 1) / TFREC_AMD_BLOCK_DEC);
+	}
+};
+
 // Everything gpu_engine's set_* calls store (gpu_engine.h says what each mode does), one copy for the engine and all its workers,
 // and the input geometry that follows from it.
 struct job_settings {
@@ -41,6 +55,7 @@ struct job_settings {
 	int occ_ratio = 0, occ_rel = 0;  // set_occupancy (0: none)
 	long occ_join = 0;
 	int dc_windows = 0;            // set_dc (0: none)
+	const std::vector<replay_file> *replay = NULL;  // set_replay (NULL: the files are dumps)
 
 	bool resampled() const { return rate_p != 1 || rate_q != 1; }
 	bool occupancy() const { return spectrum && occ_ratio; }  // -A, pass 1
@@ -153,6 +168,40 @@ inline std::vector<batch_plan> plan_batches(const std::vector<size_t> &file_bloc
 	return plan;
 }
 
+// -R: the part of a capture that one submit of `stream` holds, samples [base, base + M) of the file -> appended to the submit's
+// table (start_sample relative to base, pool_offset into `pool`), pool and pre, as tfrec_amd_submit_runs takes them (tfrec_amd/decin.py:
+// rebase).  A run is cut at the submit's boundaries: a part that begins inside a run has the run's pair before it as its pre.
+// Runs that touch -- the two halves of one the recording cut at a submit boundary -- are joined.  from: the first run that may
+// reach into the submit, moved on for the next one.
+inline void rebase_runs(const replay_file &rf, uint32_t stream, long long base, long long M, size_t &from, std::vector<tfrec_amd_run> &tab,
+			std::vector<int16_t> &pool, std::vector<int16_t> &pre)
+{
+	const size_t first = tab.size();
+	while (from < rf.runs.size() && rf.runs[from].start_sample + (long long)rf.runs[from].n_samples <= base)
+		from++;
+	for (size_t i = from; i < rf.runs.size() && rf.runs[i].start_sample < base + M; i++) {
+		const tfrec_amd_run &r = rf.runs[i];
+		const long long a = r.start_sample, lo = std::max(a, base), hi = std::min(a + (long long)r.n_samples, base + M);
+		if (lo >= hi)
+			continue;
+		const int16_t *src = rf.pool.data() + 2 * ((size_t)r.pool_offset + (size_t)(lo - a));
+		if (tab.size() > first && tab.back().start_sample + (long long)tab.back().n_samples == lo - base) {
+			tab.back().n_samples += (uint32_t)(hi - lo);
+		} else {
+			tfrec_amd_run x = r;
+			x.stream = stream;
+			x.start_sample = lo - base;
+			x.n_samples = (uint32_t)(hi - lo);
+			x.pool_offset = pool.size() / 2;
+			tab.push_back(x);
+			const int16_t *p = lo == a ? rf.pre.data() + 2 * i : src - 2;
+			pre.push_back(p[0]);
+			pre.push_back(p[1]);
+		}
+		pool.insert(pool.end(), src, src + 2 * (size_t)(hi - lo));
+	}
+}
+
 // -r: a batch's tunes as the two calls they become.  An offset within +-767 kHz is a tune behind the resampler, as it always
 // was (tfrec_amd_tune_streams: narrow); a larger one is the input-rate tune ahead of it (tfrec_amd_tune_streams_input: input).
 // A stream that goes from one kind to the other (-n) has the other kind cleared to 0; all of it is one restart.  in_tune /
@@ -240,7 +289,7 @@ inline std::vector<occ_channel> occupancy_channels(const std::vector<unsigned lo
 // What one batch of one device brings to the engine's thread: its flush events (stream = the file's index in the job), and
 // -s: its level records, [stream][the batch's blocks]
 // -S: the runs that belong to a file (file[i]: its index in the job), cut at the file's end, and the batch's sample pool, which
-//     their pool_offset indexes
+//     their pool_offset indexes; pre: the pair ahead of every run kept
 // -P: the spectrum records of input row 0, [record][bin], and their frame counts
 // -A: the detector's records of row 0 and their bitmap words, [record][N / 32]
 // -z with -D: per file of the batch its index in the job and the last window's {d_I, d_Q} of its row
@@ -249,7 +298,7 @@ struct batch_result {
 	std::vector<tfrec_amd_level> lv;
 	std::vector<tfrec_amd_run> runs;
 	std::vector<int> file;
-	std::vector<int16_t> pool;
+	std::vector<int16_t> pool, pre;
 	std::vector<uint64_t> spec_sum, spec_peak;
 	std::vector<uint32_t> spec_frames;
 	std::vector<tfrec_amd_occupancy> occ_recs;

@@ -6,6 +6,7 @@
 //   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-c kHz] [-x | -r Hz] [-F format] [-D] [-d device] [-b blocks] -s step_kHz -L dump.iq
 //   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-c kHz] [-x | -r Hz] [-F format] [-D] [-d device] [-b blocks] [-P bins[,frames]]
 //             -A [ratio[,rel[,join_kHz]]] -L dump.iq
+//   tfrec_gpu [-T hexmask] [-t thresh] [-q] [-D] [-d device[,device...]] [-b blocks] [-n streams] [-e handler | -E handler] -R prefix
 //   tfrec_gpu [-T hexmask] -X telegrams.txt
 //
 // Flags keep the reference's meaning (main.cpp:63-88, 107-164): -T sensor type bit mask (hex), -t trigger
@@ -55,7 +56,17 @@
 // <prefix>.idx gets one text line "<file index> <stream> <start_sample> <n_samples> <thresh> <flags>" per run, in submit order;
 // <prefix>.<file index>.cs16 that file's captured samples, appended submit by submit: 384 kS/s int16 interleaved I, Q, which any
 // SDR viewer opens (a file without a run gets none).  Works with -s -- a channel that triggers and decodes nothing is the case
-// it is for -- and with everything else but -X.
+// it is for -- and with everything else but -X.  <prefix>.<file index>.pre gets one int16 (I, Q) per .idx line of that file, in .idx
+// order: the decimated sample just ahead of the run (tfrec_amd_enable_capture_pre), which a viewer does not need and -R does.
+// -R prefix (not in the reference): replay a capture made by -S: decode the archived trigger windows again, without
+// the recording -- with another -T, a stricter -t, other handlers.  One job per file index found in <prefix>.idx, its length the
+// last run's end rounded up to blocks; the contexts take channel-rate input (tfrec_amd_create_decimated) and are fed the runs
+// themselves (tfrec_amd_submit_runs), cut into submits by -b.  Takes -T, -t, -W (no effect: there is no filter stage), -d, -n, -b,
+// -B, -m, -D, -q, -e / -E.  The replay gives the recording's own telegrams, bit for bit, when its demodulators are a subset of the
+// recording's whose largest window is at most the recording's, and: with a fixed threshold, -t is at least the recorded one; with
+// the auto threshold, the recording was auto from the stream's start and complete.  With -L, -x, -r, -F, -f, -c, -s, -A, -P, -z,
+// -S, -p or -X, or when .idx is missing or inconsistent -- a line that does not parse, runs of a file that overlap or are out of
+// order, a .cs16 or .pre shorter than the lines ask for --, it is a usage error: exit 2 before a device is opened.
 // -P bins[,frames_per_record] (not in the reference): the power spectrum of ONE recording, beside its decoding: an
 // exact integer DFT of bins = 64, 128, 256, 512 or 1024 bins over the raw input -- at 1.536 MS/s, or given with -x, or with -r / -F --,
 // per record of frames_per_record frames (1 .. 16384; default: the frames one block's input holds, at least 1) the sum and the peak
@@ -90,6 +101,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -218,6 +230,9 @@ struct cli {
 	long scan_step = 0;  // -s: kHz
 	bool have_scan = false;
 	const char *cap_prefix = NULL;  // -S
+	const char *replay_prefix = NULL;  // -R
+	bool have_center = false, have_format = false;  // -c, -F given (-R refuses them)
+	std::vector<replay_file> captures;  // -R: one per file index of <prefix>.idx
 	int spec_bins = 0, spec_g = 0;  // -P (spec_g 0: the default)
 	bool have_spec_p = false;
 	bool have_auto = false;  // -A
@@ -239,6 +254,7 @@ struct cli {
 	int scan_channels();
 	int tune_files();
 	int find_channels();
+	int load_capture();
 	int run();
 };
 
@@ -251,6 +267,8 @@ static void usage()
 			"  -P bins[,G] power spectrum of one dump beside its decoding: bins = 64 .. 1024 (a power of two), G frames per record; a\n"
 			"              line per bin behind the telegrams (-D: per record too)\n"
 			"  -S prefix   record the IQ of every trigger window: <prefix>.idx (a line per run) and <prefix>.<file>.cs16 (384 kS/s int16 I, Q)\n"
+			"  -R prefix   replay a capture made by -S (<prefix>.idx, .cs16, .pre): decode its trigger windows again, with -T, -t, -d, -n, -b,\n"
+			"              -D, -q, -e / -E; not with -L or anything that describes a dump\n"
 			"  -f kHz      receive frequency (default: the dumps' own, -c)\n"
 			"  -c kHz      frequency the dumps were recorded at (default 868250); -f within 767 kHz of it\n"
 			"  -x          the dumps are 15.36 MS/s u8 dumps (10x the rate); -f within 7679 kHz of -c, shifted ahead of the 10:1 stage\n"
@@ -319,7 +337,7 @@ bool cli::parse_format(const char *arg)
 int cli::parse(int argc, char **argv)
 {
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:P:A::z::h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::h")) != -1) {
 		switch (c) {
 		case 'z': {
 			const char *a = optional_arg(argc, argv);
@@ -353,11 +371,19 @@ int cli::parse(int argc, char **argv)
 				return 1;
 			}
 			break;
+		case 'R':
+			replay_prefix = optarg;
+			if (!*replay_prefix) {
+				fprintf(stderr, "tfrec_gpu: bad -R '': want the prefix of the capture to replay\n");
+				return 2;
+			}
+			break;
 		case 'T': types = (int)strtol(optarg, NULL, 16); break;
 		case 't': thresh = atoi(optarg); break;
 		case 'W': filter = 1; break;
 		case 'f':
 		case 'c':
+			have_center = have_center || c == 'c';
 			if (!parse_khz(optarg, c == 'f' ? freq : center)) {
 				fprintf(stderr, "tfrec_gpu: bad -%c '%s': want a frequency in kHz\n", c, optarg);
 				return 1;
@@ -371,6 +397,7 @@ int cli::parse(int argc, char **argv)
 			}
 			break;
 		case 'F':
+			have_format = true;
 			if (!parse_format(optarg))
 				return 1;
 			break;
@@ -410,6 +437,12 @@ int cli::parse(int argc, char **argv)
 // what excludes what, before any file is looked at
 int cli::check() const
 {
+	if (replay_prefix && (!dumps.empty() || wide || rate || have_format || freq >= 0 || have_center || have_scan || have_auto || have_spec_p ||
+			      dc_windows || cap_prefix || have_spec || hexfile)) {
+		fprintf(stderr, "tfrec_gpu: -R replays a capture, which is 384 kS/s int16 IQ and nothing else: not with -L, -x, -r, -F, -f, -c, -s, "
+				"-A, -P, -z, -S, -p or -X\n");
+		return 2;
+	}
 	if (have_slots && slots < 1) {
 		fprintf(stderr, "tfrec_gpu: -n must be >= 1\n");
 		return 1;
@@ -575,9 +608,80 @@ int cli::find_channels()
 	return -1;
 }
 
+// -R: <prefix>.idx, and per file index found in it <prefix>.<i>.cs16 and <prefix>.<i>.pre, read and checked before a device is opened
+// -> the captures, in ascending file index, and their names as the job's files
+int cli::load_capture()
+{
+	const std::string prefix(replay_prefix), idx_path = prefix + ".idx";
+	FILE *idx = fopen(idx_path.c_str(), "r");
+	if (!idx) {
+		perror(idx_path.c_str());
+		return 2;
+	}
+	std::map<int, replay_file> by_index;
+	char line[256];
+	for (long ln = 1; fgets(line, sizeof(line), idx); ln++) {
+		int f = 0, thr = 0, used = 0;
+		unsigned stream = 0, n = 0, flags = 0;
+		long long start = 0;
+		const char *why = NULL;
+		if (sscanf(line, "%d %u %lld %u %d %u %n", &f, &stream, &start, &n, &thr, &flags, &used) != 6 || line[used])
+			why = "want '<file index> <stream> <start_sample> <n_samples> <thresh> <flags>'";
+		else if (f < 0 || start < 0 || n < 1)
+			why = "a negative file index or start_sample, or an empty run";
+		else {
+			replay_file &rf = by_index[f];
+			rf.index = f;
+			const long long end = rf.runs.empty() ? 0 : rf.runs.back().start_sample + (long long)rf.runs.back().n_samples;
+			if (start < end)
+				why = "the run overlaps the file's run before it, or the file's runs are out of order";
+			else {
+				const tfrec_amd_run r = { stream, flags, start, n, thr,
+							  (uint64_t)(rf.runs.empty() ? 0 : rf.runs.back().pool_offset + rf.runs.back().n_samples) };
+				rf.runs.push_back(r);
+			}
+		}
+		if (why) {
+			fprintf(stderr, "%s:%ld: %s\n", idx_path.c_str(), ln, why);
+			fclose(idx);
+			return 2;
+		}
+	}
+	fclose(idx);
+	for (std::map<int, replay_file>::iterator it = by_index.begin(); it != by_index.end(); ++it) {
+		replay_file &rf = it->second;
+		const size_t pairs = (size_t)(rf.runs.back().pool_offset + rf.runs.back().n_samples);
+		const struct {
+			const char *ext;
+			size_t want;
+			std::vector<int16_t> *to;
+		} parts[2] = { { ".cs16", pairs, &rf.pool }, { ".pre", rf.runs.size(), &rf.pre } };
+		for (int k = 0; k < 2; k++) {
+			const std::string path = prefix + "." + std::to_string(rf.index) + parts[k].ext;
+			FILE *fp = fopen(path.c_str(), "rb");
+			if (!fp) {
+				perror(path.c_str());
+				return 2;
+			}
+			parts[k].to->resize(2 * parts[k].want);
+			const size_t got = fread(parts[k].to->data(), 4, parts[k].want, fp);
+			fclose(fp);
+			if (got != parts[k].want) {
+				fprintf(stderr, "%s: %zu pairs, the lines of %s ask for %zu\n", path.c_str(), got, idx_path.c_str(), parts[k].want);
+				return 2;
+			}
+		}
+		dumps.push_back(prefix + "." + std::to_string(rf.index));
+		captures.push_back(rf);
+	}
+	return -1;
+}
+
 int cli::run()
 {
 	gpu_engine e(dumps, types, thresh, filter, dbg, devices, blocks, per_file);
+	if (replay_prefix)
+		e.set_replay(captures);
 	if (exec || mode)
 		e.set_handler(exec, batched, mode);
 	e.set_bits_replay(bits);
@@ -607,8 +711,12 @@ int main(int argc, char **argv)
 	setvbuf(stdout, NULL, _IOFBF, 1 << 16);
 	if (c.hexfile)
 		return replay_hex(c.types, c.dbg, c.hexfile, c.exec, c.batched);
+	if (c.replay_prefix && (r = c.load_capture()) >= 0)
+		return r;
 	if (c.dumps.empty()) {
-		fprintf(stderr, "tfrec_gpu: need -L <dumpfile> or -X <hexfile>\n");
+		if (c.replay_prefix)  // (a capture without a run: nothing triggered, nothing to decode)
+			return 0;
+		fprintf(stderr, "tfrec_gpu: need -L <dumpfile>, -R <prefix> or -X <hexfile>\n");
 		return 1;
 	}
 	if (c.thresh < 0) {
