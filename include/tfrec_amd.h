@@ -705,6 +705,15 @@ int tfrec_amd_fm_dev_probe(int device, int kind, const void *records, size_t n, 
  * the step as the reference associates it; form 1: the 3-multiply form the biquad passes and WHB stage 2 run (csrc/dsp_dev.h:
  * iir_step_t).  cutoff: iir2's argument, e.g. 0.5 / spb (tfa2.cpp:321), 2.0 / 64, 0.0025 / 64 (whb.cpp:610-611).  No context. */
 int tfrec_amd_iir_probe(int device, double cutoff, int form, const double *in, size_t n, double *out);
+/* Parity probe, like tfrec_amd_iir_probe: the output row of the fp64 biquad of (slot, stream) -- slot 1-3 the TFA_2 family
+ * (tfa2.cpp:362, the int16 values widened), slot 4 WHB stage 1 (whb.cpp:651-652) -- as the biquad passes (csrc/biquad.h) left it
+ * for the most recently drained submit, read from the table set that submit used, after a sync.  The row is window-relative:
+ * window j of the chain in that submit, opened at decimated sample og, owns the 32-sample slots (og >> 5) + j ..., and its slot i
+ * holds the outputs of samples og + 32 i ...; values outside the windows are unspecified.  *n_slots: the slots of a row; out
+ * takes 32 values per slot (cap_values >= 32 * *n_slots), or out = NULL with cap_values = 0 to ask for *n_slots alone.
+ * TFREC_AMD_E_INVAL, with nothing written: slot 0 (TFA_1 has no biquad), a slot outside the context's types, a context with
+ * TFREC_AMD_F_SERIAL_CHAINS (it keeps no such rows), no submit drained yet, cap_values too small. */
+int tfrec_amd_read_biquad_row(tfrec_amd_ctx *ctx, int slot, int stream, int32_t *out, size_t cap_values, uint32_t *n_slots);
 int tfrec_amd_get_timings(tfrec_amd_ctx *ctx, tfrec_amd_timings *out);
 /* Cumulative counters of the speculative stages (window-parallel pipeline only).  They only describe how the work
  * was done -- results do not depend on them. */
@@ -716,7 +725,7 @@ typedef struct {
 	uint64_t tfa2_resliced;      /* tfa2 windows sliced again because the last_bit_idx assumption did not hold */
 	uint64_t tfa1_recomputed;    /* 64-sample steps of long TFA_1 windows whose pre-computed peak detector piece did not
 				        start from the true value and were recomputed */
-	uint64_t biquad_repair_slots; /* 32-sample slots the first repair pass ran (a segment has up to 256: csrc/tfrec_dev.h kSegSlots) */
+	uint64_t biquad_repair_slots; /* 32-sample slots the first repair pass ran (a segment has up to kSegSlots of them, csrc/tfrec_dev.h: 256 in the product build) */
 	uint64_t whb_respeculated;   /* (stream, submit) pairs whose lane-parallel WHB decision levels did not reproduce the exact
 				        recurrence's decisions and were demodulated again by the exact kernel */
 	uint64_t tfa1_scalar_groups; /* groups of 64 steps (4096 samples) of long TFA_1 windows that the lane-per-step cooperative slicer

@@ -1,8 +1,11 @@
 """In-tree build of the native libraries (hipcc cross-compiles gfx950 without a GPU).
 
-Two builds of the same HIP sources (tfrec_amd/csrc/knobs.h):
+Three builds of the same HIP sources (tfrec_amd/csrc/knobs.h):
   libtfrec_amd.so      the product: no environment knobs, no test hooks in the binary;
-  libtfrec_amd_exp.so  -DTFREC_AMD_EXPERIMENTS: the knobs read from the environment (tests that drive a hook, A/B sessions).
+  libtfrec_amd_exp.so  -DTFREC_AMD_EXPERIMENTS: the knobs read from the environment (tests that drive a hook, A/B sessions);
+  libtfrec_amd_seg.so  the experiments build with -DTFREC_AMD_SEG_SLOTS=16: biquad segments of 16 slots instead of 256, so that
+                       every rung of the biquad passes' repair ladder (csrc/biquad.h) runs on ordinary input
+                       (tests/test_biquad_ladder_gpu.py).
 
 Staleness is decided by CONTENT, not by time stamps: every object and library has a side file `<target>.stamp` holding the
 SHA-256 of everything that went into it (sources, headers, flags, this file).  A tree that arrives with prebuilt objects of
@@ -21,6 +24,7 @@ ROOT = os.path.dirname(_PKG)
 CSRC = os.path.join(_PKG, "csrc")
 LIB_SO = os.path.join(_PKG, "libtfrec_amd.so")
 LIB_EXP_SO = os.path.join(_PKG, "libtfrec_amd_exp.so")
+LIB_SEG_SO = os.path.join(_PKG, "libtfrec_amd_seg.so")
 HOST_SO = os.path.join(_PKG, "libtfrec_host.so")
 
 HIP_SOURCES = ["frontend.hip", "chains.hip", "chains2.hip", "capi.hip"]
@@ -31,6 +35,10 @@ HIP_HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
                "-Wall", "-Wno-unused-function"]
 EXP_FLAGS = ["-DTFREC_AMD_EXPERIMENTS"]
+SEG_SLOTS = 16  # the short-segment variant's kSegSlots (csrc/tfrec_dev.h derives the lower bound)
+SEG_FLAGS = EXP_FLAGS + ["-DTFREC_AMD_SEG_SLOTS=%d" % SEG_SLOTS]
+# variant -> (library, object suffix, extra flags)
+VARIANTS = {"product": (LIB_SO, "", []), "experiments": (LIB_EXP_SO, ".exp", EXP_FLAGS), "short_segments": (LIB_SEG_SO, ".seg", SEG_FLAGS)}
 
 _actions: list[str] = []
 
@@ -109,20 +117,23 @@ def _build_variant(lib_so: str, suffix: str, extra_flags: list[str], force: bool
     return lib_so
 
 
-def build_device_lib(force: bool = False, verbose: bool = False, experiments: bool = False) -> str:
-    """Compile every HIP source for gfx950 into tfrec_amd/libtfrec_amd.so (or, experiments=True, libtfrec_amd_exp.so)."""
-    if experiments:
-        return _build_variant(LIB_EXP_SO, ".exp", EXP_FLAGS, force, verbose)
-    return _build_variant(LIB_SO, "", [], force, verbose)
+def variant_name(experiments: bool = False, short_segments: bool = False) -> str:
+    return "short_segments" if short_segments else ("experiments" if experiments else "product")
+
+
+def build_device_lib(force: bool = False, verbose: bool = False, experiments: bool = False, short_segments: bool = False) -> str:
+    """Compile every HIP source for gfx950 into tfrec_amd/libtfrec_amd.so (or, experiments=True, libtfrec_amd_exp.so;
+    short_segments=True, libtfrec_amd_seg.so)."""
+    lib_so, suffix, flags = VARIANTS[variant_name(experiments, short_segments)]
+    return _build_variant(lib_so, suffix, flags, force, verbose)
 
 
 def build_all(force: bool = False, verbose: bool = False) -> None:
     del _actions[:]
-    with ThreadPoolExecutor(max_workers=2) as ex:  # the two variants beside each other (hipcc is one thread per file)
-        a = ex.submit(build_device_lib, force, verbose, False)
-        b = ex.submit(build_device_lib, force, verbose, True)
-        a.result()
-        b.result()
+    with ThreadPoolExecutor(max_workers=3) as ex:  # the three variants beside each other (hipcc is one thread per file)
+        jobs = [ex.submit(build_device_lib, force, verbose, e, g) for e, g in ((False, False), (True, False), (True, True))]
+        for j in jobs:
+            j.result()
     host = os.path.join(_PKG, "host", "Makefile")
     if os.path.exists(host):
         subprocess.check_call(["make", "-s", "-C", os.path.dirname(host)] + (["-B"] if force else []))

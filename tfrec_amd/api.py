@@ -108,29 +108,30 @@ EXPORTS = (
     "tfrec_amd_read_levels", "tfrec_amd_enable_capture", "tfrec_amd_read_captures", "tfrec_amd_enable_spectrum",
     "tfrec_amd_read_spectrum", "tfrec_amd_enable_occupancy", "tfrec_amd_read_occupancy", "tfrec_amd_create_dc", "tfrec_amd_get_dc",
     "tfrec_amd_read_dc", "tfrec_amd_reset_dc_rows", "tfrec_amd_create_decimated", "tfrec_amd_enable_capture_pre",
-    "tfrec_amd_read_capture_pre", "tfrec_amd_enable_runs_input", "tfrec_amd_submit_runs",
+    "tfrec_amd_read_capture_pre", "tfrec_amd_enable_runs_input", "tfrec_amd_submit_runs", "tfrec_amd_read_biquad_row",
 )
 
 _libs = {}
 
 
-def library_path(experiments: bool = False) -> str:
-    return _build.LIB_EXP_SO if experiments else _build.LIB_SO
+def library_path(experiments: bool = False, short_segments: bool = False) -> str:
+    return _build.VARIANTS[_build.variant_name(experiments, short_segments)][0]
 
 
-def load_library(build: bool = True, experiments: bool = False):
+def load_library(build: bool = True, experiments: bool = False, short_segments: bool = False):
     """Load libtfrec_amd.so -- or, experiments=True, libtfrec_amd_exp.so: the same sources with the environment knobs and
-    test hooks compiled in (csrc/knobs.h) -- building it in-tree first when hipcc is available.  Raises if absent."""
-    key = bool(experiments)
+    test hooks compiled in (csrc/knobs.h); or, short_segments=True, libtfrec_amd_seg.so: that build with biquad segments of
+    _build.SEG_SLOTS slots -- building it in-tree first when hipcc is available.  Raises if absent."""
+    key = _build.variant_name(experiments, short_segments)
     if key in _libs:
         return _libs[key]
     if build:
         try:
-            _build.build_device_lib(experiments=key)
+            _build.build_device_lib(experiments=bool(experiments), short_segments=bool(short_segments))
         except (OSError, FileNotFoundError):
             pass  # no hipcc on this box: use the prebuilt library that travelled with the tree
-    lib_so = library_path(key)
-    if key:
+    lib_so = library_path(experiments, short_segments)
+    if key == "experiments":
         lib_so = os.environ.get("TFREC_AMD_LIB", lib_so)  # (A/B sessions: an alternative experiments build)
     if not os.path.exists(lib_so):
         raise RuntimeError("HIP extension %s is missing: run __graft_entry__.build()" % lib_so)
@@ -157,6 +158,7 @@ def load_library(build: bool = True, experiments: bool = False):
     L.tfrec_amd_rssi_db.restype = C.c_int
     L.tfrec_amd_read_decimated.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
     L.tfrec_amd_read_stage0.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+    L.tfrec_amd_read_biquad_row.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
     L.tfrec_amd_atan_uncertain.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.tfrec_amd_get_timings.argtypes = [C.c_void_p, C.POINTER(Timings)]
     L.tfrec_amd_read_thresh.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
@@ -243,10 +245,11 @@ class Receiver:
                  device: int = 0, max_blocks: int = 48, max_events: int | None = None, all_flushes: bool = False,
                  timing: bool = False, serial_chains: bool = False, input_10x: bool = False, bits: bool = False,
                  experiments: bool = False, input_rate=None, input_format=None, levels: bool = False, dc_windows=None,
-                 dc_rows=None, decimated: bool = False):
+                 dc_rows=None, decimated: bool = False, short_segments: bool = False):
         # experiments=True: the build that reads the TFREC_AMD_* knobs / test hooks from the environment (csrc/knobs.h);
-        # the default is the product library, which has none
-        self.L = load_library(experiments=experiments)
+        # the default is the product library, which has none.  short_segments=True: the experiments build with biquad
+        # segments of _build.SEG_SLOTS slots (libtfrec_amd_seg.so)
+        self.L = load_library(experiments=experiments, short_segments=short_segments)
         if max_events is None:
             max_events = max(4096, n_streams * max_blocks * 4 * (8 if all_flushes else 2))
         flags = ((F_ALL_FLUSHES if all_flushes else 0) | (F_TIMING if timing else 0)
@@ -681,6 +684,16 @@ class Receiver:
     def decimated(self, stream: int, n_pairs: int) -> np.ndarray:
         out = np.empty(2 * n_pairs, dtype=np.int16)
         _check(self.L, self.L.tfrec_amd_read_decimated(self.h, stream, out.ctypes.data, n_pairs))
+        return out
+
+    def biquad_row(self, slot: int, stream: int) -> np.ndarray:
+        """Parity probe: the window-relative biquad output row of (slot, stream) in the most recently drained submit, int32 --
+        32 values per slot of the row, the TFA_2 family's int16 outputs widened (tfrec_amd_read_biquad_row).  Window j of the
+        chain, opened at sample og, owns the slots (og >> 5) + j ...; its slot i holds the outputs of samples og + 32 i ..."""
+        n = C.c_uint32(0)
+        _check(self.L, self.L.tfrec_amd_read_biquad_row(self.h, slot, stream, None, 0, C.byref(n)))
+        out = np.empty(32 * n.value, dtype=np.int32)
+        _check(self.L, self.L.tfrec_amd_read_biquad_row(self.h, slot, stream, out.ctypes.data, out.size, C.byref(n)))
         return out
 
     def atan_uncertain(self) -> int:

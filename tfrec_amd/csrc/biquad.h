@@ -58,7 +58,7 @@ struct ChunkIter {
 // contracting (pole radius 0.87-0.95): a run started from the WRONG state becomes bit-identical to the true
 // trajectory after a few hundred samples, and once the full state (yn, yn1 + the two last inputs) matches
 // bit for bit it matches forever.  The in-window slots of a chain, numbered consecutively across windows, are
-// cut into segments of kSegSlots slots (>= 3700 samples), and
+// cut into segments of kSegSlots slots (tfrec_dev.h: 256 in the product build, 16 in the short-segment one), and
 //   K3a spec_biquad_kernel   lane per SEGMENT (work queue): runs the segment from a zero state (every segment, the
 //                            chain's first too: the pass needs nothing of the submit before and runs on a stream of
 //                            its own, PipeCtl::ks), stores the truncated outputs the slicers consume, a (yn, yn1)
@@ -286,7 +286,7 @@ __device__ __forceinline__ BiquadEnd end_of(const Biquad &f)
 // A flat loop: per iteration every busy lane filters ONE slot of its segment, and all 64 lanes store the wave's slots
 // together (k3_store_t).  A lane that finishes its segment takes the next one from the work queue by itself -- the lanes
 // of a wave do not wait for each other's segments.  (They did: a repair run takes ~20 slots for most segments but the
-// whole segment, 116 slots, for the 1 % whose two trajectories never become bit-identical; with one such lane in
+// whole segment, kSegSlots slots, for the 1 % whose two trajectories never become bit-identical; with one such lane in
 // every second wave the repair passes took as long as the speculative pass.)  Taking a segment costs a few dependent
 // table reads during which the wave stalls, so idle lanes wait until a quarter of the wave is idle (or nothing runs).
 // Two slot buffers per lane: slot k (A) is filtered while slot k+1 (B) is in flight; then B moves to A and slot k+2 is

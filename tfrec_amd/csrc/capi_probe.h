@@ -132,6 +132,38 @@ int tfrec_amd_read_decimated(tfrec_amd_ctx *c, int stream, int16_t *out, size_t 
 	return TFREC_AMD_OK;
 }
 
+int tfrec_amd_read_biquad_row(tfrec_amd_ctx *c, int slot, int stream, int32_t *out, size_t cap_values, uint32_t *n_slots)
+{
+	if (!c || !n_slots || stream < 0 || stream >= c->cfg.n_streams || (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) ||
+	    c->last_drained < 0 || (!out && cap_values))
+		return TFREC_AMD_E_INVAL;
+	int a = -1;
+	for (int k = 0; k < c->launch.n_active; k++)
+		if (c->launch.slot[k] == slot && c->launch.params[k].kind > 0)  // (TFA_1 has no biquad stage)
+			a = k;
+	if (a < 0)
+		return TFREC_AMD_E_INVAL;
+	const int set = c->last_drained;
+	const WinTables &T = c->win[set];
+	const size_t n = (size_t)T.slots * 32;
+	if (out && cap_values < n)
+		return TFREC_AMD_E_INVAL;
+	*n_slots = (uint32_t)T.slots;
+	if (!out)
+		return TFREC_AMD_OK;
+	TRY(tfrec_amd_sync(c));
+	if (c->launch.params[a].kind == 2) {
+		HIPCHK(hipMemcpy(out, c->d_dev32[set] + (size_t)stream * n, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+	} else {
+		std::vector<int16_t> row(n);
+		const size_t ch = (size_t)a * c->cfg.n_streams + stream - (size_t)T.ld_c0;
+		HIPCHK(hipMemcpy(row.data(), c->d_ld16[set] + ch * n, n * sizeof(int16_t), hipMemcpyDeviceToHost));
+		for (size_t k = 0; k < n; k++)
+			out[k] = row[k];
+	}
+	return TFREC_AMD_OK;
+}
+
 int tfrec_amd_atan_uncertain(tfrec_amd_ctx *c, uint64_t *n)
 {
 	if (!c || !n)

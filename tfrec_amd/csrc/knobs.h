@@ -1,12 +1,15 @@
 // Test and instrumentation knobs of the library.
 //
-// TWO builds of the same sources (tfrec_amd/_build.py):
+// THREE builds of the same sources (tfrec_amd/_build.py):
 //   libtfrec_amd.so      the product -- what bench.py, the adapter and the parity tests load.  Built WITHOUT
 //                        TFREC_AMD_EXPERIMENTS: every knob below is its default as a compile-time constant, the test hooks
 //                        fold away, and neither a getenv call nor a knob's name is in the binary
 //                        (`strings libtfrec_amd.so | grep -c TFREC_AMD_DEEP` = 0; tests/test_cabi_cpu.py checks it).
 //   libtfrec_amd_exp.so  -DTFREC_AMD_EXPERIMENTS: the knobs are read from the environment.  Loaded only by the tests that
 //                        drive a hook (tests/: api.Receiver(..., experiments=True)) and by sessions under profiles/.
+//   libtfrec_amd_seg.so  the experiments build with -DTFREC_AMD_SEG_SLOTS=16 (tfrec_dev.h: kSegSlots and its lower bound): biquad
+//                        segments short enough that the second repair pass and the serial repair of biquad.h run on ordinary
+//                        input.  Loaded only by tests/test_biquad_ladder_gpu.py (api.Receiver(..., short_segments=True)).
 // What the knobs are still for (every other A/B variant of rounds 1-6 is retired: profiles/NOTES.md, "retired knobs"):
 //   test hooks        WHB_FORCE_FAIL, WHB_TEST_PERTURB (WHB check failures and redos), FM_FLAG_EPS (the discriminator's exact
 //                     slow path), COPY_GUESS_MIN (the drain's fetch-the-rest path);

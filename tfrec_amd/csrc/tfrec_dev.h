@@ -441,9 +441,23 @@ constexpr int kDeferQueue = kNQueues;
 #ifndef TFREC_AMD_SEG_SLOTS
 #define TFREC_AMD_SEG_SLOTS 256
 #endif
-constexpr int kSegSlots = TFREC_AMD_SEG_SLOTS;  // biquad segments: 256 in-window slots (>= 7400 samples: windows are >= 11 slots long).  Round 5
-                                                // (profiles/r05_ab_segments.txt): 128 -> 256 with the same number of waves = a quarter fewer repair
-                                                // slots, the batch 2.5 % shorter; 512: no better (the passes stretch), 1024: 17 % worse
+constexpr int kSegSlots = TFREC_AMD_SEG_SLOTS;  // biquad segments: 256 in-window slots in the product build (>= 7400 samples: windows are >= 11 slots
+                                                // long).  Round 5 (profiles/r05_ab_segments.txt): 128 -> 256 with the same number of waves = a quarter fewer
+                                                // repair slots, the batch 2.5 % shorter; 512: no better (the passes stretch), 1024: 17 % worse.  The
+                                                // short-segment build (tfrec_amd/_build.py: libtfrec_amd_seg.so) uses 16, the smallest power of two below.
+// The lower bound.  windows_kernel pushes one work item per segment into the item area of the segment's queue, which holds
+// n_active * n_streams * cap items with cap = m / 356 + 2 (capi_create.h; m = the decimated samples of the largest submit, a
+// multiple of kBlockDec).  The worst case is ONE biquad chain registered (n_active = 1, e.g. types 0x04 or 0x20): its queue then
+// has cap items per chain.  A chain's windows are disjoint, so their slots (ceil(n / 32) each) are at most m / 32 + count
+// <= m / 32 + cap, in at most (m / 32 + cap) / kSegSlots + 1 segments.  With S = kSegSlots that fits the area when
+//     m / (32 S) + cap / S + 1 <= cap,   i.e.   (S - 1) cap >= m / 32 + S,
+// and since cap > m / 356 + 1 it is enough that (S - 1) (m / 356 + 1) >= m / 32 + S, i.e. m (32 (S - 1) - 356) >= 32 * 356, for
+// the smallest m, one block: S >= 13 (8192 * 28 >= 11392; at S = 12 the factor is negative for every m), so 16 holds -- one block:
+// cap 25, at most (256 + 25) / 16 + 1 = 18 segments; six blocks: cap 140, at most (1536 + 140) / 16 + 1 = 105 -- and 8 does not:
+// an always-triggered stream has m / 256 = 32 segments per block against a cap of 25.  More chains of a kind never need more per
+// chain, and n_active grows with them.  This is the bound of the item area only; T.segcap (capi_create.h) scales with kSegSlots.
+static_assert((long long)kBlockDec * (32 * (kSegSlots - 1) - 356) >= 32 * 356,
+	      "kSegSlots: a single biquad chain's segments would overrun its work queue's item area (cap = m / 356 + 2 items)");
 constexpr int kSegConverged = 0x40000000, kSegRan = 0x20000000;
 constexpr int kLongWindow = 1024;  // samples; longer windows go to the wave-cooperative slicers (half of it below 1024 chains).
                                    // Until round 5 the cooperative slicers were scalar walks (51 scalar instructions per
