@@ -267,7 +267,10 @@ int tfrec_amd_get_stream_tune_wide(tfrec_amd_ctx *ctx, int stream, int32_t *tune
  * 4/3, 2.4 MS/s 25/16, 1.92 MS/s 5/4 -- which a resampling stage on the GPU brings to the 1.536 MS/s int16 (I, Q) stream that
  * enters downconvert::process_iq; the rest of the path is unchanged.  No reference counterpart: like the 10:1 stage and the
  * tuners the stage is defined here, in the reference's FIR style, and pinned by a CPU restatement (tfrec_amd/resample.py).
- *   Rates:   gcd(P, Q) = 1, 1 <= Q <= 64, 1 < P/Q < 10.  r = P/Q is the number of input samples per output sample.
+ *   Rates:   gcd(P, Q) = 1, 1 < P/Q < 10, and Q <= 64 or Q divides 1536.  r = P/Q is the number of input samples per output sample.
+ *            "Q divides 1536" is "fs_in is a whole number of kHz": every whole-kHz rate with 1536000 < fs_in < 15360000 is accepted
+ *            -- 2.0 MS/s is 125/96, 2.5 MS/s 625/384, 5 MS/s 625/192, 10 MS/s 625/96, 12.5 MS/s 3125/384.  Other denominators
+ *            above 64 (97/80, 1025/1024), rates up to 1.536 MS/s and from 15.36 MS/s on are refused.
  *   Filter:  T = 2 * ceil(3 r) taps per phase (even, <= 60; 8 at 2.048 MS/s, 10 at 2.4 MS/s).  For output sample m, counted since
  *            the stream's start or last restart:  a = m P,  i0 = floor(a / Q),  phi = a mod Q   (exact 64-bit integers)
  *   Output:  y0[m] = int16( sum_{n<T} ( x[i0 - (T-1) + n] * h[phi][n] ) >> 16 )   per rail, int32 arithmetic, arithmetic shifts,
@@ -280,10 +283,13 @@ int tfrec_amd_get_stream_tune_wide(tfrec_amd_ctx *ctx, int stream, int32_t *tune
  *   Refused: a rate where any v lies within 1e-9 of a rounding tie (the table must not depend on the host's libm), or where
  *            max_phi sum_n |h[phi][n]| * 8192 >> 16 >= 32768 (so the int16 store never wraps for u8 input): TFREC_AMD_E_INVAL.
  *   Submits: n_blocks blocks (TFREC_AMD_BLOCK_DEC decimated samples each, as always) consume exactly
- *            n_in = n_blocks * 32768 * P / Q complex input samples per stream, n_in * 2 bytes per input row; n_blocks must make
- *            that a whole number -- any value when Q is a power of two, otherwise a multiple of Q's odd part --, or the submit
- *            returns TFREC_AMD_E_INVAL and nothing is queued.  Every submit therefore begins at phase 0 on its own first input
- *            sample, and results do not depend on how a stream is cut into submits.
+ *            n_in = n_blocks * 32768 * P / Q complex input samples per stream, n_in * 2 bytes per input row; n_blocks must be a
+ *            multiple of unit(Q) = Q / gcd(Q, 64) -- the odd part of a Q <= 64, so any value when that Q is a power of two; 3, 2,
+ *            3, 4, 6, 8, 12, 24 at Q = 96, 128, 192, 256, 384, 512, 768, 1536 --, or the submit returns TFREC_AMD_E_INVAL and
+ *            nothing is queued.  Then n_in = k * P * 512 * (64 / gcd(Q, 64)) for a whole k: a whole number and a multiple of 512.
+ *            (The odd part alone would not do above 64: one block of 129/128 is 33024 samples, 64.5 times 512.)  Every submit
+ *            therefore begins at phase 0 on its own first input sample, and results do not depend on how a stream is cut into
+ *            submits.  A context whose max_blocks is below unit(Q) can be made and takes no submit.
  * cfg->flags must not contain TFREC_AMD_F_INPUT_10X (TFREC_AMD_E_INVAL).  On such a context tfrec_amd_submit_device / _host take
  * n_in * 2 bytes per row (submit_host stages exactly that, rows 0 .. R-1), tfrec_amd_read_stage0 returns y0, tfrec_amd_get_memory
  * counts the stage's buffers, tfrec_amd_tune_streams_wide returns TFREC_AMD_E_INVAL (the tune ahead of this stage is
@@ -295,19 +301,20 @@ int tfrec_amd_create_rate(const tfrec_amd_config *cfg, int32_t rate_p, int32_t r
  * tfrec_amd_get_input_rate reports), AHEAD of the resampling stage, so that a receiver can sit anywhere in a recording made at
  * that rate -- not only within the +-768 kHz that tfrec_amd_tune_streams, which acts behind the stage, can reach.  It is
  * tfrec_amd_tune_streams' mixer at the input rate, on x = (u8 - 128) << 6 (same table C, S and the same rounding):
- *     inc_in = floor((tune_hz * 2^33 * Q + 1536000 * P) / (2 * 1536000 * P)) mod 2^32          (exact 64-bit integers, floor division)
+ *     inc_in = floor((tune_hz * 2^33 * Q + 1536000 * P) / (2 * 1536000 * P)) mod 2^32          (exact integers, floor division)
  *     p      = (n * inc_in) mod 2^32,  k = p >> 20      (n: the INPUT sample's index since the stream's start or last restart)
  *     I'     = sat16((I * C[k] + Q * S[k] + 2^14) >> 15),  Q' = sat16((Q * C[k] - I * S[k] + 2^14) >> 15)
  *     y0[m]  = int16( sum_{n<T} ( x'[i0 - (T-1) + n] * h[phi][n] ) >> 16 )                  (the resampling stage, unchanged)
- * Limit: 2 * |tune_hz| * Q < 1536000 * P, that is |tune_hz| < fs_in / 2, tested in integers (the numerator of inc_in stays below
- * 2^63 for every permitted rate).  With P/Q = 10/1 the formula is inc10, with 1/1 tfrec_amd_tune_streams' inc: one definition
+ * Limit: 2 * |tune_hz| * Q < 1536000 * P, that is |tune_hz| < fs_in / 2, tested in integers (the numerator of inc_in leaves 63
+ * bits once |tune_hz| * Q >= 2^30 -- from 699051 Hz on at Q = 1536 -- and is computed in 128-bit integers).  With P/Q = 10/1 the formula is inc10, with 1/1 tfrec_amd_tune_streams' inc: one definition
  * for every rate.  tune_hz = 0 is no mixing: bit for bit the stage as it is.  The history before a start or restart is silence; a
  * history sample from the previous submit is rotated with its own (earlier) n.  The phase of a submit's first input sample is
  * (n0 * inc_in) mod 2^32, n0 = 4 * (decimated samples since the stream's origin) * P / Q, whole because every submit is.
  * tfrec_amd_tune_streams composes: it acts on y0.  tfrec_amd_read_stage0 returns the shifted, resampled y0.  Pinned by
  * tfrec_amd/tune.py (inc_in, mix_in_s16) and tfrec_amd/resample.py (resample_x16).
  *   No wrap: the mixer's output of u8 input is at most 11585 per rail, and the largest max_phi sum_n |h| of any accepted rate is
- *   108112 (at 65/64), so |y0| <= 108112 * 11585 >> 16 = 19111.  A guard stays: on a rate where
+ *   108260 (at 769/768 and 1537/1536; 108112 at 65/64 is the largest with Q <= 64), so |y0| <= 108260 * 11585 >> 16 = 19137.  A
+ *   guard stays: on a rate where
  *   max_phi sum_n |h[phi][n]| * 11585 >> 16 >= 32768 the call returns TFREC_AMD_E_INVAL.
  *   - An input tune is a restart, with the semantics, the "last wins" and the composition rules of tfrec_amd_map_streams /
  *     tfrec_amd_tune_streams_wide: reset + configure + tune + map + input tune before one submit are ONE restart; later resets
@@ -322,7 +329,7 @@ int tfrec_amd_get_stream_tune_input(tfrec_amd_ctx *ctx, int stream, int32_t *tun
 /* The context's input rate as P/Q of 1.536 MS/s: 1/1 for tfrec_amd_create, 10/1 with TFREC_AMD_F_INPUT_10X. */
 int tfrec_amd_get_input_rate(tfrec_amd_ctx *ctx, int32_t *p, int32_t *q);
 /* Bytes one input row of a submit of n_blocks blocks holds (every kind of context); TFREC_AMD_E_INVAL when n_blocks < 1 or
- * breaks the divisibility rule above. */
+ * is no multiple of unit(Q) (Submits, above). */
 int tfrec_amd_input_bytes(tfrec_amd_ctx *ctx, int n_blocks, size_t *bytes_per_stream);
 /* The tap table of a rate: taps[phi * T + n], Q * T values (cap: the room in `taps`, in values), T to *n_taps_per_phase.  taps may
  * be NULL with cap 0 (only T, or only the verdict, is wanted).  Needs no context and no GPU.  TFREC_AMD_E_INVAL: a rate outside
@@ -350,7 +357,7 @@ int tfrec_amd_resample_taps(int32_t rate_p, int32_t rate_q, int32_t *taps, int c
  *     1/1 nor accepted by tfrec_amd_create_rate.
  *   - Rows: tfrec_amd_input_bytes returns n_in * bytes per complex sample, and tfrec_amd_submit_device / _host take that many bytes
  *     per row (submit_host's staging buffer grows with it).  The 16-byte alignment rules for base and stride are unchanged -- n_in
- *     is a multiple of 8 for every permitted submit, so every row size is a 16-byte multiple --, and so is the block-count rule.
+ *     is a multiple of 512 for every permitted submit, so every row size is a 16-byte multiple --, and so is the block-count rule.
  *   - Everything that works on a rate context works: reset, configure, tfrec_amd_tune_streams, tfrec_amd_map_streams,
  *     tfrec_amd_tune_streams_input, both layouts, _SERIAL_CHAINS, _BITS, _ALL_FLUSHES, _TIMING; tfrec_amd_read_stage0 returns y0 (at
  *     1/1: x); tfrec_amd_get_memory counts what the context holds.  At 1/1 the input-rate tune returns TFREC_AMD_E_INVAL, as on a
@@ -366,8 +373,8 @@ int tfrec_amd_get_input_format(tfrec_amd_ctx *ctx, int32_t *format);
  * many streams read it.  It acts on x, the int16 value every format maps a stored component to (tfrec_amd_create_format), at the
  * context's input rate, ahead of the input-rate tune, the resampling stage, tfrec_amd_tune_streams and process_iq.  Exact integers:
  *   Windows.  L = 512 complex input samples; window w of a row covers its samples [512 w, 512 (w + 1)), counted from the row's first
- *     submit or its last DC reset.  Every permitted submit holds n_in = n_blocks * 32768 * P / Q samples, a multiple of 512: with
- *     Q = 2^a * o, o odd and 2^a <= 64, n_blocks is a multiple of o and 32768 / 2^a >= 512 is one of 512.  So no window straddles a
+ *     submit or its last DC reset.  Every permitted submit holds n_in = n_blocks * 32768 * P / Q samples, a multiple of 512: n_blocks
+ *     is a multiple of Q / gcd(Q, 64), so n_in = k * P * 512 * (64 / gcd(Q, 64)) (tfrec_amd_create_rate: Submits).  So no window straddles a
  *     submit, and results do not depend on how a row is cut into submits.
  *   Sums.  S_I[w], S_Q[w] = the window's sums of x_I and x_Q (|S| <= 2^22).
  *   Estimate.  K = avg_windows, 1 <= K <= 4096; lo = max(0, w - K + 1), c = w - lo + 1, A = S[lo] + ... + S[w] per rail (window w's

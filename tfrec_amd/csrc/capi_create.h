@@ -68,11 +68,11 @@ static const int16_t kWideTaps[20] = { 546, 451, -317, -1844, -3198, -2817, 494,
 // With dn = (n - t/2 + 1) q - phi the tap offset is d = dn / q and d / r = dn / p:
 //   g = sinc(dn / p) (0.54 + 0.46 cos(2 pi dn / (q t))),  v = g 65536 / sum g,  h = round(v), and the residual 65536 - sum h goes to
 //   the tap with the largest v (the lowest n among equals).
-// false: the rate is outside 1 < p/q < 10, q <= 64, gcd = 1, or refused -- a v within 1e-9 of a rounding tie (the table must not
-// depend on the host's libm), or max_phi sum |h| * 8192 >> 16 >= 32768 (the int16 store could wrap).
+// false: the rate is outside 1 < p/q < 10, q <= 64 or q | 1536, gcd = 1, or refused -- a v within 1e-9 of a rounding tie (the table
+// must not depend on the host's libm), or max_phi sum |h| * 8192 >> 16 >= 32768 (the int16 store could wrap).
 static bool resample_table(int32_t p, int32_t q, std::vector<int32_t> &h, int &t)
 {
-	if (p <= 0 || q <= 0 || q > kRateQMax || p <= q || (long long)p >= 10LL * q)
+	if (p <= 0 || q <= 0 || (q > kRsQMax && kRsQDiv % q != 0) || p <= q || (long long)p >= 10LL * q)
 		return false;
 	for (int a = p, b = q; b;) {  // gcd
 		const int r = a % b;
@@ -81,8 +81,8 @@ static bool resample_table(int32_t p, int32_t q, std::vector<int32_t> &h, int &t
 		if (!b && a != 1)
 			return false;
 	}
-	t = 2 * ((3 * p + q - 1) / q);
-	h.assign((size_t)q * t, 0);
+	t = 2 * ((3 * p + q - 1) / q);  // (p < 10 * 1536)
+	h.assign((size_t)q * (size_t)t, 0);
 	std::vector<double> v((size_t)t);
 	for (int phi = 0; phi < q; phi++) {
 		double total = 0.0;
@@ -287,8 +287,17 @@ static int make_front_buffers(tfrec_amd_ctx *c)
 			c->rate_abs = std::max(c->rate_abs, a);
 		}
 		std::vector<float> hf(h.size());
-		for (size_t i = 0; i < h.size(); i++)
-			hf[i] = (float)h[i] * (1.0f / 1024.0f);  // exact: |h| < 2^17
+		if (rs_streamed(c->in_q, t)) {  // resample_stream_kernel's table: [t][q], h / 65536, column j the phase (j P) mod Q
+			const size_t q = (size_t)c->in_q;
+			for (size_t j = 0; j < q; j++) {
+				const size_t phi = j * (size_t)c->in_p % q;
+				for (size_t k = 0; k < (size_t)t; k++)
+					hf[k * q + j] = (float)h[phi * t + k] * (1.0f / 65536.0f);  // exact: |h| < 2^17
+			}
+		} else {
+			for (size_t i = 0; i < h.size(); i++)
+				hf[i] = (float)h[i] * (1.0f / 1024.0f);  // exact: |h| < 2^17
+		}
 		TRY(own_device(c, c->d_rtaps, hf.size() * sizeof(float)));
 		HIPCHK(hipMemcpy(c->d_rtaps, hf.data(), hf.size() * sizeof(float), hipMemcpyHostToDevice));
 	}

@@ -3,7 +3,7 @@
 
 constexpr int kTuneLimit = 768000;  // |tune_hz| < half the 1.536 MS/s sample rate
 constexpr int kTuneWideLimit = 7680000;  // tfrec_amd_tune_streams_wide: half the 15.36 MS/s input rate
-constexpr int kRateQMax = 64;  // tfrec_amd_create_rate: the largest Q
+// tfrec_amd_create_rate's denominators are tfrec_dev.h's: Q <= kRsQMax or Q | kRsQDiv
 constexpr int k10xTail = 112;   // TFREC_AMD_F_INPUT_10X: the 10:1 stage's raw history per stream in bytes (decim10_kernel: kTail10)
 constexpr int kRateTail = 128;  // tfrec_amd_create_rate: the resampling stage's raw history per stream in bytes (resample.h: kRsTail)
 constexpr int kFmtTail = 256;   // tfrec_amd_create_format: the history per stream in bytes, 64 complex samples of x (formats.h: kFmtTailDw)
@@ -219,7 +219,7 @@ struct tfrec_amd_ctx {
 	bool in10x = false;  // TFREC_AMD_F_INPUT_10X
 	// The input rate is 1536000 in_p / in_q, resolved once (create_with): 1/1, 10/1 with TFREC_AMD_F_INPUT_10X, or the P / Q of
 	// tfrec_amd_create_rate, whose resampling stage writes d_in16 as the 10:1 stage does, from a tap table
-	// [in_q][rate_t] (h / 1024 as floats).
+	// [in_q][rate_t] (h / 1024 as floats) -- or, a table too large to stage (rs_streamed), resample_stream_kernel's (formats.h).
 	// rate_abs: max_phi sum_n |h[phi][n]| of that table, for the guard of tfrec_amd_tune_streams_input (6g), whose per-stream
 	// tune and increment per input sample live in wide_hz / wide_inc as the 10x context's wide tune does.
 	int32_t in_p = 1, in_q = 1, rate_t = 0;

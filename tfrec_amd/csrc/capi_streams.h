@@ -77,11 +77,12 @@ int tfrec_amd_get_stream_config(tfrec_amd_ctx *c, int stream, tfrec_amd_stream_c
 
 // The phase step per sample, in 2^-32 turns, of a tune of tune_hz at 1536000 P / Q samples per second:
 //   inc = floor((tune_hz * 2^33 * Q + 1536000 P) / (2 * 1536000 P)) mod 2^32
-// (DESIGN.md 6d at 1/1, 6e at 10/1, 6g at the input rate).  |tune_hz| < 7680000 and Q <= 64: the numerator stays below 2^63.
+// (DESIGN.md 6d at 1/1, 6e at 10/1, 6g at the input rate).  |tune_hz| < 7680000 and Q <= 1536: the numerator reaches 2^66.4, past
+// 64 bits from |tune_hz| Q >= 2^30 on, so it is computed in 128.
 static uint32_t phase_inc(int32_t tune_hz, long long p, long long q)
 {
-	const long long num = (long long)tune_hz * (1LL << 33) * q + 1536000LL * p, den = 2 * 1536000LL * p;
-	long long v = num / den;
+	const __int128 num = (__int128)tune_hz * ((__int128)1 << 33) * q + 1536000LL * p, den = 2 * 1536000LL * p;
+	__int128 v = num / den;
 	if (num % den != 0 && num < 0)
 		v--;  // (floor, not C's truncation)
 	return (uint32_t)(uint64_t)v;
@@ -210,7 +211,7 @@ int tfrec_amd_tune_streams_input(tfrec_amd_ctx *c, const int32_t *streams, const
 		return TFREC_AMD_E_INVAL;
 	}
 	const long long p = c->in_p, q = c->in_q;
-	if (((c->rate_abs * 11585) >> 16) >= 32768) {  // (no accepted rate comes near: 19111 at most)
+	if (((c->rate_abs * 11585) >> 16) >= 32768) {  // (no accepted rate comes near: 19137 at most)
 		snprintf(g_err, sizeof(g_err), "input rate %lld/%lld: the int16 store of a tuned stream could wrap", p, q);
 		return TFREC_AMD_E_INVAL;
 	}

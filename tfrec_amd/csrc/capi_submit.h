@@ -169,16 +169,18 @@ static int rows_in_use(const tfrec_amd_ctx *c)
 	return 1 + *std::max_element(c->row.begin(), c->row.end());
 }
 
-// Bytes of one input row of a submit of n_blocks blocks: n_blocks * 32768 * P / Q complex samples, which must be a whole
-// number (any n_blocks when Q is a power of two, otherwise a multiple of Q's odd part), of 2, 4 or 8 bytes each.
+// Bytes of one input row of a submit of n_blocks blocks: n_blocks * 32768 * P / Q complex samples of 2, 4 or 8 bytes each.
+// n_blocks must be a multiple of rs_unit(Q) = Q / gcd(Q, 64) -- the odd part of a Q <= 64, so any n_blocks when that Q is a power
+// of two --, which makes the samples a whole number and a multiple of 512.
 static int input_bytes(const tfrec_amd_ctx *c, int n_blocks, size_t *bytes)
 {
 	if (n_blocks < 1)
 		return TFREC_AMD_E_INVAL;
 	const long long p = c->in_p, q = c->in_q;
 	const long long num = (long long)n_blocks * (TFREC_AMD_BLOCK_BYTES / 2) * p;
-	if (num % q != 0) {
-		snprintf(g_err, sizeof(g_err), "%d blocks at the input rate %lld/%lld are not a whole number of input samples", n_blocks, p, q);
+	if (n_blocks % rs_unit(c->in_q) != 0) {
+		snprintf(g_err, sizeof(g_err), "%d blocks at the input rate %lld/%lld: a submit holds a multiple of %d blocks", n_blocks, p, q,
+			 rs_unit(c->in_q));
 		return TFREC_AMD_E_INVAL;
 	}
 	*bytes = (size_t)(num / q) * fmt_sample_bytes(c->fmt);

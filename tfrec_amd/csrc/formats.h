@@ -12,13 +12,21 @@
 //     stream of the launch comes out as an untuned launch makes it.  The taps run as fma(x', h / 65536, acc) on the 2^23 + 2^22
 //     accumulator in round-toward-minus-infinity mode: |h| < 2^17, so h / 65536 is exact in fp32; the FMA rounds once after the
 //     exact product and the accumulator is integer-valued, so each tap floors its own term; and every partial sum is at most
-//     max_phi sum |h| * 11585 >> 16 <= 19111 (108112 at 65/64 is the largest sum |h| of any accepted rate; the tune is refused
-//     where the bound reaches 32768), which keeps the accumulator in [2^23, 2^24) and the int16 store from wrapping.
+//     max_phi sum |h| * 11585 >> 16 <= 19137 (108260 at 769/768 and 1537/1536 is the largest sum |h| of any accepted rate, 108112
+//     at 65/64 the largest with Q <= 64; the tune is refused where the bound reaches 32768), which keeps the accumulator in
+//     [2^23, 2^24) and the int16 store from wrapping.
 //     The history is 64 complex samples per stream: of canonical x (256 bytes; x = 0 after a start or restart) for S8, S16 and
 //     F32, so one loop reads the history of those formats alike -- and the RAW 128 bytes (0x80 after a start or restart) for U8,
 //     read through the format's own loader.  A U8 context runs this kernel only while a stream is tuned and resample_kernel
 //     otherwise: both read and write that one history, so an untuned stream's survives the change in both directions.
 //     The cosine table is staged, and its 8 KB of LDS asked for, only by a launch with a tuned stream.
+//   * resample_stream_kernel<FMT> is the same stage for a rate whose table does not fit (rs_streamed: Q T > 3840, up to 360 KB at
+//     15359/1536): the image is staged by the same code (rs_stage_tile), the taps stay in global memory.  Its table is uploaded in
+//     VISIT ORDER and tap-major, as h / 65536: entry n Q + j holds tap n of the phase (j P) mod Q.  P is invertible mod Q, so that is
+//     a permutation of the phases, and output m of a stream uses column m mod Q.  Lane `tid` of a workgroup of N makes the outputs
+//     m0 + o N + tid, o < 8: for one tap and one o the lanes of a wave read 64 consecutive floats (wrapping once at Q at most)
+//     -- a coalesced 256-byte load that the XCD's L2 (4 MiB) serves -- and write 64 consecutive outputs.  The FMAs, their order
+//     and the accumulator are resample_fmt_kernel's, so the outputs are the same bits.
 //   * ingest_kernel<FMT> (base rate, 1/1; never U8, whose rows the front end reads as they are) converts each stream's row into
 //     the stage-0 buffer frontend_kernel<true, ...> reads.
 constexpr int kFmtTailDw = 64;  // history per stream: 64 complex samples of x, one dword each (T - 1 <= 59 needed)
@@ -69,27 +77,30 @@ __device__ __forceinline__ void fmt_load8(const uint8_t *__restrict__ src, uint3
 // `chan` (nullptr: stream s reads row s, nothing is tuned): {inc_in, phase of the submit's first input sample, input row, 0} per
 // stream; `tuned`: a stream of the launch has inc_in != 0 and the launch's LDS holds the table.  The history: kFmtTailDw dwords of
 // x per stream, or -- U8 -- kRsTail raw bytes.
+//
+// What a tile of tile_n = 8 blockDim.x outputs starts from: its first output m0, that output's phase, and the dword of the image
+// at which sample i0(m0) - (T-1) sits
+struct RsTile {
+	long m0;
+	unsigned phi0;
+	int sh;
+};
+
+// Stages the tile's int16 image into `raw` (8 rs_raw_chunks(p, q, t, tile_n) dwords, the cosine table behind it), writes the
+// stream's history for the next submit from the last tile, and ends in the workgroup's barrier.
 template <int FMT>
-__global__ __launch_bounds__(kRsThreads) void resample_fmt_kernel(const uint8_t *__restrict__ iq, size_t stride, long n_in, int p, int q,
-								  int t, const float *__restrict__ taps, const uint8_t *__restrict__ tail_in,
-								  uint8_t *__restrict__ tail_out, uint32_t *__restrict__ out, size_t out_stride,
-								  const uint4 *__restrict__ chan, int tuned)
+__device__ __forceinline__ RsTile rs_stage_tile(uint32_t *raw, const uint8_t *__restrict__ iq, size_t stride, long n_in, int p, int q, int t,
+						const uint8_t *__restrict__ tail_in, uint8_t *__restrict__ tail_out,
+						const uint4 *__restrict__ chan, int tuned)
 {
 	constexpr int kBps = fmt_sample_bytes(FMT);
 	constexpr bool kRawHist = FMT == kFmtU8;
 	constexpr int kHistBps = kRawHist ? kBps : 4;  // bytes per complex sample of the history
-	extern __shared__ __attribute__((aligned(16))) uint32_t fmt_lds[];
-	float *htab = reinterpret_cast<float *>(fmt_lds);
-	uint32_t *raw = fmt_lds + rs_taps_dw(q, t);
-	typedef float f32x2 __attribute__((ext_vector_type(2)));
 	const int s = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
 	const int nthreads = (int)blockDim.x, tile_n = kRsOut * (int)blockDim.x;
-	__builtin_amdgcn_s_setreg(1 | (0 << 6) | (1 << 11), 2);  // fp32 rounding toward -inf (see frontend_kernel, stage 1)
 	const long m0 = (long)tile * tile_n;
 	const uint8_t *src = iq + (size_t)(chan ? chan[s].z : (uint32_t)s) * stride;
 	const uint8_t *hist = tail_in + (size_t)s * (kFmtTailDw * kHistBps);
-	for (int i = tid; i < q * t; i += nthreads)
-		htab[i] = taps[i] * (1.0f / 64.0f);  // (h / 1024 -> h / 65536: exact)
 	// ---- the tile's first output: a = m0 P in 64 bits
 	const unsigned long long a0 = (unsigned long long)m0 * (unsigned)p;
 	const long i00 = (long)(a0 / (unsigned)q);
@@ -157,9 +168,30 @@ __global__ __launch_bounds__(kRsThreads) void resample_fmt_kernel(const uint8_t 
 		}
 	}
 	__syncthreads();
+	return RsTile{ m0, phi0, (int)(lo - b0) };
+}
+
+template <int FMT>
+__global__ __launch_bounds__(kRsThreads) void resample_fmt_kernel(const uint8_t *__restrict__ iq, size_t stride, long n_in, int p, int q,
+								  int t, const float *__restrict__ taps, const uint8_t *__restrict__ tail_in,
+								  uint8_t *__restrict__ tail_out, uint32_t *__restrict__ out, size_t out_stride,
+								  const uint4 *__restrict__ chan, int tuned)
+{
+	extern __shared__ __attribute__((aligned(16))) uint32_t fmt_lds[];
+	float *htab = reinterpret_cast<float *>(fmt_lds);
+	uint32_t *raw = fmt_lds + rs_taps_dw(q, t);
+	typedef float f32x2 __attribute__((ext_vector_type(2)));
+	const int s = blockIdx.y, tid = threadIdx.x;
+	const int nthreads = (int)blockDim.x;
+	__builtin_amdgcn_s_setreg(1 | (0 << 6) | (1 << 11), 2);  // fp32 rounding toward -inf (see frontend_kernel, stage 1)
+	for (int i = tid; i < q * t; i += nthreads)
+		htab[i] = taps[i] * (1.0f / 64.0f);  // (h / 1024 -> h / 65536: exact)
+	const RsTile g = rs_stage_tile<FMT>(raw, iq, stride, n_in, p, q, t, tail_in, tail_out, chan, tuned);
+	const long m0 = g.m0;
+	const unsigned phi0 = g.phi0;
 	// ---- the lane's outputs m0 + 8 tid + o: sample i0 - (T-1) + n is dword sh + (i0 - i00) + n of the image
-	const int sh = (int)(lo - b0);
-	const unsigned ar = phi0 + (unsigned)(kRsOut * tid) * (unsigned)p;  // a - i00 Q of the lane's first output, < 2^20
+	const int sh = g.sh;
+	const unsigned ar = phi0 + (unsigned)(kRsOut * tid) * (unsigned)p;  // a - i00 Q of the lane's first output (<= kRsArMax)
 	unsigned di = ar / (unsigned)q, phi = ar % (unsigned)q;
 	const unsigned pq = (unsigned)p / (unsigned)q, pr = (unsigned)p % (unsigned)q;
 	const float kMagic = 12582912.0f;  // 2^23 + 2^22
@@ -196,6 +228,49 @@ __global__ __launch_bounds__(kRsThreads) void resample_fmt_kernel(const uint8_t 
 #pragma unroll
 	for (int k = 0; k < kRsOut / 4; k++)
 		dst[k] = make_uint4(ow[4 * k], ow[4 * k + 1], ow[4 * k + 2], ow[4 * k + 3]);
+}
+
+// The stage for a rate whose table is streamed (rs_streamed(q, t)).  taps: [t][q] floats, h / 65536, column j the phase (j P) mod Q
+// (capi_create.h: make_inputs uploads it so).  Everything else as resample_fmt_kernel; the LDS holds the image and the cosine table only.
+template <int FMT>
+__global__ __launch_bounds__(kRsThreads) void resample_stream_kernel(const uint8_t *__restrict__ iq, size_t stride, long n_in, int p, int q,
+								     int t, const float *__restrict__ taps, const uint8_t *__restrict__ tail_in,
+								     uint8_t *__restrict__ tail_out, uint32_t *__restrict__ out, size_t out_stride,
+								     const uint4 *__restrict__ chan, int tuned)
+{
+	extern __shared__ __attribute__((aligned(16))) uint32_t rss_lds[];
+	typedef float f32x2 __attribute__((ext_vector_type(2)));
+	const int s = blockIdx.y, tid = threadIdx.x;
+	const int nthreads = (int)blockDim.x;
+	__builtin_amdgcn_s_setreg(1 | (0 << 6) | (1 << 11), 2);  // fp32 rounding toward -inf (see frontend_kernel, stage 1)
+	const RsTile g = rs_stage_tile<FMT>(rss_lds, iq, stride, n_in, p, q, t, tail_in, tail_out, chan, tuned);
+	// ---- the lane's outputs m = m0 + o nthreads + tid: a - i00 Q = phi0 + (m - m0) P (<= kRsArMax) gives i0 - i00, and m mod Q the column
+	const unsigned col0 = (unsigned)((unsigned long long)g.m0 % (unsigned)q);
+	const float kMagic = 12582912.0f;  // 2^23 + 2^22
+	const uint32_t *xp[kRsOut];
+	const float *hp[kRsOut];
+	f32x2 acc[kRsOut];
+#pragma unroll
+	for (int o = 0; o < kRsOut; o++) {
+		const unsigned k = (unsigned)(o * nthreads + tid);  // < 1024
+		xp[o] = rss_lds + g.sh + (g.phi0 + k * (unsigned)p) / (unsigned)q;
+		hp[o] = taps + (col0 + k) % (unsigned)q;
+		acc[o] = f32x2{ kMagic, kMagic };
+	}
+#pragma unroll 2
+	for (int n = 0; n < t; n++) {  // (T is even)
+#pragma unroll
+		for (int o = 0; o < kRsOut; o++) {
+			const uint32_t w = xp[o][n];
+			const f32x2 d = f32x2{ (float)(int)(int16_t)(w & 0xffffu), (float)((int)w >> 16) };  // exact
+			const float hs = hp[o][n * q];
+			acc[o] = __builtin_elementwise_fma(d, f32x2{ hs, hs }, acc[o]);
+		}
+	}
+	uint32_t *dst = out + (size_t)s * out_stride + g.m0 + tid;
+#pragma unroll
+	for (int o = 0; o < kRsOut; o++)  // the int16 store: the low half of the accumulator's mantissa
+		dst[o * nthreads] = (__float_as_uint(acc[o].x) & 0xffffu) | (__float_as_uint(acc[o].y) << 16);
 }
 
 // Base rate: chunk c (8 complex samples) of stream s's row -> dwords 8c .. 8c + 7 of the stream's stage-0 row.  `chan` as above
@@ -239,8 +314,13 @@ bool fmt_dispatch(int fmt, F f)
 	return false;
 }
 
+// ... and of a streamed launch: the image and the cosine table.  The half tile's image is at most 20.3 KB (15359/1536).
+__host__ __device__ constexpr int rs_stream_lds(int p, int q, int t, int tile) { return 8 * rs_raw_chunks(p, q, t, tile) * 4 + 2 * kTuneN; }
+static_assert(rs_stream_lds(10 * kRsQDiv - 1, kRsQDiv, kRsTMax, kRsTile / 2) <= kRsLdsMax, "the half tile serves the largest rate");
+
 // The arguments of launch_resample with the format in front; the history is the format's (above).  One geometry per rate, tuned or
-// not: half the tile where the image of a whole one and the cosine table exceed the LDS limit (resample.h).
+// not: half the tile where the image of a whole one and the cosine table exceed the LDS limit (resample.h).  A rate whose table is
+// not staged (rs_streamed; `taps` is resample_stream_kernel's table then) follows the same rule with its own LDS.
 hipError_t launch_resample_fmt(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, int p, int q, int t,
 			       const float *taps, const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride,
 			       const uint4 *chan, bool tuned)
@@ -249,12 +329,18 @@ hipError_t launch_resample_fmt(hipStream_t st, int fmt, const uint8_t *iq, size_
 	const long n_in = n_out * p / q;
 	if (tuned && !chan)
 		return hipErrorInvalidValue;
-	const int tile = rs_tuned_lds(p, q, t, kRsTile) <= kRsLdsMax ? kRsTile : kRsTile / 2;
-	const size_t lds = (size_t)rs_tuned_lds(p, q, t, tile) - (tuned ? 0 : 2 * kTuneN);
+	const bool streamed = rs_streamed(q, t);
+	const auto lds_of = [&](int tile_n) { return streamed ? rs_stream_lds(p, q, t, tile_n) : rs_tuned_lds(p, q, t, tile_n); };
+	const int tile = lds_of(kRsTile) <= kRsLdsMax ? kRsTile : kRsTile / 2;
+	const size_t lds = (size_t)lds_of(tile) - (tuned ? 0 : 2 * kTuneN);
 	const dim3 grid((unsigned)(n_out / tile), n_streams), block(tile / kRsOut);
 	const bool known = fmt_dispatch<true>(fmt, [&](auto f) {
-		hipLaunchKernelGGL(resample_fmt_kernel<decltype(f)::value>, grid, block, lds, st, iq, stride, n_in, p, q, t, taps, tail_in, tail_out,
-				   out, out_stride, chan, tuned ? 1 : 0);
+		if (streamed)
+			hipLaunchKernelGGL(resample_stream_kernel<decltype(f)::value>, grid, block, lds, st, iq, stride, n_in, p, q, t, taps, tail_in,
+					   tail_out, out, out_stride, chan, tuned ? 1 : 0);
+		else
+			hipLaunchKernelGGL(resample_fmt_kernel<decltype(f)::value>, grid, block, lds, st, iq, stride, n_in, p, q, t, taps, tail_in,
+					   tail_out, out, out_stride, chan, tuned ? 1 : 0);
 	});
 	return known ? hipGetLastError() : hipErrorInvalidValue;
 }

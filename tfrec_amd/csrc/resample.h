@@ -3,7 +3,7 @@
 // u8 IQ at fs_in = 1536000 P / Q  ->  1.536 MS/s int16 (I, Q), the "stage 0" buffer frontend_kernel<true, ...> reads.  The
 // reference has no such stage; like the 10:1 stage it is defined here in the reference's FIR style (tfrec_amd/resample.py is
 // the CPU restatement, include/tfrec_amd.h: tfrec_amd_create_rate the normative text):
-//   r = P / Q input samples per output sample, gcd(P, Q) = 1, 1 <= Q <= 64, 1 < r < 10;  T = 2 ceil(3 r) <= 60 taps per phase
+//   r = P / Q input samples per output sample, gcd(P, Q) = 1, Q <= 64 or Q | 1536, 1 < r < 10;  T = 2 ceil(3 r) <= 60 taps per phase
 //   output m of a submit:  a = m P,  i0 = a div Q,  phi = a mod Q        (every submit begins at phase 0 on its first sample)
 //   y0[m] = int16( sum_{n<T} ( x[i0 - (T-1) + n] * h[phi][n] ) >> 16 ),  x = (u8 - 128) << 6, the T - 1 samples before a
 //   submit come from the previous one's tail (silence, u8 128, after a start or restart)
@@ -19,22 +19,28 @@
 //     launch from P, Q and T (dynamic shared memory: 2.9 KB at 4/3, 3.9 KB at 25/16), so that the registers and not the
 //     largest rate's 36 KB set the occupancy of a common rate;
 //   * the tile's first output gets i0 and phi from one 64-bit division; a lane's first output is a 32-bit division away
-//     from it (the offset is below 2^20), and the lane steps (i0, phi) by (P div Q, P mod Q) from there;
+//     from it (the offset is below 2^24: kRsArMax), and the lane steps (i0, phi) by (P div Q, P mod Q) from there;
 //   * a lane makes kRsOut = 8 consecutive outputs, tap by tap: the eight FMAs of a tap go to eight accumulators.
 // `chan` (nullptr: stream s reads row s): the {.., .., input row, ..} of tfrec_amd_map_streams, as decim10_kernel<true> reads it.
 // resample_kernel is the kernel of a u8 context in which no stream has an input-rate tune (6g).  While one has, the context runs
 // resample_fmt_kernel<kFmtU8> (formats.h) on the same raw history instead: it rotates the tuned streams as it stages them.
+// These two stage the whole table, so they serve the rates with Q T <= kRsTableMax = 3840 taps (every Q <= 64, and 2.0, 2.5, 5 or
+// 10 MS/s among the Q | 1536); a rate with a larger table -- up to 92160 taps at 15359/1536 -- runs resample_stream_kernel
+// (formats.h) in every format, tuned or not, on the same histories.
 constexpr int kRsOut = 8;                      // outputs per lane
 constexpr int kRsTile = 1024;                  // outputs per workgroup
 constexpr int kRsThreads = kRsTile / kRsOut;   // 128
 constexpr int kRsTail = 128;                   // raw history per stream: 64 complex samples (T - 1 <= 59 needed), 16-byte multiple
-constexpr int kRsQMax = 64, kRsTMax = 60;
 // LDS of a launch, in dwords: the table, padded to a 16-byte multiple, then the image.  A tile's last sample is at most
 // floor((Q - 1 + 1023 P) / Q) samples behind its first output's i0, T - 1 lie before it, and the 16-byte alignment of the
 // first chunk adds at most 14 bytes.
 __host__ __device__ constexpr int rs_taps_dw(int q, int t) { return (q * t + 3) & ~3; }
 __host__ __device__ constexpr int rs_raw_chunks(int p, int q, int t, int tile = kRsTile) { return (2 * ((q - 1 + (tile - 1) * p) / q + t) + 14 + 15) / 16; }
 static_assert((rs_taps_dw(kRsQMax, kRsTMax) + 4 * rs_raw_chunks(10 * kRsQMax - 1, kRsQMax, kRsTMax)) * 4 <= 48 * 1024, "fits the default LDS limit");
+// (a staged table is at most kRsTableMax taps whatever Q, and an image at most that of r -> 10: the two bounds above and below hold
+// for the staged rates with Q | 1536 too.)  The kernels' 32-bit products: a - i00 Q of any output of a tile, and Q T.
+constexpr long kRsArMax = (long)kRsQDiv - 1 + (long)(kRsTile - 1) * (10 * kRsQDiv - 1);
+static_assert(kRsArMax < (1L << 24) && (long)kRsQDiv * kRsTMax < (1L << 17), "P <= 15359, Q <= 1536: the tile's offsets and the table's size stay far inside int");
 // ... and of the format-aware launch (formats.h: resample_fmt_kernel, which also is the tuned kernel of a u8 context): the table, the
 // int16 image (8 dwords per chunk) and the cosine table.  Where that exceeds 48 KB with a tile of 1024 outputs (the large rates)
 // the launch uses 64-thread workgroups and tiles of 512: at most 44.3 KB (639/64), so no rate needs more than the default LDS limit.
@@ -127,15 +133,16 @@ hipError_t launch_resample_fmt(hipStream_t st, int fmt, const uint8_t *iq, size_
 			       const float *taps, const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride,
 			       const uint4 *chan, bool tuned);  // formats.h
 
-// taps: [q][t] floats on the device, h / 1024; n_blocks * 32768 * p is a multiple of q (the caller checked)
+// taps: [q][t] floats on the device, h / 1024 (rs_streamed(q, t): the table resample_stream_kernel reads); n_blocks is a multiple
+// of rs_unit(q) (the caller checked), so n_blocks * 32768 * p is one of q
 // tuned: a stream has an input-rate tune (6g; chan != nullptr then): the format kernel's U8 instantiation, which reads and writes
 // the same raw history -- an untuned stream's survives the change of kernels around it in both directions
 hipError_t launch_resample(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, int p, int q, int t,
 			   const float *taps, const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride,
 			   const uint4 *chan, bool tuned)
 {
-	if (tuned)
-		return launch_resample_fmt(st, kFmtU8, iq, stride, n_streams, n_blocks, p, q, t, taps, tail_in, tail_out, out, out_stride, chan, true);
+	if (tuned || rs_streamed(q, t))  // (a streamed table: one kernel per format, tuned or not)
+		return launch_resample_fmt(st, kFmtU8, iq, stride, n_streams, n_blocks, p, q, t, taps, tail_in, tail_out, out, out_stride, chan, tuned);
 	const long n_out = (long)n_blocks * (TFREC_AMD_BLOCK_BYTES / 2);  // complex samples at 1.536 MS/s
 	const long n_in = n_out * p / q;
 	static_assert((TFREC_AMD_BLOCK_BYTES / 2) % kRsTile == 0, "resample_kernel has no partial tiles");

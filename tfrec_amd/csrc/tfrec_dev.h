@@ -31,6 +31,20 @@ constexpr int kNSlots = TFREC_AMD_NSLOTS;
 constexpr int kFmtU8 = TFREC_AMD_FMT_U8, kFmtS8 = TFREC_AMD_FMT_S8, kFmtS16 = TFREC_AMD_FMT_S16, kFmtF32 = TFREC_AMD_FMT_F32;
 constexpr int kFmtDec16 = TFREC_AMD_FMT_DEC16;  // tfrec_amd_create_decimated: int16 pairs at 384 kS/s (no kernel is templated on it)
 __host__ __device__ constexpr int fmt_sample_bytes(int fmt) { return fmt == kFmtF32 ? 8 : (fmt == kFmtS16 || fmt == kFmtDec16) ? 4 : 2; }
+// the resampling stage's rates (resample.h): Q <= kRsQMax or Q | kRsQDiv; T <= kRsTMax taps per phase.  A table [Q][T] of
+// at most kRsTableMax taps is staged in LDS by resample_kernel and resample_fmt_kernel; a larger one is streamed from global memory by
+// resample_stream_kernel, which reads it in another layout -- so whoever uploads the table and whoever launches ask rs_streamed.
+constexpr int kRsQMax = 64, kRsQDiv = 1536, kRsTMax = 60;
+constexpr int kRsTableMax = kRsQMax * kRsTMax;
+__host__ __device__ constexpr bool rs_streamed(int q, int t) { return q * t > kRsTableMax; }
+// a submit's n_blocks is a multiple of this (1 at the base rate): Q / gcd(Q, 64), the odd part of a Q <= 64
+__host__ __device__ constexpr int rs_unit(int q)
+{
+	int g = 64;
+	while (q % g)
+		g /= 2;
+	return q / g;
+}
 
 // ---- front-end tile geometry: a 256-thread workgroup per tile, kFrontOut decimated outputs (and 2 * kFrontOut
 // stage-1 outputs) per thread.  8 per thread: the per-wave scalar work (addresses, taps, edge tests) and the 6 raw

@@ -15,7 +15,7 @@ Window w's own sum is part of A, so a row's first window is already corrected.  
 its last K window sums and its window count: `state` below, (sums int64 [m, 2] with m = min(count, K), count).
 
 No window straddles a submit: a permitted submit of n_blocks blocks at the rate P / Q holds n_blocks 32768 P / Q complex samples;
-with Q = 2^a o, o odd and 2^a <= 64, n_blocks is a multiple of o, and 32768 / 2^a >= 512 is a multiple of 512 -- so every submit is a
+n_blocks is a multiple of Q / gcd(Q, 64) (resample.permitted_blocks), which makes that k P 512 (64 / gcd(Q, 64)) -- so every submit is a
 whole number of windows and the result does not depend on how a row is cut into submits (input_samples asserts it).
 """
 from __future__ import annotations

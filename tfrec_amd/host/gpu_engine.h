@@ -117,7 +117,7 @@ public:
 	// streams are mapped to it (tfrec_amd_map_streams).  Decoders, stream indices and output order stay per -L occurrence.
 	void set_wide(bool on) { job.wide = on; }
 	// -r: the dump files are u8 dumps at 1536000 p / q samples per second (tfrec_amd_create_rate).  A submit then
-	// carries a multiple of `unit` blocks, the odd part of q (the caller rounds blocks_per_submit up to one), a file is read in
+	// carries a multiple of `unit` blocks, q / gcd(q, 64) (the caller rounds blocks_per_submit up to one), a file is read in
 	// pieces of that many blocks and its trailing partial piece is dropped; everything else -- the tail of a file, -n, -d,
 	// shared paths, tunes and settings -- is as without it, and a file's tune beyond +-767 kHz (up to half the rate) becomes the
 	// input-rate tune ahead of the resampler (tfrec_amd_tune_streams_input).  Excludes set_wide.

@@ -60,13 +60,14 @@ struct job_settings {
 	bool resampled() const { return rate_p != 1 || rate_q != 1; }
 	bool occupancy() const { return spectrum && occ_ratio; }  // -A, pass 1
 	bool share() const { return slots <= 0; }  // one stream per file for the whole job: a path given several times is read once
-	// -r: the blocks a piece of a file holds, the odd part of q (1 without -r): every batch carries a multiple of it
+	// -r: the blocks a piece of a file holds, q / gcd(q, 64) -- the odd part of a q <= 64, 6 at 625/384; 1 without -r: every
+	// batch carries a multiple of it (tfrec_amd_create_rate: Submits)
 	int unit() const
 	{
-		int u = rate_q;
-		while (u % 2 == 0)
-			u /= 2;
-		return u;
+		int g = 64;
+		while (rate_q % g)
+			g /= 2;
+		return rate_q / g;
 	}
 	// bytes of a piece of `unit` blocks of a file: 65536 p / q x unit is a whole number (q is unit times a power of two <= 64);
 	// -F: times the format's bytes per complex sample / 2; 655360 with -x

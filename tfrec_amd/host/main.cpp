@@ -34,10 +34,11 @@
 // per -L occurrence.  With -n a repeated file is read once per occurrence, as before.
 // -r Hz (not in the reference): the sample rate of the -L files, for dumps that were not recorded at 1.536 MS/s -- rtl_sdr's
 // default 2048000, 2400000, 1920000 ... --: the rate is reduced to P / Q of 1536000 and the dumps are resampled on the GPU
-// (tfrec_amd_create_rate; 1 < P/Q < 10, Q <= 64).  -f / -c / -p f= reach the whole recording, |f - c| below half the
+// (tfrec_amd_create_rate; 1 < P/Q < 10, Q <= 64 or Q | 1536: every whole-kHz rate in between, 2000000, 2500000,
+// 10000000, 12500000 ...).  -f / -c / -p f= reach the whole recording, |f - c| below half the
 // rate: within +-767 kHz the shift acts behind the resampler (tfrec_amd_tune_streams), a larger one ahead of it, at the input
 // rate (tfrec_amd_tune_streams_input).  A path given to several -L is read once, as without -r.  A submit must
-// hold a whole number of input samples: -b is rounded up to the next multiple of Q's odd part.  Excludes -x.
+// hold a whole number of 512-sample windows: -b is rounded up to the next multiple of Q / gcd(Q, 64).  Excludes -x.
 // -F u8|s8|s16|f32 (not in the reference; also cu8, cs8, cs16, cf32): what the -L files hold -- rtl_sdr's offset-binary u8 (the
 // default), hackrf_transfer's signed int8, the int16 of Airspy, SDRplay, USRP and rx_sdr, or the float32 of GNU Radio, SDR++, GQRX
 // and SigMF cf32_le; little-endian, interleaved I, Q, without a header (tfrec_amd_create_format).  With -r the files
@@ -273,7 +274,8 @@ static void usage()
 			"  -c kHz      frequency the dumps were recorded at (default 868250); -f within 767 kHz of it\n"
 			"  -x          the dumps are 15.36 MS/s u8 dumps (10x the rate); -f within 7679 kHz of -c, shifted ahead of the 10:1 stage\n"
 			"              (a file given to several -L is read once and shared by its streams; with -n it is read per -L, as before)\n"
-			"  -r Hz       sample rate of the dumps (default 1536000), e.g. 2048000 or 2400000: resampled on the GPU; -b is rounded up\n"
+			"  -r Hz       sample rate of the dumps (default 1536000), e.g. 2048000, 2400000 or any whole kHz such as 2500000 or 10000000\n"
+			"              (between 1536000 and 15360000): resampled on the GPU; -b is rounded up\n"
 			"              to a block count that holds a whole number of input samples; -f less than half the rate from -c (beyond\n"
 			"              767 kHz it is shifted ahead of the resampler); not with -x\n"
 			"  -F format   what the dumps hold: u8 (default), s8, s16 or f32 (cu8, cs8, cs16, cf32): little-endian interleaved I, Q without a\n"
@@ -498,8 +500,8 @@ int cli::reduce_rate()
 		const long p = rate / a, q = 1536000 / a;
 		if (p > 0x7fffffffL || tfrec_amd_resample_taps((int32_t)p, (int32_t)q, NULL, 0, NULL) != TFREC_AMD_OK) {
 			fprintf(stderr, "tfrec_gpu: -r %ld: the rate is %ld/%ld of 1536000 S/s, which the resampler does not take (it needs "
-					"1536000 < rate < 15360000 and a denominator of at most 64, and refuses a few rates whose filter would "
-					"be ambiguous or could overflow)\n", rate, p, q);
+					"1536000 < rate < 15360000 and a whole number of kHz or a denominator of at most 64, and refuses a few rates "
+					"whose filter would be ambiguous or could overflow)\n", rate, p, q);
 			return 1;
 		}
 		in.rate_p = (int)p;

@@ -5,7 +5,8 @@ int16 stream that enters downconvert::process_iq.  The stage has no reference co
 reference's FIR style (int taps, arithmetic >> 16 per tap, int16 store), and the GPU kernel is pinned to this file bit for bit.
 Written from the definition alone: nothing here calls the C library.
 
-    r = P / Q (input samples per output sample), gcd(P, Q) = 1, 1 <= Q <= 64, 1 < r < 10
+    r = P / Q (input samples per output sample), gcd(P, Q) = 1, 1 < r < 10, and Q <= 64 or Q divides 1536 -- the latter is
+        "fs_in is a whole number of kHz": 2.0, 2.5, 5, 10, 12.5 MS/s are 125/96, 625/384, 625/192, 625/96, 3125/384
     T = 2 * ceil(3 r) taps per phase
     output m (since the stream's start or last restart):  a = m P,  i0 = a div Q,  phi = a mod Q
     y0[m] = int16( sum_{n<T} ( x[i0 - (T-1) + n] * h[phi][n] ) >> 16 )   per rail, x = (u8 - 128) << 6, x[<0] = 0
@@ -20,7 +21,8 @@ import math
 import numpy as np
 
 BASE_RATE = 1536000
-Q_MAX = 64
+Q_MAX = 64  # every denominator up to here ...
+Q_DIV = 1536  # ... and every divisor of this one
 TIE_EPS = 1e-9
 
 
@@ -37,7 +39,7 @@ def reduce_rate(rate_hz: int) -> tuple[int, int]:
 def n_taps(p: int, q: int) -> int:
     """T, the taps per phase; raises RateError for a rate outside the supported range."""
     p, q = int(p), int(q)
-    if p <= 0 or q <= 0 or q > Q_MAX or math.gcd(p, q) != 1 or not (q < p < 10 * q):
+    if p <= 0 or q <= 0 or (q > Q_MAX and Q_DIV % q) or math.gcd(p, q) != 1 or not (q < p < 10 * q):
         raise RateError("unsupported rate %d/%d" % (p, q))
     return 2 * ((3 * p + q - 1) // q)
 
@@ -66,19 +68,19 @@ def taps(p: int, q: int) -> np.ndarray:
 
 
 def permitted_blocks(q: int) -> int:
-    """Submits carry a multiple of this many blocks: the odd part of Q."""
+    """Submits carry a multiple of this many blocks: Q / gcd(Q, 64), the odd part of a Q <= 64.  A submit then holds
+    k * P * 512 * (64 / gcd(Q, 64)) input samples: a whole number of 512-sample windows.  (The odd part alone would not do at
+    Q = 128: one block of 129/128 is 33024 samples, 64.5 windows.)"""
     q = int(q)
-    while q % 2 == 0:
-        q //= 2
-    return q
+    return q // math.gcd(q, 64)
 
 
 def input_samples(n_blocks: int, p: int, q: int) -> int:
-    """Complex input samples a submit of n_blocks blocks consumes per stream; RateError if that is not an integer."""
-    num = int(n_blocks) * 32768 * int(p)
-    if n_blocks < 1 or num % int(q):
-        raise RateError("%d blocks at %d/%d is not a whole number of input samples" % (n_blocks, p, q))
-    return num // int(q)
+    """Complex input samples a submit of n_blocks blocks consumes per stream; RateError unless n_blocks is a multiple of
+    permitted_blocks(q)."""
+    if n_blocks < 1 or int(n_blocks) % permitted_blocks(q):
+        raise RateError("%d blocks at %d/%d: a submit holds a multiple of %d blocks" % (n_blocks, p, q, permitted_blocks(q)))
+    return int(n_blocks) * 32768 * int(p) // int(q)
 
 
 def resample_x16(x16, p: int, q: int, hist=None) -> np.ndarray:
