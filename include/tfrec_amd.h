@@ -415,6 +415,62 @@ int tfrec_amd_read_dc(tfrec_amd_ctx *ctx, int32_t row, int16_t *d, size_t cap_wi
  * Errors as tfrec_amd_reset_streams: a NULL list with n > 0, n < 0, a row out of range or a context without the blocker:
  * TFREC_AMD_E_INVAL, and nothing is marked; a poisoned context: TFREC_AMD_E_STATE. */
 int tfrec_amd_reset_dc_rows(tfrec_amd_ctx *ctx, const int32_t *rows, int n);
+/* IQ balancer: a context that removes each input ROW's IQ imbalance -- the gain and phase error between the I and
+ * the Q rail of a zero-IF front end, which puts a conjugate image of every signal at the mirror frequency -- behind the DC blocker
+ * (or without one) and ahead of everything else.  It belongs to an input row and acts at the context's input rate on the
+ * DC-corrected x', ahead of the input-rate tune, the resampling stage, tfrec_amd_tune_streams and process_iq.  There is no reference
+ * counterpart: this text is normative.  Exact integers:
+ *   Windows.  Those of the DC blocker: L = 512 complex input samples, counted from the row's first submit or its last reset, never
+ *     straddling a submit.  d[w] is the blocker's estimate for window w, (0, 0) on a context without the blocker (dc_windows = 0).
+ *   Moments.  Per window, on the UNCLAMPED differences u = x - d[w] per rail: A[w] = sum u_I^2, B[w] = sum u_Q^2, C[w] = sum u_I u_Q.
+ *     |u| <= 16383, so A, B <= 2^37 and |C| <= 2^37.  They follow exactly from five raw sums of one pass over the window (S_I, S_Q as
+ *     for the blocker, M_II = sum x_I^2, M_QQ = sum x_Q^2, M_IQ = sum x_I x_Q):
+ *         A = M_II - 2 d_I S_I + 512 d_I^2,  B = M_QQ - 2 d_Q S_Q + 512 d_Q^2,  C = M_IQ - d_I S_Q - d_Q S_I + 512 d_I d_Q.
+ *   Sums.  K = iq_windows, 1 <= K <= 4096; lo = max(0, w - K + 1); SA, SB, SC = the sums of A, B, C over windows lo .. w, window w
+ *     included (<= 2^49).
+ *   Estimate.  In int64, with floor division and arithmetic shifts:
+ *         s = max(0, bitlen(max(SA, SB)) - 31);  a = SA >> s, b = SB >> s, c = SC >> s;
+ *         D = a b - c^2  (a, b < 2^31, |c| <= 2^31);  r = isqrt(D), the exact floor of the square root;
+ *         t = floor((c 32768 + a) / (2 a));  g = floor((a 32768 + r) / (2 r)).
+ *     t and g are Q14: C / A and A / sqrt(A B - C^2), rounded half up.  The window gets the IDENTITY t = 0, g = 16384 if a == 0,
+ *     D <= 0, |t| > 4096, g < 12288 or g > 20480 (about +-14 degrees and +-25 %): a silent, a fully correlated or an absurd window is
+ *     passed through unchanged.  These are conditions, not measurements.
+ *   Apply.  On the clamped x' = clamp(x - d[w], -8192, 8191):  I'' = I';  v = (Q' 16384 - t I' + 8192) >> 14;
+ *     Q'' = clamp((v g + 8192) >> 14, -8192, 8191) -- int32 throughout: |t I'| <= 2^25, |v| <= 10241, |v g| < 2^28.  Everything
+ *     downstream is the text above applied to x''; its no-wrap arguments hold because |x''| <= 8192.
+ *   State.  Per row the last K triples (A, B, C) and the window count, carried from submit to submit (beside the blocker's).  A
+ *     stream restart does not touch it; tfrec_amd_reset_iq_rows clears it at the next submit; a row that a submit does not provide
+ *     keeps it.  Results do not depend on how a row is cut into submits.
+ *   Limits.  One frequency-flat correction per row, estimated on the assumption that the row's signals are proper (circular): a lone
+ *     carrier at 0 Hz is not, so a recording with a DC offset wants dc_windows > 0; the first windows of a row are estimated from
+ *     few samples.
+ * tfrec_amd_create_iq: dc_windows within [0, 4096], 0 for no DC blocker; iq_windows within [1, 4096]; formats, rates, max_rows and
+ * refusals (TFREC_AMD_F_INPUT_10X, an unknown format, a refused rate, a value out of range: TFREC_AMD_E_INVAL) as for
+ * tfrec_amd_create_dc.  With dc_windows > 0, tfrec_amd_get_dc, tfrec_amd_read_dc and tfrec_amd_reset_dc_rows work as on a
+ * tfrec_amd_create_dc context; with dc_windows = 0 they answer as on a context without a blocker.  The context is a format context
+ * in every other respect, as a DC context is: tfrec_amd_read_stage0, levels, capture and events see the CORRECTED input; the
+ * spectrum and the occupancy detector keep reading the caller's raw rows.  Memory (all in tfrec_amd_get_memory), beside the
+ * blocker's where there is one: per FIFO set the table of (t, g), 4 bytes per window, and -- without the blocker -- the corrected
+ * rows, max_rows * n_max * 4 bytes; per context a submit's five sums (32 bytes per window) and moments (24), the ring of moments
+ * (max_rows * K * 24 bytes) and the counts.  Pinned by tfrec_amd/iqbal.py.  Contexts of every other constructor launch what they
+ * launched before. */
+int tfrec_amd_create_iq(const tfrec_amd_config *cfg, int32_t format, int32_t rate_p, int32_t rate_q, int32_t dc_windows, int32_t iq_windows,
+			int32_t max_rows, tfrec_amd_ctx **out);
+/* iq_windows and max_rows of a tfrec_amd_create_iq context; 0 and 0 on every other context. */
+int tfrec_amd_get_iq(tfrec_amd_ctx *ctx, int32_t *iq_windows, int32_t *max_rows);
+/* (t, g) of one input row of the OLDEST undrained submit, with the conventions of tfrec_amd_read_dc (waits for the submit; call it
+ * BEFORE tfrec_amd_drain_events pops it; reading pops nothing): tg[2 * w] = t and tg[2 * w + 1] = g of the submit's window w, for
+ * w < *n_windows = n_in / 512; cap_windows is the room in windows.  tg may be NULL with cap_windows 0 to fetch only *n_windows.
+ * Errors: not a tfrec_amd_create_iq context, a row the submit did not use, n_windows NULL: TFREC_AMD_E_INVAL; the room too small
+ * (or tg NULL): TFREC_AMD_E_INVAL, nothing is written, but *n_windows is set; nothing undrained or a poisoned context:
+ * TFREC_AMD_E_STATE. */
+int tfrec_amd_read_iq(tfrec_amd_ctx *ctx, int32_t row, int16_t *tg, size_t cap_windows, int *n_windows);
+/* Clear the balancer's state of the listed rows (each within [0, max_rows); duplicates allowed; n == 0: nothing) at the NEXT
+ * submit: their window count restarts at 0 there.  The DC blocker's state is tfrec_amd_reset_dc_rows's.  Submits already queued
+ * are not affected; the streams that read the rows are not restarted.  Errors as tfrec_amd_reset_dc_rows: a NULL list with n > 0,
+ * n < 0, a row out of range or a context without the balancer: TFREC_AMD_E_INVAL, and nothing is marked; a poisoned context:
+ * TFREC_AMD_E_STATE. */
+int tfrec_amd_reset_iq_rows(tfrec_amd_ctx *ctx, const int32_t *rows, int n);
 
 /* Wait for submitted work. */
 int tfrec_amd_sync(tfrec_amd_ctx *ctx);

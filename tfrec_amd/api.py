@@ -107,7 +107,7 @@ EXPORTS = (
     "tfrec_amd_tune_streams_input", "tfrec_amd_get_stream_tune_input", "tfrec_amd_create_format", "tfrec_amd_get_input_format",
     "tfrec_amd_read_levels", "tfrec_amd_enable_capture", "tfrec_amd_read_captures", "tfrec_amd_enable_spectrum",
     "tfrec_amd_read_spectrum", "tfrec_amd_enable_occupancy", "tfrec_amd_read_occupancy", "tfrec_amd_create_dc", "tfrec_amd_get_dc",
-    "tfrec_amd_read_dc", "tfrec_amd_reset_dc_rows", "tfrec_amd_create_decimated", "tfrec_amd_enable_capture_pre",
+    "tfrec_amd_read_dc", "tfrec_amd_reset_dc_rows", "tfrec_amd_create_iq", "tfrec_amd_get_iq", "tfrec_amd_read_iq", "tfrec_amd_reset_iq_rows", "tfrec_amd_create_decimated", "tfrec_amd_enable_capture_pre",
     "tfrec_amd_read_capture_pre", "tfrec_amd_enable_runs_input", "tfrec_amd_submit_runs", "tfrec_amd_read_biquad_row",
 )
 
@@ -197,6 +197,10 @@ def load_library(build: bool = True, experiments: bool = False, short_segments: 
     L.tfrec_amd_get_dc.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.tfrec_amd_read_dc.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
     L.tfrec_amd_reset_dc_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.tfrec_amd_create_iq.argtypes = [C.POINTER(Config), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.tfrec_amd_get_iq.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.tfrec_amd_read_iq.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
+    L.tfrec_amd_reset_iq_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.tfrec_amd_create_decimated.argtypes = [C.POINTER(Config), C.POINTER(C.c_void_p)]
     L.tfrec_amd_enable_capture_pre.argtypes = [C.c_void_p]
     L.tfrec_amd_read_capture_pre.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
@@ -245,7 +249,7 @@ class Receiver:
                  device: int = 0, max_blocks: int = 48, max_events: int | None = None, all_flushes: bool = False,
                  timing: bool = False, serial_chains: bool = False, input_10x: bool = False, bits: bool = False,
                  experiments: bool = False, input_rate=None, input_format=None, levels: bool = False, dc_windows=None,
-                 dc_rows=None, decimated: bool = False, short_segments: bool = False):
+                 dc_rows=None, decimated: bool = False, short_segments: bool = False, iq_windows=None):
         # experiments=True: the build that reads the TFREC_AMD_* knobs / test hooks from the environment (csrc/knobs.h);
         # the default is the product library, which has none.  short_segments=True: the experiments build with biquad
         # segments of _build.SEG_SLOTS slots (libtfrec_amd_seg.so)
@@ -268,15 +272,30 @@ class Receiver:
         # dc_windows=K (1 .. 4096): the DC blocker ahead of everything, averaging over K windows of 512 input samples, for at most
         # dc_rows input rows (default: n_streams) -- with any input_format ("u8" included) and input_rate (tfrec_amd_create_dc,
         # dcblock.py)
+        # iq_windows=K (1 .. 4096): the IQ balancer behind the DC blocker (dc_windows=K') or without one (dc_windows None or 0),
+        # estimating over K of the same windows, for at most dc_rows input rows (tfrec_amd_create_iq, iqbal.py)
         # decimated=True: the rows hold int16 (I, Q) pairs at 384 kS/s, the decimated samples themselves (tfrec_amd_create_decimated,
         # decin.py): 32768 bytes per block.  submit() takes them as uint8 rows like every input, or as int16 arrays.
         self.is_decimated = bool(decimated)
         if decimated:
-            if dc_windows is not None or input_format is not None or input_rate is not None:
-                raise TfrecAmdError(E_INVAL, "decimated input has no other format, rate or DC blocker")
+            if dc_windows is not None or iq_windows is not None or input_format is not None or input_rate is not None:
+                raise TfrecAmdError(E_INVAL, "decimated input has no other format, rate, DC blocker or IQ balancer")
             _check(self.L, self.L.tfrec_amd_create_decimated(C.byref(self.cfg), C.byref(self.h)))
             self.input_rate = (1, 4)
             self.input_format = "dec16"
+        elif iq_windows is not None:
+            from . import formats
+
+            p, q = (int(v) for v in (input_rate if input_rate is not None else (1, 1)))
+            fmt = "u8" if input_format is None else input_format
+            fmt = formats.FORMATS.get(fmt, fmt) if isinstance(fmt, str) else fmt
+            rows = n_streams if dc_rows is None else int(dc_rows)
+            k_dc = 0 if dc_windows is None else int(dc_windows)
+            if not isinstance(fmt, int) or not all(-2 ** 31 <= v < 2 ** 31 for v in (p, q, fmt, k_dc, int(iq_windows), rows)):
+                raise TfrecAmdError(E_INVAL, "input_format, input_rate, dc_windows, iq_windows or dc_rows: unknown name or outside int32")
+            _check(self.L, self.L.tfrec_amd_create_iq(C.byref(self.cfg), fmt, p, q, k_dc, int(iq_windows), rows, C.byref(self.h)))
+            self.input_rate = (p, q)
+            self.input_format = formats.NAMES[fmt]
         elif dc_windows is not None:
             from . import formats
 
@@ -666,6 +685,36 @@ class Receiver:
         if nw.value:
             _check(self.L, self.L.tfrec_amd_read_dc(self.h, int(row), d.ctypes.data, nw.value, C.byref(nw)))
         return d
+
+    def iq(self) -> tuple:
+        """(iq_windows, max_rows) of an iq_windows context, (0, 0) of every other (tfrec_amd_get_iq)."""
+        k, rows = C.c_int32(-1), C.c_int32(-1)
+        _check(self.L, self.L.tfrec_amd_get_iq(self.h, C.byref(k), C.byref(rows)))
+        return int(k.value), int(rows.value)
+
+    def read_iq(self, row: int) -> np.ndarray:
+        """The balancer's (t, g) of input row `row` of the OLDEST undrained submit (tfrec_amd_read_iq; call it before the drain that
+        pops that submit) -> int16 [n_windows, 2].  TfrecAmdError(E_INVAL) on a context without the balancer or for a row the submit
+        did not use, (E_STATE) when nothing is waiting to be drained."""
+        if not -2 ** 31 <= int(row) < 2 ** 31:
+            raise TfrecAmdError(E_INVAL, "row outside int32")
+        nw = C.c_int(0)
+        rc = self.L.tfrec_amd_read_iq(self.h, int(row), None, 0, C.byref(nw))  # the count (no room: E_INVAL)
+        if rc != E_INVAL or nw.value == 0:
+            _check(self.L, rc)
+        tg = np.zeros((nw.value, 2), dtype=np.int16)
+        if nw.value:
+            _check(self.L, self.L.tfrec_amd_read_iq(self.h, int(row), tg.ctypes.data, nw.value, C.byref(nw)))
+        return tg
+
+    def reset_iq_rows(self, rows):
+        """Clear the balancer's state of the listed input rows at the next submit (tfrec_amd_reset_iq_rows); the streams are not
+        restarted and the DC blocker's state is reset_dc_rows's."""
+        idx = [int(r) for r in rows]
+        if any(not -2 ** 31 <= r < 2 ** 31 for r in idx):  # (refused before int32 could wrap an index into range)
+            raise TfrecAmdError(E_INVAL, "row outside int32")
+        a = np.ascontiguousarray(idx, dtype=np.int32)
+        _check(self.L, self.L.tfrec_amd_reset_iq_rows(self.h, a.ctypes.data if len(a) else None, len(a)))
 
     def reset_dc_rows(self, rows):
         """Clear the DC state of the listed input rows at the next submit (tfrec_amd_reset_dc_rows); the streams are not restarted."""

@@ -327,6 +327,33 @@ static int make_dc(tfrec_amd_ctx *c)
 	return TFREC_AMD_OK;
 }
 
+// tfrec_amd_create_iq: the balancer's carried state and every set's buffers (behind make_dc, whose corrected rows it shares)
+static int make_iq(tfrec_amd_ctx *c)
+{
+	IqBal &o = c->iq;
+	if (!o.on)
+		return TFREC_AMD_OK;
+	const long long n_max = ((long long)c->cfg.max_blocks * (TFREC_AMD_BLOCK_BYTES / 2) * c->in_p / c->in_q + 7) & ~7LL;  // (as make_dc)
+	const size_t rows = (size_t)o.rows;
+	o.win_stride = (int)(n_max / 512);
+	o.x_stride = (size_t)n_max * 4;
+	TRY(own_device(c, o.d_sums, rows * (size_t)o.win_stride * kIqSumsBytes));
+	TRY(own_device(c, o.d_mom, rows * (size_t)o.win_stride * kIqMomentsBytes));
+	TRY(own_device(c, o.d_ring, rows * (size_t)o.k * kIqMomentsBytes));
+	TRY(own_device(c, o.d_state, rows * sizeof(int2)));
+	HIPCHK(hipMemset(o.d_state, 0, rows * sizeof(int2)));
+	for (int k = 0; k < kSets; k++) {
+		TRY(own_device(c, o.d_tg[k], rows * (size_t)o.win_stride * sizeof(uint32_t)));
+		if (c->dc.on) {
+			o.d_x[k] = c->dc.d_x[k];
+		} else {
+			TRY(own_device(c, o.d_x[k], rows * o.x_stride));
+		}
+	}
+	o.reset_marked.assign(rows, 0);
+	return TFREC_AMD_OK;
+}
+
 // One set's window tables (chains2.hip): the rows and counters of every chain carved out of one block
 static int make_win_tables(tfrec_amd_ctx *c, int set)
 {
@@ -652,6 +679,7 @@ static int init_context(tfrec_amd_ctx *c)
 	TRY(register_chains(c));
 	TRY(make_front_buffers(c));
 	TRY(make_dc(c));
+	TRY(make_iq(c));
 	if (!(c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS))
 		TRY(make_window_state(c));
 	TRY(make_event_blocks(c));
@@ -687,9 +715,10 @@ int tfrec_amd_destroy(tfrec_amd_ctx *c)
 
 // What the three constructors share behind their own argument checks: the input's format, its rate p / q (resamp: through the
 // resampling stage; ingest: another format at the base rate) and the context made for it
-// dc_k != 0: with the DC blocker over at most dc_rows rows (tfrec_amd_create_dc)
+// dc_k != 0: with the DC blocker over at most dc_rows rows (tfrec_amd_create_dc); iq_k != 0: with the IQ balancer over as many
+// (tfrec_amd_create_iq), behind the blocker or -- dc_k == 0 -- without one
 static int create_with(const tfrec_amd_config *cfg, int32_t fmt, int32_t p, int32_t q, bool resamp, bool ingest, tfrec_amd_ctx **out,
-		       int32_t dc_k = 0, int32_t dc_rows = 0, bool decimated = false)
+		       int32_t dc_k = 0, int32_t dc_rows = 0, bool decimated = false, int32_t iq_k = 0)
 {
 	TRY(validate(cfg));
 	HIPCHK(hipSetDevice(cfg->device));
@@ -703,6 +732,12 @@ static int create_with(const tfrec_amd_config *cfg, int32_t fmt, int32_t p, int3
 		c->dc.on = true;
 		c->dc.k = dc_k;
 		c->dc.rows = dc_rows;
+	}
+	if (iq_k) {
+		c->pre_fmt = TFREC_AMD_FMT_S16;
+		c->iq.on = true;
+		c->iq.k = iq_k;
+		c->iq.rows = dc_rows;
 	}
 	c->in10x = (cfg->flags & TFREC_AMD_F_INPUT_10X) != 0;
 	c->in_p = c->in10x ? 10 : p;

@@ -138,6 +138,25 @@ struct DcBlock {
 	std::vector<uint8_t> reset_marked;
 };
 
+// tfrec_amd_create_iq: K, the rows a submit may use and the windows of the largest submit; per context a submit's
+// five raw sums ([rows][win_stride], kIqSumsBytes each) and moments (kIqMomentsBytes each), the ring of moments ([rows][K]) and the
+// rows' {m, head}; per set the table of (t, g) ([rows][win_stride]) and the corrected rows the pre-stage reads -- the DC blocker's
+// where the context has one (dc.on: its ring, state, table of d and rows are used as on a tfrec_amd_create_dc context; its sums
+// are not), the balancer's own otherwise.  reset_*: as the blocker's.
+constexpr size_t kIqSumsBytes = 32, kIqMomentsBytes = 24;  // (iqbal.h asserts them)
+struct IqBal {
+	bool on = false;
+	int k = 0, rows = 0, win_stride = 0;
+	size_t x_stride = 0;
+	void *d_sums = nullptr, *d_mom = nullptr, *d_ring = nullptr;
+	int2 *d_state = nullptr;
+	uint32_t *d_tg[kSets] = {};
+	uint8_t *d_x[kSets] = {};
+	int set_rows[kSets] = {}, set_windows[kSets] = {};
+	std::vector<int32_t> reset_pending;
+	std::vector<uint8_t> reset_marked;
+};
+
 struct tfrec_amd_ctx {
 	tfrec_amd_config cfg;
 	ChainLaunch launch;
@@ -234,6 +253,7 @@ struct tfrec_amd_ctx {
 	int32_t fmt = TFREC_AMD_FMT_U8, pre_fmt = TFREC_AMD_FMT_U8;
 	bool ingest = false;
 	DcBlock dc;
+	IqBal iq;  // tfrec_amd_create_iq: the balancer behind (or without) the blocker; pre_fmt is S16 as with dc
 	// ---- window-parallel pipeline (make_window_state).  One set per submit in flight, like the front-end outputs: the window
 	// scan and the biquads of submit k+1 fill theirs while the slicers of submit k still read the other
 	int16_t *d_ld16[kSets] = {};   // [chains][m_max] tfa2-family biquad outputs

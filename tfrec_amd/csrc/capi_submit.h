@@ -238,6 +238,40 @@ static int launch_dc_rows(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, size_t
 	return TFREC_AMD_OK;
 }
 
+// tfrec_amd_create_iq: as check_dc_rows
+static int check_iq_rows(const tfrec_amd_ctx *c)
+{
+	if (!c->iq.on || rows_in_use(c) <= c->iq.rows)
+		return TFREC_AMD_OK;
+	snprintf(g_err, sizeof(g_err), "the submit uses %d input rows, the IQ balancer was made for %d", rows_in_use(c), c->iq.rows);
+	return TFREC_AMD_E_INVAL;
+}
+
+// The IQ balancer in the place of launch_dc_rows: the rows marked by either reset call start again, then the three
+// kernels -- which do the DC blocker's work too where the context has one -- correct the submit's rows into the set's buffer.
+static int launch_iq_rows(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, size_t stride, long n_in)
+{
+	IqBal &o = c->iq;
+	DcBlock &b = c->dc;
+	hipStream_t fs = c->pipe[set].fs;
+	for (int32_t r : b.reset_pending) {
+		HIPCHK(hipMemsetAsync(b.d_state + r, 0, sizeof(int2), fs));
+		b.reset_marked[r] = 0;
+	}
+	b.reset_pending.clear();
+	for (int32_t r : o.reset_pending) {
+		HIPCHK(hipMemsetAsync(o.d_state + r, 0, sizeof(int2), fs));
+		o.reset_marked[r] = 0;
+	}
+	o.reset_pending.clear();
+	const int rows = rows_in_use(c);
+	HIPCHK(launch_iq(fs, c->fmt, d_iq, stride, rows, n_in, o.d_sums, o.win_stride, b.on ? b.k : 0, b.d_ring, b.d_state, b.d_d[set], o.d_mom,
+			 o.k, o.d_ring, o.d_state, o.d_tg[set], o.d_x[set], o.x_stride));
+	o.set_rows[set] = b.set_rows[set] = rows;
+	o.set_windows[set] = b.set_windows[set] = (int)(n_in / 512);
+	return TFREC_AMD_OK;
+}
+
 // The channel-rate front end in the place of the pre-stage and the front end: the dense kernel on the rows, or
 // -- runs: tfrec_amd_submit_runs staged this set's table -- the sparse one
 static int launch_decin_front(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, size_t stride, int n_blocks, bool runs)
@@ -273,6 +307,7 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		snprintf(g_err, sizeof(g_err), "IQ base and stream stride must be 16-byte aligned and >= one stream");
 		return TFREC_AMD_E_INVAL;
 	}
+	TRY(check_iq_rows(c));
 	TRY(check_dc_rows(c));
 	TRY(check_fifo(c));
 	TRY(check_live(c));
@@ -326,7 +361,11 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	if (c->in16) {  // ... then the standard cascade on int16 input
 		const uint8_t *pin = (const uint8_t *)d_iq;
 		size_t pstride = stride;
-		if (c->dc.on) {  // the DC blocker first: the pre-stage reads the corrected rows, an S16 input
+		if (c->iq.on) {  // the IQ balancer (with the DC blocker's work in it) first: the pre-stage reads the corrected rows
+			TRY(launch_iq_rows(c, set, pin, stride, (long)(row_bytes / fmt_sample_bytes(c->fmt))));
+			pin = c->iq.d_x[set];
+			pstride = c->iq.x_stride;
+		} else if (c->dc.on) {  // the DC blocker first: the pre-stage reads the corrected rows, an S16 input
 			TRY(launch_dc_rows(c, set, pin, stride, (long)(row_bytes / fmt_sample_bytes(c->fmt))));
 			pin = c->dc.d_x[set];
 			pstride = c->dc.x_stride;
@@ -444,6 +483,7 @@ static int submit_host_impl(tfrec_amd_ctx *c, const uint8_t *h_iq, size_t stride
 	TRY(input_bytes(c, n_blocks, &row));
 	if (rows_in_use(c) > 1 && stride < row)
 		return TFREC_AMD_E_INVAL;
+	TRY(check_iq_rows(c));
 	TRY(check_dc_rows(c));
 	TRY(check_fifo(c));
 	HIPCHK(hipSetDevice(c->cfg.device));

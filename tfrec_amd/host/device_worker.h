@@ -51,6 +51,7 @@ private:
 	int collect(size_t k, batch_result &b);
 	int read_captures(size_t k, batch_result &b);
 	int read_dc(size_t k, batch_result &b);
+	int read_iq(size_t k, batch_result &b);
 	int close_context(int r);
 
 	const job_settings &job;
@@ -217,8 +218,9 @@ inline int device_worker::open_context()
 	in_tune.assign(n, false);
 	narrow_tune.assign(n, false);
 	const char *call = "tfrec_amd_create";
-	// (the rows are known: -z sizes the blocker for them)
+	// (the rows are known: -z and -Z size the blocker and the balancer for them)
 	int r = job.replay		       ? tfrec_amd_create_decimated(&cfg, &ctx)
+		: job.iq_windows	       ? tfrec_amd_create_iq(&cfg, job.fmt, job.rate_p, job.rate_q, job.dc_windows, job.iq_windows, (int32_t)n_rows, &ctx)
 		: job.dc_windows	       ? tfrec_amd_create_dc(&cfg, job.fmt, job.rate_p, job.rate_q, job.dc_windows, (int32_t)n_rows, &ctx)
 		: job.fmt != TFREC_AMD_FMT_U8  ? tfrec_amd_create_format(&cfg, job.fmt, job.rate_p, job.rate_q, &ctx)
 		: job.resampled()	       ? tfrec_amd_create_rate(&cfg, job.rate_p, job.rate_q, &ctx)
@@ -329,13 +331,16 @@ inline int device_worker::submit(size_t k)
 	}
 	const batch_plan &b = plan[k];
 	int r = 0;
-	if (job.dc_windows && !job.share()) {
-		// -n with -z: a slot that starts a new file -- by a reset, or by the configure or tune its next file needs -- starts a new
-		// DC estimate too.  A stream's row is its own here (nothing is shared); duplicates are allowed.
+	if ((job.dc_windows || job.iq_windows) && !job.share()) {
+		// -n with -z or -Z: a slot that starts a new file -- by a reset, or by the configure or tune its next file needs -- starts a
+		// new DC and a new IQ estimate too.  A stream's row is its own here (nothing is shared); duplicates are allowed.
 		std::vector<int32_t> rows(b.reset);
 		rows.insert(rows.end(), b.conf.begin(), b.conf.end());
 		rows.insert(rows.end(), b.tune.begin(), b.tune.end());
-		r = tfrec_amd_reset_dc_rows(ctx, rows.data(), (int)rows.size());
+		if (job.dc_windows)
+			r = tfrec_amd_reset_dc_rows(ctx, rows.data(), (int)rows.size());
+		if (!r && job.iq_windows)
+			r = tfrec_amd_reset_iq_rows(ctx, rows.data(), (int)rows.size());
 	}
 	if (!r && !b.reset.empty())  // the streams whose file ended in the batch before: fresh receivers for the next files
 		r = tfrec_amd_reset_streams(ctx, b.reset.data(), (int)b.reset.size());
@@ -445,6 +450,29 @@ inline int device_worker::read_dc(size_t k, batch_result &b)
 	return r;
 }
 
+// -Z -D: the last (t, g) of every file's row
+inline int device_worker::read_iq(size_t k, batch_result &b)
+{
+	std::vector<int16_t> tg;
+	int r = 0;
+	for (size_t s = 0; s < n && r == 0; s++) {
+		if (plan[k].file[s] < 0 || !reads[s])
+			continue;
+		int nw = 0;
+		r = tfrec_amd_read_iq(ctx, in_row[s], NULL, 0, &nw);  // (the count: E_INVAL for want of room)
+		if (r == TFREC_AMD_E_INVAL && nw > 0) {
+			tg.resize(2 * (size_t)nw);
+			r = tfrec_amd_read_iq(ctx, in_row[s], tg.data(), (size_t)nw, &nw);
+			if (r == 0) {
+				b.iq_file.push_back(plan[k].file[s]);
+				b.iq_last.push_back(tg[2 * (size_t)nw - 2]);
+				b.iq_last.push_back(tg[2 * (size_t)nw - 1]);
+			}
+		}
+	}
+	return r;
+}
+
 // batch k's results: its side outputs (captures, then occupancy or spectrum, then DC, then levels), then the drain that pops it
 // and frees its host buffer for the reader
 inline int device_worker::collect(size_t k, batch_result &b)
@@ -470,6 +498,8 @@ inline int device_worker::collect(size_t k, batch_result &b)
 	}
 	if (!r && job.dc_windows && job.dbg > 0)
 		r = read_dc(k, b);
+	if (!r && job.iq_windows && job.dbg > 0)
+		r = read_iq(k, b);
 	if (!r && job.scan) {  // -s: the batch's level records
 		int nb = 0;
 		b.lv.resize(n * (size_t)bps);

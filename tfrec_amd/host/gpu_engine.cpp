@@ -189,6 +189,8 @@ struct dc_report {
 	{
 		for (size_t q = 0; q < b.dc_file.size(); q++)
 			printf("dc %s I=%d Q=%d\n", files[b.dc_file[q]].c_str(), (int)b.dc_last[2 * q], (int)b.dc_last[2 * q + 1]);
+		for (size_t q = 0; q < b.iq_file.size(); q++)  // -Z -D (set_iq)
+			printf("iq %s t=%d g=%d\n", files[b.iq_file[q]].c_str(), (int)b.iq_last[2 * q], (int)b.iq_last[2 * q + 1]);
 	}
 };
 

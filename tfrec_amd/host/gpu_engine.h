@@ -180,6 +180,10 @@ public:
 	// prints "dc <file> I=<d> Q=<d>" per submit and file: the estimate of the submit's last window of the file's row.  Under -A
 	// only pass 2 is given it: pass 1's spectrum reads the raw rows either way.  Excludes set_wide.
 	void set_dc(int windows) { job.dc_windows = windows; }
+	// -Z: the IQ balancer (tfrec_amd_create_iq) over `windows` of the same windows, behind the DC blocker of set_dc or
+	// without one, on every input row of every context, sized and reset as the blocker is.  With dbg > 0 run() prints
+	// "iq <file> t=<t> g=<g>" per submit and file: the estimate of the submit's last window of the file's row.  Excludes set_wide.
+	void set_iq(int windows) { job.iq_windows = windows; }
 	// -R: replay a capture.  The engine's files are the capture's -- captures[i] is file i of the job, read back whole,
 	// and a file's length is its last run's end rounded up to blocks --; every context takes channel-rate input
 	// (tfrec_amd_create_decimated) and is fed sparse submits (tfrec_amd_submit_runs) cut by the batch plan, so -b, -n and -d work as

@@ -55,6 +55,7 @@ struct job_settings {
 	int occ_ratio = 0, occ_rel = 0;  // set_occupancy (0: none)
 	long occ_join = 0;
 	int dc_windows = 0;            // set_dc (0: none)
+	int iq_windows = 0;            // set_iq (0: none)
 	const std::vector<replay_file> *replay = NULL;  // set_replay (NULL: the files are dumps)
 
 	bool resampled() const { return rate_p != 1 || rate_q != 1; }
@@ -306,6 +307,8 @@ struct batch_result {
 	std::vector<uint32_t> occ_bits;
 	std::vector<int> dc_file;
 	std::vector<int16_t> dc_last;
+	std::vector<int> iq_file;  // -Z -D: as dc_file and dc_last, the last window's {t, g}
+	std::vector<int16_t> iq_last;
 };
 
 // ---- the sums behind the output modes' tables, one consumer per mode: begin() prints what the mode says before a device is

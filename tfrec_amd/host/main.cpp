@@ -1,6 +1,6 @@
 // tfrec_amd/host/main.cpp -- tfrec_gpu: the reference's file-replay CLI on the GPU path.
 //
-//   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-q] [-D] [-B] [-d device[,device...]] [-b blocks]
+//   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d device[,device...]] [-b blocks]
 //             [-n streams] [-e handler | -E handler] [-m mode] [-p settings] -L dump.iq [[-p settings] -L more.iq ...]
 //   tfrec_gpu [receiver flags as above] [-c kHz] [-x | -r Hz] [-F format] [-D] -P bins[,frames_per_record] -L dump.iq
 //   tfrec_gpu [-T hexmask] [-t thresh] [-W] [-c kHz] [-x | -r Hz] [-F format] [-D] [-d device] [-b blocks] -s step_kHz -L dump.iq
@@ -96,6 +96,12 @@
 // -A and -n (a slot that starts a new file starts a new estimate); the spectrum of -P and of -A's pass 1 stays that of the raw
 // input.  With -D stdout carries "dc <file> I=<d> Q=<d>" per submit and file: the estimate of the submit's last window, in units
 // of x (a u8 LSB is 64).  Not with -x or -X.
+// -Z [windows] (not in the reference): remove every recording's IQ imbalance on the GPU (tfrec_amd_create_iq) -- the
+// gain and phase error between the rails of a zero-IF front end, whose image of a burst at the mirror frequency decodes as a
+// second transmitter.  One correction per recording, estimated in exact integers over the last `windows` windows of 512 input
+// samples (1 .. 4096, default 2048), behind -z's subtraction and ahead of every tune.  It assumes proper signals: a DC offset is
+// not one, so a recording that has one wants -z too.  Works with whatever -z works with, and not with what -z does not.  With -D
+// stdout carries "iq <file> t=<t> g=<g>" per submit and file: the submit's last window's Q14 pair (balanced: t=0 g=16384).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -242,6 +248,9 @@ struct cli {
 	// 1.536 MS/s, is derived from nothing but the burst lengths: an average much longer than any telegram (8 windows eat part of
 	// a burst and lose a telegram, 64 do not: DESIGN.md 6m); it has not been measured on real recordings.
 	long dc_windows = 0;
+	// -Z: the IQ balancer's length in the same windows (0: off).  The default is -z's, by the same reasoning -- an estimate over much
+	// more than a telegram, so that no single burst steers it; it has not been measured on real recordings either.
+	long iq_windows = 0;
 	job_settings in;                  // the input: -x, -r as P / Q, -F; it answers what follows from them (job.h)
 	std::vector<long> scan_khz;       // -s, -A: the channels
 	std::vector<file_settings> per_file;
@@ -261,7 +270,7 @@ struct cli {
 
 static void usage()
 {
-	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
+	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
 			"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
 			"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
 			"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
@@ -283,6 +292,10 @@ static void usage()
 			"  -z [n]      remove every dump's DC offset on the GPU, ahead of every tune: the mean over the last n windows of 512 input\n"
 			"              samples (default 2048, within 1 .. 4096) is subtracted from I and from Q (-D: a 'dc' line per submit); not with\n"
 			"              -x or -X; under -A the spectrum of pass 1 stays raw\n"
+			"  -Z [n]      remove every dump's IQ imbalance (gain and phase error between I and Q, whose images decode as ghost transmitters)\n"
+			"              on the GPU, behind -z and ahead of every tune: one correction per dump, estimated over the last n windows of 512\n"
+			"              input samples (default 2048, within 1 .. 4096; -D: an 'iq' line per submit); use -z with it where the dump has a\n"
+			"              DC offset; not with -x or -X\n"
 			"  -n streams  at most this many streams per device: the -L files queue for them in order\n"
 			"  -p T=<hex>,t=<n>,W=<0|1>,f=<kHz>  -T / -t / -W / -f of the -L files that follow, up to the next -p (fields left out: the global ones)\n");
 }
@@ -339,7 +352,7 @@ bool cli::parse_format(const char *arg)
 int cli::parse(int argc, char **argv)
 {
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::h")) != -1) {
 		switch (c) {
 		case 'z': {
 			const char *a = optional_arg(argc, argv);
@@ -347,6 +360,16 @@ int cli::parse(int argc, char **argv)
 			if (a && !parse_long(a, 1, 4096, dc_windows)) {
 				fprintf(stderr, "tfrec_gpu: bad -z '%s': want the windows (of 512 input samples) the DC estimate averages over, within "
 						"1 .. 4096\n", a);
+				return 1;
+			}
+			break;
+		}
+		case 'Z': {
+			const char *a = optional_arg(argc, argv);
+			iq_windows = 2048;
+			if (a && !parse_long(a, 1, 4096, iq_windows)) {
+				fprintf(stderr, "tfrec_gpu: bad -Z '%s': want the windows (of 512 input samples) the IQ estimate runs over, within 1 .. 4096\n",
+					a);
 				return 1;
 			}
 			break;
@@ -440,9 +463,9 @@ int cli::parse(int argc, char **argv)
 int cli::check() const
 {
 	if (replay_prefix && (!dumps.empty() || wide || rate || have_format || freq >= 0 || have_center || have_scan || have_auto || have_spec_p ||
-			      dc_windows || cap_prefix || have_spec || hexfile)) {
+			      dc_windows || iq_windows || cap_prefix || have_spec || hexfile)) {
 		fprintf(stderr, "tfrec_gpu: -R replays a capture, which is 384 kS/s int16 IQ and nothing else: not with -L, -x, -r, -F, -f, -c, -s, "
-				"-A, -P, -z, -S, -p or -X\n");
+				"-A, -P, -z, -Z, -S, -p or -X\n");
 		return 2;
 	}
 	if (have_slots && slots < 1) {
@@ -464,6 +487,10 @@ int cli::check() const
 	}
 	if (dc_windows && (wide || hexfile)) {
 		fprintf(stderr, "tfrec_gpu: -z removes the DC offset of -L files at 1.536 MS/s or the rate of -r: not with -x or -X\n");
+		return 1;
+	}
+	if (iq_windows && (wide || hexfile)) {
+		fprintf(stderr, "tfrec_gpu: -Z removes the IQ imbalance of -L files at 1.536 MS/s or the rate of -r: not with -x or -X\n");
 		return 1;
 	}
 	if (cap_prefix && hexfile) {
@@ -691,6 +718,8 @@ int cli::run()
 	apply_input(e, in);
 	if (dc_windows)
 		e.set_dc((int)dc_windows);
+	if (iq_windows)
+		e.set_iq((int)iq_windows);
 	if (have_scan)
 		e.set_scan(scan_khz);
 	if (cap_prefix)
