@@ -1,4 +1,5 @@
-"""Cost of the DC blocker: kernel times of dc_sums_kernel, dc_estimate_kernel and dc_apply_kernel on 1 and 64 input
+"""Cost of the DC blocker: kernel times of its three kernels -- csrc/correct.h's instantiations without the balancer,
+printed under the names they had as kernels of their own: dc_sums_kernel, dc_estimate_kernel and dc_apply_kernel -- on 1 and 64 input
 rows of 48 blocks, u8 at 1/1 and s16 at 25/16, next to their floor -- the row is read twice in its stored format (once for the sums,
 once to be corrected) and 4 bytes per complex sample are written and, by the pre-stage behind them, read again -- at the 8 TB/s HBM
 peak.  The estimate kernel is one wave per row and moves next to nothing: it is latency, not traffic.
@@ -14,6 +15,7 @@ from __future__ import annotations
 
 import argparse
 import os
+import re
 import statistics
 import subprocess
 import sys
@@ -30,6 +32,20 @@ CONTEXTS = (("u8", 1, 1, 2), ("s16", 25, 16, 4))  # format, P, Q, bytes per comp
 ROWS = (1, 64)
 K = 2048
 KERNELS = ("dc_sums_kernel", "dc_estimate_kernel", "dc_apply_kernel")
+
+
+def label(kernel_name: str):
+    """The label of a correct.h kernel in the trace, or None: correct_sums_kernel<FMT, MOM>, correct_estimate_kernel<DC, IQ> and
+    correct_apply_kernel<FMT, DC, IQ> all say in their last template argument whether the balancer is in them."""
+    m = re.search(r"correct_(sums|estimate|apply)_kernel<([^>]*)>", kernel_name)
+    if not m:
+        return None
+    return "%s_%s_kernel" % ("iq" if m.group(2).split(",")[-1].strip() in ("true", "1") else "dc", m.group(1))
+
+
+def launches(d: dict, names) -> dict:
+    """label -> durations of its instantiations' launches, the instantiations in the order of their names (by format, as CONTEXTS)."""
+    return {name: sum((d[k] for k in sorted(d) if label(k) == name), []) for name in names}
 
 
 def workload(n_blocks: int, submits: int) -> None:
@@ -56,7 +72,7 @@ def workload(n_blocks: int, submits: int) -> None:
 
 def report(trace_dir: str, n_blocks: int, submits: int) -> str:
     d = durations(trace_dir)
-    per_kernel = {name: sum((d[k] for k in sorted(d) if name in k), []) for name in KERNELS}
+    per_kernel = launches(d, KERNELS)
     lines = ["dc_cost: %d blocks per row and submit, K = %d, %d timed submits per context after %d warm-up submits"
              % (n_blocks, K, submits, WARMUP)]
     per = WARMUP + submits

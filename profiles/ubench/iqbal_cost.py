@@ -1,4 +1,5 @@
-"""Cost of the IQ balancer: kernel times of iq_sums_kernel, iq_estimate_kernel and iq_apply_kernel on 1 and 64 input
+"""Cost of the IQ balancer: kernel times of its three kernels -- csrc/correct.h's instantiations with the balancer,
+printed under the names they had as kernels of their own: iq_sums_kernel, iq_estimate_kernel and iq_apply_kernel -- on 1 and 64 input
 rows of 48 blocks, u8 at 1/1 and s16 at 25/16 -- and, in the same run and on the same rows, of the DC blocker's three kernels
 (dc_cost.py), which they replace on a balancer context: the yardstick.  The floor is the blocker's: the row is read twice in its
 stored format (once for the sums, once to be corrected) and 4 bytes per complex sample are written and, by the pre-stage behind
@@ -25,6 +26,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+from dc_cost import launches  # noqa: E402
 from resample_cost import HBM_PEAK, WARMUP, durations  # noqa: E402
 
 TIME_LIMIT = 600  # seconds, for the traced child
@@ -60,7 +62,7 @@ def workload(n_blocks: int, submits: int) -> None:
 
 def report(trace_dir: str, n_blocks: int, submits: int) -> str:
     d = durations(trace_dir)
-    per_kernel = {name: sum((d[k] for k in sorted(d) if name in k), []) for _, names in FAMILIES for name in names}
+    per_kernel = launches(d, [name for _, names in FAMILIES for name in names])
     lines = ["iqbal_cost: %d blocks per row and submit, K = %d, %d timed submits per context after %d warm-up submits"
              % (n_blocks, K, submits, WARMUP)]
     per = WARMUP + submits

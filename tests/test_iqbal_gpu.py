@@ -123,7 +123,10 @@ def assert_estimates(ds, tgs, want, sizes):
 # fmt, p, q, unit, k_dc, k_iq.  1/1: 64 windows per block; 25/16: 100, so the last piece of a scan is partial; 4/3: units of 3 blocks,
 # 256 windows.  K = 3: the ring wraps inside every submit; 64 and 100: across submits (and inside the two-unit one); 4096: never.
 CONTEXTS = [("u8", 1, 1, 1, 0, 3), ("u8", 1, 1, 1, 4, 64), ("u8", 1, 1, 1, 4, 4096), ("s8", 1, 1, 1, 4, 100), ("s8", 1, 1, 1, 0, 64),
-            ("s16", 25, 16, 1, 4, 3), ("s16", 25, 16, 1, 0, 100), ("s16", 25, 16, 1, 4, 64), ("f32", 4, 3, 3, 0, 4096), ("f32", 4, 3, 3, 4, 100)]
+            ("s16", 25, 16, 1, 4, 3), ("s16", 25, 16, 1, 0, 100), ("s16", 25, 16, 1, 4, 64), ("f32", 4, 3, 3, 0, 4096), ("f32", 4, 3, 3, 4, 100),
+            # the blocker's ring inside the balancer's estimate kernel: it fills exactly at a submit boundary (64), inside the second
+            # submit (100), never (4096)
+            ("u8", 1, 1, 1, 64, 3), ("s8", 1, 1, 1, 100, 64), ("s16", 25, 16, 1, 100, 64), ("f32", 4, 3, 3, 4096, 100)]
 
 
 @pytest.mark.parametrize("fmt,p,q,unit,k_dc,k_iq", CONTEXTS, ids=["%s-%d/%d-dc%d-K%d" % (c[0], c[1], c[2], c[4], c[5]) for c in CONTEXTS])

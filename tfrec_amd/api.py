@@ -283,40 +283,26 @@ class Receiver:
             _check(self.L, self.L.tfrec_amd_create_decimated(C.byref(self.cfg), C.byref(self.h)))
             self.input_rate = (1, 4)
             self.input_format = "dec16"
-        elif iq_windows is not None:
+        elif iq_windows is not None or dc_windows is not None or input_format is not None:
             from . import formats
 
+            fix = iq_windows is not None or dc_windows is not None
             p, q = (int(v) for v in (input_rate if input_rate is not None else (1, 1)))
             fmt = "u8" if input_format is None else input_format
             fmt = formats.FORMATS.get(fmt, fmt) if isinstance(fmt, str) else fmt
-            rows = n_streams if dc_rows is None else int(dc_rows)
+            rows = n_streams if dc_rows is None or not fix else int(dc_rows)
             k_dc = 0 if dc_windows is None else int(dc_windows)
-            if not isinstance(fmt, int) or not all(-2 ** 31 <= v < 2 ** 31 for v in (p, q, fmt, k_dc, int(iq_windows), rows)):
+            k_iq = 0 if iq_windows is None else int(iq_windows)
+            if not isinstance(fmt, int) or not all(-2 ** 31 <= v < 2 ** 31 for v in (p, q, fmt, k_dc, k_iq, rows)):
                 raise TfrecAmdError(E_INVAL, "input_format, input_rate, dc_windows, iq_windows or dc_rows: unknown name or outside int32")
-            _check(self.L, self.L.tfrec_amd_create_iq(C.byref(self.cfg), fmt, p, q, k_dc, int(iq_windows), rows, C.byref(self.h)))
-            self.input_rate = (p, q)
-            self.input_format = formats.NAMES[fmt]
-        elif dc_windows is not None:
-            from . import formats
-
-            p, q = (int(v) for v in (input_rate if input_rate is not None else (1, 1)))
-            fmt = "u8" if input_format is None else input_format
-            fmt = formats.FORMATS.get(fmt, fmt) if isinstance(fmt, str) else fmt
-            rows = n_streams if dc_rows is None else int(dc_rows)
-            if not isinstance(fmt, int) or not all(-2 ** 31 <= v < 2 ** 31 for v in (p, q, fmt, int(dc_windows), rows)):
-                raise TfrecAmdError(E_INVAL, "input_format, input_rate, dc_windows or dc_rows: unknown name or outside int32")
-            _check(self.L, self.L.tfrec_amd_create_dc(C.byref(self.cfg), fmt, p, q, int(dc_windows), rows, C.byref(self.h)))
-            self.input_rate = (p, q)
-            self.input_format = formats.NAMES[fmt]
-        elif input_format is not None:
-            from . import formats
-
-            p, q = (int(v) for v in (input_rate if input_rate is not None else (1, 1)))
-            fmt = formats.FORMATS.get(input_format, input_format) if isinstance(input_format, str) else input_format
-            if not isinstance(fmt, int) or not all(-2 ** 31 <= v < 2 ** 31 for v in (p, q, fmt)):
-                raise TfrecAmdError(E_INVAL, "input_format or input_rate: unknown name or outside int32")
-            _check(self.L, self.L.tfrec_amd_create_format(C.byref(self.cfg), fmt, p, q, C.byref(self.h)))
-            if not input_10x:
+            if iq_windows is not None:
+                rc = self.L.tfrec_amd_create_iq(C.byref(self.cfg), fmt, p, q, k_dc, k_iq, rows, C.byref(self.h))
+            elif dc_windows is not None:
+                rc = self.L.tfrec_amd_create_dc(C.byref(self.cfg), fmt, p, q, k_dc, rows, C.byref(self.h))
+            else:
+                rc = self.L.tfrec_amd_create_format(C.byref(self.cfg), fmt, p, q, C.byref(self.h))
+            _check(self.L, rc)
+            if not input_10x:  # (u8 alone goes with the 10:1 stage)
                 self.input_rate = (p, q)
             got = C.c_int32(-1)
             _check(self.L, self.L.tfrec_amd_get_input_format(self.h, C.byref(got)))
@@ -671,20 +657,30 @@ class Receiver:
         _check(self.L, self.L.tfrec_amd_get_dc(self.h, C.byref(k), C.byref(rows)))
         return int(k.value), int(rows.value)
 
+    def _read_estimates(self, read, row: int) -> np.ndarray:
+        if not -2 ** 31 <= int(row) < 2 ** 31:
+            raise TfrecAmdError(E_INVAL, "row outside int32")
+        nw = C.c_int(0)
+        rc = read(self.h, int(row), None, 0, C.byref(nw))  # the count (no room: E_INVAL)
+        if rc != E_INVAL or nw.value == 0:
+            _check(self.L, rc)
+        out = np.zeros((nw.value, 2), dtype=np.int16)
+        if nw.value:
+            _check(self.L, read(self.h, int(row), out.ctypes.data, nw.value, C.byref(nw)))
+        return out
+
+    def _reset_rows(self, reset, rows) -> None:
+        idx = [int(r) for r in rows]
+        if any(not -2 ** 31 <= r < 2 ** 31 for r in idx):  # (refused before int32 could wrap an index into range)
+            raise TfrecAmdError(E_INVAL, "row outside int32")
+        a = np.ascontiguousarray(idx, dtype=np.int32)
+        _check(self.L, reset(self.h, a.ctypes.data if len(a) else None, len(a)))
+
     def read_dc(self, row: int) -> np.ndarray:
         """The DC estimates d[w] of input row `row` of the OLDEST undrained submit (tfrec_amd_read_dc; call it before the drain that
         pops that submit) -> int16 [n_windows, 2], (I, Q).  TfrecAmdError(E_INVAL) on a context without the blocker or for a row the
         submit did not use, (E_STATE) when nothing is waiting to be drained."""
-        if not -2 ** 31 <= int(row) < 2 ** 31:
-            raise TfrecAmdError(E_INVAL, "row outside int32")
-        nw = C.c_int(0)
-        rc = self.L.tfrec_amd_read_dc(self.h, int(row), None, 0, C.byref(nw))  # the count (no room: E_INVAL)
-        if rc != E_INVAL or nw.value == 0:
-            _check(self.L, rc)
-        d = np.zeros((nw.value, 2), dtype=np.int16)
-        if nw.value:
-            _check(self.L, self.L.tfrec_amd_read_dc(self.h, int(row), d.ctypes.data, nw.value, C.byref(nw)))
-        return d
+        return self._read_estimates(self.L.tfrec_amd_read_dc, row)
 
     def iq(self) -> tuple:
         """(iq_windows, max_rows) of an iq_windows context, (0, 0) of every other (tfrec_amd_get_iq)."""
@@ -696,33 +692,16 @@ class Receiver:
         """The balancer's (t, g) of input row `row` of the OLDEST undrained submit (tfrec_amd_read_iq; call it before the drain that
         pops that submit) -> int16 [n_windows, 2].  TfrecAmdError(E_INVAL) on a context without the balancer or for a row the submit
         did not use, (E_STATE) when nothing is waiting to be drained."""
-        if not -2 ** 31 <= int(row) < 2 ** 31:
-            raise TfrecAmdError(E_INVAL, "row outside int32")
-        nw = C.c_int(0)
-        rc = self.L.tfrec_amd_read_iq(self.h, int(row), None, 0, C.byref(nw))  # the count (no room: E_INVAL)
-        if rc != E_INVAL or nw.value == 0:
-            _check(self.L, rc)
-        tg = np.zeros((nw.value, 2), dtype=np.int16)
-        if nw.value:
-            _check(self.L, self.L.tfrec_amd_read_iq(self.h, int(row), tg.ctypes.data, nw.value, C.byref(nw)))
-        return tg
+        return self._read_estimates(self.L.tfrec_amd_read_iq, row)
 
     def reset_iq_rows(self, rows):
         """Clear the balancer's state of the listed input rows at the next submit (tfrec_amd_reset_iq_rows); the streams are not
         restarted and the DC blocker's state is reset_dc_rows's."""
-        idx = [int(r) for r in rows]
-        if any(not -2 ** 31 <= r < 2 ** 31 for r in idx):  # (refused before int32 could wrap an index into range)
-            raise TfrecAmdError(E_INVAL, "row outside int32")
-        a = np.ascontiguousarray(idx, dtype=np.int32)
-        _check(self.L, self.L.tfrec_amd_reset_iq_rows(self.h, a.ctypes.data if len(a) else None, len(a)))
+        self._reset_rows(self.L.tfrec_amd_reset_iq_rows, rows)
 
     def reset_dc_rows(self, rows):
         """Clear the DC state of the listed input rows at the next submit (tfrec_amd_reset_dc_rows); the streams are not restarted."""
-        idx = [int(r) for r in rows]
-        if any(not -2 ** 31 <= r < 2 ** 31 for r in idx):  # (refused before int32 could wrap an index into range)
-            raise TfrecAmdError(E_INVAL, "row outside int32")
-        a = np.ascontiguousarray(idx, dtype=np.int32)
-        _check(self.L, self.L.tfrec_amd_reset_dc_rows(self.h, a.ctypes.data if len(a) else None, len(a)))
+        self._reset_rows(self.L.tfrec_amd_reset_dc_rows, rows)
 
     def stage0(self, stream: int, n_pairs: int) -> np.ndarray:
         """input_10x or input_rate: the 1.536 MS/s int16 IQ the 10:1 or the resampling stage produced for the last submit."""

@@ -54,8 +54,7 @@ hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t st
 hipError_t launch_occupancy(hipStream_t st, int n_rows, long n_in, int n_bins, int g, size_t max_records, const unsigned long long *sum,
 			    const unsigned long long *peak, const uint32_t *nfr, uint32_t ratio, uint32_t rel, tfrec_amd_occupancy *recs,
 			    uint32_t *bits);
-hipError_t launch_dc(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_rows, long n_in, int k, int2 *sums, int win_stride,
-		     int2 *ring, int2 *state, uint32_t *d, uint8_t *out, size_t out_stride);
+hipError_t launch_correct(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_rows, long n_in, const CorrectBufs &b);
 hipError_t launch_decin(hipStream_t st, const uint8_t *in, size_t stride, int n_streams, int n_blocks, const uint4 *chan, uint32_t *dec,
 			size_t dec_stride, unsigned long long *mask, size_t mask_stride, uint32_t *prevdec, uint32_t *last, int thresh,
 			const StreamCfg *scfg);
@@ -64,9 +63,6 @@ hipError_t launch_decin_runs(hipStream_t st, int n_streams, int n_blocks, const 
 			     size_t mask_stride, uint32_t *prevdec, uint32_t *last, int thresh, const StreamCfg *scfg);
 hipError_t launch_capture_pre(hipStream_t st, const tfrec_amd_run *runs, const CaptureHeader *hdr, uint32_t max_runs, long long sample_base,
 			      const uint32_t *dec, size_t dec_stride, const uint32_t *prevdec, uint32_t *pre);
-hipError_t launch_iq(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_rows, long n_in, void *sums, int win_stride, int dc_k,
-		     int2 *dc_ring, int2 *dc_state, uint32_t *d, void *mom, int k, void *iq_ring, int2 *iq_state, uint32_t *tg, uint8_t *out,
-		     size_t out_stride);
 }  // namespace tfrec
 
 using namespace tfrec;
@@ -76,8 +72,7 @@ using namespace tfrec;
 #include "capi_probe.h"    // the discriminator's host check, debug statistics; probes, read-backs, timings, memory, counters
 #include "capi_submit.h"   // the two kernels, a submit's resets and staging, submit_common, the submits, drain, sync, pending
 #include "capi_outputs.h"  // the level meter's, the recorder's, the spectrum's and the occupancy detector's entry points
-#include "capi_dc.h"       // the DC blocker's constructor, getter, read and reset
-#include "capi_iq.h"       // the IQ balancer's constructor, getter, read and reset
+#include "capi_correct.h"  // the DC blocker's and the IQ balancer's constructors, getters, reads and resets
 #include "capi_streams.h"  // reset, configure, the three tunes, map, and their getters
 #include "capi_decin.h"    // the channel-rate constructor, the recorder's pre samples, sparse submits
 

@@ -304,53 +304,44 @@ static int make_front_buffers(tfrec_amd_ctx *c)
 	return TFREC_AMD_OK;
 }
 
-// tfrec_amd_create_dc: the blocker's carried state (a row before its first submit: no window, m = head = 0) and every set's buffers
-static int make_dc(tfrec_amd_ctx *c)
+// One estimator's carried state (a row before its first submit: no window, m = head = 0) and every set's table
+template <class Ring>
+static int make_estimator(tfrec_amd_ctx *c, Estimator<Ring> &e)
 {
-	DcBlock &o = c->dc;
-	if (!o.on)
+	if (!e.k)
 		return TFREC_AMD_OK;
-	// the largest submit: floor(max_blocks * 32768 * P / Q) complex samples per row, up to a whole chunk; its whole windows
-	const long long n_max = ((long long)c->cfg.max_blocks * (TFREC_AMD_BLOCK_BYTES / 2) * c->in_p / c->in_q + 7) & ~7LL;
+	const InputCorrection &o = c->fix;
 	const size_t rows = (size_t)o.rows;
-	o.win_stride = (int)(n_max / 512);
-	o.x_stride = (size_t)n_max * 4;
-	TRY(own_device(c, o.d_sums, rows * (size_t)o.win_stride * sizeof(int2)));
-	TRY(own_device(c, o.d_ring, rows * (size_t)o.k * sizeof(int2)));
-	TRY(own_device(c, o.d_state, rows * sizeof(int2)));
-	HIPCHK(hipMemset(o.d_state, 0, rows * sizeof(int2)));
-	for (int k = 0; k < kSets; k++) {
-		TRY(own_device(c, o.d_d[k], rows * (size_t)o.win_stride * sizeof(uint32_t)));
-		TRY(own_device(c, o.d_x[k], rows * o.x_stride));
-	}
-	o.reset_marked.assign(rows, 0);
+	TRY(own_device(c, e.d_ring, rows * (size_t)e.k * sizeof(Ring)));
+	TRY(own_device(c, e.d_state, rows * sizeof(int2)));
+	HIPCHK(hipMemset(e.d_state, 0, rows * sizeof(int2)));
+	for (int k = 0; k < kSets; k++)
+		TRY(own_device(c, e.d_table[k], rows * (size_t)o.win_stride * sizeof(uint32_t)));
+	e.reset_marked.assign(rows, 0);
 	return TFREC_AMD_OK;
 }
 
-// tfrec_amd_create_iq: the balancer's carried state and every set's buffers (behind make_dc, whose corrected rows it shares)
-static int make_iq(tfrec_amd_ctx *c)
+// tfrec_amd_create_dc / tfrec_amd_create_iq: the estimators, a submit's sums and moments, and every set's corrected rows
+static int make_correct(tfrec_amd_ctx *c)
 {
-	IqBal &o = c->iq;
-	if (!o.on)
+	InputCorrection &o = c->fix;
+	if (!o.on())
 		return TFREC_AMD_OK;
-	const long long n_max = ((long long)c->cfg.max_blocks * (TFREC_AMD_BLOCK_BYTES / 2) * c->in_p / c->in_q + 7) & ~7LL;  // (as make_dc)
-	const size_t rows = (size_t)o.rows;
+	// the largest submit: floor(max_blocks * 32768 * P / Q) complex samples per row, up to a whole chunk; its whole windows
+	const long long n_max = ((long long)c->cfg.max_blocks * (TFREC_AMD_BLOCK_BYTES / 2) * c->in_p / c->in_q + 7) & ~7LL;
+	const size_t wins = (size_t)o.rows * (size_t)(n_max / 512);
 	o.win_stride = (int)(n_max / 512);
 	o.x_stride = (size_t)n_max * 4;
-	TRY(own_device(c, o.d_sums, rows * (size_t)o.win_stride * kIqSumsBytes));
-	TRY(own_device(c, o.d_mom, rows * (size_t)o.win_stride * kIqMomentsBytes));
-	TRY(own_device(c, o.d_ring, rows * (size_t)o.k * kIqMomentsBytes));
-	TRY(own_device(c, o.d_state, rows * sizeof(int2)));
-	HIPCHK(hipMemset(o.d_state, 0, rows * sizeof(int2)));
-	for (int k = 0; k < kSets; k++) {
-		TRY(own_device(c, o.d_tg[k], rows * (size_t)o.win_stride * sizeof(uint32_t)));
-		if (c->dc.on) {
-			o.d_x[k] = c->dc.d_x[k];
-		} else {
-			TRY(own_device(c, o.d_x[k], rows * o.x_stride));
-		}
+	TRY(make_estimator(c, o.dc));
+	TRY(make_estimator(c, o.iq));
+	if (o.dc.k)  // (behind the balancer its five sums are used and these are not: kept, tfrec_amd_get_memory reports them)
+		TRY(own_device(c, o.d_dc_sums, wins * sizeof(int2)));
+	if (o.iq.k) {
+		TRY(own_device(c, o.d_iq_sums, wins * sizeof(IqSums)));
+		TRY(own_device(c, o.d_mom, wins * sizeof(IqMoments)));
 	}
-	o.reset_marked.assign(rows, 0);
+	for (int k = 0; k < kSets; k++)
+		TRY(own_device(c, o.d_x[k], (size_t)o.rows * o.x_stride));
 	return TFREC_AMD_OK;
 }
 
@@ -678,8 +669,7 @@ static int init_context(tfrec_amd_ctx *c)
 		c->copy_guess = c->copy_guess_min = (uint32_t)std::max(1, atoi(cg));
 	TRY(register_chains(c));
 	TRY(make_front_buffers(c));
-	TRY(make_dc(c));
-	TRY(make_iq(c));
+	TRY(make_correct(c));
 	if (!(c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS))
 		TRY(make_window_state(c));
 	TRY(make_event_blocks(c));
@@ -713,12 +703,19 @@ int tfrec_amd_destroy(tfrec_amd_ctx *c)
 	return TFREC_AMD_OK;
 }
 
-// What the three constructors share behind their own argument checks: the input's format, its rate p / q (resamp: through the
-// resampling stage; ingest: another format at the base rate) and the context made for it
-// dc_k != 0: with the DC blocker over at most dc_rows rows (tfrec_amd_create_dc); iq_k != 0: with the IQ balancer over as many
-// (tfrec_amd_create_iq), behind the blocker or -- dc_k == 0 -- without one
-static int create_with(const tfrec_amd_config *cfg, int32_t fmt, int32_t p, int32_t q, bool resamp, bool ingest, tfrec_amd_ctx **out,
-		       int32_t dc_k = 0, int32_t dc_rows = 0, bool decimated = false, int32_t iq_k = 0)
+// What a constructor asks for behind its own argument checks: the format of the input rows and their rate p / q; decimated: the
+// channel-rate input (tfrec_amd_create_decimated); dc_k, iq_k != 0: with the DC blocker, the IQ balancer or both over at most `rows`
+// input rows (tfrec_amd_create_dc, tfrec_amd_create_iq)
+struct InputSpec {
+	int32_t fmt = TFREC_AMD_FMT_U8, p = 1, q = 1;
+	bool decimated = false;
+	int32_t dc_k = 0, iq_k = 0, rows = 0;
+};
+
+// The context made for an input.  Its pre-stage follows from the rate and from the format it reads (pre_fmt: S16, the corrected
+// rows, behind a correction stage): the resampling stage at another rate (resamp), the conversion of another format at the base
+// rate (ingest), none for u8 at the base rate or the channel-rate input.
+static int create_with(const tfrec_amd_config *cfg, const InputSpec &in, tfrec_amd_ctx **out)
 {
 	TRY(validate(cfg));
 	HIPCHK(hipSetDevice(cfg->device));
@@ -726,25 +723,18 @@ static int create_with(const tfrec_amd_config *cfg, int32_t fmt, int32_t p, int3
 	if (!c)
 		return TFREC_AMD_E_NOMEM;
 	c->cfg = *cfg;
-	c->fmt = c->pre_fmt = fmt;
-	if (dc_k) {  // the pre-stage reads the corrected rows
-		c->pre_fmt = TFREC_AMD_FMT_S16;
-		c->dc.on = true;
-		c->dc.k = dc_k;
-		c->dc.rows = dc_rows;
-	}
-	if (iq_k) {
-		c->pre_fmt = TFREC_AMD_FMT_S16;
-		c->iq.on = true;
-		c->iq.k = iq_k;
-		c->iq.rows = dc_rows;
-	}
+	c->fmt = in.fmt;
+	c->pre_fmt = in.dc_k || in.iq_k ? TFREC_AMD_FMT_S16 : in.fmt;
+	c->fix.dc.k = in.dc_k;
+	c->fix.iq.k = in.iq_k;
+	c->fix.rows = in.rows;
+	const bool base = in.p == 1 && in.q == 1;
 	c->in10x = (cfg->flags & TFREC_AMD_F_INPUT_10X) != 0;
-	c->in_p = c->in10x ? 10 : p;
-	c->in_q = c->in10x ? 1 : q;
-	c->resamp = resamp;
-	c->ingest = ingest;
-	c->decin.on = decimated;
+	c->in_p = c->in10x ? 10 : in.p;
+	c->in_q = c->in10x ? 1 : in.q;
+	c->resamp = !base && !in.decimated;
+	c->ingest = base && c->pre_fmt != TFREC_AMD_FMT_U8 && !in.decimated;
+	c->decin.on = in.decimated;
 	const int rc = init_context(c);
 	if (rc != TFREC_AMD_OK) {
 		tfrec_amd_destroy(c);
@@ -759,7 +749,7 @@ int tfrec_amd_create(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
 	if (!cfg || !out)
 		return TFREC_AMD_E_INVAL;
 	*out = nullptr;
-	return create_with(cfg, TFREC_AMD_FMT_U8, 1, 1, false, false, out);
+	return create_with(cfg, InputSpec{}, out);
 }
 
 int tfrec_amd_resample_taps(int32_t rate_p, int32_t rate_q, int32_t *taps, int cap, int *n_taps_per_phase)
@@ -790,7 +780,27 @@ int tfrec_amd_create_rate(const tfrec_amd_config *cfg, int32_t rate_p, int32_t r
 		return TFREC_AMD_E_INVAL;
 	}
 	TRY(tfrec_amd_resample_taps(rate_p, rate_q, nullptr, 0, nullptr));
-	return create_with(cfg, TFREC_AMD_FMT_U8, rate_p, rate_q, true, false, out);
+	return create_with(cfg, InputSpec{ .p = rate_p, .q = rate_q }, out);
+}
+
+// What the constructors that take a format share: a known format, no 10:1 stage behind it (what: the stage that refuses the flag, or
+// nullptr, the format itself), and a rate the resampling stage takes
+static int check_input(const tfrec_amd_config *cfg, int32_t format, int32_t rate_p, int32_t rate_q, const char *what)
+{
+	if (format < TFREC_AMD_FMT_U8 || format > TFREC_AMD_FMT_F32) {
+		snprintf(g_err, sizeof(g_err), "unknown input format %d", (int)format);
+		return TFREC_AMD_E_INVAL;
+	}
+	if (cfg->flags & TFREC_AMD_F_INPUT_10X) {
+		if (what)
+			snprintf(g_err, sizeof(g_err), "no %s ahead of the 10:1 stage: the 15.36 MS/s input flag is refused", what);
+		else
+			snprintf(g_err, sizeof(g_err), "the 15.36 MS/s input flag takes u8 input only");
+		return TFREC_AMD_E_INVAL;
+	}
+	if (rate_p != 1 || rate_q != 1)
+		TRY(tfrec_amd_resample_taps(rate_p, rate_q, nullptr, 0, nullptr));
+	return TFREC_AMD_OK;
 }
 
 int tfrec_amd_create_format(const tfrec_amd_config *cfg, int32_t format, int32_t rate_p, int32_t rate_q, tfrec_amd_ctx **out)
@@ -798,20 +808,10 @@ int tfrec_amd_create_format(const tfrec_amd_config *cfg, int32_t format, int32_t
 	if (!cfg || !out)
 		return TFREC_AMD_E_INVAL;
 	*out = nullptr;
-	const bool base = rate_p == 1 && rate_q == 1;
-	if (format < TFREC_AMD_FMT_U8 || format > TFREC_AMD_FMT_F32) {
-		snprintf(g_err, sizeof(g_err), "unknown input format %d", (int)format);
-		return TFREC_AMD_E_INVAL;
-	}
 	if (format == TFREC_AMD_FMT_U8)  // exactly the older constructors
-		return base ? tfrec_amd_create(cfg, out) : tfrec_amd_create_rate(cfg, rate_p, rate_q, out);
-	if (cfg->flags & TFREC_AMD_F_INPUT_10X) {
-		snprintf(g_err, sizeof(g_err), "the 15.36 MS/s input flag takes u8 input only");
-		return TFREC_AMD_E_INVAL;
-	}
-	if (!base)
-		TRY(tfrec_amd_resample_taps(rate_p, rate_q, nullptr, 0, nullptr));
-	return create_with(cfg, format, rate_p, rate_q, !base, base, out);
+		return rate_p == 1 && rate_q == 1 ? tfrec_amd_create(cfg, out) : tfrec_amd_create_rate(cfg, rate_p, rate_q, out);
+	TRY(check_input(cfg, format, rate_p, rate_q, nullptr));
+	return create_with(cfg, InputSpec{ .fmt = format, .p = rate_p, .q = rate_q }, out);
 }
 
 int tfrec_amd_get_input_format(tfrec_amd_ctx *c, int32_t *format)

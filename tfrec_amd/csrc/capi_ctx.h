@@ -122,39 +122,33 @@ struct OccupancyOut {
 	uint32_t *d_bits[kSets] = {};
 };
 
-// tfrec_amd_create_dc: K, the rows a submit may use, the largest submit's samples per row and windows; per context
-// a submit's sums ([rows][win_stride]), the ring ([rows][K]) and the rows' {m, head}; per set the table of d ([rows][win_stride]) and
-// the corrected rows (x_stride bytes each, int16 x' << 2) the pre-stage reads, and what the set's submit held.  reset_*: the rows
-// tfrec_amd_reset_dc_rows marked since the last submit (each once).
-struct DcBlock {
-	bool on = false;
-	int k = 0, rows = 0, win_stride = 0;
-	size_t x_stride = 0;
-	int2 *d_sums = nullptr, *d_ring = nullptr, *d_state = nullptr;
-	uint32_t *d_d[kSets] = {};
-	uint8_t *d_x[kSets] = {};
-	int set_rows[kSets] = {}, set_windows[kSets] = {};
+// One estimator of the input correction: K (0: the context has no such stage), the ring ([rows][K]) and the rows' {m, head}; per set
+// the table of its estimates ([rows][win_stride] int16 pairs: d, or (t, g)).  reset_*: the rows its reset call marked since the last
+// submit (each once).
+template <class Ring>
+struct Estimator {
+	int k = 0;
+	Ring *d_ring = nullptr;
+	int2 *d_state = nullptr;
+	uint32_t *d_table[kSets] = {};
 	std::vector<int32_t> reset_pending;
 	std::vector<uint8_t> reset_marked;
 };
-
-// tfrec_amd_create_iq: K, the rows a submit may use and the windows of the largest submit; per context a submit's
-// five raw sums ([rows][win_stride], kIqSumsBytes each) and moments (kIqMomentsBytes each), the ring of moments ([rows][K]) and the
-// rows' {m, head}; per set the table of (t, g) ([rows][win_stride]) and the corrected rows the pre-stage reads -- the DC blocker's
-// where the context has one (dc.on: its ring, state, table of d and rows are used as on a tfrec_amd_create_dc context; its sums
-// are not), the balancer's own otherwise.  reset_*: as the blocker's.
-constexpr size_t kIqSumsBytes = 32, kIqMomentsBytes = 24;  // (iqbal.h asserts them)
-struct IqBal {
-	bool on = false;
-	int k = 0, rows = 0, win_stride = 0;
+// tfrec_amd_create_dc / tfrec_amd_create_iq: the DC blocker, the IQ balancer, or the balancer behind the blocker,
+// ahead of the pre-stage.  The rows a submit may use, the largest submit's windows and samples per row (x_stride bytes); per set
+// the corrected rows (int16 x' << 2) the pre-stage reads and what the set's submit held; per context a submit's sums ([rows]
+// [win_stride]: the blocker's {S_I, S_Q}, the balancer's five) and the balancer's moments.
+struct InputCorrection {
+	int rows = 0, win_stride = 0;
 	size_t x_stride = 0;
-	void *d_sums = nullptr, *d_mom = nullptr, *d_ring = nullptr;
-	int2 *d_state = nullptr;
-	uint32_t *d_tg[kSets] = {};
 	uint8_t *d_x[kSets] = {};
 	int set_rows[kSets] = {}, set_windows[kSets] = {};
-	std::vector<int32_t> reset_pending;
-	std::vector<uint8_t> reset_marked;
+	Estimator<int2> dc;
+	Estimator<IqMoments> iq;
+	int2 *d_dc_sums = nullptr;
+	IqSums *d_iq_sums = nullptr;
+	IqMoments *d_mom = nullptr;
+	bool on() const { return dc.k || iq.k; }
 };
 
 struct tfrec_amd_ctx {
@@ -248,12 +242,12 @@ struct tfrec_amd_ctx {
 	// tfrec_amd_create_format: fmt is the TFREC_AMD_FMT_* of the input rows, 0 (U8) in every context of the older
 	// constructors.  A rate context with another format runs resample_fmt_kernel from a history of canonical x instead
 	// of the raw one; at the base rate (ingest: rate 1/1, no resampler) ingest_kernel converts the rows into d_in16.
-	// tfrec_amd_create_dc keeps two formats: fmt stays the caller's (input_bytes, submit_host's staging, the spectrum), pre_fmt is
-	// what the pre-stage reads -- S16, the corrected rows (dc) -- and what its history is kept in; everywhere else pre_fmt == fmt.
+	// A context with an input correction keeps two formats: fmt stays the caller's (input_bytes, submit_host's staging, the
+	// spectrum), pre_fmt is what the pre-stage reads -- S16, the corrected rows (fix) -- and what its history is kept in; everywhere
+	// else pre_fmt == fmt.
 	int32_t fmt = TFREC_AMD_FMT_U8, pre_fmt = TFREC_AMD_FMT_U8;
 	bool ingest = false;
-	DcBlock dc;
-	IqBal iq;  // tfrec_amd_create_iq: the balancer behind (or without) the blocker; pre_fmt is S16 as with dc
+	InputCorrection fix;
 	// ---- window-parallel pipeline (make_window_state).  One set per submit in flight, like the front-end outputs: the window
 	// scan and the biquads of submit k+1 fill theirs while the slicers of submit k still read the other
 	int16_t *d_ld16[kSets] = {};   // [chains][m_max] tfa2-family biquad outputs

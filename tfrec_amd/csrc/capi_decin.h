@@ -12,7 +12,7 @@ int tfrec_amd_create_decimated(const tfrec_amd_config *cfg, tfrec_amd_ctx **out)
 		return TFREC_AMD_E_INVAL;
 	}
 	// 384 kS/s = 1536000 * 1 / 4, four bytes per pair: tfrec_amd_input_bytes gives n_blocks * 32768
-	return create_with(cfg, TFREC_AMD_FMT_DEC16, 1, 4, false, false, out, 0, 0, true);
+	return create_with(cfg, InputSpec{ .fmt = TFREC_AMD_FMT_DEC16, .p = 1, .q = 4, .decimated = true }, out);
 }
 
 int tfrec_amd_enable_capture_pre(tfrec_amd_ctx *c)

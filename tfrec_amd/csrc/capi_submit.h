@@ -209,66 +209,46 @@ static int launch_prestage(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, size_
 	return TFREC_AMD_OK;
 }
 
-// tfrec_amd_create_dc: a submit may use at most max_rows input rows (checked before anything is queued)
-static int check_dc_rows(const tfrec_amd_ctx *c)
+// tfrec_amd_create_dc, tfrec_amd_create_iq: a submit may use at most max_rows input rows (checked before anything is queued)
+static int check_correct_rows(const tfrec_amd_ctx *c)
 {
-	if (!c->dc.on || rows_in_use(c) <= c->dc.rows)
+	const InputCorrection &o = c->fix;
+	if (!o.on() || rows_in_use(c) <= o.rows)
 		return TFREC_AMD_OK;
-	snprintf(g_err, sizeof(g_err), "the submit uses %d input rows, the DC blocker was made for %d", rows_in_use(c), c->dc.rows);
+	snprintf(g_err, sizeof(g_err), "the submit uses %d input rows, the %s was made for %d", rows_in_use(c), o.iq.k ? "IQ balancer" : "DC blocker",
+		 o.rows);
 	return TFREC_AMD_E_INVAL;
 }
 
-// The DC blocker on the set's front-end stream, ahead of the pre-stage: the rows marked by tfrec_amd_reset_dc_rows
-// start again (m = head = 0), then the three kernels correct the submit's rows into the set's buffer.  The context's sums, ring
-// and state are ordered from submit to submit by the stream.
-static int launch_dc_rows(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, size_t stride, long n_in)
+// the rows an estimator's reset call marked start again: m = head = 0
+template <class Ring>
+static int start_marked_rows(Estimator<Ring> &e, hipStream_t fs)
 {
-	DcBlock &o = c->dc;
-	hipStream_t fs = c->pipe[set].fs;
-	for (int32_t r : o.reset_pending) {
-		HIPCHK(hipMemsetAsync(o.d_state + r, 0, sizeof(int2), fs));
-		o.reset_marked[r] = 0;
+	for (int32_t r : e.reset_pending) {
+		HIPCHK(hipMemsetAsync(e.d_state + r, 0, sizeof(int2), fs));
+		e.reset_marked[r] = 0;
 	}
-	o.reset_pending.clear();
-	const int rows = rows_in_use(c);
-	HIPCHK(launch_dc(fs, c->fmt, d_iq, stride, rows, n_in, o.k, o.d_sums, o.win_stride, o.d_ring, o.d_state, o.d_d[set], o.d_x[set],
-			 o.x_stride));
-	o.set_rows[set] = rows;
-	o.set_windows[set] = (int)(n_in / 512);
+	e.reset_pending.clear();
 	return TFREC_AMD_OK;
 }
 
-// tfrec_amd_create_iq: as check_dc_rows
-static int check_iq_rows(const tfrec_amd_ctx *c)
+// The input correction on the set's front-end stream, ahead of the pre-stage: the rows marked by
+// tfrec_amd_reset_dc_rows or tfrec_amd_reset_iq_rows start again in that estimator, then the three kernels correct the submit's
+// rows into the set's buffer.  The context's sums, moments, rings and states are ordered from submit to submit by the stream.
+static int launch_correct_rows(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, size_t stride, long n_in)
 {
-	if (!c->iq.on || rows_in_use(c) <= c->iq.rows)
-		return TFREC_AMD_OK;
-	snprintf(g_err, sizeof(g_err), "the submit uses %d input rows, the IQ balancer was made for %d", rows_in_use(c), c->iq.rows);
-	return TFREC_AMD_E_INVAL;
-}
-
-// The IQ balancer in the place of launch_dc_rows: the rows marked by either reset call start again, then the three
-// kernels -- which do the DC blocker's work too where the context has one -- correct the submit's rows into the set's buffer.
-static int launch_iq_rows(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, size_t stride, long n_in)
-{
-	IqBal &o = c->iq;
-	DcBlock &b = c->dc;
+	InputCorrection &o = c->fix;
 	hipStream_t fs = c->pipe[set].fs;
-	for (int32_t r : b.reset_pending) {
-		HIPCHK(hipMemsetAsync(b.d_state + r, 0, sizeof(int2), fs));
-		b.reset_marked[r] = 0;
-	}
-	b.reset_pending.clear();
-	for (int32_t r : o.reset_pending) {
-		HIPCHK(hipMemsetAsync(o.d_state + r, 0, sizeof(int2), fs));
-		o.reset_marked[r] = 0;
-	}
-	o.reset_pending.clear();
+	TRY(start_marked_rows(o.dc, fs));
+	TRY(start_marked_rows(o.iq, fs));
 	const int rows = rows_in_use(c);
-	HIPCHK(launch_iq(fs, c->fmt, d_iq, stride, rows, n_in, o.d_sums, o.win_stride, b.on ? b.k : 0, b.d_ring, b.d_state, b.d_d[set], o.d_mom,
-			 o.k, o.d_ring, o.d_state, o.d_tg[set], o.d_x[set], o.x_stride));
-	o.set_rows[set] = b.set_rows[set] = rows;
-	o.set_windows[set] = b.set_windows[set] = (int)(n_in / 512);
+	const CorrectBufs b = { .dc_k = o.dc.k, .iq_k = o.iq.k, .win_stride = o.win_stride,
+				.dc_sums = o.d_dc_sums, .iq_sums = o.d_iq_sums, .mom = o.d_mom,
+				.dc_ring = o.dc.d_ring, .dc_state = o.dc.d_state, .iq_ring = o.iq.d_ring, .iq_state = o.iq.d_state,
+				.d = o.dc.d_table[set], .tg = o.iq.d_table[set], .out = o.d_x[set], .out_stride = o.x_stride };
+	HIPCHK(launch_correct(fs, c->fmt, d_iq, stride, rows, n_in, b));
+	o.set_rows[set] = rows;
+	o.set_windows[set] = (int)(n_in / 512);
 	return TFREC_AMD_OK;
 }
 
@@ -307,8 +287,7 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		snprintf(g_err, sizeof(g_err), "IQ base and stream stride must be 16-byte aligned and >= one stream");
 		return TFREC_AMD_E_INVAL;
 	}
-	TRY(check_iq_rows(c));
-	TRY(check_dc_rows(c));
+	TRY(check_correct_rows(c));
 	TRY(check_fifo(c));
 	TRY(check_live(c));
 	HIPCHK(hipSetDevice(c->cfg.device));
@@ -361,14 +340,10 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	if (c->in16) {  // ... then the standard cascade on int16 input
 		const uint8_t *pin = (const uint8_t *)d_iq;
 		size_t pstride = stride;
-		if (c->iq.on) {  // the IQ balancer (with the DC blocker's work in it) first: the pre-stage reads the corrected rows
-			TRY(launch_iq_rows(c, set, pin, stride, (long)(row_bytes / fmt_sample_bytes(c->fmt))));
-			pin = c->iq.d_x[set];
-			pstride = c->iq.x_stride;
-		} else if (c->dc.on) {  // the DC blocker first: the pre-stage reads the corrected rows, an S16 input
-			TRY(launch_dc_rows(c, set, pin, stride, (long)(row_bytes / fmt_sample_bytes(c->fmt))));
-			pin = c->dc.d_x[set];
-			pstride = c->dc.x_stride;
+		if (c->fix.on()) {  // the input correction first: the pre-stage reads the corrected rows, an S16 input
+			TRY(launch_correct_rows(c, set, pin, stride, (long)(row_bytes / fmt_sample_bytes(c->fmt))));
+			pin = c->fix.d_x[set];
+			pstride = c->fix.x_stride;
 		}
 		TRY(launch_prestage(c, set, pin, pstride, n_blocks, chan10 ? c->d_chan[set] : nullptr));
 		fin = (const uint8_t *)c->d_in16[set];
@@ -483,8 +458,7 @@ static int submit_host_impl(tfrec_amd_ctx *c, const uint8_t *h_iq, size_t stride
 	TRY(input_bytes(c, n_blocks, &row));
 	if (rows_in_use(c) > 1 && stride < row)
 		return TFREC_AMD_E_INVAL;
-	TRY(check_iq_rows(c));
-	TRY(check_dc_rows(c));
+	TRY(check_correct_rows(c));
 	TRY(check_fifo(c));
 	HIPCHK(hipSetDevice(c->cfg.device));
 	const int set = (c->head + c->inflight) % kSets;  // the set's previous user has been drained: its staging buffer is free

@@ -845,8 +845,7 @@ hipError_t launch_fmdev(hipStream_t st, const uint32_t *dec, size_t dec_stride, 
 
 #include "resample.h"  // resample_kernel, launch_resample
 #include "formats.h"   // resample_fmt_kernel, ingest_kernel and their launchers
-#include "dcblock.h"   // dc_sums_kernel, dc_estimate_kernel, dc_apply_kernel, launch_dc
-#include "iqbal.h"     // iq_sums_kernel, iq_estimate_kernel, iq_apply_kernel, launch_iq
+#include "correct.h"   // correct_sums_kernel, correct_estimate_kernel, correct_apply_kernel, launch_correct
 #include "levels.h"    // level_sum_kernel, level_trig_kernel, launch_levels
 #include "capture.h"   // capture_scan_kernel, capture_offsets_kernel, capture_copy_kernel, launch_capture
 #include "spectrum.h"  // spectrum_kernel, launch_spectrum

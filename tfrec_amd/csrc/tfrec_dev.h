@@ -202,6 +202,30 @@ struct CaptureHeader {
 	unsigned long long n_runs, n_pairs;
 };
 
+// The input correction (correct.h): what the IQ balancer keeps of a 512-sample window
+struct IqSums {  // a window's five raw sums
+	int si, sq;
+	long long mii, mqq, miq;
+};
+struct IqMoments {  // a window's A, B, C
+	long long a, b, c;
+};
+static_assert(sizeof(IqSums) == 32 && sizeof(IqMoments) == 24, "the balancer's ring stays 24-byte triples");
+// What launch_correct works on.  dc_k, iq_k: the estimators' K (0: the context has no such stage; its pointers are not used).  The
+// sums are the blocker's {S_I, S_Q} (dc_sums) in a context without the balancer, the balancer's five (iq_sums) otherwise.
+struct CorrectBufs {
+	int dc_k, iq_k, win_stride;
+	int2 *dc_sums;
+	IqSums *iq_sums;
+	IqMoments *mom;
+	int2 *dc_ring, *dc_state;
+	IqMoments *iq_ring;
+	int2 *iq_state;
+	uint32_t *d, *tg;  // the set's tables of {d_I, d_Q} and {t, g}: [rows][win_stride]
+	uint8_t *out;      // the set's corrected rows, out_stride bytes each
+	size_t out_stride;
+};
+
 // fm_dev samples decided by the exact slow path (fm_resolve.h): logged so that the host can check them against its
 // own libm when the batch is drained (capi.hip)
 struct FmLogEntry {

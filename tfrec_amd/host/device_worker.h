@@ -50,8 +50,10 @@ private:
 	int submit_runs(size_t k);
 	int collect(size_t k, batch_result &b);
 	int read_captures(size_t k, batch_result &b);
-	int read_dc(size_t k, batch_result &b);
-	int read_iq(size_t k, batch_result &b);
+	typedef int (*estimate_reader)(tfrec_amd_ctx *, int32_t, int16_t *, size_t, int *);
+	int read_last_estimate(size_t k, estimate_reader reader, std::vector<int> &files, std::vector<int16_t> &last);
+	int read_dc(size_t k, batch_result &b) { return read_last_estimate(k, tfrec_amd_read_dc, b.dc_file, b.dc_last); }  // -z -D
+	int read_iq(size_t k, batch_result &b) { return read_last_estimate(k, tfrec_amd_read_iq, b.iq_file, b.iq_last); }  // -Z -D
 	int close_context(int r);
 
 	const job_settings &job;
@@ -427,46 +429,23 @@ inline int device_worker::read_captures(size_t k, batch_result &b)
 	return 0;
 }
 
-// -z -D: the last estimate of every file's row
-inline int device_worker::read_dc(size_t k, batch_result &b)
+// -z -D, -Z -D: the last estimate of every file's row -- d, or (t, g) -- by the stage's reader
+inline int device_worker::read_last_estimate(size_t k, estimate_reader reader, std::vector<int> &files, std::vector<int16_t> &last)
 {
-	std::vector<int16_t> d;
+	std::vector<int16_t> e;
 	int r = 0;
 	for (size_t s = 0; s < n && r == 0; s++) {
 		if (plan[k].file[s] < 0 || !reads[s])
 			continue;
 		int nw = 0;
-		r = tfrec_amd_read_dc(ctx, in_row[s], NULL, 0, &nw);  // (the count: E_INVAL for want of room)
+		r = reader(ctx, in_row[s], NULL, 0, &nw);  // (the count: E_INVAL for want of room)
 		if (r == TFREC_AMD_E_INVAL && nw > 0) {
-			d.resize(2 * (size_t)nw);
-			r = tfrec_amd_read_dc(ctx, in_row[s], d.data(), (size_t)nw, &nw);
+			e.resize(2 * (size_t)nw);
+			r = reader(ctx, in_row[s], e.data(), (size_t)nw, &nw);
 			if (r == 0) {
-				b.dc_file.push_back(plan[k].file[s]);
-				b.dc_last.push_back(d[2 * (size_t)nw - 2]);
-				b.dc_last.push_back(d[2 * (size_t)nw - 1]);
-			}
-		}
-	}
-	return r;
-}
-
-// -Z -D: the last (t, g) of every file's row
-inline int device_worker::read_iq(size_t k, batch_result &b)
-{
-	std::vector<int16_t> tg;
-	int r = 0;
-	for (size_t s = 0; s < n && r == 0; s++) {
-		if (plan[k].file[s] < 0 || !reads[s])
-			continue;
-		int nw = 0;
-		r = tfrec_amd_read_iq(ctx, in_row[s], NULL, 0, &nw);  // (the count: E_INVAL for want of room)
-		if (r == TFREC_AMD_E_INVAL && nw > 0) {
-			tg.resize(2 * (size_t)nw);
-			r = tfrec_amd_read_iq(ctx, in_row[s], tg.data(), (size_t)nw, &nw);
-			if (r == 0) {
-				b.iq_file.push_back(plan[k].file[s]);
-				b.iq_last.push_back(tg[2 * (size_t)nw - 2]);
-				b.iq_last.push_back(tg[2 * (size_t)nw - 1]);
+				files.push_back(plan[k].file[s]);
+				last.push_back(e[2 * (size_t)nw - 2]);
+				last.push_back(e[2 * (size_t)nw - 1]);
 			}
 		}
 	}
