@@ -87,17 +87,20 @@ def scene():
 
 
 def want_tables(decs, states):
-    """The restatement on one submit's decimated samples -> (table, pool); states: each stream's carried state, updated."""
+    """The restatement on one submit's decimated samples -> (table, pool); states: each stream's carried state, updated.  Stream s
+    has the settings of the scene's row s mod N."""
     per = []
     for s, d in enumerate(decs):
-        runs, pool, states[s] = capture.captures(d, TYPES[s], THRESH[s], states[s])
+        runs, pool, states[s] = capture.captures(d, TYPES[s % N], THRESH[s % N], states[s])
         per.append((runs, pool))
     return capture.table(per)
 
 
-def receiver(max_blocks=NB, cap=(4096, N * M), **kw):
-    r = api.Receiver(N, CTX_TYPES, 500, 0, max_blocks=max_blocks, all_flushes=True, **kw)
-    r.configure_streams([2, 6, 7], types_mask=[TYPES[2], TYPES[6], TYPES[7]], thresh=[THRESH[2], THRESH[6], THRESH[7]])
+def receiver(max_blocks=NB, cap=(4096, N * M), n=N, **kw):
+    """n > N: stream s is set up for the scene's row s mod N."""
+    r = api.Receiver(n, CTX_TYPES, 500, 0, max_blocks=max_blocks, all_flushes=True, **kw)
+    own = [s for s in range(n) if s % N in (2, 6, 7)]
+    r.configure_streams(own, types_mask=[TYPES[s % N] for s in own], thresh=[THRESH[s % N] for s in own])
     if cap:
         r.enable_capture(*cap)
     return r
