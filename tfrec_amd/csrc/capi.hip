@@ -8,62 +8,12 @@
 #include <chrono>
 #include <functional>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "knobs.h"
 #include "tfrec_dev.h"
-
-namespace tfrec {
-hipError_t launch_decim10(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks,
-			  const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride, const uint4 *chan);
-hipError_t launch_resample(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, int p, int q, int t,
-			   const float *taps, const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride,
-			   const uint4 *chan, bool tuned);
-hipError_t launch_resample_fmt(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, int p, int q, int t,
-			       const float *taps, const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride,
-			       const uint4 *chan, bool tuned);
-hipError_t launch_ingest(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, uint32_t *out,
-			 size_t out_stride, const uint4 *chan);
-hipError_t launch_frontend(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks,
-			   const uint8_t *tail_in, uint8_t *tail_out, uint32_t *dec, size_t dec_stride,
-			   unsigned long long *mask, size_t mask_stride, uint32_t *prevdec, int thresh, const FrontTapsCfg &taps,
-			   bool in16, const uint2 *tune, const uint4 *chan);
-hipError_t launch_fmdev(hipStream_t st, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask,
-			size_t mask_stride, const uint32_t *prevdec, int16_t *fmdev, size_t fmdev_stride, EventBuf *eb,
-			int n_streams, int n_blocks, int wmax, double flag_eps);
-hipError_t launch_pipeline(const PipeCtl &P, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask,
-			   size_t mask_stride, const int16_t *fmdev, size_t fmdev_stride, int n_streams, int n_blocks,
-			   long long sample_base, const ChainLaunch &L, const WinTables &T, int16_t *ld16, int32_t *dev32,
-			   tfrec_amd_event *events, EventBuf *eb, uint32_t flags);
-hipError_t whb_chain_lds_optin();
-hipError_t launch_fm_probe(hipStream_t st, const int32_t *quads, size_t n, int32_t *out, EventBuf *eb, int kind);
-hipError_t launch_iir_probe(hipStream_t st, const double *in, size_t n, const BiquadCoef &c, double *out, int form);
-hipError_t launch_threshold(hipStream_t st, const uint32_t *dec, size_t dec_stride, unsigned long long *mask,
-			    size_t mask_stride, int n_streams, int n_blocks, FskState *fsk, int wmax, const StreamCfg *scfg);
-hipError_t launch_chains(hipStream_t st, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask,
-			 size_t mask_stride, int n_streams, int n_blocks, long long sample_base, const ChainLaunch &L,
-			 tfrec_amd_event *events, EventBuf *eb, uint32_t flags);
-hipError_t launch_levels(hipStream_t st, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask, size_t mask_stride,
-			 int n_streams, int n_blocks, LevelState *lev, const StreamCfg *scfg, tfrec_amd_level *out);
-hipError_t launch_capture(hipStream_t st, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask, size_t mask_stride,
-			  int n_streams, int n_blocks, long long sample_base, CaptureState *cst, const StreamCfg *scfg, CaptureStage *stage,
-			  int stage_cap, uint2 *cnt, uint4 *base, CaptureHeader *hdr, tfrec_amd_run *runs, uint32_t max_runs, uint32_t *pool,
-			  unsigned long long max_samples);
-hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_rows, long n_in, int n_bins, int g,
-			   size_t max_records, unsigned long long *sum, unsigned long long *peak, uint32_t *nfr);
-hipError_t launch_occupancy(hipStream_t st, int n_rows, long n_in, int n_bins, int g, size_t max_records, const unsigned long long *sum,
-			    const unsigned long long *peak, const uint32_t *nfr, uint32_t ratio, uint32_t rel, tfrec_amd_occupancy *recs,
-			    uint32_t *bits);
-hipError_t launch_correct(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_rows, long n_in, const CorrectBufs &b);
-hipError_t launch_decin(hipStream_t st, const uint8_t *in, size_t stride, int n_streams, int n_blocks, const uint4 *chan, uint32_t *dec,
-			size_t dec_stride, unsigned long long *mask, size_t mask_stride, uint32_t *prevdec, uint32_t *last, int thresh,
-			const StreamCfg *scfg);
-hipError_t launch_decin_runs(hipStream_t st, int n_streams, int n_blocks, const uint4 *tab, const uint32_t *pool, const uint32_t *pre,
-			     const int32_t *first, const uint2 *ov, uint32_t *dec, size_t dec_stride, unsigned long long *mask,
-			     size_t mask_stride, uint32_t *prevdec, uint32_t *last, int thresh, const StreamCfg *scfg);
-hipError_t launch_capture_pre(hipStream_t st, const tfrec_amd_run *runs, const CaptureHeader *hdr, uint32_t max_runs, long long sample_base,
-			      const uint32_t *dec, size_t dec_stride, const uint32_t *prevdec, uint32_t *pre);
-}  // namespace tfrec
+#include "launch.h"  // every launch_* of frontend.hip, chains.hip and chains2.hip, and the records they take (FrontOut, History, ...)
 
 using namespace tfrec;
 

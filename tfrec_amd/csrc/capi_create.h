@@ -379,67 +379,40 @@ static int make_win_tables(tfrec_amd_ctx *c, int set)
 		TRY(own_device(c, c->d_dev32[set], n * (size_t)T.slots * 32 * sizeof(int32_t) + 4096));
 	T.bit_words = (int32_t)(m_max / 64 + 3 * (size_t)T.cap + 8);
 	const size_t wins = chains * (size_t)T.cap;
-	size_t off = 0;
-	auto carve = [&](size_t bytes) {
-		const size_t o = off;
-		off += (bytes + 255) & ~(size_t)255;
-		return o;
-	};
-	const size_t o_count = carve(chains * 4), o_cont = carve(chains * 4), o_tnext = carve(chains * 4);
-	const size_t o_open = carve(wins * 4), o_close = carve(wins * 4), o_res = carve(wins * sizeof(WinResult));
-	const size_t o_dcd = carve(wins * sizeof(WinDecode)), o_wst = carve(whb ? n * (size_t)T.cap * sizeof(WhbStart) : 0);
-	const size_t o_bits = carve(chains * (size_t)T.bit_words * 4), o_items = carve((kNQueues * wins + chains) * sizeof(uint2));
-	const size_t o_queue = carve((kNQueues + 1) * sizeof(WorkQueue)), o_stats = carve(128);
 	T.segcap = (int32_t)((m_max / 32 + (size_t)T.cap) / kSegSlots + 2);
 	const size_t segs = chains * (size_t)T.segcap;
-	const size_t o_ckpt = carve(ck_chains * (size_t)T.slots * sizeof(double2));
-	const size_t o_sstart = carve(segs * sizeof(uint2)), o_vtotal = carve(chains * 4);
-	const size_t o_se1 = carve(segs * sizeof(BiquadEnd)), o_se2 = carve(segs * sizeof(BiquadEnd)), o_sfix = carve(segs * 4);
-	const size_t o_se3 = carve(segs * sizeof(BiquadEnd)), o_sfix2 = carve(segs * 4);
-	const size_t o_cand = carve(n * (size_t)T.slots * 4), o_mark = carve(n * (size_t)T.slots * sizeof(MarkPiece));
 	T.whbrec_stride = (int32_t)(m_max / 64 + 2 * (size_t)T.cap + 2 + kWhbRecSlack);
-	const size_t o_wrec = carve(whb ? n * (size_t)T.whbrec_stride * sizeof(WhbStepRec) : 0), o_wfail = carve(whb ? n * 4 : 0);
-	const size_t o_wsnap = carve(whb ? n * sizeof(ChainState) : 0), o_wx0 = carve(whb ? n * sizeof(WhbExact) : 0);
-	const size_t o_wseen = carve(whb ? n * 4 : 0);
 	T.whbdense_stride = (int32_t)(m_max + 64);
 	T.whbx_stride = (int32_t)(m_max / 64 + 2);
-	const size_t o_wdn = carve(whb ? n * 4 : 0), o_wxb = carve(whb ? n * (size_t)T.whbx_stride * 8 : 0);
-	const size_t o_wxs = carve(whb ? n * (size_t)T.whbx_stride * sizeof(double2) : 0);
-	const size_t o_wdense = carve(whb ? n * (size_t)T.whbdense_stride * 4 : 0);
-	TRY(own_device(c, c->win_block[set], off));
-	uint8_t *b = (uint8_t *)c->win_block[set];
-	T.count = (int32_t *)(b + o_count);
-	T.cont = (int32_t *)(b + o_cont);
-	T.timeout_next = (int32_t *)(b + o_tnext);
-	T.open = (int32_t *)(b + o_open);
-	T.close = (int32_t *)(b + o_close);
-	T.result = (WinResult *)(b + o_res);
-	T.decode = (WinDecode *)(b + o_dcd);
-	T.whbstart = (WhbStart *)(b + o_wst);
-	T.bits = (uint32_t *)(b + o_bits);
-	T.items = (uint2 *)(b + o_items);
-	T.queue = (WorkQueue *)(b + o_queue);
+	const size_t nw = whb ? n : 0;  // rows of the WHB arrays
+	// The arrays of one block in this order, `count` elements each and rounded up to 256 bytes: laid out once without a base
+	// for the block's size, once more on the block
+	auto layout = [&](uintptr_t base) {
+		size_t off = 0;
+		auto carve = [&](size_t count, auto *&...p) {
+			((p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + off), off += (count * sizeof(*p) + 255) & ~(size_t)255), ...);
+		};
+		carve(chains, T.count, T.cont, T.timeout_next);
+		carve(wins, T.open, T.close, T.result, T.decode);
+		carve(nw * (size_t)T.cap, T.whbstart);
+		carve(chains * (size_t)T.bit_words, T.bits);
+		carve(kNQueues * wins + chains, T.items);
+		carve(kNQueues + 1, T.queue);
+		carve(16, T.stats);
+		carve(ck_chains * (size_t)T.slots, T.ckpt);
+		carve(segs, T.segstart);
+		carve(chains, T.vtotal);
+		carve(segs, T.segend1, T.segend2, T.segfix, T.segend3, T.segfix2);
+		carve(n * (size_t)T.slots, T.cand, T.mark);
+		carve(nw * (size_t)T.whbrec_stride, T.whbrec);
+		carve(nw, T.whbfail, T.whbsnap, T.whbx0, T.whbseen, T.whbdense_n);
+		carve(nw * (size_t)T.whbx_stride, T.whbxbits, T.whbxsnap);
+		carve(nw * (size_t)T.whbdense_stride, T.whbdense);
+		return off;
+	};
+	TRY(own_device(c, c->win_block[set], layout(0)));
+	layout(reinterpret_cast<uintptr_t>(c->win_block[set]));
 	T.overflow = nullptr;  // lives in the set's event block (kEvOverflowOff): make_event_blocks, reset by every submit
-	T.stats = (unsigned long long *)(b + o_stats);
-	T.ckpt = (double2 *)(b + o_ckpt);
-	T.segstart = (uint2 *)(b + o_sstart);
-	T.vtotal = (int32_t *)(b + o_vtotal);
-	T.segend1 = (BiquadEnd *)(b + o_se1);
-	T.segend2 = (BiquadEnd *)(b + o_se2);
-	T.segfix = (int32_t *)(b + o_sfix);
-	T.segend3 = (BiquadEnd *)(b + o_se3);
-	T.segfix2 = (int32_t *)(b + o_sfix2);
-	T.cand = (uint32_t *)(b + o_cand);
-	T.mark = (MarkPiece *)(b + o_mark);
-	T.whbrec = (WhbStepRec *)(b + o_wrec);
-	T.whbfail = (int32_t *)(b + o_wfail);
-	T.whbsnap = (ChainState *)(b + o_wsnap);
-	T.whbx0 = (WhbExact *)(b + o_wx0);
-	T.whbseen = (uint32_t *)(b + o_wseen);
-	T.whbdense = (int32_t *)(b + o_wdense);
-	T.whbdense_n = (int32_t *)(b + o_wdn);
-	T.whbxbits = (unsigned long long *)(b + o_wxb);
-	T.whbxsnap = (double2 *)(b + o_wxs);
 	T.whbgen = c->d_whbgen;
 	T.whbX = c->d_whbX;
 	T.whbscr = c->d_whbscr;
@@ -630,7 +603,7 @@ static int make_streams(tfrec_amd_ctx *c, PipeCtl &S)
 	return TFREC_AMD_OK;
 }
 
-// every set's PipeCtl (the layout's streams, the set's events and buffers) and the set's other events
+// every set's PipeCtl (the layout's streams and the set's events) and the set's other events
 static int make_pipes(tfrec_amd_ctx *c, const PipeCtl &S)
 {
 	const bool serial = (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) != 0;
@@ -655,8 +628,6 @@ static int make_pipes(tfrec_amd_ctx *c, const PipeCtl &S)
 		P.whb_carry = c->d_whbcarry;
 		P.fmdev_wmax = c->fmdev_k2 ? c->wmax : 0;
 		P.fm_flag_eps = c->fm_flag_eps;
-		P.fmdev_out = c->d_fmdev[k];
-		P.prevdec = c->d_prevdec[k];
 	}
 	return TFREC_AMD_OK;
 }

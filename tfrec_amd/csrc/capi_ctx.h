@@ -166,8 +166,8 @@ struct tfrec_amd_ctx {
 	std::vector<Owned> owned;
 	size_t dev_bytes = 0, pinned_bytes = 0;  // tfrec_amd_get_memory
 	// ---- streams and events (make_streams: the layout and why; make_pipes)
-	// per set: what launch_pipeline takes for a submit of that set (the streams, the set's events and buffers); the serial
-	// layout uses its fs, cs, ev_front and done
+	// per set: what launch_pipeline takes for a submit of that set beside its FrontOut (the streams and the set's events); the
+	// serial layout uses its fs, cs, ev_front and done
 	PipeCtl pipe[kSets] = {};
 	hipStream_t cpy = nullptr;  // the drain's device-to-host copies
 	bool deep = false;          // deep layout

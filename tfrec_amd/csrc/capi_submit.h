@@ -78,6 +78,19 @@ __global__ __launch_bounds__(64) void stream_reset_kernel(StreamReset R)
 }
 }  // namespace tfrec
 
+// A carried history (d_tail, d_pre) flips per submit: [tail_sel] is what this submit reads -- and what its resets restore --,
+// [tail_sel ^ 1] what it writes for the next one
+static uint8_t *history_read(const tfrec_amd_ctx *c, uint8_t *const (&buf)[kSets]) { return buf[c->tail_sel]; }
+static History history(const tfrec_amd_ctx *c, uint8_t *const (&buf)[kSets]) { return { history_read(c, buf), buf[c->tail_sel ^ 1] }; }
+
+// The set's front-end output for a submit of n_blocks blocks: what the launchers from the front end to the chains work on
+static FrontOut front_out(const tfrec_amd_ctx *c, int set, int n_blocks)
+{
+	return { .dec = c->d_dec[set], .dec_stride = c->dec_stride, .mask = c->d_mask[set], .mask_stride = c->mask_stride,
+		 .prevdec = c->d_prevdec[set], .fmdev = c->d_fmdev[set], .fmdev_stride = c->dec_stride,
+		 .n_streams = c->cfg.n_streams, .n_blocks = n_blocks };
+}
+
 // The resets marked since the last submit, at the head of this submit's front end (fs).  Carried state is written by several
 // stages on several streams (a ChainState by the biquad stage, the slicers, the decoders' commit and the WHB check's redo), and
 // in the deep layout those of the submit before may still run while this one's front end does: the front-end stream first
@@ -105,10 +118,10 @@ static int launch_resets(tfrec_amd_ctx *c, int set)
 	R.list = c->d_reset[set];
 	R.n_list = nl;
 	R.n_streams = c->cfg.n_streams;
-	R.tail = c->d_tail[c->tail_sel];  // the buffer this submit's front end reads (the history flips per submit)
+	R.tail = history_read(c, c->d_tail);  // the buffer this submit's front end reads
 	R.tail_bytes = c->in16 ? 2 * kTailBytes : kTailBytes;
 	R.tail_fill = c->in16 ? 0 : 0x80;  // as make_front_buffers: int16 zero, or u8 128
-	R.pre = c->d_pre[c->tail_sel];
+	R.pre = history_read(c, c->d_pre);
 	R.pre_bytes = c->pre_bytes;
 	R.pre_fill = c->pre_fill;
 	R.fsk = c->d_fsk;
@@ -193,19 +206,15 @@ static int launch_prestage(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, size_
 {
 	hipStream_t fs = c->pipe[set].fs;
 	const int n = c->cfg.n_streams;
-	const uint8_t *hin = c->d_pre[c->tail_sel];
-	uint8_t *hout = c->d_pre[c->tail_sel ^ 1];
+	const History hist = history(c, c->d_pre);
 	uint32_t *out = c->d_in16[set];
 	if (c->in10x)  // 15.36 MS/s u8 -> 1.536 MS/s int16 pairs
-		HIPCHK(launch_decim10(fs, d_iq, stride, n, n_blocks, hin, hout, out, c->in16_stride, chan));
+		HIPCHK(launch_decim10(fs, d_iq, stride, n, n_blocks, hist, out, c->in16_stride, chan));
 	else if (c->ingest)  // 1.536 MS/s in another format -> x as int16 pairs
 		HIPCHK(launch_ingest(fs, c->pre_fmt, d_iq, stride, n, n_blocks, out, c->in16_stride, chan));
-	else if (c->pre_fmt != TFREC_AMD_FMT_U8)  // 1536000 P / Q S/s in another format: the format-aware resampling stage
-		HIPCHK(launch_resample_fmt(fs, c->pre_fmt, d_iq, stride, n, n_blocks, c->in_p, c->in_q, c->rate_t, c->d_rtaps, hin, hout, out,
-					   c->in16_stride, chan, c->n_wide != 0));
-	else  // 1536000 P / Q S/s u8 -> 1.536 MS/s int16 pairs
-		HIPCHK(launch_resample(fs, d_iq, stride, n, n_blocks, c->in_p, c->in_q, c->rate_t, c->d_rtaps, hin, hout, out, c->in16_stride,
-				       chan, c->n_wide != 0));
+	else  // 1536000 P / Q S/s in any format -> 1.536 MS/s int16 pairs
+		HIPCHK(launch_resample(fs, c->pre_fmt, d_iq, stride, n, n_blocks, { .p = c->in_p, .q = c->in_q, .t = c->rate_t, .taps = c->d_rtaps },
+				       hist, out, c->in16_stride, chan, c->n_wide != 0));
 	return TFREC_AMD_OK;
 }
 
@@ -254,7 +263,7 @@ static int launch_correct_rows(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, s
 
 // The channel-rate front end in the place of the pre-stage and the front end: the dense kernel on the rows, or
 // -- runs: tfrec_amd_submit_runs staged this set's table -- the sparse one
-static int launch_decin_front(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, size_t stride, int n_blocks, bool runs)
+static int launch_decin_front(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, size_t stride, const FrontOut &out, bool runs)
 {
 	hipStream_t fs = c->pipe[set].fs;
 	const RunsIn &o = c->runs_in;
@@ -262,14 +271,13 @@ static int launch_decin_front(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, si
 	const int thresh = c->cfg.thresh ? c->cfg.thresh : 500;
 	const StreamCfg *scfg = c->per_stream ? c->d_scfg : nullptr;
 	if (runs) {
-		HIPCHK(launch_decin_runs(fs, c->cfg.n_streams, n_blocks, o.d_tab[set], o.d_pool[set], o.d_pre[set], o.d_first[set], o.d_ov[set],
-					 c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->d_prevdec[set], last, thresh, scfg));
+		const RunsTables r = { .tab = o.d_tab[set], .pool = o.d_pool[set], .pre = o.d_pre[set], .first = o.d_first[set], .ov = o.d_ov[set] };
+		HIPCHK(launch_decin_runs(fs, r, out, last, thresh, scfg));
 		return TFREC_AMD_OK;
 	}
 	if (c->mapped)  // the kernel looks the row up
 		TRY(stage_chan(c, set));
-	HIPCHK(launch_decin(fs, d_iq, stride, c->cfg.n_streams, n_blocks, c->mapped ? c->d_chan[set] : nullptr, c->d_dec[set], c->dec_stride,
-			    c->d_mask[set], c->mask_stride, c->d_prevdec[set], last, thresh, scfg));
+	HIPCHK(launch_decin(fs, d_iq, stride, c->mapped ? c->d_chan[set] : nullptr, out, last, thresh, scfg));
 	return TFREC_AMD_OK;
 }
 
@@ -295,6 +303,8 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	const bool timing = (c->cfg.flags & TFREC_AMD_F_TIMING) != 0;
 	const int set = (c->head + c->inflight) % kSets;  // this submit's buffer set, events and timing events
 	const PipeCtl &P = c->pipe[set];
+	const FrontOut out = front_out(c, set, n_blocks);
+	const StreamCfg *scfg = c->per_stream ? c->d_scfg : nullptr;
 	hipEvent_t *ev = c->ev[set];
 	// Front end on its own stream: it starts when the caller's stream has produced the input, and may overlap the
 	// chains of the previous submit (different buffer set; the set's previous user was drained, see the FIFO rule).
@@ -311,16 +321,15 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		if (input_on_fs)
 			HIPCHK(hipEventRecord(c->ev_in[set], fs));
 		HIPCHK(lane_after(c->spec.lane, c->ev_in[set]));
-		const int rows = std::min(rows_in_use(c), c->spec.rows);
-		const long n_in = (long)(row_bytes / fmt_sample_bytes(c->fmt));
-		HIPCHK(launch_spectrum(c->spec.lane.st, c->fmt, (const uint8_t *)d_iq, stride, rows, n_in, c->spec.n, c->spec.g, c->spec.max_records,
-				       c->spec.d_sum[set], c->spec.d_peak[set], c->spec.d_nf[set]));
+		const SpectrumBufs b = { .n_rows = std::min(rows_in_use(c), c->spec.rows), .n_in = (long)(row_bytes / fmt_sample_bytes(c->fmt)),
+					 .n_bins = c->spec.n, .g = c->spec.g, .max_records = c->spec.max_records,
+					 .sum = c->spec.d_sum[set], .peak = c->spec.d_peak[set], .nfr = c->spec.d_nf[set] };
+		HIPCHK(launch_spectrum(c->spec.lane.st, c->fmt, (const uint8_t *)d_iq, stride, b));
 		if (c->occ.lane.on)  // the occupancy detector: on the records just queued, in stream order behind their kernel
-			HIPCHK(launch_occupancy(c->spec.lane.st, rows, n_in, c->spec.n, c->spec.g, c->spec.max_records, c->spec.d_sum[set],
-						c->spec.d_peak[set], c->spec.d_nf[set], c->occ.ratio, c->occ.rel, c->occ.d_recs[set], c->occ.d_bits[set]));
+			HIPCHK(launch_occupancy(c->spec.lane.st, b, c->occ.ratio, c->occ.rel, c->occ.d_recs[set], c->occ.d_bits[set]));
 		HIPCHK(lane_written(c->spec.lane, set));
-		c->spec.set_rows[set] = rows;
-		c->spec.set_records[set] = (int)((n_in / c->spec.n + c->spec.g - 1) / c->spec.g);
+		c->spec.set_rows[set] = b.n_rows;
+		c->spec.set_records[set] = (int)((b.n_in / b.n_bins + b.g - 1) / b.g);
 	}
 	HIPCHK(hipMemcpyAsync(c->d_eb[set], c->d_eb_fresh, kEvFreshBytes, hipMemcpyDeviceToDevice, fs));  // (+ the overflow flag)
 	if (timing)
@@ -329,7 +338,7 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	if (resets)
 		TRY(launch_resets(c, set));
 	if (c->decin.on)
-		TRY(launch_decin_front(c, set, (const uint8_t *)d_iq, stride, n_blocks, runs));
+		TRY(launch_decin_front(c, set, (const uint8_t *)d_iq, stride, out, runs));
 	const uint8_t *fin = (const uint8_t *)d_iq;
 	size_t fstride = stride;
 	// a mapped or wide-tuned context: the 10:1 stage's tuned kernel, or -- default input -- the front end that looks up the rows
@@ -352,52 +361,44 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	if (c->n_tuned || chan_front)
 		TRY(stage_tune(c, set));
 	if (!c->decin.on)
-		HIPCHK(launch_frontend(fs, fin, fstride, c->cfg.n_streams, n_blocks, c->d_tail[c->tail_sel],
-				       c->d_tail[c->tail_sel ^ 1], c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride,
-				       c->d_prevdec[set], c->cfg.thresh ? c->cfg.thresh : 500, c->taps, c->in16,
+		HIPCHK(launch_frontend(fs, fin, fstride, history(c, c->d_tail), out, c->cfg.thresh ? c->cfg.thresh : 500, c->taps, c->in16,
 				       (c->n_tuned || chan_front) ? c->d_tune[set] : nullptr, chan_front ? c->d_chan[set] : nullptr));
 	if (c->n_auto)  // auto threshold: per-block thresholds rewrite the trigger mask (fm_demod.cpp:58-73)
-		HIPCHK(launch_threshold(fs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams,
-					n_blocks, c->d_fsk, c->wmax, c->per_stream ? c->d_scfg : nullptr));
+		HIPCHK(launch_threshold(fs, out, c->d_fsk, c->wmax, scfg));
 	if (timing)
 		HIPCHK(hipEventRecord(ev[kEvFrontDone], fs));
 	if (has_kind(c->launch, 1) && !c->fmdev_k2)  // FM discriminator of the samples near trigger windows (after the mask is final)
-		HIPCHK(launch_fmdev(fs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->d_prevdec[set],
-				    c->d_fmdev[set], c->dec_stride, c->d_eb[set], c->cfg.n_streams, n_blocks, c->wmax,
-				    c->fm_flag_eps));
+		HIPCHK(launch_fmdev(fs, out, c->d_eb[set], c->wmax, c->fm_flag_eps));
 	if (timing)
 		HIPCHK(hipEventRecord(ev[kEvFmdevDone], fs));
 	HIPCHK(hipEventRecord(P.ev_front, fs));
 	if (c->lev.lane.on) {  // the level meter: behind the front end (the mask is final), beside the chains, on its own low-priority stream
 		HIPCHK(lane_after(c->lev.lane, P.ev_front));
-		HIPCHK(launch_levels(c->lev.lane.st, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams, n_blocks,
-				     c->lev.d_state, c->d_scfg, c->lev.d_records[set]));
+		HIPCHK(launch_levels(c->lev.lane.st, out, c->lev.d_state, c->d_scfg, c->lev.d_records[set]));
 		HIPCHK(lane_written(c->lev.lane, set));
 		c->lev.set_blocks[set] = n_blocks;
 	}
 	if (c->cap.lane.on) {  // the recorder: placed like the level meter, on a low-priority stream of its own
 		HIPCHK(lane_after(c->cap.lane, P.ev_front));
-		HIPCHK(launch_capture(c->cap.lane.st, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams, n_blocks,
-				      c->sample_base, c->cap.d_state, c->d_scfg, c->cap.d_stage, c->cap.stage_cap, c->cap.d_cnt, c->cap.d_base,
-				      c->cap.d_hdr[set], c->cap.d_runs[set], c->cap.max_runs, c->cap.d_pool[set], c->cap.max_samples));
+		const CaptureBufs b = { .state = c->cap.d_state, .stage = c->cap.d_stage, .stage_cap = c->cap.stage_cap, .cnt = c->cap.d_cnt,
+					.base = c->cap.d_base, .hdr = c->cap.d_hdr[set], .runs = c->cap.d_runs[set], .pool = c->cap.d_pool[set],
+					.max_runs = c->cap.max_runs, .max_samples = c->cap.max_samples };
+		HIPCHK(launch_capture(c->cap.lane.st, out, c->sample_base, b, c->d_scfg));
 		if (c->cap_pre.on)  // the pair ahead of every run: behind the copy kernel, which wrote the table
-			HIPCHK(launch_capture_pre(c->cap.lane.st, c->cap.d_runs[set], c->cap.d_hdr[set], c->cap.max_runs, c->sample_base,
-						  c->d_dec[set], c->dec_stride, c->d_prevdec[set], c->cap_pre.d_pre[set]));
+			HIPCHK(launch_capture_pre(c->cap.lane.st, out, c->sample_base, b, c->cap_pre.d_pre[set]));
 		HIPCHK(lane_written(c->cap.lane, set));
 	}
 	if (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) {
 		HIPCHK(hipStreamWaitEvent(P.cs, P.ev_front, 0));
-		HIPCHK(launch_chains(P.cs, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->cfg.n_streams, n_blocks,
-				     c->sample_base, c->launch, c->d_events[set], c->d_eb[set], c->cfg.flags));
+		HIPCHK(launch_chains(P.cs, out, c->sample_base, c->launch, c->d_events[set], c->d_eb[set], c->cfg.flags));
 		if (timing)
 			HIPCHK(hipEventRecord(ev[kEvSerialDone], P.cs));
 		for (hipEvent_t e : P.done)
 			HIPCHK(hipEventRecord(e, P.cs));
 	} else {
 		c->win[set].whb_submit_seq = c->submit_seq++;
-		HIPCHK(launch_pipeline(P, c->d_dec[set], c->dec_stride, c->d_mask[set], c->mask_stride, c->d_fmdev[set], c->dec_stride,
-				       c->cfg.n_streams, n_blocks, c->sample_base, c->launch, c->win[set], c->d_ld16[set],
-				       c->d_dev32[set], c->d_events[set], c->d_eb[set], c->cfg.flags));
+		HIPCHK(launch_pipeline(P, out, c->sample_base, c->launch, c->win[set], c->d_ld16[set], c->d_dev32[set], c->d_events[set],
+				       c->d_eb[set], c->cfg.flags));
 	}
 	report_debug_stats(c, set, n_blocks);
 	// the drain's copies, queued now

@@ -242,15 +242,12 @@ __global__ __launch_bounds__(kCapThreads) void capture_copy_kernel(const uint32_
 	}
 }
 
-hipError_t launch_capture(hipStream_t st, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask, size_t mask_stride,
-			  int n_streams, int n_blocks, long long sample_base, CaptureState *cst, const StreamCfg *scfg, CaptureStage *stage,
-			  int stage_cap, uint2 *cnt, uint4 *base, CaptureHeader *hdr, tfrec_amd_run *runs, uint32_t max_runs, uint32_t *pool,
-			  unsigned long long max_samples)
+hipError_t launch_capture(hipStream_t st, const FrontOut &o, long long sample_base, const CaptureBufs &b, const StreamCfg *scfg)
 {
-	hipLaunchKernelGGL(capture_scan_kernel, dim3(n_streams), dim3(64), 0, st, mask, mask_stride, n_blocks, cst, scfg, stage, stage_cap,
-			   cnt);
-	hipLaunchKernelGGL(capture_offsets_kernel, dim3(1), dim3(64), 0, st, cnt, n_streams, base, hdr);
-	hipLaunchKernelGGL(capture_copy_kernel, dim3(n_blocks, n_streams), dim3(kCapThreads), 0, st, dec, dec_stride, n_blocks, sample_base,
-			   stage, stage_cap, cnt, base, runs, max_runs, pool, max_samples);
+	hipLaunchKernelGGL(capture_scan_kernel, dim3(o.n_streams), dim3(64), 0, st, o.mask, o.mask_stride, o.n_blocks, b.state, scfg, b.stage,
+			   b.stage_cap, b.cnt);
+	hipLaunchKernelGGL(capture_offsets_kernel, dim3(1), dim3(64), 0, st, b.cnt, o.n_streams, b.base, b.hdr);
+	hipLaunchKernelGGL(capture_copy_kernel, dim3(o.n_blocks, o.n_streams), dim3(kCapThreads), 0, st, o.dec, o.dec_stride, o.n_blocks,
+			   sample_base, b.stage, b.stage_cap, b.cnt, b.base, b.runs, b.max_runs, b.pool, b.max_samples);
 	return hipGetLastError();
 }

@@ -22,6 +22,7 @@
 // order of the reference's normative -ffast-math x86-64 build (see oracle/tfrec_oracle.c header):
 // the biquad is ((b2*dn2 + a1*yn1) + (b0*dn + b1*dn1)) + a2*yn2.
 #include "decoder_dev.h"
+#include "launch.h"
 
 namespace tfrec {
 
@@ -292,14 +293,13 @@ __global__ __launch_bounds__(64) void chains_kernel(const uint32_t *__restrict__
 			      events, eb, flags);
 }
 
-hipError_t launch_chains(hipStream_t st, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask,
-			 size_t mask_stride, int n_streams, int n_blocks, long long sample_base, const ChainLaunch &L,
-			 tfrec_amd_event *events, EventBuf *eb, uint32_t flags)
+hipError_t launch_chains(hipStream_t st, const FrontOut &o, long long sample_base, const ChainLaunch &L, tfrec_amd_event *events,
+			 EventBuf *eb, uint32_t flags)
 {
 	if (L.n_active == 0)
 		return hipSuccess;
-	dim3 grid((n_streams + 63) / 64, L.n_active), block(64);
-	hipLaunchKernelGGL(chains_kernel, grid, block, 0, st, dec, dec_stride, mask, mask_stride, n_streams, n_blocks,
+	dim3 grid((o.n_streams + 63) / 64, L.n_active), block(64);
+	hipLaunchKernelGGL(chains_kernel, grid, block, 0, st, o.dec, o.dec_stride, o.mask, o.mask_stride, o.n_streams, o.n_blocks,
 			   sample_base, L, events, eb, flags);
 	return hipGetLastError();
 }

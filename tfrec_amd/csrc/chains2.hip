@@ -40,6 +40,7 @@
 #include <algorithm>
 
 #include "decoder_dev.h"
+#include "launch.h"
 #include <type_traits>
 #include "whb_chain_asm.h"
 
@@ -168,15 +169,14 @@ struct BitWriter {
 #include "decode.h"
 
 // ------------------------------------------------------------------------------------------------ launch
-hipError_t launch_fmdev(hipStream_t st, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask,
-			size_t mask_stride, const uint32_t *prevdec, int16_t *fmdev, size_t fmdev_stride, EventBuf *eb,
-			int n_streams, int n_blocks, int wmax, double flag_eps);
-
-hipError_t launch_pipeline(const PipeCtl &P, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask,
-			   size_t mask_stride, const int16_t *fmdev, size_t fmdev_stride, int n_streams, int n_blocks,
-			   long long sample_base, const ChainLaunch &L, const WinTables &T, int16_t *ld16, int32_t *dev32,
-			   tfrec_amd_event *events, EventBuf *eb, uint32_t flags)
+hipError_t launch_pipeline(const PipeCtl &P, const FrontOut &o, long long sample_base, const ChainLaunch &L, const WinTables &T, int16_t *ld16,
+			   int32_t *dev32, tfrec_amd_event *events, EventBuf *eb, uint32_t flags)
 {
+	const uint32_t *dec = o.dec;  // the kernels' arguments
+	const unsigned long long *mask = o.mask;
+	const int16_t *fmdev = o.fmdev;
+	const size_t dec_stride = o.dec_stride, mask_stride = o.mask_stride, fmdev_stride = o.fmdev_stride;
+	const int n_streams = o.n_streams, n_blocks = o.n_blocks;
 	// P.tev (optional): one interval per kernel, TimingMark (tfrec_dev.h)
 	auto mark = [&](int k, hipStream_t s_) {
 		if (P.tev)
@@ -334,15 +334,13 @@ hipError_t launch_pipeline(const PipeCtl &P, const uint32_t *dec, size_t dec_str
 			// discriminator + five biquad kernels -- is the stream that sets the period
 			TRY(hipStreamWaitEvent(P.fq, P.ev_front, 0));
 			mark(kMarkFmdev, P.fq);
-			TRY(launch_fmdev(P.fq, dec, dec_stride, mask, mask_stride, P.prevdec, P.fmdev_out, fmdev_stride, eb, n_streams,
-					 n_blocks, P.fmdev_wmax, P.fm_flag_eps));
+			TRY(launch_fmdev(P.fq, o, eb, P.fmdev_wmax, P.fm_flag_eps));
 			mark(kMarkFmdevEnd, P.fq);
 			TRY(hipEventRecord(P.ev_fm, P.fq));
 			TRY(hipStreamWaitEvent(P.k2, P.ev_fm, 0));
 		} else if (P.fmdev_wmax > 0) {
 			mark(kMarkFmdev, P.k2);
-			TRY(launch_fmdev(P.k2, dec, dec_stride, mask, mask_stride, P.prevdec, P.fmdev_out, fmdev_stride, eb, n_streams,
-					 n_blocks, P.fmdev_wmax, P.fm_flag_eps));
+			TRY(launch_fmdev(P.k2, o, eb, P.fmdev_wmax, P.fm_flag_eps));
 			mark(kMarkFmdevEnd, P.k2);
 		}
 		// The speculative pass needs the discriminator pass and the window scan of ITS submit only (every segment starts from

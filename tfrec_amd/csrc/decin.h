@@ -173,23 +173,20 @@ static unsigned decin_grid(int n_streams, int n_blocks)
 }
 
 // chan != nullptr: a mapped context, stream s reads row chan[s].z
-hipError_t launch_decin(hipStream_t st, const uint8_t *in, size_t stride, int n_streams, int n_blocks, const uint4 *chan, uint32_t *dec,
-			size_t dec_stride, unsigned long long *mask, size_t mask_stride, uint32_t *prevdec, uint32_t *last, int thresh,
+hipError_t launch_decin(hipStream_t st, const uint8_t *in, size_t stride, const uint4 *chan, const FrontOut &o, uint32_t *last, int thresh,
 			const StreamCfg *scfg)
 {
-	hipLaunchKernelGGL(decin_kernel<false>, dim3(decin_grid(n_streams, n_blocks)), dim3(kDecinThreads), 0, st, in, stride, n_blocks,
-			   n_streams, chan, (const uint4 *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
-			   (const int32_t *)nullptr, (const uint2 *)nullptr, dec, dec_stride, mask, mask_stride, prevdec, last, thresh, scfg);
+	hipLaunchKernelGGL(decin_kernel<false>, dim3(decin_grid(o.n_streams, o.n_blocks)), dim3(kDecinThreads), 0, st, in, stride, o.n_blocks,
+			   o.n_streams, chan, nullptr, nullptr, nullptr, nullptr, nullptr, o.dec, o.dec_stride, o.mask, o.mask_stride, o.prevdec,
+			   last, thresh, scfg);
 	return hipGetLastError();
 }
 
-hipError_t launch_decin_runs(hipStream_t st, int n_streams, int n_blocks, const uint4 *tab, const uint32_t *pool, const uint32_t *pre,
-			     const int32_t *first, const uint2 *ov, uint32_t *dec, size_t dec_stride, unsigned long long *mask,
-			     size_t mask_stride, uint32_t *prevdec, uint32_t *last, int thresh, const StreamCfg *scfg)
+hipError_t launch_decin_runs(hipStream_t st, const RunsTables &r, const FrontOut &o, uint32_t *last, int thresh, const StreamCfg *scfg)
 {
-	hipLaunchKernelGGL(decin_kernel<true>, dim3(decin_grid(n_streams, n_blocks)), dim3(kDecinThreads), 0, st, (const uint8_t *)nullptr,
-			   (size_t)0, n_blocks, n_streams, (const uint4 *)nullptr, tab, pool, pre, first, ov, dec, dec_stride, mask,
-			   mask_stride, prevdec, last, thresh, scfg);
+	hipLaunchKernelGGL(decin_kernel<true>, dim3(decin_grid(o.n_streams, o.n_blocks)), dim3(kDecinThreads), 0, st, nullptr, 0, o.n_blocks,
+			   o.n_streams, nullptr, r.tab, r.pool, r.pre, r.first, r.ov, o.dec, o.dec_stride, o.mask, o.mask_stride, o.prevdec,
+			   last, thresh, scfg);
 	return hipGetLastError();
 }
 
@@ -210,11 +207,10 @@ __global__ __launch_bounds__(256) void capture_pre_kernel(const tfrec_amd_run *_
 	}
 }
 
-hipError_t launch_capture_pre(hipStream_t st, const tfrec_amd_run *runs, const CaptureHeader *hdr, uint32_t max_runs, long long sample_base,
-			      const uint32_t *dec, size_t dec_stride, const uint32_t *prevdec, uint32_t *pre)
+hipError_t launch_capture_pre(hipStream_t st, const FrontOut &o, long long sample_base, const CaptureBufs &b, uint32_t *pre)
 {
-	const unsigned blocks = std::max(1u, std::min(256u, (max_runs + 255u) / 256u));
-	hipLaunchKernelGGL(capture_pre_kernel, dim3(blocks), dim3(256), 0, st, runs, hdr, max_runs, sample_base, dec, dec_stride, prevdec,
-			   pre);
+	const unsigned blocks = std::max(1u, std::min(256u, (b.max_runs + 255u) / 256u));
+	hipLaunchKernelGGL(capture_pre_kernel, dim3(blocks), dim3(256), 0, st, b.runs, b.hdr, b.max_runs, sample_base, o.dec, o.dec_stride,
+			   o.prevdec, pre);
 	return hipGetLastError();
 }

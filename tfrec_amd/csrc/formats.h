@@ -318,29 +318,39 @@ bool fmt_dispatch(int fmt, F f)
 __host__ __device__ constexpr int rs_stream_lds(int p, int q, int t, int tile) { return 8 * rs_raw_chunks(p, q, t, tile) * 4 + 2 * kTuneN; }
 static_assert(rs_stream_lds(10 * kRsQDiv - 1, kRsQDiv, kRsTMax, kRsTile / 2) <= kRsLdsMax, "the half tile serves the largest rate");
 
-// The arguments of launch_resample with the format in front; the history is the format's (above).  One geometry per rate, tuned or
-// not: half the tile where the image of a whole one and the cosine table exceed the LDS limit (resample.h).  A rate whose table is
-// not staged (rs_streamed; `taps` is resample_stream_kernel's table then) follows the same rule with its own LDS.
-hipError_t launch_resample_fmt(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, int p, int q, int t,
-			       const float *taps, const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride,
-			       const uint4 *chan, bool tuned)
+// The resampling stage.  rate.taps: [q][t] floats on the device, h / 1024 (rs_streamed(q, t): the table resample_stream_kernel reads);
+// n_blocks is a multiple of rs_unit(q) (the caller checked), so n_blocks * 32768 * p is one of q.  The history is the format's (above).
+// tuned: a stream has an input-rate tune (6g; chan != nullptr then).  A u8 context runs resample_kernel (resample.h) while no stream is
+// tuned and the table is staged, and the format kernel's U8 instantiation otherwise, which reads and writes the same raw history --
+// an untuned stream's survives the change of kernels around it in both directions.  The format kernels have one geometry per rate,
+// tuned or not: half the tile where the image of a whole one and the cosine table exceed the LDS limit (resample.h).  A rate whose
+// table is not staged follows the same rule with its own LDS (one kernel per format, tuned or not).
+hipError_t launch_resample(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, const RateTable &rate,
+			   History hist, uint32_t *out, size_t out_stride, const uint4 *chan, bool tuned)
 {
+	const int p = rate.p, q = rate.q, t = rate.t;
 	const long n_out = (long)n_blocks * (TFREC_AMD_BLOCK_BYTES / 2);  // complex samples at 1.536 MS/s
 	const long n_in = n_out * p / q;
+	const bool streamed = rs_streamed(q, t);
+	if (fmt == kFmtU8 && !tuned && !streamed) {
+		const size_t lds = (size_t)(rs_taps_dw(q, t) + 4 * rs_raw_chunks(p, q, t)) * 4;
+		hipLaunchKernelGGL(resample_kernel, dim3((unsigned)(n_out / kRsTile), n_streams), dim3(kRsThreads), lds, st, iq, stride, n_in, p, q,
+				   t, rate.taps, hist.in, hist.out, out, out_stride, chan);
+		return hipGetLastError();
+	}
 	if (tuned && !chan)
 		return hipErrorInvalidValue;
-	const bool streamed = rs_streamed(q, t);
 	const auto lds_of = [&](int tile_n) { return streamed ? rs_stream_lds(p, q, t, tile_n) : rs_tuned_lds(p, q, t, tile_n); };
 	const int tile = lds_of(kRsTile) <= kRsLdsMax ? kRsTile : kRsTile / 2;
 	const size_t lds = (size_t)lds_of(tile) - (tuned ? 0 : 2 * kTuneN);
 	const dim3 grid((unsigned)(n_out / tile), n_streams), block(tile / kRsOut);
 	const bool known = fmt_dispatch<true>(fmt, [&](auto f) {
 		if (streamed)
-			hipLaunchKernelGGL(resample_stream_kernel<decltype(f)::value>, grid, block, lds, st, iq, stride, n_in, p, q, t, taps, tail_in,
-					   tail_out, out, out_stride, chan, tuned ? 1 : 0);
+			hipLaunchKernelGGL(resample_stream_kernel<decltype(f)::value>, grid, block, lds, st, iq, stride, n_in, p, q, t, rate.taps, hist.in,
+					   hist.out, out, out_stride, chan, tuned ? 1 : 0);
 		else
-			hipLaunchKernelGGL(resample_fmt_kernel<decltype(f)::value>, grid, block, lds, st, iq, stride, n_in, p, q, t, taps, tail_in,
-					   tail_out, out, out_stride, chan, tuned ? 1 : 0);
+			hipLaunchKernelGGL(resample_fmt_kernel<decltype(f)::value>, grid, block, lds, st, iq, stride, n_in, p, q, t, rate.taps, hist.in,
+					   hist.out, out, out_stride, chan, tuned ? 1 : 0);
 	});
 	return known ? hipGetLastError() : hipErrorInvalidValue;
 }

@@ -31,6 +31,7 @@
 #include <stdlib.h>
 
 #include "dsp_dev.h"
+#include "launch.h"
 #include "tune_table.h"
 #include <algorithm>
 #include <type_traits>
@@ -693,25 +694,23 @@ __global__ __launch_bounds__(kThreads10) void decim10_kernel(const uint8_t *__re
 }
 
 // chan != nullptr: the tuned / mapped kernel (per stream {inc10, phase10, input row, 0})
-hipError_t launch_decim10(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks,
-			  const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride, const uint4 *chan)
+hipError_t launch_decim10(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, History hist, uint32_t *out,
+			  size_t out_stride, const uint4 *chan)
 {
 	const long n_out = (long)n_blocks * (TFREC_AMD_BLOCK_BYTES / 2);  // complex samples at 1.536 MS/s
 	static_assert(kBlockDec * 4 % kT10 == 0, "decim10_kernel has no partial tiles: a block is a whole number of them");
 	dim3 grid((unsigned)(n_out / kT10), n_streams);
 	if (chan)
-		hipLaunchKernelGGL((decim10_kernel<true, const uint4 *>), grid, dim3(kThreads10), 0, st, iq, stride, n_out, tail_in, tail_out, out, out_stride, chan);
+		hipLaunchKernelGGL((decim10_kernel<true, const uint4 *>), grid, dim3(kThreads10), 0, st, iq, stride, n_out, hist.in, hist.out, out, out_stride, chan);
 	else
-		hipLaunchKernelGGL(decim10_kernel<false>, grid, dim3(kThreads10), 0, st, iq, stride, n_out, tail_in, tail_out, out, out_stride);
+		hipLaunchKernelGGL(decim10_kernel<false>, grid, dim3(kThreads10), 0, st, iq, stride, n_out, hist.in, hist.out, out, out_stride);
 	return hipGetLastError();
 }
 
-hipError_t launch_frontend(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks,
-			   const uint8_t *tail_in, uint8_t *tail_out, uint32_t *dec, size_t dec_stride,
-			   unsigned long long *mask, size_t mask_stride, uint32_t *prevdec, int thresh, const FrontTapsCfg &taps,
-			   bool in16, const uint2 *tune, const uint4 *chan)
+hipError_t launch_frontend(hipStream_t st, const uint8_t *iq, size_t stride, History tail, const FrontOut &o, int thresh,
+			   const FrontTapsCfg &taps, bool in16, const uint2 *tune, const uint4 *chan)
 {
-	const int m_total = n_blocks * kBlockDec;
+	const int n_streams = o.n_streams, m_total = o.n_blocks * kBlockDec;
 	// (config 5's int16 entry keeps a workgroup per tile: behind the 10:1 stage, which it waits for, the persistent form measured 4 % slower)
 	const int persist = in16 ? 0 : kFrontPersist;
 	const dim3 grid = persist ? dim3((unsigned)std::min<long>(persist, (long)(m_total / kTileDec) * n_streams)) : dim3(m_total / kTileDec, n_streams);
@@ -723,26 +722,26 @@ hipError_t launch_frontend(hipStream_t st, const uint8_t *iq, size_t stride, int
 		FrontTapsMap tm;
 		static_cast<FrontTapsTune &>(tm) = tt;
 		tm.chan = chan;
-		hipLaunchKernelGGL((frontend_kernel<false, true, true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
-				   dec, dec_stride, mask, mask_stride, prevdec, thresh, tm, n_streams, persist);
+		hipLaunchKernelGGL((frontend_kernel<false, true, true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail.in, tail.out,
+				   o.dec, o.dec_stride, o.mask, o.mask_stride, o.prevdec, thresh, tm, n_streams, persist);
 	} else if (tune && in16)
-		hipLaunchKernelGGL((frontend_kernel<true, true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
-				   dec, dec_stride, mask, mask_stride, prevdec, thresh, tt, n_streams, persist);
+		hipLaunchKernelGGL((frontend_kernel<true, true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail.in, tail.out,
+				   o.dec, o.dec_stride, o.mask, o.mask_stride, o.prevdec, thresh, tt, n_streams, persist);
 	else if (tune)
-		hipLaunchKernelGGL((frontend_kernel<false, true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
-				   dec, dec_stride, mask, mask_stride, prevdec, thresh, tt, n_streams, persist);
+		hipLaunchKernelGGL((frontend_kernel<false, true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail.in, tail.out,
+				   o.dec, o.dec_stride, o.mask, o.mask_stride, o.prevdec, thresh, tt, n_streams, persist);
 	else if (taps.scfg && in16)
-		hipLaunchKernelGGL((frontend_kernel<true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
-				   dec, dec_stride, mask, mask_stride, prevdec, thresh, taps, n_streams, persist);
+		hipLaunchKernelGGL((frontend_kernel<true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail.in, tail.out,
+				   o.dec, o.dec_stride, o.mask, o.mask_stride, o.prevdec, thresh, taps, n_streams, persist);
 	else if (taps.scfg)
-		hipLaunchKernelGGL((frontend_kernel<false, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
-				   dec, dec_stride, mask, mask_stride, prevdec, thresh, taps, n_streams, persist);
+		hipLaunchKernelGGL((frontend_kernel<false, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail.in, tail.out,
+				   o.dec, o.dec_stride, o.mask, o.mask_stride, o.prevdec, thresh, taps, n_streams, persist);
 	else if (in16)
-		hipLaunchKernelGGL((frontend_kernel<true, false>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
-				   dec, dec_stride, mask, mask_stride, prevdec, thresh, narrow, n_streams, persist);
+		hipLaunchKernelGGL((frontend_kernel<true, false>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail.in, tail.out,
+				   o.dec, o.dec_stride, o.mask, o.mask_stride, o.prevdec, thresh, narrow, n_streams, persist);
 	else
-		hipLaunchKernelGGL((frontend_kernel<false, false>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail_in, tail_out,
-				   dec, dec_stride, mask, mask_stride, prevdec, thresh, narrow, n_streams, persist);
+		hipLaunchKernelGGL((frontend_kernel<false, false>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail.in, tail.out,
+				   o.dec, o.dec_stride, o.mask, o.mask_stride, o.prevdec, thresh, narrow, n_streams, persist);
 	return hipGetLastError();
 }
 
@@ -828,23 +827,21 @@ __global__ __launch_bounds__(64) void fm_resolve_kernel(const uint32_t *__restri
 	}
 }
 
-hipError_t launch_fmdev(hipStream_t st, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask,
-			size_t mask_stride, const uint32_t *prevdec, int16_t *fmdev, size_t fmdev_stride, EventBuf *eb,
-			int n_streams, int n_blocks, int wmax, double flag_eps)
+hipError_t launch_fmdev(hipStream_t st, const FrontOut &o, EventBuf *eb, int wmax, double flag_eps)
 {
-	const int m_total = n_blocks * kBlockDec;
+	const int n_streams = o.n_streams, m_total = o.n_blocks * kBlockDec;
 	const dim3 grid((unsigned)std::min<long>(kFmPersist, (long)(m_total / kFmTile) * n_streams));
-	hipLaunchKernelGGL(fmdev_kernel, grid, dim3(kFmThreads), 0, st, dec, dec_stride, mask, mask_stride, prevdec, fmdev,
-			   fmdev_stride, eb, wmax, flag_eps, m_total / kFmTile, n_streams, kFmPersist);
+	hipLaunchKernelGGL(fmdev_kernel, grid, dim3(kFmThreads), 0, st, o.dec, o.dec_stride, o.mask, o.mask_stride, o.prevdec, o.fmdev,
+			   o.fmdev_stride, eb, wmax, flag_eps, m_total / kFmTile, n_streams, kFmPersist);
 	// one-wave workgroups: the kernel normally has nothing to do, and a 256-thread workgroup waits until a CU has four
 	// wave slots and their registers free at once -- up to a millisecond on the stream that sets the batch period
-	hipLaunchKernelGGL(fm_resolve_kernel, dim3(512), dim3(64), 0, st, dec, dec_stride, prevdec, fmdev, fmdev_stride, eb,
+	hipLaunchKernelGGL(fm_resolve_kernel, dim3(512), dim3(64), 0, st, o.dec, o.dec_stride, o.prevdec, o.fmdev, o.fmdev_stride, eb,
 			   n_streams, m_total, flag_eps);
 	return hipGetLastError();
 }
 
-#include "resample.h"  // resample_kernel, launch_resample
-#include "formats.h"   // resample_fmt_kernel, ingest_kernel and their launchers
+#include "resample.h"  // resample_kernel
+#include "formats.h"   // resample_fmt_kernel, ingest_kernel, launch_resample, launch_ingest
 #include "correct.h"   // correct_sums_kernel, correct_estimate_kernel, correct_apply_kernel, launch_correct
 #include "levels.h"    // level_sum_kernel, level_trig_kernel, launch_levels
 #include "capture.h"   // capture_scan_kernel, capture_offsets_kernel, capture_copy_kernel, launch_capture

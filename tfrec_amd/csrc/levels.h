@@ -145,11 +145,10 @@ __global__ __launch_bounds__(64) void level_trig_kernel(const unsigned long long
 	}
 }
 
-hipError_t launch_levels(hipStream_t st, const uint32_t *dec, size_t dec_stride, const unsigned long long *mask, size_t mask_stride,
-			 int n_streams, int n_blocks, LevelState *lev, const StreamCfg *scfg, tfrec_amd_level *out)
+hipError_t launch_levels(hipStream_t st, const FrontOut &o, LevelState *lev, const StreamCfg *scfg, tfrec_amd_level *out)
 {
-	hipLaunchKernelGGL(level_sum_kernel, dim3(n_blocks, n_streams), dim3(kLevelThreads), 0, st, dec, dec_stride, mask, mask_stride,
-			   n_blocks, out);
-	hipLaunchKernelGGL(level_trig_kernel, dim3(n_streams), dim3(64), 0, st, mask, mask_stride, n_blocks, lev, scfg, out);
+	hipLaunchKernelGGL(level_sum_kernel, dim3(o.n_blocks, o.n_streams), dim3(kLevelThreads), 0, st, o.dec, o.dec_stride, o.mask, o.mask_stride,
+			   o.n_blocks, out);
+	hipLaunchKernelGGL(level_trig_kernel, dim3(o.n_streams), dim3(64), 0, st, o.mask, o.mask_stride, o.n_blocks, lev, scfg, out);
 	return hipGetLastError();
 }

@@ -90,19 +90,19 @@ __global__ __launch_bounds__(kOccMaxBins) void occupancy_kernel(const unsigned l
 	}
 }
 
-// The detector on the records launch_spectrum has just queued on `st` (same rows, n_in, n_bins, g, max_records).
-hipError_t launch_occupancy(hipStream_t st, int n_rows, long n_in, int n_bins, int g, size_t max_records, const unsigned long long *sum,
-			    const unsigned long long *peak, const uint32_t *nfr, uint32_t ratio, uint32_t rel, tfrec_amd_occupancy *recs,
-			    uint32_t *bits)
+// The detector on the records launch_spectrum has just queued on `st` (the same SpectrumBufs).
+hipError_t launch_occupancy(hipStream_t st, const SpectrumBufs &b, uint32_t ratio, uint32_t rel, tfrec_amd_occupancy *recs, uint32_t *bits)
 {
-	const long n_frames = n_in / n_bins;
+	const int n_rows = b.n_rows, n_bins = b.n_bins, g = b.g;
+	const size_t max_records = b.max_records;
+	const long n_frames = b.n_in / n_bins;
 	const long n_records = (n_frames + g - 1) / g;
 	if (n_bins < 64 || n_bins > kOccMaxBins || (n_bins & (n_bins - 1)) || g < 1 || n_rows < 1 || (size_t)n_records > max_records ||
 	    n_records * n_rows > 0x7fffffffL || ratio < 2 || ratio > 4096 || rel < 1 || rel > 4096)
 		return hipErrorInvalidValue;
 	if (n_records == 0)
 		return hipSuccess;
-	hipLaunchKernelGGL(occupancy_kernel, dim3((unsigned)(n_records * n_rows)), dim3((unsigned)n_bins), 0, st, sum, peak, nfr, n_bins,
+	hipLaunchKernelGGL(occupancy_kernel, dim3((unsigned)(n_records * n_rows)), dim3((unsigned)n_bins), 0, st, b.sum, b.peak, b.nfr, n_bins,
 			   (int)n_records, max_records, (unsigned long long)ratio, (unsigned long long)rel, recs, bits);
 	return hipGetLastError();
 }

@@ -129,25 +129,5 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(const uint8_t *__r
 		dst[k] = make_uint4(ow[4 * k], ow[4 * k + 1], ow[4 * k + 2], ow[4 * k + 3]);
 }
 
-hipError_t launch_resample_fmt(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, int p, int q, int t,
-			       const float *taps, const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride,
-			       const uint4 *chan, bool tuned);  // formats.h
-
-// taps: [q][t] floats on the device, h / 1024 (rs_streamed(q, t): the table resample_stream_kernel reads); n_blocks is a multiple
-// of rs_unit(q) (the caller checked), so n_blocks * 32768 * p is one of q
-// tuned: a stream has an input-rate tune (6g; chan != nullptr then): the format kernel's U8 instantiation, which reads and writes
-// the same raw history -- an untuned stream's survives the change of kernels around it in both directions
-hipError_t launch_resample(hipStream_t st, const uint8_t *iq, size_t stride, int n_streams, int n_blocks, int p, int q, int t,
-			   const float *taps, const uint8_t *tail_in, uint8_t *tail_out, uint32_t *out, size_t out_stride,
-			   const uint4 *chan, bool tuned)
-{
-	if (tuned || rs_streamed(q, t))  // (a streamed table: one kernel per format, tuned or not)
-		return launch_resample_fmt(st, kFmtU8, iq, stride, n_streams, n_blocks, p, q, t, taps, tail_in, tail_out, out, out_stride, chan, tuned);
-	const long n_out = (long)n_blocks * (TFREC_AMD_BLOCK_BYTES / 2);  // complex samples at 1.536 MS/s
-	const long n_in = n_out * p / q;
-	static_assert((TFREC_AMD_BLOCK_BYTES / 2) % kRsTile == 0, "resample_kernel has no partial tiles");
-	const size_t lds = (size_t)(rs_taps_dw(q, t) + 4 * rs_raw_chunks(p, q, t)) * 4;
-	hipLaunchKernelGGL(resample_kernel, dim3((unsigned)(n_out / kRsTile), n_streams), dim3(kRsThreads), lds, st, iq, stride, n_in, p, q,
-			   t, taps, tail_in, tail_out, out, out_stride, chan);
-	return hipGetLastError();
-}
+static_assert((TFREC_AMD_BLOCK_BYTES / 2) % kRsTile == 0, "resample_kernel has no partial tiles");
+// launch_resample (formats.h) launches it

@@ -125,10 +125,11 @@ __global__ __launch_bounds__(kSpecThreads) void spectrum_kernel(const uint8_t *_
 
 // The spectrum of rows 0 .. n_rows - 1 of a submit of n_in complex samples per row.  n_records = ceil(floor(n_in / N) / g) must
 // not exceed max_records (the caller sized the buffers from max_blocks).
-hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, int n_rows, long n_in, int n_bins, int g,
-			   size_t max_records, unsigned long long *sum, unsigned long long *peak, uint32_t *nfr)
+hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, const SpectrumBufs &b)
 {
-	const long n_frames = n_in / n_bins;
+	const int n_rows = b.n_rows, n_bins = b.n_bins, g = b.g;
+	const size_t max_records = b.max_records;
+	const long n_frames = b.n_in / n_bins;
 	const long n_records = (n_frames + g - 1) / g;
 	if (n_bins < 64 || n_bins > kSpecMaxBins || (n_bins & (n_bins - 1)) || g < 1 || n_rows < 1 || n_frames > 0x7fffffffL ||
 	    (size_t)n_records > max_records || n_records * n_rows > 0x7fffffffL)
@@ -139,8 +140,8 @@ hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t st
 	const dim3 grid((unsigned)(n_records * n_rows), (unsigned)(n_bins / threads)), block((unsigned)threads);
 	const size_t lds = (size_t)n_bins * (8 + 4 * kSpecFrames);  // the table and one batch: 40 KB at N = 1024
 	const bool known = fmt_dispatch<true>(fmt, [&](auto f) {
-		hipLaunchKernelGGL(spectrum_kernel<decltype(f)::value>, grid, block, lds, st, iq, stride, n_bins, (int)n_frames, g, (int)n_records, max_records, sum,
-				   peak, nfr);
+		hipLaunchKernelGGL(spectrum_kernel<decltype(f)::value>, grid, block, lds, st, iq, stride, n_bins, (int)n_frames, g, (int)n_records, max_records, b.sum,
+				   b.peak, b.nfr);
 	});
 	return known ? hipGetLastError() : hipErrorInvalidValue;
 }

@@ -412,7 +412,8 @@ struct WinTables {
 };
 constexpr int kStatusDead = 0xff;  // tfrec_amd_event::status of a retracted event: never reported
 
-// Streams and events of one submit of the window-parallel pipeline.  Every (protocol family, stage) pair owns a
+// Streams and events of one submit of the window-parallel pipeline (host-side only: never a kernel argument; the set's buffers
+// travel in FrontOut, launch.h).  Every (protocol family, stage) pair owns a
 // stream, so that stage A (biquads) of submit k+1 runs beside stage B (slicers, decoders) of submit k; the two
 // submits use different table / buffer sets.  k2 == cs and kw == aux is allowed (shallow layout: with the HIP
 // default of 4 hardware queues more streams would share queues and serialise).
@@ -435,11 +436,9 @@ struct PipeCtl {
 	hipEvent_t done[3];        // end of the submit on cs / aux / t1
 	hipEvent_t *tev;           // optional timing marks (TimingMark)
 	// the FM discriminator pass, when it runs at the head of stage A of the TFA_2 family (k2) instead of behind the
-	// front end (its only consumer is that stage): wmax > 0
+	// front end (its only consumer is that stage): wmax > 0.  Its rows are the submit's FrontOut (launch.h).
 	int fmdev_wmax;
 	double fm_flag_eps;  // distance of the scaled angle to an integer below which a sample goes to the exact slow path
-	int16_t *fmdev_out;
-	const uint32_t *prevdec;
 };
 // PipeCtl::tev: launch_pipeline's timing marks, one interval per kernel (tfrec_amd_get_timings reads them), stream by stream:
 //   ws : Windows | windows | WindowsEnd

@@ -63,10 +63,9 @@ __global__ __launch_bounds__(64) void threshold_kernel(const uint32_t *__restric
 	}
 }
 
-hipError_t launch_threshold(hipStream_t st, const uint32_t *dec, size_t dec_stride, unsigned long long *mask,
-			    size_t mask_stride, int n_streams, int n_blocks, FskState *fsk, int wmax, const StreamCfg *scfg)
+hipError_t launch_threshold(hipStream_t st, const FrontOut &o, FskState *fsk, int wmax, const StreamCfg *scfg)
 {
-	hipLaunchKernelGGL(threshold_kernel, dim3(n_streams), dim3(64), 0, st, dec, dec_stride, mask, mask_stride, n_blocks, fsk,
+	hipLaunchKernelGGL(threshold_kernel, dim3(o.n_streams), dim3(64), 0, st, o.dec, o.dec_stride, o.mask, o.mask_stride, o.n_blocks, fsk,
 			   wmax, scfg);
 	return hipGetLastError();
 }
