@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import parity
+import segments
 from oracle import oracle as O
 from tfrec_amd import api, formats, resample, tune
 from test_formats_cpu import KINDS, scene, scene_oracle, scene_stage0, scene_u8, stage0_of
@@ -148,6 +149,19 @@ def test_reset_in_mid_stream_equals_a_fresh_receiver():
     assert not np.array_equal(y0[2][1][:16], whole[2 * 6 * 4 * api.BLOCK_DEC:][:16])
     assert np.array_equal(y0[3][1], after[len(y0[2][1]):])
     parity.assert_stage0(y0, FOUR, scene_stage0(kind, p, q, 0), 0)
+
+
+def test_reset_at_the_base_rate_behind_the_conversion():
+    """An s8 context at 1/1 has the format conversion for a pre-stage and no pre-stage history: a reset of stream 1 before the
+    second of three one-block submits restores the front end's int16 history alone.  s8 of flipped bytes is the u8 context, so
+    the segment harness's oracles are fed the u8 rows.  Blocks 3 .. 5 of the scene: stream 1 has flushes before the reset and in
+    the block right behind it (asserted on the oracles)."""
+    u = scene_u8(1, 1)[:, 3 * api.BLOCK_BYTES:6 * api.BLOCK_BYTES]
+    hosts = parity.cut(u, (1, 1, 1))
+    with api.Receiver(2, TYPES, THRESH, 0, max_blocks=1, all_flushes=True, input_format="s8") as r:
+        total, segs = segments.run_segments(r, [h ^ 0x80 for h in hosts], {1: [("reset", [1])]}, (TYPES, THRESH, 0), hosts=hosts)
+    assert [g.k for g in segs[1]] == [0, 1] and all(len(g.orc.events_full()) > 0 for g in segs[1])
+    assert total > 0
 
 
 def test_configure_works():

@@ -17,7 +17,7 @@
 
 using namespace tfrec;
 
-#include "capi_ctx.h"      // constants, errors, tfrec_amd_ctx and what it owns, guards, checks, side lanes
+#include "capi_ctx.h"      // constants, errors, the records (InputPath, the per-stream tables, ...), tfrec_amd_ctx and what it owns, guards, checks
 #include "capi_create.h"   // chain parameters, tap tables, the context's buffers, streams and events; constructors, destroy
 #include "capi_probe.h"    // the discriminator's host check, debug statistics; probes, read-backs, timings, memory, counters
 #include "capi_submit.h"   // the two kernels, a submit's resets and staging, submit_common, the submits, drain, sync, pending

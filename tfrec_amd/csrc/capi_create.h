@@ -122,7 +122,7 @@ static StreamCfg device_cfg(const tfrec_amd_ctx *c, const tfrec_amd_stream_confi
 			d.amask |= 1u << a;
 			d.wmax = std::max(d.wmax, (int32_t)c->launch.params[a].window);
 		}
-	d.thresh = sc.thresh ? sc.thresh : 500;
+	d.thresh = thresh_or_auto(sc.thresh);
 	d.autoth = sc.thresh == 0;
 	d.wide = (uint16_t)sc.filter_type;
 	return d;
@@ -218,10 +218,57 @@ static int register_chains(tfrec_amd_ctx *c)
 	return TFREC_AMD_OK;
 }
 
-// the front end: its taps, outputs (one set per submit in flight), FIR history, the auto threshold and every stream's settings
+// a carried history's buffers, as a start leaves them
+static int make_history(tfrec_amd_ctx *c, Carried &h, int n_bufs)
+{
+	const size_t bytes = (size_t)c->cfg.n_streams * (size_t)h.bytes;
+	for (int k = 0; h.bytes && k < n_bufs; k++) {
+		TRY(own_device(c, h.buf[k], bytes));
+		HIPCHK(hipMemset(h.buf[k], h.fill, bytes));
+	}
+	return TFREC_AMD_OK;
+}
+
+// the resampling stage's tap table on the device, and rate_abs
+static int make_rate_table(tfrec_amd_ctx *c)
+{
+	InputPath &I = c->input;
+	std::vector<int32_t> h;
+	int t = 0;
+	if (!resample_table(I.rate.p, I.rate.q, h, t))  // (tfrec_amd_create_rate checked it already)
+		return TFREC_AMD_E_INVAL;
+	I.rate.t = t;
+	for (int phi = 0; phi < I.rate.q; phi++) {
+		long long a = 0;
+		for (int k = 0; k < t; k++)
+			a += llabs((long long)h[(size_t)phi * t + k]);
+		I.rate_abs = std::max(I.rate_abs, a);
+	}
+	std::vector<float> hf(h.size());
+	if (rs_streamed(I.rate.q, t)) {  // resample_stream_kernel's table: [t][q], h / 65536, column j the phase (j P) mod Q
+		const size_t q = (size_t)I.rate.q;
+		for (size_t j = 0; j < q; j++) {
+			const size_t phi = j * (size_t)I.rate.p % q;
+			for (size_t k = 0; k < (size_t)t; k++)
+				hf[k * q + j] = (float)h[phi * t + k] * (1.0f / 65536.0f);  // exact: |h| < 2^17
+		}
+	} else {
+		for (size_t i = 0; i < h.size(); i++)
+			hf[i] = (float)h[i] * (1.0f / 1024.0f);  // exact: |h| < 2^17
+	}
+	float *d_taps = nullptr;
+	TRY(own_device(c, d_taps, hf.size() * sizeof(float)));
+	HIPCHK(hipMemcpy(d_taps, hf.data(), hf.size() * sizeof(float), hipMemcpyHostToDevice));
+	I.rate.taps = d_taps;
+	return TFREC_AMD_OK;
+}
+
+// the front end: its taps, outputs (one set per submit in flight), the auto threshold, and the input path's buffers: the two
+// carried histories (here their bytes and fills are decided, once), stage 0 and the rate's tap table
 static int make_front_buffers(tfrec_amd_ctx *c)
 {
 	const tfrec_amd_config &cfg = c->cfg;
+	InputPath &I = c->input;
 	const size_t m_max = (size_t)cfg.max_blocks * kBlockDec;
 	const size_t n = (size_t)cfg.n_streams;
 	// second-stage taps (kNarrowTaps / kWideTaps), as h / 65536
@@ -236,70 +283,46 @@ static int make_front_buffers(tfrec_amd_ctx *c)
 		TRY(own_device(c, c->d_dec[k], n * c->dec_stride * sizeof(uint32_t) + 256));  // + slack: K3 loads whole 32-sample chunks at window tails
 		TRY(own_device(c, c->d_mask[k], n * c->mask_stride * sizeof(unsigned long long)));
 	}
-	// fm_demod.cpp:23-27: thresh 0 selects the adaptive mode starting at 500.  Every stream starts with the context's settings.
+	// every stream starts with the context's threshold (auto: 500)
 	TRY(own_device(c, c->d_fsk, n * sizeof(FskState)));
-	TRY(own_device(c, c->d_scfg, n * sizeof(StreamCfg)));
-	const tfrec_amd_stream_config sc0 = { cfg.types_mask, cfg.thresh, cfg.filter_type, 0 };
-	c->scfg_api.assign(n, sc0);
-	c->scfg.assign(n, device_cfg(c, sc0));
-	c->n_auto = cfg.thresh == 0 ? (int)n : 0;
-	const std::vector<FskState> fsk(n, FskState{ c->scfg[0].thresh, 0, 0, -(1 << 28) });
+	const std::vector<FskState> fsk(n, FskState{ thresh_or_auto(cfg.thresh), 0, 0, -(1 << 28) });
 	HIPCHK(hipMemcpy(c->d_fsk, fsk.data(), n * sizeof(FskState), hipMemcpyHostToDevice));
-	HIPCHK(hipMemcpy(c->d_scfg, c->scfg.data(), n * sizeof(StreamCfg), hipMemcpyHostToDevice));
 	for (int k = 0; k < kSets; k++) {
 		TRY(own_device(c, c->d_fmdev[k], n * m_max * sizeof(int16_t) + 256));  // + slack: K3 reads whole dwords past an odd tail
 		TRY(own_device(c, c->d_prevdec[k], n * sizeof(uint32_t)));
 	}
-	c->in16 = c->in10x || c->resamp || c->ingest;
-	if (c->decin.on) {  // channel-rate input: no FIR, the carried state is every stream's last pair ((0, 0) at the start)
+	if (I.channel()) {  // no FIR, the carried state is every stream's last pair ((0, 0) at the start)
 		TRY(own_device(c, c->decin.d_last, n * sizeof(uint32_t)));
 		HIPCHK(hipMemset(c->decin.d_last, 0, n * sizeof(uint32_t)));
 	}
-	const size_t tail_bytes = c->in16 ? 2 * (size_t)kTailBytes : (size_t)kTailBytes;  // int16 history is twice as wide
-	// zero FIR history == u8 value 128 (decimate::decimate zeroes hist0, dsp_stuff.cpp:145-152); int16 history of the 10x
-	// path: zero, raw u8 history of its 10:1 stage (or of the resampling stage): 128
-	for (int k = 0; k < 2; k++) {
-		TRY(own_device(c, c->d_tail[k], n * tail_bytes));
-		HIPCHK(hipMemset(c->d_tail[k], c->in16 ? 0 : 0x80, n * tail_bytes));
-	}
-	if (c->in16) {  // stage 0 and the pre-stage's history: raw u8 (silence is 128) or, a rate context in another format, x
-		c->in16_stride = 4 * m_max;  // complex samples at 1.536 MS/s per stream and submit
+	// zero FIR history == u8 value 128 (decimate::decimate zeroes hist0, dsp_stuff.cpp:145-152); behind a pre-stage the history
+	// is int16, twice as wide, and zero
+	I.tail.bytes = I.in16() ? 2 * kTailBytes : kTailBytes;
+	I.tail.fill = I.in16() ? 0 : 0x80;
+	TRY(make_history(c, I.tail, 2));
+	if (I.in16()) {
+		I.in16_stride = 4 * m_max;  // complex samples at 1.536 MS/s per stream and submit
 		for (int k = 0; k < kSets; k++)
-			TRY(own_device(c, c->d_in16[k], n * c->in16_stride * sizeof(uint32_t)));
-		const bool raw = c->pre_fmt == TFREC_AMD_FMT_U8;
-		c->pre_bytes = c->in10x ? k10xTail : c->ingest ? 0 : raw ? kRateTail : kFmtTail;
-		c->pre_fill = raw ? 0x80 : 0;
-		for (int k = 0; c->pre_bytes && k < (c->in10x ? kSets : 2); k++) {  // (the 10x context has always owned one per set)
-			TRY(own_device(c, c->d_pre[k], n * c->pre_bytes));
-			HIPCHK(hipMemset(c->d_pre[k], c->pre_fill, n * c->pre_bytes));
-		}
+			TRY(own_device(c, I.d_in16[k], n * I.in16_stride * sizeof(uint32_t)));
 	}
-	if (c->resamp) {
-		std::vector<int32_t> h;
-		int t = 0;
-		if (!resample_table(c->in_p, c->in_q, h, t))  // (tfrec_amd_create_rate checked it already)
-			return TFREC_AMD_E_INVAL;
-		c->rate_t = t;
-		for (int phi = 0; phi < c->in_q; phi++) {
-			long long a = 0;
-			for (int k = 0; k < t; k++)
-				a += llabs((long long)h[(size_t)phi * t + k]);
-			c->rate_abs = std::max(c->rate_abs, a);
-		}
-		std::vector<float> hf(h.size());
-		if (rs_streamed(c->in_q, t)) {  // resample_stream_kernel's table: [t][q], h / 65536, column j the phase (j P) mod Q
-			const size_t q = (size_t)c->in_q;
-			for (size_t j = 0; j < q; j++) {
-				const size_t phi = j * (size_t)c->in_p % q;
-				for (size_t k = 0; k < (size_t)t; k++)
-					hf[k * q + j] = (float)h[phi * t + k] * (1.0f / 65536.0f);  // exact: |h| < 2^17
-			}
-		} else {
-			for (size_t i = 0; i < h.size(); i++)
-				hf[i] = (float)h[i] * (1.0f / 1024.0f);  // exact: |h| < 2^17
-		}
-		TRY(own_device(c, c->d_rtaps, hf.size() * sizeof(float)));
-		HIPCHK(hipMemcpy(c->d_rtaps, hf.data(), hf.size() * sizeof(float), hipMemcpyHostToDevice));
+	// the pre-stage's history: raw u8 (silence is 128) or, a rate context reading another format, x (silence is 0)
+	const bool raw = I.pre_fmt == TFREC_AMD_FMT_U8;
+	switch (I.kind) {
+	case PreStage::kDecim10:
+		I.pre.bytes = k10xTail;
+		I.pre.fill = 0x80;
+		TRY(make_history(c, I.pre, kSets));  // (one per set, two used: see Carried)
+		break;
+	case PreStage::kResample:
+		I.pre.bytes = raw ? kRateTail : kFmtTail;
+		I.pre.fill = raw ? 0x80 : 0;
+		TRY(make_history(c, I.pre, 2));
+		TRY(make_rate_table(c));
+		break;
+	case PreStage::kNone:
+	case PreStage::kIngest:
+	case PreStage::kChannel:
+		break;
 	}
 	return TFREC_AMD_OK;
 }
@@ -328,7 +351,7 @@ static int make_correct(tfrec_amd_ctx *c)
 	if (!o.on())
 		return TFREC_AMD_OK;
 	// the largest submit: floor(max_blocks * 32768 * P / Q) complex samples per row, up to a whole chunk; its whole windows
-	const long long n_max = ((long long)c->cfg.max_blocks * (TFREC_AMD_BLOCK_BYTES / 2) * c->in_p / c->in_q + 7) & ~7LL;
+	const long long n_max = ((long long)c->cfg.max_blocks * (TFREC_AMD_BLOCK_BYTES / 2) * c->input.rate.p / c->input.rate.q + 7) & ~7LL;
 	const size_t wins = (size_t)o.rows * (size_t)(n_max / 512);
 	o.win_stride = (int)(n_max / 512);
 	o.x_stride = (size_t)n_max * 4;
@@ -465,10 +488,9 @@ static int make_window_state(tfrec_amd_ctx *c)
 
 // One event block per set: [EventBuf | the window tables' overflow flag, 16 B | pad to 256 | events] on the device and a
 // page-locked copy (the drain's device-to-host copy of a submit is ONE copy on the stream that sets the batch period: three
-// copies were 0.45 ms of it with their gaps); the fresh header every submit starts from; the reset lists
+// copies were 0.45 ms of it with their gaps); the fresh header every submit starts from
 static int make_event_blocks(tfrec_amd_ctx *c)
 {
-	const size_t n = (size_t)c->cfg.n_streams;
 	const size_t block = kEvHeader + (size_t)c->cfg.max_events * sizeof(tfrec_amd_event);
 	EventBuf eb;
 	memset(&eb, 0, sizeof(eb));
@@ -485,36 +507,69 @@ static int make_event_blocks(tfrec_amd_ctx *c)
 	TRY(own_device(c, c->d_eb_fresh, kEvFreshBytes));
 	HIPCHK(hipMemset(c->d_eb_fresh, 0, kEvFreshBytes));
 	HIPCHK(hipMemcpy(c->d_eb_fresh, &eb, sizeof(eb), hipMemcpyHostToDevice));
-	// tfrec_amd_reset_streams: a list of at most n_streams indices per set, and the constructor state it restores
-	TRY(own_device(c, c->d_chain_init, sizeof(ChainState)));
-	const ChainState init = chain_init_state();
-	HIPCHK(hipMemcpy(c->d_chain_init, &init, sizeof(init), hipMemcpyHostToDevice));
-	for (int k = 0; k < kSets; k++) {
-		TRY(own_device(c, c->d_reset[k], n * sizeof(int32_t)));
-		TRY(own_device(c, c->d_rcfg[k], n * sizeof(StreamCfg)));
-		TRY(own_device(c, c->d_tune[k], n * sizeof(uint2)));
-		TRY(own_device(c, c->d_chan[k], n * sizeof(uint4)));
-	}
 	for (int k = 0; k < kSets; k++) {
 		TRY(own_pinned(c, c->h_evblock[k], block));
 		HIPCHK(hipHostGetDevicePointer((void **)&c->h_evblock_dev[k], c->h_evblock[k], 0));
 		c->h_eb[k] = (EventBuf *)c->h_evblock[k];
 		c->h_events[k] = (tfrec_amd_event *)(c->h_evblock[k] + kEvHeader);
-		TRY(own_pinned(c, c->h_reset[k], n * sizeof(int32_t)));
-		TRY(own_pinned(c, c->h_rcfg[k], n * sizeof(StreamCfg)));
-		TRY(own_pinned(c, c->h_tune[k], n * sizeof(uint2)));
-		TRY(own_pinned(c, c->h_chan[k], n * sizeof(uint4)));
 	}
-	c->tune_hz.assign(n, 0);
-	c->tune_inc.assign(n, 0u);
-	c->wide_hz.assign(n, 0);
-	c->wide_inc.assign(n, 0u);
-	c->row.resize(n);
-	for (size_t s = 0; s < n; s++)
-		c->row[s] = (int32_t)s;
-	c->reset_marked.assign(n, 0);
-	c->origin.assign(n, 0);
 	return TFREC_AMD_OK;
+}
+
+// a table of n_streams entries that every submit stages: the set's device copy and its page-locked source
+template <class T>
+static int make_staged(tfrec_amd_ctx *c, T *(&d)[kSets], T *(&h)[kSets])
+{
+	const size_t bytes = (size_t)c->cfg.n_streams * sizeof(T);
+	for (int k = 0; k < kSets; k++)
+		TRY(own_device(c, d[k], bytes));
+	for (int k = 0; k < kSets; k++)
+		TRY(own_pinned(c, h[k], bytes));
+	return TFREC_AMD_OK;
+}
+
+// tfrec_amd_reset_streams: the constructor state a reset restores, a list of at most n_streams indices per set, nothing marked
+static int make_restarts(tfrec_amd_ctx *c)
+{
+	Restarts &r = c->restart;
+	TRY(own_device(c, r.d_chain_init, sizeof(ChainState)));
+	const ChainState init = chain_init_state();
+	HIPCHK(hipMemcpy(r.d_chain_init, &init, sizeof(init), hipMemcpyHostToDevice));
+	TRY(make_staged(c, r.d_list, r.h_list));
+	r.marked.assign((size_t)c->cfg.n_streams, 0);
+	r.origin.assign((size_t)c->cfg.n_streams, 0);
+	return TFREC_AMD_OK;
+}
+
+// every stream starts with the context's settings
+static int make_stream_settings(tfrec_amd_ctx *c)
+{
+	const tfrec_amd_config &cfg = c->cfg;
+	StreamSettings &o = c->settings;
+	const size_t n = (size_t)cfg.n_streams;
+	const tfrec_amd_stream_config sc0 = { cfg.types_mask, cfg.thresh, cfg.filter_type, 0 };
+	o.scfg_api.assign(n, sc0);
+	o.scfg.assign(n, device_cfg(c, sc0));
+	o.n_auto = cfg.thresh == 0 ? (int)n : 0;
+	TRY(own_device(c, o.d_scfg, n * sizeof(StreamCfg)));
+	HIPCHK(hipMemcpy(o.d_scfg, o.scfg.data(), n * sizeof(StreamCfg), hipMemcpyHostToDevice));
+	return make_staged(c, o.d_rcfg, o.h_rcfg);
+}
+
+// no stream is tuned, every stream reads its own row
+static int make_stream_tunes(tfrec_amd_ctx *c)
+{
+	StreamTunes &o = c->tunes;
+	const size_t n = (size_t)c->cfg.n_streams;
+	for (Tune *t : { &o.narrow, &o.wide }) {
+		t->hz.assign(n, 0);
+		t->inc.assign(n, 0u);
+	}
+	o.row.resize(n);
+	for (size_t s = 0; s < n; s++)
+		o.row[s] = (int32_t)s;
+	TRY(make_staged(c, o.d_tune, o.h_tune));
+	return make_staged(c, o.d_chan, o.h_chan);
 }
 
 // TFREC_AMD_F_LEVELS: the level meter's state (every stream starts like its FskState), records and lane
@@ -525,7 +580,7 @@ static int make_levels(tfrec_amd_ctx *c)
 		return TFREC_AMD_OK;
 	const size_t n = (size_t)c->cfg.n_streams;
 	TRY(own_device(c, c->lev.d_state, n * sizeof(LevelState)));
-	const std::vector<LevelState> lev(n, LevelState{ c->scfg[0].thresh, 0, 0, -(1 << 28) });
+	const std::vector<LevelState> lev(n, LevelState{ c->settings.scfg[0].thresh, 0, 0, -(1 << 28) });
 	HIPCHK(hipMemcpy(c->lev.d_state, lev.data(), n * sizeof(LevelState), hipMemcpyHostToDevice));
 	for (int k = 0; k < kSets; k++)
 		TRY(own_device(c, c->lev.d_records[k], n * (size_t)c->cfg.max_blocks * sizeof(tfrec_amd_level)));
@@ -644,6 +699,9 @@ static int init_context(tfrec_amd_ctx *c)
 	if (!(c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS))
 		TRY(make_window_state(c));
 	TRY(make_event_blocks(c));
+	TRY(make_restarts(c));
+	TRY(make_stream_settings(c));
+	TRY(make_stream_tunes(c));
 	PipeCtl streams = {};
 	TRY(make_streams(c, streams));
 	TRY(make_pipes(c, streams));
@@ -684,8 +742,7 @@ struct InputSpec {
 };
 
 // The context made for an input.  Its pre-stage follows from the rate and from the format it reads (pre_fmt: S16, the corrected
-// rows, behind a correction stage): the resampling stage at another rate (resamp), the conversion of another format at the base
-// rate (ingest), none for u8 at the base rate or the channel-rate input.
+// rows, behind a correction stage): see PreStage.
 static int create_with(const tfrec_amd_config *cfg, const InputSpec &in, tfrec_amd_ctx **out)
 {
 	TRY(validate(cfg));
@@ -694,18 +751,17 @@ static int create_with(const tfrec_amd_config *cfg, const InputSpec &in, tfrec_a
 	if (!c)
 		return TFREC_AMD_E_NOMEM;
 	c->cfg = *cfg;
-	c->fmt = in.fmt;
-	c->pre_fmt = in.dc_k || in.iq_k ? TFREC_AMD_FMT_S16 : in.fmt;
+	InputPath &I = c->input;
+	I.fmt = in.fmt;
+	I.pre_fmt = in.dc_k || in.iq_k ? TFREC_AMD_FMT_S16 : in.fmt;
 	c->fix.dc.k = in.dc_k;
 	c->fix.iq.k = in.iq_k;
 	c->fix.rows = in.rows;
-	const bool base = in.p == 1 && in.q == 1;
-	c->in10x = (cfg->flags & TFREC_AMD_F_INPUT_10X) != 0;
-	c->in_p = c->in10x ? 10 : in.p;
-	c->in_q = c->in10x ? 1 : in.q;
-	c->resamp = !base && !in.decimated;
-	c->ingest = base && c->pre_fmt != TFREC_AMD_FMT_U8 && !in.decimated;
-	c->decin.on = in.decimated;
+	const bool base = in.p == 1 && in.q == 1, x10 = (cfg->flags & TFREC_AMD_F_INPUT_10X) != 0;  // (x10: the spec is the default one)
+	I.rate.p = x10 ? 10 : in.p;
+	I.rate.q = x10 ? 1 : in.q;
+	I.kind = x10 ? PreStage::kDecim10 : in.decimated ? PreStage::kChannel : !base ? PreStage::kResample
+		 : I.pre_fmt != TFREC_AMD_FMT_U8 ? PreStage::kIngest : PreStage::kNone;
 	const int rc = init_context(c);
 	if (rc != TFREC_AMD_OK) {
 		tfrec_amd_destroy(c);
@@ -789,7 +845,7 @@ int tfrec_amd_get_input_format(tfrec_amd_ctx *c, int32_t *format)
 {
 	if (!c || !format)
 		return TFREC_AMD_E_INVAL;
-	*format = c->fmt;
+	*format = c->input.fmt;
 	return TFREC_AMD_OK;
 }
 
@@ -797,7 +853,7 @@ int tfrec_amd_get_input_rate(tfrec_amd_ctx *c, int32_t *p, int32_t *q)
 {
 	if (!c || !p || !q)
 		return TFREC_AMD_E_INVAL;
-	*p = c->in_p;
-	*q = c->in_q;
+	*p = c->input.rate.p;
+	*q = c->input.rate.q;
 	return TFREC_AMD_OK;
 }

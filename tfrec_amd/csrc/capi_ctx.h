@@ -19,6 +19,9 @@ constexpr size_t kEvHeader = (kEvFreshBytes + 255) & ~(size_t)255;
 
 static thread_local char g_err[256] = "";
 
+// fm_demod.cpp:23-27: thresh 0 selects the adaptive mode, which starts at 500
+static int thresh_or_auto(int thresh) { return thresh ? thresh : 500; }
+
 static int hip_fail(hipError_t e, const char *what)
 {
 	snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
@@ -85,9 +88,8 @@ struct CapturePre {
 	bool on = false;
 	uint32_t *d_pre[kSets] = {};
 };
-// tfrec_amd_create_decimated: the carried last pair of every stream
+// tfrec_amd_create_decimated (PreStage::kChannel): the carried last pair of every stream
 struct DecIn {
-	bool on = false;
 	uint32_t *d_last = nullptr;
 };
 // tfrec_amd_enable_runs_input: the limits and, per set, the sparse submit's table ({ start, end, pool offset low, high } per run),
@@ -151,6 +153,96 @@ struct InputCorrection {
 	bool on() const { return dc.k || iq.k; }
 };
 
+// What a context's input goes through ahead of the front end, resolved once from the constructor's InputSpec (create_with).
+// Exactly these five exist; every question about the input is a test of the kind or one of InputPath's predicates.
+enum class PreStage {
+	kNone,      // u8 at 1.536 MS/s: the front end reads the rows
+	kDecim10,   // TFREC_AMD_F_INPUT_10X: the 10:1 stage (u8 at 15.36 MS/s)
+	kResample,  // tfrec_amd_create_rate, or a format at another rate: the resampling stage
+	kIngest,    // tfrec_amd_create_format at the base rate (ingest_kernel): the format conversion
+	kChannel,   // tfrec_amd_create_decimated (6n): channel-rate input, no front end at all
+};
+// A carried history of the input: `bytes` per stream, filled with `fill` after a start or a restart (bytes == 0: no such history,
+// no buffers).  The buffers flip per submit with InputPath::sel.  make_front_buffers fills the record; history(), history_read(),
+// launch_resets and launch_prestage read it, and nothing else computes a size or a fill.
+struct Carried {
+	uint8_t *buf[kSets] = {};  // [0], [1]; the 10x context's pre-stage has always owned one per set and uses two: kept, its memory totals too
+	int bytes = 0, fill = 0;
+};
+// The context's input path.  fmt is the TFREC_AMD_FMT_* of the input rows, 0 (U8) in every context of the older constructors.  A
+// context with an input correction keeps two formats: fmt stays the caller's (input_bytes, submit_host's staging, the spectrum),
+// pre_fmt is what the pre-stage reads -- S16, the corrected rows (fix) -- and what its history is kept in; everywhere else pre_fmt
+// == fmt.  The input rate is 1536000 rate.p / rate.q: 1/1, 10/1 (kDecim10), 1/4 (kChannel) or the P / Q of kResample, whose stage
+// reads rate's tap table (launch.h; t and taps are its alone).  rate_abs: max_phi sum_n |h[phi][n]| of that table, for the guard of
+// tfrec_amd_tune_streams_input (6g).
+struct InputPath {
+	PreStage kind = PreStage::kNone;
+	int32_t fmt = TFREC_AMD_FMT_U8, pre_fmt = TFREC_AMD_FMT_U8;
+	RateTable rate = { 1, 1, 0, nullptr };
+	long long rate_abs = 0;
+	// in16(): the pre-stage writes stage 0, 1.536 MS/s int16 pairs, one buffer per set, and the front end reads int16
+	uint32_t *d_in16[kSets] = {};
+	size_t in16_stride = 0;  // uint32 units
+	// the front end's FIR history (every kind owns it; kChannel never reads it) and the pre-stage's history of the raw input or of x
+	Carried tail, pre;
+	int sel = 0;  // [sel] is what this submit reads -- and what its resets restore --, [sel ^ 1] what it writes for the next one
+
+	bool in16() const { return kind == PreStage::kDecim10 || kind == PreStage::kResample || kind == PreStage::kIngest; }
+	bool channel() const { return kind == PreStage::kChannel; }
+	// tfrec_amd_tune_streams_wide / _input: a stage that mixes at the input rate
+	bool input_tune() const { return kind == PreStage::kDecim10 || kind == PreStage::kResample; }
+	// A mapped row (tfrec_amd_map_streams) is looked up by the first kernel on the rows: the pre-stage (in16()), the front end -- in its
+	// tuned form, with the set's tune table -- or the channel-rate kernel.  The last two do it as per-stream variants: a map switches to them.
+	bool front_maps() const { return kind == PreStage::kNone; }
+	bool map_needs_per_stream() const { return !in16(); }
+	uint8_t *history_read(const Carried &h) const { return h.buf[sel]; }
+	History history(const Carried &h) const { return { h.buf[sel], h.buf[sel ^ 1] }; }
+};
+
+// tfrec_amd_configure_streams: every stream's settings as the next submit uses them (scfg, the host's copy; scfg_api as the caller
+// gave them), their device copy as the last submit used them (d_scfg: written only by stream_reset_kernel, in the entries of its
+// list), and the settings that travel with a submit's reset list (d_rcfg / h_rcfg).  per_stream: a stream was configured -- from
+// then on the kernels read d_scfg (launch.scfg, taps.scfg); before, the uniform kernels run.  n_auto: streams of scfg in auto mode.
+struct StreamSettings {
+	std::vector<StreamCfg> scfg;
+	std::vector<tfrec_amd_stream_config> scfg_api;
+	StreamCfg *d_scfg = nullptr;
+	StreamCfg *d_rcfg[kSets] = {}, *h_rcfg[kSets] = {};
+	bool per_stream = false;
+	int n_auto = 0;
+};
+// One tune: every stream's tune as the next submit uses it, its phase increment per sample, and the streams with inc != 0
+struct Tune {
+	std::vector<int32_t> hz;
+	std::vector<uint32_t> inc;
+	int n_tuned = 0;
+};
+// tfrec_amd_tune_streams (narrow: at 1.536 MS/s, DESIGN.md 6d -- while a stream is tuned the tuned front end runs; before, the kernels
+// of an untuned context), tfrec_amd_tune_streams_wide / _input (wide: per input sample of the 10:1 or the resampling stage, 6e,
+// 6g) and tfrec_amd_map_streams (row: the input row every stream reads from the next submit on, the identity until a stream is
+// mapped).  Per set, filled by the submit: the {inc, phase of the submit's first sample} the front end reads (h_tune -> d_tune)
+// and the {inc, phase, row, 0} of the kernel that looks the row up (h_chan -> d_chan; InputPath::front_maps).
+struct StreamTunes {
+	Tune narrow, wide;
+	std::vector<int32_t> row;
+	bool mapped = false;
+	uint2 *d_tune[kSets] = {}, *h_tune[kSets] = {};
+	uint4 *d_chan[kSets] = {}, *h_chan[kSets] = {};
+};
+// tfrec_amd_reset_streams: streams marked since the last submit (each once), and the per-stream sample origin -- the sample_base
+// at the stream's last reset -- that the drain subtracts from end_sample.  A submit records the origins it ran with (set_origin),
+// so that the drain of an older submit still in the FIFO uses the older ones.
+struct Restarts {
+	std::vector<int32_t> pending;
+	std::vector<uint8_t> marked;
+	std::vector<long long> origin;
+	std::vector<long long> set_origin[kSets];  // empty: no submit before the set's one carried a reset
+	int32_t *d_list[kSets] = {};  // the submit's reset list on the device (stream_reset_kernel)
+	int32_t *h_list[kSets] = {};  // ... and its page-locked source
+	ChainState *d_chain_init = nullptr;  // the constructor ChainState (chain_init_state), source of every reset
+	bool any = false;  // a submit has carried a reset: set_origin is kept from then on
+};
+
 struct tfrec_amd_ctx {
 	tfrec_amd_config cfg;
 	ChainLaunch launch;
@@ -193,60 +285,10 @@ struct tfrec_amd_ctx {
 	SpectrumOut spec;
 	OccupancyOut occ;
 	int wmax = 0;
-	// tfrec_amd_configure_streams: every stream's settings as the next submit uses them (scfg, the host's copy), their device
-	// copy as the last submit used them (d_scfg: written only by stream_reset_kernel, in the entries of its list), and the
-	// settings that travel with a submit's reset list (d_rcfg / h_rcfg).  per_stream: a stream was configured -- from then on
-	// the kernels read d_scfg (launch.scfg, taps.scfg); before, the uniform kernels run.  n_auto: streams of scfg in auto mode.
-	std::vector<StreamCfg> scfg;
-	std::vector<tfrec_amd_stream_config> scfg_api;
-	StreamCfg *d_scfg = nullptr;
-	StreamCfg *d_rcfg[kSets] = {}, *h_rcfg[kSets] = {};
-	bool per_stream = false;
-	int n_auto = 0;
-	// tfrec_amd_tune_streams: every stream's tune as the next submit uses it (tune_hz, and its phase increment tune_inc), and per
-	// set the {inc, phase of the submit's first sample} the set's front end reads (h_tune -> d_tune, filled by the submit).
-	// n_tuned: streams with inc != 0 -- while there is one, the tuned front end runs; before, the kernels of an untuned context.
-	std::vector<int32_t> tune_hz;
-	std::vector<uint32_t> tune_inc;
-	uint2 *d_tune[kSets] = {}, *h_tune[kSets] = {};
-	int n_tuned = 0;
-	// tfrec_amd_map_streams / tfrec_amd_tune_streams_wide: the input row every stream reads from the next submit
-	// on (the identity until a stream is mapped: `mapped`), every stream's wide tune and its phase increment per 15.36 MS/s
-	// sample (n_wide: streams with wide_inc != 0), and per set the {inc10, phase10, row, 0} the set's 10:1 stage -- in a context
-	// of the default input the front end, for the row -- reads (h_chan -> d_chan, filled by the submit).
-	std::vector<int32_t> row;
-	bool mapped = false;
-	std::vector<int32_t> wide_hz;
-	std::vector<uint32_t> wide_inc;
-	int n_wide = 0;
-	uint4 *d_chan[kSets] = {}, *h_chan[kSets] = {};
-	uint8_t *d_tail[kSets] = {};  // FIR history: [tail_sel] is read by the next front end, [tail_sel ^ 1] written
-	int tail_sel = 0;
-	// in16: a pre-stage (launch_prestage: the 10:1 stage, the resampling stage or the format conversion) writes stage 0, 1.536 MS/s
-	// int16 pairs, one buffer per set, and the front end reads int16.  Its history of the input, if it keeps one: pre_bytes per
-	// stream, pre_fill after a start or restart, [tail_sel] read and [tail_sel ^ 1] written like d_tail (make_front_buffers).
-	uint32_t *d_in16[kSets] = {};
-	size_t in16_stride = 0;  // uint32 units
-	uint8_t *d_pre[kSets] = {};
-	int pre_bytes = 0, pre_fill = 0;
-	bool in10x = false;  // TFREC_AMD_F_INPUT_10X
-	// The input rate is 1536000 in_p / in_q, resolved once (create_with): 1/1, 10/1 with TFREC_AMD_F_INPUT_10X, or the P / Q of
-	// tfrec_amd_create_rate, whose resampling stage writes d_in16 as the 10:1 stage does, from a tap table
-	// [in_q][rate_t] (h / 1024 as floats) -- or, a table too large to stage (rs_streamed), resample_stream_kernel's (formats.h).
-	// rate_abs: max_phi sum_n |h[phi][n]| of that table, for the guard of tfrec_amd_tune_streams_input (6g), whose per-stream
-	// tune and increment per input sample live in wide_hz / wide_inc as the 10x context's wide tune does.
-	int32_t in_p = 1, in_q = 1, rate_t = 0;
-	long long rate_abs = 0;
-	bool resamp = false, in16 = false;
-	float *d_rtaps = nullptr;
-	// tfrec_amd_create_format: fmt is the TFREC_AMD_FMT_* of the input rows, 0 (U8) in every context of the older
-	// constructors.  A rate context with another format runs resample_fmt_kernel from a history of canonical x instead
-	// of the raw one; at the base rate (ingest: rate 1/1, no resampler) ingest_kernel converts the rows into d_in16.
-	// A context with an input correction keeps two formats: fmt stays the caller's (input_bytes, submit_host's staging, the
-	// spectrum), pre_fmt is what the pre-stage reads -- S16, the corrected rows (fix) -- and what its history is kept in; everywhere
-	// else pre_fmt == fmt.
-	int32_t fmt = TFREC_AMD_FMT_U8, pre_fmt = TFREC_AMD_FMT_U8;
-	bool ingest = false;
+	InputPath input;  // ---- the input, resolved once (create_with); its stage-0 buffers, histories and tap table (make_front_buffers)
+	StreamSettings settings;  // ---- per-stream tables, by concern (make_stream_settings, make_stream_tunes, make_restarts)
+	StreamTunes tunes;
+	Restarts restart;
 	InputCorrection fix;
 	// ---- window-parallel pipeline (make_window_state).  One set per submit in flight, like the front-end outputs: the window
 	// scan and the biquads of submit k+1 fill theirs while the slicers of submit k still read the other
@@ -286,18 +328,7 @@ struct tfrec_amd_ctx {
 	size_t stage_bytes[kSets] = {};
 	long long sample_base = 0;
 	int last_blocks = 0;
-	// tfrec_amd_reset_streams: streams marked since the last submit (each once), and the per-stream sample origin -- the
-	// sample_base at the stream's last reset -- that the drain subtracts from end_sample.  A submit records the origins it
-	// ran with (set_origin), so that the drain of an older submit still in the FIFO uses the older ones.
-	std::vector<int32_t> reset_pending;
-	std::vector<uint8_t> reset_marked;
-	std::vector<long long> origin;
-	std::vector<long long> set_origin[kSets];  // empty: no submit before the set's one carried a reset
-	int32_t *d_reset[kSets] = {};  // the submit's reset list on the device (stream_reset_kernel)
-	int32_t *h_reset[kSets] = {};  // ... and its page-locked source
-	ChainState *d_chain_init = nullptr;  // the constructor ChainState (chain_init_state), source of every reset
 	bool submitted = false;              // pipe[last_set].done has been recorded
-	bool any_reset = false;              // a submit has carried a reset: set_origin is kept from then on
 	bool timed = false;
 	// fm_dev samples decided by the exact slow path: all / checked against this host's libm at drain / differing from
 	// it / closer to a rounding midpoint than glibc's error bound

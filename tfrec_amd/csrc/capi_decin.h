@@ -81,7 +81,7 @@ int tfrec_amd_enable_runs_input(tfrec_amd_ctx *c, uint32_t max_runs, uint64_t ma
 {
 	if (!c)
 		return TFREC_AMD_E_INVAL;
-	if (!c->decin.on) {
+	if (!c->input.channel()) {
 		snprintf(g_err, sizeof(g_err), "sparse submits feed a channel-rate context (tfrec_amd_create_decimated)");
 		return TFREC_AMD_E_INVAL;
 	}
@@ -170,7 +170,7 @@ static int submit_runs_impl(tfrec_amd_ctx *c, const tfrec_amd_run *runs, uint32_
 		snprintf(g_err, sizeof(g_err), "sparse submits are off: call tfrec_amd_enable_runs_input before the first submit");
 		return TFREC_AMD_E_INVAL;
 	}
-	if (c->mapped) {
+	if (c->tunes.mapped) {
 		snprintf(g_err, sizeof(g_err), "a mapped context takes dense submits only");
 		return TFREC_AMD_E_INVAL;
 	}
@@ -197,7 +197,7 @@ static int submit_runs_impl(tfrec_amd_ctx *c, const tfrec_amd_run *runs, uint32_
 		uint32_t p;
 		memcpy(&p, pre + 2 * (size_t)i, 4);
 		o.h_pre[set][i] = p;
-		if (start == 0 && !c->reset_marked[r.stream])  // its own predecessor; a stream that restarts here has none
+		if (start == 0 && !c->restart.marked[r.stream])  // its own predecessor; a stream that restarts here has none
 			o.h_ov[set][r.stream] = make_uint2(1u, p);
 	}
 	for (int s = 0; s < n; s++)

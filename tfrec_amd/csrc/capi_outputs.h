@@ -75,7 +75,7 @@ int tfrec_amd_enable_capture(tfrec_amd_ctx *c, uint32_t max_runs, uint64_t max_s
 	TRY(own_device(c, o.d_base, n * sizeof(uint4)));
 	std::vector<CaptureState> st(n);
 	for (size_t s = 0; s < n; s++)  // every stream starts like its FskState (a configure ahead of the first submit is a restart)
-		st[s] = CaptureState{ c->scfg[s].thresh, 0, 0, -(1 << 28) };
+		st[s] = CaptureState{ c->settings.scfg[s].thresh, 0, 0, -(1 << 28) };
 	HIPCHK(hipMemcpy(o.d_state, st.data(), n * sizeof(CaptureState), hipMemcpyHostToDevice));
 	for (int k = 0; k < kSets; k++) {
 		TRY(own_device(c, o.d_runs[k], (size_t)max_runs * sizeof(tfrec_amd_run)));
@@ -125,8 +125,8 @@ int tfrec_amd_read_captures(tfrec_amd_ctx *c, tfrec_amd_run *runs, size_t cap_ru
 			 (unsigned long long)pairs);
 		return TFREC_AMD_E_INVAL;
 	}
-	if (!c->set_origin[set].empty()) {  // start_sample counts from the stream's last restart, as end_sample does
-		const std::vector<long long> &org = c->set_origin[set];
+	if (!c->restart.set_origin[set].empty()) {  // start_sample counts from the stream's last restart, as end_sample does
+		const std::vector<long long> &org = c->restart.set_origin[set];
 		for (size_t i = 0; i < have; i++)
 			if (tmp[i].stream < org.size())
 				tmp[i].start_sample -= org[tmp[i].stream];
@@ -150,14 +150,14 @@ int tfrec_amd_enable_spectrum(tfrec_amd_ctx *c, int32_t n_bins, int32_t frames_p
 			 "n_bins is 64, 128, 256, 512 or 1024, frames_per_record within [1, 16384], max_rows within [1, n_streams]");
 		return TFREC_AMD_E_INVAL;
 	}
-	if (c->decin.on) {
+	if (c->input.channel()) {
 		snprintf(g_err, sizeof(g_err), "the spectrum's bounds assume |x| <= 8192: a channel-rate context has none");
 		return TFREC_AMD_E_INVAL;
 	}
 	TRY(begin_side_enable(c, c->spec.lane, "spectrum"));
 	HIPCHK(hipSetDevice(c->cfg.device));
 	// the largest submit: floor(max_blocks * 32768 * P / Q) complex samples per row
-	const long long n_in = (long long)c->cfg.max_blocks * (TFREC_AMD_BLOCK_BYTES / 2) * c->in_p / c->in_q;
+	const long long n_in = (long long)c->cfg.max_blocks * (TFREC_AMD_BLOCK_BYTES / 2) * c->input.rate.p / c->input.rate.q;
 	const long long frames = n_in / n_bins;
 	const size_t rows = (size_t)max_rows, n = (size_t)n_bins;
 	const size_t records = (size_t)((frames + frames_per_record - 1) / frames_per_record);

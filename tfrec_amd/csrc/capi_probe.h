@@ -113,11 +113,11 @@ static void report_debug_stats(tfrec_amd_ctx *c, int set, int n_blocks)
 
 int tfrec_amd_read_stage0(tfrec_amd_ctx *c, int stream, int16_t *out, size_t n_pairs)
 {
-	if (!c || !out || !c->in16 || stream < 0 || stream >= c->cfg.n_streams ||
+	if (!c || !out || !c->input.in16() || stream < 0 || stream >= c->cfg.n_streams ||
 	    n_pairs > (size_t)c->last_blocks * 4 * kBlockDec)
 		return TFREC_AMD_E_INVAL;
 	TRY(tfrec_amd_sync(c));
-	HIPCHK(hipMemcpy(out, c->d_in16[c->last_set] + (size_t)stream * c->in16_stride, n_pairs * sizeof(uint32_t),
+	HIPCHK(hipMemcpy(out, c->input.d_in16[c->last_set] + (size_t)stream * c->input.in16_stride, n_pairs * sizeof(uint32_t),
 			 hipMemcpyDeviceToHost));
 	return TFREC_AMD_OK;
 }
@@ -258,7 +258,7 @@ int tfrec_amd_read_thresh(tfrec_amd_ctx *c, int stream, int *thresh)
 {
 	if (!c || !thresh || stream < 0 || stream >= c->cfg.n_streams)
 		return TFREC_AMD_E_INVAL;
-	if (!c->per_stream && c->cfg.thresh) {  // (a configured stream's FskState holds its fixed threshold: stream_reset_kernel)
+	if (!c->settings.per_stream && c->cfg.thresh) {  // (a configured stream's FskState holds its fixed threshold: stream_reset_kernel)
 		*thresh = c->cfg.thresh;
 		return TFREC_AMD_OK;
 	}

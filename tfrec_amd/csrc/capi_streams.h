@@ -4,11 +4,11 @@
 // a configure or a tune: from the next submit on the kernels read every stream's own settings
 static void use_per_stream(tfrec_amd_ctx *c)
 {
-	if (c->per_stream)
+	if (c->settings.per_stream)
 		return;
-	c->per_stream = true;
-	c->launch.scfg = c->d_scfg;
-	c->taps.scfg = c->d_scfg;
+	c->settings.per_stream = true;
+	c->launch.scfg = c->settings.d_scfg;
+	c->taps.scfg = c->settings.d_scfg;
 	for (int k = 0; k < 20; k++)  // f2: the narrow taps from now on (w: the wide ones)
 		c->taps.f2[k][0] = c->taps.f2[k][1] = (float)kNarrowTaps[k] / 65536.0f;
 }
@@ -16,9 +16,9 @@ static void use_per_stream(tfrec_amd_ctx *c)
 // mark stream s to restart at the next submit (once per submit)
 static void mark_restart(tfrec_amd_ctx *c, int32_t s)
 {
-	if (!c->reset_marked[s]) {
-		c->reset_marked[s] = 1;
-		c->reset_pending.push_back(s);
+	if (!c->restart.marked[s]) {
+		c->restart.marked[s] = 1;
+		c->restart.pending.push_back(s);
 	}
 }
 
@@ -56,13 +56,13 @@ int tfrec_amd_configure_streams(tfrec_amd_ctx *c, const int32_t *streams, const 
 	// nothing but the settings)
 	for (int i = 0; i < n; i++) {
 		const int s = streams[i];
-		c->scfg_api[s] = cfgs[i];
-		c->scfg[s] = device_cfg(c, cfgs[i]);
+		c->settings.scfg_api[s] = cfgs[i];
+		c->settings.scfg[s] = device_cfg(c, cfgs[i]);
 		mark_restart(c, s);
 	}
-	c->n_auto = 0;
-	for (const StreamCfg &d : c->scfg)
-		c->n_auto += d.autoth;
+	c->settings.n_auto = 0;
+	for (const StreamCfg &d : c->settings.scfg)
+		c->settings.n_auto += d.autoth;
 	use_per_stream(c);
 	return TFREC_AMD_OK;
 }
@@ -71,7 +71,7 @@ int tfrec_amd_get_stream_config(tfrec_amd_ctx *c, int stream, tfrec_amd_stream_c
 {
 	if (!c || !out || stream < 0 || stream >= c->cfg.n_streams)
 		return TFREC_AMD_E_INVAL;
-	*out = c->scfg_api[stream];
+	*out = c->settings.scfg_api[stream];
 	return TFREC_AMD_OK;
 }
 
@@ -89,10 +89,10 @@ static uint32_t phase_inc(int32_t tune_hz, long long p, long long q)
 }
 
 // What the three tunes share, behind their own preconditions: every stream and tune checked (out_of_range(tune_hz) writes the
-// message) before anything changes; then hz / inc of the listed streams, their restart -- a tune is a reset with a new tune,
-// exactly as a configure is one with new settings -- and the count of tuned streams.
+// message) before anything changes; then the tune's hz / inc of the listed streams, their restart -- a tune is a reset with a new
+// tune, exactly as a configure is one with new settings -- and its count of tuned streams.
 static int tune_common(tfrec_amd_ctx *c, const int32_t *streams, const int32_t *tune_hz, int n, long long p, long long q,
-		       const std::function<bool(int32_t)> &out_of_range, std::vector<int32_t> &hz, std::vector<uint32_t> &inc, int &n_tuned)
+		       const std::function<bool(int32_t)> &out_of_range, Tune &t)
 {
 	for (int i = 0; i < n; i++) {
 		TRY(check_stream(c, streams[i]));
@@ -102,13 +102,13 @@ static int tune_common(tfrec_amd_ctx *c, const int32_t *streams, const int32_t *
 	TRY(check_live(c));
 	for (int i = 0; i < n; i++) {
 		const int s = streams[i];
-		hz[s] = tune_hz[i];
-		inc[s] = phase_inc(tune_hz[i], p, q);
+		t.hz[s] = tune_hz[i];
+		t.inc[s] = phase_inc(tune_hz[i], p, q);
 		mark_restart(c, s);
 	}
-	n_tuned = 0;
-	for (const uint32_t v : inc)
-		n_tuned += v != 0;
+	t.n_tuned = 0;
+	for (const uint32_t v : t.inc)
+		t.n_tuned += v != 0;
 	return TFREC_AMD_OK;
 }
 
@@ -125,12 +125,11 @@ int tfrec_amd_tune_streams(tfrec_amd_ctx *c, const int32_t *streams, const int32
 {
 	if (!c || n < 0 || (n > 0 && (!streams || !tune_hz)))
 		return TFREC_AMD_E_INVAL;
-	if (c->decin.on) {
+	if (c->input.channel()) {
 		snprintf(g_err, sizeof(g_err), "the tunes are defined ahead of process_iq: a channel-rate context has none");
 		return TFREC_AMD_E_INVAL;
 	}
-	TRY(tune_common(c, streams, tune_hz, n, 1, 1, [](int32_t hz) { return outside_limit(hz, kTuneLimit); }, c->tune_hz, c->tune_inc,
-			c->n_tuned));
+	TRY(tune_common(c, streams, tune_hz, n, 1, 1, [](int32_t hz) { return outside_limit(hz, kTuneLimit); }, c->tunes.narrow));
 	if (n > 0)
 		use_per_stream(c);
 	return TFREC_AMD_OK;
@@ -140,7 +139,7 @@ int tfrec_amd_get_stream_tune(tfrec_amd_ctx *c, int stream, int32_t *tune_hz)
 {
 	if (!c || !tune_hz || stream < 0 || stream >= c->cfg.n_streams)
 		return TFREC_AMD_E_INVAL;
-	*tune_hz = c->tune_hz[stream];
+	*tune_hz = c->tunes.narrow.hz[stream];
 	return TFREC_AMD_OK;
 }
 
@@ -160,11 +159,11 @@ int tfrec_amd_map_streams(tfrec_amd_ctx *c, const int32_t *streams, const int32_
 	if (n == 0)
 		return TFREC_AMD_OK;
 	for (int i = 0; i < n; i++) {
-		c->row[streams[i]] = inputs[i];
+		c->tunes.row[streams[i]] = inputs[i];
 		mark_restart(c, streams[i]);
 	}
-	c->mapped = true;
-	if (!c->in16)  // (the mapped front end is a per-stream variant; with the 10x input or a rate the pre-stage maps)
+	c->tunes.mapped = true;
+	if (c->input.map_needs_per_stream())
 		use_per_stream(c);
 	return TFREC_AMD_OK;
 }
@@ -173,7 +172,7 @@ int tfrec_amd_get_stream_input(tfrec_amd_ctx *c, int stream, int32_t *input)
 {
 	if (!c || !input || stream < 0 || stream >= c->cfg.n_streams)
 		return TFREC_AMD_E_INVAL;
-	*input = c->row[stream];
+	*input = c->tunes.row[stream];
 	return TFREC_AMD_OK;
 }
 
@@ -181,20 +180,19 @@ int tfrec_amd_tune_streams_wide(tfrec_amd_ctx *c, const int32_t *streams, const 
 {
 	if (!c || n < 0 || (n > 0 && (!streams || !tune_hz)))
 		return TFREC_AMD_E_INVAL;
-	if (!c->in10x) {
+	if (c->input.kind != PreStage::kDecim10) {
 		snprintf(g_err, sizeof(g_err), "the wide tune acts ahead of the 10:1 stage: the context needs the 15.36 MS/s input flag%s",
-			 c->resamp ? " (the tune ahead of the resampling stage is tfrec_amd_tune_streams_input)" : "");
+			 c->input.kind == PreStage::kResample ? " (the tune ahead of the resampling stage is tfrec_amd_tune_streams_input)" : "");
 		return TFREC_AMD_E_INVAL;
 	}
-	return tune_common(c, streams, tune_hz, n, 10, 1, [](int32_t hz) { return outside_limit(hz, kTuneWideLimit); }, c->wide_hz,
-			   c->wide_inc, c->n_wide);
+	return tune_common(c, streams, tune_hz, n, 10, 1, [](int32_t hz) { return outside_limit(hz, kTuneWideLimit); }, c->tunes.wide);
 }
 
 int tfrec_amd_get_stream_tune_wide(tfrec_amd_ctx *c, int stream, int32_t *tune_hz)
 {
 	if (!c || !tune_hz || stream < 0 || stream >= c->cfg.n_streams)
 		return TFREC_AMD_E_INVAL;
-	*tune_hz = c->wide_hz[stream];
+	*tune_hz = c->tunes.wide.hz[stream];
 	return TFREC_AMD_OK;
 }
 
@@ -203,15 +201,15 @@ int tfrec_amd_tune_streams_input(tfrec_amd_ctx *c, const int32_t *streams, const
 {
 	if (!c || n < 0 || (n > 0 && (!streams || !tune_hz)))
 		return TFREC_AMD_E_INVAL;
-	if (c->in10x)
+	if (c->input.kind == PreStage::kDecim10)
 		return tfrec_amd_tune_streams_wide(c, streams, tune_hz, n);
-	if (!c->resamp) {
+	if (!c->input.input_tune()) {
 		snprintf(g_err, sizeof(g_err), "the input-rate tune acts ahead of a resampling or 10:1 stage, and this context has none: "
 					       "tfrec_amd_tune_streams tunes its 1.536 MS/s input");
 		return TFREC_AMD_E_INVAL;
 	}
-	const long long p = c->in_p, q = c->in_q;
-	if (((c->rate_abs * 11585) >> 16) >= 32768) {  // (no accepted rate comes near: 19137 at most)
+	const long long p = c->input.rate.p, q = c->input.rate.q;
+	if (((c->input.rate_abs * 11585) >> 16) >= 32768) {  // (no accepted rate comes near: 19137 at most)
 		snprintf(g_err, sizeof(g_err), "input rate %lld/%lld: the int16 store of a tuned stream could wrap", p, q);
 		return TFREC_AMD_E_INVAL;
 	}
@@ -222,7 +220,7 @@ int tfrec_amd_tune_streams_input(tfrec_amd_ctx *c, const int32_t *streams, const
 			 (1536000LL * p + 2 * q - 1) / (2 * q));
 		return true;
 	};
-	return tune_common(c, streams, tune_hz, n, p, q, outside, c->wide_hz, c->wide_inc, c->n_wide);
+	return tune_common(c, streams, tune_hz, n, p, q, outside, c->tunes.wide);
 }
 
 int tfrec_amd_get_stream_tune_input(tfrec_amd_ctx *c, int stream, int32_t *tune_hz)

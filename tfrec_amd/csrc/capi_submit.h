@@ -78,11 +78,6 @@ __global__ __launch_bounds__(64) void stream_reset_kernel(StreamReset R)
 }
 }  // namespace tfrec
 
-// A carried history (d_tail, d_pre) flips per submit: [tail_sel] is what this submit reads -- and what its resets restore --,
-// [tail_sel ^ 1] what it writes for the next one
-static uint8_t *history_read(const tfrec_amd_ctx *c, uint8_t *const (&buf)[kSets]) { return buf[c->tail_sel]; }
-static History history(const tfrec_amd_ctx *c, uint8_t *const (&buf)[kSets]) { return { history_read(c, buf), buf[c->tail_sel ^ 1] }; }
-
 // The set's front-end output for a submit of n_blocks blocks: what the launchers from the front end to the chains work on
 static FrontOut front_out(const tfrec_amd_ctx *c, int set, int n_blocks)
 {
@@ -107,37 +102,22 @@ static int launch_resets(tfrec_amd_ctx *c, int set)
 		for (const SideLane *l : { &c->lev.lane, &c->cap.lane })
 			if (l->on)
 				HIPCHK(hipStreamWaitEvent(fs, l->written[c->last_set], 0));
-	const int nl = (int)c->reset_pending.size();
-	memcpy(c->h_reset[set], c->reset_pending.data(), (size_t)nl * sizeof(int32_t));  // (the set's last copy was drained)
+	const InputPath &I = c->input;
+	const Restarts &r = c->restart;
+	const StreamSettings &S = c->settings;
+	const int nl = (int)r.pending.size();
+	memcpy(r.h_list[set], r.pending.data(), (size_t)nl * sizeof(int32_t));  // (the set's last copy was drained)
 	for (int i = 0; i < nl; i++)  // a reset stream restarts with its own current settings
-		c->h_rcfg[set][i] = c->scfg[c->reset_pending[i]];
-	HIPCHK(hipMemcpyAsync(c->d_reset[set], c->h_reset[set], (size_t)nl * sizeof(int32_t), hipMemcpyHostToDevice, fs));
-	HIPCHK(hipMemcpyAsync(c->d_rcfg[set], c->h_rcfg[set], (size_t)nl * sizeof(StreamCfg), hipMemcpyHostToDevice, fs));
-	StreamReset R;
-	memset(&R, 0, sizeof(R));
-	R.list = c->d_reset[set];
-	R.n_list = nl;
-	R.n_streams = c->cfg.n_streams;
-	R.tail = history_read(c, c->d_tail);  // the buffer this submit's front end reads
-	R.tail_bytes = c->in16 ? 2 * kTailBytes : kTailBytes;
-	R.tail_fill = c->in16 ? 0 : 0x80;  // as make_front_buffers: int16 zero, or u8 128
-	R.pre = history_read(c, c->d_pre);
-	R.pre_bytes = c->pre_bytes;
-	R.pre_fill = c->pre_fill;
-	R.fsk = c->d_fsk;
-	R.lev = c->lev.d_state;
-	R.cap = c->cap.d_state;
-	R.cfgs = c->d_rcfg[set];
-	R.scfg = c->d_scfg;
-	R.n_active = c->launch.n_active;
-	for (int a = 0; a < c->launch.n_active; a++)
-		R.states[a] = c->launch.states[a];
-	R.chain_init = c->d_chain_init;
-	R.tcarry = c->d_tcarry;
-	R.whbx = c->d_whbx;
-	R.whbcarry = c->d_whbcarry;
-	R.whbX = c->d_whbX;
-	R.last = c->decin.d_last;
+		S.h_rcfg[set][i] = S.scfg[r.pending[i]];
+	HIPCHK(hipMemcpyAsync(r.d_list[set], r.h_list[set], (size_t)nl * sizeof(int32_t), hipMemcpyHostToDevice, fs));
+	HIPCHK(hipMemcpyAsync(S.d_rcfg[set], S.h_rcfg[set], (size_t)nl * sizeof(StreamCfg), hipMemcpyHostToDevice, fs));
+	StreamReset R = { .list = r.d_list[set], .n_list = nl, .n_streams = c->cfg.n_streams,
+			  .tail = I.history_read(I.tail), .tail_bytes = I.tail.bytes, .tail_fill = I.tail.fill,  // what this submit's front end
+			  .pre = I.history_read(I.pre), .pre_bytes = I.pre.bytes, .pre_fill = I.pre.fill,        // and pre-stage read
+			  .fsk = c->d_fsk, .lev = c->lev.d_state, .cap = c->cap.d_state, .cfgs = S.d_rcfg[set], .scfg = S.d_scfg,
+			  .n_active = c->launch.n_active, .states = {}, .chain_init = r.d_chain_init, .tcarry = c->d_tcarry,
+			  .whbx = c->d_whbx, .whbcarry = c->d_whbcarry, .whbX = c->d_whbX, .last = c->decin.d_last };
+	std::copy_n(c->launch.states, R.n_active, R.states);
 	hipLaunchKernelGGL(tfrec::stream_reset_kernel, dim3(nl), dim3(64), 0, fs, R);
 	HIPCHK(hipGetLastError());
 	return TFREC_AMD_OK;
@@ -150,11 +130,11 @@ static int launch_resets(tfrec_amd_ctx *c, int set)
 static int stage_tune(tfrec_amd_ctx *c, int set)
 {
 	for (int s = 0; s < c->cfg.n_streams; s++) {
-		const uint32_t inc = c->tune_inc[s];
-		const long long n0 = c->reset_marked[s] ? 0 : 4 * (c->sample_base - c->origin[s]);
-		c->h_tune[set][s] = make_uint2(inc, (uint32_t)((uint64_t)n0 * inc));
+		const uint32_t inc = c->tunes.narrow.inc[s];
+		const long long n0 = c->restart.marked[s] ? 0 : 4 * (c->sample_base - c->restart.origin[s]);
+		c->tunes.h_tune[set][s] = make_uint2(inc, (uint32_t)((uint64_t)n0 * inc));
 	}
-	HIPCHK(hipMemcpyAsync(c->d_tune[set], c->h_tune[set], (size_t)c->cfg.n_streams * sizeof(uint2), hipMemcpyHostToDevice,
+	HIPCHK(hipMemcpyAsync(c->tunes.d_tune[set], c->tunes.h_tune[set], (size_t)c->cfg.n_streams * sizeof(uint2), hipMemcpyHostToDevice,
 			      c->pipe[set].fs));
 	return TFREC_AMD_OK;
 }
@@ -165,11 +145,11 @@ static int stage_tune(tfrec_amd_ctx *c, int set)
 static int stage_chan(tfrec_amd_ctx *c, int set)
 {
 	for (int s = 0; s < c->cfg.n_streams; s++) {
-		const uint32_t inc = c->wide_inc[s];
-		const long long n0 = c->reset_marked[s] ? 0 : 4 * (c->sample_base - c->origin[s]) * c->in_p / c->in_q;
-		c->h_chan[set][s] = make_uint4(inc, (uint32_t)((uint64_t)n0 * inc), (uint32_t)c->row[s], 0u);
+		const uint32_t inc = c->tunes.wide.inc[s];
+		const long long n0 = c->restart.marked[s] ? 0 : 4 * (c->sample_base - c->restart.origin[s]) * c->input.rate.p / c->input.rate.q;
+		c->tunes.h_chan[set][s] = make_uint4(inc, (uint32_t)((uint64_t)n0 * inc), (uint32_t)c->tunes.row[s], 0u);
 	}
-	HIPCHK(hipMemcpyAsync(c->d_chan[set], c->h_chan[set], (size_t)c->cfg.n_streams * sizeof(uint4), hipMemcpyHostToDevice,
+	HIPCHK(hipMemcpyAsync(c->tunes.d_chan[set], c->tunes.h_chan[set], (size_t)c->cfg.n_streams * sizeof(uint4), hipMemcpyHostToDevice,
 			      c->pipe[set].fs));
 	return TFREC_AMD_OK;
 }
@@ -177,9 +157,9 @@ static int stage_chan(tfrec_amd_ctx *c, int set)
 // rows of the input batch the streams read: 1 + the highest one mapped
 static int rows_in_use(const tfrec_amd_ctx *c)
 {
-	if (!c->mapped)
+	if (!c->tunes.mapped)
 		return c->cfg.n_streams;
-	return 1 + *std::max_element(c->row.begin(), c->row.end());
+	return 1 + *std::max_element(c->tunes.row.begin(), c->tunes.row.end());
 }
 
 // Bytes of one input row of a submit of n_blocks blocks: n_blocks * 32768 * P / Q complex samples of 2, 4 or 8 bytes each.
@@ -189,14 +169,14 @@ static int input_bytes(const tfrec_amd_ctx *c, int n_blocks, size_t *bytes)
 {
 	if (n_blocks < 1)
 		return TFREC_AMD_E_INVAL;
-	const long long p = c->in_p, q = c->in_q;
+	const long long p = c->input.rate.p, q = c->input.rate.q;
 	const long long num = (long long)n_blocks * (TFREC_AMD_BLOCK_BYTES / 2) * p;
-	if (n_blocks % rs_unit(c->in_q) != 0) {
+	if (n_blocks % rs_unit(c->input.rate.q) != 0) {
 		snprintf(g_err, sizeof(g_err), "%d blocks at the input rate %lld/%lld: a submit holds a multiple of %d blocks", n_blocks, p, q,
-			 rs_unit(c->in_q));
+			 rs_unit(c->input.rate.q));
 		return TFREC_AMD_E_INVAL;
 	}
-	*bytes = (size_t)(num / q) * fmt_sample_bytes(c->fmt);
+	*bytes = (size_t)(num / q) * fmt_sample_bytes(c->input.fmt);
 	return TFREC_AMD_OK;
 }
 
@@ -204,17 +184,25 @@ static int input_bytes(const tfrec_amd_ctx *c, int n_blocks, size_t *bytes)
 // where a stream is mapped or has an input-rate tune (stage_chan), or nullptr.
 static int launch_prestage(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, size_t stride, int n_blocks, const uint4 *chan)
 {
+	const InputPath &I = c->input;
 	hipStream_t fs = c->pipe[set].fs;
 	const int n = c->cfg.n_streams;
-	const History hist = history(c, c->d_pre);
-	uint32_t *out = c->d_in16[set];
-	if (c->in10x)  // 15.36 MS/s u8 -> 1.536 MS/s int16 pairs
-		HIPCHK(launch_decim10(fs, d_iq, stride, n, n_blocks, hist, out, c->in16_stride, chan));
-	else if (c->ingest)  // 1.536 MS/s in another format -> x as int16 pairs
-		HIPCHK(launch_ingest(fs, c->pre_fmt, d_iq, stride, n, n_blocks, out, c->in16_stride, chan));
-	else  // 1536000 P / Q S/s in any format -> 1.536 MS/s int16 pairs
-		HIPCHK(launch_resample(fs, c->pre_fmt, d_iq, stride, n, n_blocks, { .p = c->in_p, .q = c->in_q, .t = c->rate_t, .taps = c->d_rtaps },
-				       hist, out, c->in16_stride, chan, c->n_wide != 0));
+	const History hist = I.history(I.pre);
+	uint32_t *out = I.d_in16[set];
+	switch (I.kind) {  // (no default: a new kind does not compile until it is handled)
+	case PreStage::kDecim10:  // 15.36 MS/s u8 -> 1.536 MS/s int16 pairs
+		HIPCHK(launch_decim10(fs, d_iq, stride, n, n_blocks, hist, out, I.in16_stride, chan));
+		break;
+	case PreStage::kIngest:  // 1.536 MS/s in another format -> x as int16 pairs
+		HIPCHK(launch_ingest(fs, I.pre_fmt, d_iq, stride, n, n_blocks, out, I.in16_stride, chan));
+		break;
+	case PreStage::kResample:  // 1536000 P / Q S/s in any format -> 1.536 MS/s int16 pairs
+		HIPCHK(launch_resample(fs, I.pre_fmt, d_iq, stride, n, n_blocks, I.rate, hist, out, I.in16_stride, chan, c->tunes.wide.n_tuned != 0));
+		break;
+	case PreStage::kNone:
+	case PreStage::kChannel:  // (no pre-stage: submit_common asks in16() first)
+		break;
+	}
 	return TFREC_AMD_OK;
 }
 
@@ -255,7 +243,7 @@ static int launch_correct_rows(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, s
 				.dc_sums = o.d_dc_sums, .iq_sums = o.d_iq_sums, .mom = o.d_mom,
 				.dc_ring = o.dc.d_ring, .dc_state = o.dc.d_state, .iq_ring = o.iq.d_ring, .iq_state = o.iq.d_state,
 				.d = o.dc.d_table[set], .tg = o.iq.d_table[set], .out = o.d_x[set], .out_stride = o.x_stride };
-	HIPCHK(launch_correct(fs, c->fmt, d_iq, stride, rows, n_in, b));
+	HIPCHK(launch_correct(fs, c->input.fmt, d_iq, stride, rows, n_in, b));
 	o.set_rows[set] = rows;
 	o.set_windows[set] = (int)(n_in / 512);
 	return TFREC_AMD_OK;
@@ -268,16 +256,16 @@ static int launch_decin_front(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, si
 	hipStream_t fs = c->pipe[set].fs;
 	const RunsIn &o = c->runs_in;
 	uint32_t *last = c->decin.d_last;
-	const int thresh = c->cfg.thresh ? c->cfg.thresh : 500;
-	const StreamCfg *scfg = c->per_stream ? c->d_scfg : nullptr;
+	const int thresh = thresh_or_auto(c->cfg.thresh);
+	const StreamCfg *scfg = c->settings.per_stream ? c->settings.d_scfg : nullptr;
 	if (runs) {
 		const RunsTables r = { .tab = o.d_tab[set], .pool = o.d_pool[set], .pre = o.d_pre[set], .first = o.d_first[set], .ov = o.d_ov[set] };
 		HIPCHK(launch_decin_runs(fs, r, out, last, thresh, scfg));
 		return TFREC_AMD_OK;
 	}
-	if (c->mapped)  // the kernel looks the row up
+	if (c->tunes.mapped)  // the kernel looks the row up
 		TRY(stage_chan(c, set));
-	HIPCHK(launch_decin(fs, d_iq, stride, c->mapped ? c->d_chan[set] : nullptr, out, last, thresh, scfg));
+	HIPCHK(launch_decin(fs, d_iq, stride, c->tunes.mapped ? c->tunes.d_chan[set] : nullptr, out, last, thresh, scfg));
 	return TFREC_AMD_OK;
 }
 
@@ -304,7 +292,9 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	const int set = (c->head + c->inflight) % kSets;  // this submit's buffer set, events and timing events
 	const PipeCtl &P = c->pipe[set];
 	const FrontOut out = front_out(c, set, n_blocks);
-	const StreamCfg *scfg = c->per_stream ? c->d_scfg : nullptr;
+	const InputPath &I = c->input;
+	const StreamTunes &T = c->tunes;
+	const StreamCfg *scfg = c->settings.per_stream ? c->settings.d_scfg : nullptr;
 	hipEvent_t *ev = c->ev[set];
 	// Front end on its own stream: it starts when the caller's stream has produced the input, and may overlap the
 	// chains of the previous submit (different buffer set; the set's previous user was drained, see the FIFO rule).
@@ -321,10 +311,10 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		if (input_on_fs)
 			HIPCHK(hipEventRecord(c->ev_in[set], fs));
 		HIPCHK(lane_after(c->spec.lane, c->ev_in[set]));
-		const SpectrumBufs b = { .n_rows = std::min(rows_in_use(c), c->spec.rows), .n_in = (long)(row_bytes / fmt_sample_bytes(c->fmt)),
+		const SpectrumBufs b = { .n_rows = std::min(rows_in_use(c), c->spec.rows), .n_in = (long)(row_bytes / fmt_sample_bytes(I.fmt)),
 					 .n_bins = c->spec.n, .g = c->spec.g, .max_records = c->spec.max_records,
 					 .sum = c->spec.d_sum[set], .peak = c->spec.d_peak[set], .nfr = c->spec.d_nf[set] };
-		HIPCHK(launch_spectrum(c->spec.lane.st, c->fmt, (const uint8_t *)d_iq, stride, b));
+		HIPCHK(launch_spectrum(c->spec.lane.st, I.fmt, (const uint8_t *)d_iq, stride, b));
 		if (c->occ.lane.on)  // the occupancy detector: on the records just queued, in stream order behind their kernel
 			HIPCHK(launch_occupancy(c->spec.lane.st, b, c->occ.ratio, c->occ.rel, c->occ.d_recs[set], c->occ.d_bits[set]));
 		HIPCHK(lane_written(c->spec.lane, set));
@@ -334,36 +324,37 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	HIPCHK(hipMemcpyAsync(c->d_eb[set], c->d_eb_fresh, kEvFreshBytes, hipMemcpyDeviceToDevice, fs));  // (+ the overflow flag)
 	if (timing)
 		HIPCHK(hipEventRecord(ev[kEvSubmit], fs));
-	const bool resets = !c->reset_pending.empty();
+	const bool resets = !c->restart.pending.empty();
 	if (resets)
 		TRY(launch_resets(c, set));
-	if (c->decin.on)
+	if (I.channel())
 		TRY(launch_decin_front(c, set, (const uint8_t *)d_iq, stride, out, runs));
 	const uint8_t *fin = (const uint8_t *)d_iq;
 	size_t fstride = stride;
-	// a mapped or wide-tuned context: the 10:1 stage's tuned kernel, or -- default input -- the front end that looks up the rows
-	// (a rate context: the resampling stage looks the row up, as the 10:1 stage does)
-	const bool chan10 = c->in16 && (c->mapped || c->n_wide), chan_front = !c->in16 && c->mapped && !c->decin.on;
-	if (chan10 || chan_front)
+	// Who reads the set's {inc, phase, row, 0}: the pre-stage, for a mapped row or an input-rate tune -- or, a mapped context of
+	// the default input, the front end, which then runs in its tuned form (the channel-rate kernel: launch_decin_front)
+	const bool chan_pre = I.in16() && (T.mapped || T.wide.n_tuned), chan_front = I.front_maps() && T.mapped;
+	const bool tuned = T.narrow.n_tuned || chan_front;
+	if (chan_pre || chan_front)
 		TRY(stage_chan(c, set));
-	if (c->in16) {  // ... then the standard cascade on int16 input
+	if (I.in16()) {  // ... then the standard cascade on int16 input
 		const uint8_t *pin = (const uint8_t *)d_iq;
 		size_t pstride = stride;
 		if (c->fix.on()) {  // the input correction first: the pre-stage reads the corrected rows, an S16 input
-			TRY(launch_correct_rows(c, set, pin, stride, (long)(row_bytes / fmt_sample_bytes(c->fmt))));
+			TRY(launch_correct_rows(c, set, pin, stride, (long)(row_bytes / fmt_sample_bytes(I.fmt))));
 			pin = c->fix.d_x[set];
 			pstride = c->fix.x_stride;
 		}
-		TRY(launch_prestage(c, set, pin, pstride, n_blocks, chan10 ? c->d_chan[set] : nullptr));
-		fin = (const uint8_t *)c->d_in16[set];
-		fstride = c->in16_stride * sizeof(uint32_t);
+		TRY(launch_prestage(c, set, pin, pstride, n_blocks, chan_pre ? T.d_chan[set] : nullptr));
+		fin = (const uint8_t *)I.d_in16[set];
+		fstride = I.in16_stride * sizeof(uint32_t);
 	}
-	if (c->n_tuned || chan_front)
+	if (tuned)
 		TRY(stage_tune(c, set));
-	if (!c->decin.on)
-		HIPCHK(launch_frontend(fs, fin, fstride, history(c, c->d_tail), out, c->cfg.thresh ? c->cfg.thresh : 500, c->taps, c->in16,
-				       (c->n_tuned || chan_front) ? c->d_tune[set] : nullptr, chan_front ? c->d_chan[set] : nullptr));
-	if (c->n_auto)  // auto threshold: per-block thresholds rewrite the trigger mask (fm_demod.cpp:58-73)
+	if (!I.channel())
+		HIPCHK(launch_frontend(fs, fin, fstride, I.history(I.tail), out, thresh_or_auto(c->cfg.thresh), c->taps, I.in16(),
+				       tuned ? T.d_tune[set] : nullptr, chan_front ? T.d_chan[set] : nullptr));
+	if (c->settings.n_auto)  // auto threshold: per-block thresholds rewrite the trigger mask (fm_demod.cpp:58-73)
 		HIPCHK(launch_threshold(fs, out, c->d_fsk, c->wmax, scfg));
 	if (timing)
 		HIPCHK(hipEventRecord(ev[kEvFrontDone], fs));
@@ -374,7 +365,7 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	HIPCHK(hipEventRecord(P.ev_front, fs));
 	if (c->lev.lane.on) {  // the level meter: behind the front end (the mask is final), beside the chains, on its own low-priority stream
 		HIPCHK(lane_after(c->lev.lane, P.ev_front));
-		HIPCHK(launch_levels(c->lev.lane.st, out, c->lev.d_state, c->d_scfg, c->lev.d_records[set]));
+		HIPCHK(launch_levels(c->lev.lane.st, out, c->lev.d_state, c->settings.d_scfg, c->lev.d_records[set]));
 		HIPCHK(lane_written(c->lev.lane, set));
 		c->lev.set_blocks[set] = n_blocks;
 	}
@@ -383,7 +374,7 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		const CaptureBufs b = { .state = c->cap.d_state, .stage = c->cap.d_stage, .stage_cap = c->cap.stage_cap, .cnt = c->cap.d_cnt,
 					.base = c->cap.d_base, .hdr = c->cap.d_hdr[set], .runs = c->cap.d_runs[set], .pool = c->cap.d_pool[set],
 					.max_runs = c->cap.max_runs, .max_samples = c->cap.max_samples };
-		HIPCHK(launch_capture(c->cap.lane.st, out, c->sample_base, b, c->d_scfg));
+		HIPCHK(launch_capture(c->cap.lane.st, out, c->sample_base, b, c->settings.d_scfg));
 		if (c->cap_pre.on)  // the pair ahead of every run: behind the copy kernel, which wrote the table
 			HIPCHK(launch_capture_pre(c->cap.lane.st, out, c->sample_base, b, c->cap_pre.d_pre[set]));
 		HIPCHK(lane_written(c->cap.lane, set));
@@ -421,21 +412,20 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 	HIPCHK(hipEventRecord(c->copied[set], c->cpy));
 	if (timing)
 		c->timed = true;
-	if (resets) {
-		for (int32_t r : c->reset_pending) {
-			c->origin[r] = c->sample_base;
-			c->reset_marked[r] = 0;
-		}
-		c->reset_pending.clear();
+	Restarts &R = c->restart;
+	for (int32_t s : R.pending) {
+		R.origin[s] = c->sample_base;
+		R.marked[s] = 0;
 	}
+	R.pending.clear();
 	// (until the first reset the origins are all zero: nothing is recorded, and the drain subtracts nothing)
-	c->any_reset = c->any_reset || resets;
-	if (c->any_reset)
-		c->set_origin[set] = c->origin;
+	R.any = R.any || resets;
+	if (R.any)
+		R.set_origin[set] = R.origin;
 	c->submitted = true;
 	c->inflight++;
 	c->last_set = set;
-	c->tail_sel ^= 1;
+	c->input.sel ^= 1;
 	c->sample_base += (long long)n_blocks * kBlockDec;
 	c->last_blocks = n_blocks;
 	guard.ok = true;
@@ -563,8 +553,8 @@ int tfrec_amd_drain_events(tfrec_amd_ctx *c, tfrec_amd_event *out, int cap, int 
 			if (tmp[i].status != kStatusDead)
 				tmp[live++] = tmp[i];
 	}
-	if (!c->set_origin[set].empty()) {  // end_sample counts from the stream's last reset: flushes and BITS chunks (window opens) alike
-		const std::vector<long long> &org = c->set_origin[set];
+	if (!c->restart.set_origin[set].empty()) {  // end_sample counts from the stream's last reset: flushes and BITS chunks (window opens) alike
+		const std::vector<long long> &org = c->restart.set_origin[set];
 		for (uint32_t i = 0; i < live; i++)
 			if (tmp[i].stream < org.size())
 				tmp[i].end_sample -= org[tmp[i].stream];

@@ -718,30 +718,27 @@ hipError_t launch_frontend(hipStream_t st, const uint8_t *iq, size_t stride, His
 	FrontTapsTune tt;  // tune != nullptr (a stream is tuned; implies scfg): the tuned kernels
 	static_cast<FrontTapsCfg &>(tt) = taps;
 	tt.tune = tune;
-	if (chan && tune && !in16) {  // a mapped context (default input): the tuned kernel that looks up every stream's input row
-		FrontTapsMap tm;
-		static_cast<FrontTapsTune &>(tm) = tt;
-		tm.chan = chan;
-		hipLaunchKernelGGL((frontend_kernel<false, true, true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail.in, tail.out,
-				   o.dec, o.dec_stride, o.mask, o.mask_stride, o.prevdec, thresh, tm, n_streams, persist);
-	} else if (tune && in16)
-		hipLaunchKernelGGL((frontend_kernel<true, true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail.in, tail.out,
-				   o.dec, o.dec_stride, o.mask, o.mask_stride, o.prevdec, thresh, tt, n_streams, persist);
+	FrontTapsMap tm;  // chan != nullptr too, default input: the tuned kernel that looks up every stream's input row
+	static_cast<FrontTapsTune &>(tm) = tt;
+	tm.chan = chan;
+	const auto launch = [&](auto kernel, const auto &taps_rec) {  // (the kernel's own taps record, passed by value)
+		hipLaunchKernelGGL(kernel, grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail.in, tail.out, o.dec, o.dec_stride, o.mask,
+				   o.mask_stride, o.prevdec, thresh, taps_rec, n_streams, persist);
+	};
+	if (chan && tune && !in16)
+		launch(frontend_kernel<false, true, true, true>, tm);
+	else if (tune && in16)
+		launch(frontend_kernel<true, true, true>, tt);
 	else if (tune)
-		hipLaunchKernelGGL((frontend_kernel<false, true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail.in, tail.out,
-				   o.dec, o.dec_stride, o.mask, o.mask_stride, o.prevdec, thresh, tt, n_streams, persist);
+		launch(frontend_kernel<false, true, true>, tt);
 	else if (taps.scfg && in16)
-		hipLaunchKernelGGL((frontend_kernel<true, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail.in, tail.out,
-				   o.dec, o.dec_stride, o.mask, o.mask_stride, o.prevdec, thresh, taps, n_streams, persist);
+		launch(frontend_kernel<true, true>, taps);
 	else if (taps.scfg)
-		hipLaunchKernelGGL((frontend_kernel<false, true>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail.in, tail.out,
-				   o.dec, o.dec_stride, o.mask, o.mask_stride, o.prevdec, thresh, taps, n_streams, persist);
+		launch(frontend_kernel<false, true>, taps);
 	else if (in16)
-		hipLaunchKernelGGL((frontend_kernel<true, false>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail.in, tail.out,
-				   o.dec, o.dec_stride, o.mask, o.mask_stride, o.prevdec, thresh, narrow, n_streams, persist);
+		launch(frontend_kernel<true, false>, narrow);
 	else
-		hipLaunchKernelGGL((frontend_kernel<false, false>), grid, dim3(kFrontThreads), 0, st, iq, stride, m_total, tail.in, tail.out,
-				   o.dec, o.dec_stride, o.mask, o.mask_stride, o.prevdec, thresh, narrow, n_streams, persist);
+		launch(frontend_kernel<false, false>, narrow);
 	return hipGetLastError();
 }
 
