@@ -637,6 +637,66 @@ int tfrec_amd_enable_runs_input(tfrec_amd_ctx *ctx, uint32_t max_runs, uint64_t 
 int tfrec_amd_submit_runs(tfrec_amd_ctx *ctx, const tfrec_amd_run *runs, uint32_t n_runs, const int16_t *samples, uint64_t n_pairs,
 			  const int16_t *pre, int n_blocks);
 
+/* Burst meter (tfrec_amd_enable_burst_meter): for every run of the recorder's table -- every trigger window, decoded or
+ * not, of any protocol or none -- where its carrier sits relative to the receive frequency and how wide its FSK is: an exact integer
+ * histogram of the instantaneous frequency.  It sits on the recorder as tfrec_amd_enable_capture_pre does.  There is no reference
+ * counterpart: this text is normative, tfrec_amd/burst.py restates it.  Exact integers only.
+ *   Samples:  for entry e of a submit's table (tfrec_amd_run: stream s, submit-relative start a, n = n_samples, flags), z[k] = (I, Q) is
+ *             the decimated pair at submit-relative index a + k, 0 <= k < n -- exactly the values tfrec_amd_read_decimated returns.
+ *             z[-1] is the pair at a - 1; for a == 0 the stream's last pair of the submit before.
+ *   Products: over k = k0 .. n-1, k0 = 0 if flags & TFREC_AMD_RUN_CONTINUES, else 1: the product of a trigger's first sample with the
+ *             noise sample ahead of it is left out, and the product across a submit boundary is counted once, in the CONTINUES piece.
+ *             dot = I[k] I[k-1] + Q[k] Q[k-1],  crs = Q[k] I[k-1] - I[k] Q[k-1]  in int64 (|dot|, |crs| <= 2^31): fm_dev's cr and cj
+ *             (dsp_stuff.cpp:284-289).  A tone above the receive frequency gives crs > 0.
+ *   Bin:      a product with dot == 0 && crs == 0 is skipped.  Otherwise, with C[k] = round(32767 cos(2 pi k / 4096)), S[k] = C[(k - 1024)
+ *             mod 4096] (tfrec_amd_tune_streams' table, no other), its bin is the j in 0..63 that maximises dot C[64 j] + crs S[64 j]
+ *             (int64, < 2^47), the lowest j on a tie.  Bin j is the direction 2 pi j / 64: 6000 b Hz at 384 kS/s, b = j for j < 32,
+ *             else j - 64.  Any evaluation that provably returns the same j is allowed.
+ *   Record:   the fields below; pwr_max and energy run over all n samples, n_products, sum_dot, sum_crs and hist over the counted
+ *             products.  The record repeats the table entry's fields, so a caller needs neither the table nor the pool.
+ *   Cutting:  a burst is a chain of pieces: piece i + 1 has CONTINUES, piece i OPEN, on the same stream.  Merging a chain adds
+ *             n_samples, n_products, the sums, energy and hist and takes the largest pwr_max; the result does not depend on how
+ *             the stream was cut into submits.  A restart drops the chain, as it drops the carried trigger.
+ *   Summary (what a caller makes of a record; normative for tfrec_gpu -M and burst.py):  P = n_products, thr = (P + 15) / 16; bin j is
+ *             occupied iff P > 0 and hist[j] >= thr.  None occupied: no carrier (noise spreads over the bins).  Otherwise lo, hi = the
+ *             smallest and largest signed index b of an occupied bin, centre_hz = 3000 (lo + hi), deviation_hz = 3000 (hi - lo).
+ *             Signals near +-192 kHz wrap around; they lie far outside the channel filter.  The factor 16 was chosen on the
+ *             synthetic golden scenes; neither it nor the usefulness of centre and deviation has been measured on real recordings.
+ *   Sign:     the reference's TFA_2 line prints "Offset" = -1536.0 * offset / 131072 kHz (tfa2.cpp:169) with offset the decoder's mean
+ *             of fm_dev: it is positive for a carrier BELOW the receive frequency, so it has the opposite sign of centre_hz.  Golden
+ *             TFA_2 scene, first telegram: received 20 kHz higher (tfrec_amd_tune_streams +20000, the carrier 20 kHz below) the
+ *             reference prints Offset +26.2 kHz and centre_hz is -21000; received 20 kHz lower, -13.7 kHz and +21000; untuned, +6.2
+ *             kHz and +3000. */
+typedef struct {            /* 320 bytes */
+	uint32_t stream;        /* these five: copied from the table entry */
+	uint32_t flags;
+	int64_t  start_sample;
+	uint32_t n_samples;
+	int32_t  thresh;
+	int32_t  pwr_max;       /* max over all n samples of |I| + |Q| */
+	uint32_t n_products;    /* products counted = the sum of hist */
+	int64_t  sum_dot;       /* over the counted products; |sum| <= 2^56 */
+	int64_t  sum_crs;
+	uint64_t energy;        /* sum over all n samples of I*I + Q*Q */
+	uint32_t hist[64];      /* the bin counts */
+	uint32_t reserved[2];   /* 0 */
+} tfrec_amd_burst;
+/* Turn the meter on: after tfrec_amd_enable_capture, before the first submit.  max_runs * 320 bytes of device memory per FIFO set,
+ * counted in tfrec_amd_get_memory.  Errors: no recorder or a second call: TFREC_AMD_E_INVAL; after the first submit or a poisoned
+ * context: TFREC_AMD_E_STATE; TFREC_AMD_E_NOMEM as elsewhere; a call that fails leaves the context exactly as it was.  A context on
+ * which it was never called holds and launches what it did.  Valid on every kind of context and in every mode, as the recorder is; on
+ * a tfrec_amd_submit_runs submit the samples between the runs are (0, 0), and their products fall to the zero rule.  Its two kernels
+ * run on the recorder's low-priority stream behind its own. */
+int tfrec_amd_enable_burst_meter(tfrec_amd_ctx *ctx);
+/* out[i] = the record of entry i of the table tfrec_amd_read_captures returns for the same submit.  Conventions of
+ * tfrec_amd_read_capture_pre: the OLDEST undrained submit, read BEFORE the drain that pops it; reading pops nothing; cap_runs is the
+ * room in records; *n_runs the submit's true run count; out may be NULL with cap_runs 0 to fetch the count alone.  The meter reads the
+ * decimated samples, not the pool: records are delivered for every entry below min(n_runs, max_runs), whatever max_samples is (a
+ * recorder with a pool of one pair runs the meter alone).  n_runs > max_runs: TFREC_AMD_E_OVERFLOW with that prefix delivered.
+ * Errors: not enabled, NULL ctx / n_runs / out (with cap_runs > 0), room too small (nothing written, *n_runs set): TFREC_AMD_E_INVAL;
+ * nothing undrained or poisoned: TFREC_AMD_E_STATE. */
+int tfrec_amd_read_bursts(tfrec_amd_ctx *ctx, tfrec_amd_burst *out, size_t cap_runs, uint32_t *n_runs);
+
 /* Power spectrum of the input rows (tfrec_amd_enable_spectrum): where in a recording there is energy, and where the
  * short bursts are that an average hides -- before a receiver is placed.  It belongs to an input ROW of a submit, not to a stream: it
  * is taken on x, the int16 value every format maps a stored component to (tfrec_amd_create_format; -8192 <= x <= 8191), at the

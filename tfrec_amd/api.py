@@ -13,6 +13,7 @@ from fractions import Fraction
 import numpy as np
 
 from . import _build
+from .burst import BURST_DTYPE  # tfrec_amd_burst
 from .capture import RUN_DTYPE  # tfrec_amd_run
 from .levels import LEVEL_DTYPE  # tfrec_amd_level
 from .occupancy import OCC_DTYPE  # tfrec_amd_occupancy
@@ -109,6 +110,7 @@ EXPORTS = (
     "tfrec_amd_read_spectrum", "tfrec_amd_enable_occupancy", "tfrec_amd_read_occupancy", "tfrec_amd_create_dc", "tfrec_amd_get_dc",
     "tfrec_amd_read_dc", "tfrec_amd_reset_dc_rows", "tfrec_amd_create_iq", "tfrec_amd_get_iq", "tfrec_amd_read_iq", "tfrec_amd_reset_iq_rows", "tfrec_amd_create_decimated", "tfrec_amd_enable_capture_pre",
     "tfrec_amd_read_capture_pre", "tfrec_amd_enable_runs_input", "tfrec_amd_submit_runs", "tfrec_amd_read_biquad_row",
+    "tfrec_amd_enable_burst_meter", "tfrec_amd_read_bursts",
 )
 
 _libs = {}
@@ -206,6 +208,8 @@ def load_library(build: bool = True, experiments: bool = False, short_segments: 
     L.tfrec_amd_read_capture_pre.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
     L.tfrec_amd_enable_runs_input.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
     L.tfrec_amd_submit_runs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
+    L.tfrec_amd_enable_burst_meter.argtypes = [C.c_void_p]
+    L.tfrec_amd_read_bursts.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
     L.tfrec_amd_fifo_depth.restype = C.c_int
     if L.tfrec_amd_fifo_depth() != FIFO_DEPTH:
         raise RuntimeError("libtfrec_amd.so was built with FIFO depth %d, this binding expects %d" % (
@@ -249,7 +253,7 @@ class Receiver:
                  device: int = 0, max_blocks: int = 48, max_events: int | None = None, all_flushes: bool = False,
                  timing: bool = False, serial_chains: bool = False, input_10x: bool = False, bits: bool = False,
                  experiments: bool = False, input_rate=None, input_format=None, levels: bool = False, dc_windows=None,
-                 dc_rows=None, decimated: bool = False, short_segments: bool = False, iq_windows=None):
+                 dc_rows=None, decimated: bool = False, short_segments: bool = False, iq_windows=None, burst_meter: bool = False):
         # experiments=True: the build that reads the TFREC_AMD_* knobs / test hooks from the environment (csrc/knobs.h);
         # the default is the product library, which has none.  short_segments=True: the experiments build with biquad
         # segments of _build.SEG_SLOTS slots (libtfrec_amd_seg.so)
@@ -321,6 +325,11 @@ class Receiver:
         self.max_events = max_events
         self._keep = ()
         self._rows = None  # map_streams: every stream's input row (None: the identity)
+        # burst_meter=True: the burst meter alone (burst.py) -- the recorder with room for every run a submit can hold and a pool of
+        # one pair, and the meter on it.  A receiver that sizes its recorder itself calls enable_capture, then enable_burst_meter.
+        if burst_meter:
+            self.enable_capture(n_streams * (max_blocks * BLOCK_DEC // 356 + 3), 1)
+            self.enable_burst_meter()
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -572,6 +581,27 @@ class Receiver:
         if rc == E_OVERFLOW:  # the delivered prefix is the table's
             pre = pre[:len(self.read_captures(allow_overflow=True)[0])]
         return pre
+
+    def enable_burst_meter(self):
+        """Turn the burst meter on (tfrec_amd_enable_burst_meter; after enable_capture, before the first submit).  read_bursts
+        returns its records."""
+        _check(self.L, self.L.tfrec_amd_enable_burst_meter(self.h))
+
+    def read_bursts(self, allow_overflow: bool = False) -> np.ndarray:
+        """The burst records of the OLDEST undrained submit (tfrec_amd_read_bursts; call it before the drain that pops that
+        submit) -> a BURST_DTYPE array, one record per entry of that submit's run table (burst.py).  They do not depend on the pool:
+        a table with more than max_runs entries (E_OVERFLOW) raises unless allow_overflow, then its first max_runs records are
+        returned; burst_total holds the submit's true run count."""
+        ok = (E_OK, E_OVERFLOW) if allow_overflow else (E_OK,)
+        nr = C.c_uint32(0)
+        rc = self.L.tfrec_amd_read_bursts(self.h, None, 0, C.byref(nr))  # the count (no room: E_INVAL)
+        self.burst_total = int(nr.value)
+        if rc != E_INVAL or nr.value == 0:
+            _check(self.L, rc, ok=ok)
+            return np.zeros(0, dtype=BURST_DTYPE)
+        out = np.zeros(min(nr.value, getattr(self, "_capture", (0, 0))[0]), dtype=BURST_DTYPE)
+        _check(self.L, self.L.tfrec_amd_read_bursts(self.h, out.ctypes.data, len(out), C.byref(nr)), ok=ok)
+        return out
 
     def enable_runs_input(self, max_runs: int, max_samples: int):
         """Turn sparse submits on (tfrec_amd_enable_runs_input; decimated receivers, before the first submit): a submit_runs may

@@ -25,6 +25,7 @@ using namespace tfrec;
 #include "capi_correct.h"  // the DC blocker's and the IQ balancer's constructors, getters, reads and resets
 #include "capi_streams.h"  // reset, configure, the three tunes, map, and their getters
 #include "capi_decin.h"    // the channel-rate constructor, the recorder's pre samples, sparse submits
+#include "capi_burst.h"    // the burst meter's enable and read
 
 extern "C" {
 

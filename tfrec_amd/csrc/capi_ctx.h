@@ -88,6 +88,11 @@ struct CapturePre {
 	bool on = false;
 	uint32_t *d_pre[kSets] = {};
 };
+// tfrec_amd_enable_burst_meter: per set the record of every run of the set's table
+struct BurstMeter {
+	bool on = false;
+	tfrec_amd_burst *d_recs[kSets] = {};
+};
 // tfrec_amd_create_decimated (PreStage::kChannel): the carried last pair of every stream
 struct DecIn {
 	uint32_t *d_last = nullptr;
@@ -280,6 +285,7 @@ struct tfrec_amd_ctx {
 	LevelsOut lev;  // ---- side outputs
 	CaptureOut cap;
 	CapturePre cap_pre;
+	BurstMeter burst;
 	DecIn decin;
 	RunsIn runs_in;
 	SpectrumOut spec;

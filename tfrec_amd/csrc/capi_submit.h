@@ -377,6 +377,8 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		HIPCHK(launch_capture(c->cap.lane.st, out, c->sample_base, b, c->settings.d_scfg));
 		if (c->cap_pre.on)  // the pair ahead of every run: behind the copy kernel, which wrote the table
 			HIPCHK(launch_capture_pre(c->cap.lane.st, out, c->sample_base, b, c->cap_pre.d_pre[set]));
+		if (c->burst.on)  // the burst meter: behind the copy kernel too, on the table and the recorder's working set
+			HIPCHK(launch_burst_meter(c->cap.lane.st, out, b, c->burst.d_recs[set]));
 		HIPCHK(lane_written(c->cap.lane, set));
 	}
 	if (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) {

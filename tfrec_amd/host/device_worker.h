@@ -50,6 +50,7 @@ private:
 	int submit_runs(size_t k);
 	int collect(size_t k, batch_result &b);
 	int read_captures(size_t k, batch_result &b);
+	int read_bursts(size_t k, batch_result &b);
 	typedef int (*estimate_reader)(tfrec_amd_ctx *, int32_t, int16_t *, size_t, int *);
 	int read_last_estimate(size_t k, estimate_reader reader, std::vector<int> &files, std::vector<int16_t> &last);
 	int read_dc(size_t k, batch_result &b) { return read_last_estimate(k, tfrec_amd_read_dc, b.dc_file, b.dc_last); }  // -z -D
@@ -235,14 +236,18 @@ inline int device_worker::open_context()
 		call = "tfrec_amd_map_streams";
 		r = tfrec_amd_map_streams(ctx, all.data(), in_row.data(), (int)n);
 	}
-	if (!r && job.capture) {  // -S, sized so that no submit overflows: every sample, and a stream's runs are >= 356 samples long but two
-		call = "tfrec_amd_enable_capture";
+	if (!r && job.recorder()) {  // -S, sized so that no submit overflows: every sample, and a stream's runs are >= 356 samples long but two
+		call = "tfrec_amd_enable_capture";  // (-M without -S: the table alone, a pool of one pair)
 		r = tfrec_amd_enable_capture(ctx, (uint32_t)(n * ((size_t)bps * TFREC_AMD_BLOCK_DEC / 356 + 3)),
-					     (uint64_t)n * (uint64_t)bps * TFREC_AMD_BLOCK_DEC);
+					     job.capture ? (uint64_t)n * (uint64_t)bps * TFREC_AMD_BLOCK_DEC : 1);
 	}
 	if (!r && job.capture) {  // ... and the pair ahead of every run
 		call = "tfrec_amd_enable_capture_pre";
 		r = tfrec_amd_enable_capture_pre(ctx);
+	}
+	if (!r && job.metering()) {  // -M: the meter on the recorder's table
+		call = "tfrec_amd_enable_burst_meter";
+		r = tfrec_amd_enable_burst_meter(ctx);
 	}
 	if (!r && job.replay) {  // -R, sized so that every submit fits: its files' runs (a cut adds one per stream), every sample at most
 		uint64_t runs = 0, pairs = 0;
@@ -429,6 +434,40 @@ inline int device_worker::read_captures(size_t k, batch_result &b)
 	return 0;
 }
 
+// -M: the batch's burst records.  stream -> file, as for the events; a record that begins behind its file's end is dropped, one that
+// reaches over it has its n_samples cut there (its sums are the device's: the padding is silence)
+inline int device_worker::read_bursts(size_t k, batch_result &b)
+{
+	uint32_t nr = 0;
+	int r = tfrec_amd_read_bursts(ctx, NULL, 0, &nr);  // (the count: E_INVAL for want of room)
+	if (r == TFREC_AMD_E_INVAL && nr) {
+		b.bursts.resize(nr);
+		r = tfrec_amd_read_bursts(ctx, b.bursts.data(), b.bursts.size(), &nr);
+	}
+	if (r == TFREC_AMD_E_OVERFLOW) {  // (cannot happen: the table is sized for the worst case)
+		fprintf(stderr, "tfrec_amd: device %d batch %zu: more runs than the table holds, %zu of %u burst records kept\n", device, k,
+			b.bursts.size(), (unsigned)nr);
+		r = 0;
+	}
+	if (r)
+		return r;
+	const std::vector<int> &file = plan[k].file;
+	size_t kept = 0;
+	for (size_t q = 0; q < b.bursts.size(); q++) {
+		tfrec_amd_burst x = b.bursts[q];
+		if (x.stream >= file.size() || file[x.stream] < 0)
+			continue;
+		const long long end = (long long)file_blocks[file[x.stream]] * TFREC_AMD_BLOCK_DEC;
+		if (x.start_sample >= end)
+			continue;
+		x.n_samples = (uint32_t)std::min<long long>(x.n_samples, end - x.start_sample);
+		x.stream = (uint32_t)file[x.stream];
+		b.bursts[kept++] = x;
+	}
+	b.bursts.resize(kept);
+	return 0;
+}
+
 // -z -D, -Z -D: the last estimate of every file's row -- d, or (t, g) -- by the stage's reader
 inline int device_worker::read_last_estimate(size_t k, estimate_reader reader, std::vector<int> &files, std::vector<int16_t> &last)
 {
@@ -457,6 +496,8 @@ inline int device_worker::read_last_estimate(size_t k, estimate_reader reader, s
 inline int device_worker::collect(size_t k, batch_result &b)
 {
 	int r = job.capture ? read_captures(k, b) : 0;
+	if (!r && job.metering())
+		r = read_bursts(k, b);
 	if (!r && job.occupancy()) {  // -A: the detector's records in place of the spectrum's, 16 + N / 8 bytes each
 		int nr = 0;
 		r = tfrec_amd_read_occupancy(ctx, 0, NULL, NULL, 0, &nr);  // (the count: E_INVAL for want of room)

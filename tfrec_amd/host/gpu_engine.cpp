@@ -266,9 +266,14 @@ void scan_table::finish() const
 		const channel_sum &c = chan[s];
 		for (const tfrec_amd_level &r : c.rec)  // fm_demod.cpp:61, per channel
 			printf("%ld Trigger ratio %d/%d, avg %d\n", job->scan_khz[s], (int)r.triggered, TFREC_AMD_BLOCK_DEC, (int)r.triggered_avg);
-		printf("scan %ld blocks=%llu mean_pwr=%llu peak=%d over=%llu triggered=%llu thresh=%d telegrams=%llu\n", job->scan_khz[s], c.blocks,
+		printf("scan %ld blocks=%llu mean_pwr=%llu peak=%d over=%llu triggered=%llu thresh=%d telegrams=%llu", job->scan_khz[s], c.blocks,
 		       c.blocks ? c.pwr_sum / ((unsigned long long)TFREC_AMD_BLOCK_DEC * c.blocks) : 0ull, c.peak, c.over, c.triggered,
 		       c.blocks ? c.thresh : ((*settings)[s].thresh ? (*settings)[s].thresh : 500), c.telegrams);
+		if (job->metering() && c.burst_carrier)  // -M: where the channel's strongest burst sits relative to the channel, in Hz
+			printf(" burst_centre=%ld", c.burst_centre);
+		else if (job->metering())
+			printf(" burst_centre=-");
+		printf("\n");
 	}
 }
 
@@ -329,6 +334,9 @@ int gpu_engine::run()
 	spectrum_table spec;
 	occupancy_list occ;
 	scan_table scan;
+	burst_merger bursts;
+	std::vector<tfrec_amd_burst> ended;
+	bursts.begin(n);
 	if (job.spectrum)
 		spec.begin(job);
 	if (job.occupancy())
@@ -363,6 +371,16 @@ int gpu_engine::run()
 			if ((rc = cap.take(b)))
 				break;
 			dc.take(b, files);
+			if (job.metering()) {  // -M: the bursts that ended with this batch -- into the scan table, or a line each
+				ended.clear();
+				bursts.take(b, workers[d].plan[k], file_blocks, ended);
+				for (const tfrec_amd_burst &x : ended) {
+					if (job.scan)
+						scan.chan[x.stream].note(x);
+					else
+						printf("%s\n", burst_line(files[x.stream], x).c_str());
+				}
+			}
 			if (job.occupancy()) {  // no replay: the channel list is the product
 				const unsigned long long first = occ.records;
 				const size_t count = occ.take(b, workers[d].plan[k].nb, file_blocks[0]);

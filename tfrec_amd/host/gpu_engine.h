@@ -189,6 +189,14 @@ public:
 	// (tfrec_amd_create_decimated) and is fed sparse submits (tfrec_amd_submit_runs) cut by the batch plan, so -b, -n and -d work as
 	// with dumps.  captures outlives the engine.  Excludes every set_* that concerns the input.
 	void set_replay(const std::vector<replay_file> &captures) { job.replay = &captures; }
+	// -M: the burst meter (tfrec_amd_enable_burst_meter).  Every context enables the recorder -- set_capture's, or with
+	// set_capture's room for runs and a pool of one pair -- and the meter on it; run() merges the records' chains across the batches
+	// of a file (job.h: burst_merger; a chain still open at the file's end is flushed there) and prints, as each burst ends,
+	//   burst <file> <start_sample> <n_samples> <pwr_max> <centre_hz|-> <deviation_hz|->
+	// (job.h: burst_summary; "-": no bin is occupied).  With set_scan the lines are not printed: the table's lines end in
+	// " burst_centre=<Hz|->", the centre of the channel's burst with the largest pwr_max.  Under -A it is the scan's, not pass 1's.
+	// Neither the 1/16 rule behind the summary nor its usefulness has been measured on real recordings.
+	void set_meter() { job.meter = true; }
 	// returns 0 on success, a TFREC_AMD_E_* code otherwise
 	int run();
 	// decoders of stream s in slot order (NULL for slots not registered)

@@ -56,10 +56,13 @@ struct job_settings {
 	long occ_join = 0;
 	int dc_windows = 0;            // set_dc (0: none)
 	int iq_windows = 0;            // set_iq (0: none)
+	bool meter = false;            // set_meter
 	const std::vector<replay_file> *replay = NULL;  // set_replay (NULL: the files are dumps)
 
 	bool resampled() const { return rate_p != 1 || rate_q != 1; }
 	bool occupancy() const { return spectrum && occ_ratio; }  // -A, pass 1
+	bool recorder() const { return capture || metering(); }  // the contexts enable the recorder: for -S, or as the meter's table
+	bool metering() const { return meter && !occupancy(); }  // -M (under -A: in the scan, not in pass 1)
 	bool share() const { return slots <= 0; }  // one stream per file for the whole job: a path given several times is read once
 	// -r: the blocks a piece of a file holds, q / gcd(q, 64) -- the odd part of a q <= 64, 6 at 625/384; 1 without -r: every
 	// batch carries a multiple of it (tfrec_amd_create_rate: Submits)
@@ -295,7 +298,9 @@ inline std::vector<occ_channel> occupancy_channels(const std::vector<unsigned lo
 // -P: the spectrum records of input row 0, [record][bin], and their frame counts
 // -A: the detector's records of row 0 and their bitmap words, [record][N / 32]
 // -z with -D: per file of the batch its index in the job and the last window's {d_I, d_Q} of its row
+// -M: the burst records that belong to a file (stream = its index in the job), n_samples cut at the file's end
 struct batch_result {
+	std::vector<tfrec_amd_burst> bursts;
 	std::vector<tfrec_amd_event> ev;
 	std::vector<tfrec_amd_level> lv;
 	std::vector<tfrec_amd_run> runs;
@@ -373,13 +378,116 @@ struct occupancy_list {
 	int finish();
 };
 
+// ---- -M: the burst meter's records (include/tfrec_amd.h: tfrec_amd_burst, whose text is normative; tfrec_amd/burst.py restates
+// merge, summary and the line)
+
+// piece p, which CONTINUES the chain c, added to it
+inline void burst_add(tfrec_amd_burst &c, const tfrec_amd_burst &p)
+{
+	c.n_samples += p.n_samples;
+	c.n_products += p.n_products;
+	c.sum_dot += p.sum_dot;
+	c.sum_crs += p.sum_crs;
+	c.energy += p.energy;
+	for (int j = 0; j < 64; j++)
+		c.hist[j] += p.hist[j];
+	c.pwr_max = std::max(c.pwr_max, p.pwr_max);
+	c.flags = (c.flags & TFREC_AMD_RUN_CONTINUES) | (p.flags & TFREC_AMD_RUN_OPEN);
+}
+
+// -> whether a bin is occupied (hist[j] >= (P + 15) / 16, P = n_products > 0); then centre and deviation in Hz from the smallest
+// and the largest signed index of an occupied bin
+inline bool burst_summary(const tfrec_amd_burst &r, long &centre_hz, long &deviation_hz)
+{
+	const unsigned long long thr = ((unsigned long long)r.n_products + 15) / 16;
+	int lo = 64, hi = -64;
+	for (int j = 0; j < 64 && r.n_products; j++)
+		if (r.hist[j] >= thr) {
+			const int b = j < 32 ? j : j - 64;
+			lo = std::min(lo, b);
+			hi = std::max(hi, b);
+		}
+	if (hi < lo)
+		return false;
+	centre_hz = 3000L * (lo + hi);
+	deviation_hz = 3000L * (hi - lo);
+	return true;
+}
+
+// burst <file> <start_sample> <n_samples> <pwr_max> <centre_hz|-> <deviation_hz|->
+inline std::string burst_line(const std::string &file, const tfrec_amd_burst &r)
+{
+	long c = 0, d = 0;
+	std::string s = "burst " + file + " " + std::to_string((long long)r.start_sample) + " " + std::to_string(r.n_samples) + " " +
+			std::to_string(r.pwr_max);
+	if (burst_summary(r, c, d))
+		return s + " " + std::to_string(c) + " " + std::to_string(d);
+	return s + " - -";
+}
+
+// The chains of pieces across a job's batches, per file (a record's stream is its file's index in the job).  A chain ends with a
+// piece that is not OPEN, with a batch that does not continue it, and with its file: a chain still open at a file's end is flushed
+// there.  take() appends the bursts that ended with the batch, in the order in which they ended.
+struct burst_merger {
+	std::vector<tfrec_amd_burst> chain;
+	std::vector<char> open, seen;
+	std::vector<unsigned long long> blocks;  // of every file, in the batches so far
+	void begin(size_t n_files)
+	{
+		chain.resize(n_files);
+		open.assign(n_files, 0);
+		seen.assign(n_files, 0);
+		blocks.assign(n_files, 0);
+	}
+	void take(const batch_result &b, const batch_plan &p, const std::vector<size_t> &file_blocks, std::vector<tfrec_amd_burst> &out)
+	{
+		for (const tfrec_amd_burst &r : b.bursts) {
+			const size_t f = r.stream;
+			if ((r.flags & TFREC_AMD_RUN_CONTINUES) && open[f]) {
+				burst_add(chain[f], r);
+			} else {
+				if (open[f])
+					out.push_back(chain[f]);
+				chain[f] = r;
+				open[f] = 1;
+			}
+			seen[f] = 1;
+			if (!(r.flags & TFREC_AMD_RUN_OPEN)) {
+				out.push_back(chain[f]);
+				open[f] = 0;
+			}
+		}
+		for (int f : p.file) {
+			if (f < 0)
+				continue;
+			blocks[f] += (unsigned long long)p.nb;
+			if (open[f] && (!seen[f] || blocks[f] >= file_blocks[f])) {
+				out.push_back(chain[f]);
+				open[f] = 0;
+			}
+			seen[f] = 0;
+		}
+	}
+};
+
 // -s: the scan table (gpu_engine.h: set_scan).  Per channel (file) the sums of its level records, its telegrams, and with -D
-// every record.
+// every record; with -M the centre of the channel's burst with the largest pwr_max (the first of them).
 struct scan_table {
 	struct channel_sum {
 		unsigned long long blocks = 0, pwr_sum = 0, over = 0, triggered = 0, telegrams = 0;
 		int peak = 0, thresh = 0;
 		std::vector<tfrec_amd_level> rec;
+		int burst_peak = -1;  // -M: no burst so far
+		bool burst_carrier = false;
+		long burst_centre = 0;
+		void note(const tfrec_amd_burst &r)
+		{
+			long dev = 0;
+			if (r.pwr_max > burst_peak) {
+				burst_peak = r.pwr_max;
+				burst_carrier = burst_summary(r, burst_centre, dev);
+			}
+		}
 	};
 	const job_settings *job;
 	const std::vector<file_settings> *settings;

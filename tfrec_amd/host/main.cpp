@@ -68,6 +68,16 @@
 // the auto threshold, the recording was auto from the stream's start and complete.  With -L, -x, -r, -F, -f, -c, -s, -A, -P, -z,
 // -S, -p or -X, or when .idx is missing or inconsistent -- a line that does not parse, runs of a file that overlap or are out of
 // order, a .cs16 or .pre shorter than the lines ask for --, it is a usage error: exit 2 before a device is opened.
+// -M (not in the reference): the burst meter (tfrec_amd_enable_burst_meter): for every trigger window of every file,
+// whether or not anything decoded in it, where its carrier sits relative to the receive frequency and how wide its FSK is -- what
+// -f and -W are chosen from.  The contexts enable the recorder (-S's, or the table alone with a pool of one pair) and the meter;
+// the pieces of a window that is cut by a submit boundary are merged, and stdout gets, as each window ends (a window still open at
+// its file's end: there),
+//   burst <file> <start_sample> <n_samples> <pwr_max> <centre_hz|-> <deviation_hz|->
+// centre and deviation in Hz by the header's integer rule (a bin of 6 kHz is occupied when it holds 1/16 of the window's products; "-":
+// none does, no carrier).  With -s or -A the lines are left out and every line of the channel table ends in burst_centre=<Hz|->, the
+// centre of the channel's window with the largest pwr_max.  Works with -R, -S, -n, -d and every input option; not with -X.  The
+// 1/16 rule was chosen on synthetic scenes; it has not been measured on real recordings.
 // -P bins[,frames_per_record] (not in the reference): the power spectrum of ONE recording, beside its decoding: an
 // exact integer DFT of bins = 64, 128, 256, 512 or 1024 bins over the raw input -- at 1.536 MS/s, or given with -x, or with -r / -F --,
 // per record of frames_per_record frames (1 .. 16384; default: the frames one block's input holds, at least 1) the sum and the peak
@@ -238,6 +248,7 @@ struct cli {
 	bool have_scan = false;
 	const char *cap_prefix = NULL;  // -S
 	const char *replay_prefix = NULL;  // -R
+	bool meter = false;  // -M
 	bool have_center = false, have_format = false;  // -c, -F given (-R refuses them)
 	std::vector<replay_file> captures;  // -R: one per file index of <prefix>.idx
 	int spec_bins = 0, spec_g = 0;  // -P (spec_g 0: the default)
@@ -270,7 +281,7 @@ struct cli {
 
 static void usage()
 {
-	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
+	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
 			"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
 			"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
 			"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
@@ -279,6 +290,9 @@ static void usage()
 			"  -S prefix   record the IQ of every trigger window: <prefix>.idx (a line per run) and <prefix>.<file>.cs16 (384 kS/s int16 I, Q)\n"
 			"  -R prefix   replay a capture made by -S (<prefix>.idx, .cs16, .pre): decode its trigger windows again, with -T, -t, -d, -n, -b,\n"
 			"              -D, -q, -e / -E; not with -L or anything that describes a dump\n"
+			"  -M          measure every burst's carrier offset and FSK deviation on the GPU, decoded or not: a line 'burst <file>\n"
+			"              <start_sample> <n_samples> <pwr_max> <centre_hz|-> <deviation_hz|->' per trigger window (-: no carrier); with -s or\n"
+			"              -A a column burst_centre= of the channel's strongest burst instead; also with -R; not with -X\n"
 			"  -f kHz      receive frequency (default: the dumps' own, -c)\n"
 			"  -c kHz      frequency the dumps were recorded at (default 868250); -f within 767 kHz of it\n"
 			"  -x          the dumps are 15.36 MS/s u8 dumps (10x the rate); -f within 7679 kHz of -c, shifted ahead of the 10:1 stage\n"
@@ -352,8 +366,9 @@ bool cli::parse_format(const char *arg)
 int cli::parse(int argc, char **argv)
 {
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::Mh")) != -1) {
 		switch (c) {
+		case 'M': meter = true; break;
 		case 'z': {
 			const char *a = optional_arg(argc, argv);
 			dc_windows = 2048;
@@ -491,6 +506,10 @@ int cli::check() const
 	}
 	if (iq_windows && (wide || hexfile)) {
 		fprintf(stderr, "tfrec_gpu: -Z removes the IQ imbalance of -L files at 1.536 MS/s or the rate of -r: not with -x or -X\n");
+		return 1;
+	}
+	if (meter && hexfile) {
+		fprintf(stderr, "tfrec_gpu: -M measures the bursts of -L files or of a capture (-R): not with -X\n");
 		return 1;
 	}
 	if (cap_prefix && hexfile) {
@@ -724,6 +743,8 @@ int cli::run()
 		e.set_scan(scan_khz);
 	if (cap_prefix)
 		e.set_capture(cap_prefix);
+	if (meter)
+		e.set_meter();
 	if (have_spec_p)  // the default record: the frames one block's input holds
 		e.set_spectrum(spec_bins, spec_g ? spec_g : (int)std::max(1L, (long)in.input_samples(1) / spec_bins), center);
 	int rc = e.run();
