@@ -472,6 +472,74 @@ int tfrec_amd_read_iq(tfrec_amd_ctx *ctx, int32_t row, int16_t *tg, size_t cap_w
  * TFREC_AMD_E_STATE. */
 int tfrec_amd_reset_iq_rows(tfrec_amd_ctx *ctx, const int32_t *rows, int n);
 
+/* Save and restore a stream's receiver state: everything one submit leaves for the next -- what
+ * tfrec_amd_reset_streams restores, copied instead of filled -- as one self-describing blob per stream, so that a stream can
+ * leave the context that holds it: into a recreated context after a poisoned one (from its last snapshot), into a context of
+ * another n_streams, max_blocks or device, or into a later run.  A stream loaded into stream j of a context B continues there
+ * exactly as it would have in its source: its events in B, behind those it produced before the save, are those of the
+ * uninterrupted receiver in every field (seq, end_sample, the recorder's start_sample and the tunes' phases included).
+ *
+ * A blob is this 128-byte header (little endian, packed as declared) followed by an opaque payload of payload_bytes bytes;
+ * tfrec_amd_stream_state_bytes is the whole blob's size in THIS context, a multiple of 16, the same for every stream.  The
+ * header names nothing of the source context: no stream index, no device, no n_streams. */
+#define TFREC_AMD_STATE_MAGIC 0x54534654u /* "TFST" */
+#define TFREC_AMD_STATE_FORMAT 1u
+typedef struct {            /* 128 bytes */
+	uint32_t magic;             /*   0  TFREC_AMD_STATE_MAGIC */
+	uint32_t format;            /*   4  TFREC_AMD_STATE_FORMAT */
+	uint64_t version_hash;      /*   8  FNV-1a (64 bit) of the bytes of tfrec_amd_version(): a blob of another build is refused */
+	/* the signature: what must be equal in the source and the target context */
+	int32_t input_kind;         /*  16  0 u8 at 1.536 MS/s, 1 TFREC_AMD_F_INPUT_10X, 2 a resampling stage, 3 a format at 1/1, 4 decimated */
+	int32_t format_in;          /*  20  TFREC_AMD_FMT_* of the input rows */
+	int32_t format_pre;         /*  24  ... and of what the pre-stage reads (S16 behind an input correction) */
+	int32_t rate_p, rate_q;     /*  28  the input rate 1536000 P / Q */
+	int32_t tail_bytes;         /*  36  the front end's FIR history per stream */
+	int32_t pre_bytes;          /*  40  the pre-stage's history per stream */
+	uint32_t types_mask;        /*  44  the context's registered demodulators */
+	uint32_t flags;             /*  48  the context's TFREC_AMD_F_SERIAL_CHAINS and TFREC_AMD_F_LEVELS, nothing else */
+	uint32_t recorder;          /*  52  1: tfrec_amd_enable_capture was called */
+	int32_t dc_windows;         /*  56  the DC blocker's K, 0 without one */
+	int32_t iq_windows;         /*  60  the IQ balancer's K, 0 without one */
+	uint32_t chain_state_bytes; /*  64  the size of one demodulator's carried record in this build */
+	uint32_t payload_bytes;     /*  68  bytes behind the header */
+	int64_t samples_since_restart;    /*  72  decimated samples the stream has run since its start or last restart */
+	tfrec_amd_stream_config config;   /*  80  the stream's settings */
+	int32_t tune_hz;            /*  96  tfrec_amd_tune_streams */
+	int32_t tune_wide_hz;       /* 100  tfrec_amd_tune_streams_wide (0 in a context without the 10:1 stage) */
+	int32_t tune_input_hz;      /* 104  tfrec_amd_tune_streams_input (0 in a context without an input-rate mixer) */
+	uint8_t reserved[20];       /* 108  zero */
+} tfrec_amd_state_header;
+/* n_streams, max_blocks, max_events, the device, the pipeline layout and every flag but the two named are deliberately no part of
+ * the signature: they may differ between the source and the target. */
+int tfrec_amd_stream_state_bytes(tfrec_amd_ctx *ctx, size_t *bytes);
+/* Save streams[0..n) (distinct) into blobs[i * bytes .. (i + 1) * bytes), bytes = tfrec_amd_stream_state_bytes.
+ *   - Waits for everything queued, as tfrec_amd_sync does: the state saved is the state behind the LAST submit made.  That wait
+ *     is the call's price; a context that never calls it runs exactly as before.
+ *   - Drains nothing: undrained submits stay in the FIFO and drain unchanged, and the context continues as if it had not saved.
+ *   - One kernel gathers the listed streams into a device staging buffer (made at the first save or load, n_streams blobs,
+ *     counted by tfrec_amd_get_memory from then on), one copy brings it out.  Two saves without a submit between them give the
+ *     same bytes.
+ * Errors: a poisoned context, or a stream with a reset, configure, tune or map (or its row with a tfrec_amd_reset_dc_rows /
+ * _iq_rows) pending since the last submit -- its state is about to be replaced: TFREC_AMD_E_STATE.  An index out of range or
+ * listed twice, n < 0, a NULL pointer with n > 0, cap_bytes < n * bytes, a stream that reads another row than its own or whose row
+ * another stream reads (tfrec_amd_map_streams; shared rows are not saved): TFREC_AMD_E_INVAL.  Nothing is written then. */
+int tfrec_amd_save_streams(tfrec_amd_ctx *ctx, const int32_t *streams, int n, void *blobs, size_t cap_bytes);
+/* Load blobs[i] (n blobs of tfrec_amd_stream_state_bytes each, bytes >= n * that) into streams[i] (distinct) of this context.
+ *   - Every blob is validated before anything is touched: magic, format, version hash, the signature against this context's,
+ *     payload_bytes, samples_since_restart >= 0, the settings and the tunes under the checks of tfrec_amd_configure_streams and
+ *     the tune calls.  Any refusal leaves the context exactly as it was.
+ *   - Then it waits as a save does and scatters the payloads with the kernel of the save (one table of the inventory serves both
+ *     directions).  The settings and tunes are applied as tfrec_amd_configure_streams and the tune calls would apply them, but
+ *     without their restart; the stream's sample origin becomes (samples submitted so far) - samples_since_restart, so that
+ *     end_sample, seq, the recorder's start_sample and the phase of every mixer continue.  Submits still in the FIFO drain with
+ *     the origins they ran with.
+ *   - Not carried: context-wide counters (tfrec_amd_get_stats, _get_fm_stats, timings) and side-output records of submits
+ *     already made.
+ * Errors: a poisoned context, or a listed stream with a restart pending (it would replace what was loaded): TFREC_AMD_E_STATE;
+ * an index out of range or listed twice, a mapped stream as for a save, n < 0, a NULL pointer with n > 0, bytes too small, or a
+ * blob refused by the validation: TFREC_AMD_E_INVAL (tfrec_amd_last_error says which field). */
+int tfrec_amd_load_streams(tfrec_amd_ctx *ctx, const int32_t *streams, int n, const void *blobs, size_t bytes);
+
 /* Wait for submitted work. */
 int tfrec_amd_sync(tfrec_amd_ctx *ctx);
 

@@ -110,7 +110,8 @@ EXPORTS = (
     "tfrec_amd_read_spectrum", "tfrec_amd_enable_occupancy", "tfrec_amd_read_occupancy", "tfrec_amd_create_dc", "tfrec_amd_get_dc",
     "tfrec_amd_read_dc", "tfrec_amd_reset_dc_rows", "tfrec_amd_create_iq", "tfrec_amd_get_iq", "tfrec_amd_read_iq", "tfrec_amd_reset_iq_rows", "tfrec_amd_create_decimated", "tfrec_amd_enable_capture_pre",
     "tfrec_amd_read_capture_pre", "tfrec_amd_enable_runs_input", "tfrec_amd_submit_runs", "tfrec_amd_read_biquad_row",
-    "tfrec_amd_enable_burst_meter", "tfrec_amd_read_bursts",
+    "tfrec_amd_enable_burst_meter", "tfrec_amd_read_bursts", "tfrec_amd_stream_state_bytes", "tfrec_amd_save_streams",
+    "tfrec_amd_load_streams",
 )
 
 _libs = {}
@@ -210,6 +211,9 @@ def load_library(build: bool = True, experiments: bool = False, short_segments: 
     L.tfrec_amd_submit_runs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
     L.tfrec_amd_enable_burst_meter.argtypes = [C.c_void_p]
     L.tfrec_amd_read_bursts.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+    L.tfrec_amd_stream_state_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
+    L.tfrec_amd_save_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+    L.tfrec_amd_load_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
     L.tfrec_amd_fifo_depth.restype = C.c_int
     if L.tfrec_amd_fifo_depth() != FIFO_DEPTH:
         raise RuntimeError("libtfrec_amd.so was built with FIFO depth %d, this binding expects %d" % (
@@ -387,6 +391,38 @@ class Receiver:
             raise TfrecAmdError(E_INVAL, "stream index outside [0, %d)" % self.n_streams)
         a = np.ascontiguousarray(idx, dtype=np.int32)
         _check(self.L, self.L.tfrec_amd_reset_streams(self.h, a.ctypes.data if len(a) else None, len(a)))
+
+    @property
+    def state_bytes(self) -> int:
+        """Bytes of one stream's state blob in this receiver (tfrec_amd_stream_state_bytes; state.py restates its header)."""
+        v = C.c_size_t(0)
+        _check(self.L, self.L.tfrec_amd_stream_state_bytes(self.h, C.byref(v)))
+        return int(v.value)
+
+    def _stream_list(self, streams):
+        idx = [int(s) for s in streams]
+        if any(s < 0 or s >= self.n_streams for s in idx):  # (refused before int32 could wrap an index into range)
+            raise TfrecAmdError(E_INVAL, "stream index outside [0, %d)" % self.n_streams)
+        return np.ascontiguousarray(idx, dtype=np.int32)
+
+    def save_streams(self, streams) -> np.ndarray:
+        """The listed streams' receiver state behind the last submit made (tfrec_amd_save_streams) -> uint8 [n, state_bytes], one
+        blob per stream.  Waits for everything queued and drains nothing.  TfrecAmdError(E_STATE) for a stream with a restart
+        pending, (E_INVAL) for a repeated index or a mapped stream."""
+        a = self._stream_list(streams)
+        out = np.zeros((len(a), self.state_bytes), dtype=np.uint8)
+        _check(self.L, self.L.tfrec_amd_save_streams(self.h, a.ctypes.data if len(a) else None, len(a),
+                                                     out.ctypes.data if len(a) else None, out.nbytes))
+        return out
+
+    def load_streams(self, streams, blobs):
+        """Continue the saved receivers blobs[i] in streams[i] (tfrec_amd_load_streams): their settings, tunes, sample count and all
+        carried state, from the next submit on.  A blob this receiver cannot continue -- another build, input, types mask,
+        levels / recorder / serial-chains setting -- raises TfrecAmdError(E_INVAL) and nothing changes."""
+        a = self._stream_list(streams)
+        b = np.ascontiguousarray(blobs, dtype=np.uint8).reshape(len(a), -1) if len(a) else np.zeros((0, 0), dtype=np.uint8)
+        _check(self.L, self.L.tfrec_amd_load_streams(self.h, a.ctypes.data if len(a) else None, len(a),
+                                                     b.ctypes.data if len(a) else None, b.nbytes))
 
     def configure_streams(self, streams, types_mask=None, thresh=None, filter_type=None):
         """Give the listed streams their own settings (tfrec_amd_configure_streams): each of types_mask, thresh and filter_type

@@ -14,6 +14,7 @@
 #include "knobs.h"
 #include "tfrec_dev.h"
 #include "launch.h"  // every launch_* of frontend.hip, chains.hip and chains2.hip, and the records they take (FrontOut, History, ...)
+#include "state.h"   // stream_state_kernel and its segment table (save / load)
 
 using namespace tfrec;
 
@@ -26,6 +27,7 @@ using namespace tfrec;
 #include "capi_streams.h"  // reset, configure, the three tunes, map, and their getters
 #include "capi_decin.h"    // the channel-rate constructor, the recorder's pre samples, sparse submits
 #include "capi_burst.h"    // the burst meter's enable and read
+#include "capi_state.h"    // a stream's state blob: its header, the inventory table, save and load
 
 extern "C" {
 

@@ -248,6 +248,13 @@ struct Restarts {
 	bool any = false;  // a submit has carried a reset: set_origin is kept from then on
 };
 
+// tfrec_amd_save_streams / tfrec_amd_load_streams: the device staging of n_streams blobs and the list of the
+// streams a call names, both made by the first call (nullptr before it)
+struct StateStage {
+	uint8_t *d_blobs = nullptr;
+	int32_t *d_list = nullptr;
+};
+
 struct tfrec_amd_ctx {
 	tfrec_amd_config cfg;
 	ChainLaunch launch;
@@ -347,6 +354,7 @@ struct tfrec_amd_ctx {
 	// state, the FIFO's bookkeeping), so the context cannot continue exactly.  Every later submit / drain returns
 	// TFREC_AMD_E_STATE; destroy and recreate.
 	bool poisoned = false;
+	StateStage state;  // ---- save / load (capi_state.h)
 	// TFREC_AMD_HOST_PROF=1: host-side time of the submit / drain calls, printed when the context is destroyed
 	double hp_submit = 0, hp_wait = 0, hp_copy = 0, hp_sort = 0, hp_gap = 0, hp_lat = 0, hp_s2s = 0;
 	long hp_n = 0, hp_gap_n = 0;

@@ -89,5 +89,8 @@ hipError_t launch_threshold(hipStream_t st, const FrontOut &o, FskState *fsk, in
 hipError_t launch_pipeline(const PipeCtl &P, const FrontOut &o, long long sample_base, const ChainLaunch &L, const WinTables &T, int16_t *ld16,
 			   int32_t *dev32, tfrec_amd_event *events, EventBuf *eb, uint32_t flags);
 hipError_t whb_chain_lds_optin();
+// ---- capi.hip (state.h): a save's gather of the listed streams' carried state into the staging buffer, or a load's scatter
+struct StateTable;
+hipError_t launch_stream_state(hipStream_t st, bool load, const StateTable &T, const int32_t *list, int n_list, uint8_t *stage);
 
 }  // namespace tfrec

@@ -56,6 +56,8 @@ private:
 	int read_dc(size_t k, batch_result &b) { return read_last_estimate(k, tfrec_amd_read_dc, b.dc_file, b.dc_last); }  // -z -D
 	int read_iq(size_t k, batch_result &b) { return read_last_estimate(k, tfrec_amd_read_iq, b.iq_file, b.iq_last); }  // -Z -D
 	int close_context(int r);
+	int load_kept();
+	int save_ended(size_t k);
 
 	const job_settings &job;
 	const std::vector<std::string> &files;
@@ -107,7 +109,7 @@ inline device_worker::device_worker(const job_settings &job_, const std::vector<
 		dflt.types |= settings[s].types;
 	if (job.slots > 0)
 		n = std::min(n, (size_t)job.slots);
-	plan = plan_batches(file_blocks, settings, dflt, s0, s1, n, bps);
+	plan = plan_batches(file_blocks, settings, dflt, s0, s1, n, bps, job.keeping());
 }
 
 inline void device_worker::push(batch_result &&b)
@@ -174,6 +176,8 @@ inline int device_worker::work()
 		if (!r)
 			push(std::move(b));
 	}
+	if (!r && job.keeping())  // -k: the files that ended with the last batch
+		r = save_ended(plan.size());
 	return close_context(r);
 }
 
@@ -283,6 +287,7 @@ inline void device_worker::read_batches()
 {
 	std::vector<FILE *> fd(s1 - s0, (FILE *)NULL);
 	std::vector<size_t> fleft(file_blocks.begin() + s0, file_blocks.begin() + s1);
+	std::vector<size_t> head_pos(s1 - s0, 0);  // -K: bytes of the file's carried-in rest read so far
 	const size_t piece = job.piece_bytes();
 	for (size_t k = 0; k < plan.size(); k++) {
 		{
@@ -305,7 +310,14 @@ inline void device_worker::read_batches()
 					read_failed = true;
 				}
 				if (fp) {
-					got = fread(dst, 1, want, fp);
+					if (job.cont) {  // -K: the rest of the part before comes ahead of the file's own bytes
+						const std::vector<uint8_t> &head = (*job.cont)[f].rest;
+						size_t &pos = head_pos[f - s0];
+						got = std::min(want, head.size() - pos);
+						memcpy(dst, head.data() + pos, got);
+						pos += got;
+					}
+					got += fread(dst + got, 1, want - got, fp);
 					got -= got % piece;
 					size_t &left = fleft[f - s0];
 					left -= std::min<size_t>(left, (size_t)b.nb);
@@ -337,7 +349,13 @@ inline int device_worker::submit(size_t k)
 		rcv.wait(lk, [&]() { return filled > k; });
 	}
 	const batch_plan &b = plan[k];
-	int r = 0;
+	int r = job.keeping() ? save_ended(k) : 0;
+	if (r)
+		return r;
+	if (job.cont && k == 0) {  // -K: the saved settings, tunes and state instead of the files' own configure and tune
+		r = load_kept();
+		return r ? r : tfrec_amd_submit_host(ctx, host[k % kBufs], row, b.nb);
+	}
 	if ((job.dc_windows || job.iq_windows) && !job.share()) {
 		// -n with -z or -Z: a slot that starts a new file -- by a reset, or by the configure or tune its next file needs -- starts a
 		// new DC and a new IQ estimate too.  A stream's row is its own here (nothing is shared); duplicates are allowed.
@@ -366,6 +384,58 @@ inline int device_worker::submit(size_t k)
 	if (r)
 		return r;
 	return job.replay ? submit_runs(k) : tfrec_amd_submit_host(ctx, host[k % kBufs], row, b.nb);
+}
+
+// -K: every file's saved state into its stream, ahead of the first batch (without -n every file starts there)
+inline int device_worker::load_kept()
+{
+	size_t bytes = 0;
+	int r = tfrec_amd_stream_state_bytes(ctx, &bytes);
+	std::vector<int32_t> streams;
+	std::vector<uint8_t> blobs;
+	for (size_t s = 0; s < n && !r; s++) {
+		const int f = plan[0].file[s];
+		if (f < 0)
+			continue;
+		const std::vector<uint8_t> &st = (*job.cont)[f].state;
+		if (st.size() != bytes) {
+			fprintf(stderr, "%s: %zu bytes, a stream's state in this run takes %zu (other -T, -x, -r, -F, -z or -Z than the run that kept it?)\n",
+				job_settings::kept_path(job.cont_prefix, (size_t)f, ".state").c_str(), st.size(), bytes);
+			return TFREC_AMD_E_INVAL;
+		}
+		streams.push_back((int32_t)s);
+		blobs.insert(blobs.end(), st.begin(), st.end());
+	}
+	return r ? r : tfrec_amd_load_streams(ctx, streams.data(), (int)streams.size(), blobs.data(), blobs.size());
+}
+
+// -k: the streams whose file's last batch was batch k - 1, saved to <prefix>.<file>.state before batch k is submitted (k ==
+// plan.size(): at the end of the job).  The save waits for everything queued and drains nothing.
+inline int device_worker::save_ended(size_t k)
+{
+	if (k == 0)
+		return 0;
+	std::vector<int32_t> streams;
+	for (size_t s = 0; s < n; s++)
+		if (plan[k - 1].file[s] >= 0 && (k == plan.size() || plan[k].file[s] != plan[k - 1].file[s]))
+			streams.push_back((int32_t)s);
+	if (streams.empty())
+		return 0;
+	size_t bytes = 0;
+	int r = tfrec_amd_stream_state_bytes(ctx, &bytes);
+	std::vector<uint8_t> blobs(streams.size() * bytes);
+	if (!r)
+		r = tfrec_amd_save_streams(ctx, streams.data(), (int)streams.size(), blobs.data(), blobs.size());
+	for (size_t i = 0; i < streams.size() && !r; i++) {
+		const std::string path = job_settings::kept_path(job.keep_prefix, (size_t)plan[k - 1].file[streams[i]], ".state");
+		FILE *fp = fopen(path.c_str(), "wb");
+		const bool ok = fp && fwrite(blobs.data() + i * bytes, 1, bytes, fp) == bytes;
+		if ((fp && fclose(fp)) || !ok) {
+			perror(path.c_str());
+			r = TFREC_AMD_E_INVAL;
+		}
+	}
+	return r;
 }
 
 // -R: batch k as a sparse submit -- every stream's part of its file's capture (the tables are ordered by stream)

@@ -299,6 +299,62 @@ static bool replays_before(const tfrec_amd_event &a, const tfrec_amd_event &b)
 	return ab && a.offset < b.offset;
 }
 
+// -K: a whole file into `to` -> whether it could be read (must: a missing file is reported)
+static bool read_whole(const std::string &path, std::vector<uint8_t> &to, bool must)
+{
+	to.clear();
+	FILE *f = fopen(path.c_str(), "rb");
+	if (!f) {
+		if (must)
+			perror(path.c_str());
+		return false;
+	}
+	uint8_t buf[65536];
+	for (size_t got; (got = fread(buf, 1, sizeof(buf), f)) > 0;)
+		to.insert(to.end(), buf, buf + got);
+	const bool ok = !ferror(f);
+	fclose(f);
+	if (!ok)
+		perror(path.c_str());
+	return ok;
+}
+
+// -k: file s's <prefix>.<s>.rest -- the last bytes of (the head carried in, the file) that filled no piece -- and, for a file that
+// ran nothing, the .state it continued from
+static int write_kept_rest(const job_settings &job, size_t s, const std::string &file, const kept_bytes &k)
+{
+	const kept_input *in = job.cont ? &(*job.cont)[s] : NULL;
+	const std::string path = job_settings::kept_path(job.keep_prefix, s, ".rest");
+	std::vector<uint8_t> rest;
+	if (in)
+		rest.assign(in->rest.end() - (long)k.rest_head, in->rest.end());
+	rest.resize(k.rest_head + k.rest_file);
+	FILE *f = fopen(file.c_str(), "rb");
+	bool ok = f && fseek(f, -(long)k.rest_file, SEEK_END) == 0 && fread(rest.data() + k.rest_head, 1, k.rest_file, f) == k.rest_file;
+	if (f)
+		fclose(f);
+	if (!ok) {
+		perror(file.c_str());
+		return TFREC_AMD_E_INVAL;
+	}
+	FILE *o = fopen(path.c_str(), "wb");
+	ok = o && fwrite(rest.data(), 1, rest.size(), o) == rest.size();
+	if (o && fclose(o))
+		ok = false;
+	if (ok && k.blocks == 0 && in) {  // nothing ran: the state goes on unchanged
+		const std::string sp = job_settings::kept_path(job.keep_prefix, s, ".state");
+		FILE *so = fopen(sp.c_str(), "wb");
+		ok = so && fwrite(in->state.data(), 1, in->state.size(), so) == in->state.size();
+		if (so && fclose(so))
+			ok = false;
+	}
+	if (!ok) {
+		perror(path.c_str());
+		return TFREC_AMD_E_INVAL;
+	}
+	return 0;
+}
+
 // One worker (host thread + context + HIP streams) per device entry, streams sharded by index over them; this thread
 // takes the devices' events batch by batch, in device = stream order, and replays them into the decoders: stdout and
 // the handler records come out in the order of a single-device run whatever the number of devices.
@@ -313,6 +369,24 @@ int gpu_engine::run()
 		file_blocks[s] = (*job.replay)[s].blocks();
 		stream_samples[s] = (long long)file_blocks[s] * TFREC_AMD_BLOCK_DEC;
 	}
+	std::vector<kept_input> cont(job.continuing() ? n : 0);  // -K: every file's state and rest, before a device is opened
+	for (size_t s = 0; s < cont.size(); s++) {
+		if (!read_whole(job_settings::kept_path(job.cont_prefix, s, ".state"), cont[s].state, true) ||
+		    cont[s].state.size() < sizeof(tfrec_amd_state_header))
+			return TFREC_AMD_E_INVAL;
+		read_whole(job_settings::kept_path(job.cont_prefix, s, ".rest"), cont[s].rest, false);
+		tfrec_amd_state_header h;  // the saved settings are the stream's: this run's must not ask for others
+		memcpy(&h, cont[s].state.data(), sizeof(h));
+		const file_settings &fs = settings[s];
+		if (h.config.types_mask != fs.types || h.config.thresh != fs.thresh || h.config.filter_type != fs.filter) {
+			fprintf(stderr, "%s: kept with -T %x -t %d%s, this run asks for -T %x -t %d%s\n",
+				job_settings::kept_path(job.cont_prefix, s, ".state").c_str(), (unsigned)h.config.types_mask, (int)h.config.thresh,
+				h.config.filter_type ? " -W" : "", (unsigned)fs.types, fs.thresh, fs.filter ? " -W" : "");
+			return TFREC_AMD_E_INVAL;
+		}
+	}
+	job.cont = job.continuing() ? &cont : NULL;
+	std::vector<kept_bytes> kept(n);
 	for (size_t s = 0; s < n && !job.replay; s++) {
 		FILE *f = fopen(files[s].c_str(), "rb");
 		if (!f) {
@@ -320,12 +394,15 @@ int gpu_engine::run()
 			return TFREC_AMD_E_INVAL;
 		}
 		fseek(f, 0, SEEK_END);
-		// trailing partial block dropped, engine.cpp:72-76 (-r: a trailing partial piece of `unit` blocks)
-		const size_t blocks = (size_t)ftell(f) / piece * (size_t)unit;
+		// trailing partial block dropped, engine.cpp:72-76 (-r: a trailing partial piece of `unit` blocks; -k keeps it for the next
+		// part, -K reads the last part's ahead of the file)
+		kept[s] = plan_kept_bytes(cont.empty() ? 0 : cont[s].rest.size(), (size_t)ftell(f), piece, unit);
+		const size_t blocks = kept[s].blocks;
 		fclose(f);
 		if (job.dbg > 0 && job.fmt != TFREC_AMD_FMT_U8)  // -D with -F: how the file is cut
 			fprintf(stderr, "%s: %zu blocks, %zu bytes per %d\n", files[s].c_str(), blocks, piece, unit);
-		stream_samples[s] = (long long)blocks * TFREC_AMD_BLOCK_DEC;
+		// (-K: end_sample goes on counting from the saved sample count)
+		stream_samples[s] = (cont.empty() ? 0 : cont[s].samples()) + (long long)blocks * TFREC_AMD_BLOCK_DEC;
 		file_blocks[s] = blocks;
 	}
 	// what the output modes say before a device is opened
@@ -414,6 +491,9 @@ int gpu_engine::run()
 	}
 	if (cap.finish() && !rc)
 		rc = TFREC_AMD_E_INVAL;
+	for (size_t s = 0; s < n && job.keeping() && !rc; s++)  // -k: what is left of every file for its next part
+		rc = write_kept_rest(job, s, files[s], kept[s]);
+	job.cont = NULL;
 	if (job.scan && !rc)
 		scan.finish();
 	if (out_mode)  // -m 1: summary at the end (decoder.cpp:98-109)

@@ -197,6 +197,18 @@ public:
 	// " burst_centre=<Hz|->", the centre of the channel's burst with the largest pwr_max.  Under -A it is the scan's, not pass 1's.
 	// Neither the 1/16 rule behind the summary nor its usefulness has been measured on real recordings.
 	void set_meter() { job.meter = true; }
+	// -k: keep.  A file is processed in whole pieces only and nothing is padded; before the first batch behind a
+	// file's last one is submitted -- and at the end of the job -- its stream is saved (tfrec_amd_save_streams) to
+	// <prefix>.<file index>.state, and at the end of a run without an error the bytes that did not fill a piece are written to
+	// <prefix>.<file index>.rest (empty when none).  A file of no whole piece runs nothing: its .rest is all of it, its .state the
+	// one it continued from, if any.
+	// -K: continue.  <prefix>.<file index>.state is loaded into the file's stream before its first batch
+	// (tfrec_amd_load_streams: the saved settings, which the file's own must equal -- run() fails otherwise --, and the saved tunes), the bytes of
+	// <prefix>.<file index>.rest are read ahead of the file's own, and end_sample goes on counting from the saved sample count.
+	// Both: one stream per file for the whole job (no -n), every path once.  The host decoders' own memory (the -m 1 table, the
+	// "#nnn" counter) is not carried.  run() fails with TFREC_AMD_E_INVAL if a .state cannot be read.
+	void set_keep(const std::string &prefix) { job.keep_prefix = prefix; }
+	void set_continue(const std::string &prefix) { job.cont_prefix = prefix; }
 	// returns 0 on success, a TFREC_AMD_E_* code otherwise
 	int run();
 	// decoders of stream s in slot order (NULL for slots not registered)

@@ -6,6 +6,7 @@
 #define TFREC_AMD_HOST_JOB_H
 
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <string>
@@ -36,6 +37,41 @@ struct replay_file {
 	}
 };
 
+// -K: what a file continues from, read back whole before a device is opened: the stream's state blob (<prefix>.<file>.state,
+// tfrec_amd_load_streams) and the bytes of the part before it that did not fill a piece (<prefix>.<file>.rest; none: empty)
+struct kept_input {
+	std::vector<uint8_t> state, rest;
+	long long samples() const  // the decimated samples the stream has run (the blob header's samples_since_restart)
+	{
+		tfrec_amd_state_header h;
+		if (state.size() < sizeof(h))
+			return 0;
+		memcpy(&h, state.data(), sizeof(h));
+		return h.samples_since_restart;
+	}
+};
+
+// -k / -K: how the bytes of a file that arrives in pieces are used.  The input is `head` bytes carried in (-K's .rest, 0 without)
+// followed by the file's `file` bytes; it is processed in whole pieces of `piece` bytes = `unit` blocks and nothing is padded.
+// What does not fill a piece is the rest -- its last bytes, rest_head of them still the head's (a file shorter than a piece) and
+// rest_file the file's own last ones --, which -k writes out for the next part and a run without -k drops, as it always did.
+struct kept_bytes {
+	size_t blocks;                // whole blocks processed: pieces x unit
+	size_t used_head, used_file;  // bytes of the head and of the file that the pieces hold
+	size_t rest_head, rest_file;  // the rest, in input order: the head's last rest_head bytes, then the file's last rest_file
+};
+inline kept_bytes plan_kept_bytes(size_t head, size_t file, size_t piece, int unit)
+{
+	kept_bytes k;
+	const size_t used = piece ? (head + file) / piece * piece : 0;
+	k.blocks = piece ? used / piece * (size_t)unit : 0;
+	k.used_head = std::min(head, used);
+	k.used_file = used - k.used_head;
+	k.rest_head = head - k.used_head;
+	k.rest_file = file - k.used_file;
+	return k;
+}
+
 // Everything gpu_engine's set_* calls store (gpu_engine.h says what each mode does), one copy for the engine and all its workers,
 // and the input geometry that follows from it.
 struct job_settings {
@@ -58,6 +94,13 @@ struct job_settings {
 	int iq_windows = 0;            // set_iq (0: none)
 	bool meter = false;            // set_meter
 	const std::vector<replay_file> *replay = NULL;  // set_replay (NULL: the files are dumps)
+	std::string keep_prefix;       // set_keep ("": none)
+	std::string cont_prefix;       // set_continue ("": none)
+	const std::vector<kept_input> *cont = NULL;  // ... and what it read, per file (the engine's, before the workers start)
+
+	bool keeping() const { return !keep_prefix.empty(); }
+	bool continuing() const { return !cont_prefix.empty(); }
+	static std::string kept_path(const std::string &prefix, size_t file, const char *ext) { return prefix + "." + std::to_string(file) + ext; }
 
 	bool resampled() const { return rate_p != 1 || rate_q != 1; }
 	bool occupancy() const { return spectrum && occ_ratio; }  // -A, pass 1
@@ -119,9 +162,10 @@ struct batch_plan {
 // Files take free streams in order; a file's last batch may be partial (padded with silence, its events cut by the engine).
 // A batch has bps blocks unless no stream needs that many.  With one stream per file this is the plan of a run without -n:
 // every file starts in the first batch and no stream is ever reset.
-// settings: every file's; dflt: the context's.
+// settings: every file's; dflt: the context's.  whole (-k): no batch reaches past the end of a file it carries -- it has the blocks of
+// the file with the fewest left --, so that no stream is fed padding before its state is saved.
 inline std::vector<batch_plan> plan_batches(const std::vector<size_t> &file_blocks, const std::vector<file_settings> &settings,
-					    const file_settings &dflt, size_t s0, size_t s1, size_t nslots, int bps)
+					    const file_settings &dflt, size_t s0, size_t s1, size_t nslots, int bps, bool whole = false)
 {
 	std::vector<batch_plan> plan;
 	std::vector<file_settings> has(nslots, dflt);  // the settings each stream runs with
@@ -154,13 +198,15 @@ inline std::vector<batch_plan> plan_batches(const std::vector<size_t> &file_bloc
 				used[j] = true;
 			}
 		}
-		size_t most = 0;
+		size_t most = 0, least = (size_t)bps;
 		for (size_t j = 0; j < nslots; j++)
-			if (cur[j] >= 0)
+			if (cur[j] >= 0) {
 				most = std::max(most, left[j]);
+				least = std::min(least, left[j]);
+			}
 		if (most == 0)
 			break;
-		b.nb = (int)std::min<size_t>((size_t)bps, most);
+		b.nb = (int)(whole ? least : std::min<size_t>((size_t)bps, most));
 		b.file = cur;
 		for (size_t j = 0; j < nslots; j++)
 			if (cur[j] >= 0) {

@@ -249,6 +249,7 @@ struct cli {
 	const char *cap_prefix = NULL;  // -S
 	const char *replay_prefix = NULL;  // -R
 	bool meter = false;  // -M
+	const char *keep_prefix = NULL, *cont_prefix = NULL;  // -k, -K
 	bool have_center = false, have_format = false;  // -c, -F given (-R refuses them)
 	std::vector<replay_file> captures;  // -R: one per file index of <prefix>.idx
 	int spec_bins = 0, spec_g = 0;  // -P (spec_g 0: the default)
@@ -281,7 +282,7 @@ struct cli {
 
 static void usage()
 {
-	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
+	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
 			"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
 			"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
 			"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
@@ -293,6 +294,15 @@ static void usage()
 			"  -M          measure every burst's carrier offset and FSK deviation on the GPU, decoded or not: a line 'burst <file>\n"
 			"              <start_sample> <n_samples> <pwr_max> <centre_hz|-> <deviation_hz|->' per trigger window (-: no carrier); with -s or\n"
 			"              -A a column burst_centre= of the channel's strongest burst instead; also with -R; not with -X\n"
+			"  -k prefix   keep: for a recording that arrives in parts.  Every -L file is processed in whole blocks only (nothing is padded), then\n"
+			"              its receiver's state is saved to <prefix>.<file index>.state and the bytes that filled no block to\n"
+			"              <prefix>.<file index>.rest\n"
+			"  -K prefix   continue: before it starts, every -L file's receiver is loaded from <prefix>.<file index>.state (this run's -T, -t\n"
+			"              and -W must be the saved ones; the saved -f applies) and <prefix>.<file index>.rest is read ahead of the file's own bytes: the\n"
+			"              telegrams of the parts, -k on one and -K on the next, are those of the whole recording, one that lies across two\n"
+			"              parts included.  Same -T, -x, -r, -F, -z, -Z as the run that kept it.  Both may be given.  The host decoders' own\n"
+			"              memory is not carried: the -m 1 table and the '#nnn' counter start again.  Not with -n, -s, -A, -P, -R, -S, -M, -X\n"
+			"              or a path given to more than one -L\n"
 			"  -f kHz      receive frequency (default: the dumps' own, -c)\n"
 			"  -c kHz      frequency the dumps were recorded at (default 868250); -f within 767 kHz of it\n"
 			"  -x          the dumps are 15.36 MS/s u8 dumps (10x the rate); -f within 7679 kHz of -c, shifted ahead of the 10:1 stage\n"
@@ -366,9 +376,17 @@ bool cli::parse_format(const char *arg)
 int cli::parse(int argc, char **argv)
 {
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::Mh")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::Mk:K:h")) != -1) {
 		switch (c) {
 		case 'M': meter = true; break;
+		case 'k':
+		case 'K':
+			(c == 'k' ? keep_prefix : cont_prefix) = optarg;
+			if (!*optarg) {
+				fprintf(stderr, "tfrec_gpu: bad -%c '': want the prefix of the .state and .rest files\n", c);
+				return 2;
+			}
+			break;
 		case 'z': {
 			const char *a = optional_arg(argc, argv);
 			dc_windows = 2048;
@@ -482,6 +500,29 @@ int cli::check() const
 		fprintf(stderr, "tfrec_gpu: -R replays a capture, which is 384 kS/s int16 IQ and nothing else: not with -L, -x, -r, -F, -f, -c, -s, "
 				"-A, -P, -z, -Z, -S, -p or -X\n");
 		return 2;
+	}
+	if (keep_prefix || cont_prefix) {  // -k, -K: usage errors, before a device is opened
+		if (have_slots || have_scan || have_auto || have_spec_p || replay_prefix || cap_prefix || meter || hexfile) {
+			fprintf(stderr, "tfrec_gpu: -k and -K carry the receivers of -L files from one run to the next: not with -n, -s, -A, -P, -R, -S, "
+					"-M or -X\n");
+			return 2;
+		}
+		for (size_t i = 0; i < dumps.size(); i++)
+			for (size_t j = 0; j < i; j++)
+				if (dumps[i] == dumps[j]) {
+					fprintf(stderr, "tfrec_gpu: -k / -K: %s is given to more than one -L (a shared input's state is not kept)\n", dumps[i].c_str());
+					return 2;
+				}
+		for (size_t i = 0; i < dumps.size() && cont_prefix; i++) {
+			const std::string path = job_settings::kept_path(cont_prefix, i, ".state");
+			FILE *f = fopen(path.c_str(), "rb");
+			if (!f) {
+				fprintf(stderr, "tfrec_gpu: -K: ");
+				perror(path.c_str());
+				return 2;
+			}
+			fclose(f);
+		}
 	}
 	if (have_slots && slots < 1) {
 		fprintf(stderr, "tfrec_gpu: -n must be >= 1\n");
@@ -745,6 +786,10 @@ int cli::run()
 		e.set_capture(cap_prefix);
 	if (meter)
 		e.set_meter();
+	if (keep_prefix)
+		e.set_keep(keep_prefix);
+	if (cont_prefix)
+		e.set_continue(cont_prefix);
 	if (have_spec_p)  // the default record: the frames one block's input holds
 		e.set_spectrum(spec_bins, spec_g ? spec_g : (int)std::max(1L, (long)in.input_samples(1) / spec_bins), center);
 	int rc = e.run();
