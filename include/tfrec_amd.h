@@ -765,6 +765,76 @@ int tfrec_amd_enable_burst_meter(tfrec_amd_ctx *ctx);
  * nothing undrained or poisoned: TFREC_AMD_E_STATE. */
 int tfrec_amd_read_bursts(tfrec_amd_ctx *ctx, tfrec_amd_burst *out, size_t cap_runs, uint32_t *n_runs);
 
+/* Burst envelope (tfrec_amd_enable_burst_envelope): for every run of the recorder's table how long the burst itself was
+ * -- a run's n_samples includes the trigger's hold of W - 1 samples of noise behind the burst --, how far it stood above that noise,
+ * and whether it was one clean burst or a broken one.  It sits on the recorder as the burst meter does and is independent of it.
+ * There is no reference counterpart: this text is normative, tfrec_amd/envelope.py restates it.  Exact integers only.
+ *   Samples:  for entry e of a submit's table (tfrec_amd_run: stream s, submit-relative start a, n = n_samples, flags), z[k] = (I, Q) is
+ *             the decimated pair at submit-relative index a + k, 0 <= k < n, as tfrec_amd_read_decimated returns it.
+ *   Over:     over[k] is bit a + k of the stream's FINAL trigger mask of that submit: |I| + |Q| > the threshold in force at that sample,
+ *             the quantity tfrec_amd_level.n_over counts.  The mask of an auto stream is the one the threshold pass rewrote block by
+ *             block.  On a tfrec_amd_submit_runs submit the samples between the runs are (0, 0) and never over.
+ *   Record:   n_over = the number of k with over[k];  last_over = the largest such k, or -1 if there is none (a run without CONTINUES
+ *             starts at an over sample, so -1 occurs only in CONTINUES pieces).  head = the samples k <= last_over, tail = the samples
+ *             k > last_over: a run's last W - 1 samples are tail by construction, the burst's own noise reference.
+ *             energy_head, energy_tail = the sums of I*I + Q*Q over head and over tail.
+ *             A gap is a maximal stretch of not-over samples inside the head with an over sample on both sides within this piece:
+ *             n_gaps counts them, max_gap is the longest (0 if none).  lead_not_over = the not-over samples before the piece's first
+ *             over sample (n if there is none): 0 unless the piece CONTINUES; it is what rebuilds a gap that straddles a cut.
+ *             dot_*, crs_*, nprod_*: the burst meter's products (tfrec_amd_burst: Products, with its k0, its zero rule and its z[-1]),
+ *             product k counted in head if k <= last_over, else in tail: the mean frequency of the burst without its noise tail.
+ *   Cutting:  a burst is a chain of pieces: piece i + 1 has CONTINUES, piece i OPEN, on the same stream.  Two adjacent pieces A, B (or
+ *             a merged chain A and the next piece B) merge into the record the uncut run would have had:  n = nA + nB;  n_over adds;
+ *             if B has an over sample (last_over_B >= 0): last_over = nA + last_over_B, head = head_A + tail_A + head_B, tail = tail_B;
+ *             else last_over = last_over_A, head = head_A, tail = tail_A + tail_B -- for the energies, the product sums and counts.
+ *             lead_not_over = lead_A if A has an over sample, else nA + lead_B.  With j = (nA - 1 - last_over_A) + lead_B, the stretch
+ *             joined at the cut:  n_gaps = gaps_A + gaps_B + (A and B both have an over sample and j > 0), max_gap = max(max_A, max_B,
+ *             j if both have one).  A stretch counts once; one that ends up behind the chain's final last_over is tail, not a gap.
+ *             stream, start_sample, thresh and CONTINUES are A's, OPEN is B's.  The result does not depend on how the stream was cut
+ *             into submits.  A restart drops the chain, as it drops the carried trigger.
+ *   Summary (what a caller makes of a merged record; normative for tfrec_gpu -Q and envelope.py):  len = last_over + 1, the burst's
+ *             length;  n_tail = n - len;  ratio_c = floor(100 * energy_head * n_tail / (energy_tail * len)) in 128-bit integers: the
+ *             mean power of the burst over the mean power of its noise tail, in hundredths.  It is defined only if the chain is not
+ *             OPEN, len > 0, energy_tail > 0 and n_tail >= 64 (a condition, not a measurement: a shorter tail -- a chain cut off by
+ *             the input's end or by a restart -- is no noise reference).  snr_db = 10 log10(ratio_c / 100) in host double, printed
+ *             with one decimal; undefined when ratio_c is undefined or 0.  snr_db is presentation only: its last digit may depend on
+ *             the host's libm at a rounding tie; every exact comparison is made on ratio_c. */
+typedef struct {            /* 128 bytes */
+	uint32_t stream;        /* these five: copied from the table entry */
+	uint32_t flags;
+	int64_t  start_sample;
+	uint32_t n_samples;
+	int32_t  thresh;
+	uint32_t n_over;        /* samples with over[k] */
+	int32_t  last_over;     /* the largest k with over[k]; -1: none */
+	uint64_t energy_head;   /* sum of I*I + Q*Q over k <= last_over */
+	uint64_t energy_tail;   /* ... over k > last_over */
+	uint32_t n_gaps;
+	uint32_t max_gap;
+	uint32_t lead_not_over;
+	uint32_t nprod_head;    /* products counted with k <= last_over */
+	int64_t  dot_head;
+	int64_t  crs_head;
+	int64_t  dot_tail;
+	int64_t  crs_tail;
+	uint32_t nprod_tail;
+	uint32_t reserved[7];   /* 0 */
+} tfrec_amd_envelope;
+/* Turn the envelope on: after tfrec_amd_enable_capture, before the first submit.  max_runs * 128 bytes of device memory per FIFO set,
+ * counted in tfrec_amd_get_memory.  Errors: no recorder or a second call: TFREC_AMD_E_INVAL; after the first submit or a poisoned
+ * context: TFREC_AMD_E_STATE; TFREC_AMD_E_NOMEM as elsewhere; a call that fails leaves the context exactly as it was.  A context on
+ * which it was never called holds and launches what it did.  Independent of tfrec_amd_enable_burst_meter: either, both or neither.
+ * Valid on every kind of context and in every mode, as the recorder is.  Its three kernels run on the recorder's low-priority stream
+ * behind its own and behind the burst meter's. */
+int tfrec_amd_enable_burst_envelope(tfrec_amd_ctx *ctx);
+/* out[i] = the record of entry i of the table tfrec_amd_read_captures returns for the same submit.  Conventions of tfrec_amd_read_bursts:
+ * the OLDEST undrained submit, read BEFORE the drain that pops it; reading pops nothing; cap_runs is the room in records; *n_runs the
+ * submit's true run count; out may be NULL with cap_runs 0 to fetch the count alone.  It reads the decimated samples and the mask, not
+ * the pool: records are delivered for every entry below min(n_runs, max_runs), whatever max_samples is.  n_runs > max_runs:
+ * TFREC_AMD_E_OVERFLOW with that prefix delivered.  Errors: not enabled, NULL ctx / n_runs / out (with cap_runs > 0), room too small
+ * (nothing written, *n_runs set): TFREC_AMD_E_INVAL; nothing undrained or poisoned: TFREC_AMD_E_STATE. */
+int tfrec_amd_read_burst_envelopes(tfrec_amd_ctx *ctx, tfrec_amd_envelope *out, size_t cap_runs, uint32_t *n_runs);
+
 /* Power spectrum of the input rows (tfrec_amd_enable_spectrum): where in a recording there is energy, and where the
  * short bursts are that an average hides -- before a receiver is placed.  It belongs to an input ROW of a submit, not to a stream: it
  * is taken on x, the int16 value every format maps a stored component to (tfrec_amd_create_format; -8192 <= x <= 8191), at the

@@ -184,15 +184,16 @@ def merge(pieces):
     return o
 
 
-def chains(submits, restarts=None):
+def chains(submits, restarts=None, join=None):
     """submits: one BURST_DTYPE array per submit, in order -> the merged bursts, in the order in which they end (per submit: table
     order), a chain still open behind the last submit last (by stream).  restarts: {submit index: streams that restart with it}:
-    their open chains end there."""
+    their open chains end there.  join: what merges a chain's pieces (default: merge; envelope.py passes its own)."""
+    join = join or merge
     open_, out = {}, []
     for k, recs in enumerate(submits):
         for s in sorted((restarts or {}).get(k, ())):
             if s in open_:
-                out.append(merge(open_.pop(s)))
+                out.append(join(open_.pop(s)))
         seen = set()
         for r in recs:
             s = int(r["stream"])
@@ -201,15 +202,15 @@ def chains(submits, restarts=None):
                 open_[s].append(r)
             else:
                 if s in open_:  # (cannot happen without a restart: an open piece is continued)
-                    out.append(merge(open_.pop(s)))
+                    out.append(join(open_.pop(s)))
                 open_[s] = [r]
             seen.add(s)
             if not fl & RUN_OPEN:
-                out.append(merge(open_.pop(s)))
+                out.append(join(open_.pop(s)))
         for s in sorted(set(open_) - seen):  # open, and nothing of the stream at this submit's first sample: the trigger ended there
-            out.append(merge(open_.pop(s)))
+            out.append(join(open_.pop(s)))
     for s in sorted(open_):
-        out.append(merge(open_[s]))
+        out.append(join(open_[s]))
     return out
 
 

@@ -27,6 +27,7 @@ using namespace tfrec;
 #include "capi_streams.h"  // reset, configure, the three tunes, map, and their getters
 #include "capi_decin.h"    // the channel-rate constructor, the recorder's pre samples, sparse submits
 #include "capi_burst.h"    // the burst meter's enable and read
+#include "capi_envelope.h" // the burst envelope's enable and read
 #include "capi_state.h"    // a stream's state blob: its header, the inventory table, save and load
 
 extern "C" {

@@ -93,6 +93,11 @@ struct BurstMeter {
 	bool on = false;
 	tfrec_amd_burst *d_recs[kSets] = {};
 };
+// tfrec_amd_enable_burst_envelope: per set the record of every run of the set's table
+struct BurstEnvelope {
+	bool on = false;
+	tfrec_amd_envelope *d_recs[kSets] = {};
+};
 // tfrec_amd_create_decimated (PreStage::kChannel): the carried last pair of every stream
 struct DecIn {
 	uint32_t *d_last = nullptr;
@@ -293,6 +298,7 @@ struct tfrec_amd_ctx {
 	CaptureOut cap;
 	CapturePre cap_pre;
 	BurstMeter burst;
+	BurstEnvelope env;
 	DecIn decin;
 	RunsIn runs_in;
 	SpectrumOut spec;

@@ -379,6 +379,8 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 			HIPCHK(launch_capture_pre(c->cap.lane.st, out, c->sample_base, b, c->cap_pre.d_pre[set]));
 		if (c->burst.on)  // the burst meter: behind the copy kernel too, on the table and the recorder's working set
 			HIPCHK(launch_burst_meter(c->cap.lane.st, out, b, c->burst.d_recs[set]));
+		if (c->env.on)  // the burst envelope: behind the copy kernel and the meter, on the table, the working set and the final mask
+			HIPCHK(launch_burst_envelope(c->cap.lane.st, out, b, c->env.d_recs[set]));
 		HIPCHK(lane_written(c->cap.lane, set));
 	}
 	if (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) {

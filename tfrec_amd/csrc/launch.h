@@ -76,6 +76,7 @@ hipError_t launch_levels(hipStream_t st, const FrontOut &o, LevelState *lev, con
 hipError_t launch_capture(hipStream_t st, const FrontOut &o, long long sample_base, const CaptureBufs &b, const StreamCfg *scfg);
 hipError_t launch_capture_pre(hipStream_t st, const FrontOut &o, long long sample_base, const CaptureBufs &b, uint32_t *pre);
 hipError_t launch_burst_meter(hipStream_t st, const FrontOut &o, const CaptureBufs &b, tfrec_amd_burst *out);
+hipError_t launch_burst_envelope(hipStream_t st, const FrontOut &o, const CaptureBufs &b, tfrec_amd_envelope *out);
 hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, const SpectrumBufs &b);
 hipError_t launch_occupancy(hipStream_t st, const SpectrumBufs &b, uint32_t ratio, uint32_t rel, tfrec_amd_occupancy *recs, uint32_t *bits);
 // ... and the parity probes

@@ -51,6 +51,7 @@ private:
 	int collect(size_t k, batch_result &b);
 	int read_captures(size_t k, batch_result &b);
 	int read_bursts(size_t k, batch_result &b);
+	int read_envelopes(size_t k, batch_result &b);
 	typedef int (*estimate_reader)(tfrec_amd_ctx *, int32_t, int16_t *, size_t, int *);
 	int read_last_estimate(size_t k, estimate_reader reader, std::vector<int> &files, std::vector<int16_t> &last);
 	int read_dc(size_t k, batch_result &b) { return read_last_estimate(k, tfrec_amd_read_dc, b.dc_file, b.dc_last); }  // -z -D
@@ -241,7 +242,7 @@ inline int device_worker::open_context()
 		r = tfrec_amd_map_streams(ctx, all.data(), in_row.data(), (int)n);
 	}
 	if (!r && job.recorder()) {  // -S, sized so that no submit overflows: every sample, and a stream's runs are >= 356 samples long but two
-		call = "tfrec_amd_enable_capture";  // (-M without -S: the table alone, a pool of one pair)
+		call = "tfrec_amd_enable_capture";  // (-M or -Q without -S: the table alone, a pool of one pair)
 		r = tfrec_amd_enable_capture(ctx, (uint32_t)(n * ((size_t)bps * TFREC_AMD_BLOCK_DEC / 356 + 3)),
 					     job.capture ? (uint64_t)n * (uint64_t)bps * TFREC_AMD_BLOCK_DEC : 1);
 	}
@@ -252,6 +253,10 @@ inline int device_worker::open_context()
 	if (!r && job.metering()) {  // -M: the meter on the recorder's table
 		call = "tfrec_amd_enable_burst_meter";
 		r = tfrec_amd_enable_burst_meter(ctx);
+	}
+	if (!r && job.enveloping()) {  // -Q: the envelope on the recorder's table
+		call = "tfrec_amd_enable_burst_envelope";
+		r = tfrec_amd_enable_burst_envelope(ctx);
 	}
 	if (!r && job.replay) {  // -R, sized so that every submit fits: its files' runs (a cut adds one per stream), every sample at most
 		uint64_t runs = 0, pairs = 0;
@@ -538,6 +543,44 @@ inline int device_worker::read_bursts(size_t k, batch_result &b)
 	return 0;
 }
 
+// -Q: the batch's envelope records.  stream -> file, as for the events; a record that begins behind its file's end is dropped, one
+// that reaches over it has its n_samples cut there and is OPEN: the input's end cut its tail (its sums are the device's: the
+// padding is silence and never over, so last_over lies ahead of the cut)
+inline int device_worker::read_envelopes(size_t k, batch_result &b)
+{
+	uint32_t nr = 0;
+	int r = tfrec_amd_read_burst_envelopes(ctx, NULL, 0, &nr);  // (the count: E_INVAL for want of room)
+	if (r == TFREC_AMD_E_INVAL && nr) {
+		b.envelopes.resize(nr);
+		r = tfrec_amd_read_burst_envelopes(ctx, b.envelopes.data(), b.envelopes.size(), &nr);
+	}
+	if (r == TFREC_AMD_E_OVERFLOW) {  // (cannot happen: the table is sized for the worst case)
+		fprintf(stderr, "tfrec_amd: device %d batch %zu: more runs than the table holds, %zu of %u envelope records kept\n", device, k,
+			b.envelopes.size(), (unsigned)nr);
+		r = 0;
+	}
+	if (r)
+		return r;
+	const std::vector<int> &file = plan[k].file;
+	size_t kept = 0;
+	for (size_t q = 0; q < b.envelopes.size(); q++) {
+		tfrec_amd_envelope x = b.envelopes[q];
+		if (x.stream >= file.size() || file[x.stream] < 0)
+			continue;
+		const long long end = (long long)file_blocks[file[x.stream]] * TFREC_AMD_BLOCK_DEC;
+		if (x.start_sample >= end)
+			continue;
+		if (x.start_sample + (long long)x.n_samples > end) {
+			x.n_samples = (uint32_t)(end - x.start_sample);
+			x.flags |= TFREC_AMD_RUN_OPEN;
+		}
+		x.stream = (uint32_t)file[x.stream];
+		b.envelopes[kept++] = x;
+	}
+	b.envelopes.resize(kept);
+	return 0;
+}
+
 // -z -D, -Z -D: the last estimate of every file's row -- d, or (t, g) -- by the stage's reader
 inline int device_worker::read_last_estimate(size_t k, estimate_reader reader, std::vector<int> &files, std::vector<int16_t> &last)
 {
@@ -568,6 +611,8 @@ inline int device_worker::collect(size_t k, batch_result &b)
 	int r = job.capture ? read_captures(k, b) : 0;
 	if (!r && job.metering())
 		r = read_bursts(k, b);
+	if (!r && job.enveloping())
+		r = read_envelopes(k, b);
 	if (!r && job.occupancy()) {  // -A: the detector's records in place of the spectrum's, 16 + N / 8 bytes each
 		int nr = 0;
 		r = tfrec_amd_read_occupancy(ctx, 0, NULL, NULL, 0, &nr);  // (the count: E_INVAL for want of room)

@@ -273,6 +273,11 @@ void scan_table::finish() const
 			printf(" burst_centre=%ld", c.burst_centre);
 		else if (job->metering())
 			printf(" burst_centre=-");
+		unsigned long long ratio = 0;
+		if (job->enveloping() && c.burst_snr(ratio))  // -Q: the median ratio_c of the channel's bursts that have one
+			printf(" burst_snr=%llu.%02llu", ratio / 100, ratio % 100);
+		else if (job->enveloping())
+			printf(" burst_snr=-");
 		printf("\n");
 	}
 }
@@ -414,6 +419,9 @@ int gpu_engine::run()
 	burst_merger bursts;
 	std::vector<tfrec_amd_burst> ended;
 	bursts.begin(n);
+	envelope_merger envelopes;
+	std::vector<tfrec_amd_envelope> extents;
+	envelopes.begin(n);
 	if (job.spectrum)
 		spec.begin(job);
 	if (job.occupancy())
@@ -456,6 +464,16 @@ int gpu_engine::run()
 						scan.chan[x.stream].note(x);
 					else
 						printf("%s\n", burst_line(files[x.stream], x).c_str());
+				}
+			}
+			if (job.enveloping()) {  // -Q: likewise, behind -M's lines of the batch
+				extents.clear();
+				envelopes.take(b, workers[d].plan[k], file_blocks, extents);
+				for (const tfrec_amd_envelope &x : extents) {
+					if (job.scan)
+						scan.chan[x.stream].note(x);
+					else
+						printf("%s\n", envelope_line(files[x.stream], x).c_str());
 				}
 			}
 			if (job.occupancy()) {  // no replay: the channel list is the product

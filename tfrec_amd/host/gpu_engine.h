@@ -197,6 +197,14 @@ public:
 	// " burst_centre=<Hz|->", the centre of the channel's burst with the largest pwr_max.  Under -A it is the scan's, not pass 1's.
 	// Neither the 1/16 rule behind the summary nor its usefulness has been measured on real recordings.
 	void set_meter() { job.meter = true; }
+	// -Q: the burst envelope (tfrec_amd_enable_burst_envelope), with or without -M.  Every context enables the recorder
+	// as for -M and the envelope on it; run() merges the records' chains across the batches of a file (job.h: envelope_merger; a
+	// chain still open at the file's end is flushed there, OPEN) and prints, as each burst ends,
+	//   extent <file> <start_sample> <n_samples> <burst_samples> <n_over> <n_gaps> <max_gap> <ratio_c|-> <snr_db|->
+	// (job.h: envelope_summary; ratio_c in hundredths as %d.%02d, "-": undefined).  With set_scan the lines are not printed: the
+	// table's lines end in " burst_snr=<ratio_c|->", the median ratio_c of the channel's bursts that have one (of an even count the
+	// lower middle one).  Under -A it is the scan's, not pass 1's.
+	void set_envelope() { job.envelope = true; }
 	// -k: keep.  A file is processed in whole pieces only and nothing is padded; before the first batch behind a
 	// file's last one is submitted -- and at the end of the job -- its stream is saved (tfrec_amd_save_streams) to
 	// <prefix>.<file index>.state, and at the end of a run without an error the bytes that did not fill a piece are written to

@@ -5,7 +5,9 @@
 #ifndef TFREC_AMD_HOST_JOB_H
 #define TFREC_AMD_HOST_JOB_H
 
+#include <math.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -93,6 +95,7 @@ struct job_settings {
 	int dc_windows = 0;            // set_dc (0: none)
 	int iq_windows = 0;            // set_iq (0: none)
 	bool meter = false;            // set_meter
+	bool envelope = false;         // set_envelope
 	const std::vector<replay_file> *replay = NULL;  // set_replay (NULL: the files are dumps)
 	std::string keep_prefix;       // set_keep ("": none)
 	std::string cont_prefix;       // set_continue ("": none)
@@ -104,8 +107,9 @@ struct job_settings {
 
 	bool resampled() const { return rate_p != 1 || rate_q != 1; }
 	bool occupancy() const { return spectrum && occ_ratio; }  // -A, pass 1
-	bool recorder() const { return capture || metering(); }  // the contexts enable the recorder: for -S, or as the meter's table
+	bool recorder() const { return capture || metering() || enveloping(); }  // the contexts enable the recorder: for -S, or as the meter's or the envelope's table
 	bool metering() const { return meter && !occupancy(); }  // -M (under -A: in the scan, not in pass 1)
+	bool enveloping() const { return envelope && !occupancy(); }  // -Q (likewise)
 	bool share() const { return slots <= 0; }  // one stream per file for the whole job: a path given several times is read once
 	// -r: the blocks a piece of a file holds, q / gcd(q, 64) -- the odd part of a q <= 64, 6 at 625/384; 1 without -r: every
 	// batch carries a multiple of it (tfrec_amd_create_rate: Submits)
@@ -345,8 +349,10 @@ inline std::vector<occ_channel> occupancy_channels(const std::vector<unsigned lo
 // -A: the detector's records of row 0 and their bitmap words, [record][N / 32]
 // -z with -D: per file of the batch its index in the job and the last window's {d_I, d_Q} of its row
 // -M: the burst records that belong to a file (stream = its index in the job), n_samples cut at the file's end
+// -Q: the envelope records likewise; one that is cut at the file's end is OPEN (the input's end cut its tail)
 struct batch_result {
 	std::vector<tfrec_amd_burst> bursts;
+	std::vector<tfrec_amd_envelope> envelopes;
 	std::vector<tfrec_amd_event> ev;
 	std::vector<tfrec_amd_level> lv;
 	std::vector<tfrec_amd_run> runs;
@@ -471,11 +477,81 @@ inline std::string burst_line(const std::string &file, const tfrec_amd_burst &r)
 	return s + " - -";
 }
 
+// ---- -Q: the burst envelope's records (include/tfrec_amd.h: tfrec_amd_envelope, whose text is normative; tfrec_amd/envelope.py
+// restates merge, summary and the line)
+
+// piece p, which CONTINUES the chain c, merged into it: the record the two would have had as one piece (the header's Cutting)
+inline void envelope_add(tfrec_amd_envelope &c, const tfrec_amd_envelope &p)
+{
+	const long long na = c.n_samples, la = c.last_over, lb = p.last_over;
+	const long long joined = (na - 1 - la) + p.lead_not_over;  // the stretch of not-over samples across the cut
+	const bool both = la >= 0 && lb >= 0;
+	c.n_gaps += p.n_gaps + (both && joined > 0 ? 1u : 0u);
+	c.max_gap = std::max(std::max(c.max_gap, p.max_gap), both ? (uint32_t)joined : 0u);
+	if (la < 0)
+		c.lead_not_over = (uint32_t)(na + p.lead_not_over);
+	if (lb >= 0) {  // everything of c lies ahead of p's last over sample: head
+		c.energy_head += c.energy_tail + p.energy_head;
+		c.dot_head += c.dot_tail + p.dot_head;
+		c.crs_head += c.crs_tail + p.crs_head;
+		c.nprod_head += c.nprod_tail + p.nprod_head;
+		c.energy_tail = p.energy_tail;
+		c.dot_tail = p.dot_tail;
+		c.crs_tail = p.crs_tail;
+		c.nprod_tail = p.nprod_tail;
+		c.last_over = (int32_t)(na + lb);
+	} else {  // (p's head is empty)
+		c.energy_tail += p.energy_tail;
+		c.dot_tail += p.dot_tail;
+		c.crs_tail += p.crs_tail;
+		c.nprod_tail += p.nprod_tail;
+	}
+	c.n_samples += p.n_samples;
+	c.n_over += p.n_over;
+	c.flags = (c.flags & TFREC_AMD_RUN_CONTINUES) | (p.flags & TFREC_AMD_RUN_OPEN);
+}
+
+// -> the burst's length and its tail's, and whether ratio_c is defined (the chain not OPEN, len > 0, energy_tail > 0, n_tail >= 64);
+// then ratio_c = floor(100 energy_head n_tail / (energy_tail len)), in 128-bit integers
+inline bool envelope_summary(const tfrec_amd_envelope &r, long long &len, long long &n_tail, unsigned long long &ratio_c)
+{
+	len = (long long)r.last_over + 1;
+	n_tail = (long long)r.n_samples - len;
+	if ((r.flags & TFREC_AMD_RUN_OPEN) || len <= 0 || !r.energy_tail || n_tail < 64)
+		return false;
+	const unsigned __int128 num = (unsigned __int128)100 * r.energy_head * (unsigned long long)n_tail;
+	const unsigned __int128 den = (unsigned __int128)r.energy_tail * (unsigned long long)len;
+	ratio_c = (unsigned long long)(num / den);  // (< 100 * 2^31 * 2^32)
+	return true;
+}
+
+// extent <file> <start_sample> <n_samples> <burst_samples> <n_over> <n_gaps> <max_gap> <ratio_c as %d.%02d|-> <snr_db|->
+inline std::string envelope_line(const std::string &file, const tfrec_amd_envelope &r)
+{
+	long long len = 0, n_tail = 0;
+	unsigned long long ratio = 0;
+	const bool have = envelope_summary(r, len, n_tail, ratio);
+	std::string s = "extent " + file + " " + std::to_string((long long)r.start_sample) + " " + std::to_string(r.n_samples) + " " +
+			std::to_string(len) + " " + std::to_string(r.n_over) + " " + std::to_string(r.n_gaps) + " " + std::to_string(r.max_gap);
+	if (!have)
+		return s + " - -";
+	char buf[96];
+	snprintf(buf, sizeof(buf), " %llu.%02llu", ratio / 100, ratio % 100);
+	s += buf;
+	if (!ratio)
+		return s + " -";
+	snprintf(buf, sizeof(buf), " %.1f", 10.0 * log10((double)ratio / 100.0));  // presentation only: ratio_c is the exact figure
+	return s + buf;
+}
+
+inline void chain_add(tfrec_amd_burst &c, const tfrec_amd_burst &p) { burst_add(c, p); }
+inline void chain_add(tfrec_amd_envelope &c, const tfrec_amd_envelope &p) { envelope_add(c, p); }
+
 // The chains of pieces across a job's batches, per file (a record's stream is its file's index in the job).  A chain ends with a
 // piece that is not OPEN, with a batch that does not continue it, and with its file: a chain still open at a file's end is flushed
 // there.  take() appends the bursts that ended with the batch, in the order in which they ended.
-struct burst_merger {
-	std::vector<tfrec_amd_burst> chain;
+template <class R> struct chain_merger {
+	std::vector<R> chain;
 	std::vector<char> open, seen;
 	std::vector<unsigned long long> blocks;  // of every file, in the batches so far
 	void begin(size_t n_files)
@@ -485,12 +561,12 @@ struct burst_merger {
 		seen.assign(n_files, 0);
 		blocks.assign(n_files, 0);
 	}
-	void take(const batch_result &b, const batch_plan &p, const std::vector<size_t> &file_blocks, std::vector<tfrec_amd_burst> &out)
+	void take(const std::vector<R> &recs, const batch_plan &p, const std::vector<size_t> &file_blocks, std::vector<R> &out)
 	{
-		for (const tfrec_amd_burst &r : b.bursts) {
+		for (const R &r : recs) {
 			const size_t f = r.stream;
 			if ((r.flags & TFREC_AMD_RUN_CONTINUES) && open[f]) {
-				burst_add(chain[f], r);
+				chain_add(chain[f], r);
 			} else {
 				if (open[f])
 					out.push_back(chain[f]);
@@ -515,6 +591,18 @@ struct burst_merger {
 		}
 	}
 };
+struct burst_merger : chain_merger<tfrec_amd_burst> {  // -M
+	void take(const batch_result &b, const batch_plan &p, const std::vector<size_t> &file_blocks, std::vector<tfrec_amd_burst> &out)
+	{
+		chain_merger<tfrec_amd_burst>::take(b.bursts, p, file_blocks, out);
+	}
+};
+struct envelope_merger : chain_merger<tfrec_amd_envelope> {  // -Q
+	void take(const batch_result &b, const batch_plan &p, const std::vector<size_t> &file_blocks, std::vector<tfrec_amd_envelope> &out)
+	{
+		chain_merger<tfrec_amd_envelope>::take(b.envelopes, p, file_blocks, out);
+	}
+};
 
 // -s: the scan table (gpu_engine.h: set_scan).  Per channel (file) the sums of its level records, its telegrams, and with -D
 // every record; with -M the centre of the channel's burst with the largest pwr_max (the first of them).
@@ -533,6 +621,24 @@ struct scan_table {
 				burst_peak = r.pwr_max;
 				burst_carrier = burst_summary(r, burst_centre, dev);
 			}
+		}
+		std::vector<unsigned long long> ratios;  // -Q: ratio_c of the channel's chains that have one
+		void note(const tfrec_amd_envelope &r)
+		{
+			long long len = 0, n_tail = 0;
+			unsigned long long ratio = 0;
+			if (envelope_summary(r, len, n_tail, ratio))
+				ratios.push_back(ratio);
+		}
+		// the median: of an even count the lower of the two in the middle
+		bool burst_snr(unsigned long long &ratio) const
+		{
+			if (ratios.empty())
+				return false;
+			std::vector<unsigned long long> v(ratios);
+			std::sort(v.begin(), v.end());
+			ratio = v[(v.size() - 1) / 2];
+			return true;
 		}
 	};
 	const job_settings *job;

@@ -78,6 +78,17 @@
 // none does, no carrier).  With -s or -A the lines are left out and every line of the channel table ends in burst_centre=<Hz|->, the
 // centre of the channel's window with the largest pwr_max.  Works with -R, -S, -n, -d and every input option; not with -X.  The
 // 1/16 rule was chosen on synthetic scenes; it has not been measured on real recordings.
+// -Q (not in the reference): the burst envelope (tfrec_amd_enable_burst_envelope): for every trigger window of every
+// file, whether or not anything decoded in it, how long the burst itself was (a window's n_samples includes the trigger's hold of W - 1
+// samples of noise behind it), how far it stood above that noise, and whether it was one burst or a broken one.  The contexts enable
+// the recorder as for -M and the envelope; the pieces of a window that is cut by a submit boundary are merged, and stdout gets, as
+// each window ends (a window still open at its file's end: there),
+//   extent <file> <start_sample> <n_samples> <burst_samples> <n_over> <n_gaps> <max_gap> <ratio_c|-> <snr_db|->
+// burst_samples: up to the last sample over the threshold; n_over: the samples over it; n_gaps, max_gap: the stretches below it
+// inside the burst; ratio_c: the burst's mean power over its tail's, exact, printed in hundredths ("-": the window is open at the
+// input's end, or its tail is shorter than 64 samples or silent); snr_db = 10 log10 of it, one decimal.  With -s or -A the lines are
+// left out and every line of the channel table ends in burst_snr=<ratio_c|->, the median of the channel's windows that have one.
+// Works with -M, -R, -S, -n, -d and every input option; not with -X.
 // -P bins[,frames_per_record] (not in the reference): the power spectrum of ONE recording, beside its decoding: an
 // exact integer DFT of bins = 64, 128, 256, 512 or 1024 bins over the raw input -- at 1.536 MS/s, or given with -x, or with -r / -F --,
 // per record of frames_per_record frames (1 .. 16384; default: the frames one block's input holds, at least 1) the sum and the peak
@@ -249,6 +260,7 @@ struct cli {
 	const char *cap_prefix = NULL;  // -S
 	const char *replay_prefix = NULL;  // -R
 	bool meter = false;  // -M
+	bool envelope = false;  // -Q
 	const char *keep_prefix = NULL, *cont_prefix = NULL;  // -k, -K
 	bool have_center = false, have_format = false;  // -c, -F given (-R refuses them)
 	std::vector<replay_file> captures;  // -R: one per file index of <prefix>.idx
@@ -282,7 +294,7 @@ struct cli {
 
 static void usage()
 {
-	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
+	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
 			"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
 			"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
 			"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
@@ -294,6 +306,10 @@ static void usage()
 			"  -M          measure every burst's carrier offset and FSK deviation on the GPU, decoded or not: a line 'burst <file>\n"
 			"              <start_sample> <n_samples> <pwr_max> <centre_hz|-> <deviation_hz|->' per trigger window (-: no carrier); with -s or\n"
 			"              -A a column burst_centre= of the channel's strongest burst instead; also with -R; not with -X\n"
+			"  -Q          measure every burst's length, gaps and signal-to-noise ratio on the GPU, decoded or not: a line 'extent <file>\n"
+			"              <start_sample> <n_samples> <burst_samples> <n_over> <n_gaps> <max_gap> <ratio|-> <snr_db|->' per trigger window\n"
+			"              (-: no noise tail to compare with); with -s or -A a column burst_snr= of the channel's median ratio instead;\n"
+			"              also with -M and -R; not with -X, -k or -K\n"
 			"  -k prefix   keep: for a recording that arrives in parts.  Every -L file is processed in whole blocks only (nothing is padded), then\n"
 			"              its receiver's state is saved to <prefix>.<file index>.state and the bytes that filled no block to\n"
 			"              <prefix>.<file index>.rest\n"
@@ -376,9 +392,10 @@ bool cli::parse_format(const char *arg)
 int cli::parse(int argc, char **argv)
 {
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::Mk:K:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQk:K:h")) != -1) {
 		switch (c) {
 		case 'M': meter = true; break;
+		case 'Q': envelope = true; break;
 		case 'k':
 		case 'K':
 			(c == 'k' ? keep_prefix : cont_prefix) = optarg;
@@ -507,6 +524,10 @@ int cli::check() const
 					"-M or -X\n");
 			return 2;
 		}
+		if (envelope) {
+			fprintf(stderr, "tfrec_gpu: -k and -K do not carry a burst across runs: not with -Q\n");
+			return 2;
+		}
 		for (size_t i = 0; i < dumps.size(); i++)
 			for (size_t j = 0; j < i; j++)
 				if (dumps[i] == dumps[j]) {
@@ -551,6 +572,10 @@ int cli::check() const
 	}
 	if (meter && hexfile) {
 		fprintf(stderr, "tfrec_gpu: -M measures the bursts of -L files or of a capture (-R): not with -X\n");
+		return 1;
+	}
+	if (envelope && hexfile) {
+		fprintf(stderr, "tfrec_gpu: -Q measures the bursts of -L files or of a capture (-R): not with -X\n");
 		return 1;
 	}
 	if (cap_prefix && hexfile) {
@@ -786,6 +811,8 @@ int cli::run()
 		e.set_capture(cap_prefix);
 	if (meter)
 		e.set_meter();
+	if (envelope)
+		e.set_envelope();
 	if (keep_prefix)
 		e.set_keep(keep_prefix);
 	if (cont_prefix)
