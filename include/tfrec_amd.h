@@ -835,6 +835,67 @@ int tfrec_amd_enable_burst_envelope(tfrec_amd_ctx *ctx);
  * (nothing written, *n_runs set): TFREC_AMD_E_INVAL; nothing undrained or poisoned: TFREC_AMD_E_STATE. */
 int tfrec_amd_read_burst_envelopes(tfrec_amd_ctx *ctx, tfrec_amd_envelope *out, size_t cap_runs, uint32_t *n_runs);
 
+/* Burst clock (tfrec_amd_enable_burst_clock): for every run of the recorder's table how fast the burst is keyed -- the
+ * one property that separates the five protocols (38400, 17240, 9600, 8842 and 6000 bit/s) from each other and from foreign
+ * transmitters.  It sits on the recorder as the burst meter and the envelope do and is independent of both.  There is no reference
+ * counterpart: this text is normative, tfrec_amd/clock.py restates it.  Exact integers only.
+ *   Samples:  for entry e of a submit's table (tfrec_amd_run: stream s, submit-relative start a, n = n_samples, flags), z[m] = (I, Q) is
+ *             the decimated pair at submit-relative index m, as tfrec_amd_read_decimated returns it.
+ *   Segments: segment q is the samples [1024 q, 1024 q + 1024); it counts for the entry iff it lies wholly inside [a, a + n).  Every
+ *             submit is a whole number of 8192-sample blocks and start_sample counts from a restart at a submit boundary, so a
+ *             submit-relative multiple of 1024 is one in start_sample terms: a segment never straddles a cut, and it is whole in a
+ *             piece iff it is whole in the uncut run.  Nothing outside the segment is read: no prevdec, no pair ahead of the run.
+ *   Products: with m' = m mod 1024: for m' >= 1, dot[m] = I[m] I[m-1] + Q[m] Q[m-1] and crs[m] = Q[m] I[m-1] - I[m] Q[m-1] (the burst
+ *             meter's products), in 64 bits; |dot|, |crs| <= 2^31.  mx = the largest |dot| or |crs| of the segment.  mx == 0: the
+ *             segment is SILENT, counts in n_silent and adds nothing else.  Otherwise sh = max(0, bitlength(mx) - 15) (bitlength(2^31)
+ *             = 32), d = dot >> sh, c = crs >> sh, arithmetic shifts: -2^15 <= d, c < 2^15.
+ *   Signal:   for m' >= 2, g[m] = d[m] d[m-1] + c[m] c[m-1], |g| <= 2^31, and g16[m] = min(g[m] >> 16, 32767), an int16 (the minimum
+ *             binds only where all four factors are -2^15);  g16[m] = 0 for m' < 2.  This is the real part of the second-order
+ *             product: it dips at every frequency transition, does not depend on the carrier offset, and is weighted by the fourth
+ *             power of the amplitude, so a run's noise tail does not count; the shift normalises each segment by its own peak.
+ *   Spectrum: for bins j = 4 .. 131 (375 j Hz; array index j - 4):  X_re = sum over the segment of g16[m] C[(4 j m') mod 4096], X_im
+ *             likewise with S -- C, S the tune table of tfrec_amd_tune_streams --, |X| < 2^40;  P_j = (X_re >> 16)^2 + (X_im >> 16)^2
+ *             < 2^49.
+ *   Record:   n_segments = the entry's counted segments that are not silent, n_silent = those that are, spec[j - 4] = the sum of P_j
+ *             over the former.
+ *   Cutting:  a burst is a chain of pieces as for tfrec_amd_burst.  Merging adds n_samples, n_segments, n_silent and spec (spec
+ *             saturates at 2^64 - 1, which cannot happen below 2^15 segments); stream, start_sample, thresh and CONTINUES are the
+ *             first piece's, OPEN is the last one's.  By the segment rule the result is the uncut run's record.  A restart drops the
+ *             chain.
+ *   Summary (what a caller makes of a merged record; normative for tfrec_gpu -C and clock.py), in 128-bit integers, P[j] = spec[j - 4]:
+ *             the band is j = 12 .. 128 (4500 .. 48000 Hz, 117 bins), tot its sum; the summary is undefined iff n_segments == 0 or tot
+ *             == 0.  jp = the lowest j of the band's maximum;  num = P[jp+1] - P[jp-1], den = 2 P[jp] - P[jp-1] - P[jp+1];  off =
+ *             floor((375 num + den) / (2 den)) if den > 0 and neither neighbour exceeds P[jp], else 0 (floor for a negative numerator
+ *             too);  clock_hz = 375 jp + off;  quality_c = floor(100 * 117 * P[jp] / tot), the peak over the band's mean in
+ *             hundredths.  The resolution is the 375 Hz bin, off a refinement; a rate above 48 kHz or below 4.5 kHz is not found; on a
+ *             preamble or Manchester-like data a harmonic or the half rate may win; no quality threshold is built in.  Neither the
+ *             band, the segment length nor the usefulness of quality_c has been measured on real recordings. */
+typedef struct {            /* 1056 bytes */
+	uint32_t stream;        /* these five: copied from the table entry */
+	uint32_t flags;
+	int64_t  start_sample;
+	uint32_t n_samples;
+	int32_t  thresh;
+	uint32_t n_segments;    /* counted segments that are not silent */
+	uint32_t n_silent;      /* counted segments whose every product is zero */
+	uint64_t spec[128];     /* bin j = 4 + index, 375 j Hz: the sum of P_j over the n_segments segments */
+} tfrec_amd_clock;
+/* Turn the clock on: after tfrec_amd_enable_capture, before the first submit.  max_runs * 1056 bytes of device memory per FIFO set,
+ * counted in tfrec_amd_get_memory.  Errors: no recorder, a second call, or a context of max_blocks >= 4096 (a record's spec is summed
+ * on the device: below 2^15 segments it cannot overflow): TFREC_AMD_E_INVAL; after the first submit or a poisoned context:
+ * TFREC_AMD_E_STATE; TFREC_AMD_E_NOMEM as elsewhere; a call that fails leaves the context exactly as it was.  A context on which it
+ * was never called holds and launches what it did.  Independent of tfrec_amd_enable_burst_meter and tfrec_amd_enable_burst_envelope:
+ * any subset.  Valid on every kind of context and in every mode, as the recorder is.  Its two kernels run on the recorder's
+ * low-priority stream behind its own, the burst meter's and the envelope's. */
+int tfrec_amd_enable_burst_clock(tfrec_amd_ctx *ctx);
+/* out[i] = the record of entry i of the table tfrec_amd_read_captures returns for the same submit.  Conventions of tfrec_amd_read_bursts:
+ * the OLDEST undrained submit, read BEFORE the drain that pops it; reading pops nothing; cap_runs is the room in records; *n_runs the
+ * submit's true run count; out may be NULL with cap_runs 0 to fetch the count alone.  It reads the decimated samples, not the pool:
+ * records are delivered for every entry below min(n_runs, max_runs), whatever max_samples is.  n_runs > max_runs:
+ * TFREC_AMD_E_OVERFLOW with that prefix delivered.  Errors: not enabled, NULL ctx / n_runs / out (with cap_runs > 0), room too small
+ * (nothing written, *n_runs set): TFREC_AMD_E_INVAL; nothing undrained or poisoned: TFREC_AMD_E_STATE. */
+int tfrec_amd_read_burst_clocks(tfrec_amd_ctx *ctx, tfrec_amd_clock *out, size_t cap_runs, uint32_t *n_runs);
+
 /* Power spectrum of the input rows (tfrec_amd_enable_spectrum): where in a recording there is energy, and where the
  * short bursts are that an average hides -- before a receiver is placed.  It belongs to an input ROW of a submit, not to a stream: it
  * is taken on x, the int16 value every format maps a stored component to (tfrec_amd_create_format; -8192 <= x <= 8191), at the

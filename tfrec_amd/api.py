@@ -15,6 +15,7 @@ import numpy as np
 from . import _build
 from .burst import BURST_DTYPE  # tfrec_amd_burst
 from .capture import RUN_DTYPE  # tfrec_amd_run
+from .clock import CLOCK_DTYPE  # tfrec_amd_clock
 from .envelope import ENVELOPE_DTYPE  # tfrec_amd_envelope
 from .levels import LEVEL_DTYPE  # tfrec_amd_level
 from .occupancy import OCC_DTYPE  # tfrec_amd_occupancy
@@ -113,6 +114,7 @@ EXPORTS = (
     "tfrec_amd_read_capture_pre", "tfrec_amd_enable_runs_input", "tfrec_amd_submit_runs", "tfrec_amd_read_biquad_row",
     "tfrec_amd_enable_burst_meter", "tfrec_amd_read_bursts", "tfrec_amd_stream_state_bytes", "tfrec_amd_save_streams",
     "tfrec_amd_load_streams", "tfrec_amd_enable_burst_envelope", "tfrec_amd_read_burst_envelopes",
+    "tfrec_amd_enable_burst_clock", "tfrec_amd_read_burst_clocks",
 )
 
 _libs = {}
@@ -214,6 +216,8 @@ def load_library(build: bool = True, experiments: bool = False, short_segments: 
     L.tfrec_amd_read_bursts.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
     L.tfrec_amd_enable_burst_envelope.argtypes = [C.c_void_p]
     L.tfrec_amd_read_burst_envelopes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+    L.tfrec_amd_enable_burst_clock.argtypes = [C.c_void_p]
+    L.tfrec_amd_read_burst_clocks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
     L.tfrec_amd_stream_state_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
     L.tfrec_amd_save_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
     L.tfrec_amd_load_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
@@ -661,6 +665,27 @@ class Receiver:
             return np.zeros(0, dtype=ENVELOPE_DTYPE)
         out = np.zeros(min(nr.value, getattr(self, "_capture", (0, 0))[0]), dtype=ENVELOPE_DTYPE)
         _check(self.L, self.L.tfrec_amd_read_burst_envelopes(self.h, out.ctypes.data, len(out), C.byref(nr)), ok=ok)
+        return out
+
+    def enable_burst_clock(self):
+        """Turn the burst clock on (tfrec_amd_enable_burst_clock; after enable_capture, before the first submit; with or without
+        the burst meter and the envelope).  read_burst_clocks returns its records."""
+        _check(self.L, self.L.tfrec_amd_enable_burst_clock(self.h))
+
+    def read_burst_clocks(self, allow_overflow: bool = False) -> np.ndarray:
+        """The clock records of the OLDEST undrained submit (tfrec_amd_read_burst_clocks; call it before the drain that pops that
+        submit) -> a CLOCK_DTYPE array, one record per entry of that submit's run table (clock.py).  They do not depend on the
+        pool: a table with more than max_runs entries (E_OVERFLOW) raises unless allow_overflow, then its first max_runs records
+        are returned; clock_total holds the submit's true run count."""
+        ok = (E_OK, E_OVERFLOW) if allow_overflow else (E_OK,)
+        nr = C.c_uint32(0)
+        rc = self.L.tfrec_amd_read_burst_clocks(self.h, None, 0, C.byref(nr))  # the count (no room: E_INVAL)
+        self.clock_total = int(nr.value)
+        if rc != E_INVAL or nr.value == 0:
+            _check(self.L, rc, ok=ok)
+            return np.zeros(0, dtype=CLOCK_DTYPE)
+        out = np.zeros(min(nr.value, getattr(self, "_capture", (0, 0))[0]), dtype=CLOCK_DTYPE)
+        _check(self.L, self.L.tfrec_amd_read_burst_clocks(self.h, out.ctypes.data, len(out), C.byref(nr)), ok=ok)
         return out
 
     def enable_runs_input(self, max_runs: int, max_samples: int):

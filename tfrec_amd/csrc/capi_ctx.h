@@ -98,6 +98,11 @@ struct BurstEnvelope {
 	bool on = false;
 	tfrec_amd_envelope *d_recs[kSets] = {};
 };
+// tfrec_amd_enable_burst_clock: per set the record of every run of the set's table
+struct BurstClock {
+	bool on = false;
+	tfrec_amd_clock *d_recs[kSets] = {};
+};
 // tfrec_amd_create_decimated (PreStage::kChannel): the carried last pair of every stream
 struct DecIn {
 	uint32_t *d_last = nullptr;
@@ -299,6 +304,7 @@ struct tfrec_amd_ctx {
 	CapturePre cap_pre;
 	BurstMeter burst;
 	BurstEnvelope env;
+	BurstClock clk;
 	DecIn decin;
 	RunsIn runs_in;
 	SpectrumOut spec;

@@ -381,6 +381,8 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 			HIPCHK(launch_burst_meter(c->cap.lane.st, out, b, c->burst.d_recs[set]));
 		if (c->env.on)  // the burst envelope: behind the copy kernel and the meter, on the table, the working set and the final mask
 			HIPCHK(launch_burst_envelope(c->cap.lane.st, out, b, c->env.d_recs[set]));
+		if (c->clk.on)  // the burst clock: behind the envelope, on the table, the working set and the decimated samples
+			HIPCHK(launch_burst_clock(c->cap.lane.st, out, b, c->clk.d_recs[set]));
 		HIPCHK(lane_written(c->cap.lane, set));
 	}
 	if (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) {

@@ -77,6 +77,7 @@ hipError_t launch_capture(hipStream_t st, const FrontOut &o, long long sample_ba
 hipError_t launch_capture_pre(hipStream_t st, const FrontOut &o, long long sample_base, const CaptureBufs &b, uint32_t *pre);
 hipError_t launch_burst_meter(hipStream_t st, const FrontOut &o, const CaptureBufs &b, tfrec_amd_burst *out);
 hipError_t launch_burst_envelope(hipStream_t st, const FrontOut &o, const CaptureBufs &b, tfrec_amd_envelope *out);
+hipError_t launch_burst_clock(hipStream_t st, const FrontOut &o, const CaptureBufs &b, tfrec_amd_clock *out);
 hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, const SpectrumBufs &b);
 hipError_t launch_occupancy(hipStream_t st, const SpectrumBufs &b, uint32_t ratio, uint32_t rel, tfrec_amd_occupancy *recs, uint32_t *bits);
 // ... and the parity probes

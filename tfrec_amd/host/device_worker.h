@@ -52,6 +52,7 @@ private:
 	int read_captures(size_t k, batch_result &b);
 	int read_bursts(size_t k, batch_result &b);
 	int read_envelopes(size_t k, batch_result &b);
+	int read_clocks(size_t k, batch_result &b);
 	typedef int (*estimate_reader)(tfrec_amd_ctx *, int32_t, int16_t *, size_t, int *);
 	int read_last_estimate(size_t k, estimate_reader reader, std::vector<int> &files, std::vector<int16_t> &last);
 	int read_dc(size_t k, batch_result &b) { return read_last_estimate(k, tfrec_amd_read_dc, b.dc_file, b.dc_last); }  // -z -D
@@ -242,7 +243,7 @@ inline int device_worker::open_context()
 		r = tfrec_amd_map_streams(ctx, all.data(), in_row.data(), (int)n);
 	}
 	if (!r && job.recorder()) {  // -S, sized so that no submit overflows: every sample, and a stream's runs are >= 356 samples long but two
-		call = "tfrec_amd_enable_capture";  // (-M or -Q without -S: the table alone, a pool of one pair)
+		call = "tfrec_amd_enable_capture";  // (-M, -Q or -C without -S: the table alone, a pool of one pair)
 		r = tfrec_amd_enable_capture(ctx, (uint32_t)(n * ((size_t)bps * TFREC_AMD_BLOCK_DEC / 356 + 3)),
 					     job.capture ? (uint64_t)n * (uint64_t)bps * TFREC_AMD_BLOCK_DEC : 1);
 	}
@@ -257,6 +258,10 @@ inline int device_worker::open_context()
 	if (!r && job.enveloping()) {  // -Q: the envelope on the recorder's table
 		call = "tfrec_amd_enable_burst_envelope";
 		r = tfrec_amd_enable_burst_envelope(ctx);
+	}
+	if (!r && job.clocking()) {  // -C: the clock on the recorder's table
+		call = "tfrec_amd_enable_burst_clock";
+		r = tfrec_amd_enable_burst_clock(ctx);
 	}
 	if (!r && job.replay) {  // -R, sized so that every submit fits: its files' runs (a cut adds one per stream), every sample at most
 		uint64_t runs = 0, pairs = 0;
@@ -581,6 +586,44 @@ inline int device_worker::read_envelopes(size_t k, batch_result &b)
 	return 0;
 }
 
+// -C: the batch's clock records.  stream -> file, as for the events; a record that begins behind its file's end is dropped, one
+// that reaches over it has its n_samples cut there and is OPEN (its sums are the device's: the padding is silence, and a segment
+// of silence counts in n_silent and adds nothing else)
+inline int device_worker::read_clocks(size_t k, batch_result &b)
+{
+	uint32_t nr = 0;
+	int r = tfrec_amd_read_burst_clocks(ctx, NULL, 0, &nr);  // (the count: E_INVAL for want of room)
+	if (r == TFREC_AMD_E_INVAL && nr) {
+		b.clocks.resize(nr);
+		r = tfrec_amd_read_burst_clocks(ctx, b.clocks.data(), b.clocks.size(), &nr);
+	}
+	if (r == TFREC_AMD_E_OVERFLOW) {  // (cannot happen: the table is sized for the worst case)
+		fprintf(stderr, "tfrec_amd: device %d batch %zu: more runs than the table holds, %zu of %u clock records kept\n", device, k,
+			b.clocks.size(), (unsigned)nr);
+		r = 0;
+	}
+	if (r)
+		return r;
+	const std::vector<int> &file = plan[k].file;
+	size_t kept = 0;
+	for (size_t q = 0; q < b.clocks.size(); q++) {
+		tfrec_amd_clock x = b.clocks[q];
+		if (x.stream >= file.size() || file[x.stream] < 0)
+			continue;
+		const long long end = (long long)file_blocks[file[x.stream]] * TFREC_AMD_BLOCK_DEC;
+		if (x.start_sample >= end)
+			continue;
+		if (x.start_sample + (long long)x.n_samples > end) {
+			x.n_samples = (uint32_t)(end - x.start_sample);
+			x.flags |= TFREC_AMD_RUN_OPEN;
+		}
+		x.stream = (uint32_t)file[x.stream];
+		b.clocks[kept++] = x;
+	}
+	b.clocks.resize(kept);
+	return 0;
+}
+
 // -z -D, -Z -D: the last estimate of every file's row -- d, or (t, g) -- by the stage's reader
 inline int device_worker::read_last_estimate(size_t k, estimate_reader reader, std::vector<int> &files, std::vector<int16_t> &last)
 {
@@ -613,6 +656,8 @@ inline int device_worker::collect(size_t k, batch_result &b)
 		r = read_bursts(k, b);
 	if (!r && job.enveloping())
 		r = read_envelopes(k, b);
+	if (!r && job.clocking())
+		r = read_clocks(k, b);
 	if (!r && job.occupancy()) {  // -A: the detector's records in place of the spectrum's, 16 + N / 8 bytes each
 		int nr = 0;
 		r = tfrec_amd_read_occupancy(ctx, 0, NULL, NULL, 0, &nr);  // (the count: E_INVAL for want of room)

@@ -278,6 +278,10 @@ void scan_table::finish() const
 			printf(" burst_snr=%llu.%02llu", ratio / 100, ratio % 100);
 		else if (job->enveloping())
 			printf(" burst_snr=-");
+		if (job->clocking() && c.have_clock)  // -C: the clock of the channel's burst with the largest quality_c
+			printf(" burst_clock=%lld", c.clock_hz);
+		else if (job->clocking())
+			printf(" burst_clock=-");
 		printf("\n");
 	}
 }
@@ -422,6 +426,9 @@ int gpu_engine::run()
 	envelope_merger envelopes;
 	std::vector<tfrec_amd_envelope> extents;
 	envelopes.begin(n);
+	clock_merger clocks;
+	std::vector<tfrec_amd_clock> keyed;
+	clocks.begin(n);
 	if (job.spectrum)
 		spec.begin(job);
 	if (job.occupancy())
@@ -474,6 +481,16 @@ int gpu_engine::run()
 						scan.chan[x.stream].note(x);
 					else
 						printf("%s\n", envelope_line(files[x.stream], x).c_str());
+				}
+			}
+			if (job.clocking()) {  // -C: likewise, behind -Q's lines of the batch
+				keyed.clear();
+				clocks.take(b, workers[d].plan[k], file_blocks, keyed);
+				for (const tfrec_amd_clock &x : keyed) {
+					if (job.scan)
+						scan.chan[x.stream].note(x);
+					else
+						printf("%s\n", clock_line(files[x.stream], x).c_str());
 				}
 			}
 			if (job.occupancy()) {  // no replay: the channel list is the product

@@ -205,6 +205,15 @@ public:
 	// table's lines end in " burst_snr=<ratio_c|->", the median ratio_c of the channel's bursts that have one (of an even count the
 	// lower middle one).  Under -A it is the scan's, not pass 1's.
 	void set_envelope() { job.envelope = true; }
+	// -C: the burst clock (tfrec_amd_enable_burst_clock), with or without -M and -Q.  Every context enables the
+	// recorder as for -M and the clock on it; run() merges the records' chains across the batches of a file (job.h: clock_merger; a
+	// chain still open at the file's end is flushed there, OPEN) and prints, as each burst ends,
+	//   clock <file> <start_sample> <n_samples> <n_segments> <clock_hz|-> <quality|->
+	// (job.h: clock_summary; quality_c in hundredths as %d.%02d, "-": no whole segment, or an empty band).  With set_scan the lines
+	// are not printed: the table's lines end in " burst_clock=<Hz|->", the clock_hz of the channel's chain with the largest quality_c,
+	// the earliest among equals.  Under -A it is the scan's, not pass 1's.  Neither the band, the segment length nor the usefulness
+	// of quality_c has been measured on real recordings.
+	void set_clock() { job.clock = true; }
 	// -k: keep.  A file is processed in whole pieces only and nothing is padded; before the first batch behind a
 	// file's last one is submitted -- and at the end of the job -- its stream is saved (tfrec_amd_save_streams) to
 	// <prefix>.<file index>.state, and at the end of a run without an error the bytes that did not fill a piece are written to

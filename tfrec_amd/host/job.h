@@ -96,6 +96,7 @@ struct job_settings {
 	int iq_windows = 0;            // set_iq (0: none)
 	bool meter = false;            // set_meter
 	bool envelope = false;         // set_envelope
+	bool clock = false;            // set_clock
 	const std::vector<replay_file> *replay = NULL;  // set_replay (NULL: the files are dumps)
 	std::string keep_prefix;       // set_keep ("": none)
 	std::string cont_prefix;       // set_continue ("": none)
@@ -107,9 +108,10 @@ struct job_settings {
 
 	bool resampled() const { return rate_p != 1 || rate_q != 1; }
 	bool occupancy() const { return spectrum && occ_ratio; }  // -A, pass 1
-	bool recorder() const { return capture || metering() || enveloping(); }  // the contexts enable the recorder: for -S, or as the meter's or the envelope's table
+	bool recorder() const { return capture || metering() || enveloping() || clocking(); }  // the contexts enable the recorder: for -S, or as the meter's, the envelope's or the clock's table
 	bool metering() const { return meter && !occupancy(); }  // -M (under -A: in the scan, not in pass 1)
 	bool enveloping() const { return envelope && !occupancy(); }  // -Q (likewise)
+	bool clocking() const { return clock && !occupancy(); }  // -C (likewise)
 	bool share() const { return slots <= 0; }  // one stream per file for the whole job: a path given several times is read once
 	// -r: the blocks a piece of a file holds, q / gcd(q, 64) -- the odd part of a q <= 64, 6 at 625/384; 1 without -r: every
 	// batch carries a multiple of it (tfrec_amd_create_rate: Submits)
@@ -350,9 +352,11 @@ inline std::vector<occ_channel> occupancy_channels(const std::vector<unsigned lo
 // -z with -D: per file of the batch its index in the job and the last window's {d_I, d_Q} of its row
 // -M: the burst records that belong to a file (stream = its index in the job), n_samples cut at the file's end
 // -Q: the envelope records likewise; one that is cut at the file's end is OPEN (the input's end cut its tail)
+// -C: the clock records likewise
 struct batch_result {
 	std::vector<tfrec_amd_burst> bursts;
 	std::vector<tfrec_amd_envelope> envelopes;
+	std::vector<tfrec_amd_clock> clocks;
 	std::vector<tfrec_amd_event> ev;
 	std::vector<tfrec_amd_level> lv;
 	std::vector<tfrec_amd_run> runs;
@@ -544,7 +548,63 @@ inline std::string envelope_line(const std::string &file, const tfrec_amd_envelo
 	return s + buf;
 }
 
+// ---- -C: the burst clock's records (include/tfrec_amd.h: tfrec_amd_clock, whose text is normative; tfrec_amd/clock.py restates
+// merge, summary and the line)
+
+// piece p, which CONTINUES the chain c, merged into it: the sums added, spec saturating at 2^64 - 1 (the header's Cutting)
+inline void clock_add(tfrec_amd_clock &c, const tfrec_amd_clock &p)
+{
+	c.n_samples += p.n_samples;
+	c.n_segments += p.n_segments;
+	c.n_silent += p.n_silent;
+	for (int i = 0; i < 128; i++) {
+		const uint64_t v = c.spec[i] + p.spec[i];
+		c.spec[i] = v < p.spec[i] ? UINT64_MAX : v;
+	}
+	c.flags = (c.flags & TFREC_AMD_RUN_CONTINUES) | (p.flags & TFREC_AMD_RUN_OPEN);
+}
+
+// -> whether the summary is defined (n_segments > 0 and the band j = 12 .. 128 not empty); then clock_hz = 375 jp + off and
+// quality_c = floor(100 * 117 * P[jp] / tot), in 128-bit integers (P[j] = spec[j - 4] may be saturated: 117 of them need 71 bits)
+inline bool clock_summary(const tfrec_amd_clock &r, long long &clock_hz, unsigned long long &quality_c)
+{
+	unsigned __int128 tot = 0;
+	int jp = 12;
+	for (int j = 12; j <= 128; j++) {
+		tot += r.spec[j - 4];
+		if (r.spec[j - 4] > r.spec[jp - 4])
+			jp = j;  // (the lowest j of the maximum)
+	}
+	if (!r.n_segments || !tot)
+		return false;
+	const __int128 p0 = r.spec[jp - 4], pm = r.spec[jp - 5], pp = r.spec[jp - 3];
+	const __int128 num = pp - pm, den = 2 * p0 - pm - pp;
+	__int128 off = 0;
+	if (den > 0 && pm <= p0 && pp <= p0) {
+		const __int128 a = 375 * num + den, b = 2 * den;  // floor(a / b), b > 0
+		off = a / b - ((a % b) < 0 ? 1 : 0);
+	}
+	clock_hz = 375LL * jp + (long long)off;
+	quality_c = (unsigned long long)((unsigned __int128)100 * 117 * (unsigned __int128)p0 / tot);  // (<= 100 * 117)
+	return true;
+}
+
+// clock <file> <start_sample> <n_samples> <n_segments> <clock_hz|-> <quality_c as %d.%02d|->
+inline std::string clock_line(const std::string &file, const tfrec_amd_clock &r)
+{
+	long long hz = 0;
+	unsigned long long q = 0;
+	std::string s = "clock " + file + " " + std::to_string((long long)r.start_sample) + " " + std::to_string(r.n_samples) + " " +
+			std::to_string(r.n_segments);
+	if (!clock_summary(r, hz, q))
+		return s + " - -";
+	char buf[96];
+	snprintf(buf, sizeof(buf), " %lld %llu.%02llu", hz, q / 100, q % 100);
+	return s + buf;
+}
+
 inline void chain_add(tfrec_amd_burst &c, const tfrec_amd_burst &p) { burst_add(c, p); }
+inline void chain_add(tfrec_amd_clock &c, const tfrec_amd_clock &p) { clock_add(c, p); }
 inline void chain_add(tfrec_amd_envelope &c, const tfrec_amd_envelope &p) { envelope_add(c, p); }
 
 // The chains of pieces across a job's batches, per file (a record's stream is its file's index in the job).  A chain ends with a
@@ -603,6 +663,12 @@ struct envelope_merger : chain_merger<tfrec_amd_envelope> {  // -Q
 		chain_merger<tfrec_amd_envelope>::take(b.envelopes, p, file_blocks, out);
 	}
 };
+struct clock_merger : chain_merger<tfrec_amd_clock> {  // -C
+	void take(const batch_result &b, const batch_plan &p, const std::vector<size_t> &file_blocks, std::vector<tfrec_amd_clock> &out)
+	{
+		chain_merger<tfrec_amd_clock>::take(b.clocks, p, file_blocks, out);
+	}
+};
 
 // -s: the scan table (gpu_engine.h: set_scan).  Per channel (file) the sums of its level records, its telegrams, and with -D
 // every record; with -M the centre of the channel's burst with the largest pwr_max (the first of them).
@@ -629,6 +695,19 @@ struct scan_table {
 			unsigned long long ratio = 0;
 			if (envelope_summary(r, len, n_tail, ratio))
 				ratios.push_back(ratio);
+		}
+		bool have_clock = false;  // -C: the clock of the channel's chain with the largest quality_c, the earliest among equals
+		long long clock_hz = 0;
+		unsigned long long clock_quality = 0;
+		void note(const tfrec_amd_clock &r)
+		{
+			long long hz = 0;
+			unsigned long long q = 0;
+			if (clock_summary(r, hz, q) && (!have_clock || q > clock_quality)) {
+				have_clock = true;
+				clock_hz = hz;
+				clock_quality = q;
+			}
 		}
 		// the median: of an even count the lower of the two in the middle
 		bool burst_snr(unsigned long long &ratio) const

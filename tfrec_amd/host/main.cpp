@@ -89,6 +89,18 @@
 // input's end, or its tail is shorter than 64 samples or silent); snr_db = 10 log10 of it, one decimal.  With -s or -A the lines are
 // left out and every line of the channel table ends in burst_snr=<ratio_c|->, the median of the channel's windows that have one.
 // Works with -M, -R, -S, -n, -d and every input option; not with -X.
+// -C (not in the reference): the burst clock (tfrec_amd_enable_burst_clock): for every trigger window of every file,
+// whether or not anything decoded in it, how fast the burst is keyed -- what separates the five protocols (38400, 17240, 9600, 8842,
+// 6000 bit/s) from each other and from foreign transmitters.  The contexts enable the recorder as for -M and the clock; the pieces of
+// a window that is cut by a submit boundary are merged, and stdout gets, as each window ends (a window still open at its file's end:
+// there),
+//   clock <file> <start_sample> <n_samples> <n_segments> <clock_hz|-> <quality|->
+// n_segments: the whole 1024-sample segments of the window that entered the spectrum; clock_hz: the peak of the spectrum of the
+// window's frequency transitions between 4.5 and 48 kHz, in 375 Hz bins refined by its neighbours; quality: that peak over the
+// band's mean, in hundredths ("-": the window holds no whole segment).  With -s or -A the lines are left out and every line of the
+// channel table ends in burst_clock=<Hz|->, the clock of the channel's window with the largest quality.  Works with -M, -Q, -R, -S,
+// -n, -d and every input option; not with -X, -k or -K.  No quality threshold is built in: noise reads a quality of a few units,
+// a clean telegram 25 or more on synthetic scenes; none of it has been measured on real recordings.
 // -P bins[,frames_per_record] (not in the reference): the power spectrum of ONE recording, beside its decoding: an
 // exact integer DFT of bins = 64, 128, 256, 512 or 1024 bins over the raw input -- at 1.536 MS/s, or given with -x, or with -r / -F --,
 // per record of frames_per_record frames (1 .. 16384; default: the frames one block's input holds, at least 1) the sum and the peak
@@ -261,6 +273,7 @@ struct cli {
 	const char *replay_prefix = NULL;  // -R
 	bool meter = false;  // -M
 	bool envelope = false;  // -Q
+	bool clock = false;  // -C
 	const char *keep_prefix = NULL, *cont_prefix = NULL;  // -k, -K
 	bool have_center = false, have_format = false;  // -c, -F given (-R refuses them)
 	std::vector<replay_file> captures;  // -R: one per file index of <prefix>.idx
@@ -294,7 +307,7 @@ struct cli {
 
 static void usage()
 {
-	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
+	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
 			"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
 			"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
 			"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
@@ -310,6 +323,10 @@ static void usage()
 			"              <start_sample> <n_samples> <burst_samples> <n_over> <n_gaps> <max_gap> <ratio|-> <snr_db|->' per trigger window\n"
 			"              (-: no noise tail to compare with); with -s or -A a column burst_snr= of the channel's median ratio instead;\n"
 			"              also with -M and -R; not with -X, -k or -K\n"
+			"  -C          measure every burst's symbol rate on the GPU, decoded or not: a line 'clock <file> <start_sample> <n_samples>\n"
+			"              <n_segments> <clock_hz|-> <quality|->' per trigger window (quality: the spectral peak over the band's mean; -: no\n"
+			"              whole 1024-sample segment); with -s or -A a column burst_clock= of the channel's best-quality burst instead;\n"
+			"              also with -M, -Q and -R; not with -X, -k or -K\n"
 			"  -k prefix   keep: for a recording that arrives in parts.  Every -L file is processed in whole blocks only (nothing is padded), then\n"
 			"              its receiver's state is saved to <prefix>.<file index>.state and the bytes that filled no block to\n"
 			"              <prefix>.<file index>.rest\n"
@@ -392,10 +409,11 @@ bool cli::parse_format(const char *arg)
 int cli::parse(int argc, char **argv)
 {
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQk:K:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCk:K:h")) != -1) {
 		switch (c) {
 		case 'M': meter = true; break;
 		case 'Q': envelope = true; break;
+		case 'C': clock = true; break;
 		case 'k':
 		case 'K':
 			(c == 'k' ? keep_prefix : cont_prefix) = optarg;
@@ -528,6 +546,10 @@ int cli::check() const
 			fprintf(stderr, "tfrec_gpu: -k and -K do not carry a burst across runs: not with -Q\n");
 			return 2;
 		}
+		if (clock) {
+			fprintf(stderr, "tfrec_gpu: -k and -K do not carry a burst across runs: not with -C\n");
+			return 2;
+		}
 		for (size_t i = 0; i < dumps.size(); i++)
 			for (size_t j = 0; j < i; j++)
 				if (dumps[i] == dumps[j]) {
@@ -576,6 +598,10 @@ int cli::check() const
 	}
 	if (envelope && hexfile) {
 		fprintf(stderr, "tfrec_gpu: -Q measures the bursts of -L files or of a capture (-R): not with -X\n");
+		return 1;
+	}
+	if (clock && hexfile) {
+		fprintf(stderr, "tfrec_gpu: -C measures the bursts of -L files or of a capture (-R): not with -X\n");
 		return 1;
 	}
 	if (cap_prefix && hexfile) {
@@ -813,6 +839,8 @@ int cli::run()
 		e.set_meter();
 	if (envelope)
 		e.set_envelope();
+	if (clock)
+		e.set_clock();
 	if (keep_prefix)
 		e.set_keep(keep_prefix);
 	if (cont_prefix)
