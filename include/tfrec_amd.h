@@ -896,6 +896,78 @@ int tfrec_amd_enable_burst_clock(tfrec_amd_ctx *ctx);
  * (nothing written, *n_runs set): TFREC_AMD_E_INVAL; nothing undrained or poisoned: TFREC_AMD_E_STATE. */
 int tfrec_amd_read_burst_clocks(tfrec_amd_ctx *ctx, tfrec_amd_clock *out, size_t cap_runs, uint32_t *n_runs);
 
+/* Burst track (tfrec_amd_enable_burst_track): for every run of the recorder's table what the burst SAID -- one bit per
+ * captured sample, the sign of a quadrature discriminator about a centre frequency, boxcar-smoothed: 1 above the centre.  With the
+ * rate from the burst clock and the centre from the burst meter a caller slices it into the burst's bits, at any rate, decoded or
+ * not.  It sits on the recorder as the meter, the envelope and the clock do and is independent of them.  There is no reference
+ * counterpart: this text is normative, tfrec_amd/track.py restates it.  Exact integers only.
+ *   Settings: smooth = L, 1 .. 16, fixed at enable.  Per stream a centre hz, |hz| <= 192000, default 0
+ *             (tfrec_amd_set_burst_track_centre); its table index r = floor((8192 hz + 384000) / 768000) mod 4096, a true floor for a
+ *             negative hz too; C[], S[] are the tune table of tfrec_amd_tune_streams and no other.  A new centre takes effect with the
+ *             next submit.  It is not a restart: a chain that spans the change is sliced with both, every product -- the carried ones
+ *             included -- with the centre of the submit that forms it.
+ *   Samples:  for entry e of a submit's table (tfrec_amd_run: stream s, submit-relative start a, n = n_samples, flags), z[k] = (I, Q),
+ *             k = 0 .. n - 1, is the decimated pair at submit-relative index a + k, as for tfrec_amd_burst.  prior = the samples of the
+ *             same chain ahead of this piece, held at 16: 0 without TFREC_AMD_RUN_CONTINUES, else min(16, prior' + n') of the OPEN
+ *             piece (prior', n') that ended the submit before.
+ *   Products: dot[k] = I[k] I[k-1] + Q[k] Q[k-1] and crs[k] = Q[k] I[k-1] - I[k] Q[k-1], the burst meter's products, in 64 bits;
+ *             v[k] = crs[k] C[r] - dot[k] S[r], |v| < 2^47.  v[k] = 0 for the chain's first sample (k = 0 with prior = 0), and nothing
+ *             ahead of the chain's first sample is ever used.  In a CONTINUES piece z[k] for -16 <= k < 0 are the stream's last 16
+ *             pairs of the submit before, so the products of k - i < 0 are those of that submit's last samples.
+ *   Track:    t[k] = 1 iff the sum of v[k - i] over 0 <= i < min(L, k + prior) is greater than 0 (no term: 0; a zero sum: 0); the
+ *             sum stays below 2^51.
+ *   Bits:     a bitmap of uint32 words: t[k] of entry e is bit (pool_offset_e + k) & 31 of word (pool_offset_e + k) >> 5, pool_offset
+ *             the table entry's.  Bits that belong to no run, or to a run whose samples do not fit max_samples, are 0.
+ *   Record:   the entry's first 24 bytes, bit_offset = its pool_offset, last_over = tfrec_amd_envelope's (the run-relative index of the
+ *             run's last sample over the threshold in the final trigger mask, -1: none), n_ones = the number of k with t[k] = 1
+ *             (counted whether or not the bits fit).
+ *   Cutting:  a burst is a chain of pieces as for tfrec_amd_burst.  Merging concatenates the tracks, adds n_samples and n_ones, merges
+ *             last_over by the envelope's rule (the last piece that has one, offset by the samples ahead of it), and takes the first
+ *             piece's stream, start_sample, thresh and CONTINUES and the last piece's OPEN.  With one centre the merged record and
+ *             track do not depend on how the stream was cut into submits.  A restart drops the chain.  tfrec_amd_save_streams does
+ *             not carry the 16 pairs: a chain that continues behind tfrec_amd_load_streams uses what the context itself carried.
+ *   Slicing (what a caller makes of a merged track; normative for tfrec_gpu -G and track.py): the input is the track's first
+ *             last_over + 1 samples (none if -1) and a rate R in bit/s.  sym(l) = floor((2 l R + 384000) / 768000).  Walk the maximal
+ *             runs (w, m) of equal track value w and length m in order, keeping (v, l): while nothing is kept a run with sym(m) == 0 is
+ *             dropped and the first other run becomes (v, l); afterwards a run with sym(m) == 0 or w == v adds m to l, any other run
+ *             emits sym(l) symbols of v and becomes (v, l); at the end sym(l) of v are emitted.  The bits are packed MSB-first.
+ *             This is a discriminator and a run-length slicer, not a demodulator: it has no clock recovery, the five built-in
+ *             decoders' filters are not applied, and a burst whose deviation is small against its carrier offset does not slice
+ *             about the wrong centre.  Nothing of it has been measured on real recordings. */
+typedef struct {            /* 40 bytes */
+	uint32_t stream;        /* these five: copied from the table entry */
+	uint32_t flags;
+	int64_t  start_sample;
+	uint32_t n_samples;
+	int32_t  thresh;
+	uint64_t bit_offset;    /* the entry's pool_offset: t[k] is bit bit_offset + k of the bitmap */
+	int32_t  last_over;     /* as tfrec_amd_envelope's */
+	uint32_t n_ones;        /* the number of k with t[k] = 1 */
+} tfrec_amd_track;
+/* Turn the track on: after tfrec_amd_enable_capture, before the first submit; smooth = L.  Device memory, counted in
+ * tfrec_amd_get_memory: per FIFO set max_runs * 40 bytes, ceil(max_samples / 32) words and n_streams centre indices; per stream the
+ * carried 16 pairs and prior (68 bytes); n_streams * 4 page-locked bytes per FIFO set.  Errors: smooth outside 1 .. 16, no recorder
+ * or a second call: TFREC_AMD_E_INVAL; after the first submit or a poisoned context: TFREC_AMD_E_STATE; TFREC_AMD_E_NOMEM as
+ * elsewhere; a call that fails leaves the context exactly as it was.  A context on which it was never called holds and launches
+ * what it did.  Independent of the meter, the envelope and the clock: any subset.  Valid on every kind of context and in every
+ * mode, as the recorder is, tfrec_amd_submit_runs included.  Its three kernels run on the recorder's low-priority stream behind
+ * the others'. */
+int tfrec_amd_enable_burst_track(tfrec_amd_ctx *ctx, int32_t smooth);
+/* The centre of streams[i] becomes hz[i], from the next submit on (tfrec_amd_configure_streams' argument rules: n >= 0, both arrays
+ * non-NULL when n > 0, every stream checked before anything is set).  |hz| > 192000, a stream out of range, or a context without
+ * the track: TFREC_AMD_E_INVAL and nothing is set; a poisoned context: TFREC_AMD_E_STATE. */
+int tfrec_amd_set_burst_track_centre(tfrec_amd_ctx *ctx, const int32_t *streams, const int32_t *hz, int n);
+/* out[i] = the record of entry i of the table tfrec_amd_read_captures returns for the same submit, words = the bitmap.  The records
+ * follow tfrec_amd_read_bursts' conventions (the OLDEST undrained submit, read BEFORE the drain that pops it; reading pops nothing;
+ * out may be NULL with cap_runs 0; delivered for every entry below min(n_runs, max_runs)), the words tfrec_amd_read_captures' for the
+ * pool: *n_words = ceil(delivered pairs / 32), the pairs being the submit's, or on an overflow those of the prefix of whole runs
+ * the capture delivers; words may be NULL with cap_words 0, then none are copied.  More runs than max_runs or more pairs than
+ * max_samples: TFREC_AMD_E_OVERFLOW with those prefixes delivered.  Errors: not enabled, NULL ctx / n_runs / n_words / out (with
+ * cap_runs > 0) / words (with cap_words > 0), room too small (nothing written, the counts set): TFREC_AMD_E_INVAL; nothing undrained
+ * or poisoned: TFREC_AMD_E_STATE. */
+int tfrec_amd_read_burst_tracks(tfrec_amd_ctx *ctx, tfrec_amd_track *out, size_t cap_runs, uint32_t *n_runs, uint32_t *words,
+				size_t cap_words, uint64_t *n_words);
+
 /* Power spectrum of the input rows (tfrec_amd_enable_spectrum): where in a recording there is energy, and where the
  * short bursts are that an average hides -- before a receiver is placed.  It belongs to an input ROW of a submit, not to a stream: it
  * is taken on x, the int16 value every format maps a stored component to (tfrec_amd_create_format; -8192 <= x <= 8191), at the

@@ -19,6 +19,7 @@ from .clock import CLOCK_DTYPE  # tfrec_amd_clock
 from .envelope import ENVELOPE_DTYPE  # tfrec_amd_envelope
 from .levels import LEVEL_DTYPE  # tfrec_amd_level
 from .occupancy import OCC_DTYPE  # tfrec_amd_occupancy
+from .track import TRACK_DTYPE  # tfrec_amd_track
 
 BLOCK_BYTES = 65536
 BLOCK_DEC = 8192
@@ -115,6 +116,7 @@ EXPORTS = (
     "tfrec_amd_enable_burst_meter", "tfrec_amd_read_bursts", "tfrec_amd_stream_state_bytes", "tfrec_amd_save_streams",
     "tfrec_amd_load_streams", "tfrec_amd_enable_burst_envelope", "tfrec_amd_read_burst_envelopes",
     "tfrec_amd_enable_burst_clock", "tfrec_amd_read_burst_clocks",
+    "tfrec_amd_enable_burst_track", "tfrec_amd_set_burst_track_centre", "tfrec_amd_read_burst_tracks",
 )
 
 _libs = {}
@@ -218,6 +220,10 @@ def load_library(build: bool = True, experiments: bool = False, short_segments: 
     L.tfrec_amd_read_burst_envelopes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
     L.tfrec_amd_enable_burst_clock.argtypes = [C.c_void_p]
     L.tfrec_amd_read_burst_clocks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+    L.tfrec_amd_enable_burst_track.argtypes = [C.c_void_p, C.c_int32]
+    L.tfrec_amd_set_burst_track_centre.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.tfrec_amd_read_burst_tracks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
+                                              C.POINTER(C.c_uint64)]
     L.tfrec_amd_stream_state_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
     L.tfrec_amd_save_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
     L.tfrec_amd_load_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
@@ -687,6 +693,47 @@ class Receiver:
         out = np.zeros(min(nr.value, getattr(self, "_capture", (0, 0))[0]), dtype=CLOCK_DTYPE)
         _check(self.L, self.L.tfrec_amd_read_burst_clocks(self.h, out.ctypes.data, len(out), C.byref(nr)), ok=ok)
         return out
+
+    def enable_burst_track(self, smooth: int):
+        """Turn the burst track on (tfrec_amd_enable_burst_track; after enable_capture, before the first submit; with or without
+        the meter, the envelope and the clock): a bit per captured sample, the sign of a discriminator about the stream's centre
+        smoothed over `smooth` (1 .. 16) products.  read_burst_tracks returns the records and the bitmap."""
+        if not -2 ** 31 <= int(smooth) < 2 ** 31:  # (refused before ctypes could wrap a value into range)
+            raise TfrecAmdError(E_INVAL, "smooth outside its type")
+        _check(self.L, self.L.tfrec_amd_enable_burst_track(self.h, int(smooth)))
+
+    def set_burst_track_centre(self, streams, hz):
+        """The listed streams' centres in Hz (tfrec_amd_set_burst_track_centre): one value for all of them or one per listed
+        stream, |hz| <= 192000, in force from the next submit on.  Not a restart."""
+        idx = [int(s) for s in streams]
+        if any(s < 0 or s >= self.n_streams for s in idx):  # (refused before int32 could wrap an index into range)
+            raise TfrecAmdError(E_INVAL, "stream index outside [0, %d)" % self.n_streams)
+        v = [int(hz)] * len(idx) if np.ndim(hz) == 0 else [int(x) for x in hz]
+        if len(v) != len(idx):
+            raise ValueError("%d values for %d streams" % (len(v), len(idx)))
+        if any(abs(x) >= 2 ** 31 for x in v):
+            raise TfrecAmdError(E_INVAL, "centre outside its type")
+        a, b = np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(v, dtype=np.int32)
+        _check(self.L, self.L.tfrec_amd_set_burst_track_centre(self.h, a.ctypes.data if len(a) else None,
+                                                               b.ctypes.data if len(a) else None, len(a)))
+
+    def read_burst_tracks(self, allow_overflow: bool = False):
+        """The track of the OLDEST undrained submit (tfrec_amd_read_burst_tracks; call it before the drain that pops that submit)
+        -> (a TRACK_DTYPE array, one record per entry of that submit's run table; the bitmap's uint32 words): track.bits_of(rec,
+        words) is a record's track.  An overflowed table or pool (E_OVERFLOW) raises unless allow_overflow; then the records below
+        max_runs and the words of the pairs read_captures delivers are returned.  track_total holds the submit's true run count."""
+        ok = (E_OK, E_OVERFLOW) if allow_overflow else (E_OK,)
+        nr, nw = C.c_uint32(0), C.c_uint64(0)
+        rc = self.L.tfrec_amd_read_burst_tracks(self.h, None, 0, C.byref(nr), None, 0, C.byref(nw))  # the counts (no room: E_INVAL)
+        self.track_total = int(nr.value)
+        if rc != E_INVAL or nr.value == 0:
+            _check(self.L, rc, ok=ok)
+            return np.zeros(0, dtype=TRACK_DTYPE), np.zeros(0, dtype=np.uint32)
+        out = np.zeros(min(nr.value, getattr(self, "_capture", (0, 0))[0]), dtype=TRACK_DTYPE)
+        words = np.zeros(int(nw.value), dtype=np.uint32)
+        _check(self.L, self.L.tfrec_amd_read_burst_tracks(self.h, out.ctypes.data, len(out), C.byref(nr),
+                                                          words.ctypes.data if len(words) else None, len(words), C.byref(nw)), ok=ok)
+        return out, words
 
     def enable_runs_input(self, max_runs: int, max_samples: int):
         """Turn sparse submits on (tfrec_amd_enable_runs_input; decimated receivers, before the first submit): a submit_runs may

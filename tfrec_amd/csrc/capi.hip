@@ -29,6 +29,7 @@ using namespace tfrec;
 #include "capi_burst.h"    // the burst meter's enable and read
 #include "capi_envelope.h" // the burst envelope's enable and read
 #include "capi_clock.h"    // the burst clock's enable and read
+#include "capi_track.h"    // the burst track's enable, centres and read
 #include "capi_state.h"    // a stream's state blob: its header, the inventory table, save and load
 
 extern "C" {

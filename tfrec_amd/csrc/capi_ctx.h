@@ -103,6 +103,19 @@ struct BurstClock {
 	bool on = false;
 	tfrec_amd_clock *d_recs[kSets] = {};
 };
+// tfrec_amd_enable_burst_track: L; every stream's centre index as the next submit uses it; per set the record of
+// every run of the set's table, the bitmap (ceil(max_samples / 32) words) and the submit's centre indices with their page-locked
+// source; per stream the carried last 16 pairs and chain position (track_carry_kernel)
+struct BurstTrack {
+	bool on = false;
+	int smooth = 0;
+	size_t n_words = 0;
+	std::vector<int32_t> idx;
+	tfrec_amd_track *d_recs[kSets] = {};
+	uint32_t *d_words[kSets] = {};
+	int32_t *d_idx[kSets] = {}, *h_idx[kSets] = {};
+	uint32_t *d_carry = nullptr, *d_prior = nullptr;
+};
 // tfrec_amd_create_decimated (PreStage::kChannel): the carried last pair of every stream
 struct DecIn {
 	uint32_t *d_last = nullptr;
@@ -305,6 +318,7 @@ struct tfrec_amd_ctx {
 	BurstMeter burst;
 	BurstEnvelope env;
 	BurstClock clk;
+	BurstTrack trk;
 	DecIn decin;
 	RunsIn runs_in;
 	SpectrumOut spec;

@@ -269,6 +269,19 @@ static int launch_decin_front(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, si
 	return TFREC_AMD_OK;
 }
 
+// The burst track on the recorder's lane: the centre indices the submit runs with, staged like stage_tune's
+// (h_idx[set] is free: the set's previous submit, whose copy read it, has been drained), then its three kernels
+static int launch_track(tfrec_amd_ctx *c, int set, const FrontOut &out, const CaptureBufs &b)
+{
+	BurstTrack &o = c->trk;
+	std::copy(o.idx.begin(), o.idx.end(), o.h_idx[set]);
+	HIPCHK(hipMemcpyAsync(o.d_idx[set], o.h_idx[set], o.idx.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->cap.lane.st));
+	const TrackBufs k = { .recs = o.d_recs[set], .words = o.d_words[set], .centre = o.d_idx[set], .carry = o.d_carry, .prior = o.d_prior,
+			      .smooth = o.smooth };
+	HIPCHK(launch_burst_track(c->cap.lane.st, out, b, k));
+	return TFREC_AMD_OK;
+}
+
 // input_on_fs: the input was produced on the front-end stream itself (staged host input): no event needed
 // runs: a sparse submit (tfrec_amd_submit_runs, which checked and staged everything on the front-end stream): there are no rows
 static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int n_blocks, void *hip_stream, bool input_on_fs,
@@ -383,6 +396,8 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 			HIPCHK(launch_burst_envelope(c->cap.lane.st, out, b, c->env.d_recs[set]));
 		if (c->clk.on)  // the burst clock: behind the envelope, on the table, the working set and the decimated samples
 			HIPCHK(launch_burst_clock(c->cap.lane.st, out, b, c->clk.d_recs[set]));
+		if (c->trk.on)  // the burst track: behind the clock, on the table, the working set, the samples, the final mask and its own carry
+			TRY(launch_track(c, set, out, b));
 		HIPCHK(lane_written(c->cap.lane, set));
 	}
 	if (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) {

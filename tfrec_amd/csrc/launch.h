@@ -37,6 +37,15 @@ struct CaptureBufs {
 	uint32_t max_runs;
 	unsigned long long max_samples;
 };
+// The burst track's buffers (track.h): the set's records, bitmap and centre indices, the carried 16 pairs and chain position of every
+// stream, and L
+struct TrackBufs {
+	tfrec_amd_track *recs;
+	uint32_t *words;
+	const int32_t *centre;
+	uint32_t *carry, *prior;
+	int smooth;
+};
 // The spectrum of rows 0 .. n_rows - 1 of a submit of n_in complex samples per row, and the set's records: [rows][max_records][n_bins]
 // sums and peaks, [rows][max_records] frame counts.  launch_occupancy reads what launch_spectrum has just queued on the stream.
 struct SpectrumBufs {
@@ -78,6 +87,7 @@ hipError_t launch_capture_pre(hipStream_t st, const FrontOut &o, long long sampl
 hipError_t launch_burst_meter(hipStream_t st, const FrontOut &o, const CaptureBufs &b, tfrec_amd_burst *out);
 hipError_t launch_burst_envelope(hipStream_t st, const FrontOut &o, const CaptureBufs &b, tfrec_amd_envelope *out);
 hipError_t launch_burst_clock(hipStream_t st, const FrontOut &o, const CaptureBufs &b, tfrec_amd_clock *out);
+hipError_t launch_burst_track(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);
 hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, const SpectrumBufs &b);
 hipError_t launch_occupancy(hipStream_t st, const SpectrumBufs &b, uint32_t ratio, uint32_t rel, tfrec_amd_occupancy *recs, uint32_t *bits);
 // ... and the parity probes

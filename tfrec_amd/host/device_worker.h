@@ -53,6 +53,7 @@ private:
 	int read_bursts(size_t k, batch_result &b);
 	int read_envelopes(size_t k, batch_result &b);
 	int read_clocks(size_t k, batch_result &b);
+	int read_tracks(size_t k, batch_result &b);
 	typedef int (*estimate_reader)(tfrec_amd_ctx *, int32_t, int16_t *, size_t, int *);
 	int read_last_estimate(size_t k, estimate_reader reader, std::vector<int> &files, std::vector<int16_t> &last);
 	int read_dc(size_t k, batch_result &b) { return read_last_estimate(k, tfrec_amd_read_dc, b.dc_file, b.dc_last); }  // -z -D
@@ -243,9 +244,9 @@ inline int device_worker::open_context()
 		r = tfrec_amd_map_streams(ctx, all.data(), in_row.data(), (int)n);
 	}
 	if (!r && job.recorder()) {  // -S, sized so that no submit overflows: every sample, and a stream's runs are >= 356 samples long but two
-		call = "tfrec_amd_enable_capture";  // (-M, -Q or -C without -S: the table alone, a pool of one pair)
+		call = "tfrec_amd_enable_capture";  // (-M, -Q or -C without -S: the table alone, a pool of one pair; -G: the bitmap has the pool's size)
 		r = tfrec_amd_enable_capture(ctx, (uint32_t)(n * ((size_t)bps * TFREC_AMD_BLOCK_DEC / 356 + 3)),
-					     job.capture ? (uint64_t)n * (uint64_t)bps * TFREC_AMD_BLOCK_DEC : 1);
+					     job.capture || job.tracking() ? (uint64_t)n * (uint64_t)bps * TFREC_AMD_BLOCK_DEC : 1);
 	}
 	if (!r && job.capture) {  // ... and the pair ahead of every run
 		call = "tfrec_amd_enable_capture_pre";
@@ -262,6 +263,17 @@ inline int device_worker::open_context()
 	if (!r && job.clocking()) {  // -C: the clock on the recorder's table
 		call = "tfrec_amd_enable_burst_clock";
 		r = tfrec_amd_enable_burst_clock(ctx);
+	}
+	if (!r && job.tracking()) {  // -G: the track on the recorder's table, every stream about the one centre
+		call = "tfrec_amd_enable_burst_track";
+		r = tfrec_amd_enable_burst_track(ctx, job.track_smooth());
+		if (!r && job.track_centre) {
+			std::vector<int32_t> all(n), hz(n, (int32_t)job.track_centre);
+			for (size_t s = 0; s < n; s++)
+				all[s] = (int32_t)s;
+			call = "tfrec_amd_set_burst_track_centre";
+			r = tfrec_amd_set_burst_track_centre(ctx, all.data(), hz.data(), (int)n);
+		}
 	}
 	if (!r && job.replay) {  // -R, sized so that every submit fits: its files' runs (a cut adds one per stream), every sample at most
 		uint64_t runs = 0, pairs = 0;
@@ -624,6 +636,45 @@ inline int device_worker::read_clocks(size_t k, batch_result &b)
 	return 0;
 }
 
+// -G: the batch's track records, each with its bits out of the batch's bitmap.  stream -> file, as for the events; a record that
+// begins behind its file's end is dropped, one that reaches over it is cut there and is OPEN (job.h: track_take)
+inline int device_worker::read_tracks(size_t k, batch_result &b)
+{
+	uint32_t nr = 0;
+	uint64_t nw = 0;
+	std::vector<tfrec_amd_track> recs;
+	std::vector<uint32_t> words;
+	int r = tfrec_amd_read_burst_tracks(ctx, NULL, 0, &nr, NULL, 0, &nw);  // (the counts: E_INVAL for want of room)
+	if (r == TFREC_AMD_E_INVAL && nr) {
+		recs.resize(nr);
+		words.resize((size_t)nw + 1);
+		r = tfrec_amd_read_burst_tracks(ctx, recs.data(), recs.size(), &nr, words.data(), words.size(), &nw);
+	}
+	if (r == TFREC_AMD_E_OVERFLOW) {  // (cannot happen: the table and the pool are sized for the worst case)
+		fprintf(stderr, "tfrec_amd: device %d batch %zu: more runs or pairs than the recorder holds, the track is incomplete\n", device, k);
+		return r;
+	}
+	if (r)
+		return r;
+	const std::vector<int> &file = plan[k].file;
+	for (size_t q = 0; q < recs.size(); q++) {
+		tfrec_amd_track x = recs[q];
+		if (x.stream >= file.size() || file[x.stream] < 0)
+			continue;
+		const long long end = (long long)file_blocks[file[x.stream]] * TFREC_AMD_BLOCK_DEC;
+		if (x.start_sample >= end)
+			continue;
+		uint32_t n = x.n_samples;
+		if (x.start_sample + (long long)n > end) {
+			n = (uint32_t)(end - x.start_sample);
+			x.flags |= TFREC_AMD_RUN_OPEN;
+		}
+		x.stream = (uint32_t)file[x.stream];
+		b.tracks.push_back(track_take(x, words.data(), n));
+	}
+	return 0;
+}
+
 // -z -D, -Z -D: the last estimate of every file's row -- d, or (t, g) -- by the stage's reader
 inline int device_worker::read_last_estimate(size_t k, estimate_reader reader, std::vector<int> &files, std::vector<int16_t> &last)
 {
@@ -658,6 +709,8 @@ inline int device_worker::collect(size_t k, batch_result &b)
 		r = read_envelopes(k, b);
 	if (!r && job.clocking())
 		r = read_clocks(k, b);
+	if (!r && job.tracking())
+		r = read_tracks(k, b);
 	if (!r && job.occupancy()) {  // -A: the detector's records in place of the spectrum's, 16 + N / 8 bytes each
 		int nr = 0;
 		r = tfrec_amd_read_occupancy(ctx, 0, NULL, NULL, 0, &nr);  // (the count: E_INVAL for want of room)

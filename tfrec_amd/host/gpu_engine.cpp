@@ -429,6 +429,9 @@ int gpu_engine::run()
 	clock_merger clocks;
 	std::vector<tfrec_amd_clock> keyed;
 	clocks.begin(n);
+	track_merger tracks;
+	std::vector<track_piece> said;
+	tracks.begin(n);
 	if (job.spectrum)
 		spec.begin(job);
 	if (job.occupancy())
@@ -492,6 +495,12 @@ int gpu_engine::run()
 					else
 						printf("%s\n", clock_line(files[x.stream], x).c_str());
 				}
+			}
+			if (job.tracking()) {  // -G: likewise, behind -C's lines of the batch
+				said.clear();
+				tracks.take(b, workers[d].plan[k], file_blocks, said);
+				for (const track_piece &x : said)
+					printf("%s\n", track_line(files[x.stream], x, job.track_rate).c_str());
 			}
 			if (job.occupancy()) {  // no replay: the channel list is the product
 				const unsigned long long first = occ.records;

@@ -214,6 +214,19 @@ public:
 	// the earliest among equals.  Under -A it is the scan's, not pass 1's.  Neither the band, the segment length nor the usefulness
 	// of quality_c has been measured on real recordings.
 	void set_clock() { job.clock = true; }
+	// -G: the burst track (tfrec_amd_enable_burst_track), with or without -M, -Q and -C.  Every context enables the
+	// recorder with a pool for every sample (the bitmap has the pool's size) and the track on it, L = half a symbol of `rate` held
+	// within 1 .. 16, every stream about centre_hz; run() merges the records' chains and their bits across the batches of a file
+	// (job.h: track_merger; a chain still open at the file's end is flushed there, OPEN; at most the first 2^20 samples of a chain
+	// are kept) and prints, as each burst ends,
+	//   bits <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->
+	// (job.h: track_slice, track_line: the run-length slice at `rate` of the first burst_samples = last_over + 1 samples, MSB-first;
+	// "+": the chain is longer than what is kept; "-": no symbol).  Nothing of it has been measured on real recordings.
+	void set_track(long rate, long centre_hz)
+	{
+		job.track_rate = rate;
+		job.track_centre = centre_hz;
+	}
 	// -k: keep.  A file is processed in whole pieces only and nothing is padded; before the first batch behind a
 	// file's last one is submitted -- and at the end of the job -- its stream is saved (tfrec_amd_save_streams) to
 	// <prefix>.<file index>.state, and at the end of a run without an error the bytes that did not fill a piece are written to

@@ -97,6 +97,8 @@ struct job_settings {
 	bool meter = false;            // set_meter
 	bool envelope = false;         // set_envelope
 	bool clock = false;            // set_clock
+	long track_rate = 0;           // set_track (0: none): the rate in bit/s, 1000 .. 96000
+	long track_centre = 0;         // ... and every stream's centre in Hz
 	const std::vector<replay_file> *replay = NULL;  // set_replay (NULL: the files are dumps)
 	std::string keep_prefix;       // set_keep ("": none)
 	std::string cont_prefix;       // set_continue ("": none)
@@ -108,7 +110,10 @@ struct job_settings {
 
 	bool resampled() const { return rate_p != 1 || rate_q != 1; }
 	bool occupancy() const { return spectrum && occ_ratio; }  // -A, pass 1
-	bool recorder() const { return capture || metering() || enveloping() || clocking(); }  // the contexts enable the recorder: for -S, or as the meter's, the envelope's or the clock's table
+	bool recorder() const { return capture || metering() || enveloping() || clocking() || tracking(); }  // the contexts enable the recorder: for -S, or as the meter's, the envelope's, the clock's or the track's table
+	bool tracking() const { return track_rate != 0; }  // -G (never with -s or -A)
+	// -G's L: half a symbol, (384000 + rate) / (2 rate) held within 1 .. 16
+	int track_smooth() const { return (int)std::max(1L, std::min(16L, (384000 + track_rate) / (2 * track_rate))); }
 	bool metering() const { return meter && !occupancy(); }  // -M (under -A: in the scan, not in pass 1)
 	bool enveloping() const { return envelope && !occupancy(); }  // -Q (likewise)
 	bool clocking() const { return clock && !occupancy(); }  // -C (likewise)
@@ -353,7 +358,18 @@ inline std::vector<occ_channel> occupancy_channels(const std::vector<unsigned lo
 // -M: the burst records that belong to a file (stream = its index in the job), n_samples cut at the file's end
 // -Q: the envelope records likewise; one that is cut at the file's end is OPEN (the input's end cut its tail)
 // -C: the clock records likewise
+// -G: the track records likewise, each with its bits out of the batch's bitmap (track_piece; its functions are further down)
+constexpr uint64_t kTrackKeep = 1ull << 20;  // the samples of a chain's track that are kept
+
+// A record with its track: bit k of the track is bit k & 31 of bits[k >> 5], for k < min(n_samples, 2^20)
+struct track_piece : tfrec_amd_track {
+	std::vector<uint32_t> bits;
+	uint64_t kept() const { return std::min<uint64_t>(n_samples, kTrackKeep); }
+	bool bit(uint64_t k) const { return (bits[k >> 5] >> (k & 31)) & 1u; }
+};
+
 struct batch_result {
+	std::vector<track_piece> tracks;
 	std::vector<tfrec_amd_burst> bursts;
 	std::vector<tfrec_amd_envelope> envelopes;
 	std::vector<tfrec_amd_clock> clocks;
@@ -603,7 +619,108 @@ inline std::string clock_line(const std::string &file, const tfrec_amd_clock &r)
 	return s + buf;
 }
 
+// ---- -G: the burst track's records and bits (include/tfrec_amd.h: tfrec_amd_track, whose text is normative; tfrec_amd/track.py
+// restates merge, the slicer and the line)
+
+// n bits of src from bit src_off on -> dst, from its bit dst_len on, as far as the kept 2^20 reach
+inline void track_append(std::vector<uint32_t> &dst, uint64_t dst_len, const uint32_t *src, uint64_t src_off, uint64_t n)
+{
+	if (dst_len >= kTrackKeep)
+		return;
+	n = std::min(n, kTrackKeep - dst_len);
+	dst.resize((size_t)((dst_len + n + 31) >> 5), 0u);
+	for (uint64_t k = 0; k < n; k++)
+		if ((src[(src_off + k) >> 5] >> ((src_off + k) & 31)) & 1u)
+			dst[(dst_len + k) >> 5] |= 1u << ((dst_len + k) & 31);
+}
+
+// a device record and the submit's bitmap -> the piece, n samples of it (n <= the record's: the file's end may cut it): its bits
+// from bit_offset on, n_ones counted again on what is kept of a cut piece
+inline track_piece track_take(const tfrec_amd_track &r, const uint32_t *words, uint32_t n)
+{
+	track_piece p;
+	static_cast<tfrec_amd_track &>(p) = r;
+	const bool cut = n < r.n_samples;
+	p.n_samples = n;
+	track_append(p.bits, 0, words, r.bit_offset, n);
+	if (cut) {
+		p.n_ones = 0;
+		for (uint64_t k = 0; k < p.kept(); k++)
+			p.n_ones += p.bit(k);
+		if (p.last_over >= (int32_t)n)  // (the padding behind a file's end is silence: not over)
+			p.last_over = (int32_t)n - 1;
+	}
+	return p;
+}
+
+// piece p, which CONTINUES the chain c, merged into it (the header's Cutting): the tracks concatenated, n_samples and n_ones added,
+// last_over by the envelope's rule
+inline void track_add(track_piece &c, const track_piece &p)
+{
+	if (!p.bits.empty())
+		track_append(c.bits, c.kept(), p.bits.data(), 0, p.kept());
+	if (p.last_over >= 0)
+		c.last_over = (int32_t)((long long)c.n_samples + p.last_over);
+	c.n_samples += p.n_samples;
+	c.n_ones += p.n_ones;
+	c.flags = (c.flags & TFREC_AMD_RUN_CONTINUES) | (p.flags & TFREC_AMD_RUN_OPEN);
+}
+
+// sym(l) = floor((2 l R + 384000) / 768000) (l <= 2^20, R <= 96000: below 2^39)
+inline uint64_t track_sym(uint64_t l, long rate) { return (2 * l * (uint64_t)rate + 384000) / 768000; }
+
+// The header's Slicing on the first min(last_over + 1, 2^20) samples of a merged track -> the symbols, one per byte
+inline std::vector<uint8_t> track_slice(const track_piece &c, long rate)
+{
+	std::vector<uint8_t> out;
+	const uint64_t n = c.last_over < 0 ? 0 : std::min<uint64_t>((uint64_t)c.last_over + 1, c.kept());
+	bool have = false, v = false;
+	uint64_t l = 0;
+	for (uint64_t k = 0; k < n;) {
+		const bool w = c.bit(k);
+		uint64_t m = 1;
+		while (k + m < n && c.bit(k + m) == w)
+			m++;
+		k += m;
+		if (!have) {
+			if (track_sym(m, rate)) {
+				have = true;
+				v = w;
+				l = m;
+			}
+		} else if (track_sym(m, rate) == 0 || w == v) {
+			l += m;
+		} else {
+			out.insert(out.end(), (size_t)track_sym(l, rate), (uint8_t)v);
+			v = w;
+			l = m;
+		}
+	}
+	if (have)
+		out.insert(out.end(), (size_t)track_sym(l, rate), (uint8_t)v);
+	return out;
+}
+
+// bits <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->: MSB-first, the last nibble zero-padded; + when the
+// chain is longer than the 2^20 samples kept
+inline std::string track_line(const std::string &file, const track_piece &c, long rate)
+{
+	const std::vector<uint8_t> sy = track_slice(c, rate);
+	std::string s = "bits " + file + " " + std::to_string((long long)c.start_sample) + " " + std::to_string(c.n_samples) + " " +
+			std::to_string((long long)c.last_over + 1) + " " + std::to_string(sy.size()) + (c.n_samples > kTrackKeep ? "+" : "") + " ";
+	if (sy.empty())
+		return s + "-";
+	for (size_t i = 0; i < sy.size(); i += 4) {
+		int nib = 0;
+		for (size_t j = 0; j < 4; j++)
+			nib = 2 * nib + (i + j < sy.size() ? sy[i + j] : 0);
+		s += "0123456789abcdef"[nib];
+	}
+	return s;
+}
+
 inline void chain_add(tfrec_amd_burst &c, const tfrec_amd_burst &p) { burst_add(c, p); }
+inline void chain_add(track_piece &c, const track_piece &p) { track_add(c, p); }
 inline void chain_add(tfrec_amd_clock &c, const tfrec_amd_clock &p) { clock_add(c, p); }
 inline void chain_add(tfrec_amd_envelope &c, const tfrec_amd_envelope &p) { envelope_add(c, p); }
 
@@ -667,6 +784,13 @@ struct clock_merger : chain_merger<tfrec_amd_clock> {  // -C
 	void take(const batch_result &b, const batch_plan &p, const std::vector<size_t> &file_blocks, std::vector<tfrec_amd_clock> &out)
 	{
 		chain_merger<tfrec_amd_clock>::take(b.clocks, p, file_blocks, out);
+	}
+};
+
+struct track_merger : chain_merger<track_piece> {  // -G
+	void take(const batch_result &b, const batch_plan &p, const std::vector<size_t> &file_blocks, std::vector<track_piece> &out)
+	{
+		chain_merger<track_piece>::take(b.tracks, p, file_blocks, out);
 	}
 };
 

@@ -101,6 +101,17 @@
 // channel table ends in burst_clock=<Hz|->, the clock of the channel's window with the largest quality.  Works with -M, -Q, -R, -S,
 // -n, -d and every input option; not with -X, -k or -K.  No quality threshold is built in: noise reads a quality of a few units,
 // a clean telegram 25 or more on synthetic scenes; none of it has been measured on real recordings.
+// -G rate[,centre_hz] (not in the reference): the burst track (tfrec_amd_enable_burst_track): for every trigger window
+// of every file, whether or not anything decoded in it, what the burst said when it is read at `rate` bit/s (1000 .. 96000: -C's
+// reading) about centre_hz (|centre_hz| <= 192000, default 0: -M's reading).  The contexts enable the recorder with a pool for every
+// sample and the track, smoothed over half a symbol (at most 16 samples); the pieces of a window that is cut by a submit boundary are
+// merged, and stdout gets, as each window ends (a window still open at its file's end: there),
+//   bits <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->
+// burst_samples: -Q's; the bits: the run-length slice of the track's first burst_samples samples, MSB-first, 1 above the centre, the
+// last nibble zero-padded ("-": none; "+": the window is longer than the 2^20 samples that are kept).  It is a discriminator and a
+// slicer, not a demodulator: no clock recovery, no matched filter; the golden TFA_1 and WHB scenes do not slice with it.  Works with
+// -M, -Q, -C, -S, -R, -n, -d and every input option; not with -X, -k, -K, -s or -A.  Nothing of it has been measured on real
+// recordings.
 // -P bins[,frames_per_record] (not in the reference): the power spectrum of ONE recording, beside its decoding: an
 // exact integer DFT of bins = 64, 128, 256, 512 or 1024 bins over the raw input -- at 1.536 MS/s, or given with -x, or with -r / -F --,
 // per record of frames_per_record frames (1 .. 16384; default: the frames one block's input holds, at least 1) the sum and the peak
@@ -274,6 +285,7 @@ struct cli {
 	bool meter = false;  // -M
 	bool envelope = false;  // -Q
 	bool clock = false;  // -C
+	long track_rate = 0, track_centre = 0;  // -G (rate 0: not given)
 	const char *keep_prefix = NULL, *cont_prefix = NULL;  // -k, -K
 	bool have_center = false, have_format = false;  // -c, -F given (-R refuses them)
 	std::vector<replay_file> captures;  // -R: one per file index of <prefix>.idx
@@ -307,7 +319,7 @@ struct cli {
 
 static void usage()
 {
-	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
+	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-G rate[,centre_hz]] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
 			"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
 			"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
 			"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
@@ -327,6 +339,10 @@ static void usage()
 			"              <n_segments> <clock_hz|-> <quality|->' per trigger window (quality: the spectral peak over the band's mean; -: no\n"
 			"              whole 1024-sample segment); with -s or -A a column burst_clock= of the channel's best-quality burst instead;\n"
 			"              also with -M, -Q and -R; not with -X, -k or -K\n"
+			"  -G r[,c]    read every burst's bits on the GPU, decoded or not, at r bit/s (1000 .. 96000) about the centre c Hz (default 0): a\n"
+			"              line 'bits <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->' per trigger window, MSB-first,\n"
+			"              1 above the centre (+: longer than the 2^20 samples kept); also with -M, -Q, -C, -S and -R; not with -X, -k, -K,\n"
+			"              -s or -A\n"
 			"  -k prefix   keep: for a recording that arrives in parts.  Every -L file is processed in whole blocks only (nothing is padded), then\n"
 			"              its receiver's state is saved to <prefix>.<file index>.state and the bytes that filled no block to\n"
 			"              <prefix>.<file index>.rest\n"
@@ -409,11 +425,21 @@ bool cli::parse_format(const char *arg)
 int cli::parse(int argc, char **argv)
 {
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCk:K:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCG:k:K:h")) != -1) {
 		switch (c) {
 		case 'M': meter = true; break;
 		case 'Q': envelope = true; break;
 		case 'C': clock = true; break;
+		case 'G': {
+			const char *comma = strchr(optarg, ',');
+			if (!parse_long(std::string(optarg, comma ? (size_t)(comma - optarg) : strlen(optarg)).c_str(), 1000, 96000, track_rate) ||
+			    (comma && !parse_long(comma + 1, -192000, 192000, track_centre))) {
+				fprintf(stderr, "tfrec_gpu: bad -G '%s': want <rate>[,<centre_hz>], the rate within 1000 .. 96000 bit/s, the centre within "
+						"-192000 .. 192000 Hz\n", optarg);
+				return 1;
+			}
+			break;
+		}
 		case 'k':
 		case 'K':
 			(c == 'k' ? keep_prefix : cont_prefix) = optarg;
@@ -550,6 +576,10 @@ int cli::check() const
 			fprintf(stderr, "tfrec_gpu: -k and -K do not carry a burst across runs: not with -C\n");
 			return 2;
 		}
+		if (track_rate) {
+			fprintf(stderr, "tfrec_gpu: -k and -K do not carry a burst across runs: not with -G\n");
+			return 2;
+		}
 		for (size_t i = 0; i < dumps.size(); i++)
 			for (size_t j = 0; j < i; j++)
 				if (dumps[i] == dumps[j]) {
@@ -602,6 +632,10 @@ int cli::check() const
 	}
 	if (clock && hexfile) {
 		fprintf(stderr, "tfrec_gpu: -C measures the bursts of -L files or of a capture (-R): not with -X\n");
+		return 1;
+	}
+	if (track_rate && (hexfile || have_scan || have_auto)) {
+		fprintf(stderr, "tfrec_gpu: -G reads the bursts of -L files or of a capture (-R), a line per burst: not with -X, -s or -A\n");
 		return 1;
 	}
 	if (cap_prefix && hexfile) {
@@ -841,6 +875,8 @@ int cli::run()
 		e.set_envelope();
 	if (clock)
 		e.set_clock();
+	if (track_rate)
+		e.set_track(track_rate, track_centre);
 	if (keep_prefix)
 		e.set_keep(keep_prefix);
 	if (cont_prefix)

@@ -1,0 +1,262 @@
+"""The burst track (tfrec_amd_enable_burst_track, include/tfrec_amd.h: tfrec_amd_track) restated in numpy -- no GPU
+needed.  Written from the header's definition alone; exact integers throughout.
+
+Per captured sample of every run of the recorder's table one bit: the sign of a quadrature discriminator about the stream's
+centre, boxcar-smoothed over L products -- 1 above the centre --, packed where the sample's pair lies in the pool; per run a
+40-byte record.  A run-length slicer turns a merged track and a rate into the burst's bits.  Nothing here has been measured on
+real recordings.
+
+  index_of           the table index r of a centre in Hz;
+  tracks             vectorised, from the definition: one submit's records and bitmap from every stream's decimated samples, its
+                     over bits (or the thresholds that give them), its run table and the state the submit before left;
+  tracks_bruteforce  the same sample by sample, in Python integers;
+  bits_of            a record's track out of the bitmap;  merge: a chain of pieces -> the record and track of the uncut run;
+  chains             the chains of a sequence of submits (burst.chains' walk);
+  slice_bits         a track and a rate -> the symbols;  line: tfrec_gpu -G's output line;
+  device_bytes, pinned_bytes   what tfrec_amd_enable_burst_track adds to tfrec_amd_get_memory.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import burst, envelope, tune
+from .capture import RUN_CONTINUES, RUN_OPEN
+
+AHEAD = 16  # the pairs carried from submit to submit, and the largest L
+CENTRE_MAX = 192000
+KEEP = 1 << 20  # the samples of a chain's track the host keeps
+TRACK_DTYPE = np.dtype([("stream", "<u4"), ("flags", "<u4"), ("start_sample", "<i8"), ("n_samples", "<u4"), ("thresh", "<i4"),
+                        ("bit_offset", "<u8"), ("last_over", "<i4"), ("n_ones", "<u4")])
+assert TRACK_DTYPE.itemsize == 40
+
+
+def index_of(hz: int) -> int:
+    """r = floor((8192 hz + 384000) / 768000) mod 4096 (Python's // is a true floor)."""
+    hz = int(hz)
+    if abs(hz) > CENTRE_MAX:
+        raise ValueError("centre %d Hz outside [-%d, %d]" % (hz, CENTRE_MAX, CENTRE_MAX))
+    return (8192 * hz + 384000) // 768000 % 4096
+
+
+def fresh_state(n_streams: int) -> dict:
+    """What a context carries before its first submit: no pairs, no chain."""
+    return {"carry": np.zeros((n_streams, AHEAD, 2), dtype=np.int16), "prior": np.zeros(n_streams, dtype=np.int64)}
+
+
+def _copied(run):
+    o = np.zeros((), dtype=TRACK_DTYPE)
+    for f in ("stream", "flags", "n_samples", "thresh"):
+        o[f] = run[f]
+    o["start_sample"] = int(run["start_sample"])
+    o["bit_offset"] = int(run["pool_offset"])
+    return o
+
+
+def _window(dec, r, base):
+    s = int(r["stream"])
+    a = int(r["start_sample"]) - (int(base[s]) if base is not None else 0)
+    n = int(r["n_samples"])
+    assert 0 <= a and a + n <= len(burst._pairs(dec[s])) and n >= 1
+    cont = bool(int(r["flags"]) & RUN_CONTINUES)
+    assert not cont or a == 0
+    return s, a, n, cont
+
+
+def _next_state(dec, runs, state, base):
+    """The state behind the submit: every stream's last 16 pairs, and prior = min(16, prior' + n) of the stream's OPEN run."""
+    nxt = {"carry": np.array([burst._pairs(d)[-AHEAD:] for d in dec], dtype=np.int16), "prior": np.zeros(len(dec), dtype=np.int64)}
+    for r in runs:
+        if int(r["flags"]) & RUN_OPEN:
+            s = int(r["stream"])
+            before = int(state["prior"][s]) if int(r["flags"]) & RUN_CONTINUES else 0
+            nxt["prior"][s] = min(AHEAD, before + int(r["n_samples"]))
+    return nxt
+
+
+def _pack(out, tr, max_samples):
+    """The runs' tracks -> the bitmap: t[k] at bit bit_offset + k; a run whose samples do not fit max_samples leaves no bit."""
+    ends = [int(o["bit_offset"]) + int(o["n_samples"]) for o in out]
+    fit = [max_samples is None or e <= max_samples for e in ends]
+    total = max([e for e, f in zip(ends, fit) if f], default=0)
+    flat = np.zeros(((total + 31) // 32) * 32, dtype=np.uint8)
+    for o, t, f in zip(out, tr, fit):
+        if f:
+            flat[int(o["bit_offset"]):int(o["bit_offset"]) + len(t)] = t
+    return np.packbits(flat.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1)
+
+
+def tracks(dec, mask_or_thresh, runs, smooth, centres=None, state=None, base=None, max_samples=None):
+    """One submit.  dec[s]: stream s's decimated samples of the submit (int16 pairs, as tfrec_amd_read_decimated returns them);
+    mask_or_thresh[s]: its over bits or the threshold behind them (envelope.envelopes'); runs: the submit's table (RUN_DTYPE);
+    smooth: L; centres[s]: the stream's centre in Hz (default 0); state: what the submit before returned (default: a fresh
+    context's); base[s]: the start_sample of the submit's first sample of stream s (default 0); max_samples: the pool's size
+    (default: everything fits) -> (a TRACK_DTYPE array, one record per table entry; the bitmap's uint32 words, as many as the
+    pairs that fit need; the state behind the submit)."""
+    L = int(smooth)
+    assert 1 <= L <= AHEAD
+    state = fresh_state(len(dec)) if state is None else state
+    c, s_ = tune.table()
+    out = np.zeros(len(runs), dtype=TRACK_DTYPE)
+    tr = []
+    for e, r in enumerate(runs):
+        s, a, n, cont = _window(dec, r, base)
+        ri = index_of(centres[s]) if centres is not None else 0
+        C, S = int(c[ri]), int(s_[ri])
+        z = np.concatenate([np.asarray(state["carry"][s], dtype=np.int64).reshape(AHEAD, 2), burst._pairs(dec[s]).astype(np.int64)])
+        cf = a - (int(state["prior"][s]) if cont else 0)  # the chain's first sample, submit-relative
+        m = np.arange(a - (AHEAD - 1), a + n)  # every sample a product may be needed of; z's index is m + 16
+        I, Q, Ip, Qp = z[m + AHEAD, 0], z[m + AHEAD, 1], z[m + AHEAD - 1, 0], z[m + AHEAD - 1, 1]
+        v = np.where(m > cf, (Q * Ip - I * Qp) * C - (I * Ip + Q * Qp) * S, 0)  # (|v| < 2^47)
+        cs = np.concatenate([[0], np.cumsum(v)])
+        p = np.arange(n) + AHEAD  # sample a + k is v[k + 15]: the sum of v[k + 16 - L .. k + 15]
+        t = (cs[p] - cs[p - L]) > 0
+        o = _copied(r)
+        over = envelope._over(burst._pairs(dec[s]).astype(np.int64), mask_or_thresh[s])[a:a + n]
+        idx = np.flatnonzero(over)
+        o["last_over"] = int(idx[-1]) if len(idx) else -1
+        o["n_ones"] = int(np.count_nonzero(t))
+        out[e] = o
+        tr.append(t.astype(np.uint8))
+    return out, _pack(out, tr, max_samples), _next_state(dec, runs, state, base)
+
+
+def tracks_bruteforce(dec, mask_or_thresh, runs, smooth, centres=None, state=None, base=None, max_samples=None):
+    """The same, one sample at a time in Python integers, as the header words it: the sum of v[k - i] over i < min(L, k + prior)."""
+    L = int(smooth)
+    state = fresh_state(len(dec)) if state is None else state
+    c, s_ = tune.table()
+    out = np.zeros(len(runs), dtype=TRACK_DTYPE)
+    tr = []
+    for e, r in enumerate(runs):
+        s, a, n, cont = _window(dec, r, base)
+        ri = index_of(centres[s]) if centres is not None else 0
+        C, S = int(c[ri]), int(s_[ri])
+        row = burst._pairs(dec[s]).tolist()
+        ahead = np.asarray(state["carry"][s]).reshape(AHEAD, 2).tolist()
+        prior = int(state["prior"][s]) if cont else 0
+        over = envelope._over(burst._pairs(dec[s]).astype(np.int64), mask_or_thresh[s]).tolist()
+
+        def z(k):  # run-relative; k < 0 only in a CONTINUES run, whose a == 0
+            return row[a + k] if a + k >= 0 else ahead[AHEAD + a + k]
+
+        def v(k):
+            if k == -prior:  # the chain's first sample
+                return 0
+            (i, q), (ip, qp) = z(k), z(k - 1)
+            return (q * ip - i * qp) * C - (i * ip + q * qp) * S
+
+        t, last = [], -1
+        for k in range(n):
+            total = 0
+            for i in range(min(L, k + prior)):
+                total += v(k - i)
+            t.append(1 if total > 0 else 0)
+            if over[a + k]:
+                last = k
+        o = _copied(r)
+        o["last_over"], o["n_ones"] = last, sum(t)
+        out[e] = o
+        tr.append(np.array(t, dtype=np.uint8))
+    return out, _pack(out, tr, max_samples), _next_state(dec, runs, state, base)
+
+
+def bits_of(rec, words):
+    """A record's track out of its submit's bitmap -> uint8 [n_samples]."""
+    b0, n = int(rec["bit_offset"]), int(rec["n_samples"])
+    w = np.asarray(words, dtype="<u4")[b0 // 32:(b0 + n + 31) // 32]
+    return np.unpackbits(w.view(np.uint8), bitorder="little")[b0 % 32:b0 % 32 + n]
+
+
+class Piece:
+    """A record with its track; read like the record (burst.chains looks at stream and flags)."""
+
+    def __init__(self, rec, bits):
+        self.rec, self.bits = rec, np.asarray(bits, dtype=np.uint8)
+
+    def __getitem__(self, f):
+        return self.rec[f]
+
+
+def merge(pieces):
+    """A chain of pieces (in order; piece i + 1 has CONTINUES, piece i OPEN, one stream) -> one Piece, that of the uncut run: the
+    tracks concatenated, n_samples and n_ones added, last_over the last piece's that has one, offset by the samples ahead of it;
+    the first piece's stream, start_sample, thresh, bit_offset and CONTINUES, the last one's OPEN."""
+    pieces = list(pieces)
+    o = pieces[0].rec.copy()
+    for p in pieces[1:]:
+        assert p["stream"] == o["stream"] and int(p["flags"]) & RUN_CONTINUES
+        if int(p["last_over"]) >= 0:
+            o["last_over"] = int(o["n_samples"]) + int(p["last_over"])
+        o["n_samples"] = int(o["n_samples"]) + int(p["n_samples"])
+        o["n_ones"] = int(o["n_ones"]) + int(p["n_ones"])
+    o["flags"] = (int(pieces[0]["flags"]) & RUN_CONTINUES) | (int(pieces[-1]["flags"]) & RUN_OPEN)
+    return Piece(o, np.concatenate([p.bits for p in pieces]))
+
+
+def chains(submits, restarts=None):
+    """submits: one (records, words) per submit, in order -> the merged bursts as Pieces, in burst.chains' order (as they end; a
+    chain still open behind the last submit last, by stream).  restarts: {submit index: streams that restart with it}."""
+    return burst.chains([[Piece(r, bits_of(r, w)) for r in recs] for recs, w in submits], restarts, join=merge)
+
+
+def sym(l: int, rate: int) -> int:
+    return (2 * int(l) * int(rate) + 384000) // 768000
+
+
+def slice_bits(bits, rate: int) -> list:
+    """The header's Slicing: the maximal runs of equal value in order; a run too short for a symbol joins the run ahead of it
+    (ahead of the first kept run it is dropped) -> the symbols, a list of 0 / 1."""
+    b = np.asarray(bits, dtype=np.uint8)
+    out = []
+    if len(b) == 0:
+        return out
+    edges = np.flatnonzero(np.diff(b)) + 1
+    starts = np.concatenate([[0], edges])
+    lens = np.diff(np.concatenate([starts, [len(b)]]))
+    kept = None  # (v, l)
+    for w, m in zip(b[starts].tolist(), lens.tolist()):
+        if kept is None:
+            if sym(m, rate):
+                kept = (w, m)
+        elif sym(m, rate) == 0 or w == kept[0]:
+            kept = (kept[0], kept[1] + m)
+        else:
+            out += [kept[0]] * sym(kept[1], rate)
+            kept = (w, m)
+    if kept is not None:
+        out += [kept[0]] * sym(kept[1], rate)
+    return out
+
+
+def hex_of(symbols) -> str:
+    """MSB-first, the last nibble zero-padded."""
+    s = list(symbols) + [0] * (-len(symbols) % 4)
+    return "".join("%x" % (8 * s[i] + 4 * s[i + 1] + 2 * s[i + 2] + s[i + 3]) for i in range(0, len(s), 4))
+
+
+def line(name: str, piece, rate: int) -> str:
+    """tfrec_gpu -G: bits <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->: the slice of the track's first
+    burst_samples = last_over + 1 samples, of the first 2^20 at most (then the + behind n_bits: n_samples > 2^20)."""
+    rec = piece.rec
+    length = int(rec["last_over"]) + 1
+    symbols = slice_bits(piece.bits[:KEEP][:length], rate)
+    return "bits %s %d %d %d %d%s %s" % (name, int(rec["start_sample"]), int(rec["n_samples"]), length, len(symbols),
+                                         "+" if int(rec["n_samples"]) > KEEP else "", hex_of(symbols) if symbols else "-")
+
+
+def smooth_of(rate: int) -> int:
+    """tfrec_gpu -G's L: half a symbol, (384000 + rate) // (2 rate) held within 1 .. 16."""
+    return max(1, min(AHEAD, (384000 + int(rate)) // (2 * int(rate))))
+
+
+def device_bytes(n_streams: int, max_runs: int, max_samples: int) -> int:
+    """What tfrec_amd_enable_burst_track adds to tfrec_amd_get_memory's device bytes: per FIFO set the records, the bitmap and the
+    centre indices; per stream the carried 16 pairs and prior."""
+    from .api import FIFO_DEPTH
+    return FIFO_DEPTH * (max_runs * TRACK_DTYPE.itemsize + 4 * ((max_samples + 31) // 32) + 4 * n_streams) + n_streams * (4 * AHEAD + 4)
+
+
+def pinned_bytes(n_streams: int) -> int:
+    """... and to its page-locked bytes: the centre indices' source per FIFO set."""
+    from .api import FIFO_DEPTH
+    return FIFO_DEPTH * 4 * n_streams
