@@ -724,7 +724,10 @@ int tfrec_amd_submit_runs(tfrec_amd_ctx *ctx, const tfrec_amd_run *runs, uint32_
  *             products.  The record repeats the table entry's fields, so a caller needs neither the table nor the pool.
  *   Cutting:  a burst is a chain of pieces: piece i + 1 has CONTINUES, piece i OPEN, on the same stream.  Merging a chain adds
  *             n_samples, n_products, the sums, energy and hist and takes the largest pwr_max; the result does not depend on how
- *             the stream was cut into submits.  A restart drops the chain, as it drops the carried trigger.
+ *             the stream was cut into submits.  A restart drops the chain, as it drops the carried trigger.  A chain whose last piece
+ *             is OPEN and which the next submit does not continue (no CONTINUES piece of its stream) ended with that submit's last
+ *             sample: the merged record is complete and its OPEN is cleared, as the uncut run's is.  This holds for every record
+ *             that is merged by chains (tfrec_amd_envelope, tfrec_amd_clock, tfrec_amd_track).
  *   Summary (what a caller makes of a record; normative for tfrec_gpu -M and burst.py):  P = n_products, thr = (P + 15) / 16; bin j is
  *             occupied iff P > 0 and hist[j] >= thr.  None occupied: no carrier (noise spreads over the bins).  Otherwise lo, hi = the
  *             smallest and largest signed index b of an occupied bin, centre_hz = 3000 (lo + hi), deviation_hz = 3000 (hi - lo).

@@ -187,9 +187,16 @@ def merge(pieces):
 def chains(submits, restarts=None, join=None):
     """submits: one BURST_DTYPE array per submit, in order -> the merged bursts, in the order in which they end (per submit: table
     order), a chain still open behind the last submit last (by stream).  restarts: {submit index: streams that restart with it}:
-    their open chains end there.  join: what merges a chain's pieces (default: merge; envelope.py passes its own)."""
+    their open chains end there.  join: what merges a chain's pieces (default: merge; envelope.py passes its own).
+    A chain whose last piece is OPEN and which the next submit does not continue ended with that piece's last sample, the submit's
+    last: the trigger's hold ran out exactly there.  Its record is complete, and OPEN is cleared, as in the uncut run's record."""
     join = join or merge
     open_, out = {}, []
+
+    def ended(o):  # (a restart's and the last submit's chains keep OPEN: what lies behind them is not known)
+        o["flags"] = int(o["flags"]) & ~RUN_OPEN
+        return o
+
     for k, recs in enumerate(submits):
         for s in sorted((restarts or {}).get(k, ())):
             if s in open_:
@@ -201,14 +208,14 @@ def chains(submits, restarts=None, join=None):
             if fl & RUN_CONTINUES and s in open_:
                 open_[s].append(r)
             else:
-                if s in open_:  # (cannot happen without a restart: an open piece is continued)
-                    out.append(join(open_.pop(s)))
+                if s in open_:  # the chain ended with the submit before; this run began later in this one
+                    out.append(ended(join(open_.pop(s))))
                 open_[s] = [r]
             seen.add(s)
             if not fl & RUN_OPEN:
                 out.append(join(open_.pop(s)))
         for s in sorted(set(open_) - seen):  # open, and nothing of the stream at this submit's first sample: the trigger ended there
-            out.append(join(open_.pop(s)))
+            out.append(ended(join(open_.pop(s))))
     for s in sorted(open_):
         out.append(join(open_[s]))
     return out

@@ -726,7 +726,9 @@ inline void chain_add(tfrec_amd_envelope &c, const tfrec_amd_envelope &p) { enve
 
 // The chains of pieces across a job's batches, per file (a record's stream is its file's index in the job).  A chain ends with a
 // piece that is not OPEN, with a batch that does not continue it, and with its file: a chain still open at a file's end is flushed
-// there.  take() appends the bursts that ended with the batch, in the order in which they ended.
+// there.  A chain that the next batch does not continue ended with its last piece's last sample -- the trigger's hold ran out with
+// the batch --: its record is complete and OPEN is cleared, as in the record of the uncut run.  take() appends the bursts that ended
+// with the batch, in the order in which they ended.
 template <class R> struct chain_merger {
 	std::vector<R> chain;
 	std::vector<char> open, seen;
@@ -745,8 +747,10 @@ template <class R> struct chain_merger {
 			if ((r.flags & TFREC_AMD_RUN_CONTINUES) && open[f]) {
 				chain_add(chain[f], r);
 			} else {
-				if (open[f])
+				if (open[f]) {
+					chain[f].flags &= ~TFREC_AMD_RUN_OPEN;
 					out.push_back(chain[f]);
+				}
 				chain[f] = r;
 				open[f] = 1;
 			}
@@ -761,6 +765,8 @@ template <class R> struct chain_merger {
 				continue;
 			blocks[f] += (unsigned long long)p.nb;
 			if (open[f] && (!seen[f] || blocks[f] >= file_blocks[f])) {
+				if (!seen[f])
+					chain[f].flags &= ~TFREC_AMD_RUN_OPEN;
 				out.push_back(chain[f]);
 				open[f] = 0;
 			}

@@ -176,6 +176,9 @@ class Piece:
     def __getitem__(self, f):
         return self.rec[f]
 
+    def __setitem__(self, f, v):
+        self.rec[f] = v
+
 
 def merge(pieces):
     """A chain of pieces (in order; piece i + 1 has CONTINUES, piece i OPEN, one stream) -> one Piece, that of the uncut run: the
