@@ -971,6 +971,71 @@ int tfrec_amd_set_burst_track_centre(tfrec_amd_ctx *ctx, const int32_t *streams,
 int tfrec_amd_read_burst_tracks(tfrec_amd_ctx *ctx, tfrec_amd_track *out, size_t cap_runs, uint32_t *n_runs, uint32_t *words,
 				size_t cap_words, uint64_t *n_words);
 
+/* Burst sync (tfrec_amd_enable_burst_sync): for every run of the recorder's table WHERE A FRAME BEGINS -- one bit per
+ * captured sample, 1 where the burst track, read at P symbol centres that end at the sample, is a known sync word but for at most E
+ * places.  The symbol timing comes from where the matches lie; a caller reads the payload at symbol centres from there.  It sits on
+ * the burst track and needs it.  There is no reference counterpart: this text is normative, tfrec_amd/sync.py restates it.  Exact
+ * integers only.
+ *   Settings: fixed at enable.  A rate R in bit/s, 1000 .. 96000; a pattern, the low P bits of a uint64, 8 <= P <= 64, the most
+ *             significant of them transmitted first: pattern bit j, j = 0 .. P - 1, is (pattern >> j) & 1, and bit 0 is the LAST one
+ *             transmitted; E with 0 <= E and 2 E < P; the flag TFREC_AMD_SYNC_BOTH.  delta(i) = floor((768000 i + R) / (2 R)), the
+ *             samples from a symbol's centre to the centre i symbols on (delta(0) = 0); span = delta(P - 1) <= 2047.
+ *   History:  for entry e of a submit's table with track t[0 .. n) (tfrec_amd_track), t[-1], t[-2], ... are the track bits of the
+ *             same chain ahead of this piece, of which H are available: H = 0 without TFREC_AMD_RUN_CONTINUES, else H =
+ *             min(2047, H' + n') of the OPEN piece (H', n') that ended the submit before.  Per stream the device carries the last
+ *             2047 track bits of the chain of its OPEN run and H; a piece shorter than 2047 samples that continues a chain combines
+ *             what was carried with its own bits.
+ *   Distance: for k + H >= span, d[k] = the number of j in 0 .. P - 1 with t[k - delta(j)] != pattern bit j (bit 0 sits at k
+ *             itself); otherwise d[k] is undefined.
+ *   Match:    m[k] = 1 iff d[k] is defined and (d[k] <= E, or TFREC_AMD_SYNC_BOTH and d[k] >= P - E: the complemented word).
+ *   Bits:     packed exactly as the track's: m[k] of entry e is bit (pool_offset_e + k) & 31 of word (pool_offset_e + k) >> 5.  Bits
+ *             that belong to no run are 0.  A run whose samples do not fit max_samples is not looked at: its bits are 0, its n_hits
+ *             0, its best 0xffffffff, and it leaves H = 0 behind it, so that its continuation starts without history; so does an
+ *             OPEN run beyond max_runs, which has no record.  The independence of the cut (below) is therefore claimed only for
+ *             submits without TFREC_AMD_E_OVERFLOW.
+ *   Record:   the entry's first 24 bytes, bit_offset = its pool_offset, n_hits = the number of k with m[k] = 1, best = the minimum of
+ *             d[k] over the defined k -- with TFREC_AMD_SYNC_BOTH of min(d[k], P - d[k]) -- or 0xffffffff where no k is defined,
+ *             best_at = the first k that has it (0 where none), and a reserved word, 0.
+ *   Cutting:  a burst is a chain of pieces as for tfrec_amd_burst.  Merging concatenates the match tracks, adds n_samples and
+ *             n_hits, takes the smaller best -- on a tie the earlier piece's -- with its best_at offset by the samples ahead of
+ *             its piece, and the flags as for tfrec_amd_track.  With one track centre and no overflow the merged record and match
+ *             track do not depend on how the stream was cut into submits.  A restart needs nothing: only a CONTINUES run reads what
+ *             was carried.  tfrec_amd_save_streams does not carry the history: a chain that continues behind
+ *             tfrec_amd_load_streams uses what the context itself carried.
+ *   Framing (what a caller makes of a chain's merged track and match track; normative for tfrec_gpu -Y and sync.py): the input is
+ *             the first last_over + 1 samples of both (last_over: the merged tfrec_amd_track's), of the first 2^20 at most.  The
+ *             plateaus are the maximal runs [a, b] of ones in m; a plateau's sample is c = (a + b) >> 1.  For each plateau, in
+ *             order, d[c] is counted again on the merged track, a track bit ahead of its first one reading 0: the polarity is +
+ *             if d[c] <= E, else -, and the errors are d[c] or P - d[c] accordingly.  The payload is the track's bits at
+ *             c + delta(i) for i = 1, 2, ... (delta by the same formula beyond P - 1) up to the number of bits wanted; it stops at
+ *             the first position outside the input, and is complemented under -.  It is packed MSB-first.
+ * Nothing of it has been measured on real recordings. */
+#define TFREC_AMD_SYNC_BOTH 1u  /* tfrec_amd_enable_burst_sync's flag: the complemented pattern matches too */
+typedef struct {            /* 48 bytes */
+	uint32_t stream;        /* these five: copied from the table entry */
+	uint32_t flags;
+	int64_t  start_sample;
+	uint32_t n_samples;
+	int32_t  thresh;
+	uint64_t bit_offset;    /* the entry's pool_offset: m[k] is bit bit_offset + k of the bitmap */
+	uint32_t n_hits;        /* the number of k with m[k] = 1 */
+	uint32_t best;          /* the smallest distance; 0xffffffff: none defined */
+	uint32_t best_at;       /* the first k that has it */
+	uint32_t reserved;      /* 0 */
+} tfrec_amd_burst_sync;
+/* Turn the sync on: after tfrec_amd_enable_burst_track, before the first submit, once.  pattern: its low n_bits bits (higher ones
+ * are ignored); flags: 0 or TFREC_AMD_SYNC_BOTH.  Device memory, counted in tfrec_amd_get_memory: per FIFO set max_runs * 48 bytes
+ * and ceil(max_samples / 32) words; per stream the carried 64 words and H (260 bytes); no page-locked memory.  Errors: a rate
+ * outside 1000 .. 96000, n_bits outside 8 .. 64, max_errors < 0 or 2 max_errors >= n_bits, an unknown flag, a span above 2047, no
+ * burst track or a second call: TFREC_AMD_E_INVAL; after the first submit or a poisoned context: TFREC_AMD_E_STATE;
+ * TFREC_AMD_E_NOMEM as elsewhere; a call that fails leaves the context exactly as it was.  A context on which it was never called
+ * holds and launches what it did.  Its three kernels run on the recorder's low-priority stream behind the track's. */
+int tfrec_amd_enable_burst_sync(tfrec_amd_ctx *ctx, int32_t rate, uint64_t pattern, int32_t n_bits, int32_t max_errors, uint32_t flags);
+/* out[i] = the record of entry i of the table tfrec_amd_read_captures returns for the same submit, words = the match bitmap:
+ * tfrec_amd_read_burst_tracks' conventions, counts, prefixes on TFREC_AMD_E_OVERFLOW and errors throughout. */
+int tfrec_amd_read_burst_syncs(tfrec_amd_ctx *ctx, tfrec_amd_burst_sync *out, size_t cap_runs, uint32_t *n_runs, uint32_t *words,
+			       size_t cap_words, uint64_t *n_words);
+
 /* Power spectrum of the input rows (tfrec_amd_enable_spectrum): where in a recording there is energy, and where the
  * short bursts are that an average hides -- before a receiver is placed.  It belongs to an input ROW of a submit, not to a stream: it
  * is taken on x, the int16 value every format maps a stored component to (tfrec_amd_create_format; -8192 <= x <= 8191), at the

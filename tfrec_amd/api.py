@@ -19,6 +19,7 @@ from .clock import CLOCK_DTYPE  # tfrec_amd_clock
 from .envelope import ENVELOPE_DTYPE  # tfrec_amd_envelope
 from .levels import LEVEL_DTYPE  # tfrec_amd_level
 from .occupancy import OCC_DTYPE  # tfrec_amd_occupancy
+from .sync import SYNC_DTYPE  # tfrec_amd_burst_sync
 from .track import TRACK_DTYPE  # tfrec_amd_track
 
 BLOCK_BYTES = 65536
@@ -117,6 +118,7 @@ EXPORTS = (
     "tfrec_amd_load_streams", "tfrec_amd_enable_burst_envelope", "tfrec_amd_read_burst_envelopes",
     "tfrec_amd_enable_burst_clock", "tfrec_amd_read_burst_clocks",
     "tfrec_amd_enable_burst_track", "tfrec_amd_set_burst_track_centre", "tfrec_amd_read_burst_tracks",
+    "tfrec_amd_enable_burst_sync", "tfrec_amd_read_burst_syncs",
 )
 
 _libs = {}
@@ -224,6 +226,9 @@ def load_library(build: bool = True, experiments: bool = False, short_segments: 
     L.tfrec_amd_set_burst_track_centre.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tfrec_amd_read_burst_tracks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
                                               C.POINTER(C.c_uint64)]
+    L.tfrec_amd_enable_burst_sync.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_uint32]
+    L.tfrec_amd_read_burst_syncs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
+                                             C.POINTER(C.c_uint64)]
     L.tfrec_amd_stream_state_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
     L.tfrec_amd_save_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
     L.tfrec_amd_load_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
@@ -733,6 +738,34 @@ class Receiver:
         words = np.zeros(int(nw.value), dtype=np.uint32)
         _check(self.L, self.L.tfrec_amd_read_burst_tracks(self.h, out.ctypes.data, len(out), C.byref(nr),
                                                           words.ctypes.data if len(words) else None, len(words), C.byref(nw)), ok=ok)
+        return out, words
+
+    def enable_burst_sync(self, rate: int, pattern: int, n_bits: int, max_errors: int = 0, both: bool = False):
+        """Turn the burst sync on (tfrec_amd_enable_burst_sync; after enable_burst_track, before the first submit): a bit per
+        captured sample, 1 where the track read at `rate` bit/s ends in the low `n_bits` (8 .. 64) bits of `pattern`, MSB first,
+        but for at most `max_errors` places; `both`: the complemented pattern too.  read_burst_syncs returns the records and the
+        match bitmap."""
+        for v, name in ((rate, "rate"), (n_bits, "n_bits"), (max_errors, "max_errors")):
+            if not -2 ** 31 <= int(v) < 2 ** 31:  # (refused before ctypes could wrap a value into range)
+                raise TfrecAmdError(E_INVAL, name + " outside its type")
+        _check(self.L, self.L.tfrec_amd_enable_burst_sync(self.h, int(rate), int(pattern) & (2 ** 64 - 1), int(n_bits), int(max_errors),
+                                                          1 if both else 0))
+
+    def read_burst_syncs(self, allow_overflow: bool = False):
+        """The sync of the OLDEST undrained submit (tfrec_amd_read_burst_syncs; call it before the drain that pops that submit)
+        -> (a SYNC_DTYPE array, one record per entry of that submit's run table; the match bitmap's uint32 words): sync.bits_of(rec,
+        words) is a record's match track.  Overflow as for read_burst_tracks.  sync_total holds the submit's true run count."""
+        ok = (E_OK, E_OVERFLOW) if allow_overflow else (E_OK,)
+        nr, nw = C.c_uint32(0), C.c_uint64(0)
+        rc = self.L.tfrec_amd_read_burst_syncs(self.h, None, 0, C.byref(nr), None, 0, C.byref(nw))  # the counts (no room: E_INVAL)
+        self.sync_total = int(nr.value)
+        if rc != E_INVAL or nr.value == 0:
+            _check(self.L, rc, ok=ok)
+            return np.zeros(0, dtype=SYNC_DTYPE), np.zeros(0, dtype=np.uint32)
+        out = np.zeros(min(nr.value, getattr(self, "_capture", (0, 0))[0]), dtype=SYNC_DTYPE)
+        words = np.zeros(int(nw.value), dtype=np.uint32)
+        _check(self.L, self.L.tfrec_amd_read_burst_syncs(self.h, out.ctypes.data, len(out), C.byref(nr),
+                                                         words.ctypes.data if len(words) else None, len(words), C.byref(nw)), ok=ok)
         return out, words
 
     def enable_runs_input(self, max_runs: int, max_samples: int):

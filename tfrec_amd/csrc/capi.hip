@@ -30,6 +30,7 @@ using namespace tfrec;
 #include "capi_envelope.h" // the burst envelope's enable and read
 #include "capi_clock.h"    // the burst clock's enable and read
 #include "capi_track.h"    // the burst track's enable, centres and read
+#include "capi_sync.h"     // the burst sync's enable and read
 #include "capi_state.h"    // a stream's state blob: its header, the inventory table, save and load
 
 extern "C" {

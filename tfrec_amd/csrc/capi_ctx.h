@@ -116,6 +116,17 @@ struct BurstTrack {
 	int32_t *d_idx[kSets] = {}, *h_idx[kSets] = {};
 	uint32_t *d_carry = nullptr, *d_prior = nullptr;
 };
+// tfrec_amd_enable_burst_sync: the settings; per set the record of every run of the set's table and the match
+// bitmap (the track's size); per stream the carried 64 words of track bits and H (sync_carry_kernel)
+struct BurstSync {
+	bool on = false;
+	int rate = 0, n_bits = 0, max_errors = 0;
+	uint32_t flags = 0;
+	unsigned long long pattern = 0;
+	tfrec_amd_burst_sync *d_recs[kSets] = {};
+	uint32_t *d_words[kSets] = {};
+	uint32_t *d_carry = nullptr, *d_hist = nullptr;
+};
 // tfrec_amd_create_decimated (PreStage::kChannel): the carried last pair of every stream
 struct DecIn {
 	uint32_t *d_last = nullptr;
@@ -319,6 +330,7 @@ struct tfrec_amd_ctx {
 	BurstEnvelope env;
 	BurstClock clk;
 	BurstTrack trk;
+	BurstSync syn;
 	DecIn decin;
 	RunsIn runs_in;
 	SpectrumOut spec;

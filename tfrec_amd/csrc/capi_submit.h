@@ -282,6 +282,14 @@ static int launch_track(tfrec_amd_ctx *c, int set, const FrontOut &out, const Ca
 	return TFREC_AMD_OK;
 }
 
+// The burst sync's buffers of a set
+static SyncBufs sync_bufs(const tfrec_amd_ctx *c, int set)
+{
+	const BurstSync &o = c->syn;
+	return { .recs = o.d_recs[set], .words = o.d_words[set], .track = c->trk.d_words[set], .carry = o.d_carry, .hist = o.d_hist,
+		 .rate = o.rate, .n_bits = o.n_bits, .max_errors = o.max_errors, .flags = o.flags, .pattern = o.pattern };
+}
+
 // input_on_fs: the input was produced on the front-end stream itself (staged host input): no event needed
 // runs: a sparse submit (tfrec_amd_submit_runs, which checked and staged everything on the front-end stream): there are no rows
 static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int n_blocks, void *hip_stream, bool input_on_fs,
@@ -398,6 +406,8 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 			HIPCHK(launch_burst_clock(c->cap.lane.st, out, b, c->clk.d_recs[set]));
 		if (c->trk.on)  // the burst track: behind the clock, on the table, the working set, the samples, the final mask and its own carry
 			TRY(launch_track(c, set, out, b));
+		if (c->syn.on)  // the burst sync: behind the track's carry kernel, on the table, the working set, the track's bitmap and its own carry
+			HIPCHK(launch_burst_sync(c->cap.lane.st, out, b, sync_bufs(c, set)));
 		HIPCHK(lane_written(c->cap.lane, set));
 	}
 	if (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) {

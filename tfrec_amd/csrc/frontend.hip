@@ -846,6 +846,7 @@ hipError_t launch_fmdev(hipStream_t st, const FrontOut &o, EventBuf *eb, int wma
 #include "envelope.h"  // envelope_init_kernel, envelope_mask_kernel, envelope_accum_kernel, launch_burst_envelope
 #include "clock.h"     // clock_init_kernel, clock_accum_kernel, launch_burst_clock
 #include "track.h"     // track_init_kernel, track_kernel, track_carry_kernel, launch_burst_track
+#include "sync.h"      // sync_init_kernel, sync_kernel, sync_carry_kernel, launch_burst_sync
 #include "spectrum.h"  // spectrum_kernel, launch_spectrum
 #include "occupancy.h"  // occupancy_kernel, launch_occupancy
 #include "decin.h"     // decin_kernel, capture_pre_kernel and their launchers

@@ -46,6 +46,17 @@ struct TrackBufs {
 	uint32_t *carry, *prior;
 	int smooth;
 };
+// The burst sync's buffers and settings (sync.h): the set's records and match bitmap, the set's track bitmap, the carried 64 words
+// of track bits and H of every stream
+struct SyncBufs {
+	tfrec_amd_burst_sync *recs;
+	uint32_t *words;
+	const uint32_t *track;
+	uint32_t *carry, *hist;
+	int rate, n_bits, max_errors;
+	uint32_t flags;
+	unsigned long long pattern;
+};
 // The spectrum of rows 0 .. n_rows - 1 of a submit of n_in complex samples per row, and the set's records: [rows][max_records][n_bins]
 // sums and peaks, [rows][max_records] frame counts.  launch_occupancy reads what launch_spectrum has just queued on the stream.
 struct SpectrumBufs {
@@ -88,6 +99,7 @@ hipError_t launch_burst_meter(hipStream_t st, const FrontOut &o, const CaptureBu
 hipError_t launch_burst_envelope(hipStream_t st, const FrontOut &o, const CaptureBufs &b, tfrec_amd_envelope *out);
 hipError_t launch_burst_clock(hipStream_t st, const FrontOut &o, const CaptureBufs &b, tfrec_amd_clock *out);
 hipError_t launch_burst_track(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);
+hipError_t launch_burst_sync(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const SyncBufs &k);
 hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, const SpectrumBufs &b);
 hipError_t launch_occupancy(hipStream_t st, const SpectrumBufs &b, uint32_t ratio, uint32_t rel, tfrec_amd_occupancy *recs, uint32_t *bits);
 // ... and the parity probes

@@ -275,6 +275,11 @@ inline int device_worker::open_context()
 			r = tfrec_amd_set_burst_track_centre(ctx, all.data(), hz.data(), (int)n);
 		}
 	}
+	if (!r && job.syncing()) {  // -Y: the sync on the track, at -G's rate
+		call = "tfrec_amd_enable_burst_sync";
+		r = tfrec_amd_enable_burst_sync(ctx, (int32_t)job.track_rate, job.sync_pattern, job.sync_bits, job.sync_errors,
+						job.sync_both ? TFREC_AMD_SYNC_BOTH : 0u);
+	}
 	if (!r && job.replay) {  // -R, sized so that every submit fits: its files' runs (a cut adds one per stream), every sample at most
 		uint64_t runs = 0, pairs = 0;
 		for (size_t f = s0; f < s1; f++) {
@@ -637,7 +642,8 @@ inline int device_worker::read_clocks(size_t k, batch_result &b)
 }
 
 // -G: the batch's track records, each with its bits out of the batch's bitmap.  stream -> file, as for the events; a record that
-// begins behind its file's end is dropped, one that reaches over it is cut there and is OPEN (job.h: track_take)
+// begins behind its file's end is dropped, one that reaches over it is cut there and is OPEN (job.h: track_take).  -Y: the sync
+// records of the same entries with them, each with its match track (job.h: sync_take), in b.syncs in place of b.tracks
 inline int device_worker::read_tracks(size_t k, batch_result &b)
 {
 	uint32_t nr = 0;
@@ -656,6 +662,22 @@ inline int device_worker::read_tracks(size_t k, batch_result &b)
 	}
 	if (r)
 		return r;
+	std::vector<tfrec_amd_burst_sync> srecs;
+	std::vector<uint32_t> swords;
+	if (job.syncing()) {
+		r = tfrec_amd_read_burst_syncs(ctx, NULL, 0, &nr, NULL, 0, &nw);
+		if (r == TFREC_AMD_E_INVAL && nr) {
+			srecs.resize(nr);
+			swords.resize((size_t)nw + 1);
+			r = tfrec_amd_read_burst_syncs(ctx, srecs.data(), srecs.size(), &nr, swords.data(), swords.size(), &nw);
+		}
+		if (r)
+			return r;
+		if (srecs.size() != recs.size()) {
+			fprintf(stderr, "tfrec_amd: device %d batch %zu: %zu sync records beside %zu track records\n", device, k, srecs.size(), recs.size());
+			return TFREC_AMD_E_STATE;
+		}
+	}
 	const std::vector<int> &file = plan[k].file;
 	for (size_t q = 0; q < recs.size(); q++) {
 		tfrec_amd_track x = recs[q];
@@ -670,7 +692,10 @@ inline int device_worker::read_tracks(size_t k, batch_result &b)
 			x.flags |= TFREC_AMD_RUN_OPEN;
 		}
 		x.stream = (uint32_t)file[x.stream];
-		b.tracks.push_back(track_take(x, words.data(), n));
+		if (job.syncing())
+			b.syncs.push_back(sync_take(srecs[q], swords.data(), track_take(x, words.data(), n)));
+		else
+			b.tracks.push_back(track_take(x, words.data(), n));
 	}
 	return 0;
 }

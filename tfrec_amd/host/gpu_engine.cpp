@@ -432,6 +432,9 @@ int gpu_engine::run()
 	track_merger tracks;
 	std::vector<track_piece> said;
 	tracks.begin(n);
+	sync_merger syncs;
+	std::vector<sync_piece> framed;
+	syncs.begin(n);
 	if (job.spectrum)
 		spec.begin(job);
 	if (job.occupancy())
@@ -496,7 +499,15 @@ int gpu_engine::run()
 						printf("%s\n", clock_line(files[x.stream], x).c_str());
 				}
 			}
-			if (job.tracking()) {  // -G: likewise, behind -C's lines of the batch
+			if (job.syncing()) {  // -G -Y: -G's line of each burst, and behind it a line per frame found in it
+				framed.clear();
+				syncs.take(b, workers[d].plan[k], file_blocks, framed);
+				for (const sync_piece &x : framed) {
+					printf("%s\n", track_line(files[x.stream], x.trk, job.track_rate).c_str());
+					for (const sync_frame &f : sync_frames(x, job))
+						printf("%s\n", sync_line(files[x.stream], x, f).c_str());
+				}
+			} else if (job.tracking()) {  // -G: likewise, behind -C's lines of the batch
 				said.clear();
 				tracks.take(b, workers[d].plan[k], file_blocks, said);
 				for (const track_piece &x : said)

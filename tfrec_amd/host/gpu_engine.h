@@ -227,6 +227,21 @@ public:
 		job.track_rate = rate;
 		job.track_centre = centre_hz;
 	}
+	// -Y (with -G): the burst sync (tfrec_amd_enable_burst_sync) on the track, at -G's rate: the sync word is the low
+	// n_bits of pattern, MSB first.  run() merges the sync records' chains and their match tracks beside the track's (job.h:
+	// sync_merger) and prints, behind each burst's bits line, in the order of their samples,
+	//   frame <file> <start_sample> <sync_sample> <errors> <+|-> <n_bits> <hex|->
+	// (job.h: sync_frames, sync_line: per plateau of matches inside the burst the payload's first `bytes` bytes, read at symbol
+	// centres from the plateau's middle, MSB-first; "-": the complemented word matched and the payload is complemented).  The
+	// defaults -- no errors, 8 bytes, one polarity -- are not tuned on anything: nothing of it has been measured on real recordings.
+	void set_sync(unsigned long long pattern, int n_bits, int errors, int bytes, bool both)
+	{
+		job.sync_pattern = pattern;
+		job.sync_bits = n_bits;
+		job.sync_errors = errors;
+		job.sync_bytes = bytes;
+		job.sync_both = both;
+	}
 	// -k: keep.  A file is processed in whole pieces only and nothing is padded; before the first batch behind a
 	// file's last one is submitted -- and at the end of the job -- its stream is saved (tfrec_amd_save_streams) to
 	// <prefix>.<file index>.state, and at the end of a run without an error the bytes that did not fill a piece are written to

@@ -99,6 +99,11 @@ struct job_settings {
 	bool clock = false;            // set_clock
 	long track_rate = 0;           // set_track (0: none): the rate in bit/s, 1000 .. 96000
 	long track_centre = 0;         // ... and every stream's centre in Hz
+	int sync_bits = 0;             // set_sync (0: none): P, the sync word's bits, 8 .. 64
+	unsigned long long sync_pattern = 0;  // ... the word, in its low P bits
+	int sync_errors = 0;           // ... E
+	int sync_bytes = 8;            // ... the payload bytes read behind the word
+	bool sync_both = false;        // ... the complemented word too
 	const std::vector<replay_file> *replay = NULL;  // set_replay (NULL: the files are dumps)
 	std::string keep_prefix;       // set_keep ("": none)
 	std::string cont_prefix;       // set_continue ("": none)
@@ -112,6 +117,7 @@ struct job_settings {
 	bool occupancy() const { return spectrum && occ_ratio; }  // -A, pass 1
 	bool recorder() const { return capture || metering() || enveloping() || clocking() || tracking(); }  // the contexts enable the recorder: for -S, or as the meter's, the envelope's, the clock's or the track's table
 	bool tracking() const { return track_rate != 0; }  // -G (never with -s or -A)
+	bool syncing() const { return sync_bits != 0; }  // -Y (only with -G)
 	// -G's L: half a symbol, (384000 + rate) / (2 rate) held within 1 .. 16
 	int track_smooth() const { return (int)std::max(1L, std::min(16L, (384000 + track_rate) / (2 * track_rate))); }
 	bool metering() const { return meter && !occupancy(); }  // -M (under -A: in the scan, not in pass 1)
@@ -368,8 +374,17 @@ struct track_piece : tfrec_amd_track {
 	bool bit(uint64_t k) const { return (bits[k >> 5] >> (k & 31)) & 1u; }
 };
 
+// -Y: a sync record with its match track (packed as a track_piece's bits) and the track piece of the same table entry
+struct sync_piece : tfrec_amd_burst_sync {
+	std::vector<uint32_t> match;
+	track_piece trk;
+	uint64_t kept() const { return std::min<uint64_t>(n_samples, kTrackKeep); }
+	bool hit(uint64_t k) const { return (match[k >> 5] >> (k & 31)) & 1u; }
+};
+
 struct batch_result {
 	std::vector<track_piece> tracks;
+	std::vector<sync_piece> syncs;  // (-Y: in place of tracks)
 	std::vector<tfrec_amd_burst> bursts;
 	std::vector<tfrec_amd_envelope> envelopes;
 	std::vector<tfrec_amd_clock> clocks;
@@ -719,7 +734,114 @@ inline std::string track_line(const std::string &file, const track_piece &c, lon
 	return s;
 }
 
+// ---- -Y: the burst sync's records, match tracks and frames (include/tfrec_amd.h: tfrec_amd_burst_sync, whose text is normative;
+// tfrec_amd/sync.py restates merge, the framing and the line)
+
+// a device record, the submit's match bitmap and the entry's track piece -> the piece, as many samples of it as the track piece
+// has (the file's end may cut both): n_hits counted again on what is kept of a cut piece; its best and best_at stay if best_at lies
+// ahead of the cut and are none (0xffffffff, 0) otherwise -- the minimum over the kept part alone is not known, and no line shows it
+inline sync_piece sync_take(const tfrec_amd_burst_sync &r, const uint32_t *words, const track_piece &t)
+{
+	sync_piece p;
+	static_cast<tfrec_amd_burst_sync &>(p) = r;
+	p.trk = t;
+	p.stream = t.stream;
+	p.flags = t.flags;
+	const bool cut = t.n_samples < r.n_samples;
+	p.n_samples = t.n_samples;
+	track_append(p.match, 0, words, r.bit_offset, p.n_samples);
+	if (cut) {
+		p.n_hits = 0;
+		for (uint64_t k = 0; k < p.kept(); k++)
+			p.n_hits += p.hit(k);
+		if (p.best_at >= p.n_samples) {
+			p.best = 0xffffffffu;
+			p.best_at = 0;
+		}
+	}
+	return p;
+}
+
+// piece p, which CONTINUES the chain c, merged into it (the header's Cutting): the match tracks concatenated, n_samples and n_hits
+// added, the smaller best (on a tie the earlier piece's) with its best_at offset by the samples ahead; the track pieces by track_add
+inline void sync_add(sync_piece &c, const sync_piece &p)
+{
+	if (!p.match.empty())
+		track_append(c.match, c.kept(), p.match.data(), 0, p.kept());
+	if (p.best < c.best) {
+		c.best = p.best;
+		c.best_at = c.n_samples + p.best_at;
+	}
+	c.n_samples += p.n_samples;
+	c.n_hits += p.n_hits;
+	c.flags = (c.flags & TFREC_AMD_RUN_CONTINUES) | (p.flags & TFREC_AMD_RUN_OPEN);
+	track_add(c.trk, p.trk);
+}
+
+// delta(i) = floor((768000 i + R) / (2 R))
+inline uint64_t sync_delta(uint64_t i, long rate) { return (768000 * i + (uint64_t)rate) / (2 * (uint64_t)rate); }
+
+struct sync_frame {
+	uint64_t c = 0;    // the plateau's sample, chain-relative
+	int errors = 0;
+	bool plus = true;  // the polarity
+	std::vector<uint8_t> bits;  // the payload, one per byte
+};
+
+// The header's Framing on the first min(last_over + 1, 2^20) samples of a chain's merged track and match track
+inline std::vector<sync_frame> sync_frames(const sync_piece &c, const job_settings &job)
+{
+	std::vector<sync_frame> out;
+	const int P = job.sync_bits, E = job.sync_errors;
+	const uint64_t n = c.trk.last_over < 0 ? 0 : std::min<uint64_t>((uint64_t)c.trk.last_over + 1, c.kept());
+	for (uint64_t k = 0; k < n;) {
+		if (!c.hit(k)) {
+			k++;
+			continue;
+		}
+		uint64_t b = k;
+		while (b + 1 < n && c.hit(b + 1))
+			b++;
+		sync_frame f;
+		f.c = (k + b) >> 1;
+		int d = 0;
+		for (int j = 0; j < P; j++) {
+			const uint64_t back = sync_delta((uint64_t)j, job.track_rate);
+			const bool t = back <= f.c ? c.trk.bit(f.c - back) : false;  // (ahead of the track: 0)
+			d += t != (bool)((job.sync_pattern >> j) & 1ull);
+		}
+		f.plus = d <= E;
+		f.errors = f.plus ? d : P - d;
+		for (int i = 1; i <= 8 * job.sync_bytes; i++) {
+			const uint64_t q = f.c + sync_delta((uint64_t)i, job.track_rate);
+			if (q >= n)
+				break;
+			f.bits.push_back((uint8_t)(c.trk.bit(q) == f.plus));
+		}
+		out.push_back(f);
+		k = b + 1;
+	}
+	return out;
+}
+
+// frame <file> <start_sample> <sync_sample> <errors> <+|-> <n_bits> <hex|->: MSB-first, the last nibble zero-padded
+inline std::string sync_line(const std::string &file, const sync_piece &c, const sync_frame &f)
+{
+	std::string s = "frame " + file + " " + std::to_string((long long)c.start_sample) + " " + std::to_string((long long)c.start_sample + (long long)f.c) +
+			" " + std::to_string(f.errors) + " " + (f.plus ? "+" : "-") + " " + std::to_string(f.bits.size()) + " ";
+	if (f.bits.empty())
+		return s + "-";
+	for (size_t i = 0; i < f.bits.size(); i += 4) {
+		int nib = 0;
+		for (size_t j = 0; j < 4; j++)
+			nib = 2 * nib + (i + j < f.bits.size() ? f.bits[i + j] : 0);
+		s += "0123456789abcdef"[nib];
+	}
+	return s;
+}
+
 inline void chain_add(tfrec_amd_burst &c, const tfrec_amd_burst &p) { burst_add(c, p); }
+inline void chain_add(sync_piece &c, const sync_piece &p) { sync_add(c, p); }
 inline void chain_add(track_piece &c, const track_piece &p) { track_add(c, p); }
 inline void chain_add(tfrec_amd_clock &c, const tfrec_amd_clock &p) { clock_add(c, p); }
 inline void chain_add(tfrec_amd_envelope &c, const tfrec_amd_envelope &p) { envelope_add(c, p); }
@@ -797,6 +919,15 @@ struct track_merger : chain_merger<track_piece> {  // -G
 	void take(const batch_result &b, const batch_plan &p, const std::vector<size_t> &file_blocks, std::vector<track_piece> &out)
 	{
 		chain_merger<track_piece>::take(b.tracks, p, file_blocks, out);
+	}
+};
+
+struct sync_merger : chain_merger<sync_piece> {  // -Y
+	void take(const batch_result &b, const batch_plan &p, const std::vector<size_t> &file_blocks, std::vector<sync_piece> &out)
+	{
+		chain_merger<sync_piece>::take(b.syncs, p, file_blocks, out);
+		for (sync_piece &x : out)  // (the merger clears OPEN on the chain's own flags: the track piece's follow)
+			x.trk.flags = x.flags;
 	}
 };
 

@@ -112,6 +112,15 @@
 // slicer, not a demodulator: no clock recovery, no matched filter; the golden TFA_1 and WHB scenes do not slice with it.  Works with
 // -M, -Q, -C, -S, -R, -n, -d and every input option; not with -X, -k, -K, -s or -A.  Nothing of it has been measured on real
 // recordings.
+// -Y hex[,errors[,bytes[,both]]] (not in the reference; with -G): the burst sync (tfrec_amd_enable_burst_sync): the
+// sync word is the 2 .. 16 hex digits (8 .. 64 bits), MSB first; the track, read at -G's rate at symbol centres, may differ from it
+// in `errors` places (default 0, below half the bits); both = 1 accepts the complemented word too (default 0).  Behind each burst's
+// bits line stdout gets, for every plateau of matching samples inside the burst, in order,
+//   frame <file> <start_sample> <sync_sample> <errors> <+|-> <n_bits> <hex|->
+// sync_sample: the plateau's middle, where the word's last bit is read; the hex: the `bytes` bytes (1 .. 256, default 8) read at
+// symbol centres behind it, MSB-first, as far as the burst reaches, complemented under "-".  No CRC is checked.  A word whose span
+// at the rate exceeds 2047 samples is refused.  Works where -G works.  The defaults are not tuned on anything: nothing of it has
+// been measured on real recordings.
 // -P bins[,frames_per_record] (not in the reference): the power spectrum of ONE recording, beside its decoding: an
 // exact integer DFT of bins = 64, 128, 256, 512 or 1024 bins over the raw input -- at 1.536 MS/s, or given with -x, or with -r / -F --,
 // per record of frames_per_record frames (1 .. 16384; default: the frames one block's input holds, at least 1) the sum and the peak
@@ -286,6 +295,9 @@ struct cli {
 	bool envelope = false;  // -Q
 	bool clock = false;  // -C
 	long track_rate = 0, track_centre = 0;  // -G (rate 0: not given)
+	int sync_bits = 0;  // -Y (0: not given): the word's bits, the word, errors, bytes, both
+	unsigned long long sync_pattern = 0;
+	long sync_errors = 0, sync_bytes = 8, sync_both = 0;
 	const char *keep_prefix = NULL, *cont_prefix = NULL;  // -k, -K
 	bool have_center = false, have_format = false;  // -c, -F given (-R refuses them)
 	std::vector<replay_file> captures;  // -R: one per file index of <prefix>.idx
@@ -319,7 +331,7 @@ struct cli {
 
 static void usage()
 {
-	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-G rate[,centre_hz]] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
+	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-G rate[,centre_hz]] [-Y hex[,errors[,bytes[,both]]]] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
 			"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
 			"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
 			"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
@@ -343,6 +355,9 @@ static void usage()
 			"              line 'bits <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->' per trigger window, MSB-first,\n"
 			"              1 above the centre (+: longer than the 2^20 samples kept); also with -M, -Q, -C, -S and -R; not with -X, -k, -K,\n"
 			"              -s or -A\n"
+			"  -Y h[,e[,n[,b]]]  with -G: find the sync word h (2 .. 16 hex digits, MSB first) in every burst's track with at most e bit errors\n"
+			"              (default 0), b = 1: or its complement, and read the n bytes behind it (default 8) at symbol centres: a line 'frame <file>\n"
+			"              <start_sample> <sync_sample> <errors> <+|-> <n_bits> <hex|->' per match, behind the burst's bits line\n"
 			"  -k prefix   keep: for a recording that arrives in parts.  Every -L file is processed in whole blocks only (nothing is padded), then\n"
 			"              its receiver's state is saved to <prefix>.<file index>.state and the bytes that filled no block to\n"
 			"              <prefix>.<file index>.rest\n"
@@ -425,7 +440,7 @@ bool cli::parse_format(const char *arg)
 int cli::parse(int argc, char **argv)
 {
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCG:k:K:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCG:Y:k:K:h")) != -1) {
 		switch (c) {
 		case 'M': meter = true; break;
 		case 'Q': envelope = true; break;
@@ -436,6 +451,30 @@ int cli::parse(int argc, char **argv)
 			    (comma && !parse_long(comma + 1, -192000, 192000, track_centre))) {
 				fprintf(stderr, "tfrec_gpu: bad -G '%s': want <rate>[,<centre_hz>], the rate within 1000 .. 96000 bit/s, the centre within "
 						"-192000 .. 192000 Hz\n", optarg);
+				return 1;
+			}
+			break;
+		}
+		case 'Y': {
+			std::vector<std::string> part(1);
+			for (const char *q = optarg; *q; q++) {
+				if (*q == ',')
+					part.push_back("");
+				else
+					part.back() += *q;
+			}
+			const std::string &hex = part[0];
+			bool ok = part.size() <= 4 && hex.size() >= 2 && hex.size() <= 16 && hex.find_first_not_of("0123456789abcdefABCDEF") == std::string::npos;
+			if (ok) {
+				sync_bits = 4 * (int)hex.size();
+				sync_pattern = strtoull(hex.c_str(), NULL, 16);
+				ok = (part.size() < 2 || parse_long(part[1].c_str(), 0, (sync_bits - 1) / 2, sync_errors)) &&
+				     (part.size() < 3 || parse_long(part[2].c_str(), 1, 256, sync_bytes)) &&
+				     (part.size() < 4 || parse_long(part[3].c_str(), 0, 1, sync_both));
+			}
+			if (!ok) {
+				fprintf(stderr, "tfrec_gpu: bad -Y '%s': want <hex>[,<errors>[,<bytes>[,<both>]]], 2 .. 16 hex digits, errors below half the word's "
+						"bits, 1 .. 256 bytes, both 0 or 1\n", optarg);
 				return 1;
 			}
 			break;
@@ -632,6 +671,15 @@ int cli::check() const
 	}
 	if (clock && hexfile) {
 		fprintf(stderr, "tfrec_gpu: -C measures the bursts of -L files or of a capture (-R): not with -X\n");
+		return 1;
+	}
+	if (sync_bits && !track_rate) {
+		fprintf(stderr, "tfrec_gpu: -Y finds its sync word in the track of -G: give -G rate[,centre_hz] with it\n");
+		return 1;
+	}
+	if (sync_bits && (768000LL * (sync_bits - 1) + track_rate) / (2LL * track_rate) > 2047) {
+		fprintf(stderr, "tfrec_gpu: -Y: %d bits at %ld bit/s span %lld samples, more than 2047\n", sync_bits, track_rate,
+			(768000LL * (sync_bits - 1) + track_rate) / (2LL * track_rate));
 		return 1;
 	}
 	if (track_rate && (hexfile || have_scan || have_auto)) {
@@ -877,6 +925,8 @@ int cli::run()
 		e.set_clock();
 	if (track_rate)
 		e.set_track(track_rate, track_centre);
+	if (sync_bits)
+		e.set_sync(sync_pattern, sync_bits, (int)sync_errors, (int)sync_bytes, sync_both != 0);
 	if (keep_prefix)
 		e.set_keep(keep_prefix);
 	if (cont_prefix)
