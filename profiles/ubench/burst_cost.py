@@ -1,4 +1,4 @@
-"""Cost of the burst meter: kernel time of burst_init_kernel and burst_accum_kernel, and the period per submit of a
+"""Cost of the burst meter: kernel time of run_records_init_kernel<tfrec_amd_burst> and burst_accum_kernel, and the period per submit of a
 context with the meter against a plain one and one with the recorder's table alone, on the same input in the same session.
 
     python profiles/ubench/burst_cost.py [--out DIR] [--streams 1024] [--blocks 48] [--submits 12] [--bursts 6]
@@ -27,7 +27,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from resample_cost import HBM_PEAK, WARMUP, durations  # noqa: E402
 
 TIME_LIMIT = 600  # seconds, for the traced child
-KERNELS = ("burst_init_kernel", "burst_accum_kernel", "capture_copy_kernel")
+KERNELS = ("run_records_init_kernel<tfrec_amd_burst>", "burst_accum_kernel", "capture_copy_kernel")
 
 
 def workload(n_streams: int, n_blocks: int, submits: int, bursts: int) -> None:

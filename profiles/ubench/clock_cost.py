@@ -1,4 +1,4 @@
-"""Cost of the burst clock: kernel time of clock_init_kernel and clock_accum_kernel beside burst_accum_kernel's, and
+"""Cost of the burst clock: kernel time of run_records_init_kernel<tfrec_amd_clock> and clock_accum_kernel beside burst_accum_kernel's, and
 the period per submit of a context with the clock against one with the burst meter, one with the recorder's table alone and a
 plain one, on the same input in the same session.
 
@@ -29,7 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from resample_cost import HBM_PEAK, WARMUP, durations  # noqa: E402
 
 TIME_LIMIT = 600  # seconds, for the traced child
-KERNELS = ("clock_init_kernel", "clock_accum_kernel", "burst_accum_kernel", "capture_copy_kernel")
+KERNELS = ("run_records_init_kernel<tfrec_amd_clock>", "clock_accum_kernel", "burst_accum_kernel", "capture_copy_kernel")
 KINDS = ("clock", "meter", "table", "plain")
 
 

@@ -1,4 +1,4 @@
-"""Cost of the burst envelope: kernel time of envelope_init_kernel, envelope_mask_kernel (pass A) and
+"""Cost of the burst envelope: kernel time of run_records_init_kernel<tfrec_amd_envelope>, envelope_mask_kernel (pass A) and
 envelope_accum_kernel (pass B), and the period per submit of a context with the envelope against one with the burst meter, one with the
 recorder's table alone and a plain one, on the same input in the same session.
 
@@ -28,7 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from resample_cost import HBM_PEAK, WARMUP, durations  # noqa: E402
 
 TIME_LIMIT = 600  # seconds, for the traced child
-KERNELS = ("envelope_init_kernel", "envelope_mask_kernel", "envelope_accum_kernel", "burst_accum_kernel", "capture_copy_kernel")
+KERNELS = ("run_records_init_kernel<tfrec_amd_envelope>", "envelope_mask_kernel", "envelope_accum_kernel", "burst_accum_kernel", "capture_copy_kernel")
 KINDS = ("envelope", "meter", "table", "plain")
 
 

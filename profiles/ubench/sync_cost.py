@@ -1,4 +1,4 @@
-"""Cost of the burst sync: kernel time of sync_init_kernel, sync_kernel and sync_carry_kernel beside track_kernel's,
+"""Cost of the burst sync: kernel time of run_records_init_kernel<tfrec_amd_burst_sync>, sync_kernel and sync_carry_kernel beside track_kernel's,
 for a word of 16 bits and one of 64 at 17240 bit/s, and the period per submit of a context with the sync against one with the
 track alone (the same recorder and pool), on the same input in the same session.
 
@@ -29,7 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from resample_cost import HBM_PEAK, WARMUP, durations  # noqa: E402
 
 TIME_LIMIT = 600  # seconds, for the traced child
-KERNELS = ("sync_init_kernel", "sync_kernel", "sync_carry_kernel", "track_kernel")
+KERNELS = ("run_records_init_kernel<tfrec_amd_burst_sync>", "sync_kernel", "sync_carry_kernel", "track_kernel")
 # context -> (the word, its bits); None: the track alone
 KINDS = (("sync16", (0x2DD4, 16)), ("sync64", (0x5A0FF0A5C3963C69, 64)), ("track", None))
 

@@ -1,4 +1,4 @@
-"""Cost of the burst track: kernel time of track_init_kernel, track_kernel and track_carry_kernel beside
+"""Cost of the burst track: kernel time of run_records_init_kernel<tfrec_amd_track>, track_kernel and track_carry_kernel beside
 capture_copy_kernel's, and the period per submit of a context with the track against one with the recorder alone (the same pool:
 the bitmap has the pool's size) and a plain one, on the same input in the same session.
 
@@ -28,7 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from resample_cost import HBM_PEAK, WARMUP, durations  # noqa: E402
 
 TIME_LIMIT = 600  # seconds, for the traced child
-KERNELS = ("track_init_kernel", "track_kernel", "track_carry_kernel", "capture_copy_kernel")
+KERNELS = ("run_records_init_kernel<tfrec_amd_track>", "track_kernel", "track_carry_kernel", "capture_copy_kernel")
 KINDS = ("track", "recorder", "plain")
 
 

@@ -198,7 +198,7 @@ def test_summary_of_the_golden_tfa_2_burst_and_of_its_rotations():
 def merge_driver(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("burst_merge") / "burst_merge_driver")
     subprocess.check_call(["g++", "-std=c++11", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-o", exe, os.path.join(parity.ROOT, "tests", "burst_merge_driver.cpp")])
+                           "-o", exe, os.path.join(parity.ROOT, "tests", "merge_driver.cpp")])
     return exe
 
 
@@ -228,7 +228,7 @@ def test_the_host_merge_prints_the_restatements_lines(merge_driver):
         chains = burst.chains(subs)
         assert any(int(c["n_samples"]) > B for c in chains) or f == 0
         want += [burst.line(name, c) for c in chains]
-    out = subprocess.run([merge_driver], input="".join(ln + "\n" for ln in lines), capture_output=True, text=True, timeout=120)
+    out = subprocess.run([merge_driver, "burst"], input="".join(ln + "\n" for ln in lines), capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr
     assert out.stdout.splitlines() == want and len(want) >= 3
     assert want[-1].split()[3] == str(3 * B - int(want[-1].split()[2]))  # the noise file's chain reaches the file's end

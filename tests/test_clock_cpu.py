@@ -313,7 +313,7 @@ def test_merge_takes_the_ends_flags_and_spec_saturates():
 def merge_driver(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("clock_merge") / "clock_merge_driver")
     subprocess.check_call(["g++", "-std=c++11", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-o", exe, os.path.join(parity.ROOT, "tests", "clock_merge_driver.cpp")])
+                           "-o", exe, os.path.join(parity.ROOT, "tests", "merge_driver.cpp")])
     return exe
 
 
@@ -351,7 +351,7 @@ def test_the_host_merge_prints_the_restatements_lines(merge_driver):
     m = clock.merge(chain)
     assert m["spec"][46] == (1 << 64) - 1 and m["n_segments"] == 24
     want.append(clock.line("c.iq", m))
-    out = subprocess.run([merge_driver], input="".join(ln + "\n" for ln in lines), capture_output=True, text=True, timeout=120)
+    out = subprocess.run([merge_driver, "clock"], input="".join(ln + "\n" for ln in lines), capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr
     assert out.stdout.splitlines() == want
     assert want[0].split()[4:] == ["27", "5997", "60.05"] and want[-5].endswith(" 1 - -") and want[-4].endswith(" 0 - -")

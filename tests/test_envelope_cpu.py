@@ -336,7 +336,7 @@ def test_the_ratio_needs_128_bits():
 def merge_driver(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("envelope_merge") / "envelope_merge_driver")
     subprocess.check_call(["g++", "-std=c++11", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-o", exe, os.path.join(parity.ROOT, "tests", "envelope_merge_driver.cpp")])
+                           "-o", exe, os.path.join(parity.ROOT, "tests", "merge_driver.cpp")])
     return exe
 
 
@@ -369,7 +369,7 @@ def test_the_host_merge_prints_the_restatements_lines(merge_driver):
     for p in pieces:
         lines += ["batch 1 2", rec_line(2, p)]
     want.append(envelope.line("c.iq", envelope.merge(pieces)))
-    out = subprocess.run([merge_driver], input="".join(ln + "\n" for ln in lines), capture_output=True, text=True, timeout=120)
+    out = subprocess.run([merge_driver, "envelope"], input="".join(ln + "\n" for ln in lines), capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr
     assert out.stdout.splitlines() == want and len(want) >= 4
     assert any(ln.split()[8] != "-" and int(ln.split()[6]) >= 1 for ln in want[:-2])  # a golden burst with gaps and a ratio

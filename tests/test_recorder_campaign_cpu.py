@@ -156,12 +156,12 @@ def test_a_chain_that_ends_with_a_submits_last_sample_merges_into_the_uncut_runs
     assert all(int(c["flags"]) & capture.RUN_OPEN for c in kept) and len(kept) == 4
     exe = str(tmp_path / "envelope_merge_driver")
     subprocess.check_call(["g++", "-std=c++11", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-o", exe, os.path.join(parity.ROOT, "tests", "envelope_merge_driver.cpp")])
+                           "-o", exe, os.path.join(parity.ROOT, "tests", "merge_driver.cpp")])
     lines = ["file a.iq 2", "file b.iq 2"]
     for e in a:
         lines.append("batch 1 0 1")
         lines += [rec_line(int(r["stream"]), r) for r in e["envelope"]]
-    out = subprocess.run([exe], input="".join(ln + "\n" for ln in lines), capture_output=True, text=True, timeout=120)
+    out = subprocess.run([exe, "envelope"], input="".join(ln + "\n" for ln in lines), capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr
     want = [envelope.line("ab"[int(c["stream"])] + ".iq", c) for c in envelope.chains([e["envelope"] for e in b])]
     assert sorted(out.stdout.splitlines()) == sorted(want) and len(want) == 3

@@ -310,7 +310,7 @@ def test_merge_takes_the_smaller_best_and_on_a_tie_the_earlier_piece():
 def merge_driver(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("sync_merge") / "sync_merge_driver")
     subprocess.check_call(["g++", "-std=c++11", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-o", exe, os.path.join(parity.ROOT, "tests", "sync_merge_driver.cpp")])
+                           "-o", exe, os.path.join(parity.ROOT, "tests", "merge_driver.cpp")])
     return exe
 
 
@@ -335,7 +335,7 @@ def expected_lines(name, tsubs, ssubs, st, n_bytes):
 
 def run_driver(exe, st, n_bytes, lines):
     head = ["sync %d %x %d %d %d %d" % (st.rate, st.pattern, st.P, st.E, n_bytes, st.both)]
-    out = subprocess.run([exe], input="".join(ln + "\n" for ln in head + lines), capture_output=True, text=True, timeout=120)
+    out = subprocess.run([exe, "sync"], input="".join(ln + "\n" for ln in head + lines), capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr
     return out.stdout.splitlines()
 

@@ -310,7 +310,7 @@ def test_the_cap_of_two_to_the_twenty_samples():
 def merge_driver(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("track_merge") / "track_merge_driver")
     subprocess.check_call(["g++", "-std=c++11", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-o", exe, os.path.join(parity.ROOT, "tests", "track_merge_driver.cpp")])
+                           "-o", exe, os.path.join(parity.ROOT, "tests", "merge_driver.cpp")])
     return exe
 
 
@@ -368,7 +368,7 @@ def test_the_host_merge_prints_the_restatements_lines(merge_driver):
     cut["n_samples"], cut["last_over"], cut["flags"] = 50, 49, OPEN
     want.append(track.line("c.iq", track.Piece(cut, bits[:50]), R))
     assert want[-1] == "bits c.iq %d 50 50 2 4" % (8192 * 4096 - 50)
-    out = subprocess.run([merge_driver], input="".join(ln + "\n" for ln in lines), capture_output=True, text=True, timeout=120)
+    out = subprocess.run([merge_driver, "track"], input="".join(ln + "\n" for ln in lines), capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr
     assert out.stdout.splitlines() == want
 
@@ -379,7 +379,7 @@ def test_the_host_keeps_two_to_the_twenty_samples_of_a_chain(merge_driver):
     for r, b in zip(recs, bits):
         words = np.packbits(b.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1)
         lines += batch_lines(16, [0], [r], words, 0)
-    out = subprocess.run([merge_driver], input="".join(ln + "\n" for ln in lines), capture_output=True, text=True, timeout=120)
+    out = subprocess.run([merge_driver, "track"], input="".join(ln + "\n" for ln in lines), capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr
     want = track.line("a.iq", track.merge([track.Piece(r, b) for r, b in zip(recs, bits)]), 17240)
     assert out.stdout.splitlines() == [want] and "+" in want.split()[5]

@@ -636,6 +636,27 @@ class Receiver:
             pre = pre[:len(self.read_captures(allow_overflow=True)[0])]
         return pre
 
+    def _read_run_records(self, fn, dtype, total_attr, allow_overflow, words=False):
+        """What the reads of the five burst stages share: the records of the oldest undrained submit by `fn` -- the count first
+        (no room: E_INVAL), then the records, and with `words` the bitmap's uint32 words beside them.  `total_attr` is given the
+        submit's true run count; E_OVERFLOW raises unless allow_overflow."""
+        ok = (E_OK, E_OVERFLOW) if allow_overflow else (E_OK,)
+        nr, nw = C.c_uint32(0), C.c_uint64(0)
+        counts = (None, 0, C.byref(nw)) if words else ()
+        rc = fn(self.h, None, 0, C.byref(nr), *counts)  # the counts (no room: E_INVAL)
+        setattr(self, total_attr, int(nr.value))
+        bits = np.zeros(0, dtype=np.uint32)
+        if rc != E_INVAL or nr.value == 0:
+            _check(self.L, rc, ok=ok)
+            out = np.zeros(0, dtype=dtype)
+            return (out, bits) if words else out
+        out = np.zeros(min(nr.value, getattr(self, "_capture", (0, 0))[0]), dtype=dtype)
+        if words:
+            bits = np.zeros(int(nw.value), dtype=np.uint32)
+            counts = (bits.ctypes.data if len(bits) else None, len(bits), C.byref(nw))
+        _check(self.L, fn(self.h, out.ctypes.data, len(out), C.byref(nr), *counts), ok=ok)
+        return (out, bits) if words else out
+
     def enable_burst_meter(self):
         """Turn the burst meter on (tfrec_amd_enable_burst_meter; after enable_capture, before the first submit).  read_bursts
         returns its records."""
@@ -646,16 +667,7 @@ class Receiver:
         submit) -> a BURST_DTYPE array, one record per entry of that submit's run table (burst.py).  They do not depend on the pool:
         a table with more than max_runs entries (E_OVERFLOW) raises unless allow_overflow, then its first max_runs records are
         returned; burst_total holds the submit's true run count."""
-        ok = (E_OK, E_OVERFLOW) if allow_overflow else (E_OK,)
-        nr = C.c_uint32(0)
-        rc = self.L.tfrec_amd_read_bursts(self.h, None, 0, C.byref(nr))  # the count (no room: E_INVAL)
-        self.burst_total = int(nr.value)
-        if rc != E_INVAL or nr.value == 0:
-            _check(self.L, rc, ok=ok)
-            return np.zeros(0, dtype=BURST_DTYPE)
-        out = np.zeros(min(nr.value, getattr(self, "_capture", (0, 0))[0]), dtype=BURST_DTYPE)
-        _check(self.L, self.L.tfrec_amd_read_bursts(self.h, out.ctypes.data, len(out), C.byref(nr)), ok=ok)
-        return out
+        return self._read_run_records(self.L.tfrec_amd_read_bursts, BURST_DTYPE, "burst_total", allow_overflow)
 
     def enable_burst_envelope(self):
         """Turn the burst envelope on (tfrec_amd_enable_burst_envelope; after enable_capture, before the first submit; with or
@@ -667,16 +679,7 @@ class Receiver:
         that submit) -> an ENVELOPE_DTYPE array, one record per entry of that submit's run table (envelope.py).  They do not depend
         on the pool: a table with more than max_runs entries (E_OVERFLOW) raises unless allow_overflow, then its first max_runs
         records are returned; envelope_total holds the submit's true run count."""
-        ok = (E_OK, E_OVERFLOW) if allow_overflow else (E_OK,)
-        nr = C.c_uint32(0)
-        rc = self.L.tfrec_amd_read_burst_envelopes(self.h, None, 0, C.byref(nr))  # the count (no room: E_INVAL)
-        self.envelope_total = int(nr.value)
-        if rc != E_INVAL or nr.value == 0:
-            _check(self.L, rc, ok=ok)
-            return np.zeros(0, dtype=ENVELOPE_DTYPE)
-        out = np.zeros(min(nr.value, getattr(self, "_capture", (0, 0))[0]), dtype=ENVELOPE_DTYPE)
-        _check(self.L, self.L.tfrec_amd_read_burst_envelopes(self.h, out.ctypes.data, len(out), C.byref(nr)), ok=ok)
-        return out
+        return self._read_run_records(self.L.tfrec_amd_read_burst_envelopes, ENVELOPE_DTYPE, "envelope_total", allow_overflow)
 
     def enable_burst_clock(self):
         """Turn the burst clock on (tfrec_amd_enable_burst_clock; after enable_capture, before the first submit; with or without
@@ -688,16 +691,7 @@ class Receiver:
         submit) -> a CLOCK_DTYPE array, one record per entry of that submit's run table (clock.py).  They do not depend on the
         pool: a table with more than max_runs entries (E_OVERFLOW) raises unless allow_overflow, then its first max_runs records
         are returned; clock_total holds the submit's true run count."""
-        ok = (E_OK, E_OVERFLOW) if allow_overflow else (E_OK,)
-        nr = C.c_uint32(0)
-        rc = self.L.tfrec_amd_read_burst_clocks(self.h, None, 0, C.byref(nr))  # the count (no room: E_INVAL)
-        self.clock_total = int(nr.value)
-        if rc != E_INVAL or nr.value == 0:
-            _check(self.L, rc, ok=ok)
-            return np.zeros(0, dtype=CLOCK_DTYPE)
-        out = np.zeros(min(nr.value, getattr(self, "_capture", (0, 0))[0]), dtype=CLOCK_DTYPE)
-        _check(self.L, self.L.tfrec_amd_read_burst_clocks(self.h, out.ctypes.data, len(out), C.byref(nr)), ok=ok)
-        return out
+        return self._read_run_records(self.L.tfrec_amd_read_burst_clocks, CLOCK_DTYPE, "clock_total", allow_overflow)
 
     def enable_burst_track(self, smooth: int):
         """Turn the burst track on (tfrec_amd_enable_burst_track; after enable_capture, before the first submit; with or without
@@ -727,18 +721,7 @@ class Receiver:
         -> (a TRACK_DTYPE array, one record per entry of that submit's run table; the bitmap's uint32 words): track.bits_of(rec,
         words) is a record's track.  An overflowed table or pool (E_OVERFLOW) raises unless allow_overflow; then the records below
         max_runs and the words of the pairs read_captures delivers are returned.  track_total holds the submit's true run count."""
-        ok = (E_OK, E_OVERFLOW) if allow_overflow else (E_OK,)
-        nr, nw = C.c_uint32(0), C.c_uint64(0)
-        rc = self.L.tfrec_amd_read_burst_tracks(self.h, None, 0, C.byref(nr), None, 0, C.byref(nw))  # the counts (no room: E_INVAL)
-        self.track_total = int(nr.value)
-        if rc != E_INVAL or nr.value == 0:
-            _check(self.L, rc, ok=ok)
-            return np.zeros(0, dtype=TRACK_DTYPE), np.zeros(0, dtype=np.uint32)
-        out = np.zeros(min(nr.value, getattr(self, "_capture", (0, 0))[0]), dtype=TRACK_DTYPE)
-        words = np.zeros(int(nw.value), dtype=np.uint32)
-        _check(self.L, self.L.tfrec_amd_read_burst_tracks(self.h, out.ctypes.data, len(out), C.byref(nr),
-                                                          words.ctypes.data if len(words) else None, len(words), C.byref(nw)), ok=ok)
-        return out, words
+        return self._read_run_records(self.L.tfrec_amd_read_burst_tracks, TRACK_DTYPE, "track_total", allow_overflow, words=True)
 
     def enable_burst_sync(self, rate: int, pattern: int, n_bits: int, max_errors: int = 0, both: bool = False):
         """Turn the burst sync on (tfrec_amd_enable_burst_sync; after enable_burst_track, before the first submit): a bit per
@@ -755,18 +738,7 @@ class Receiver:
         """The sync of the OLDEST undrained submit (tfrec_amd_read_burst_syncs; call it before the drain that pops that submit)
         -> (a SYNC_DTYPE array, one record per entry of that submit's run table; the match bitmap's uint32 words): sync.bits_of(rec,
         words) is a record's match track.  Overflow as for read_burst_tracks.  sync_total holds the submit's true run count."""
-        ok = (E_OK, E_OVERFLOW) if allow_overflow else (E_OK,)
-        nr, nw = C.c_uint32(0), C.c_uint64(0)
-        rc = self.L.tfrec_amd_read_burst_syncs(self.h, None, 0, C.byref(nr), None, 0, C.byref(nw))  # the counts (no room: E_INVAL)
-        self.sync_total = int(nr.value)
-        if rc != E_INVAL or nr.value == 0:
-            _check(self.L, rc, ok=ok)
-            return np.zeros(0, dtype=SYNC_DTYPE), np.zeros(0, dtype=np.uint32)
-        out = np.zeros(min(nr.value, getattr(self, "_capture", (0, 0))[0]), dtype=SYNC_DTYPE)
-        words = np.zeros(int(nw.value), dtype=np.uint32)
-        _check(self.L, self.L.tfrec_amd_read_burst_syncs(self.h, out.ctypes.data, len(out), C.byref(nr),
-                                                         words.ctypes.data if len(words) else None, len(words), C.byref(nw)), ok=ok)
-        return out, words
+        return self._read_run_records(self.L.tfrec_amd_read_burst_syncs, SYNC_DTYPE, "sync_total", allow_overflow, words=True)
 
     def enable_runs_input(self, max_runs: int, max_samples: int):
         """Turn sparse submits on (tfrec_amd_enable_runs_input; decimated receivers, before the first submit): a submit_runs may

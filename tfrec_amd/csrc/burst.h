@@ -1,17 +1,24 @@
 // tfrec_amd/csrc/burst.h -- the burst meter (tfrec_amd_enable_burst_meter, include/tfrec_amd.h: tfrec_amd_burst): per
 // run of the recorder's table a histogram over 64 directions of the products z[k] conj(z[k-1]) of consecutive decimated samples,
-// their sums, the run's energy and its peak.  Two kernels behind capture_copy_kernel on the recorder's low-priority lane; they read
-// the recorder's table and working set, the decimated samples and prevdec, and nothing a demodulator owns.  Exact integers only:
-// every quantity is an integer sum or maximum, so the order of the atomics that combine the pieces cannot matter.  Included by
-// frontend.hip (inside namespace tfrec) behind capture.h.  tfrec_amd/burst.py restates the result.
+// their sums, the run's energy and its peak.  Two kernels (capture.h's run_records_init_kernel and burst_accum_kernel) behind
+// capture_copy_kernel on the recorder's low-priority lane; they read the recorder's table and working set, the decimated samples
+// and prevdec, and nothing a demodulator owns.  Exact integers only: every quantity is an integer sum or maximum, so the order of
+// the atomics that combine the pieces cannot matter.  Included by frontend.hip (inside namespace tfrec) behind capture.h.
+// tfrec_amd/burst.py restates the result.
 #pragma once
 
 static_assert(sizeof(tfrec_amd_burst) == 320 && offsetof(tfrec_amd_burst, pwr_max) == 24 && offsetof(tfrec_amd_burst, hist) == 56 &&
 		      offsetof(tfrec_amd_run, pool_offset) == 24,
-	      "burst_init_kernel copies a table entry's first 24 bytes and zeroes the rest");
+	      "the init kernel copies a table entry's first 24 bytes and zeroes the rest");
+// run_records_init_kernel's rule: the copied fields from the entry capture_copy_kernel wrote (its first 24 bytes are the record's),
+// everything else zero
+template <>
+__device__ inline uint32_t run_record_word<tfrec_amd_burst>(const uint32_t *src, int w)
+{
+	return w < 6 ? src[w] : 0u;
+}
 
 constexpr int kBurstThreads = 256;  // burst_accum_kernel: a workgroup per (stream, block), a sample per lane and step
-constexpr int kBurstWords = (int)(sizeof(tfrec_amd_burst) / 4);
 
 // The bin of a product: the j in 0..63 that maximises dot C[64 j] + crs S[64 j], the lowest on a tie.  Evaluated without the 64
 // scores.  The table is exact under a quarter turn -- C[64 (j + 16)] = -S[64 j], S[64 (j + 16)] = C[64 j], from C[-k] = C[k] and
@@ -65,32 +72,10 @@ __device__ inline int burst_bin(long long dot, long long crs)
 	return (16 * q + n) & 63;
 }
 
-// The records of the submit's table entries below max_runs: the copied fields from the entry capture_copy_kernel wrote (its first
-// 24 bytes are the record's), everything else zero.  A dword per lane.
-__global__ __launch_bounds__(256) void burst_init_kernel(const tfrec_amd_run *__restrict__ runs, const CaptureHeader *__restrict__ hdr,
-							  uint32_t max_runs, tfrec_amd_burst *__restrict__ out)
-{
-	const unsigned long long total = hdr->n_runs;
-	const size_t words = (size_t)(total < max_runs ? (uint32_t)total : max_runs) * kBurstWords;
-	for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) {
-		const size_t e = i / kBurstWords;
-		const int w = (int)(i - e * kBurstWords);
-		reinterpret_cast<uint32_t *>(out + e)[w] = w < 6 ? reinterpret_cast<const uint32_t *>(runs + e)[w] : 0u;
-	}
-}
-
-__device__ inline long long burst_wave_sum(long long v)
-{
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1)
-		v += __shfl_xor(v, d);
-	return v;
-}
-
 // Block blockIdx.x of stream blockIdx.y: the part inside the block of every run of the stream that meets it -> added to the run's
-// record.  The runs that meet the block are the index range [lo, hi) of the stream's staged runs, found as capture_copy_kernel
-// finds them; a run's part is walked in steps of kBurstThreads samples, a sample per lane, so a short run costs one step and a
-// stream that never leaves its window is spread over its blocks.  The product at sample n pairs it with sample n - 1: inside
+// record.  The runs that meet the block are the index range [lo, hi) of the stream's staged runs, found by capture_run_range; a
+// run's part is walked in steps of kBurstThreads samples, a sample per lane, so a short run costs one step and a stream that
+// never leaves its window is spread over its blocks.  The product at sample n pairs it with sample n - 1: inside
 // the row, or prevdec[s] at the submit's first sample; it is left out at a run's first sample unless the run CONTINUES (its
 // start is then the submit's first sample).  Products are formed in 64 bits: |dot|, |crs| <= 2^31 for any int16 pairs.
 // Per run and block: the histogram in LDS, sums and peak reduced over each wave and then in LDS; one round of integer atomics to
@@ -107,31 +92,20 @@ __global__ __launch_bounds__(kBurstThreads) void burst_accum_kernel(const uint32
 		return;
 	const CaptureStage *srow = stage + (size_t)s * stage_cap;
 	const unsigned long long e0 = base[s].x;  // the stream's first table entry
-	__shared__ int l_lo, l_hi, l_pmax;
+	__shared__ int l_pmax;
 	__shared__ uint32_t l_np, l_hist[64];
 	__shared__ unsigned long long l_sum[3];
 	if (t == 0)
-		l_lo = l_hi = l_pmax = 0;
+		l_pmax = 0;
 	if (t == 1)
 		l_np = 0;
 	if (t >= 2 && t < 5)
 		l_sum[t - 2] = 0;
 	if (t >= 64 && t < 128)
 		l_hist[t - 64] = 0;
-	__syncthreads();
 	const int b0 = b * kBlockDec, b1 = b0 + kBlockDec;
-	int lo = 0, hi = 0;
-	for (int k = t; k < nr; k += kBurstThreads) {
-		lo += srow[k].end <= b0;
-		hi += srow[k].start < b1;
-	}
-	if (lo)
-		atomicAdd(&l_lo, lo);
-	if (hi)
-		atomicAdd(&l_hi, hi);
-	__syncthreads();
-	lo = l_lo;
-	hi = l_hi;
+	int lo, hi;
+	capture_run_range(srow, nr, b0, b1, t, kBurstThreads, lo, hi);
 	const uint32_t *row = dec + (size_t)s * dec_stride;
 	for (int k = lo; k < hi; k++) {
 		if (e0 + (unsigned)k >= max_runs)
@@ -202,8 +176,7 @@ __global__ __launch_bounds__(kBurstThreads) void burst_accum_kernel(const uint32
 
 hipError_t launch_burst_meter(hipStream_t st, const FrontOut &o, const CaptureBufs &b, tfrec_amd_burst *out)
 {
-	const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>(1024, ((size_t)b.max_runs * kBurstWords + 255) / 256));
-	hipLaunchKernelGGL(burst_init_kernel, dim3(blocks), dim3(256), 0, st, b.runs, b.hdr, b.max_runs, out);
+	launch_run_records_init(st, b, out, nullptr);
 	hipLaunchKernelGGL(burst_accum_kernel, dim3(o.n_blocks, o.n_streams), dim3(kBurstThreads), 0, st, o.dec, o.dec_stride, o.n_blocks,
 			   o.prevdec, b.stage, b.stage_cap, b.cnt, b.base, b.max_runs, out);
 	return hipGetLastError();

@@ -88,42 +88,30 @@ struct CapturePre {
 	bool on = false;
 	uint32_t *d_pre[kSets] = {};
 };
-// tfrec_amd_enable_burst_meter: per set the record of every run of the set's table
-struct BurstMeter {
+// A burst stage on the recorder's table: per set the record of every run of the set's table.  The whole of the
+// meter's (tfrec_amd_enable_burst_meter, 6p), the envelope's (6r) and the clock's (6s) members; the base of the track's and the sync's
+template <class Rec>
+struct RunRecords {
 	bool on = false;
-	tfrec_amd_burst *d_recs[kSets] = {};
+	Rec *d_recs[kSets] = {};
 };
-// tfrec_amd_enable_burst_envelope: per set the record of every run of the set's table
-struct BurstEnvelope {
-	bool on = false;
-	tfrec_amd_envelope *d_recs[kSets] = {};
-};
-// tfrec_amd_enable_burst_clock: per set the record of every run of the set's table
-struct BurstClock {
-	bool on = false;
-	tfrec_amd_clock *d_recs[kSets] = {};
-};
-// tfrec_amd_enable_burst_track: L; every stream's centre index as the next submit uses it; per set the record of
-// every run of the set's table, the bitmap (ceil(max_samples / 32) words) and the submit's centre indices with their page-locked
+// tfrec_amd_enable_burst_track: L; every stream's centre index as the next submit uses it; per set the records
+// (RunRecords), the bitmap (ceil(max_samples / 32) words) and the submit's centre indices with their page-locked
 // source; per stream the carried last 16 pairs and chain position (track_carry_kernel)
-struct BurstTrack {
-	bool on = false;
+struct BurstTrack : RunRecords<tfrec_amd_track> {
 	int smooth = 0;
 	size_t n_words = 0;
 	std::vector<int32_t> idx;
-	tfrec_amd_track *d_recs[kSets] = {};
 	uint32_t *d_words[kSets] = {};
 	int32_t *d_idx[kSets] = {}, *h_idx[kSets] = {};
 	uint32_t *d_carry = nullptr, *d_prior = nullptr;
 };
-// tfrec_amd_enable_burst_sync: the settings; per set the record of every run of the set's table and the match
+// tfrec_amd_enable_burst_sync: the settings; per set the records (RunRecords) and the match
 // bitmap (the track's size); per stream the carried 64 words of track bits and H (sync_carry_kernel)
-struct BurstSync {
-	bool on = false;
+struct BurstSync : RunRecords<tfrec_amd_burst_sync> {
 	int rate = 0, n_bits = 0, max_errors = 0;
 	uint32_t flags = 0;
 	unsigned long long pattern = 0;
-	tfrec_amd_burst_sync *d_recs[kSets] = {};
 	uint32_t *d_words[kSets] = {};
 	uint32_t *d_carry = nullptr, *d_hist = nullptr;
 };
@@ -326,9 +314,9 @@ struct tfrec_amd_ctx {
 	LevelsOut lev;  // ---- side outputs
 	CaptureOut cap;
 	CapturePre cap_pre;
-	BurstMeter burst;
-	BurstEnvelope env;
-	BurstClock clk;
+	RunRecords<tfrec_amd_burst> burst;
+	RunRecords<tfrec_amd_envelope> env;
+	RunRecords<tfrec_amd_clock> clk;
 	BurstTrack trk;
 	BurstSync syn;
 	DecIn decin;

@@ -1,8 +1,9 @@
 // tfrec_amd/csrc/capture.h -- the squelched recorder (tfrec_amd_enable_capture, include/tfrec_amd.h: tfrec_amd_run):
 // the decimated IQ of every triggered sample, packed run by run, with a table that says where each run lay.  Three kernels behind
 // the front end, on a low-priority stream of their own; they read the decimated samples and the FINAL trigger mask, like the level
-// meter, and nothing a demodulator owns.  Included by frontend.hip (inside namespace tfrec); CaptureState and CaptureStage are
-// declared in tfrec_dev.h.  tfrec_amd/capture.py restates the result.
+// meter, and nothing a demodulator owns.  Also what the burst stages behind it (burst.h .. sync.h) share: the run lookup
+// (capture_run_range), the records' init kernel (run_records_init_kernel) and burst_wave_sum.  Included by frontend.hip (inside
+// namespace tfrec); CaptureState and CaptureStage are declared in tfrec_dev.h.  tfrec_amd/capture.py restates the result.
 //
 // A sample is captured while it lies within wmax samples after a trigger, the trigger's own sample included (level_trig_kernel's
 // `triggered`).  wmax >= 356 > 64, so within one 64-sample mask word the captured samples are [0, carried) -- what an earlier
@@ -29,6 +30,78 @@ __device__ inline int cap_prefix_excl(int v, int lane)  // exclusive prefix sum 
 			x += o;
 	}
 	return x - v;
+}
+
+__device__ inline long long burst_wave_sum(long long v)  // the sum over the wave's lanes, in every lane
+{
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1)
+		v += __shfl_xor(v, d);
+	return v;
+}
+
+// The run lookup of a (stream, block) workgroup, for capture_copy_kernel and every burst stage's kernel behind it.  The stream's nr
+// staged runs (srow) are sorted, so those that meet the block's samples [b0, b1) are the index range [lo, hi): lo = runs that end at
+// or before the block's first sample, hi = runs that start before its end -- two counts (integer sums: their order does not
+// matter), a strided share per lane, joined by two LDS atomics.  Called by all `threads` lanes of the workgroup; two barriers;
+// leaves lo and hi in every lane.  What else a kernel zeroes in LDS ahead of the call is in place behind the first barrier.
+__device__ inline void capture_run_range(const CaptureStage *__restrict__ srow, int nr, int b0, int b1, int lane, int threads, int &lo, int &hi)
+{
+	__shared__ int l_lo, l_hi;
+	if (lane == 0)
+		l_lo = l_hi = 0;
+	__syncthreads();
+	lo = hi = 0;
+	for (int k = lane; k < nr; k += threads) {
+		lo += srow[k].end <= b0;
+		hi += srow[k].start < b1;
+	}
+	if (lo)
+		atomicAdd(&l_lo, lo);
+	if (hi)
+		atomicAdd(&l_hi, hi);
+	__syncthreads();
+	lo = l_lo;
+	hi = l_hi;
+}
+
+// The records of a burst stage, one per table entry of the submit below max_runs: word w of a record is run_record_word<Rec>(src,
+// w), src being the dwords of the entry capture_copy_kernel wrote -- each stage states its rule next to its record's
+// static_assert.  With a bitmap (words != null) the zeroed words of the submit's pairs too, as far as the pool holds them.  A
+// dword per lane.
+template <class Rec>
+__device__ inline uint32_t run_record_word(const uint32_t *src, int w);
+template <class Rec>
+__global__ __launch_bounds__(256) void run_records_init_kernel(const tfrec_amd_run *__restrict__ runs, const CaptureHeader *__restrict__ hdr,
+								uint32_t max_runs, unsigned long long max_samples, Rec *__restrict__ out,
+								uint32_t *__restrict__ words)
+{
+	constexpr int kWords = (int)(sizeof(Rec) / 4);
+	const unsigned long long total = hdr->n_runs;
+	const size_t rw = (size_t)(total < max_runs ? (uint32_t)total : max_runs) * kWords;
+	size_t bw = 0;
+	if (words) {
+		const unsigned long long pairs = hdr->n_pairs < max_samples ? hdr->n_pairs : max_samples;
+		bw = (size_t)((pairs + 31) >> 5);
+	}
+	for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < rw + bw; i += (size_t)gridDim.x * 256) {
+		if (i >= rw) {
+			words[i - rw] = 0u;
+			continue;
+		}
+		const size_t e = i / kWords;
+		const int w = (int)(i - e * kWords);
+		reinterpret_cast<uint32_t *>(out + e)[w] = run_record_word<Rec>(reinterpret_cast<const uint32_t *>(runs + e), w);
+	}
+}
+
+// The init kernel's launch: as many workgroups as the records and the bitmap (max_samples bits, with words) have dwords, 1024 at the most
+template <class Rec>
+void launch_run_records_init(hipStream_t st, const CaptureBufs &b, Rec *out, uint32_t *words)
+{
+	const size_t dwords = (size_t)b.max_runs * (sizeof(Rec) / 4) + (words ? (size_t)((b.max_samples + 31) >> 5) : 0);
+	const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>(1024, (dwords + 255) / 256));
+	hipLaunchKernelGGL(run_records_init_kernel<Rec>, dim3(blocks), dim3(256), 0, st, b.runs, b.hdr, b.max_runs, b.max_samples, out, words);
 }
 
 // The runs of stream blockIdx.x in this submit -> stage[s * stage_cap + k] (submit-relative start and exclusive end, the
@@ -166,8 +239,7 @@ __global__ __launch_bounds__(64) void capture_offsets_kernel(const uint2 *__rest
 // stream's entries of the run table.  Capacity: a table entry is written only below max_runs, a run's pairs only when the whole
 // run ends at or below max_samples; both conditions are monotone in table order, so what is written is a prefix (the host
 // cuts it to whole runs that satisfy both).
-// The runs are sorted, so those that meet the block are the index range [lo, hi): lo = runs that end at or before the block's
-// first sample, hi = runs that start before its end -- two counts (integer sums: their order does not matter).  Each such run's
+// The runs that meet the block are the index range [lo, hi) of the stream's staged runs (capture_run_range).  Each such run's
 // part of the block is copied in steps of kCapTile source samples: one aligned 16-byte load per lane into LDS, then four
 // rounds in which consecutive lanes store consecutive pairs -- a wave writes 256 contiguous bytes of the pool, wherever the run
 // begins in it.  The loops are uniform over the workgroup.
@@ -200,24 +272,10 @@ __global__ __launch_bounds__(kCapThreads) void capture_copy_kernel(const uint32_
 			o.pool_offset = pool0 + r.rank;
 			runs[e] = o;
 		}
-	__shared__ int l_lo, l_hi;
 	__shared__ uint4 l_tile[kCapThreads];
-	if (t == 0)
-		l_lo = l_hi = 0;
-	__syncthreads();
 	const int b0 = b * kBlockDec, b1 = b0 + kBlockDec;
-	int lo = 0, hi = 0;
-	for (int k = t; k < nr; k += kCapThreads) {
-		lo += srow[k].end <= b0;
-		hi += srow[k].start < b1;
-	}
-	if (lo)
-		atomicAdd(&l_lo, lo);
-	if (hi)
-		atomicAdd(&l_hi, hi);
-	__syncthreads();
-	lo = l_lo;
-	hi = l_hi;
+	int lo, hi;
+	capture_run_range(srow, nr, b0, b1, t, kCapThreads, lo, hi);
 	const uint32_t *row = dec + (size_t)s * dec_stride;
 	const uint32_t *tile = reinterpret_cast<const uint32_t *>(l_tile);
 	for (int k = lo; k < hi; k++) {

@@ -1,40 +1,33 @@
 // tfrec_amd/csrc/clock.h -- the burst clock (tfrec_amd_enable_burst_clock, include/tfrec_amd.h: tfrec_amd_clock): per
 // run of the recorder's table the power spectrum, 128 bins of 375 Hz, of the second-order product of the decimated samples, summed
-// over the 1024-sample segments that lie wholly inside the run: it peaks at the symbol rate.  Two kernels behind the envelope's on
-// the recorder's low-priority lane; they read the recorder's table and working set and the decimated samples, and nothing a
-// demodulator owns -- not even prevdec: a segment reads its own 1024 pairs only.  Exact integers only: every combined quantity is an
-// integer sum, so the order of the atomics that combine the blocks cannot matter.  Included by frontend.hip (inside namespace tfrec)
-// behind envelope.h.  tfrec_amd/clock.py restates the result.
+// over the 1024-sample segments that lie wholly inside the run: it peaks at the symbol rate.  Two kernels (capture.h's
+// run_records_init_kernel and clock_accum_kernel) behind the envelope's on the recorder's low-priority lane; they read the
+// recorder's table and working set and the decimated samples, and nothing a demodulator owns -- not even prevdec: a segment reads
+// its own 1024 pairs only.  Exact integers only: every combined quantity is an integer sum, so the order of the atomics that
+// combine the blocks cannot matter.  Included by frontend.hip (inside namespace tfrec) behind envelope.h.  tfrec_amd/clock.py
+// restates the result.
 #pragma once
 
 static_assert(sizeof(tfrec_amd_clock) == 1056 && offsetof(tfrec_amd_clock, n_segments) == 24 && offsetof(tfrec_amd_clock, spec) == 32 &&
 		      offsetof(tfrec_amd_run, pool_offset) == 24,
-	      "clock_init_kernel copies a table entry's first 24 bytes and zeroes the rest");
+	      "the init kernel copies a table entry's first 24 bytes and zeroes the rest");
+// run_records_init_kernel's rule: the copied fields from the entry capture_copy_kernel wrote (its first 24 bytes are the record's),
+// everything else zero
+template <>
+__device__ inline uint32_t run_record_word<tfrec_amd_clock>(const uint32_t *src, int w)
+{
+	return w < 6 ? src[w] : 0u;
+}
 
 constexpr int kClockThreads = 256;  // clock_accum_kernel: a workgroup per (stream, block); two lanes per bin
-constexpr int kClockWords = (int)(sizeof(tfrec_amd_clock) / 4);
 constexpr int kClockSeg = 1024;  // samples per segment
 constexpr int kClockBins = 128;  // bins j = kClockBin0 .. kClockBin0 + 127
 constexpr int kClockBin0 = 4;
 static_assert(kBlockDec % kClockSeg == 0 && kClockSeg == 4 * kClockThreads && kClockThreads == 2 * kClockBins && kTuneN == 4096,
 	      "a block is 8 whole segments, a lane forms 4 products, and bin j steps 4 j entries of the 4096-entry table per sample");
 
-// The records of the submit's table entries below max_runs: the copied fields from the entry capture_copy_kernel wrote (its first
-// 24 bytes are the record's), everything else zero.  A dword per lane.
-__global__ __launch_bounds__(256) void clock_init_kernel(const tfrec_amd_run *__restrict__ runs, const CaptureHeader *__restrict__ hdr,
-							  uint32_t max_runs, tfrec_amd_clock *__restrict__ out)
-{
-	const unsigned long long total = hdr->n_runs;
-	const size_t words = (size_t)(total < max_runs ? (uint32_t)total : max_runs) * kClockWords;
-	for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) {
-		const size_t e = i / kClockWords;
-		const int w = (int)(i - e * kClockWords);
-		reinterpret_cast<uint32_t *>(out + e)[w] = w < 6 ? reinterpret_cast<const uint32_t *>(runs + e)[w] : 0u;
-	}
-}
-
-// Block blockIdx.x of stream blockIdx.y: for every run of the stream that meets the block (burst_accum_kernel's range [lo, hi) of
-// the staged runs), each of the block's 8 segments that lies wholly inside the run -> its spectrum, summed over the segments in
+// Block blockIdx.x of stream blockIdx.y: for every run of the stream that meets the block (capture_run_range's [lo, hi) of the
+// staged runs), each of the block's 8 segments that lies wholly inside the run -> its spectrum, summed over the segments in
 // registers (lane t < 128 owns bin 4 + t) and added to the run's record in one round of 64-bit atomics.  Per segment:
 //   1. the 1024 pairs into LDS, 4 per lane (m' = t, t + 256, ...);
 //   2. dot, crs of m' >= 1 in 64 bits (|.| <= 2^31), their largest magnitude over the wave by shuffles and over the workgroup in LDS;
@@ -57,29 +50,15 @@ __global__ __launch_bounds__(kClockThreads) void clock_accum_kernel(const uint32
 		return;
 	const CaptureStage *srow = stage + (size_t)s * stage_cap;
 	const unsigned long long e0 = base[s].x;  // the stream's first table entry
-	__shared__ int l_lo, l_hi;
 	__shared__ uint32_t l_mx;
 	__shared__ uint32_t l_tab[kClockSeg];   // (C[4 k], S[4 k]) as int16 halves: the entries (4 j m') mod 4096 can reach
 	__shared__ uint32_t l_z[kClockSeg];     // the segment's pairs
 	__shared__ uint32_t l_dc[kClockSeg];    // (d, c) as int16 halves
 	__shared__ __attribute__((aligned(4))) int16_t l_g[kClockSeg];
 	__shared__ long long l_part[2][kClockBins][2];
-	if (t == 0)
-		l_lo = l_hi = 0;
-	__syncthreads();
 	const int b0 = b * kBlockDec, b1 = b0 + kBlockDec;
-	int lo = 0, hi = 0;
-	for (int k = t; k < nr; k += kClockThreads) {
-		lo += srow[k].end <= b0;
-		hi += srow[k].start < b1;
-	}
-	if (lo)
-		atomicAdd(&l_lo, lo);
-	if (hi)
-		atomicAdd(&l_hi, hi);
-	__syncthreads();
-	lo = l_lo;
-	hi = l_hi;
+	int lo, hi;
+	capture_run_range(srow, nr, b0, b1, t, kClockThreads, lo, hi);
 	if (lo >= hi)
 		return;
 	for (int i = t; i < kClockSeg; i += kClockThreads)
@@ -191,8 +170,7 @@ __global__ __launch_bounds__(kClockThreads) void clock_accum_kernel(const uint32
 
 hipError_t launch_burst_clock(hipStream_t st, const FrontOut &o, const CaptureBufs &b, tfrec_amd_clock *out)
 {
-	const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>(1024, ((size_t)b.max_runs * kClockWords + 255) / 256));
-	hipLaunchKernelGGL(clock_init_kernel, dim3(blocks), dim3(256), 0, st, b.runs, b.hdr, b.max_runs, out);
+	launch_run_records_init(st, b, out, nullptr);
 	hipLaunchKernelGGL(clock_accum_kernel, dim3(o.n_blocks, o.n_streams), dim3(kClockThreads), 0, st, o.dec, o.dec_stride, o.n_blocks,
 			   b.stage, b.stage_cap, b.cnt, b.base, b.max_runs, out);
 	return hipGetLastError();

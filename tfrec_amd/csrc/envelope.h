@@ -1,39 +1,29 @@
 // tfrec_amd/csrc/envelope.h -- the burst envelope (tfrec_amd_enable_burst_envelope, include/tfrec_amd.h: tfrec_amd_envelope; DESIGN.md
 // 6r): per run of the recorder's table the over samples' count and last index, the gaps between them, and the energy and product
-// sums split at the last over sample.  Three kernels behind capture_copy_kernel (and the burst meter's) on the recorder's
-// low-priority lane; they read the recorder's table and working set, the decimated samples, prevdec and the FINAL trigger mask, and
-// nothing a demodulator owns.  Exact integers only: every combined quantity is an integer sum, count, maximum or minimum, so the
-// order of the atomics cannot matter.  Included by frontend.hip (inside namespace tfrec) behind burst.h.  tfrec_amd/envelope.py
-// restates the result.
+// sums split at the last over sample.  Three kernels (capture.h's run_records_init_kernel and the two passes) behind
+// capture_copy_kernel (and the burst meter's) on the recorder's low-priority lane; they read the recorder's table and working set,
+// the decimated samples, prevdec and the FINAL trigger mask, and nothing a demodulator owns.  Exact integers only: every combined
+// quantity is an integer sum, count, maximum or minimum, so the order of the atomics cannot matter.  Included by frontend.hip
+// (inside namespace tfrec) behind burst.h.  tfrec_amd/envelope.py restates the result.
 #pragma once
 
 static_assert(sizeof(tfrec_amd_envelope) == 128 && offsetof(tfrec_amd_envelope, n_over) == 24 && offsetof(tfrec_amd_envelope, last_over) == 28 &&
 		      offsetof(tfrec_amd_envelope, energy_head) == 32 && offsetof(tfrec_amd_envelope, lead_not_over) == 56 &&
 		      offsetof(tfrec_amd_envelope, dot_head) == 64 && offsetof(tfrec_amd_envelope, nprod_tail) == 96,
-	      "envelope_init_kernel writes the record by dwords; envelope_accum_kernel takes the four product sums as one array");
+	      "the init kernel writes the record by dwords; envelope_accum_kernel takes the four product sums as one array");
+// run_records_init_kernel's rule: the copied fields from the entry capture_copy_kernel wrote (its first 24 bytes are the record's),
+// last_over = -1, lead_not_over = n_samples -- what a piece without an over sample keeps --, everything else zero
+template <>
+__device__ inline uint32_t run_record_word<tfrec_amd_envelope>(const uint32_t *src, int w)
+{
+	return w < 6 ? src[w] : w == 7 ? 0xffffffffu : w == 14 ? src[4] : 0u;
+}
 
 constexpr int kEnvMaskThreads = kCapMaskWords;  // envelope_mask_kernel: a workgroup per (stream, block), a mask word per lane
 constexpr int kEnvThreads = 256;                // envelope_accum_kernel: a sample per lane and step
-constexpr int kEnvWords = (int)(sizeof(tfrec_amd_envelope) / 4);
-
-// The records of the submit's table entries below max_runs: the copied fields from the entry capture_copy_kernel wrote (its first
-// 24 bytes are the record's), last_over = -1, lead_not_over = n_samples -- what a piece without an over sample keeps --,
-// everything else zero.  A dword per lane.
-__global__ __launch_bounds__(256) void envelope_init_kernel(const tfrec_amd_run *__restrict__ runs, const CaptureHeader *__restrict__ hdr,
-							     uint32_t max_runs, tfrec_amd_envelope *__restrict__ out)
-{
-	const unsigned long long total = hdr->n_runs;
-	const size_t words = (size_t)(total < max_runs ? (uint32_t)total : max_runs) * kEnvWords;
-	for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (size_t)gridDim.x * 256) {
-		const size_t e = i / kEnvWords;
-		const int w = (int)(i - e * kEnvWords);
-		const uint32_t *src = reinterpret_cast<const uint32_t *>(runs + e);
-		reinterpret_cast<uint32_t *>(out + e)[w] = w < 6 ? src[w] : w == 7 ? 0xffffffffu : w == 14 ? src[4] : 0u;
-	}
-}
 
 // Pass A.  Block blockIdx.x of stream blockIdx.y, from the mask words alone: for every run of the stream that meets the block
-// (the index range [lo, hi) of the staged runs, found as capture_copy_kernel finds them) the words of the run's part of the block,
+// (the index range [lo, hi) of the staged runs, found by capture_run_range) the words of the run's part of the block,
 // a word per lane, cut to the run's samples ->
 //   n_over         the words' popcounts, added;
 //   last_over      the run-relative index of the part's highest bit, an atomic maximum;
@@ -57,23 +47,9 @@ __global__ __launch_bounds__(kEnvMaskThreads) void envelope_mask_kernel(const un
 		return;
 	const CaptureStage *srow = stage + (size_t)s * stage_cap;
 	const unsigned long long e0 = base[s].x;  // the stream's first table entry
-	__shared__ int l_lo, l_hi;
-	if (t == 0)
-		l_lo = l_hi = 0;
-	__syncthreads();
 	const int b0 = b * kBlockDec, b1 = b0 + kBlockDec;
-	int lo = 0, hi = 0;
-	for (int k = t; k < nr; k += kEnvMaskThreads) {
-		lo += srow[k].end <= b0;
-		hi += srow[k].start < b1;
-	}
-	if (lo)
-		atomicAdd(&l_lo, lo);
-	if (hi)
-		atomicAdd(&l_hi, hi);
-	__syncthreads();
-	lo = l_lo;
-	hi = l_hi;
+	int lo, hi;
+	capture_run_range(srow, nr, b0, b1, t, kEnvMaskThreads, lo, hi);
 	const unsigned long long *mrow = mask + (size_t)s * mask_stride;
 	for (int k = lo; k < hi; k++) {
 		if (e0 + (unsigned)k >= max_runs)
@@ -160,29 +136,15 @@ __global__ __launch_bounds__(kEnvThreads) void envelope_accum_kernel(const uint3
 		return;
 	const CaptureStage *srow = stage + (size_t)s * stage_cap;
 	const unsigned long long e0 = base[s].x;
-	__shared__ int l_lo, l_hi;
 	__shared__ uint32_t l_np[2];
 	__shared__ unsigned long long l_sum[6];  // energy head, tail; dot head, crs head, dot tail, crs tail
-	if (t == 0)
-		l_lo = l_hi = 0;
 	if (t >= 2 && t < 4)
 		l_np[t - 2] = 0;
 	if (t >= 4 && t < 10)
 		l_sum[t - 4] = 0;
-	__syncthreads();
 	const int b0 = b * kBlockDec, b1 = b0 + kBlockDec;
-	int lo = 0, hi = 0;
-	for (int k = t; k < nr; k += kEnvThreads) {
-		lo += srow[k].end <= b0;
-		hi += srow[k].start < b1;
-	}
-	if (lo)
-		atomicAdd(&l_lo, lo);
-	if (hi)
-		atomicAdd(&l_hi, hi);
-	__syncthreads();
-	lo = l_lo;
-	hi = l_hi;
+	int lo, hi;
+	capture_run_range(srow, nr, b0, b1, t, kEnvThreads, lo, hi);
 	const uint32_t *row = dec + (size_t)s * dec_stride;
 	for (int k = lo; k < hi; k++) {
 		if (e0 + (unsigned)k >= max_runs)
@@ -246,8 +208,7 @@ __global__ __launch_bounds__(kEnvThreads) void envelope_accum_kernel(const uint3
 
 hipError_t launch_burst_envelope(hipStream_t st, const FrontOut &o, const CaptureBufs &b, tfrec_amd_envelope *out)
 {
-	const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>(1024, ((size_t)b.max_runs * kEnvWords + 255) / 256));
-	hipLaunchKernelGGL(envelope_init_kernel, dim3(blocks), dim3(256), 0, st, b.runs, b.hdr, b.max_runs, out);
+	launch_run_records_init(st, b, out, nullptr);
 	hipLaunchKernelGGL(envelope_mask_kernel, dim3(o.n_blocks, o.n_streams), dim3(kEnvMaskThreads), 0, st, o.mask, o.mask_stride, b.stage,
 			   b.stage_cap, b.cnt, b.base, b.max_runs, out);
 	hipLaunchKernelGGL(envelope_accum_kernel, dim3(o.n_blocks, o.n_streams), dim3(kEnvThreads), 0, st, o.dec, o.dec_stride, o.prevdec, b.stage,

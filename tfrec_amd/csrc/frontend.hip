@@ -841,12 +841,13 @@ hipError_t launch_fmdev(hipStream_t st, const FrontOut &o, EventBuf *eb, int wma
 #include "formats.h"   // resample_fmt_kernel, ingest_kernel, launch_resample, launch_ingest
 #include "correct.h"   // correct_sums_kernel, correct_estimate_kernel, correct_apply_kernel, launch_correct
 #include "levels.h"    // level_sum_kernel, level_trig_kernel, launch_levels
-#include "capture.h"   // capture_scan_kernel, capture_offsets_kernel, capture_copy_kernel, launch_capture
-#include "burst.h"     // burst_init_kernel, burst_accum_kernel, launch_burst_meter
-#include "envelope.h"  // envelope_init_kernel, envelope_mask_kernel, envelope_accum_kernel, launch_burst_envelope
-#include "clock.h"     // clock_init_kernel, clock_accum_kernel, launch_burst_clock
-#include "track.h"     // track_init_kernel, track_kernel, track_carry_kernel, launch_burst_track
-#include "sync.h"      // sync_init_kernel, sync_kernel, sync_carry_kernel, launch_burst_sync
+#include "capture.h"   // capture_scan_kernel, capture_offsets_kernel, capture_copy_kernel, launch_capture; for the burst stages
+                       // capture_run_range, run_records_init_kernel<Rec>, burst_wave_sum
+#include "burst.h"     // burst_accum_kernel, launch_burst_meter
+#include "envelope.h"  // envelope_mask_kernel, envelope_accum_kernel, launch_burst_envelope
+#include "clock.h"     // clock_accum_kernel, launch_burst_clock
+#include "track.h"     // track_kernel, track_carry_kernel, launch_burst_track
+#include "sync.h"      // sync_kernel, sync_carry_kernel, launch_burst_sync
 #include "spectrum.h"  // spectrum_kernel, launch_spectrum
 #include "occupancy.h"  // occupancy_kernel, launch_occupancy
 #include "decin.h"     // decin_kernel, capture_pre_kernel and their launchers

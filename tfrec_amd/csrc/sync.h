@@ -1,19 +1,27 @@
 // tfrec_amd/csrc/sync.h -- the burst sync (tfrec_amd_enable_burst_sync, include/tfrec_amd.h: tfrec_amd_burst_sync): per
 // captured sample of every run of the recorder's table one bit, 1 where the burst track read at P symbol centres that end at the
 // sample is the sync word but for at most E places, packed where the track's bit lies; per run a 48-byte record.  Three kernels
-// behind the track's on the recorder's low-priority lane; they read the recorder's table and working set, the track's bitmap of
-// the same set -- complete: track_kernel has ended -- and the 2048 track bits and H they carried themselves.  Integers only: the
-// bits are joined by OR on a zeroed bitmap, n_hits is a sum and (best, best_at) one 64-bit minimum, so the order of the atomics
-// cannot matter.  The distances are counted bit-sliced: 32 samples a lane, eight planes (the form DESIGN.md 6u records).  Included
-// by frontend.hip (inside namespace tfrec) behind track.h.  tfrec_amd/sync.py restates the result.
+// (capture.h's run_records_init_kernel, sync_kernel, sync_carry_kernel) behind the track's on the recorder's low-priority lane;
+// they read the recorder's table and working set, the track's bitmap of the same set -- complete: track_kernel has ended -- and
+// the 2048 track bits and H they carried themselves.  Integers only: the bits are joined by OR on a zeroed bitmap, n_hits is a sum
+// and (best, best_at) one 64-bit minimum, so the order of the atomics cannot matter.  The distances are counted bit-sliced: 32
+// samples a lane, eight planes (the form DESIGN.md 6u records).  Included by frontend.hip (inside namespace tfrec) behind track.h.
+// tfrec_amd/sync.py restates the result.
 #pragma once
 
 static_assert(sizeof(tfrec_amd_burst_sync) == 48 && offsetof(tfrec_amd_burst_sync, bit_offset) == 24 && offsetof(tfrec_amd_burst_sync, n_hits) == 32 &&
 		      offsetof(tfrec_amd_burst_sync, best) == 36 && offsetof(tfrec_amd_burst_sync, best_at) == 40 && offsetof(tfrec_amd_burst_sync, reserved) == 44,
-	      "sync_init_kernel copies a table entry's 32 bytes; sync_kernel keeps (best << 32) | best_at in the record's last 8 bytes");
+	      "the init kernel copies a table entry's 32 bytes; sync_kernel keeps (best << 32) | best_at in the record's last 8 bytes");
+// run_records_init_kernel's rule -- the entry's 32 bytes (its first 24 and its pool_offset), n_hits = 0, best = 0xffffffff and the
+// 64-bit minimum's start, all ones, in the last 8 bytes (sync_carry_kernel turns them into best_at and the reserved 0) --; it zeroes
+// the match bitmap too
+template <>
+__device__ inline uint32_t run_record_word<tfrec_amd_burst_sync>(const uint32_t *src, int w)
+{
+	return w < 8 ? src[w] : w == 8 ? 0u : 0xffffffffu;
+}
 
 constexpr int kSyncThreads = 256;  // sync_kernel: a workgroup per (stream, block), 32 consecutive samples -- one word -- per lane
-constexpr int kSyncWords = (int)(sizeof(tfrec_amd_burst_sync) / 4);
 constexpr int kSyncHist = 2047;       // the track bits ahead of a sample that a distance may need: the largest span
 constexpr int kSyncCarryWords = 64;   // per stream: bit c of the carried words is t[c - 2048] of the piece that continues the chain
 constexpr int kSyncCarryBits = 32 * kSyncCarryWords;
@@ -53,29 +61,8 @@ __device__ inline uint32_t sync_chain_word(int k0, bool cont, const uint32_t *__
 	return v;
 }
 
-// The records of the submit's table entries below max_runs -- the entry's 32 bytes (its first 24 and its pool_offset), n_hits = 0,
-// best = 0xffffffff and the 64-bit minimum's start, all ones, in the last 8 bytes (sync_carry_kernel turns them into best_at and
-// the reserved 0) -- and the zeroed words of the submit's pairs, as far as the pool holds them.  A dword per lane.
-__global__ __launch_bounds__(256) void sync_init_kernel(const tfrec_amd_run *__restrict__ runs, const CaptureHeader *__restrict__ hdr,
-							 uint32_t max_runs, unsigned long long max_samples, tfrec_amd_burst_sync *__restrict__ out,
-							 uint32_t *__restrict__ words)
-{
-	const unsigned long long total = hdr->n_runs, pairs = hdr->n_pairs < max_samples ? hdr->n_pairs : max_samples;
-	const size_t rw = (size_t)(total < max_runs ? (uint32_t)total : max_runs) * kSyncWords;
-	const size_t bw = (size_t)((pairs + 31) >> 5);
-	for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < rw + bw; i += (size_t)gridDim.x * 256) {
-		if (i >= rw) {
-			words[i - rw] = 0u;
-			continue;
-		}
-		const size_t e = i / kSyncWords;
-		const int w = (int)(i - e * kSyncWords);
-		reinterpret_cast<uint32_t *>(out + e)[w] = w < 8 ? reinterpret_cast<const uint32_t *>(runs + e)[w] : w == 8 ? 0u : 0xffffffffu;
-	}
-}
-
-// Block blockIdx.x of stream blockIdx.y, with track_kernel's geometry and run lookup: for every run of the stream that meets the
-// block (the range [lo, hi) of the staged runs) and fits the pool, the match track of the run's part of the block.
+// Block blockIdx.x of stream blockIdx.y, with track_kernel's geometry and capture_run_range's lookup: for every run of the stream
+// that meets the block (the range [lo, hi) of the staged runs) and fits the pool, the match track of the run's part of the block.
 //   1. LDS word i holds the chain's bits at the submit-relative samples b0 - 2048 + 32 i .. + 31 (sync_chain_word: the track's
 //      bitmap where they lie in this submit -- a run's pool region is contiguous --, the carried words ahead of it), as far as a
 //      distance of the block's part can need them; 321 words.
@@ -103,7 +90,6 @@ __global__ __launch_bounds__(kSyncThreads) void sync_kernel(const CaptureStage *
 	const uint4 bs = base[s];
 	const uint32_t e0 = bs.x;  // the stream's first table entry
 	const unsigned long long pool0 = (unsigned long long)bs.z | ((unsigned long long)bs.w << 32);
-	__shared__ int l_lo, l_hi;
 	__shared__ uint32_t l_hits;
 	__shared__ unsigned long long l_best;
 	__shared__ int l_delta[64];
@@ -112,7 +98,6 @@ __global__ __launch_bounds__(kSyncThreads) void sync_kernel(const CaptureStage *
 								   // loop-invariant masks do not sit in scalar registers
 	__shared__ uint32_t l_t[kSyncLds];
 	if (t == 0) {
-		l_lo = l_hi = 0;
 		l_hits = 0;
 		l_best = ~0ull;
 	}
@@ -123,20 +108,9 @@ __global__ __launch_bounds__(kSyncThreads) void sync_kernel(const CaptureStage *
 	}
 	if (t < P)
 		l_delta[t] = (int)((768000u * (unsigned)t + (unsigned)rate) / (2u * (unsigned)rate));  // (below 2^26)
-	__syncthreads();
 	const int b0 = b * kBlockDec, b1 = b0 + kBlockDec;
-	int lo = 0, hi = 0;
-	for (int k = t; k < nr; k += kSyncThreads) {
-		lo += srow[k].end <= b0;
-		hi += srow[k].start < b1;
-	}
-	if (lo)
-		atomicAdd(&l_lo, lo);
-	if (hi)
-		atomicAdd(&l_hi, hi);
-	__syncthreads();
-	lo = l_lo;
-	hi = l_hi;
+	int lo, hi;
+	capture_run_range(srow, nr, b0, b1, t, kSyncThreads, lo, hi);
 	if (lo >= hi)
 		return;
 	const size_t nw = (size_t)((max_samples + 31) >> 5);
@@ -314,9 +288,7 @@ __global__ __launch_bounds__(kSyncCarryWords) void sync_carry_kernel(int n_block
 
 hipError_t launch_burst_sync(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const SyncBufs &k)
 {
-	const size_t dwords = (size_t)b.max_runs * kSyncWords + (size_t)((b.max_samples + 31) >> 5);
-	const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>(1024, (dwords + 255) / 256));
-	hipLaunchKernelGGL(sync_init_kernel, dim3(blocks), dim3(256), 0, st, b.runs, b.hdr, b.max_runs, b.max_samples, k.recs, k.words);
+	launch_run_records_init(st, b, k.recs, k.words);
 	hipLaunchKernelGGL(sync_kernel, dim3(o.n_blocks, o.n_streams), dim3(kSyncThreads), 0, st, b.stage, b.stage_cap, b.cnt, b.base, b.max_runs,
 			   b.max_samples, k.track, k.carry, k.hist, k.rate, k.n_bits, k.max_errors, k.flags, k.pattern, k.recs, k.words);
 	hipLaunchKernelGGL(sync_carry_kernel, dim3(o.n_streams), dim3(kSyncCarryWords), 0, st, o.n_blocks, b.stage, b.stage_cap, b.cnt, b.base,

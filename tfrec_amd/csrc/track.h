@@ -1,19 +1,25 @@
 // tfrec_amd/csrc/track.h -- the burst track (tfrec_amd_enable_burst_track, include/tfrec_amd.h: tfrec_amd_track): per
 // captured sample of every run of the recorder's table one bit, the sign of a quadrature discriminator about the stream's centre,
 // boxcar-smoothed over L products, packed where the sample's pair lies in the pool; per run a 40-byte record.  Three kernels
-// behind the clock's on the recorder's low-priority lane; they read the recorder's table and working set, the decimated samples,
-// the FINAL trigger mask and the 16 pairs and the chain position they carried themselves, and nothing a demodulator owns -- not
-// even prevdec.  Exact integers only: the bits are joined by OR on a zeroed bitmap, n_ones is a sum and last_over a maximum, so
-// the order of the atomics cannot matter.  Included by frontend.hip (inside namespace tfrec) behind clock.h.  tfrec_amd/track.py
-// restates the result.
+// (capture.h's run_records_init_kernel, track_kernel, track_carry_kernel) behind the clock's on the recorder's low-priority lane;
+// they read the recorder's table and working set, the decimated samples, the FINAL trigger mask and the 16 pairs and the chain
+// position they carried themselves, and nothing a demodulator owns -- not even prevdec.  Exact integers only: the bits are joined
+// by OR on a zeroed bitmap, n_ones is a sum and last_over a maximum, so the order of the atomics cannot matter.  Included by
+// frontend.hip (inside namespace tfrec) behind clock.h.  tfrec_amd/track.py restates the result.
 #pragma once
 
 static_assert(sizeof(tfrec_amd_track) == 40 && offsetof(tfrec_amd_track, bit_offset) == 24 && offsetof(tfrec_amd_track, last_over) == 32 &&
 		      offsetof(tfrec_amd_track, n_ones) == 36 && offsetof(tfrec_amd_run, pool_offset) == 24 && sizeof(tfrec_amd_run) == 32,
-	      "track_init_kernel copies a table entry's 32 bytes: its first 24 and its pool_offset");
+	      "the init kernel copies a table entry's 32 bytes: its first 24 and its pool_offset");
+// run_records_init_kernel's rule -- the entry's 32 bytes (its first 24 and its pool_offset), last_over = -1, n_ones = 0 --; it zeroes
+// the track's bitmap too
+template <>
+__device__ inline uint32_t run_record_word<tfrec_amd_track>(const uint32_t *src, int w)
+{
+	return w < 8 ? src[w] : w == 8 ? 0xffffffffu : 0u;
+}
 
 constexpr int kTrackThreads = 256;  // track_kernel: a workgroup per (stream, block), 32 consecutive samples -- one word -- per lane
-constexpr int kTrackWords = (int)(sizeof(tfrec_amd_track) / 4);
 constexpr int kTrackAhead = 16;  // the pairs kept ahead of a block: the largest L
 constexpr int kTrackSlots = kBlockDec + kTrackAhead;
 static_assert(kBlockDec == 32 * kTrackThreads && kTuneN == 4096, "a lane builds one word; the centre's index is one of 4096");
@@ -23,28 +29,8 @@ static_assert(kBlockDec == 32 * kTrackThreads && kTuneN == 4096, "a lane builds 
 __device__ inline int track_slot(int q) { return q + (q >> 5); }
 constexpr int kTrackLds = kTrackSlots + (kTrackSlots >> 5) + 1;
 
-// The records of the submit's table entries below max_runs -- the entry's 32 bytes (its first 24 and its pool_offset), last_over
-// = -1, n_ones = 0 -- and the zeroed words of the submit's pairs, as far as the pool holds them.  A dword per lane.
-__global__ __launch_bounds__(256) void track_init_kernel(const tfrec_amd_run *__restrict__ runs, const CaptureHeader *__restrict__ hdr,
-							  uint32_t max_runs, unsigned long long max_samples, tfrec_amd_track *__restrict__ out,
-							  uint32_t *__restrict__ words)
-{
-	const unsigned long long total = hdr->n_runs, pairs = hdr->n_pairs < max_samples ? hdr->n_pairs : max_samples;
-	const size_t rw = (size_t)(total < max_runs ? (uint32_t)total : max_runs) * kTrackWords;
-	const size_t bw = (size_t)((pairs + 31) >> 5);
-	for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < rw + bw; i += (size_t)gridDim.x * 256) {
-		if (i >= rw) {
-			words[i - rw] = 0u;
-			continue;
-		}
-		const size_t e = i / kTrackWords;
-		const int w = (int)(i - e * kTrackWords);
-		reinterpret_cast<uint32_t *>(out + e)[w] = w < 8 ? reinterpret_cast<const uint32_t *>(runs + e)[w] : w == 8 ? 0xffffffffu : 0u;
-	}
-}
-
-// Block blockIdx.x of stream blockIdx.y, with burst_accum_kernel's geometry and run lookup: for every run of the stream that meets
-// the block (the range [lo, hi) of the staged runs) the track of the run's part of the block.
+// Block blockIdx.x of stream blockIdx.y, with burst_accum_kernel's geometry and capture_run_range's lookup: for every run of the
+// stream that meets the block (the range [lo, hi) of the staged runs) the track of the run's part of the block.
 //   1. The block's 8192 pairs and the 16 ahead of it into LDS, coalesced: the 16 are the row's own, or for block 0 the stream's
 //      carried ones (track_carry_kernel).  A block without a run ends before that.
 //   2. Lane t owns the samples [b0 + 32 t, b0 + 32 t + 32).  With cf = the chain's first sample, submit-relative (the run's start,
@@ -73,28 +59,16 @@ __global__ __launch_bounds__(kTrackThreads) void track_kernel(const uint32_t *__
 	const uint4 bs = base[s];
 	const unsigned long long e0 = bs.x;  // the stream's first table entry
 	const unsigned long long pool0 = (unsigned long long)bs.z | ((unsigned long long)bs.w << 32);
-	__shared__ int l_lo, l_hi, l_last;
+	__shared__ int l_last;
 	__shared__ uint32_t l_ones;
 	__shared__ uint32_t l_z[kTrackLds];
 	if (t == 0) {
-		l_lo = l_hi = 0;
 		l_last = -1;
 		l_ones = 0;
 	}
-	__syncthreads();
 	const int b0 = b * kBlockDec, b1 = b0 + kBlockDec;
-	int lo = 0, hi = 0;
-	for (int k = t; k < nr; k += kTrackThreads) {
-		lo += srow[k].end <= b0;
-		hi += srow[k].start < b1;
-	}
-	if (lo)
-		atomicAdd(&l_lo, lo);
-	if (hi)
-		atomicAdd(&l_hi, hi);
-	__syncthreads();
-	lo = l_lo;
-	hi = l_hi;
+	int lo, hi;
+	capture_run_range(srow, nr, b0, b1, t, kTrackThreads, lo, hi);
 	if (lo >= hi)
 		return;
 	const uint32_t *row = dec + (size_t)s * dec_stride;
@@ -210,9 +184,7 @@ __global__ __launch_bounds__(256) void track_carry_kernel(const uint32_t *__rest
 
 hipError_t launch_burst_track(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k)
 {
-	const size_t dwords = (size_t)b.max_runs * kTrackWords + (size_t)((b.max_samples + 31) >> 5);
-	const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>(1024, (dwords + 255) / 256));
-	hipLaunchKernelGGL(track_init_kernel, dim3(blocks), dim3(256), 0, st, b.runs, b.hdr, b.max_runs, b.max_samples, k.recs, k.words);
+	launch_run_records_init(st, b, k.recs, k.words);
 	hipLaunchKernelGGL(track_kernel, dim3(o.n_blocks, o.n_streams), dim3(kTrackThreads), 0, st, o.dec, o.dec_stride, o.mask, o.mask_stride,
 			   b.stage, b.stage_cap, b.cnt, b.base, b.max_runs, b.max_samples, k.centre, k.carry, k.prior, k.smooth, k.recs, k.words);
 	hipLaunchKernelGGL(track_carry_kernel, dim3((o.n_streams + 256 / kTrackAhead - 1) / (256 / kTrackAhead)), dim3(256), 0, st, o.dec,

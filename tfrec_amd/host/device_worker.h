@@ -50,9 +50,11 @@ private:
 	int submit_runs(size_t k);
 	int collect(size_t k, batch_result &b);
 	int read_captures(size_t k, batch_result &b);
-	int read_bursts(size_t k, batch_result &b);
-	int read_envelopes(size_t k, batch_result &b);
-	int read_clocks(size_t k, batch_result &b);
+	template <class R>
+	int read_run_records(size_t k, int (*reader)(tfrec_amd_ctx *, R *, size_t, uint32_t *), const char *noun, bool cut_opens, std::vector<R> &recs);
+	template <class R>
+	int read_run_bitmaps(int (*reader)(tfrec_amd_ctx *, R *, size_t, uint32_t *, uint32_t *, size_t, uint64_t *), std::vector<R> &recs,
+			     std::vector<uint32_t> &words);
 	int read_tracks(size_t k, batch_result &b);
 	typedef int (*estimate_reader)(tfrec_amd_ctx *, int32_t, int16_t *, size_t, int *);
 	int read_last_estimate(size_t k, estimate_reader reader, std::vector<int> &files, std::vector<int16_t> &last);
@@ -531,167 +533,80 @@ inline int device_worker::read_captures(size_t k, batch_result &b)
 	return 0;
 }
 
-// -M: the batch's burst records.  stream -> file, as for the events; a record that begins behind its file's end is dropped, one that
-// reaches over it has its n_samples cut there (its sums are the device's: the padding is silence)
-inline int device_worker::read_bursts(size_t k, batch_result &b)
+// -M, -Q, -C: the batch's records of one burst stage by the stage's reader: the count, then the records; an overflow is reported and
+// the job goes on.  Then stream -> file, as for the events, and the file-end cut (job.h: cut_at_file_end): a record that begins
+// behind its file's end is dropped, one that reaches over it has its n_samples cut there and, but for -M, is OPEN
+template <class R>
+inline int device_worker::read_run_records(size_t k, int (*reader)(tfrec_amd_ctx *, R *, size_t, uint32_t *), const char *noun, bool cut_opens,
+					   std::vector<R> &recs)
 {
 	uint32_t nr = 0;
-	int r = tfrec_amd_read_bursts(ctx, NULL, 0, &nr);  // (the count: E_INVAL for want of room)
+	int r = reader(ctx, NULL, 0, &nr);  // (the count: E_INVAL for want of room)
 	if (r == TFREC_AMD_E_INVAL && nr) {
-		b.bursts.resize(nr);
-		r = tfrec_amd_read_bursts(ctx, b.bursts.data(), b.bursts.size(), &nr);
+		recs.resize(nr);
+		r = reader(ctx, recs.data(), recs.size(), &nr);
 	}
 	if (r == TFREC_AMD_E_OVERFLOW) {  // (cannot happen: the table is sized for the worst case)
-		fprintf(stderr, "tfrec_amd: device %d batch %zu: more runs than the table holds, %zu of %u burst records kept\n", device, k,
-			b.bursts.size(), (unsigned)nr);
+		fprintf(stderr, "tfrec_amd: device %d batch %zu: more runs than the table holds, %zu of %u %s records kept\n", device, k, recs.size(),
+			(unsigned)nr, noun);
 		r = 0;
 	}
 	if (r)
 		return r;
-	const std::vector<int> &file = plan[k].file;
 	size_t kept = 0;
-	for (size_t q = 0; q < b.bursts.size(); q++) {
-		tfrec_amd_burst x = b.bursts[q];
-		if (x.stream >= file.size() || file[x.stream] < 0)
-			continue;
-		const long long end = (long long)file_blocks[file[x.stream]] * TFREC_AMD_BLOCK_DEC;
-		if (x.start_sample >= end)
-			continue;
-		x.n_samples = (uint32_t)std::min<long long>(x.n_samples, end - x.start_sample);
-		x.stream = (uint32_t)file[x.stream];
-		b.bursts[kept++] = x;
+	for (size_t q = 0; q < recs.size(); q++) {
+		R x = recs[q];
+		if (cut_at_file_end(x, plan[k].file, file_blocks, cut_opens))
+			recs[kept++] = x;
 	}
-	b.bursts.resize(kept);
+	recs.resize(kept);
 	return 0;
 }
 
-// -Q: the batch's envelope records.  stream -> file, as for the events; a record that begins behind its file's end is dropped, one
-// that reaches over it has its n_samples cut there and is OPEN: the input's end cut its tail (its sums are the device's: the
-// padding is silence and never over, so last_over lies ahead of the cut)
-inline int device_worker::read_envelopes(size_t k, batch_result &b)
-{
-	uint32_t nr = 0;
-	int r = tfrec_amd_read_burst_envelopes(ctx, NULL, 0, &nr);  // (the count: E_INVAL for want of room)
-	if (r == TFREC_AMD_E_INVAL && nr) {
-		b.envelopes.resize(nr);
-		r = tfrec_amd_read_burst_envelopes(ctx, b.envelopes.data(), b.envelopes.size(), &nr);
-	}
-	if (r == TFREC_AMD_E_OVERFLOW) {  // (cannot happen: the table is sized for the worst case)
-		fprintf(stderr, "tfrec_amd: device %d batch %zu: more runs than the table holds, %zu of %u envelope records kept\n", device, k,
-			b.envelopes.size(), (unsigned)nr);
-		r = 0;
-	}
-	if (r)
-		return r;
-	const std::vector<int> &file = plan[k].file;
-	size_t kept = 0;
-	for (size_t q = 0; q < b.envelopes.size(); q++) {
-		tfrec_amd_envelope x = b.envelopes[q];
-		if (x.stream >= file.size() || file[x.stream] < 0)
-			continue;
-		const long long end = (long long)file_blocks[file[x.stream]] * TFREC_AMD_BLOCK_DEC;
-		if (x.start_sample >= end)
-			continue;
-		if (x.start_sample + (long long)x.n_samples > end) {
-			x.n_samples = (uint32_t)(end - x.start_sample);
-			x.flags |= TFREC_AMD_RUN_OPEN;
-		}
-		x.stream = (uint32_t)file[x.stream];
-		b.envelopes[kept++] = x;
-	}
-	b.envelopes.resize(kept);
-	return 0;
-}
-
-// -C: the batch's clock records.  stream -> file, as for the events; a record that begins behind its file's end is dropped, one
-// that reaches over it has its n_samples cut there and is OPEN (its sums are the device's: the padding is silence, and a segment
-// of silence counts in n_silent and adds nothing else)
-inline int device_worker::read_clocks(size_t k, batch_result &b)
-{
-	uint32_t nr = 0;
-	int r = tfrec_amd_read_burst_clocks(ctx, NULL, 0, &nr);  // (the count: E_INVAL for want of room)
-	if (r == TFREC_AMD_E_INVAL && nr) {
-		b.clocks.resize(nr);
-		r = tfrec_amd_read_burst_clocks(ctx, b.clocks.data(), b.clocks.size(), &nr);
-	}
-	if (r == TFREC_AMD_E_OVERFLOW) {  // (cannot happen: the table is sized for the worst case)
-		fprintf(stderr, "tfrec_amd: device %d batch %zu: more runs than the table holds, %zu of %u clock records kept\n", device, k,
-			b.clocks.size(), (unsigned)nr);
-		r = 0;
-	}
-	if (r)
-		return r;
-	const std::vector<int> &file = plan[k].file;
-	size_t kept = 0;
-	for (size_t q = 0; q < b.clocks.size(); q++) {
-		tfrec_amd_clock x = b.clocks[q];
-		if (x.stream >= file.size() || file[x.stream] < 0)
-			continue;
-		const long long end = (long long)file_blocks[file[x.stream]] * TFREC_AMD_BLOCK_DEC;
-		if (x.start_sample >= end)
-			continue;
-		if (x.start_sample + (long long)x.n_samples > end) {
-			x.n_samples = (uint32_t)(end - x.start_sample);
-			x.flags |= TFREC_AMD_RUN_OPEN;
-		}
-		x.stream = (uint32_t)file[x.stream];
-		b.clocks[kept++] = x;
-	}
-	b.clocks.resize(kept);
-	return 0;
-}
-
-// -G: the batch's track records, each with its bits out of the batch's bitmap.  stream -> file, as for the events; a record that
-// begins behind its file's end is dropped, one that reaches over it is cut there and is OPEN (job.h: track_take).  -Y: the sync
-// records of the same entries with them, each with its match track (job.h: sync_take), in b.syncs in place of b.tracks
-inline int device_worker::read_tracks(size_t k, batch_result &b)
+// -G, -Y: the batch's records and bitmap words of one stage by the stage's reader: the counts, then both
+template <class R>
+inline int device_worker::read_run_bitmaps(int (*reader)(tfrec_amd_ctx *, R *, size_t, uint32_t *, uint32_t *, size_t, uint64_t *),
+					   std::vector<R> &recs, std::vector<uint32_t> &words)
 {
 	uint32_t nr = 0;
 	uint64_t nw = 0;
-	std::vector<tfrec_amd_track> recs;
-	std::vector<uint32_t> words;
-	int r = tfrec_amd_read_burst_tracks(ctx, NULL, 0, &nr, NULL, 0, &nw);  // (the counts: E_INVAL for want of room)
+	int r = reader(ctx, NULL, 0, &nr, NULL, 0, &nw);  // (the counts: E_INVAL for want of room)
 	if (r == TFREC_AMD_E_INVAL && nr) {
 		recs.resize(nr);
 		words.resize((size_t)nw + 1);
-		r = tfrec_amd_read_burst_tracks(ctx, recs.data(), recs.size(), &nr, words.data(), words.size(), &nw);
+		r = reader(ctx, recs.data(), recs.size(), &nr, words.data(), words.size(), &nw);
 	}
-	if (r == TFREC_AMD_E_OVERFLOW) {  // (cannot happen: the table and the pool are sized for the worst case)
+	return r;
+}
+
+// -G: the batch's track records, each with its bits out of the batch's bitmap.  stream -> file and the file-end cut as above; a
+// record that reaches over its file's end is cut there and is OPEN (job.h: track_take).  -Y: the sync records of the same entries
+// with them, each with its match track (job.h: sync_take), in b.syncs in place of b.tracks
+inline int device_worker::read_tracks(size_t k, batch_result &b)
+{
+	std::vector<tfrec_amd_track> recs;
+	std::vector<uint32_t> words;
+	int r = read_run_bitmaps(tfrec_amd_read_burst_tracks, recs, words);
+	if (r == TFREC_AMD_E_OVERFLOW)  // (cannot happen: the table and the pool are sized for the worst case)
 		fprintf(stderr, "tfrec_amd: device %d batch %zu: more runs or pairs than the recorder holds, the track is incomplete\n", device, k);
-		return r;
-	}
 	if (r)
 		return r;
 	std::vector<tfrec_amd_burst_sync> srecs;
 	std::vector<uint32_t> swords;
 	if (job.syncing()) {
-		r = tfrec_amd_read_burst_syncs(ctx, NULL, 0, &nr, NULL, 0, &nw);
-		if (r == TFREC_AMD_E_INVAL && nr) {
-			srecs.resize(nr);
-			swords.resize((size_t)nw + 1);
-			r = tfrec_amd_read_burst_syncs(ctx, srecs.data(), srecs.size(), &nr, swords.data(), swords.size(), &nw);
-		}
-		if (r)
+		if ((r = read_run_bitmaps(tfrec_amd_read_burst_syncs, srecs, swords)))
 			return r;
 		if (srecs.size() != recs.size()) {
 			fprintf(stderr, "tfrec_amd: device %d batch %zu: %zu sync records beside %zu track records\n", device, k, srecs.size(), recs.size());
 			return TFREC_AMD_E_STATE;
 		}
 	}
-	const std::vector<int> &file = plan[k].file;
 	for (size_t q = 0; q < recs.size(); q++) {
 		tfrec_amd_track x = recs[q];
-		if (x.stream >= file.size() || file[x.stream] < 0)
+		if (!cut_at_file_end(x, plan[k].file, file_blocks, true))
 			continue;
-		const long long end = (long long)file_blocks[file[x.stream]] * TFREC_AMD_BLOCK_DEC;
-		if (x.start_sample >= end)
-			continue;
-		uint32_t n = x.n_samples;
-		if (x.start_sample + (long long)n > end) {
-			n = (uint32_t)(end - x.start_sample);
-			x.flags |= TFREC_AMD_RUN_OPEN;
-		}
-		x.stream = (uint32_t)file[x.stream];
+		const uint32_t n = x.n_samples;  // (track_take is given the device's record and what the cut keeps of it)
+		x.n_samples = recs[q].n_samples;
 		if (job.syncing())
 			b.syncs.push_back(sync_take(srecs[q], swords.data(), track_take(x, words.data(), n)));
 		else
@@ -729,11 +644,11 @@ inline int device_worker::collect(size_t k, batch_result &b)
 {
 	int r = job.capture ? read_captures(k, b) : 0;
 	if (!r && job.metering())
-		r = read_bursts(k, b);
+		r = read_run_records(k, tfrec_amd_read_bursts, "burst", false, b.bursts);  // (-M alone: a cut record is not marked OPEN)
 	if (!r && job.enveloping())
-		r = read_envelopes(k, b);
+		r = read_run_records(k, tfrec_amd_read_burst_envelopes, "envelope", true, b.envelopes);
 	if (!r && job.clocking())
-		r = read_clocks(k, b);
+		r = read_run_records(k, tfrec_amd_read_burst_clocks, "clock", true, b.clocks);
 	if (!r && job.tracking())
 		r = read_tracks(k, b);
 	if (!r && job.occupancy()) {  // -A: the detector's records in place of the spectrum's, 16 + N / 8 bytes each

@@ -194,6 +194,27 @@ struct dc_report {
 	}
 };
 
+// -M, -Q, -C: a stage's chains across the batches (job.h: chain_merger); take() sends the bursts that ended with a batch into the
+// scan table, or prints the stage's line for each
+template <class R>
+struct chain_report : chain_merger<R> {
+	std::string (*line)(const std::string &file, const R &r);
+	std::vector<R> ended;
+	explicit chain_report(std::string (*l)(const std::string &, const R &)) : line(l) {}
+	void take(const std::vector<R> &recs, const batch_plan &p, const std::vector<size_t> &file_blocks, const std::vector<std::string> &files,
+		  scan_table *scan)
+	{
+		ended.clear();
+		chain_merger<R>::take(recs, p, file_blocks, ended);
+		for (const R &x : ended) {
+			if (scan)
+				scan->chan[x.stream].note(x);
+			else
+				printf("%s\n", line(files[x.stream], x).c_str());
+		}
+	}
+};
+
 void spectrum_table::begin(const job_settings &job)
 {
 	n = job.spec_n;
@@ -420,16 +441,13 @@ int gpu_engine::run()
 	spectrum_table spec;
 	occupancy_list occ;
 	scan_table scan;
-	burst_merger bursts;
-	std::vector<tfrec_amd_burst> ended;
+	chain_report<tfrec_amd_burst> bursts(burst_line);
 	bursts.begin(n);
-	envelope_merger envelopes;
-	std::vector<tfrec_amd_envelope> extents;
+	chain_report<tfrec_amd_envelope> envelopes(envelope_line);
 	envelopes.begin(n);
-	clock_merger clocks;
-	std::vector<tfrec_amd_clock> keyed;
+	chain_report<tfrec_amd_clock> clocks(clock_line);
 	clocks.begin(n);
-	track_merger tracks;
+	chain_merger<track_piece> tracks;
 	std::vector<track_piece> said;
 	tracks.begin(n);
 	sync_merger syncs;
@@ -469,39 +487,16 @@ int gpu_engine::run()
 			if ((rc = cap.take(b)))
 				break;
 			dc.take(b, files);
-			if (job.metering()) {  // -M: the bursts that ended with this batch -- into the scan table, or a line each
-				ended.clear();
-				bursts.take(b, workers[d].plan[k], file_blocks, ended);
-				for (const tfrec_amd_burst &x : ended) {
-					if (job.scan)
-						scan.chan[x.stream].note(x);
-					else
-						printf("%s\n", burst_line(files[x.stream], x).c_str());
-				}
-			}
-			if (job.enveloping()) {  // -Q: likewise, behind -M's lines of the batch
-				extents.clear();
-				envelopes.take(b, workers[d].plan[k], file_blocks, extents);
-				for (const tfrec_amd_envelope &x : extents) {
-					if (job.scan)
-						scan.chan[x.stream].note(x);
-					else
-						printf("%s\n", envelope_line(files[x.stream], x).c_str());
-				}
-			}
-			if (job.clocking()) {  // -C: likewise, behind -Q's lines of the batch
-				keyed.clear();
-				clocks.take(b, workers[d].plan[k], file_blocks, keyed);
-				for (const tfrec_amd_clock &x : keyed) {
-					if (job.scan)
-						scan.chan[x.stream].note(x);
-					else
-						printf("%s\n", clock_line(files[x.stream], x).c_str());
-				}
-			}
+			scan_table *const into = job.scan ? &scan : NULL;
+			if (job.metering())  // -M: the bursts that ended with this batch -- into the scan table, or a line each
+				bursts.take(b.bursts, workers[d].plan[k], file_blocks, files, into);
+			if (job.enveloping())  // -Q: likewise, behind -M's lines of the batch
+				envelopes.take(b.envelopes, workers[d].plan[k], file_blocks, files, into);
+			if (job.clocking())  // -C: likewise, behind -Q's lines of the batch
+				clocks.take(b.clocks, workers[d].plan[k], file_blocks, files, into);
 			if (job.syncing()) {  // -G -Y: -G's line of each burst, and behind it a line per frame found in it
 				framed.clear();
-				syncs.take(b, workers[d].plan[k], file_blocks, framed);
+				syncs.take(b.syncs, workers[d].plan[k], file_blocks, framed);
 				for (const sync_piece &x : framed) {
 					printf("%s\n", track_line(files[x.stream], x.trk, job.track_rate).c_str());
 					for (const sync_frame &f : sync_frames(x, job))
@@ -509,7 +504,7 @@ int gpu_engine::run()
 				}
 			} else if (job.tracking()) {  // -G: likewise, behind -C's lines of the batch
 				said.clear();
-				tracks.take(b, workers[d].plan[k], file_blocks, said);
+				tracks.take(b.tracks, workers[d].plan[k], file_blocks, said);
 				for (const track_piece &x : said)
 					printf("%s\n", track_line(files[x.stream], x, job.track_rate).c_str());
 			}

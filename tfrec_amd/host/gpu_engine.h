@@ -191,14 +191,14 @@ public:
 	void set_replay(const std::vector<replay_file> &captures) { job.replay = &captures; }
 	// -M: the burst meter (tfrec_amd_enable_burst_meter).  Every context enables the recorder -- set_capture's, or with
 	// set_capture's room for runs and a pool of one pair -- and the meter on it; run() merges the records' chains across the batches
-	// of a file (job.h: burst_merger; a chain still open at the file's end is flushed there) and prints, as each burst ends,
+	// of a file (job.h: chain_merger; a chain still open at the file's end is flushed there) and prints, as each burst ends,
 	//   burst <file> <start_sample> <n_samples> <pwr_max> <centre_hz|-> <deviation_hz|->
 	// (job.h: burst_summary; "-": no bin is occupied).  With set_scan the lines are not printed: the table's lines end in
 	// " burst_centre=<Hz|->", the centre of the channel's burst with the largest pwr_max.  Under -A it is the scan's, not pass 1's.
 	// Neither the 1/16 rule behind the summary nor its usefulness has been measured on real recordings.
 	void set_meter() { job.meter = true; }
 	// -Q: the burst envelope (tfrec_amd_enable_burst_envelope), with or without -M.  Every context enables the recorder
-	// as for -M and the envelope on it; run() merges the records' chains across the batches of a file (job.h: envelope_merger; a
+	// as for -M and the envelope on it; run() merges the records' chains across the batches of a file (job.h: chain_merger; a
 	// chain still open at the file's end is flushed there, OPEN) and prints, as each burst ends,
 	//   extent <file> <start_sample> <n_samples> <burst_samples> <n_over> <n_gaps> <max_gap> <ratio_c|-> <snr_db|->
 	// (job.h: envelope_summary; ratio_c in hundredths as %d.%02d, "-": undefined).  With set_scan the lines are not printed: the
@@ -206,7 +206,7 @@ public:
 	// lower middle one).  Under -A it is the scan's, not pass 1's.
 	void set_envelope() { job.envelope = true; }
 	// -C: the burst clock (tfrec_amd_enable_burst_clock), with or without -M and -Q.  Every context enables the
-	// recorder as for -M and the clock on it; run() merges the records' chains across the batches of a file (job.h: clock_merger; a
+	// recorder as for -M and the clock on it; run() merges the records' chains across the batches of a file (job.h: chain_merger; a
 	// chain still open at the file's end is flushed there, OPEN) and prints, as each burst ends,
 	//   clock <file> <start_sample> <n_samples> <n_segments> <clock_hz|-> <quality|->
 	// (job.h: clock_summary; quality_c in hundredths as %d.%02d, "-": no whole segment, or an empty band).  With set_scan the lines
@@ -217,7 +217,7 @@ public:
 	// -G: the burst track (tfrec_amd_enable_burst_track), with or without -M, -Q and -C.  Every context enables the
 	// recorder with a pool for every sample (the bitmap has the pool's size) and the track on it, L = half a symbol of `rate` held
 	// within 1 .. 16, every stream about centre_hz; run() merges the records' chains and their bits across the batches of a file
-	// (job.h: track_merger; a chain still open at the file's end is flushed there, OPEN; at most the first 2^20 samples of a chain
+	// (job.h: chain_merger; a chain still open at the file's end is flushed there, OPEN; at most the first 2^20 samples of a chain
 	// are kept) and prints, as each burst ends,
 	//   bits <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->
 	// (job.h: track_slice, track_line: the run-length slice at `rate` of the first burst_samples = last_over + 1 samples, MSB-first;

@@ -361,11 +361,35 @@ inline std::vector<occ_channel> occupancy_channels(const std::vector<unsigned lo
 // -P: the spectrum records of input row 0, [record][bin], and their frame counts
 // -A: the detector's records of row 0 and their bitmap words, [record][N / 32]
 // -z with -D: per file of the batch its index in the job and the last window's {d_I, d_Q} of its row
-// -M: the burst records that belong to a file (stream = its index in the job), n_samples cut at the file's end
+// -M: the burst records that belong to a file (stream = its index in the job), n_samples cut at the file's end (cut_at_file_end)
 // -Q: the envelope records likewise; one that is cut at the file's end is OPEN (the input's end cut its tail)
 // -C: the clock records likewise
 // -G: the track records likewise, each with its bits out of the batch's bitmap (track_piece; its functions are further down)
 constexpr uint64_t kTrackKeep = 1ull << 20;  // the samples of a chain's track that are kept
+
+// The file-end cut of a burst stage's record (-M, -Q, -C, -G, -Y), as the device delivers it: stream is the batch's slot, `file`
+// the batch's map from slot to file (its index in the job; -1: idle) and file_blocks every file's length.  A record of an idle
+// slot, of a slot beyond the map, or that begins at or behind its file's end is dropped (false).  Otherwise stream becomes the
+// file's index, and a record that reaches over the file's end keeps the n_samples inside the file; cut_opens: it is then OPEN too
+// -- the input's end cut its tail --, which every stage's reader asks for but -M's.  The record's sums stay the device's: the
+// padding behind a file's end is silence.
+template <class R>
+inline bool cut_at_file_end(R &x, const std::vector<int> &file, const std::vector<size_t> &file_blocks, bool cut_opens)
+{
+	if (x.stream >= file.size() || file[x.stream] < 0)
+		return false;
+	const int f = file[x.stream];
+	const long long end = (long long)file_blocks[f] * TFREC_AMD_BLOCK_DEC;
+	if (x.start_sample >= end)
+		return false;
+	if (x.start_sample + (long long)x.n_samples > end) {
+		x.n_samples = (uint32_t)(end - x.start_sample);
+		if (cut_opens)
+			x.flags |= TFREC_AMD_RUN_OPEN;
+	}
+	x.stream = (uint32_t)f;
+	return true;
+}
 
 // A record with its track: bit k of the track is bit k & 31 of bits[k >> 5], for k < min(n_samples, 2^20)
 struct track_piece : tfrec_amd_track {
@@ -896,36 +920,11 @@ template <class R> struct chain_merger {
 		}
 	}
 };
-struct burst_merger : chain_merger<tfrec_amd_burst> {  // -M
-	void take(const batch_result &b, const batch_plan &p, const std::vector<size_t> &file_blocks, std::vector<tfrec_amd_burst> &out)
+// -M, -Q, -C and -G take a batch_result's bursts, envelopes, clocks and tracks with chain_merger<R>::take as it is; -Y its syncs:
+struct sync_merger : chain_merger<sync_piece> {
+	void take(const std::vector<sync_piece> &recs, const batch_plan &p, const std::vector<size_t> &file_blocks, std::vector<sync_piece> &out)
 	{
-		chain_merger<tfrec_amd_burst>::take(b.bursts, p, file_blocks, out);
-	}
-};
-struct envelope_merger : chain_merger<tfrec_amd_envelope> {  // -Q
-	void take(const batch_result &b, const batch_plan &p, const std::vector<size_t> &file_blocks, std::vector<tfrec_amd_envelope> &out)
-	{
-		chain_merger<tfrec_amd_envelope>::take(b.envelopes, p, file_blocks, out);
-	}
-};
-struct clock_merger : chain_merger<tfrec_amd_clock> {  // -C
-	void take(const batch_result &b, const batch_plan &p, const std::vector<size_t> &file_blocks, std::vector<tfrec_amd_clock> &out)
-	{
-		chain_merger<tfrec_amd_clock>::take(b.clocks, p, file_blocks, out);
-	}
-};
-
-struct track_merger : chain_merger<track_piece> {  // -G
-	void take(const batch_result &b, const batch_plan &p, const std::vector<size_t> &file_blocks, std::vector<track_piece> &out)
-	{
-		chain_merger<track_piece>::take(b.tracks, p, file_blocks, out);
-	}
-};
-
-struct sync_merger : chain_merger<sync_piece> {  // -Y
-	void take(const batch_result &b, const batch_plan &p, const std::vector<size_t> &file_blocks, std::vector<sync_piece> &out)
-	{
-		chain_merger<sync_piece>::take(b.syncs, p, file_blocks, out);
+		chain_merger<sync_piece>::take(recs, p, file_blocks, out);
 		for (sync_piece &x : out)  // (the merger clears OPEN on the chain's own flags: the track piece's follow)
 			x.trk.flags = x.flags;
 	}
