@@ -1,8 +1,8 @@
-"""Randomised exact-parity campaign for the squelched recorder and the four measurements on its run table: the burst meter, the
-envelope, the clock and the track (capture.h, burst.h, envelope.h, clock.h, track.h).  Random stream counts, masks (per context and
-per stream), cuts, submits in flight, resets, tight recorder caps and subsets of the measurements; rows made by hand so that every
-run's edges are known and land on the kernels' own strides.  Every comparison is byte for byte with the restatements in
-tfrec_amd/{capture,levels,burst,envelope,clock,track}.py; nothing here has a tolerance.
+"""Randomised exact-parity campaign for the squelched recorder and the measurements on its run table: the burst meter, the envelope,
+the clock, the track and the sync (capture.h, burst.h, envelope.h, clock.h, track.h, sync.h).  Random stream counts, masks (per
+context and per stream), cuts, submits in flight, resets, tight recorder caps and subsets of the measurements; rows made by hand so
+that every run's edges are known and land on the kernels' own strides.  Every comparison is byte for byte with the restatements in
+tfrec_amd/{capture,levels,burst,envelope,clock,track,sync}.py; nothing here has a tolerance.
     python tests/recorder_campaign.py <seed> <rounds>      (tests/test_recorder_campaign_gpu.py runs a short fixed campaign,
                                                             tests/test_recorder_campaign_cpu.py holds the generator to its classes)
 
@@ -17,6 +17,13 @@ row is built from (classes_hit() measures them back from capture.captures on the
    5  a run across a block boundary, 1 .. 16 ahead of it  11  a not-over gap of W - 1 inside a run: in a block, across a block
    6  the same at a submit cut                                boundary, across a submit cut
                                                           12  a run of 2046 samples from 1024 q + 1, and one of 2047
+
+The burst sync (sync.h, tfrec_amd/sync.py) is a fifth measurement, behind the track: about half the rounds have one.  Its settings
+(draw_sync) come from a generator of their own, seeded (seed, SYNC_STREAM), so that a seed's rows, masks, cuts, drains, resets, caps,
+L and centres are what they were without it; a round with a sync measures the track too.  Every submit's records and match bitmap
+are compared with the restatement on the track the same context returned (test_sync_gpu.read_sync), under the plan's caps as the
+header's Bits paragraph states them, and the merged chains with the restatement on the uncut rows.  SYNC_CLASSES names the sync's
+own edges; sync_classes_hit() measures them back from the restatement on a plan.
 """
 import functools
 import os
@@ -31,22 +38,27 @@ for _p in (_HERE, os.path.join(_HERE, "..")):
 import test_capture_gpu as TC  # noqa: E402
 import test_clock_gpu as TK  # noqa: E402
 import test_envelope_gpu as TE  # noqa: E402
+import test_sync_gpu as TS  # noqa: E402
 import test_track_gpu as TT  # noqa: E402
 from test_clock_cpu import keyed  # noqa: E402
+from test_sync_cpu import stripped as sync_stripped  # noqa: E402
 from test_track_cpu import stripped  # noqa: E402
-from tfrec_amd import api, burst, capture, clock, decin, envelope, levels, track  # noqa: E402
+from tfrec_amd import api, burst, capture, clock, decin, envelope, levels, sync, track  # noqa: E402
 
 B = api.BLOCK_DEC
 T = 100  # the rows' threshold: their quiet parts stay below it
 EDGE64 = (0, 1, 31, 32, 33, 63)
 CTX_MASKS = (0x02, 0x01, 0x20, 0x08, 0x2F)
 MEASURES = ("meter", "envelope", "clock", "track")
-MODULES = {"meter": burst, "envelope": envelope, "clock": clock, "track": track}
+MODULES = {"meter": burst, "envelope": envelope, "clock": clock, "track": track, "sync": sync}
 DENSE_PERIOD = 357  # a window of mask 0x02 (356) and the one uncaptured sample behind it
 ZONE = 1100  # the samples ahead of a block boundary kept for the boundary's own item
 TABLE_FIELDS = ("stream", "flags", "start_sample", "n_samples", "thresh")
-SEEDS = (12, 19, 21, 24)  # the fixed campaign of tests/test_recorder_campaign_gpu.py: ROUNDS rounds each
+SEEDS = (12, 19, 21, 24, 35, 91)  # the fixed campaign of tests/test_recorder_campaign_gpu.py: ROUNDS rounds each (35 and 91 came
+# with the sync: a store with D < 0, a continuing piece with nothing defined, a hit behind 2047 carried bits)
 ROUNDS = 6
+SYNC_STREAM = 0x73796E63  # the sync's settings are drawn from a generator of their own, seeded (seed, this): the plan's draws stay
+CONT, OPEN = capture.RUN_CONTINUES, capture.RUN_OPEN
 quiet = TE.quiet
 
 
@@ -161,7 +173,7 @@ def _boundary(rng, P, W, end, cut=False):
     return [(l - n + 1, l), (l + W, l + W + _len(rng) - 1)]
 
 
-def _fill_row(rng, row, W, cuts):
+def _fill_row(rng, row, W, cuts, kind=None):
     nb = len(row) // B
     E = nb * B
     marks = sorted(set(cuts) | {nb})
@@ -175,7 +187,7 @@ def _fill_row(rng, row, W, cuts):
             if st is None:
                 continue
             for a, l in st:
-                _paint(rng, row, a, l, W)
+                _paint(rng, row, a, l, W, kind)
             free = st[-1][1] + W + 1
             pos = free + int(rng.integers(0, 3)) * int(rng.integers(0, 300))
         if P < E and (k + 1) in cuts and rng.integers(6) == 0:  # class 8
@@ -183,7 +195,7 @@ def _fill_row(rng, row, W, cuts):
             P2 = B * min(m for m in marks if m > k + 1)
             if a >= free:
                 l = P2 + int(rng.integers(0, 300)) if P2 < E else E - 1
-                _paint(rng, row, a, l, W, ("tone", "noise")[int(rng.integers(2))])
+                _paint(rng, row, a, l, W, kind or ("tone", "noise")[int(rng.integers(2))])
                 free = l + W + 1
                 k = P2 // B
                 continue
@@ -193,18 +205,19 @@ def _fill_row(rng, row, W, cuts):
                 break
             st = []
         for a, l in st:
-            _paint(rng, row, a, l, W)
+            _paint(rng, row, a, l, W, kind)
         if st:
             free = st[-1][1] + W + 1
         k += 1
 
 
-def rows(rng, n_streams, n_blocks, windows, cuts=()):
+def rows(rng, n_streams, n_blocks, windows, cuts=(), kind=None):
     """int16 [n_streams, n_blocks B, 2] for a channel-rate context; windows[s]: stream s's W; cuts: the block indices at which the
-    input will be cut into submits (the classes at a submit cut are placed there).  Pure numpy, deterministic in rng."""
+    input will be cut into submits (the classes at a submit cut are placed there); kind: every stretch is of this kind of _paint's
+    (default: drawn).  Pure numpy, deterministic in rng."""
     out = np.stack([quiet(n_blocks, int(rng.integers(1 << 30))) for _ in range(n_streams)])
     for s in range(n_streams):
-        _fill_row(rng, out[s], int(windows[s]), set(int(c) for c in cuts))
+        _fill_row(rng, out[s], int(windows[s]), set(int(c) for c in cuts), kind)
     return out
 
 
@@ -284,11 +297,21 @@ def classes_hit(x, masks, thresh, sizes):
 
 
 # ---- one round's plan: everything that is drawn, and what the restatements expect of it
-def restate(p, sizes, reset=None, measure=()):
+def sync_on(p, measure):
+    """The sync sits on the track: a plan's settings are in force where the track is measured."""
+    return p.get("sync") is not None and "track" in measure
+
+
+def restate(p, sizes, reset=None, measure=(), caps=True):
     """The restatements over the plan's rows cut into submits of `sizes` blocks, the streams of reset[1] restarted with submit
-    reset[0] -> one dict per submit: the full table and pool (no caps), the level records, and the records of `measure`."""
+    reset[0] -> one dict per submit: the full table and pool (no caps), the level records, and the records of `measure`.  With
+    the track and a plan's sync: "sync", the sync's records and words, and "sync_state", what the submit before left.  The sync
+    alone is a capped context's (caps: the plan's, if it has any): it looks at the delivered records -- those below max_runs -- and
+    at the runs that fit max_samples, and carries what these leave (the header's Bits paragraph)."""
     n, x = p["n"], p["dec"]
     cst, lst, base, prev, tst, pos, out = [None] * n, [None] * n, [0] * n, TE.zeros(n), None, 0, []
+    sst = sync.fresh_state(n)
+    mr, ms = (p.get("cap") if caps else None) or (None, None)
     for k, nb in enumerate(sizes):
         if reset and reset[0] == k:
             for s in reset[1]:
@@ -313,6 +336,9 @@ def restate(p, sizes, reset=None, measure=()):
         if "track" in measure:
             recs, words, tst = track.tracks(decs, thr, table[0], p["L"], p["centres"], tst, base=base)
             e["track"] = (recs, words)
+            if sync_on(p, measure):
+                srecs, swords, nxt = sync.syncs(recs[:mr], words, p["sync"], sst, n, max_samples=ms)
+                e["sync"], e["sync_state"], sst = (srecs, swords), sst, nxt
         out.append(e)
         prev, pos, base = TE.last_pairs(decs), pos + nb, [v + nb * B for v in base]
     return out
@@ -326,14 +352,18 @@ def finish(p):
     return p
 
 
-def make_plan(x, ctx_mask, masks, sizes, L=5, centres=None, thresh=None, drains=None, reset=None, cap=None, measure=MEASURES):
-    """A plan from its parts.  configured: the streams whose settings are not the context's (tfrec_amd_configure_streams)."""
+def make_plan(x, ctx_mask, masks, sizes, L=5, centres=None, thresh=None, drains=None, reset=None, cap=None, measure=MEASURES, sync=None):
+    """A plan from its parts.  configured: the streams whose settings are not the context's (tfrec_amd_configure_streams).  sync:
+    a sync.Settings or None; a plan that has one measures the track too (drawn: the measurements as they were given)."""
     n = len(x)
     thresh = list(thresh or [T] * n)
+    drawn = tuple(measure)
+    if sync is not None:
+        measure = tuple(m for m in MEASURES if m in drawn or m == "track")
     return finish(dict(n=n, nb=x.shape[1] // B, x=np.ascontiguousarray(x), ctx_mask=ctx_mask, masks=list(masks), sizes=tuple(sizes),
                        thresh=thresh, configured=[s for s in range(n) if masks[s] != ctx_mask or thresh[s] != T], L=L,
                        centres=list(centres or [0] * n), drains=list(drains or [None] * len(sizes)), reset=reset, cap=cap,
-                       measure=tuple(measure)))
+                       measure=tuple(measure), drawn=drawn, sync=sync))
 
 
 def full_cap(p):
@@ -350,8 +380,43 @@ def _submasks(rng, ctx_mask):
             return m
 
 
-def plan(rng, rnd=0):
-    """Draw one round."""
+def sync_rng(seed):
+    """The generator the sync's settings are drawn from: the plan's own generator draws what it drew without a sync."""
+    return np.random.default_rng([int(seed), SYNC_STREAM])
+
+
+def min_rate(P):
+    """The smallest legal rate for P pattern bits: its span is the largest there is (2047 where no rate steps over it)."""
+    R = max(1000, 384000 * (P - 1) // 2048)
+    while sync.deltas(R, P)[-1] > sync.HISTORY:
+        R += 1
+    return R
+
+
+def draw_sync(srng, rnd=0):
+    """A round's sync.Settings, or None: every round with rnd % 3 == 0 has one and a quarter of the others, half of all.  The
+    settings at which the kernel's arithmetic changes are drawn as often as the ones in between: P = 8 and 64, E = 0 and its
+    limit, a span inside one lane's word (below 32: P = 8 and a rate above 85333), the largest span, and the patterns of one
+    bit value, which the tracks of constant samples and of the dense row's holds meet."""
+    if rnd % 3 and srng.integers(4):
+        return None
+    P = int((8, 64, srng.integers(9, 64))[int(srng.integers(3))])
+    k = int(srng.integers(5))
+    if k == 0:  # span < 32
+        P, rate = 8, int(srng.integers(85334, 96001))
+    elif k == 1:  # the largest span
+        rate = min_rate(P)
+    else:  # in between, short spans more often than long ones: most runs are a few hundred samples
+        lo = min_rate(P)
+        rate = int(lo * (96000 / lo) ** (1 - float(srng.random()) ** 2))
+    E = int((0, (P - 1) // 2, srng.integers(0, (P - 1) // 2 + 1))[int(srng.integers(3))])
+    ones = (1 << P) - 1
+    pattern = (0, ones, 0xAAAAAAAAAAAAAAAA & ones, int(srng.integers(0, 1 << 63)) * 2 + int(srng.integers(2)) & ones)[int(srng.integers(4))]
+    return sync.Settings(rate, pattern, P, E, bool(srng.integers(2)))
+
+
+def plan(rng, rnd=0, srng=None):
+    """Draw one round; srng: the generator of the sync's settings (default: no sync)."""
     kind = int(rng.integers(10))  # 0: the dense row alone, 12 blocks under mask 0x02; 1, 2: it is one stream beside ordinary rows
     if kind == 0:
         n, nb, ctx_mask = int(rng.integers(1, 4)), 12, 0x02
@@ -393,7 +458,8 @@ def plan(rng, rnd=0):
     L = int((1, 16, rng.integers(1, 17))[int(rng.integers(3))])
     edge = rng.integers(8, size=n)  # the centre's limits and 0 now and then
     centres = [(-192000, 192000, 0)[e] if e < 3 else int(v) for e, v in zip(edge, rng.integers(-192000, 192001, size=n))]
-    p = make_plan(x, ctx_mask, masks, sizes, L=L, centres=centres, thresh=thresh, drains=drains, reset=reset, measure=measure)
+    p = make_plan(x, ctx_mask, masks, sizes, L=L, centres=centres, thresh=thresh, drains=drains, reset=reset, measure=measure,
+                  sync=draw_sync(srng, rnd) if srng is not None else None)
     if rng.integers(3) == 0:  # tight caps: a prefix is delivered
         tabs = [e["table"][0] for e in p["expect"]]
         k = int(np.argmax([len(t) for t in tabs]))
@@ -409,11 +475,124 @@ def plan(rng, rnd=0):
     return p
 
 
-def describe(p):
-    return "streams %d blocks %d ctx %02x masks %s thresh %s sizes %s drains %s L %d centres %s reset %s cap %s measure %s" % (
+def describe(p, with_sync=True):
+    """with_sync=False: the plan as it was drawn ahead of the sync's settings, which also add the track to `measure`."""
+    st = p.get("sync")
+    text = "streams %d blocks %d ctx %02x masks %s thresh %s sizes %s drains %s L %d centres %s reset %s cap %s measure %s" % (
         p["n"], p["nb"], p["ctx_mask"], ["%02x" % m for m in p["masks"]] if p["configured"] else "-",
         p["thresh"] if p["configured"] else "-", list(p["sizes"]), p["drains"], p["L"], p["centres"], p["reset"], p["cap"],
-        ",".join(p["measure"]))
+        ",".join(p["measure"] if with_sync else p["drawn"]))
+    if not with_sync:
+        return text
+    return text + (" sync -" if st is None else " sync rate %d pattern %x P %d E %d both %d span %d" % (
+        st.rate, st.pattern, st.P, st.E, st.both, st.span))
+
+
+# ---- the sync's own classes, measured back from the restatement on a plan
+SYNC_CLASSES = (
+    "P:8", "P:64", "E:0", "E:limit", "both:on", "both:off", "span:<32", "span:2047", "pattern:zeros", "pattern:ones", "pattern:mixed",
+    "defined-inside",        # a CONTINUES record whose first defined sample lies inside it: 0 < span - H < n_samples
+    "defined-inside:H<32",   # ... with 0 < H < 32
+    "continues:none",        # a CONTINUES record that is not OPEN and has no defined sample
+    "H2047:early-hit",       # a CONTINUES record with H = 2047 and a hit among its first span samples
+    "hit:continues-first",   # a hit at sample 0 of a CONTINUES record
+    "hit:open-last",         # a hit at the last sample of an OPEN record
+    "word:shared",           # a run's last sample is a hit, its bit is not a word's last, and another run follows in the pool
+    "word:D<0",              # hits in the pool's first run, which starts off a lane's first sample: the store with D < 0
+    "across:block",          # a hit at a k for which k and k - span lie in different blocks of one submit
+    "across:cut",            # ... in different submits
+    "both:plain", "both:complement", "both:tie",  # under BOTH: where a record's best comes from
+    "min:two-blocks",        # the smallest distance is attained in two blocks of a record (best_at: the earlier)
+    "min:two-words",         # ... in two 32-sample words of one block
+    "dense:>256",            # a stream with more than 256 sync records in one submit
+    "overflow:max_runs", "overflow:max_samples",  # a submit that overflows, with a sync
+    "continues:H=0",         # a CONTINUES record whose predecessor did not fit: it starts without history
+    "reset:mid-chain")       # a reset between two submits: the reset stream's chain is dropped, another stream's continues
+
+
+def _distances(st, h, t):
+    """The header's Distance, counted in place: a piece's track t with the available history h -> (the first defined k, d[k] from
+    there on)."""
+    H, n = len(h), len(t)
+    k0 = max(0, st.span - H)
+    ext = np.concatenate([h, t]).astype(np.int64)
+    d = np.zeros(max(0, n - k0), dtype=np.int64)
+    for j in range(st.P):
+        a = H + k0 - st.delta[j]
+        d += ext[a:a + len(d)] != st.bit[j]
+    return k0, d
+
+
+def sync_classes_hit(p):
+    """The sync's edge classes a plan holds, from the restatement of its submits (under its caps) -> a set of SYNC_CLASSES'
+    labels; none for a plan without a sync."""
+    st = p["sync"]
+    if st is None:
+        return set()
+    ones = (1 << st.P) - 1
+    hit = {"both:on" if st.both else "both:off",
+           "pattern:zeros" if st.pattern == 0 else "pattern:ones" if st.pattern == ones else "pattern:mixed"}
+    hit |= {lab for lab, on in (("P:8", st.P == 8), ("P:64", st.P == 64), ("E:0", st.E == 0), ("E:limit", st.E == (st.P - 1) // 2),
+                                ("span:<32", st.span < 32), ("span:2047", st.span == 2047)) if on}
+    sub = restate(p, p["sizes"], p["reset"], ("track",))
+    ms = p["cap"][1] if p["cap"] else None
+    for e in sub:
+        (trecs, twords), (recs, words), state = e["track"], e["sync"], e["sync_state"]
+        if len(recs) and np.bincount(recs["stream"]).max() > 256:
+            hit.add("dense:>256")
+        if p["cap"] and len(e["table"][0]) > p["cap"][0]:
+            hit.add("overflow:max_runs")
+        if p["cap"] and len(e["table"][1]) > p["cap"][1]:
+            hit.add("overflow:max_samples")
+        for i, r in enumerate(recs):
+            if not sync._fits(r, ms):
+                continue
+            s, a, n, cont = int(r["stream"]), int(r["start_sample"]), int(r["n_samples"]), bool(int(r["flags"]) & CONT)
+            h = np.asarray(state["bits"][s], dtype=np.uint8)[-sync.HISTORY:] if cont else np.zeros(0, dtype=np.uint8)
+            H = len(h)
+            m, t = sync.bits_of(r, words), track.bits_of(trecs[i], twords)
+            k0, d = _distances(st, h, t)
+            assert np.array_equal(m[k0:], (d <= st.E) | (st.both & (d >= st.P - st.E))) and not m[:k0].any()
+            if cont:
+                if 0 < st.span - H < n:
+                    hit |= {"defined-inside"} | ({"defined-inside:H<32"} if 0 < H < 32 else set())
+                if not int(r["flags"]) & OPEN and int(r["best"]) == sync.NONE:
+                    hit.add("continues:none")
+                if H == 0:
+                    hit.add("continues:H=0")
+                if m[:st.span].any():
+                    hit |= {"across:cut"} | ({"H2047:early-hit"} if H == sync.HISTORY else set())
+                if m[0]:
+                    hit.add("hit:continues-first")
+            if int(r["flags"]) & OPEN and m[-1]:
+                hit.add("hit:open-last")
+            if m[-1] and (int(r["bit_offset"]) + n) % 32 and i + 1 < len(recs) and sync._fits(recs[i + 1], ms):
+                hit.add("word:shared")
+            if int(r["bit_offset"]) == 0 and a % 32 and m[:32 - a % 32].any():
+                hit.add("word:D<0")
+            at = np.flatnonzero(m)
+            at = at[at >= st.span]
+            if ((a + at) // B != (a + at - st.span) // B).any():
+                hit.add("across:block")
+            if len(d):
+                if st.both:
+                    lo, hi = int(d.min()), st.P - int(d.max())
+                    hit.add("both:plain" if lo < hi else "both:complement" if hi < lo else "both:tie")
+                f = np.minimum(d, st.P - d) if st.both else d
+                where = a + k0 + np.flatnonzero(f == f.min())
+                if len(set((where // B).tolist())) > 1:
+                    hit.add("min:two-blocks")
+                if any(len(set((where[where // B == b] // 32).tolist())) > 1 for b in set((where // B).tolist())):
+                    hit.add("min:two-words")
+    if p["reset"]:
+        j, streams = p["reset"]
+        prev, cur = sub[j - 1]["sync"][0], sub[j]["sync"][0]
+        for s in streams:
+            mine = cur[cur["stream"] == s]
+            dropped = ((prev["stream"] == s) & (prev["flags"] & OPEN != 0)).any() and len(mine) and not int(mine[0]["flags"]) & CONT
+            if dropped and ((cur["flags"] & CONT != 0) & ~np.isin(cur["stream"], streams)).any():
+                hit.add("reset:mid-chain")
+    return hit
 
 
 # ---- one plan on the GPU
@@ -433,8 +612,10 @@ def _same_table(got, runs, label):
         assert len(bad) == 0, "%s: record %d repeats table field %s wrongly" % (label, bad[0], f)
 
 
-def _check_submit(r, p, k, measure, tst, newest):
-    """Every read of the oldest undrained submit, which is the plan's k-th -> (what was read, the track's state behind it)."""
+def _check_submit(r, p, k, measure, states, newest):
+    """Every read of the oldest undrained submit, which is the plan's k-th; states: the track's and the sync's state ahead of it
+    -> (what was read, the two states behind it)."""
+    tst, sst = states
     e = p["expect"][k]
     nb, decs, base, prev = e["nb"], e["decs"], e["base"], e["prev"]
     label = "submit %d" % k
@@ -470,10 +651,19 @@ def _check_submit(r, p, k, measure, tst, newest):
             thr = [np.repeat(v["thresh"].astype(np.int64), B) for v in e["levels"]]
             nxt = track.tracks(decs, thr, e["table"][0], p["L"], p["centres"], tst, base=base)[2]
         got["track"], tst = (recs, words), nxt
-    for m in measure:
-        n_rec = len(got[m][0] if m == "track" else got[m])
+        if sync_on(p, measure):
+            # test_sync_gpu.read_sync's rule: the restatement on the track records and words this context returned for the submit.
+            # The state it returns is what the delivered records leave -- behind an overflow too: a run that does not fit
+            # max_samples leaves H = 0, and so does an OPEN run beyond max_runs, which has no record
+            srecs, swords, sst = TS.read_sync(r, p["sync"], sst, recs, words, overflow=over)
+            assert r.sync_total == len(e["table"][0]), "%s sync: total %d" % (label, r.sync_total)
+            _same_table(srecs, full, label + " sync")
+            assert len(swords) == (len(wp) + 31) // 32, "%s sync: %d words for %d delivered pairs" % (label, len(swords), len(wp))
+            got["sync"] = (srecs, swords)
+    for m in tuple(measure) + (("sync",) if "sync" in got else ()):
+        n_rec = len(got[m][0] if m in ("track", "sync") else got[m])
         assert n_rec == len(full), "%s %s: %d records of %d" % (label, m, n_rec, len(full))
-    return got, tst
+    return got, (tst, sst)
 
 
 def merged(m, pieces, restarts=None):
@@ -484,10 +674,11 @@ def merged(m, pieces, restarts=None):
 def same_chains(m, got, want, label):
     assert len(got) == len(want), "%s %s: %d chains, want %d" % (label, m, len(got), len(want))
     for i, (a, b) in enumerate(zip(got, want)):
-        if m == "track":
-            assert stripped(a.rec) == stripped(b.rec), "%s track: chain %d: got %s want %s" % (label, i, stripped(a.rec), stripped(b.rec))
-            assert np.array_equal(a.bits, b.bits), "%s track: chain %d (stream %d from %d): bits" % (
-                label, i, a["stream"], a["start_sample"])
+        if m in ("track", "sync"):  # the record without its place in its own submit's pool, and the bits
+            strip = stripped if m == "track" else sync_stripped
+            assert strip(a.rec) == strip(b.rec), "%s %s: chain %d: got %s want %s" % (label, m, i, strip(a.rec), strip(b.rec))
+            assert np.array_equal(a.bits, b.bits), "%s %s: chain %d (stream %d from %d): bits" % (
+                label, m, i, a["stream"], a["start_sample"])
         else:
             for f in a.dtype.names:
                 assert np.array_equal(a[f], b[f]), "%s %s: chain %d (stream %d from %d) field %s: got %s want %s" % (
@@ -511,7 +702,10 @@ def run_plan(p, measure=None, receiver=None):
              "track": lambda: r.enable_burst_track(p["L"])}[m]()
         if "track" in measure:
             r.set_burst_track_centre(range(n), p["centres"])
-        reads, tst, pos = [], None, 0
+        if sync_on(p, measure):
+            st = p["sync"]
+            r.enable_burst_sync(st.rate, st.pattern, st.P, st.E, st.both)
+        reads, states, pos = [], (None, None), 0
         for k, nb in enumerate(sizes):
             if p["reset"] and p["reset"][0] == k:
                 r.reset_streams(p["reset"][1])
@@ -519,7 +713,7 @@ def run_plan(p, measure=None, receiver=None):
             pos += nb
             keep = p["drains"][k] if k + 1 < len(sizes) else 0
             while keep is not None and k + 1 - len(reads) > keep:
-                got, tst = _check_submit(r, p, len(reads), measure, tst, newest=len(reads) == k)
+                got, states = _check_submit(r, p, len(reads), measure, states, newest=len(reads) == k)
                 reads.append(got)
                 r.drain()
         TE.raises(api.E_STATE, r.read_captures)  # nothing undrained
@@ -527,15 +721,15 @@ def run_plan(p, measure=None, receiver=None):
     if measure and len(sizes) > 1 and not overflowed:
         j = p["reset"][0] if p["reset"] else None
         blocks = int(np.sum(sizes[:j])) if j else 0
-        ref = restate(p, (blocks, p["nb"] - blocks) if j else (p["nb"],), (1, p["reset"][1]) if j else None, measure)
-        for m in measure:
+        ref = restate(p, (blocks, p["nb"] - blocks) if j else (p["nb"],), (1, p["reset"][1]) if j else None, measure, caps=False)
+        for m in tuple(measure) + (("sync",) if sync_on(p, measure) else ()):
             same_chains(m, merged(m, [g[m] for g in reads], {j: p["reset"][1]} if j else None),
                         merged(m, [e[m] for e in ref], {1: p["reset"][1]} if j else None), "chains")
     return reads
 
 
-def _round(rng, rnd, verbose=True, seed=None, receiver=None):
-    p = plan(rng, rnd)
+def _round(rng, rnd, verbose=True, seed=None, receiver=None, srng=None):
+    p = plan(rng, rnd, srng)
     try:
         reads = run_plan(p, receiver=receiver)
         runs = sum(len(g["table"][0]) for g in reads)
@@ -549,14 +743,14 @@ def _round(rng, rnd, verbose=True, seed=None, receiver=None):
 
 def campaign(seed: int, rounds: int, verbose: bool = True, receiver=None) -> int:
     """-> the number of bad rounds."""
-    rng = np.random.default_rng(seed)
-    return sum(_round(rng, rnd, verbose, seed, receiver) for rnd in range(rounds))
+    rng, srng = np.random.default_rng(seed), sync_rng(seed)
+    return sum(_round(rng, rnd, verbose, seed, receiver, srng) for rnd in range(rounds))
 
 
 def plans(seed: int, rounds: int):
     """The plans campaign(seed, rounds) draws, without a GPU."""
-    rng = np.random.default_rng(seed)
-    return [plan(rng, rnd) for rnd in range(rounds)]
+    rng, srng = np.random.default_rng(seed), sync_rng(seed)
+    return [plan(rng, rnd, srng) for rnd in range(rounds)]
 
 
 if __name__ == "__main__":

@@ -1,26 +1,33 @@
 """The randomised campaign of tests/recorder_campaign.py on the GPU: the recorder's table and pool, the level records, and the burst
-meter's, the envelope's, the clock's and the track's records and bitmap, byte for byte against the restatements, on rows whose runs
-land on the kernels' own strides -- and the layouts no hand-aimed module reaches: more runs in a stream's submit than a workgroup
-has lanes, a dense stream beside sparse ones at 65 streams, and the four measurements alone and together.  Everything is an exact
-integer; nothing here has a tolerance.  tests/test_recorder_campaign_cpu.py shows that the fixed seeds reach every edge class.
+meter's, the envelope's, the clock's, the track's and the sync's records and bitmaps, byte for byte against the restatements, on
+rows whose runs land on the kernels' own strides -- and the layouts no hand-aimed module reaches: more runs in a stream's submit
+than a workgroup has lanes, a dense stream beside sparse ones at 65 streams, the measurements alone and together, and tracks of one
+value under a sync word of one value, where every hit can be counted.  Everything is an exact integer; nothing here has a
+tolerance.  tests/test_recorder_campaign_cpu.py shows that the fixed seeds reach every edge class, the sync's included.
 
-The fixed campaign: seeds recorder_campaign.SEEDS = (12, 19, 21, 24), recorder_campaign.ROUNDS = 6 rounds each.  Wall times measured
-on an MI355X host (the restatements on the CPU dominate; the first case also loads the library and starts the device):
-  test_campaign[12] 8.3 s, [19] 0.6 s, [21] 0.5 s, [24] 0.7 s
-  test_densest_runs_overrun_every_lookup_stride 1.0 s, test_dense_stream_beside_sparse_ones_at_65_streams 0.9 s,
-  test_each_measurement_alone_equals_all_four_together 0.3 s; the module 13 s.
-python tests/recorder_campaign.py <seed> 50 reported 0 mismatches for the seeds 1001 and 2002, which are not in the list.
+The fixed campaign: seeds recorder_campaign.SEEDS = (12, 19, 21, 24, 35, 91), recorder_campaign.ROUNDS = 6 rounds each; about half
+the rounds have a sync.  Wall times measured on an MI355X host (the restatements on the CPU dominate; the first case also loads the
+library and starts the device):
+  test_campaign[12] 8.5 s, [19] 0.7 s, [21] 0.5 s, [24] 0.7 s, [35] 0.3 s, [91] 0.4 s
+  test_densest_runs_overrun_every_lookup_stride 1.2 s, test_dense_stream_beside_sparse_ones_at_65_streams 0.9 s,
+  test_each_measurement_alone_equals_all_four_together 0.3 s,
+  test_tracks_of_one_value_give_exact_hit_counts_at_every_edge 0.1 s a case; the module 15 s.
+python tests/recorder_campaign.py <seed> 50, with the sync in its rounds, reported 0 mismatches for the seeds 1001 and 2002, which are
+not in the list.
 """
+import functools
+
 import numpy as np
 import pytest
 
 import recorder_campaign as RC
-from tfrec_amd import capture
+from tfrec_amd import capture, sync
 
 pytestmark = pytest.mark.gpu
 
 B = RC.B
 ALL = RC.MEASURES
+SHORT = sync.Settings(96000, 0x2D, 8, 2, True)  # a span of 28 samples: most samples of a 356-sample run have their distance
 
 
 @pytest.mark.parametrize("seed", RC.SEEDS)
@@ -38,18 +45,20 @@ def test_densest_runs_overrun_every_lookup_stride():
     room for 279."""
     x = np.stack([RC.dense(12)] * 3)
     centres = [0, 20000, -192000]
-    whole = RC.run_plan(RC.make_plan(x, 0x02, [0x02] * 3, (12,), L=5, centres=centres))
+    whole = RC.run_plan(RC.make_plan(x, 0x02, [0x02] * 3, (12,), L=5, centres=centres, sync=SHORT))
     runs = whole[0]["table"][0]
     stage_cap = 12 * B // 356 + 3
     for s in range(3):
         mine = runs[runs["stream"] == s]
         assert 256 < len(mine) <= stage_cap and mine[-1]["flags"] == capture.RUN_OPEN
-    for m in ALL:
-        assert len(whole[0][m][0] if m == "track" else whole[0][m]) == len(runs) == 3 * 276
+    for m in ALL + ("sync",):
+        assert len(whole[0][m][0] if m in ("track", "sync") else whole[0][m]) == len(runs) == 3 * 276
+    srecs = whole[0]["sync"][0]  # five trips of the carry kernel's record loop per stream, and matches in nearly every run
+    assert np.count_nonzero(srecs["n_hits"]) > 800 and (srecs["best"] <= SHORT.P // 2).all()
     # the same rows cut as (5, 7), both submits queued before the first read: the merged chains are the uncut ones
-    cut = RC.run_plan(RC.make_plan(x, 0x02, [0x02] * 3, (5, 7), L=5, centres=centres, drains=[None, None]))
+    cut = RC.run_plan(RC.make_plan(x, 0x02, [0x02] * 3, (5, 7), L=5, centres=centres, drains=[None, None], sync=SHORT))
     assert all(max(np.count_nonzero(g["table"][0]["stream"] == s) for s in range(3)) > 100 for g in cut)
-    for m in ALL:
+    for m in ALL + ("sync",):
         RC.same_chains(m, RC.merged(m, pieces(cut, m)), RC.merged(m, pieces(whole, m)), "cut (5, 7)")
 
 
@@ -60,9 +69,10 @@ def test_dense_stream_beside_sparse_ones_at_65_streams():
     masks = [0x02 if s % 4 == 0 else 0x2F for s in range(n)]
     x = RC.rows(np.random.default_rng(65), n, nb, [RC.window(m) for m in masks], cuts=(1,))
     x[::4] = RC.dense(nb)
-    p = RC.make_plan(x, 0x2F, masks, (1, 1), L=7, centres=[(0, 20000, -35000)[s % 3] for s in range(n)], drains=[None, None])
+    p = RC.make_plan(x, 0x2F, masks, (1, 1), L=7, centres=[(0, 20000, -35000)[s % 3] for s in range(n)], drains=[None, None], sync=SHORT)
     assert p["configured"] == list(range(0, n, 4))
     reads = RC.run_plan(p)
+    assert all(np.count_nonzero(g["sync"][0]["n_hits"]) > len(g["sync"][0]) // 2 for g in reads)
     for g in reads:
         per = np.bincount(g["table"][0]["stream"], minlength=n)
         assert (per[::4] >= B // RC.DENSE_PERIOD).all() and per[64] >= 22 and np.delete(per, np.arange(0, n, 4)).min() >= 1
@@ -75,9 +85,10 @@ def test_each_measurement_alone_equals_all_four_together():
     rng = np.random.default_rng(4)
     masks = [0x2F, 0x02, 0x21, 0x08, 0x2F]
     x = RC.rows(rng, 5, 3, [RC.window(m) for m in masks], cuts=(1,))
-    p = RC.make_plan(x, 0x2F, masks, (1, 2), L=9, centres=[0, 192000, -192000, 20000, -35000], drains=[None, None])
+    p = RC.make_plan(x, 0x2F, masks, (1, 2), L=9, centres=[0, 192000, -192000, 20000, -35000], drains=[None, None], sync=SHORT)
     assert sum(len(e["table"][0]) for e in p["expect"]) >= 40
-    plain = RC.run_plan(p, measure=())
+    plain = RC.run_plan(p, measure=())  # (no track: no sync either)
+    assert "sync" not in plain[0]
     every = RC.run_plan(p, measure=ALL)
     for k, (a, b) in enumerate(zip(plain, every)):
         assert a["table"][0].tobytes() == b["table"][0].tobytes() and a["table"][1].tobytes() == b["table"][1].tobytes(), k
@@ -85,7 +96,77 @@ def test_each_measurement_alone_equals_all_four_together():
         alone = RC.run_plan(p, measure=(m,))
         for k, (a, b, c) in enumerate(zip(alone, every, plain)):
             assert a["table"][0].tobytes() == c["table"][0].tobytes() and a["table"][1].tobytes() == c["table"][1].tobytes(), (m, k)
-            if m == "track":
+            if m == "track":  # ... and the sync with only the track beside it is the sync beside all four
                 assert a[m][0].tobytes() == b[m][0].tobytes() and a[m][1].tobytes() == b[m][1].tobytes(), (m, k)
+                assert a["sync"][0].tobytes() == b["sync"][0].tobytes() and a["sync"][1].tobytes() == b["sync"][1].tobytes(), ("sync", k)
+                assert a["sync"][0]["n_hits"].sum() > 0
             else:
                 RC.same_records(a[m], b[m], "%s alone, submit %d" % (m, k))
+
+
+# ---- exact hit counts: tracks of one value under a pattern of one value
+HIT_MASKS = [0x2F, 0x02, 0x20]
+HIT_CENTRES = [0, -35000, 20000]
+
+
+@functools.lru_cache(maxsize=None)
+def hit_rows():
+    """int16 [3, 2 B, 2], to be cut (1, 1): the campaign's generator with every stretch of the `const` kind -- all its samples are
+    one pair, so every cross product is 0 and the track over the stretch is one value: 0 about the centre 0 (a zero sum), and
+    about the centre -35000 Hz 1, about 20000 Hz 0 (the sign of -dot S[r]) -- placed by _interior and _boundary at the campaign's
+    classes 1, 2, 5 (at the cut: 6), 7 and 9; stream 0 also holds a stretch of 1600 samples that is open through the cut."""
+    x = RC.rows(np.random.default_rng(5), 3, 2, [RC.window(m) for m in HIT_MASKS], cuts=(1,), kind="const")
+    x[0, B - 700:B + 900] = (3000, 0)
+    hit = RC.classes_hit(x, HIT_MASKS, [RC.T] * 3, (1, 1))
+    assert {"6", "7", "9"} <= hit and {lab[0] for lab in hit} >= {"1", "2"} and "5" in RC.classes_hit(x, HIT_MASKS, [RC.T] * 3, (2,))
+    x.setflags(write=False)
+    return x
+
+
+def constant_stretches(st, tchain):
+    """The stretches of consecutive hits that a merged track's runs of one value give, counted from the track's bits alone: over
+    a maximal run [u, v] of the value w every tap of the samples u + span .. v reads w, so each of them is a hit if w is the
+    pattern's one bit value (d = 0) or, under BOTH, the other (d = P) -> [(first, last sample)], chain-relative, 65 and longer."""
+    w_hit = {st.bit[0]} | ({1 - st.bit[0]} if st.both else set())
+    edges = np.flatnonzero(np.diff(tchain.bits.astype(np.int8))) + 1
+    out = []
+    for u, e in zip(np.concatenate([[0], edges]), np.concatenate([edges, [len(tchain.bits)]])):
+        if int(tchain.bits[u]) in w_hit and e - (u + st.span) >= 65:
+            out.append((int(u) + st.span, int(e) - 1))
+    return out
+
+
+@pytest.mark.parametrize("rate", [96000, 8960])
+@pytest.mark.parametrize("pattern,both", [(0x00, False), (0xFF, True)])
+def test_tracks_of_one_value_give_exact_hit_counts_at_every_edge(rate, pattern, both):
+    """The masks j0, j1 and `mask`, the `g &=` cut-off behind a run and the two stores, at every edge at once: the all-zero
+    pattern, then the all-one pattern under BOTH, with E = 0, at a span of 28 (inside one lane's word) and of 300.  The restated
+    tracks of the `const` stretches are constant as hit_rows says (the CPU run of constant_stretches showed it), so the patterns
+    stay all-zero and all-one.  Besides run_plan's byte-for-byte comparison: several chains have a stretch of 65 and more
+    consecutive hits, whose length follows from the track's bits alone; one crosses sample B, which is a block boundary inside the
+    uncut submit and the cut of (1, 1); the matches over every stretch number its length, in both."""
+    st = sync.Settings(rate, pattern, 8, 0, both)
+    assert st.span == (28 if rate == 96000 else 300) and st.pattern in (0, 0xFF)
+    plans = [RC.make_plan(hit_rows(), 0x2F, HIT_MASKS, sizes, L=5, centres=HIT_CENTRES, drains=[None] * len(sizes), measure=("track",),
+                          sync=st) for sizes in ((2,), (1, 1))]
+    ref = RC.restate(plans[0], (2,), measure=("track",))
+    tch, sch = RC.merged("track", [ref[0]["track"]]), RC.merged("sync", [ref[0]["sync"]])
+    want = [(i, a, b) for i, t in enumerate(tch) for a, b in constant_stretches(st, t)]
+    assert len({i for i, _, _ in want}) >= 3, want
+    across = [(i, a, b) for i, a, b in want if int(tch[i]["start_sample"]) + a < B - 32 and int(tch[i]["start_sample"]) + b > B + 32]
+    assert across and {int(tch[i]["stream"]) for i, _, _ in across} >= {0}
+    if both:  # tracks of both values match
+        assert {int(tch[i].bits[a]) for i, a, _ in want} == {0, 1}
+    for i, a, b in want:
+        assert sch[i].bits[a:b + 1].all() and int(sch[i]["n_hits"]) >= b - a + 1
+    for p in plans:
+        reads = RC.run_plan(p)
+        if len(p["sizes"]) == 2:  # the stretch across the cut: ones at the first piece's last sample and the second's first
+            first, second = reads[0]["sync"], reads[1]["sync"]
+            o = first[0][(first[0]["stream"] == 0) & (first[0]["flags"] & capture.RUN_OPEN != 0)]
+            c = second[0][(second[0]["stream"] == 0) & (second[0]["flags"] & capture.RUN_CONTINUES != 0)]
+            assert len(o) == len(c) == 1 and sync.bits_of(o[0], first[1])[-65:].all() and sync.bits_of(c[0], second[1])[:65].all()
+        got = RC.merged("sync", pieces(reads, "sync"))
+        RC.same_chains("sync", got, sch, "sizes %s" % (p["sizes"],))
+        for i, a, b in want:
+            assert int(np.count_nonzero(got[i].bits[a:b + 1])) == b - a + 1, (p["sizes"], i, a, b)
