@@ -21,7 +21,7 @@ row is built from (classes_hit() measures them back from capture.captures on the
 The burst sync (sync.h, tfrec_amd/sync.py) is a fifth measurement, behind the track: about half the rounds have one.  Its settings
 (draw_sync) come from a generator of their own, seeded (seed, SYNC_STREAM), so that a seed's rows, masks, cuts, drains, resets, caps,
 L and centres are what they were without it; a round with a sync measures the track too.  Every submit's records and match bitmap
-are compared with the restatement on the track the same context returned (test_sync_gpu.read_sync), under the plan's caps as the
+are compared with the restatement on the track the same context returned (recorder.read_sync), under the plan's caps as the
 header's Bits paragraph states them, and the merged chains with the restatement on the uncut rows.  SYNC_CLASSES names the sync's
 own edges; sync_classes_hit() measures them back from the restatement on a plan.
 """
@@ -35,31 +35,20 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 for _p in (_HERE, os.path.join(_HERE, "..")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
-import test_capture_gpu as TC  # noqa: E402
-import test_clock_gpu as TK  # noqa: E402
-import test_envelope_gpu as TE  # noqa: E402
-import test_sync_gpu as TS  # noqa: E402
-import test_track_gpu as TT  # noqa: E402
-from test_clock_cpu import keyed  # noqa: E402
-from test_sync_cpu import stripped as sync_stripped  # noqa: E402
-from test_track_cpu import stripped  # noqa: E402
+import recorder as R  # noqa: E402
+from recorder import B, CONT, OPEN, STAGES, T, last_pairs, raises, same_chains, same_records, same_table, zeros  # noqa: E402, F401
+from recorder_rows import keyed, quiet  # noqa: E402
 from tfrec_amd import api, burst, capture, clock, decin, envelope, levels, sync, track  # noqa: E402
 
-B = api.BLOCK_DEC
-T = 100  # the rows' threshold: their quiet parts stay below it
 EDGE64 = (0, 1, 31, 32, 33, 63)
 CTX_MASKS = (0x02, 0x01, 0x20, 0x08, 0x2F)
 MEASURES = ("meter", "envelope", "clock", "track")
-MODULES = {"meter": burst, "envelope": envelope, "clock": clock, "track": track, "sync": sync}
 DENSE_PERIOD = 357  # a window of mask 0x02 (356) and the one uncaptured sample behind it
 ZONE = 1100  # the samples ahead of a block boundary kept for the boundary's own item
-TABLE_FIELDS = ("stream", "flags", "start_sample", "n_samples", "thresh")
 SEEDS = (12, 19, 21, 24, 35, 91)  # the fixed campaign of tests/test_recorder_campaign_gpu.py: ROUNDS rounds each (35 and 91 came
 # with the sync: a store with D < 0, a continuing piece with nothing defined, a hit behind 2047 carried bits)
 ROUNDS = 6
 SYNC_STREAM = 0x73796E63  # the sync's settings are drawn from a generator of their own, seeded (seed, this): the plan's draws stay
-CONT, OPEN = capture.RUN_CONTINUES, capture.RUN_OPEN
-quiet = TE.quiet
 
 
 def window(mask):
@@ -309,7 +298,7 @@ def restate(p, sizes, reset=None, measure=(), caps=True):
     alone is a capped context's (caps: the plan's, if it has any): it looks at the delivered records -- those below max_runs -- and
     at the runs that fit max_samples, and carries what these leave (the header's Bits paragraph)."""
     n, x = p["n"], p["dec"]
-    cst, lst, base, prev, tst, pos, out = [None] * n, [None] * n, [0] * n, TE.zeros(n), None, 0, []
+    cst, lst, base, prev, tst, pos, out = [None] * n, [None] * n, [0] * n, zeros(n), None, 0, []
     sst = sync.fresh_state(n)
     mr, ms = (p.get("cap") if caps else None) or (None, None)
     for k, nb in enumerate(sizes):
@@ -340,7 +329,7 @@ def restate(p, sizes, reset=None, measure=(), caps=True):
                 srecs, swords, nxt = sync.syncs(recs[:mr], words, p["sync"], sst, n, max_samples=ms)
                 e["sync"], e["sync_state"], sst = (srecs, swords), sst, nxt
         out.append(e)
-        prev, pos, base = TE.last_pairs(decs), pos + nb, [v + nb * B for v in base]
+        prev, pos, base = last_pairs(decs), pos + nb, [v + nb * B for v in base]
     return out
 
 
@@ -596,94 +585,56 @@ def sync_classes_hit(p):
 
 
 # ---- one plan on the GPU
-def same_records(got, want, label):
-    """Byte for byte; the message names the first differing record and field."""
-    assert got.dtype == want.dtype and len(got) == len(want), "%s: %d records, want %d" % (label, len(got), len(want))
-    for f in want.dtype.names:
-        bad = np.flatnonzero((got[f] != want[f]).reshape(len(got), -1).any(axis=1))
-        assert len(bad) == 0, "%s: record %d field %s: got %s want %s" % (
-            label, bad[0], f, got[f][bad[0]].tolist(), want[f][bad[0]].tolist())
-    assert got.tobytes() == want.tobytes(), label
-
-
-def _same_table(got, runs, label):
-    for f in TABLE_FIELDS:
-        bad = np.flatnonzero(got[f] != runs[f][:len(got)]) if len(got) <= len(runs) else [0]
-        assert len(bad) == 0, "%s: record %d repeats table field %s wrongly" % (label, bad[0], f)
-
-
 def _check_submit(r, p, k, measure, states, newest):
     """Every read of the oldest undrained submit, which is the plan's k-th; states: the track's and the sync's state ahead of it
-    -> (what was read, the two states behind it)."""
+    -> (what was read, the two states behind it).  The reads are recorder.py's: each holds its records to the restatement on what
+    the context itself returned; here they are also held to the restatement on the generated rows."""
     tst, sst = states
     e = p["expect"][k]
     nb, decs, base, prev = e["nb"], e["decs"], e["base"], e["prev"]
-    label = "submit %d" % k
     cap = p["cap"] or full_cap(p)
     wr, wp, over = capture.prefix(e["table"][0], e["table"][1], *cap)
     got = dict(table=r.read_captures(allow_overflow=True))
-    assert r.capture_overflow == over and r.capture_totals == (len(e["table"][0]), len(e["table"][1])), "%s: totals %s overflow %s" % (
-        label, r.capture_totals, r.capture_overflow)
-    TC.assert_tables(got["table"], (wr, wp), label)  # independent of the context: the restatement on the generated rows
+    assert r.capture_overflow == over and r.capture_totals == (len(e["table"][0]), len(e["table"][1])), "totals %s overflow %s" % (
+        r.capture_totals, r.capture_overflow)
+    R.assert_tables(got["table"], (wr, wp))  # independent of the context: the restatement on the generated rows
     got["levels"] = r.read_levels()
     for f in levels.LEVEL_DTYPE.names:
-        assert np.array_equal(got["levels"][f], e["levels"][f]), "%s: levels field %s" % (label, f)
+        assert np.array_equal(got["levels"][f], e["levels"][f]), "levels field %s" % f
     if newest:  # (tfrec_amd_read_decimated returns the last submit's samples)
         for s in range(p["n"]):
-            assert np.array_equal(r.decimated(s, nb * B), decs[s]), "%s: stream %d's decimated samples" % (label, s)
-    full = e["table"][0][:cap[0]]
+            assert np.array_equal(r.decimated(s, nb * B), decs[s]), "stream %d's decimated samples" % s
     if "meter" in measure:
-        m = r.read_bursts(allow_overflow=over)
-        assert r.burst_total == len(e["table"][0])
-        _same_table(m, full, label + " meter")
-        same_records(m, burst.bursts(decs, m[list(TABLE_FIELDS)], prev, base=base), label + " meter")
-        got["meter"] = m
+        got["meter"] = R.read_meter(r, nb, prev, base, overflow=over, decs=decs)[0]
     if "envelope" in measure:
-        got["envelope"] = TE.read_submit(r, nb, prev, base, overflow=over, decs=decs)[0]
-        _same_table(got["envelope"], full, label + " envelope")
+        got["envelope"] = R.read_envelope(r, nb, prev, base, overflow=over, decs=decs)[0]
     if "clock" in measure:
-        got["clock"] = TK.read_submit(r, nb, base, overflow=over, decs=decs)[0]
-        _same_table(got["clock"], full, label + " clock")
+        got["clock"] = R.read_clock(r, nb, base, overflow=over, decs=decs)[0]
     if "track" in measure:
-        recs, words, _, nxt = TT.read_submit(r, nb, base, p["L"], p["centres"], tst, overflow=over, decs=decs)
-        _same_table(recs, full, label + " track")
+        recs, words, _, nxt = R.read_track(r, nb, base, p["L"], p["centres"], tst, overflow=over, decs=decs)
         if over:  # the chains' carried state is the whole table's, not the delivered prefix's
             thr = [np.repeat(v["thresh"].astype(np.int64), B) for v in e["levels"]]
             nxt = track.tracks(decs, thr, e["table"][0], p["L"], p["centres"], tst, base=base)[2]
         got["track"], tst = (recs, words), nxt
         if sync_on(p, measure):
-            # test_sync_gpu.read_sync's rule: the restatement on the track records and words this context returned for the submit.
-            # The state it returns is what the delivered records leave -- behind an overflow too: a run that does not fit
-            # max_samples leaves H = 0, and so does an OPEN run beyond max_runs, which has no record
-            srecs, swords, sst = TS.read_sync(r, p["sync"], sst, recs, words, overflow=over)
-            assert r.sync_total == len(e["table"][0]), "%s sync: total %d" % (label, r.sync_total)
-            _same_table(srecs, full, label + " sync")
-            assert len(swords) == (len(wp) + 31) // 32, "%s sync: %d words for %d delivered pairs" % (label, len(swords), len(wp))
+            # read_sync's rule: the restatement on the track records and words this context returned for the submit.  The state
+            # it returns is what the delivered records leave -- behind an overflow too: a run that does not fit max_samples leaves
+            # H = 0, and so does an OPEN run beyond max_runs, which has no record
+            srecs, swords, sst = R.read_sync(r, p["sync"], sst, recs, words, overflow=over)
+            assert len(swords) == (len(wp) + 31) // 32, "sync: %d words for %d delivered pairs" % (len(swords), len(wp))
             got["sync"] = (srecs, swords)
-    for m in tuple(measure) + (("sync",) if "sync" in got else ()):
-        n_rec = len(got[m][0] if m in ("track", "sync") else got[m])
-        assert n_rec == len(full), "%s %s: %d records of %d" % (label, m, n_rec, len(full))
+    full = e["table"][0][:cap[0]]
+    for m in tuple(measure) + (("sync",) if "sync" in got else ()):  # under an overflow too: the total, and the table's prefix
+        recs, total = got[m][0] if m in ("track", "sync") else got[m], getattr(r, STAGES[m].total)
+        assert total == len(e["table"][0]), "%s: a total of %d for %d runs" % (m, total, len(e["table"][0]))
+        same_table(recs, full, m)
+        assert len(recs) == len(full), "%s: %d records of %d" % (m, len(recs), len(full))
     return got, (tst, sst)
 
 
 def merged(m, pieces, restarts=None):
     """A measurement's chains over the submits' pieces, by stream (within a stream: in the order of the samples)."""
-    return sorted(MODULES[m].chains(pieces, restarts), key=lambda c: int(c["stream"]))
-
-
-def same_chains(m, got, want, label):
-    assert len(got) == len(want), "%s %s: %d chains, want %d" % (label, m, len(got), len(want))
-    for i, (a, b) in enumerate(zip(got, want)):
-        if m in ("track", "sync"):  # the record without its place in its own submit's pool, and the bits
-            strip = stripped if m == "track" else sync_stripped
-            assert strip(a.rec) == strip(b.rec), "%s %s: chain %d: got %s want %s" % (label, m, i, strip(a.rec), strip(b.rec))
-            assert np.array_equal(a.bits, b.bits), "%s %s: chain %d (stream %d from %d): bits" % (
-                label, m, i, a["stream"], a["start_sample"])
-        else:
-            for f in a.dtype.names:
-                assert np.array_equal(a[f], b[f]), "%s %s: chain %d (stream %d from %d) field %s: got %s want %s" % (
-                    label, m, i, a["stream"], a["start_sample"], f, a[f].tolist(), b[f].tolist())
-            assert a.tobytes() == b.tobytes()
+    return sorted(STAGES[m].module.chains(pieces, restarts), key=lambda c: int(c["stream"]))
 
 
 def run_plan(p, measure=None, receiver=None):
@@ -697,14 +648,12 @@ def run_plan(p, measure=None, receiver=None):
             own = p["configured"]
             r.configure_streams(own, types_mask=[p["masks"][s] for s in own], thresh=[p["thresh"][s] for s in own])
         r.enable_capture(*(p["cap"] or full_cap(p)))
-        for m in measure:
-            {"meter": r.enable_burst_meter, "envelope": r.enable_burst_envelope, "clock": r.enable_burst_clock,
-             "track": lambda: r.enable_burst_track(p["L"])}[m]()
+        R.enable(r, {m: (p["L"],) if m == "track" else () for m in measure})
         if "track" in measure:
             r.set_burst_track_centre(range(n), p["centres"])
         if sync_on(p, measure):
             st = p["sync"]
-            r.enable_burst_sync(st.rate, st.pattern, st.P, st.E, st.both)
+            R.enable(r, {"sync": (st.rate, st.pattern, st.P, st.E, st.both)})
         reads, states, pos = [], (None, None), 0
         for k, nb in enumerate(sizes):
             if p["reset"] and p["reset"][0] == k:
@@ -713,10 +662,13 @@ def run_plan(p, measure=None, receiver=None):
             pos += nb
             keep = p["drains"][k] if k + 1 < len(sizes) else 0
             while keep is not None and k + 1 - len(reads) > keep:
-                got, states = _check_submit(r, p, len(reads), measure, states, newest=len(reads) == k)
+                try:
+                    got, states = _check_submit(r, p, len(reads), measure, states, newest=len(reads) == k)
+                except AssertionError as err:
+                    raise AssertionError("submit %d: %s" % (len(reads), err)) from None
                 reads.append(got)
                 r.drain()
-        TE.raises(api.E_STATE, r.read_captures)  # nothing undrained
+        raises(api.E_STATE, r.read_captures)  # nothing undrained
     overflowed = any(capture.prefix(e["table"][0], e["table"][1], *(p["cap"] or full_cap(p)))[2] for e in p["expect"])
     if measure and len(sizes) > 1 and not overflowed:
         j = p["reset"][0] if p["reset"] else None

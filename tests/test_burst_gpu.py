@@ -2,64 +2,37 @@
 
 The records are compared with the restatement tfrec_amd/burst.py run on the context's OWN decimated samples
 (tfrec_amd_read_decimated) and its own run table, so the front end and the recorder ahead of the meter are whatever the context
-runs.  The aimed scene is test_capture_gpu's: eight streams of four blocks with a run across a block boundary, runs ending on word
-edges, runs open at the submit's last 1, 3 and 5 samples, a noise row that stays inside its window and a quiet row.  Everything is an
-exact integer; nothing here has a tolerance."""
+runs (recorder.read_meter).  The aimed scene is recorder_rows.scene: eight streams of four blocks with a run across a block
+boundary, runs ending on word edges, runs open at the submit's last 1, 3 and 5 samples, a noise row that stays inside its window and
+a quiet row.  Everything is an exact integer; nothing here has a tolerance."""
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import parity
-import test_capture_gpu as TC
+import recorder as R
+from recorder import B, cli_lines, last_pairs, raises, read_meter, same_chains, same_records, zeros
+from recorder_rows import CTX_TYPES, M, N, NB, scene
 from tfrec_amd import api, burst, capture, decin, resample, synth
 
 pytestmark = pytest.mark.gpu
 
-B = api.BLOCK_DEC
-NB, M, N = TC.NB, TC.M, TC.N
-FIELDS = [f for f in burst.BURST_DTYPE.names]
-
-
-def raises(code, f, *a, **kw):
-    with pytest.raises(api.TfrecAmdError) as e:
-        f(*a, **kw)
-    assert e.value.code == code, e.value
-
 
 def receiver(**kw):
-    r = TC.receiver(**kw)
+    r = R.receiver(**kw)
     r.enable_burst_meter()
     return r
 
 
-def assert_records(got, want, label=""):
-    assert got.dtype == burst.BURST_DTYPE and len(got) == len(want), "%s: %d records, want %d" % (label, len(got), len(want))
-    for f in FIELDS:
-        assert np.array_equal(got[f], want[f]), "%s %s: first differing record %d" % (
-            label, f, int(np.flatnonzero((got[f] != want[f]).reshape(len(got), -1).any(axis=1))[0]))
-    assert (got["hist"].sum(axis=1) == got["n_products"]).all(), label
-
-
-def last_pairs(decs):
-    return [np.asarray(d).reshape(-1, 2)[-1] for d in decs]
-
-
-def zeros(n):
-    return [np.zeros(2, dtype=np.int16)] * n
-
-
 @functools.lru_cache(maxsize=None)
 def one_submit(serial=False):
-    """-> (records, the table, every stream's decimated samples, events)."""
+    """-> (records, the table, every stream's decimated samples, events); the records are the restatement's."""
     with receiver(serial_chains=serial) as r:
-        r.submit(TC.scene())
-        decs = [r.decimated(s, M) for s in range(N)]
-        runs, _ = r.read_captures()
-        recs = r.read_bursts()
-        assert r.burst_total == len(runs)
+        r.submit(scene())
+        r.read_captures()  # (refused had the recorder overflowed: read_meter then holds the records to the whole table and total)
+        recs, decs, runs = read_meter(r, NB, zeros(N), [0] * N)
         assert r.read_bursts().tobytes() == recs.tobytes()  # reading pops nothing
         ev = r.drain()
         raises(api.E_STATE, r.read_bursts)  # nothing undrained
@@ -68,7 +41,7 @@ def one_submit(serial=False):
 
 def test_the_records_equal_the_restatement_on_the_aimed_scene():
     recs, runs, decs, ev = one_submit()
-    assert_records(recs, burst.bursts(decs, runs, zeros(N)))
+    same_records(recs, burst.bursts(decs, runs, zeros(N)))  # (on the table itself; read_meter: on what the records repeat of it)
     of = lambda s: recs[recs["stream"] == s]  # noqa: E731
     assert len(of(0)) == 0 and len(of(1)) == 1  # the quiet row; the run across the boundary between blocks 1 and 2 ...
     r1 = of(1)[0]
@@ -78,53 +51,47 @@ def test_the_records_equal_the_restatement_on_the_aimed_scene():
     r6 = of(6)[-1]  # the noise row never leaves its window: one run over (nearly) all four blocks, spread over their workgroups
     assert r6["n_samples"] >= M - 16 and r6["n_products"] > 3 * B
     assert burst.summary(r1) is not None
-    assert parity.sort_events(ev).tobytes() == parity.sort_events(TC.one_submit()[2]).tobytes()  # the events do not notice
+    assert parity.sort_events(ev).tobytes() == parity.sort_events(R.one_submit()[2]).tobytes()  # the events do not notice
 
 
 def test_one_plus_three_queued_before_the_first_read_and_the_merged_chains():
     whole, wruns, decs, _ = one_submit()
-    parts = parity.cut(TC.scene(), (1, 3))
+    parts = parity.cut(scene(), (1, 3))
     with receiver(max_blocks=3) as r:
         for p in parts:
             r.submit(p)
-        got = []
-        for _ in parts:
-            got.append((r.read_captures()[0], r.read_bursts()))
+        got, prev, pos = [], zeros(N), 0
+        for k, nb in enumerate((1, 3)):  # (the front end does not depend on the cut: the uncut context's samples)
+            d = [x[2 * pos * B:2 * (pos + nb) * B] for x in decs]
+            r.read_captures()  # (nothing overflowed)
+            recs, _, runs = read_meter(r, nb, prev, [pos * B] * N, decs=d)
+            if k == 1:  # the CONTINUES piece used prevdec: with (0, 0) ahead of it the restatement counts one product less
+                c = np.flatnonzero(runs["flags"] & capture.RUN_CONTINUES)
+                assert len(c) >= 1 and (runs["stream"][c] == 6).all()
+                blind = burst.bursts(d, runs, zeros(N), base=[pos * B] * N)
+                assert (blind["n_products"][c] == recs["n_products"][c] - 1).all()
+            got.append(recs)
+            prev, pos = last_pairs(d), pos + nb
             r.drain()
-    prev, pos = zeros(N), 0
-    for k, nb in enumerate((1, 3)):  # (the front end does not depend on the cut: the uncut context's samples)
-        d = [x[2 * pos * B:2 * (pos + nb) * B] for x in decs]
-        want = burst.bursts(d, got[k][0], prev, base=[pos * B] * N)
-        assert_records(got[k][1], want, "submit %d" % k)
-        if k == 1:  # the CONTINUES piece used prevdec: with (0, 0) ahead of it the restatement counts one product less
-            c = np.flatnonzero(got[k][0]["flags"] & capture.RUN_CONTINUES)
-            assert len(c) >= 1 and (got[k][0]["stream"][c] == 6).all()
-            blind = burst.bursts(d, got[k][0], zeros(N), base=[pos * B] * N)
-            assert (blind["n_products"][c] == want["n_products"][c] - 1).all()
-        prev, pos = last_pairs(d), pos + nb
-    merged, uncut = burst.chains([g[1] for g in got]), burst.chains([whole])
     key = lambda r: (int(r["stream"]), int(r["start_sample"]))  # noqa: E731
-    merged, uncut = sorted(merged, key=key), sorted(uncut, key=key)
+    merged, uncut = sorted(burst.chains(got), key=key), sorted(burst.chains([whole]), key=key)
     assert len(merged) == len(uncut) == len(whole)
-    for a, b in zip(merged, uncut):
-        assert a.tobytes() == b.tobytes(), key(a)
+    same_chains("meter", merged, uncut, "1 + 3")
 
 
 def test_a_reset_between_submits_gives_no_continues_and_leaves_the_first_product_out():
-    parts = parity.cut(TC.scene(), (2, 2))
+    parts = parity.cut(scene(), (2, 2))
     with receiver(max_blocks=2) as r:
         r.submit(parts[0])
-        d0 = [r.decimated(s, 2 * B) for s in range(N)]
-        runs0, got0 = r.read_captures()[0], r.read_bursts()
+        r.read_captures()  # (nothing overflowed)
+        got0, d0, _ = read_meter(r, 2, zeros(N), [0] * N)
         r.drain()
         r.reset_streams([1, 6])
         r.submit(parts[1])
-        d1 = [r.decimated(s, 2 * B) for s in range(N)]
-        runs1, got1 = r.read_captures()[0], r.read_bursts()
+        base = [0 if s in (1, 6) else 2 * B for s in range(N)]  # a reset stream counts from 0 again
+        r.read_captures()
+        got1, _, _ = read_meter(r, 2, last_pairs(d0), base)
         r.drain()
-    assert_records(got0, burst.bursts(d0, runs0, zeros(N)), "before the reset")
-    base = [0 if s in (1, 6) else 2 * B for s in range(N)]  # a reset stream counts from 0 again
-    assert_records(got1, burst.bursts(d1, runs1, last_pairs(d0), base=base), "after the reset")
     r6 = got1[got1["stream"] == 6]
     assert not (r6["flags"] & capture.RUN_CONTINUES).any() and r6[0]["start_sample"] < 16
     assert r6[0]["n_products"] <= r6[0]["n_samples"] - 1  # its first sample has no product
@@ -137,21 +104,20 @@ def test_a_reset_between_submits_gives_no_continues_and_leaves_the_first_product
 def test_overflow_delivers_the_prefix_and_a_pool_of_one_pair_delivers_everything():
     whole, wruns, decs, _ = one_submit()
     with receiver(cap=(len(wruns) - 1, N * M)) as r:
-        r.submit(TC.scene())
+        r.submit(scene())
         raises(api.E_OVERFLOW, r.read_bursts)
         got = r.read_bursts(allow_overflow=True)
         assert r.burst_total == len(wruns)
-        assert_records(got, whole[:-1], "the prefix")
+        same_records(got, whole[:-1], "the prefix")
         r.drain()
-        r.submit(TC.scene()[:, :api.BLOCK_BYTES])  # the next submit -- one block, so that it fits -- is exact, CONTINUES included
-        d = [r.decimated(s, B) for s in range(N)]
-        runs2, got2 = r.read_captures()[0], r.read_bursts()
+        r.submit(scene()[:, :api.BLOCK_BYTES])  # the next submit -- one block, so that it fits -- is exact, CONTINUES included
+        r.read_captures()  # (nothing overflowed)
+        got2, _, runs2 = read_meter(r, 1, last_pairs(decs), [M] * N)
         r.drain()
     assert (runs2["flags"] & capture.RUN_CONTINUES).any()
-    assert_records(got2, burst.bursts(d, runs2, last_pairs(decs), base=[M] * N), "behind the overflow")
     with receiver(cap=(4096, 1)) as r:  # the meter alone: the pool holds nothing, the table and the records are whole
-        r.submit(TC.scene())
-        assert_records(r.read_bursts(), whole, "a pool of one pair")
+        r.submit(scene())
+        same_records(r.read_bursts(), whole, "a pool of one pair")
         r.drain()
 
 
@@ -207,7 +173,8 @@ def test_hand_made_rows_on_a_channel_rate_context(n):
     per = [capture.captures(d, 0x2F, 500)[:2] for d in decs]
     runs = capture.table(per)[0]
     want = burst.bursts(decs, runs, zeros(n))
-    assert_records(got, want)
+    same_records(got, want)
+    assert (got["hist"].sum(axis=1) == got["n_products"]).all()
     assert (got["stream"] == runs["stream"]).all() and len(np.unique(got["stream"])) == n - len(range(5, n, 6))  # (row 5 is quiet)
     # the rows hold what they are meant to hold (the values: the restatement's, on the CPU)
     first = {int(s): got[got["stream"] == s] for s in range(len(rows))}
@@ -228,12 +195,7 @@ def check_plain(r, parts, types, thresh, submit=None):
     prev, pos, total, all_recs = zeros(n), 0, 0, []
     for p in parts:
         nb = submit(r, p) if submit else r.submit(p)
-        decs = [r.decimated(s, nb * B) for s in range(n)]
-        runs, got = r.read_captures(allow_overflow=True)[0], r.read_bursts()
-        if not r.capture_overflow:
-            assert len(runs) == len(got)
-        want = burst.bursts(decs, got[["stream", "flags", "start_sample", "n_samples", "thresh"]], prev, base=[pos * B] * n)
-        assert_records(got, want)
+        got, decs, _ = read_meter(r, nb, prev, [pos * B] * n)
         r.drain()
         prev, pos, total = last_pairs(decs), pos + nb, total + int(got["n_products"].sum())
         all_recs.append(got)
@@ -294,13 +256,12 @@ def test_a_submit_runs_replay_gives_the_recordings_records():
         total, rep = check_plain(r, [0, 1], 0x2F, 500, submit=submit)
     a, b = burst.chains(recs), burst.chains(rep)
     assert len(a) == len(b) >= 1 and total > 1000
-    for u, v in zip(a, b):
-        assert u.tobytes() == v.tobytes()
+    same_chains("meter", b, a, "the replay")
 
 
 def test_without_the_call_nothing_changes_and_a_failed_enable_leaves_the_context_as_it_was():
     n, mb = 3, 2
-    with api.Receiver(n, TC.CTX_TYPES, 500, 0, max_blocks=mb) as r:
+    with api.Receiver(n, CTX_TYPES, 500, 0, max_blocks=mb) as r:
         plain = r.memory()
         raises(api.E_INVAL, r.enable_burst_meter)  # no recorder
         raises(api.E_INVAL, r.read_bursts)
@@ -308,14 +269,14 @@ def test_without_the_call_nothing_changes_and_a_failed_enable_leaves_the_context
         r.enable_capture(64, 1024)
         rec = r.memory()
         raises(api.E_INVAL, r.read_bursts)  # the recorder alone: no meter
-        r.submit(TC.scene()[:n, :api.BLOCK_BYTES])
+        r.submit(scene()[:n, :api.BLOCK_BYTES])
         raises(api.E_INVAL, r.read_bursts)
         submitted = r.memory()  # (a host submit's staging is counted)
         raises(api.E_STATE, r.enable_burst_meter)  # after the first submit
         assert r.memory() == submitted
         runs_plain = r.read_captures()
         ev_plain = r.drain()
-    with api.Receiver(n, TC.CTX_TYPES, 500, 0, max_blocks=mb) as r:
+    with api.Receiver(n, CTX_TYPES, 500, 0, max_blocks=mb) as r:
         r.enable_capture(64, 1024)
         assert r.memory() == rec  # a recorder without the meter holds what it held
         r.enable_burst_meter()
@@ -324,7 +285,7 @@ def test_without_the_call_nothing_changes_and_a_failed_enable_leaves_the_context
         raises(api.E_INVAL, r.enable_burst_meter)  # a second call: refused, and nothing changes
         assert r.memory() == m
         raises(api.E_STATE, r.read_bursts)  # nothing undrained
-        r.submit(TC.scene()[:n, :api.BLOCK_BYTES])
+        r.submit(scene()[:n, :api.BLOCK_BYTES])
         nr = api.C.c_uint32(0)
         buf = np.full(320, 0x55, dtype=np.uint8)  # the caller's room too small: E_INVAL, nothing written, the count set
         assert r.L.tfrec_amd_read_bursts(r.h, buf.ctypes.data, 0, api.C.byref(nr)) == api.E_INVAL and (buf == 0x55).all()
@@ -333,17 +294,11 @@ def test_without_the_call_nothing_changes_and_a_failed_enable_leaves_the_context
         assert nr.value == len(recs) == len(runs_plain[0]) == 1
         runs = r.read_captures()
         ev = r.drain()
-    TC.assert_tables(runs, runs_plain)
+    R.assert_tables(runs, runs_plain)
     assert parity.sort_events(ev).tobytes() == parity.sort_events(ev_plain).tobytes()
 
 
 # ---- tfrec_gpu -M
-def cli_bursts(args, timeout=300):
-    out = subprocess.run([parity.CLI] + args, capture_output=True, text=True, timeout=timeout)
-    assert out.returncode == 0, out.stderr
-    return [ln for ln in out.stdout.splitlines() if ln.startswith("burst ")], parity.telegram_lines(out.stdout)
-
-
 def test_cli_burst_lines_of_the_golden_tfa_2_scene(tmp_path):
     parity.build_cli()
     z = np.load(os.path.join(parity.ROOT, "tests", "golden", "iq_tfa_2.npz"))
@@ -352,9 +307,9 @@ def test_cli_burst_lines_of_the_golden_tfa_2_scene(tmp_path):
     f = str(tmp_path / "tfa2.iq")
     x.tofile(f)
     base = ["-T", "2f", "-t", "500", "-b", "2"]
-    plain = cli_bursts(base + ["-L", f])
-    got = cli_bursts(["-M"] + base + ["-L", f])
-    assert plain[0] == [] and got[1] == plain[1] and len(got[1]) >= 1  # the telegrams do not notice
+    plain = cli_lines(base + ["-L", f], "burst")
+    got = cli_lines(["-M"] + base + ["-L", f], "burst")
+    assert plain["burst"] == [] and got["telegrams"] == plain["telegrams"] and len(got["telegrams"]) >= 1  # the telegrams do not notice
     # the restatement: the oracle's front end (the context's, bit for bit), capture.py and burst.py submit by submit (-b 2: 2 + 1)
     o = parity.fresh_oracle(x, 0x2F, 500, keep_dec=True)
     dec = o.dec().reshape(-1, 2)
@@ -365,12 +320,12 @@ def test_cli_burst_lines_of_the_golden_tfa_2_scene(tmp_path):
         recs.append(burst.bursts([part], runs, prev, base=[a * B]))
         prev = last_pairs([part])
     want = [burst.line(f, c) for c in burst.chains(recs)]
-    assert got[0] == want and len(want) >= 1
+    assert got["burst"] == want and len(want) >= 1
     assert any(ln.split()[5] != "-" for ln in want)
     # the same through a recycled slot beside a second file, and with the recorder's files beside it
     f2 = str(tmp_path / "short.iq")
     x[:2 * api.BLOCK_BYTES].tofile(f2)
-    slot = cli_bursts(["-M", "-n", "1"] + base + ["-L", f, "-L", f2])
-    assert [ln for ln in slot[0] if ln.split()[1] == f] == want
-    both = cli_bursts(["-M", "-S", str(tmp_path / "cap")] + base + ["-L", f])
-    assert both[0] == want and os.path.getsize(str(tmp_path / "cap") + ".0.cs16") > 0
+    slot = cli_lines(["-M", "-n", "1"] + base + ["-L", f, "-L", f2], "burst")
+    assert [ln for ln in slot["burst"] if ln.split()[1] == f] == want
+    both = cli_lines(["-M", "-S", str(tmp_path / "cap")] + base + ["-L", f], "burst")
+    assert both["burst"] == want and os.path.getsize(str(tmp_path / "cap") + ".0.cs16") > 0

@@ -2,7 +2,7 @@
 
 The run table and the pool are compared with the restatement tfrec_amd/capture.py run on the context's OWN decimated samples
 (tfrec_amd_read_decimated), so the front end ahead of the recorder is whatever the context runs; the events still equal the
-oracle's.  The scene, eight streams of four blocks, is aimed on the CPU (the oracle's front end is the context's, bit for bit) at
+oracle's.  The scene (recorder_rows.scene), eight streams of four blocks, is aimed on the CPU (the oracle's front end is the context's, bit for bit) at
 the layouts the kernels can get wrong; every aim is asserted again on what the context returned.
 
   0  near-silence: no run, an empty entry in the scan over the streams
@@ -21,114 +21,11 @@ import pytest
 
 import parity
 from oracle import oracle as O
+from recorder import B, assert_tables, one_submit, receiver
+from recorder_rows import CTX_TYPES, M, N, THRESH, TYPES, carrier, scene, want_tables
 from tfrec_amd import api, capture, levels, resample, synth
 
 pytestmark = pytest.mark.gpu
-
-B = api.BLOCK_DEC
-NB = 4
-M = NB * B
-N = 8
-TYPES = [0x2F, 0x2F, 0x02, 0x2F, 0x2F, 0x2F, 0x2F, 0x01]
-THRESH = [500, 500, 500, 500, 500, 500, 0, 500]
-CTX_TYPES = 0x2F
-
-
-def oracle_runs(x, types, thresh):
-    o = O.Oracle(types, thresh, 0, keep_dec=True)
-    o.process(x)
-    return capture.captures(o.dec(), types, thresh)[0]
-
-
-def burst(x, first, last):
-    """raw complex samples [first, last) of the u8 stream x: a carrier at full scale on I."""
-    x[2 * first:2 * last:2] = 228
-    x[2 * first + 1:2 * last:2] = 128
-
-
-def aim(base, place, measure, target, types, thresh, modulo=None):
-    """Move a burst until measure(runs) == target (modulo: in that residue class).  The front end decimates by four and is time
-    invariant, so one decimated sample is four raw ones: a few rounds, the noise around the edge permitting."""
-    pos = 0
-    for _ in range(12):
-        x = base.copy()
-        place(x, pos)
-        got = measure(oracle_runs(x, types, thresh))
-        d = target - got
-        if modulo:
-            d = (d + modulo // 2) % modulo - modulo // 2
-        if d == 0:
-            return x
-        pos += 4 * d
-    raise AssertionError("the burst did not settle")
-
-
-@functools.lru_cache(maxsize=None)
-def scene():
-    rng = np.random.default_rng(17)
-    n = NB * api.BLOCK_BYTES
-    quiet = lambda: rng.integers(126, 131, n, dtype=np.uint8)  # noqa: E731
-    end = lambda r: int(r["start_sample"] + r["n_samples"])  # noqa: E731
-    rows = [quiet()]
-    # 1: 300 decimated samples of carrier that end 100 ahead of block 2 -- the run crosses into it -- starting at bit 63 of a word
-    rows.append(aim(quiet(), lambda x, p: burst(x, 4 * (2 * B - 400) + p, 4 * (2 * B - 400) + p + 1200),
-                    lambda r: int(r[0]["start_sample"]) % 64, 63, TYPES[1], THRESH[1], modulo=64))
-    # 2: the burst's end moves until the run's last sample is bit 0 of a word
-    rows.append(aim(quiet(), lambda x, p: burst(x, 4 * 5000, 4 * 5300 + p), lambda r: (end(r[0]) - 1) % 64, 0, TYPES[2], THRESH[2],
-                    modulo=64))
-    for k, length in ((3, 1), (4, 3), (5, 5)):
-        rows.append(aim(quiet(), lambda x, p: burst(x, 4 * (M - 40) + p, n // 2), lambda r: int(r[-1]["start_sample"]), M - length,
-                        TYPES[k], THRESH[k]))
-    rows.append(rng.integers(0, 256, n, dtype=np.uint8))
-    rows.append(rows[1].copy())
-    iq = np.stack(rows)
-    iq.setflags(write=False)
-    return iq
-
-
-def want_tables(decs, states):
-    """The restatement on one submit's decimated samples -> (table, pool); states: each stream's carried state, updated.  Stream s
-    has the settings of the scene's row s mod N."""
-    per = []
-    for s, d in enumerate(decs):
-        runs, pool, states[s] = capture.captures(d, TYPES[s % N], THRESH[s % N], states[s])
-        per.append((runs, pool))
-    return capture.table(per)
-
-
-def receiver(max_blocks=NB, cap=(4096, N * M), n=N, **kw):
-    """n > N: stream s is set up for the scene's row s mod N."""
-    r = api.Receiver(n, CTX_TYPES, 500, 0, max_blocks=max_blocks, all_flushes=True, **kw)
-    own = [s for s in range(n) if s % N in (2, 6, 7)]
-    r.configure_streams(own, types_mask=[TYPES[s % N] for s in own], thresh=[THRESH[s % N] for s in own])
-    if cap:
-        r.enable_capture(*cap)
-    return r
-
-
-def assert_tables(got, want, label=""):
-    (runs, pool), (wruns, wpool) = got, want
-    assert runs.dtype == capture.RUN_DTYPE and pool.dtype == np.int16
-    for f in capture.RUN_DTYPE.names:
-        assert np.array_equal(runs[f], wruns[f]), "%s %s: got %s want %s" % (label, f, runs[f].tolist(), wruns[f].tolist())
-    assert pool.shape == wpool.shape and np.array_equal(pool, wpool), "%s pool" % label
-
-
-@functools.lru_cache(maxsize=None)
-def one_submit(serial=False):
-    """-> ((table, pool), the restatement's, events, every stream's decimated samples, thresholds read back, the final states)."""
-    with receiver(serial_chains=serial) as r:
-        r.submit(scene())
-        decs = [r.decimated(s, M) for s in range(N)]
-        got = r.read_captures()
-        assert r.capture_totals == (len(got[0]), len(got[1])) and not r.capture_overflow
-        again = r.read_captures()  # reading pops nothing
-        assert again[0].tobytes() == got[0].tobytes() and again[1].tobytes() == got[1].tobytes()
-        ev = r.drain()
-        th = [r.thresh(s) for s in range(N)]
-    states = [None] * N
-    want = want_tables(decs, states)
-    return got, want, ev, decs, th, states
 
 
 def test_table_and_pool_equal_the_restatement():
@@ -397,7 +294,7 @@ def test_a_failed_enable_leaves_the_context_as_it_was():
         m = r.memory()
         assert m["device_bytes"] - before["device_bytes"] == one_enable and m["pinned_host_bytes"] == before["pinned_host_bytes"]
         x = np.random.default_rng(23).integers(126, 131, api.BLOCK_BYTES, dtype=np.uint8)
-        burst(x, 4 * 3000, 4 * 3050)  # one run, the burst and the longest window behind it: it fits the pool
+        carrier(x, 4 * 3000, 4 * 3050)  # one run, the burst and the longest window behind it: it fits the pool
         assert 0 < check_plain(r, [x.reshape(1, -1)], CTX_TYPES, 500) <= 1024
 
 

@@ -5,7 +5,7 @@ behaviour under cutting, saturation, tfrec_gpu's merge (tfrec_amd/host/job.h, co
 and undefined-behaviour sanitizers), the struct and the exports, and what tfrec_gpu decides before it opens a device.
 
 The records are exact integers.  The only tolerances are on readings in Hz: 150 Hz against a nominal rate (the bin is 375 Hz; the
-largest error on the golden scenes is 101 Hz), and what rounding a rotated scene to int16 can move (see rotated())."""
+largest error on the golden scenes is 101 Hz), and what rounding a rotated scene to int16 can move (see recorder_rows.rotated())."""
 import ctypes as C
 import functools
 import os
@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import parity
+from recorder_rows import golden_dec, keyed, mx_rows, rotated, silent_rows
 from tfrec_amd import api, capture, clock, levels, synth
 from test_levels_cpu import crafted_dec
 
@@ -24,13 +25,6 @@ GOLDEN = ("tfa_1", "tfa_2", "tfa_3", "tx22", "whb")
 NOMINAL = dict(tfa_1=38400, tfa_2=17240, tfa_3=9600, tx22=8842, whb=6000)  # synth's bit rates
 CONT, OPEN = capture.RUN_CONTINUES, capture.RUN_OPEN
 MARGIN = 150  # Hz
-
-
-@functools.lru_cache(maxsize=None)
-def golden_dec(name):
-    d = np.load(os.path.join(parity.ROOT, "tests", "golden", "iq_%s.npz" % name))["dec"]
-    d.setflags(write=False)
-    return d
 
 
 def records(dec, types=0x2F, thresh=500, state=None, base=0):
@@ -64,16 +58,6 @@ def table(*rows):
 
 def same(a, b):
     assert a.dtype == b.dtype == clock.CLOCK_DTYPE and a.tobytes() == b.tobytes()
-
-
-def keyed(n_blocks, period, seed=1, amp=3000):
-    """A two-tone signal whose frequency flips every `period` samples, with a little noise -> int16 [2 M]."""
-    n = np.arange(n_blocks * B)
-    f = np.where((n // period) % 2 == 0, 1.0, -1.0) * 0.12
-    ph = np.cumsum(f)
-    rng = np.random.default_rng(seed)
-    z = amp * np.exp(2j * np.pi * ph) + rng.normal(0, 20, len(n)) + 1j * rng.normal(0, 20, len(n))
-    return np.stack([np.rint(z.real), np.rint(z.imag)], axis=1).astype(np.int16).reshape(-1)
 
 
 # ---- the restatement against its per-sample form
@@ -123,14 +107,6 @@ def test_every_golden_telegram_reads_its_nominal_rate(thresh):
             assert abs(hz - NOMINAL[name]) <= MARGIN and q >= 2500  # (a clean telegram: 25 or more)
             worst = max(worst, abs(hz - NOMINAL[name]))
     assert worst == 101  # the figure DESIGN.md 6s states; the nearest pair of protocols is 758 Hz apart
-
-
-def rotated(dec, hz):
-    """The scene shifted by hz, rounded to int16.  The rounding adds 0.29 LSB rms to samples that stand above the threshold of 500:
-    under 1e-3 of a product, so a reading moves by a Hz or two at most and quality_c by well under 1 per cent."""
-    z = dec.reshape(-1, 2).astype(np.float64)
-    y = (z[:, 0] + 1j * z[:, 1]) * np.exp(2j * np.pi * hz * np.arange(len(z)) / 384000.0)
-    return np.clip(np.stack([np.rint(y.real), np.rint(y.imag)], axis=1), -32768, 32767).astype(np.int16).reshape(-1)
 
 
 @pytest.mark.parametrize("hz", [20000, -35000])
@@ -185,13 +161,6 @@ def test_segment_edges():
     assert abs(hz - 38400) <= 375 and qual > 2500
 
 
-def silent_rows(n_blocks=1):
-    """Every other sample (0, 0) with a large pair between: the trigger stays up while every product is zero."""
-    z = np.zeros((n_blocks * B, 2), dtype=np.int16)
-    z[1::2] = (3000, -2000)
-    return z.reshape(-1)
-
-
 def test_a_silent_segment():
     dec = silent_rows()
     runs = capture.captures(dec, 0x2F, 500)[0]
@@ -204,28 +173,6 @@ def test_a_silent_segment():
     recs = clock.clocks([mixed], runs)
     same(recs, clock.clocks_bruteforce([mixed], runs))
     assert (recs[0]["n_segments"], recs[0]["n_silent"]) == (1, 6) and clock.summary(recs[0]) is not None
-
-
-def mx_rows():
-    """Segments whose largest product is 2^15 - 1, 2^15, 2^16 - 1, 2^16 and 2^31, the two constants of the issue (dot = 32761 and
-    33124), and the one sequence whose four factors are all -2^15: every product -65535 (1 + i), mx = 2^16 - 1."""
-    z = np.zeros((B, 2), dtype=np.int16)
-
-    def alternate(k, a, b):
-        z[SEG * k:SEG * (k + 1):2], z[SEG * k + 1:SEG * (k + 1):2] = a, b
-
-    alternate(0, (217, 0), (151, 0))  # 217 * 151 = 2^15 - 1
-    alternate(1, (128, 128), (128, 128))  # 2 * 128^2 = 2^15
-    alternate(2, (255, 0), (257, 0))  # 2^16 - 1
-    alternate(3, (256, 0), (256, 0))  # 2^16
-    alternate(4, (-32768, -32768), (-32768, -32768))  # 2^31
-    alternate(5, (181, 0), (181, 0))
-    alternate(6, (182, 0), (182, 0))
-    w = complex(-257, 0)
-    for m in range(SEG):  # z[m+1] conj(z[m]) = -65535 (1 + i)
-        z[SEG * 7 + m] = (round(w.real), round(w.imag))
-        w = -65535 * (1 + 1j) * w / abs(w) ** 2
-    return z.reshape(-1)
 
 
 def test_the_normalising_shift_at_its_steps():

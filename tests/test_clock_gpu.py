@@ -2,64 +2,25 @@
 
 The records are compared, byte for byte, with the restatement tfrec_amd/clock.py run on the context's OWN decimated samples
 (tfrec_amd_read_decimated) and its own run table, so the front end and the recorder ahead of the clock are whatever the context
-runs.  Channel-rate contexts (tfrec_amd_create_decimated) take hand-made decimated samples: the layouts the kernels can get wrong
-are placed exactly.  Everything is an exact integer; nothing here has a tolerance."""
+runs (recorder.read_clock).  Channel-rate contexts (tfrec_amd_create_decimated) take hand-made decimated samples: the layouts the
+kernels can get wrong are placed exactly.  Everything is an exact integer; nothing here has a tolerance."""
 import functools
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import parity
-import test_capture_gpu as TC
-import test_envelope_gpu as TE
-from test_clock_cpu import keyed, mx_rows, silent_rows
+import recorder as R
+from recorder import B, CONT, OPEN, W, cli_lines, hand_receiver, raises, read_clock, read_envelope, same_chains, same_records, zeros
+from recorder_rows import CTX_TYPES, N, NB, SEG, golden_iq, keyed, mx_rows, quiet, scene, silent_rows
 from tfrec_amd import api, burst, capture, clock, decin
 
 pytestmark = pytest.mark.gpu
-
-B = api.BLOCK_DEC
-SEG = clock.SEG
-W = 694  # the largest window of -T 2f
-T = 100  # the hand-made rows' threshold: their quiet parts stay below it (|I| + |Q| <= 80)
-CONT, OPEN = capture.RUN_CONTINUES, capture.RUN_OPEN
-FIELDS = list(clock.CLOCK_DTYPE.names)
-zeros, last_pairs, raises, golden_iq = TE.zeros, TE.last_pairs, TE.raises, TE.golden_iq
-
-
-def assert_records(got, want, label=""):
-    assert got.dtype == clock.CLOCK_DTYPE and len(got) == len(want), "%s: %d records, want %d" % (label, len(got), len(want))
-    for f in FIELDS:
-        assert np.array_equal(got[f], want[f]), "%s %s: first differing record %d: got %s want %s" % (
-            label, f, int(np.flatnonzero((got[f] != want[f]).reshape(len(got), -1).any(axis=1))[0]),
-            got[f].reshape(len(got), -1)[:, :6].tolist()[:8], want[f].reshape(len(got), -1)[:, :6].tolist()[:8])
-    assert got.tobytes() == want.tobytes(), label
-
-
-def read_submit(r, nb, base, overflow=False, decs=None):
-    """The oldest undrained submit of nb blocks: its records against the restatement on what the context itself returns ->
-    (records, every stream's decimated samples, the run table).  decs: that submit's decimated samples where a later submit is
-    queued behind it (tfrec_amd_read_decimated returns the last submit's)."""
-    n = r.n_streams
-    if decs is None:
-        decs = [r.decimated(s, nb * B) for s in range(n)]
-    runs = r.read_captures(allow_overflow=True)[0]
-    got = r.read_burst_clocks(allow_overflow=overflow)
-    table = got[["stream", "flags", "start_sample", "n_samples", "thresh"]]
-    if not r.capture_overflow:
-        assert len(runs) == len(got) == r.clock_total
-        for f in table.dtype.names:
-            assert np.array_equal(runs[f], got[f]), f
-    assert_records(got, clock.clocks(decs, table, base=base))
-    return got, decs, runs
+CLOCK = ("clock",)  # hand_receiver's stages
 
 
 # ---- hand-made rows on a channel-rate context
-def quiet(nb, seed):
-    return np.random.default_rng(seed).integers(-40, 41, size=(nb * B, 2)).astype(np.int16)
-
-
 @functools.lru_cache(maxsize=None)
 def hand_rows():
     """int16 [2, 2 B, 2].  A tone (every sample over the threshold) from a to b gives the run [a, b + W): its last W - 1 samples
@@ -81,19 +42,12 @@ def hand_rows():
     return rows
 
 
-def hand_receiver(n, nb, thresh=T, cap=None, **kw):
-    r = api.Receiver(n, 0x2F, thresh, 0, max_blocks=nb, decimated=True, **kw)
-    r.enable_capture(*(cap or (32 * n, 1)))
-    r.enable_burst_clock()
-    return r
-
-
 @functools.lru_cache(maxsize=None)
 def hand_uncut():
     rows = hand_rows()
-    with hand_receiver(2, 2) as r:
+    with hand_receiver(2, 2, CLOCK, levels=False) as r:
         r.submit(np.ascontiguousarray(rows))
-        got, decs, runs = read_submit(r, 2, [0, 0])
+        got, decs, runs = read_clock(r, 2, [0, 0])
         assert r.read_burst_clocks().tobytes() == got.tobytes()  # reading pops nothing
         r.drain()
         raises(api.E_STATE, r.read_burst_clocks)  # nothing undrained
@@ -124,13 +78,13 @@ def test_two_streams_of_two_blocks_of_hand_made_samples():
 def test_the_same_input_in_two_submits_and_the_merged_chains():
     whole = hand_uncut()
     rows = hand_rows()
-    with hand_receiver(2, 1) as r:
+    with hand_receiver(2, 1, CLOCK, levels=False) as r:
         for k in range(2):  # both queued before the first read
             r.submit(np.ascontiguousarray(rows[:, k * B:(k + 1) * B]))
         got = []
         for k in range(2):
             part = decin.clamp(rows[:, k * B:(k + 1) * B])  # (a channel-rate context's samples are its input, clamped: hand_uncut)
-            got.append(read_submit(r, 1, [k * B] * 2, decs=[part[s].reshape(-1) for s in range(2)])[0])
+            got.append(read_clock(r, 1, [k * B] * 2, decs=[part[s].reshape(-1) for s in range(2)])[0])
             r.drain()
     c = got[1][(got[1]["flags"] & CONT) != 0]
     assert c["stream"].tolist() == [1] and c[0]["start_sample"] == B and c[0]["n_segments"] == 8
@@ -139,17 +93,16 @@ def test_the_same_input_in_two_submits_and_the_merged_chains():
     key = lambda r: (int(r["stream"]), int(r["start_sample"]))  # noqa: E731
     merged, uncut = sorted(clock.chains(got), key=key), sorted(clock.chains([whole]), key=key)
     assert len(merged) == len(uncut) == len(whole)
-    for a, b in zip(merged, uncut):
-        assert a.tobytes() == b.tobytes(), key(a)
+    same_chains("clock", merged, uncut, "1 + 1")
 
 
 def test_an_auto_stream_of_eight_blocks():
     nb = 8
     rng = np.random.default_rng(31)
     x = np.stack([rng.integers(-400, 401, size=(nb * B, 2)), rng.integers(-330, 331, size=(nb * B, 2))]).astype(np.int16)
-    with hand_receiver(2, nb, thresh=0) as r:
+    with hand_receiver(2, nb, CLOCK, levels=False, thresh=0) as r:
         r.submit(x)
-        got, decs, runs = read_submit(r, nb, [0, 0])
+        got, decs, runs = read_clock(r, nb, [0, 0])
         r.drain()
     r0 = got[got["stream"] == 0]
     assert len(r0) == 1 and r0[0]["n_samples"] >= nb * B - 16 and r0[0]["flags"] == OPEN
@@ -164,9 +117,9 @@ def test_stream_counts_across_a_waves_end(n):
              keyed(nb, 16, seed=6, amp=9000).reshape(-1, 2), quiet(nb, 43)]  # rows 0 .. 2 never leave their window
     kinds[0][0] = (300, 300)  # (... from the first sample on)
     x = np.ascontiguousarray(np.stack(kinds)[np.arange(n) % len(kinds)])
-    with hand_receiver(n, nb) as r:
+    with hand_receiver(n, nb, CLOCK, levels=False) as r:
         r.submit(x)
-        got, decs, runs = read_submit(r, nb, [0] * n)
+        got, decs, runs = read_clock(r, nb, [0] * n)
         r.drain()
     assert got["stream"].tolist() == [s for s in range(n) if s % 4 != 3]  # (row 3 is quiet)
     assert (got["n_samples"] == nb * B).all() and (got["n_segments"] == 8 * nb).all() and (got["flags"] == OPEN).all()
@@ -177,7 +130,7 @@ def test_stream_counts_across_a_waves_end(n):
 
 # ---- the other kinds of context
 def scene_receiver(**kw):
-    r = TC.receiver(**kw)
+    r = R.receiver(**kw)
     r.enable_burst_clock()
     return r
 
@@ -185,22 +138,22 @@ def scene_receiver(**kw):
 @functools.lru_cache(maxsize=None)
 def scene_uncut():
     with scene_receiver() as r:
-        r.submit(TC.scene())
-        got, decs, runs = read_submit(r, TC.NB, [0] * TC.N)
+        r.submit(scene())
+        got, decs, runs = read_clock(r, NB, [0] * N)
         ev = r.drain()
     return got, decs, runs, ev
 
 
 def test_a_reset_mid_chain_drops_the_chain():
-    parts = parity.cut(TC.scene(), (2, 2))
+    parts = parity.cut(scene(), (2, 2))
     with scene_receiver(max_blocks=2) as r:
         r.submit(parts[0])
-        got0, d0, _ = read_submit(r, 2, [0] * TC.N)
+        got0, d0, _ = read_clock(r, 2, [0] * N)
         r.drain()
         r.reset_streams([1, 6])
         r.submit(parts[1])
-        base = [0 if s in (1, 6) else 2 * B for s in range(TC.N)]  # a reset stream counts from 0 again
-        got1, _, _ = read_submit(r, 2, base)
+        base = [0 if s in (1, 6) else 2 * B for s in range(N)]  # a reset stream counts from 0 again
+        got1, _, _ = read_clock(r, 2, base)
         r.drain()
     assert got0[got0["stream"] == 6][-1]["flags"] & OPEN
     r6 = got1[got1["stream"] == 6]
@@ -214,7 +167,7 @@ def test_a_reset_mid_chain_drops_the_chain():
     assert dropped.tobytes() == clock.merge([got0[got0["stream"] == 6][-1]]).tobytes() and dropped["flags"] & OPEN
     assert dropped["start_sample"] + dropped["n_samples"] == 2 * B and dropped["n_segments"] >= 8
     whole, _, _, ev = scene_uncut()
-    assert parity.sort_events(ev).tobytes() == parity.sort_events(TC.one_submit()[2]).tobytes()  # the events do not notice
+    assert parity.sort_events(ev).tobytes() == parity.sort_events(R.one_submit()[2]).tobytes()  # the events do not notice
     seven = [c for c in ch if c["stream"] == 7 and c["start_sample"] < 2 * B < c["start_sample"] + c["n_samples"]]
     assert len(seven) == 1 and seven[0].tobytes() == [c for c in clock.chains([whole])
                                                       if c["stream"] == 7 and c["start_sample"] == seven[0]["start_sample"]][0].tobytes()
@@ -239,15 +192,15 @@ def test_a_golden_scene_with_the_meter_and_the_envelope_beside_it_and_none():
         r.enable_burst_meter()
         r.enable_burst_envelope()
         r.submit(x)
-        got, decs, runs = read_submit(r, 4, [0])
-        TE.read_submit(r, 4, zeros(1), [0])  # the envelope's records, exact
+        got, decs, runs = read_clock(r, 4, [0])
+        read_envelope(r, 4, zeros(1), [0])  # the envelope's records, exact
         bursts = r.read_bursts()
         tab = r.read_captures()
         ev = r.drain()
     with api.Receiver(1, 0x2F, 500, 0, max_blocks=4, all_flushes=True) as r:
         assert r.memory() == plain_mem  # a context without the call holds what it held
     assert bursts.tobytes() == burst.bursts(decs, runs, zeros(1)).tobytes() and len(bursts) == len(got) >= 2
-    TC.assert_tables(tab, plain_runs)
+    R.assert_tables(tab, plain_runs)
     assert parity.sort_events(ev).tobytes() == parity.sort_events(plain).tobytes() and len(ev) >= 1
     sm = [clock.summary(c) for c in got if c["n_segments"] >= 1]
     assert len(sm) >= 2 and all(abs(hz - 17240) <= 150 and q >= 2500 for hz, q in sm)  # TFA_2's bit rate
@@ -265,7 +218,7 @@ def test_a_submit_runs_replay_gives_the_recordings_records():
         for p, nb in zip(parity.cut(x, (1, 3)), (1, 3)):
             r.submit(p)
             tabs.append(r.read_captures(pre=True))
-            recs.append(read_submit(r, nb, [pos * B])[0])
+            recs.append(read_clock(r, nb, [pos * B])[0])
             pos += nb
             r.drain()
     off = 0
@@ -282,35 +235,34 @@ def test_a_submit_runs_replay_gives_the_recordings_records():
         for k in range(2):
             t, p, q = decin.rebase(runs, pool, pre, 2 * k * B, 2 * B)
             assert r.submit_runs(t, p, q, 2) == 2
-            rep.append(read_submit(r, 2, [2 * k * B])[0])
+            rep.append(read_clock(r, 2, [2 * k * B])[0])
             r.drain()
     a, b = clock.chains(recs), clock.chains(rep)
     assert len(a) == len(b) >= 2 and sum(int(c["n_segments"]) for c in a) >= 3
-    for u, v in zip(a, b):
-        assert u.tobytes() == v.tobytes()
+    same_chains("clock", b, a, "the replay")
 
 
 def test_overflow_delivers_the_prefix_and_a_pool_of_one_pair_delivers_everything():
     whole = hand_uncut()
     rows = np.ascontiguousarray(hand_rows())
-    with hand_receiver(2, 2, cap=(len(whole) - 1, 1)) as r:
+    with hand_receiver(2, 2, CLOCK, levels=False, cap=(len(whole) - 1, 1)) as r:
         r.submit(rows)
         raises(api.E_OVERFLOW, r.read_burst_clocks)
         got = r.read_burst_clocks(allow_overflow=True)
         assert r.clock_total == len(whole)
-        assert_records(got, whole[:-1], "the prefix")
+        same_records(got, whole[:-1], "the prefix")
         r.drain()
-    with hand_receiver(2, 2, cap=(len(whole), 1)) as r:  # the clock alone, the table just large enough
+    with hand_receiver(2, 2, CLOCK, levels=False, cap=(len(whole), 1)) as r:  # the clock alone, the table just large enough
         r.submit(rows)
-        assert_records(r.read_burst_clocks(), whole, "a pool of one pair")
+        same_records(r.read_burst_clocks(), whole, "a pool of one pair")
         assert len(r.read_captures(allow_overflow=True)[1]) <= 1  # the pool itself held nothing
         r.drain()
 
 
 def test_the_refusals_of_the_enable_call_and_what_a_context_without_it_holds():
     n, mb = 3, 2
-    x = TC.scene()[:n, :api.BLOCK_BYTES]
-    with api.Receiver(n, TC.CTX_TYPES, 500, 0, max_blocks=mb) as r:
+    x = scene()[:n, :api.BLOCK_BYTES]
+    with api.Receiver(n, CTX_TYPES, 500, 0, max_blocks=mb) as r:
         plain = r.memory()
         raises(api.E_INVAL, r.enable_burst_clock)  # no recorder
         raises(api.E_INVAL, r.read_burst_clocks)
@@ -325,7 +277,7 @@ def test_the_refusals_of_the_enable_call_and_what_a_context_without_it_holds():
         assert r.memory() == submitted
         runs_plain = r.read_captures()
         ev_plain = r.drain()
-    with api.Receiver(n, TC.CTX_TYPES, 500, 0, max_blocks=mb) as r:
+    with api.Receiver(n, CTX_TYPES, 500, 0, max_blocks=mb) as r:
         r.enable_capture(64, 1024)
         assert r.memory() == rec  # a recorder without the clock holds what it held
         r.enable_burst_clock()
@@ -346,7 +298,7 @@ def test_the_refusals_of_the_enable_call_and_what_a_context_without_it_holds():
         assert nr.value == len(recs) == len(runs_plain[0]) == len(r.read_bursts()) == len(r.read_burst_envelopes()) == 1
         runs = r.read_captures()
         ev = r.drain()
-    TC.assert_tables(runs, runs_plain)
+    R.assert_tables(runs, runs_plain)
     assert parity.sort_events(ev).tobytes() == parity.sort_events(ev_plain).tobytes()
 
 
@@ -360,13 +312,6 @@ def test_a_context_of_4096_blocks_is_refused():
 
 
 # ---- tfrec_gpu -C
-def cli_lines(args, timeout=300):
-    out = subprocess.run([parity.CLI] + args, capture_output=True, text=True, timeout=timeout)
-    assert out.returncode == 0, out.stderr
-    pick = lambda word: [ln for ln in out.stdout.splitlines() if ln.startswith(word + " ")]  # noqa: E731
-    return pick("clock"), pick("burst"), pick("extent"), parity.telegram_lines(out.stdout), pick("scan")
-
-
 @functools.lru_cache(maxsize=None)
 def whb_lines():
     """The golden WHB scene's first 6 blocks -> (its bytes, the lines clock.py expects of tfrec_gpu -C -b 2 on a file named %s)."""
@@ -385,6 +330,7 @@ def whb_lines():
 
 
 BASE = ["-T", "2f", "-t", "500", "-b", "2"]  # -b 2: the burst lies in all three batches
+WORDS = ("clock", "burst", "extent", "scan")
 
 
 def test_cli_clock_lines_of_the_golden_whb_scene_cut_into_batches(tmp_path):
@@ -393,14 +339,14 @@ def test_cli_clock_lines_of_the_golden_whb_scene_cut_into_batches(tmp_path):
     f = str(tmp_path / "whb.iq")
     x.tofile(f)
     want = [ln % f for ln in want]
-    plain = cli_lines(BASE + ["-L", f])
-    got = cli_lines(["-C"] + BASE + ["-L", f])
-    assert plain[0] == [] and got[3] == plain[3] and got[1] == got[2] == []  # the telegrams do not notice
-    assert got[0] == want and len(want) >= 1
+    plain = cli_lines(BASE + ["-L", f], *WORDS)
+    got = cli_lines(["-C"] + BASE + ["-L", f], *WORDS)
+    assert plain["clock"] == [] and got["telegrams"] == plain["telegrams"] and got["burst"] == got["extent"] == []  # the telegrams do not notice
+    assert got["clock"] == want and len(want) >= 1
     f2 = str(tmp_path / "short.iq")  # through a recycled slot beside a second file
     x[:2 * api.BLOCK_BYTES].tofile(f2)
-    slot = cli_lines(["-C", "-n", "1"] + BASE + ["-L", f, "-L", f2])
-    assert [ln for ln in slot[0] if ln.split()[1] == f] == want
+    slot = cli_lines(["-C", "-n", "1"] + BASE + ["-L", f, "-L", f2], *WORDS)
+    assert [ln for ln in slot["clock"] if ln.split()[1] == f] == want
 
 
 def test_cli_clock_beside_the_meter_and_the_envelope_and_the_scans_column(tmp_path):
@@ -410,12 +356,13 @@ def test_cli_clock_beside_the_meter_and_the_envelope_and_the_scans_column(tmp_pa
     x.tofile(f)
     want = [ln % f for ln in want]
     # beside -M and -Q: all three kinds of line, each what it is alone
-    alone = cli_lines(["-M", "-Q"] + BASE + ["-L", f])
-    both = cli_lines(["-M", "-Q", "-C"] + BASE + ["-L", f])
-    assert alone[0] == [] and both[0] == want and both[1] == alone[1] and both[2] == alone[2] and both[3] == alone[3]
-    assert len(alone[1]) == len(alone[2]) == len(want)
+    alone = cli_lines(["-M", "-Q"] + BASE + ["-L", f], *WORDS)
+    both = cli_lines(["-M", "-Q", "-C"] + BASE + ["-L", f], *WORDS)
+    assert alone["clock"] == [] and both["clock"] == want
+    assert all(both[w] == alone[w] for w in ("burst", "extent", "telegrams"))
+    assert len(alone["burst"]) == len(alone["extent"]) == len(want)
     # the channel table's column
-    scan = cli_lines(["-C", "-s", "100", "-t", "500", "-L", f])
-    assert scan[0] == [] and len(scan[4]) >= 3 and all(re.search(r" burst_clock=(-|\d+)$", ln) for ln in scan[4])
-    assert any(not ln.endswith("=-") for ln in scan[4])
-    assert all("burst_clock" not in ln for ln in cli_lines(["-s", "100", "-t", "500", "-L", f])[4])
+    scan = cli_lines(["-C", "-s", "100", "-t", "500", "-L", f], *WORDS)
+    assert scan["clock"] == [] and len(scan["scan"]) >= 3 and all(re.search(r" burst_clock=(-|\d+)$", ln) for ln in scan["scan"])
+    assert any(not ln.endswith("=-") for ln in scan["scan"])
+    assert all("burst_clock" not in ln for ln in cli_lines(["-s", "100", "-t", "500", "-L", f], "scan")["scan"])

@@ -4,7 +4,7 @@ DESIGN.md 6n), bit for bit.
 The five golden scenes tests/golden/iq_*.npz are five streams of four blocks.  Their decimated samples, fed to a channel-rate
 context, give the oracle's events of the original bytes; their capture with the pre samples, replayed through sparse submits, gives
 the events of the context that recorded it -- every field -- however the replay is cut.  The pre samples are compared with the
-restatement tfrec_amd/decin.py on the recording context's own decimated samples, on the aimed scene of test_capture_gpu.py."""
+restatement tfrec_amd/decin.py on the recording context's own decimated samples, on the aimed scene (recorder_rows.scene)."""
 import functools
 import os
 import subprocess
@@ -13,7 +13,9 @@ import numpy as np
 import pytest
 
 import parity
-import test_capture_gpu as TC
+import recorder as R
+from recorder import pre_of, raises, same_events
+from recorder_rows import carrier, scene
 from tfrec_amd import api, capture, decin, levels
 
 pytestmark = pytest.mark.gpu
@@ -24,12 +26,6 @@ M = NB * B
 NAMES = ("tfa_1", "tfa_2", "tfa_3", "tx22", "whb")
 N = len(NAMES)
 TYPES = 0x2F
-
-
-def raises(code, f, *a, **kw):
-    with pytest.raises(api.TfrecAmdError) as e:
-        f(*a, **kw)
-    assert e.value.code == code, e.value
 
 
 @functools.lru_cache(maxsize=None)
@@ -54,11 +50,6 @@ def assert_oracle(ev, types=TYPES, thresh=500):
         n += parity.assert_stream(ev, s, o)
     assert n > 0
     return n
-
-
-def same_events(a, b):
-    a, b = parity.sort_events(a), parity.sort_events(b)
-    assert len(a) == len(b) and a.tobytes() == b.tobytes()
 
 
 # ---- 1. dense
@@ -125,27 +116,23 @@ def test_dense_full_scale_values_read_back_clamped():
 
 
 # ---- 2. the recorder's pre samples
-def pre_of(decs, runs, prev=None, base=0):
-    return decin.pre_samples(np.stack([d.reshape(-1, 2) for d in decs]), runs, prev, base)
-
-
 def test_pre_on_the_aimed_scene_one_submit_and_one_plus_three():
-    got, _, ev, decs, _, _ = TC.one_submit()
-    with TC.receiver() as r:
+    got, _, ev, decs, _, _ = R.one_submit()
+    with R.receiver() as r:
         r.enable_capture_pre()
-        r.submit(TC.scene())
+        r.submit(scene())
         runs, pool, pre = r.read_captures(pre=True)
         assert np.array_equal(pre, r.read_capture_pre())  # reading pops nothing
         same_events(r.drain(), ev)
-    TC.assert_tables((runs, pool), got)  # the table and the pool do not notice
+    R.assert_tables((runs, pool), got)  # the table and the pool do not notice
     assert np.array_equal(pre, pre_of(decs, runs)) and pre.dtype == np.int16 and pre.shape == (len(runs), 2)
     r1 = runs[runs["stream"] == 1][0]
     assert r1["start_sample"] % 64 == 63  # a run at bit 63 of a mask word: its pre is bit 62's sample
     assert np.array_equal(pre[runs["stream"] == 1][0], decs[1].reshape(-1, 2)[int(r1["start_sample"]) - 1])
     assert pre.any()
     # 1 + 3, queued: stream 6's second run starts at the submit's first sample and continues -- its pre is the first submit's last
-    parts = parity.cut(TC.scene(), (1, 3))
-    with TC.receiver(max_blocks=3) as r:
+    parts = parity.cut(scene(), (1, 3))
+    with R.receiver(max_blocks=3) as r:
         r.enable_capture_pre()
         for p in parts:
             r.submit(p)
@@ -165,8 +152,8 @@ def test_pre_on_the_aimed_scene_one_submit_and_one_plus_three():
 def loud_ends():
     """One block of u8 silence with a carrier over its first and its last samples: a run at sample 0, a loud last sample."""
     x = np.full(api.BLOCK_BYTES, 128, dtype=np.uint8)
-    TC.burst(x, 0, 2000)
-    TC.burst(x, 4 * (B - 40), 4 * B)
+    carrier(x, 0, 2000)
+    carrier(x, 4 * (B - 40), 4 * B)
     return x.reshape(1, -1)
 
 
@@ -195,11 +182,11 @@ def test_pre_at_a_fresh_streams_first_sample_and_after_a_reset():
 
 @pytest.mark.parametrize("short", ["runs", "samples"])
 def test_pre_under_an_overflow_is_the_tables_prefix(short):
-    (runs, pool), _, _, decs, _, _ = TC.one_submit()
+    (runs, pool), _, _, decs, _, _ = R.one_submit()
     cap = (len(runs) - 1, len(pool)) if short == "runs" else (len(runs), len(pool) - 1)
-    with TC.receiver(cap=cap) as r:
+    with R.receiver(cap=cap) as r:
         r.enable_capture_pre()
-        r.submit(TC.scene())
+        r.submit(scene())
         raises(api.E_OVERFLOW, r.read_capture_pre)
         got = r.read_captures(allow_overflow=True, pre=True)
         r.drain()
@@ -220,7 +207,7 @@ def test_pre_memory_call_order_and_arguments():
         assert m["pinned_host_bytes"] == without["pinned_host_bytes"]
         raises(api.E_INVAL, r.enable_capture_pre)  # a second time
         raises(api.E_STATE, r.read_capture_pre)  # nothing undrained
-        r.submit(TC.scene()[:n, :api.BLOCK_BYTES])
+        r.submit(scene()[:n, :api.BLOCK_BYTES])
         runs, pool, pre = r.read_captures(pre=True)
         assert len(runs) == 1 == len(pre)
         nr = api.C.c_uint32(0)
@@ -231,7 +218,7 @@ def test_pre_memory_call_order_and_arguments():
     with api.Receiver(n, TYPES, 500, 0, max_blocks=mb) as r:  # a recorder without the call holds what it held
         r.enable_capture(max_runs, 1024)
         assert r.memory() == without
-        r.submit(TC.scene()[:n, :api.BLOCK_BYTES])
+        r.submit(scene()[:n, :api.BLOCK_BYTES])
         raises(api.E_STATE, r.enable_capture_pre)  # after the first submit
         raises(api.E_INVAL, r.read_capture_pre)
         r.drain()
@@ -466,9 +453,9 @@ def test_an_ordinary_context_is_what_it_was_with_and_without_the_pre_samples():
     parity.assert_stream(ev, 0, oracles()[0][k])
     assert np.array_equal(d.reshape(-1, 2), oracles()[1][k])
     runs, pool, _ = capture.captures(d, TYPES, 500)
-    TC.assert_tables(cap, capture.table([(runs, pool)]))
+    R.assert_tables(cap, capture.table([(runs, pool)]))
     assert lv[0].tobytes() == levels.levels(d, TYPES, 500)[0].tobytes()
-    TC.assert_tables(cap2, cap)
+    R.assert_tables(cap2, cap)
     assert lv2.tobytes() == lv.tobytes()
     same_events(ev2, ev)
 

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import parity
+from recorder_rows import rec_line
 from tfrec_amd import api, capture, envelope, levels
 from test_levels_cpu import crafted_dec
 
@@ -338,13 +339,6 @@ def merge_driver(tmp_path_factory):
     subprocess.check_call(["g++", "-std=c++11", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-o", exe, os.path.join(parity.ROOT, "tests", "merge_driver.cpp")])
     return exe
-
-
-def rec_line(f, r):
-    v = [f] + [int(r[k]) for k in ("flags", "start_sample", "n_samples", "thresh", "n_over", "last_over", "energy_head", "energy_tail",
-                                   "n_gaps", "max_gap", "lead_not_over", "nprod_head", "dot_head", "crs_head", "dot_tail", "crs_tail",
-                                   "nprod_tail")]
-    return "rec " + " ".join("%d" % x for x in v)
 
 
 def test_the_host_merge_prints_the_restatements_lines(merge_driver):

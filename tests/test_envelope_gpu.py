@@ -4,92 +4,26 @@ for bit.
 The records are compared, byte for byte, with the restatement tfrec_amd/envelope.py run on the context's OWN decimated samples
 (tfrec_amd_read_decimated), its own run table and the thresholds read back from the same submit (the level meter's per block, which
 an auto stream steps; the run table's where the threshold is fixed), so the front end and the recorder ahead of the envelope are
-whatever the context runs.  Channel-rate contexts (tfrec_amd_create_decimated) take hand-made decimated samples: the layouts the
-kernels can get wrong are placed exactly.  Everything is an exact integer; nothing here has a tolerance."""
+whatever the context runs (recorder.read_envelope).  Channel-rate contexts (tfrec_amd_create_decimated) take hand-made decimated
+samples: the layouts the kernels can get wrong are placed exactly.  Everything is an exact integer; nothing here has a tolerance."""
 import functools
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import parity
-import test_capture_gpu as TC
+import recorder as R
+from recorder import (B, CONT, OPEN, TABLE_FIELDS, W, cli_lines, hand_receiver, last_pairs, raises, read_envelope, same_chains,
+                      same_records, zeros)
+from recorder_rows import CTX_TYPES, M, N, NB, gap_ladder, golden_iq, loud, quiet, scene
 from tfrec_amd import api, burst, capture, decin, envelope
 
 pytestmark = pytest.mark.gpu
-
-B = api.BLOCK_DEC
-W = 694  # the largest window of -T 2f
-CONT, OPEN = capture.RUN_CONTINUES, capture.RUN_OPEN
-FIELDS = list(envelope.ENVELOPE_DTYPE.names)
-
-
-def raises(code, f, *a, **kw):
-    with pytest.raises(api.TfrecAmdError) as e:
-        f(*a, **kw)
-    assert e.value.code == code, e.value
-
-
-def assert_records(got, want, label=""):
-    assert got.dtype == envelope.ENVELOPE_DTYPE and len(got) == len(want), "%s: %d records, want %d" % (label, len(got), len(want))
-    for f in FIELDS:
-        assert np.array_equal(got[f], want[f]), "%s %s: first differing record %d: got %s want %s" % (
-            label, f, int(np.flatnonzero((got[f] != want[f]).reshape(len(got), -1).any(axis=1))[0]), got[f].tolist()[:12],
-            want[f].tolist()[:12])
-    assert got.tobytes() == want.tobytes(), label
-
-
-def last_pairs(decs):
-    return [np.asarray(d).reshape(-1, 2)[-1] for d in decs]
-
-
-def zeros(n):
-    return [np.zeros(2, dtype=np.int16)] * n
-
-
-def read_submit(r, nb, prev, base, levels=True, overflow=False, decs=None):
-    """The oldest undrained submit of nb blocks: its records against the restatement on what the context itself returns ->
-    (records, every stream's decimated samples, the run table).  decs: that submit's decimated samples where a later submit is
-    queued behind it (tfrec_amd_read_decimated returns the last submit's)."""
-    n = r.n_streams
-    if decs is None:
-        decs = [r.decimated(s, nb * B) for s in range(n)]
-    runs = r.read_captures(allow_overflow=True)[0]
-    got = r.read_burst_envelopes(allow_overflow=overflow)
-    if levels:  # the threshold in force in every block, as the level meter reports it
-        lev = r.read_levels()
-        thr = [np.repeat(lev[s]["thresh"].astype(np.int64), B) for s in range(n)]
-    else:  # a fixed threshold: the run's own
-        thr = [int(r.thresh(s)) for s in range(n)]
-    table = got[["stream", "flags", "start_sample", "n_samples", "thresh"]]
-    if not r.capture_overflow:
-        assert len(runs) == len(got) == r.envelope_total
-        for f in table.dtype.names:
-            assert np.array_equal(runs[f], got[f]), f
-    assert_records(got, envelope.envelopes(decs, thr, table, prev, base=base))
-    return got, decs, runs
+ENVELOPE = ("envelope",)  # hand_receiver's stages; the rows here are made for a threshold of 500
 
 
 # ---- hand-made rows on a channel-rate context
-def quiet(nb, seed):
-    return np.random.default_rng(seed).integers(-40, 41, size=(nb * B, 2)).astype(np.int16)
-
-
-def loud(row, where, v=(3000, -3000)):
-    for p in where:
-        row[p] = v
-
-
-def gap_ladder(start):
-    """Over samples with gaps of 1, 63, 64 and 65 not-over samples between them."""
-    out = [start]
-    for g in (1, 63, 64, 65):
-        out.append(out[-1] + g + 1)
-    return out
-
-
 @functools.lru_cache(maxsize=None)
 def hand_rows(nb=2):
     """int16 [2, nb B, 2] and what is where.  Stream 0: a burst at the submit's first sample; one inside a mask word; the gap ladder
@@ -116,19 +50,12 @@ def hand_rows(nb=2):
     return rows, where, where1
 
 
-def hand_receiver(n, nb, thresh=500, levels=True, cap=None, **kw):
-    r = api.Receiver(n, 0x2F, thresh, 0, max_blocks=nb, decimated=True, levels=levels, **kw)
-    r.enable_capture(*(cap or (32 * n, 1)))
-    r.enable_burst_envelope()
-    return r
-
-
 @functools.lru_cache(maxsize=None)
 def hand_uncut():
     rows, where, where1 = hand_rows()
-    with hand_receiver(2, 2) as r:
+    with hand_receiver(2, 2, ENVELOPE, thresh=500) as r:
         r.submit(np.ascontiguousarray(rows))
-        got, decs, runs = read_submit(r, 2, zeros(2), [0, 0])
+        got, decs, runs = read_envelope(r, 2, zeros(2), [0, 0])
         assert r.read_burst_envelopes().tobytes() == got.tobytes()  # reading pops nothing
         r.drain()
         raises(api.E_STATE, r.read_burst_envelopes)  # nothing undrained
@@ -166,13 +93,13 @@ def test_two_streams_of_two_blocks_of_hand_made_samples():
 def test_the_same_input_in_two_submits_and_the_merged_chains():
     whole = hand_uncut()
     rows, where, where1 = hand_rows()
-    with hand_receiver(2, 1) as r:
+    with hand_receiver(2, 1, ENVELOPE, thresh=500) as r:
         for k in range(2):  # both queued before the first read
             r.submit(np.ascontiguousarray(rows[:, k * B:(k + 1) * B]))
         got, prev = [], zeros(2)
         for k in range(2):
             part = decin.clamp(rows[:, k * B:(k + 1) * B])  # (a channel-rate context's samples are its input, clamped: hand_uncut)
-            recs, decs, _ = read_submit(r, 1, prev, [k * B] * 2, decs=[part[s].reshape(-1) for s in range(2)])
+            recs, decs, _ = read_envelope(r, 1, prev, [k * B] * 2, decs=[part[s].reshape(-1) for s in range(2)])
             got.append(recs)
             prev = last_pairs(decs)
             r.drain()
@@ -183,12 +110,10 @@ def test_the_same_input_in_two_submits_and_the_merged_chains():
     assert c[1]["energy_head"] == 0 and c[1]["nprod_tail"] == W - 300  # ... with the product across the cut, from prevdec
     o = got[0][(got[0]["flags"] & OPEN) != 0]
     assert o["stream"].tolist() == [0, 1] and o["last_over"].tolist() == [0, 0] and o["n_samples"].tolist() == [10, 300]
-    merged, uncut = envelope.chains(got), envelope.chains([whole])
     key = lambda r: (int(r["stream"]), int(r["start_sample"]))  # noqa: E731
-    merged, uncut = sorted(merged, key=key), sorted(uncut, key=key)
+    merged, uncut = sorted(envelope.chains(got), key=key), sorted(envelope.chains([whole]), key=key)
     assert len(merged) == len(uncut) == len(whole)
-    for a, b in zip(merged, uncut):
-        assert a.tobytes() == b.tobytes(), key(a)
+    same_chains("envelope", merged, uncut, "1 + 1")
 
 
 def test_an_auto_stream_whose_threshold_steps_inside_a_run():
@@ -197,16 +122,16 @@ def test_an_auto_stream_whose_threshold_steps_inside_a_run():
     nb = 8
     rng = np.random.default_rng(31)
     x = np.stack([rng.integers(-400, 401, size=(nb * B, 2)), rng.integers(-330, 331, size=(nb * B, 2))]).astype(np.int16)
-    with hand_receiver(2, nb, thresh=0) as r:
+    with hand_receiver(2, nb, ENVELOPE, thresh=0) as r:
         r.submit(x)
         lev = r.read_levels()
-        got, decs, runs = read_submit(r, nb, zeros(2), [0, 0])
+        got, decs, runs = read_envelope(r, nb, zeros(2), [0, 0])
         r.drain()
     th = lev["thresh"]
     assert th[0, 0] == 500 and th[0, -1] != 500 and len(set(th[0].tolist())) >= 2, th.tolist()
     r0 = got[got["stream"] == 0]
     assert len(r0) == 1 and r0[0]["n_samples"] >= nb * B - 16 and r0[0]["flags"] == OPEN and r0[0]["thresh"] == 500
-    blind = envelope.envelopes(decs, [500, 500], got[["stream", "flags", "start_sample", "n_samples", "thresh"]], zeros(2))
+    blind = envelope.envelopes(decs, [500, 500], got[list(TABLE_FIELDS)], zeros(2))
     assert blind[0]["n_over"] != r0[0]["n_over"]  # with the run's first threshold throughout, the count is another
     assert r0[0]["n_gaps"] > 1000 and r0[0]["max_gap"] < W
 
@@ -218,9 +143,9 @@ def test_stream_counts_across_a_waves_end(n):
     rng = np.random.default_rng(41)
     kinds = [rows[0], rows[1], rng.integers(-400, 401, size=(nb * B, 2)).astype(np.int16), quiet(nb, 43)]  # 2: never leaves its window
     x = np.ascontiguousarray(np.stack(kinds)[np.arange(n) % len(kinds)])
-    with hand_receiver(n, nb, levels=False) as r:
+    with hand_receiver(n, nb, ENVELOPE, thresh=500, levels=False) as r:
         r.submit(x)
-        got, decs, runs = read_submit(r, nb, zeros(n), [0] * n, levels=False)
+        got, decs, runs = read_envelope(r, nb, zeros(n), [0] * n, levels=False)
         r.drain()
     assert sorted(set(got["stream"].tolist())) == [s for s in range(n) if s % 4 != 3]  # (row 3 is quiet)
     noise = got[got["stream"] % 4 == 2]
@@ -235,7 +160,7 @@ def test_stream_counts_across_a_waves_end(n):
 
 # ---- the other kinds of context
 def scene_receiver(**kw):
-    r = TC.receiver(levels=True, **kw)
+    r = R.receiver(levels=True, **kw)
     r.enable_burst_envelope()
     return r
 
@@ -243,8 +168,8 @@ def scene_receiver(**kw):
 @functools.lru_cache(maxsize=None)
 def scene_uncut():
     with scene_receiver() as r:
-        r.submit(TC.scene())
-        got, decs, runs = read_submit(r, TC.NB, zeros(TC.N), [0] * TC.N)
+        r.submit(scene())
+        got, decs, runs = read_envelope(r, NB, zeros(N), [0] * N)
         ev = r.drain()
     return got, decs, runs, ev
 
@@ -257,20 +182,20 @@ def test_the_aimed_u8_scene_and_its_events():
     assert of(7)[0]["last_over"] + 400 == of(7)[0]["n_samples"]  # TFA_1 alone: its own window
     for s, length in ((3, 1), (4, 3), (5, 5)):
         assert of(s)[-1]["n_samples"] == length and of(s)[-1]["last_over"] <= length - 1
-    assert of(6)[-1]["n_samples"] >= TC.M - 16 and of(6)[-1]["n_gaps"] > 100  # the auto stream over noise
-    assert parity.sort_events(ev).tobytes() == parity.sort_events(TC.one_submit()[2]).tobytes()  # the events do not notice
+    assert of(6)[-1]["n_samples"] >= M - 16 and of(6)[-1]["n_gaps"] > 100  # the auto stream over noise
+    assert parity.sort_events(ev).tobytes() == parity.sort_events(R.one_submit()[2]).tobytes()  # the events do not notice
 
 
 def test_a_reset_mid_chain_drops_the_chain():
-    parts = parity.cut(TC.scene(), (2, 2))
+    parts = parity.cut(scene(), (2, 2))
     with scene_receiver(max_blocks=2) as r:
         r.submit(parts[0])
-        got0, d0, _ = read_submit(r, 2, zeros(TC.N), [0] * TC.N)
+        got0, d0, _ = read_envelope(r, 2, zeros(N), [0] * N)
         r.drain()
         r.reset_streams([1, 6])
         r.submit(parts[1])
-        base = [0 if s in (1, 6) else 2 * B for s in range(TC.N)]  # a reset stream counts from 0 again
-        got1, _, _ = read_submit(r, 2, last_pairs(d0), base)
+        base = [0 if s in (1, 6) else 2 * B for s in range(N)]  # a reset stream counts from 0 again
+        got1, _, _ = read_envelope(r, 2, last_pairs(d0), base)
         r.drain()
     assert got0[got0["stream"] == 6][-1]["flags"] & OPEN
     r6 = got1[got1["stream"] == 6]
@@ -288,10 +213,6 @@ def test_a_reset_mid_chain_drops_the_chain():
                                                       if c["stream"] == 7 and c["start_sample"] == seven[0]["start_sample"]][0].tobytes()
 
 
-def golden_iq(name="tfa_2", nb=4):
-    return np.load(os.path.join(parity.ROOT, "tests", "golden", "iq_%s.npz" % name))["iq"][None, :nb * api.BLOCK_BYTES]
-
-
 def test_a_golden_scene_with_the_burst_meter_beside_it_and_neither():
     x = golden_iq()
     with api.Receiver(1, 0x2F, 500, 0, max_blocks=4, all_flushes=True) as r:
@@ -303,7 +224,7 @@ def test_a_golden_scene_with_the_burst_meter_beside_it_and_neither():
         r.enable_burst_meter()
         r.enable_burst_envelope()
         r.submit(x)
-        got, decs, runs = read_submit(r, 4, zeros(1), [0])
+        got, decs, runs = read_envelope(r, 4, zeros(1), [0])
         bursts = r.read_bursts()
         ev = r.drain()
     with api.Receiver(1, 0x2F, 500, 0, max_blocks=4, all_flushes=True) as r:
@@ -331,7 +252,7 @@ def test_a_submit_runs_replay_gives_the_recordings_records():
         for p, nb in zip(parity.cut(x, (1, 3)), (1, 3)):
             r.submit(p)
             tabs.append(r.read_captures(pre=True))
-            got, decs, _ = read_submit(r, nb, prev, [pos * B])
+            got, decs, _ = read_envelope(r, nb, prev, [pos * B])
             recs.append(got)
             prev, pos = last_pairs(decs), pos + nb
             r.drain()
@@ -349,7 +270,7 @@ def test_a_submit_runs_replay_gives_the_recordings_records():
         for k in range(2):
             t, p, q = decin.rebase(runs, pool, pre, 2 * k * B, 2 * B)
             assert r.submit_runs(t, p, q, 2) == 2
-            got, decs, _ = read_submit(r, 2, prev, [2 * k * B], levels=False)
+            got, decs, _ = read_envelope(r, 2, prev, [2 * k * B], levels=False)
             z = decs[0].reshape(-1, 2)
             covered = np.zeros(2 * B, dtype=bool)
             for c in got:  # a run's samples, and the pair ahead of it, which a sparse submit carries too (it is not over)
@@ -361,31 +282,30 @@ def test_a_submit_runs_replay_gives_the_recordings_records():
             r.drain()
     a, b = envelope.chains(recs), envelope.chains(rep)
     assert len(a) == len(b) >= 2
-    for u, v in zip(a, b):
-        assert u.tobytes() == v.tobytes()
+    same_chains("envelope", b, a, "the replay")
 
 
 def test_overflow_delivers_the_prefix_and_a_pool_of_one_pair_delivers_everything():
     whole = hand_uncut()
     rows = np.ascontiguousarray(hand_rows()[0])
-    with hand_receiver(2, 2, cap=(len(whole) - 1, 1)) as r:
+    with hand_receiver(2, 2, ENVELOPE, thresh=500, cap=(len(whole) - 1, 1)) as r:
         r.submit(rows)
         raises(api.E_OVERFLOW, r.read_burst_envelopes)
         got = r.read_burst_envelopes(allow_overflow=True)
         assert r.envelope_total == len(whole)
-        assert_records(got, whole[:-1], "the prefix")
+        same_records(got, whole[:-1], "the prefix")
         r.drain()
-    with hand_receiver(2, 2, cap=(len(whole), 1), levels=False) as r:  # the envelope alone, the table just large enough
+    with hand_receiver(2, 2, ENVELOPE, thresh=500, cap=(len(whole), 1), levels=False) as r:  # the envelope alone, the table just large enough
         r.submit(rows)
-        assert_records(r.read_burst_envelopes(), whole, "a pool of one pair")
+        same_records(r.read_burst_envelopes(), whole, "a pool of one pair")
         assert len(r.read_captures(allow_overflow=True)[1]) <= 1  # the pool itself held nothing
         r.drain()
 
 
 def test_the_refusals_of_the_enable_call_and_what_a_context_without_it_holds():
     n, mb = 3, 2
-    x = TC.scene()[:n, :api.BLOCK_BYTES]
-    with api.Receiver(n, TC.CTX_TYPES, 500, 0, max_blocks=mb) as r:
+    x = scene()[:n, :api.BLOCK_BYTES]
+    with api.Receiver(n, CTX_TYPES, 500, 0, max_blocks=mb) as r:
         plain = r.memory()
         raises(api.E_INVAL, r.enable_burst_envelope)  # no recorder
         raises(api.E_INVAL, r.read_burst_envelopes)
@@ -400,7 +320,7 @@ def test_the_refusals_of_the_enable_call_and_what_a_context_without_it_holds():
         assert r.memory() == submitted
         runs_plain = r.read_captures()
         ev_plain = r.drain()
-    with api.Receiver(n, TC.CTX_TYPES, 500, 0, max_blocks=mb) as r:
+    with api.Receiver(n, CTX_TYPES, 500, 0, max_blocks=mb) as r:
         r.enable_capture(64, 1024)
         assert r.memory() == rec  # a recorder without the envelope holds what it held
         r.enable_burst_envelope()
@@ -420,16 +340,12 @@ def test_the_refusals_of_the_enable_call_and_what_a_context_without_it_holds():
         assert nr.value == len(recs) == len(runs_plain[0]) == len(r.read_bursts()) == 1
         runs = r.read_captures()
         ev = r.drain()
-    TC.assert_tables(runs, runs_plain)
+    R.assert_tables(runs, runs_plain)
     assert parity.sort_events(ev).tobytes() == parity.sort_events(ev_plain).tobytes()
 
 
 # ---- tfrec_gpu -Q
-def cli_lines(args, timeout=300):
-    out = subprocess.run([parity.CLI] + args, capture_output=True, text=True, timeout=timeout)
-    assert out.returncode == 0, out.stderr
-    pick = lambda word: [ln for ln in out.stdout.splitlines() if ln.startswith(word + " ")]  # noqa: E731
-    return pick("extent"), pick("burst"), parity.telegram_lines(out.stdout), pick("scan")
+WORDS = ("extent", "burst", "scan")
 
 
 def test_cli_extent_lines_of_the_golden_whb_scene_cut_into_batches(tmp_path):
@@ -439,9 +355,9 @@ def test_cli_extent_lines_of_the_golden_whb_scene_cut_into_batches(tmp_path):
     f = str(tmp_path / "whb.iq")
     x.tofile(f)
     base = ["-T", "2f", "-t", str(T), "-b", "2"]
-    plain = cli_lines(base + ["-L", f])
-    got = cli_lines(["-Q"] + base + ["-L", f])
-    assert plain[0] == [] and got[2] == plain[2] and got[1] == []  # the telegrams do not notice
+    plain = cli_lines(base + ["-L", f], *WORDS)
+    got = cli_lines(["-Q"] + base + ["-L", f], *WORDS)
+    assert plain["extent"] == [] and got["telegrams"] == plain["telegrams"] and got["burst"] == []  # the telegrams do not notice
     # the restatement: the oracle's front end (the context's, bit for bit), capture.py and envelope.py submit by submit (2 + 2 + 2)
     dec = parity.fresh_oracle(x, 0x2F, T, keep_dec=True).dec().reshape(-1, 2)
     recs, st, prev = [], None, zeros(1)
@@ -452,18 +368,18 @@ def test_cli_extent_lines_of_the_golden_whb_scene_cut_into_batches(tmp_path):
         prev = last_pairs([part])
     assert any(c["flags"] & CONT for c in recs[1]) and any(c["flags"] & CONT for c in recs[2])  # a burst is cut by the batches, twice
     want = [envelope.line(f, c) for c in envelope.chains(recs)]
-    assert got[0] == want and len(want) >= 1
+    assert got["extent"] == want and len(want) >= 1
     assert any(ln.split()[8] != "-" and int(ln.split()[6]) >= 1 and int(ln.split()[3]) > 2 * B for ln in want)  # a ratio, and gaps
     # beside -M: both kinds of line, each what it is alone; through a recycled slot beside a second file
-    meter = cli_lines(["-M"] + base + ["-L", f])
-    both = cli_lines(["-M", "-Q"] + base + ["-L", f])
-    assert both[0] == want and both[1] == meter[1] and len(meter[1]) == len(want)
+    meter = cli_lines(["-M"] + base + ["-L", f], *WORDS)
+    both = cli_lines(["-M", "-Q"] + base + ["-L", f], *WORDS)
+    assert both["extent"] == want and both["burst"] == meter["burst"] and len(meter["burst"]) == len(want)
     f2 = str(tmp_path / "short.iq")
     x[:2 * api.BLOCK_BYTES].tofile(f2)
-    slot = cli_lines(["-Q", "-n", "1"] + base + ["-L", f, "-L", f2])
-    assert [ln for ln in slot[0] if ln.split()[1] == f] == want
+    slot = cli_lines(["-Q", "-n", "1"] + base + ["-L", f, "-L", f2], *WORDS)
+    assert [ln for ln in slot["extent"] if ln.split()[1] == f] == want
     # the channel table's column
-    scan = cli_lines(["-Q", "-s", "100", "-t", "500", "-L", f])
-    assert scan[0] == [] and len(scan[3]) >= 3 and all(re.search(r" burst_snr=(-|\d+\.\d\d)$", ln) for ln in scan[3])
-    assert any(not ln.endswith("=-") for ln in scan[3])
-    assert all("burst_snr" not in ln for ln in cli_lines(["-s", "100", "-t", "500", "-L", f])[3])
+    scan = cli_lines(["-Q", "-s", "100", "-t", "500", "-L", f], *WORDS)
+    assert scan["extent"] == [] and len(scan["scan"]) >= 3 and all(re.search(r" burst_snr=(-|\d+\.\d\d)$", ln) for ln in scan["scan"])
+    assert any(not ln.endswith("=-") for ln in scan["scan"])
+    assert all("burst_snr" not in ln for ln in cli_lines(["-s", "100", "-t", "500", "-L", f], "scan")["scan"])

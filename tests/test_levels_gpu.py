@@ -13,6 +13,7 @@ import pytest
 
 import parity
 from oracle import oracle as O
+from recorder import same_records
 from tfrec_amd import api, levels, resample, synth, tune
 from test_input_tune_cpu import input_oracle, stage0_of
 
@@ -94,17 +95,12 @@ def base_run(thresh, sizes, serial=False):
     return np.concatenate(got, axis=1), np.concatenate(want, axis=1), np.concatenate(evs), th
 
 
-def assert_records(got, want, label=""):
-    for f in levels.LEVEL_DTYPE.names:
-        assert np.array_equal(got[f], want[f]), "%s %s: got %s want %s" % (label, f, got[f].tolist(), want[f].tolist())
-
-
 @pytest.mark.parametrize("thresh", [500, 0])
 def test_records_equal_the_restatement_however_the_stream_is_cut(thresh):
     one, want, ev, _ = base_run(thresh, (4,))
     cut, want_cut, ev_cut, _ = base_run(thresh, (1, 3))
-    assert_records(one, want, "one submit")
-    assert_records(cut, want_cut, "1 + 3")
+    same_records(one, want, "one submit")
+    same_records(cut, want_cut, "1 + 3")
     assert one.tobytes() == cut.tobytes()
     # the scene is what it is meant to be
     assert one["triggered"][0].sum() == 0 and one["n_over"][0].sum() == 0 and one["pwr_max"][0].max() < 500
@@ -188,7 +184,7 @@ def test_a_reset_restarts_the_level_state_of_that_stream_alone():
         got, want, evs, _ = run_levels(r, parity.cut(two, (4, 2)), [TYPES] * 3, [0] * 3, before=before)
         assert [r.thresh(s) for s in range(3)] == [int(got[1][s][-1]["thresh"]) for s in range(3)]  # (runs 6 and 2: no step)
     for k in range(2):
-        assert_records(got[k], want[k], "submit %d" % k)
+        same_records(got[k], want[k], "submit %d" % k)
     assert got[1]["thresh"].tolist() == [[498, 498], [500, 500], [502, 502]]
     assert got[1]["triggered_avg"][1][0] == got[1]["triggered"][1][0] // 32  # from zero again
     assert got[1]["triggered_avg"][2][0] == (31 * int(got[0]["triggered_avg"][2][-1]) + B) // 32  # carried on
@@ -209,7 +205,7 @@ def test_triggered_follows_each_streams_own_window():
         got, want, evs, _ = run_levels(r, parity.cut(iq, (2, 2)), types, thresh)
         th2 = r.thresh(2)
     got, want, ev = np.concatenate(got, axis=1), np.concatenate(want, axis=1), np.concatenate(evs)
-    assert_records(got, want)
+    same_records(got, want)
     assert np.array_equal(got["n_over"][0], got["n_over"][1]) and np.array_equal(got["energy"][0], got["energy"][2])
     assert got["triggered"][1][1] - got["triggered"][0][1] >= 694 - 400  # the window behind block 0's last sample, at least
     assert (got["triggered"][0] <= got["triggered"][1]).all() and got["triggered"][2].tolist() == got["triggered"][1].tolist()
@@ -235,7 +231,7 @@ def test_the_scans_configuration_on_a_rate_context():
         r.tune_streams_input([0], [hz_in[0]])
         r.tune_streams([1], [hz_behind[1]])
         got, want, evs, _ = run_levels(r, [row], [TYPES] * 3, [500] * 3)
-    assert_records(got[0], want[0])
+    same_records(got[0], want[0])
     assert (got[0]["triggered"].sum(axis=1) > 0).all()
     tele = []
     for s in range(3):
@@ -249,12 +245,12 @@ def test_a_10x_context_and_a_serial_one():
     iq10 = np.stack([synth.gen_stream(9, s, 1, rate_mult=10) for s in range(2)])
     with api.Receiver(2, TYPES, 0, 0, max_blocks=1, all_flushes=True, levels=True, input_10x=True) as r:
         got, want, evs, _ = run_levels(r, [iq10], [TYPES] * 2, [0] * 2)
-    assert_records(got[0], want[0], "10x")
+    same_records(got[0], want[0], "10x")
     assert got[0].shape == (2, 1) and got[0]["energy"].min() > 0
     for s in range(2):
         parity.assert_stream(evs[0], s, parity.fresh_oracle(iq10[s], TYPES, 0, in10x=True), "10x stream %d" % s)
     ser, want, ev, th = base_run(0, (1, 3), True)
-    assert_records(ser, want, "serial")
+    same_records(ser, want, "serial")
     assert ser.tobytes() == base_run(0, (1, 3))[0].tobytes() and th == base_run(0, (1, 3))[3]
     for s in range(3):
         parity.assert_stream(ev, s, parity.fresh_oracle(scene()[s], TYPES, 0), "serial stream %d" % s)

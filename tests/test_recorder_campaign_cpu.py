@@ -197,7 +197,7 @@ def test_a_chain_that_ends_with_a_submits_last_sample_merges_into_the_uncut_runs
     import subprocess
 
     import parity
-    from test_envelope_cpu import rec_line
+    from recorder_rows import rec_line
 
     W = 694
     x = np.stack([RC.quiet(2, 51), RC.quiet(2, 52)])

@@ -16,6 +16,7 @@ import pytest
 
 import parity
 from oracle import oracle as O
+from recorder import raises
 from tfrec_amd import api, formats, resample, state, synth, tune
 
 pytestmark = pytest.mark.gpu
@@ -24,12 +25,6 @@ B = api.BLOCK_BYTES
 TYPES = 0x2F
 NB_ = 65                      # B's streams
 DST = (64, 0, 33, 63, 17)     # where A's streams 0 .. 4 continue in B
-
-
-def raises(code, f, *a, **kw):
-    with pytest.raises(api.TfrecAmdError) as e:
-        f(*a, **kw)
-    assert e.value.code == code, e.value
 
 
 @functools.lru_cache(maxsize=None)

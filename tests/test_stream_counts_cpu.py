@@ -12,8 +12,8 @@ import functools
 import numpy as np
 
 import parity
+import recorder_rows as RR
 import segments
-import test_capture_gpu as TC
 from oracle import oracle as O
 from test_channels_gpu import CFGS, DFLT, ROW_TUNES, ROWS, make_rows
 from tfrec_amd import api, capture, synth
@@ -203,13 +203,13 @@ CAP_CUT = 78  # reads row 6, triggered throughout: the longest run of the table
 
 
 def cap_kind(s):
-    """The row of test_capture_gpu.scene() stream s reads, with that row's TYPES and THRESH."""
-    return s % TC.N
+    """The row of recorder_rows.scene() stream s reads, with that row's TYPES and THRESH."""
+    return s % RR.N
 
 
 @functools.lru_cache(maxsize=None)
 def cap_rows():
-    iq = TC.scene()[[cap_kind(s) for s in range(CAP_N)]]
+    iq = RR.scene()[[cap_kind(s) for s in range(CAP_N)]]
     iq.setflags(write=False)
     return iq
 
@@ -219,10 +219,10 @@ def cap_restated():
     """The restatement on the oracle's decimated samples (the context's front end is the oracle's, bit for bit) -> (table, pool)
     of one submit of the whole scene."""
     kinds = []
-    for k in range(TC.N):
-        o = O.Oracle(TC.TYPES[k], TC.THRESH[k], 0, keep_dec=True)
-        o.process(TC.scene()[k])
-        kinds.append(capture.captures(o.dec(), TC.TYPES[k], TC.THRESH[k])[:2])
+    for k in range(RR.N):
+        o = O.Oracle(RR.TYPES[k], RR.THRESH[k], 0, keep_dec=True)
+        o.process(RR.scene()[k])
+        kinds.append(capture.captures(o.dec(), RR.TYPES[k], RR.THRESH[k])[:2])
     return capture.table([kinds[cap_kind(s)] for s in range(CAP_N)])
 
 
@@ -240,7 +240,7 @@ def test_the_capture_scene_has_runs_on_both_sides_of_stream_64_and_none_on_it():
     per = np.bincount(runs["stream"], minlength=CAP_N)
     assert per[64] == 0 and per[63] > 0 and cap_kind(64) == 0  # a step of the prefix scan begins with an empty entry
     assert per[:64].any() and per[65:].any()
-    for k in range(TC.N):  # every row kind lands on both sides
+    for k in range(RR.N):  # every row kind lands on both sides
         assert any(cap_kind(s) == k for s in range(64)) and any(cap_kind(s) == k for s in range(65, CAP_N))
     assert per[6::8].min() > 0 and (per[0::8] == 0).all() and (per[1:6] == 1).all()
     assert int(runs["pool_offset"][-1] + runs["n_samples"][-1]) == len(pool) > 2 ** 16

@@ -15,11 +15,12 @@ import numpy as np
 import pytest
 
 import parity
+import recorder as R
+import recorder_rows as RR
 import segments
-import test_capture_gpu as TC
 import test_stream_counts_cpu as C
+from recorder import pre_of, same_events
 from test_channels_gpu import DFLT, device_parts, make_rows
-from test_decin_gpu import pre_of, same_events
 from tfrec_amd import api, capture, decin, levels
 
 pytestmark = pytest.mark.gpu
@@ -144,11 +145,11 @@ def test_shared_rows_and_stream_lists_across_index_64(mode, monkeypatch):
 
 # ---- 4. levels, capture, capture_pre and the replay
 N4 = C.CAP_N
-NB, M = TC.NB, TC.M
+NB, M = RR.NB, RR.M
 
 
 def recorder(max_blocks=NB, cap=(4096, N4 * M)):
-    r = TC.receiver(max_blocks=max_blocks, cap=cap, n=N4, levels=True)
+    r = R.receiver(max_blocks=max_blocks, cap=cap, n=N4, levels=True)
     r.enable_capture_pre()
     return r
 
@@ -157,14 +158,14 @@ def want_levels(decs, states):
     out = []
     for s, d in enumerate(decs):
         k = C.cap_kind(s)
-        rec, states[s] = levels.levels(d, TC.TYPES[k], TC.THRESH[k], states[s])
+        rec, states[s] = levels.levels(d, RR.TYPES[k], RR.THRESH[k], states[s])
         out.append(rec)
     return np.stack(out)
 
 
 @functools.lru_cache(maxsize=None)
 def kind_oracles():
-    return [parity.fresh_oracle(TC.scene()[k], TC.TYPES[k], TC.THRESH[k]) for k in range(TC.N)]
+    return [parity.fresh_oracle(RR.scene()[k], RR.TYPES[k], RR.THRESH[k]) for k in range(RR.N)]
 
 
 def assert_oracle(ev):
@@ -188,9 +189,9 @@ def one_submit():
 
 def test_table_pool_pre_samples_and_levels_of_97_streams_equal_the_restatements():
     (runs, pool, pre), lv, ev, decs = one_submit()
-    want = TC.want_tables(decs, [None] * N4)
-    TC.assert_tables((runs, pool), want)
-    TC.assert_tables((runs, pool), C.cap_restated(), "the oracle's front end")
+    want = RR.want_tables(decs, [None] * N4)
+    R.assert_tables((runs, pool), want)
+    R.assert_tables((runs, pool), C.cap_restated(), "the oracle's front end")
     assert np.array_equal(pre, pre_of(decs, runs)) and pre.shape == (len(runs), 2) and pre.any()
     assert lv.tobytes() == want_levels(decs, [None] * N4).tobytes()
     assert_oracle(ev)
@@ -218,7 +219,7 @@ def test_one_plus_three_queued_before_the_first_read():
     cstates, lstates, pos, prev = [None] * N4, [None] * N4, 0, None
     for k, nb in enumerate(sizes):
         part = [d[2 * pos * B:2 * (pos + nb) * B] for d in decs]
-        TC.assert_tables(got[k][:2], TC.want_tables(part, cstates), "submit %d" % k)
+        R.assert_tables(got[k][:2], RR.want_tables(part, cstates), "submit %d" % k)
         assert np.array_equal(got[k][2], pre_of(part, got[k][0], prev, base=pos * B)), "submit %d pre" % k
         assert lv[k].tobytes() == want_levels(part, lstates).tobytes(), "submit %d levels" % k
         prev = np.stack([d.reshape(-1, 2)[-1] for d in part])
@@ -237,7 +238,7 @@ def test_overflow_behind_stream_64_delivers_a_prefix_and_the_next_submit_is_exac
     states = [None] * N4
     with recorder(cap=cap) as r:
         r.submit(C.cap_rows())
-        want = TC.want_tables([r.decimated(s, M) for s in range(N4)], states)
+        want = RR.want_tables([r.decimated(s, M) for s in range(N4)], states)
         with pytest.raises(api.TfrecAmdError) as e:
             r.read_captures()
         assert e.value.code == api.E_OVERFLOW
@@ -245,16 +246,16 @@ def test_overflow_behind_stream_64_delivers_a_prefix_and_the_next_submit_is_exac
         assert r.capture_overflow and r.capture_totals == (len(want[0]), len(want[1])) == (len(runs), len(pool))
         wr, wp, ov = capture.prefix(want[0], want[1], *cap)
         assert ov and wr[-1]["stream"] == C.CAP_CUT - 1 and (wr["stream"] > 64).any()
-        TC.assert_tables(got[:2], (wr, wp), "the prefix")
+        R.assert_tables(got[:2], (wr, wp), "the prefix")
         assert np.array_equal(got[2], one_submit()[0][2][:len(wr)])
         ev = r.drain()
         # the next submit -- one block, so that it fits -- captures normally, its CONTINUES flags included
         r.submit(C.cap_rows()[:, :api.BLOCK_BYTES])
-        want2 = TC.want_tables([r.decimated(s, B) for s in range(N4)], states)
+        want2 = RR.want_tables([r.decimated(s, B) for s in range(N4)], states)
         got2 = r.read_captures()
         assert not r.capture_overflow
         r.drain()
-    TC.assert_tables(got2, want2, "the submit behind the overflow")
+    R.assert_tables(got2, want2, "the submit behind the overflow")
     assert (got2[0][got2[0]["flags"] & capture.RUN_CONTINUES != 0]["stream"] > 64).any()
     same_events(ev, ev1)  # the events do not notice
 
@@ -262,7 +263,7 @@ def test_overflow_behind_stream_64_delivers_a_prefix_and_the_next_submit_is_exac
 def test_a_replayed_capture_of_97_streams_gives_the_recordings_events_bit_for_bit():
     (runs, pool, pre), lv, ev, _ = one_submit()
     sizes = (2, 2)
-    with TC.receiver(max_blocks=max(sizes), cap=None, n=N4, levels=True, decimated=True) as r:
+    with R.receiver(max_blocks=max(sizes), cap=None, n=N4, levels=True, decimated=True) as r:
         r.enable_runs_input(len(runs) + len(sizes) * N4, len(pool) + 1)
         pos, glv, evs = 0, [], []
         for nb in sizes:

@@ -15,17 +15,13 @@ import numpy as np
 import pytest
 
 import parity
+from recorder_rows import (GOLDEN, PAYLOADS, PLATEAUS, RATE, WORD, frame_symbols, golden_dec, rotated, submits, word_bits,
+                           sync_stripped as stripped)
 from tfrec_amd import api, capture, levels, sync, track
-from test_clock_cpu import golden_dec, rotated
 from test_levels_cpu import crafted_dec
-from test_track_cpu import GOLDEN, RATE, submits
 
 B = levels.BLOCK_DEC
 CONT, OPEN = capture.RUN_CONTINUES, capture.RUN_OPEN
-WORD = 0x2DD4
-# DESIGN.md 6u's table: per scene and run the plateau at E = 0 and E = 1 and the 32 bits read behind the sync word
-PLATEAUS = dict(tfa_2=((520, 541), (521, 540)), tfa_3=((1571, 1606), (1570, 1609)), tx22=((1357, 1397), (1358, 1397)))
-PAYLOADS = dict(tfa_2=("96070960", "98812225"), tfa_3=("9144363d", "96846244"), tx22=("a5920189", "acdb0681"))
 
 
 def sync_submits(tsubs, st, brute=False, n_streams=1):
@@ -73,26 +69,6 @@ def symbols_track(symbols, rate, lead=0):
     n = -(-384000 * len(symbols) // rate)
     idx = np.minimum(np.arange(n) * rate // 384000, len(symbols) - 1)
     return np.concatenate([np.zeros(lead, dtype=np.uint8), np.asarray(symbols, dtype=np.uint8)[idx]])
-
-
-def word_bits(word, n_bits):
-    return [(word >> (n_bits - 1 - i)) & 1 for i in range(n_bits)]  # MSB first
-
-
-# ---- hand-made FSK rows (shared with tests/test_sync_gpu.py)
-def fsk(symbols, rate, amp=6000, dev=40000, phase=0.0):
-    """A phase-continuous two-tone signal, +dev Hz for a 1, at `rate` bit/s -> int16 [n, 2]."""
-    n = -(-384000 * len(symbols) // rate)
-    idx = np.minimum(np.arange(n) * rate // 384000, len(symbols) - 1)
-    f = np.where(np.asarray(symbols)[idx] != 0, dev, -dev)
-    ph = phase + 2 * np.pi * np.cumsum(f) / 384000.0
-    return np.stack([np.rint(amp * np.cos(ph)), np.rint(amp * np.sin(ph))], axis=1).astype(np.int16)
-
-
-def frame_symbols(word, n_bits, seed, pre=16, pay=32, invert=False):
-    rng = np.random.default_rng(seed)
-    s = [1, 0] * (pre // 2) + word_bits(word, n_bits) + rng.integers(0, 2, pay).tolist()
-    return [1 - x for x in s] if invert else s
 
 
 # ---- the restatement against its per-sample form
@@ -223,10 +199,6 @@ def test_the_first_defined_sample():
 
 
 # ---- cutting
-def stripped(rec):
-    return [int(rec[f]) for f in sync.SYNC_DTYPE.names if f != "bit_offset"]  # (a piece's place in its own submit's pool)
-
-
 @pytest.mark.parametrize("name,drop", [("tfa_2", 0), ("tfa_3", 0), ("tfa_2", 2000), ("tfa_3", 3000)])
 def test_the_merged_chains_are_the_uncut_stream_for_every_block_cut(name, drop):
     """The scenes as they are -- their bursts lie inside blocks --, and with their first `drop` samples taken away, so that the first

@@ -2,7 +2,7 @@
 
 The records and the match bitmap's words are compared, byte for byte, with the restatement tfrec_amd/sync.py run on the context's
 OWN track (tfrec_amd_read_burst_tracks) and run table, and that track with tfrec_amd/track.py on the context's own decimated
-samples (tests/test_track_gpu.py: read_submit), so everything ahead of the sync is whatever the context runs.  Channel-rate
+samples (tests/recorder.py: read_sync on read_track), so everything ahead of the sync is whatever the context runs.  Channel-rate
 contexts take hand-made FSK rows with the sync word planted where the kernels can go wrong; every such case asserts that the
 expected match track has a one in the place it is about.  Everything is an exact integer; nothing here has a tolerance.
 
@@ -11,56 +11,28 @@ whole submit, at least 8192 samples -- never 500.  The three-piece chain here is
 of 1000 and 500 samples, which need the carried words combined, are tests/test_sync_cpu.py's, on the restatement.  Nothing here is
 measured on real recordings."""
 import functools
-import subprocess
 
 import numpy as np
 import pytest
 
 import parity
-import test_capture_gpu as TC
-import test_clock_gpu as TK
-import test_envelope_gpu as TE
-import test_track_gpu as TT
-from test_sync_cpu import PAYLOADS, PLATEAUS, WORD, frame_symbols, fsk, stripped
-from tfrec_amd import api, burst, capture, decin, sync, track
+import recorder as R
+from recorder import (B, CONT, OPEN, W, cli_lines, hand_receiver, raises, read_clock, read_envelope, read_sync, read_track,
+                      same_chains, same_records, zeros)
+from recorder_rows import CTX_TYPES, PAYLOADS, PLATEAUS, WORD, frame_symbols, fsk, golden_iq, quiet, scene, shifted_tfa_2
+from tfrec_amd import api, burst, decin, sync, track
 
 pytestmark = pytest.mark.gpu
 
-B = api.BLOCK_DEC
-W, T = TT.W, TT.T
-CONT, OPEN = capture.RUN_CONTINUES, capture.RUN_OPEN
-FIELDS = list(sync.SYNC_DTYPE.names)
-zeros, raises, golden_iq, quiet = TE.zeros, TE.raises, TE.golden_iq, TE.quiet
 WORD64 = 0x5A0FF0A5C3963C69
 # (rate, word, P, E, BOTH): P = 8, 16, 24 (span 2047) and 64; E = 0 and P / 2 - 1; BOTH with stream 1's frames inverted
 CASES = {"p16": (17240, WORD, 16, 0, False), "p16_e7": (17240, WORD, 16, 7, False), "p8": (17240, 0xD4, 8, 0, False),
          "p64": (12000, WORD64, 64, 3, False), "p24_span2047": (4315, 0xAA2DD4, 24, 1, False), "both": (17240, WORD, 16, 1, True)}
 
 
-def assert_records(got, want, label=""):
-    assert got.dtype == sync.SYNC_DTYPE and len(got) == len(want), "%s: %d records, want %d" % (label, len(got), len(want))
-    for f in FIELDS:
-        assert np.array_equal(got[f], want[f]), "%s %s: got %s want %s" % (label, f, got[f].tolist()[:12], want[f].tolist()[:12])
-    assert got.tobytes() == want.tobytes(), label
-
-
-def read_sync(r, st, state, trecs, twords, overflow=False):
-    """The oldest undrained submit's sync records and words against the restatement on the track records and words the context
-    returned for it -> (records, words, the state behind the submit)."""
-    got, words = r.read_burst_syncs(allow_overflow=overflow)
-    if not r.capture_overflow:
-        assert len(got) == len(trecs) == r.sync_total
-    want, wwords, state = sync.syncs(trecs, twords, st, state, r.n_streams, max_samples=r._capture[1])
-    assert_records(got, want)
-    TT.assert_words(words, wwords)
-    assert TT.table_of(got).tobytes() == TT.table_of(trecs).tobytes()
-    return got, words, state
-
-
 def receiver(n, nb, st, cap=None, **kw):
-    r = TT.hand_receiver(n, nb, track.smooth_of(st.rate), cap=cap, **kw)
-    r.enable_burst_sync(st.rate, st.pattern, st.P, st.E, st.both)
-    return r
+    stages = {"track": (track.smooth_of(st.rate),), "sync": (st.rate, st.pattern, st.P, st.E, st.both)}
+    return hand_receiver(n, nb, stages, cap=cap, **kw)
 
 
 def run_cut(rows, st, sizes, cap=None, resets=None):
@@ -87,8 +59,8 @@ def run_cut(rows, st, sizes, cap=None, resets=None):
                         origin[s] = pos * B
                 r.submit(x)
             part = decin.clamp(x)
-            trecs, twords, _, tstate = TT.read_submit(r, nb, [pos * B - o for o in origin], L, [0] * n, tstate,
-                                                      decs=[part[s].reshape(-1) for s in range(n)], overflow=cap is not None)
+            trecs, twords, _, tstate = read_track(r, nb, [pos * B - o for o in origin], L, [0] * n, tstate,
+                                                  decs=[part[s].reshape(-1) for s in range(n)], overflow=cap is not None)
             srecs, swords, sstate = read_sync(r, st, sstate, trecs, twords, overflow=cap is not None)
             if i == 0:
                 again = r.read_burst_syncs(allow_overflow=cap is not None)  # reading pops nothing
@@ -205,8 +177,7 @@ def test_the_same_rows_in_two_submits_queued_before_the_first_read(case):
     assert o["stream"].tolist() == [0, 1] and sync.bits_of(o[1], ssubs[0][1])[-1] == 1
     got = merged(tsubs, ssubs)
     assert len(got[1]) == len(whole[1])
-    for a, b in zip(got[1], whole[1]):
-        assert stripped(a.rec) == stripped(b.rec) and np.array_equal(a.bits, b.bits), (int(a["stream"]), int(a["start_sample"]))
+    same_chains("sync", got[1], whole[1], "1 + 1")
 
 
 @functools.lru_cache(maxsize=None)
@@ -239,8 +210,8 @@ def test_a_chain_of_three_pieces():
     whole = merged(*run_cut(long_rows(), st, (3,)))
     got = merged(tsubs, ssubs)
     assert len(got[1]) == len(whole[1]) == 2
-    for a, b in zip(got[1], whole[1]):
-        assert stripped(a.rec) == stripped(b.rec) and np.array_equal(a.bits, b.bits) and int(a["n_hits"]) > 100
+    same_chains("sync", got[1], whole[1], "1 + 1 + 1")
+    assert all(int(a["n_hits"]) > 100 for a in got[1])
 
 
 def test_a_reset_mid_chain_drops_the_history():
@@ -283,7 +254,7 @@ def test_overflow_on_max_runs_and_on_max_samples_delivers_the_prefixes():
     rows = hand_rows("p16")
     whole = hand_uncut("p16")[1][0][0]
     tsubs, ssubs = run_cut(rows, st, (2,), cap=(len(whole) - 1, 4 * B))  # the table a run short
-    assert_records(ssubs[0][0], whole[:-1], "the prefix")
+    same_records(ssubs[0][0], whole[:-1], "the prefix")
     assert len(ssubs[0][1]) == (int(whole[-1]["bit_offset"]) + 31) // 32
     with receiver(2, 2, st, cap=(len(whole) - 1, 4 * B)) as r:
         r.submit(np.ascontiguousarray(rows))
@@ -296,7 +267,7 @@ def test_overflow_on_max_runs_and_on_max_samples_delivers_the_prefixes():
     room = int(full[0][0]["n_samples"].sum()) - 1
     tsubs, ssubs = run_cut(rows, st, (1, 1), cap=(32, room))
     a, wa = ssubs[0]
-    assert_records(a[:-1], full[0][0][:-1], "the runs that fit")
+    same_records(a[:-1], full[0][0][:-1], "the runs that fit")
     assert a[-1]["stream"] == 1 and a[-1]["flags"] & OPEN and (a[-1]["best"], a[-1]["best_at"], a[-1]["n_hits"]) == (sync.NONE, 0, 0)
     assert full[0][0][-1]["n_hits"] > 0 and len(wa) == (int(a[-1]["bit_offset"]) + 31) // 32
     b, wb = ssubs[1]  # (the second submit is smaller: everything fits)
@@ -334,10 +305,10 @@ def test_the_golden_tfa_2_scene_with_all_five_measurements_and_none():
         r.enable_burst_meter()
         r.enable_burst_envelope()
         r.submit(x)
-        trecs, twords, decs, _ = TT.read_submit(r, 4, [0], 11, [0], None)
+        trecs, twords, decs, _ = read_track(r, 4, [0], 11, [0], None)
         got, words, _ = read_sync(r, st, None, trecs, twords)
-        TK.read_submit(r, 4, [0])  # the clock's records, exact
-        env = TE.read_submit(r, 4, zeros(1), [0])[0]  # the envelope's
+        read_clock(r, 4, [0])  # the clock's records, exact
+        env = read_envelope(r, 4, zeros(1), [0])[0]  # the envelope's
         bursts = r.read_bursts()
         tab = r.read_captures()
         ev = r.drain()
@@ -346,7 +317,7 @@ def test_the_golden_tfa_2_scene_with_all_five_measurements_and_none():
     assert bursts.tobytes() == burst.bursts(decs, tab[0], zeros(1)).tobytes() and len(bursts) == len(got) == 2
     assert np.array_equal(env["last_over"], trecs["last_over"])
     assert trecs.tobytes() == plain_track[0].tobytes() and twords.tobytes() == plain_track[1].tobytes()
-    TC.assert_tables(tab, plain_runs)
+    R.assert_tables(tab, plain_runs)
     assert parity.sort_events(ev).tobytes() == parity.sort_events(plain).tobytes() and len(ev) >= 1
     tch, sch = track.chains([(trecs, twords)]), sync.chains([(got, words)])
     assert [sync.plateaus(s.bits) for s in sch] == [[p] for p in PLATEAUS["tfa_2"]]
@@ -355,8 +326,8 @@ def test_the_golden_tfa_2_scene_with_all_five_measurements_and_none():
 
 
 def test_the_refusals():
-    x = TC.scene()[:3, :api.BLOCK_BYTES]
-    with api.Receiver(3, TC.CTX_TYPES, 500, 0, max_blocks=2) as r:
+    x = scene()[:3, :api.BLOCK_BYTES]
+    with api.Receiver(3, CTX_TYPES, 500, 0, max_blocks=2) as r:
         raises(api.E_INVAL, r.enable_burst_sync, 17240, WORD, 16)  # no recorder, no track
         raises(api.E_INVAL, r.read_burst_syncs)
         r.enable_capture(64, 1024)
@@ -387,7 +358,7 @@ def test_the_refusals():
         got, words, _ = read_sync(r, sync.Settings(4315, 0xAA2DD4, 24, 11, True), None, trecs, twords)
         assert buf.tobytes() == got.tobytes()
         r.drain()
-    with api.Receiver(3, TC.CTX_TYPES, 500, 0, max_blocks=2) as r:
+    with api.Receiver(3, CTX_TYPES, 500, 0, max_blocks=2) as r:
         r.enable_capture(64, 1024)
         r.enable_burst_track(11)
         r.submit(x)
@@ -409,7 +380,7 @@ def test_a_submit_runs_replay_gives_the_recordings_sync():
         for p, nb in zip(parity.cut(x, (1, 3)), (1, 3)):
             r.submit(p)
             tabs.append(r.read_captures(pre=True))
-            g, w, _, tst = TT.read_submit(r, nb, [pos * B], L, [0], tst)
+            g, w, _, tst = read_track(r, nb, [pos * B], L, [0], tst)
             sg, sw, sst = read_sync(r, st, sst, g, w)
             recs.append((sg, sw))
             pos += nb
@@ -429,39 +400,34 @@ def test_a_submit_runs_replay_gives_the_recordings_sync():
         for k in range(2):
             t, p, q = decin.rebase(runs, pool, pre, 2 * k * B, 2 * B)
             assert r.submit_runs(t, p, q, 2) == 2
-            g, w, _, tst = TT.read_submit(r, 2, [2 * k * B], L, [0], tst, levels=False)
+            g, w, _, tst = read_track(r, 2, [2 * k * B], L, [0], tst, levels=False)
             sg, sw, sst = read_sync(r, st, sst, g, w)
             rep.append((sg, sw))
             r.drain()
     a, b = sync.chains(recs), sync.chains(rep)
     assert len(a) == len(b) == 2
-    for u, v in zip(a, b):
-        assert stripped(u.rec) == stripped(v.rec) and np.array_equal(u.bits, v.bits) and u.bits.any()
+    same_chains("sync", b, a, "the replay")
+    assert all(u.bits.any() for u in a)
 
 
 # ---- tfrec_gpu -G -Y
-def cli_lines(args, timeout=300):
-    out = subprocess.run([parity.CLI] + args, capture_output=True, text=True, timeout=timeout)
-    assert out.returncode == 0, out.stderr
-    keep = [ln for ln in out.stdout.splitlines() if ln.startswith("bits ") or ln.startswith("frame ")]
-    return keep, parity.telegram_lines(out.stdout)
-
-
 def test_cli_frame_lines_of_the_golden_tfa_2_scene_cut_into_three_batches(tmp_path):
     parity.build_cli()
-    x, bits = TT.shifted_tfa_2()  # both telegrams lie across a batch boundary
+    x, bits = shifted_tfa_2()  # both telegrams lie across a batch boundary
     f = str(tmp_path / "tfa2.iq")
     x.tofile(f)
     bits = [ln % f for ln in bits]
-    plain = cli_lines(["-G", "17240"] + TT.BASE + ["-L", f])
-    assert plain[0] == bits
-    got = cli_lines(["-G", "17240", "-Y", "2dd4,0,4"] + TT.BASE + ["-L", f])
-    assert got[1] == plain[1] and [ln for ln in got[0] if ln.startswith("bits ")] == bits
-    assert [ln.split()[0] for ln in got[0]] == ["bits", "frame", "bits", "frame"]
-    frames = [ln.split() for ln in got[0] if ln.startswith("frame ")]
+    base = ["-T", "2f", "-t", "500", "-b", "2"]
+    either = ("bits", "frame")  # both kinds of line, in the order they were printed
+    plain = cli_lines(["-G", "17240"] + base + ["-L", f], either)
+    assert plain[either] == bits
+    got = cli_lines(["-G", "17240", "-Y", "2dd4,0,4"] + base + ["-L", f], either, "bits", "frame")
+    assert got["telegrams"] == plain["telegrams"] and got["bits"] == bits
+    assert [ln.split()[0] for ln in got[either]] == ["bits", "frame", "bits", "frame"]
+    frames = [ln.split() for ln in got["frame"]]
     assert [fr[7] for fr in frames] == list(PAYLOADS["tfa_2"]) and all(fr[1] == f and fr[4:7] == ["0", "+", "32"] for fr in frames)
     for fr, b, p in zip(frames, bits, PLATEAUS["tfa_2"]):
         assert fr[2] == b.split()[2] and int(fr[3]) - int(fr[2]) == (p[0] + p[1]) >> 1
-    both = cli_lines(["-Y", "d22b,1,4,1", "-G", "17240"] + TT.BASE + ["-L", f])  # the complemented word: the same frames, read as -, bit for bit the complement
-    assert [ln.split()[4:] for ln in both[0] if ln.startswith("frame ")] == [["0", "-", "32", "%08x" % (int(p, 16) ^ 0xFFFFFFFF)]
-                                                                                        for p in PAYLOADS["tfa_2"]]
+    # the complemented word: the same frames, read as -, bit for bit the complement
+    both = cli_lines(["-Y", "d22b,1,4,1", "-G", "17240"] + base + ["-L", f], "frame")
+    assert [ln.split()[4:] for ln in both["frame"]] == [["0", "-", "32", "%08x" % (int(p, 16) ^ 0xFFFFFFFF)] for p in PAYLOADS["tfa_2"]]

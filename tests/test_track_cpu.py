@@ -16,32 +16,12 @@ import numpy as np
 import pytest
 
 import parity
+from recorder_rows import GOLDEN, RATE, TELEGRAMS, bit_string, golden_dec, pattern, rotated, stripped, submits
 from tfrec_amd import api, capture, envelope, levels, track, tune
-from test_clock_cpu import golden_dec, rotated
 from test_levels_cpu import crafted_dec
 
 B = levels.BLOCK_DEC
-GOLDEN = ("tfa_1", "tfa_2", "tfa_3", "tx22", "whb")
-RATE = dict(tfa_1=38400, tfa_2=17240, tfa_3=9600, tx22=8842, whb=6000)
 CONT, OPEN = capture.RUN_CONTINUES, capture.RUN_OPEN
-# the first six bytes of each run's golden telegram (tx22: slot 3's events)
-TELEGRAMS = dict(tfa_2=("2dd496070960", "2dd498812225"), tfa_3=("2dd49144363d", "2dd496846244"), tx22=("2dd4a5920189", "2dd4acdb0681"))
-
-
-def submits(dec, sizes, L, centre=0, types=0x2F, thresh=500, brute=False):
-    """The stream cut into submits of `sizes` blocks -> [(records, words)], the recorder's, the thresholds' and the track's state
-    carried from one to the next."""
-    cst = est = tst = None
-    pos, out = 0, []
-    for nb in sizes:
-        part = dec[2 * pos * B:2 * (pos + nb) * B]
-        runs, _, cst = capture.captures(part, types, thresh, cst)
-        thr, est = envelope.thresholds(part, types, thresh, est)
-        form = track.tracks_bruteforce if brute else track.tracks
-        recs, words, tst = form([part], [thr], runs, L, [centre], tst, base=[pos * B])
-        out.append((recs, words))
-        pos += nb
-    return out
 
 
 @functools.lru_cache(maxsize=None)
@@ -105,14 +85,6 @@ def test_the_vectorised_form_equals_the_per_sample_one_on_the_golden_scenes(name
 
 
 # ---- what the bursts said
-def bit_string(symbols):
-    return "".join("01"[s] for s in symbols)
-
-
-def pattern(hex48):
-    return bin(int(hex48, 16))[2:].zfill(48)
-
-
 @pytest.mark.parametrize("hz", [0, 20000])
 def test_the_golden_telegrams_first_six_bytes_are_read(hz):
     """MSB-first and in positive polarity, from the first last_over + 1 samples; after a rotation by +20 kHz about centre 20000."""
@@ -188,10 +160,6 @@ def test_the_quarter_turn_centres():
 
 
 # ---- cutting
-def stripped(rec):
-    return [int(rec[f]) for f in track.TRACK_DTYPE.names if f != "bit_offset"]  # (a piece's place in its own submit's pool)
-
-
 @pytest.mark.parametrize("name", ["tfa_2", "whb"])
 def test_the_merged_chains_are_the_uncut_stream_for_every_block_cut(name):
     dec = golden_dec(name)

@@ -3,76 +3,22 @@ tfrec_gpu -G), bit for bit.
 
 The records and the bitmap's words are compared, byte for byte, with the restatement tfrec_amd/track.py run on the context's OWN
 decimated samples (tfrec_amd_read_decimated), its own run table and the thresholds read back from the same submit, so the front end
-and the recorder ahead of the track are whatever the context runs.  Channel-rate contexts (tfrec_amd_create_decimated) take
-hand-made decimated samples: the layouts the kernels can get wrong are placed exactly.  Everything is an exact integer; nothing
-here has a tolerance.  Nothing here is measured on real recordings."""
+and the recorder ahead of the track are whatever the context runs (recorder.read_track).  Channel-rate contexts
+(tfrec_amd_create_decimated) take hand-made decimated samples: the layouts the kernels can get wrong are placed exactly.
+Everything is an exact integer; nothing here has a tolerance.  Nothing here is measured on real recordings."""
 import functools
-import subprocess
 
 import numpy as np
 import pytest
 
 import parity
-import test_capture_gpu as TC
-import test_clock_gpu as TK
-import test_envelope_gpu as TE
-from test_clock_cpu import keyed
-from test_track_cpu import TELEGRAMS, bit_string, pattern, stripped
-from tfrec_amd import api, burst, capture, decin, envelope, track
+import recorder as R
+from recorder import (B, CONT, OPEN, W, cli_lines, hand_receiver, raises, read_clock, read_envelope, read_track, same_chains,
+                      same_records, zeros)
+from recorder_rows import CTX_TYPES, N, NB, TELEGRAMS, bit_string, golden_iq, keyed, pattern, quiet, scene, shifted_tfa_2
+from tfrec_amd import api, burst, decin, track
 
 pytestmark = pytest.mark.gpu
-
-B = api.BLOCK_DEC
-W = 694  # the largest window of -T 2f
-T = 100  # the hand-made rows' threshold: their quiet parts stay below it (|I| + |Q| <= 80)
-CONT, OPEN = capture.RUN_CONTINUES, capture.RUN_OPEN
-FIELDS = list(track.TRACK_DTYPE.names)
-zeros, raises, golden_iq, quiet = TE.zeros, TE.raises, TE.golden_iq, TE.quiet
-
-
-def assert_records(got, want, label=""):
-    assert got.dtype == track.TRACK_DTYPE and len(got) == len(want), "%s: %d records, want %d" % (label, len(got), len(want))
-    for f in FIELDS:
-        assert np.array_equal(got[f], want[f]), "%s %s: got %s want %s" % (label, f, got[f].tolist()[:12], want[f].tolist()[:12])
-    assert got.tobytes() == want.tobytes(), label
-
-
-def assert_words(got, want, label=""):
-    assert got.dtype == np.uint32 and len(got) == len(want), "%s: %d words, want %d" % (label, len(got), len(want))
-    bad = np.flatnonzero(got != want)
-    assert len(bad) == 0, "%s: %d words differ, the first at %d: got %08x want %08x" % (label, len(bad), bad[0], got[bad[0]], want[bad[0]])
-
-
-def table_of(recs):
-    """The run table a submit's records repeat: their first 24 bytes and bit_offset."""
-    t = np.zeros(len(recs), dtype=capture.RUN_DTYPE)
-    for f in ("stream", "flags", "start_sample", "n_samples", "thresh"):
-        t[f] = recs[f]
-    t["pool_offset"] = recs["bit_offset"]
-    return t
-
-
-def read_submit(r, nb, base, L, centres, state, overflow=False, decs=None, levels=True):
-    """The oldest undrained submit of nb blocks: its records and words against the restatement on what the context itself returns
-    -> (records, words, every stream's decimated samples, the state behind the submit).  decs: that submit's decimated samples
-    where a later submit is queued behind it (tfrec_amd_read_decimated returns the last submit's)."""
-    n = r.n_streams
-    if decs is None:
-        decs = [r.decimated(s, nb * B) for s in range(n)]
-    runs = r.read_captures(allow_overflow=True)[0]
-    got, words = r.read_burst_tracks(allow_overflow=overflow)
-    if levels:  # the threshold in force in every block, as the level meter reports it
-        lev = r.read_levels()
-        thr = [np.repeat(lev[s]["thresh"].astype(np.int64), B) for s in range(n)]
-    else:
-        thr = [int(r.thresh(s)) for s in range(n)]
-    if not r.capture_overflow:
-        assert len(runs) == len(got) == r.track_total
-        assert table_of(got).tobytes() == runs.tobytes()
-    want, wwords, state = track.tracks(decs, thr, table_of(got), L, centres, state, base=base, max_samples=r._capture[1])
-    assert_records(got, want)
-    assert_words(words, wwords)
-    return got, words, decs, state
 
 
 # ---- hand-made rows on a channel-rate context
@@ -100,20 +46,13 @@ def hand_rows():
     return rows
 
 
-def hand_receiver(n, nb, L, thresh=T, cap=None, **kw):
-    r = api.Receiver(n, 0x2F, thresh, 0, max_blocks=nb, decimated=True, levels=True, **kw)
-    r.enable_capture(*(cap or (32 * n, n * nb * B)))
-    r.enable_burst_track(L)
-    return r
-
-
 @functools.lru_cache(maxsize=None)
 def hand_uncut(L):
     rows = hand_rows()
-    with hand_receiver(2, 2, L) as r:
+    with hand_receiver(2, 2, {"track": (L,)}) as r:
         r.set_burst_track_centre([0, 1], CENTRES[L])
         r.submit(np.ascontiguousarray(rows))
-        got, words, decs, _ = read_submit(r, 2, [0, 0], L, CENTRES[L], None)
+        got, words, decs, _ = read_track(r, 2, [0, 0], L, CENTRES[L], None)
         again = r.read_burst_tracks()  # reading pops nothing
         assert again[0].tobytes() == got.tobytes() and again[1].tobytes() == words.tobytes()
         r.drain()
@@ -153,14 +92,14 @@ def test_two_streams_of_two_blocks_of_hand_made_samples(L):
 def test_the_same_rows_in_two_submits_queued_before_the_first_read(L):
     whole, wwords = hand_uncut(L)
     rows = hand_rows()
-    with hand_receiver(2, 1, L) as r:
+    with hand_receiver(2, 1, {"track": (L,)}) as r:
         r.set_burst_track_centre([0, 1], CENTRES[L])
         for k in range(2):  # both queued before the first read
             r.submit(np.ascontiguousarray(rows[:, k * B:(k + 1) * B]))
         got, st = [], None
         for k in range(2):
             part = decin.clamp(rows[:, k * B:(k + 1) * B])  # (a channel-rate context's samples are its input, clamped: hand_uncut)
-            recs, words, _, st = read_submit(r, 1, [k * B] * 2, L, CENTRES[L], st, decs=[part[s].reshape(-1) for s in range(2)])
+            recs, words, _, st = read_track(r, 1, [k * B] * 2, L, CENTRES[L], st, decs=[part[s].reshape(-1) for s in range(2)])
             if k == 0:
                 assert st["prior"].tolist() == [3, 0]  # stream 0's chain begins 3 samples ahead of the cut
             got.append((recs, words))
@@ -172,8 +111,7 @@ def test_the_same_rows_in_two_submits_queued_before_the_first_read(L):
     key = lambda c: (int(c["stream"]), int(c["start_sample"]))  # noqa: E731
     merged, uncut = sorted(track.chains(got), key=key), sorted(track.chains([(whole, wwords)]), key=key)
     assert len(merged) == len(uncut) == len(whole)
-    for a, b in zip(merged, uncut):
-        assert stripped(a.rec) == stripped(b.rec) and np.array_equal(a.bits, b.bits), key(a)
+    same_chains("track", merged, uncut, "1 + 1")
 
 
 @pytest.mark.parametrize("n", [65, 97])
@@ -185,10 +123,10 @@ def test_stream_counts_across_a_waves_end(n):
     kinds[0][0] = (300, 300)  # (... from the first sample on)
     x = np.ascontiguousarray(np.stack(kinds)[np.arange(n) % len(kinds)])
     centres = [(0, 20000, -35000)[s % 3] for s in range(n)]
-    with hand_receiver(n, nb, L) as r:
+    with hand_receiver(n, nb, {"track": (L,)}) as r:
         r.set_burst_track_centre(range(n), centres)
         r.submit(x)
-        got, words, decs, st = read_submit(r, nb, [0] * n, L, centres, None)
+        got, words, decs, st = read_track(r, nb, [0] * n, L, centres, None)
         r.drain()
     assert got["stream"].tolist() == [s for s in range(n) if s % 4 != 3]  # (row 3 is quiet)
     assert (got["n_samples"] == nb * B).all() and (got["flags"] == OPEN).all() and len(words) == len(got) * nb * B // 32
@@ -203,17 +141,17 @@ def test_a_centre_changed_between_two_submits():
     """Not a restart: the chain continues, and the second piece -- the carried products included -- is formed about the new centre."""
     rows = hand_rows()
     L = 5
-    with hand_receiver(2, 1, L) as r:
+    with hand_receiver(2, 1, {"track": (L,)}) as r:
         raises(api.E_INVAL, r.set_burst_track_centre, [0], [192001])
         raises(api.E_INVAL, r.set_burst_track_centre, [0, 2], [0, 0])  # a stream out of range: nothing is set
         raises(api.E_INVAL, r.set_burst_track_centre, [1, 0], [5000, -192001])
         r.set_burst_track_centre([], [])
         r.submit(np.ascontiguousarray(rows[:, :B]))
-        a, wa, d0, st = read_submit(r, 1, [0, 0], L, [0, 0], None)  # the refused calls set nothing
+        a, wa, d0, st = read_track(r, 1, [0, 0], L, [0, 0], None)  # the refused calls set nothing
         r.drain()
         r.set_burst_track_centre([0, 1], [-60000, 192000])
         r.submit(np.ascontiguousarray(rows[:, B:]))
-        b, wb, _, st = read_submit(r, 1, [B, B], L, [-60000, 192000], st)
+        b, wb, _, st = read_track(r, 1, [B, B], L, [-60000, 192000], st)
         r.drain()
     assert b[0]["flags"] & CONT and b[0]["stream"] == 0
     ch = [c for c in track.chains([(a, wa), (b, wb)]) if c["stream"] == 0 and c["start_sample"] == B - 3]
@@ -224,24 +162,24 @@ def test_a_centre_changed_between_two_submits():
 
 # ---- the other kinds of context
 def scene_receiver(L, **kw):
-    r = TC.receiver(levels=True, **kw)
+    r = R.receiver(levels=True, **kw)
     r.enable_burst_track(L)
     return r
 
 
 def test_a_reset_mid_chain_drops_the_chain():
     L = 9
-    parts = parity.cut(TC.scene(), (2, 2))
+    parts = parity.cut(scene(), (2, 2))
     cen = [0, 20000, 0, -35000, 0, 0, 20000, 20000]
     with scene_receiver(L, max_blocks=2) as r:
-        r.set_burst_track_centre(range(TC.N), cen)
+        r.set_burst_track_centre(range(N), cen)
         r.submit(parts[0])
-        got0, w0, _, st = read_submit(r, 2, [0] * TC.N, L, cen, None)
+        got0, w0, _, st = read_track(r, 2, [0] * N, L, cen, None)
         r.drain()
         r.reset_streams([1, 6])
         r.submit(parts[1])
-        base = [0 if s in (1, 6) else 2 * B for s in range(TC.N)]  # a reset stream counts from 0 again
-        got1, w1, _, st = read_submit(r, 2, base, L, cen, st)
+        base = [0 if s in (1, 6) else 2 * B for s in range(N)]  # a reset stream counts from 0 again
+        got1, w1, _, st = read_track(r, 2, base, L, cen, st)
         ev1 = r.drain()
     assert got0[got0["stream"] == 6][-1]["flags"] & OPEN
     r6 = got1[got1["stream"] == 6]
@@ -252,14 +190,15 @@ def test_a_reset_mid_chain_drops_the_chain():
     six = [c for c in ch if c["stream"] == 6]
     assert len(six) == len(got0[got0["stream"] == 6]) + len(r6)  # nothing of stream 6 was merged across the reset
     with scene_receiver(L) as r:  # the uncut scene: stream 7's chain across the cut is the uncut run
-        r.set_burst_track_centre(range(TC.N), cen)
-        r.submit(TC.scene())
-        whole, ww, _, _ = read_submit(r, TC.NB, [0] * TC.N, L, cen, None)
+        r.set_burst_track_centre(range(N), cen)
+        r.submit(scene())
+        whole, ww, _, _ = read_track(r, NB, [0] * N, L, cen, None)
         r.drain()
     seven = [c for c in ch if c["stream"] == 7 and c["start_sample"] < 2 * B < c["start_sample"] + c["n_samples"]]
     assert len(seven) == 1
     u = [c for c in track.chains([(whole, ww)]) if c["stream"] == 7 and c["start_sample"] == seven[0]["start_sample"]]
-    assert len(u) == 1 and stripped(u[0].rec) == stripped(seven[0].rec) and np.array_equal(u[0].bits, seven[0].bits)
+    assert len(u) == 1
+    same_chains("track", seven, u, "stream 7 across the cut")
 
 
 def test_the_golden_tfa_2_scene_with_all_four_measurements_and_none():
@@ -282,9 +221,9 @@ def test_the_golden_tfa_2_scene_with_all_four_measurements_and_none():
         r.enable_burst_meter()
         r.enable_burst_envelope()
         r.submit(x)
-        got, words, decs, _ = read_submit(r, 4, [0], 11, [0], None)
-        TK.read_submit(r, 4, [0])  # the clock's records, exact
-        env = TE.read_submit(r, 4, zeros(1), [0])[0]  # the envelope's
+        got, words, decs, _ = read_track(r, 4, [0], 11, [0], None)
+        read_clock(r, 4, [0])  # the clock's records, exact
+        env = read_envelope(r, 4, zeros(1), [0])[0]  # the envelope's
         bursts = r.read_bursts()
         tab = r.read_captures()
         ev = r.drain()
@@ -292,7 +231,7 @@ def test_the_golden_tfa_2_scene_with_all_four_measurements_and_none():
         assert r.memory() == plain_mem  # a context without the call holds what it held
     assert bursts.tobytes() == burst.bursts(decs, tab[0], zeros(1)).tobytes() and len(bursts) == len(got) == 2
     assert np.array_equal(env["last_over"], got["last_over"])
-    TC.assert_tables(tab, plain_runs)
+    R.assert_tables(tab, plain_runs)
     assert parity.sort_events(ev).tobytes() == parity.sort_events(plain).tobytes() and len(ev) >= 1
     lines = [track.line("f", c, 17240) for c in track.chains([(got, words)])]
     assert [ln.split()[4:6] for ln in lines] == [["1474", "66"], ["1475", "66"]]
@@ -313,7 +252,7 @@ def test_a_submit_runs_replay_gives_the_recordings_track():
         for p, nb in zip(parity.cut(x, (1, 3)), (1, 3)):
             r.submit(p)
             tabs.append(r.read_captures(pre=True))
-            g, w, _, st = read_submit(r, nb, [pos * B], L, [0], st)
+            g, w, _, st = read_track(r, nb, [pos * B], L, [0], st)
             recs.append((g, w))
             pos += nb
             r.drain()
@@ -331,43 +270,42 @@ def test_a_submit_runs_replay_gives_the_recordings_track():
         for k in range(2):
             t, p, q = decin.rebase(runs, pool, pre, 2 * k * B, 2 * B)
             assert r.submit_runs(t, p, q, 2) == 2
-            g, w, _, st = read_submit(r, 2, [2 * k * B], L, [0], st, levels=False)
+            g, w, _, st = read_track(r, 2, [2 * k * B], L, [0], st, levels=False)
             rep.append((g, w))
             r.drain()
     a, b = track.chains(recs), track.chains(rep)
     assert len(a) == len(b) == 2
-    for u, v in zip(a, b):
-        assert stripped(u.rec) == stripped(v.rec) and np.array_equal(u.bits, v.bits)
+    same_chains("track", b, a, "the replay")
 
 
 def test_overflow_on_max_runs_and_on_max_samples_delivers_the_prefixes():
     L = 5
     whole, wwords = hand_uncut(L)
     rows = np.ascontiguousarray(hand_rows())
-    with hand_receiver(2, 2, L, cap=(len(whole) - 1, 4 * B)) as r:  # the table a run short
+    with hand_receiver(2, 2, {"track": (L,)}, cap=(len(whole) - 1, 4 * B)) as r:  # the table a run short
         r.set_burst_track_centre([0, 1], CENTRES[L])
         r.submit(rows)
         raises(api.E_OVERFLOW, r.read_burst_tracks)
-        got, words, _, _ = read_submit(r, 2, [0, 0], L, CENTRES[L], None, overflow=True)
+        got, words, _, _ = read_track(r, 2, [0, 0], L, CENTRES[L], None, overflow=True)
         assert r.track_total == len(whole) and r.capture_overflow
-        assert_records(got, whole[:-1], "the prefix")
+        same_records(got, whole[:-1], "the prefix")
         assert len(words) == (int(whole[-1]["bit_offset"]) + 31) // 32  # the pairs of the runs the table holds
         r.drain()
     room = int(whole[3]["bit_offset"] + whole[3]["n_samples"])  # the pool holds the first four runs, and not the fifth
-    with hand_receiver(2, 2, L, cap=(32, room + 10)) as r:
+    with hand_receiver(2, 2, {"track": (L,)}, cap=(32, room + 10)) as r:
         r.set_burst_track_centre([0, 1], CENTRES[L])
         r.submit(rows)
         raises(api.E_OVERFLOW, r.read_burst_tracks)
-        got, words, _, _ = read_submit(r, 2, [0, 0], L, CENTRES[L], None, overflow=True)
-        assert_records(got, whole, "every record")  # ... n_ones of the runs whose bits did not fit included
+        got, words, _, _ = read_track(r, 2, [0, 0], L, CENTRES[L], None, overflow=True)
+        same_records(got, whole, "every record")  # ... n_ones of the runs whose bits did not fit included
         assert len(words) == (room + 31) // 32 and len(r.read_captures(allow_overflow=True)[0]) == 4
         r.drain()
 
 
 def test_the_refusals_and_the_memory_sums():
     n, mb = 3, 2
-    x = TC.scene()[:n, :api.BLOCK_BYTES]
-    with api.Receiver(n, TC.CTX_TYPES, 500, 0, max_blocks=mb) as r:
+    x = scene()[:n, :api.BLOCK_BYTES]
+    with api.Receiver(n, CTX_TYPES, 500, 0, max_blocks=mb) as r:
         plain = r.memory()
         raises(api.E_INVAL, r.enable_burst_track, 5)  # no recorder
         raises(api.E_INVAL, r.read_burst_tracks)
@@ -386,7 +324,7 @@ def test_the_refusals_and_the_memory_sums():
         assert r.memory() == submitted
         runs_plain = r.read_captures()
         ev_plain = r.drain()
-    with api.Receiver(n, TC.CTX_TYPES, 500, 0, max_blocks=mb) as r:
+    with api.Receiver(n, CTX_TYPES, 500, 0, max_blocks=mb) as r:
         r.enable_capture(64, 1024)
         assert r.memory() == rec  # a recorder without the track holds what it held
         r.enable_burst_track(16)
@@ -418,43 +356,13 @@ def test_the_refusals_and_the_memory_sums():
         assert len(recs) == len(runs_plain[0]) == len(r.read_bursts()) == len(r.read_burst_clocks()) == 1
         runs = r.read_captures()
         ev = r.drain()
-    TC.assert_tables(runs, runs_plain)
+    R.assert_tables(runs, runs_plain)
     assert parity.sort_events(ev).tobytes() == parity.sort_events(ev_plain).tobytes()
 
 
 # ---- tfrec_gpu -G
-def cli_lines(args, timeout=300):
-    out = subprocess.run([parity.CLI] + args, capture_output=True, text=True, timeout=timeout)
-    assert out.returncode == 0, out.stderr
-    pick = lambda word: [ln for ln in out.stdout.splitlines() if ln.startswith(word + " ")]  # noqa: E731
-    return pick("bits"), pick("burst"), pick("extent"), pick("clock"), parity.telegram_lines(out.stdout)
-
-
-@functools.lru_cache(maxsize=None)
-def shifted_tfa_2():
-    """The golden TFA_2 scene moved 5500 decimated samples back inside 6 blocks of silence, so that -b 2 makes three batches and
-    both telegrams lie across a batch boundary -> (its bytes, the lines track.py expects of tfrec_gpu -G 17240 on a file named %s)."""
-    x = np.full(6 * api.BLOCK_BYTES, 128, dtype=np.uint8)
-    scene = golden_iq()[0]
-    x[8 * 5500:8 * 5500 + len(scene)] = scene
-    # the restatement: the oracle's front end (the context's, bit for bit), capture.py, envelope.py's thresholds and track.py submit
-    # by submit (2 + 2 + 2)
-    dec = parity.fresh_oracle(x, 0x2F, 500, keep_dec=True).dec().reshape(-1, 2)
-    subs, cst, est, tst = [], None, None, None
-    for a, b in ((0, 2), (2, 4), (4, 6)):
-        part = dec[a * B:b * B].reshape(-1)
-        runs, _, cst = capture.captures(part, 0x2F, 500, cst)
-        thr, est = envelope.thresholds(part, 0x2F, 500, est)
-        recs, words, tst = track.tracks([part], [thr], runs, 11, [0], tst, base=[a * B])
-        subs.append((recs, words))
-    assert any(c["flags"] & CONT for c in subs[1][0]) and any(c["flags"] & CONT for c in subs[2][0])  # both bursts are cut
-    chains = track.chains(subs)
-    for c, tel in zip(chains, TELEGRAMS["tfa_2"]):
-        assert pattern(tel) in bit_string(track.slice_bits(c.bits[:int(c["last_over"]) + 1], 17240))
-    return x, [track.line("%s", c, 17240) for c in chains]
-
-
 BASE = ["-T", "2f", "-t", "500", "-b", "2"]
+WORDS = ("bits", "burst", "extent", "clock")
 
 
 def test_cli_bits_lines_of_the_golden_tfa_2_scene_cut_into_three_batches(tmp_path):
@@ -464,15 +372,17 @@ def test_cli_bits_lines_of_the_golden_tfa_2_scene_cut_into_three_batches(tmp_pat
     x.tofile(f)
     want = [ln % f for ln in want]
     assert len(want) == 2 and all(ln.split()[5] == "66" for ln in want)
-    plain = cli_lines(BASE + ["-L", f])
-    got = cli_lines(["-G", "17240"] + BASE + ["-L", f])
-    assert plain[0] == [] and got[4] == plain[4] and got[1] == got[2] == got[3] == []  # the telegrams do not notice
-    assert got[0] == want
+    plain = cli_lines(BASE + ["-L", f], *WORDS)
+    got = cli_lines(["-G", "17240"] + BASE + ["-L", f], *WORDS)
+    assert plain["bits"] == [] and got["telegrams"] == plain["telegrams"]  # the telegrams do not notice
+    assert got["burst"] == got["extent"] == got["clock"] == []
+    assert got["bits"] == want
     f2 = str(tmp_path / "short.iq")  # through a recycled slot beside a second file
     x[:2 * api.BLOCK_BYTES].tofile(f2)
-    slot = cli_lines(["-G", "17240", "-n", "1"] + BASE + ["-L", f, "-L", f2])
-    assert [ln for ln in slot[0] if ln.split()[1] == f] == want
+    slot = cli_lines(["-G", "17240", "-n", "1"] + BASE + ["-L", f, "-L", f2], *WORDS)
+    assert [ln for ln in slot["bits"] if ln.split()[1] == f] == want
     # beside -M, -Q and -C: all four kinds of line, each what it is alone
-    alone = cli_lines(["-M", "-Q", "-C"] + BASE + ["-L", f])
-    every = cli_lines(["-M", "-Q", "-C", "-G", "17240,0"] + BASE + ["-L", f])
-    assert alone[0] == [] and every[0] == want and every[1:] == alone[1:] and len(alone[1]) == len(alone[2]) == len(alone[3]) == 2
+    alone = cli_lines(["-M", "-Q", "-C"] + BASE + ["-L", f], *WORDS)
+    every = cli_lines(["-M", "-Q", "-C", "-G", "17240,0"] + BASE + ["-L", f], *WORDS)
+    assert alone["bits"] == [] and every["bits"] == want and len(alone["burst"]) == len(alone["extent"]) == len(alone["clock"]) == 2
+    assert all(every[w] == alone[w] for w in ("burst", "extent", "clock", "telegrams"))
