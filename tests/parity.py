@@ -1,8 +1,11 @@
 """The harness the HIP-path tests share: feeding a Receiver through its submit FIFO, fresh oracles, and the comparisons of
 drained events with the oracle's -- every field, per slot in order, seq, the bit log --; the runner of rate and format
-receivers with its cutter, stage-0 comparison and input builders; the table of receiver modes; building and running tfrec_gpu.
+receivers with its cutter, stage-0 comparison and input builders; the table of receiver modes; building and running tfrec_gpu;
+the golden vectors' records and digests; the imports of a file, for the rule that no test module imports another.
 Imported as a plain module (`import parity`) from the test modules and from tests/stress_gpu.py."""
+import ast
 import functools
+import hashlib
 import os
 import subprocess
 
@@ -44,6 +47,11 @@ def to_device(parts):
     import torch
 
     return [torch.from_numpy(h).to("cuda:0") for h in parts]
+
+
+def device_parts(iq, sizes, block=api.BLOCK_BYTES):
+    hosts = [np.ascontiguousarray(p) for p in cut(iq, sizes, block)]
+    return to_device(hosts), hosts
 
 
 def run_fifo(r, parts, depth=api.FIFO_DEPTH, before=None, after=None):
@@ -318,6 +326,11 @@ def build_cli():
     return CLI
 
 
+def run_cli(args, timeout=120):
+    """tfrec_gpu, whatever its exit status -> the CompletedProcess."""
+    return subprocess.run([CLI] + args, capture_output=True, text=True, timeout=timeout)
+
+
 def cli_stdout(args, timeout=600):
     out = subprocess.run([CLI] + args, capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0, out.stderr
@@ -330,3 +343,24 @@ def cli(args, sink, timeout=600):
     out = subprocess.run([CLI] + args + ["-E", "cat > %s" % sink], capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0, out.stderr
     return out.stdout, [ln.split()[:-1] for ln in open(sink).read().splitlines()]
+
+
+# ---- the golden vectors (tests/golden/*.json)
+def golden_data(recs):
+    return [(r[0], r[1], int(r[2], 16), float.fromhex(r[3]), float.fromhex(r[4]), r[5], r[6], r[7], r[8]) for r in recs]
+
+
+def sha256_of(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+# ---- the import rule
+def imports_of(path, source=None):
+    """The top-level names of every module a file imports, anywhere in it (source: the text to parse in the file's place)."""
+    out = set()
+    for node in ast.walk(ast.parse(open(path).read() if source is None else source, path)):
+        if isinstance(node, ast.Import):
+            out |= {a.name.split(".")[0] for a in node.names}
+        elif isinstance(node, ast.ImportFrom) and node.module and node.level == 0:
+            out.add(node.module.split(".")[0])
+    return out

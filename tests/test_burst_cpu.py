@@ -15,7 +15,7 @@ import pytest
 
 import parity
 from tfrec_amd import api, burst, capture, levels, tune
-from test_levels_cpu import crafted_dec
+from meter_rows import crafted_dec
 
 B = levels.BLOCK_DEC
 GOLDEN = ("tfa_1", "tfa_2", "tfa_3", "tx22", "whb")
@@ -259,18 +259,15 @@ def test_the_struct_and_the_exports(tmp_path):
 
 
 def test_cli_meter_usage_errors(tmp_path):
-    cli = parity.build_cli()
+    parity.build_cli()
     f = str(tmp_path / "missing.iq")
 
-    def run(args):
-        return subprocess.run([cli] + args, capture_output=True, text=True, timeout=120)
-
-    out = run(["-M", "-X", f])
+    out = parity.run_cli(["-M", "-X", f])
     assert out.returncode == 1 and "-M measures" in out.stderr
-    out = run(["-h"])
+    out = parity.run_cli(["-h"])
     assert "-M " in out.stderr
     for args in (["-M", "-L", f], ["-M", "-s", "50", "-L", f], ["-M", "-S", str(tmp_path / "cap"), "-n", "1", "-L", f]):
-        out = run(args)  # accepted: the file is looked for
+        out = parity.run_cli(args)  # accepted: the file is looked for
         assert out.returncode == 2 and "missing.iq" in out.stderr, args
-    out = run(["-M", "-R", str(tmp_path / "nothing")])  # accepted with -R: the capture is looked for
+    out = parity.run_cli(["-M", "-R", str(tmp_path / "nothing")])  # accepted with -R: the capture is looked for
     assert out.returncode == 2 and "-R replays" not in out.stderr

@@ -12,7 +12,7 @@ import pytest
 
 import parity
 from tfrec_amd import api, capture, levels
-from test_levels_cpu import SUBSETS, crafted_dec
+from meter_rows import SUBSETS, crafted_dec
 
 B = levels.BLOCK_DEC
 PAIR_GAPS = lambda W: (W - 1, W, W + 1, W + 2)  # noqa: E731  (crafted_dec's trigger pairs, from sample 200 on)
@@ -197,21 +197,18 @@ def test_the_struct_and_the_exports(tmp_path):
 
 # ---- tfrec_gpu -S: what is decided before a device is opened
 def test_cli_capture_usage_errors(tmp_path):
-    cli = parity.build_cli()
+    parity.build_cli()
     f = str(tmp_path / "missing.iq")
     pre = str(tmp_path / "cap")
 
-    def run(args):
-        return subprocess.run([cli] + args, capture_output=True, text=True, timeout=120)
-
-    out = run(["-S", pre, "-X", f])
+    out = parity.run_cli(["-S", pre, "-X", f])
     assert out.returncode == 1 and "-S records" in out.stderr
-    out = run(["-S", "", "-L", f])
+    out = parity.run_cli(["-S", "", "-L", f])
     assert out.returncode == 1 and "bad -S" in out.stderr
-    out = run(["-S"])
+    out = parity.run_cli(["-S"])
     assert out.returncode == 1
     for args in (["-S", pre, "-L", f], ["-S", pre, "-s", "50", "-L", f]):  # accepted: the file is looked for
-        out = run(args)
+        out = parity.run_cli(args)
         assert out.returncode == 2 and "missing.iq" in out.stderr, args
     assert not os.path.exists(pre + ".idx")
 

@@ -11,23 +11,11 @@ import numpy as np
 import pytest
 
 import parity
+from input_rows import EMPTY_HZ, WIDE_BURSTS, wide_scene
 from oracle import oracle as O
-from tfrec_amd import api, synth, tune
+from tfrec_amd import api, tune
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-# the wide scene every test of the feature uses (test_channels_gpu.py too): one burst per protocol of the TFA_2 family and TFA_1,
-# each at its own offset in the 15.36 MS/s band, each in its own time slot; nothing at EMPTY_HZ
-WIDE_BLOCKS = 4
-WIDE_BURSTS = ((-5200000, 0), (-1100000, 1), (3300000, 2), (6900000, 3))  # (offset in Hz, protocol = slot)
-EMPTY_HZ = 2000000
-
-
-def wide_scene(seed=41, n_blocks=WIDE_BLOCKS, amp=40):
-    n = n_blocks * api.BLOCK_BYTES // 2 * 10  # input samples
-    bursts = [dict(proto=p, start=(200000 + j * (n - 400000) // 4) // 10 * 10, payload_seed=5 + j, f0_hz=f, amp=amp)
-              for j, (f, p) in enumerate(WIDE_BURSTS)]
-    return synth.gen_scene(seed, n_blocks, bursts, rate_mult=10)
 
 
 def receive(x16, f):

@@ -10,34 +10,11 @@ import pytest
 
 import parity
 import segments
+from input_rows import CFGS, DFLT, EMPTY_HZ, ROW_TUNES, ROWS, WIDE_BURSTS, WIDE_SCENE_BLOCKS, make_rows, wide_scene
+from parity import device_parts
 from tfrec_amd import api, synth, tune
-from test_channels_cpu import EMPTY_HZ, WIDE_BLOCKS, WIDE_BURSTS, wide_scene
 
 pytestmark = pytest.mark.gpu
-
-DFLT = (0x2F, 500, 0)
-ROWS = 6
-# the four receivers of row j are tuned to ROW_TUNES[j]; each row carries a burst at every one of them (and one at the centre)
-ROW_TUNES = [(0, 200000, -250000, 25000), (150000, 0, -400000, 767999), (-767999, 12345, 0, 500000),
-             (-200000, 99999, 700001, 0), (0, -25000, 31, -654321), (300000, -1, -500000, 0)]
-CFGS = {1: (0x2F, 500, 1), 2: (0x03, 0, 0), 4: (0x21, 300, 0), 5: (0x2F, 0, 1), 7: (0x01, 500, 0), 8: (0x2F, 900, 0),
-        10: (0x02, 0, 1), 13: (0x2F, 300, 0), 14: (0x06, 0, 0), 17: (0x0C, 500, 0), 20: (0x28, 500, 1), 23: (0x01, 0, 1)}
-
-
-def make_rows(seed, n_blocks, rows=ROWS):
-    out = []
-    n = n_blocks * api.BLOCK_BYTES // 2
-    for j in range(rows):
-        offs = sorted(set(ROW_TUNES[j % len(ROW_TUNES)]) | {0})
-        bursts = [dict(proto=(j + i) % 5, start=20000 + i * (n - 60000) // len(offs), payload_seed=7 + j + 11 * i, f0_hz=f,
-                       amp=50 + 5 * i) for i, f in enumerate(offs)]
-        out.append(synth.gen_scene(seed * 100 + j, n_blocks, bursts))
-    return np.stack(out)
-
-
-def device_parts(iq, sizes, block=api.BLOCK_BYTES):
-    hosts = [np.ascontiguousarray(p) for p in parity.cut(iq, sizes, block)]
-    return parity.to_device(hosts), hosts
 
 
 @pytest.mark.parametrize("mode", ["deep", "shallow", "serial_chains", "bits"])
@@ -77,7 +54,7 @@ def test_wideband_receivers_of_one_row():
     """The CPU test's scene on ONE row of a 10x context: a receiver per planted offset, one on an empty frequency, an untuned
     one, one that combines a wide tune with a 1.536 MS/s tune, the two limits; a restart in mid-stream."""
     sizes = (1, 2, 1)
-    assert sum(sizes) == WIDE_BLOCKS
+    assert sum(sizes) == WIDE_SCENE_BLOCKS
     wides = [f for f, _ in WIDE_BURSTS] + [EMPTY_HZ, 0, 3300000 - 200000, 7679999, -7679999]
     n = len(wides)
     tunes = [0] * n

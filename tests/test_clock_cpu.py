@@ -17,7 +17,7 @@ import pytest
 import parity
 from recorder_rows import golden_dec, keyed, mx_rows, rotated, silent_rows
 from tfrec_amd import api, capture, clock, levels, synth
-from test_levels_cpu import crafted_dec
+from meter_rows import crafted_dec
 
 B = levels.BLOCK_DEC
 SEG = clock.SEG
@@ -328,26 +328,23 @@ def test_the_struct_and_the_exports(tmp_path):
 
 
 def test_cli_clock_usage_errors(tmp_path):
-    cli = parity.build_cli()
+    parity.build_cli()
     f = str(tmp_path / "missing.iq")
 
-    def run(args):
-        return subprocess.run([cli] + args, capture_output=True, text=True, timeout=120)
-
-    out = run(["-C", "-X", f])
+    out = parity.run_cli(["-C", "-X", f])
     assert out.returncode == 1 and "-C measures" in out.stderr
-    out = run(["-M", "-Q", "-C", "-X", f])  # -M's own refusal comes first and is what it was
+    out = parity.run_cli(["-M", "-Q", "-C", "-X", f])  # -M's own refusal comes first and is what it was
     assert out.returncode == 1 and "-M measures" in out.stderr
-    out = run(["-Q", "-C", "-X", f])
+    out = parity.run_cli(["-Q", "-C", "-X", f])
     assert out.returncode == 1 and "-Q measures" in out.stderr
-    out = run(["-h"])
+    out = parity.run_cli(["-h"])
     assert "-C " in out.stderr and "[-C]" in out.stderr
     for args in (["-C", "-k", str(tmp_path / "keep"), "-L", f], ["-C", "-K", str(tmp_path / "keep"), "-L", f]):
-        out = run(args)
+        out = parity.run_cli(args)
         assert out.returncode == 2 and "not with -C" in out.stderr, args
     for args in (["-C", "-L", f], ["-C", "-M", "-Q", "-L", f], ["-C", "-s", "50", "-L", f],
                  ["-C", "-S", str(tmp_path / "cap"), "-n", "1", "-L", f]):
-        out = run(args)  # accepted: the file is looked for
+        out = parity.run_cli(args)  # accepted: the file is looked for
         assert out.returncode == 2 and "missing.iq" in out.stderr, args
-    out = run(["-C", "-R", str(tmp_path / "nothing")])  # accepted with -R: the capture is looked for
+    out = parity.run_cli(["-C", "-R", str(tmp_path / "nothing")])  # accepted with -R: the capture is looked for
     assert out.returncode == 2 and "-R replays" not in out.stderr

@@ -4,21 +4,18 @@ the golden scenes behind the oracle, the exports and what tfrec_gpu decides befo
 
 Everything is an exact integer; nothing here has a tolerance."""
 import ctypes as C
-import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import parity
+from meter_rows import golden_scene, offset_scene
 from oracle import oracle as O
 from tfrec_amd import api, dcblock, formats
 
 L = dcblock.L
-GOLDEN = os.path.join(parity.ROOT, "tests", "golden")
 SCENES = ("tfa_1", "tfa_2", "tfa_3", "tx22", "whb")
-OFFSET = (8, -4)  # the acceptance test's offset in u8 LSB: +d on I, -d / 2 on Q
 
 
 def noisy_rows(fmt, n, seed, dc=(300, -170)):
@@ -172,22 +169,6 @@ def test_every_permitted_submit_of_every_q_is_whole_windows():
 
 
 # ---- the acceptance table: the golden scenes with a DC offset, behind the oracle
-@functools.lru_cache(maxsize=None)
-def golden_scene(name):
-    z = np.load(os.path.join(GOLDEN, "iq_%s.npz" % name))
-    iq = z["iq"][:len(z["iq"]) // api.BLOCK_BYTES * api.BLOCK_BYTES]  # whole blocks
-    o = O.Oracle(0x2F, 500)
-    o.process(iq)
-    return iq, o.text()
-
-
-def offset_scene(name, d=OFFSET):
-    """The scene's u8 bytes with +d[0] on I and d[1] on Q, clipped to 0 .. 255."""
-    iq, _ = golden_scene(name)
-    v = iq.astype(np.int32).reshape(-1, 2) + np.asarray(d)
-    return np.clip(v, 0, 255).astype(np.uint8).reshape(-1)
-
-
 @pytest.mark.parametrize("name", SCENES)
 def test_offset_scenes_decode_behind_the_blocker_and_not_without(name):
     iq, clean = golden_scene(name)
@@ -242,23 +223,19 @@ def cli():
     return parity.build_cli()
 
 
-def run_cli(cli, args):
-    return subprocess.run([cli] + args, capture_output=True, text=True, timeout=120)
-
-
 def test_cli_usage_errors(cli, tmp_path):
     f = str(tmp_path / "missing.iq")
     for extra in (["-x"], ["-X", f]):
-        out = run_cli(cli, ["-z", "-L", f] + extra)
+        out = parity.run_cli(["-z", "-L", f] + extra)
         assert out.returncode == 1 and "-z removes the DC offset" in out.stderr, extra
     for bad in ("0", "4097", "64x", "9999999999"):
         for args in (["-z", bad], ["-z" + bad]):
-            out = run_cli(cli, args + ["-L", f])
+            out = parity.run_cli(args + ["-L", f])
             assert out.returncode == 1 and "bad -z" in out.stderr, args
     for args in (["-z"], ["-z", "1"], ["-z4096"], ["-z", "-r", "2048000", "-F", "s16"], ["-z", "64", "-c", "868250", "-f", "868300"],
                  ["-z", "-p", "t=300"], ["-z", "-s", "50"], ["-z", "-S", str(tmp_path / "cap")], ["-z", "-P", "256"], ["-z", "-A"],
                  ["-z", "-n", "1"], ["-D", "-z", "2048"]):
-        out = run_cli(cli, args + ["-L", f])  # accepted: the file is looked for
+        out = parity.run_cli(args + ["-L", f])  # accepted: the file is looked for
         assert out.returncode == 2 and "missing.iq" in out.stderr, args
-    out = run_cli(cli, ["-h"])
+    out = parity.run_cli(["-h"])
     assert out.returncode == 0 and "-z [n]" in out.stderr

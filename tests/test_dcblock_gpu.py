@@ -11,9 +11,10 @@ import numpy as np
 import pytest
 
 import parity
+from input_rows import stage0_of_x
+from meter_rows import OFFSET, golden_scene, offset_scene
 from oracle import oracle as O
 from tfrec_amd import api, dcblock, formats, resample, synth, tune
-from test_dcblock_cpu import OFFSET, golden_scene, offset_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -63,11 +64,6 @@ def corrected(rows, fmt, k, sizes, p=1, q=1, reset_before=None):
         assert pos == len(row)
         out.append((np.concatenate(xs), ds))
     return out
-
-
-def stage0_of_x(x, p, q, input_hz=0):
-    x = tune.mix_in_s16(x, input_hz, p, q) if input_hz else x
-    return x if (p, q) == (1, 1) else resample.resample_x16(x, p, q)
 
 
 def oracle_of(y0, narrow_hz=0, types=TYPES, thresh=THRESH, **kw):

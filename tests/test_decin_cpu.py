@@ -12,7 +12,7 @@ import pytest
 
 import parity
 from tfrec_amd import api, capture, decin, levels
-from test_levels_cpu import crafted_dec
+from meter_rows import crafted_dec
 
 B = levels.BLOCK_DEC
 TYPE_SETS = (0x2F, 0x01, 0x02, 0x24)
@@ -189,21 +189,18 @@ def write_capture(pre, lines, pairs, pres):
 
 
 def test_cli_replay_usage_errors(tmp_path):
-    cli = parity.build_cli()
+    parity.build_cli()
     f = str(tmp_path / "some.iq")
     pre = str(tmp_path / "cap")
     write_capture(pre, ["0 0 100 10 500 0", "0 0 400 20 500 0"], 30, 2)
 
-    def run(args):
-        return subprocess.run([cli] + args, capture_output=True, text=True, timeout=120)
-
     for extra in (["-L", f], ["-x"], ["-r", "2048000"], ["-F", "s16"], ["-f", "868300"], ["-c", "868250"], ["-s", "50"], ["-A"],
                   ["-P", "64"], ["-z"], ["-S", str(tmp_path / "other")], ["-X", f], ["-p", "t=500"]):
-        out = run(["-R", pre] + extra)
+        out = parity.run_cli(["-R", pre] + extra)
         assert out.returncode == 2 and "-R replays" in out.stderr and out.stdout == "", extra
-    out = run(["-R", ""])
+    out = parity.run_cli(["-R", ""])
     assert out.returncode == 2 and "bad -R" in out.stderr
-    assert run(["-R"]).returncode == 1  # (getopt's: the argument is missing)
+    assert parity.run_cli(["-R"]).returncode == 1  # (getopt's: the argument is missing)
     assert not os.path.exists(str(tmp_path / "other") + ".idx")
 
 

@@ -15,7 +15,7 @@ import pytest
 import parity
 from recorder_rows import rec_line
 from tfrec_amd import api, capture, envelope, levels
-from test_levels_cpu import crafted_dec
+from meter_rows import crafted_dec
 
 B = levels.BLOCK_DEC
 GOLDEN = ("tfa_1", "tfa_2", "tfa_3", "tx22", "whb")
@@ -396,24 +396,21 @@ def test_the_struct_and_the_exports(tmp_path):
 
 
 def test_cli_envelope_usage_errors(tmp_path):
-    cli = parity.build_cli()
+    parity.build_cli()
     f = str(tmp_path / "missing.iq")
 
-    def run(args):
-        return subprocess.run([cli] + args, capture_output=True, text=True, timeout=120)
-
-    out = run(["-Q", "-X", f])
+    out = parity.run_cli(["-Q", "-X", f])
     assert out.returncode == 1 and "-Q measures" in out.stderr
-    out = run(["-M", "-Q", "-X", f])  # -M's own refusal comes first and is what it was
+    out = parity.run_cli(["-M", "-Q", "-X", f])  # -M's own refusal comes first and is what it was
     assert out.returncode == 1 and "-M measures" in out.stderr
-    out = run(["-h"])
+    out = parity.run_cli(["-h"])
     assert "-Q " in out.stderr and "[-Q]" in out.stderr
     for args in (["-Q", "-k", str(tmp_path / "keep"), "-L", f], ["-Q", "-K", str(tmp_path / "keep"), "-L", f]):
-        out = run(args)
+        out = parity.run_cli(args)
         assert out.returncode == 2 and "not with -Q" in out.stderr, args
     for args in (["-Q", "-L", f], ["-Q", "-M", "-L", f], ["-Q", "-s", "50", "-L", f],
                  ["-Q", "-S", str(tmp_path / "cap"), "-n", "1", "-L", f]):
-        out = run(args)  # accepted: the file is looked for
+        out = parity.run_cli(args)  # accepted: the file is looked for
         assert out.returncode == 2 and "missing.iq" in out.stderr, args
-    out = run(["-Q", "-R", str(tmp_path / "nothing")])  # accepted with -R: the capture is looked for
+    out = parity.run_cli(["-Q", "-R", str(tmp_path / "nothing")])  # accepted with -R: the capture is looked for
     assert out.returncode == 2 and "-R replays" not in out.stderr

@@ -3,72 +3,12 @@ the definition's table at every boundary, the encoders, the argument errors the 
 opened, tfrec_gpu's block-size arithmetic, and the scenes the GPU tests decode.
 
 Everything is bit-exact; nothing here has a tolerance."""
-import functools
-import subprocess
-
 import numpy as np
 import pytest
 
 import parity
-from oracle import oracle as O
-from tfrec_amd import api, formats, resample, synth
-from test_resample_cpu import SCENE_BLOCKS, SCENE_STREAMS, THRESH, TYPES, rate_scene
-
-# ---- the scenes of the GPU tests (test_formats_gpu.py imports them).  `kind` names a format and how the scene fills it:
-#   s8    the u8 scene's bytes ^ 0x80: the same x
-#   s16   ((u8 - 128) << 8) + e, e in [-128, 127]: full-scale int16 whose content below u8's resolution reaches x
-#   s16d  (x << 2) + d, d in [-2, 1]: the bits >> 2 drops -- a negative d moves x down by one, the shift floors
-#   f32   the s16 scene's values / 32768: v = s16 / 4 lands on quarters, so rint rounds where >> 2 floors, ties included
-KINDS = {"s8": "s8", "s16": "s16", "s16d": "s16", "f32": "f32"}
-SCENE_RATES = [(4, 3), (25, 16), (1, 1)]
-
-
-@functools.lru_cache(maxsize=None)
-def scene_u8(p, q):
-    """[streams, bytes]: test_resample_cpu's scene of the rate, or -- 1/1 -- the generator's streams of the same seeds."""
-    if (p, q) != (1, 1):
-        return rate_scene(p, q)
-    return np.stack([synth.gen_stream(seed, s, SCENE_BLOCKS, 0x1F, 256, rate_mult=1) for seed, s in SCENE_STREAMS])
-
-
-@functools.lru_cache(maxsize=None)
-def scene(kind, p, q):
-    """[streams, bytes] (uint8, read-only): the scene of one rate as rows of the kind's format."""
-    u = scene_u8(p, q)
-    rng = np.random.default_rng(100 * p + q)
-    if kind == "s8":
-        rows = u ^ 0x80
-    elif kind == "s16d":
-        x = (u.astype(np.int32) - 128) << 6
-        rows = np.clip((x << 2) + rng.integers(-2, 2, u.shape), -32768, 32767).astype("<i2").view(np.uint8)
-    else:
-        v = np.clip(((u.astype(np.int32) - 128) << 8) + rng.integers(-128, 128, u.shape), -32768, 32767)
-        rows = v.astype("<i2").view(np.uint8) if kind == "s16" else (v.astype(np.float32) / np.float32(32768.0)).astype("<f4").view(np.uint8)
-    rows = np.ascontiguousarray(rows)
-    assert rows.shape == (len(u), u.shape[1] * formats.bytes_per_sample(KINDS[kind]) // 2)
-    rows.setflags(write=False)
-    return rows
-
-
-def stage0_of(fmt, row, p, q):
-    """The restatement's stage 0 of one stream's row: x, resampled unless the rate is 1/1."""
-    x = formats.to_x(fmt, row)
-    return x if (p, q) == (1, 1) else resample.resample_x16(x, p, q)
-
-
-@functools.lru_cache(maxsize=None)
-def scene_stage0(kind, p, q, s):
-    y = stage0_of(KINDS[kind], scene(kind, p, q)[s], p, q)
-    y.setflags(write=False)
-    return y
-
-
-@functools.lru_cache(maxsize=None)
-def scene_oracle(kind, p, q, s, log_bits=False):
-    """The oracle fed the restatement's stage 0 of stream s of a scene (computed once per session)."""
-    o = O.Oracle(TYPES, THRESH, 0, log_bits=log_bits)
-    o.process_s16(scene_stage0(kind, p, q, s))
-    return o
+from input_rows import KINDS, SCENE_STREAMS, THRESH, TYPES, scene, scene_oracle, scene_u8
+from tfrec_amd import api, formats
 
 
 def f32_bytes(values):
@@ -205,24 +145,20 @@ def cli():
     return parity.build_cli()
 
 
-def run_cli(cli, args):
-    return subprocess.run([cli] + args, capture_output=True, text=True, timeout=120)
-
-
 def test_cli_format_argument_errors(cli, tmp_path):
     missing = str(tmp_path / "missing.iq")
     for bad in ("s24", "", "S16", "u16", "f64"):
-        out = run_cli(cli, ["-F", bad, "-L", missing])
+        out = parity.run_cli(["-F", bad, "-L", missing])
         assert out.returncode == 1 and "bad -F" in out.stderr, bad
     for fmt in ("s16", "cs8", "f32"):
-        out = run_cli(cli, ["-F", fmt, "-x", "-L", missing])
+        out = parity.run_cli(["-F", fmt, "-x", "-L", missing])
         assert out.returncode == 1 and "exclude" in out.stderr, fmt
-    out = run_cli(cli, ["-F", "u8", "-x", "-L", missing])  # u8 is no format of its own: the file is looked for
+    out = parity.run_cli(["-F", "u8", "-x", "-L", missing])  # u8 is no format of its own: the file is looked for
     assert out.returncode == 2 and "missing.iq" in out.stderr
     for fmt in ("u8", "cu8", "s8", "cs8", "s16", "cs16", "f32", "cf32"):
-        out = run_cli(cli, ["-F", fmt, "-r", "2048000", "-b", "4", "-L", missing])
+        out = parity.run_cli(["-F", fmt, "-r", "2048000", "-b", "4", "-L", missing])
         assert out.returncode == 2 and "missing.iq" in out.stderr and "rounded up to 6" in out.stderr, fmt
-    out = run_cli(cli, ["-F", "s16", "-r", "1000000", "-L", missing])
+    out = parity.run_cli(["-F", "s16", "-r", "1000000", "-L", missing])
     assert out.returncode == 1 and "does not take" in out.stderr
 
 
@@ -240,6 +176,6 @@ def test_cli_block_size_arithmetic(cli, tmp_path, args, piece, unit):
     f = tmp_path / "two_and_a_bit.iq"
     with open(f, "wb") as fd:
         fd.truncate(2 * piece + piece // 2)
-    out = run_cli(cli, args + ["-D", "-b", str(unit), "-L", str(f)])
+    out = parity.run_cli(args + ["-D", "-b", str(unit), "-L", str(f)])
     assert "%s: %d blocks, %d bytes per %d\n" % (f, 2 * unit, piece, unit) in out.stderr, out.stderr
     assert out.returncode in (0, 2)

@@ -1,8 +1,8 @@
 """Sample formats on the GPU (tfrec_amd_create_format, tfrec_gpu -F), bit for bit.
 
 Stage 0 is pinned by the restatement (formats.to_x ahead of resample.resample_x16 and tune.mix_in_s16), everything behind it by
-the oracle's process_s16 fed that restatement's output.  The scenes are test_formats_cpu.py's, which asserts that the oracle
-decodes at least 8 telegrams from each; every restatement and oracle of a scene is computed once per session there."""
+the oracle's process_s16 fed that restatement's output.  The scenes are input_rows.py's, where every restatement and oracle of a
+scene is computed once per session; test_formats_cpu.py asserts that the oracle decodes at least 8 telegrams from each."""
 import functools
 import subprocess
 
@@ -11,10 +11,9 @@ import pytest
 
 import parity
 import segments
+from input_rows import KINDS, SCENE_BLOCKS, THRESH, TYPES, format_stage0, scene, scene_oracle, scene_stage0, scene_u8
 from oracle import oracle as O
 from tfrec_amd import api, formats, resample, tune
-from test_formats_cpu import KINDS, scene, scene_oracle, scene_stage0, scene_u8, stage0_of
-from test_resample_cpu import SCENE_BLOCKS, THRESH, TYPES
 
 pytestmark = pytest.mark.gpu
 
@@ -45,7 +44,7 @@ def test_stage0_of_the_large_rates(fmt, p, q):
     sizes = (1, 1)
     rows = parity.full_scale_row(fmt, resample.input_samples(2, p, q), 29)
     _, y0 = run_input(rows, sizes, p, q, fmt, all_flushes=True, max_events=1 << 16)
-    parity.assert_stage0(y0, sizes, stage0_of(fmt, rows[0], p, q), 0, fmt)
+    parity.assert_stage0(y0, sizes, format_stage0(fmt, rows[0], p, q), 0, fmt)
 
 
 EDGES = [np.nan, np.inf, -np.inf, 2.0, -2.0, 1.0, -1.0, 0.99993896, -0.99993896, 0.5 / 8192, 1.5 / 8192, 2.5 / 8192, -0.5 / 8192,
@@ -67,7 +66,7 @@ def test_f32_edge_values(p, q, nb):
     x = formats.to_x("f32", rows[0])
     assert np.isnan(v).any() and x.min() == -8192 and x.max() == 8191
     _, y0 = run_input(rows, (nb,), p, q, "f32", all_flushes=True, max_events=1 << 16)
-    parity.assert_stage0(y0, (nb,), stage0_of("f32", rows[0], p, q), 0)
+    parity.assert_stage0(y0, (nb,), format_stage0("f32", rows[0], p, q), 0)
 
 
 # ---- events equal the oracle behind the restatement
@@ -135,7 +134,7 @@ def test_reset_in_mid_stream_equals_a_fresh_receiver():
     rows = scene(kind, p, q)
     evs, y0 = run_input(rows, FOUR, p, q, "s16", all_flushes=True, before=lambda r, k: r.reset_streams([1]) if k == 2 else None)
     cut = 4 * resample.input_samples(6, p, q)
-    after = stage0_of("s16", rows[1][cut:], p, q)  # zero history behind the cut
+    after = format_stage0("s16", rows[1][cut:], p, q)  # zero history behind the cut
     whole = scene_stage0(kind, p, q, 1)
     parity.assert_segment(np.concatenate(evs), 0, scene_oracle(kind, p, q, 0), "stream 0")
     o1, o2 = O.Oracle(TYPES, THRESH, 0), O.Oracle(TYPES, THRESH, 0)
@@ -204,7 +203,7 @@ def test_tunes_and_a_shared_row(shared):
         orc = parity.tuned_oracle(p, q, TUNES, "s16", 0, hz, types=TYPES, thresh=THRESH)
         assert parity.assert_segment(ev, s, orc, "stream %d tune %d" % (s, hz)) > 0
         assert parity.decoded(orc) == [s]  # each receiver decodes the burst it is tuned to
-        parity.assert_stage0(y0, sizes, stage0_of("s16", row[0], p, q), s)  # stage 0 is ahead of the tune
+        parity.assert_stage0(y0, sizes, format_stage0("s16", row[0], p, q), s)  # stage 0 is ahead of the tune
 
 
 def test_input_tune_beside_an_untuned_stream():
@@ -335,7 +334,7 @@ def test_cli_replays_s16_and_f32_dumps(tmp_path):
                                  capture_output=True, text=True, timeout=600)
             assert out.returncode == 0 and "rounded up to 6" in out.stderr, out.stderr
             o = O.Oracle(TYPES, THRESH, 0)
-            o.process_s16(stage0_of(fmt, rows[s], p, q))
+            o.process_s16(format_stage0(fmt, rows[s], p, q))
             want = [ln for ln in o.text().splitlines() if ln.strip() and not ln.startswith("Inverted") and not ln.startswith("WHB:")]
             got = [ln for ln in out.stdout.splitlines() if ln.strip() and not ln.startswith("WHB:")]
             assert got == want and len(want) >= 4, (fmt, s)

@@ -5,49 +5,13 @@ the presence of the interface, tfrec_gpu's argument handling, and the scenes the
 Everything is bit-exact; nothing here has a tolerance."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import parity
-from oracle import oracle as O
-from tfrec_amd import api, resample, synth, tune
-
-TYPES, THRESH = 0x2F, 500
-
-# ---- the scenes of the GPU tests (test_input_tune_gpu.py imports them): one recording per rate with a burst of its own protocol
-# at every frequency of WIDE_SCENES -- at the centre, inside +-768 kHz and beyond it.  Chosen on the CPU so that the oracle
-# decodes each burst for exactly the receiver tuned to it, and so that a burst beyond +-768 kHz stays out of reach of the
-# tune behind the resampler (asserted below).
-WIDE_SCENES = {(25, 16): (0, 300000, 1100000, -1050000),  # 2.4 MS/s: +-1.2 MHz
-               (25, 12): (0, -400000, 1300000)}           # 3.2 MS/s: +-1.6 MHz
-WIDE_BLOCKS = 6
-
-
-def wide_row(p, q, n_blocks=WIDE_BLOCKS, seed=77):
-    """[1, bytes]: u8 IQ at 1536000 p / q with burst j (protocol j) at WIDE_SCENES[p, q][j] Hz from the centre."""
-    freqs = WIDE_SCENES[p, q]
-    n = n_blocks * api.BLOCK_BYTES // 2 * p
-    bursts = [dict(proto=j, start=(40000 * p + j * (n - 100000 * p) // len(freqs)) // q * q, payload_seed=21 + j, f0_hz=f, amp=50)
-              for j, f in enumerate(freqs)]
-    x = synth.gen_scene(seed, n_blocks, bursts, rate_mult=p).reshape(-1, 2)[::q]
-    x = np.ascontiguousarray(x).reshape(1, -1)
-    assert x.shape[1] == 2 * resample.input_samples(n_blocks, p, q)
-    return x
-
-
-def stage0_of(x, p, q, input_hz):
-    """The restatement's stage 0 of one stream's input with an input-rate tune."""
-    return resample.resample_x16(tune.mix_in_s16(tune.s16_of_u8(x), input_hz, p, q), p, q)
-
-
-def input_oracle(x, p, q, input_hz, narrow_hz=0, log_bits=False):
-    """The oracle fed the restatement: the input-rate mixer, the resampling stage, then the tune behind it."""
-    o = O.Oracle(TYPES, THRESH, 0, log_bits=log_bits)
-    o.process_s16(tune.mix_s16(stage0_of(x, p, q, input_hz), narrow_hz, 0))
-    return o
-
+from input_rows import WIDE_SCENES, input_oracle, wide_row
+from tfrec_amd import api, resample, tune
 
 # ---- inc_in
 CORNERS = (0, 1, -1, 1000, -1000, 250000, -250000, 767999, -767999)
@@ -163,26 +127,22 @@ def cli():
     return parity.build_cli()
 
 
-def run_cli(cli, args):
-    return subprocess.run([cli] + args, capture_output=True, text=True, timeout=120)
-
-
 def test_cli_accepts_tunes_up_to_half_the_rate(cli, tmp_path):
     missing = str(tmp_path / "missing.iq")
     # beyond 767 kHz, below half the rate: accepted, the run ends at the missing file
     for rate, khz in (("2400000", 900), ("2400000", -1199), ("2048000", 1023), ("3200000", -1599), ("2400000", 767)):
-        out = run_cli(cli, ["-r", rate, "-c", "868250", "-f", str(868250 + khz), "-L", missing])
+        out = parity.run_cli(["-r", rate, "-c", "868250", "-f", str(868250 + khz), "-L", missing])
         assert out.returncode == 2 and "missing.iq" in out.stderr, (rate, khz, out.stderr)
-        out = run_cli(cli, ["-r", rate, "-c", "868250", "-p", "f=%d" % (868250 + khz), "-L", missing])
+        out = parity.run_cli(["-r", rate, "-c", "868250", "-p", "f=%d" % (868250 + khz), "-L", missing])
         assert out.returncode == 2 and "missing.iq" in out.stderr, (rate, khz, out.stderr)
     # at half the rate and beyond: refused, and the text names the rate
     for rate, khz in (("2400000", 1200), ("2400000", -1200), ("2048000", 1024), ("3200000", 1600), ("2400000", 5000)):
-        out = run_cli(cli, ["-r", rate, "-c", "868250", "-p", "f=%d" % (868250 + khz), "-L", missing])
+        out = parity.run_cli(["-r", rate, "-c", "868250", "-p", "f=%d" % (868250 + khz), "-L", missing])
         assert out.returncode == 1 and rate in out.stderr and "missing.iq" not in out.stderr, (rate, khz, out.stderr)
     # without -r the limit is what it was
-    out = run_cli(cli, ["-c", "868250", "-f", "869150", "-L", missing])
+    out = parity.run_cli(["-c", "868250", "-f", "869150", "-L", missing])
     assert out.returncode == 1 and "767 kHz" in out.stderr
-    out = run_cli(cli, ["-r", "2400000", "-x", "-f", "869150", "-L", missing])
+    out = parity.run_cli(["-r", "2400000", "-x", "-f", "869150", "-L", missing])
     assert out.returncode == 1 and "exclude" in out.stderr
 
 

@@ -1,23 +1,21 @@
 """The input-rate tune on the GPU (tfrec_amd_tune_streams_input, tfrec_gpu -r with -f), bit for bit.
 
 Stage 0 is pinned by the restatement (tune.mix_in_s16, resample.resample_x16), everything behind it by the oracle's process_s16 fed
-that restatement's output.  The scenes are the recordings of test_input_tune_cpu.py at 2.4 MS/s (25/16) and 3.2 MS/s (25/12),
-which asserts that the oracle decodes each burst for exactly the receiver tuned to it."""
+that restatement's output.  The scenes are input_rows.py's recordings at 2.4 MS/s (25/16) and 3.2 MS/s (25/12); test_input_tune_cpu.py
+asserts that the oracle decodes each burst for exactly the receiver tuned to it."""
 import functools
 
 import numpy as np
 import pytest
 
 import parity
+from input_rows import THRESH, TYPES, WIDE_BURSTS, WIDE_ROW_BLOCKS, WIDE_SCENES, input_oracle, oracle_of, tuned_stage0, wide_row, wide_scene
 from tfrec_amd import api, resample
-from test_channels_cpu import WIDE_BURSTS, wide_scene
-from test_input_tune_cpu import THRESH, TYPES, WIDE_BLOCKS, WIDE_SCENES, input_oracle, stage0_of, wide_row
-from test_resample_cpu import oracle_of
 
 pytestmark = pytest.mark.gpu
 
 run_input = functools.partial(parity.run_input, types=TYPES, thresh=THRESH)
-SIZES = {(25, 16): (1, 2, 2, 1), (25, 12): (3, 3)}  # the scenes' WIDE_BLOCKS blocks cut into submits
+SIZES = {(25, 16): (1, 2, 2, 1), (25, 12): (3, 3)}  # the scenes' WIDE_ROW_BLOCKS blocks cut into submits
 
 
 def receivers(p, q):
@@ -48,7 +46,7 @@ def test_stage0_equals_the_restatement(p, q, sizes):
 
     _, y0 = run_input(iq, sizes, p, q, before=before, all_flushes=True, max_events=1 << 16)
     for s in range(3):
-        want = stage0_of(iq[s], p, q, hz[s])
+        want = tuned_stage0(iq[s], p, q, hz[s])
         if hz[s] == 0:
             assert np.array_equal(want, resample.resample_s16(iq[s], p, q))
         parity.assert_stage0(y0, sizes, want, s)
@@ -73,7 +71,7 @@ def test_an_untuned_stream_keeps_its_history_while_the_kernels_change_around_it(
     _, y0 = run_input(iq, sizes, p, q, before=before, all_flushes=True, max_events=1 << 16)
     assert np.array_equal(np.concatenate([y[1] for y in y0]), resample.resample_s16(iq[1], p, q))
     c1 = 2 * resample.input_samples(1, p, q)
-    assert np.array_equal(y0[1][0], stage0_of(iq[0][c1:], p, q, hz)[:len(y0[1][0])])  # (the tuned kernel did run in between)
+    assert np.array_equal(y0[1][0], tuned_stage0(iq[0][c1:], p, q, hz)[:len(y0[1][0])])  # (the tuned kernel did run in between)
 
 
 @pytest.mark.parametrize("p,q", sorted(WIDE_SCENES))
@@ -99,7 +97,7 @@ def test_events_equal_the_oracle_behind_the_restatement(mode, p, q, monkeypatch)
 def test_results_do_not_depend_on_the_cut(p, q):
     row = wide_row(p, q)
     freqs, before = receivers(p, q)
-    one, _ = run_input(row, (WIDE_BLOCKS,), p, q, n_streams=len(freqs), before=before, all_flushes=True)
+    one, _ = run_input(row, (WIDE_ROW_BLOCKS,), p, q, n_streams=len(freqs), before=before, all_flushes=True)
     cut, _ = run_input(row, SIZES[p, q], p, q, n_streams=len(freqs), before=before, all_flushes=True)
     a, b = parity.sort_events(np.concatenate(one)), parity.sort_events(np.concatenate(cut))
     assert len(a) >= len(freqs) and a.tobytes() == b.tobytes()
@@ -130,9 +128,9 @@ def test_a_tune_and_a_reset_in_mid_stream_equal_fresh_receivers():
     n += parity.assert_segment(np.concatenate(evs[2:]), 1, input_oracle(x[c2:], p, q, f1), "stream 1 after the reset")
     assert n > 0
     assert np.array_equal(y0[0][0], resample.resample_s16(x, p, q)[:len(y0[0][0])])
-    assert np.array_equal(y0[1][0], stage0_of(x[c1:], p, q, f0)[:len(y0[1][0])])  # zero history and phase 0 behind the cut
-    assert np.array_equal(y0[2][1], stage0_of(x[c2:], p, q, f1)[:len(y0[2][1])])
-    assert np.array_equal(y0[1][1], stage0_of(x, p, q, f1)[len(y0[0][1]):][:len(y0[1][1])])  # stream 1 carried on there
+    assert np.array_equal(y0[1][0], tuned_stage0(x[c1:], p, q, f0)[:len(y0[1][0])])  # zero history and phase 0 behind the cut
+    assert np.array_equal(y0[2][1], tuned_stage0(x[c2:], p, q, f1)[:len(y0[2][1])])
+    assert np.array_equal(y0[1][1], tuned_stage0(x, p, q, f1)[len(y0[0][1]):][:len(y0[1][1])])  # stream 1 carried on there
 
 
 @pytest.mark.parametrize("p,q", sorted(WIDE_SCENES))
@@ -188,7 +186,7 @@ def test_the_tune_behind_the_resampler_composes():
         orc = input_oracle(row[0], p, q, a, b)
         parity.assert_segment(ev, s, orc, "stream %d" % s)
         assert parity.decoded(orc) == [want[s]]
-        assert np.array_equal(y0[0][s], stage0_of(row[0], p, q, a)[:len(y0[0][s])])  # stage 0 is ahead of that tune
+        assert np.array_equal(y0[0][s], tuned_stage0(row[0], p, q, a)[:len(y0[0][s])])  # stage 0 is ahead of that tune
 
 
 def test_on_a_10x_context_the_call_is_the_wide_tune():
@@ -228,7 +226,7 @@ def test_error_paths_mark_nothing():
     p, q = 25, 16
     x = wide_row(p, q)
     iq = np.repeat(x, 2, axis=0)
-    with api.Receiver(2, TYPES, THRESH, 0, max_blocks=WIDE_BLOCKS, all_flushes=True, input_rate=(p, q)) as r:
+    with api.Receiver(2, TYPES, THRESH, 0, max_blocks=WIDE_ROW_BLOCKS, all_flushes=True, input_rate=(p, q)) as r:
         for streams, hz in (([0, 1], [100, 1200000]), ([0, 1], [100, -1200000]), ([1, 2], [100, 100]), ([-1], [100]),
                             ([0], [2 ** 31 - 1])):
             with pytest.raises(api.TfrecAmdError) as e:

@@ -5,30 +5,17 @@ before it opens a device.
 
 Everything but the FFT of the tone test is an exact integer; nothing here has a tolerance."""
 import ctypes as C
-import functools
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import parity
-from oracle import oracle as O
-from tfrec_amd import api, dcblock, formats, iqbal, resample, synth, tune
+from meter_rows import GHOST_FREQS, IDENT, THRESH, TYPES, ghost_oracles, guard_rows, impair
+from tfrec_amd import api, dcblock, formats, iqbal
 
 L = iqbal.L
-IDENT = (0, 16384)
-TYPES, THRESH = 0x2F, 500
-
-
-def impair(x, gain, deg):
-    """x (interleaved int16) with Q <- gain (Q cos(deg) + I sin(deg)), rounded and clamped to the rails."""
-    v = np.asarray(x, dtype=np.int16).reshape(-1, 2).astype(np.float64)
-    ph = np.deg2rad(deg)
-    out = np.asarray(x, dtype=np.int16).reshape(-1, 2).copy()
-    out[:, 1] = np.clip(np.rint(gain * (v[:, 1] * np.cos(ph) + v[:, 0] * np.sin(ph))), -8192, 8191).astype(np.int16)
-    return out.reshape(-1)
 
 
 def noisy_row(fmt, n, seed, dc=(300, -170), gain=1.1, deg=5.0, rails=True):
@@ -138,16 +125,6 @@ def unguarded(sa, sb, sc):
     return a, dd, (c * 32768 + a) // (2 * a), (a * 32768 + r) // (2 * r)
 
 
-def guard_rows(n_win=4):
-    """name -> interleaved int16 x of n_win windows that trips exactly that guard; `fine` trips none."""
-    rng = np.random.default_rng(4)
-    i = rng.integers(-3000, 3000, n_win * L)
-    q0 = rng.integers(-3000, 3000, n_win * L)
-    rows = {"silence": (0 * i, 0 * i), "correlated": (i, i), "t": (i, i // 2 + rng.integers(-40, 40, n_win * L)), "g": (i, 2 * q0),
-            "fine": (i, q0 + i // 8)}
-    return {k: np.stack(v, axis=1).astype(np.int16).reshape(-1) for k, v in rows.items()}
-
-
 def test_each_guard_is_tripped_by_its_row():
     rows = guard_rows()
     for name, x in rows.items():
@@ -250,48 +227,7 @@ def test_the_image_of_an_impaired_tone_falls(gain, deg):
     assert after < before
 
 
-# ---- the ghost telegrams (the GPU tests import the scene)
-GHOST_RATE = (25, 16)  # 2.4 MS/s
-# burst j: protocol j.  (With burst 1 at -500 kHz the restatement's receiver at +500 kHz does not decode the raw image -- a
-# TFA_2 ghost is there at +500, -600 and +450 kHz and not at -400 or -550 -- so that burst sits at +500 kHz.)
-GHOST_FREQS = (300000, 500000, 700000, -900000)
-GHOST_BLOCKS = 6
-GHOST_K = 2048
-GHOST_IMPAIRMENT = (1.12, 8.0)  # an image at about -21 dBc
-
-
-@functools.lru_cache(maxsize=None)
-def ghost_scene():
-    """(raw, x): the S16 row (read-only bytes) of the 2.4 MS/s scene with a burst of protocol j at GHOST_FREQS[j], its Q rail
-    impaired by GHOST_IMPAIRMENT, and its x."""
-    p, q = GHOST_RATE
-    n = GHOST_BLOCKS * api.BLOCK_BYTES // 2 * p
-    bursts = [dict(proto=j, start=(40000 * p + j * (n - 100000 * p) // len(GHOST_FREQS)) // q * q, payload_seed=21 + j, f0_hz=f, amp=50)
-              for j, f in enumerate(GHOST_FREQS)]
-    u = np.ascontiguousarray(synth.gen_scene(77, GHOST_BLOCKS, bursts, rate_mult=p).reshape(-1, 2)[::q]).reshape(-1)
-    x = impair(tune.s16_of_u8(u), *GHOST_IMPAIRMENT)
-    raw = formats.encode("s16", x)
-    raw.setflags(write=False)
-    x.setflags(write=False)
-    return raw, x
-
-
-def receiver_oracle(x, hz):
-    """The oracle of the receiver with the input-rate tune hz on the input-rate samples x."""
-    p, q = GHOST_RATE
-    o = O.Oracle(TYPES, THRESH, 0)
-    o.process_s16(resample.resample_x16(tune.mix_in_s16(x, hz, p, q), p, q))
-    return o
-
-
-@functools.lru_cache(maxsize=None)
-def ghost_oracles(balanced):
-    """The eight receivers' oracles, in the order +f0, -f0, +f1, ...: on the raw scene, or behind the balancer (K = GHOST_K)."""
-    raw, x = ghost_scene()
-    z = iqbal.iq_balance(raw, "s16", 0, GHOST_K)[0] if balanced else x
-    return [receiver_oracle(z, sgn * f) for f in GHOST_FREQS for sgn in (1, -1)]
-
-
+# ---- the ghost telegrams
 def test_every_image_decodes_as_a_ghost_and_none_behind_the_balancer():
     raw_t = [parity.decoded(o) for o in ghost_oracles(False)]
     bal_t = [parity.decoded(o) for o in ghost_oracles(True)]
@@ -351,25 +287,21 @@ def cli():
     return parity.build_cli()
 
 
-def run_cli(cli, args):
-    return subprocess.run([cli] + args, capture_output=True, text=True, timeout=120)
-
-
 def test_cli_usage_errors(cli, tmp_path):
     f = str(tmp_path / "missing.iq")
     for extra in (["-x"], ["-X", f]):
-        out = run_cli(cli, ["-Z", "-L", f] + extra)
+        out = parity.run_cli(["-Z", "-L", f] + extra)
         assert out.returncode == 1 and "-Z removes the IQ imbalance" in out.stderr, extra
-    out = run_cli(cli, ["-Z", "-R", str(tmp_path / "cap")])
+    out = parity.run_cli(["-Z", "-R", str(tmp_path / "cap")])
     assert out.returncode == 2 and "-Z" in out.stderr
     for bad in ("0", "4097", "64x", "9999999999"):
         for args in (["-Z", bad], ["-Z" + bad]):
-            out = run_cli(cli, args + ["-L", f])
+            out = parity.run_cli(args + ["-L", f])
             assert out.returncode == 1 and "bad -Z" in out.stderr, args
     for args in (["-Z"], ["-Z", "1"], ["-Z4096"], ["-Z", "-z"], ["-z", "64", "-Z", "100"], ["-Z", "-r", "2048000", "-F", "s16"],
                  ["-Z", "64", "-c", "868250", "-f", "868300"], ["-Z", "-p", "t=300"], ["-Z", "-s", "50"], ["-Z", "-S", str(tmp_path / "cap")],
                  ["-Z", "-P", "256"], ["-Z", "-A"], ["-Z", "-n", "1"], ["-D", "-Z", "2048"]):
-        out = run_cli(cli, args + ["-L", f])  # accepted: the file is looked for
+        out = parity.run_cli(args + ["-L", f])  # accepted: the file is looked for
         assert out.returncode == 2 and "missing.iq" in out.stderr, args
-    out = run_cli(cli, ["-h"])
+    out = parity.run_cli(["-h"])
     assert out.returncode == 0 and "-Z [n]" in out.stderr and "-z [n]" in out.stderr

@@ -4,7 +4,7 @@ bit.
 (t, g), d and stage 0 are pinned by the restatement (formats.to_x -> iqbal.iq_balance -> tune.mix_in_s16 / resample.resample_x16),
 everything behind stage 0 by the oracle's process_s16 fed that chain's output.  The scenes are synthetic recordings of 4 units
 (a unit: one block, three at 4/3) with one burst per row, a DC offset of a few u8 LSB and an IQ imbalance on each row; the ghost
-scene is test_iqbal_cpu's."""
+scene is meter_rows.py's."""
 import functools
 import subprocess
 
@@ -12,10 +12,11 @@ import numpy as np
 import pytest
 
 import parity
+from input_rows import stage0_of_x
+from meter_rows import (GHOST_BLOCKS, GHOST_FREQS, GHOST_K, GHOST_RATE, IDENT, ghost_oracles, ghost_scene, guard_rows, impair,
+                        receiver_oracle)
 from oracle import oracle as O
 from tfrec_amd import api, dcblock, formats, iqbal, resample, synth, tune
-from test_iqbal_cpu import (GHOST_BLOCKS, GHOST_FREQS, GHOST_K, GHOST_RATE, IDENT, ghost_oracles, ghost_scene, guard_rows, impair,
-                            receiver_oracle)
 
 pytestmark = pytest.mark.gpu
 
@@ -65,11 +66,6 @@ def balanced(rows, fmt, k_dc, k_iq, sizes, p=1, q=1, reset_before=None):
         assert pos == len(row)
         out.append((np.concatenate(xs), ds, tgs))
     return out
-
-
-def stage0_of_x(x, p, q, input_hz=0):
-    x = tune.mix_in_s16(x, input_hz, p, q) if input_hz else x
-    return x if (p, q) == (1, 1) else resample.resample_x16(x, p, q)
 
 
 def oracle_of(y0, **kw):
@@ -190,7 +186,7 @@ def test_guard_rows_pass_through_unchanged():
 def test_no_mirror_receiver_decodes_behind_the_balancer():
     """Eight receivers on ONE row (max_rows = 1): an input-rate tune to every burst and to every mirror.  Their events are the
     oracle's behind the restatement: every burst is decoded, no mirror receiver decodes -- where the oracle of the raw row decodes
-    every burst twice (test_iqbal_cpu)."""
+    every burst twice (test_iqbal_cpu.py)."""
     p, q = GHOST_RATE
     raw, _ = ghost_scene()
     tunes = [sgn * f for f in GHOST_FREQS for sgn in (1, -1)]

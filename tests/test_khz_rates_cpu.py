@@ -1,10 +1,10 @@
 """The whole-kHz rates of the resampling stage (Q <= 64 or Q | 1536) without a GPU: the library's tap tables against
 the restatement tfrec_amd/resample.py at the new denominators, the figures the kernels' bounds rest on over all 12 960 new rates,
 the rates that stay refused, the block rule unit(Q) = Q / gcd(Q, 64), the input-rate tune's increment where its numerator leaves
-64 bits, tfrec_gpu -r's argument handling, and the rates, rows and scenes of the GPU tests (test_khz_rates_gpu.py imports them).
+64 bits, tfrec_gpu -r's argument handling, and what the rates, rows and scenes of the GPU tests (input_rows.py's KHZ_SWEEP and
+khz_scene) are there for.
 
 Everything is bit-exact; nothing here has a tolerance."""
-import functools
 import math
 from concurrent.futures import ThreadPoolExecutor
 from fractions import Fraction
@@ -13,9 +13,8 @@ import numpy as np
 import pytest
 
 import parity
-from tfrec_amd import api, formats, resample, tune
-from test_input_tune_cpu import stage0_of as tuned_stage0_of
-from test_resample_cpu import oracle_of, rate_stream, run_cli, SCENE_STREAMS
+from input_rows import KHZ_SCENE_RATES, KHZ_SWEEP, KHZ_SWEEP_BY_RATE, khz_scene, khz_sweep_rows, khz_sweep_stage0, khz_sweep_tunes, oracle_of
+from tfrec_amd import api, resample, tune
 
 NEW_Q = (96, 128, 192, 256, 384, 512, 768, 1536)  # the divisors of 1536 above 64
 # 2.0, 2.5, 5, 10, 12.5 and 2.205 MS/s; the smallest rate of Q = 128, 768 and 1536; the largest rate of all
@@ -133,55 +132,30 @@ def cli():
 def test_cli_takes_the_whole_khz_rates(cli, tmp_path):
     missing = str(tmp_path / "missing.iq")
     for hz in ("2000000", "2500000", "10000000", "12500000", "1537000"):
-        out = run_cli(cli, ["-r", hz, "-L", missing])
+        out = parity.run_cli(["-r", hz, "-L", missing])
         assert out.returncode == 2 and "missing.iq" in out.stderr and "does not take" not in out.stderr, (hz, out.stderr)
-    out = run_cli(cli, ["-r", "2500000", "-b", "4", "-L", missing])  # 625/384: multiples of 6
+    out = parity.run_cli(["-r", "2500000", "-b", "4", "-L", missing])  # 625/384: multiples of 6
     assert out.returncode == 2 and "-b 4 rounded up to 6" in out.stderr
-    out = run_cli(cli, ["-r", "1548000", "-b", "1", "-L", missing])  # 129/128: multiples of 2, not of the odd part
+    out = parity.run_cli(["-r", "1548000", "-b", "1", "-L", missing])  # 129/128: multiples of 2, not of the odd part
     assert out.returncode == 2 and "-b 1 rounded up to 2" in out.stderr
-    out = run_cli(cli, ["-r", "1537500", "-L", missing])  # 1025/1024
+    out = parity.run_cli(["-r", "1537500", "-L", missing])  # 1025/1024
     assert out.returncode == 1 and "does not take" in out.stderr
 
 
-# ---- what the GPU tests run (test_khz_rates_gpu.py): (P, Q, streams, submits in blocks, untuned formats, format of the tuned case)
-#   125/96      T 8, unit 3, a small table (768 taps): the staged kernels
-#   625/384     Q T = 3840, the largest table the staged kernels take; unit 6
-#   129/128     unit 2, where the odd part would say 1
-#   3125/384    T 50, 19200 taps (75 KB): the first case whose table cannot sit in LDS; a half-tile rate
-#   735/512     Q 512, T 10: 5120 taps
-#   1537/1536   T 8: every output of a tile another phase
-#   15359/1536  T 60: the largest table (92160 taps) and the largest P; two streams and two formats keep the restatement within seconds
-SWEEP = [
-    (125, 96, 3, (3, 6, 3), ("u8", "s8", "s16", "f32"), "s8"),
-    (625, 384, 3, (6, 12, 6), ("u8", "s8", "s16", "f32"), "s16"),
-    (129, 128, 3, (2, 4, 2), ("u8", "s8", "s16", "f32"), "f32"),
-    (3125, 384, 3, (6, 12, 6), ("u8", "s8", "s16", "f32"), "s8"),
-    (735, 512, 3, (8, 16, 8), ("u8", "s8", "s16", "f32"), "s16"),
-    (1537, 1536, 3, (24, 24), ("u8", "s8", "s16", "f32"), "f32"),
-    (15359, 1536, 2, (24, 24), ("u8", "s16"), "s16"),
-]
-SWEEP_IDS = ["%d/%d" % r[:2] for r in SWEEP]
-SWEEP_BY_RATE = {r[:2]: r for r in SWEEP}
+# ---- what the GPU tests run (test_khz_rates_gpu.py)
 STAGED_MAX = 3840  # csrc/tfrec_dev.h: kRsTableMax
 
 
-def sweep_tunes(p, q, fmt):
-    """Per stream; at the two rates whose tunes overflow a 64-bit numerator, those tunes."""
-    if (p, q) == (15359, 1536):
-        return (7000001, 0) if fmt == "u8" else (0, -699051)
-    return (6249999 if (p, q) == (3125, 384) else 1234, 0, -123457)
-
-
 def test_sweep_rates_are_what_they_are_there_for():
-    for p, q, n, sizes, fmts, tuned_fmt in SWEEP:
+    for p, q, n, sizes, fmts, tuned_fmt in KHZ_SWEEP:
         unit = resample.permitted_blocks(q)
         assert sizes == ((unit, 2 * unit, unit) if q != 1536 else (24, 24)) and all(nb % unit == 0 for nb in sizes)
         assert tuned_fmt in fmts and fmts[0] == "u8" and n == (2 if p == 15359 else 3)
         for fmt in ("u8", tuned_fmt):
-            for hz in sweep_tunes(p, q, fmt):
+            for hz in khz_sweep_tunes(p, q, fmt):
                 tune.inc_in(hz, p, q)  # (inside half the input rate)
-    t = {r[:2]: resample.n_taps(*r[:2]) for r in SWEEP}
-    assert [t[r[:2]] for r in SWEEP] == [8, 10, 8, 50, 10, 8, 60]
+    t = {r[:2]: resample.n_taps(*r[:2]) for r in KHZ_SWEEP}
+    assert [t[r[:2]] for r in KHZ_SWEEP] == [8, 10, 8, 50, 10, 8, 60]
     table = {r: r[1] * t[r] for r in t}
     assert table[125, 96] == 768 and table[625, 384] == STAGED_MAX == 64 * 60 and table[129, 128] == 1024
     assert table[3125, 384] == 19200 and table[735, 512] == 5120 and table[1537, 1536] == 12288 and table[15359, 1536] == 92160
@@ -192,70 +166,21 @@ def test_sweep_rates_are_what_they_are_there_for():
     assert 6249999 * 2 ** 33 * 384 >= 2 ** 63
 
 
-@functools.lru_cache(maxsize=None)
-def sweep_rows(fmt, p, q):
-    """[streams, bytes] (uint8, read-only): different full-scale random data per stream."""
-    _, _, n_streams, sizes, _, _ = SWEEP_BY_RATE[p, q]
-    n = resample.input_samples(sum(sizes), p, q)
-    if fmt == "u8":
-        rows = np.random.default_rng(1000 * p + q).integers(0, 256, (n_streams, 2 * n), dtype=np.uint8)
-    else:
-        rows = np.concatenate([parity.full_scale_row(fmt, n, 1000 * p + q + 7 * s + 1) for s in range(n_streams)])
-    assert rows.shape == (n_streams, n * formats.bytes_per_sample(fmt)) and not np.array_equal(rows[0], rows[1])
-    rows.setflags(write=False)
-    return rows
-
-
-@functools.lru_cache(maxsize=None)
-def sweep_stage0(fmt, p, q, tuned):
-    """The restatement's stage 0 of every stream of sweep_rows over the whole run (read-only)."""
-    rows = sweep_rows(fmt, p, q)
-    hz = sweep_tunes(p, q, fmt) if tuned else (0,) * len(rows)
-
-    def one(s):
-        if fmt == "u8":
-            y = tuned_stage0_of(rows[s], p, q, hz[s]) if tuned else resample.resample_s16(rows[s], p, q)
-        else:
-            x = formats.to_x(fmt, rows[s])
-            y = resample.resample_x16(tune.mix_in_s16(x, hz[s], p, q) if hz[s] else x, p, q)
-        assert len(y) == 2 * sum(SWEEP_BY_RATE[p, q][3]) * 32768
-        y.setflags(write=False)
-        return y
-
-    with ThreadPoolExecutor(len(rows)) as ex:  # (numpy releases the GIL in the gathers and sums)
-        return tuple(ex.map(one, range(len(rows))))
-
-
 @pytest.mark.parametrize("p,q", [(129, 128), (3125, 384)])
 def test_cutting_at_the_unit_reproduces_the_stream(p, q):
     """What the GPU sweep expects is consistent in itself: the u8 row cut into its submits, each from the T - 1 raw samples before
     it, is the uncut stream."""
     t = resample.n_taps(p, q)
-    u8 = sweep_rows("u8", p, q)[0]
+    u8 = khz_sweep_rows("u8", p, q)[0]
     parts, pos = [], 0
-    for nb in SWEEP_BY_RATE[p, q][3]:
+    for nb in KHZ_SWEEP_BY_RATE[p, q][3]:
         n = 2 * resample.input_samples(nb, p, q)
         parts.append(resample.resample_s16(u8[pos:pos + n], p, q, hist=u8[pos - 2 * (t - 1):pos] if pos else None))
         pos += n
-    assert pos == len(u8) and np.array_equal(np.concatenate(parts), sweep_stage0("u8", p, q, False)[0])
+    assert pos == len(u8) and np.array_equal(np.concatenate(parts), khz_sweep_stage0("u8", p, q, False)[0])
 
 
-# ---- the scenes of the end-to-end tests: the generator's streams at rate_mult = P with every Q-th complex sample kept
-SCENE_RATES = [(125, 96), (3125, 384)]
-SCENE_BLOCKS = 12
-
-
-@functools.lru_cache(maxsize=None)
-def khz_scene(p, q, n_blocks=SCENE_BLOCKS):
-    """test_resample_cpu.rate_scene (read-only), its streams generated beside each other: at P = 3125 the generator makes 2.4 GB per
-    stream before the decimation by Q."""
-    with ThreadPoolExecutor(len(SCENE_STREAMS)) as ex:
-        iq = np.stack(list(ex.map(lambda a: rate_stream(p, q, a[0], a[1], n_blocks), SCENE_STREAMS)))
-    iq.setflags(write=False)
-    return iq
-
-
-@pytest.mark.parametrize("p,q", SCENE_RATES)
+@pytest.mark.parametrize("p,q", KHZ_SCENE_RATES)
 def test_gpu_scenes_decode_every_protocol(p, q):
     """Non-vacuity of the end-to-end GPU test: the oracle alone, fed the restatement's stage 0 of the scene, yields a status-1
     telegram of every protocol at each rate, and at least one in every stream."""

@@ -4,21 +4,20 @@ denominators whose table still fits (125/96, 625/384, 129/128) and resample_stre
 needs a 128-bit numerator --, across a reset and on a shared row; the decode behind the stage end to end; the DC blocker and the
 refusals under the block rule unit(Q) = Q / gcd(Q, 64).
 
-test_khz_rates_cpu.py holds the rates, rows and scenes and asserts what each is there for.  Every sweep run is full-scale data
+input_rows.py holds the rates, rows and scenes; test_khz_rates_cpu.py asserts what each is there for.  Every sweep run is full-scale data
 over submits of (unit, 2 unit, unit) blocks -- (24, 24) at Q = 1536 -- on a context of the largest: stage 0 is read back after each
 submit and compared per stream and submit with the restatement (tfrec_amd/resample.py, tune.py, formats.py) by np.array_equal."""
 import numpy as np
 import pytest
 
 import parity
+from input_rows import (KHZ_SCENE_RATES, KHZ_SWEEP, KHZ_SWEEP_BY_RATE, KHZ_SWEEP_IDS, THRESH, TYPES, format_stage0, khz_scene, khz_sweep_rows,
+                        khz_sweep_stage0, khz_sweep_tunes, oracle_of, rate_scene)
 from tfrec_amd import api, dcblock, formats, resample, tune
-from test_formats_cpu import stage0_of as fmt_stage0_of
-from test_resample_cpu import THRESH, TYPES, oracle_of, rate_scene
-from test_khz_rates_cpu import SCENE_RATES, SWEEP, SWEEP_BY_RATE, SWEEP_IDS, khz_scene, sweep_rows, sweep_stage0, sweep_tunes
 
 pytestmark = pytest.mark.gpu
 
-RATES = [r[:2] for r in SWEEP]
+RATES = [r[:2] for r in KHZ_SWEEP]
 
 
 def stage0_run(fmt, rows, sizes, p, q, before=None, n_streams=None):
@@ -28,38 +27,38 @@ def stage0_run(fmt, rows, sizes, p, q, before=None, n_streams=None):
 
 
 def sweep(fmt, p, q, tuned):
-    _, _, n, sizes, fmts, _ = SWEEP_BY_RATE[p, q]
+    _, _, n, sizes, fmts, _ = KHZ_SWEEP_BY_RATE[p, q]
     assert fmt in fmts  # (15359/1536 runs u8 and s16 only)
-    hz = sweep_tunes(p, q, fmt)
+    hz = khz_sweep_tunes(p, q, fmt)
 
     def before(r, k):
         if tuned and k == 0:
             r.tune_streams_input(list(range(n)), hz)
             assert [r.stream_tune_input(s) for s in range(n)] == list(hz)
 
-    y0 = stage0_run(fmt, sweep_rows(fmt, p, q), sizes, p, q, before=before)
-    want = sweep_stage0(fmt, p, q, tuned)
+    y0 = stage0_run(fmt, khz_sweep_rows(fmt, p, q), sizes, p, q, before=before)
+    want = khz_sweep_stage0(fmt, p, q, tuned)
     label = "%d/%d %s%s" % (p, q, fmt, " tuned" if tuned else "")
     for s in range(n):
         parity.assert_stage0(y0, sizes, want[s], s, label, 1024)
     if tuned:  # the tunes act: a tuned stream is not the untuned restatement
         s = [i for i in range(n) if hz[i]][0]
-        assert not np.array_equal(want[s], sweep_stage0(fmt, p, q, False)[s])
+        assert not np.array_equal(want[s], khz_sweep_stage0(fmt, p, q, False)[s])
 
 
-@pytest.mark.parametrize("p,q", RATES, ids=SWEEP_IDS)
+@pytest.mark.parametrize("p,q", RATES, ids=KHZ_SWEEP_IDS)
 def test_u8_untuned(p, q):
     """resample_kernel where the table is staged, resample_stream_kernel<U8> where it is not."""
     sweep("u8", p, q, False)
 
 
-@pytest.mark.parametrize("p,q", RATES, ids=SWEEP_IDS)
+@pytest.mark.parametrize("p,q", RATES, ids=KHZ_SWEEP_IDS)
 def test_u8_mixed_tunes_in_one_launch(p, q):
     """Stream 0 tuned, stream 1 untuned, stream 2 tuned negative (15359/1536: +7000001 Hz and an untuned stream)."""
     sweep("u8", p, q, True)
 
 
-FORMAT_CASES = [(fmt, r[0], r[1]) for r in SWEEP for fmt in r[4][1:]]
+FORMAT_CASES = [(fmt, r[0], r[1]) for r in KHZ_SWEEP for fmt in r[4][1:]]
 
 
 @pytest.mark.parametrize("fmt,p,q", FORMAT_CASES, ids=["%s-%d/%d" % c for c in FORMAT_CASES])
@@ -67,10 +66,10 @@ def test_formats_untuned(fmt, p, q):
     sweep(fmt, p, q, False)
 
 
-@pytest.mark.parametrize("p,q", RATES, ids=SWEEP_IDS)
+@pytest.mark.parametrize("p,q", RATES, ids=KHZ_SWEEP_IDS)
 def test_one_format_with_mixed_tunes(p, q):
     """The format cycles down the table (15359/1536: s16 with an untuned stream and -699051 Hz)."""
-    sweep(SWEEP_BY_RATE[p, q][5], p, q, True)
+    sweep(KHZ_SWEEP_BY_RATE[p, q][5], p, q, True)
 
 
 # ---- beside the sweep
@@ -78,15 +77,15 @@ def test_one_format_with_mixed_tunes(p, q):
 def test_reset_before_the_second_submit(fmt, p, q):
     """reset_streams([1]) before the second submit: from there stream 1 is the restatement of the remaining input from zero
     history and phase 0; stream 0 carries on."""
-    sizes = SWEEP_BY_RATE[p, q][3]
-    rows = sweep_rows(fmt, p, q)[:2]
+    sizes = KHZ_SWEEP_BY_RATE[p, q][3]
+    rows = khz_sweep_rows(fmt, p, q)[:2]
     y0 = stage0_run(fmt, rows, sizes, p, q, before=lambda r, k: r.reset_streams([1]) if k == 1 else None)
 
     def restated(row):
-        return resample.resample_s16(row, p, q) if fmt == "u8" else fmt_stage0_of(fmt, row, p, q)
+        return resample.resample_s16(row, p, q) if fmt == "u8" else format_stage0(fmt, row, p, q)
 
     cut = formats.bytes_per_sample(fmt) * resample.input_samples(sizes[0], p, q)
-    whole = sweep_stage0(fmt, p, q, False)
+    whole = khz_sweep_stage0(fmt, p, q, False)
     label = "%d/%d %s" % (p, q, fmt)
     parity.assert_stage0(y0, sizes, whole[0], 0, label + " beside a reset", 1024)
     n0 = 2 * sizes[0] * 4 * api.BLOCK_DEC
@@ -98,8 +97,8 @@ def test_reset_before_the_second_submit(fmt, p, q):
 def test_shared_row_with_three_input_tunes():
     """3125/384, f32: three streams read row 0 with three input tunes, and the submits carry that one row."""
     p, q, fmt = 3125, 384, "f32"
-    sizes, hz = SWEEP_BY_RATE[p, q][3], (6249999, 1234, -123457)
-    row = sweep_rows(fmt, p, q)[:1].copy()
+    sizes, hz = KHZ_SWEEP_BY_RATE[p, q][3], (6249999, 1234, -123457)
+    row = khz_sweep_rows(fmt, p, q)[:1].copy()
 
     def before(r, k):
         if k == 0:
@@ -114,7 +113,7 @@ def test_shared_row_with_three_input_tunes():
         parity.assert_stage0(y0, sizes, want, s, "3125/384 f32 shared row", 512)
 
 
-@pytest.mark.parametrize("p,q", SCENE_RATES)
+@pytest.mark.parametrize("p,q", KHZ_SCENE_RATES)
 def test_events_equal_the_oracle_behind_the_restatement(p, q):
     """End to end at 2.0 and 12.5 MS/s: every stream's events are the oracle's on the restatement's stage 0, every flush
     reported, with a decoded telegram in every stream."""
@@ -132,7 +131,7 @@ def test_dc_blocker_at_2500000():
     (dcblock.dc_block ahead of resample_x16); a submit of 3 blocks -- whole samples, not a multiple of the unit -- is refused
     and queues nothing."""
     p, q, fmt, k, sizes = 625, 384, "s8", 64, (6, 6)
-    rows = sweep_rows(fmt, p, q)[:2, :formats.bytes_per_sample(fmt) * resample.input_samples(12, p, q)]
+    rows = khz_sweep_rows(fmt, p, q)[:2, :formats.bytes_per_sample(fmt) * resample.input_samples(12, p, q)]
     parts = parity.cut_input(rows.copy(), sizes, fmt, p, q)
     with api.Receiver(2, TYPES, THRESH, 0, max_blocks=6, input_format=fmt, input_rate=(p, q), dc_windows=k, all_flushes=True) as r:
         assert r.dc() == (k, 2)

@@ -3,20 +3,17 @@ tfrec_amd/levels.py against a per-sample simulation of the reference's loops and
 of its state, and what tfrec_gpu decides before it opens a device.
 
 Everything is an exact integer; nothing here has a tolerance."""
-import itertools
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import parity
+from meter_rows import SUBSETS, crafted_dec
 from oracle import oracle as O
 from tfrec_amd import api, levels, synth
 
 B = levels.BLOCK_DEC
-TYPE_BITS = (0x01, 0x02, 0x04, 0x08, 0x20)
-SUBSETS = [sum(c) for k in range(1, 6) for c in itertools.combinations(TYPE_BITS, k)]
 
 
 def test_windows_are_the_reference_values():
@@ -27,26 +24,6 @@ def test_windows_are_the_reference_values():
             levels.windows(bad)
     assert levels.LEVEL_DTYPE.itemsize == 32 and api.LEVEL_DTYPE is levels.LEVEL_DTYPE
     assert api.F_LEVELS == 32 and "tfrec_amd_read_levels" in api.EXPORTS
-
-
-def crafted_dec(W, seed, n_blocks=3):
-    """Quiet noise with single loud samples (pwr 6000 > any threshold here): one at the last sample of block 0; pairs whose
-    distances are W - 1, W, W + 1 and W + 2 -- gaps of W - 2 .. W + 1 quiet samples between two triggers, the ones around the
-    point where the first trigger's window ends --; one W / 2 ahead of the boundary between blocks 1 and 2, whose window
-    straddles it, and the one at the end of block 0, whose window lies wholly in block 1; a few at random."""
-    rng = np.random.default_rng(seed)
-    dec = rng.integers(-40, 41, size=(n_blocks * B, 2)).astype(np.int16)
-    loud = [B - 1, 2 * B - W // 2]
-    pos = 200
-    for d in (W - 1, W, W + 1, W + 2):
-        loud += [pos, pos + d]
-        pos += d + W + 100  # the next pair starts in the open again
-    assert pos < B - W
-    loud += [int(v) for v in rng.integers(2 * B + W, n_blocks * B - 1, 3)]
-    loud.append(n_blocks * B - 1)  # ... and one whose window is cut by the end of the input
-    for p in loud:
-        dec[p] = (3000, -3000)
-    return dec, sorted(loud)
 
 
 @pytest.mark.parametrize("types", SUBSETS, ids=["%02x" % t for t in SUBSETS])
@@ -142,28 +119,24 @@ def cli():
     return parity.build_cli()
 
 
-def run_cli(cli, args):
-    return subprocess.run([cli] + args, capture_output=True, text=True, timeout=120)
-
-
 def test_cli_scan_usage_errors(cli, tmp_path):
     f = str(tmp_path / "missing.iq")
     for extra in (["-n", "2"], ["-p", "t=100"], ["-f", "868300"], ["-e", "true"], ["-E", "cat"], ["-X", f], ["-L", f],
                   ["-d", "0,1"]):
-        out = run_cli(cli, ["-s", "50", "-L", f] + extra)
+        out = parity.run_cli(["-s", "50", "-L", f] + extra)
         assert out.returncode == 1 and "-s scans one -L file" in out.stderr, extra
     for bad in ("0", "-5", "x", "", "2.5"):
-        out = run_cli(cli, ["-s", bad, "-L", f])
+        out = parity.run_cli(["-s", bad, "-L", f])
         assert out.returncode == 1 and "bad -s" in out.stderr, bad
     # 1.536 MS/s: 1153 channels at 1 kHz; -x: 14977 at 1 kHz are too many, 4 kHz gives 3745
-    out = run_cli(cli, ["-s", "1", "-x", "-L", f])
+    out = parity.run_cli(["-s", "1", "-x", "-L", f])
     assert out.returncode == 1 and "14977 channels" in out.stderr and "at most 4096" in out.stderr
-    out = run_cli(cli, ["-s", "1", "-r", "9600000", "-L", f])
+    out = parity.run_cli(["-s", "1", "-r", "9600000", "-L", f])
     assert out.returncode == 1 and "at most 4096" in out.stderr
     for args in (["-s", "1"], ["-s", "4", "-x"], ["-s", "50", "-r", "2400000", "-F", "s16"]):
-        out = run_cli(cli, args + ["-L", f])  # accepted: the file is looked for
+        out = parity.run_cli(args + ["-L", f])  # accepted: the file is looked for
         assert out.returncode == 2 and "missing.iq" in out.stderr, args
-    out = run_cli(cli, ["-s", "50"])
+    out = parity.run_cli(["-s", "50"])
     assert out.returncode == 1 and "need -L" in out.stderr
 
 
@@ -179,7 +152,7 @@ def test_cli_scan_channel_list(cli, tmp_path, args, fs_in, place):
     f = tmp_path / "empty.iq"
     f.write_bytes(b"")
     c = 868300
-    out = run_cli(cli, args + ["-s", "50", "-c", str(c), "-L", str(f)])
+    out = parity.run_cli(args + ["-s", "50", "-c", str(c), "-L", str(f)])
     assert out.returncode in (0, 2)
     got = re.findall(r"^scan channel (\d+) kHz: tune (-?\d+) Hz (.*)$", out.stderr, re.M)
     want = levels.scan_channels(c, 50, fs_in)

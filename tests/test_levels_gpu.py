@@ -12,10 +12,11 @@ import numpy as np
 import pytest
 
 import parity
+from input_rows import input_oracle, tuned_stage0
+from meter_rows import scan_file
 from oracle import oracle as O
 from recorder import same_records
 from tfrec_amd import api, levels, resample, synth, tune
-from test_input_tune_cpu import input_oracle, stage0_of
 
 pytestmark = pytest.mark.gpu
 
@@ -275,25 +276,6 @@ def test_without_the_flag_nothing_is_held_and_the_call_is_refused():
     assert flagged["pinned_host_bytes"] == plain["pinned_host_bytes"]
 
 
-def scan_file():
-    """262144 bytes at 2.048 MS/s: the first three blocks of the golden TFA_2 scene, brought from 1.536 MS/s to 4/3 of it (zero
-    stuffing by 4, a windowed-sinc low-pass, every third sample) and moved to +600 kHz."""
-    z = np.load(os.path.join(parity.ROOT, "tests", "golden", "iq_tfa_2.npz"))
-    u = z["iq"][:3 * api.BLOCK_BYTES].astype(np.float64).reshape(-1, 2) - 128.0
-    x = np.zeros(4 * len(u), dtype=np.complex128)
-    x[::4] = u[:, 0] + 1j * u[:, 1]
-    t = np.arange(-64, 65)
-    h = np.sinc(t / 4.0 * 0.8) * np.hamming(len(t))
-    h *= 4.0 / h.sum()
-    y = np.convolve(x, h, mode="same")[::3]
-    y = y * np.exp(2j * np.pi * 600000.0 / 2048000.0 * np.arange(len(y)))
-    out = np.empty((len(y), 2), dtype=np.uint8)
-    out[:, 0] = np.clip(np.rint(y.real) + 128, 0, 255)
-    out[:, 1] = np.clip(np.rint(y.imag) + 128, 0, 255)
-    assert out.size == 2 * resample.input_samples(3, 4, 3) == 262144
-    return out.reshape(-1)
-
-
 def test_cli_scan_finds_the_channel(tmp_path):
     cli = parity.build_cli()
     x = scan_file()
@@ -310,7 +292,7 @@ def test_cli_scan_finds_the_channel(tmp_path):
     field = lambda ln, k: int(dict(p.split("=") for p in ln.split()[2:])[k])  # noqa: E731
     # the restatement of the channel at c + 600: the tune behind the resampler, the oracle's front end, levels.py
     o = O.Oracle(TYPES, 500, 0, keep_dec=True)
-    o.process_s16(tune.mix_s16(stage0_of(x, 4, 3, 0), 600000, 0))
+    o.process_s16(tune.mix_s16(tuned_stage0(x, 4, 3, 0), 600000, 0))
     rec, _ = levels.levels(o.dec(), TYPES, 500)
     telegrams = sum(1 for e in o.events_full() if e[7] == 1 and e[1] < 3 * B)
     assert telegrams >= 1

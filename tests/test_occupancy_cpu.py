@@ -4,14 +4,13 @@ hits into channels, and what tfrec_gpu decides before it opens a device.
 """
 import functools
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import parity
+from meter_rows import scan_file
 from tfrec_amd import api, occupancy, spectrum
-from test_levels_gpu import scan_file
 
 
 def direct(s, p, nf, ratio, rel):
@@ -177,25 +176,21 @@ def cli():
     return parity.build_cli()
 
 
-def run_cli(cli, args):
-    return subprocess.run([cli] + args, capture_output=True, text=True, timeout=120)
-
-
 def test_cli_usage_errors(cli, tmp_path):
     f = str(tmp_path / "missing.iq")
     for extra in (["-s", "50"], ["-n", "2"], ["-p", "t=100"], ["-f", "868300"], ["-e", "true"], ["-E", "true"], ["-X", f], ["-S", "x"],
                   ["-L", f], ["-d", "0,1"]):
-        out = run_cli(cli, ["-A", "-L", f] + extra)
+        out = parity.run_cli(["-A", "-L", f] + extra)
         assert out.returncode == 1 and "-A finds and scans the channels of one -L file" in out.stderr, extra
     for bad in ("1", "4097", "32,0", "32,4097", "32,16,100001", "32,16,5,1", "32,", "32,x", "32;16", "0"):
         for args in (["-A", bad], ["-A" + bad]):
-            out = run_cli(cli, args + ["-L", f])
+            out = parity.run_cli(args + ["-L", f])
             assert out.returncode == 1 and "bad -A" in out.stderr, args
     for args in (["-A"], ["-A", "2"], ["-A4096,4096,0"], ["-A", "32,16,100000", "-x"], ["-A", "-P", "1024", "-r", "2400000", "-F", "s16"],
                  ["-c", "433920", "-A", "64,1"]):
-        out = run_cli(cli, args + ["-L", f])  # accepted: the file is looked for
+        out = parity.run_cli(args + ["-L", f])  # accepted: the file is looked for
         assert out.returncode == 2 and "missing.iq" in out.stderr, args
-    out = run_cli(cli, ["-A"])
+    out = parity.run_cli(["-A"])
     assert out.returncode == 1 and "need -L" in out.stderr
 
 
@@ -204,7 +199,7 @@ def test_cli_a_bad_argument_is_echoed(cli, tmp_path):
     f = str(tmp_path / "missing.iq")
     for bad in ("1", "32,16,5,1", "32,", "4097,2"):
         for args in (["-A", bad], ["-A" + bad]):
-            out = run_cli(cli, args + ["-L", f])
+            out = parity.run_cli(args + ["-L", f])
             assert out.returncode == 1 and out.stderr.startswith("tfrec_gpu: bad -A '%s': want [ratio[,rel[,join_kHz]]]" % bad), (args, out.stderr)
 
 
@@ -219,7 +214,7 @@ def test_cli_bin_list(cli, tmp_path, args, fs_in, n_bins, g, occ):
     channel, no scan -- where a device can be opened at all)."""
     f = tmp_path / "empty.iq"
     f.write_bytes(b"")
-    out = run_cli(cli, args + ["-L", str(f)])
+    out = parity.run_cli(args + ["-L", str(f)])
     assert out.returncode in (0, 2)
     c = int(args[args.index("-c") + 1])
     assert "spec: %d bins, %d frames per record, input rate %d S/s" % (n_bins, g, fs_in) in out.stderr

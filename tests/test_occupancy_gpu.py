@@ -7,9 +7,8 @@ import numpy as np
 import pytest
 
 import parity
+from meter_rows import assert_spectrum, golden, scan_file, tone, u8_rows, want_u8
 from tfrec_amd import api, occupancy, resample, spectrum
-from test_levels_gpu import scan_file
-from test_spectrum_gpu import assert_spectrum, golden, tone, u8_rows, want_u8
 
 pytestmark = pytest.mark.gpu
 

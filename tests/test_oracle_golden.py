@@ -1,7 +1,6 @@
 """CPU tests: the oracle's C restatement against the golden vectors minted from the REAL reference
 (oracle/mint_golden.py, run where /root/reference exists).  Bit-exact, no tolerances."""
 import ctypes as C
-import hashlib
 import json
 import os
 
@@ -9,20 +8,13 @@ import numpy as np
 import pytest
 
 import parity
+from parity import golden_data, sha256_of
 from oracle import oracle as O
 from tfrec_amd import synth
 
 
-def _data(recs):
-    return [(r[0], r[1], int(r[2], 16), float.fromhex(r[3]), float.fromhex(r[4]), r[5], r[6], r[7], r[8]) for r in recs]
-
-
 def _events(evs):
     return [(e[0], e[1], e[2], e[3], e[4], bytes.fromhex(e[5])) for e in evs]
-
-
-def _sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
 def test_readme_known_answer(golden_dir):
@@ -39,7 +31,7 @@ def test_byte_level_known_answers(golden_dir):
         o = O.Oracle(c["types"])
         o.hex(bytes(int(x, 16) for x in c["hex"].split()))
         assert [ln for ln in o.text().splitlines() if ln.strip()] == c["text"], c["hex"]
-        assert o.data() == _data(c["data"]), c["hex"]
+        assert o.data() == golden_data(c["data"]), c["hex"]
         assert o.events() == _events(c["events"]), c["hex"]
         parity.status_pinned_by_text(o.events_full(), "\n".join(c["text"]), c["hex"])
 
@@ -65,12 +57,12 @@ def test_synthetic_streams_against_reference_outputs(golden_dir):
     assert len(cases) >= 6
     for c in cases:
         iq = synth.gen_stream(c["seed"], c["stream"], c["n_blocks"], c["proto_mask"], c["noise_q8"])
-        assert _sha(iq) == c["iq_sha256"], "generator drifted: seed %d stream %d" % (c["seed"], c["stream"])
+        assert sha256_of(iq) == c["iq_sha256"], "generator drifted: seed %d stream %d" % (c["seed"], c["stream"])
         o = O.Oracle(c["types"], c["thresh"], c["wide"], keep_dec=True)
         assert o.process(iq) == c["n_blocks"]
-        assert _sha(o.dec()) == c["dec_sha256"]
+        assert sha256_of(o.dec()) == c["dec_sha256"]
         assert o.events() == _events(c["events"])
-        assert o.data() == _data(c["data"])
+        assert o.data() == golden_data(c["data"])
         assert o.text() == c["text"]
         parity.status_pinned_by_text(o.events_full(), c["text"], "seed %d stream %d" % (c["seed"], c["stream"]))
 
@@ -86,11 +78,11 @@ def test_inverted_polarity_streams_against_reference_outputs(golden_dir):
     cases = json.load(open(os.path.join(golden_dir, "inverted_sync.json")))["cases"]
     for c in cases:
         iq = _inverted_iq(c)
-        assert _sha(iq) == c["iq_sha256"]
+        assert sha256_of(iq) == c["iq_sha256"]
         o = O.Oracle(c["types"], c["thresh"], c["wide"], log_bits=True)
         assert o.process(iq) == c["n_blocks"]
         assert o.events() == _events(c["events"])
-        assert o.data() == _data(c["data"])
+        assert o.data() == golden_data(c["data"])
         assert o.text() == c["text"] and c["text"].count("Inverted SYNC") >= 3
         assert o.bits_text() == c["bits"]
 
@@ -101,14 +93,14 @@ def test_config5_int16_entry_against_reference_outputs(golden_dir):
     assert len(cases) >= 2
     for c in cases:
         iq = synth.gen_stream(c["seed"], c["stream"], c["n_blocks"], c["proto_mask"], c["noise_q8"], rate_mult=10)
-        assert _sha(iq) == c["iq_sha256"], "generator drifted: seed %d stream %d" % (c["seed"], c["stream"])
+        assert sha256_of(iq) == c["iq_sha256"], "generator drifted: seed %d stream %d" % (c["seed"], c["stream"])
         x16 = O.decim10(iq)
-        assert _sha(x16) == c["stage0_sha256"]
+        assert sha256_of(x16) == c["stage0_sha256"]
         o = O.Oracle(c["types"], c["thresh"], c["wide"], keep_dec=True)
         assert o.process_s16(x16) == c["n_blocks"]
-        assert _sha(o.dec()) == c["dec_sha256"]
+        assert sha256_of(o.dec()) == c["dec_sha256"]
         assert o.events() == _events(c["events"])
-        assert o.data() == _data(c["data"])
+        assert o.data() == golden_data(c["data"])
         assert o.text() == c["text"]
         assert len(o.events()) >= 10
 
@@ -121,7 +113,7 @@ def test_raw_iq_fixtures(golden_dir, name):
     o.process(z["iq"])
     assert np.array_equal(o.dec(), z["dec"])
     assert o.events() == _events(meta["events"])
-    assert o.data() == _data(meta["data"])
+    assert o.data() == golden_data(meta["data"])
     assert o.text() == meta["text"] and len(meta["text"]) > 0
 
 

@@ -1,6 +1,8 @@
 """CPU tests of the shared GPU parity harness (tests/parity.py, tests/segments.py): the parts the GPU suite can check only
 indirectly -- the order in which run_fifo submits and drains, the cuts, the default-mode rule, the parse of the oracle's bit
-log, a segment's oracle fed part by part, the stage-0 comparison and the table of modes."""
+log, a segment's oracle fed part by part, the stage-0 comparison, the table of modes, and the rule that no file under tests/
+imports a test module."""
+import glob
 import os
 from types import SimpleNamespace
 
@@ -203,3 +205,15 @@ def test_mode_kwargs_is_the_table_the_modules_spelt_out(mode, monkeypatch):
     assert layout == {"deep": 6, "shallow": 4, "serial_chains": 2, "default_mode": 6, "bits": 6, "host": 6}[mode]
     assert flags == dict(bits=mode == "bits", default_mode=mode == "default_mode", host=mode == "host")
     assert os.environ.get("TFREC_AMD_DEEP") == ("0" if mode == "shallow" else None)
+
+
+def test_no_file_under_tests_imports_a_test_module():
+    """What test modules share lives in plain modules (parity, segments, recorder, recorder_rows, input_rows, meter_rows,
+    stream_count_rows): which tests are collected never decides which test modules are loaded."""
+    assert parity.imports_of("<from>", "from test_levels_cpu import crafted_dec\n") == {"test_levels_cpu"}
+    assert parity.imports_of("<inside>", "import os.path\n\n\ndef f():\n    import test_x as X\n    return X\n") == {"os", "test_x"}
+    paths = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "*.py")))
+    assert len(paths) > 50
+    for p in paths:
+        found = sorted(m for m in parity.imports_of(p) if m.startswith("test_"))
+        assert not found, "%s imports %s" % (os.path.basename(p), found)

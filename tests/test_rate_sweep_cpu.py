@@ -1,77 +1,26 @@
 """The resampling stage across its whole rate range, without a GPU: the library's tap table against the restatement
 tfrec_amd/resample.py at EVERY accepted rate P/Q (gcd 1, Q <= 64, 1 < P/Q < 10: 11 339 rates), the properties the kernels rely
-on at every one of them, and the rates, rows and expectations of the GPU sweep (test_rate_sweep_gpu.py imports them).
+on at every one of them, and what the rates, rows and expectations of the GPU sweep (input_rows.py's RATE_SWEEP) are there for.
 
 Everything is bit-exact; nothing here has a tolerance."""
-import functools
 import math
 
 import numpy as np
 import pytest
 
-import parity
+from input_rows import (LDS_LIMIT, RATE_SWEEP, RATE_SWEEP_FORMAT, RATE_SWEEP_IDS, rate_sweep_rows, rate_sweep_sizes, rate_sweep_stage0,
+                        rate_sweep_tunes, raw_chunks, tile_of, tuned_lds)
 from tfrec_amd import api, formats, resample, tune
-from test_input_tune_cpu import stage0_of as tuned_stage0_of
-
-# ---- the rates of the GPU sweep: (P, Q, T, block unit, tile of the tuned and the format launches, format of case (d)).
-# Each is there for something the kernels care about; test_sweep_rates_are_what_they_are_there_for asserts it.
-#   65/64         the smallest r: T = 8, the largest sum |h| (108112), 64 phases, phi wraps on almost every output
-#   3/2, 127/64   T = 10 and 12; r just under 2
-#   2/1, 4/1, 9/1 Q = 1: one phase, P mod Q = 0; T = 12, 24, 54
-#   19/2          T = 58 with Q = 2
-#   39/4          T = 60 with a small Q: the tile's first read reaches 59 samples into the history; a half-tile rate (49344)
-#   461/64        the last whole-tile rate: the tuned launch's LDS is exactly the 49152-byte limit
-#   267/32, 463/64  the first half-tile rates: 49248 and 49280
-#   639/64        the largest rate: the plain kernel's LDS maximum (35936), T = 60
-#   5/3, 25/12    block unit 3
-#   7/5           block unit 5
-# The format of case (d) cycles s8, s16, f32 down the table, so that each format meets whole-tile and half-tile rates.
-SWEEP_RATES = [
-    (65, 64, 8, 1, 1024, "s8"),
-    (3, 2, 10, 1, 1024, "s16"),
-    (127, 64, 12, 1, 1024, "f32"),
-    (2, 1, 12, 1, 1024, "s8"),
-    (4, 1, 24, 1, 1024, "s16"),
-    (9, 1, 54, 1, 1024, "f32"),
-    (19, 2, 58, 1, 1024, "s8"),
-    (39, 4, 60, 1, 512, "s16"),
-    (461, 64, 44, 1, 1024, "f32"),
-    (267, 32, 52, 1, 512, "s8"),
-    (463, 64, 44, 1, 512, "s16"),
-    (639, 64, 60, 1, 512, "f32"),
-    (5, 3, 10, 3, 1024, "s8"),
-    (25, 12, 14, 3, 1024, "s16"),
-    (7, 5, 10, 5, 1024, "f32"),
-]
-SWEEP_IDS = ["%d/%d" % r[:2] for r in SWEEP_RATES]
-SWEEP_FORMAT = {r[:2]: r[5] for r in SWEEP_RATES}
-SWEEP_STREAMS = 3
-LDS_LIMIT = 49152
 
 
 def all_rates():
     return [(p, q) for q in range(1, resample.Q_MAX + 1) for p in range(q + 1, 10 * q) if math.gcd(p, q) == 1]
 
 
-# ---- the launch geometry as csrc/resample.h documents it, restated: this records why a rate is in the sweep
-def raw_chunks(p, q, t, tile):
-    """16-byte chunks of raw u8 a tile stages: its samples (the last one floor((Q - 1 + (tile - 1) P) / Q) behind the first
-    output's i0, T - 1 before it) and up to 14 bytes of alignment."""
-    return (2 * ((q - 1 + (tile - 1) * p) // q + t) + 29) // 16
-
-
-def tuned_lds(p, q, t, tile):
-    """Bytes of LDS of a tuned launch: the table padded to 4 dwords, the int16 image (8 dwords per chunk), the cosine table."""
-    return (((q * t + 3) & ~3) + 8 * raw_chunks(p, q, t, tile)) * 4 + 8192
-
-
 def plain_lds(p, q, t):
-    """... and of resample_kernel: the table and the raw image (4 dwords per chunk), always a whole tile."""
+    """Bytes of LDS of resample_kernel (input_rows.tuned_lds: of a tuned launch): the table and the raw image (4 dwords per chunk),
+    always a whole tile."""
     return (((q * t + 3) & ~3) + 4 * raw_chunks(p, q, t, 1024)) * 4
-
-
-def tile_of(p, q, t):
-    return 1024 if tuned_lds(p, q, t, 1024) <= LDS_LIMIT else 512
 
 
 # ---- every rate
@@ -116,20 +65,20 @@ def test_every_rate_library_taps_equal_the_restatement():
 def test_sweep_rates_are_what_they_are_there_for():
     """Non-vacuity of test_rate_sweep_gpu.py: each rate has the T, the Q, the block unit and the side of the whole-tile /
     half-tile decision it is listed with, computed from the geometry csrc/resample.h documents."""
-    for p, q, t, unit, tile, fmt in SWEEP_RATES:
+    for p, q, t, unit, tile, fmt in RATE_SWEEP:
         assert math.gcd(p, q) == 1 and q <= 64 and q < p < 10 * q
         assert resample.n_taps(p, q) == t and resample.permitted_blocks(q) == unit, (p, q)
         assert tile_of(p, q, t) == tile, (p, q, tuned_lds(p, q, t, 1024))
         assert tuned_lds(p, q, t, tile) <= LDS_LIMIT and plain_lds(p, q, t) <= LDS_LIMIT
-    by_rate = {r[:2]: r for r in SWEEP_RATES}
-    assert len(by_rate) == len(SWEEP_RATES) == 15
+    by_rate = {r[:2]: r for r in RATE_SWEEP}
+    assert len(by_rate) == len(RATE_SWEEP) == 15
     # the edges of T and Q
     assert min(all_rates(), key=lambda r: r[0] / r[1]) == (65, 64) and resample.abs_sum_max(65, 64) == 108112
     assert [by_rate[r][2] for r in ((65, 64), (3, 2), (127, 64))] == [8, 10, 12] and 2 * 127 < 2 * 2 * 64
     assert [by_rate[r][2] for r in ((2, 1), (4, 1), (9, 1))] == [12, 24, 54]
     assert by_rate[19, 2][2] == 58 and by_rate[39, 4][2] == by_rate[639, 64][2] == 60
     assert max(all_rates(), key=lambda r: r[0] / r[1]) == (639, 64)
-    assert sorted({r[3] for r in SWEEP_RATES}) == [1, 3, 5]
+    assert sorted({r[3] for r in RATE_SWEEP}) == [1, 3, 5]
     # the whole-tile / half-tile threshold, from both sides
     lds = {r: tuned_lds(r[0], r[1], resample.n_taps(*r), 1024) for r in all_rates()}
     half = sorted((v, r) for r, v in lds.items() if v > LDS_LIMIT)
@@ -141,79 +90,33 @@ def test_sweep_rates_are_what_they_are_there_for():
     assert max(plain_lds(r[0], r[1], resample.n_taps(*r)) for r in all_rates()) == plain_lds(639, 64, 60) == 35936
     assert max(tuned_lds(r[0], r[1], resample.n_taps(*r), 512) for _, r in half) <= LDS_LIMIT
     # every format of case (d) meets a whole-tile and a half-tile rate
-    assert {(r[5], r[4]) for r in SWEEP_RATES} == {(f, n) for f in ("s8", "s16", "f32") for n in (512, 1024)}
-    assert [r[5] for r in SWEEP_RATES] == ["s8", "s16", "f32"] * 5
+    assert {(r[5], r[4]) for r in RATE_SWEEP} == {(f, n) for f in ("s8", "s16", "f32") for n in (512, 1024)}
+    assert [r[5] for r in RATE_SWEEP] == ["s8", "s16", "f32"] * 5
 
 
-# ---- the rows and the expectations of the GPU sweep, computed once per session
-def sweep_sizes(q):
-    """The submits of a sweep run, in blocks: both history buffers are used and the first one reused, the phase carries twice,
-    and the first and last submits are smaller than the context's buffers (max_blocks = 2 units)."""
-    unit = resample.permitted_blocks(q)
-    return (unit, 2 * unit, unit)
-
-
-def sweep_tunes(p, q):
-    """Per stream: 1234 Hz inside the limit of the input-rate tune, untuned, and a negative tune."""
-    return ((1536000 * p + 2 * q - 1) // (2 * q) - 1 - 1234, 0, -123457)
-
-
-@functools.lru_cache(maxsize=None)
-def sweep_rows(fmt, p, q):
-    """[streams, bytes] (uint8, read-only): different full-scale random data per stream, so that a row mix-up shows; the f32
-    rows reach beyond +-1, so that the clamp acts."""
-    n = resample.input_samples(sum(sweep_sizes(q)), p, q)
-    if fmt == "u8":
-        rows = np.random.default_rng(1000 * p + q).integers(0, 256, (SWEEP_STREAMS, 2 * n), dtype=np.uint8)
-    else:
-        rows = np.concatenate([parity.full_scale_row(fmt, n, 1000 * p + q + 7 * s + 1) for s in range(SWEEP_STREAMS)])
-    assert rows.shape == (SWEEP_STREAMS, n * formats.bytes_per_sample(fmt)) and not np.array_equal(rows[0], rows[1])
-    rows.setflags(write=False)
-    return rows
-
-
-@functools.lru_cache(maxsize=None)
-def sweep_stage0(fmt, p, q, tuned):
-    """The restatement's stage 0 of every stream of sweep_rows over the whole run (read-only): u8 through resample_s16 or --
-    tuned -- test_input_tune_cpu's stage0_of, a format through formats.to_x, tune.mix_in_s16 and resample_x16."""
-    rows = sweep_rows(fmt, p, q)
-    hz = sweep_tunes(p, q) if tuned else (0,) * SWEEP_STREAMS
-    out = []
-    for s in range(SWEEP_STREAMS):
-        if fmt == "u8":
-            y = tuned_stage0_of(rows[s], p, q, hz[s]) if tuned else resample.resample_s16(rows[s], p, q)
-        else:
-            x = formats.to_x(fmt, rows[s])
-            y = resample.resample_x16(tune.mix_in_s16(x, hz[s], p, q) if hz[s] else x, p, q)
-        assert len(y) == 2 * sum(sweep_sizes(q)) * 32768
-        y.setflags(write=False)
-        out.append(y)
-    return tuple(out)
-
-
-@pytest.mark.parametrize("p,q", [r[:2] for r in SWEEP_RATES], ids=SWEEP_IDS)
+@pytest.mark.parametrize("p,q", [r[:2] for r in RATE_SWEEP], ids=RATE_SWEEP_IDS)
 def test_cutting_the_sweep_rows_reproduces_the_stream(p, q):
     """What the GPU sweep expects is consistent in itself: the sweep's u8 row cut into its (unit, 2 unit, unit) submits, each
     from the T - 1 raw samples before it, is the uncut stream; and so is the (d)-format row behind tune.mix_in_s16 with the phase
     carried (the history is rotated with its own sample numbers) and resample_x16.  An untuned stream of a tuned launch is the
     untuned restatement."""
     t = resample.n_taps(p, q)
-    sizes = sweep_sizes(q)
-    u8 = sweep_rows("u8", p, q)[0]
+    sizes = rate_sweep_sizes(q)
+    u8 = rate_sweep_rows("u8", p, q)[0]
     parts, pos = [], 0
     for nb in sizes:
         n = 2 * resample.input_samples(nb, p, q)
         parts.append(resample.resample_s16(u8[pos:pos + n], p, q, hist=u8[pos - 2 * (t - 1):pos] if pos else None))
         assert len(parts[-1]) == 2 * nb * 32768
         pos += n
-    assert pos == len(u8) and np.array_equal(np.concatenate(parts), sweep_stage0("u8", p, q, False)[0])
-    assert np.array_equal(sweep_stage0("u8", p, q, True)[1], sweep_stage0("u8", p, q, False)[1])
-    assert not np.array_equal(sweep_stage0("u8", p, q, True)[0], sweep_stage0("u8", p, q, False)[0])
+    assert pos == len(u8) and np.array_equal(np.concatenate(parts), rate_sweep_stage0("u8", p, q, False)[0])
+    assert np.array_equal(rate_sweep_stage0("u8", p, q, True)[1], rate_sweep_stage0("u8", p, q, False)[1])
+    assert not np.array_equal(rate_sweep_stage0("u8", p, q, True)[0], rate_sweep_stage0("u8", p, q, False)[0])
 
-    fmt = SWEEP_FORMAT[p, q]
-    hz = sweep_tunes(p, q)[0]
+    fmt = RATE_SWEEP_FORMAT[p, q]
+    hz = rate_sweep_tunes(p, q)[0]
     assert 2 * (hz + 1234) * q < 1536000 * p <= 2 * (hz + 1235) * q  # 1234 Hz inside the limit
-    x = formats.to_x(fmt, sweep_rows(fmt, p, q)[0])
+    x = formats.to_x(fmt, rate_sweep_rows(fmt, p, q)[0])
     assert x.min() == -8192 and x.max() == (8128 if fmt == "s8" else 8191)
     parts, pos = [], 0  # (pos counts int16 values: two per complex sample)
     for nb in sizes:
@@ -222,5 +125,5 @@ def test_cutting_the_sweep_rows_reproduces_the_stream(p, q):
         m = tune.mix_in_s16(x[pos - lead:pos + n], hz, p, q, (pos - lead) // 2)
         parts.append(resample.resample_x16(m[lead:], p, q, hist=m[:lead] if lead else None))
         pos += n
-    assert pos == len(x) and np.array_equal(np.concatenate(parts), sweep_stage0(fmt, p, q, True)[0])
-    assert np.array_equal(sweep_stage0(fmt, p, q, True)[1], sweep_stage0(fmt, p, q, False)[1])
+    assert pos == len(x) and np.array_equal(np.concatenate(parts), rate_sweep_stage0(fmt, p, q, True)[0])
+    assert np.array_equal(rate_sweep_stage0(fmt, p, q, True)[1], rate_sweep_stage0(fmt, p, q, False)[1])

@@ -1,6 +1,6 @@
 """The resampling kernels on the GPU across the rate range, bit for bit: resample_kernel, resample_fmt_kernel<U8> (the tuned u8 kernel) and
-resample_fmt_kernel<S8 | S16 | F32> at the rates of test_rate_sweep_cpu.SWEEP_RATES (the edges of T, Q, the LDS and the
-whole-tile / half-tile decision; that module asserts what each rate is there for and that the expectations are consistent in
+resample_fmt_kernel<S8 | S16 | F32> at the rates of input_rows.RATE_SWEEP (the edges of T, Q, the LDS and the
+whole-tile / half-tile decision; test_rate_sweep_cpu.py asserts what each rate is there for and that the expectations are consistent in
 themselves), and ingest_kernel's row lookup.
 
 Every run is three streams of different full-scale data over submits of (unit, 2 unit, unit) blocks on a context of 2 units:
@@ -11,15 +11,13 @@ import numpy as np
 import pytest
 
 import parity
+from input_rows import (RATE_SWEEP, RATE_SWEEP_FORMAT, RATE_SWEEP_IDS, RATE_SWEEP_STREAMS, THRESH, TYPES, format_stage0, rate_sweep_rows,
+                        rate_sweep_sizes, rate_sweep_stage0, rate_sweep_tunes, tile_of)
 from tfrec_amd import api, formats, resample, tune
-from test_formats_cpu import stage0_of as fmt_stage0_of
-from test_resample_cpu import THRESH, TYPES
-from test_rate_sweep_cpu import (SWEEP_FORMAT, SWEEP_IDS, SWEEP_RATES, SWEEP_STREAMS, sweep_rows, sweep_sizes, sweep_stage0,
-                                 sweep_tunes, tile_of)
 
 pytestmark = pytest.mark.gpu
 
-RATES = [r[:2] for r in SWEEP_RATES]
+RATES = [r[:2] for r in RATE_SWEEP]
 
 
 def stage0_run(fmt, rows, sizes, p, q, before=None, n_streams=None):
@@ -30,49 +28,49 @@ def stage0_run(fmt, rows, sizes, p, q, before=None, n_streams=None):
 
 
 def tune_first(p, q):
-    hz = sweep_tunes(p, q)
+    hz = rate_sweep_tunes(p, q)
 
     def before(r, k):
         if k == 0:
-            r.tune_streams_input(list(range(SWEEP_STREAMS)), hz)
-            assert [r.stream_tune_input(s) for s in range(SWEEP_STREAMS)] == list(hz)
+            r.tune_streams_input(list(range(RATE_SWEEP_STREAMS)), hz)
+            assert [r.stream_tune_input(s) for s in range(RATE_SWEEP_STREAMS)] == list(hz)
 
     return before
 
 
 def sweep(fmt, p, q, tuned):
-    sizes = sweep_sizes(q)
-    y0 = stage0_run(fmt, sweep_rows(fmt, p, q), sizes, p, q, before=tune_first(p, q) if tuned else None)
-    want = sweep_stage0(fmt, p, q, tuned)
+    sizes = rate_sweep_sizes(q)
+    y0 = stage0_run(fmt, rate_sweep_rows(fmt, p, q), sizes, p, q, before=tune_first(p, q) if tuned else None)
+    want = rate_sweep_stage0(fmt, p, q, tuned)
     label = "%d/%d %s%s" % (p, q, fmt, " tuned" if tuned else "")
     tile = 1024 if fmt == "u8" and not tuned else tile_of(p, q, resample.n_taps(p, q))
-    for s in range(SWEEP_STREAMS):
+    for s in range(RATE_SWEEP_STREAMS):
         parity.assert_stage0(y0, sizes, want[s], s, label, tile)
 
 
-@pytest.mark.parametrize("p,q", RATES, ids=SWEEP_IDS)
+@pytest.mark.parametrize("p,q", RATES, ids=RATE_SWEEP_IDS)
 def test_u8_untuned(p, q):
     """(a) resample_kernel: the kernel tfrec_gpu -r uses by default."""
     sweep("u8", p, q, False)
 
 
-@pytest.mark.parametrize("p,q", RATES, ids=SWEEP_IDS)
+@pytest.mark.parametrize("p,q", RATES, ids=RATE_SWEEP_IDS)
 def test_u8_mixed_tunes_in_one_launch(p, q):
     """(b) resample_fmt_kernel<U8>, the tuned u8 kernel: stream 0 tuned 1234 Hz inside the limit, stream 1 untuned, stream 2 tuned to -123457 Hz."""
     sweep("u8", p, q, True)
 
 
-@pytest.mark.parametrize("p,q", RATES, ids=SWEEP_IDS)
+@pytest.mark.parametrize("p,q", RATES, ids=RATE_SWEEP_IDS)
 @pytest.mark.parametrize("fmt", ["s8", "s16", "f32"])
 def test_formats_untuned(fmt, p, q):
     """(c) resample_fmt_kernel<FMT> launched without the cosine table."""
     sweep(fmt, p, q, False)
 
 
-@pytest.mark.parametrize("p,q", RATES, ids=SWEEP_IDS)
+@pytest.mark.parametrize("p,q", RATES, ids=RATE_SWEEP_IDS)
 def test_one_format_with_mixed_tunes(p, q):
     """(d) resample_fmt_kernel<FMT> with the tunes of (b); the format cycles s8, s16, f32 down the table."""
-    sweep(SWEEP_FORMAT[p, q], p, q, True)
+    sweep(RATE_SWEEP_FORMAT[p, q], p, q, True)
 
 
 # ---- beside the sweep
@@ -92,7 +90,7 @@ def test_base_rate_format_context_reads_mapped_rows(fmt):
     half = rows.shape[1] // 2
     for k in range(2):
         for s in range(3):
-            want = fmt_stage0_of(fmt, rows[rows_of[k][s], k * half:(k + 1) * half], 1, 1)
+            want = format_stage0(fmt, rows[rows_of[k][s], k * half:(k + 1) * half], 1, 1)
             assert np.array_equal(y0[k][s], want), "%s submit %d stream %d: %s" % (fmt, k, s, parity.first_difference(y0[k][s], want, 2048))
     assert not np.array_equal(y0[0][0], y0[0][2]) and not np.array_equal(y0[1][0], y0[1][1])
 
@@ -100,8 +98,8 @@ def test_base_rate_format_context_reads_mapped_rows(fmt):
 def test_shared_row_at_a_half_tile_rate():
     """39/4, f32: three streams read row 0 with three input tunes, and the submits carry that one row."""
     p, q, fmt = 39, 4, "f32"
-    sizes, hz = sweep_sizes(q), sweep_tunes(p, q)
-    row = sweep_rows(fmt, p, q)[:1].copy()
+    sizes, hz = rate_sweep_sizes(q), rate_sweep_tunes(p, q)
+    row = rate_sweep_rows(fmt, p, q)[:1].copy()
 
     def before(r, k):
         if k == 0:
@@ -112,7 +110,7 @@ def test_shared_row_at_a_half_tile_rate():
     y0 = stage0_run(fmt, row, sizes, p, q, before=before, n_streams=3)
     x = formats.to_x(fmt, row[0])
     for s in range(3):
-        want = sweep_stage0(fmt, p, q, True)[0] if s == 0 else resample.resample_x16(tune.mix_in_s16(x, hz[s], p, q), p, q)
+        want = rate_sweep_stage0(fmt, p, q, True)[0] if s == 0 else resample.resample_x16(tune.mix_in_s16(x, hz[s], p, q), p, q)
         parity.assert_stage0(y0, sizes, want, s, "39/4 f32 shared row", 512)
 
 
@@ -120,7 +118,7 @@ def test_shared_row_at_a_half_tile_rate():
 def test_reset_at_an_edge_rate(fmt, p, q):
     """reset_streams([1]) before the second submit: from there stream 1 is the restatement of the remaining input from zero
     history and phase 0; stream 0 carries on."""
-    sizes = sweep_sizes(q)
+    sizes = rate_sweep_sizes(q)
     if fmt == "u8":
         rows = parity.loud_and_quiet(p, q, sizes, 2, 1000 * p + q)
     else:
@@ -128,7 +126,7 @@ def test_reset_at_an_edge_rate(fmt, p, q):
     y0 = stage0_run(fmt, rows, sizes, p, q, before=lambda r, k: r.reset_streams([1]) if k == 1 else None)
 
     def restated(row):
-        return resample.resample_s16(row, p, q) if fmt == "u8" else fmt_stage0_of(fmt, row, p, q)
+        return resample.resample_s16(row, p, q) if fmt == "u8" else format_stage0(fmt, row, p, q)
 
     tile = 1024 if fmt == "u8" else tile_of(p, q, resample.n_taps(p, q))
     cut = formats.bytes_per_sample(fmt) * resample.input_samples(sizes[0], p, q)

@@ -1,7 +1,6 @@
 """CPU tests of the recorder family's harness (tests/recorder.py, tests/recorder_rows.py): the parts the GPU suite can check only
 indirectly -- that the comparisons pass on equal inputs and, on one changed value, fail with a message that says where; how
 tfrec_gpu's lines are picked by their first word; and that no test module of the family imports another."""
-import ast
 import glob
 import os
 import re
@@ -11,6 +10,7 @@ import pytest
 
 import parity
 import recorder as R
+from parity import imports_of
 from tfrec_amd import capture
 
 DTYPES = {"run": capture.RUN_DTYPE, **{m: st.dtype for m, st in R.STAGES.items()}}
@@ -99,17 +99,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 FAMILY = re.compile(r"test_((capture|burst|envelope|clock|track|sync|decin)_(gpu|cpu)|recorder_campaign_(gpu|cpu))$")
 
 
-def imports_of(path):
-    """The top-level names of every module a file imports, anywhere in it."""
-    out = set()
-    for node in ast.walk(ast.parse(open(path).read(), path)):
-        if isinstance(node, ast.Import):
-            out |= {a.name.split(".")[0] for a in node.names}
-        elif isinstance(node, ast.ImportFrom) and node.module and node.level == 0:
-            out.add(node.module.split(".")[0])
-    return out
-
-
 def test_no_module_imports_a_test_module_of_the_family_and_the_harness_imports_no_test_module():
     paths = sorted(glob.glob(os.path.join(HERE, "*.py")))
     assert len(paths) > 50 and {"recorder.py", "recorder_rows.py", "recorder_campaign.py"} <= {os.path.basename(p) for p in paths}
@@ -119,5 +108,5 @@ def test_no_module_imports_a_test_module_of_the_family_and_the_harness_imports_n
         assert not [m for m in found if FAMILY.match(m)], "%s imports %s" % (name, sorted(m for m in found if FAMILY.match(m)))
         if name in ("recorder.py", "recorder_rows.py", "recorder_campaign.py"):
             assert not [m for m in found if m.startswith("test_")], "%s imports %s" % (name, sorted(found))
-    assert "test_levels_cpu" in imports_of(os.path.join(HERE, "test_capture_cpu.py"))  # (imports_of sees `from m import n`)
+    assert "meter_rows" in imports_of(os.path.join(HERE, "test_capture_cpu.py"))  # (imports_of sees `from m import n`)
     assert "recorder_rows" in imports_of(os.path.join(HERE, "test_recorder_campaign_cpu.py"))  # ... and one inside a function

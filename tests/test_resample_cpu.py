@@ -2,43 +2,14 @@
 the properties of the definition, the scenes the GPU tests decode, and tfrec_gpu -r's argument handling.
 
 Everything is bit-exact; nothing here has a tolerance."""
-import subprocess
-
 import numpy as np
 import pytest
 
 import parity
-from oracle import oracle as O
-from tfrec_amd import api, resample, synth
+from input_rows import SCENE_RATES, oracle_of, rate_scene
+from tfrec_amd import api, resample
 
 RATES = [(4, 3), (25, 16), (5, 4), (5, 3), (15, 8), (25, 12), (2, 1), (4, 1), (75, 64)]
-TYPES, THRESH = 0x2F, 500
-
-# ---- the scenes of the GPU tests (test_resample_gpu.py imports them): the generator's streams at rate_mult = P with every
-# Q-th complex sample kept are recordings at 1536000 P / Q samples per second -- 2.048 MS/s and 2.4 MS/s
-SCENE_RATES = [(4, 3), (25, 16)]
-SCENE_BLOCKS = 12
-SCENE_STREAMS = [(1, 0), (3, 1)]  # (seed, stream): chosen on the CPU so that every protocol decodes (asserted below)
-
-
-def rate_stream(p, q, seed, stream, n_blocks=SCENE_BLOCKS, noise_q8=256):
-    """u8 IQ of n_blocks blocks' worth of input at 1536000 p / q samples per second."""
-    x = synth.gen_stream(seed, stream, n_blocks, 0x1F, noise_q8, rate_mult=p).reshape(-1, 2)[::q]
-    x = np.ascontiguousarray(x).reshape(-1)
-    assert len(x) == 2 * resample.input_samples(n_blocks, p, q)
-    return x
-
-
-def rate_scene(p, q, n_blocks=SCENE_BLOCKS):
-    """[streams, bytes]: the scene of one rate."""
-    return np.stack([rate_stream(p, q, seed, s, n_blocks) for seed, s in SCENE_STREAMS])
-
-
-def oracle_of(x, p, q, types=TYPES, thresh=THRESH, wide=0, log_bits=False):
-    """The oracle fed the restatement's stage 0 of one stream's input."""
-    o = O.Oracle(types, thresh, wide, log_bits=log_bits)
-    o.process_s16(resample.resample_s16(x, p, q))
-    return o
 
 
 # ---- tap tables
@@ -156,36 +127,32 @@ def cli():
     return parity.build_cli()
 
 
-def run_cli(cli, args):
-    return subprocess.run([cli] + args, capture_output=True, text=True, timeout=120)
-
-
 def test_cli_rate_argument_errors(cli, tmp_path):
     missing = str(tmp_path / "missing.iq")
     for bad in ("abc", "0", "-5", "2048000x", ""):
-        out = run_cli(cli, ["-r", bad, "-L", missing])
+        out = parity.run_cli(["-r", bad, "-L", missing])
         assert out.returncode == 1 and "bad -r" in out.stderr, bad
-    out = run_cli(cli, ["-r", "2048000", "-x", "-L", missing])
+    out = parity.run_cli(["-r", "2048000", "-x", "-L", missing])
     assert out.returncode == 1 and "exclude" in out.stderr
     # refused by the library's rules: below 1.536 MS/s, at 15.36 MS/s, a denominator above 64
     for hz in ("1000000", "15360000", "1536001", "20000000"):
-        out = run_cli(cli, ["-r", hz, "-L", missing])
+        out = parity.run_cli(["-r", hz, "-L", missing])
         assert out.returncode == 1 and "does not take" in out.stderr, hz
     # 1536000 itself is the default input: no resampler, the file is looked for
-    out = run_cli(cli, ["-r", "1536000", "-L", missing])
+    out = parity.run_cli(["-r", "1536000", "-L", missing])
     assert out.returncode == 2 and "missing.iq" in out.stderr
 
 
 def test_cli_rounds_the_block_count_up(cli, tmp_path):
     missing = str(tmp_path / "missing.iq")
     # 2.048 MS/s = 4/3: multiples of 3 blocks; the run then ends at the missing file, before any device is opened
-    out = run_cli(cli, ["-r", "2048000", "-b", "16", "-L", missing])
+    out = parity.run_cli(["-r", "2048000", "-b", "16", "-L", missing])
     assert out.returncode == 2 and "-b 16 rounded up to 18" in out.stderr and "missing.iq" in out.stderr
-    out = run_cli(cli, ["-r", "2048000", "-b", "18", "-L", missing])
+    out = parity.run_cli(["-r", "2048000", "-b", "18", "-L", missing])
     assert out.returncode == 2 and "rounded" not in out.stderr
     # 2.4 MS/s = 25/16: Q is a power of two, any block count
-    out = run_cli(cli, ["-r", "2400000", "-b", "7", "-L", missing])
+    out = parity.run_cli(["-r", "2400000", "-b", "7", "-L", missing])
     assert out.returncode == 2 and "rounded" not in out.stderr
     # 3.2 MS/s = 25/12: multiples of 3 again
-    out = run_cli(cli, ["-r", "3200000", "-b", "1", "-L", missing])
+    out = parity.run_cli(["-r", "3200000", "-b", "1", "-L", missing])
     assert out.returncode == 2 and "-b 1 rounded up to 3" in out.stderr

@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 
 import parity
+from input_rows import SCENE_BLOCKS, SCENE_RATES, THRESH, TYPES, oracle_of, rate_scene
 from tfrec_amd import api, resample
-from test_resample_cpu import SCENE_BLOCKS, SCENE_RATES, THRESH, TYPES, oracle_of, rate_scene
 
 pytestmark = pytest.mark.gpu
 

@@ -14,7 +14,7 @@ from oracle import scenes as S
 from tfrec_amd import synth
 
 import parity
-from test_oracle_golden import _data, _sha
+from parity import golden_data, sha256_of
 
 
 @pytest.fixture(scope="module")
@@ -36,13 +36,13 @@ def test_scenes_against_reference_outputs(cases):
     for c in cases:
         tag = c["spec"]["name"]
         iq = S.render(c["spec"])
-        assert _sha(iq) == c["iq_sha256"], "generator drifted: " + tag
+        assert sha256_of(iq) == c["iq_sha256"], "generator drifted: " + tag
         o = O.Oracle(c["types"], c["thresh"], c["wide"], log_bits=True, keep_dec=True)
         o.process(iq)
-        assert _sha(o.dec()) == c["dec_sha256"], tag
+        assert sha256_of(o.dec()) == c["dec_sha256"], tag
         assert S.flush_counts(o.events()) == c["flushes"], tag
         assert S.events_digest(o.events()) == c["events_sha256"], tag
-        assert o.data() == _data(c["data"]), tag
+        assert o.data() == golden_data(c["data"]), tag
         assert o.text() == c["text"], tag
         assert hashlib.sha256(o.bits_text().encode()).hexdigest() == c["bits_sha256"], tag
         parity.status_pinned_by_text(o.events_full(), c["text"], tag)

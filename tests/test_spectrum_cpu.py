@@ -3,7 +3,6 @@ brute-force evaluation of the definition, the window, the exactness bound recomp
 tfrec_gpu decides before it opens a device.
 """
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -148,22 +147,18 @@ def cli():
     return parity.build_cli()
 
 
-def run_cli(cli, args):
-    return subprocess.run([cli] + args, capture_output=True, text=True, timeout=120)
-
-
 def test_cli_spectrum_usage_errors(cli, tmp_path):
     f = str(tmp_path / "missing.iq")
     for extra in (["-s", "50"], ["-n", "2"], ["-p", "t=100"], ["-L", f], ["-d", "0,1"], ["-X", f]):
-        out = run_cli(cli, ["-P", "256", "-L", f] + extra)
+        out = parity.run_cli(["-P", "256", "-L", f] + extra)
         assert out.returncode == 1 and "-P takes the spectrum of one -L file" in out.stderr, extra
     for bad in ("0", "100", "2048", "32", "x", "", "256,", "256,0", "256,16385", "256,x", "256;4", "-64"):
-        out = run_cli(cli, ["-P", bad, "-L", f])
+        out = parity.run_cli(["-P", bad, "-L", f])
         assert out.returncode == 1 and "bad -P" in out.stderr, bad
     for args in (["-P", "64"], ["-P", "1024,16384", "-x"], ["-P", "256,1", "-r", "2400000", "-F", "s16"], ["-P", "512", "-c", "433920"]):
-        out = run_cli(cli, args + ["-L", f])  # accepted: the file is looked for
+        out = parity.run_cli(args + ["-L", f])  # accepted: the file is looked for
         assert out.returncode == 2 and "missing.iq" in out.stderr, args
-    out = run_cli(cli, ["-P", "256"])
+    out = parity.run_cli(["-P", "256"])
     assert out.returncode == 1 and "need -L" in out.stderr
 
 
@@ -178,7 +173,7 @@ def test_cli_spectrum_bin_list(cli, tmp_path, args, fs_in, n_bins, g):
     holds (32768 P / Q samples) -- listed before a device is opened (the run itself then needs one)."""
     f = tmp_path / "empty.iq"
     f.write_bytes(b"")
-    out = run_cli(cli, args + ["-L", str(f)])
+    out = parity.run_cli(args + ["-L", str(f)])
     assert out.returncode in (0, 2)
     c = int(args[args.index("-c") + 1])
     assert "spec: %d bins, %d frames per record, input rate %d S/s" % (n_bins, g, fs_in) in out.stderr

@@ -1,53 +1,19 @@
 """The per-input power spectrum on the GPU (tfrec_amd_enable_spectrum, tfrec_amd_read_spectrum, tfrec_gpu -P), bit
 for bit: every record is compared with the restatement tfrec_amd/spectrum.py run on the very bytes submitted.  The transform is
 an exact integer DFT, so there is no tolerance anywhere."""
-import functools
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import parity
+from meter_rows import assert_spectrum, golden, scan_file, tone, u8_rows, want_u8
 from tfrec_amd import api, resample, spectrum
-from test_levels_gpu import scan_file
 
 pytestmark = pytest.mark.gpu
 
 TYPES = 0x2F
 BB = api.BLOCK_BYTES
-
-
-def assert_spectrum(got, want, label=""):
-    for name, g, w in zip(("sum", "peak", "n_frames"), got, want):
-        assert g.dtype == w.dtype and g.shape == w.shape, "%s %s: %s %s, want %s %s" % (label, name, g.dtype, g.shape, w.dtype, w.shape)
-        if not np.array_equal(g, w):
-            bad = np.argwhere(g != w)
-            raise AssertionError("%s %s: %d values differ, first at %s: got %d, want %d" % (
-                label, name, len(bad), tuple(bad[0]), g[tuple(bad[0])], w[tuple(bad[0])]))
-
-
-def tone(n, f_rel, amp):
-    ph = 2.0 * np.pi * f_rel * np.arange(n)
-    return np.stack([amp * np.cos(ph), amp * np.sin(ph)], axis=1).reshape(-1)
-
-
-@functools.lru_cache(maxsize=None)
-def u8_rows(n_blocks=2):
-    """[3, n_blocks] u8: random full-range bytes plus a tone, all bytes 0, samples alternating 0 and 255."""
-    n = n_blocks * BB // 2
-    rng = np.random.default_rng(11)
-    a = np.clip(rng.integers(0, 256, 2 * n) + np.rint(tone(n, 0.1337, 60.0)), 0, 255).astype(np.uint8)
-    z = np.zeros(2 * n, dtype=np.uint8)
-    y = np.repeat(np.tile(np.array([0, 255], dtype=np.uint8), n // 2), 2)
-    rows = np.stack([a, z, y])
-    rows.setflags(write=False)
-    return rows
-
-
-@functools.lru_cache(maxsize=None)
-def want_u8(n_bins, g, n_blocks=2, first=0):
-    return [spectrum.spectrum(row[first * BB:(first + n_blocks) * BB], n_bins, g, fmt="u8") for row in u8_rows(max(2, first + n_blocks))]
 
 
 @pytest.mark.parametrize("n_bins,g,n_blocks", [(64, 7, 2), (256, 7, 2), (1024, 5, 1)])
@@ -112,15 +78,6 @@ def test_a_10x_context():
     assert got[0][2].tolist() == [100] * 25 + [60]
     assert_spectrum(got[0], spectrum.spectrum(row[0], 128, 100, fmt="u8"), "10x")
     assert int(np.argmax(got[0][0].sum(axis=0))) == 128 - round(0.31 * 128)
-
-
-@functools.lru_cache(maxsize=None)
-def golden():
-    """[1, 3 blocks]: the start of the golden TFA_2 scene."""
-    z = np.load(os.path.join(parity.ROOT, "tests", "golden", "iq_tfa_2.npz"))
-    x = np.ascontiguousarray(z["iq"][:3 * BB]).reshape(1, -1)
-    x.setflags(write=False)
-    return x
 
 
 def test_events_levels_and_captures_do_not_depend_on_it():

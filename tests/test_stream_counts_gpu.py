@@ -7,8 +7,8 @@ capture_offsets_kernel (a prefix scan that carries its totals from one step of 6
 indexed through a stream list.  97 = 3 * 32 + 1 = 64 + 33 and 65 = 2 * 32 + 1 = 64 + 1 put a second group and a ragged tail behind
 the first.
 
-The inputs, and every condition assumed about them here -- that the compared events, runs and telegrams exist, on the streams behind
-index 64 too --, are in tests/test_stream_counts_cpu.py."""
+The inputs are in tests/stream_count_rows.py; every condition assumed about them here -- that the compared events, runs and telegrams
+exist, on the streams behind index 64 too -- is asserted in tests/test_stream_counts_cpu.py."""
 import functools
 
 import numpy as np
@@ -18,9 +18,10 @@ import parity
 import recorder as R
 import recorder_rows as RR
 import segments
-import test_stream_counts_cpu as C
+import stream_count_rows as C
+from input_rows import DFLT, make_rows
+from parity import device_parts
 from recorder import pre_of, same_events
-from test_channels_gpu import DFLT, device_parts, make_rows
 from tfrec_amd import api, capture, decin, levels
 
 pytestmark = pytest.mark.gpu

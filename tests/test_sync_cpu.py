@@ -18,7 +18,7 @@ import parity
 from recorder_rows import (GOLDEN, PAYLOADS, PLATEAUS, RATE, WORD, frame_symbols, golden_dec, rotated, submits, word_bits,
                            sync_stripped as stripped)
 from tfrec_amd import api, capture, levels, sync, track
-from test_levels_cpu import crafted_dec
+from meter_rows import crafted_dec
 
 B = levels.BLOCK_DEC
 CONT, OPEN = capture.RUN_CONTINUES, capture.RUN_OPEN
@@ -384,28 +384,25 @@ def test_the_struct_and_the_exports(tmp_path):
 
 
 def test_cli_sync_usage_errors(tmp_path):
-    cli = parity.build_cli()
+    parity.build_cli()
     f = str(tmp_path / "missing.iq")
 
-    def run(args):
-        return subprocess.run([cli] + args, capture_output=True, text=True, timeout=120)
-
-    out = run(["-Y", "2dd4", "-L", f])
+    out = parity.run_cli(["-Y", "2dd4", "-L", f])
     assert out.returncode == 1 and "-Y finds" in out.stderr  # without -G
     for bad in ("2", "2dd4a5920189acdb0", "2dx4", "", "2dd4,8", "2dd4,-1", "2dd4,0,0", "2dd4,0,257", "2dd4,0,4,2", "2dd4,0,4,1,0", "2dd4,"):
-        out = run(["-G", "17240", "-Y", bad, "-L", f])
+        out = parity.run_cli(["-G", "17240", "-Y", bad, "-L", f])
         assert out.returncode == 1 and "bad -Y" in out.stderr, bad
-    out = run(["-G", "4315", "-Y", "1aa2dd4", "-L", f])  # 28 bits at 4315 bit/s: 2403 samples
+    out = parity.run_cli(["-G", "4315", "-Y", "1aa2dd4", "-L", f])  # 28 bits at 4315 bit/s: 2403 samples
     assert out.returncode == 1 and "more than 2047" in out.stderr
     for args in (["-X", f], ["-s", "50", "-L", f], ["-A", "-L", f]):
-        out = run(["-G", "17240", "-Y", "2dd4"] + args)
+        out = parity.run_cli(["-G", "17240", "-Y", "2dd4"] + args)
         assert out.returncode == 1 and "-G reads" in out.stderr, args
     for k in ("-k", "-K"):
-        out = run(["-G", "17240", "-Y", "2dd4", k, str(tmp_path / "keep"), "-L", f])
+        out = parity.run_cli(["-G", "17240", "-Y", "2dd4", k, str(tmp_path / "keep"), "-L", f])
         assert out.returncode == 2 and "not with -G" in out.stderr
-    out = run(["-h"])
+    out = parity.run_cli(["-h"])
     assert "-Y h[,e[,n[,b]]]" in out.stderr and "[-Y hex[,errors[,bytes[,both]]]]" in out.stderr
     for args in (["-G", "17240", "-Y", "2dd4"], ["-G", "17240", "-Y", "2DD4,7,256,1"], ["-G", "4315", "-Y", "aa2dd4,11"],
                  ["-G", "96000", "-Y", "0123456789abcdef,31,1,0", "-M", "-Q", "-C"], ["-Y", "d4,3", "-G", "17240,20000"]):
-        out = run(args + ["-L", f])  # accepted: the file is looked for
+        out = parity.run_cli(args + ["-L", f])  # accepted: the file is looked for
         assert out.returncode == 2 and "missing.iq" in out.stderr, args

@@ -18,7 +18,7 @@ import pytest
 import parity
 from recorder_rows import GOLDEN, RATE, TELEGRAMS, bit_string, golden_dec, pattern, rotated, stripped, submits
 from tfrec_amd import api, capture, envelope, levels, track, tune
-from test_levels_cpu import crafted_dec
+from meter_rows import crafted_dec
 
 B = levels.BLOCK_DEC
 CONT, OPEN = capture.RUN_CONTINUES, capture.RUN_OPEN
@@ -382,28 +382,25 @@ def test_the_struct_and_the_exports(tmp_path):
 
 
 def test_cli_track_usage_errors(tmp_path):
-    cli = parity.build_cli()
+    parity.build_cli()
     f = str(tmp_path / "missing.iq")
 
-    def run(args):
-        return subprocess.run([cli] + args, capture_output=True, text=True, timeout=120)
-
     for args in (["-G", "17240", "-X", f], ["-G", "17240", "-s", "50", "-L", f], ["-G", "17240", "-A", "-L", f]):
-        out = run(args)
+        out = parity.run_cli(args)
         assert out.returncode == 1 and "-G reads" in out.stderr, args
-    out = run(["-M", "-G", "17240", "-X", f])  # -M's own refusal comes first and is what it was
+    out = parity.run_cli(["-M", "-G", "17240", "-X", f])  # -M's own refusal comes first and is what it was
     assert out.returncode == 1 and "-M measures" in out.stderr
     for bad in ("999", "96001", "abc", "17240,192001", "17240,-192001", "17240,", ",5"):
-        out = run(["-G", bad, "-L", f])
+        out = parity.run_cli(["-G", bad, "-L", f])
         assert out.returncode == 1 and "bad -G" in out.stderr, bad
-    out = run(["-h"])
+    out = parity.run_cli(["-h"])
     assert "-G r[,c]" in out.stderr and "[-G rate[,centre_hz]]" in out.stderr
     for args in (["-G", "17240", "-k", str(tmp_path / "keep"), "-L", f], ["-G", "17240", "-K", str(tmp_path / "keep"), "-L", f]):
-        out = run(args)
+        out = parity.run_cli(args)
         assert out.returncode == 2 and "not with -G" in out.stderr, args
     for args in (["-G", "17240", "-L", f], ["-G", "96000,-192000", "-L", f], ["-G", "1000,192000", "-M", "-Q", "-C", "-L", f],
                  ["-G", "17240", "-S", str(tmp_path / "cap"), "-n", "1", "-L", f], ["-G", "17240", "-d", "0", "-L", f]):
-        out = run(args)  # accepted: the file is looked for
+        out = parity.run_cli(args)  # accepted: the file is looked for
         assert out.returncode == 2 and "missing.iq" in out.stderr, args
-    out = run(["-G", "17240", "-R", str(tmp_path / "nothing")])  # accepted with -R: the capture is looked for
+    out = parity.run_cli(["-G", "17240", "-R", str(tmp_path / "nothing")])  # accepted with -R: the capture is looked for
     assert out.returncode == 2 and "-R replays" not in out.stderr
