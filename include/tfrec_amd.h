@@ -971,6 +971,37 @@ int tfrec_amd_set_burst_track_centre(tfrec_amd_ctx *ctx, const int32_t *streams,
 int tfrec_amd_read_burst_tracks(tfrec_amd_ctx *ctx, tfrec_amd_track *out, size_t cap_runs, uint32_t *n_runs, uint32_t *words,
 				size_t cap_words, uint64_t *n_words);
 
+/* Amplitude track (tfrec_amd_enable_burst_track_amplitude): a MODE of the burst track for on-off keyed bursts -- one
+ * bit per captured sample, 1 where the burst's smoothed amplitude lies above a level.  A context has the frequency track above or the
+ * amplitude track, never both.  The record (tfrec_amd_track), the bitmap's layout (Bits), last_over, n_ones and bit_offset (Record),
+ * the merging rules (Cutting), the carry (the stream's last 16 pairs, and prior as under Samples), the overflow prefixes and
+ * tfrec_amd_read_burst_tracks are exactly the frequency track's; so are the Slicing and everything the burst sync makes of a track.
+ * Only the bit differs.  There is no reference counterpart: this text is normative, tfrec_amd/track.py (amplitude_tracks) restates
+ * it.  Exact integers only.
+ *   Settings: smooth = L, 1 .. 16, fixed at enable.  Per stream a level, 0 .. 65535, default 0 (tfrec_amd_set_burst_track_level), in
+ *             the trigger's own unit: pwr = |I| + |Q| of a decimated pair, the unit of a stream's threshold and of tfrec_amd_burst's
+ *             pwr_max.  A new level takes effect with the next submit.  It is not a restart: a chain that spans the change is sliced
+ *             with both, every sum with the level of the submit that forms it.
+ *   Bit:      for entry e with samples z[k] = (I, Q) and prior as for the frequency track, p[k] = |I| + |Q| (at most 65536).
+ *             t[k] = 1 iff the sum of p[k - i] over the i with 0 <= i < L and k - i >= -prior is greater than L * level.  Samples
+ *             ahead of the chain's first one count as 0 and are never read, so a burst's first L - 1 bits lean towards 0.  In a
+ *             CONTINUES piece z[k] for -16 <= k < 0 are the stream's last 16 pairs of the submit before.  The sum stays below 2^21; a
+ *             sum equal to L * level gives 0.  With one level and no TFREC_AMD_E_OVERFLOW the merged chain's track does not depend on
+ *             how the stream was cut into submits.
+ *   Pulses (what a caller makes of a merged track; normative for tfrec_gpu -O and track.py): take the track's first last_over + 1
+ *             samples (none if -1) and the maximal runs of equal value in order; drop a leading run of zeros and a trailing run of
+ *             zeros.  What remains alternates pulse width, gap width, ..., pulse width, in samples (nothing remains: no pulse).
+ *             This is a level slicer with a level the caller gives, not an automatic gain control: a level too low reads the noise
+ *             between pulses, one too high reads nothing.  Nothing of it has been measured on real recordings. */
+/* Turn the track on in amplitude mode: tfrec_amd_enable_burst_track's rules, memory (the per-set values staged per stream are the
+ * levels: the same bytes) and errors; a context whose track is on already, in either mode, refuses both enables with
+ * TFREC_AMD_E_INVAL.  tfrec_amd_enable_burst_sync works on either mode.  One kernel differs on the recorder's stream. */
+int tfrec_amd_enable_burst_track_amplitude(tfrec_amd_ctx *ctx, int32_t smooth);
+/* The level of streams[i] becomes level[i], from the next submit on (tfrec_amd_set_burst_track_centre's argument rules).  A level
+ * outside 0 .. 65535, a stream out of range, or a context whose track is off or in frequency mode: TFREC_AMD_E_INVAL and nothing is
+ * set; a poisoned context: TFREC_AMD_E_STATE.  tfrec_amd_set_burst_track_centre on an amplitude context is TFREC_AMD_E_INVAL. */
+int tfrec_amd_set_burst_track_level(tfrec_amd_ctx *ctx, const int32_t *streams, const int32_t *level, int n);
+
 /* Burst sync (tfrec_amd_enable_burst_sync): for every run of the recorder's table WHERE A FRAME BEGINS -- one bit per
  * captured sample, 1 where the burst track, read at P symbol centres that end at the sample, is a known sync word but for at most E
  * places.  The symbol timing comes from where the matches lie; a caller reads the payload at symbol centres from there.  It sits on

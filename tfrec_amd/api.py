@@ -118,6 +118,7 @@ EXPORTS = (
     "tfrec_amd_load_streams", "tfrec_amd_enable_burst_envelope", "tfrec_amd_read_burst_envelopes",
     "tfrec_amd_enable_burst_clock", "tfrec_amd_read_burst_clocks",
     "tfrec_amd_enable_burst_track", "tfrec_amd_set_burst_track_centre", "tfrec_amd_read_burst_tracks",
+    "tfrec_amd_enable_burst_track_amplitude", "tfrec_amd_set_burst_track_level",
     "tfrec_amd_enable_burst_sync", "tfrec_amd_read_burst_syncs",
 )
 
@@ -224,6 +225,8 @@ def load_library(build: bool = True, experiments: bool = False, short_segments: 
     L.tfrec_amd_read_burst_clocks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
     L.tfrec_amd_enable_burst_track.argtypes = [C.c_void_p, C.c_int32]
     L.tfrec_amd_set_burst_track_centre.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.tfrec_amd_enable_burst_track_amplitude.argtypes = [C.c_void_p, C.c_int32]
+    L.tfrec_amd_set_burst_track_level.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tfrec_amd_read_burst_tracks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
                                               C.POINTER(C.c_uint64)]
     L.tfrec_amd_enable_burst_sync.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_uint32]
@@ -715,6 +718,29 @@ class Receiver:
         a, b = np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(v, dtype=np.int32)
         _check(self.L, self.L.tfrec_amd_set_burst_track_centre(self.h, a.ctypes.data if len(a) else None,
                                                                b.ctypes.data if len(a) else None, len(a)))
+
+    def enable_burst_track_amplitude(self, smooth: int):
+        """Turn the burst track on in amplitude mode (tfrec_amd_enable_burst_track_amplitude; enable_burst_track's rules, and
+        instead of it): a bit per captured sample, 1 where the sum of `smooth` (1 .. 16) powers |I| + |Q| lies above `smooth`
+        times the stream's level -- an on-off keyed burst's track.  read_burst_tracks returns the records and the bitmap."""
+        if not -2 ** 31 <= int(smooth) < 2 ** 31:  # (refused before ctypes could wrap a value into range)
+            raise TfrecAmdError(E_INVAL, "smooth outside its type")
+        _check(self.L, self.L.tfrec_amd_enable_burst_track_amplitude(self.h, int(smooth)))
+
+    def set_burst_track_level(self, streams, level):
+        """The listed streams' levels (tfrec_amd_set_burst_track_level): one value for all of them or one per listed stream,
+        0 .. 65535 in the trigger's unit, in force from the next submit on.  Not a restart."""
+        idx = [int(s) for s in streams]
+        if any(s < 0 or s >= self.n_streams for s in idx):  # (refused before int32 could wrap an index into range)
+            raise TfrecAmdError(E_INVAL, "stream index outside [0, %d)" % self.n_streams)
+        v = [int(level)] * len(idx) if np.ndim(level) == 0 else [int(x) for x in level]
+        if len(v) != len(idx):
+            raise ValueError("%d values for %d streams" % (len(v), len(idx)))
+        if any(abs(x) >= 2 ** 31 for x in v):
+            raise TfrecAmdError(E_INVAL, "level outside its type")
+        a, b = np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(v, dtype=np.int32)
+        _check(self.L, self.L.tfrec_amd_set_burst_track_level(self.h, a.ctypes.data if len(a) else None,
+                                                              b.ctypes.data if len(a) else None, len(a)))
 
     def read_burst_tracks(self, allow_overflow: bool = False):
         """The track of the OLDEST undrained submit (tfrec_amd_read_burst_tracks; call it before the drain that pops that submit)

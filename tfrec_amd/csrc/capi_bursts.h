@@ -1,5 +1,5 @@
 // tfrec_amd/csrc/capi_bursts.h -- the entry points of the five burst stages on the recorder's table: the meter, the
-// envelope (6r), the clock (6s), the track (6t, with its centres) and the sync (6u).  What they share comes first -- the enables'
+// envelope (6r), the clock (6s), the track (6t, with its centres; 6v, its amplitude mode, with its levels) and the sync (6u).  What they share comes first -- the enables'
 // preflight, the rebase of start_sample, the record-only reader and the record-plus-bitmap reader --, then each
 // stage's enable and read, which add their own argument checks and buffers.  Included by capi.hip, which lists what is where.
 #pragma once
@@ -171,6 +171,7 @@ int tfrec_amd_read_burst_clocks(tfrec_amd_ctx *c, tfrec_amd_clock *out, size_t c
 
 // ---- the track
 constexpr int kTrackCentreLimit = 192000;  // |hz| <= half the 384 kS/s channel rate
+constexpr int kTrackLevelLimit = 65535;    // the amplitude mode's level: the trigger's unit, |I| + |Q|
 
 // r = floor((8192 hz + 384000) / 768000) mod 4096, a true floor (|hz| <= 192000: the numerator stays inside 32 bits' worth of 64)
 static int32_t track_index(int32_t hz)
@@ -180,7 +181,8 @@ static int32_t track_index(int32_t hz)
 	return (int32_t)(q & 4095);
 }
 
-int tfrec_amd_enable_burst_track(tfrec_amd_ctx *c, int32_t smooth)
+// Both modes' enable: the frequency track (6t) or the amplitude track (6v), which differ in one kernel and in what idx holds
+static int enable_track(tfrec_amd_ctx *c, int32_t smooth, bool amplitude)
 {
 	if (!c)
 		return TFREC_AMD_E_INVAL;
@@ -205,9 +207,12 @@ int tfrec_amd_enable_burst_track(tfrec_amd_ctx *c, int32_t smooth)
 	HIPCHK(hipMemset(o.d_prior, 0, n * sizeof(uint32_t)));
 	o.idx.assign(n, 0);
 	o.smooth = smooth;
+	o.amplitude = amplitude;
 	o.on = guard.ok = true;
 	return TFREC_AMD_OK;
 }
+int tfrec_amd_enable_burst_track(tfrec_amd_ctx *c, int32_t smooth) { return enable_track(c, smooth, false); }
+int tfrec_amd_enable_burst_track_amplitude(tfrec_amd_ctx *c, int32_t smooth) { return enable_track(c, smooth, true); }
 
 int tfrec_amd_set_burst_track_centre(tfrec_amd_ctx *c, const int32_t *streams, const int32_t *hz, int n)
 {
@@ -215,6 +220,10 @@ int tfrec_amd_set_burst_track_centre(tfrec_amd_ctx *c, const int32_t *streams, c
 		return TFREC_AMD_E_INVAL;
 	if (!c->trk.on) {
 		snprintf(g_err, sizeof(g_err), "the burst track is off: call tfrec_amd_enable_burst_track before the first submit");
+		return TFREC_AMD_E_INVAL;
+	}
+	if (c->trk.amplitude) {
+		snprintf(g_err, sizeof(g_err), "the burst track is the amplitude's: it has levels (tfrec_amd_set_burst_track_level), no centres");
 		return TFREC_AMD_E_INVAL;
 	}
 	for (int i = 0; i < n; i++) {
@@ -227,6 +236,27 @@ int tfrec_amd_set_burst_track_centre(tfrec_amd_ctx *c, const int32_t *streams, c
 	TRY(check_live(c));
 	for (int i = 0; i < n; i++)
 		c->trk.idx[streams[i]] = track_index(hz[i]);
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_set_burst_track_level(tfrec_amd_ctx *c, const int32_t *streams, const int32_t *level, int n)
+{
+	if (!c || n < 0 || (n > 0 && (!streams || !level)))
+		return TFREC_AMD_E_INVAL;
+	if (!c->trk.on || !c->trk.amplitude) {
+		snprintf(g_err, sizeof(g_err), "the amplitude track is off: call tfrec_amd_enable_burst_track_amplitude before the first submit");
+		return TFREC_AMD_E_INVAL;
+	}
+	for (int i = 0; i < n; i++) {
+		TRY(check_stream(c, streams[i]));
+		if (level[i] < 0 || level[i] > kTrackLevelLimit) {
+			snprintf(g_err, sizeof(g_err), "the amplitude track's level %d outside [0, %d]", (int)level[i], kTrackLevelLimit);
+			return TFREC_AMD_E_INVAL;
+		}
+	}
+	TRY(check_live(c));
+	for (int i = 0; i < n; i++)
+		c->trk.idx[streams[i]] = level[i];
 	return TFREC_AMD_OK;
 }
 

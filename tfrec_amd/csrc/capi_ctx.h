@@ -97,8 +97,10 @@ struct RunRecords {
 };
 // tfrec_amd_enable_burst_track: L; every stream's centre index as the next submit uses it; per set the records
 // (RunRecords), the bitmap (ceil(max_samples / 32) words) and the submit's centre indices with their page-locked
-// source; per stream the carried last 16 pairs and chain position (track_carry_kernel)
+// source; per stream the carried last 16 pairs and chain position (track_carry_kernel).  amplitude: the track's other mode
+// (tfrec_amd_enable_burst_track_amplitude), in which idx, d_idx and h_idx hold every stream's level instead
 struct BurstTrack : RunRecords<tfrec_amd_track> {
+	bool amplitude = false;
 	int smooth = 0;
 	size_t n_words = 0;
 	std::vector<int32_t> idx;

@@ -270,7 +270,8 @@ static int launch_decin_front(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, si
 }
 
 // The burst track on the recorder's lane: the centre indices the submit runs with, staged like stage_tune's
-// (h_idx[set] is free: the set's previous submit, whose copy read it, has been drained), then its three kernels
+// (h_idx[set] is free: the set's previous submit, whose copy read it, has been drained), then its three kernels.  In amplitude
+// mode (6v) the staged values are the levels and the middle kernel is amplitude_kernel
 static int launch_track(tfrec_amd_ctx *c, int set, const FrontOut &out, const CaptureBufs &b)
 {
 	BurstTrack &o = c->trk;
@@ -278,7 +279,7 @@ static int launch_track(tfrec_amd_ctx *c, int set, const FrontOut &out, const Ca
 	HIPCHK(hipMemcpyAsync(o.d_idx[set], o.h_idx[set], o.idx.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->cap.lane.st));
 	const TrackBufs k = { .recs = o.d_recs[set], .words = o.d_words[set], .centre = o.d_idx[set], .carry = o.d_carry, .prior = o.d_prior,
 			      .smooth = o.smooth };
-	HIPCHK(launch_burst_track(c->cap.lane.st, out, b, k));
+	HIPCHK(o.amplitude ? launch_burst_track_amplitude(c->cap.lane.st, out, b, k) : launch_burst_track(c->cap.lane.st, out, b, k));
 	return TFREC_AMD_OK;
 }
 

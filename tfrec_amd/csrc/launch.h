@@ -99,6 +99,7 @@ hipError_t launch_burst_meter(hipStream_t st, const FrontOut &o, const CaptureBu
 hipError_t launch_burst_envelope(hipStream_t st, const FrontOut &o, const CaptureBufs &b, tfrec_amd_envelope *out);
 hipError_t launch_burst_clock(hipStream_t st, const FrontOut &o, const CaptureBufs &b, tfrec_amd_clock *out);
 hipError_t launch_burst_track(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);
+hipError_t launch_burst_track_amplitude(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);  // (k.centre: the levels)
 hipError_t launch_burst_sync(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const SyncBufs &k);
 hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, const SpectrumBufs &b);
 hipError_t launch_occupancy(hipStream_t st, const SpectrumBufs &b, uint32_t ratio, uint32_t rel, tfrec_amd_occupancy *recs, uint32_t *bits);

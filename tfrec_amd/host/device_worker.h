@@ -266,7 +266,17 @@ inline int device_worker::open_context()
 		call = "tfrec_amd_enable_burst_clock";
 		r = tfrec_amd_enable_burst_clock(ctx);
 	}
-	if (!r && job.tracking()) {  // -G: the track on the recorder's table, every stream about the one centre
+	if (!r && job.amplitude()) {  // -G -O: the track in amplitude mode, every stream at the one level
+		call = "tfrec_amd_enable_burst_track_amplitude";
+		r = tfrec_amd_enable_burst_track_amplitude(ctx, job.track_smooth());
+		if (!r && job.track_level) {
+			std::vector<int32_t> all(n), level(n, (int32_t)job.track_level);
+			for (size_t i = 0; i < n; i++)
+				all[i] = (int32_t)i;
+			call = "tfrec_amd_set_burst_track_level";
+			r = tfrec_amd_set_burst_track_level(ctx, all.data(), level.data(), (int)n);
+		}
+	} else if (!r && job.tracking()) {  // -G: the track on the recorder's table, every stream about the one centre
 		call = "tfrec_amd_enable_burst_track";
 		r = tfrec_amd_enable_burst_track(ctx, job.track_smooth());
 		if (!r && job.track_centre) {

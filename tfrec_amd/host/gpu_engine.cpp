@@ -499,14 +499,19 @@ int gpu_engine::run()
 				syncs.take(b.syncs, workers[d].plan[k], file_blocks, framed);
 				for (const sync_piece &x : framed) {
 					printf("%s\n", track_line(files[x.stream], x.trk, job.track_rate).c_str());
+					if (job.amplitude())  // -O: the burst's pulses behind its bits
+						printf("%s\n", pulses_line(files[x.stream], x.trk).c_str());
 					for (const sync_frame &f : sync_frames(x, job))
 						printf("%s\n", sync_line(files[x.stream], x, f).c_str());
 				}
 			} else if (job.tracking()) {  // -G: likewise, behind -C's lines of the batch
 				said.clear();
 				tracks.take(b.tracks, workers[d].plan[k], file_blocks, said);
-				for (const track_piece &x : said)
+				for (const track_piece &x : said) {
 					printf("%s\n", track_line(files[x.stream], x, job.track_rate).c_str());
+					if (job.amplitude())
+						printf("%s\n", pulses_line(files[x.stream], x).c_str());
+				}
 			}
 			if (job.occupancy()) {  // no replay: the channel list is the product
 				const unsigned long long first = occ.records;

@@ -227,6 +227,10 @@ public:
 		job.track_rate = rate;
 		job.track_centre = centre_hz;
 	}
+	// -O (with -G): the track is the amplitude's (tfrec_amd_enable_burst_track_amplitude), L as -G's, every stream at
+	// `level` (0 .. 65535, the trigger's unit); the centre is not used.  Behind each burst's bits line run() prints its pulses
+	// (job.h: track_pulses, pulses_line)
+	void set_track_level(long level) { job.track_level = level; }
 	// -Y (with -G): the burst sync (tfrec_amd_enable_burst_sync) on the track, at -G's rate: the sync word is the low
 	// n_bits of pattern, MSB first.  run() merges the sync records' chains and their match tracks beside the track's (job.h:
 	// sync_merger) and prints, behind each burst's bits line, in the order of their samples,

@@ -99,6 +99,7 @@ struct job_settings {
 	bool clock = false;            // set_clock
 	long track_rate = 0;           // set_track (0: none): the rate in bit/s, 1000 .. 96000
 	long track_centre = 0;         // ... and every stream's centre in Hz
+	long track_level = -1;         // set_track_level (-1: none): -O, the track is the amplitude's, every stream at this level, 0 .. 65535
 	int sync_bits = 0;             // set_sync (0: none): P, the sync word's bits, 8 .. 64
 	unsigned long long sync_pattern = 0;  // ... the word, in its low P bits
 	int sync_errors = 0;           // ... E
@@ -118,6 +119,7 @@ struct job_settings {
 	bool recorder() const { return capture || metering() || enveloping() || clocking() || tracking(); }  // the contexts enable the recorder: for -S, or as the meter's, the envelope's, the clock's or the track's table
 	bool tracking() const { return track_rate != 0; }  // -G (never with -s or -A)
 	bool syncing() const { return sync_bits != 0; }  // -Y (only with -G)
+	bool amplitude() const { return track_level >= 0; }  // -O (only with -G)
 	// -G's L: half a symbol, (384000 + rate) / (2 rate) held within 1 .. 16
 	int track_smooth() const { return (int)std::max(1L, std::min(16L, (384000 + track_rate) / (2 * track_rate))); }
 	bool metering() const { return meter && !occupancy(); }  // -M (under -A: in the scan, not in pass 1)
@@ -755,6 +757,47 @@ inline std::string track_line(const std::string &file, const track_piece &c, lon
 			nib = 2 * nib + (i + j < sy.size() ? sy[i + j] : 0);
 		s += "0123456789abcdef"[nib];
 	}
+	return s;
+}
+
+// ---- -O: the pulses of an amplitude track (include/tfrec_amd.h: "Amplitude track", Pulses, whose text is normative; tfrec_amd/track.py
+// restates both)
+constexpr size_t kPulsesListed = 64;  // the pulses a line lists
+
+// The maximal runs of equal value of the first min(last_over + 1, 2^20) samples of a merged track, less a leading and a trailing
+// run of zeros -> pulse, gap, pulse, ..., pulse in samples (empty: no pulse)
+inline std::vector<uint64_t> track_pulses(const track_piece &c)
+{
+	std::vector<uint64_t> out;
+	uint64_t n = c.last_over < 0 ? 0 : std::min<uint64_t>((uint64_t)c.last_over + 1, c.kept());
+	uint64_t k = 0;
+	while (k < n && !c.bit(k))
+		k++;
+	while (n > k && !c.bit(n - 1))
+		n--;
+	while (k < n) {
+		const bool w = c.bit(k);
+		uint64_t m = 1;
+		while (k + m < n && c.bit(k + m) == w)
+			m++;
+		out.push_back(m);
+		k += m;
+	}
+	return out;
+}
+
+// pulses <file> <start_sample> <n_samples> <burst_samples> <n_pulses>[+] <w0,g0,w1,...|->: the first 64 pulses with the gaps between
+// them; + when the track holds more
+inline std::string pulses_line(const std::string &file, const track_piece &c)
+{
+	const std::vector<uint64_t> w = track_pulses(c);
+	const size_t n = (w.size() + 1) / 2, shown = std::min(w.size(), 2 * kPulsesListed - 1);
+	std::string s = "pulses " + file + " " + std::to_string((long long)c.start_sample) + " " + std::to_string(c.n_samples) + " " +
+			std::to_string((long long)c.last_over + 1) + " " + std::to_string(std::min(n, kPulsesListed)) + (n > kPulsesListed ? "+" : "") + " ";
+	if (!shown)
+		return s + "-";
+	for (size_t i = 0; i < shown; i++)
+		s += (i ? "," : "") + std::to_string(w[i]);
 	return s;
 }
 

@@ -112,6 +112,13 @@
 // slicer, not a demodulator: no clock recovery, no matched filter; the golden TFA_1 and WHB scenes do not slice with it.  Works with
 // -M, -Q, -C, -S, -R, -n, -d and every input option; not with -X, -k, -K, -s or -A.  Nothing of it has been measured on real
 // recordings.
+// -O level (not in the reference; with -G rate, no centre): the track is the amplitude's (tfrec_amd_enable_burst_track_amplitude, DESIGN.md
+// 6v), for on-off keyed bursts: 1 where the sum of L powers |I| + |Q| lies above L times level (0 .. 65535, -t's unit; L: -G's).  The
+// bits line and -Y's frame lines are read off that track, and behind each bits line stdout gets
+//   pulses <file> <start_sample> <n_samples> <burst_samples> <n_pulses>[+] <w0,g0,w1,...|->
+// the widths in samples of the track's pulses and of the gaps between them ("-": no pulse; "+": more than the 64 pulses listed).
+// Works where -G works.  A level slicer with the level the user gives (half of -M's pwr_max is a place to start, not a tuned
+// default), not an AGC; nothing of it has been measured on real recordings.
 // -Y hex[,errors[,bytes[,both]]] (not in the reference; with -G): the burst sync (tfrec_amd_enable_burst_sync): the
 // sync word is the 2 .. 16 hex digits (8 .. 64 bits), MSB first; the track, read at -G's rate at symbol centres, may differ from it
 // in `errors` places (default 0, below half the bits); both = 1 accepts the complemented word too (default 0).  Behind each burst's
@@ -295,6 +302,8 @@ struct cli {
 	bool envelope = false;  // -Q
 	bool clock = false;  // -C
 	long track_rate = 0, track_centre = 0;  // -G (rate 0: not given)
+	bool track_centre_given = false;
+	long track_level = -1;  // -O (-1: not given)
 	int sync_bits = 0;  // -Y (0: not given): the word's bits, the word, errors, bytes, both
 	unsigned long long sync_pattern = 0;
 	long sync_errors = 0, sync_bytes = 8, sync_both = 0;
@@ -331,7 +340,7 @@ struct cli {
 
 static void usage()
 {
-	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-G rate[,centre_hz]] [-Y hex[,errors[,bytes[,both]]]] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
+	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-G rate[,centre_hz]] [-O level] [-Y hex[,errors[,bytes[,both]]]] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
 			"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
 			"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
 			"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
@@ -355,6 +364,10 @@ static void usage()
 			"              line 'bits <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->' per trigger window, MSB-first,\n"
 			"              1 above the centre (+: longer than the 2^20 samples kept); also with -M, -Q, -C, -S and -R; not with -X, -k, -K,\n"
 			"              -s or -A\n"
+			"  -O level    with -G r: read on-off keyed bursts: the track is 1 where the burst's amplitude (|I| + |Q|, -t's unit, smoothed as -G's)\n"
+			"              lies above level (0 .. 65535; a place to start: half of -M's pwr_max); behind each bits line a line 'pulses <file>\n"
+			"              <start_sample> <n_samples> <burst_samples> <n_pulses>[+] <w0,g0,w1,...|->', pulse and gap widths in samples (+: more\n"
+			"              than the 64 pulses listed); no centre with it; works where -G works\n"
 			"  -Y h[,e[,n[,b]]]  with -G: find the sync word h (2 .. 16 hex digits, MSB first) in every burst's track with at most e bit errors\n"
 			"              (default 0), b = 1: or its complement, and read the n bytes behind it (default 8) at symbol centres: a line 'frame <file>\n"
 			"              <start_sample> <sync_sample> <errors> <+|-> <n_bits> <hex|->' per match, behind the burst's bits line\n"
@@ -440,7 +453,7 @@ bool cli::parse_format(const char *arg)
 int cli::parse(int argc, char **argv)
 {
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCG:Y:k:K:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCG:O:Y:k:K:h")) != -1) {
 		switch (c) {
 		case 'M': meter = true; break;
 		case 'Q': envelope = true; break;
@@ -453,8 +466,15 @@ int cli::parse(int argc, char **argv)
 						"-192000 .. 192000 Hz\n", optarg);
 				return 1;
 			}
+			track_centre_given = comma != NULL;
 			break;
 		}
+		case 'O':
+			if (!parse_long(optarg, 0, 65535, track_level)) {
+				fprintf(stderr, "tfrec_gpu: bad -O '%s': want <level>, within 0 .. 65535 in -t's unit\n", optarg);
+				return 1;
+			}
+			break;
 		case 'Y': {
 			std::vector<std::string> part(1);
 			for (const char *q = optarg; *q; q++) {
@@ -671,6 +691,10 @@ int cli::check() const
 	}
 	if (clock && hexfile) {
 		fprintf(stderr, "tfrec_gpu: -C measures the bursts of -L files or of a capture (-R): not with -X\n");
+		return 1;
+	}
+	if (track_level >= 0 && (!track_rate || track_centre_given)) {
+		fprintf(stderr, "tfrec_gpu: bad -O: it reads the amplitude track at the rate of -G: give -G rate with it, without a centre\n");
 		return 1;
 	}
 	if (sync_bits && !track_rate) {
@@ -925,6 +949,8 @@ int cli::run()
 		e.set_clock();
 	if (track_rate)
 		e.set_track(track_rate, track_centre);
+	if (track_level >= 0)
+		e.set_track_level(track_level);
 	if (sync_bits)
 		e.set_sync(sync_pattern, sync_bits, (int)sync_errors, (int)sync_bytes, sync_both != 0);
 	if (keep_prefix)

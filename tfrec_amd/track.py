@@ -14,6 +14,12 @@ real recordings.
   chains             the chains of a sequence of submits (burst.chains' walk);
   slice_bits         a track and a rate -> the symbols;  line: tfrec_gpu -G's output line;
   device_bytes, pinned_bytes   what tfrec_amd_enable_burst_track adds to tfrec_amd_get_memory.
+
+The track's amplitude mode (tfrec_amd_enable_burst_track_amplitude, the header's "Amplitude track") -- the same
+records, bitmap and state, the bit 1 where the sum of L powers |I| + |Q| lies above L times the stream's level:
+
+  amplitude_tracks, amplitude_tracks_bruteforce   tracks' and tracks_bruteforce's counterparts, a level per stream for the centre;
+  pulses             a merged track -> the widths pulse, gap, ..., pulse;  pulses_line: tfrec_gpu -O's output line.
 """
 from __future__ import annotations
 
@@ -158,6 +164,104 @@ def tracks_bruteforce(dec, mask_or_thresh, runs, smooth, centres=None, state=Non
         out[e] = o
         tr.append(np.array(t, dtype=np.uint8))
     return out, _pack(out, tr, max_samples), _next_state(dec, runs, state, base)
+
+
+LEVEL_MAX = 65535
+PULSES_LISTED = 64  # the pulses tfrec_gpu -O lists
+
+
+def _levels(levels, n_streams):
+    lv = [0] * n_streams if levels is None else [int(x) for x in levels]
+    assert len(lv) == n_streams and all(0 <= x <= LEVEL_MAX for x in lv)
+    return lv
+
+
+def amplitude_tracks(dec, mask_or_thresh, runs, smooth, levels=None, state=None, base=None, max_samples=None):
+    """One submit of the amplitude track: tracks' inputs, outputs and carried state, with levels[s] (0 .. 65535, default 0), the
+    stream's level, in the centres' place."""
+    L = int(smooth)
+    assert 1 <= L <= AHEAD
+    state = fresh_state(len(dec)) if state is None else state
+    lv = _levels(levels, len(dec))
+    out = np.zeros(len(runs), dtype=TRACK_DTYPE)
+    tr = []
+    for e, r in enumerate(runs):
+        s, a, n, cont = _window(dec, r, base)
+        z = np.concatenate([np.asarray(state["carry"][s], dtype=np.int64).reshape(AHEAD, 2), burst._pairs(dec[s]).astype(np.int64)])
+        cf = a - (int(state["prior"][s]) if cont else 0)  # the chain's first sample, submit-relative
+        m = np.arange(a - (AHEAD - 1), a + n)  # every sample a power may be needed of; z's index is m + 16
+        p = np.where(m >= cf, np.abs(z[m + AHEAD, 0]) + np.abs(z[m + AHEAD, 1]), 0)  # (<= 65536)
+        cs = np.concatenate([[0], np.cumsum(p)])
+        q = np.arange(n) + AHEAD  # sample a + k is p[k + 15]: the sum of p[k + 16 - L .. k + 15]
+        t = (cs[q] - cs[q - L]) > L * lv[s]
+        o = _copied(r)
+        over = envelope._over(burst._pairs(dec[s]).astype(np.int64), mask_or_thresh[s])[a:a + n]
+        idx = np.flatnonzero(over)
+        o["last_over"] = int(idx[-1]) if len(idx) else -1
+        o["n_ones"] = int(np.count_nonzero(t))
+        out[e] = o
+        tr.append(t.astype(np.uint8))
+    return out, _pack(out, tr, max_samples), _next_state(dec, runs, state, base)
+
+
+def amplitude_tracks_bruteforce(dec, mask_or_thresh, runs, smooth, levels=None, state=None, base=None, max_samples=None):
+    """The same, one sample at a time in Python integers, as the header words it: t[k] = 1 iff the sum of p[k - i] over
+    0 <= i < L with k - i >= -prior is greater than L * level."""
+    L = int(smooth)
+    state = fresh_state(len(dec)) if state is None else state
+    lv = _levels(levels, len(dec))
+    out = np.zeros(len(runs), dtype=TRACK_DTYPE)
+    tr = []
+    for e, r in enumerate(runs):
+        s, a, n, cont = _window(dec, r, base)
+        row = burst._pairs(dec[s]).tolist()
+        ahead = np.asarray(state["carry"][s]).reshape(AHEAD, 2).tolist()
+        prior = int(state["prior"][s]) if cont else 0
+        over = envelope._over(burst._pairs(dec[s]).astype(np.int64), mask_or_thresh[s]).tolist()
+
+        def p(k):  # run-relative; k < 0 only in a CONTINUES run, whose a == 0
+            i, q = row[a + k] if a + k >= 0 else ahead[AHEAD + a + k]
+            return abs(i) + abs(q)
+
+        t, last = [], -1
+        for k in range(n):
+            total = 0
+            for i in range(L):
+                if k - i >= -prior:
+                    total += p(k - i)
+            t.append(1 if total > L * lv[s] else 0)
+            if over[a + k]:
+                last = k
+        o = _copied(r)
+        o["last_over"], o["n_ones"] = last, sum(t)
+        out[e] = o
+        tr.append(np.array(t, dtype=np.uint8))
+    return out, _pack(out, tr, max_samples), _next_state(dec, runs, state, base)
+
+
+def pulses(bits) -> list:
+    """The header's Pulses: the maximal runs of equal value of a track (already cut to its first last_over + 1 samples), less a
+    leading and a trailing run of zeros -> [pulse, gap, pulse, ..., pulse] in samples ([]: no pulse)."""
+    b = np.asarray(bits, dtype=np.uint8)
+    on = np.flatnonzero(b)
+    if len(on) == 0:
+        return []
+    b = b[on[0]:on[-1] + 1]
+    edges = np.flatnonzero(np.diff(b)) + 1
+    return np.diff(np.concatenate([[0], edges, [len(b)]])).tolist()
+
+
+def pulses_line(name: str, piece) -> str:
+    """tfrec_gpu -O: pulses <file> <start_sample> <n_samples> <burst_samples> <n_pulses>[+] <w0,g0,w1,...|->: the pulses of the
+    track's first burst_samples = last_over + 1 samples, of the first 2^20 at most; the first 64 pulses are listed (with the gaps
+    between them), a + behind n_pulses marks more."""
+    rec = piece.rec
+    length = int(rec["last_over"]) + 1
+    w = pulses(piece.bits[:KEEP][:length])
+    n = (len(w) + 1) // 2
+    shown = w[:2 * PULSES_LISTED - 1]
+    return "pulses %s %d %d %d %d%s %s" % (name, int(rec["start_sample"]), int(rec["n_samples"]), length, min(n, PULSES_LISTED),
+                                           "+" if n > PULSES_LISTED else "", ",".join("%d" % x for x in shown) if shown else "-")
 
 
 def bits_of(rec, words):
