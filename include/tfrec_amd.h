@@ -1002,6 +1002,65 @@ int tfrec_amd_enable_burst_track_amplitude(tfrec_amd_ctx *ctx, int32_t smooth);
  * set; a poisoned context: TFREC_AMD_E_STATE.  tfrec_amd_set_burst_track_centre on an amplitude context is TFREC_AMD_E_INVAL. */
 int tfrec_amd_set_burst_track_level(tfrec_amd_ctx *ctx, const int32_t *streams, const int32_t *level, int n);
 
+/* Auto-centre track (tfrec_amd_enable_burst_track_auto): a third MODE of the burst track, for a stream that holds the
+ * bursts of several transmitters, each with its own carrier offset: every chain is tracked about a centre measured on its own first
+ * samples, in the same submit, ahead of the track.  A context has the frequency track, the amplitude track or this one.  The record
+ * (tfrec_amd_track), the bitmap, last_over, n_ones, the 16 carried pairs and prior, the merging rules, the overflow prefixes and
+ * tfrec_amd_read_burst_tracks are exactly the frequency track's; so are the Slicing and everything the burst sync makes of a track.
+ * Only the table index r that forms v[k] = crs[k] C[r] - dot[k] S[r] differs: it is the ENTRY's, not the stream's.  There is no
+ * reference counterpart: this text is normative, tfrec_amd/track.py (head_centres, auto_tracks) restates it.  Exact integers only.
+ *   Settings: fixed at enable: smooth = L, 1 .. 16, and head = K, 64 .. 4096 (K = 64 counts 63 products at the most and never
+ *             measures).  Per stream the set centre hz, |hz| <= 192000, default 0 (tfrec_amd_set_burst_track_centre; in force from
+ *             the next submit on): the FALLBACK.
+ *   Counted:  for an entry without TFREC_AMD_RUN_CONTINUES, submit-relative start a and n samples, the products dot[k], crs[k] of the
+ *             frequency track for 1 <= k < min(n, K); product k is counted iff over[a + k] and over[a + k - 1], over being the
+ *             stream's final trigger mask, the one last_over is taken from.  Both pairs are then over a threshold >= 0, so neither is
+ *             (0, 0) and the product is not.  The head is read from the decimated samples, not from the pool: max_samples does not
+ *             matter to it.
+ *   Centre:   P = the number of counted products, hist[j] their count in bin j of tfrec_amd_burst's 64 bins of 6 kHz.  If P >= 64, bin
+ *             j is occupied iff hist[j] >= floor((P + 15) / 16); lo and hi are the smallest and the largest SIGNED index (j for
+ *             j < 32, j - 64 otherwise) of an occupied bin.  With an occupied bin: centre_hz = 3000 (lo + hi), deviation_hz =
+ *             3000 (hi - lo), source MEASURED.  With P < 64, or with no occupied bin (products spread so thinly that no bin holds
+ *             a sixteenth of them: noise): centre_hz = the stream's set centre, deviation_hz = 0, source FALLBACK.  n_counted = P in
+ *             both.  r = floor((8192 centre_hz + 384000) / 768000) mod 4096, as for the frequency track.
+ *   Chains:   an entry with TFREC_AMD_RUN_CONTINUES takes r and centre_hz of the OPEN entry that ended the submit before: source
+ *             INHERITED, n_counted = deviation_hz = 0.  Where that entry had no record (it lay beyond max_runs) the set centre is
+ *             used, source FALLBACK.  A restart needs nothing: the run behind it does not CONTINUE and is measured as a chain's
+ *             first piece.  tfrec_amd_save_streams does not carry the centre.
+ *   Limits:   the chain's first piece decides for the whole chain.  The merged track therefore does not depend on the cut whenever
+ *             the chain's first piece holds at least min(n_chain, K) samples; a chain that begins within K samples of a submit's
+ *             end is centred on what its first piece has (fewer than 65 samples: the fallback).  The histogram is not circular: a
+ *             burst whose |centre| + deviation approaches 192 kHz wraps around and reads wrongly.  Nothing of it has been measured on
+ *             real recordings.
+ *   Cutting:  merging a chain keeps the first piece's centre record and gives it the merged flags and n_samples of tfrec_amd_track. */
+#define TFREC_AMD_CENTRE_MEASURED 0u
+#define TFREC_AMD_CENTRE_FALLBACK 1u
+#define TFREC_AMD_CENTRE_INHERITED 2u
+typedef struct {            /* 48 bytes */
+	uint32_t stream;        /* these five: copied from the table entry */
+	uint32_t flags;
+	int64_t  start_sample;
+	uint32_t n_samples;
+	int32_t  thresh;
+	uint32_t n_counted;     /* P */
+	uint32_t source;        /* TFREC_AMD_CENTRE_* */
+	int32_t  centre_hz;     /* the one the entry's track is formed about */
+	int32_t  deviation_hz;  /* of a measured centre, else 0 */
+	int32_t  index;         /* r */
+	uint32_t reserved;      /* 0 */
+} tfrec_amd_track_centre;
+/* Turn the track on in auto-centre mode: tfrec_amd_enable_burst_track's rules and errors, and head outside 64 .. 4096:
+ * TFREC_AMD_E_INVAL; a context whose track is on already, in any mode, refuses all three enables with TFREC_AMD_E_INVAL.  Memory: the
+ * frequency track's (the per-set values staged per stream are the set centres in Hz: the same bytes), and per FIFO set max_runs * 48
+ * bytes, per stream the carried index and centre (8 bytes).  tfrec_amd_set_burst_track_centre sets the fallback;
+ * tfrec_amd_set_burst_track_level is TFREC_AMD_E_INVAL.  tfrec_amd_enable_burst_sync works on this mode too.  Six launches on the
+ * recorder's stream: both records' inits, the head's histogram and resolve, the track about every entry's index, the two carries. */
+int tfrec_amd_enable_burst_track_auto(tfrec_amd_ctx *ctx, int32_t smooth, int32_t head);
+/* out[i] = the centre record of entry i of the table tfrec_amd_read_captures returns for the same submit: tfrec_amd_read_bursts'
+ * conventions, counts, prefix on TFREC_AMD_E_OVERFLOW (records for every entry below min(n_runs, max_runs), whatever max_samples
+ * is) and errors; a context whose track is off or in another mode: TFREC_AMD_E_INVAL. */
+int tfrec_amd_read_burst_track_centres(tfrec_amd_ctx *ctx, tfrec_amd_track_centre *out, size_t cap_runs, uint32_t *n_runs);
+
 /* Burst sync (tfrec_amd_enable_burst_sync): for every run of the recorder's table WHERE A FRAME BEGINS -- one bit per
  * captured sample, 1 where the burst track, read at P symbol centres that end at the sample, is a known sync word but for at most E
  * places.  The symbol timing comes from where the matches lie; a caller reads the payload at symbol centres from there.  It sits on

@@ -119,6 +119,7 @@ EXPORTS = (
     "tfrec_amd_enable_burst_clock", "tfrec_amd_read_burst_clocks",
     "tfrec_amd_enable_burst_track", "tfrec_amd_set_burst_track_centre", "tfrec_amd_read_burst_tracks",
     "tfrec_amd_enable_burst_track_amplitude", "tfrec_amd_set_burst_track_level",
+    "tfrec_amd_enable_burst_track_auto", "tfrec_amd_read_burst_track_centres",
     "tfrec_amd_enable_burst_sync", "tfrec_amd_read_burst_syncs",
 )
 
@@ -227,6 +228,8 @@ def load_library(build: bool = True, experiments: bool = False, short_segments: 
     L.tfrec_amd_set_burst_track_centre.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tfrec_amd_enable_burst_track_amplitude.argtypes = [C.c_void_p, C.c_int32]
     L.tfrec_amd_set_burst_track_level.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.tfrec_amd_enable_burst_track_auto.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    L.tfrec_amd_read_burst_track_centres.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
     L.tfrec_amd_read_burst_tracks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
                                               C.POINTER(C.c_uint64)]
     L.tfrec_amd_enable_burst_sync.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_uint32]
@@ -741,6 +744,23 @@ class Receiver:
         a, b = np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(v, dtype=np.int32)
         _check(self.L, self.L.tfrec_amd_set_burst_track_level(self.h, a.ctypes.data if len(a) else None,
                                                               b.ctypes.data if len(a) else None, len(a)))
+
+    def enable_burst_track_auto(self, smooth: int, head: int = 1024):
+        """Turn the burst track on in auto-centre mode (tfrec_amd_enable_burst_track_auto; enable_burst_track's rules, and instead
+        of it): every chain is tracked about a centre measured on the first `head` (64 .. 4096) samples of its first piece;
+        set_burst_track_centre sets the fallback.  read_burst_tracks returns the records and the bitmap,
+        read_burst_track_centres every entry's centre."""
+        if not (-2 ** 31 <= int(smooth) < 2 ** 31 and -2 ** 31 <= int(head) < 2 ** 31):  # (refused before ctypes could wrap a value into range)
+            raise TfrecAmdError(E_INVAL, "smooth or head outside its type")
+        _check(self.L, self.L.tfrec_amd_enable_burst_track_auto(self.h, int(smooth), int(head)))
+
+    def read_burst_track_centres(self, allow_overflow: bool = False) -> np.ndarray:
+        """The centre records of the OLDEST undrained submit (tfrec_amd_read_burst_track_centres; call it before the drain that
+        pops that submit) -> a CENTRE_DTYPE array, one record per entry of that submit's run table (track.py).  They do not depend
+        on the pool: a table with more than max_runs entries (E_OVERFLOW) raises unless allow_overflow, then its first max_runs
+        records are returned; centre_total holds the submit's true run count."""
+        from .track import CENTRE_DTYPE
+        return self._read_run_records(self.L.tfrec_amd_read_burst_track_centres, CENTRE_DTYPE, "centre_total", allow_overflow)
 
     def read_burst_tracks(self, allow_overflow: bool = False):
         """The track of the OLDEST undrained submit (tfrec_amd_read_burst_tracks; call it before the drain that pops that submit)

@@ -1,5 +1,5 @@
 // tfrec_amd/csrc/capi_bursts.h -- the entry points of the five burst stages on the recorder's table: the meter, the
-// envelope (6r), the clock (6s), the track (6t, with its centres; 6v, its amplitude mode, with its levels) and the sync (6u).  What they share comes first -- the enables'
+// envelope (6r), the clock (6s), the track (6t, with its centres; 6v, its amplitude mode, with its levels; 6w, its auto-centre mode, with its centre records) and the sync (6u).  What they share comes first -- the enables'
 // preflight, the rebase of start_sample, the record-only reader and the record-plus-bitmap reader --, then each
 // stage's enable and read, which add their own argument checks and buffers.  Included by capi.hip, which lists what is where.
 #pragma once
@@ -12,6 +12,7 @@ constexpr StageNames kMeterNames = { "burst meter", "burst", "tfrec_amd_enable_b
 constexpr StageNames kEnvelopeNames = { "burst envelope", "envelope", "tfrec_amd_enable_burst_envelope" };
 constexpr StageNames kClockNames = { "burst clock", "clock", "tfrec_amd_enable_burst_clock" };
 constexpr StageNames kTrackNames = { "burst track", "track", "tfrec_amd_enable_burst_track" };
+constexpr StageNames kCentreNames = { "auto-centre track", "centre", "tfrec_amd_enable_burst_track_auto" };
 constexpr StageNames kSyncNames = { "burst sync", "sync", "tfrec_amd_enable_burst_sync" };
 
 // What every enable checks behind its own arguments, in this order: what the stage works on (`needs`, switched on by
@@ -181,13 +182,20 @@ static int32_t track_index(int32_t hz)
 	return (int32_t)(q & 4095);
 }
 
-// Both modes' enable: the frequency track (6t) or the amplitude track (6v), which differ in one kernel and in what idx holds
-static int enable_track(tfrec_amd_ctx *c, int32_t smooth, bool amplitude)
+constexpr int kTrackHeadMin = 64, kTrackHeadMax = 4096;  // the auto-centre mode's K
+
+// Every mode's enable: the frequency track (6t) or the amplitude track (6v), which differ in one kernel and in what idx holds, or
+// the auto-centre track (6w: head = K != 0), whose idx holds the set centres in Hz and which adds its records and its carry
+static int enable_track(tfrec_amd_ctx *c, int32_t smooth, bool amplitude, int32_t head = 0)
 {
 	if (!c)
 		return TFREC_AMD_E_INVAL;
 	if (smooth < 1 || smooth > 16) {
 		snprintf(g_err, sizeof(g_err), "the burst track's smooth is within [1, 16]");
+		return TFREC_AMD_E_INVAL;
+	}
+	if (head && (head < kTrackHeadMin || head > kTrackHeadMax)) {
+		snprintf(g_err, sizeof(g_err), "the auto-centre track's head is within [%d, %d]", kTrackHeadMin, kTrackHeadMax);
 		return TFREC_AMD_E_INVAL;
 	}
 	TRY(recorder_preflight(c, kTrackNames, c->trk.on));
@@ -205,6 +213,14 @@ static int enable_track(tfrec_amd_ctx *c, int32_t smooth, bool amplitude)
 	TRY(own_device(c, o.d_prior, n * sizeof(uint32_t)));
 	HIPCHK(hipMemset(o.d_carry, 0, n * 16 * sizeof(uint32_t)));  // (never used before a submit has written them: no first submit CONTINUES)
 	HIPCHK(hipMemset(o.d_prior, 0, n * sizeof(uint32_t)));
+	if (head) {
+		for (int k = 0; k < kSets; k++)
+			TRY(own_device(c, o.cen.d_recs[k], (size_t)c->cap.max_runs * sizeof(tfrec_amd_track_centre)));
+		TRY(own_device(c, o.d_ccarry, n * sizeof(int2)));
+		HIPCHK(hipMemset(o.d_ccarry, 0xff, n * sizeof(int2)));  // index -1: nothing carried
+		o.head = head;
+		o.cen.on = true;
+	}
 	o.idx.assign(n, 0);
 	o.smooth = smooth;
 	o.amplitude = amplitude;
@@ -213,6 +229,14 @@ static int enable_track(tfrec_amd_ctx *c, int32_t smooth, bool amplitude)
 }
 int tfrec_amd_enable_burst_track(tfrec_amd_ctx *c, int32_t smooth) { return enable_track(c, smooth, false); }
 int tfrec_amd_enable_burst_track_amplitude(tfrec_amd_ctx *c, int32_t smooth) { return enable_track(c, smooth, true); }
+int tfrec_amd_enable_burst_track_auto(tfrec_amd_ctx *c, int32_t smooth, int32_t head)
+{
+	if (c && !head) {  // (0 is enable_track's "no head")
+		snprintf(g_err, sizeof(g_err), "the auto-centre track's head is within [%d, %d]", kTrackHeadMin, kTrackHeadMax);
+		return TFREC_AMD_E_INVAL;
+	}
+	return enable_track(c, smooth, false, head);
+}
 
 int tfrec_amd_set_burst_track_centre(tfrec_amd_ctx *c, const int32_t *streams, const int32_t *hz, int n)
 {
@@ -235,7 +259,7 @@ int tfrec_amd_set_burst_track_centre(tfrec_amd_ctx *c, const int32_t *streams, c
 	}
 	TRY(check_live(c));
 	for (int i = 0; i < n; i++)
-		c->trk.idx[streams[i]] = track_index(hz[i]);
+		c->trk.idx[streams[i]] = c->trk.cen.on ? hz[i] : track_index(hz[i]);  // (auto-centre mode: the fallback, in Hz)
 	return TFREC_AMD_OK;
 }
 
@@ -264,6 +288,11 @@ int tfrec_amd_read_burst_tracks(tfrec_amd_ctx *c, tfrec_amd_track *out, size_t c
 				uint64_t *n_words)
 {
 	return c ? read_run_bitmaps(c, c->trk, c->trk.d_words, kTrackNames, out, cap_runs, n_runs, words, cap_words, n_words) : TFREC_AMD_E_INVAL;
+}
+
+int tfrec_amd_read_burst_track_centres(tfrec_amd_ctx *c, tfrec_amd_track_centre *out, size_t cap_runs, uint32_t *n_runs)
+{
+	return c ? read_run_records(c, c->trk.cen, kCentreNames, out, cap_runs, n_runs) : TFREC_AMD_E_INVAL;
 }
 
 // ---- the sync

@@ -38,13 +38,16 @@ struct CaptureBufs {
 	unsigned long long max_samples;
 };
 // The burst track's buffers (track.h): the set's records, bitmap and centre indices, the carried 16 pairs and chain position of every
-// stream, and L
+// stream, and L; in auto-centre mode (centre.h) also the set's centre records, every stream's carried index and centre, and K
 struct TrackBufs {
 	tfrec_amd_track *recs;
 	uint32_t *words;
 	const int32_t *centre;
 	uint32_t *carry, *prior;
 	int smooth;
+	tfrec_amd_track_centre *cen;
+	int2 *ccarry;
+	int head;
 };
 // The burst sync's buffers and settings (sync.h): the set's records and match bitmap, the set's track bitmap, the carried 64 words
 // of track bits and H of every stream
@@ -100,6 +103,7 @@ hipError_t launch_burst_envelope(hipStream_t st, const FrontOut &o, const Captur
 hipError_t launch_burst_clock(hipStream_t st, const FrontOut &o, const CaptureBufs &b, tfrec_amd_clock *out);
 hipError_t launch_burst_track(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);
 hipError_t launch_burst_track_amplitude(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);  // (k.centre: the levels)
+hipError_t launch_burst_track_auto(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);  // (k.centre: the set centres in Hz)
 hipError_t launch_burst_sync(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const SyncBufs &k);
 hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, const SpectrumBufs &b);
 hipError_t launch_occupancy(hipStream_t st, const SpectrumBufs &b, uint32_t ratio, uint32_t rel, tfrec_amd_occupancy *recs, uint32_t *bits);

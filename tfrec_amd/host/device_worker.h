@@ -276,6 +276,9 @@ inline int device_worker::open_context()
 			call = "tfrec_amd_set_burst_track_level";
 			r = tfrec_amd_set_burst_track_level(ctx, all.data(), level.data(), (int)n);
 		}
+	} else if (!r && job.centring()) {  // -G rate,auto: the track in auto-centre mode, the fallback centre 0
+		call = "tfrec_amd_enable_burst_track_auto";
+		r = tfrec_amd_enable_burst_track_auto(ctx, job.track_smooth(), kTrackAutoHead);
 	} else if (!r && job.tracking()) {  // -G: the track on the recorder's table, every stream about the one centre
 		call = "tfrec_amd_enable_burst_track";
 		r = tfrec_amd_enable_burst_track(ctx, job.track_smooth());
@@ -591,7 +594,8 @@ inline int device_worker::read_run_bitmaps(int (*reader)(tfrec_amd_ctx *, R *, s
 
 // -G: the batch's track records, each with its bits out of the batch's bitmap.  stream -> file and the file-end cut as above; a
 // record that reaches over its file's end is cut there and is OPEN (job.h: track_take).  -Y: the sync records of the same entries
-// with them, each with its match track (job.h: sync_take), in b.syncs in place of b.tracks
+// with them, each with its match track (job.h: sync_take), in b.syncs in place of b.tracks.  -G rate,auto: every track piece with
+// the centre record of its entry (job.h: centre_take)
 inline int device_worker::read_tracks(size_t k, batch_result &b)
 {
 	std::vector<tfrec_amd_track> recs;
@@ -601,6 +605,21 @@ inline int device_worker::read_tracks(size_t k, batch_result &b)
 		fprintf(stderr, "tfrec_amd: device %d batch %zu: more runs or pairs than the recorder holds, the track is incomplete\n", device, k);
 	if (r)
 		return r;
+	std::vector<tfrec_amd_track_centre> crecs;
+	if (job.centring()) {
+		uint32_t nr = 0;
+		r = tfrec_amd_read_burst_track_centres(ctx, NULL, 0, &nr);  // (the count: E_INVAL for want of room)
+		if (r == TFREC_AMD_E_INVAL && nr) {
+			crecs.resize(nr);
+			r = tfrec_amd_read_burst_track_centres(ctx, crecs.data(), crecs.size(), &nr);
+		}
+		if (r)
+			return r;
+		if (crecs.size() != recs.size()) {
+			fprintf(stderr, "tfrec_amd: device %d batch %zu: %zu centre records beside %zu track records\n", device, k, crecs.size(), recs.size());
+			return TFREC_AMD_E_STATE;
+		}
+	}
 	std::vector<tfrec_amd_burst_sync> srecs;
 	std::vector<uint32_t> swords;
 	if (job.syncing()) {
@@ -617,10 +636,13 @@ inline int device_worker::read_tracks(size_t k, batch_result &b)
 			continue;
 		const uint32_t n = x.n_samples;  // (track_take is given the device's record and what the cut keeps of it)
 		x.n_samples = recs[q].n_samples;
+		track_piece t = track_take(x, words.data(), n);
+		if (job.centring())
+			centre_take(t, crecs[q]);
 		if (job.syncing())
-			b.syncs.push_back(sync_take(srecs[q], swords.data(), track_take(x, words.data(), n)));
+			b.syncs.push_back(sync_take(srecs[q], swords.data(), t));
 		else
-			b.tracks.push_back(track_take(x, words.data(), n));
+			b.tracks.push_back(std::move(t));
 	}
 	return 0;
 }

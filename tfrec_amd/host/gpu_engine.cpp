@@ -498,6 +498,8 @@ int gpu_engine::run()
 				framed.clear();
 				syncs.take(b.syncs, workers[d].plan[k], file_blocks, framed);
 				for (const sync_piece &x : framed) {
+					if (job.centring())  // -G rate,auto: the burst's centre ahead of its bits
+						printf("%s\n", centre_line(files[x.stream], x.trk).c_str());
 					printf("%s\n", track_line(files[x.stream], x.trk, job.track_rate).c_str());
 					if (job.amplitude())  // -O: the burst's pulses behind its bits
 						printf("%s\n", pulses_line(files[x.stream], x.trk).c_str());
@@ -508,6 +510,8 @@ int gpu_engine::run()
 				said.clear();
 				tracks.take(b.tracks, workers[d].plan[k], file_blocks, said);
 				for (const track_piece &x : said) {
+					if (job.centring())
+						printf("%s\n", centre_line(files[x.stream], x).c_str());
 					printf("%s\n", track_line(files[x.stream], x, job.track_rate).c_str());
 					if (job.amplitude())
 						printf("%s\n", pulses_line(files[x.stream], x).c_str());

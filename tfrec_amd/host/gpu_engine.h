@@ -231,6 +231,9 @@ public:
 	// `level` (0 .. 65535, the trigger's unit); the centre is not used.  Behind each burst's bits line run() prints its pulses
 	// (job.h: track_pulses, pulses_line)
 	void set_track_level(long level) { job.track_level = level; }
+	// -G rate,auto (with set_track(rate, 0)): the track is the auto-centre's (tfrec_amd_enable_burst_track_auto), L as -G's,
+	// K = 1024, the fallback centre 0.  Ahead of each burst's bits line run() prints its centre (job.h: centre_take, centre_line)
+	void set_track_auto() { job.track_auto = true; }
 	// -Y (with -G): the burst sync (tfrec_amd_enable_burst_sync) on the track, at -G's rate: the sync word is the low
 	// n_bits of pattern, MSB first.  run() merges the sync records' chains and their match tracks beside the track's (job.h:
 	// sync_merger) and prints, behind each burst's bits line, in the order of their samples,

@@ -100,6 +100,7 @@ struct job_settings {
 	long track_rate = 0;           // set_track (0: none): the rate in bit/s, 1000 .. 96000
 	long track_centre = 0;         // ... and every stream's centre in Hz
 	long track_level = -1;         // set_track_level (-1: none): -O, the track is the amplitude's, every stream at this level, 0 .. 65535
+	bool track_auto = false;       // set_track_auto: -G rate,auto, every chain about its own measured centre (K = kTrackAutoHead)
 	int sync_bits = 0;             // set_sync (0: none): P, the sync word's bits, 8 .. 64
 	unsigned long long sync_pattern = 0;  // ... the word, in its low P bits
 	int sync_errors = 0;           // ... E
@@ -120,6 +121,7 @@ struct job_settings {
 	bool tracking() const { return track_rate != 0; }  // -G (never with -s or -A)
 	bool syncing() const { return sync_bits != 0; }  // -Y (only with -G)
 	bool amplitude() const { return track_level >= 0; }  // -O (only with -G)
+	bool centring() const { return track_auto; }  // -G rate,auto (never with -O)
 	// -G's L: half a symbol, (384000 + rate) / (2 rate) held within 1 .. 16
 	int track_smooth() const { return (int)std::max(1L, std::min(16L, (384000 + track_rate) / (2 * track_rate))); }
 	bool metering() const { return meter && !occupancy(); }  // -M (under -A: in the scan, not in pass 1)
@@ -393,9 +395,12 @@ inline bool cut_at_file_end(R &x, const std::vector<int> &file, const std::vecto
 	return true;
 }
 
-// A record with its track: bit k of the track is bit k & 31 of bits[k >> 5], for k < min(n_samples, 2^20)
+// A record with its track: bit k of the track is bit k & 31 of bits[k >> 5], for k < min(n_samples, 2^20).  -G rate,auto: with
+// the centre record of the same table entry (centred; centre_take)
 struct track_piece : tfrec_amd_track {
 	std::vector<uint32_t> bits;
+	bool centred = false;
+	tfrec_amd_track_centre cen = {};
 	uint64_t kept() const { return std::min<uint64_t>(n_samples, kTrackKeep); }
 	bool bit(uint64_t k) const { return (bits[k >> 5] >> (k & 31)) & 1u; }
 };
@@ -758,6 +763,28 @@ inline std::string track_line(const std::string &file, const track_piece &c, lon
 		s += "0123456789abcdef"[nib];
 	}
 	return s;
+}
+
+// ---- -G rate,auto: the centre record of a track piece (include/tfrec_amd.h: "Auto-centre track", tfrec_amd_track_centre, whose text is
+// normative; tfrec_amd/track.py restates the merge and the line)
+constexpr int kTrackAutoHead = 1024;  // -G rate,auto's K
+
+// The entry's centre record joins its track piece.  Merging a chain (track_add) leaves it alone: the chain's record is the first
+// piece's, and its flags and n_samples are the merged track piece's
+inline void centre_take(track_piece &p, const tfrec_amd_track_centre &c)
+{
+	p.cen = c;
+	p.centred = true;
+}
+
+// centre <file> <start_sample> <n_samples> <n_counted> <centre_hz> <deviation_hz|-> <m|f|i>: the deviation only of a measured centre;
+// i: a chain whose first piece the output does not hold
+inline std::string centre_line(const std::string &file, const track_piece &c)
+{
+	const uint32_t src = c.cen.source <= TFREC_AMD_CENTRE_INHERITED ? c.cen.source : TFREC_AMD_CENTRE_INHERITED;
+	return "centre " + file + " " + std::to_string((long long)c.start_sample) + " " + std::to_string(c.n_samples) + " " +
+	       std::to_string(c.cen.n_counted) + " " + std::to_string(c.cen.centre_hz) + " " +
+	       (src == TFREC_AMD_CENTRE_MEASURED ? std::to_string(c.cen.deviation_hz) : std::string("-")) + " " + "mfi"[src];
 }
 
 // ---- -O: the pulses of an amplitude track (include/tfrec_amd.h: "Amplitude track", Pulses, whose text is normative; tfrec_amd/track.py

@@ -112,6 +112,14 @@
 // slicer, not a demodulator: no clock recovery, no matched filter; the golden TFA_1 and WHB scenes do not slice with it.  Works with
 // -M, -Q, -C, -S, -R, -n, -d and every input option; not with -X, -k, -K, -s or -A.  Nothing of it has been measured on real
 // recordings.
+// -G rate,auto (not in the reference): the track in auto-centre mode (tfrec_amd_enable_burst_track_auto), for recordings that
+// hold several transmitters, each with its own carrier offset: every burst is tracked about a centre measured on its own first
+// 1024 samples (fewer than 65 of them over the threshold, or no bin with a sixteenth of the products: centre 0).  Ahead of each
+// burst's bits line stdout gets
+//   centre <file> <start_sample> <n_samples> <n_counted> <centre_hz> <deviation_hz|-> <m|f|i>
+// m: measured, f: the fallback (no deviation), i: inherited from a piece the output does not hold.  A burst that begins within 1024
+// samples of a batch's end is centred on what that batch holds of it.  Works where -G works, -Y included; not with -O.  Nothing of
+// it has been measured on real recordings.
 // -O level (not in the reference; with -G rate, no centre): the track is the amplitude's (tfrec_amd_enable_burst_track_amplitude, DESIGN.md
 // 6v), for on-off keyed bursts: 1 where the sum of L powers |I| + |Q| lies above L times level (0 .. 65535, -t's unit; L: -G's).  The
 // bits line and -Y's frame lines are read off that track, and behind each bits line stdout gets
@@ -303,6 +311,7 @@ struct cli {
 	bool clock = false;  // -C
 	long track_rate = 0, track_centre = 0;  // -G (rate 0: not given)
 	bool track_centre_given = false;
+	bool track_auto = false;  // -G rate,auto
 	long track_level = -1;  // -O (-1: not given)
 	int sync_bits = 0;  // -Y (0: not given): the word's bits, the word, errors, bytes, both
 	unsigned long long sync_pattern = 0;
@@ -340,7 +349,7 @@ struct cli {
 
 static void usage()
 {
-	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-G rate[,centre_hz]] [-O level] [-Y hex[,errors[,bytes[,both]]]] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
+	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-G rate[,centre_hz]] [-G rate,auto] [-O level] [-Y hex[,errors[,bytes[,both]]]] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
 			"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
 			"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
 			"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
@@ -364,6 +373,9 @@ static void usage()
 			"              line 'bits <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->' per trigger window, MSB-first,\n"
 			"              1 above the centre (+: longer than the 2^20 samples kept); also with -M, -Q, -C, -S and -R; not with -X, -k, -K,\n"
 			"              -s or -A\n"
+			"  -G r,auto   as -G r, every burst about a centre measured on its own first 1024 samples -- a recording of several transmitters\n"
+			"              in one pass --, and ahead of each bits line a line 'centre <file> <start_sample> <n_samples> <n_counted> <centre_hz>\n"
+			"              <deviation_hz|-> <m|f|i>' (m: measured; f: too few samples over the threshold, centre 0; i: inherited); not with -O\n"
 			"  -O level    with -G r: read on-off keyed bursts: the track is 1 where the burst's amplitude (|I| + |Q|, -t's unit, smoothed as -G's)\n"
 			"              lies above level (0 .. 65535; a place to start: half of -M's pwr_max); behind each bits line a line 'pulses <file>\n"
 			"              <start_sample> <n_samples> <burst_samples> <n_pulses>[+] <w0,g0,w1,...|->', pulse and gap widths in samples (+: more\n"
@@ -460,13 +472,16 @@ int cli::parse(int argc, char **argv)
 		case 'C': clock = true; break;
 		case 'G': {
 			const char *comma = strchr(optarg, ',');
+			track_auto = comma && !strcmp(comma + 1, "auto");
 			if (!parse_long(std::string(optarg, comma ? (size_t)(comma - optarg) : strlen(optarg)).c_str(), 1000, 96000, track_rate) ||
-			    (comma && !parse_long(comma + 1, -192000, 192000, track_centre))) {
-				fprintf(stderr, "tfrec_gpu: bad -G '%s': want <rate>[,<centre_hz>], the rate within 1000 .. 96000 bit/s, the centre within "
+			    (comma && !track_auto && !parse_long(comma + 1, -192000, 192000, track_centre))) {
+				fprintf(stderr, "tfrec_gpu: bad -G '%s': want <rate>[,<centre_hz>] or <rate>,auto, the rate within 1000 .. 96000 bit/s, the centre within "
 						"-192000 .. 192000 Hz\n", optarg);
 				return 1;
 			}
-			track_centre_given = comma != NULL;
+			track_centre_given = comma != NULL && !track_auto;
+			if (track_auto)
+				track_centre = 0;
 			break;
 		}
 		case 'O':
@@ -691,6 +706,10 @@ int cli::check() const
 	}
 	if (clock && hexfile) {
 		fprintf(stderr, "tfrec_gpu: -C measures the bursts of -L files or of a capture (-R): not with -X\n");
+		return 1;
+	}
+	if (track_level >= 0 && track_auto) {
+		fprintf(stderr, "tfrec_gpu: -G rate,auto centres the frequency track: not with -O, whose track is the amplitude's\n");
 		return 1;
 	}
 	if (track_level >= 0 && (!track_rate || track_centre_given)) {
@@ -951,6 +970,8 @@ int cli::run()
 		e.set_track(track_rate, track_centre);
 	if (track_level >= 0)
 		e.set_track_level(track_level);
+	if (track_auto)
+		e.set_track_auto();
 	if (sync_bits)
 		e.set_sync(sync_pattern, sync_bits, (int)sync_errors, (int)sync_bytes, sync_both != 0);
 	if (keep_prefix)

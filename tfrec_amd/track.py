@@ -20,6 +20,14 @@ records, bitmap and state, the bit 1 where the sum of L powers |I| + |Q| lies ab
 
   amplitude_tracks, amplitude_tracks_bruteforce   tracks' and tracks_bruteforce's counterparts, a level per stream for the centre;
   pulses             a merged track -> the widths pulse, gap, ..., pulse;  pulses_line: tfrec_gpu -O's output line.
+
+The track's auto-centre mode (tfrec_amd_enable_burst_track_auto, the header's "Auto-centre track") -- the same track
+about a table index per ENTRY, measured on the first K samples of the chain's first piece:
+
+  head_centres, head_centres_bruteforce   one submit's centre records (CENTRE_DTYPE) and the carried state, vectorised and per sample;
+  auto_tracks        the centre records, then tracks(..., run_index=...) about them;
+  merge_centres, centre_chains   a chain keeps its first piece's record;  centre_line: tfrec_gpu -G rate,auto's output line;
+  auto_device_bytes  what tfrec_amd_enable_burst_track_auto adds to tfrec_amd_get_memory (pinned: pinned_bytes).
 """
 from __future__ import annotations
 
@@ -91,12 +99,13 @@ def _pack(out, tr, max_samples):
     return np.packbits(flat.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1)
 
 
-def tracks(dec, mask_or_thresh, runs, smooth, centres=None, state=None, base=None, max_samples=None):
+def tracks(dec, mask_or_thresh, runs, smooth, centres=None, state=None, base=None, max_samples=None, run_index=None):
     """One submit.  dec[s]: stream s's decimated samples of the submit (int16 pairs, as tfrec_amd_read_decimated returns them);
     mask_or_thresh[s]: its over bits or the threshold behind them (envelope.envelopes'); runs: the submit's table (RUN_DTYPE);
     smooth: L; centres[s]: the stream's centre in Hz (default 0); state: what the submit before returned (default: a fresh
     context's); base[s]: the start_sample of the submit's first sample of stream s (default 0); max_samples: the pool's size
-    (default: everything fits) -> (a TRACK_DTYPE array, one record per table entry; the bitmap's uint32 words, as many as the
+    (default: everything fits); run_index[e]: entry e's own table index r in the stream's centre's place (the auto-centre track:
+    head_centres' records' index) -> (a TRACK_DTYPE array, one record per table entry; the bitmap's uint32 words, as many as the
     pairs that fit need; the state behind the submit)."""
     L = int(smooth)
     assert 1 <= L <= AHEAD
@@ -106,7 +115,7 @@ def tracks(dec, mask_or_thresh, runs, smooth, centres=None, state=None, base=Non
     tr = []
     for e, r in enumerate(runs):
         s, a, n, cont = _window(dec, r, base)
-        ri = index_of(centres[s]) if centres is not None else 0
+        ri = int(run_index[e]) if run_index is not None else index_of(centres[s]) if centres is not None else 0
         C, S = int(c[ri]), int(s_[ri])
         z = np.concatenate([np.asarray(state["carry"][s], dtype=np.int64).reshape(AHEAD, 2), burst._pairs(dec[s]).astype(np.int64)])
         cf = a - (int(state["prior"][s]) if cont else 0)  # the chain's first sample, submit-relative
@@ -126,7 +135,7 @@ def tracks(dec, mask_or_thresh, runs, smooth, centres=None, state=None, base=Non
     return out, _pack(out, tr, max_samples), _next_state(dec, runs, state, base)
 
 
-def tracks_bruteforce(dec, mask_or_thresh, runs, smooth, centres=None, state=None, base=None, max_samples=None):
+def tracks_bruteforce(dec, mask_or_thresh, runs, smooth, centres=None, state=None, base=None, max_samples=None, run_index=None):
     """The same, one sample at a time in Python integers, as the header words it: the sum of v[k - i] over i < min(L, k + prior)."""
     L = int(smooth)
     state = fresh_state(len(dec)) if state is None else state
@@ -135,7 +144,7 @@ def tracks_bruteforce(dec, mask_or_thresh, runs, smooth, centres=None, state=Non
     tr = []
     for e, r in enumerate(runs):
         s, a, n, cont = _window(dec, r, base)
-        ri = index_of(centres[s]) if centres is not None else 0
+        ri = int(run_index[e]) if run_index is not None else index_of(centres[s]) if centres is not None else 0
         C, S = int(c[ri]), int(s_[ri])
         row = burst._pairs(dec[s]).tolist()
         ahead = np.asarray(state["carry"][s]).reshape(AHEAD, 2).tolist()
@@ -264,6 +273,153 @@ def pulses_line(name: str, piece) -> str:
                                            "+" if n > PULSES_LISTED else "", ",".join("%d" % x for x in shown) if shown else "-")
 
 
+# ---- the auto-centre track (tfrec_amd_enable_burst_track_auto, the header's "Auto-centre track")
+CENTRE_DTYPE = np.dtype([("stream", "<u4"), ("flags", "<u4"), ("start_sample", "<i8"), ("n_samples", "<u4"), ("thresh", "<i4"),
+                         ("n_counted", "<u4"), ("source", "<u4"), ("centre_hz", "<i4"), ("deviation_hz", "<i4"), ("index", "<i4"),
+                         ("reserved", "<u4")])
+assert CENTRE_DTYPE.itemsize == 48
+MEASURED, FALLBACK, INHERITED = 0, 1, 2  # a centre record's source
+HEAD_MIN, HEAD_MAX = 64, 4096  # K
+COUNT_MIN = 64  # the counted products a measured centre needs
+
+
+def fresh_centre_state(n_streams: int) -> dict:
+    """What a context carries before its first submit, and for a stream without an OPEN run that has a record: nothing (index -1)."""
+    return {"index": np.full(n_streams, -1, dtype=np.int64), "centre_hz": np.zeros(n_streams, dtype=np.int64)}
+
+
+def _centre_copied(run):
+    o = np.zeros((), dtype=CENTRE_DTYPE)
+    for f in ("stream", "flags", "n_samples", "thresh"):
+        o[f] = run[f]
+    o["start_sample"] = int(run["start_sample"])
+    return o
+
+
+def _fallbacks(fallback, n_streams):
+    fb = [0] * n_streams if fallback is None else [int(x) for x in fallback]
+    assert len(fb) == n_streams and all(abs(x) <= CENTRE_MAX for x in fb)
+    return fb
+
+
+def _next_centre_state(n_streams, out):
+    nxt = fresh_centre_state(n_streams)
+    for o in out:
+        if int(o["flags"]) & RUN_OPEN:
+            nxt["index"][int(o["stream"])], nxt["centre_hz"][int(o["stream"])] = int(o["index"]), int(o["centre_hz"])
+    return nxt
+
+
+def head_centres(dec, mask_or_thresh, runs, head, fallback=None, state=None, base=None):
+    """One submit's centre records.  tracks' dec, mask_or_thresh, runs and base; head: K; fallback[s]: the stream's set centre in Hz
+    (default 0); state: what the submit before returned (default: a fresh context's).  runs holds the entries that have a record
+    (those below max_runs): an OPEN run that is not among them leaves nothing behind -> (a CENTRE_DTYPE array, one record per
+    entry; the state behind the submit: per stream the index and centre of its OPEN run, index -1 without one)."""
+    K = int(head)
+    assert HEAD_MIN <= K <= HEAD_MAX
+    state = fresh_centre_state(len(dec)) if state is None else state
+    fb = _fallbacks(fallback, len(dec))
+    out = np.zeros(len(runs), dtype=CENTRE_DTYPE)
+    sign = np.where(np.arange(burst.N_BINS) < burst.N_BINS // 2, np.arange(burst.N_BINS), np.arange(burst.N_BINS) - burst.N_BINS)
+    for e, r in enumerate(runs):
+        s, a, n, cont = _window(dec, r, base)
+        o = _centre_copied(r)
+        if cont:
+            if int(state["index"][s]) >= 0:
+                o["source"], o["centre_hz"], o["index"] = INHERITED, int(state["centre_hz"][s]), int(state["index"][s])
+            else:
+                o["source"], o["centre_hz"], o["index"] = FALLBACK, fb[s], index_of(fb[s])
+            out[e] = o
+            continue
+        nh = min(n, K)
+        z = burst._pairs(dec[s]).astype(np.int64)
+        over = envelope._over(z, mask_or_thresh[s])[a:a + nh]
+        z = z[a:a + nh]
+        I, Q, Ip, Qp = z[1:, 0], z[1:, 1], z[:-1, 0], z[:-1, 1]
+        both = over[1:] & over[:-1]
+        dot, crs = (I * Ip + Q * Qp)[both], (Q * Ip - I * Qp)[both]
+        P = len(dot)
+        hist = np.bincount(burst._bins(dot, crs), minlength=burst.N_BINS) if P else np.zeros(burst.N_BINS, dtype=np.int64)
+        occ = sign[hist >= (P + 15) // 16] if P >= COUNT_MIN else sign[:0]
+        o["n_counted"] = P
+        if len(occ):
+            lo, hi = int(occ.min()), int(occ.max())
+            o["source"], o["centre_hz"], o["deviation_hz"] = MEASURED, 3000 * (lo + hi), 3000 * (hi - lo)
+        else:
+            o["source"], o["centre_hz"] = FALLBACK, fb[s]
+        o["index"] = index_of(int(o["centre_hz"]))
+        out[e] = o
+    return out, _next_centre_state(len(dec), out)
+
+
+def head_centres_bruteforce(dec, mask_or_thresh, runs, head, fallback=None, state=None, base=None):
+    """The same, one sample at a time in Python integers, as the header words it."""
+    K = int(head)
+    state = fresh_centre_state(len(dec)) if state is None else state
+    fb = _fallbacks(fallback, len(dec))
+    out = np.zeros(len(runs), dtype=CENTRE_DTYPE)
+    for e, r in enumerate(runs):
+        s, a, n, cont = _window(dec, r, base)
+        o = _centre_copied(r)
+        if cont:
+            idx = int(state["index"][s])
+            src, hz, dev, cnt = (INHERITED, int(state["centre_hz"][s]), 0, 0) if idx >= 0 else (FALLBACK, fb[s], 0, 0)
+            idx = idx if idx >= 0 else index_of(hz)
+        else:
+            row = burst._pairs(dec[s]).tolist()
+            over = envelope._over(burst._pairs(dec[s]).astype(np.int64), mask_or_thresh[s]).tolist()
+            hist, cnt = [0] * burst.N_BINS, 0
+            for k in range(1, min(n, K)):
+                if over[a + k] and over[a + k - 1]:
+                    (i, q), (ip, qp) = row[a + k], row[a + k - 1]
+                    hist[burst.bin_of(i * ip + q * qp, q * ip - i * qp)] += 1
+                    cnt += 1
+            occ = [burst.signed_bin(j) for j in range(burst.N_BINS) if cnt >= COUNT_MIN and hist[j] >= (cnt + 15) // 16]
+            if occ:
+                src, hz, dev = MEASURED, 3000 * (min(occ) + max(occ)), 3000 * (max(occ) - min(occ))
+            else:
+                src, hz, dev = FALLBACK, fb[s], 0
+            idx = index_of(hz)
+        o["n_counted"], o["source"], o["centre_hz"], o["deviation_hz"], o["index"] = cnt, src, hz, dev, idx
+        out[e] = o
+    return out, _next_centre_state(len(dec), out)
+
+
+def auto_tracks(dec, mask_or_thresh, runs, smooth, head, fallback=None, state=None, base=None, max_samples=None, brute=False):
+    """One submit of the auto-centre track: the centre records, then the track about every entry's own index.  state: (the
+    track's, the centres') of the submit before, or None -> (centre records, track records, words, the state behind the submit)."""
+    tst, cst = state if state is not None else (None, None)
+    cen, cst = (head_centres_bruteforce if brute else head_centres)(dec, mask_or_thresh, runs, head, fallback, cst, base)
+    recs, words, tst = (tracks_bruteforce if brute else tracks)(dec, mask_or_thresh, runs, smooth, None, tst, base, max_samples,
+                                                                 run_index=cen["index"])
+    return cen, recs, words, (tst, cst)
+
+
+def merge_centres(pieces):
+    """A chain's centre records (in order) -> the uncut run's: the first piece's, with the chain's flags (track.merge's) and the
+    pieces' n_samples added.  The chain's first piece decides for the whole chain."""
+    pieces = list(pieces)
+    o = pieces[0].copy()
+    for p in pieces[1:]:
+        assert p["stream"] == o["stream"] and int(p["flags"]) & RUN_CONTINUES
+        o["n_samples"] = int(o["n_samples"]) + int(p["n_samples"])
+    o["flags"] = (int(pieces[0]["flags"]) & RUN_CONTINUES) | (int(pieces[-1]["flags"]) & RUN_OPEN)
+    return o
+
+
+def centre_chains(submits, restarts=None):
+    """submits: one CENTRE_DTYPE array per submit, in order -> the merged records, in burst.chains' order."""
+    return burst.chains(submits, restarts, join=merge_centres)
+
+
+def centre_line(name: str, rec) -> str:
+    """tfrec_gpu -G rate,auto: centre <file> <start_sample> <n_samples> <n_counted> <centre_hz> <deviation_hz|-> <m|f|i>, ahead of
+    the burst's bits line; the deviation only of a measured centre; i: a chain whose first piece the output does not hold."""
+    src = int(rec["source"])
+    return "centre %s %d %d %d %d %s %s" % (name, int(rec["start_sample"]), int(rec["n_samples"]), int(rec["n_counted"]),
+                                            int(rec["centre_hz"]), "%d" % int(rec["deviation_hz"]) if src == MEASURED else "-", "mfi"[src])
+
+
 def bits_of(rec, words):
     """A record's track out of its submit's bitmap -> uint8 [n_samples]."""
     b0, n = int(rec["bit_offset"]), int(rec["n_samples"])
@@ -367,3 +523,10 @@ def pinned_bytes(n_streams: int) -> int:
     """... and to its page-locked bytes: the centre indices' source per FIFO set."""
     from .api import FIFO_DEPTH
     return FIFO_DEPTH * 4 * n_streams
+
+
+def auto_device_bytes(n_streams: int, max_runs: int, max_samples: int) -> int:
+    """What tfrec_amd_enable_burst_track_auto adds to the device bytes: the track's, per FIFO set the centre records, per stream the
+    carried index and centre."""
+    from .api import FIFO_DEPTH
+    return device_bytes(n_streams, max_runs, max_samples) + FIFO_DEPTH * max_runs * CENTRE_DTYPE.itemsize + 8 * n_streams
