@@ -1061,6 +1061,57 @@ int tfrec_amd_enable_burst_track_auto(tfrec_amd_ctx *ctx, int32_t smooth, int32_
  * is) and errors; a context whose track is off or in another mode: TFREC_AMD_E_INVAL. */
 int tfrec_amd_read_burst_track_centres(tfrec_amd_ctx *ctx, tfrec_amd_track_centre *out, size_t cap_runs, uint32_t *n_runs);
 
+/* Phase track (tfrec_amd_enable_burst_track_phase): a fourth MODE of the burst track, for PHASE-keyed bursts, whose
+ * frequency does not move and on which a discriminator has nothing to read: a differential phase detector at a lag of m samples -- a
+ * symbol -- about the burst's own carrier, measured on the chain's first samples in the same submit.  A context has the frequency
+ * track, the amplitude track, the auto-centre track or this one.  The record (tfrec_amd_track), the bitmap and its packing, last_over,
+ * n_ones, the merging rules, the overflow prefixes, tfrec_amd_read_burst_tracks, and tfrec_amd_read_burst_track_centres with
+ * tfrec_amd_track_centre and its three sources are exactly the frequency track's and the auto-centre track's; so are the Slicing and
+ * everything the burst sync makes of a track.  There is no reference counterpart: this text is normative, tfrec_amd/track.py
+ * (head_carriers, phase_tracks) restates it.  Exact integers only.
+ *   Settings: fixed at enable: smooth = L, 1 .. 16, the detector's boxcar; head = K, 64 .. 4096, the samples of a chain's first piece
+ *             the carrier is measured on (K = 64 counts 63 products at the most and never measures); lag = m, 1 .. 64, the
+ *             detector's lag in samples.  Per stream the set centre hz, |hz| <= 192000, default 0
+ *             (tfrec_amd_set_burst_track_centre; in force from the next submit on): the FALLBACK.
+ *   Carrier:  for an entry without TFREC_AMD_RUN_CONTINUES, submit-relative start a and n samples, the counted products are the
+ *             auto-centre track's: dot[k], crs[k] of the frequency track for 1 <= k < min(n, K), counted iff over[a + k] and
+ *             over[a + k - 1] in the stream's final trigger mask.  P is their number, A the sum of dot over them and B the sum of
+ *             crs: |dot|, |crs| <= 2^31 and P <= 4095, so |A|, |B| < 2^43.  With C[], S[] the tune table (C[r] = round(32767 cos(2 pi
+ *             r / 4096)), S[r] = C[(r - 1024) mod 4096]), score(r) = A C[r] + B S[r] and cross(r) = B C[r] - A S[r]; both stay below
+ *             2^59.  If P >= 64 and (A, B) != (0, 0): r is the index in 0 .. 4095 with score(r) > 0 that minimises |cross(r)|, on a
+ *             tie the smallest such index (one exists: the index nearest the direction of (A, B) has a positive score); source
+ *             MEASURED, centre_hz = floor(375 rs / 4) with rs = r below 2048 and r - 4096 otherwise, deviation_hz = 0.  The zero of
+ *             the cross term, not the maximum of the score: near its peak the score changes per index by about a tenth of the
+ *             table's rounding, the cross term by about 50 times its rounding.  Otherwise r = floor((8192 hz + 384000) / 768000) mod
+ *             4096 of the stream's set centre hz, centre_hz = hz, deviation_hz = 0, source FALLBACK.  n_counted = P in both.
+ *   Chains:   an entry with TFREC_AMD_RUN_CONTINUES is exactly the auto-centre track's: INHERITED from the OPEN entry that ended the
+ *             submit before, or FALLBACK where that entry had no record; n_counted = deviation_hz = 0.
+ *   Products: rm = (r m) mod 4096.  c(k) is sample k's index in its chain, counted from the chain's first sample (k + prior in an
+ *             entry that CONTINUES, k otherwise, k being run-relative).  For c(k) >= m: dm = I[k] I[k-m] + Q[k] Q[k-m], cm = Q[k]
+ *             I[k-m] - I[k] Q[k-m], u[k] = dm C[rm] + cm S[rm]: the real part of z[k] conj(z[k-m]) turned back by the carrier's
+ *             advance over m samples; |u| < 2^47.  u[k] = 0 for c(k) < m: nothing ahead of the chain is ever used.
+ *   Track:    t[k] = 1 iff the sum of u[k - i] over 0 <= i < L is greater than 0, terms ahead of the chain counting as 0; a zero sum
+ *             gives 0.  1: the same phase as m samples ago.  For an NRZ-S signal -- the carrier toggles on every 0 bit -- with m
+ *             one symbol that is the data bit itself.
+ *   Carried:  per stream the last 80 pairs of the submit and prior = min(80, prior' + n') of its OPEN piece.  80 = 64 + 16: t[k] of
+ *             a piece's first sample (k = 0) sums u[-i] for i <= L - 1 <= 15, u[-i] reads z[-i - m] with m <= 64: 79 pairs back
+ *             at the most, and c(k) >= m is decided alike by prior and by min(80, prior) since k - i + 80 >= 65 > m.  Also, as in
+ *             the auto-centre track, the index and centre of the run that reaches the submit's end.  tfrec_amd_save_streams carries
+ *             none of it.
+ *   Cutting:  the merged track is the uncut run's whenever the chain's first piece holds at least min(n_chain, K) samples; a chain
+ *             that begins within K samples of a submit's end is read about what its first piece has (fewer than 65 samples: the
+ *             fallback).  Merging a chain keeps the first piece's centre record.
+ *   Limits:   the carrier is the direction of the SUM of the head's one-sample products: a signal whose products cancel (a phase
+ *             that flips by a half turn every sample) has no carrier this way and falls back.  The detector reads a symbol
+ *             against the one before it; m must be the symbol's length to within the boxcar.  No descrambler, no bit order: a
+ *             caller makes bytes of the bits.  Nothing of it has been measured on real recordings. */
+/* Turn the track on in phase mode: tfrec_amd_enable_burst_track_auto's rules and errors, and lag outside 1 .. 64: TFREC_AMD_E_INVAL; a
+ * context whose track is on already, in any mode, refuses all four enables with TFREC_AMD_E_INVAL.  Memory: the auto-centre track's
+ * with 80 carried pairs per stream in the place of its 16 (320 bytes for 64).  tfrec_amd_set_burst_track_centre sets the fallback;
+ * tfrec_amd_set_burst_track_level is TFREC_AMD_E_INVAL.  tfrec_amd_enable_burst_sync works on this mode too.  Six launches on the
+ * recorder's stream: both records' inits, the head's carrier, the detector about every entry's index, the two carries. */
+int tfrec_amd_enable_burst_track_phase(tfrec_amd_ctx *ctx, int32_t smooth, int32_t head, int32_t lag);
+
 /* Burst sync (tfrec_amd_enable_burst_sync): for every run of the recorder's table WHERE A FRAME BEGINS -- one bit per
  * captured sample, 1 where the burst track, read at P symbol centres that end at the sample, is a known sync word but for at most E
  * places.  The symbol timing comes from where the matches lie; a caller reads the payload at symbol centres from there.  It sits on

@@ -119,7 +119,7 @@ EXPORTS = (
     "tfrec_amd_enable_burst_clock", "tfrec_amd_read_burst_clocks",
     "tfrec_amd_enable_burst_track", "tfrec_amd_set_burst_track_centre", "tfrec_amd_read_burst_tracks",
     "tfrec_amd_enable_burst_track_amplitude", "tfrec_amd_set_burst_track_level",
-    "tfrec_amd_enable_burst_track_auto", "tfrec_amd_read_burst_track_centres",
+    "tfrec_amd_enable_burst_track_auto", "tfrec_amd_read_burst_track_centres", "tfrec_amd_enable_burst_track_phase",
     "tfrec_amd_enable_burst_sync", "tfrec_amd_read_burst_syncs",
 )
 
@@ -230,6 +230,7 @@ def load_library(build: bool = True, experiments: bool = False, short_segments: 
     L.tfrec_amd_set_burst_track_level.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tfrec_amd_enable_burst_track_auto.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     L.tfrec_amd_read_burst_track_centres.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+    L.tfrec_amd_enable_burst_track_phase.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     L.tfrec_amd_read_burst_tracks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
                                               C.POINTER(C.c_uint64)]
     L.tfrec_amd_enable_burst_sync.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_uint32]
@@ -753,6 +754,15 @@ class Receiver:
         if not (-2 ** 31 <= int(smooth) < 2 ** 31 and -2 ** 31 <= int(head) < 2 ** 31):  # (refused before ctypes could wrap a value into range)
             raise TfrecAmdError(E_INVAL, "smooth or head outside its type")
         _check(self.L, self.L.tfrec_amd_enable_burst_track_auto(self.h, int(smooth), int(head)))
+
+    def enable_burst_track_phase(self, smooth: int, head: int = 1024, lag: int = 1):
+        """Turn the burst track on in phase mode (tfrec_amd_enable_burst_track_phase; enable_burst_track's rules, and instead of
+        it), for phase-keyed bursts: a differential phase detector at a lag of `lag` (1 .. 64) samples, boxcar `smooth`, about
+        the carrier measured on the first `head` (64 .. 4096) samples of every chain's first piece; set_burst_track_centre sets the
+        fallback.  read_burst_tracks returns the records and the bitmap, read_burst_track_centres every entry's carrier."""
+        if not all(-2 ** 31 <= int(v) < 2 ** 31 for v in (smooth, head, lag)):  # (refused before ctypes could wrap a value into range)
+            raise TfrecAmdError(E_INVAL, "smooth, head or lag outside its type")
+        _check(self.L, self.L.tfrec_amd_enable_burst_track_phase(self.h, int(smooth), int(head), int(lag)))
 
     def read_burst_track_centres(self, allow_overflow: bool = False) -> np.ndarray:
         """The centre records of the OLDEST undrained submit (tfrec_amd_read_burst_track_centres; call it before the drain that

@@ -1,5 +1,5 @@
 // tfrec_amd/csrc/capi_bursts.h -- the entry points of the five burst stages on the recorder's table: the meter, the
-// envelope (6r), the clock (6s), the track (6t, with its centres; 6v, its amplitude mode, with its levels; 6w, its auto-centre mode, with its centre records) and the sync (6u).  What they share comes first -- the enables'
+// envelope (6r), the clock (6s), the track (6t, with its centres; 6v, its amplitude mode, with its levels; 6w, its auto-centre mode, with its centre records; 6x, its phase mode) and the sync (6u).  What they share comes first -- the enables'
 // preflight, the rebase of start_sample, the record-only reader and the record-plus-bitmap reader --, then each
 // stage's enable and read, which add their own argument checks and buffers.  Included by capi.hip, which lists what is where.
 #pragma once
@@ -183,10 +183,12 @@ static int32_t track_index(int32_t hz)
 }
 
 constexpr int kTrackHeadMin = 64, kTrackHeadMax = 4096;  // the auto-centre mode's K
+constexpr int kTrackLagMin = 1, kTrackLagMax = 64;        // the phase mode's m
 
 // Every mode's enable: the frequency track (6t) or the amplitude track (6v), which differ in one kernel and in what idx holds, or
-// the auto-centre track (6w: head = K != 0), whose idx holds the set centres in Hz and which adds its records and its carry
-static int enable_track(tfrec_amd_ctx *c, int32_t smooth, bool amplitude, int32_t head = 0)
+// the auto-centre track (6w: head = K != 0), whose idx holds the set centres in Hz and which adds its records and its carry, or the
+// phase track (6x: head and lag = m != 0), which is the auto-centre's with 80 carried pairs per stream for its 16
+static int enable_track(tfrec_amd_ctx *c, int32_t smooth, bool amplitude, int32_t head = 0, int32_t lag = 0)
 {
 	if (!c)
 		return TFREC_AMD_E_INVAL;
@@ -196,6 +198,10 @@ static int enable_track(tfrec_amd_ctx *c, int32_t smooth, bool amplitude, int32_
 	}
 	if (head && (head < kTrackHeadMin || head > kTrackHeadMax)) {
 		snprintf(g_err, sizeof(g_err), "the auto-centre track's head is within [%d, %d]", kTrackHeadMin, kTrackHeadMax);
+		return TFREC_AMD_E_INVAL;
+	}
+	if (lag && (lag < kTrackLagMin || lag > kTrackLagMax)) {
+		snprintf(g_err, sizeof(g_err), "the phase track's lag is within [%d, %d]", kTrackLagMin, kTrackLagMax);
 		return TFREC_AMD_E_INVAL;
 	}
 	TRY(recorder_preflight(c, kTrackNames, c->trk.on));
@@ -209,9 +215,10 @@ static int enable_track(tfrec_amd_ctx *c, int32_t smooth, bool amplitude, int32_
 		TRY(own_device(c, o.d_idx[k], n * sizeof(int32_t)));
 		TRY(own_pinned(c, o.h_idx[k], n * sizeof(int32_t)));
 	}
-	TRY(own_device(c, o.d_carry, n * 16 * sizeof(uint32_t)));
+	const size_t ahead = lag ? 80 : 16;  // the pairs a stream carries (track.h: kTrackAhead; phase.h: kPhaseAhead)
+	TRY(own_device(c, o.d_carry, n * ahead * sizeof(uint32_t)));
 	TRY(own_device(c, o.d_prior, n * sizeof(uint32_t)));
-	HIPCHK(hipMemset(o.d_carry, 0, n * 16 * sizeof(uint32_t)));  // (never used before a submit has written them: no first submit CONTINUES)
+	HIPCHK(hipMemset(o.d_carry, 0, n * ahead * sizeof(uint32_t)));  // (never used before a submit has written them: no first submit CONTINUES)
 	HIPCHK(hipMemset(o.d_prior, 0, n * sizeof(uint32_t)));
 	if (head) {
 		for (int k = 0; k < kSets; k++)
@@ -219,6 +226,7 @@ static int enable_track(tfrec_amd_ctx *c, int32_t smooth, bool amplitude, int32_
 		TRY(own_device(c, o.d_ccarry, n * sizeof(int2)));
 		HIPCHK(hipMemset(o.d_ccarry, 0xff, n * sizeof(int2)));  // index -1: nothing carried
 		o.head = head;
+		o.lag = lag;
 		o.cen.on = true;
 	}
 	o.idx.assign(n, 0);
@@ -236,6 +244,15 @@ int tfrec_amd_enable_burst_track_auto(tfrec_amd_ctx *c, int32_t smooth, int32_t 
 		return TFREC_AMD_E_INVAL;
 	}
 	return enable_track(c, smooth, false, head);
+}
+int tfrec_amd_enable_burst_track_phase(tfrec_amd_ctx *c, int32_t smooth, int32_t head, int32_t lag)
+{
+	if (c && (!head || !lag)) {  // (0 is enable_track's "no head" and "no lag")
+		snprintf(g_err, sizeof(g_err), "the phase track's head is within [%d, %d], its lag within [%d, %d]", kTrackHeadMin, kTrackHeadMax, kTrackLagMin,
+			 kTrackLagMax);
+		return TFREC_AMD_E_INVAL;
+	}
+	return enable_track(c, smooth, false, head, lag);
 }
 
 int tfrec_amd_set_burst_track_centre(tfrec_amd_ctx *c, const int32_t *streams, const int32_t *hz, int n)

@@ -100,11 +100,13 @@ struct RunRecords {
 // source; per stream the carried last 16 pairs and chain position (track_carry_kernel).  amplitude: the track's other mode
 // (tfrec_amd_enable_burst_track_amplitude), in which idx, d_idx and h_idx hold every stream's level instead.  cen.on:
 // its third mode (tfrec_amd_enable_burst_track_auto), in which they hold every stream's set centre in Hz, with K, per
-// set the centre records and per stream the carried index and centre (centre_carry_kernel)
+// set the centre records and per stream the carried index and centre (centre_carry_kernel).  lag != 0: its fourth mode
+// (tfrec_amd_enable_burst_track_phase), the third's buffers with 80 carried pairs per stream in d_carry, and m
 struct BurstTrack : RunRecords<tfrec_amd_track> {
 	bool amplitude = false;
 	RunRecords<tfrec_amd_track_centre> cen;
 	int head = 0;
+	int lag = 0;
 	int2 *d_ccarry = nullptr;
 	int smooth = 0;
 	size_t n_words = 0;

@@ -272,15 +272,17 @@ static int launch_decin_front(tfrec_amd_ctx *c, int set, const uint8_t *d_iq, si
 // The burst track on the recorder's lane: the centre indices the submit runs with, staged like stage_tune's
 // (h_idx[set] is free: the set's previous submit, whose copy read it, has been drained), then its three kernels.  In amplitude
 // mode (6v) the staged values are the levels and the middle kernel is amplitude_kernel; in auto-centre mode (6w) they are the set
-// centres in Hz, and the head's kernel and the centre's carry join the sequence
+// centres in Hz, and the head's kernel and the centre's carry join the sequence; in phase mode (6x) they are too, and all three
+// kernels are phase.h's
 static int launch_track(tfrec_amd_ctx *c, int set, const FrontOut &out, const CaptureBufs &b)
 {
 	BurstTrack &o = c->trk;
 	std::copy(o.idx.begin(), o.idx.end(), o.h_idx[set]);
 	HIPCHK(hipMemcpyAsync(o.d_idx[set], o.h_idx[set], o.idx.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->cap.lane.st));
 	const TrackBufs k = { .recs = o.d_recs[set], .words = o.d_words[set], .centre = o.d_idx[set], .carry = o.d_carry, .prior = o.d_prior,
-			      .smooth = o.smooth, .cen = o.cen.d_recs[set], .ccarry = o.d_ccarry, .head = o.head };
-	HIPCHK(o.cen.on      ? launch_burst_track_auto(c->cap.lane.st, out, b, k)
+			      .smooth = o.smooth, .cen = o.cen.d_recs[set], .ccarry = o.d_ccarry, .head = o.head, .lag = o.lag };
+	HIPCHK(o.lag         ? launch_burst_track_phase(c->cap.lane.st, out, b, k)
+	       : o.cen.on    ? launch_burst_track_auto(c->cap.lane.st, out, b, k)
 	       : o.amplitude ? launch_burst_track_amplitude(c->cap.lane.st, out, b, k)
 			     : launch_burst_track(c->cap.lane.st, out, b, k));
 	return TFREC_AMD_OK;

@@ -849,6 +849,7 @@ hipError_t launch_fmdev(hipStream_t st, const FrontOut &o, EventBuf *eb, int wma
 #include "track.h"     // track_kernel, track_carry_kernel, launch_burst_track
 #include "amplitude.h"  // amplitude_kernel, launch_burst_track_amplitude
 #include "centre.h"    // centre_head_kernel, track_centre_kernel, centre_carry_kernel, launch_burst_track_auto
+#include "phase.h"     // carrier_head_kernel, phase_kernel, phase_carry_kernel, launch_burst_track_phase
 #include "sync.h"      // sync_kernel, sync_carry_kernel, launch_burst_sync
 #include "spectrum.h"  // spectrum_kernel, launch_spectrum
 #include "occupancy.h"  // occupancy_kernel, launch_occupancy

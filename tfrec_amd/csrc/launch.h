@@ -38,7 +38,8 @@ struct CaptureBufs {
 	unsigned long long max_samples;
 };
 // The burst track's buffers (track.h): the set's records, bitmap and centre indices, the carried 16 pairs and chain position of every
-// stream, and L; in auto-centre mode (centre.h) also the set's centre records, every stream's carried index and centre, and K
+// stream, and L; in auto-centre mode (centre.h) also the set's centre records, every stream's carried index and centre, and K; in
+// phase mode (phase.h) those too, carry holds 80 pairs per stream, and m
 struct TrackBufs {
 	tfrec_amd_track *recs;
 	uint32_t *words;
@@ -48,6 +49,7 @@ struct TrackBufs {
 	tfrec_amd_track_centre *cen;
 	int2 *ccarry;
 	int head;
+	int lag;
 };
 // The burst sync's buffers and settings (sync.h): the set's records and match bitmap, the set's track bitmap, the carried 64 words
 // of track bits and H of every stream
@@ -104,6 +106,7 @@ hipError_t launch_burst_clock(hipStream_t st, const FrontOut &o, const CaptureBu
 hipError_t launch_burst_track(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);
 hipError_t launch_burst_track_amplitude(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);  // (k.centre: the levels)
 hipError_t launch_burst_track_auto(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);  // (k.centre: the set centres in Hz)
+hipError_t launch_burst_track_phase(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);  // (k.centre: the set centres in Hz; k.carry: 80 pairs a stream)
 hipError_t launch_burst_sync(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const SyncBufs &k);
 hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, const SpectrumBufs &b);
 hipError_t launch_occupancy(hipStream_t st, const SpectrumBufs &b, uint32_t ratio, uint32_t rel, tfrec_amd_occupancy *recs, uint32_t *bits);

@@ -276,6 +276,9 @@ inline int device_worker::open_context()
 			call = "tfrec_amd_set_burst_track_level";
 			r = tfrec_amd_set_burst_track_level(ctx, all.data(), level.data(), (int)n);
 		}
+	} else if (!r && job.phasing()) {  // -G rate,psk: the track in phase mode, the fallback centre 0
+		call = "tfrec_amd_enable_burst_track_phase";
+		r = tfrec_amd_enable_burst_track_phase(ctx, job.track_smooth(), kTrackAutoHead, job.track_lag);
 	} else if (!r && job.centring()) {  // -G rate,auto: the track in auto-centre mode, the fallback centre 0
 		call = "tfrec_amd_enable_burst_track_auto";
 		r = tfrec_amd_enable_burst_track_auto(ctx, job.track_smooth(), kTrackAutoHead);

@@ -498,7 +498,7 @@ int gpu_engine::run()
 				framed.clear();
 				syncs.take(b.syncs, workers[d].plan[k], file_blocks, framed);
 				for (const sync_piece &x : framed) {
-					if (job.centring())  // -G rate,auto: the burst's centre ahead of its bits
+					if (job.centring())  // -G rate,auto and -G rate,psk: the burst's centre ahead of its bits
 						printf("%s\n", centre_line(files[x.stream], x.trk).c_str());
 					printf("%s\n", track_line(files[x.stream], x.trk, job.track_rate).c_str());
 					if (job.amplitude())  // -O: the burst's pulses behind its bits

@@ -101,6 +101,7 @@ struct job_settings {
 	long track_centre = 0;         // ... and every stream's centre in Hz
 	long track_level = -1;         // set_track_level (-1: none): -O, the track is the amplitude's, every stream at this level, 0 .. 65535
 	bool track_auto = false;       // set_track_auto: -G rate,auto, every chain about its own measured centre (K = kTrackAutoHead)
+	int track_lag = 0;             // set_track_phase (0: none): -G rate,psk, the phase track's m, 1 .. 64 (with track_auto: its centre records)
 	int sync_bits = 0;             // set_sync (0: none): P, the sync word's bits, 8 .. 64
 	unsigned long long sync_pattern = 0;  // ... the word, in its low P bits
 	int sync_errors = 0;           // ... E
@@ -121,7 +122,8 @@ struct job_settings {
 	bool tracking() const { return track_rate != 0; }  // -G (never with -s or -A)
 	bool syncing() const { return sync_bits != 0; }  // -Y (only with -G)
 	bool amplitude() const { return track_level >= 0; }  // -O (only with -G)
-	bool centring() const { return track_auto; }  // -G rate,auto (never with -O)
+	bool centring() const { return track_auto; }  // -G rate,auto or -G rate,psk: the track has centre records (never with -O)
+	bool phasing() const { return track_lag != 0; }  // -G rate,psk
 	// -G's L: half a symbol, (384000 + rate) / (2 rate) held within 1 .. 16
 	int track_smooth() const { return (int)std::max(1L, std::min(16L, (384000 + track_rate) / (2 * track_rate))); }
 	bool metering() const { return meter && !occupancy(); }  // -M (under -A: in the scan, not in pass 1)

@@ -120,6 +120,12 @@
 // m: measured, f: the fallback (no deviation), i: inherited from a piece the output does not hold.  A burst that begins within 1024
 // samples of a batch's end is centred on what that batch holds of it.  Works where -G works, -Y included; not with -O.  Nothing of
 // it has been measured on real recordings.
+// -G rate,psk[,lag] (not in the reference): the track in phase mode (tfrec_amd_enable_burst_track_phase), for phase-keyed
+// bursts, whose frequency does not move: a differential phase detector at a lag of a symbol (lag samples, 1 .. 64; default
+// floor((768000 + rate) / (2 rate)), a usage error above 64) about the burst's own carrier, measured on its first 1024 samples.  1: the
+// same phase as a symbol ago -- an NRZ-S transmitter's data bit.  -G rate,auto's centre line comes ahead of each bits line, its
+// deviation always 0.  No descrambler and no byte order: the bits are the detector's.  Works where -G rate,auto works, -Y included;
+// not with -O.  Nothing of it has been measured on real recordings.
 // -O level (not in the reference; with -G rate, no centre): the track is the amplitude's (tfrec_amd_enable_burst_track_amplitude, DESIGN.md
 // 6v), for on-off keyed bursts: 1 where the sum of L powers |I| + |Q| lies above L times level (0 .. 65535, -t's unit; L: -G's).  The
 // bits line and -Y's frame lines are read off that track, and behind each bits line stdout gets
@@ -312,6 +318,7 @@ struct cli {
 	long track_rate = 0, track_centre = 0;  // -G (rate 0: not given)
 	bool track_centre_given = false;
 	bool track_auto = false;  // -G rate,auto
+	long track_lag = 0;  // -G rate,psk[,lag] (0: not given): m
 	long track_level = -1;  // -O (-1: not given)
 	int sync_bits = 0;  // -Y (0: not given): the word's bits, the word, errors, bytes, both
 	unsigned long long sync_pattern = 0;
@@ -349,7 +356,7 @@ struct cli {
 
 static void usage()
 {
-	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-G rate[,centre_hz]] [-G rate,auto] [-O level] [-Y hex[,errors[,bytes[,both]]]] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
+	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-G rate[,centre_hz]] [-G rate,auto] [-G rate,psk[,lag]] [-O level] [-Y hex[,errors[,bytes[,both]]]] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
 			"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
 			"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
 			"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
@@ -376,6 +383,9 @@ static void usage()
 			"  -G r,auto   as -G r, every burst about a centre measured on its own first 1024 samples -- a recording of several transmitters\n"
 			"              in one pass --, and ahead of each bits line a line 'centre <file> <start_sample> <n_samples> <n_counted> <centre_hz>\n"
 			"              <deviation_hz|-> <m|f|i>' (m: measured; f: too few samples over the threshold, centre 0; i: inherited); not with -O\n"
+			"  -G r,psk[,m] read phase-keyed bursts: the track is 1 where the phase is the one of m samples ago (1 .. 64; default a symbol,\n"
+			"              (768000 + r) / (2 r)), about the burst's own carrier, measured on its first 1024 samples -- an NRZ-S transmitter's\n"
+			"              bits --, and ahead of each bits line -G r,auto's centre line; not with -O\n"
 			"  -O level    with -G r: read on-off keyed bursts: the track is 1 where the burst's amplitude (|I| + |Q|, -t's unit, smoothed as -G's)\n"
 			"              lies above level (0 .. 65535; a place to start: half of -M's pwr_max); behind each bits line a line 'pulses <file>\n"
 			"              <start_sample> <n_samples> <burst_samples> <n_pulses>[+] <w0,g0,w1,...|->', pulse and gap widths in samples (+: more\n"
@@ -473,14 +483,25 @@ int cli::parse(int argc, char **argv)
 		case 'G': {
 			const char *comma = strchr(optarg, ',');
 			track_auto = comma && !strcmp(comma + 1, "auto");
+			const bool psk = comma && !strncmp(comma + 1, "psk", 3) && (comma[4] == '\0' || comma[4] == ',');
+			track_lag = 0;
 			if (!parse_long(std::string(optarg, comma ? (size_t)(comma - optarg) : strlen(optarg)).c_str(), 1000, 96000, track_rate) ||
-			    (comma && !track_auto && !parse_long(comma + 1, -192000, 192000, track_centre))) {
-				fprintf(stderr, "tfrec_gpu: bad -G '%s': want <rate>[,<centre_hz>] or <rate>,auto, the rate within 1000 .. 96000 bit/s, the centre within "
-						"-192000 .. 192000 Hz\n", optarg);
+			    (comma && !track_auto && !psk && !parse_long(comma + 1, -192000, 192000, track_centre)) ||
+			    (psk && comma[4] == ',' && !parse_long(comma + 5, 1, 64, track_lag))) {
+				fprintf(stderr, "tfrec_gpu: bad -G '%s': want <rate>[,<centre_hz>], <rate>,auto or <rate>,psk[,<lag>], the rate within 1000 .. 96000 bit/s, "
+						"the centre within -192000 .. 192000 Hz, the lag within 1 .. 64 samples\n", optarg);
 				return 1;
 			}
-			track_centre_given = comma != NULL && !track_auto;
-			if (track_auto)
+			if (psk && !track_lag) {  // a symbol in samples
+				track_lag = (768000 + track_rate) / (2 * track_rate);
+				if (track_lag > 64) {
+					fprintf(stderr, "tfrec_gpu: bad -G '%s': a symbol at %ld bit/s is %ld samples, more than the lag's 64: give <rate>,psk,<lag>\n", optarg,
+						track_rate, track_lag);
+					return 1;
+				}
+			}
+			track_centre_given = comma != NULL && !track_auto && !psk;
+			if (track_auto || psk)
 				track_centre = 0;
 			break;
 		}
@@ -706,6 +727,10 @@ int cli::check() const
 	}
 	if (clock && hexfile) {
 		fprintf(stderr, "tfrec_gpu: -C measures the bursts of -L files or of a capture (-R): not with -X\n");
+		return 1;
+	}
+	if (track_level >= 0 && track_lag) {
+		fprintf(stderr, "tfrec_gpu: -G rate,psk reads the phase track: not with -O, whose track is the amplitude's\n");
 		return 1;
 	}
 	if (track_level >= 0 && track_auto) {
@@ -972,6 +997,8 @@ int cli::run()
 		e.set_track_level(track_level);
 	if (track_auto)
 		e.set_track_auto();
+	if (track_lag)
+		e.set_track_phase((int)track_lag);
 	if (sync_bits)
 		e.set_sync(sync_pattern, sync_bits, (int)sync_errors, (int)sync_bytes, sync_both != 0);
 	if (keep_prefix)

@@ -28,6 +28,15 @@ about a table index per ENTRY, measured on the first K samples of the chain's fi
   auto_tracks        the centre records, then tracks(..., run_index=...) about them;
   merge_centres, centre_chains   a chain keeps its first piece's record;  centre_line: tfrec_gpu -G rate,auto's output line;
   auto_device_bytes  what tfrec_amd_enable_burst_track_auto adds to tfrec_amd_get_memory (pinned: pinned_bytes).
+
+The track's phase mode (tfrec_amd_enable_burst_track_phase, the header's "Phase track") -- the same records, bitmap
+and centre records, for phase-keyed bursts: a differential phase detector at a lag of m samples about the carrier measured on
+the first K samples of the chain's first piece:
+
+  carrier_index, carrier_index_bruteforce   the search over the 4096 table directions for the sums A, B of a head's products;
+  head_carriers, head_carriers_bruteforce   one submit's carrier records (CENTRE_DTYPE) and the carried state;
+  phase_tracks, phase_tracks_bruteforce     the carrier records, then the detector about them; fresh_phase_state: the 80 pairs;
+  lag_of             tfrec_gpu -G rate,psk's m;  phase_device_bytes: what the enable call adds to tfrec_amd_get_memory.
 """
 from __future__ import annotations
 
@@ -530,3 +539,219 @@ def auto_device_bytes(n_streams: int, max_runs: int, max_samples: int) -> int:
     carried index and centre."""
     from .api import FIFO_DEPTH
     return device_bytes(n_streams, max_runs, max_samples) + FIFO_DEPTH * max_runs * CENTRE_DTYPE.itemsize + 8 * n_streams
+
+
+# ---- the phase track (tfrec_amd_enable_burst_track_phase, the header's "Phase track"; DESIGN.md 6x)
+PHASE_AHEAD = 80  # the pairs carried from submit to submit: LAG_MAX + AHEAD, what c(k) >= m and z[k - i - m] can reach back to
+LAG_MIN, LAG_MAX = 1, 64  # m
+
+
+def lag_of(rate: int) -> int:
+    """tfrec_gpu -G rate,psk's m: a symbol in samples, floor((768000 + rate) / (2 rate)) (a usage error above 64)."""
+    return (768000 + int(rate)) // (2 * int(rate))
+
+
+def fresh_phase_state(n_streams: int) -> dict:
+    """What a phase context carries before its first submit: no pairs, no chain."""
+    return {"carry": np.zeros((n_streams, PHASE_AHEAD, 2), dtype=np.int16), "prior": np.zeros(n_streams, dtype=np.int64)}
+
+
+def _next_phase_state(dec, runs, state):
+    """The state behind the submit: every stream's last 80 pairs, and prior = min(80, prior' + n) of the stream's OPEN run."""
+    nxt = {"carry": np.array([burst._pairs(d)[-PHASE_AHEAD:] for d in dec], dtype=np.int16), "prior": np.zeros(len(dec), dtype=np.int64)}
+    for r in runs:
+        if int(r["flags"]) & RUN_OPEN:
+            s = int(r["stream"])
+            before = int(state["prior"][s]) if int(r["flags"]) & RUN_CONTINUES else 0
+            nxt["prior"][s] = min(PHASE_AHEAD, before + int(r["n_samples"]))
+    return nxt
+
+
+def carrier_index(A: int, B: int) -> int:
+    """The header's search, vectorised: the smallest r of 0 .. 4095 with score(r) = A C[r] + B S[r] > 0 that minimises
+    |cross(r)| = |B C[r] - A S[r]|; |A|, |B| < 2^43, so both stay below 2^59.  (A, B) != (0, 0)."""
+    A, B = int(A), int(B)
+    assert (A or B) and abs(A) < 1 << 43 and abs(B) < 1 << 43
+    c, s_ = tune.table()
+    c, s_ = c.astype(np.int64), s_.astype(np.int64)
+    score, cross = A * c + B * s_, np.abs(B * c - A * s_)
+    return int(np.argmin(np.where(score > 0, cross, np.iinfo(np.int64).max)))  # (argmin: the first of equal minima)
+
+
+def carrier_index_bruteforce(A: int, B: int) -> int:
+    """The same over all 4096 candidates in Python integers."""
+    c, s_ = tune.table()
+    best = None
+    for r in range(4096):
+        C, S = int(c[r]), int(s_[r])
+        if A * C + B * S > 0 and (best is None or abs(B * C - A * S) < best[0]):
+            best = (abs(B * C - A * S), r)
+    return best[1]
+
+
+def carrier_hz(r: int) -> int:
+    """centre_hz of a measured index: floor(375 rs / 4), rs = r below 2048 and r - 4096 otherwise."""
+    return 375 * (r if r < 2048 else r - 4096) // 4
+
+
+def head_carriers(dec, mask_or_thresh, runs, head, fallback=None, state=None, base=None):
+    """One submit's carrier records: head_centres' arguments, results and carried state, the centre of an entry without
+    CONTINUES measured as the header's "Phase track" words it -- the sums A, B of the head's counted products and the zero of the
+    cross term over the 4096 table directions."""
+    K = int(head)
+    assert HEAD_MIN <= K <= HEAD_MAX
+    state = fresh_centre_state(len(dec)) if state is None else state
+    fb = _fallbacks(fallback, len(dec))
+    out = np.zeros(len(runs), dtype=CENTRE_DTYPE)
+    for e, r in enumerate(runs):
+        s, a, n, cont = _window(dec, r, base)
+        o = _centre_copied(r)
+        if cont:
+            if int(state["index"][s]) >= 0:
+                o["source"], o["centre_hz"], o["index"] = INHERITED, int(state["centre_hz"][s]), int(state["index"][s])
+            else:
+                o["source"], o["centre_hz"], o["index"] = FALLBACK, fb[s], index_of(fb[s])
+            out[e] = o
+            continue
+        nh = min(n, K)
+        z = burst._pairs(dec[s]).astype(np.int64)
+        over = envelope._over(z, mask_or_thresh[s])[a:a + nh]
+        z = z[a:a + nh]
+        I, Q, Ip, Qp = z[1:, 0], z[1:, 1], z[:-1, 0], z[:-1, 1]
+        both = over[1:] & over[:-1]
+        A, B = int((I * Ip + Q * Qp)[both].sum()), int((Q * Ip - I * Qp)[both].sum())
+        P = int(np.count_nonzero(both))
+        o["n_counted"] = P
+        if P >= COUNT_MIN and (A or B):
+            ri = carrier_index(A, B)
+            o["source"], o["centre_hz"], o["index"] = MEASURED, carrier_hz(ri), ri
+        else:
+            o["source"], o["centre_hz"], o["index"] = FALLBACK, fb[s], index_of(fb[s])
+        out[e] = o
+    return out, _next_centre_state(len(dec), out)
+
+
+def head_carriers_bruteforce(dec, mask_or_thresh, runs, head, fallback=None, state=None, base=None):
+    """The same, one sample and one candidate at a time in Python integers, as the header words it."""
+    K = int(head)
+    state = fresh_centre_state(len(dec)) if state is None else state
+    fb = _fallbacks(fallback, len(dec))
+    out = np.zeros(len(runs), dtype=CENTRE_DTYPE)
+    for e, r in enumerate(runs):
+        s, a, n, cont = _window(dec, r, base)
+        o = _centre_copied(r)
+        cnt = 0
+        if cont:
+            idx = int(state["index"][s])
+            src, hz = (INHERITED, int(state["centre_hz"][s])) if idx >= 0 else (FALLBACK, fb[s])
+            idx = idx if idx >= 0 else index_of(hz)
+        else:
+            row = burst._pairs(dec[s]).tolist()
+            over = envelope._over(burst._pairs(dec[s]).astype(np.int64), mask_or_thresh[s]).tolist()
+            A = B = 0
+            for k in range(1, min(n, K)):
+                if over[a + k] and over[a + k - 1]:
+                    (i, q), (ip, qp) = row[a + k], row[a + k - 1]
+                    A, B, cnt = A + i * ip + q * qp, B + q * ip - i * qp, cnt + 1
+            if cnt >= COUNT_MIN and (A or B):
+                idx = carrier_index_bruteforce(A, B)
+                src, hz = MEASURED, carrier_hz(idx)
+            else:
+                src, hz = FALLBACK, fb[s]
+                idx = index_of(hz)
+        o["n_counted"], o["source"], o["centre_hz"], o["index"] = cnt, src, hz, idx
+        out[e] = o
+    return out, _next_centre_state(len(dec), out)
+
+
+def _phase_settings(smooth, lag):
+    L, m = int(smooth), int(lag)
+    assert 1 <= L <= AHEAD and LAG_MIN <= m <= LAG_MAX
+    return L, m
+
+
+def phase_tracks(dec, mask_or_thresh, runs, smooth, lag, head, fallback=None, state=None, base=None, max_samples=None):
+    """One submit of the phase track: the carrier records (head_carriers), then per entry the differential detector at lag m
+    about the entry's index r: u[k] = dm C[rm] + cm S[rm], rm = r m mod 4096, of the pairs at k and k - m, 0 where the chain holds
+    fewer than m samples ahead of k; t[k] = 1 iff the sum of u[k - i] over i < L is greater than 0.  state: (the 80 pairs and prior,
+    the centres') of the submit before, or None -> (carrier records, track records, words, the state behind the submit)."""
+    L, m = _phase_settings(smooth, lag)
+    pst, cst = state if state is not None else (None, None)
+    pst = fresh_phase_state(len(dec)) if pst is None else pst
+    cen, cst = head_carriers(dec, mask_or_thresh, runs, head, fallback, cst, base)
+    c, s_ = tune.table()
+    out = np.zeros(len(runs), dtype=TRACK_DTYPE)
+    tr = []
+    H = PHASE_AHEAD
+    for e, r in enumerate(runs):
+        s, a, n, cont = _window(dec, r, base)
+        rm = int(cen[e]["index"]) * m % 4096
+        C, S = int(c[rm]), int(s_[rm])
+        z = np.concatenate([np.asarray(pst["carry"][s], dtype=np.int64).reshape(H, 2), burst._pairs(dec[s]).astype(np.int64)])
+        cf = a - (int(pst["prior"][s]) if cont else 0)  # the chain's first sample, submit-relative (>= -80)
+        k = np.arange(a - (AHEAD - 1), a + n)  # every sample a product may be needed of; z's index is k + 80
+        ok = k - cf >= m  # (then k - m >= cf >= -80)
+        kk = np.where(ok, k, m)  # (a harmless index where the product is not used)
+        I, Q, Ip, Qp = z[kk + H, 0], z[kk + H, 1], z[kk + H - m, 0], z[kk + H - m, 1]
+        u = np.where(ok, (I * Ip + Q * Qp) * C + (Q * Ip - I * Qp) * S, 0)  # (|u| < 2^47)
+        cs = np.concatenate([[0], np.cumsum(u)])
+        p = np.arange(n) + AHEAD  # sample a + j is u[j + 15]: the sum of u[j + 16 - L .. j + 15]
+        t = (cs[p] - cs[p - L]) > 0
+        o = _copied(r)
+        over = envelope._over(burst._pairs(dec[s]).astype(np.int64), mask_or_thresh[s])[a:a + n]
+        idx = np.flatnonzero(over)
+        o["last_over"] = int(idx[-1]) if len(idx) else -1
+        o["n_ones"] = int(np.count_nonzero(t))
+        out[e] = o
+        tr.append(t.astype(np.uint8))
+    return cen, out, _pack(out, tr, max_samples), (_next_phase_state(dec, runs, pst), cst)
+
+
+def phase_tracks_bruteforce(dec, mask_or_thresh, runs, smooth, lag, head, fallback=None, state=None, base=None, max_samples=None):
+    """The same, one sample at a time in Python integers, as the header words it: c(k) counts from the chain's first sample."""
+    L, m = _phase_settings(smooth, lag)
+    pst, cst = state if state is not None else (None, None)
+    pst = fresh_phase_state(len(dec)) if pst is None else pst
+    cen, cst = head_carriers_bruteforce(dec, mask_or_thresh, runs, head, fallback, cst, base)
+    c, s_ = tune.table()
+    out = np.zeros(len(runs), dtype=TRACK_DTYPE)
+    tr = []
+    for e, r in enumerate(runs):
+        s, a, n, cont = _window(dec, r, base)
+        rm = int(cen[e]["index"]) * m % 4096
+        C, S = int(c[rm]), int(s_[rm])
+        row = burst._pairs(dec[s]).tolist()
+        ahead = np.asarray(pst["carry"][s]).reshape(PHASE_AHEAD, 2).tolist()
+        prior = int(pst["prior"][s]) if cont else 0
+        over = envelope._over(burst._pairs(dec[s]).astype(np.int64), mask_or_thresh[s]).tolist()
+
+        def z(k):  # run-relative; k < 0 only in a CONTINUES run, whose a == 0
+            return row[a + k] if a + k >= 0 else ahead[PHASE_AHEAD + a + k]
+
+        def u(k):
+            if k + prior < m:  # c(k) < m (c(k) < 0: ahead of the chain)
+                return 0
+            (i, q), (ip, qp) = z(k), z(k - m)
+            return (i * ip + q * qp) * C + (q * ip - i * qp) * S
+
+        t, last = [], -1
+        for k in range(n):
+            total = 0
+            for i in range(L):
+                total += u(k - i)
+            t.append(1 if total > 0 else 0)
+            if over[a + k]:
+                last = k
+        o = _copied(r)
+        o["last_over"], o["n_ones"] = last, sum(t)
+        out[e] = o
+        tr.append(np.array(t, dtype=np.uint8))
+    return cen, out, _pack(out, tr, max_samples), (_next_phase_state(dec, runs, pst), cst)
+
+
+def phase_device_bytes(n_streams: int, max_runs: int, max_samples: int) -> int:
+    """What tfrec_amd_enable_burst_track_phase adds to the device bytes: per FIFO set the track records, the bitmap, the set centres
+    and the centre records; per stream the carried 80 pairs, prior and the carried index and centre."""
+    from .api import FIFO_DEPTH
+    return (FIFO_DEPTH * (max_runs * (TRACK_DTYPE.itemsize + CENTRE_DTYPE.itemsize) + 4 * ((max_samples + 31) // 32) + 4 * n_streams) +
+            n_streams * (4 * PHASE_AHEAD + 4 + 8))
