@@ -183,6 +183,94 @@ def read_track(r, nb, base, L, centres, state, overflow=False, decs=None, levels
     return got, words, decs, state
 
 
+def read_amp(r, nb, base, L, lv, state, overflow=False, decs=None, levels=True):
+    """The oldest undrained submit's track records and words against amplitude_tracks on what the context itself returned ->
+    (records, words, decimated samples, the state behind the submit)."""
+    decs, runs, thr = submit_view(r, nb, decs, levels)
+    got, words = _read(r, "track", runs, overflow)
+    if not r.capture_overflow:
+        assert np.array_equal(got["bit_offset"], runs["pool_offset"]), "track: bit_offset is not the run's pool_offset"
+    want, wwords, state = track.amplitude_tracks(decs, thr, table_of(got), L, lv, state, base=base, max_samples=r._capture[1])
+    same_records(got, want, "amplitude track")
+    same_words(words, wwords, "amplitude track")
+    return got, words, decs, state
+
+
+def _read_centres(r, got, overflow, label):
+    cen = r.read_burst_track_centres(allow_overflow=overflow)
+    assert cen.dtype == track.CENTRE_DTYPE and len(cen) == len(got) and r.centre_total == r.track_total, (
+        "%s: %d records of %s for %d track records, totals %d and %d" % (label, len(cen), cen.dtype, len(got), r.centre_total, r.track_total))
+    same_table(cen, table_of(got), label)  # (the track's records repeat the table: _read; a full pool cuts the table short, not the records)
+    return cen
+
+
+def read_auto(r, nb, base, L, K, fb, state, overflow=False, decs=None, levels=True):
+    """The oldest undrained submit's centre records, track records and words against auto_tracks on what the context itself
+    returned -> (centre records, track records, words, decimated samples, the state behind the submit)."""
+    decs, runs, thr = submit_view(r, nb, decs, levels)
+    got, words = _read(r, "track", runs, overflow)
+    cen = _read_centres(r, got, overflow, "centre")
+    wcen, want, wwords, state = track.auto_tracks(decs, thr, table_of(got), L, K, fb, state, base=base, max_samples=r._capture[1])
+    same_records(cen, wcen, "centre")
+    same_records(got, want, "auto-centre track")
+    same_words(words, wwords, "auto-centre track")
+    assert np.array_equal(cen["index"], [track.index_of(h) for h in cen["centre_hz"]]) and not cen["reserved"].any(), "centre: index or reserved"
+    return cen, got, words, decs, state
+
+
+def read_phase(r, nb, base, L, m, K, fb, state, overflow=False, decs=None, levels=True):
+    """The oldest undrained submit's carrier records, track records and words against phase_tracks on what the context itself
+    returned -> (carrier records, track records, words, decimated samples, the state behind the submit)."""
+    decs, runs, thr = submit_view(r, nb, decs, levels)
+    got, words = _read(r, "track", runs, overflow)
+    cen = _read_centres(r, got, overflow, "carrier")
+    wcen, want, wwords, state = track.phase_tracks(decs, thr, table_of(got), L, m, K, fb, state, base=base, max_samples=r._capture[1])
+    same_records(cen, wcen, "carrier")
+    same_records(got, want, "phase track")
+    same_words(words, wwords, "phase track")
+    assert not cen["reserved"].any() and not cen["deviation_hz"].any(), "carrier: reserved or deviation_hz"
+    return cen, got, words, decs, state
+
+
+# ---- the track's modes: None (the frequency track about a set centre), ("amplitude", levels), ("auto", K), ("phase", K, lag)
+def mode_tracks(mode, decs, thr, runs, L, centres, state=None, base=None, max_samples=None, brute=False):
+    """One submit's restatement in the track's mode -> (centre records or None, track records, words, the state behind the submit:
+    the track's alone, or (the track's, the centres') in the modes that have centre records).  centres: the set centres, which
+    are the fallbacks of auto and phase; the amplitude mode has the mode's own levels in their place."""
+    kw = dict(base=base, max_samples=max_samples)
+    if mode is None:
+        return (None,) + (track.tracks_bruteforce if brute else track.tracks)(decs, thr, runs, L, centres, state, **kw)
+    if mode[0] == "amplitude":
+        return (None,) + (track.amplitude_tracks_bruteforce if brute else track.amplitude_tracks)(decs, thr, runs, L, mode[1], state, **kw)
+    if mode[0] == "auto":
+        return track.auto_tracks(decs, thr, runs, L, mode[1], centres, state, brute=brute, **kw)
+    return (track.phase_tracks_bruteforce if brute else track.phase_tracks)(decs, thr, runs, L, mode[2], mode[1], centres, state, **kw)
+
+
+def enable_mode(r, mode, L):
+    if mode is None:
+        r.enable_burst_track(L)
+    elif mode[0] == "amplitude":
+        r.enable_burst_track_amplitude(L)
+    elif mode[0] == "auto":
+        r.enable_burst_track_auto(L, mode[1])
+    else:
+        r.enable_burst_track_phase(L, mode[1], mode[2])
+
+
+def read_mode(r, mode, nb, base, L, centres, state, overflow=False, decs=None, levels=True):
+    """read_track, read_amp, read_auto or read_phase by the mode -> (centre records or None, records, words, decimated samples,
+    the state behind the submit)."""
+    kw = dict(overflow=overflow, decs=decs, levels=levels)
+    if mode is None:
+        return (None,) + read_track(r, nb, base, L, centres, state, **kw)
+    if mode[0] == "amplitude":
+        return (None,) + read_amp(r, nb, base, L, mode[1], state, **kw)
+    if mode[0] == "auto":
+        return read_auto(r, nb, base, L, mode[1], centres, state, **kw)
+    return read_phase(r, nb, base, L, mode[2], mode[1], centres, state, **kw)
+
+
 def read_sync(r, st, state, trecs, twords, overflow=False):
     """The oldest undrained submit's sync records and words against the restatement on the track records and words the context
     returned for it -> (records, words, the state behind the submit)."""

@@ -14,7 +14,7 @@ import amplitude_rows as A
 import parity
 import recorder as R
 from amplitude_rows import B, CONT, LEVELS, OPEN, W
-from recorder import cli_lines, hand_receiver, raises, same_chains, same_records
+from recorder import cli_lines, hand_receiver, raises, read_amp, same_chains, same_records
 from recorder_rows import CTX_TYPES, golden_iq, scene
 from tfrec_amd import api, decin, sync, track
 
@@ -26,19 +26,6 @@ def amp_receiver(n, nb, L, cap=None, **kw):
     r = hand_receiver(n, nb, (), cap=cap or (32 * n, n * nb * B), **kw)
     r.enable_burst_track_amplitude(L)
     return r
-
-
-def read_amp(r, nb, base, L, lv, state, overflow=False, decs=None, levels=True):
-    """The oldest undrained submit's track records and words against amplitude_tracks on what the context itself returned ->
-    (records, words, decimated samples, the state behind the submit)."""
-    decs, runs, thr = R.submit_view(r, nb, decs, levels)
-    got, words = R._read(r, "track", runs, overflow)
-    if not r.capture_overflow:
-        assert np.array_equal(got["bit_offset"], runs["pool_offset"]), "track: bit_offset is not the run's pool_offset"
-    want, wwords, state = track.amplitude_tracks(decs, thr, R.table_of(got), L, lv, state, base=base, max_samples=r._capture[1])
-    same_records(got, want, "amplitude track")
-    R.same_words(words, wwords, "amplitude track")
-    return got, words, decs, state
 
 
 key = lambda c: (int(c["stream"]), int(c["start_sample"]))  # noqa: E731

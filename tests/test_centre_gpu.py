@@ -16,7 +16,7 @@ import centre_rows as C
 import parity
 import recorder as R
 from centre_rows import B, CONT, FALLBACK, OPEN
-from recorder import cli_lines, hand_receiver, raises, same_chains, same_records, zeros
+from recorder import cli_lines, hand_receiver, raises, read_auto, same_chains, same_records, zeros
 from recorder_rows import CTX_TYPES, RATE, TELEGRAMS, golden_iq, scene
 from tfrec_amd import api, burst, decin, sync, track
 
@@ -31,22 +31,6 @@ def auto_receiver(n, nb, L, K, cap=None, **kw):
     r = hand_receiver(n, nb, (), cap=cap or (32 * n, n * nb * B), **kw)
     r.enable_burst_track_auto(L, K)
     return r
-
-
-def read_auto(r, nb, base, L, K, fb, state, overflow=False, decs=None, levels=True):
-    """The oldest undrained submit's centre records, track records and words against auto_tracks on what the context itself
-    returned -> (centre records, track records, words, decimated samples, the state behind the submit)."""
-    decs, runs, thr = R.submit_view(r, nb, decs, levels)
-    got, words = R._read(r, "track", runs, overflow)
-    cen = r.read_burst_track_centres(allow_overflow=overflow)
-    assert cen.dtype == track.CENTRE_DTYPE and len(cen) == len(got) and r.centre_total == r.track_total
-    R.same_table(cen, R.table_of(got), "centre")  # (the track's records repeat the table: _read; a full pool cuts the table short, not the records)
-    wcen, want, wwords, state = track.auto_tracks(decs, thr, R.table_of(got), L, K, fb, state, base=base, max_samples=r._capture[1])
-    same_records(cen, wcen, "centre")
-    same_records(got, want, "auto-centre track")
-    R.same_words(words, wwords, "auto-centre track")
-    assert np.array_equal(cen["index"], [track.index_of(h) for h in cen["centre_hz"]]) and not cen["reserved"].any()
-    return cen, got, words, decs, state
 
 
 # ---- hand-made rows on a channel-rate context

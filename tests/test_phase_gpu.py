@@ -15,7 +15,7 @@ import parity
 import phase_rows as P
 import recorder as R
 from phase_rows import B, CONT, FALLBACK, OPEN
-from recorder import cli_lines, hand_receiver, raises, same_chains, same_records, zeros
+from recorder import cli_lines, hand_receiver, raises, read_phase, same_chains, same_records, zeros
 from recorder_rows import CTX_TYPES, golden_iq, quiet, scene
 from tfrec_amd import api, burst, decin, sync, track
 
@@ -30,22 +30,6 @@ def phase_receiver(n, nb, L, m, K, cap=None, **kw):
     r = hand_receiver(n, nb, (), cap=cap or (32 * n, n * nb * B), **kw)
     r.enable_burst_track_phase(L, K, m)
     return r
-
-
-def read_phase(r, nb, base, L, m, K, fb, state, overflow=False, decs=None, levels=True):
-    """The oldest undrained submit's carrier records, track records and words against phase_tracks on what the context itself
-    returned -> (carrier records, track records, words, decimated samples, the state behind the submit)."""
-    decs, runs, thr = R.submit_view(r, nb, decs, levels)
-    got, words = R._read(r, "track", runs, overflow)
-    cen = r.read_burst_track_centres(allow_overflow=overflow)
-    assert cen.dtype == track.CENTRE_DTYPE and len(cen) == len(got) and r.centre_total == r.track_total
-    R.same_table(cen, R.table_of(got), "carrier")
-    wcen, want, wwords, state = track.phase_tracks(decs, thr, R.table_of(got), L, m, K, fb, state, base=base, max_samples=r._capture[1])
-    same_records(cen, wcen, "carrier")
-    same_records(got, want, "phase track")
-    R.same_words(words, wwords, "phase track")
-    assert not cen["reserved"].any() and not cen["deviation_hz"].any()
-    return cen, got, words, decs, state
 
 
 # ---- hand-made rows on a channel-rate context

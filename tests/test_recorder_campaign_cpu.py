@@ -3,15 +3,19 @@ reach every edge class the campaign names (measured back from capture.captures o
 class of the burst sync's (measured back from its restatement on the plans), the sync's settings leave the earlier seeds' plans as
 they were, the restatements the kernels are held to equal their per-sample forms at those edges, and the campaign's own checks --
 run against a model of the receiver put together from the restatements -- pass, notice one planted wrong bit, and notice a sync
-that is wrong by one in each of the places where a kernel could be."""
+that is wrong by one in each of the places where a kernel could be.  The same for the track's amplitude, auto-centre and phase modes:
+MODE_SEEDS reach every label of MODE_CLASSES, at most a quarter of the auto and phase chains are exempt from the merged check, the
+fast restatements of the modes equal their per-sample forms, the campaign with modes on passes on the model, notices a planted bit
+in the centre records and in each mode's track, and notices each of the mistakes of MODE_WRONG."""
 import functools
 import hashlib
 
 import numpy as np
 import pytest
 
+import recorder as R
 import recorder_campaign as RC
-from tfrec_amd import api, burst, capture, clock, decin, envelope, levels, sync, track
+from tfrec_amd import api, burst, capture, clock, decin, envelope, levels, sync, track, tune
 
 B = RC.B
 
@@ -237,6 +241,8 @@ class ModelReceiver:
     one read whose result is returned with one bit wrong."""
     plant = None
     syncs = staticmethod(sync.syncs)
+    mode_tracks = staticmethod(R.mode_tracks)
+    inherit_wrong = False
 
     def __init__(self, n_streams, types_mask, thresh, filter_type, max_blocks, decimated, levels):
         assert decimated and levels
@@ -244,7 +250,7 @@ class ModelReceiver:
         self.masks, self.thr, self.on, self.q = [types_mask] * n, [thresh] * n, set(), []
         self.cst, self.lst, self.base, self.prev, self.tst = [None] * n, [None] * n, [0] * n, [np.zeros(2, dtype=np.int16)] * n, None
         self.centres = [0] * n
-        self.sync, self.sst = None, None
+        self.sync, self.sst, self.mode = None, None, None
 
     def __enter__(self):
         return self
@@ -271,6 +277,23 @@ class ModelReceiver:
     def enable_burst_track(self, smooth):
         self.on.add("track")
         self.L = smooth
+
+    def enable_burst_track_amplitude(self, smooth):
+        self.enable_burst_track(smooth)
+        self.mode = ("amplitude", [0] * self.n_streams)
+
+    def enable_burst_track_auto(self, smooth, head=1024):
+        self.enable_burst_track(smooth)
+        self.mode = ("auto", head)
+
+    def enable_burst_track_phase(self, smooth, head=1024, lag=1):
+        self.enable_burst_track(smooth)
+        self.mode = ("phase", head, lag)
+
+    def set_burst_track_level(self, streams, level):
+        assert self.mode[0] == "amplitude"
+        for s, v in zip(streams, level):
+            self.mode[1][s] = v
 
     def enable_burst_sync(self, rate, pattern, n_bits, max_errors=0, both=False):
         assert "track" in self.on
@@ -305,9 +328,14 @@ class ModelReceiver:
         if "clock" in self.on:
             e["clock"] = clock.clocks(decs, runs[:mr], base=self.base)
         if "track" in self.on:
-            recs, words, _ = track.tracks(decs, thr, runs[:mr], self.L, self.centres, self.tst, base=self.base, max_samples=ms)
-            self.tst = track.tracks(decs, thr, runs, self.L, self.centres, self.tst, base=self.base)[2]
+            cen, recs, words, own = self.mode_tracks(self.mode, decs, thr, runs[:mr], self.L, self.centres, self.tst, base=self.base,
+                                                     max_samples=ms)
+            self.tst = self.mode_tracks(self.mode, decs, thr, runs, self.L, self.centres, self.tst, base=self.base)[3]
             e["track"] = (recs, words[:(len(e["prefix"][1]) + 31) // 32])
+            if cen is not None:  # the carried pairs and prior: the whole table's; the carried index: the delivered records'
+                e["centres"] = cen
+                if not self.inherit_wrong:
+                    self.tst = (self.tst[0], own[1])
             if self.sync is not None:  # on the delivered records and the runs that fit, as the header's Bits paragraph states
                 srecs, swords, self.sst = self.syncs(recs, e["track"][1], self.sync, self.sst, n, max_samples=ms)
                 e["sync"] = (srecs, swords[:len(e["track"][1])])
@@ -354,6 +382,11 @@ class ModelReceiver:
     def read_burst_tracks(self, allow_overflow=False):
         e, out = self._oldest("track", allow_overflow, samples=True)
         self.track_total = len(e["runs"])
+        return out
+
+    def read_burst_track_centres(self, allow_overflow=False):
+        e, out = self._oldest("centres", allow_overflow)
+        self.centre_total = len(e["runs"])
         return out
 
     def read_burst_syncs(self, allow_overflow=False):
@@ -440,3 +473,232 @@ def test_the_campaign_passes_on_a_model_of_the_receiver_and_notices_a_planted_bi
         assert 1 <= bad <= uses, name
         out = capsys.readouterr().out
         assert out.count("MISMATCH") == bad and "seed %d round" % seed in out and "streams" in out, out
+
+
+# ---- the track's modes in the campaign
+@functools.lru_cache(maxsize=None)
+def mode_plans():
+    return [p for seed in RC.MODE_SEEDS for p in RC.plans(seed, RC.ROUNDS, modes=True)]
+
+
+@functools.lru_cache(maxsize=None)
+def mode_hits():
+    hit = set()
+    for p in mode_plans():
+        hit |= RC.mode_classes_hit(p)
+    return hit
+
+
+@pytest.mark.parametrize("label", RC.MODE_CLASSES)
+def test_the_mode_seeds_reach_every_mode_class(label):
+    assert label in mode_hits()
+
+
+def test_the_mode_rounds_draw_their_settings_and_leave_the_old_seeds_alone():
+    assert 4 <= len(RC.MODE_SEEDS) <= 6 and not set(RC.MODE_SEEDS) & set(RC.SEEDS)
+    assert all(p["mode"] is None for p in fixed_plans())  # the six old seeds stay in frequency mode (their digests: above)
+    ps = mode_plans()
+    assert [p["mode"][0] for p in ps] == ["amplitude", "auto", "phase"] * (len(ps) // 3) and all("track" in p["measure"] for p in ps)
+    with_sync = [p for p in ps if p["sync"] is not None]
+    assert len(ps) // 3 < len(with_sync) < 5 * len(ps) // 6 and {p["mode"][0] for p in with_sync} == {"amplitude", "auto", "phase"}
+    Ks = [p["mode"][1] for p in ps if p["mode"][0] != "amplitude"]
+    lags = [p["mode"][2] for p in ps if p["mode"][0] == "phase"]
+    assert {64, 4096} <= set(Ks) and any(66 < K < 4096 for K in Ks) and {1, 64} <= set(lags) and any(1 < m < 64 for m in lags)
+    assert any((p["L"], p["mode"][2]) == (16, 64) for p in ps if p["mode"][0] == "phase")
+    lv = [(v, t) for p in ps if p["mode"][0] == "amplitude" for v, t in zip(p["mode"][1], p["thresh"])]
+    assert {0, 65535, 3000, 2999} <= {v for v, _ in lv} and any(v == t for v, t in lv)
+    assert {-192000, 0, 192000} <= {c for p in ps if p["mode"][0] != "amplitude" for c in p["centres"]}
+    assert all(" mode %s " % p["mode"][0] in RC.describe(p) for p in ps)
+    kinds = np.random.default_rng(1)  # the default call paints what it painted: the extra kinds are drawn only where they are asked for
+    assert RC.rows(kinds, 2, 2, [694, 356], cuts=(1,), extra=()).tobytes() == RC.rows(np.random.default_rng(1), 2, 2, [694, 356], cuts=(1,)).tobytes()
+
+
+def test_at_most_a_quarter_of_the_auto_and_phase_chains_are_exempt_from_the_merged_check():
+    """A chain whose first piece begins fewer than K samples ahead of a cut and reaches it has a shorter head than the uncut run:
+    run_plan compares its flags and length alone.  The condition, counted on the plans."""
+    counts = [RC.exempt_counts(p) for p in mode_plans()]
+    ex, chains = sum(c[0] for c in counts), sum(c[1] for c in counts)
+    assert sum(1 for c in counts if c[1]) >= 6 and ex >= 1 and 4 * ex <= chains, (ex, chains)
+
+
+def test_there_is_a_tie_in_the_carrier_search_and_the_smaller_index_wins():
+    ties = RC.tie_pairs()
+    assert len(ties) == 1048 and ties[-1][2] == (0, 4095)
+    for i, q, (r0, r1) in ties[:3] + ties[-3:]:
+        for g in (1, 200 * 64):
+            assert track.carrier_index(g * i, g * q) == track.carrier_index_bruteforce(g * i, g * q) == r0 < r1
+
+
+def mode_brute_equals_fast(x, masks, thresh, sizes, L, centres, mode, first=None):
+    """brute_equals_fast for a mode: amplitude_tracks, head_centres and tracks about them, head_carriers and phase_tracks against
+    their per-sample forms, submit by submit, the carried state included."""
+    n, dec = len(x), decin.clamp(x)
+    mode = (mode[0], mode[1][:n]) if mode[0] == "amplitude" else mode  # (a level per stream)
+    cst, lst, fast, brute, pos, base, total = [None] * n, [None] * n, None, None, 0, [0] * n, 0
+    for nb in sizes:
+        decs = [np.ascontiguousarray(dec[s, pos * B:(pos + nb) * B]).reshape(-1) for s in range(n)]
+        per, thr = [], []
+        for s in range(n):
+            runs, pool, cst[s] = capture.captures(decs[s], masks[s], thresh[s], cst[s])
+            lev, lst[s] = levels.levels(decs[s], masks[s], thresh[s], lst[s])
+            per.append((runs, pool))
+            thr.append(np.repeat(lev["thresh"].astype(np.int64), B))
+        table = capture.table(per)[0][:first]
+        a = R.mode_tracks(mode, decs, thr, table, L, centres, fast, base=base)
+        b = R.mode_tracks(mode, decs, thr, table, L, centres, brute, base=base, brute=True)
+        if a[0] is not None:
+            RC.same_records(a[0], b[0], "centres")
+        RC.same_records(a[1], b[1], "tracks")
+        assert np.array_equal(a[2], b[2]), "words"
+        fast, brute = a[3], b[3]
+        for u, v in zip(fast if isinstance(fast, tuple) else (fast,), brute if isinstance(brute, tuple) else (brute,)):
+            assert sorted(u) == sorted(v) and all(np.array_equal(u[f], v[f]) for f in u), "the carried state"
+        total += len(table)
+        pos, base = pos + nb, [v + nb * B for v in base]
+    return total
+
+
+MODES = (("amplitude", [3000, 100]), ("auto", 128), ("phase", 128, 7))
+
+
+@pytest.mark.parametrize("mode", MODES, ids=lambda m: m[0])
+def test_the_fast_mode_restatements_equal_the_per_sample_ones_on_a_generated_round(mode):
+    rng = np.random.default_rng(RC.MODE_SEEDS[0])
+    masks, sizes = [0x2F, 0x02], (1, 1)
+    x = RC.rows(rng, 2, 2, [RC.window(m) for m in masks], cuts=(1,), extra=RC.MODE_KINDS)
+    assert mode_brute_equals_fast(x, masks, [RC.T, 90], sizes, 7, [20000, -192000], mode) >= 10
+
+
+@pytest.mark.parametrize("mode", MODES, ids=lambda m: m[0])
+def test_the_fast_mode_restatements_equal_the_per_sample_ones_on_the_dense_rows_first_40_runs(mode):
+    assert mode_brute_equals_fast(RC.dense_heads(2, (1, 4, 7))[None], [0x02], [RC.T], (2,), 16, [35000], mode, first=40) == 40
+
+
+# ---- a mode's restatement that is wrong in one place, where a kernel could be wrong by one
+MODE_WRONG = {  # the mistake -> what it is; a seed of MODE_SEEDS notices each
+    "head:K+1": "the head takes one product too many (k <= nh)",
+    "count:>64": "P > 64 instead of P >= 64",
+    "occ:floor": "a bin is occupied from P // 16 on",
+    "mask:one-sample": "only the later sample's over bit is tested",
+    "wrap:unsigned": "lo and hi are taken without the rotation by 32",
+    "zero-sums:measured": "sums of (0, 0) are measured: no candidate has a positive score, index 0 stays",
+    "tie:larger-r": "of two candidates with equal |cross| the larger index is kept",
+    "lag:edge": "k - cf <= lag is taken for undefined",
+    "prior:ignored": "cf = the run's start in a continuing piece",
+    "inherit:after-overflow": "an index is carried from an OPEN entry that had no record",
+    "amp:>=": "sum >= L * level",
+    "amp:prior": "a continuing piece's prior is taken one too small: the power of the chain's first sample is dropped"}
+# prior:79 -- the phase track's prior clamped at 79 -- cannot be noticed in what a context returns: a product at k' >= -(L - 1) of a
+# continuing piece is defined iff k' + prior >= m, and with L + m <= 80 both 79 and 80 define every one of them.  In the same way
+# the amplitude track's prior of 16 taken as 15 defines every power L <= 16 reaches; amp:prior is therefore the mistake one step on
+
+
+def wrong_mode_tracks(mode, decs, thr, runs, L, centres, state=None, base=None, max_samples=None, brute=False, wrong=None):
+    """recorder.mode_tracks for the three modes written out once more, entry by entry on definedness masks, with one place to be
+    wrong at (wrong=None: nowhere)."""
+    if mode is None:
+        return R.mode_tracks(mode, decs, thr, runs, L, centres, state, base, max_samples)
+    name, n = mode[0], len(decs)
+    heads, ahead = name != "amplitude", track.PHASE_AHEAD if name == "phase" else track.AHEAD
+    tst, cst = (state if state is not None else (None, None)) if heads else (state, None)
+    tst = tst if tst is not None else {"carry": np.zeros((n, ahead, 2), dtype=np.int16), "prior": np.zeros(n, dtype=np.int64)}
+    cst = cst if cst is not None else track.fresh_centre_state(n)
+    tc, ts = (t.astype(np.int64) for t in tune.table())
+    index_of = lambda hz: (8192 * hz + 384000) // 768000 % 4096  # noqa: E731
+    out, tr = np.zeros(len(runs), dtype=track.TRACK_DTYPE), []
+    cen = np.zeros(len(runs), dtype=track.CENTRE_DTYPE) if heads else None
+    for e, r in enumerate(runs):
+        s, a, nn, cont = track._window(decs, r, base)
+        z = burst._pairs(decs[s]).astype(np.int64)
+        over = envelope._over(z, thr[s])
+        prior = int(tst["prior"][s]) if cont else 0
+        if heads:  # ---- the entry's centre
+            o, K, fb = track._centre_copied(r), mode[1], int(centres[s])
+            src, hz, dev, cnt, idx = track.FALLBACK, fb, 0, 0, index_of(fb)
+            if cont:
+                if int(cst["index"][s]) >= 0:
+                    src, hz, idx = track.INHERITED, int(cst["centre_hz"][s]), int(cst["index"][s])
+            else:
+                nh = min(min(nn, K) + (wrong == "head:K+1"), len(z) - a)
+                zz, ov = z[a:a + nh], over[a:a + nh]
+                both = ov[1:] & (ov[:-1] | (wrong == "mask:one-sample"))
+                dot, crs = (zz[1:, 0] * zz[:-1, 0] + zz[1:, 1] * zz[:-1, 1])[both], (zz[1:, 1] * zz[:-1, 0] - zz[1:, 0] * zz[:-1, 1])[both]
+                cnt = len(dot)
+                if cnt > track.COUNT_MIN - (wrong != "count:>64"):
+                    if name == "auto":
+                        h = np.bincount(burst._bins(dot, crs), minlength=burst.N_BINS)
+                        occ = np.flatnonzero(h >= (cnt // 16 if wrong == "occ:floor" else (cnt + 15) // 16))
+                        if wrong != "wrap:unsigned":
+                            occ = np.where(occ < burst.N_BINS // 2, occ, occ - burst.N_BINS)
+                        if len(occ):
+                            src, hz, dev = track.MEASURED, 3000 * int(occ.min() + occ.max()), 3000 * int(occ.max() - occ.min())
+                            idx = index_of(hz)
+                    else:
+                        A, Bs = int(dot.sum()), int(crs.sum())
+                        if A or Bs or wrong == "zero-sums:measured":
+                            cross = np.where(A * tc + Bs * ts > 0, np.abs(Bs * tc - A * ts), np.iinfo(np.int64).max)
+                            best = np.flatnonzero(cross == cross.min())
+                            idx = int(best[-1] if wrong == "tie:larger-r" else best[0])
+                            src, hz = track.MEASURED, track.carrier_hz(idx)
+            o["n_counted"], o["source"], o["centre_hz"], o["deviation_hz"], o["index"] = cnt, src, hz, dev, idx
+            cen[e] = o
+        # ---- the entry's track: the terms at k = -(L - 1) .. nn - 1, run-relative, each with whether it is defined
+        ext = np.concatenate([np.asarray(tst["carry"][s], dtype=np.int64).reshape(ahead, 2), z])
+        k = np.arange(-(L - 1), nn)
+        at = a + k + ahead
+        if name == "amplitude":
+            val, first, limit = np.abs(ext[at, 0]) + np.abs(ext[at, 1]), int(wrong == "amp:prior" and cont), L * int(mode[1][s])
+        else:
+            m = mode[2] if name == "phase" else 1
+            first = m + (wrong == "lag:edge" and name == "phase")
+            prior = 0 if wrong == "prior:ignored" and name == "phase" else prior
+            lo = np.maximum(at - m, 0)  # (a harmless index where the term is not defined)
+            I, Q, Ip, Qp = ext[at, 0], ext[at, 1], ext[lo, 0], ext[lo, 1]
+            if name == "phase":
+                rm = idx * m % 4096
+                val = (I * Ip + Q * Qp) * tc[rm] + (Q * Ip - I * Qp) * ts[rm]
+            else:
+                val = (Q * Ip - I * Qp) * tc[idx] - (I * Ip + Q * Qp) * ts[idx]
+            limit = 0
+        cs = np.concatenate([[0], np.cumsum(np.where(k + prior >= first, val, 0))])
+        sums = cs[L:] - cs[:-L]
+        t = sums >= limit if wrong == "amp:>=" else sums > limit
+        o = track._copied(r)
+        w = np.flatnonzero(over[a:a + nn])
+        o["last_over"], o["n_ones"] = int(w[-1]) if len(w) else -1, int(np.count_nonzero(t))
+        out[e] = o
+        tr.append(t.astype(np.uint8))
+    nxt = {"carry": np.array([burst._pairs(d)[-ahead:] for d in decs], dtype=np.int16), "prior": np.zeros(n, dtype=np.int64)}
+    for r in runs:
+        if int(r["flags"]) & capture.RUN_OPEN:
+            s = int(r["stream"])
+            nxt["prior"][s] = min(ahead, (int(tst["prior"][s]) if int(r["flags"]) & capture.RUN_CONTINUES else 0) + int(r["n_samples"]))
+    return cen, out, track._pack(out, tr, max_samples), (nxt, track._next_centre_state(n, cen)) if heads else nxt
+
+
+def mode_mistaken(wrong):
+    return type("Mistaken", (ModelReceiver,), {"mode_tracks": staticmethod(functools.partial(wrong_mode_tracks, wrong=wrong)),
+                                               "inherit_wrong": wrong == "inherit:after-overflow"})
+
+
+def test_the_modes_written_out_once_more_are_the_restatements(capsys):
+    assert sum(RC.campaign(seed, RC.ROUNDS, verbose=False, receiver=mode_mistaken(None), modes=True) for seed in RC.MODE_SEEDS) == 0
+    assert capsys.readouterr().out == ""
+
+
+@pytest.mark.parametrize("wrong", sorted(MODE_WRONG))
+def test_the_mode_campaign_notices_a_mode_that_is_wrong_in_one_place(wrong, capsys):
+    assert any(RC.campaign(seed, RC.ROUNDS, verbose=False, receiver=mode_mistaken(wrong), modes=True) for seed in RC.MODE_SEEDS)  # (the first is enough)
+    assert "MISMATCH" in capsys.readouterr().out
+
+
+def test_the_mode_campaign_passes_on_a_model_of_the_receiver_and_notices_a_planted_bit(capsys):
+    assert sum(RC.campaign(seed, RC.ROUNDS, verbose=False, receiver=ModelReceiver, modes=True) for seed in RC.MODE_SEEDS) == 0
+    assert capsys.readouterr().out == ""
+    seed = RC.MODE_SEEDS[0]
+    ps = RC.plans(seed, RC.ROUNDS, modes=True)
+    for name, uses in (("centres", sum(1 for p in ps if p["mode"][0] != "amplitude")), ("track", len(ps))):
+        bad = RC.campaign(seed, RC.ROUNDS, verbose=False, receiver=planted(name), modes=True)
+        assert 1 <= bad <= uses and (name != "track" or bad >= 3), (name, bad)  # (the track: in each of the three modes)
+        out = capsys.readouterr().out
+        assert out.count("MISMATCH") == bad and " mode " in out, out

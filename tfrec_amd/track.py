@@ -108,6 +108,29 @@ def _pack(out, tr, max_samples):
     return np.packbits(flat.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1)
 
 
+class _Rows:
+    """Per stream and per call, computed once however many entries the stream has: its pairs as int64, its over bits, and the
+    pairs behind the carried ones."""
+
+    def __init__(self, dec, mask_or_thresh, carry=None):
+        self.dec, self.mot, self.carry, self.z, self.ov, self.ex = dec, mask_or_thresh, carry, {}, {}, {}
+
+    def pairs(self, s):
+        if s not in self.z:
+            self.z[s] = burst._pairs(self.dec[s]).astype(np.int64)
+        return self.z[s]
+
+    def over(self, s):
+        if s not in self.ov:
+            self.ov[s] = envelope._over(self.pairs(s), self.mot[s])
+        return self.ov[s]
+
+    def extended(self, s):
+        if s not in self.ex:
+            self.ex[s] = np.concatenate([np.asarray(self.carry[s], dtype=np.int64).reshape(-1, 2), self.pairs(s)])
+        return self.ex[s]
+
+
 def tracks(dec, mask_or_thresh, runs, smooth, centres=None, state=None, base=None, max_samples=None, run_index=None):
     """One submit.  dec[s]: stream s's decimated samples of the submit (int16 pairs, as tfrec_amd_read_decimated returns them);
     mask_or_thresh[s]: its over bits or the threshold behind them (envelope.envelopes'); runs: the submit's table (RUN_DTYPE);
@@ -122,11 +145,12 @@ def tracks(dec, mask_or_thresh, runs, smooth, centres=None, state=None, base=Non
     c, s_ = tune.table()
     out = np.zeros(len(runs), dtype=TRACK_DTYPE)
     tr = []
+    rows = _Rows(dec, mask_or_thresh, state["carry"])
     for e, r in enumerate(runs):
         s, a, n, cont = _window(dec, r, base)
         ri = int(run_index[e]) if run_index is not None else index_of(centres[s]) if centres is not None else 0
         C, S = int(c[ri]), int(s_[ri])
-        z = np.concatenate([np.asarray(state["carry"][s], dtype=np.int64).reshape(AHEAD, 2), burst._pairs(dec[s]).astype(np.int64)])
+        z = rows.extended(s)
         cf = a - (int(state["prior"][s]) if cont else 0)  # the chain's first sample, submit-relative
         m = np.arange(a - (AHEAD - 1), a + n)  # every sample a product may be needed of; z's index is m + 16
         I, Q, Ip, Qp = z[m + AHEAD, 0], z[m + AHEAD, 1], z[m + AHEAD - 1, 0], z[m + AHEAD - 1, 1]
@@ -135,7 +159,7 @@ def tracks(dec, mask_or_thresh, runs, smooth, centres=None, state=None, base=Non
         p = np.arange(n) + AHEAD  # sample a + k is v[k + 15]: the sum of v[k + 16 - L .. k + 15]
         t = (cs[p] - cs[p - L]) > 0
         o = _copied(r)
-        over = envelope._over(burst._pairs(dec[s]).astype(np.int64), mask_or_thresh[s])[a:a + n]
+        over = rows.over(s)[a:a + n]
         idx = np.flatnonzero(over)
         o["last_over"] = int(idx[-1]) if len(idx) else -1
         o["n_ones"] = int(np.count_nonzero(t))
@@ -203,9 +227,10 @@ def amplitude_tracks(dec, mask_or_thresh, runs, smooth, levels=None, state=None,
     lv = _levels(levels, len(dec))
     out = np.zeros(len(runs), dtype=TRACK_DTYPE)
     tr = []
+    rows = _Rows(dec, mask_or_thresh, state["carry"])
     for e, r in enumerate(runs):
         s, a, n, cont = _window(dec, r, base)
-        z = np.concatenate([np.asarray(state["carry"][s], dtype=np.int64).reshape(AHEAD, 2), burst._pairs(dec[s]).astype(np.int64)])
+        z = rows.extended(s)
         cf = a - (int(state["prior"][s]) if cont else 0)  # the chain's first sample, submit-relative
         m = np.arange(a - (AHEAD - 1), a + n)  # every sample a power may be needed of; z's index is m + 16
         p = np.where(m >= cf, np.abs(z[m + AHEAD, 0]) + np.abs(z[m + AHEAD, 1]), 0)  # (<= 65536)
@@ -213,7 +238,7 @@ def amplitude_tracks(dec, mask_or_thresh, runs, smooth, levels=None, state=None,
         q = np.arange(n) + AHEAD  # sample a + k is p[k + 15]: the sum of p[k + 16 - L .. k + 15]
         t = (cs[q] - cs[q - L]) > L * lv[s]
         o = _copied(r)
-        over = envelope._over(burst._pairs(dec[s]).astype(np.int64), mask_or_thresh[s])[a:a + n]
+        over = rows.over(s)[a:a + n]
         idx = np.flatnonzero(over)
         o["last_over"] = int(idx[-1]) if len(idx) else -1
         o["n_ones"] = int(np.count_nonzero(t))
@@ -329,6 +354,7 @@ def head_centres(dec, mask_or_thresh, runs, head, fallback=None, state=None, bas
     state = fresh_centre_state(len(dec)) if state is None else state
     fb = _fallbacks(fallback, len(dec))
     out = np.zeros(len(runs), dtype=CENTRE_DTYPE)
+    rows = _Rows(dec, mask_or_thresh)
     sign = np.where(np.arange(burst.N_BINS) < burst.N_BINS // 2, np.arange(burst.N_BINS), np.arange(burst.N_BINS) - burst.N_BINS)
     for e, r in enumerate(runs):
         s, a, n, cont = _window(dec, r, base)
@@ -341,9 +367,8 @@ def head_centres(dec, mask_or_thresh, runs, head, fallback=None, state=None, bas
             out[e] = o
             continue
         nh = min(n, K)
-        z = burst._pairs(dec[s]).astype(np.int64)
-        over = envelope._over(z, mask_or_thresh[s])[a:a + nh]
-        z = z[a:a + nh]
+        over = rows.over(s)[a:a + nh]
+        z = rows.pairs(s)[a:a + nh]
         I, Q, Ip, Qp = z[1:, 0], z[1:, 1], z[:-1, 0], z[:-1, 1]
         both = over[1:] & over[:-1]
         dot, crs = (I * Ip + Q * Qp)[both], (Q * Ip - I * Qp)[both]
@@ -603,6 +628,7 @@ def head_carriers(dec, mask_or_thresh, runs, head, fallback=None, state=None, ba
     state = fresh_centre_state(len(dec)) if state is None else state
     fb = _fallbacks(fallback, len(dec))
     out = np.zeros(len(runs), dtype=CENTRE_DTYPE)
+    rows = _Rows(dec, mask_or_thresh)
     for e, r in enumerate(runs):
         s, a, n, cont = _window(dec, r, base)
         o = _centre_copied(r)
@@ -614,9 +640,8 @@ def head_carriers(dec, mask_or_thresh, runs, head, fallback=None, state=None, ba
             out[e] = o
             continue
         nh = min(n, K)
-        z = burst._pairs(dec[s]).astype(np.int64)
-        over = envelope._over(z, mask_or_thresh[s])[a:a + nh]
-        z = z[a:a + nh]
+        over = rows.over(s)[a:a + nh]
+        z = rows.pairs(s)[a:a + nh]
         I, Q, Ip, Qp = z[1:, 0], z[1:, 1], z[:-1, 0], z[:-1, 1]
         both = over[1:] & over[:-1]
         A, B = int((I * Ip + Q * Qp)[both].sum()), int((Q * Ip - I * Qp)[both].sum())
@@ -683,11 +708,12 @@ def phase_tracks(dec, mask_or_thresh, runs, smooth, lag, head, fallback=None, st
     out = np.zeros(len(runs), dtype=TRACK_DTYPE)
     tr = []
     H = PHASE_AHEAD
+    rows = _Rows(dec, mask_or_thresh, pst["carry"])
     for e, r in enumerate(runs):
         s, a, n, cont = _window(dec, r, base)
         rm = int(cen[e]["index"]) * m % 4096
         C, S = int(c[rm]), int(s_[rm])
-        z = np.concatenate([np.asarray(pst["carry"][s], dtype=np.int64).reshape(H, 2), burst._pairs(dec[s]).astype(np.int64)])
+        z = rows.extended(s)
         cf = a - (int(pst["prior"][s]) if cont else 0)  # the chain's first sample, submit-relative (>= -80)
         k = np.arange(a - (AHEAD - 1), a + n)  # every sample a product may be needed of; z's index is k + 80
         ok = k - cf >= m  # (then k - m >= cf >= -80)
@@ -698,7 +724,7 @@ def phase_tracks(dec, mask_or_thresh, runs, smooth, lag, head, fallback=None, st
         p = np.arange(n) + AHEAD  # sample a + j is u[j + 15]: the sum of u[j + 16 - L .. j + 15]
         t = (cs[p] - cs[p - L]) > 0
         o = _copied(r)
-        over = envelope._over(burst._pairs(dec[s]).astype(np.int64), mask_or_thresh[s])[a:a + n]
+        over = rows.over(s)[a:a + n]
         idx = np.flatnonzero(over)
         o["last_over"] = int(idx[-1]) if len(idx) else -1
         o["n_ones"] = int(np.count_nonzero(t))
