@@ -244,7 +244,8 @@ def mint_iq_fixtures(tmp):
 def scene_cases():
     """The scenes pinned in scenes.json: every row of the families but the dense ones, which are pinned at 4 blocks (their
     full 24-block form is checked for packing on the oracle by tests/test_scenes_cpu.py); the level rows also with the
-    auto threshold and the wide filter."""
+    auto threshold and the wide filter.  The frames and splices families come last: a re-mint adds their lines and leaves
+    the others as they are."""
     from oracle import scenes as S
 
     cases = []

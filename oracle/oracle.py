@@ -101,6 +101,8 @@ def lib():
         L.orc_num_dec.argtypes = [C.c_void_p]
         L.orc_dec.restype = C.POINTER(C.c_int16)
         L.orc_dec.argtypes = [C.c_void_p]
+        L.orc_pending_bits.restype = C.c_size_t
+        L.orc_pending_bits.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         L.orc_thresh.restype = C.c_int
         L.orc_thresh.argtypes = [C.c_void_p]
         L.orc_atan_uncertain.restype = C.c_uint64
@@ -200,6 +202,13 @@ class Oracle:
 
     def thresh(self) -> int:
         return int(self.L.orc_thresh(self.h))
+
+    def pending_bits(self, slot: int) -> str:
+        """The bits the slot's decoder was handed since its last flush, as the bit log writes them (log_bits on)."""
+        n = int(self.L.orc_pending_bits(self.h, slot, None, 0))
+        buf = (C.c_uint8 * max(n, 1))()
+        self.L.orc_pending_bits(self.h, slot, buf, n)
+        return "".join("01"[b] for b in buf[:n])
 
     def clear(self):
         self.L.orc_clear_logs(self.h)

@@ -1,12 +1,16 @@
 """Scene families: hand-placed inputs for the window geometry and the state that crosses windows -- TEST INFRASTRUCTURE.
 
-Two kinds of rows, both integer-only (the bytes are the same on every machine):
-  scene  -- tfrec_amd.synth.gen_scene over an explicit burst list (repeats, collisions, clock offsets, levels);
+Three kinds of rows, all integer-only (the bytes are the same on every machine):
+  scene  -- tfrec_amd.synth.gen_scene over an explicit burst list (repeats, collisions, clock offsets, levels, hand-built
+            frames; iq_swap: I and Q exchanged, every FSK deviation negated);
   comb   -- copies of one short pulse pasted so that the trigger test |I| + |Q| > thresh (fm_demod.cpp:45,
-            frontend.hip:8) fires on chosen decimated samples (dense windows, block and submit edges).
+            frontend.hip:8) fires on chosen decimated samples (dense windows, block and submit edges);
+  splice -- a scene cut open by stretches of silence, the rest shifted back (a burst's parts in separate trigger windows).
 
 A family is a list of rows run as one batch.  oracle/mint_golden.py pins a subset against the real reference
-(tests/golden/scenes.json); tests/test_scenes_cpu.py and tests/test_gpu_scenes.py replay them.
+(tests/golden/scenes.json); tests/test_scenes_cpu.py and tests/test_gpu_scenes.py replay them.  The last two families,
+frames and splices, are about the decoders' carried state: tests/test_carried_cpu.py measures their classes,
+tests/test_carried_gpu.py runs them through reset, save / load and tfrec_gpu.
 """
 from __future__ import annotations
 
@@ -93,11 +97,39 @@ def render_comb(spec) -> np.ndarray:
     return iq
 
 
+def render_splice(spec) -> np.ndarray:
+    """spec["base"] rendered, then cut open: at every input sample `at` of spec["cuts"] = [[at, n], ...] (positions in the base,
+    ascending, at and n multiples of 4: the decimation phase of what follows is kept) n samples of silence (0x80) are inserted and
+    the rest is shifted back; what no longer fits the row is dropped.  spec["dots"]: input samples of the spliced row (multiples
+    of 4, inside silence) that get a dot pulse, each a trigger window that hands the decoders nothing."""
+    base = render(spec["base"]).reshape(-1, 2)
+    n = spec["n_blocks"] * 32768
+    parts, pos = [], 0
+    for at, gap in spec["cuts"]:
+        assert at % 4 == 0 and gap % 4 == 0 and pos <= at <= len(base), spec["name"]
+        parts += [base[pos:at], np.full((gap, 2), 128, np.uint8)]
+        pos = at
+    parts.append(base[pos:])
+    iq = np.concatenate(parts)
+    assert len(iq) >= n and not (iq[n:] != 128).any(), spec["name"]  # only silence falls off the end
+    iq = np.ascontiguousarray(iq[:n])
+    for at in spec.get("dots", ()):
+        assert at % 4 == 0 and (iq[at - 64:at + 64] == 128).all(), spec["name"]
+        iq[at] = 128 + DOT_AMP
+    return iq.reshape(-1)
+
+
 def render(spec) -> np.ndarray:
     if spec["kind"] == "comb":
         return render_comb(spec)
-    return synth.gen_scene(spec["seed"], spec["n_blocks"], spec["bursts"], spec.get("noise_q8", 256),
-                           tuple(spec.get("dc_iq", (0, 0))))
+    if spec["kind"] == "splice":
+        return render_splice(spec)
+    # (a hand-built frame is written as hex digits, so that a spec stays plain JSON)
+    bursts = [dict(b, frame=bytes.fromhex(b["frame"])) if isinstance(b.get("frame"), str) else b for b in spec["bursts"]]
+    iq = synth.gen_scene(spec["seed"], spec["n_blocks"], bursts, spec.get("noise_q8", 256), tuple(spec.get("dc_iq", (0, 0))))
+    if spec.get("iq_swap"):
+        iq = iq.reshape(-1, 2)[:, ::-1].reshape(-1).copy()  # Q, I: the spectrum mirrored, every FSK deviation negated
+    return iq
 
 
 def render_batch(rows) -> np.ndarray:
@@ -242,7 +274,288 @@ def _levels():
     return rows
 
 
-FAMILIES = dict(dense=_dense, edges=_edges, repeats=_repeats, collisions=_collisions, drift=_drift, levels=_levels)
+# ------------------------------------------------------------------------------------------------ hand-built frames
+#
+# The decoders' carried state (decode.h, whb_commit.h, chains.hip): what one trigger window or one submit leaves to the next.
+# `frames` makes verdicts and bytes depend on it with hand-built frames on a clean signal, `splices` cuts a burst open inside
+# its sync word.  Every row is 8 blocks; tests/test_carried_cpu.py measures each class back from the oracle.
+
+CARRIED_BLOCKS = 8
+CARRIED_CUTS = [2, 2, 4]           # submits (blocks) of the GPU tests: boundaries at input samples 65536 and 131072
+CUT_A, CUT_B = 65536, 131072
+BAUD = (38400, 17240, 9600, 8842, 6000)
+PREAMBLE = (200, 8, 24, 16, 200)   # on-air bits ahead of the frame (iqgen.c burst_bits)
+
+
+def bit_sample(proto: int, start: int, bit: int) -> int:
+    """Input sample at which on-air bit `bit` of a burst that starts at `start` begins (iqgen.c bit_end, nominal clock)."""
+    return start + bit * 1536000 // BAUD[proto]
+
+
+def frame_span(proto: int, start: int, nbytes: int) -> tuple:
+    """(end of the sync word, end of the frame's last byte) of a burst, in input samples."""
+    sync = 4 if proto == 4 else 2
+    return bit_sample(proto, start, PREAMBLE[proto] + 8 * sync), bit_sample(proto, start, PREAMBLE[proto] + 8 * nbytes)
+
+
+def crc8(data: bytes) -> int:
+    """Polynomial 0x31, MSB first, from 0 (tfa1.cpp, tfa2.cpp)."""
+    c = 0
+    for v in data:
+        c ^= v
+        for _ in range(8):
+            c = ((c << 1) ^ 0x31) & 0xff if c & 0x80 else (c << 1) & 0xff
+    return c
+
+
+WHB_INIT = {0x02: 0x97d97a26, 0x03: 0xf59c5a1e, 0x04: 0x98e1d11f}   # whb.cpp:50-62, the types used here
+
+
+def crc32(data: bytes, init: int) -> int:
+    """Polynomial 0x04c11db7, MSB first (whb.cpp)."""
+    c = init
+    for v in data:
+        c ^= v << 24
+        for _ in range(8):
+            c = ((c << 1) ^ 0x04c11db7) & 0xffffffff if c & 0x80000000 else (c << 1) & 0xffffffff
+    return c
+
+
+def _hexs(b) -> str:
+    return bytes(b).hex()
+
+
+def complemented(frame: str) -> str:
+    return _hexs(v ^ 0xff for v in bytes.fromhex(frame))
+
+
+def tfa23_frame(ident: int, temp: int, hum: int) -> str:
+    """2d d4 | 9, id (6 bits), 2 zero bits, (temp + 40) * 10 as three BCD digits | humidity | crc8 (tfa2.cpp:6-52)."""
+    t = "%03d" % temp
+    body = bytes([0x90 | (ident >> 2), ((ident & 3) << 6) | int(t[0]), (int(t[1]) << 4) | int(t[2]), hum])
+    return _hexs(b"\x2d\xd4" + body + bytes([crc8(body)]))
+
+
+def tx22_frame(ident: int, words, nibble: int = 0xa, num=None) -> str:
+    """2d d4 | nibble, id (6 bits), no error, num | num 16-bit words | crc8 over all behind the sync."""
+    num = len(words) if num is None else num
+    body = bytes([(nibble << 4) | (ident >> 2), ((ident & 3) << 6) | 0x10 | num]) + b"".join(w.to_bytes(2, "big") for w in words)
+    return _hexs(b"\x2d\xd4" + body + bytes([crc8(body)]))
+
+
+def whb_frame(stype: int, body: bytes, plen=None) -> str:
+    """4b 2d d4 2b | plen | type | body | crc32 over plen .. body; plen = the crc's index in the frame unless given."""
+    n = 6 + len(body) if plen is None else plen
+    msg = bytes([n, stype]) + body
+    return _hexs(b"\x4b\x2d\xd4\x2b" + msg + crc32(msg, WHB_INIT[stype]).to_bytes(4, "big"))
+
+
+def _fb(proto, start, frame, **kw):
+    return dict(proto=proto, start=start, frame=frame, amp=60, **kw)
+
+
+def _frames_row(name, seed, bursts, **kw):
+    return dict(kind="scene", name=name, seed=seed, n_blocks=CARRIED_BLOCKS, noise_q8=256, bursts=bursts, **kw)
+
+
+def _filler(n: int) -> str:
+    """n bytes without an edge pattern that holds a sync word of any decoder, plain or complemented, at any bit offset."""
+    return "33" * n
+
+
+# TX22 stale pair: B's flush has byte_cnt 10 or 11, its num is 7, so tfa2_decoder::flush_tx22 takes the checksum over
+# rdata[2 .. 17] and compares it with rdata[18]: the bytes from 10 or 11 on are what A (19 bytes) left.  A's last byte is chosen
+# so that B is accepted (from B's flush on the oracle: what lies between B's last byte and its byte_cnt is the demodulator's).
+TX22_A = tx22_frame(0x12, [0x0512, 0x1045, 0x2123, 0x3456, 0x4234, 0x0678, 0x1099])
+TX22_B = "2dd4a257112233"
+TX22_C = tx22_frame(0x2a, [0x0345, 0x1067, 0x2111])   # 11 bytes: its byte_cnt 14 leaves bytes 11 .. 13 on top of A's
+TX22_A18 = dict(accept=0x27, over=0x30)           # A's byte 18 for the pair to be accepted, without and with C in between
+
+# WHB stale pair: B (8 bytes, byte_cnt 14) has plen 20: the CRC-32 runs over rdata[4 .. 19] and is compared with
+# rdata[20 .. 23]; bytes 14 .. 23 are A's
+WHB_A = whb_frame(0x03, bytes(range(0x41, 0x41 + 20)))  # 30 bytes
+WHB_B = "4b2dd42b1402a5c3"
+WHB_A20 = "a9282701"                            # A's bytes 20 .. 23 for B to be accepted
+
+
+def _set_bytes(frame: str, at: int, val: bytes) -> str:
+    f = bytearray(bytes.fromhex(frame))
+    f[at:at + len(val)] = val
+    return _hexs(f)
+
+
+POLARITY = {1: [tfa23_frame(0x15, 612, 45), tfa23_frame(0x2b, 587, 61), tfa23_frame(0x07, 633, 38)],
+            2: [tfa23_frame(0x31, 655, 52), tfa23_frame(0x0e, 571, 77), tfa23_frame(0x22, 604, 49)],
+            3: [tx22_frame(0x05, [0x0622, 0x1034]), tx22_frame(0x19, [0x0587, 0x1099, 0x2123]), tx22_frame(0x33, [0x0601, 0x1042])]}
+
+
+def _straddle(proto: int, nbytes: int, cut: int) -> int:
+    """A burst start (a multiple of 4) that puts `cut` half way between the end of the sync word and the frame's last byte."""
+    a, b = frame_span(proto, 0, nbytes)
+    return (cut - (a + b) // 2) // 4 * 4
+
+
+def _frames():
+    rows = []
+    for p in (1, 2, 3):
+        name = synth.PROTO_NAMES[p].lower()
+        f, g, h = POLARITY[p]
+        gi = complemented(g)
+        n = len(g) // 2
+        # the complemented frame lies across the first submit cut: st.invert crosses it in ChainState
+        s1 = _straddle(p, n, CUT_A)
+        rows.append(_frames_row("pol_%s_inverted" % name, 600 + p, [_fb(p, s1, gi)]))
+        for tag, gap in (("one_window", 600), ("split", 4 * (WINDOW[p] + 40))):
+            s0 = s1 - gap - synth.burst_length(p, len(f) // 2)
+            s2 = s1 + synth.burst_length(p, n) + gap
+            rows.append(_frames_row("pol_%s_%s" % (name, tag), 610 + p, [_fb(p, s0, f), _fb(p, s1, gi), _fb(p, s2, h)]))
+        rows.append(_frames_row("pol_%s_iq_swap" % name, 620 + p,
+                                [_frames_burst(p, 30000, 31 + p, amp=60), _frames_burst(p, _straddle(p, 7, CUT_B), 41 + p, amp=60)],
+                                iq_swap=1))
+    # ---- TX22 lengths and num
+    # (what follows a frame's last byte is the demodulator's: the noise seeds of the length rows are the ones at which the
+    # oracle counts exactly these bytes -- tests/test_carried_cpu.py measures them)
+    rows.append(_frames_row("tx22_n6_n7_num0_nibble", 632, [
+        _fb(3, 8000, "2dd4"), _fb(3, 40000, "2dd4a1"), _fb(3, 80000, tx22_frame(0x11, [])),
+        _fb(3, 120000, tx22_frame(0x11, [0x0622, 0x1034], nibble=0xb))]))
+    long_tx22 = tx22_frame(0x05, [0x0622, 0x1034])
+    rows.append(_frames_row("tx22_n63", 631, [_fb(3, 8000, long_tx22 + _filler(50))]))
+    rows.append(_frames_row("tx22_n64", 633, [_fb(3, 8000, long_tx22 + _filler(51))]))
+    rows.append(_frames_row("tx22_num7", 636, [_fb(3, 8000, TX22_A)]))
+    a = {k: _set_bytes(TX22_A, 18, bytes([v])) for k, v in TX22_A18.items()}
+    a["reject"] = _set_bytes(TX22_A, 18, bytes([TX22_A18["accept"] ^ 0x10]))
+    rows.append(_frames_row("tx22_stale_accept", 634, [_fb(3, 4000, a["accept"]), _fb(3, 70000, TX22_B)]))
+    rows.append(_frames_row("tx22_stale_reject", 634, [_fb(3, 4000, a["reject"]), _fb(3, 70000, TX22_B)]))
+    rows.append(_frames_row("tx22_stale_over", 635, [_fb(3, 4000, a["over"]), _fb(3, 40000, TX22_C), _fb(3, 70000, TX22_B)]))
+    # ---- WHB lengths and plen
+    rows.append(_frames_row("whb_n10_n11", 640, [_fb(4, 8000, "4b2dd42b"), _fb(4, 100000, "4b2dd42b0a")]))
+    body = bytes(range(0x61, 0x61 + 44))
+    rows.append(_frames_row("whb_n60", 641, [_fb(4, 8000, whb_frame(0x02, body))]))              # 54 bytes
+    rows.append(_frames_row("whb_n61", 642, [_fb(4, 8000, whb_frame(0x02, body + b"\x7e"))]))   # 55 bytes
+    rows.append(_frames_row("whb_plen_0_3_4", 643, [_fb(4, 4000 + 85000 * k, "4b2dd42b%02x02" % pl) for k, pl in enumerate((0, 3, 4))]))
+    rows.append(_frames_row("whb_plen_60_61_type", 644, [_fb(4, 4000, "4b2dd42b3c02"), _fb(4, 89000, "4b2dd42b3d02"),
+                                                         _fb(4, 174000, "4b2dd42b0a05112233")]))
+    acc = bytes.fromhex(WHB_A20)
+    rej = bytes([acc[0], acc[1], acc[2] ^ 0x04, acc[3]])
+    rows.append(_frames_row("whb_stale_accept", 645, [_fb(4, 4000, _set_bytes(WHB_A, 20, acc)), _fb(4, 136000, WHB_B)]))
+    rows.append(_frames_row("whb_stale_reject", 645, [_fb(4, 4000, _set_bytes(WHB_A, 20, rej)), _fb(4, 136000, WHB_B)]))
+    # ---- TFA_1 lengths: a telegram with two bytes behind its checksum, then frames of 4, 3 and 5 bytes
+    t = "2dd465b086202360e05697"
+    rows.append(_frames_row("tfa1_n10_n9_n11", 652, [_fb(0, 10000, t + "c35a"), _fb(0, 40000, t[:8]), _fb(0, 70000, t[:6]),
+                                                    _fb(0, 100000, t[:10])]))
+    # ---- long counts: a sync word and then abutting bursts without one, all in one trigger window
+    for p, first, nb in ((1, "2dd4", 5), (0, "2dd4", 4)):
+        n = synth.burst_length(p, 64)
+        rows.append(_frames_row("long_%s" % synth.PROTO_NAMES[p].lower(), 660 + p,
+                                [_fb(p, 4000 + k * n, (first + _filler(62)) if k == 0 else _filler(64)) for k in range(nb)]))
+    return rows
+
+
+# ---- splices: a burst cut open, the parts in separate trigger windows.  Noise 0: a window in the silence hands the decoders no
+# bit, so the bits of the two parts meet in the shift register as if nothing lay between them.
+#
+# TFA_1: README.md:123's telegram, cut SPLIT_AT's bits into its sync word (found on the oracle: of the 140 positions
+# between bit 1 and bit 16, a multiple of 4 samples apart, these 50 decode -- at the others the demodulator loses or adds a
+# bit at the cut).  460 decimated samples of silence: more than the 400 of TFA_1's window, so the first part is flushed as an
+# empty window, and the telegram of the second exists only through the shift register the flush did not clear.
+#
+# WHB: whb_decoder carries its descrambler (lfsr) and the NRZ-S / PSK parities across windows, and a window that ends unsynced
+# does not even flush.  But no cut of a WHB burst was found after which the demodulator's bits continue where they stopped: at
+# each of the 4 .. 47 bit positions ahead of and behind the sync word, every 4 samples, at three seeds, amplitudes 30 .. 100 and
+# offsets 0 .. -5 kHz, whb_demod hands over two more bits at the cut (the level's decay is a peak to it) -- so the
+# self-synchronising descrambler needs its 17 bits again, and a sync word fewer than 17 bits behind the second window's first
+# bit is never found, whatever lfsr was handed over.  The nearest cuts that still decode lie 18 bits ahead of the sync word;
+# the WHB rows use those, and tests/test_carried_cpu.py shows both: the rows decode, and the handed-over lfsr decides nothing.
+TFA1_TELEGRAM = "2dd465b086202360e05697"
+SPLICE_START = 30000
+SPLIT_AT = {3: 38140, 5: 38220, 7: 38300, 10: 38420, 12: 38500}   # bits into the sync word -> cut, for a burst at SPLICE_START
+SPLICE_GAP = 4 * 460
+WHB_SPLICE_AT = 30000 + 200 * 256 - 18 * 256 + 64                  # 17.75 bits ahead of the sync word
+WHB_SPLICE_GAP = 4 * 560
+
+
+def _splice(name, proto, shift, at, gap, dots=(), **burst):
+    """A burst of `proto` at SPLICE_START + shift, cut at at + shift."""
+    base = dict(kind="scene", name=name + "_base", seed=500 + (proto == 4), n_blocks=CARRIED_BLOCKS, noise_q8=0,
+                bursts=[dict(proto=proto, start=SPLICE_START + shift, amp=60, **burst)])
+    ats = [at] if isinstance(at, int) else at   # (several cuts: each position in the burst, each `gap` wide)
+    return dict(kind="splice", name=name, n_blocks=CARRIED_BLOCKS, base=base, cuts=[[a + shift, gap] for a in ats],
+                dots=[d + shift for d in dots])
+
+
+def splice_parts(row) -> tuple:
+    """(last input sample of the first part + 1, first input sample of the second part) of a splice row, in the row."""
+    at, gap = row["cuts"][0]
+    return at, at + gap
+
+
+def _splices():
+    rows = []
+    g = SPLICE_GAP
+    t1 = dict(frame=TFA1_TELEGRAM)
+    for bit, at in sorted(SPLIT_AT.items()):   # both windows in one submit
+        rows.append(_splice("tfa1_split_bit%d" % bit, 0, 0, at, g, **t1))
+    for bit in (5, 10):
+        at = SPLIT_AT[bit]
+        # the first window closes 400 decimated samples behind the cut, the second part begins 460 behind it: the submit cut
+        # at 430 puts the second part into window 0 of the next submit
+        rows.append(_splice("tfa1_split_bit%d_submit_cut" % bit, 0, CUT_A - 4 * 430 - at, at, g, **t1))
+        # the submit cut 200 samples behind the cut: the first window is still open there, closes as window 0 of the next
+        # submit without a bit, and the second part is its window 1 (have = 0)
+        rows.append(_splice("tfa1_split_bit%d_open_at_cut" % bit, 0, CUT_A - 4 * 200 - at, at, g, **t1))
+    at = SPLIT_AT[7]
+    # one and two dot windows between the parts, in one submit ...
+    rows.append(_splice("tfa1_split_one_empty", 0, 0, at, 2 * g, dots=[at + g], **t1))
+    rows.append(_splice("tfa1_split_two_empty", 0, 0, at, 3 * g, dots=[at + g, at + 2 * g], **t1))
+    # ... and with the first part in the submit before: the submit cut between the first flush and the dot
+    rows.append(_splice("tfa1_split_empty_behind_cut", 0, CUT_A - 4 * 430 - at, at, 2 * g, dots=[at + g], **t1))
+    # cut twice inside the sync word: the middle window holds 7 of its bits, the last window's register is pieced together
+    # from two windows (one submit), and from one window and ChainState.sr (0 < have < 32: the middle window is window 0 of the
+    # submit behind the cut)
+    a1, a2 = SPLIT_AT[3], SPLIT_AT[10]
+    rows.append(_splice("tfa1_split_three_ways", 0, 0, [a1, a2], g, **t1))
+    rows.append(_splice("tfa1_split_three_ways_submit_cut", 0, CUT_A - 4 * 430 - a1, [a1, a2], g, **t1))
+    # WHB, cut in its preamble
+    w = dict(payload_seed=5)
+    rows.append(_splice("whb_cut_preamble", 4, 0, WHB_SPLICE_AT, WHB_SPLICE_GAP, **w))
+    # (the submit cut 540 samples behind the cut: the first window, 512 long, has closed there)
+    rows.append(_splice("whb_cut_preamble_submit_cut", 4, CUT_B - 4 * 540 - WHB_SPLICE_AT, WHB_SPLICE_AT, WHB_SPLICE_GAP, **w))
+    return rows
+
+
+FAMILIES = dict(dense=_dense, edges=_edges, repeats=_repeats, collisions=_collisions, drift=_drift, levels=_levels,
+                frames=_frames, splices=_splices)
+
+
+def carried_boundaries() -> list:
+    """The submit boundaries of CARRIED_CUTS in input samples."""
+    return [int(v) * 32768 for v in np.cumsum(CARRIED_CUTS)]
+
+
+def carried_cut_claims(fam) -> list:
+    """Where the submits of CARRIED_CUTS must cut a family's rows for state to be carried in ChainState: [(row name, the submit
+    boundary in input samples, lo, hi)], the boundary to lie in (lo, hi) -- inside every complemented frame between its sync word
+    and its last byte, between A and B of a stale pair, between the parts of a splice that is meant to lie across a cut."""
+    out = []
+    for row in FAMILIES[fam]():
+        name = row["name"]
+        if name.startswith("pol_"):
+            p = row["bursts"][0]["proto"]
+            for b in row["bursts"]:
+                inverted = row.get("iq_swap") or ("frame" in b and b["frame"].startswith("d22b"))
+                a, e = frame_span(p, b["start"], len(b["frame"]) // 2 if "frame" in b else 7)
+                for cut in (CUT_A, CUT_B):
+                    if inverted and a < cut < e:
+                        out.append((name, cut, a, e))
+        elif "_stale_" in name:
+            a, b = row["bursts"][-2], row["bursts"][-1]
+            cut = CUT_B if a["proto"] == 4 else CUT_A
+            out.append((name, cut, frame_span(a["proto"], a["start"], len(a["frame"]) // 2)[1], b["start"]))
+        elif row["kind"] == "splice" and ("submit_cut" in name or "at_cut" in name or "behind_cut" in name):
+            lo, hi = splice_parts(row)
+            out.append((name, CUT_B if name.startswith("whb") else CUT_A, lo, hi))
+    return out
+
 
 
 def family(name: str) -> list:

@@ -1261,6 +1261,17 @@ size_t orc_num_dec(const orc_t *o) { return o->ndec; }
 const int16_t *orc_dec(const orc_t *o) { return o->dec; }
 const char *orc_bits_text(const orc_t *o) { return o->bitstext.p ? o->bitstext.p : ""; }
 int orc_thresh(const orc_t *o) { return o->thresh; }
+size_t orc_pending_bits(const orc_t *o, int slot, unsigned char *out, size_t cap)
+{
+	for (int n = 0; n < o->ndem; n++)
+		if (o->dem[n].dec.slot == slot) {
+			const dec_t *d = &o->dem[n].dec;
+			if (out)
+				memcpy(out, d->bits, d->nbits < cap ? d->nbits : cap);
+			return d->nbits;
+		}
+	return 0;
+}
 uint64_t orc_atan_uncertain(const orc_t *o)
 {
 	(void)o;

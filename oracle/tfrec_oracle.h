@@ -86,6 +86,10 @@ size_t orc_num_dec(const orc_t *o); /* int16 count of the kept decimated stream 
 const int16_t *orc_dec(const orc_t *o);
 /* bit log: per flush "slot nbits bits..." records, as text */
 const char *orc_bits_text(const orc_t *o);
+/* bits handed to the slot's store_bit since its last flush (log_bits on; the first cap of them -> out[], a byte each): a WHB
+ * window that ends unsynced does not flush, so its bits stay ahead of the next window's in the next record -- the count is
+ * where the next window's begin */
+size_t orc_pending_bits(const orc_t *o, int slot, unsigned char *out, size_t cap);
 int orc_thresh(const orc_t *o); /* current trigger threshold (auto mode moves it) */
 uint64_t orc_atan_uncertain(const orc_t *o); /* samples whose fm_dev truncation is within 1e-6 of flipping */
 void orc_clear_logs(orc_t *o);

@@ -1,5 +1,5 @@
 """GPU tests on the scene families (oracle/scenes.py): dense windows, block and submit edges, repeated frames, colliding
-protocols, bit clock offsets and signal levels through the HIP path, event by event against the oracle -- and the scenes the
+protocols, bit clock offsets, signal levels, hand-built frames and spliced bursts through the HIP path, event by event against the oracle -- and the scenes the
 real reference pinned (tests/golden/scenes.json), plus the reference-minted IQ fixtures, against the golden outputs
 directly, with no oracle in between."""
 import hashlib
@@ -16,12 +16,13 @@ from tfrec_amd import api, synth
 pytestmark = pytest.mark.gpu
 
 # submit cuts per family (blocks); tests/test_scenes_cpu.py checked the tables for exactly these
-CUTS = dict(dense=[24], edges=[1, 2, 5, 4], repeats=[24], collisions=[7, 25], drift=[32], levels=[16])
+CUTS = dict(dense=[24], edges=[1, 2, 5, 4], repeats=[24], collisions=[7, 25], drift=[32], levels=[16],
+            frames=S.CARRIED_CUTS, splices=S.CARRIED_CUTS)  # (the last two: inside inverted frames, stale pairs and splices)
 # fallbacks each family reaches in the pipeline (stats() counters, observed on an MI355X for these fixed inputs; only "> 0"
 # is asserted -- how the work is split is not part of the contract)
 REACHES = dict(dense=["tfa2_resliced", "tfa1_scalar_groups"], edges=["biquad_unconverged"],
                repeats=["tfa2_resliced", "tfa2_scalar_groups"], collisions=["tfa2_scalar_groups", "biquad_unconverged"],
-               drift=["tfa2_scalar_groups", "biquad_unconverged"], levels=["tfa2_scalar_groups"])
+               drift=["tfa2_scalar_groups", "biquad_unconverged"], levels=["tfa2_scalar_groups"], frames=[], splices=[])
 
 
 def _sha(a):
@@ -69,7 +70,7 @@ def test_dense_windows_fill_the_window_table(serial):
         assert all(st[k] > 0 for k in REACHES["dense"]), st
 
 
-@pytest.mark.parametrize("fam", ["edges", "repeats", "collisions", "drift", "levels"])
+@pytest.mark.parametrize("fam", ["edges", "repeats", "collisions", "drift", "levels", "frames", "splices"])
 @SERIAL
 def test_scene_family_all_flushes(fam, serial):
     rows, iq = _family(fam)
@@ -82,7 +83,7 @@ def test_scene_family_all_flushes(fam, serial):
         assert all(st[k] > 0 for k in REACHES[fam]), st
 
 
-@pytest.mark.parametrize("fam", ["dense", "edges", "repeats", "collisions", "drift", "levels"])
+@pytest.mark.parametrize("fam", ["dense", "edges", "repeats", "collisions", "drift", "levels", "frames", "splices"])
 def test_scene_family_default_mode(fam):
     rows, iq = _family(fam)
     ev, st, fm = _run(iq, CUTS[fam])
@@ -105,7 +106,7 @@ def test_levels_with_auto_threshold_and_wide_filter(thresh, wide):
     assert fm["host_mismatch"] == 0
 
 
-@pytest.mark.parametrize("fam", ["repeats", "collisions", "drift"])
+@pytest.mark.parametrize("fam", ["repeats", "collisions", "drift", "frames", "splices"])
 def test_scene_bits_equal_the_oracle_flush_by_flush(fam):
     """TFREC_AMD_F_BITS on the scenes with several frames per window, interference and bit clock offsets: every bit handed to
     decoder::store_bit, flush by flush, against Oracle(log_bits=True).bits_text()."""

@@ -130,7 +130,8 @@ def test_dense_windows_reach_the_table_bound():
         assert reached[slot] >= m // w, slot  # every chain at its own tightest packing
 
 
-FAMILY_SUBMITS = dict(dense=[24], edges=[1, 2, 5, 4], repeats=[24], collisions=[7, 25], drift=[32], levels=[16])
+FAMILY_SUBMITS = dict(dense=[24], edges=[1, 2, 5, 4], repeats=[24], collisions=[7, 25], drift=[32], levels=[16],
+                      frames=S.CARRIED_CUTS, splices=S.CARRIED_CUTS)
 
 
 @pytest.mark.parametrize("fam", sorted(S.FAMILIES))
