@@ -1177,6 +1177,49 @@ int tfrec_amd_enable_burst_sync(tfrec_amd_ctx *ctx, int32_t rate, uint64_t patte
 int tfrec_amd_read_burst_syncs(tfrec_amd_ctx *ctx, tfrec_amd_burst_sync *out, size_t cap_runs, uint32_t *n_runs, uint32_t *words,
 			       size_t cap_words, uint64_t *n_words);
 
+/* Line code (tfrec_amd_enable_burst_code): an optional stage of the burst track, valid in any of its four modes, for
+ * transmitters whose bits are differentially coded (NRZI, NRZ-S) or scrambled by a self-synchronising scrambler (G3RUH) on the air: a
+ * sync word that exists only behind the line decoder is never found on the raw track.  Such a decoder is an XOR of the track with
+ * copies of itself delayed by whole symbols, so its output has the track's shape: one bit per captured sample.  With the code on,
+ * tfrec_amd_enable_burst_sync correlates the CODED track, and its own carried history holds coded bits.  There is no reference
+ * counterpart: this text is normative, tfrec_amd/linecode.py restates it.  Exact integers only.
+ *   Settings: fixed at enable.  A rate R in bit/s, 1000 .. 96000; taps, a non-zero uint32: bit j - 1 set means a delay of j symbols,
+ *             j = 1 .. 32; the flag TFREC_AMD_CODE_INVERT.  delta(j) = floor((768000 j + R) / (2 R)), the burst sync's delta;
+ *             span = delta(the highest set tap) <= 2047.  G3RUH (1 + x^12 + x^17) is taps 0x10800, NRZI taps 1, NRZ-S taps 1 with
+ *             INVERT.
+ *   History:  for entry e of a submit's table with track t[0 .. n) (tfrec_amd_track), t[x] for x < 0 is the track bit of the same
+ *             chain ahead of this piece, where the chain has one.  H of them are available: H = 0 without TFREC_AMD_RUN_CONTINUES,
+ *             else H = min(2047, H' + n') of the OPEN piece (H', n') that ended the submit before; H < 2047 is the whole chain so
+ *             far.  t[x] = 0 for x < -H: ahead of the chain's first sample.  Per stream the device carries the last 2047 track bits
+ *             of the chain of its OPEN run and H, separately from the burst sync's.
+ *   Bit:      u[k] = t[k] ^ (the XOR over the set taps j of t[k - delta(j)]) ^ invert, for 0 <= k < n; invert is 1 under
+ *             TFREC_AMD_CODE_INVERT, which therefore also complements what the bits ahead of the chain contribute (0 ^ 1).
+ *   Bits:     packed exactly as the track's: u[k] of entry e is bit (pool_offset_e + k) & 31 of word (pool_offset_e + k) >> 5.  Bits
+ *             that belong to no run are 0.  A run whose samples do not fit max_samples has no track: its bits are 0, its n_ones 0,
+ *             and it leaves H = 0 behind it; so does an OPEN run beyond max_runs, which has no record.  The independence of the cut
+ *             is therefore claimed only for submits without TFREC_AMD_E_OVERFLOW.
+ *   Record:   a tfrec_amd_track: the entry's first 24 bytes, bit_offset = its pool_offset, last_over = the track record's of the same
+ *             entry, n_ones = the number of k with u[k] = 1.  The track's merging rules, its Slicing and the burst sync's Framing
+ *             work on it unchanged.
+ *   Cutting:  with one track centre and no overflow the merged record and coded track do not depend on how the stream was cut into
+ *             submits.  A restart drops the chain: the run behind it does not CONTINUE.  tfrec_amd_save_streams does not carry the
+ *             history: a chain that continues behind tfrec_amd_load_streams uses what the context itself carried.
+ * No CRC, no Manchester decoding, no additive (frame-synchronous) scrambler.  Nothing of it has been measured on real recordings. */
+#define TFREC_AMD_CODE_INVERT 1u  /* tfrec_amd_enable_burst_code's flag: the coded bit is complemented */
+/* Turn the line code on: after tfrec_amd_enable_burst_track (any mode), before the first submit, once; before or after
+ * tfrec_amd_enable_burst_sync.  Device memory, counted in tfrec_amd_get_memory: per FIFO set max_runs * 40 bytes and
+ * ceil(max_samples / 32) words; per stream the carried 64 words and H (260 bytes); no page-locked memory.  Errors: a rate outside
+ * 1000 .. 96000, taps == 0, an unknown flag, a span above 2047, no burst track or a second call: TFREC_AMD_E_INVAL, and nothing is
+ * allocated; after the first submit or a poisoned context: TFREC_AMD_E_STATE; TFREC_AMD_E_NOMEM as elsewhere; a call that fails
+ * leaves the context exactly as it was.  A context on which it was never called holds and launches what it did.  Valid wherever the
+ * recorder is, tfrec_amd_submit_runs included.  Its three kernels run on the recorder's low-priority stream behind the track's and
+ * ahead of the sync's. */
+int tfrec_amd_enable_burst_code(tfrec_amd_ctx *ctx, int32_t rate, uint32_t taps, uint32_t flags);
+/* out[i] = the coded record of entry i of the table tfrec_amd_read_captures returns for the same submit, words = the coded bitmap:
+ * tfrec_amd_read_burst_tracks' conventions, counts, prefixes on TFREC_AMD_E_OVERFLOW and errors throughout. */
+int tfrec_amd_read_burst_codes(tfrec_amd_ctx *ctx, tfrec_amd_track *out, size_t cap_runs, uint32_t *n_runs, uint32_t *words,
+			       size_t cap_words, uint64_t *n_words);
+
 /* Power spectrum of the input rows (tfrec_amd_enable_spectrum): where in a recording there is energy, and where the
  * short bursts are that an average hides -- before a receiver is placed.  It belongs to an input ROW of a submit, not to a stream: it
  * is taken on x, the int16 value every format maps a stored component to (tfrec_amd_create_format; -8192 <= x <= 8191), at the

@@ -121,6 +121,7 @@ EXPORTS = (
     "tfrec_amd_enable_burst_track_amplitude", "tfrec_amd_set_burst_track_level",
     "tfrec_amd_enable_burst_track_auto", "tfrec_amd_read_burst_track_centres", "tfrec_amd_enable_burst_track_phase",
     "tfrec_amd_enable_burst_sync", "tfrec_amd_read_burst_syncs",
+    "tfrec_amd_enable_burst_code", "tfrec_amd_read_burst_codes",
 )
 
 _libs = {}
@@ -235,6 +236,9 @@ def load_library(build: bool = True, experiments: bool = False, short_segments: 
                                               C.POINTER(C.c_uint64)]
     L.tfrec_amd_enable_burst_sync.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_uint32]
     L.tfrec_amd_read_burst_syncs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
+                                             C.POINTER(C.c_uint64)]
+    L.tfrec_amd_enable_burst_code.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32]
+    L.tfrec_amd_read_burst_codes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
                                              C.POINTER(C.c_uint64)]
     L.tfrec_amd_stream_state_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
     L.tfrec_amd_save_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
@@ -795,6 +799,22 @@ class Receiver:
         -> (a SYNC_DTYPE array, one record per entry of that submit's run table; the match bitmap's uint32 words): sync.bits_of(rec,
         words) is a record's match track.  Overflow as for read_burst_tracks.  sync_total holds the submit's true run count."""
         return self._read_run_records(self.L.tfrec_amd_read_burst_syncs, SYNC_DTYPE, "sync_total", allow_overflow, words=True)
+
+    def enable_burst_code(self, rate: int, taps: int, invert: bool = False):
+        """Turn the line code on (tfrec_amd_enable_burst_code; after enable_burst_track in any mode, before the first submit,
+        before or after enable_burst_sync): a bit per captured sample, the track XORed with itself delayed by j symbols at `rate`
+        bit/s for every set bit j - 1 of `taps` (linecode.NAMED: g3ruh, nrzi, nrzs), complemented under `invert`.
+        read_burst_codes returns the records and the coded bitmap; the sync then works on the coded track."""
+        if not -2 ** 31 <= int(rate) < 2 ** 31 or not 0 <= int(taps) < 2 ** 32:  # (refused before ctypes could wrap a value into range)
+            raise TfrecAmdError(E_INVAL, "rate or taps outside its type")
+        _check(self.L, self.L.tfrec_amd_enable_burst_code(self.h, int(rate), int(taps), 1 if invert else 0))
+
+    def read_burst_codes(self, allow_overflow: bool = False):
+        """The coded track of the OLDEST undrained submit (tfrec_amd_read_burst_codes; call it before the drain that pops that
+        submit) -> (a TRACK_DTYPE array, one record per entry of that submit's run table; the coded bitmap's uint32 words):
+        track.bits_of(rec, words) is a record's coded track.  Overflow as for read_burst_tracks.  code_total holds the submit's
+        true run count."""
+        return self._read_run_records(self.L.tfrec_amd_read_burst_codes, TRACK_DTYPE, "code_total", allow_overflow, words=True)
 
     def enable_runs_input(self, max_runs: int, max_samples: int):
         """Turn sparse submits on (tfrec_amd_enable_runs_input; decimated receivers, before the first submit): a submit_runs may

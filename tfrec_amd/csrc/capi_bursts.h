@@ -1,5 +1,5 @@
 // tfrec_amd/csrc/capi_bursts.h -- the entry points of the five burst stages on the recorder's table: the meter, the
-// envelope (6r), the clock (6s), the track (6t, with its centres; 6v, its amplitude mode, with its levels; 6w, its auto-centre mode, with its centre records; 6x, its phase mode) and the sync (6u).  What they share comes first -- the enables'
+// envelope (6r), the clock (6s), the track (6t, with its centres; 6v, its amplitude mode, with its levels; 6w, its auto-centre mode, with its centre records; 6x, its phase mode; 6y, its line code) and the sync (6u).  What they share comes first -- the enables'
 // preflight, the rebase of start_sample, the record-only reader and the record-plus-bitmap reader --, then each
 // stage's enable and read, which add their own argument checks and buffers.  Included by capi.hip, which lists what is where.
 #pragma once
@@ -13,6 +13,7 @@ constexpr StageNames kEnvelopeNames = { "burst envelope", "envelope", "tfrec_amd
 constexpr StageNames kClockNames = { "burst clock", "clock", "tfrec_amd_enable_burst_clock" };
 constexpr StageNames kTrackNames = { "burst track", "track", "tfrec_amd_enable_burst_track" };
 constexpr StageNames kCentreNames = { "auto-centre track", "centre", "tfrec_amd_enable_burst_track_auto" };
+constexpr StageNames kCodeNames = { "line code", "code", "tfrec_amd_enable_burst_code" };
 constexpr StageNames kSyncNames = { "burst sync", "sync", "tfrec_amd_enable_burst_sync" };
 
 // What every enable checks behind its own arguments, in this order: what the stage works on (`needs`, switched on by
@@ -365,4 +366,52 @@ int tfrec_amd_read_burst_syncs(tfrec_amd_ctx *c, tfrec_amd_burst_sync *out, size
 			       uint64_t *n_words)
 {
 	return c ? read_run_bitmaps(c, c->syn, c->syn.d_words, kSyncNames, out, cap_runs, n_runs, words, cap_words, n_words) : TFREC_AMD_E_INVAL;
+}
+
+// ---- the line code
+int tfrec_amd_enable_burst_code(tfrec_amd_ctx *c, int32_t rate, uint32_t taps, uint32_t flags)
+{
+	if (!c)
+		return TFREC_AMD_E_INVAL;
+	if (rate < 1000 || rate > 96000) {
+		snprintf(g_err, sizeof(g_err), "the line code's rate is within [1000, 96000] bit/s");
+		return TFREC_AMD_E_INVAL;
+	}
+	if (!taps) {
+		snprintf(g_err, sizeof(g_err), "the line code has at least one tap");
+		return TFREC_AMD_E_INVAL;
+	}
+	if (flags & ~TFREC_AMD_CODE_INVERT) {
+		snprintf(g_err, sizeof(g_err), "the line code's flags are 0 or 1, the complemented output");
+		return TFREC_AMD_E_INVAL;
+	}
+	const int top = 32 - __builtin_clz(taps);  // the highest tap's delay in symbols
+	const long long span = (768000LL * top + rate) / (2LL * rate);
+	if (span > kSyncSpanLimit) {
+		snprintf(g_err, sizeof(g_err), "the line code's taps span %lld samples at %d bit/s, more than %d", span, (int)rate, kSyncSpanLimit);
+		return TFREC_AMD_E_INVAL;
+	}
+	TRY(enable_preflight(c, kCodeNames, c->trk.on, "the burst track", "tfrec_amd_enable_burst_track", c->code.on));
+	EnableGuard<BurstCode> guard(c, c->code);
+	BurstCode &o = c->code;
+	const size_t n = (size_t)c->cfg.n_streams;
+	for (int k = 0; k < kSets; k++) {
+		TRY(own_device(c, o.d_recs[k], (size_t)c->cap.max_runs * sizeof(tfrec_amd_track)));
+		TRY(own_device(c, o.d_words[k], c->trk.n_words * sizeof(uint32_t)));
+	}
+	TRY(own_device(c, o.d_carry, n * 64 * sizeof(uint32_t)));
+	TRY(own_device(c, o.d_hist, n * sizeof(uint32_t)));
+	HIPCHK(hipMemset(o.d_carry, 0, n * 64 * sizeof(uint32_t)));  // (never used before a submit has written them: no first submit CONTINUES)
+	HIPCHK(hipMemset(o.d_hist, 0, n * sizeof(uint32_t)));
+	o.rate = rate;
+	o.taps = taps;
+	o.flags = flags;
+	o.on = guard.ok = true;
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_read_burst_codes(tfrec_amd_ctx *c, tfrec_amd_track *out, size_t cap_runs, uint32_t *n_runs, uint32_t *words, size_t cap_words,
+			       uint64_t *n_words)
+{
+	return c ? read_run_bitmaps(c, c->code, c->code.d_words, kCodeNames, out, cap_runs, n_runs, words, cap_words, n_words) : TFREC_AMD_E_INVAL;
 }

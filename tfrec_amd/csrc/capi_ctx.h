@@ -124,6 +124,14 @@ struct BurstSync : RunRecords<tfrec_amd_burst_sync> {
 	uint32_t *d_words[kSets] = {};
 	uint32_t *d_carry = nullptr, *d_hist = nullptr;
 };
+// tfrec_amd_enable_burst_code: the settings; per set the records (RunRecords) and the coded bitmap (the track's
+// size); per stream the carried 64 words of track bits and H (linecode_carry_kernel)
+struct BurstCode : RunRecords<tfrec_amd_track> {
+	int rate = 0;
+	uint32_t taps = 0, flags = 0;
+	uint32_t *d_words[kSets] = {};
+	uint32_t *d_carry = nullptr, *d_hist = nullptr;
+};
 // tfrec_amd_create_decimated (PreStage::kChannel): the carried last pair of every stream
 struct DecIn {
 	uint32_t *d_last = nullptr;
@@ -328,6 +336,7 @@ struct tfrec_amd_ctx {
 	RunRecords<tfrec_amd_clock> clk;
 	BurstTrack trk;
 	BurstSync syn;
+	BurstCode code;
 	DecIn decin;
 	RunsIn runs_in;
 	SpectrumOut spec;

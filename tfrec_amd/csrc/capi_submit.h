@@ -288,11 +288,19 @@ static int launch_track(tfrec_amd_ctx *c, int set, const FrontOut &out, const Ca
 	return TFREC_AMD_OK;
 }
 
-// The burst sync's buffers of a set
+// The line code's buffers of a set
+static CodeBufs code_bufs(const tfrec_amd_ctx *c, int set)
+{
+	const BurstCode &o = c->code;
+	return { .recs = o.d_recs[set], .words = o.d_words[set], .trecs = c->trk.d_recs[set], .track = c->trk.d_words[set], .carry = o.d_carry,
+		 .hist = o.d_hist, .rate = o.rate, .taps = o.taps, .flags = o.flags };
+}
+
+// The burst sync's buffers of a set: with the line code on, the track it reads is the coded one
 static SyncBufs sync_bufs(const tfrec_amd_ctx *c, int set)
 {
 	const BurstSync &o = c->syn;
-	return { .recs = o.d_recs[set], .words = o.d_words[set], .track = c->trk.d_words[set], .carry = o.d_carry, .hist = o.d_hist,
+	return { .recs = o.d_recs[set], .words = o.d_words[set], .track = c->code.on ? c->code.d_words[set] : c->trk.d_words[set], .carry = o.d_carry, .hist = o.d_hist,
 		 .rate = o.rate, .n_bits = o.n_bits, .max_errors = o.max_errors, .flags = o.flags, .pattern = o.pattern };
 }
 
@@ -412,6 +420,8 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 			HIPCHK(launch_burst_clock(c->cap.lane.st, out, b, c->clk.d_recs[set]));
 		if (c->trk.on)  // the burst track: behind the clock, on the table, the working set, the samples, the final mask and its own carry
 			TRY(launch_track(c, set, out, b));
+		if (c->code.on)  // the line code: behind the track's carry kernel, on the table, the working set, the track's records and bitmap and its own carry
+			HIPCHK(launch_burst_code(c->cap.lane.st, out, b, code_bufs(c, set)));
 		if (c->syn.on)  // the burst sync: behind the track's carry kernel, on the table, the working set, the track's bitmap and its own carry
 			HIPCHK(launch_burst_sync(c->cap.lane.st, out, b, sync_bufs(c, set)));
 		HIPCHK(lane_written(c->cap.lane, set));

@@ -62,6 +62,17 @@ struct SyncBufs {
 	uint32_t flags;
 	unsigned long long pattern;
 };
+// The line code's buffers and settings (linecode.h): the set's records and coded bitmap, the set's track records and bitmap, the
+// carried 64 words of track bits and H of every stream
+struct CodeBufs {
+	tfrec_amd_track *recs;
+	uint32_t *words;
+	const tfrec_amd_track *trecs;
+	const uint32_t *track;
+	uint32_t *carry, *hist;
+	int rate;
+	uint32_t taps, flags;
+};
 // The spectrum of rows 0 .. n_rows - 1 of a submit of n_in complex samples per row, and the set's records: [rows][max_records][n_bins]
 // sums and peaks, [rows][max_records] frame counts.  launch_occupancy reads what launch_spectrum has just queued on the stream.
 struct SpectrumBufs {
@@ -108,6 +119,7 @@ hipError_t launch_burst_track_amplitude(hipStream_t st, const FrontOut &o, const
 hipError_t launch_burst_track_auto(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);  // (k.centre: the set centres in Hz)
 hipError_t launch_burst_track_phase(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);  // (k.centre: the set centres in Hz; k.carry: 80 pairs a stream)
 hipError_t launch_burst_sync(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const SyncBufs &k);
+hipError_t launch_burst_code(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const CodeBufs &k);
 hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, const SpectrumBufs &b);
 hipError_t launch_occupancy(hipStream_t st, const SpectrumBufs &b, uint32_t ratio, uint32_t rel, tfrec_amd_occupancy *recs, uint32_t *bits);
 // ... and the parity probes

@@ -293,6 +293,10 @@ inline int device_worker::open_context()
 			r = tfrec_amd_set_burst_track_centre(ctx, all.data(), hz.data(), (int)n);
 		}
 	}
+	if (!r && job.coding()) {  // -U: the line code on the track, at -G's rate
+		call = "tfrec_amd_enable_burst_code";
+		r = tfrec_amd_enable_burst_code(ctx, (int32_t)job.track_rate, job.code_taps, job.code_invert ? TFREC_AMD_CODE_INVERT : 0u);
+	}
 	if (!r && job.syncing()) {  // -Y: the sync on the track, at -G's rate
 		call = "tfrec_amd_enable_burst_sync";
 		r = tfrec_amd_enable_burst_sync(ctx, (int32_t)job.track_rate, job.sync_pattern, job.sync_bits, job.sync_errors,
@@ -598,7 +602,9 @@ inline int device_worker::read_run_bitmaps(int (*reader)(tfrec_amd_ctx *, R *, s
 // -G: the batch's track records, each with its bits out of the batch's bitmap.  stream -> file and the file-end cut as above; a
 // record that reaches over its file's end is cut there and is OPEN (job.h: track_take).  -Y: the sync records of the same entries
 // with them, each with its match track (job.h: sync_take), in b.syncs in place of b.tracks.  -G rate,auto: every track piece with
-// the centre record of its entry (job.h: centre_take)
+// the centre record of its entry (job.h: centre_take).  -U: the coded records of the same entries too, each a track piece of its
+// own with the coded bits (cut alike): in b.codes beside b.tracks, or with -Y as the sync piece's track piece, b.tracks keeping the
+// raw pieces for the bits line
 inline int device_worker::read_tracks(size_t k, batch_result &b)
 {
 	std::vector<tfrec_amd_track> recs;
@@ -633,6 +639,16 @@ inline int device_worker::read_tracks(size_t k, batch_result &b)
 			return TFREC_AMD_E_STATE;
 		}
 	}
+	std::vector<tfrec_amd_track> urecs;  // -U: the coded records and words of the same entries
+	std::vector<uint32_t> uwords;
+	if (job.coding()) {
+		if ((r = read_run_bitmaps(tfrec_amd_read_burst_codes, urecs, uwords)))
+			return r;
+		if (urecs.size() != recs.size()) {
+			fprintf(stderr, "tfrec_amd: device %d batch %zu: %zu coded records beside %zu track records\n", device, k, urecs.size(), recs.size());
+			return TFREC_AMD_E_STATE;
+		}
+	}
 	for (size_t q = 0; q < recs.size(); q++) {
 		tfrec_amd_track x = recs[q];
 		if (!cut_at_file_end(x, plan[k].file, file_blocks, true))
@@ -642,10 +658,19 @@ inline int device_worker::read_tracks(size_t k, batch_result &b)
 		track_piece t = track_take(x, words.data(), n);
 		if (job.centring())
 			centre_take(t, crecs[q]);
-		if (job.syncing())
-			b.syncs.push_back(sync_take(srecs[q], swords.data(), t));
-		else
+		if (job.coding()) {  // the coded piece: the cut entry with the coded record's n_ones and bits; the sync's frames are read from it
+			x.n_ones = urecs[q].n_ones;
+			track_piece u = track_take(x, uwords.data(), n);
+			if (job.syncing())
+				b.syncs.push_back(sync_take(srecs[q], swords.data(), u));
+			else
+				b.codes.push_back(std::move(u));
 			b.tracks.push_back(std::move(t));
+		} else if (job.syncing()) {
+			b.syncs.push_back(sync_take(srecs[q], swords.data(), t));
+		} else {
+			b.tracks.push_back(std::move(t));
+		}
 	}
 	return 0;
 }

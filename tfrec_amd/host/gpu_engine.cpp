@@ -447,9 +447,10 @@ int gpu_engine::run()
 	envelopes.begin(n);
 	chain_report<tfrec_amd_clock> clocks(clock_line);
 	clocks.begin(n);
-	chain_merger<track_piece> tracks;
-	std::vector<track_piece> said;
+	chain_merger<track_piece> tracks, codes;
+	std::vector<track_piece> said, coded;
 	tracks.begin(n);
+	codes.begin(n);
 	sync_merger syncs;
 	std::vector<sync_piece> framed;
 	syncs.begin(n);
@@ -494,7 +495,28 @@ int gpu_engine::run()
 				envelopes.take(b.envelopes, workers[d].plan[k], file_blocks, files, into);
 			if (job.clocking())  // -C: likewise, behind -Q's lines of the batch
 				clocks.take(b.clocks, workers[d].plan[k], file_blocks, files, into);
-			if (job.syncing()) {  // -G -Y: -G's line of each burst, and behind it a line per frame found in it
+			if (job.coding()) {  // -G -U: -G's lines of each burst, its code line, and with -Y a line per frame found on the coded track
+				said.clear();
+				tracks.take(b.tracks, workers[d].plan[k], file_blocks, said);
+				framed.clear();
+				coded.clear();
+				if (job.syncing())
+					syncs.take(b.syncs, workers[d].plan[k], file_blocks, framed);
+				else
+					codes.take(b.codes, workers[d].plan[k], file_blocks, coded);
+				for (size_t i = 0; i < said.size(); i++) {  // (the same entries with the same flags: the chains end together, in one order)
+					const track_piece &x = said[i];
+					if (job.centring())
+						printf("%s\n", centre_line(files[x.stream], x).c_str());
+					printf("%s\n", track_line(files[x.stream], x, job.track_rate).c_str());
+					if (job.amplitude())
+						printf("%s\n", pulses_line(files[x.stream], x).c_str());
+					printf("%s\n", code_line(files[x.stream], job.syncing() ? framed[i].trk : coded[i], job.track_rate).c_str());
+					if (job.syncing())
+						for (const sync_frame &f : sync_frames(framed[i], job))
+							printf("%s\n", sync_line(files[x.stream], framed[i], f, job.sync_lsb).c_str());
+				}
+			} else if (job.syncing()) {  // -G -Y: -G's line of each burst, and behind it a line per frame found in it
 				framed.clear();
 				syncs.take(b.syncs, workers[d].plan[k], file_blocks, framed);
 				for (const sync_piece &x : framed) {
@@ -504,7 +526,7 @@ int gpu_engine::run()
 					if (job.amplitude())  // -O: the burst's pulses behind its bits
 						printf("%s\n", pulses_line(files[x.stream], x.trk).c_str());
 					for (const sync_frame &f : sync_frames(x, job))
-						printf("%s\n", sync_line(files[x.stream], x, f).c_str());
+						printf("%s\n", sync_line(files[x.stream], x, f, job.sync_lsb).c_str());
 				}
 			} else if (job.tracking()) {  // -G: likewise, behind -C's lines of the batch
 				said.clear();

@@ -248,13 +248,25 @@ public:
 	// (job.h: sync_frames, sync_line: per plateau of matches inside the burst the payload's first `bytes` bytes, read at symbol
 	// centres from the plateau's middle, MSB-first; "-": the complemented word matched and the payload is complemented).  The
 	// defaults -- no errors, 8 bytes, one polarity -- are not tuned on anything: nothing of it has been measured on real recordings.
-	void set_sync(unsigned long long pattern, int n_bits, int errors, int bytes, bool both)
+	void set_sync(unsigned long long pattern, int n_bits, int errors, int bytes, bool both, bool lsb = false)
 	{
 		job.sync_pattern = pattern;
 		job.sync_bits = n_bits;
 		job.sync_errors = errors;
 		job.sync_bytes = bytes;
 		job.sync_both = both;
+		job.sync_lsb = lsb;  // the frames' hex LSB-first per byte (job.h: sync_line)
+	}
+	// -U (with -G): the line code (tfrec_amd_enable_burst_code) on the track, at -G's rate: taps bit j - 1 is a delay of j
+	// symbols, invert complements the coded bit.  run() merges the coded pieces' chains beside the track's (they are track pieces:
+	// chain_merger<track_piece>) and prints, behind each burst's bits line,
+	//   code <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->
+	// (job.h: code_line: the coded track through -G's slicer); -Y's frames are then found on and read from the coded track.  Nothing of
+	// it has been measured on real recordings.
+	void set_code(uint32_t taps, bool invert)
+	{
+		job.code_taps = taps;
+		job.code_invert = invert;
 	}
 	// -k: keep.  A file is processed in whole pieces only and nothing is padded; before the first batch behind a
 	// file's last one is submitted -- and at the end of the job -- its stream is saved (tfrec_amd_save_streams) to

@@ -8,6 +8,7 @@
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -107,6 +108,9 @@ struct job_settings {
 	int sync_errors = 0;           // ... E
 	int sync_bytes = 8;            // ... the payload bytes read behind the word
 	bool sync_both = false;        // ... the complemented word too
+	bool sync_lsb = false;         // ... the frames' hex LSB-first per byte
+	uint32_t code_taps = 0;        // set_code (0: none): -U, the line code's taps, bit j - 1 a delay of j symbols at -G's rate
+	bool code_invert = false;      // ... and its INVERT
 	const std::vector<replay_file> *replay = NULL;  // set_replay (NULL: the files are dumps)
 	std::string keep_prefix;       // set_keep ("": none)
 	std::string cont_prefix;       // set_continue ("": none)
@@ -121,6 +125,7 @@ struct job_settings {
 	bool recorder() const { return capture || metering() || enveloping() || clocking() || tracking(); }  // the contexts enable the recorder: for -S, or as the meter's, the envelope's, the clock's or the track's table
 	bool tracking() const { return track_rate != 0; }  // -G (never with -s or -A)
 	bool syncing() const { return sync_bits != 0; }  // -Y (only with -G)
+	bool coding() const { return code_taps != 0; }  // -U (only with -G)
 	bool amplitude() const { return track_level >= 0; }  // -O (only with -G)
 	bool centring() const { return track_auto; }  // -G rate,auto or -G rate,psk: the track has centre records (never with -O)
 	bool phasing() const { return track_lag != 0; }  // -G rate,psk
@@ -417,7 +422,8 @@ struct sync_piece : tfrec_amd_burst_sync {
 
 struct batch_result {
 	std::vector<track_piece> tracks;
-	std::vector<sync_piece> syncs;  // (-Y: in place of tracks)
+	std::vector<sync_piece> syncs;  // (-Y: in place of tracks; -U -Y: beside them, each with the CODED piece of its entry for its track piece)
+	std::vector<track_piece> codes;  // (-U without -Y: the coded pieces of the entries in tracks)
 	std::vector<tfrec_amd_burst> bursts;
 	std::vector<tfrec_amd_envelope> envelopes;
 	std::vector<tfrec_amd_clock> clocks;
@@ -920,13 +926,24 @@ inline std::vector<sync_frame> sync_frames(const sync_piece &c, const job_settin
 	return out;
 }
 
-// frame <file> <start_sample> <sync_sample> <errors> <+|-> <n_bits> <hex|->: MSB-first, the last nibble zero-padded
-inline std::string sync_line(const std::string &file, const sync_piece &c, const sync_frame &f)
+// frame <file> <start_sample> <sync_sample> <errors> <+|-> <n_bits> <hex|->: MSB-first, the last nibble zero-padded -- or, lsb,
+// every byte with the first received bit as bit 0, a last partial byte zero-filled at the top, two digits a byte
+inline std::string sync_line(const std::string &file, const sync_piece &c, const sync_frame &f, bool lsb = false)
 {
 	std::string s = "frame " + file + " " + std::to_string((long long)c.start_sample) + " " + std::to_string((long long)c.start_sample + (long long)f.c) +
 			" " + std::to_string(f.errors) + " " + (f.plus ? "+" : "-") + " " + std::to_string(f.bits.size()) + " ";
 	if (f.bits.empty())
 		return s + "-";
+	if (lsb) {
+		for (size_t i = 0; i < f.bits.size(); i += 8) {
+			int byte = 0;
+			for (size_t j = 0; j < 8 && i + j < f.bits.size(); j++)
+				byte |= f.bits[i + j] << j;
+			s += "0123456789abcdef"[byte >> 4];
+			s += "0123456789abcdef"[byte & 15];
+		}
+		return s;
+	}
 	for (size_t i = 0; i < f.bits.size(); i += 4) {
 		int nib = 0;
 		for (size_t j = 0; j < 4; j++)
@@ -935,6 +952,46 @@ inline std::string sync_line(const std::string &file, const sync_piece &c, const
 	}
 	return s;
 }
+
+// ---- -U: the line code (include/tfrec_amd.h: "Line code", whose text is normative; tfrec_amd/linecode.py restates the span and the line).
+// A coded piece is a track_piece: track_take, track_add and chain_merger<track_piece> take it as it is.
+
+// -U's argument: g3ruh | nrzi | nrzs | <1 .. 8 hex digits, not 0>, each with an optional ",inv" -> the taps and INVERT (false: bad)
+inline bool code_parse(const char *arg, uint32_t &taps, bool &invert)
+{
+	std::string a(arg);
+	invert = false;
+	const size_t comma = a.find(',');
+	if (comma != std::string::npos) {
+		if (a.substr(comma + 1) != "inv")
+			return false;
+		invert = true;
+		a.resize(comma);
+	}
+	if (a == "g3ruh") {
+		taps = 0x10800u;  // 1 + x^12 + x^17
+	} else if (a == "nrzi" || a == "nrzs") {
+		taps = 1u;
+		invert = invert != (a == "nrzs");  // (nrzs is nrzi complemented)
+	} else {
+		if (a.empty() || a.size() > 8 || a.find_first_not_of("0123456789abcdefABCDEF") != std::string::npos)
+			return false;
+		taps = (uint32_t)strtoul(a.c_str(), NULL, 16);
+	}
+	return taps != 0;
+}
+
+// span = delta(the highest set tap), taps != 0
+inline uint64_t code_span(uint32_t taps, long rate)
+{
+	int top = 32;
+	while (!((taps >> (top - 1)) & 1u))
+		top--;
+	return sync_delta((uint64_t)top, rate);
+}
+
+// code <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->: -G's bits line of the coded piece
+inline std::string code_line(const std::string &file, const track_piece &c, long rate) { return "code" + track_line(file, c, rate).substr(4); }
 
 inline void chain_add(tfrec_amd_burst &c, const tfrec_amd_burst &p) { burst_add(c, p); }
 inline void chain_add(sync_piece &c, const sync_piece &p) { sync_add(c, p); }

@@ -142,6 +142,17 @@
 // symbol centres behind it, MSB-first, as far as the burst reaches, complemented under "-".  No CRC is checked.  A word whose span
 // at the rate exceeds 2047 samples is refused.  Works where -G works.  The defaults are not tuned on anything: nothing of it has
 // been measured on real recordings.
+// A fifth field, -Y hex,errors,bytes,both,1 (lsb): the frames' hex is LSB-first per byte -- every byte assembled with the first
+// received bit as bit 0, a last partial byte zero-filled at the top, always two digits a byte; n_bits is unchanged.  The field is a
+// flag that is given as 1 or left out; it is independent of -U.
+// -U g3ruh|nrzi|nrzs|<hex taps>[,inv] (not in the reference; with -G): the line code (tfrec_amd_enable_burst_code), for
+// transmitters that code their bits differentially or scramble them with a self-synchronising scrambler: the track XORed with
+// itself delayed by j symbols at -G's rate for every set bit j - 1 of the taps (1 .. 8 hex digits, not 0; g3ruh = 10800, the taps 12
+// and 17; nrzi = 1; nrzs = 1,inv), complemented under inv.  Behind each burst's bits line stdout gets
+//   code <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->
+// the coded track through -G's slicer; -Y's frames are found on and read from the coded track.  Taps whose span at the rate exceeds
+// 2047 samples are refused.  Works with what -G works with.  No CRC, no Manchester decoding, no additive scrambler; nothing of it has
+// been measured on real recordings.
 // -P bins[,frames_per_record] (not in the reference): the power spectrum of ONE recording, beside its decoding: an
 // exact integer DFT of bins = 64, 128, 256, 512 or 1024 bins over the raw input -- at 1.536 MS/s, or given with -x, or with -r / -F --,
 // per record of frames_per_record frames (1 .. 16384; default: the frames one block's input holds, at least 1) the sum and the peak
@@ -322,7 +333,9 @@ struct cli {
 	long track_level = -1;  // -O (-1: not given)
 	int sync_bits = 0;  // -Y (0: not given): the word's bits, the word, errors, bytes, both
 	unsigned long long sync_pattern = 0;
-	long sync_errors = 0, sync_bytes = 8, sync_both = 0;
+	long sync_errors = 0, sync_bytes = 8, sync_both = 0, sync_lsb = 0;
+	uint32_t code_taps = 0;  // -U (0: not given): the taps and INVERT
+	bool code_invert = false;
 	const char *keep_prefix = NULL, *cont_prefix = NULL;  // -k, -K
 	bool have_center = false, have_format = false;  // -c, -F given (-R refuses them)
 	std::vector<replay_file> captures;  // -R: one per file index of <prefix>.idx
@@ -356,7 +369,7 @@ struct cli {
 
 static void usage()
 {
-	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-G rate[,centre_hz]] [-G rate,auto] [-G rate,psk[,lag]] [-O level] [-Y hex[,errors[,bytes[,both]]]] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
+	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-G rate[,centre_hz]] [-G rate,auto] [-G rate,psk[,lag]] [-O level] [-Y hex[,errors[,bytes[,both]]]] [-Y hex,errors,bytes,both,1] [-U g3ruh|nrzi|nrzs|hextaps[,inv]] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
 			"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
 			"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
 			"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
@@ -393,6 +406,10 @@ static void usage()
 			"  -Y h[,e[,n[,b]]]  with -G: find the sync word h (2 .. 16 hex digits, MSB first) in every burst's track with at most e bit errors\n"
 			"              (default 0), b = 1: or its complement, and read the n bytes behind it (default 8) at symbol centres: a line 'frame <file>\n"
 			"              <start_sample> <sync_sample> <errors> <+|-> <n_bits> <hex|->' per match, behind the burst's bits line\n"
+			"  -Y h,e,n,b,1  as -Y h,e,n,b, the frames' hex LSB-first per byte (the first received bit is bit 0; two digits a byte)\n"
+			"  -U code[,inv] with -G: a line code ahead of the slicer and of -Y: g3ruh (descrambler, taps 12 and 17), nrzi, nrzs, or hex taps\n"
+			"              (bit j - 1: the track XORed with itself j symbols ago), inv: complemented; behind each bits line a line 'code <file>\n"
+			"              <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->', and -Y's frames are read from the coded track\n"
 			"  -k prefix   keep: for a recording that arrives in parts.  Every -L file is processed in whole blocks only (nothing is padded), then\n"
 			"              its receiver's state is saved to <prefix>.<file index>.state and the bytes that filled no block to\n"
 			"              <prefix>.<file index>.rest\n"
@@ -475,7 +492,7 @@ bool cli::parse_format(const char *arg)
 int cli::parse(int argc, char **argv)
 {
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCG:O:Y:k:K:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCG:O:Y:U:k:K:h")) != -1) {
 		switch (c) {
 		case 'M': meter = true; break;
 		case 'Q': envelope = true; break;
@@ -520,21 +537,28 @@ int cli::parse(int argc, char **argv)
 					part.back() += *q;
 			}
 			const std::string &hex = part[0];
-			bool ok = part.size() <= 4 && hex.size() >= 2 && hex.size() <= 16 && hex.find_first_not_of("0123456789abcdefABCDEF") == std::string::npos;
+			bool ok = part.size() <= 5 && hex.size() >= 2 && hex.size() <= 16 && hex.find_first_not_of("0123456789abcdefABCDEF") == std::string::npos;
 			if (ok) {
 				sync_bits = 4 * (int)hex.size();
 				sync_pattern = strtoull(hex.c_str(), NULL, 16);
 				ok = (part.size() < 2 || parse_long(part[1].c_str(), 0, (sync_bits - 1) / 2, sync_errors)) &&
 				     (part.size() < 3 || parse_long(part[2].c_str(), 1, 256, sync_bytes)) &&
-				     (part.size() < 4 || parse_long(part[3].c_str(), 0, 1, sync_both));
+				     (part.size() < 4 || parse_long(part[3].c_str(), 0, 1, sync_both)) &&
+				     (part.size() < 5 || parse_long(part[4].c_str(), 1, 1, sync_lsb));  // (a flag: 1, or left out)
 			}
 			if (!ok) {
 				fprintf(stderr, "tfrec_gpu: bad -Y '%s': want <hex>[,<errors>[,<bytes>[,<both>]]], 2 .. 16 hex digits, errors below half the word's "
-						"bits, 1 .. 256 bytes, both 0 or 1\n", optarg);
+						"bits, 1 .. 256 bytes, both 0 or 1; a fifth field is 1: LSB-first bytes\n", optarg);
 				return 1;
 			}
 			break;
 		}
+		case 'U':
+			if (!code_parse(optarg, code_taps, code_invert)) {
+				fprintf(stderr, "tfrec_gpu: bad -U '%s': want g3ruh, nrzi, nrzs or 1 .. 8 hex digits of taps (not 0), each with an optional ,inv\n", optarg);
+				return 1;
+			}
+			break;
 		case 'k':
 		case 'K':
 			(c == 'k' ? keep_prefix : cont_prefix) = optarg;
@@ -748,6 +772,15 @@ int cli::check() const
 	if (sync_bits && (768000LL * (sync_bits - 1) + track_rate) / (2LL * track_rate) > 2047) {
 		fprintf(stderr, "tfrec_gpu: -Y: %d bits at %ld bit/s span %lld samples, more than 2047\n", sync_bits, track_rate,
 			(768000LL * (sync_bits - 1) + track_rate) / (2LL * track_rate));
+		return 1;
+	}
+	if (code_taps && !track_rate) {
+		fprintf(stderr, "tfrec_gpu: -U codes the track of -G: give -G rate[,centre_hz] with it\n");
+		return 1;
+	}
+	if (code_taps && code_span(code_taps, track_rate) > 2047) {
+		fprintf(stderr, "tfrec_gpu: -U: the taps %x at %ld bit/s span %llu samples, more than 2047\n", (unsigned)code_taps, track_rate,
+			(unsigned long long)code_span(code_taps, track_rate));
 		return 1;
 	}
 	if (track_rate && (hexfile || have_scan || have_auto)) {
@@ -1000,7 +1033,9 @@ int cli::run()
 	if (track_lag)
 		e.set_track_phase((int)track_lag);
 	if (sync_bits)
-		e.set_sync(sync_pattern, sync_bits, (int)sync_errors, (int)sync_bytes, sync_both != 0);
+		e.set_sync(sync_pattern, sync_bits, (int)sync_errors, (int)sync_bytes, sync_both != 0, sync_lsb != 0);
+	if (code_taps)
+		e.set_code(code_taps, code_invert);
 	if (keep_prefix)
 		e.set_keep(keep_prefix);
 	if (cont_prefix)

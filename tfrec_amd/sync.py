@@ -13,7 +13,7 @@ here has been measured on real recordings.
   syncs_bruteforce   the same sample by sample, in Python integers;
   bits_of            a record's match track out of the bitmap;  merge: a chain of pieces -> the record and match track of the
                      uncut run;  chains: the chains of a sequence of submits (burst.chains' walk);
-  frames             a merged track and match track -> the frames;  line: tfrec_gpu -Y's output line;
+  frames             a merged track and match track -> the frames;  line: tfrec_gpu -Y's output line (lsb: the byte order);
   device_bytes       what tfrec_amd_enable_burst_sync adds to tfrec_amd_get_memory (pinned_bytes: nothing).
 """
 from __future__ import annotations
@@ -213,9 +213,23 @@ def plateaus(m) -> list:
     return [(int(a), int(b) - 1) for a, b in zip(e[0::2], e[1::2])]
 
 
-def frames(tpiece, spiece, settings: Settings, n_bytes: int = 8) -> list:
+class LsbBits(list):
+    """A payload's bits, in the order received, that line() prints LSB-first per byte."""
+
+
+def hex_of(bits, lsb: bool = False) -> str:
+    """The payload's hex: MSB-first with the last nibble zero-padded (track.hex_of) -- or, lsb, every byte assembled with the first
+    received bit as bit 0, a last partial byte zero-filled at the top, always two digits a byte."""
+    if not lsb:
+        return track.hex_of(bits)
+    b = list(bits)
+    return "".join("%02x" % sum(v << i for i, v in enumerate(b[k:k + 8])) for k in range(0, len(b), 8))
+
+
+def frames(tpiece, spiece, settings: Settings, n_bytes: int = 8, lsb: bool = False) -> list:
     """The header's Framing on a chain's merged track (a track.Piece) and match track (a Piece) -> [(c, errors, '+' or '-', the
-    payload's bits as a list)], in the order of c."""
+    payload's bits as a list)], in the order of c.  lsb: the list is an LsbBits, which line() prints LSB-first per byte; the bits
+    and their number are the same."""
     st = settings
     length = min(int(tpiece.rec["last_over"]) + 1, KEEP, len(tpiece.bits))
     t = tpiece.bits[:length].tolist()
@@ -230,15 +244,17 @@ def frames(tpiece, spiece, settings: Settings, n_bytes: int = 8) -> list:
             if q >= length:
                 break
             pay.append(t[q] if plus else 1 - t[q])
-        out.append((c, d if plus else st.P - d, "+" if plus else "-", pay))
+        out.append((c, d if plus else st.P - d, "+" if plus else "-", LsbBits(pay) if lsb else pay))
     return out
 
 
-def line(name: str, spiece, frame) -> str:
-    """tfrec_gpu -Y: frame <file> <start_sample> <sync_sample> <errors> <+|-> <n_bits> <hex|->."""
+def line(name: str, spiece, frame, lsb: bool = False) -> str:
+    """tfrec_gpu -Y: frame <file> <start_sample> <sync_sample> <errors> <+|-> <n_bits> <hex|->; lsb (or a frame of frames(...,
+    lsb=True)): the hex LSB-first per byte."""
     c, errors, pol, pay = frame
     start = int(spiece.rec["start_sample"])
-    return "frame %s %d %d %d %s %d %s" % (name, start, start + c, errors, pol, len(pay), track.hex_of(pay) if pay else "-")
+    lsb = lsb or isinstance(pay, LsbBits)
+    return "frame %s %d %d %d %s %d %s" % (name, start, start + c, errors, pol, len(pay), hex_of(pay, lsb) if pay else "-")
 
 
 def device_bytes(n_streams: int, max_runs: int, max_samples: int) -> int:
