@@ -1204,7 +1204,7 @@ int tfrec_amd_read_burst_syncs(tfrec_amd_ctx *ctx, tfrec_amd_burst_sync *out, si
  *   Cutting:  with one track centre and no overflow the merged record and coded track do not depend on how the stream was cut into
  *             submits.  A restart drops the chain: the run behind it does not CONTINUE.  tfrec_amd_save_streams does not carry the
  *             history: a chain that continues behind tfrec_amd_load_streams uses what the context itself carried.
- * No CRC, no Manchester decoding, no additive (frame-synchronous) scrambler.  Nothing of it has been measured on real recordings. */
+ * No CRC of its own (see the frame check below), no Manchester decoding, no additive (frame-synchronous) scrambler.  Nothing of it has been measured on real recordings. */
 #define TFREC_AMD_CODE_INVERT 1u  /* tfrec_amd_enable_burst_code's flag: the coded bit is complemented */
 /* Turn the line code on: after tfrec_amd_enable_burst_track (any mode), before the first submit, once; before or after
  * tfrec_amd_enable_burst_sync.  Device memory, counted in tfrec_amd_get_memory: per FIFO set max_runs * 40 bytes and
@@ -1219,6 +1219,74 @@ int tfrec_amd_enable_burst_code(tfrec_amd_ctx *ctx, int32_t rate, uint32_t taps,
  * tfrec_amd_read_burst_tracks' conventions, counts, prefixes on TFREC_AMD_E_OVERFLOW and errors throughout. */
 int tfrec_amd_read_burst_codes(tfrec_amd_ctx *ctx, tfrec_amd_track *out, size_t cap_runs, uint32_t *n_runs, uint32_t *words,
 			       size_t cap_words, uint64_t *n_words);
+
+/* Frame check (tfrec_amd_enable_burst_crc): an optional stage of the burst track, valid in any of its four modes: for
+ * every run of the recorder's table WHERE A FRAME THAT CARRIES ITS OWN CRC ENDS -- one bit per captured sample, 1 where the N bytes
+ * whose last bit sits at the sample, read at the Framing's symbol centres, check.  Its input track t is the coded bitmap where
+ * tfrec_amd_enable_burst_code is on, else the track's -- the burst sync's input; the choice is made per submit, so the enables may
+ * come in any order.  It needs no sync: it finds frames behind a sync word nobody knows.  There is no reference counterpart: this
+ * text is normative, tfrec_amd/crc.py restates it.  Exact integers only.
+ *   Settings: fixed at enable.  A rate R in bit/s, 1000 .. 96000; n_bytes = N, 1 .. 256, the frame behind the sync word: skipped
+ *             bytes, covered bytes and the CRC field; skip = S >= 0; width = W, one of 8, 16, 24, 32; S + W / 8 < N (at least one
+ *             covered byte); poly non-zero; poly, init and xorout below 2^W; the flags TFREC_AMD_CRC_LSB (a byte's first received bit
+ *             is its bit 0; otherwise its bit 7) and TFREC_AMD_CRC_INVERT (every bit is complemented before use).  delta(i) =
+ *             floor((768000 i + R) / (2 R)), the burst sync's; D = delta(8 N) <= 16383.  At 6001 bit/s N = 32 gives D = 16381; at 6000
+ *             it gives 16384 and is refused.
+ *   Bits:     for sample k of an entry, b_i = t[k - (D - delta(i))] ^ invert, i = 1 .. 8 N; b_{8N} sits at k itself.  These are the
+ *             Framing's payload positions for a sync centre c = k - D.  Byte j, j = 0 .. N - 1, is assembled from b_{8j+1} .. b_{8j+8}
+ *             in the flag's order.
+ *   CRC:      with no reflection: r = init; for each covered byte j, S <= j < N - W / 8: r ^= byte << (W - 8), then eight times r =
+ *             ((r << 1) ^ poly if r's top bit was set, else r << 1) mod 2^W.  field = the last W / 8 bytes, big-endian.
+ *             v[k] = 1 iff k + H >= D and (r ^ xorout) == field.
+ *   History:  the burst sync's with a longer reach: H = 0 without TFREC_AMD_RUN_CONTINUES, else H = min(16383, H' + n') of the OPEN
+ *             piece (H', n') that ended the submit before.  Per stream the device carries the chain's last 16384 input-track bits
+ *             (512 words) and H, its own, separate from the sync's and the code's.  A sample with k + H < D is undefined and reads 0,
+ *             so bits ahead of the chain's first sample are never used and stale carried words cannot matter.  A run that does not
+ *             fit max_samples, or an OPEN run beyond max_runs: bits 0, n_ok 0, first_at none, and H = 0 behind it; the independence
+ *             of the cut is claimed without TFREC_AMD_E_OVERFLOW only.  A reset drops the chain: the run behind it does not
+ *             CONTINUE.  tfrec_amd_save_streams does not carry the history.
+ *   Bits of v: packed exactly as the track's, at the entry's pool_offset.  Bits that belong to no run are 0.
+ *   Record:   the entry's first 24 bytes, bit_offset = its pool_offset, n_ok = the number of k with v[k] = 1, first_at = the first
+ *             such k, or 0xffffffff where there is none.
+ *   Merging:  the v tracks are concatenated, n_samples and n_ok added; first_at is that of the first piece that has one, offset by
+ *             the samples ahead of that piece; the flags as for tfrec_amd_track.  Without overflow the merged record and check track
+ *             do not depend on how the stream was cut into submits.
+ *   Verdict   (an addition to the burst sync's Framing; normative for tfrec_gpu -V and crc.py): a frame of polarity + with all 8 N
+ *             payload bits is ok iff v[c + D] = 1 on the merged check track, else bad; c + D = c + delta(8 N) is the position of its
+ *             last bit and lies inside the input.  A frame with fewer bits has no verdict.  tfrec_gpu keeps the first 2^20 samples
+ *             of a chain's tracks (the Framing's input): a frame whose last bit lies behind them has no verdict there ("-"), and
+ *             a piece that a file's end cuts has n_ok and first_at counted again on what is kept; crc.py has no such limit.
+ *   Limits:   one N per context (TX22's telegrams of 7 and 9 bytes need two).  Reflected CRCs, the complemented reading under
+ *             TFREC_AMD_SYNC_BOTH and frames whose length a byte of the frame gives are out of scope; the complement only changes
+ *             the constant the residue starts from.  With init = 0 and xorout = 0 an all-zero frame checks, so a burst's constant
+ *             stretches raise n_ok: n_ok alone is a detector only for CRCs with a non-zero init.  Nothing of it has been measured
+ *             on real recordings. */
+#define TFREC_AMD_CRC_LSB 1u     /* tfrec_amd_enable_burst_crc's flags: a byte's first received bit is its bit 0 */
+#define TFREC_AMD_CRC_INVERT 2u  /* ... every input bit is complemented before use */
+typedef struct {            /* 40 bytes */
+	uint32_t stream;        /* these five: copied from the table entry */
+	uint32_t flags;
+	int64_t  start_sample;
+	uint32_t n_samples;
+	int32_t  thresh;
+	uint64_t bit_offset;    /* the entry's pool_offset: v[k] is bit bit_offset + k of the bitmap */
+	uint32_t n_ok;          /* the number of k with v[k] = 1 */
+	uint32_t first_at;      /* the first such k; 0xffffffff: none */
+} tfrec_amd_burst_crc;
+/* Turn the frame check on: after tfrec_amd_enable_burst_track (any mode), before the first submit, once; before or after
+ * tfrec_amd_enable_burst_code and tfrec_amd_enable_burst_sync, and without them.  Device memory, counted in tfrec_amd_get_memory: per
+ * FIFO set max_runs * 40 bytes and ceil(max_samples / 32) words; per stream the carried 512 words and H (2052 bytes); once, the term
+ * table, 8 n_bytes terms of 8 bytes; no page-locked memory.  Errors: any setting outside the above, an unknown flag, D > 16383, no
+ * burst track or a second call: TFREC_AMD_E_INVAL, and nothing is allocated; after the first submit or a poisoned context:
+ * TFREC_AMD_E_STATE; TFREC_AMD_E_NOMEM as elsewhere; a call that fails leaves the context exactly as it was.  A context on which it
+ * was never called holds and launches what it did.  Valid wherever the recorder is, tfrec_amd_submit_runs included.  Its three
+ * kernels run on the recorder's low-priority stream behind the line code's (or the track's). */
+int tfrec_amd_enable_burst_crc(tfrec_amd_ctx *ctx, int32_t rate, int32_t n_bytes, int32_t skip, int32_t width, uint32_t poly, uint32_t init,
+			       uint32_t xorout, uint32_t flags);
+/* out[i] = the record of entry i of the table tfrec_amd_read_captures returns for the same submit, words = the check bitmap:
+ * tfrec_amd_read_burst_tracks' conventions, counts, prefixes on TFREC_AMD_E_OVERFLOW and errors throughout. */
+int tfrec_amd_read_burst_crcs(tfrec_amd_ctx *ctx, tfrec_amd_burst_crc *out, size_t cap_runs, uint32_t *n_runs, uint32_t *words,
+			      size_t cap_words, uint64_t *n_words);
 
 /* Power spectrum of the input rows (tfrec_amd_enable_spectrum): where in a recording there is energy, and where the
  * short bursts are that an average hides -- before a receiver is placed.  It belongs to an input ROW of a submit, not to a stream: it

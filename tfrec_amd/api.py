@@ -16,6 +16,7 @@ from . import _build
 from .burst import BURST_DTYPE  # tfrec_amd_burst
 from .capture import RUN_DTYPE  # tfrec_amd_run
 from .clock import CLOCK_DTYPE  # tfrec_amd_clock
+from .crc import CRC_DTYPE  # tfrec_amd_burst_crc
 from .envelope import ENVELOPE_DTYPE  # tfrec_amd_envelope
 from .levels import LEVEL_DTYPE  # tfrec_amd_level
 from .occupancy import OCC_DTYPE  # tfrec_amd_occupancy
@@ -122,6 +123,7 @@ EXPORTS = (
     "tfrec_amd_enable_burst_track_auto", "tfrec_amd_read_burst_track_centres", "tfrec_amd_enable_burst_track_phase",
     "tfrec_amd_enable_burst_sync", "tfrec_amd_read_burst_syncs",
     "tfrec_amd_enable_burst_code", "tfrec_amd_read_burst_codes",
+    "tfrec_amd_enable_burst_crc", "tfrec_amd_read_burst_crcs",
 )
 
 _libs = {}
@@ -240,6 +242,10 @@ def load_library(build: bool = True, experiments: bool = False, short_segments: 
     L.tfrec_amd_enable_burst_code.argtypes = [C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32]
     L.tfrec_amd_read_burst_codes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
                                              C.POINTER(C.c_uint64)]
+    L.tfrec_amd_enable_burst_crc.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                             C.c_uint32]
+    L.tfrec_amd_read_burst_crcs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
+                                            C.POINTER(C.c_uint64)]
     L.tfrec_amd_stream_state_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
     L.tfrec_amd_save_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
     L.tfrec_amd_load_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
@@ -815,6 +821,25 @@ class Receiver:
         track.bits_of(rec, words) is a record's coded track.  Overflow as for read_burst_tracks.  code_total holds the submit's
         true run count."""
         return self._read_run_records(self.L.tfrec_amd_read_burst_codes, TRACK_DTYPE, "code_total", allow_overflow, words=True)
+
+    def enable_burst_crc(self, rate: int, n_bytes: int, width: int, poly: int, init: int = 0, xorout: int = 0, skip: int = 0,
+                         lsb: bool = False, invert: bool = False):
+        """Turn the frame check on (tfrec_amd_enable_burst_crc; after enable_burst_track in any mode, before the first submit, in
+        any order with enable_burst_code and enable_burst_sync, or without them): a bit per captured sample, 1 where the n_bytes
+        bytes whose last bit sits at the sample -- read at symbol centres at `rate` bit/s from the sync's input track -- carry
+        their own CRC (crc.Settings).  read_burst_crcs returns the records and the check bitmap."""
+        args = (rate, n_bytes, skip, width)
+        if not all(-2 ** 31 <= int(a) < 2 ** 31 for a in args) or not all(0 <= int(a) < 2 ** 32 for a in (poly, init, xorout)):
+            raise TfrecAmdError(E_INVAL, "a setting outside its type")  # (refused before ctypes could wrap a value into range)
+        _check(self.L, self.L.tfrec_amd_enable_burst_crc(self.h, int(rate), int(n_bytes), int(skip), int(width), int(poly), int(init),
+                                                         int(xorout), (1 if lsb else 0) | (2 if invert else 0)))
+
+    def read_burst_crcs(self, allow_overflow: bool = False):
+        """The check track of the OLDEST undrained submit (tfrec_amd_read_burst_crcs; call it before the drain that pops that
+        submit) -> (a CRC_DTYPE array, one record per entry of that submit's run table; the check bitmap's uint32 words):
+        crc.bits_of(rec, words) is a record's check track.  Overflow as for read_burst_tracks.  crc_total holds the submit's true
+        run count."""
+        return self._read_run_records(self.L.tfrec_amd_read_burst_crcs, CRC_DTYPE, "crc_total", allow_overflow, words=True)
 
     def enable_runs_input(self, max_runs: int, max_samples: int):
         """Turn sparse submits on (tfrec_amd_enable_runs_input; decimated receivers, before the first submit): a submit_runs may

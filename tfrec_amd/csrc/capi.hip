@@ -11,6 +11,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "crc_table.h"  // the frame check's settings and term table: plain C++
 #include "knobs.h"
 #include "tfrec_dev.h"
 #include "launch.h"  // every launch_* of frontend.hip, chains.hip and chains2.hip, and the records they take (FrontOut, History, ...)
@@ -26,7 +27,7 @@ using namespace tfrec;
 #include "capi_correct.h"  // the DC blocker's and the IQ balancer's constructors, getters, reads and resets
 #include "capi_streams.h"  // reset, configure, the three tunes, map, and their getters
 #include "capi_decin.h"    // the channel-rate constructor, the recorder's pre samples, sparse submits
-#include "capi_bursts.h"   // the five burst stages (meter, envelope, clock, track, sync): the shared preflight and readers, each enable and read, the track's four modes and its line code
+#include "capi_bursts.h"   // the five burst stages (meter, envelope, clock, track, sync): the shared preflight and readers, each enable and read, the track's four modes, its line code and its frame check
 #include "capi_state.h"    // a stream's state blob: its header, the inventory table, save and load
 
 extern "C" {

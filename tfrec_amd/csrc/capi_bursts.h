@@ -1,5 +1,5 @@
 // tfrec_amd/csrc/capi_bursts.h -- the entry points of the five burst stages on the recorder's table: the meter, the
-// envelope (6r), the clock (6s), the track (6t, with its centres; 6v, its amplitude mode, with its levels; 6w, its auto-centre mode, with its centre records; 6x, its phase mode; 6y, its line code) and the sync (6u).  What they share comes first -- the enables'
+// envelope (6r), the clock (6s), the track (6t, with its centres; 6v, its amplitude mode, with its levels; 6w, its auto-centre mode, with its centre records; 6x, its phase mode; 6y, its line code; 6z, its frame check) and the sync (6u).  What they share comes first -- the enables'
 // preflight, the rebase of start_sample, the record-only reader and the record-plus-bitmap reader --, then each
 // stage's enable and read, which add their own argument checks and buffers.  Included by capi.hip, which lists what is where.
 #pragma once
@@ -14,6 +14,7 @@ constexpr StageNames kClockNames = { "burst clock", "clock", "tfrec_amd_enable_b
 constexpr StageNames kTrackNames = { "burst track", "track", "tfrec_amd_enable_burst_track" };
 constexpr StageNames kCentreNames = { "auto-centre track", "centre", "tfrec_amd_enable_burst_track_auto" };
 constexpr StageNames kCodeNames = { "line code", "code", "tfrec_amd_enable_burst_code" };
+constexpr StageNames kCrcNames = { "frame check", "crc", "tfrec_amd_enable_burst_crc" };
 constexpr StageNames kSyncNames = { "burst sync", "sync", "tfrec_amd_enable_burst_sync" };
 
 // What every enable checks behind its own arguments, in this order: what the stage works on (`needs`, switched on by
@@ -414,4 +415,49 @@ int tfrec_amd_read_burst_codes(tfrec_amd_ctx *c, tfrec_amd_track *out, size_t ca
 			       uint64_t *n_words)
 {
 	return c ? read_run_bitmaps(c, c->code, c->code.d_words, kCodeNames, out, cap_runs, n_runs, words, cap_words, n_words) : TFREC_AMD_E_INVAL;
+}
+
+// ---- the frame check
+int tfrec_amd_enable_burst_crc(tfrec_amd_ctx *c, int32_t rate, int32_t n_bytes, int32_t skip, int32_t width, uint32_t poly, uint32_t init,
+			       uint32_t xorout, uint32_t flags)
+{
+	if (!c)
+		return TFREC_AMD_E_INVAL;
+	const tfrec_crc::Settings st = { rate, n_bytes, skip, width, poly, init, xorout, flags };
+	if (const char *why = tfrec_crc::refusal(st)) {
+		snprintf(g_err, sizeof(g_err), "%s", why);
+		return TFREC_AMD_E_INVAL;
+	}
+	TRY(enable_preflight(c, kCrcNames, c->trk.on, "the burst track", "tfrec_amd_enable_burst_track", c->crc.on));
+	EnableGuard<BurstCrc> guard(c, c->crc);
+	BurstCrc &o = c->crc;
+	const size_t n = (size_t)c->cfg.n_streams;
+	std::vector<tfrec_crc::Term> terms;
+	uint32_t r0 = 0;
+	tfrec_crc::build(st, terms, r0);
+	static_assert(sizeof(tfrec_crc::Term) == sizeof(uint2), "crc_kernel reads a term as a uint2 (off, col)");
+	for (int k = 0; k < kSets; k++) {
+		TRY(own_device(c, o.d_recs[k], (size_t)c->cap.max_runs * sizeof(tfrec_amd_burst_crc)));
+		TRY(own_device(c, o.d_words[k], c->trk.n_words * sizeof(uint32_t)));
+	}
+	TRY(own_device(c, o.d_carry, n * 512 * sizeof(uint32_t)));
+	TRY(own_device(c, o.d_hist, n * sizeof(uint32_t)));
+	TRY(own_device(c, o.d_terms, (size_t)8 * (size_t)n_bytes * sizeof(uint2)));
+	HIPCHK(hipMemset(o.d_carry, 0, n * 512 * sizeof(uint32_t)));  // (never used before a submit has written them: no first submit CONTINUES)
+	HIPCHK(hipMemset(o.d_hist, 0, n * sizeof(uint32_t)));
+	HIPCHK(hipMemset(o.d_terms, 0, (size_t)8 * (size_t)n_bytes * sizeof(uint2)));
+	if (!terms.empty())
+		HIPCHK(hipMemcpy(o.d_terms, terms.data(), terms.size() * sizeof(uint2), hipMemcpyHostToDevice));
+	o.reach = (int)tfrec_crc::reach(st);
+	o.width = width;
+	o.n_terms = (int)terms.size();
+	o.r0 = r0;
+	o.on = guard.ok = true;
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_read_burst_crcs(tfrec_amd_ctx *c, tfrec_amd_burst_crc *out, size_t cap_runs, uint32_t *n_runs, uint32_t *words, size_t cap_words,
+			      uint64_t *n_words)
+{
+	return c ? read_run_bitmaps(c, c->crc, c->crc.d_words, kCrcNames, out, cap_runs, n_runs, words, cap_words, n_words) : TFREC_AMD_E_INVAL;
 }

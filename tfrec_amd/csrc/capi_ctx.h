@@ -132,6 +132,16 @@ struct BurstCode : RunRecords<tfrec_amd_track> {
 	uint32_t *d_words[kSets] = {};
 	uint32_t *d_carry = nullptr, *d_hist = nullptr;
 };
+// tfrec_amd_enable_burst_crc: the settings as crc_kernel takes them (D, r0, the width, the terms' number); per set
+// the records (RunRecords) and the check bitmap (the track's size); per stream the carried 512 words of input bits and H
+// (crc_carry_kernel); once, the term table (8 N pairs)
+struct BurstCrc : RunRecords<tfrec_amd_burst_crc> {
+	int reach = 0, width = 0, n_terms = 0;
+	uint32_t r0 = 0;
+	uint32_t *d_words[kSets] = {};
+	uint32_t *d_carry = nullptr, *d_hist = nullptr;
+	uint2 *d_terms = nullptr;
+};
 // tfrec_amd_create_decimated (PreStage::kChannel): the carried last pair of every stream
 struct DecIn {
 	uint32_t *d_last = nullptr;
@@ -337,6 +347,7 @@ struct tfrec_amd_ctx {
 	BurstTrack trk;
 	BurstSync syn;
 	BurstCode code;
+	BurstCrc crc;
 	DecIn decin;
 	RunsIn runs_in;
 	SpectrumOut spec;

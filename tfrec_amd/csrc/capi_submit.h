@@ -296,6 +296,14 @@ static CodeBufs code_bufs(const tfrec_amd_ctx *c, int set)
 		 .hist = o.d_hist, .rate = o.rate, .taps = o.taps, .flags = o.flags };
 }
 
+// The frame check's buffers of a set: its input is the bitmap the sync reads
+static CrcBufs crc_bufs(const tfrec_amd_ctx *c, int set)
+{
+	const BurstCrc &o = c->crc;
+	return { .recs = o.d_recs[set], .words = o.d_words[set], .track = c->code.on ? c->code.d_words[set] : c->trk.d_words[set], .carry = o.d_carry,
+		 .hist = o.d_hist, .terms = o.d_terms, .n_terms = o.n_terms, .reach = o.reach, .width = o.width, .r0 = o.r0 };
+}
+
 // The burst sync's buffers of a set: with the line code on, the track it reads is the coded one
 static SyncBufs sync_bufs(const tfrec_amd_ctx *c, int set)
 {
@@ -424,6 +432,8 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 			HIPCHK(launch_burst_code(c->cap.lane.st, out, b, code_bufs(c, set)));
 		if (c->syn.on)  // the burst sync: behind the track's carry kernel, on the table, the working set, the track's bitmap and its own carry
 			HIPCHK(launch_burst_sync(c->cap.lane.st, out, b, sync_bufs(c, set)));
+		if (c->crc.on)  // the frame check: behind the code's (or the track's) carry kernel, on the table, the working set, the sync's input bitmap and its own carry
+			HIPCHK(launch_burst_crc(c->cap.lane.st, out, b, crc_bufs(c, set)));
 		HIPCHK(lane_written(c->cap.lane, set));
 	}
 	if (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) {

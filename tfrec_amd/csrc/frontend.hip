@@ -852,6 +852,7 @@ hipError_t launch_fmdev(hipStream_t st, const FrontOut &o, EventBuf *eb, int wma
 #include "phase.h"     // carrier_head_kernel, phase_kernel, phase_carry_kernel, launch_burst_track_phase
 #include "sync.h"      // sync_kernel, sync_carry_kernel, launch_burst_sync
 #include "linecode.h"  // linecode_kernel, linecode_carry_kernel, launch_burst_code
+#include "crc.h"       // crc_kernel, crc_carry_kernel, launch_burst_crc
 #include "spectrum.h"  // spectrum_kernel, launch_spectrum
 #include "occupancy.h"  // occupancy_kernel, launch_occupancy
 #include "decin.h"     // decin_kernel, capture_pre_kernel and their launchers

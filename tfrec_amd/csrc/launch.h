@@ -73,6 +73,18 @@ struct CodeBufs {
 	int rate;
 	uint32_t taps, flags;
 };
+// The frame check's buffers and settings (crc.h): the set's records and check bitmap, the input bitmap of the same set (the coded
+// one where the line code is on, else the track's), the carried 512 words of input bits and H of every stream, the term table
+// (crc_table.h: n_terms pairs (off, col)), D, r0 and the CRC's width
+struct CrcBufs {
+	tfrec_amd_burst_crc *recs;
+	uint32_t *words;
+	const uint32_t *track;
+	uint32_t *carry, *hist;
+	const uint2 *terms;
+	int n_terms, reach, width;
+	uint32_t r0;
+};
 // The spectrum of rows 0 .. n_rows - 1 of a submit of n_in complex samples per row, and the set's records: [rows][max_records][n_bins]
 // sums and peaks, [rows][max_records] frame counts.  launch_occupancy reads what launch_spectrum has just queued on the stream.
 struct SpectrumBufs {
@@ -120,6 +132,7 @@ hipError_t launch_burst_track_auto(hipStream_t st, const FrontOut &o, const Capt
 hipError_t launch_burst_track_phase(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);  // (k.centre: the set centres in Hz; k.carry: 80 pairs a stream)
 hipError_t launch_burst_sync(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const SyncBufs &k);
 hipError_t launch_burst_code(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const CodeBufs &k);
+hipError_t launch_burst_crc(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const CrcBufs &k);
 hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, const SpectrumBufs &b);
 hipError_t launch_occupancy(hipStream_t st, const SpectrumBufs &b, uint32_t ratio, uint32_t rel, tfrec_amd_occupancy *recs, uint32_t *bits);
 // ... and the parity probes

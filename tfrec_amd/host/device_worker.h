@@ -302,6 +302,11 @@ inline int device_worker::open_context()
 		r = tfrec_amd_enable_burst_sync(ctx, (int32_t)job.track_rate, job.sync_pattern, job.sync_bits, job.sync_errors,
 						job.sync_both ? TFREC_AMD_SYNC_BOTH : 0u);
 	}
+	if (!r && job.checking()) {  // -V: the frame check on the sync's input track, at -G's rate, on -Y's bytes
+		const tfrec_crc::Settings s = job.crc_settings();
+		call = "tfrec_amd_enable_burst_crc";
+		r = tfrec_amd_enable_burst_crc(ctx, s.rate, s.n_bytes, s.skip, s.width, s.poly, s.init, s.xorout, s.flags);
+	}
 	if (!r && job.replay) {  // -R, sized so that every submit fits: its files' runs (a cut adds one per stream), every sample at most
 		uint64_t runs = 0, pairs = 0;
 		for (size_t f = s0; f < s1; f++) {
@@ -604,7 +609,8 @@ inline int device_worker::read_run_bitmaps(int (*reader)(tfrec_amd_ctx *, R *, s
 // with them, each with its match track (job.h: sync_take), in b.syncs in place of b.tracks.  -G rate,auto: every track piece with
 // the centre record of its entry (job.h: centre_take).  -U: the coded records of the same entries too, each a track piece of its
 // own with the coded bits (cut alike): in b.codes beside b.tracks, or with -Y as the sync piece's track piece, b.tracks keeping the
-// raw pieces for the bits line
+// raw pieces for the bits line.  -V (with -Y): the check records of the same entries, each with its check track (job.h: crc_take),
+// in b.crcs beside b.syncs
 inline int device_worker::read_tracks(size_t k, batch_result &b)
 {
 	std::vector<tfrec_amd_track> recs;
@@ -649,6 +655,16 @@ inline int device_worker::read_tracks(size_t k, batch_result &b)
 			return TFREC_AMD_E_STATE;
 		}
 	}
+	std::vector<tfrec_amd_burst_crc> vrecs;  // -V: the check records and words of the same entries
+	std::vector<uint32_t> vwords;
+	if (job.checking()) {
+		if ((r = read_run_bitmaps(tfrec_amd_read_burst_crcs, vrecs, vwords)))
+			return r;
+		if (vrecs.size() != recs.size()) {
+			fprintf(stderr, "tfrec_amd: device %d batch %zu: %zu check records beside %zu track records\n", device, k, vrecs.size(), recs.size());
+			return TFREC_AMD_E_STATE;
+		}
+	}
 	for (size_t q = 0; q < recs.size(); q++) {
 		tfrec_amd_track x = recs[q];
 		if (!cut_at_file_end(x, plan[k].file, file_blocks, true))
@@ -658,6 +674,8 @@ inline int device_worker::read_tracks(size_t k, batch_result &b)
 		track_piece t = track_take(x, words.data(), n);
 		if (job.centring())
 			centre_take(t, crecs[q]);
+		if (job.checking())
+			b.crcs.push_back(crc_take(vrecs[q], vwords.data(), t));
 		if (job.coding()) {  // the coded piece: the cut entry with the coded record's n_ones and bits; the sync's frames are read from it
 			x.n_ones = urecs[q].n_ones;
 			track_piece u = track_take(x, uwords.data(), n);

@@ -194,6 +194,17 @@ struct dc_report {
 	}
 };
 
+// -Y's frame line; with -V its verdict as one more field (job.h: crc_verdict) on the check piece of the same burst: checked[i]
+// belongs to the i-th burst that ended with the batch -- the mergers see the same flags, so the chains end together, in one order
+static std::string frame_line(const std::string &file, const sync_piece &x, const sync_frame &f, const job_settings &job,
+			      const std::vector<crc_piece> &checked, size_t i, uint64_t crc_reach)
+{
+	std::string s = sync_line(file, x, f, job.sync_lsb);
+	if (job.checking())
+		s += std::string(" ") + crc_verdict(checked.at(i), f, job.sync_bytes, crc_reach);
+	return s;
+}
+
 // -M, -Q, -C: a stage's chains across the batches (job.h: chain_merger); take() sends the bursts that ended with a batch into the
 // scan table, or prints the stage's line for each
 template <class R>
@@ -454,6 +465,10 @@ int gpu_engine::run()
 	sync_merger syncs;
 	std::vector<sync_piece> framed;
 	syncs.begin(n);
+	chain_merger<crc_piece> crcs;
+	std::vector<crc_piece> checked;
+	crcs.begin(n);
+	const uint64_t crc_reach = job.checking() ? (uint64_t)tfrec_crc::reach(job.crc_settings()) : 0;
 	if (job.spectrum)
 		spec.begin(job);
 	if (job.occupancy())
@@ -495,6 +510,9 @@ int gpu_engine::run()
 				envelopes.take(b.envelopes, workers[d].plan[k], file_blocks, files, into);
 			if (job.clocking())  // -C: likewise, behind -Q's lines of the batch
 				clocks.take(b.clocks, workers[d].plan[k], file_blocks, files, into);
+			checked.clear();
+			if (job.checking())  // -V (with -Y): the check pieces of the sync's entries -- the same flags, so the chains end together, in one order
+				crcs.take(b.crcs, workers[d].plan[k], file_blocks, checked);
 			if (job.coding()) {  // -G -U: -G's lines of each burst, its code line, and with -Y a line per frame found on the coded track
 				said.clear();
 				tracks.take(b.tracks, workers[d].plan[k], file_blocks, said);
@@ -504,6 +522,11 @@ int gpu_engine::run()
 					syncs.take(b.syncs, workers[d].plan[k], file_blocks, framed);
 				else
 					codes.take(b.codes, workers[d].plan[k], file_blocks, coded);
+				if (job.checking() && checked.size() != framed.size()) {
+					fprintf(stderr, "tfrec_amd: batch %zu: %zu check chains ended beside %zu sync chains\n", k, checked.size(), framed.size());
+					rc = TFREC_AMD_E_STATE;
+					break;
+				}
 				for (size_t i = 0; i < said.size(); i++) {  // (the same entries with the same flags: the chains end together, in one order)
 					const track_piece &x = said[i];
 					if (job.centring())
@@ -514,19 +537,29 @@ int gpu_engine::run()
 					printf("%s\n", code_line(files[x.stream], job.syncing() ? framed[i].trk : coded[i], job.track_rate).c_str());
 					if (job.syncing())
 						for (const sync_frame &f : sync_frames(framed[i], job))
-							printf("%s\n", sync_line(files[x.stream], framed[i], f, job.sync_lsb).c_str());
+							printf("%s\n", frame_line(files[x.stream], framed[i], f, job, checked, i, crc_reach).c_str());
+					if (job.checking())  // -V: the burst's crc line behind its frame lines
+						printf("%s\n", crc_line(files[x.stream], checked[i], crc_reach).c_str());
 				}
 			} else if (job.syncing()) {  // -G -Y: -G's line of each burst, and behind it a line per frame found in it
 				framed.clear();
 				syncs.take(b.syncs, workers[d].plan[k], file_blocks, framed);
-				for (const sync_piece &x : framed) {
+				if (job.checking() && checked.size() != framed.size()) {
+					fprintf(stderr, "tfrec_amd: batch %zu: %zu check chains ended beside %zu sync chains\n", k, checked.size(), framed.size());
+					rc = TFREC_AMD_E_STATE;
+					break;
+				}
+				for (size_t i = 0; i < framed.size(); i++) {
+					const sync_piece &x = framed[i];
 					if (job.centring())  // -G rate,auto and -G rate,psk: the burst's centre ahead of its bits
 						printf("%s\n", centre_line(files[x.stream], x.trk).c_str());
 					printf("%s\n", track_line(files[x.stream], x.trk, job.track_rate).c_str());
 					if (job.amplitude())  // -O: the burst's pulses behind its bits
 						printf("%s\n", pulses_line(files[x.stream], x.trk).c_str());
 					for (const sync_frame &f : sync_frames(x, job))
-						printf("%s\n", sync_line(files[x.stream], x, f, job.sync_lsb).c_str());
+						printf("%s\n", frame_line(files[x.stream], x, f, job, checked, i, crc_reach).c_str());
+					if (job.checking())  // -V: the burst's crc line behind its frame lines
+						printf("%s\n", crc_line(files[x.stream], checked[i], crc_reach).c_str());
 				}
 			} else if (job.tracking()) {  // -G: likewise, behind -C's lines of the batch
 				said.clear();

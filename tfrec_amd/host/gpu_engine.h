@@ -268,6 +268,21 @@ public:
 		job.code_taps = taps;
 		job.code_invert = invert;
 	}
+	// -V (with -G and -Y): the frame check (tfrec_amd_enable_burst_crc) on the track the sync reads, at -G's rate, on
+	// -Y's bytes in -Y's byte order: width, poly, init, xorout, the skipped bytes and INVERT.  run() merges the check pieces'
+	// chains beside the sync's (job.h: chain_merger<crc_piece>); every frame line ends in one more field, ok, bad or - (job.h:
+	// crc_verdict), and behind a burst's frame lines comes
+	//   crc <file> <start_sample> <n_samples> <n_ok> <sample|->
+	// (job.h: crc_line).  Nothing of it has been measured on real recordings.
+	void set_crc(int width, uint32_t poly, uint32_t init, uint32_t xorout, int skip, bool invert)
+	{
+		job.crc_width = width;
+		job.crc_poly = poly;
+		job.crc_init = init;
+		job.crc_xorout = xorout;
+		job.crc_skip = skip;
+		job.crc_invert = invert;
+	}
 	// -k: keep.  A file is processed in whole pieces only and nothing is padded; before the first batch behind a
 	// file's last one is submitted -- and at the end of the job -- its stream is saved (tfrec_amd_save_streams) to
 	// <prefix>.<file index>.state, and at the end of a run without an error the bytes that did not fill a piece are written to

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/tfrec_amd.h"
+#include "../csrc/crc_table.h"  // the frame check's settings, as the enable call checks them: plain C++
 
 // -T, -t, -W and the tune of one dump file (tfrec_gpu -p; tune: -f minus -c, in Hz, tfrec_amd_tune_streams)
 struct file_settings {
@@ -111,6 +112,10 @@ struct job_settings {
 	bool sync_lsb = false;         // ... the frames' hex LSB-first per byte
 	uint32_t code_taps = 0;        // set_code (0: none): -U, the line code's taps, bit j - 1 a delay of j symbols at -G's rate
 	bool code_invert = false;      // ... and its INVERT
+	int crc_width = 0;             // set_crc (0: none): -V, the frame check's width; its N is sync_bytes, its byte order sync_lsb, its rate -G's
+	uint32_t crc_poly = 0, crc_init = 0, crc_xorout = 0;  // ...
+	int crc_skip = 0;              // ... the bytes behind the sync word that the CRC does not cover
+	bool crc_invert = false;       // ... and its INVERT
 	const std::vector<replay_file> *replay = NULL;  // set_replay (NULL: the files are dumps)
 	std::string keep_prefix;       // set_keep ("": none)
 	std::string cont_prefix;       // set_continue ("": none)
@@ -126,6 +131,13 @@ struct job_settings {
 	bool tracking() const { return track_rate != 0; }  // -G (never with -s or -A)
 	bool syncing() const { return sync_bits != 0; }  // -Y (only with -G)
 	bool coding() const { return code_taps != 0; }  // -U (only with -G)
+	bool checking() const { return crc_width != 0; }  // -V (only with -Y)
+	tfrec_crc::Settings crc_settings() const  // tfrec_amd_enable_burst_crc's arguments
+	{
+		const tfrec_crc::Settings s = { (int32_t)track_rate, (int32_t)sync_bytes, (int32_t)crc_skip, (int32_t)crc_width, crc_poly, crc_init, crc_xorout,
+						(sync_lsb ? TFREC_AMD_CRC_LSB : 0u) | (crc_invert ? TFREC_AMD_CRC_INVERT : 0u) };
+		return s;
+	}
 	bool amplitude() const { return track_level >= 0; }  // -O (only with -G)
 	bool centring() const { return track_auto; }  // -G rate,auto or -G rate,psk: the track has centre records (never with -O)
 	bool phasing() const { return track_lag != 0; }  // -G rate,psk
@@ -420,10 +432,18 @@ struct sync_piece : tfrec_amd_burst_sync {
 	bool hit(uint64_t k) const { return (match[k >> 5] >> (k & 31)) & 1u; }
 };
 
+// -V: a check record with its check track (packed as a track_piece's bits)
+struct crc_piece : tfrec_amd_burst_crc {
+	std::vector<uint32_t> ok;
+	uint64_t kept() const { return std::min<uint64_t>(n_samples, kTrackKeep); }
+	bool bit(uint64_t k) const { return (ok[k >> 5] >> (k & 31)) & 1u; }
+};
+
 struct batch_result {
 	std::vector<track_piece> tracks;
 	std::vector<sync_piece> syncs;  // (-Y: in place of tracks; -U -Y: beside them, each with the CODED piece of its entry for its track piece)
 	std::vector<track_piece> codes;  // (-U without -Y: the coded pieces of the entries in tracks)
+	std::vector<crc_piece> crcs;  // (-V: the check pieces of the entries in syncs)
 	std::vector<tfrec_amd_burst> bursts;
 	std::vector<tfrec_amd_envelope> envelopes;
 	std::vector<tfrec_amd_clock> clocks;
@@ -993,7 +1013,98 @@ inline uint64_t code_span(uint32_t taps, long rate)
 // code <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->: -G's bits line of the coded piece
 inline std::string code_line(const std::string &file, const track_piece &c, long rate) { return "code" + track_line(file, c, rate).substr(4); }
 
+// ---- -V: the frame check (include/tfrec_amd.h: "Frame check", whose text is normative; tfrec_amd/crc.py restates merge, the verdict and
+// the line; ../csrc/crc_table.h holds the settings' rules)
+
+// -V's argument: width,poly[,init[,xorout[,skip[,inv]]]] -- width and skip decimal, poly, init and xorout 1 .. 8 hex digits, inv 0 or
+// 1 -> the fields (false: bad).  Whether the settings hold together is tfrec_crc::refusal's to say, once -G's rate and -Y's bytes
+// are known.
+inline bool crc_parse(const char *arg, int &width, uint32_t &poly, uint32_t &init, uint32_t &xorout, int &skip, bool &invert)
+{
+	std::vector<std::string> part(1);
+	for (const char *q = arg; *q; q++) {
+		if (*q == ',')
+			part.push_back("");
+		else
+			part.back() += *q;
+	}
+	if (part.size() < 2 || part.size() > 6)
+		return false;
+	for (size_t i = 0; i < part.size(); i++) {
+		const bool hex = i >= 1 && i <= 3;
+		if (part[i].empty() || part[i].size() > (hex ? 8u : 3u) || part[i].find_first_not_of(hex ? "0123456789abcdefABCDEF" : "0123456789") != std::string::npos)
+			return false;
+	}
+	width = atoi(part[0].c_str());
+	poly = (uint32_t)strtoul(part[1].c_str(), NULL, 16);
+	init = part.size() > 2 ? (uint32_t)strtoul(part[2].c_str(), NULL, 16) : 0u;
+	xorout = part.size() > 3 ? (uint32_t)strtoul(part[3].c_str(), NULL, 16) : 0u;
+	skip = part.size() > 4 ? atoi(part[4].c_str()) : 0;
+	invert = false;
+	if (part.size() > 5) {
+		if (part[5] != "0" && part[5] != "1")
+			return false;
+		invert = part[5] == "1";
+	}
+	return width != 0;
+}
+
+// a device record, the submit's check bitmap and the entry's track piece -> the piece, as many samples of it as the track piece has
+// (the file's end may cut both): n_ok and first_at counted again on what is kept of a cut piece
+inline crc_piece crc_take(const tfrec_amd_burst_crc &r, const uint32_t *words, const track_piece &t)
+{
+	crc_piece p;
+	static_cast<tfrec_amd_burst_crc &>(p) = r;
+	p.stream = t.stream;
+	p.flags = t.flags;
+	const bool cut = t.n_samples < r.n_samples;
+	p.n_samples = t.n_samples;
+	track_append(p.ok, 0, words, r.bit_offset, p.n_samples);
+	if (cut) {
+		p.n_ok = 0;
+		p.first_at = 0xffffffffu;
+		for (uint64_t k = 0; k < p.kept(); k++) {
+			if (!p.bit(k))
+				continue;
+			if (!p.n_ok++)
+				p.first_at = (uint32_t)k;
+		}
+	}
+	return p;
+}
+
+// piece p, which CONTINUES the chain c, merged into it (the header's Merging): the check tracks concatenated, n_samples and n_ok
+// added, first_at that of the first piece that has one, offset by the samples ahead of it
+inline void crc_add(crc_piece &c, const crc_piece &p)
+{
+	if (!p.ok.empty())
+		track_append(c.ok, c.kept(), p.ok.data(), 0, p.kept());
+	if (c.first_at == 0xffffffffu && p.first_at != 0xffffffffu)
+		c.first_at = c.n_samples + p.first_at;
+	c.n_samples += p.n_samples;
+	c.n_ok += p.n_ok;
+	c.flags = (c.flags & TFREC_AMD_RUN_CONTINUES) | (p.flags & TFREC_AMD_RUN_OPEN);
+}
+
+// The header's Verdict: a frame of polarity + with all 8 N payload bits is "ok" iff v[c + D] = 1 on the chain's merged check track,
+// else "bad"; any other frame has none, "-".  (c + D is the frame's last bit: inside the input; behind the kept 2^20 samples: none)
+inline const char *crc_verdict(const crc_piece &v, const sync_frame &f, int n_bytes, uint64_t D)
+{
+	if (!f.plus || f.bits.size() != (size_t)(8 * n_bytes) || f.c + D >= v.kept())
+		return "-";
+	return v.bit(f.c + D) ? "ok" : "bad";
+}
+
+// crc <file> <start_sample> <n_samples> <n_ok> <sample|->: the last field is start_sample + first_at - D, where a sync word would
+// have ended
+inline std::string crc_line(const std::string &file, const crc_piece &c, uint64_t D)
+{
+	return "crc " + file + " " + std::to_string((long long)c.start_sample) + " " + std::to_string(c.n_samples) + " " + std::to_string(c.n_ok) + " " +
+	       (c.first_at == 0xffffffffu ? std::string("-") : std::to_string((long long)c.start_sample + (long long)c.first_at - (long long)D));
+}
+
 inline void chain_add(tfrec_amd_burst &c, const tfrec_amd_burst &p) { burst_add(c, p); }
+inline void chain_add(crc_piece &c, const crc_piece &p) { crc_add(c, p); }
 inline void chain_add(sync_piece &c, const sync_piece &p) { sync_add(c, p); }
 inline void chain_add(track_piece &c, const track_piece &p) { track_add(c, p); }
 inline void chain_add(tfrec_amd_clock &c, const tfrec_amd_clock &p) { clock_add(c, p); }

@@ -139,7 +139,7 @@
 // bits line stdout gets, for every plateau of matching samples inside the burst, in order,
 //   frame <file> <start_sample> <sync_sample> <errors> <+|-> <n_bits> <hex|->
 // sync_sample: the plateau's middle, where the word's last bit is read; the hex: the `bytes` bytes (1 .. 256, default 8) read at
-// symbol centres behind it, MSB-first, as far as the burst reaches, complemented under "-".  No CRC is checked.  A word whose span
+// symbol centres behind it, MSB-first, as far as the burst reaches, complemented under "-".  No CRC is checked unless -V asks for it.  A word whose span
 // at the rate exceeds 2047 samples is refused.  Works where -G works.  The defaults are not tuned on anything: nothing of it has
 // been measured on real recordings.
 // A fifth field, -Y hex,errors,bytes,both,1 (lsb): the frames' hex is LSB-first per byte -- every byte assembled with the first
@@ -151,8 +151,17 @@
 // and 17; nrzi = 1; nrzs = 1,inv), complemented under inv.  Behind each burst's bits line stdout gets
 //   code <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->
 // the coded track through -G's slicer; -Y's frames are found on and read from the coded track.  Taps whose span at the rate exceeds
-// 2047 samples are refused.  Works with what -G works with.  No CRC, no Manchester decoding, no additive scrambler; nothing of it has
+// 2047 samples are refused.  Works with what -G works with.  No CRC of its own (see -V), no Manchester decoding, no additive scrambler; nothing of it has
 // been measured on real recordings.
+// -V width,poly[,init[,xorout[,skip[,inv]]]] (not in the reference; with -G and -Y): the frame check (tfrec_amd_enable_burst_crc,
+// DESIGN.md 6z): every frame's CRC, checked on the GPU on the track -Y reads.  The frame is -Y's bytes in -Y's byte order (its fifth
+// field); width is 8, 16, 24 or 32, poly, init and xorout are hex, skip the bytes behind the sync word that the CRC does not cover,
+// inv 1: every bit complemented.  The CRC is unreflected, its field the frame's last width / 8 bytes, big-endian.  Every frame line
+// ends in one more field -- ok, bad, or - for a frame that is short or of polarity - --, and behind a burst's frame lines stdout gets
+//   crc <file> <start_sample> <n_samples> <n_ok> <sample|->
+// the samples of the burst at which a frame that checks ends, and where the sync word of the first would have ended: a frame finder
+// for bursts whose sync word nobody knows.  With init 0 and xorout 0 a constant stretch checks too.  Not with -Y's both; a frame that
+// reaches over 16383 samples at the rate is refused.  Nothing of it has been measured on real recordings.
 // -P bins[,frames_per_record] (not in the reference): the power spectrum of ONE recording, beside its decoding: an
 // exact integer DFT of bins = 64, 128, 256, 512 or 1024 bins over the raw input -- at 1.536 MS/s, or given with -x, or with -r / -F --,
 // per record of frames_per_record frames (1 .. 16384; default: the frames one block's input holds, at least 1) the sum and the peak
@@ -336,6 +345,9 @@ struct cli {
 	long sync_errors = 0, sync_bytes = 8, sync_both = 0, sync_lsb = 0;
 	uint32_t code_taps = 0;  // -U (0: not given): the taps and INVERT
 	bool code_invert = false;
+	int crc_width = 0, crc_skip = 0;  // -V (width 0: not given)
+	uint32_t crc_poly = 0, crc_init = 0, crc_xorout = 0;
+	bool crc_invert = false;
 	const char *keep_prefix = NULL, *cont_prefix = NULL;  // -k, -K
 	bool have_center = false, have_format = false;  // -c, -F given (-R refuses them)
 	std::vector<replay_file> captures;  // -R: one per file index of <prefix>.idx
@@ -369,7 +381,7 @@ struct cli {
 
 static void usage()
 {
-	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-G rate[,centre_hz]] [-G rate,auto] [-G rate,psk[,lag]] [-O level] [-Y hex[,errors[,bytes[,both]]]] [-Y hex,errors,bytes,both,1] [-U g3ruh|nrzi|nrzs|hextaps[,inv]] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
+	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-G rate[,centre_hz]] [-G rate,auto] [-G rate,psk[,lag]] [-O level] [-Y hex[,errors[,bytes[,both]]]] [-Y hex,errors,bytes,both,1] [-U g3ruh|nrzi|nrzs|hextaps[,inv]] [-V width,poly[,init[,xorout[,skip[,inv]]]]] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
 			"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
 			"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
 			"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
@@ -410,6 +422,9 @@ static void usage()
 			"  -U code[,inv] with -G: a line code ahead of the slicer and of -Y: g3ruh (descrambler, taps 12 and 17), nrzi, nrzs, or hex taps\n"
 			"              (bit j - 1: the track XORed with itself j symbols ago), inv: complemented; behind each bits line a line 'code <file>\n"
 			"              <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->', and -Y's frames are read from the coded track\n"
+			"  -V w,p[,i[,x[,s[,v]]]]  with -G and -Y: check every frame's CRC on the GPU: width w (8, 16, 24, 32), poly p, init i and xorout x in\n"
+			"              hex, s bytes skipped behind the sync word, v = 1: complemented bits; the frame is -Y's n bytes, the CRC its last w / 8:\n"
+			"              every frame line ends in ok, bad or -, and behind them a line 'crc <file> <start_sample> <n_samples> <n_ok> <sample|->'\n"
 			"  -k prefix   keep: for a recording that arrives in parts.  Every -L file is processed in whole blocks only (nothing is padded), then\n"
 			"              its receiver's state is saved to <prefix>.<file index>.state and the bytes that filled no block to\n"
 			"              <prefix>.<file index>.rest\n"
@@ -492,7 +507,7 @@ bool cli::parse_format(const char *arg)
 int cli::parse(int argc, char **argv)
 {
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCG:O:Y:U:k:K:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCG:O:Y:U:V:k:K:h")) != -1) {
 		switch (c) {
 		case 'M': meter = true; break;
 		case 'Q': envelope = true; break;
@@ -556,6 +571,13 @@ int cli::parse(int argc, char **argv)
 		case 'U':
 			if (!code_parse(optarg, code_taps, code_invert)) {
 				fprintf(stderr, "tfrec_gpu: bad -U '%s': want g3ruh, nrzi, nrzs or 1 .. 8 hex digits of taps (not 0), each with an optional ,inv\n", optarg);
+				return 1;
+			}
+			break;
+		case 'V':
+			if (!crc_parse(optarg, crc_width, crc_poly, crc_init, crc_xorout, crc_skip, crc_invert)) {
+				fprintf(stderr, "tfrec_gpu: bad -V '%s': want <width>,<poly>[,<init>[,<xorout>[,<skip>[,<inv>]]]]: width 8, 16, 24 or 32, poly, init and "
+						"xorout 1 .. 8 hex digits, skip a number, inv 0 or 1\n", optarg);
 				return 1;
 			}
 			break;
@@ -782,6 +804,22 @@ int cli::check() const
 		fprintf(stderr, "tfrec_gpu: -U: the taps %x at %ld bit/s span %llu samples, more than 2047\n", (unsigned)code_taps, track_rate,
 			(unsigned long long)code_span(code_taps, track_rate));
 		return 1;
+	}
+	if (crc_width && !(sync_bits && track_rate)) {
+		fprintf(stderr, "tfrec_gpu: -V checks the frames of -Y: give -G rate and -Y hex,errors,bytes with it\n");
+		return 1;
+	}
+	if (crc_width && sync_both) {
+		fprintf(stderr, "tfrec_gpu: -V checks frames of polarity + alone: not with -Y's both\n");
+		return 1;
+	}
+	if (crc_width) {
+		const tfrec_crc::Settings s = { (int32_t)track_rate, (int32_t)sync_bytes, (int32_t)crc_skip, (int32_t)crc_width, crc_poly, crc_init, crc_xorout,
+						(sync_lsb ? TFREC_AMD_CRC_LSB : 0u) | (crc_invert ? TFREC_AMD_CRC_INVERT : 0u) };
+		if (const char *why = tfrec_crc::refusal(s)) {
+			fprintf(stderr, "tfrec_gpu: -V: %s (%ld bit/s, %ld bytes: D = %lld)\n", why, track_rate, sync_bytes, tfrec_crc::reach(s));
+			return 1;
+		}
 	}
 	if (track_rate && (hexfile || have_scan || have_auto)) {
 		fprintf(stderr, "tfrec_gpu: -G reads the bursts of -L files or of a capture (-R), a line per burst: not with -X, -s or -A\n");
@@ -1036,6 +1074,8 @@ int cli::run()
 		e.set_sync(sync_pattern, sync_bits, (int)sync_errors, (int)sync_bytes, sync_both != 0, sync_lsb != 0);
 	if (code_taps)
 		e.set_code(code_taps, code_invert);
+	if (crc_width)
+		e.set_crc(crc_width, crc_poly, crc_init, crc_xorout, crc_skip, crc_invert);
 	if (keep_prefix)
 		e.set_keep(keep_prefix);
 	if (cont_prefix)
