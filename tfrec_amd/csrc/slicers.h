@@ -114,10 +114,13 @@ __device__ __forceinline__ void tfa2_candidate(Slicer &f, BitWriter &bw, int g, 
 }
 
 // One sample of tfa2_demod::demod inside a window (tfa2.cpp:357-412), ld = (int)iir->step(fm_dev(...)).
-// iq: the decimated sample itself (looked at while 4 < bitcnt < 10 only: tfa2.cpp:371-375)
-__device__ __forceinline__ void tfa2_sample(Slicer &f, BitWriter &bw, int g, int k, int ld, uint32_t iq, double spb, uint64_t nb_mul)
+// -> whether the sample is in the power phase 4 < bitcnt < 10 (tfa2.cpp:371-375, bitcnt as it stands before this sample's
+// candidate edge: the sample at which it becomes 5 is not, the one at which it becomes 10 is).  rssi_i is not touched here: no
+// decision reads it, so the caller sums the phase's samples behind the walk (tfa2_power below)
+__device__ __forceinline__ bool tfa2_sample(Slicer &f, BitWriter &bw, int g, int k, int ld, double spb, uint64_t nb_mul)
 {
 	const int index = slicer_index(f, k);
+	const bool power = f.bitcnt > 4 && f.bitcnt < 10;
 	if (f.bitcnt < 10) {
 		const bool up = ld > f.dmax, down = ld < f.dmin;
 		if (up)
@@ -128,16 +131,19 @@ __device__ __forceinline__ void tfa2_sample(Slicer &f, BitWriter &bw, int g, int
 			f.offset = (f.dmax + f.dmin) / 2;
 			tfa2_thresholds(f);
 		}
-		if (f.bitcnt > 4) {  // wrapping int32 arithmetic as in the reference binary (tfa2.cpp:373)
-			const int I = (int)(int16_t)(iq & 0xffff), Q = (int)iq >> 16;
-			const uint32_t t = (uint32_t)f.rssi_i + (uint32_t)(I * I) + (uint32_t)(Q * Q);
-			f.rssi_i = (int)((uint32_t)f.rssi_i + (uint32_t)((int)t / 100));
-		}
 	}
 	const int hi = f.hi, lo = f.lo;
 	const int bit = ld > hi ? 1 : 0;
 	if ((ld > hi || ld < lo) && bit != f.last_bit)
 		tfa2_candidate(f, bw, g, index, bit, spb, nb_mul);
+	return power;
+}
+// The power phase's update for one decimated sample: wrapping int32 arithmetic as in the reference binary (tfa2.cpp:373)
+__device__ __forceinline__ int tfa2_power(int rssi_i, uint32_t iq)
+{
+	const int I = (int)(int16_t)(iq & 0xffff), Q = (int)iq >> 16;
+	const uint32_t t = (uint32_t)rssi_i + (uint32_t)(I * I) + (uint32_t)(Q * Q);
+	return (int)((uint32_t)rssi_i + (uint32_t)((int)t / 100));
 }
 
 // Run one window [g0, last] of a TFA_1 (KIND 0) or TFA_2-family (KIND 1) slicer.  `f` carries the state in and
@@ -149,6 +155,78 @@ struct Slot8 {
 struct Slot4 {
 	uint4 q0, q1, q2, q3;
 };
+
+// a 16-byte load that was moved back by d samples to stay inside the window: the wanted samples to the front (d >= 4: none is)
+__device__ __forceinline__ uint4 quad_shift(uint4 v, int d)
+{
+	if (d >= 2) {
+		v.x = v.z;
+		v.y = v.w;
+		d -= 2;
+	}
+	if (d >= 1) {
+		v.x = v.y;
+		v.y = v.z;
+		v.z = v.w;
+	}
+	return v;
+}
+
+// The power phase of one window part [g0, last], behind its walk: tfa2_power over the samples [ga, gb] in order (ga < 0: the
+// part has none).  The samples that update rssi_i are one contiguous run, since bitcnt never decreases inside a window, and
+// nothing but the flush reads rssi_i: so the walk only notes where the run begins and ends, and the samples are read here in
+// 32-sample pieces, the next piece requested before the current one is consumed -- one wait per piece where the walk had one
+// per sample.  Only samples of [g0, last] are read: a 16-byte load that would pass `last` is moved back to end there.
+__device__ __forceinline__ int tfa2_power_run(int rssi_i, int ga, int gb, int g0, int last, const uint32_t *__restrict__ drow)
+{
+	if (__ballot(ga >= 0) == 0ull)
+		return rssi_i;
+	if (ga >= 0 && last - g0 < 3) {  // shorter than one 16-byte load (a resumed window that closes at once): sample by sample
+		for (int g = ga; g <= gb; g++)
+			rssi_i = tfa2_power(rssi_i, drow[g]);
+		ga = -1;
+	}
+	if (ga < 0)
+		return rssi_i;
+	const int lim = last - 3;  // >= g0
+	auto load = [&](int base) -> Slot8 {
+		auto quad = [&](int g) -> uint4 {
+			const u32x4_a4 v = *reinterpret_cast<const u32x4_a4 *>(drow + (g < lim ? g : lim));
+			return make_uint4(v.x, v.y, v.z, v.w);
+		};
+		Slot8 r;
+		r.q0 = quad(base); r.q1 = quad(base + 4); r.q2 = quad(base + 8); r.q3 = quad(base + 12);
+		r.q4 = quad(base + 16); r.q5 = quad(base + 20); r.q6 = quad(base + 24); r.q7 = quad(base + 28);
+		return r;
+	};
+	Slot8 cur = load(ga);
+	for (int base = ga; base <= gb; base += kChunk) {
+		const Slot8 nxt = load(base + kChunk <= gb ? base + kChunk : base);
+		if (base + 28 > lim) {  // the window ends in this piece: its last loads were moved back
+			const int d = base - lim;
+			cur.q0 = quad_shift(cur.q0, d); cur.q1 = quad_shift(cur.q1, d + 4); cur.q2 = quad_shift(cur.q2, d + 8);
+			cur.q3 = quad_shift(cur.q3, d + 12); cur.q4 = quad_shift(cur.q4, d + 16); cur.q5 = quad_shift(cur.q5, d + 20);
+			cur.q6 = quad_shift(cur.q6, d + 24); cur.q7 = quad_shift(cur.q7, d + 28);
+		}
+		const int left = gb - base;  // sample k of the piece belongs to the run if k <= left
+		auto quad = [&](const uint4 &v, int k) {
+			const int r0 = tfa2_power(rssi_i, v.x);
+			rssi_i = k <= left ? r0 : rssi_i;
+			const int r1 = tfa2_power(rssi_i, v.y);
+			rssi_i = k + 1 <= left ? r1 : rssi_i;
+			const int r2 = tfa2_power(rssi_i, v.z);
+			rssi_i = k + 2 <= left ? r2 : rssi_i;
+			const int r3 = tfa2_power(rssi_i, v.w);
+			rssi_i = k + 3 <= left ? r3 : rssi_i;
+		};
+		quad(cur.q0, 0); quad(cur.q1, 4); quad(cur.q2, 8); quad(cur.q3, 12);
+		quad(cur.q4, 16); quad(cur.q5, 20); quad(cur.q6, 24); quad(cur.q7, 28);
+		// (without this the copy is scheduled register by register into the sums above, each behind a wait for a load just issued)
+		__builtin_amdgcn_sched_barrier(0);
+		cur = nxt;
+	}
+	return rssi_i;
+}
 
 // Run one window [g0, last] of a TFA_1 (KIND 0) or TFA_2-family (KIND 1) slicer.  Each 32-sample chunk is moved
 // from registers to the lane's LDS column, the next chunk's loads are issued, then the chunk is walked from
@@ -218,6 +296,8 @@ __device__ __forceinline__ int run_window(Slicer &f, BitWriter &bw, int g0, int 
 			return r;
 		};
 		Slot4 cur = load(0);
+		int ga = -1, gb = -1;  // this call's first and last sample of the power phase
+		int done = nch;
 		for (int i = 0; i < nch; i++) {
 			my_lds[0 * 64] = cur.q0; my_lds[1 * 64] = cur.q1; my_lds[2 * 64] = cur.q2; my_lds[3 * 64] = cur.q3;
 			const Slot4 nxt = load(i + 1 < nch ? i + 1 : i);
@@ -234,18 +314,30 @@ __device__ __forceinline__ int run_window(Slicer &f, BitWriter &bw, int g0, int 
 					if (8 * q + t < nv) {
 						const int ld = (int)(int16_t)((vw[t >> 1] >> (16 * (t & 1))) & 0xffff);
 						// sample 8 q + t of the chunk: group 2 q + (t >> 2) of four, component t & 3
-						// (the sample itself is looked at while 4 < bitcnt < 10 only: tfa2.cpp:371-375.  Staging the chunk's 32 samples in
-						// LDS instead of this load-and-wait made the slicers 20 % faster and the batch 3 % slower: profiles/NOTES.md round 3)
-						const uint32_t iq = (f.bitcnt > 4 && f.bitcnt < 10) ? drow[g0 + kChunk * i + 8 * q + t] : 0u;
-						tfa2_sample(f, bw, g0 + kChunk * i + 8 * q + t, 8 * q + t, ld, iq, spb, nb_mul);
+						// (the sample itself is looked at while 4 < bitcnt < 10 only, and only for rssi_i: tfa2.cpp:371-375.  No load of it
+						// here: a load-and-wait cost the whole wave a memory round trip at every sample at which one lane was in that
+						// phase, and staging every chunk's 32 samples in LDS made the slicers 20 % faster and the batch 3 % slower
+						// (profiles/NOTES.md round 3).  The phase's samples are one run [ga, gb], summed behind the loop: tfa2_power_run,
+						// profiles/slicer_power_sum_ab.txt)
+						const int g = g0 + kChunk * i + 8 * q + t;
+						if (tfa2_sample(f, bw, g, 8 * q + t, ld, spb, nb_mul)) {
+							ga = ga < 0 ? g : ga;
+							gb = g;
+						}
 					}
 				}
 			}
 			bw.chunk_end();
 			cur = nxt;
-			if (head_chunks > 0 && (f.bitcnt >= 10 || i + 1 >= head_chunks) && i + 1 < nch)
-				return i + 1;
+			if (head_chunks > 0 && (f.bitcnt >= 10 || i + 1 >= head_chunks) && i + 1 < nch) {
+				done = i + 1;
+				break;
+			}
 		}
+		// before every way out: the hand-over at head_chunks or on bitcnt >= 10, and the window's end
+		f.rssi_i = tfa2_power_run(f.rssi_i, ga, gb, g0, last, drow);
+		if (done < nch)
+			return done;
 	}
 	const int bl = last >> 13;
 	if (bl != f.cur_block) {
