@@ -1288,6 +1288,69 @@ int tfrec_amd_enable_burst_crc(tfrec_amd_ctx *ctx, int32_t rate, int32_t n_bytes
 int tfrec_amd_read_burst_crcs(tfrec_amd_ctx *ctx, tfrec_amd_burst_crc *out, size_t cap_runs, uint32_t *n_runs, uint32_t *words,
 			      size_t cap_words, uint64_t *n_words);
 
+/* Packet check (tfrec_amd_enable_burst_packets): an optional stage behind the burst sync and beside the frame check,
+ * for transmitters whose packets carry their own length (the CC1101, RFM69, SX1231 and Si446x packet engines): preamble, sync word, a
+ * LENGTH BYTE, the payload, a CRC over both, optionally all of it XORed with a whitening sequence.  The frame check assumes one
+ * length per context; here the length is data, so every match of the sync is a candidate that is read, de-whitened, measured and
+ * checked on its own.  There is no reference counterpart: this text is normative, tfrec_amd/packet.py restates it.  Exact integers.
+ *   Settings: fixed at enable.  rate R, the burst sync's; len_min <= len_max, 0 .. 255; len_add, 0 .. 16: bytes behind the length
+ *             byte that the length does not count, apart from the CRC field; skip >= 0: bytes behind the sync word that the CRC does
+ *             not cover (0: the length byte is covered, as in the CC1101); width = W, poly, init, xorout: unreflected, exactly as
+ *             tfrec_amd_enable_burst_crc takes them; skip < 1 + len_min + len_add (the shortest packet has a covered byte); the flags
+ *             TFREC_AMD_CRC_LSB and TFREC_AMD_CRC_INVERT, the frame check's; whiten: n_whiten bytes, 0 .. 274, NULL meaning none.
+ *             T(L) = 1 + L + len_add + W / 8, a packet's bytes; delta(i) = floor((768000 i + R) / (2 R)), the burst sync's;
+ *             delta(8 T(len_max)) <= 16383: at 38400 bit/s that admits len_max + len_add = 201 with a 16-bit CRC.
+ *   Inputs:   x, the burst sync's input track (the coded bitmap where tfrec_amd_enable_burst_code is on, else the track's; chosen
+ *             per submit), and m, the burst sync's match track, both along a chain: the carried history and this submit's run.
+ *   Candidate: every c with m[c] = 1.  Its byte j is assembled from x[c + delta(8 j + q + 1)] ^ invert, q = 0 .. 7, in received
+ *             order, in the flag's order (LSB: the first received bit is bit 0), and then XORed with whiten[j] where j < n_whiten.
+ *             L = byte 0.  A candidate with L outside [len_min, len_max] is dropped.  T = T(L); its END is k = c + delta(8 T).
+ *   Evaluated: a candidate is evaluated exactly once: by the run piece that holds sample k, and only if the chain holds everything
+ *             from c on (c + H >= 0 relative to the piece; H as below).  A candidate whose end lies behind the burst is never
+ *             evaluated.  It CHECKS if the CRC over the de-whitened bytes skip .. T - W / 8 - 1 equals the de-whitened field, the
+ *             last W / 8 bytes, big-endian: the frame check's CRC rule with N = T.
+ *   History:  the frame check's: H = 0 without TFREC_AMD_RUN_CONTINUES, else H = min(16383, H' + n') of the OPEN piece (H', n') that
+ *             ended the submit before.  Per stream the device carries the chain's last 16384 input bits, its last 16384 match bits
+ *             (2 x 512 words) and H, its own.  Match bits ahead of the chain's H available samples read 0.  A run that does not fit
+ *             max_samples, or an OPEN run beyond max_runs: bits 0, counts 0, first_at none, and H = 0 behind it.  A reset drops the
+ *             chain: the run behind it does not CONTINUE.  tfrec_amd_save_streams does not carry the history.
+ *   Bits:     v[k] = 1 iff some candidate that ends at k checks; packed exactly as the track's, at the entry's pool_offset.
+ *   Record:   the entry's first 24 bytes, bit_offset = its pool_offset, n_seen = the candidates evaluated in the piece, n_ok = those
+ *             of them that check, first_at = the smallest k at which one checks, or 0xffffffff where there is none, reserved = 0.
+ *   Merging:  the v tracks are concatenated, n_samples, n_seen and n_ok added; first_at is that of the first piece that has one,
+ *             offset by the samples ahead of that piece; the flags as for tfrec_amd_track.  Without overflow the merged record and
+ *             bits do not depend on how the stream was cut into submits.
+ *   Limits:   a sync's plateau is several samples wide, so a packet that checks is seen and counted at each of them: n_ok counts
+ *             samples, not packets.  No Manchester or 3-of-6 symbol codes, no reflected CRCs, no interleaved CRC blocks, no two-byte
+ *             lengths, not with TFREC_AMD_SYNC_BOTH.  Nothing of it has been measured on real recordings. */
+typedef struct {            /* 48 bytes */
+	uint32_t stream;        /* these five: copied from the table entry */
+	uint32_t flags;
+	int64_t  start_sample;
+	uint32_t n_samples;
+	int32_t  thresh;
+	uint64_t bit_offset;    /* the entry's pool_offset: v[k] is bit bit_offset + k of the bitmap */
+	uint32_t n_seen;        /* the candidates evaluated: L in range, the end inside the piece, the chain holds them */
+	uint32_t n_ok;          /* ... of which check */
+	uint32_t first_at;      /* the smallest k at which one checks; 0xffffffff: none */
+	uint32_t reserved;      /* 0 */
+} tfrec_amd_burst_packet;
+/* Turn the packet check on: after tfrec_amd_enable_burst_sync, before the first submit, once; before or after
+ * tfrec_amd_enable_burst_code and tfrec_amd_enable_burst_crc.  Device memory, counted in tfrec_amd_get_memory: per FIFO set max_runs *
+ * 48 bytes and ceil(max_samples / 32) words; per stream the carried 1024 words and H (4100 bytes); once, the tables, 3 x 276 words;
+ * no page-locked memory.  Errors: any setting outside the above, an unknown flag, a longest packet that reaches over 16383 samples,
+ * no burst sync, a rate that is not the sync's, a sync with TFREC_AMD_SYNC_BOTH, or a second call: TFREC_AMD_E_INVAL, and nothing is
+ * allocated; after the first submit or a poisoned context: TFREC_AMD_E_STATE; TFREC_AMD_E_NOMEM as elsewhere; a call that fails leaves
+ * the context exactly as it was.  A context on which it was never called holds and launches what it did.  Its three kernels run on
+ * the recorder's low-priority stream behind the sync's. */
+int tfrec_amd_enable_burst_packets(tfrec_amd_ctx *ctx, int32_t rate, int32_t len_min, int32_t len_max, int32_t len_add, int32_t skip,
+				   int32_t width, uint32_t poly, uint32_t init, uint32_t xorout, const uint8_t *whiten, int32_t n_whiten,
+				   uint32_t flags);
+/* out[i] = the record of entry i of the table tfrec_amd_read_captures returns for the same submit, words = the ok bitmap:
+ * tfrec_amd_read_burst_tracks' conventions, counts, prefixes on TFREC_AMD_E_OVERFLOW and errors throughout. */
+int tfrec_amd_read_burst_packets(tfrec_amd_ctx *ctx, tfrec_amd_burst_packet *out, size_t cap_runs, uint32_t *n_runs, uint32_t *words,
+				 size_t cap_words, uint64_t *n_words);
+
 /* Power spectrum of the input rows (tfrec_amd_enable_spectrum): where in a recording there is energy, and where the
  * short bursts are that an average hides -- before a receiver is placed.  It belongs to an input ROW of a submit, not to a stream: it
  * is taken on x, the int16 value every format maps a stored component to (tfrec_amd_create_format; -8192 <= x <= 8191), at the

@@ -20,6 +20,7 @@ from .crc import CRC_DTYPE  # tfrec_amd_burst_crc
 from .envelope import ENVELOPE_DTYPE  # tfrec_amd_envelope
 from .levels import LEVEL_DTYPE  # tfrec_amd_level
 from .occupancy import OCC_DTYPE  # tfrec_amd_occupancy
+from .packet import PACKET_DTYPE  # tfrec_amd_burst_packet
 from .sync import SYNC_DTYPE  # tfrec_amd_burst_sync
 from .track import TRACK_DTYPE  # tfrec_amd_track
 
@@ -124,6 +125,7 @@ EXPORTS = (
     "tfrec_amd_enable_burst_sync", "tfrec_amd_read_burst_syncs",
     "tfrec_amd_enable_burst_code", "tfrec_amd_read_burst_codes",
     "tfrec_amd_enable_burst_crc", "tfrec_amd_read_burst_crcs",
+    "tfrec_amd_enable_burst_packets", "tfrec_amd_read_burst_packets",
 )
 
 _libs = {}
@@ -246,6 +248,10 @@ def load_library(build: bool = True, experiments: bool = False, short_segments: 
                                              C.c_uint32]
     L.tfrec_amd_read_burst_crcs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
                                             C.POINTER(C.c_uint64)]
+    L.tfrec_amd_enable_burst_packets.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
+                                                 C.c_uint32, C.c_uint32, C.c_char_p, C.c_int32, C.c_uint32]
+    L.tfrec_amd_read_burst_packets.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
+                                               C.POINTER(C.c_uint64)]
     L.tfrec_amd_stream_state_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
     L.tfrec_amd_save_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
     L.tfrec_amd_load_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
@@ -840,6 +846,27 @@ class Receiver:
         crc.bits_of(rec, words) is a record's check track.  Overflow as for read_burst_tracks.  crc_total holds the submit's true
         run count."""
         return self._read_run_records(self.L.tfrec_amd_read_burst_crcs, CRC_DTYPE, "crc_total", allow_overflow, words=True)
+
+    def enable_burst_packets(self, rate: int, len_max: int, width: int, poly: int, init: int = 0, xorout: int = 0, len_min: int = 0,
+                             len_add: int = 0, skip: int = 0, whiten: bytes = b"", lsb: bool = False, invert: bool = False):
+        """Turn the packet check on (tfrec_amd_enable_burst_packets; after enable_burst_sync, before the first submit): every match
+        of the sync is a candidate packet -- a length byte, that many bytes, len_add more and a CRC, read at symbol centres at
+        `rate` bit/s from the sync's input track and XORed with `whiten` -- and a bit per captured sample says whether one that
+        checks ends there (packet.Settings).  read_burst_packets returns the records and the ok bitmap."""
+        args = (rate, len_min, len_max, len_add, skip, width)
+        if not all(-2 ** 31 <= int(a) < 2 ** 31 for a in args) or not all(0 <= int(a) < 2 ** 32 for a in (poly, init, xorout)):
+            raise TfrecAmdError(E_INVAL, "a setting outside its type")  # (refused before ctypes could wrap a value into range)
+        whiten = bytes(whiten)
+        _check(self.L, self.L.tfrec_amd_enable_burst_packets(self.h, int(rate), int(len_min), int(len_max), int(len_add), int(skip), int(width),
+                                                             int(poly), int(init), int(xorout), whiten or None, len(whiten),
+                                                             (1 if lsb else 0) | (2 if invert else 0)))
+
+    def read_burst_packets(self, allow_overflow: bool = False):
+        """The packet check of the OLDEST undrained submit (tfrec_amd_read_burst_packets; call it before the drain that pops that
+        submit) -> (a PACKET_DTYPE array, one record per entry of that submit's run table; the ok bitmap's uint32 words):
+        packet.bits_of(rec, words) is a record's ok track.  Overflow as for read_burst_tracks.  packet_total holds the submit's
+        true run count."""
+        return self._read_run_records(self.L.tfrec_amd_read_burst_packets, PACKET_DTYPE, "packet_total", allow_overflow, words=True)
 
     def enable_runs_input(self, max_runs: int, max_samples: int):
         """Turn sparse submits on (tfrec_amd_enable_runs_input; decimated receivers, before the first submit): a submit_runs may

@@ -1,5 +1,5 @@
 // tfrec_amd/csrc/capi_bursts.h -- the entry points of the five burst stages on the recorder's table: the meter, the
-// envelope (6r), the clock (6s), the track (6t, with its centres; 6v, its amplitude mode, with its levels; 6w, its auto-centre mode, with its centre records; 6x, its phase mode; 6y, its line code; 6z, its frame check) and the sync (6u).  What they share comes first -- the enables'
+// envelope (6r), the clock (6s), the track (6t, with its centres; 6v, its amplitude mode, with its levels; 6w, its auto-centre mode, with its centre records; 6x, its phase mode; 6y, its line code; 6z, its frame check; 6za, its packet check) and the sync (6u).  What they share comes first -- the enables'
 // preflight, the rebase of start_sample, the record-only reader and the record-plus-bitmap reader --, then each
 // stage's enable and read, which add their own argument checks and buffers.  Included by capi.hip, which lists what is where.
 #pragma once
@@ -15,6 +15,7 @@ constexpr StageNames kTrackNames = { "burst track", "track", "tfrec_amd_enable_b
 constexpr StageNames kCentreNames = { "auto-centre track", "centre", "tfrec_amd_enable_burst_track_auto" };
 constexpr StageNames kCodeNames = { "line code", "code", "tfrec_amd_enable_burst_code" };
 constexpr StageNames kCrcNames = { "frame check", "crc", "tfrec_amd_enable_burst_crc" };
+constexpr StageNames kPacketNames = { "packet check", "packet", "tfrec_amd_enable_burst_packets" };
 constexpr StageNames kSyncNames = { "burst sync", "sync", "tfrec_amd_enable_burst_sync" };
 
 // What every enable checks behind its own arguments, in this order: what the stage works on (`needs`, switched on by
@@ -460,4 +461,53 @@ int tfrec_amd_read_burst_crcs(tfrec_amd_ctx *c, tfrec_amd_burst_crc *out, size_t
 			      uint64_t *n_words)
 {
 	return c ? read_run_bitmaps(c, c->crc, c->crc.d_words, kCrcNames, out, cap_runs, n_runs, words, cap_words, n_words) : TFREC_AMD_E_INVAL;
+}
+
+// ---- the packet check
+int tfrec_amd_enable_burst_packets(tfrec_amd_ctx *c, int32_t rate, int32_t len_min, int32_t len_max, int32_t len_add, int32_t skip, int32_t width,
+				   uint32_t poly, uint32_t init, uint32_t xorout, const uint8_t *whiten, int32_t n_whiten, uint32_t flags)
+{
+	if (!c)
+		return TFREC_AMD_E_INVAL;
+	if (!whiten)
+		n_whiten = 0;
+	const tfrec_packet::Settings st = { rate, len_min, len_max, len_add, skip, width, poly, init, xorout, flags, n_whiten };
+	if (const char *why = tfrec_packet::refusal(st)) {
+		snprintf(g_err, sizeof(g_err), "%s", why);
+		return TFREC_AMD_E_INVAL;
+	}
+	const char *limit = nullptr;
+	if (c->syn.on && c->syn.rate != rate)
+		limit = "the burst sync's rate";
+	else if (c->syn.on && (c->syn.flags & TFREC_AMD_SYNC_BOTH))
+		limit = "a burst sync that matches the word alone, not its complement too";
+	TRY(enable_preflight(c, kPacketNames, c->syn.on, "the burst sync's matches", "tfrec_amd_enable_burst_sync", c->pkt.on, limit));
+	EnableGuard<BurstPacket> guard(c, c->pkt);
+	BurstPacket &o = c->pkt;
+	const size_t n = (size_t)c->cfg.n_streams;
+	static_assert(tfrec_packet::kMaxBytes == kPacketMaxBytes, "packet_kernel indexes the table by packet_table.h's size");
+	std::vector<uint32_t> table;
+	tfrec_packet::build(st, table);
+	table.resize(3 * (size_t)kPacketMaxBytes, 0u);  // (bytes behind the sequence are not whitened)
+	for (int i = 0; i < n_whiten; i++)
+		table[2 * (size_t)kPacketMaxBytes + i] = whiten[i];
+	for (int k = 0; k < kSets; k++) {
+		TRY(own_device(c, o.d_recs[k], (size_t)c->cap.max_runs * sizeof(tfrec_amd_burst_packet)));
+		TRY(own_device(c, o.d_words[k], c->trk.n_words * sizeof(uint32_t)));
+	}
+	TRY(own_device(c, o.d_carry, n * kPacketCarryWords * sizeof(uint32_t)));
+	TRY(own_device(c, o.d_hist, n * sizeof(uint32_t)));
+	TRY(own_device(c, o.d_table, table.size() * sizeof(uint32_t)));
+	HIPCHK(hipMemset(o.d_carry, 0, n * kPacketCarryWords * sizeof(uint32_t)));  // (never used before a submit has written them: no first submit CONTINUES)
+	HIPCHK(hipMemset(o.d_hist, 0, n * sizeof(uint32_t)));
+	HIPCHK(hipMemcpy(o.d_table, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+	o.set = { rate, len_min, len_max, len_add, skip, width, poly, xorout, flags };
+	o.on = guard.ok = true;
+	return TFREC_AMD_OK;
+}
+
+int tfrec_amd_read_burst_packets(tfrec_amd_ctx *c, tfrec_amd_burst_packet *out, size_t cap_runs, uint32_t *n_runs, uint32_t *words,
+				 size_t cap_words, uint64_t *n_words)
+{
+	return c ? read_run_bitmaps(c, c->pkt, c->pkt.d_words, kPacketNames, out, cap_runs, n_runs, words, cap_words, n_words) : TFREC_AMD_E_INVAL;
 }

@@ -142,6 +142,14 @@ struct BurstCrc : RunRecords<tfrec_amd_burst_crc> {
 	uint32_t *d_carry = nullptr, *d_hist = nullptr;
 	uint2 *d_terms = nullptr;
 };
+// tfrec_amd_enable_burst_packets: the settings as packet_kernel takes them; per set the records (RunRecords) and
+// the ok bitmap (the track's size); per stream the carried 2 x 512 words of input and match bits and H (packet_carry_kernel); once,
+// the table (x8, i8 and the whitening bytes: 3 x 276 words)
+struct BurstPacket : RunRecords<tfrec_amd_burst_packet> {
+	PacketSettings set = {};
+	uint32_t *d_words[kSets] = {};
+	uint32_t *d_carry = nullptr, *d_hist = nullptr, *d_table = nullptr;
+};
 // tfrec_amd_create_decimated (PreStage::kChannel): the carried last pair of every stream
 struct DecIn {
 	uint32_t *d_last = nullptr;
@@ -348,6 +356,7 @@ struct tfrec_amd_ctx {
 	BurstSync syn;
 	BurstCode code;
 	BurstCrc crc;
+	BurstPacket pkt;
 	DecIn decin;
 	RunsIn runs_in;
 	SpectrumOut spec;

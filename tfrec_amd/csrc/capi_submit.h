@@ -304,6 +304,14 @@ static CrcBufs crc_bufs(const tfrec_amd_ctx *c, int set)
 		 .hist = o.d_hist, .terms = o.d_terms, .n_terms = o.n_terms, .reach = o.reach, .width = o.width, .r0 = o.r0 };
 }
 
+// The packet check's buffers of a set: its input is the bitmap the sync reads, and the sync's match bitmap
+static PacketBufs packet_bufs(const tfrec_amd_ctx *c, int set)
+{
+	const BurstPacket &o = c->pkt;
+	return { .recs = o.d_recs[set], .words = o.d_words[set], .track = c->code.on ? c->code.d_words[set] : c->trk.d_words[set],
+		 .match = c->syn.d_words[set], .carry = o.d_carry, .hist = o.d_hist, .table = o.d_table, .set = o.set };
+}
+
 // The burst sync's buffers of a set: with the line code on, the track it reads is the coded one
 static SyncBufs sync_bufs(const tfrec_amd_ctx *c, int set)
 {
@@ -434,6 +442,8 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 			HIPCHK(launch_burst_sync(c->cap.lane.st, out, b, sync_bufs(c, set)));
 		if (c->crc.on)  // the frame check: behind the code's (or the track's) carry kernel, on the table, the working set, the sync's input bitmap and its own carry
 			HIPCHK(launch_burst_crc(c->cap.lane.st, out, b, crc_bufs(c, set)));
+		if (c->pkt.on)  // the packet check: behind the sync's carry kernel, on the table, the working set, the sync's input and match bitmaps and its own carry
+			HIPCHK(launch_burst_packet(c->cap.lane.st, out, b, packet_bufs(c, set)));
 		HIPCHK(lane_written(c->cap.lane, set));
 	}
 	if (c->cfg.flags & TFREC_AMD_F_SERIAL_CHAINS) {

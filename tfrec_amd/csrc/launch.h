@@ -85,6 +85,23 @@ struct CrcBufs {
 	int n_terms, reach, width;
 	uint32_t r0;
 };
+// The packet check's settings as packet_kernel takes them (packet.h), and its buffers: the set's records and ok bitmap, the input
+// bitmap and the sync's match bitmap of the same set, per stream the carried 2 x 512 words (input bits, then match bits) and H, and
+// the table (packet_table.h: x8[276], i8[276], then the whitening bytes, one a word)
+constexpr int kPacketMaxBytes = 276;      // the largest T: 1 + 255 + 16 + 4 (packet_table.h: kMaxBytes)
+constexpr int kPacketCarryWords = 1024;   // per stream: the 512 words of input bits, then the 512 of match bits
+struct PacketSettings {
+	int rate, len_min, len_max, len_add, skip, width;
+	uint32_t poly, xorout, flags;
+};
+struct PacketBufs {
+	tfrec_amd_burst_packet *recs;
+	uint32_t *words;
+	const uint32_t *track, *match;
+	uint32_t *carry, *hist;
+	const uint32_t *table;
+	PacketSettings set;
+};
 // The spectrum of rows 0 .. n_rows - 1 of a submit of n_in complex samples per row, and the set's records: [rows][max_records][n_bins]
 // sums and peaks, [rows][max_records] frame counts.  launch_occupancy reads what launch_spectrum has just queued on the stream.
 struct SpectrumBufs {
@@ -133,6 +150,7 @@ hipError_t launch_burst_track_phase(hipStream_t st, const FrontOut &o, const Cap
 hipError_t launch_burst_sync(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const SyncBufs &k);
 hipError_t launch_burst_code(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const CodeBufs &k);
 hipError_t launch_burst_crc(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const CrcBufs &k);
+hipError_t launch_burst_packet(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const PacketBufs &k);
 hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, const SpectrumBufs &b);
 hipError_t launch_occupancy(hipStream_t st, const SpectrumBufs &b, uint32_t ratio, uint32_t rel, tfrec_amd_occupancy *recs, uint32_t *bits);
 // ... and the parity probes

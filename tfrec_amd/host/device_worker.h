@@ -307,6 +307,12 @@ inline int device_worker::open_context()
 		call = "tfrec_amd_enable_burst_crc";
 		r = tfrec_amd_enable_burst_crc(ctx, s.rate, s.n_bytes, s.skip, s.width, s.poly, s.init, s.xorout, s.flags);
 	}
+	if (!r && job.packeting()) {  // -N: the packet check behind the sync, at -G's rate, with -V's CRC and -Y's byte order
+		const tfrec_packet::Settings s = job.packet_settings();
+		call = "tfrec_amd_enable_burst_packets";
+		r = tfrec_amd_enable_burst_packets(ctx, s.rate, s.len_min, s.len_max, s.len_add, s.skip, s.width, s.poly, s.init, s.xorout,
+						   job.pkt_whiten.empty() ? NULL : job.pkt_whiten.data(), s.n_whiten, s.flags);
+	}
 	if (!r && job.replay) {  // -R, sized so that every submit fits: its files' runs (a cut adds one per stream), every sample at most
 		uint64_t runs = 0, pairs = 0;
 		for (size_t f = s0; f < s1; f++) {
@@ -610,7 +616,8 @@ inline int device_worker::read_run_bitmaps(int (*reader)(tfrec_amd_ctx *, R *, s
 // the centre record of its entry (job.h: centre_take).  -U: the coded records of the same entries too, each a track piece of its
 // own with the coded bits (cut alike): in b.codes beside b.tracks, or with -Y as the sync piece's track piece, b.tracks keeping the
 // raw pieces for the bits line.  -V (with -Y): the check records of the same entries, each with its check track (job.h: crc_take),
-// in b.crcs beside b.syncs
+// in b.crcs beside b.syncs.  -N (with -Y): the packet records of the same entries, each with its ok track (job.h: packet_take), in
+// b.pkts beside b.syncs
 inline int device_worker::read_tracks(size_t k, batch_result &b)
 {
 	std::vector<tfrec_amd_track> recs;
@@ -665,6 +672,16 @@ inline int device_worker::read_tracks(size_t k, batch_result &b)
 			return TFREC_AMD_E_STATE;
 		}
 	}
+	std::vector<tfrec_amd_burst_packet> precs;  // -N: the packet records and words of the same entries
+	std::vector<uint32_t> pwords;
+	if (job.packeting()) {
+		if ((r = read_run_bitmaps(tfrec_amd_read_burst_packets, precs, pwords)))
+			return r;
+		if (precs.size() != recs.size()) {
+			fprintf(stderr, "tfrec_amd: device %d batch %zu: %zu packet records beside %zu track records\n", device, k, precs.size(), recs.size());
+			return TFREC_AMD_E_STATE;
+		}
+	}
 	for (size_t q = 0; q < recs.size(); q++) {
 		tfrec_amd_track x = recs[q];
 		if (!cut_at_file_end(x, plan[k].file, file_blocks, true))
@@ -676,6 +693,8 @@ inline int device_worker::read_tracks(size_t k, batch_result &b)
 			centre_take(t, crecs[q]);
 		if (job.checking())
 			b.crcs.push_back(crc_take(vrecs[q], vwords.data(), t));
+		if (job.packeting())
+			b.pkts.push_back(packet_take(precs[q], pwords.data(), t));
 		if (job.coding()) {  // the coded piece: the cut entry with the coded record's n_ones and bits; the sync's frames are read from it
 			x.n_ones = urecs[q].n_ones;
 			track_piece u = track_take(x, uwords.data(), n);

@@ -468,6 +468,9 @@ int gpu_engine::run()
 	chain_merger<crc_piece> crcs;
 	std::vector<crc_piece> checked;
 	crcs.begin(n);
+	chain_merger<packet_piece> pkts;
+	std::vector<packet_piece> packed;
+	pkts.begin(n);
 	const uint64_t crc_reach = job.checking() ? (uint64_t)tfrec_crc::reach(job.crc_settings()) : 0;
 	if (job.spectrum)
 		spec.begin(job);
@@ -513,6 +516,9 @@ int gpu_engine::run()
 			checked.clear();
 			if (job.checking())  // -V (with -Y): the check pieces of the sync's entries -- the same flags, so the chains end together, in one order
 				crcs.take(b.crcs, workers[d].plan[k], file_blocks, checked);
+			packed.clear();
+			if (job.packeting())  // -N (with -Y): the packet pieces of the sync's entries, likewise
+				pkts.take(b.pkts, workers[d].plan[k], file_blocks, packed);
 			if (job.coding()) {  // -G -U: -G's lines of each burst, its code line, and with -Y a line per frame found on the coded track
 				said.clear();
 				tracks.take(b.tracks, workers[d].plan[k], file_blocks, said);
@@ -524,6 +530,11 @@ int gpu_engine::run()
 					codes.take(b.codes, workers[d].plan[k], file_blocks, coded);
 				if (job.checking() && checked.size() != framed.size()) {
 					fprintf(stderr, "tfrec_amd: batch %zu: %zu check chains ended beside %zu sync chains\n", k, checked.size(), framed.size());
+					rc = TFREC_AMD_E_STATE;
+					break;
+				}
+				if (job.packeting() && packed.size() != framed.size()) {
+					fprintf(stderr, "tfrec_amd: batch %zu: %zu packet chains ended beside %zu sync chains\n", k, packed.size(), framed.size());
 					rc = TFREC_AMD_E_STATE;
 					break;
 				}
@@ -540,12 +551,22 @@ int gpu_engine::run()
 							printf("%s\n", frame_line(files[x.stream], framed[i], f, job, checked, i, crc_reach).c_str());
 					if (job.checking())  // -V: the burst's crc line behind its frame lines
 						printf("%s\n", crc_line(files[x.stream], checked[i], crc_reach).c_str());
+					if (job.packeting()) {  // -N: a packet line per plateau behind the burst's frame lines, then its pkts line
+						for (const sync_frame &f : sync_frames(framed[i], job))
+							printf("%s\n", packet_line(files[x.stream], framed[i], f, packed[i], job).c_str());
+						printf("%s\n", pkts_line(files[x.stream], packed[i]).c_str());
+					}
 				}
 			} else if (job.syncing()) {  // -G -Y: -G's line of each burst, and behind it a line per frame found in it
 				framed.clear();
 				syncs.take(b.syncs, workers[d].plan[k], file_blocks, framed);
 				if (job.checking() && checked.size() != framed.size()) {
 					fprintf(stderr, "tfrec_amd: batch %zu: %zu check chains ended beside %zu sync chains\n", k, checked.size(), framed.size());
+					rc = TFREC_AMD_E_STATE;
+					break;
+				}
+				if (job.packeting() && packed.size() != framed.size()) {
+					fprintf(stderr, "tfrec_amd: batch %zu: %zu packet chains ended beside %zu sync chains\n", k, packed.size(), framed.size());
 					rc = TFREC_AMD_E_STATE;
 					break;
 				}
@@ -560,6 +581,11 @@ int gpu_engine::run()
 						printf("%s\n", frame_line(files[x.stream], x, f, job, checked, i, crc_reach).c_str());
 					if (job.checking())  // -V: the burst's crc line behind its frame lines
 						printf("%s\n", crc_line(files[x.stream], checked[i], crc_reach).c_str());
+					if (job.packeting()) {  // -N: a packet line per plateau behind the burst's frame lines, then its pkts line
+						for (const sync_frame &f : sync_frames(x, job))
+							printf("%s\n", packet_line(files[x.stream], x, f, packed[i], job).c_str());
+						printf("%s\n", pkts_line(files[x.stream], packed[i]).c_str());
+					}
 				}
 			} else if (job.tracking()) {  // -G: likewise, behind -C's lines of the batch
 				said.clear();

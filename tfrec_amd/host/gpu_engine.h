@@ -283,6 +283,20 @@ public:
 		job.crc_skip = skip;
 		job.crc_invert = invert;
 	}
+	// -N (with -G, -Y and -V): the packet check (tfrec_amd_enable_burst_packets) behind the sync, at -G's rate, with -V's
+	// CRC and -Y's byte order; with it -V configures this stage and the frame check stays off.  run() merges the packet pieces' chains
+	// beside the sync's; behind a burst's frame lines comes, per plateau of the sync,
+	//   packet <file> <start_sample> <sync_sample> <len|-> <ok|bad|-> <hex|->
+	// (job.h: packet_line) and then
+	//   pkts <file> <start_sample> <n_samples> <n_seen> <n_ok> <sample|->
+	// (job.h: pkts_line).  Nothing of it has been measured on real recordings.
+	void set_packets(int len_max, int len_min, int add, const std::vector<uint8_t> &whiten)
+	{
+		job.pkt_len_max = len_max;
+		job.pkt_len_min = len_min;
+		job.pkt_add = add;
+		job.pkt_whiten = whiten;
+	}
 	// -k: keep.  A file is processed in whole pieces only and nothing is padded; before the first batch behind a
 	// file's last one is submitted -- and at the end of the job -- its stream is saved (tfrec_amd_save_streams) to
 	// <prefix>.<file index>.state, and at the end of a run without an error the bytes that did not fill a piece are written to

@@ -17,6 +17,7 @@
 
 #include "../../include/tfrec_amd.h"
 #include "../csrc/crc_table.h"  // the frame check's settings, as the enable call checks them: plain C++
+#include "../csrc/packet_table.h"  // the packet check's, likewise
 
 // -T, -t, -W and the tune of one dump file (tfrec_gpu -p; tune: -f minus -c, in Hz, tfrec_amd_tune_streams)
 struct file_settings {
@@ -116,6 +117,9 @@ struct job_settings {
 	uint32_t crc_poly = 0, crc_init = 0, crc_xorout = 0;  // ...
 	int crc_skip = 0;              // ... the bytes behind the sync word that the CRC does not cover
 	bool crc_invert = false;       // ... and its INVERT
+	int pkt_len_max = -1;          // set_packets (-1: none): -N, the packet check's largest length byte; its CRC is -V's, its byte order sync_lsb, its rate -G's
+	int pkt_len_min = 0, pkt_add = 0;  // ... the smallest, and the bytes behind the length byte that it does not count
+	std::vector<uint8_t> pkt_whiten;   // ... the whitening sequence (empty: none)
 	const std::vector<replay_file> *replay = NULL;  // set_replay (NULL: the files are dumps)
 	std::string keep_prefix;       // set_keep ("": none)
 	std::string cont_prefix;       // set_continue ("": none)
@@ -131,7 +135,15 @@ struct job_settings {
 	bool tracking() const { return track_rate != 0; }  // -G (never with -s or -A)
 	bool syncing() const { return sync_bits != 0; }  // -Y (only with -G)
 	bool coding() const { return code_taps != 0; }  // -U (only with -G)
-	bool checking() const { return crc_width != 0; }  // -V (only with -Y)
+	bool packeting() const { return pkt_len_max >= 0; }  // -N (only with -Y and -V)
+	bool checking() const { return crc_width != 0 && !packeting(); }  // -V (only with -Y); with -N it configures the packet check and the frame check stays off
+	tfrec_packet::Settings packet_settings() const  // tfrec_amd_enable_burst_packets' arguments
+	{
+		const tfrec_packet::Settings s = { (int32_t)track_rate, (int32_t)pkt_len_min, (int32_t)pkt_len_max, (int32_t)pkt_add, (int32_t)crc_skip, (int32_t)crc_width,
+						   crc_poly, crc_init, crc_xorout, (sync_lsb ? TFREC_AMD_CRC_LSB : 0u) | (crc_invert ? TFREC_AMD_CRC_INVERT : 0u),
+						   (int32_t)pkt_whiten.size() };
+		return s;
+	}
 	tfrec_crc::Settings crc_settings() const  // tfrec_amd_enable_burst_crc's arguments
 	{
 		const tfrec_crc::Settings s = { (int32_t)track_rate, (int32_t)sync_bytes, (int32_t)crc_skip, (int32_t)crc_width, crc_poly, crc_init, crc_xorout,
@@ -439,11 +451,19 @@ struct crc_piece : tfrec_amd_burst_crc {
 	bool bit(uint64_t k) const { return (ok[k >> 5] >> (k & 31)) & 1u; }
 };
 
+// -N: a packet record with its ok track (packed as a track_piece's bits)
+struct packet_piece : tfrec_amd_burst_packet {
+	std::vector<uint32_t> ok;
+	uint64_t kept() const { return std::min<uint64_t>(n_samples, kTrackKeep); }
+	bool bit(uint64_t k) const { return (ok[k >> 5] >> (k & 31)) & 1u; }
+};
+
 struct batch_result {
 	std::vector<track_piece> tracks;
 	std::vector<sync_piece> syncs;  // (-Y: in place of tracks; -U -Y: beside them, each with the CODED piece of its entry for its track piece)
 	std::vector<track_piece> codes;  // (-U without -Y: the coded pieces of the entries in tracks)
 	std::vector<crc_piece> crcs;  // (-V: the check pieces of the entries in syncs)
+	std::vector<packet_piece> pkts;  // (-N: the packet pieces of the entries in syncs)
 	std::vector<tfrec_amd_burst> bursts;
 	std::vector<tfrec_amd_envelope> envelopes;
 	std::vector<tfrec_amd_clock> clocks;
@@ -1103,7 +1123,126 @@ inline std::string crc_line(const std::string &file, const crc_piece &c, uint64_
 	       (c.first_at == 0xffffffffu ? std::string("-") : std::to_string((long long)c.start_sample + (long long)c.first_at - (long long)D));
 }
 
+// ---- -N: the packet check (include/tfrec_amd.h: "Packet check", whose text is normative; tfrec_amd/packet.py restates merge, read and the
+// lines; ../csrc/packet_table.h holds the settings' rules)
+
+// -N's argument: len_max[,len_min[,add[,pn9|<hex>]]] -- decimal numbers, then the whitening sequence: pn9 (the CC1101's, 274 bytes)
+// or an even number of hex digits -> the fields (false: bad).  Whether the settings hold together is tfrec_packet::refusal's to say.
+inline bool packet_parse(const char *arg, int &len_max, int &len_min, int &add, std::vector<uint8_t> &whiten)
+{
+	std::vector<std::string> part(1);
+	for (const char *q = arg; *q; q++) {
+		if (*q == ',')
+			part.push_back("");
+		else
+			part.back() += *q;
+	}
+	if (part.size() > 4)
+		return false;
+	for (size_t i = 0; i < part.size() && i < 3; i++)
+		if (part[i].empty() || part[i].size() > 3 || part[i].find_first_not_of("0123456789") != std::string::npos)
+			return false;
+	len_max = atoi(part[0].c_str());
+	len_min = part.size() > 1 ? atoi(part[1].c_str()) : 0;
+	add = part.size() > 2 ? atoi(part[2].c_str()) : 0;
+	whiten.clear();
+	if (part.size() > 3) {
+		const std::string &w = part[3];
+		if (w == "pn9") {  // a 9-bit register seeded 0x1ff; a byte is its low 8 bits, then eight steps of new = b0 ^ b5, shift right, new into bit 8
+			uint32_t r = 0x1ffu;
+			for (int i = 0; i < tfrec_packet::kMaxWhiten; i++) {
+				whiten.push_back((uint8_t)(r & 0xffu));
+				for (int q = 0; q < 8; q++)
+					r = (r >> 1) | (((r ^ (r >> 5)) & 1u) << 8);
+			}
+		} else {
+			if (w.empty() || w.size() % 2 || w.size() > 2 * (size_t)tfrec_packet::kMaxWhiten || w.find_first_not_of("0123456789abcdefABCDEF") != std::string::npos)
+				return false;
+			for (size_t i = 0; i < w.size(); i += 2)
+				whiten.push_back((uint8_t)strtoul(w.substr(i, 2).c_str(), NULL, 16));
+		}
+	}
+	return true;
+}
+
+// a device record, the submit's ok bitmap and the entry's track piece -> the piece, as many samples of it as the track piece has:
+// n_ok and first_at counted again on what is kept of a piece that the file's end cuts (n_seen stays the device's)
+inline packet_piece packet_take(const tfrec_amd_burst_packet &r, const uint32_t *words, const track_piece &t)
+{
+	packet_piece p;
+	static_cast<tfrec_amd_burst_packet &>(p) = r;
+	p.stream = t.stream;
+	p.flags = t.flags;
+	const bool cut = t.n_samples < r.n_samples;
+	p.n_samples = t.n_samples;
+	track_append(p.ok, 0, words, r.bit_offset, p.n_samples);
+	if (cut) {
+		p.n_ok = 0;
+		p.first_at = 0xffffffffu;
+		for (uint64_t k = 0; k < p.kept(); k++) {
+			if (!p.bit(k))
+				continue;
+			if (!p.n_ok++)
+				p.first_at = (uint32_t)k;
+		}
+	}
+	return p;
+}
+
+// piece p, which CONTINUES the chain c, merged into it (the header's Merging)
+inline void packet_add(packet_piece &c, const packet_piece &p)
+{
+	if (!p.ok.empty())
+		track_append(c.ok, c.kept(), p.ok.data(), 0, p.kept());
+	if (c.first_at == 0xffffffffu && p.first_at != 0xffffffffu)
+		c.first_at = c.n_samples + p.first_at;
+	c.n_samples += p.n_samples;
+	c.n_seen += p.n_seen;
+	c.n_ok += p.n_ok;
+	c.flags = (c.flags & TFREC_AMD_RUN_CONTINUES) | (p.flags & TFREC_AMD_RUN_OPEN);
+}
+
+// packet <file> <start_sample> <sync_sample> <len|-> <ok|bad|-> <hex|->: the candidate at a plateau's sample f.c, read host-side from
+// the chain's merged track (the first min(last_over + 1, 2^20) samples, as the frames are): its de-whitened length byte, its
+// bytes, and the ok track's bit at its end; "-" where the length byte or the end lies behind that, or the length is out of range
+inline std::string packet_line(const std::string &file, const sync_piece &c, const sync_frame &f, const packet_piece &v, const job_settings &job)
+{
+	const tfrec_packet::Settings st = job.packet_settings();
+	const uint64_t n = c.trk.last_over < 0 ? 0 : std::min<uint64_t>((uint64_t)c.trk.last_over + 1, c.kept());
+	const std::string head = "packet " + file + " " + std::to_string((long long)c.start_sample) + " " + std::to_string((long long)c.start_sample + (long long)f.c) + " ";
+	auto byte = [&](int j) {
+		int b = 0;
+		for (int q = 0; q < 8; q++) {
+			const bool t = c.trk.bit(f.c + sync_delta((uint64_t)(8 * j + q + 1), job.track_rate)) != job.crc_invert;
+			b |= (int)t << (job.sync_lsb ? q : 7 - q);
+		}
+		return b ^ ((size_t)j < job.pkt_whiten.size() ? job.pkt_whiten[(size_t)j] : 0);
+	};
+	if (f.c + sync_delta(8, job.track_rate) >= n)
+		return head + "- - -";
+	const int L = byte(0), T = tfrec_packet::total(st, L);
+	const uint64_t k = f.c + sync_delta((uint64_t)(8 * T), job.track_rate);
+	if (L < st.len_min || L > st.len_max || k >= n)
+		return head + std::to_string(L) + " - -";
+	std::string hex;
+	for (int j = 0; j < T; j++) {
+		const int b = byte(j);
+		hex += "0123456789abcdef"[b >> 4];
+		hex += "0123456789abcdef"[b & 15];
+	}
+	return head + std::to_string(L) + " " + (v.bit(k) ? "ok" : "bad") + " " + hex;
+}
+
+// pkts <file> <start_sample> <n_samples> <n_seen> <n_ok> <sample|->: the last field is start_sample + first_at, where the first
+// packet that checks ends
+inline std::string pkts_line(const std::string &file, const packet_piece &c)
+{
+	return "pkts " + file + " " + std::to_string((long long)c.start_sample) + " " + std::to_string(c.n_samples) + " " + std::to_string(c.n_seen) + " " +
+	       std::to_string(c.n_ok) + " " + (c.first_at == 0xffffffffu ? std::string("-") : std::to_string((long long)c.start_sample + (long long)c.first_at));
+}
+
 inline void chain_add(tfrec_amd_burst &c, const tfrec_amd_burst &p) { burst_add(c, p); }
+inline void chain_add(packet_piece &c, const packet_piece &p) { packet_add(c, p); }
 inline void chain_add(crc_piece &c, const crc_piece &p) { crc_add(c, p); }
 inline void chain_add(sync_piece &c, const sync_piece &p) { sync_add(c, p); }
 inline void chain_add(track_piece &c, const track_piece &p) { track_add(c, p); }

@@ -162,6 +162,18 @@
 // the samples of the burst at which a frame that checks ends, and where the sync word of the first would have ended: a frame finder
 // for bursts whose sync word nobody knows.  With init 0 and xorout 0 a constant stretch checks too.  Not with -Y's both; a frame that
 // reaches over 16383 samples at the rate is refused.  Nothing of it has been measured on real recordings.
+// -N len_max[,len_min[,add[,pn9|<hex>]]] (not in the reference; with -G, -Y and -V): the packet check (tfrec_amd_enable_burst_packets,
+// DESIGN.md 6za), for transmitters whose packets carry a length byte behind the sync word (CC1101, RFM69, SX1231, Si446x).  Every match
+// of -Y's word is a candidate: its first byte, de-whitened, is the length L within len_min .. len_max, the packet has 1 + L + add +
+// width / 8 bytes, and the CRC is -V's -- width, poly, init, xorout, skip, inv --, which with -N configures this stage: the fixed-length
+// frame check stays off and the frame lines carry no verdict.  -Y's fifth field gives the byte order.  pn9 is the CC1101's whitening
+// sequence; hex bytes give another.  Behind each burst's frame lines stdout gets, per plateau of the sync,
+//   packet <file> <start_sample> <sync_sample> <len|-> <ok|bad|-> <hex|->
+// the de-whitened bytes read from the merged track at the plateau's middle, as the frames are, and then
+//   pkts <file> <start_sample> <n_samples> <n_seen> <n_ok> <sample|->
+// the candidates evaluated, those that check (a plateau is several samples wide: samples, not packets) and where the first one ends.
+// Works where -G works, -R included; the longest packet may reach 16383 samples at the rate.  Nothing of it has been measured on
+// real recordings.
 // -P bins[,frames_per_record] (not in the reference): the power spectrum of ONE recording, beside its decoding: an
 // exact integer DFT of bins = 64, 128, 256, 512 or 1024 bins over the raw input -- at 1.536 MS/s, or given with -x, or with -r / -F --,
 // per record of frames_per_record frames (1 .. 16384; default: the frames one block's input holds, at least 1) the sum and the peak
@@ -348,6 +360,8 @@ struct cli {
 	int crc_width = 0, crc_skip = 0;  // -V (width 0: not given)
 	uint32_t crc_poly = 0, crc_init = 0, crc_xorout = 0;
 	bool crc_invert = false;
+	int pkt_len_max = -1, pkt_len_min = 0, pkt_add = 0;  // -N (len_max -1: not given)
+	std::vector<uint8_t> pkt_whiten;
 	const char *keep_prefix = NULL, *cont_prefix = NULL;  // -k, -K
 	bool have_center = false, have_format = false;  // -c, -F given (-R refuses them)
 	std::vector<replay_file> captures;  // -R: one per file index of <prefix>.idx
@@ -381,7 +395,7 @@ struct cli {
 
 static void usage()
 {
-	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-G rate[,centre_hz]] [-G rate,auto] [-G rate,psk[,lag]] [-O level] [-Y hex[,errors[,bytes[,both]]]] [-Y hex,errors,bytes,both,1] [-U g3ruh|nrzi|nrzs|hextaps[,inv]] [-V width,poly[,init[,xorout[,skip[,inv]]]]] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
+	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-G rate[,centre_hz]] [-G rate,auto] [-G rate,psk[,lag]] [-O level] [-Y hex[,errors[,bytes[,both]]]] [-Y hex,errors,bytes,both,1] [-U g3ruh|nrzi|nrzs|hextaps[,inv]] [-V width,poly[,init[,xorout[,skip[,inv]]]]] [-N len_max[,len_min[,add[,pn9|hex]]]] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
 			"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
 			"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
 			"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
@@ -425,6 +439,10 @@ static void usage()
 			"  -V w,p[,i[,x[,s[,v]]]]  with -G and -Y: check every frame's CRC on the GPU: width w (8, 16, 24, 32), poly p, init i and xorout x in\n"
 			"              hex, s bytes skipped behind the sync word, v = 1: complemented bits; the frame is -Y's n bytes, the CRC its last w / 8:\n"
 			"              every frame line ends in ok, bad or -, and behind them a line 'crc <file> <start_sample> <n_samples> <n_ok> <sample|->'\n"
+			"  -N m[,n[,a[,w]]]  with -G, -Y and -V: packets with a length byte behind -Y's word: lengths n .. m (n default 0), a bytes the length\n"
+			"              does not count, whitened with w (pn9, or hex bytes); the CRC is -V's (which then checks no fixed frame), the byte order -Y's:\n"
+			"              behind a burst's frame lines 'packet <file> <start_sample> <sync_sample> <len> <ok|bad|-> <hex|->' per match of the word,\n"
+			"              then 'pkts <file> <start_sample> <n_samples> <n_seen> <n_ok> <sample|->'\n"
 			"  -k prefix   keep: for a recording that arrives in parts.  Every -L file is processed in whole blocks only (nothing is padded), then\n"
 			"              its receiver's state is saved to <prefix>.<file index>.state and the bytes that filled no block to\n"
 			"              <prefix>.<file index>.rest\n"
@@ -507,7 +525,7 @@ bool cli::parse_format(const char *arg)
 int cli::parse(int argc, char **argv)
 {
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCG:O:Y:U:V:k:K:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCG:O:Y:U:V:N:k:K:h")) != -1) {
 		switch (c) {
 		case 'M': meter = true; break;
 		case 'Q': envelope = true; break;
@@ -578,6 +596,13 @@ int cli::parse(int argc, char **argv)
 			if (!crc_parse(optarg, crc_width, crc_poly, crc_init, crc_xorout, crc_skip, crc_invert)) {
 				fprintf(stderr, "tfrec_gpu: bad -V '%s': want <width>,<poly>[,<init>[,<xorout>[,<skip>[,<inv>]]]]: width 8, 16, 24 or 32, poly, init and "
 						"xorout 1 .. 8 hex digits, skip a number, inv 0 or 1\n", optarg);
+				return 1;
+			}
+			break;
+		case 'N':
+			if (!packet_parse(optarg, pkt_len_max, pkt_len_min, pkt_add, pkt_whiten)) {
+				fprintf(stderr, "tfrec_gpu: bad -N '%s': want <len_max>[,<len_min>[,<add>[,pn9|<hex>]]]: numbers, then the whitening sequence, pn9 or "
+						"an even number of hex digits, 274 bytes at most\n", optarg);
 				return 1;
 			}
 			break;
@@ -813,7 +838,21 @@ int cli::check() const
 		fprintf(stderr, "tfrec_gpu: -V checks frames of polarity + alone: not with -Y's both\n");
 		return 1;
 	}
-	if (crc_width) {
+	if (pkt_len_max >= 0 && !(crc_width && sync_bits && track_rate)) {
+		fprintf(stderr, "tfrec_gpu: -N checks the packets behind -Y's word with -V's CRC: give -G rate, -Y hex and -V width,poly with it\n");
+		return 1;
+	}
+	if (pkt_len_max >= 0) {
+		const tfrec_packet::Settings s = { (int32_t)track_rate, (int32_t)pkt_len_min, (int32_t)pkt_len_max, (int32_t)pkt_add, (int32_t)crc_skip, (int32_t)crc_width,
+						   crc_poly, crc_init, crc_xorout, (sync_lsb ? TFREC_AMD_CRC_LSB : 0u) | (crc_invert ? TFREC_AMD_CRC_INVERT : 0u),
+						   (int32_t)pkt_whiten.size() };
+		if (const char *why = tfrec_packet::refusal(s)) {
+			fprintf(stderr, "tfrec_gpu: -N: %s (%ld bit/s, lengths %d .. %d: the longest packet reaches %lld samples)\n", why, track_rate, pkt_len_min,
+				pkt_len_max, tfrec_packet::reach(s));
+			return 1;
+		}
+	}
+	if (crc_width && pkt_len_max < 0) {
 		const tfrec_crc::Settings s = { (int32_t)track_rate, (int32_t)sync_bytes, (int32_t)crc_skip, (int32_t)crc_width, crc_poly, crc_init, crc_xorout,
 						(sync_lsb ? TFREC_AMD_CRC_LSB : 0u) | (crc_invert ? TFREC_AMD_CRC_INVERT : 0u) };
 		if (const char *why = tfrec_crc::refusal(s)) {
@@ -1076,6 +1115,8 @@ int cli::run()
 		e.set_code(code_taps, code_invert);
 	if (crc_width)
 		e.set_crc(crc_width, crc_poly, crc_init, crc_xorout, crc_skip, crc_invert);
+	if (pkt_len_max >= 0)
+		e.set_packets(pkt_len_max, pkt_len_min, pkt_add, pkt_whiten);
 	if (keep_prefix)
 		e.set_keep(keep_prefix);
 	if (cont_prefix)
