@@ -1351,6 +1351,67 @@ int tfrec_amd_enable_burst_packets(tfrec_amd_ctx *ctx, int32_t rate, int32_t len
 int tfrec_amd_read_burst_packets(tfrec_amd_ctx *ctx, tfrec_amd_burst_packet *out, size_t cap_runs, uint32_t *n_runs, uint32_t *words,
 				 size_t cap_words, uint64_t *n_words);
 
+/* Pulse slicer (tfrec_amd_enable_burst_symbols): an optional stage of the burst track, valid in any of its modes though
+ * meant for the amplitude mode, for on-off keyed transmitters whose bit is the WIDTH of a pulse or of the gap behind it (FS20 / HMS /
+ * EM / KS300, the LaCrosse TX3 family): nothing that reads at fixed symbol centres gives their bits.  It reads the track's bitmap,
+ * never the coded one, needs neither sync nor CRC, and its output has a shape of its own: one bit per SYMBOL.  There is no reference
+ * counterpart: this text is normative, tfrec_amd/pulsecode.py restates it.  Exact integers only.
+ *   Settings: fixed at enable.  mode, TFREC_AMD_PULSE_WIDTH or TFREC_AMD_PULSE_GAP; lo, mid, hi in captured samples, 1 <= lo <= mid <=
+ *             hi <= 2046; the flag TFREC_AMD_PULSE_SHORT_ONE: a short stretch reads 1, otherwise it reads 0.
+ *   History:  the line code's rule: for entry e of a submit's table with track t[0 .. n), t[x] for x < 0 is the chain's track ahead of
+ *             the piece.  H bits are available: H = 0 without TFREC_AMD_RUN_CONTINUES, else H = min(2047, H' + n') of the OPEN piece
+ *             that ended the submit before.  t[x] = 0 for x < -H.  The stage carries its own 64 words and H per stream, apart from the
+ *             sync's and the code's.  A run that does not fit max_samples, or an OPEN run beyond max_runs, gives nothing and leaves
+ *             H = 0.  A reset drops the chain.  tfrec_amd_save_streams and _load_streams do not carry the history.
+ *   Stretch:  for sample k of a piece, l(k) is the number of consecutive x = k - 1, k - 2, ... >= -H with t[x] = t[k - 1], counted to
+ *             2047 at most.  The stretch reaches the chain's start iff l(k) = k + H < 2047; l = 0 at the chain's first sample counts
+ *             as reaching it.
+ *   Edge:     the deciding edge is, in WIDTH mode, a fall: t[k] = 0 and t[k - 1] = 1; in GAP mode a rise: t[k] = 1 and t[k - 1] = 0,
+ *             the chain's first sample included when it is 1.
+ *   Class:    with w = l(k) at a deciding edge, in this order: GAP with a stretch that reaches the chain's start: a break -- this is
+ *             where a frame begins --; w < lo: a glitch, which gives no symbol and is only counted (the neighbouring stretches are NOT
+ *             joined); lo <= w < mid: short; mid <= w <= hi: long; w > hi: a break.  The cap at 2047 therefore never decides.
+ *   Symbols:  the piece's short, long and break decisions in order of k.  Symbol i of entry e is bit pool_offset_e + i of two bitmaps,
+ *             both packed as the track's: `bits` holds the symbol's value (short or long by the flag, 0 for a break), `marks` holds 1
+ *             iff the symbol is a break.  A piece of n bits has at most (n + 1) / 2 symbols.  Bits behind a piece's n_symbols and
+ *             bits of no run are 0.
+ *   Record:   the entry's first 24 bytes, bit_offset = its pool_offset, n_symbols, n_breaks (the symbols that are breaks), n_glitches,
+ *             reserved = 0.
+ *   Merging:  the pieces' symbol streams are concatenated at bit granularity and the three counts added; n_samples and the flags as
+ *             for tfrec_amd_track.  Without TFREC_AMD_E_OVERFLOW the merged record and stream do not depend on how the stream was
+ *             cut into submits.
+ *   Limits:   no rise-to-rise (period) mode, no Manchester code, no parity or checksum of any protocol.  A gap code's last gap has
+ *             no closing rise and is lost.  A level set badly splits pulses, as in the amplitude track.  Nothing of it has been
+ *             measured on real recordings. */
+#define TFREC_AMD_PULSE_WIDTH 0      /* tfrec_amd_enable_burst_symbols' mode: the symbol is the width of a pulse, decided at its fall */
+#define TFREC_AMD_PULSE_GAP 1        /* ... of a gap, decided at the rise behind it */
+#define TFREC_AMD_PULSE_SHORT_ONE 1u /* its flag: a short stretch reads 1 and a long one 0 */
+typedef struct {            /* 48 bytes */
+	uint32_t stream;        /* these five: copied from the table entry */
+	uint32_t flags;
+	int64_t  start_sample;
+	uint32_t n_samples;
+	int32_t  thresh;
+	uint64_t bit_offset;    /* the entry's pool_offset: symbol i is bit bit_offset + i of both bitmaps */
+	uint32_t n_symbols;     /* the short, long and break decisions of the piece */
+	uint32_t n_breaks;      /* ... of which are breaks */
+	uint32_t n_glitches;    /* the deciding edges behind a stretch shorter than lo */
+	uint32_t reserved;      /* 0 */
+} tfrec_amd_burst_symbols;
+/* Turn the pulse slicer on: after tfrec_amd_enable_burst_track (any mode), before the first submit, once.  Device memory, counted in
+ * tfrec_amd_get_memory: per FIFO set max_runs * 48 bytes and five bitmaps of ceil(max_samples / 32) words (bits, marks and the three
+ * device-only per-sample ones); per stream the carried 64 words and H (260 bytes); no page-locked memory.  Errors: a mode or a
+ * setting outside the above, an unknown flag, no burst track or a second call: TFREC_AMD_E_INVAL, and nothing is allocated; after the
+ * first submit or a poisoned context: TFREC_AMD_E_STATE; TFREC_AMD_E_NOMEM as elsewhere; a call that fails leaves the context exactly
+ * as it was.  A context on which it was never called holds and launches what it did.  Its kernels run on the recorder's low-priority
+ * stream behind the track's. */
+int tfrec_amd_enable_burst_symbols(tfrec_amd_ctx *ctx, int32_t mode, int32_t lo, int32_t mid, int32_t hi, uint32_t flags);
+/* out[i] = the record of entry i of the table tfrec_amd_read_captures returns for the same submit, bits and marks = the two symbol
+ * bitmaps, cap_words words of room each (both null: the counts and the records alone): tfrec_amd_read_burst_tracks' conventions,
+ * counts -- n_words is the track's, the words of the pairs delivered --, prefixes on TFREC_AMD_E_OVERFLOW and errors throughout. */
+int tfrec_amd_read_burst_symbols(tfrec_amd_ctx *ctx, tfrec_amd_burst_symbols *out, size_t cap_runs, uint32_t *n_runs, uint32_t *bits,
+				 uint32_t *marks, size_t cap_words, uint64_t *n_words);
+
 /* Power spectrum of the input rows (tfrec_amd_enable_spectrum): where in a recording there is energy, and where the
  * short bursts are that an average hides -- before a receiver is placed.  It belongs to an input ROW of a submit, not to a stream: it
  * is taken on x, the int16 value every format maps a stored component to (tfrec_amd_create_format; -8192 <= x <= 8191), at the

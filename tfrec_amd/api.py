@@ -21,6 +21,7 @@ from .envelope import ENVELOPE_DTYPE  # tfrec_amd_envelope
 from .levels import LEVEL_DTYPE  # tfrec_amd_level
 from .occupancy import OCC_DTYPE  # tfrec_amd_occupancy
 from .packet import PACKET_DTYPE  # tfrec_amd_burst_packet
+from .pulsecode import SYMBOLS_DTYPE  # tfrec_amd_burst_symbols
 from .sync import SYNC_DTYPE  # tfrec_amd_burst_sync
 from .track import TRACK_DTYPE  # tfrec_amd_track
 
@@ -126,6 +127,7 @@ EXPORTS = (
     "tfrec_amd_enable_burst_code", "tfrec_amd_read_burst_codes",
     "tfrec_amd_enable_burst_crc", "tfrec_amd_read_burst_crcs",
     "tfrec_amd_enable_burst_packets", "tfrec_amd_read_burst_packets",
+    "tfrec_amd_enable_burst_symbols", "tfrec_amd_read_burst_symbols",
 )
 
 _libs = {}
@@ -251,6 +253,9 @@ def load_library(build: bool = True, experiments: bool = False, short_segments: 
     L.tfrec_amd_enable_burst_packets.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32,
                                                  C.c_uint32, C.c_uint32, C.c_char_p, C.c_int32, C.c_uint32]
     L.tfrec_amd_read_burst_packets.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
+                                               C.POINTER(C.c_uint64)]
+    L.tfrec_amd_enable_burst_symbols.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32]
+    L.tfrec_amd_read_burst_symbols.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_size_t,
                                                C.POINTER(C.c_uint64)]
     L.tfrec_amd_stream_state_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
     L.tfrec_amd_save_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
@@ -867,6 +872,29 @@ class Receiver:
         packet.bits_of(rec, words) is a record's ok track.  Overflow as for read_burst_tracks.  packet_total holds the submit's
         true run count."""
         return self._read_run_records(self.L.tfrec_amd_read_burst_packets, PACKET_DTYPE, "packet_total", allow_overflow, words=True)
+
+    def enable_burst_symbols(self, mode: int, lo: int, mid: int, hi: int, short_one: bool = False):
+        """Turn the pulse slicer on (tfrec_amd_enable_burst_symbols; after enable_burst_track in any mode, before the first submit):
+        a symbol per deciding edge of the track -- a fall (mode pulsecode.WIDTH) or a rise (pulsecode.GAP) --, short, long or
+        break by the samples lo, mid, hi of the stretch ahead of it; short reads 1 under `short_one`.  read_burst_symbols returns
+        the records and the two symbol bitmaps."""
+        if not all(-2 ** 31 <= int(a) < 2 ** 31 for a in (mode, lo, mid, hi)):  # (refused before ctypes could wrap a value into range)
+            raise TfrecAmdError(E_INVAL, "a setting outside its type")
+        _check(self.L, self.L.tfrec_amd_enable_burst_symbols(self.h, int(mode), int(lo), int(mid), int(hi), 1 if short_one else 0))
+
+    def read_burst_symbols(self, allow_overflow: bool = False):
+        """The symbols of the OLDEST undrained submit (tfrec_amd_read_burst_symbols; call it before the drain that pops that
+        submit) -> (a SYMBOLS_DTYPE array, one record per entry of that submit's run table; the bits bitmap's and the marks
+        bitmap's uint32 words): pulsecode.piece_of(rec, bits, marks) is a record's symbols.  Overflow as for read_burst_tracks.
+        symbols_total holds the submit's true run count."""
+        marks = []
+
+        def fn(h, out, cap_runs, nr, words, cap_words, nw):  # the shared reader's shape: marks beside bits, as many words
+            marks[:] = [np.zeros(int(cap_words), dtype=np.uint32)]
+            return self.L.tfrec_amd_read_burst_symbols(h, out, cap_runs, nr, words, marks[0].ctypes.data if words else None, cap_words, nw)
+
+        recs, bits = self._read_run_records(fn, SYMBOLS_DTYPE, "symbols_total", allow_overflow, words=True)
+        return recs, bits, marks[0][:len(bits)]
 
     def enable_runs_input(self, max_runs: int, max_samples: int):
         """Turn sparse submits on (tfrec_amd_enable_runs_input; decimated receivers, before the first submit): a submit_runs may

@@ -1,5 +1,5 @@
 // tfrec_amd/csrc/capi_bursts.h -- the entry points of the five burst stages on the recorder's table: the meter, the
-// envelope (6r), the clock (6s), the track (6t, with its centres; 6v, its amplitude mode, with its levels; 6w, its auto-centre mode, with its centre records; 6x, its phase mode; 6y, its line code; 6z, its frame check; 6za, its packet check) and the sync (6u).  What they share comes first -- the enables'
+// envelope (6r), the clock (6s), the track (6t, with its centres; 6v, its amplitude mode, with its levels; 6w, its auto-centre mode, with its centre records; 6x, its phase mode; 6y, its line code; 6z, its frame check; 6za, its packet check; 6zb, its pulse slicer) and the sync (6u).  What they share comes first -- the enables'
 // preflight, the rebase of start_sample, the record-only reader and the record-plus-bitmap reader --, then each
 // stage's enable and read, which add their own argument checks and buffers.  Included by capi.hip, which lists what is where.
 #pragma once
@@ -14,6 +14,7 @@ constexpr StageNames kClockNames = { "burst clock", "clock", "tfrec_amd_enable_b
 constexpr StageNames kTrackNames = { "burst track", "track", "tfrec_amd_enable_burst_track" };
 constexpr StageNames kCentreNames = { "auto-centre track", "centre", "tfrec_amd_enable_burst_track_auto" };
 constexpr StageNames kCodeNames = { "line code", "code", "tfrec_amd_enable_burst_code" };
+constexpr StageNames kPulseNames = { "pulse slicer", "symbols", "tfrec_amd_enable_burst_symbols" };
 constexpr StageNames kCrcNames = { "frame check", "crc", "tfrec_amd_enable_burst_crc" };
 constexpr StageNames kPacketNames = { "packet check", "packet", "tfrec_amd_enable_burst_packets" };
 constexpr StageNames kSyncNames = { "burst sync", "sync", "tfrec_amd_enable_burst_sync" };
@@ -510,4 +511,56 @@ int tfrec_amd_read_burst_packets(tfrec_amd_ctx *c, tfrec_amd_burst_packet *out, 
 				 size_t cap_words, uint64_t *n_words)
 {
 	return c ? read_run_bitmaps(c, c->pkt, c->pkt.d_words, kPacketNames, out, cap_runs, n_runs, words, cap_words, n_words) : TFREC_AMD_E_INVAL;
+}
+
+// ---- the pulse slicer
+int tfrec_amd_enable_burst_symbols(tfrec_amd_ctx *c, int32_t mode, int32_t lo, int32_t mid, int32_t hi, uint32_t flags)
+{
+	if (!c)
+		return TFREC_AMD_E_INVAL;
+	if (mode != TFREC_AMD_PULSE_WIDTH && mode != TFREC_AMD_PULSE_GAP) {
+		snprintf(g_err, sizeof(g_err), "the pulse slicer's mode is 0, a pulse's width, or 1, a gap's");
+		return TFREC_AMD_E_INVAL;
+	}
+	if (lo < 1 || mid < lo || hi < mid || hi > 2046) {
+		snprintf(g_err, sizeof(g_err), "the pulse slicer's widths are 1 <= lo <= mid <= hi <= 2046 samples");
+		return TFREC_AMD_E_INVAL;
+	}
+	if (flags & ~TFREC_AMD_PULSE_SHORT_ONE) {
+		snprintf(g_err, sizeof(g_err), "the pulse slicer's flags are 0 or 1, a short stretch reads 1");
+		return TFREC_AMD_E_INVAL;
+	}
+	TRY(enable_preflight(c, kPulseNames, c->trk.on, "the burst track", "tfrec_amd_enable_burst_track", c->pls.on));
+	EnableGuard<BurstSymbols> guard(c, c->pls);
+	BurstSymbols &o = c->pls;
+	const size_t n = (size_t)c->cfg.n_streams;
+	for (int k = 0; k < kSets; k++) {
+		TRY(own_device(c, o.d_recs[k], (size_t)c->cap.max_runs * sizeof(tfrec_amd_burst_symbols)));
+		TRY(own_device(c, o.d_maps[k], kPulseMaps * c->trk.n_words * sizeof(uint32_t)));
+		o.d_bits[k] = o.d_maps[k];
+		o.d_marks[k] = o.d_maps[k] + c->trk.n_words;
+	}
+	TRY(own_device(c, o.d_carry, n * 64 * sizeof(uint32_t)));
+	TRY(own_device(c, o.d_hist, n * sizeof(uint32_t)));
+	HIPCHK(hipMemset(o.d_carry, 0, n * 64 * sizeof(uint32_t)));  // (never used before a submit has written them: no first submit CONTINUES)
+	HIPCHK(hipMemset(o.d_hist, 0, n * sizeof(uint32_t)));
+	o.mode = mode;
+	o.lo = lo;
+	o.mid = mid;
+	o.hi = hi;
+	o.flags = flags;
+	o.on = guard.ok = true;
+	return TFREC_AMD_OK;
+}
+
+// the records and `bits` by the shared reader, then `marks` by the same: the counts and the verdict are equal
+int tfrec_amd_read_burst_symbols(tfrec_amd_ctx *c, tfrec_amd_burst_symbols *out, size_t cap_runs, uint32_t *n_runs, uint32_t *bits,
+				 uint32_t *marks, size_t cap_words, uint64_t *n_words)
+{
+	if (!c || !bits != !marks)
+		return TFREC_AMD_E_INVAL;
+	const int r = read_run_bitmaps(c, c->pls, c->pls.d_bits, kPulseNames, out, cap_runs, n_runs, bits, cap_words, n_words);
+	if (!marks || (r != TFREC_AMD_OK && r != TFREC_AMD_E_OVERFLOW))
+		return r;
+	return read_run_bitmaps(c, c->pls, c->pls.d_marks, kPulseNames, out, cap_runs, n_runs, marks, cap_words, n_words);
 }

@@ -132,6 +132,15 @@ struct BurstCode : RunRecords<tfrec_amd_track> {
 	uint32_t *d_words[kSets] = {};
 	uint32_t *d_carry = nullptr, *d_hist = nullptr;
 };
+// tfrec_amd_enable_burst_symbols: the settings; per set the records (RunRecords) and the five bitmaps in one
+// allocation (bits, marks, the three per-sample ones: the track's size each); per stream the carried 64 words of track bits and H
+struct BurstSymbols : RunRecords<tfrec_amd_burst_symbols> {
+	int mode = 0, lo = 0, mid = 0, hi = 0;
+	uint32_t flags = 0;
+	uint32_t *d_maps[kSets] = {};
+	uint32_t *d_bits[kSets] = {}, *d_marks[kSets] = {};  // (the first two of d_maps, as the readers take them)
+	uint32_t *d_carry = nullptr, *d_hist = nullptr;
+};
 // tfrec_amd_enable_burst_crc: the settings as crc_kernel takes them (D, r0, the width, the terms' number); per set
 // the records (RunRecords) and the check bitmap (the track's size); per stream the carried 512 words of input bits and H
 // (crc_carry_kernel); once, the term table (8 N pairs)
@@ -355,6 +364,7 @@ struct tfrec_amd_ctx {
 	BurstTrack trk;
 	BurstSync syn;
 	BurstCode code;
+	BurstSymbols pls;
 	BurstCrc crc;
 	BurstPacket pkt;
 	DecIn decin;

@@ -296,6 +296,14 @@ static CodeBufs code_bufs(const tfrec_amd_ctx *c, int set)
 		 .hist = o.d_hist, .rate = o.rate, .taps = o.taps, .flags = o.flags };
 }
 
+// The pulse slicer's buffers of a set: it reads the track's bitmap, never the coded one
+static PulseBufs pulse_bufs(const tfrec_amd_ctx *c, int set)
+{
+	const BurstSymbols &o = c->pls;
+	return { .recs = o.d_recs[set], .maps = o.d_maps[set], .track = c->trk.d_words[set], .carry = o.d_carry, .hist = o.d_hist, .mode = o.mode,
+		 .lo = o.lo, .mid = o.mid, .hi = o.hi, .flags = o.flags };
+}
+
 // The frame check's buffers of a set: its input is the bitmap the sync reads
 static CrcBufs crc_bufs(const tfrec_amd_ctx *c, int set)
 {
@@ -436,6 +444,8 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 			HIPCHK(launch_burst_clock(c->cap.lane.st, out, b, c->clk.d_recs[set]));
 		if (c->trk.on)  // the burst track: behind the clock, on the table, the working set, the samples, the final mask and its own carry
 			TRY(launch_track(c, set, out, b));
+		if (c->pls.on)  // the pulse slicer: behind the track's carry kernel, on the table, the working set, the track's bitmap and its own carry
+			HIPCHK(launch_burst_symbols(c->cap.lane.st, out, b, pulse_bufs(c, set)));
 		if (c->code.on)  // the line code: behind the track's carry kernel, on the table, the working set, the track's records and bitmap and its own carry
 			HIPCHK(launch_burst_code(c->cap.lane.st, out, b, code_bufs(c, set)));
 		if (c->syn.on)  // the burst sync: behind the track's carry kernel, on the table, the working set, the track's bitmap and its own carry

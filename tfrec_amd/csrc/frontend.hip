@@ -853,6 +853,7 @@ hipError_t launch_fmdev(hipStream_t st, const FrontOut &o, EventBuf *eb, int wma
 #include "sync.h"      // sync_kernel, sync_carry_kernel, launch_burst_sync
 #include "linecode.h"  // linecode_kernel, linecode_carry_kernel, launch_burst_code
 #include "crc.h"       // crc_kernel, crc_carry_kernel, launch_burst_crc
+#include "pulsecode.h"  // pulse_kernel, pulse_pack_kernel, launch_burst_symbols
 #include "packet.h"    // packet_kernel, packet_carry_kernel, launch_burst_packet
 #include "spectrum.h"  // spectrum_kernel, launch_spectrum
 #include "occupancy.h"  // occupancy_kernel, launch_occupancy

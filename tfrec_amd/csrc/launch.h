@@ -73,6 +73,18 @@ struct CodeBufs {
 	int rate;
 	uint32_t taps, flags;
 };
+// The pulse slicer's buffers and settings (pulsecode.h): the set's records and five bitmaps of ceil(max_samples / 32) words each (bits,
+// marks, then the device-only per-sample event, value and mark bitmaps), the set's track bitmap, the carried 64 words of track bits
+// and H of every stream
+constexpr int kPulseMaps = 5;
+struct PulseBufs {
+	tfrec_amd_burst_symbols *recs;
+	uint32_t *maps;
+	const uint32_t *track;
+	uint32_t *carry, *hist;
+	int mode, lo, mid, hi;
+	uint32_t flags;
+};
 // The frame check's buffers and settings (crc.h): the set's records and check bitmap, the input bitmap of the same set (the coded
 // one where the line code is on, else the track's), the carried 512 words of input bits and H of every stream, the term table
 // (crc_table.h: n_terms pairs (off, col)), D, r0 and the CRC's width
@@ -149,6 +161,7 @@ hipError_t launch_burst_track_auto(hipStream_t st, const FrontOut &o, const Capt
 hipError_t launch_burst_track_phase(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);  // (k.centre: the set centres in Hz; k.carry: 80 pairs a stream)
 hipError_t launch_burst_sync(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const SyncBufs &k);
 hipError_t launch_burst_code(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const CodeBufs &k);
+hipError_t launch_burst_symbols(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const PulseBufs &k);
 hipError_t launch_burst_crc(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const CrcBufs &k);
 hipError_t launch_burst_packet(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const PacketBufs &k);
 hipError_t launch_spectrum(hipStream_t st, int fmt, const uint8_t *iq, size_t stride, const SpectrumBufs &b);

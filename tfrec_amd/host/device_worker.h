@@ -293,6 +293,11 @@ inline int device_worker::open_context()
 			r = tfrec_amd_set_burst_track_centre(ctx, all.data(), hz.data(), (int)n);
 		}
 	}
+	if (!r && job.slicing()) {  // -J: the pulse slicer on the track
+		call = "tfrec_amd_enable_burst_symbols";
+		r = tfrec_amd_enable_burst_symbols(ctx, job.pulse_mode, job.pulse_lo, job.pulse_mid, job.pulse_hi,
+						   job.pulse_short_one ? TFREC_AMD_PULSE_SHORT_ONE : 0u);
+	}
 	if (!r && job.coding()) {  // -U: the line code on the track, at -G's rate
 		call = "tfrec_amd_enable_burst_code";
 		r = tfrec_amd_enable_burst_code(ctx, (int32_t)job.track_rate, job.code_taps, job.code_invert ? TFREC_AMD_CODE_INVERT : 0u);
@@ -617,7 +622,7 @@ inline int device_worker::read_run_bitmaps(int (*reader)(tfrec_amd_ctx *, R *, s
 // own with the coded bits (cut alike): in b.codes beside b.tracks, or with -Y as the sync piece's track piece, b.tracks keeping the
 // raw pieces for the bits line.  -V (with -Y): the check records of the same entries, each with its check track (job.h: crc_take),
 // in b.crcs beside b.syncs.  -N (with -Y): the packet records of the same entries, each with its ok track (job.h: packet_take), in
-// b.pkts beside b.syncs
+// b.pkts beside b.syncs.  -J: the symbols records of the same entries, each with its symbols (job.h: symbols_take), in b.symbols
 inline int device_worker::read_tracks(size_t k, batch_result &b)
 {
 	std::vector<tfrec_amd_track> recs;
@@ -682,6 +687,25 @@ inline int device_worker::read_tracks(size_t k, batch_result &b)
 			return TFREC_AMD_E_STATE;
 		}
 	}
+	std::vector<tfrec_amd_burst_symbols> jrecs;  // -J: the symbols records and both bitmaps of the same entries
+	std::vector<uint32_t> jbits, jmarks;
+	if (job.slicing()) {
+		uint32_t nr = 0;
+		uint64_t nw = 0;
+		r = tfrec_amd_read_burst_symbols(ctx, NULL, 0, &nr, NULL, NULL, 0, &nw);  // (the counts: E_INVAL for want of room)
+		if (r == TFREC_AMD_E_INVAL && nr) {
+			jrecs.resize(nr);
+			jbits.resize((size_t)nw + 1);
+			jmarks.resize((size_t)nw + 1);
+			r = tfrec_amd_read_burst_symbols(ctx, jrecs.data(), jrecs.size(), &nr, jbits.data(), jmarks.data(), jbits.size(), &nw);
+		}
+		if (r)
+			return r;
+		if (jrecs.size() != recs.size()) {
+			fprintf(stderr, "tfrec_amd: device %d batch %zu: %zu symbols records beside %zu track records\n", device, k, jrecs.size(), recs.size());
+			return TFREC_AMD_E_STATE;
+		}
+	}
 	for (size_t q = 0; q < recs.size(); q++) {
 		tfrec_amd_track x = recs[q];
 		if (!cut_at_file_end(x, plan[k].file, file_blocks, true))
@@ -695,6 +719,8 @@ inline int device_worker::read_tracks(size_t k, batch_result &b)
 			b.crcs.push_back(crc_take(vrecs[q], vwords.data(), t));
 		if (job.packeting())
 			b.pkts.push_back(packet_take(precs[q], pwords.data(), t));
+		if (job.slicing())
+			b.symbols.push_back(symbols_take(jrecs[q], jbits.data(), jmarks.data(), t));
 		if (job.coding()) {  // the coded piece: the cut entry with the coded record's n_ones and bits; the sync's frames are read from it
 			x.n_ones = urecs[q].n_ones;
 			track_piece u = track_take(x, uwords.data(), n);

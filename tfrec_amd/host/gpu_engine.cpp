@@ -471,6 +471,20 @@ int gpu_engine::run()
 	chain_merger<packet_piece> pkts;
 	std::vector<packet_piece> packed;
 	pkts.begin(n);
+	chain_merger<symbol_piece> symbols;
+	std::vector<symbol_piece> sliced;
+	symbols.begin(n);
+	// -J: the burst's symbols line behind its bits (and pulses) line; the symbol pieces have their entries' flags, so the chains end together, in one order
+	auto say_symbols = [&](const std::string &file, size_t i, size_t ended) {
+		if (!job.slicing())
+			return true;
+		if (sliced.size() != ended) {
+			fprintf(stderr, "tfrec_amd: %zu symbol chains ended beside %zu track chains\n", sliced.size(), ended);
+			return false;
+		}
+		printf("%s\n", symbols_line(file, sliced[i]).c_str());
+		return true;
+	};
 	const uint64_t crc_reach = job.checking() ? (uint64_t)tfrec_crc::reach(job.crc_settings()) : 0;
 	if (job.spectrum)
 		spec.begin(job);
@@ -519,6 +533,9 @@ int gpu_engine::run()
 			packed.clear();
 			if (job.packeting())  // -N (with -Y): the packet pieces of the sync's entries, likewise
 				pkts.take(b.pkts, workers[d].plan[k], file_blocks, packed);
+			sliced.clear();
+			if (job.slicing())  // -J: the symbol pieces of the track's entries, likewise
+				symbols.take(b.symbols, workers[d].plan[k], file_blocks, sliced);
 			if (job.coding()) {  // -G -U: -G's lines of each burst, its code line, and with -Y a line per frame found on the coded track
 				said.clear();
 				tracks.take(b.tracks, workers[d].plan[k], file_blocks, said);
@@ -545,6 +562,8 @@ int gpu_engine::run()
 					printf("%s\n", track_line(files[x.stream], x, job.track_rate).c_str());
 					if (job.amplitude())
 						printf("%s\n", pulses_line(files[x.stream], x).c_str());
+					if (!say_symbols(files[x.stream], i, said.size()))
+						rc = TFREC_AMD_E_STATE;
 					printf("%s\n", code_line(files[x.stream], job.syncing() ? framed[i].trk : coded[i], job.track_rate).c_str());
 					if (job.syncing())
 						for (const sync_frame &f : sync_frames(framed[i], job))
@@ -577,6 +596,8 @@ int gpu_engine::run()
 					printf("%s\n", track_line(files[x.stream], x.trk, job.track_rate).c_str());
 					if (job.amplitude())  // -O: the burst's pulses behind its bits
 						printf("%s\n", pulses_line(files[x.stream], x.trk).c_str());
+					if (!say_symbols(files[x.stream], i, framed.size()))
+						rc = TFREC_AMD_E_STATE;
 					for (const sync_frame &f : sync_frames(x, job))
 						printf("%s\n", frame_line(files[x.stream], x, f, job, checked, i, crc_reach).c_str());
 					if (job.checking())  // -V: the burst's crc line behind its frame lines
@@ -590,12 +611,15 @@ int gpu_engine::run()
 			} else if (job.tracking()) {  // -G: likewise, behind -C's lines of the batch
 				said.clear();
 				tracks.take(b.tracks, workers[d].plan[k], file_blocks, said);
-				for (const track_piece &x : said) {
+				for (size_t i = 0; i < said.size(); i++) {
+					const track_piece &x = said[i];
 					if (job.centring())
 						printf("%s\n", centre_line(files[x.stream], x).c_str());
 					printf("%s\n", track_line(files[x.stream], x, job.track_rate).c_str());
 					if (job.amplitude())
 						printf("%s\n", pulses_line(files[x.stream], x).c_str());
+					if (!say_symbols(files[x.stream], i, said.size()))
+						rc = TFREC_AMD_E_STATE;
 				}
 			}
 			if (job.occupancy()) {  // no replay: the channel list is the product

@@ -268,6 +268,19 @@ public:
 		job.code_taps = taps;
 		job.code_invert = invert;
 	}
+	// -J (with -G): the pulse slicer (tfrec_amd_enable_burst_symbols) on the track, for pulse-width and pulse-gap keyed
+	// bursts.  run() merges the symbol pieces' chains beside the track's (job.h: chain_merger<symbol_piece>) and prints, behind each
+	// burst's bits line (and pulses line under -O),
+	//   symbols <file> <start_sample> <n_samples> <n_symbols>[+] <n_breaks> <n_glitches> <text|->
+	// (job.h: symbols_line).  Nothing of it has been measured on real recordings.
+	void set_symbols(int mode, int lo, int mid, int hi, bool short_one)
+	{
+		job.pulse_mode = mode;
+		job.pulse_lo = lo;
+		job.pulse_mid = mid;
+		job.pulse_hi = hi;
+		job.pulse_short_one = short_one;
+	}
 	// -V (with -G and -Y): the frame check (tfrec_amd_enable_burst_crc) on the track the sync reads, at -G's rate, on
 	// -Y's bytes in -Y's byte order: width, poly, init, xorout, the skipped bytes and INVERT.  run() merges the check pieces'
 	// chains beside the sync's (job.h: chain_merger<crc_piece>); every frame line ends in one more field, ok, bad or - (job.h:

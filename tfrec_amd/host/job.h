@@ -117,6 +117,9 @@ struct job_settings {
 	uint32_t crc_poly = 0, crc_init = 0, crc_xorout = 0;  // ...
 	int crc_skip = 0;              // ... the bytes behind the sync word that the CRC does not cover
 	bool crc_invert = false;       // ... and its INVERT
+	int pulse_mode = -1;           // set_symbols (-1: none): -J, the pulse slicer's mode (TFREC_AMD_PULSE_WIDTH or _GAP) on -G's track
+	int pulse_lo = 0, pulse_mid = 0, pulse_hi = 0;  // ... its widths in captured samples
+	bool pulse_short_one = false;  // ... and its SHORT_ONE
 	int pkt_len_max = -1;          // set_packets (-1: none): -N, the packet check's largest length byte; its CRC is -V's, its byte order sync_lsb, its rate -G's
 	int pkt_len_min = 0, pkt_add = 0;  // ... the smallest, and the bytes behind the length byte that it does not count
 	std::vector<uint8_t> pkt_whiten;   // ... the whitening sequence (empty: none)
@@ -135,6 +138,7 @@ struct job_settings {
 	bool tracking() const { return track_rate != 0; }  // -G (never with -s or -A)
 	bool syncing() const { return sync_bits != 0; }  // -Y (only with -G)
 	bool coding() const { return code_taps != 0; }  // -U (only with -G)
+	bool slicing() const { return pulse_mode >= 0; }  // -J (only with -G)
 	bool packeting() const { return pkt_len_max >= 0; }  // -N (only with -Y and -V)
 	bool checking() const { return crc_width != 0 && !packeting(); }  // -V (only with -Y); with -N it configures the packet check and the frame check stays off
 	tfrec_packet::Settings packet_settings() const  // tfrec_amd_enable_burst_packets' arguments
@@ -458,8 +462,16 @@ struct packet_piece : tfrec_amd_burst_packet {
 	bool bit(uint64_t k) const { return (ok[k >> 5] >> (k & 31)) & 1u; }
 };
 
+// -J: a symbols record with its first min(n_symbols, 2048) symbols: bit i of bits is symbol i's value, of marks whether it is a break
+constexpr uint64_t kSymbolsListed = 2048;
+struct symbol_piece : tfrec_amd_burst_symbols {
+	std::vector<uint32_t> bits, marks;
+	uint64_t kept() const { return std::min<uint64_t>(n_symbols, kSymbolsListed); }
+};
+
 struct batch_result {
 	std::vector<track_piece> tracks;
+	std::vector<symbol_piece> symbols;  // (-J: the symbol pieces of the entries in tracks or syncs)
 	std::vector<sync_piece> syncs;  // (-Y: in place of tracks; -U -Y: beside them, each with the CODED piece of its entry for its track piece)
 	std::vector<track_piece> codes;  // (-U without -Y: the coded pieces of the entries in tracks)
 	std::vector<crc_piece> crcs;  // (-V: the check pieces of the entries in syncs)
@@ -876,6 +888,85 @@ inline std::string pulses_line(const std::string &file, const track_piece &c)
 	return s;
 }
 
+// ---- -J: the pulse slicer (include/tfrec_amd.h: "Pulse slicer", whose text is normative; tfrec_amd/pulsecode.py restates merge and the line)
+
+// -J's argument: width|gap,lo,mid,hi[,1] -- the mode, three decimal widths in samples, and 1 for SHORT_ONE -> the fields (false: bad,
+// the settings' rule 1 <= lo <= mid <= hi <= 2046 included)
+inline bool pulse_parse(const char *arg, int &mode, int &lo, int &mid, int &hi, bool &short_one)
+{
+	std::vector<std::string> part(1);
+	for (const char *q = arg; *q; q++) {
+		if (*q == ',')
+			part.push_back("");
+		else
+			part.back() += *q;
+	}
+	if (part.size() < 4 || part.size() > 5 || (part[0] != "width" && part[0] != "gap") || (part.size() == 5 && part[4] != "1"))
+		return false;
+	for (size_t i = 1; i < 4; i++)
+		if (part[i].empty() || part[i].size() > 4 || part[i].find_first_not_of("0123456789") != std::string::npos)
+			return false;
+	mode = part[0] == "gap" ? TFREC_AMD_PULSE_GAP : TFREC_AMD_PULSE_WIDTH;
+	lo = atoi(part[1].c_str());
+	mid = atoi(part[2].c_str());
+	hi = atoi(part[3].c_str());
+	short_one = part.size() == 5;
+	return 1 <= lo && lo <= mid && mid <= hi && hi <= 2046;
+}
+
+// n bits of src from bit src_off on -> dst, from its bit dst_len on
+inline void symbols_append(std::vector<uint32_t> &dst, uint64_t dst_len, const uint32_t *src, uint64_t src_off, uint64_t n)
+{
+	dst.resize((size_t)((dst_len + n + 31) >> 5), 0u);
+	for (uint64_t k = 0; k < n; k++)
+		if ((src[(src_off + k) >> 5] >> ((src_off + k) & 31)) & 1u)
+			dst[(dst_len + k) >> 5] |= 1u << ((dst_len + k) & 31);
+}
+
+// a device record, the submit's two symbol bitmaps and the entry's track piece -> the piece, with the track piece's stream, flags and
+// n_samples (the file's end may cut it).  The symbols and the counts stay the device's: the padding behind a file's end is silence.
+inline symbol_piece symbols_take(const tfrec_amd_burst_symbols &r, const uint32_t *bits, const uint32_t *marks, const track_piece &t)
+{
+	symbol_piece p;
+	static_cast<tfrec_amd_burst_symbols &>(p) = r;
+	p.stream = t.stream;
+	p.flags = t.flags;
+	p.n_samples = t.n_samples;
+	symbols_append(p.bits, 0, bits, r.bit_offset, p.kept());
+	symbols_append(p.marks, 0, marks, r.bit_offset, p.kept());
+	return p;
+}
+
+// piece p, which CONTINUES the chain c, merged into it (the header's Merging): the symbol streams concatenated at bit granularity, as
+// far as the 2048 listed reach, n_samples and the three counts added
+inline void symbols_add(symbol_piece &c, const symbol_piece &p)
+{
+	const uint64_t have = c.kept(), n = std::min<uint64_t>(p.kept(), kSymbolsListed - have);
+	if (n) {
+		symbols_append(c.bits, have, p.bits.data(), 0, n);
+		symbols_append(c.marks, have, p.marks.data(), 0, n);
+	}
+	c.n_samples += p.n_samples;
+	c.n_symbols += p.n_symbols;
+	c.n_breaks += p.n_breaks;
+	c.n_glitches += p.n_glitches;
+	c.flags = (c.flags & TFREC_AMD_RUN_CONTINUES) | (p.flags & TFREC_AMD_RUN_OPEN);
+}
+
+// symbols <file> <start_sample> <n_samples> <n_symbols>[+] <n_breaks> <n_glitches> <text|->: the first 2048 symbols as 0, 1 and / (a
+// break); + when the burst holds more
+inline std::string symbols_line(const std::string &file, const symbol_piece &c)
+{
+	std::string s = "symbols " + file + " " + std::to_string((long long)c.start_sample) + " " + std::to_string(c.n_samples) + " " +
+			std::to_string(c.n_symbols) + (c.n_symbols > kSymbolsListed ? "+" : "") + " " + std::to_string(c.n_breaks) + " " +
+			std::to_string(c.n_glitches) + " ";
+	if (!c.kept())
+		return s + "-";
+	for (uint64_t i = 0; i < c.kept(); i++)
+		s += (c.marks[i >> 5] >> (i & 31)) & 1u ? '/' : (c.bits[i >> 5] >> (i & 31)) & 1u ? '1' : '0';
+	return s;
+}
+
 // ---- -Y: the burst sync's records, match tracks and frames (include/tfrec_amd.h: tfrec_amd_burst_sync, whose text is normative;
 // tfrec_amd/sync.py restates merge, the framing and the line)
 
@@ -1243,6 +1334,7 @@ inline std::string pkts_line(const std::string &file, const packet_piece &c)
 
 inline void chain_add(tfrec_amd_burst &c, const tfrec_amd_burst &p) { burst_add(c, p); }
 inline void chain_add(packet_piece &c, const packet_piece &p) { packet_add(c, p); }
+inline void chain_add(symbol_piece &c, const symbol_piece &p) { symbols_add(c, p); }
 inline void chain_add(crc_piece &c, const crc_piece &p) { crc_add(c, p); }
 inline void chain_add(sync_piece &c, const sync_piece &p) { sync_add(c, p); }
 inline void chain_add(track_piece &c, const track_piece &p) { track_add(c, p); }

@@ -162,6 +162,12 @@
 // the samples of the burst at which a frame that checks ends, and where the sync word of the first would have ended: a frame finder
 // for bursts whose sync word nobody knows.  With init 0 and xorout 0 a constant stretch checks too.  Not with -Y's both; a frame that
 // reaches over 16383 samples at the rate is refused.  Nothing of it has been measured on real recordings.
+// -J width|gap,lo,mid,hi[,1] (not in the reference; with -G, meant for -O): the pulse slicer (tfrec_amd_enable_burst_symbols, DESIGN.md
+// 6zb), for on-off keyed transmitters whose bit is the width of a pulse (width) or of the gap behind it (gap): FS20 is width,100,192,300
+// at 384 kS/s.  A stretch of lo .. mid - 1 samples is short, of mid .. hi long, above hi a break (/), below lo a glitch that is only
+// counted; short reads 0, with ,1 it reads 1.  Behind each burst's bits line (and pulses line under -O) stdout gets
+//   symbols <file> <start_sample> <n_samples> <n_symbols>[+] <n_breaks> <n_glitches> <text|->
+// the first 2048 symbols.  Refused where -G is.  Nothing of it has been measured on real recordings.
 // -N len_max[,len_min[,add[,pn9|<hex>]]] (not in the reference; with -G, -Y and -V): the packet check (tfrec_amd_enable_burst_packets,
 // DESIGN.md 6za), for transmitters whose packets carry a length byte behind the sync word (CC1101, RFM69, SX1231, Si446x).  Every match
 // of -Y's word is a candidate: its first byte, de-whitened, is the length L within len_min .. len_max, the packet has 1 + L + add +
@@ -360,6 +366,8 @@ struct cli {
 	int crc_width = 0, crc_skip = 0;  // -V (width 0: not given)
 	uint32_t crc_poly = 0, crc_init = 0, crc_xorout = 0;
 	bool crc_invert = false;
+	int pulse_mode = -1, pulse_lo = 0, pulse_mid = 0, pulse_hi = 0;  // -J (mode -1: not given)
+	bool pulse_short_one = false;
 	int pkt_len_max = -1, pkt_len_min = 0, pkt_add = 0;  // -N (len_max -1: not given)
 	std::vector<uint8_t> pkt_whiten;
 	const char *keep_prefix = NULL, *cont_prefix = NULL;  // -k, -K
@@ -395,7 +403,7 @@ struct cli {
 
 static void usage()
 {
-	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-G rate[,centre_hz]] [-G rate,auto] [-G rate,psk[,lag]] [-O level] [-Y hex[,errors[,bytes[,both]]]] [-Y hex,errors,bytes,both,1] [-U g3ruh|nrzi|nrzs|hextaps[,inv]] [-V width,poly[,init[,xorout[,skip[,inv]]]]] [-N len_max[,len_min[,add[,pn9|hex]]]] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
+	fprintf(stderr, "usage: tfrec_gpu [-T hexmask] [-t thresh] [-W] [-f kHz] [-c kHz] [-x | -r Hz] [-F format] [-z [windows]] [-Z [windows]] [-q] [-D] [-B] [-d dev] [-b blocks] [-n streams] [-S prefix] [-M] [-Q] [-C] [-G rate[,centre_hz]] [-G rate,auto] [-G rate,psk[,lag]] [-O level] [-Y hex[,errors[,bytes[,both]]]] [-Y hex,errors,bytes,both,1] [-U g3ruh|nrzi|nrzs|hextaps[,inv]] [-V width,poly[,init[,xorout[,skip[,inv]]]]] [-N len_max[,len_min[,add[,pn9|hex]]]] [-J width|gap,lo,mid,hi[,1]] [-k prefix] [-K prefix] [-p settings] -L dump [[-p settings] -L dump ...] | -s step_kHz -L dump | -P bins[,frames] -L dump | -A [ratio[,rel[,join_kHz]]] -L dump | -X hexfile\n"
 			"  -A [r[,l[,j]]] find the occupied channels of one dump on the GPU (a bin's peak r times over the noise floor, default 32, and\n"
 			"              within 1/l of the record's strongest, default 16; bins at most j kHz apart join, default 50), then scan those\n"
 			"  -s kHz      scan one dump: a receiver every kHz step across it, a table of levels and telegrams per channel (-D: per block)\n"
@@ -439,6 +447,9 @@ static void usage()
 			"  -V w,p[,i[,x[,s[,v]]]]  with -G and -Y: check every frame's CRC on the GPU: width w (8, 16, 24, 32), poly p, init i and xorout x in\n"
 			"              hex, s bytes skipped behind the sync word, v = 1: complemented bits; the frame is -Y's n bytes, the CRC its last w / 8:\n"
 			"              every frame line ends in ok, bad or -, and behind them a line 'crc <file> <start_sample> <n_samples> <n_ok> <sample|->'\n"
+			"  -J m,lo,mid,hi[,1]  with -G (meant for -O): pulse-width (m = width) or pulse-gap (m = gap) keyed bursts: a symbol per pulse (gap), short\n"
+			"              below mid samples and long from it, a break above hi, dropped below lo; short reads 0, with ,1 it reads 1: behind a burst's bits\n"
+			"              (and pulses) line 'symbols <file> <start_sample> <n_samples> <n_symbols> <n_breaks> <n_glitches> <text>', a break being /\n"
 			"  -N m[,n[,a[,w]]]  with -G, -Y and -V: packets with a length byte behind -Y's word: lengths n .. m (n default 0), a bytes the length\n"
 			"              does not count, whitened with w (pn9, or hex bytes); the CRC is -V's (which then checks no fixed frame), the byte order -Y's:\n"
 			"              behind a burst's frame lines 'packet <file> <start_sample> <sync_sample> <len> <ok|bad|-> <hex|->' per match of the word,\n"
@@ -525,7 +536,7 @@ bool cli::parse_format(const char *arg)
 int cli::parse(int argc, char **argv)
 {
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCG:O:Y:U:V:N:k:K:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCG:O:Y:U:V:N:J:k:K:h")) != -1) {
 		switch (c) {
 		case 'M': meter = true; break;
 		case 'Q': envelope = true; break;
@@ -596,6 +607,13 @@ int cli::parse(int argc, char **argv)
 			if (!crc_parse(optarg, crc_width, crc_poly, crc_init, crc_xorout, crc_skip, crc_invert)) {
 				fprintf(stderr, "tfrec_gpu: bad -V '%s': want <width>,<poly>[,<init>[,<xorout>[,<skip>[,<inv>]]]]: width 8, 16, 24 or 32, poly, init and "
 						"xorout 1 .. 8 hex digits, skip a number, inv 0 or 1\n", optarg);
+				return 1;
+			}
+			break;
+		case 'J':
+			if (!pulse_parse(optarg, pulse_mode, pulse_lo, pulse_mid, pulse_hi, pulse_short_one)) {
+				fprintf(stderr, "tfrec_gpu: bad -J '%s': want width|gap,<lo>,<mid>,<hi>[,1]: the widths in samples, 1 <= lo <= mid <= hi <= 2046, "
+						"and 1 where a short stretch reads 1\n", optarg);
 				return 1;
 			}
 			break;
@@ -819,6 +837,10 @@ int cli::check() const
 	if (sync_bits && (768000LL * (sync_bits - 1) + track_rate) / (2LL * track_rate) > 2047) {
 		fprintf(stderr, "tfrec_gpu: -Y: %d bits at %ld bit/s span %lld samples, more than 2047\n", sync_bits, track_rate,
 			(768000LL * (sync_bits - 1) + track_rate) / (2LL * track_rate));
+		return 1;
+	}
+	if (pulse_mode >= 0 && !track_rate) {
+		fprintf(stderr, "tfrec_gpu: -J slices the track of -G: give -G rate[,centre_hz] with it\n");
 		return 1;
 	}
 	if (code_taps && !track_rate) {
@@ -1115,6 +1137,8 @@ int cli::run()
 		e.set_code(code_taps, code_invert);
 	if (crc_width)
 		e.set_crc(crc_width, crc_poly, crc_init, crc_xorout, crc_skip, crc_invert);
+	if (pulse_mode >= 0)
+		e.set_symbols(pulse_mode, pulse_lo, pulse_mid, pulse_hi, pulse_short_one);
 	if (pkt_len_max >= 0)
 		e.set_packets(pkt_len_max, pkt_len_min, pkt_add, pkt_whiten);
 	if (keep_prefix)
