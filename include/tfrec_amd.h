@@ -899,6 +899,49 @@ int tfrec_amd_enable_burst_clock(tfrec_amd_ctx *ctx);
  * (nothing written, *n_runs set): TFREC_AMD_E_INVAL; nothing undrained or poisoned: TFREC_AMD_E_STATE. */
 int tfrec_amd_read_burst_clocks(tfrec_amd_ctx *ctx, tfrec_amd_clock *out, size_t cap_runs, uint32_t *n_runs);
 
+/* Envelope clock (tfrec_amd_enable_burst_keying): for every run of the recorder's table how fast the burst's AMPLITUDE is
+ * keyed -- what the burst clock cannot see: an on-off keyed burst has no frequency transitions, and FS20 (about 0.8 .. 1.25 kHz) and
+ * the slow OOK sensors (1 .. 5 kbit/s) lie below the clock's band and are far finer than its 375 Hz bins.  The sibling of the burst
+ * clock on the recorder, independent of it and of every other burst stage.  There is no reference counterpart: this text is normative,
+ * tfrec_amd/clock.py (keyings) restates it.  Exact integers only; no floating point.
+ *   Samples:  as for the burst clock: entry e of a submit's table (stream s, submit-relative start a, n = n_samples), z[m] = (I, Q) the
+ *             decimated pair at submit-relative index m.
+ *   Segments: segment q is the samples [4096 q, 4096 q + 4096); it counts for the entry iff it lies wholly inside [a, a + n).  A block
+ *             holds two segments, so the burst clock's cutting argument holds word for word: a segment never straddles a cut, and it is
+ *             whole in a piece iff it is whole in the uncut run.  Nothing outside the segment is read.
+ *   Signal:   amp[m] = |I| + |Q|, 0 .. 65536, the amplitude track's measure; mx = its maximum over the segment.  mx == 0: the segment is
+ *             SILENT, counts in n_silent and adds nothing else.  Otherwise sh = max(0, bitlength(mx) - 14) and x[m'] = amp[m] >> sh, 0 <=
+ *             x < 2^14, m' = m mod 4096.  The mean is not removed: the segment is a whole period of every bin.
+ *   Spectrum: for bins j = 1 .. 128 (93.75 j Hz; array index j - 1):  X_re = sum over the segment of x[m'] C[(j m') mod 4096], X_im
+ *             likewise with S -- C, S the tune table of tfrec_amd_tune_streams, read at step 1 --, |X| < 4096 * 2^14 * 2^15 = 2^41;
+ *             P_j = (X_re >> 17)^2 + (X_im >> 17)^2 < 2^49, arithmetic shifts.  Nothing is rounded between the first product and the
+ *             last sum.
+ *   Record:   tfrec_amd_clock itself: the entry's first 24 bytes, n_segments = the entry's counted segments that are not silent,
+ *             n_silent = those that are, spec[j - 1] = the sum of P_j over the former.
+ *   Cutting:  as for the burst clock: merging adds n_samples, n_segments, n_silent and spec (saturating at 2^64 - 1, which cannot
+ *             happen below 2^15 segments); a restart drops the chain.
+ *   Summary (normative for tfrec_gpu -a and clock.py), the burst clock's with another band and unit, P[j] = spec[j - 1]: the band is
+ *             j = 3 .. 127 (281.25 .. 11906.25 Hz, 125 bins; bins 1 and 2 hold the burst's own outline, 2 and 128 serve only as
+ *             neighbours), tot its sum; undefined iff n_segments == 0 or tot == 0.  jp = the lowest j of the band's maximum;  num =
+ *             P[jp+1] - P[jp-1], den = 2 P[jp] - P[jp-1] - P[jp+1];  off = floor((375 num + den) / (2 den)) if den > 0 and neither
+ *             neighbour exceeds P[jp], else 0;  keying_qhz = 375 jp + off, in QUARTER-Hz (a bin is 375 / 4 Hz), printed as Hz with two
+ *             decimals: qhz / 4 and 25 (qhz mod 4);  quality_c = floor(100 * 125 * P[jp] / tot).
+ *   Limits:   a run shorter than 8191 samples may hold no whole segment.  An alternating on/off pattern reads its PULSE-PAIR rate: half
+ *             the bit rate for NRZ 1010; a pulse-width code reads a mixture of its two symbol periods.  A square envelope has odd
+ *             harmonics.  No threshold is built in.  The band, the segment length and the usefulness of quality_c rest on synthetic
+ *             input: nothing of it has been measured on real recordings.
+ * Turn it on after tfrec_amd_enable_capture and before the first submit.  Device memory, counted in tfrec_amd_get_memory: max_runs * 1056
+ * bytes per FIFO set, a work list of 16 * max_blocks * n_streams bytes, and 2 MB of twiddle planes, which a kernel builds from the tune
+ * table during the call.  Errors: no recorder, a second call, or a context of max_blocks >= 16384 (a record's spec is summed on the
+ * device: below 2^15 segments it cannot overflow): TFREC_AMD_E_INVAL; after the first submit or a poisoned context: TFREC_AMD_E_STATE;
+ * TFREC_AMD_E_NOMEM as elsewhere; a call that fails leaves the context exactly as it was.  A context on which it was never called holds
+ * and launches what it did.  Independent of the burst meter, the envelope, the clock and the track: any subset.  Valid on every kind of
+ * context, tfrec_amd_submit_runs' included.  Its three kernels run on the recorder's low-priority stream behind the burst clock's. */
+int tfrec_amd_enable_burst_keying(tfrec_amd_ctx *ctx);
+/* out[i] = the envelope clock's record of entry i of the table tfrec_amd_read_captures returns for the same submit.  Conventions, errors
+ * and the TFREC_AMD_E_OVERFLOW prefix of tfrec_amd_read_burst_clocks. */
+int tfrec_amd_read_burst_keyings(tfrec_amd_ctx *ctx, tfrec_amd_clock *out, size_t cap_runs, uint32_t *n_runs);
+
 /* Burst track (tfrec_amd_enable_burst_track): for every run of the recorder's table what the burst SAID -- one bit per
  * captured sample, the sign of a quadrature discriminator about a centre frequency, boxcar-smoothed: 1 above the centre.  With the
  * rate from the burst clock and the centre from the burst meter a caller slices it into the burst's bits, at any rate, decoded or

@@ -120,6 +120,7 @@ EXPORTS = (
     "tfrec_amd_enable_burst_meter", "tfrec_amd_read_bursts", "tfrec_amd_stream_state_bytes", "tfrec_amd_save_streams",
     "tfrec_amd_load_streams", "tfrec_amd_enable_burst_envelope", "tfrec_amd_read_burst_envelopes",
     "tfrec_amd_enable_burst_clock", "tfrec_amd_read_burst_clocks",
+    "tfrec_amd_enable_burst_keying", "tfrec_amd_read_burst_keyings",
     "tfrec_amd_enable_burst_track", "tfrec_amd_set_burst_track_centre", "tfrec_amd_read_burst_tracks",
     "tfrec_amd_enable_burst_track_amplitude", "tfrec_amd_set_burst_track_level",
     "tfrec_amd_enable_burst_track_auto", "tfrec_amd_read_burst_track_centres", "tfrec_amd_enable_burst_track_phase",
@@ -231,6 +232,8 @@ def load_library(build: bool = True, experiments: bool = False, short_segments: 
     L.tfrec_amd_read_burst_envelopes.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
     L.tfrec_amd_enable_burst_clock.argtypes = [C.c_void_p]
     L.tfrec_amd_read_burst_clocks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+    L.tfrec_amd_enable_burst_keying.argtypes = [C.c_void_p]
+    L.tfrec_amd_read_burst_keyings.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
     L.tfrec_amd_enable_burst_track.argtypes = [C.c_void_p, C.c_int32]
     L.tfrec_amd_set_burst_track_centre.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tfrec_amd_enable_burst_track_amplitude.argtypes = [C.c_void_p, C.c_int32]
@@ -720,6 +723,17 @@ class Receiver:
         pool: a table with more than max_runs entries (E_OVERFLOW) raises unless allow_overflow, then its first max_runs records
         are returned; clock_total holds the submit's true run count."""
         return self._read_run_records(self.L.tfrec_amd_read_burst_clocks, CLOCK_DTYPE, "clock_total", allow_overflow)
+
+    def enable_burst_keying(self):
+        """Turn the envelope clock on (tfrec_amd_enable_burst_keying; after enable_capture, before the first submit; with or without
+        any other burst stage).  read_burst_keyings returns its records."""
+        _check(self.L, self.L.tfrec_amd_enable_burst_keying(self.h))
+
+    def read_burst_keyings(self, allow_overflow: bool = False) -> np.ndarray:
+        """The envelope clock's records of the OLDEST undrained submit (tfrec_amd_read_burst_keyings; read_burst_clocks'
+        conventions) -> a CLOCK_DTYPE array, one record per entry of that submit's run table (clock.keyings).  allow_overflow: as
+        read_burst_clocks; keying_total holds the submit's true run count."""
+        return self._read_run_records(self.L.tfrec_amd_read_burst_keyings, CLOCK_DTYPE, "keying_total", allow_overflow)
 
     def enable_burst_track(self, smooth: int):
         """Turn the burst track on (tfrec_amd_enable_burst_track; after enable_capture, before the first submit; with or without

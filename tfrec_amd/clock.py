@@ -10,6 +10,12 @@ frequency transition, so its spectrum peaks at the symbol rate.
   clocks_bruteforce  the same sample by sample and bin by bin, in Python integers;
   merge              a chain of pieces -> the record of the uncut run;  chains: the chains of a sequence of submits (burst.chains' walk);
   summary            clock_hz and quality_c of a merged record;  line: tfrec_gpu -C's output line.
+
+The envelope clock (tfrec_amd_enable_burst_keying) is its sibling on the burst's amplitude |I| + |Q|: 4096-sample
+segments, 128 bins of 93.75 Hz from 93.75 Hz, the same record, merge and chains, and the same summary with another band and unit:
+
+  keyings            vectorised, one submit's records;  keyings_bruteforce: sample by sample in Python integers;
+  summary(rec, KEYING), line(name, rec, KEYING)  keying_qhz (quarter-Hz) and quality_c;  tfrec_gpu -a's output line.
 """
 from __future__ import annotations
 
@@ -28,6 +34,13 @@ CLOCK_DTYPE = np.dtype([("stream", "<u4"), ("flags", "<u4"), ("start_sample", "<
 assert CLOCK_DTYPE.itemsize == 1056
 SUMMED = ("n_samples", "n_segments", "n_silent")
 SPEC_MAX = (1 << 64) - 1
+# What the summary and the line take beside the record: the line's word, spec[0]'s bin, the band (inclusive) and whether 375 jp + off
+# is quarter-Hz, printed as Hz with two decimals (a bin of 375 / 4 Hz), or Hz
+CLOCK = ("clock", BIN0, BAND, False)
+KEY_SEG = 4096  # the envelope clock: samples per segment
+KEY_BIN0 = 1
+KEY_BAND = (3, 127)  # 281.25 .. 11906.25 Hz
+KEYING = ("keying", KEY_BIN0, KEY_BAND, True)
 
 
 def _tables():
@@ -151,6 +164,78 @@ def clocks_bruteforce(dec, runs, base=None):
     return out
 
 
+def _key_tables():
+    """C[(j m') mod 4096] and S[...] as int64 [128, 4096]."""
+    c, s = tune.table()
+    k = (np.arange(KEY_BIN0, KEY_BIN0 + N_BINS)[:, None] * np.arange(KEY_SEG)[None, :]) % (1 << tune.TABLE_BITS)
+    return c.astype(np.int64)[k], s.astype(np.int64)[k]
+
+
+_KEY_TABLES = []  # (made on first use: 8 MB)
+
+
+def keyings(dec, runs, base=None):
+    """The envelope clock's records of one submit; arguments and result as clocks'."""
+    if not _KEY_TABLES:
+        _KEY_TABLES.extend(_key_tables())
+    cm, sm = _KEY_TABLES
+    out = np.zeros(len(runs), dtype=CLOCK_DTYPE)
+    for e, r in enumerate(runs):
+        s, a, n = _window(dec, r, base)
+        z = burst._pairs(dec[s]).astype(np.int64)
+        o = _copied(r)
+        rows = []
+        for q in range(-(-a // KEY_SEG), (a + n) // KEY_SEG):
+            amp = np.abs(z[KEY_SEG * q:KEY_SEG * q + KEY_SEG]).sum(axis=1)
+            mx = int(amp.max())
+            if mx == 0:
+                o["n_silent"] += 1
+            else:
+                rows.append(amp >> max(0, mx.bit_length() - 14))
+        o["n_segments"] = len(rows)
+        if rows:
+            X = np.array(rows, dtype=np.int64)
+            xr, xi = (X @ cm.T) >> 17, (X @ sm.T) >> 17  # |X| < 2^41: exact in int64
+            o["spec"] = (xr * xr + xi * xi).sum(axis=0).astype(np.uint64)
+        out[e] = o
+    return out
+
+
+def keyings_bruteforce(dec, runs, base=None):
+    """The same, one sample and one bin at a time in Python integers."""
+    c, s_ = tune.table()
+    C, S = [int(v) for v in c], [int(v) for v in s_]
+    out = np.zeros(len(runs), dtype=CLOCK_DTYPE)
+    for e, r in enumerate(runs):
+        s, a, n = _window(dec, r, base)
+        z = burst._pairs(dec[s]).tolist()
+        nseg = nsil = 0
+        spec = [0] * N_BINS
+        for q in range(len(z) // KEY_SEG):
+            if not (a <= KEY_SEG * q and KEY_SEG * q + KEY_SEG <= a + n):
+                continue
+            amp = [abs(i) + abs(k) for i, k in z[KEY_SEG * q:KEY_SEG * q + KEY_SEG]]
+            mx = max(amp)
+            if mx == 0:
+                nsil += 1
+                continue
+            nseg += 1
+            sh = max(0, mx.bit_length() - 14)
+            x = [v >> sh for v in amp]
+            for i in range(N_BINS):
+                j = KEY_BIN0 + i
+                xr = xi = 0
+                for m in range(KEY_SEG):
+                    if x[m]:
+                        xr += x[m] * C[(j * m) % 4096]
+                        xi += x[m] * S[(j * m) % 4096]
+                spec[i] += (xr >> 17) ** 2 + (xi >> 17) ** 2
+        o = _copied(r)
+        o["n_segments"], o["n_silent"], o["spec"] = nseg, nsil, spec
+        out[e] = o
+    return out
+
+
 def merge(pieces):
     """A chain of pieces (in order; piece i + 1 has CONTINUES, piece i OPEN, one stream) -> one record, that of the uncut run: the
     first piece's stream, start_sample and thresh, the first piece's CONTINUES and the last one's OPEN, n_samples, n_segments,
@@ -174,26 +259,29 @@ def chains(submits, restarts=None):
     return burst.chains(submits, restarts, join=merge)
 
 
-def summary(rec):
+def summary(rec, kind=CLOCK):
     """-> (clock_hz, quality_c) of a merged record, or None when n_segments == 0 or the band is empty.  P[j] = spec[j - 4]; the band
     is j = 12 .. 128; jp the lowest j of its maximum; off = floor((375 num + den) / (2 den)) with num = P[jp+1] - P[jp-1], den =
     2 P[jp] - P[jp-1] - P[jp+1], if den > 0 and neither neighbour exceeds P[jp], else 0; clock_hz = 375 jp + off; quality_c =
-    floor(100 * 117 * P[jp] / tot), the peak over the band's mean in hundredths."""
+    floor(100 * 117 * P[jp] / tot), the peak over the band's mean in hundredths.  kind=KEYING: the envelope clock's, P[j] =
+    spec[j - 1], the band j = 3 .. 127 (125 bins), and 375 jp + off is keying_qhz, in quarter-Hz."""
+    _, bin0, (lo, hi), _ = kind
     P = [int(v) for v in rec["spec"]]
-    lo, hi = BAND
-    band = P[lo - BIN0:hi - BIN0 + 1]
+    band = P[lo - bin0:hi - bin0 + 1]
     tot = sum(band)
     if int(rec["n_segments"]) == 0 or tot == 0:
         return None
     jp = lo + band.index(max(band))
-    p0, pm, pp = P[jp - BIN0], P[jp - 1 - BIN0], P[jp + 1 - BIN0]
+    p0, pm, pp = P[jp - bin0], P[jp - 1 - bin0], P[jp + 1 - bin0]
     num, den = pp - pm, 2 * p0 - pm - pp
     off = (BIN_HZ * num + den) // (2 * den) if den > 0 and pm <= p0 and pp <= p0 else 0
     return BIN_HZ * jp + off, 100 * len(band) * p0 // tot
 
 
-def line(name: str, rec) -> str:
-    """tfrec_gpu -C: clock <file> <start_sample> <n_samples> <n_segments> <clock_hz|-> <quality as %d.%02d|->"""
-    sm = summary(rec)
-    return "clock %s %d %d %d %s %s" % (name, int(rec["start_sample"]), int(rec["n_samples"]), int(rec["n_segments"]),
-                                       "-" if sm is None else "%d" % sm[0], "-" if sm is None else "%d.%02d" % (sm[1] // 100, sm[1] % 100))
+def line(name: str, rec, kind=CLOCK) -> str:
+    """tfrec_gpu -C: clock <file> <start_sample> <n_samples> <n_segments> <clock_hz|-> <quality as %d.%02d|->;  kind=KEYING: -a's
+    keying <file> <start_sample> <n_samples> <n_segments> <keying_hz as %d.%02d|-> <quality as %d.%02d|->"""
+    sm = summary(rec, kind)
+    rate = "-" if sm is None else "%d.%02d" % (sm[0] // 4, 25 * (sm[0] % 4)) if kind[3] else "%d" % sm[0]
+    return "%s %s %d %d %d %s %s" % (kind[0], name, int(rec["start_sample"]), int(rec["n_samples"]), int(rec["n_segments"]), rate,
+                                    "-" if sm is None else "%d.%02d" % (sm[1] // 100, sm[1] % 100))

@@ -95,6 +95,13 @@ struct RunRecords {
 	bool on = false;
 	Rec *d_recs[kSets] = {};
 };
+// tfrec_amd_enable_burst_keying: per set the records (RunRecords: the clock's record); once, the work list of the
+// largest submit with its length, and the twiddle planes
+struct BurstKeying : RunRecords<tfrec_amd_clock> {
+	uint2 *d_work = nullptr;
+	uint32_t *d_n_work = nullptr;
+	int8_t *d_planes = nullptr;
+};
 // tfrec_amd_enable_burst_track: L; every stream's centre index as the next submit uses it; per set the records
 // (RunRecords), the bitmap (ceil(max_samples / 32) words) and the submit's centre indices with their page-locked
 // source; per stream the carried last 16 pairs and chain position (track_carry_kernel).  amplitude: the track's other mode
@@ -361,6 +368,7 @@ struct tfrec_amd_ctx {
 	RunRecords<tfrec_amd_burst> burst;
 	RunRecords<tfrec_amd_envelope> env;
 	RunRecords<tfrec_amd_clock> clk;
+	BurstKeying key;
 	BurstTrack trk;
 	BurstSync syn;
 	BurstCode code;

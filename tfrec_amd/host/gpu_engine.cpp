@@ -458,6 +458,8 @@ int gpu_engine::run()
 	envelopes.begin(n);
 	chain_report<tfrec_amd_clock> clocks(clock_line);
 	clocks.begin(n);
+	chain_report<tfrec_amd_clock> keyings(keying_line);
+	keyings.begin(n);
 	chain_merger<track_piece> tracks, codes;
 	std::vector<track_piece> said, coded;
 	tracks.begin(n);
@@ -527,6 +529,8 @@ int gpu_engine::run()
 				envelopes.take(b.envelopes, workers[d].plan[k], file_blocks, files, into);
 			if (job.clocking())  // -C: likewise, behind -Q's lines of the batch
 				clocks.take(b.clocks, workers[d].plan[k], file_blocks, files, into);
+			if (job.keying)  // -a: likewise, behind -C's lines of the batch (never with a scan)
+				keyings.take(b.keyings, workers[d].plan[k], file_blocks, files, NULL);
 			checked.clear();
 			if (job.checking())  // -V (with -Y): the check pieces of the sync's entries -- the same flags, so the chains end together, in one order
 				crcs.take(b.crcs, workers[d].plan[k], file_blocks, checked);

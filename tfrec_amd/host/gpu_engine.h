@@ -214,6 +214,11 @@ public:
 	// the earliest among equals.  Under -A it is the scan's, not pass 1's.  Neither the band, the segment length nor the usefulness
 	// of quality_c has been measured on real recordings.
 	void set_clock() { job.clock = true; }
+	// -a: the envelope clock (tfrec_amd_enable_burst_keying), with or without any of -M, -Q, -C and -G.  Every context
+	// enables the recorder as for -M and the stage on it; run() merges the records' chains as -C's -- the record is -C's -- and prints
+	//   keying <file> <start_sample> <n_samples> <n_segments> <keying_hz|-> <quality|->
+	// (job.h: spectrum_summary with kKeyingBand; keying_hz from quarter-Hz as %d.%02d).  Never with set_scan.
+	void set_keying() { job.keying = true; }
 	// -G: the burst track (tfrec_amd_enable_burst_track), with or without -M, -Q and -C.  Every context enables the
 	// recorder with a pool for every sample (the bitmap has the pool's size) and the track on it, L = half a symbol of `rate` held
 	// within 1 .. 16, every stream about centre_hz; run() merges the records' chains and their bits across the batches of a file

@@ -100,6 +100,7 @@ struct job_settings {
 	bool meter = false;            // set_meter
 	bool envelope = false;         // set_envelope
 	bool clock = false;            // set_clock
+	bool keying = false;           // set_keying
 	long track_rate = 0;           // set_track (0: none): the rate in bit/s, 1000 .. 96000
 	long track_centre = 0;         // ... and every stream's centre in Hz
 	long track_level = -1;         // set_track_level (-1: none): -O, the track is the amplitude's, every stream at this level, 0 .. 65535
@@ -134,7 +135,7 @@ struct job_settings {
 
 	bool resampled() const { return rate_p != 1 || rate_q != 1; }
 	bool occupancy() const { return spectrum && occ_ratio; }  // -A, pass 1
-	bool recorder() const { return capture || metering() || enveloping() || clocking() || tracking(); }  // the contexts enable the recorder: for -S, or as the meter's, the envelope's, the clock's or the track's table
+	bool recorder() const { return capture || metering() || enveloping() || clocking() || keying || tracking(); }  // the contexts enable the recorder: for -S, or as the meter's, the envelope's, the clock's, the envelope clock's or the track's table
 	bool tracking() const { return track_rate != 0; }  // -G (never with -s or -A)
 	bool syncing() const { return sync_bits != 0; }  // -Y (only with -G)
 	bool coding() const { return code_taps != 0; }  // -U (only with -G)
@@ -403,6 +404,7 @@ inline std::vector<occ_channel> occupancy_channels(const std::vector<unsigned lo
 // -M: the burst records that belong to a file (stream = its index in the job), n_samples cut at the file's end (cut_at_file_end)
 // -Q: the envelope records likewise; one that is cut at the file's end is OPEN (the input's end cut its tail)
 // -C: the clock records likewise
+// -a: the envelope clock's records likewise (the same record)
 // -G: the track records likewise, each with its bits out of the batch's bitmap (track_piece; its functions are further down)
 constexpr uint64_t kTrackKeep = 1ull << 20;  // the samples of a chain's track that are kept
 
@@ -479,6 +481,7 @@ struct batch_result {
 	std::vector<tfrec_amd_burst> bursts;
 	std::vector<tfrec_amd_envelope> envelopes;
 	std::vector<tfrec_amd_clock> clocks;
+	std::vector<tfrec_amd_clock> keyings;
 	std::vector<tfrec_amd_event> ev;
 	std::vector<tfrec_amd_level> lv;
 	std::vector<tfrec_amd_run> runs;
@@ -686,44 +689,66 @@ inline void clock_add(tfrec_amd_clock &c, const tfrec_amd_clock &p)
 	c.flags = (c.flags & TFREC_AMD_RUN_CONTINUES) | (p.flags & TFREC_AMD_RUN_OPEN);
 }
 
-// -> whether the summary is defined (n_segments > 0 and the band j = 12 .. 128 not empty); then clock_hz = 375 jp + off and
-// quality_c = floor(100 * 117 * P[jp] / tot), in 128-bit integers (P[j] = spec[j - 4] may be saturated: 117 of them need 71 bits)
-inline bool clock_summary(const tfrec_amd_clock &r, long long &clock_hz, unsigned long long &quality_c)
+// A summary's band and unit: spec[0]'s bin, the band (inclusive), and the line's word.  quarter_hz: 375 jp + off is in quarter-Hz
+// (a bin of 375 / 4 Hz) and printed as Hz with two decimals
+struct spectrum_band {
+	int bin0, lo, hi;
+	bool quarter_hz;
+	const char *word;
+};
+constexpr spectrum_band kClockBand = { 4, 12, 128, false, "clock" };   // -C: 4500 .. 48000 Hz in 375 Hz bins
+constexpr spectrum_band kKeyingBand = { 1, 3, 127, true, "keying" };   // -a: 281.25 .. 11906.25 Hz in 93.75 Hz bins (the header's "Envelope clock")
+
+// -> whether the summary is defined (n_segments > 0 and the band not empty); then rate = 375 jp + off and quality_c = floor(100 *
+// bins * P[jp] / tot), in 128-bit integers (P[j] = spec[j - bin0] may be saturated: 125 of them need 71 bits)
+inline bool spectrum_summary(const tfrec_amd_clock &r, const spectrum_band &k, long long &rate, unsigned long long &quality_c)
 {
 	unsigned __int128 tot = 0;
-	int jp = 12;
-	for (int j = 12; j <= 128; j++) {
-		tot += r.spec[j - 4];
-		if (r.spec[j - 4] > r.spec[jp - 4])
+	int jp = k.lo;
+	for (int j = k.lo; j <= k.hi; j++) {
+		tot += r.spec[j - k.bin0];
+		if (r.spec[j - k.bin0] > r.spec[jp - k.bin0])
 			jp = j;  // (the lowest j of the maximum)
 	}
 	if (!r.n_segments || !tot)
 		return false;
-	const __int128 p0 = r.spec[jp - 4], pm = r.spec[jp - 5], pp = r.spec[jp - 3];
+	const __int128 p0 = r.spec[jp - k.bin0], pm = r.spec[jp - k.bin0 - 1], pp = r.spec[jp - k.bin0 + 1];
 	const __int128 num = pp - pm, den = 2 * p0 - pm - pp;
 	__int128 off = 0;
 	if (den > 0 && pm <= p0 && pp <= p0) {
 		const __int128 a = 375 * num + den, b = 2 * den;  // floor(a / b), b > 0
 		off = a / b - ((a % b) < 0 ? 1 : 0);
 	}
-	clock_hz = 375LL * jp + (long long)off;
-	quality_c = (unsigned long long)((unsigned __int128)100 * 117 * (unsigned __int128)p0 / tot);  // (<= 100 * 117)
+	rate = 375LL * jp + (long long)off;
+	quality_c = (unsigned long long)((unsigned __int128)100 * (unsigned)(k.hi - k.lo + 1) * (unsigned __int128)p0 / tot);  // (<= 100 * bins)
 	return true;
 }
+// -C's: the band j = 12 .. 128, clock_hz in Hz, quality_c = floor(100 * 117 * P[jp] / tot)
+inline bool clock_summary(const tfrec_amd_clock &r, long long &clock_hz, unsigned long long &quality_c)
+{
+	return spectrum_summary(r, kClockBand, clock_hz, quality_c);
+}
 
-// clock <file> <start_sample> <n_samples> <n_segments> <clock_hz|-> <quality_c as %d.%02d|->
-inline std::string clock_line(const std::string &file, const tfrec_amd_clock &r)
+// <word> <file> <start_sample> <n_samples> <n_segments> <rate|-> <quality_c as %d.%02d|->; the rate as %d, or from quarter-Hz as %d.%02d
+inline std::string spectrum_line(const std::string &file, const tfrec_amd_clock &r, const spectrum_band &k)
 {
 	long long hz = 0;
 	unsigned long long q = 0;
-	std::string s = "clock " + file + " " + std::to_string((long long)r.start_sample) + " " + std::to_string(r.n_samples) + " " +
+	std::string s = std::string(k.word) + " " + file + " " + std::to_string((long long)r.start_sample) + " " + std::to_string(r.n_samples) + " " +
 			std::to_string(r.n_segments);
-	if (!clock_summary(r, hz, q))
+	if (!spectrum_summary(r, k, hz, q))
 		return s + " - -";
 	char buf[96];
-	snprintf(buf, sizeof(buf), " %lld %llu.%02llu", hz, q / 100, q % 100);
+	if (k.quarter_hz)
+		snprintf(buf, sizeof(buf), " %lld.%02lld %llu.%02llu", hz / 4, 25 * (hz % 4), q / 100, q % 100);
+	else
+		snprintf(buf, sizeof(buf), " %lld %llu.%02llu", hz, q / 100, q % 100);
 	return s + buf;
 }
+// clock <file> <start_sample> <n_samples> <n_segments> <clock_hz|-> <quality_c as %d.%02d|->
+inline std::string clock_line(const std::string &file, const tfrec_amd_clock &r) { return spectrum_line(file, r, kClockBand); }
+// -a: keying <file> <start_sample> <n_samples> <n_segments> <keying_hz as %d.%02d|-> <quality_c as %d.%02d|->
+inline std::string keying_line(const std::string &file, const tfrec_amd_clock &r) { return spectrum_line(file, r, kKeyingBand); }
 
 // ---- -G: the burst track's records and bits (include/tfrec_amd.h: tfrec_amd_track, whose text is normative; tfrec_amd/track.py
 // restates merge, the slicer and the line)

@@ -101,6 +101,17 @@
 // channel table ends in burst_clock=<Hz|->, the clock of the channel's window with the largest quality.  Works with -M, -Q, -R, -S,
 // -n, -d and every input option; not with -X, -k or -K.  No quality threshold is built in: noise reads a quality of a few units,
 // a clean telegram 25 or more on synthetic scenes; none of it has been measured on real recordings.
+// -a (not in the reference): the envelope clock (tfrec_amd_enable_burst_keying): for every trigger window of every file how
+// fast the burst's AMPLITUDE is keyed -- the rate of an on-off keyed or pulse-width burst (FS20, HMS, EM, KS300, the NRZ OOK sensors),
+// which -C cannot see and which -G's rate and -J's widths are chosen from.  The contexts enable the recorder as for -M and the stage;
+// the pieces of a window are merged as -C's, and stdout gets, as each window ends,
+//   keying <file> <start_sample> <n_samples> <n_segments> <keying_hz|-> <quality|->
+// n_segments: the whole 4096-sample segments of the window that entered the spectrum; keying_hz: the peak of the spectrum of the
+// window's amplitude between 281.25 and 11906.25 Hz, in 93.75 Hz bins refined by its neighbours, with two decimals; quality: that peak
+// over the band's mean, in hundredths ("-": the window holds no whole segment -- one shorter than 8191 samples may not).  An
+// alternating pattern reads its pulse-pair rate, half the bit rate of NRZ 1010; a pulse-width code a mixture of its two symbol
+// periods; a square envelope has odd harmonics.  Works with -M, -Q, -C, -G, -O, -J, -S, -R, -n, -d and every input option; not with
+// -X, -k, -K, -s or -A.  No threshold is built in; nothing of it has been measured on real recordings.
 // -G rate[,centre_hz] (not in the reference): the burst track (tfrec_amd_enable_burst_track): for every trigger window
 // of every file, whether or not anything decoded in it, what the burst said when it is read at `rate` bit/s (1000 .. 96000: -C's
 // reading) about centre_hz (|centre_hz| <= 192000, default 0: -M's reading).  The contexts enable the recorder with a pool for every
@@ -353,6 +364,7 @@ struct cli {
 	bool meter = false;  // -M
 	bool envelope = false;  // -Q
 	bool clock = false;  // -C
+	bool keying = false;  // -a
 	long track_rate = 0, track_centre = 0;  // -G (rate 0: not given)
 	bool track_centre_given = false;
 	bool track_auto = false;  // -G rate,auto
@@ -423,6 +435,11 @@ static void usage()
 			"              <n_segments> <clock_hz|-> <quality|->' per trigger window (quality: the spectral peak over the band's mean; -: no\n"
 			"              whole 1024-sample segment); with -s or -A a column burst_clock= of the channel's best-quality burst instead;\n"
 			"              also with -M, -Q and -R; not with -X, -k or -K\n"
+			"  -a          measure every burst's keying rate on the GPU, the rate its amplitude is switched at (on-off keyed and pulse-width\n"
+			"              bursts, which -C cannot see): a line 'keying <file> <start_sample> <n_samples> <n_segments> <keying_hz|->\n"
+			"              <quality|->' per trigger window (keying_hz: 93.75 Hz bins between 281.25 Hz and 11.9 kHz, two decimals; an\n"
+			"              alternating pattern reads its pulse-pair rate; -: no whole 4096-sample segment); also with -M, -Q, -C, -G, -O, -J,\n"
+			"              -S and -R; not with -X, -k, -K, -s or -A\n"
 			"  -G r[,c]    read every burst's bits on the GPU, decoded or not, at r bit/s (1000 .. 96000) about the centre c Hz (default 0): a\n"
 			"              line 'bits <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->' per trigger window, MSB-first,\n"
 			"              1 above the centre (+: longer than the 2^20 samples kept); also with -M, -Q, -C, -S and -R; not with -X, -k, -K,\n"
@@ -536,11 +553,12 @@ bool cli::parse_format(const char *arg)
 int cli::parse(int argc, char **argv)
 {
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCG:O:Y:U:V:N:J:k:K:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCaG:O:Y:U:V:N:J:k:K:h")) != -1) {
 		switch (c) {
 		case 'M': meter = true; break;
 		case 'Q': envelope = true; break;
 		case 'C': clock = true; break;
+		case 'a': keying = true; break;
 		case 'G': {
 			const char *comma = strchr(optarg, ',');
 			track_auto = comma && !strcmp(comma + 1, "auto");
@@ -760,6 +778,10 @@ int cli::check() const
 			fprintf(stderr, "tfrec_gpu: -k and -K do not carry a burst across runs: not with -C\n");
 			return 2;
 		}
+		if (keying) {
+			fprintf(stderr, "tfrec_gpu: -k and -K do not carry a burst across runs: not with -a\n");
+			return 2;
+		}
 		if (track_rate) {
 			fprintf(stderr, "tfrec_gpu: -k and -K do not carry a burst across runs: not with -G\n");
 			return 2;
@@ -816,6 +838,10 @@ int cli::check() const
 	}
 	if (clock && hexfile) {
 		fprintf(stderr, "tfrec_gpu: -C measures the bursts of -L files or of a capture (-R): not with -X\n");
+		return 1;
+	}
+	if (keying && (hexfile || have_scan || have_auto)) {
+		fprintf(stderr, "tfrec_gpu: -a measures the bursts of -L files or of a capture (-R), a line per burst: not with -X, -s or -A\n");
 		return 1;
 	}
 	if (track_level >= 0 && track_lag) {
@@ -1123,6 +1149,8 @@ int cli::run()
 		e.set_envelope();
 	if (clock)
 		e.set_clock();
+	if (keying)
+		e.set_keying();
 	if (track_rate)
 		e.set_track(track_rate, track_centre);
 	if (track_level >= 0)
