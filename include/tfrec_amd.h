@@ -942,6 +942,67 @@ int tfrec_amd_enable_burst_keying(tfrec_amd_ctx *ctx);
  * and the TFREC_AMD_E_OVERFLOW prefix of tfrec_amd_read_burst_clocks. */
 int tfrec_amd_read_burst_keyings(tfrec_amd_ctx *ctx, tfrec_amd_clock *out, size_t cap_runs, uint32_t *n_runs);
 
+/* Burst band (tfrec_amd_enable_burst_band): for every run of the recorder's table the power spectrum of the burst's own
+ * IQ -- where its carrier or its two tones lie, to a fraction of a 750 Hz bin (the burst meter's histogram has 6 kHz bins and cannot
+ * tell two sensors of one type apart by their crystal offset), how wide the burst is (what a -W choice rests on), and whether two
+ * transmitters share the window.  One more sibling of the burst clock on the recorder, independent of every other burst stage.  There
+ * is no reference counterpart: this text is normative, tfrec_amd/band.py restates it.  Exact integers only; no floating point.
+ *   Samples:  as for the burst clock: entry e of a submit's table (stream s, submit-relative start a, n = n_samples), z[m] = (I, Q) the
+ *             decimated pair at submit-relative index m.
+ *   Segments: segment q is the samples [512 q, 512 q + 512); it counts for the entry iff it lies wholly inside [a, a + n).  A block
+ *             holds 16 segments, so the burst clock's cutting argument holds word for word: a segment never straddles a cut, and it is
+ *             whole in a piece iff it is whole in the uncut run.  Nothing outside the segment is read.
+ *   Normalise: mx = the largest |I| or |Q| of the segment, |-32768| = 32768.  mx == 0: the segment is SILENT, counts in n_silent and
+ *             adds nothing else.  Otherwise sh = max(0, bitlength(mx) - 13), xI = I >> sh, xQ = Q >> sh, arithmetic shifts: -2^13 <= xI,
+ *             xQ < 2^13.
+ *   Window:   with m' = m mod 512, Wn[m'] = 32767 - C[(8 m') mod 4096], C the tune table of tfrec_amd_tune_streams: a Hann window, 0 at
+ *             m' = 0 and 65534 at m' = 256.  wI = (xI * Wn) >> 16, wQ = (xQ * Wn) >> 16, arithmetic shifts: -2^13 <= wI, wQ < 2^13.
+ *   Spectrum: for bins j = -128 .. 127 (750 j Hz; array index j + 128), t = (8 j m') & 4095 (two's complement) and S[i] = C[(i - 1024)
+ *             & 4095]:  X_re = sum over the segment of wI C[t] + wQ S[t],  X_im = sum of wQ C[t] - wI S[t],  |X| < 2^38;  P_j = (X_re >>
+ *             14)^2 + (X_im >> 14)^2 < 2^49, arithmetic shifts.  Nothing is rounded between the first product and the last sum.  A
+ *             tone that ADVANCES in phase (I = cos, Q = sin of a growing angle) peaks at a positive j.
+ *   Record:   the entry's first 24 bytes, n_segments = the entry's counted segments that are not silent, n_silent = those that are,
+ *             spec[j + 128] = the sum of P_j over the former.
+ *   Cutting:  as for the burst clock: merging adds n_samples, n_segments, n_silent and spec (saturating at 2^64 - 1, which cannot
+ *             happen below 2^15 segments); the flags follow the clock's rule; a restart drops the chain.
+ *   Summary (normative for tfrec_gpu -I and band.py), in 128-bit integers, P[j] = spec[j + 128], tot the sum of all 256: undefined iff
+ *             n_segments == 0 or tot == 0.
+ *             peak_hz = 750 jp + off: jp the lowest j of the maximum; off the clock's parabola in this bin's unit: num = P[jp+1] -
+ *             P[jp-1], den = 2 P[jp] - P[jp-1] - P[jp+1], off = floor((750 num + den) / (2 den)) if den > 0 and neither neighbour
+ *             exceeds P[jp], else 0; and 0 at jp = -128 and jp = 127, which lack a neighbour.
+ *             centre_hz = floor(750 sum j P[j] / tot), the centroid, floor toward minus infinity.
+ *             bw_hz = 750 (hi - lo + 1), lo the largest j with 200 * sum_{i<j} P[i] <= tot, hi the smallest j with 200 * sum_{i>j} P[i]
+ *             <= tot: the band that holds 99 % of the power, half a percent cut from either side.
+ *             lo_hz = 750 jl, hi_hz = 750 jh: jl the lowest j of the maximum over j <= c, jh that over j > c, c = min(floor(centre_hz /
+ *             750), 126) (so neither side is empty).  For an FSK burst these are its two tones, (hi_hz - lo_hz) / 2 its deviation;
+ *             for a single carrier or an on-off keyed burst they mean nothing.
+ *   Limits:   a run shorter than 1023 samples may hold no whole segment.  The resolution is the 750 Hz bin widened by the window (the
+ *             Hann main lobe spans four bins), off a refinement.  The 256 bins are the middle half of the 384 kS/s channel: a signal
+ *             beyond +-96 kHz, which the channel filter has mostly removed, has no bin, and only the window's leakage of it shows,
+ *             strongest at the band's nearer end.  The band, the segment
+ *             length, the window and the 99 % rule rest on synthetic input: nothing of it has been measured on real recordings.
+ * Turn it on after tfrec_amd_enable_capture and before the first submit.  Device memory, counted in tfrec_amd_get_memory: max_runs * 2080
+ * bytes per FIFO set, a work list of 128 * max_blocks * n_streams bytes with its length, and 1 MB of twiddle planes, which a kernel
+ * builds from the tune table during the call.  Errors: no recorder, a second call, or a context of max_blocks >= 2048 (a record's spec is
+ * summed on the device: below 2^15 segments it cannot overflow): TFREC_AMD_E_INVAL; after the first submit or a poisoned context:
+ * TFREC_AMD_E_STATE; TFREC_AMD_E_NOMEM as elsewhere; a call that fails leaves the context exactly as it was.  A context on which it was
+ * never called holds and launches what it did.  Independent of every other burst stage: any subset.  Valid on every kind of context,
+ * tfrec_amd_submit_runs' included.  Its three kernels run on the recorder's low-priority stream behind the envelope clock's. */
+typedef struct {            /* 2080 bytes */
+	uint32_t stream;        /* these five: copied from the table entry */
+	uint32_t flags;
+	int64_t  start_sample;
+	uint32_t n_samples;
+	int32_t  thresh;
+	uint32_t n_segments;    /* counted segments that are not silent */
+	uint32_t n_silent;      /* counted segments whose every sample is (0, 0) */
+	uint64_t spec[256];     /* bin j = index - 128, 750 j Hz: the sum of P_j over the n_segments segments */
+} tfrec_amd_band;
+int tfrec_amd_enable_burst_band(tfrec_amd_ctx *ctx);
+/* out[i] = the burst band's record of entry i of the table tfrec_amd_read_captures returns for the same submit.  Conventions, errors
+ * and the TFREC_AMD_E_OVERFLOW prefix of tfrec_amd_read_burst_clocks. */
+int tfrec_amd_read_burst_bands(tfrec_amd_ctx *ctx, tfrec_amd_band *out, size_t cap_runs, uint32_t *n_runs);
+
 /* Burst track (tfrec_amd_enable_burst_track): for every run of the recorder's table what the burst SAID -- one bit per
  * captured sample, the sign of a quadrature discriminator about a centre frequency, boxcar-smoothed: 1 above the centre.  With the
  * rate from the burst clock and the centre from the burst meter a caller slices it into the burst's bits, at any rate, decoded or

@@ -15,6 +15,7 @@ import numpy as np
 from . import _build
 from .burst import BURST_DTYPE  # tfrec_amd_burst
 from .capture import RUN_DTYPE  # tfrec_amd_run
+from .band import BAND_DTYPE  # tfrec_amd_band
 from .clock import CLOCK_DTYPE  # tfrec_amd_clock
 from .crc import CRC_DTYPE  # tfrec_amd_burst_crc
 from .envelope import ENVELOPE_DTYPE  # tfrec_amd_envelope
@@ -121,6 +122,7 @@ EXPORTS = (
     "tfrec_amd_load_streams", "tfrec_amd_enable_burst_envelope", "tfrec_amd_read_burst_envelopes",
     "tfrec_amd_enable_burst_clock", "tfrec_amd_read_burst_clocks",
     "tfrec_amd_enable_burst_keying", "tfrec_amd_read_burst_keyings",
+    "tfrec_amd_enable_burst_band", "tfrec_amd_read_burst_bands",
     "tfrec_amd_enable_burst_track", "tfrec_amd_set_burst_track_centre", "tfrec_amd_read_burst_tracks",
     "tfrec_amd_enable_burst_track_amplitude", "tfrec_amd_set_burst_track_level",
     "tfrec_amd_enable_burst_track_auto", "tfrec_amd_read_burst_track_centres", "tfrec_amd_enable_burst_track_phase",
@@ -234,6 +236,8 @@ def load_library(build: bool = True, experiments: bool = False, short_segments: 
     L.tfrec_amd_read_burst_clocks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
     L.tfrec_amd_enable_burst_keying.argtypes = [C.c_void_p]
     L.tfrec_amd_read_burst_keyings.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+    L.tfrec_amd_enable_burst_band.argtypes = [C.c_void_p]
+    L.tfrec_amd_read_burst_bands.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
     L.tfrec_amd_enable_burst_track.argtypes = [C.c_void_p, C.c_int32]
     L.tfrec_amd_set_burst_track_centre.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tfrec_amd_enable_burst_track_amplitude.argtypes = [C.c_void_p, C.c_int32]
@@ -734,6 +738,17 @@ class Receiver:
         conventions) -> a CLOCK_DTYPE array, one record per entry of that submit's run table (clock.keyings).  allow_overflow: as
         read_burst_clocks; keying_total holds the submit's true run count."""
         return self._read_run_records(self.L.tfrec_amd_read_burst_keyings, CLOCK_DTYPE, "keying_total", allow_overflow)
+
+    def enable_burst_band(self):
+        """Turn the burst band on (tfrec_amd_enable_burst_band; after enable_capture, before the first submit; with or without any
+        other burst stage).  read_burst_bands returns its records."""
+        _check(self.L, self.L.tfrec_amd_enable_burst_band(self.h))
+
+    def read_burst_bands(self, allow_overflow: bool = False) -> np.ndarray:
+        """The burst band's records of the OLDEST undrained submit (tfrec_amd_read_burst_bands; read_burst_clocks' conventions) -> a
+        BAND_DTYPE array, one record per entry of that submit's run table (band.py).  allow_overflow: as read_burst_clocks;
+        band_total holds the submit's true run count."""
+        return self._read_run_records(self.L.tfrec_amd_read_burst_bands, BAND_DTYPE, "band_total", allow_overflow)
 
     def enable_burst_track(self, smooth: int):
         """Turn the burst track on (tfrec_amd_enable_burst_track; after enable_capture, before the first submit; with or without

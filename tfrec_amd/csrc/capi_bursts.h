@@ -1,5 +1,5 @@
 // tfrec_amd/csrc/capi_bursts.h -- the entry points of the five burst stages on the recorder's table: the meter, the
-// envelope (6r), the clock (6s), the envelope clock (6zc: the clock's record and reader), the track (6t, with its centres; 6v, its amplitude mode, with its levels; 6w, its auto-centre mode, with its centre records; 6x, its phase mode; 6y, its line code; 6z, its frame check; 6za, its packet check; 6zb, its pulse slicer) and the sync (6u).  What they share comes first -- the enables'
+// envelope (6r), the clock (6s), the envelope clock (6zc: the clock's record and reader), the burst band (6zd), the track (6t, with its centres; 6v, its amplitude mode, with its levels; 6w, its auto-centre mode, with its centre records; 6x, its phase mode; 6y, its line code; 6z, its frame check; 6za, its packet check; 6zb, its pulse slicer) and the sync (6u).  What they share comes first -- the enables'
 // preflight, the rebase of start_sample, the record-only reader and the record-plus-bitmap reader --, then each
 // stage's enable and read, which add their own argument checks and buffers.  Included by capi.hip, which lists what is where.
 #pragma once
@@ -12,6 +12,7 @@ constexpr StageNames kMeterNames = { "burst meter", "burst", "tfrec_amd_enable_b
 constexpr StageNames kEnvelopeNames = { "burst envelope", "envelope", "tfrec_amd_enable_burst_envelope" };
 constexpr StageNames kClockNames = { "burst clock", "clock", "tfrec_amd_enable_burst_clock" };
 constexpr StageNames kKeyingNames = { "envelope clock", "keying", "tfrec_amd_enable_burst_keying" };
+constexpr StageNames kBandNames = { "burst band", "band", "tfrec_amd_enable_burst_band" };
 constexpr StageNames kTrackNames = { "burst track", "track", "tfrec_amd_enable_burst_track" };
 constexpr StageNames kCentreNames = { "auto-centre track", "centre", "tfrec_amd_enable_burst_track_auto" };
 constexpr StageNames kCodeNames = { "line code", "code", "tfrec_amd_enable_burst_code" };
@@ -197,6 +198,30 @@ int tfrec_amd_enable_burst_keying(tfrec_amd_ctx *c)
 int tfrec_amd_read_burst_keyings(tfrec_amd_ctx *c, tfrec_amd_clock *out, size_t cap_runs, uint32_t *n_runs)
 {
 	return c ? read_run_records(c, c->key, kKeyingNames, out, cap_runs, n_runs) : TFREC_AMD_E_INVAL;
+}
+
+// The burst band: its own record, the clock's reader; beside the sets' records the work list of the largest submit and B's planes,
+// which band_planes_kernel builds here, once
+int tfrec_amd_enable_burst_band(tfrec_amd_ctx *c)
+{
+	if (!c)
+		return TFREC_AMD_E_INVAL;
+	// 16 segments a block: a record's device-side sums stay below 2^15 segments
+	TRY(recorder_preflight(c, kBandNames, c->band.on, c->cfg.max_blocks >= 2048 ? "max_blocks < 2048" : nullptr));
+	EnableGuard<BurstBand> guard(c, c->band);
+	for (int k = 0; k < kSets; k++)
+		TRY(own_device(c, c->band.d_recs[k], (size_t)c->cap.max_runs * sizeof(tfrec_amd_band)));
+	TRY(own_device(c, c->band.d_work, (size_t)16 * c->cfg.max_blocks * c->cfg.n_streams * sizeof(uint2)));
+	TRY(own_device(c, c->band.d_n_work, sizeof(uint32_t)));
+	TRY(own_device(c, c->band.d_planes, kBandPlaneBytes));
+	HIPCHK(launch_band_planes(c->cap.lane.st, c->band.d_planes));  // (the lane's kernels of every submit come behind it)
+	HIPCHK(hipStreamSynchronize(c->cap.lane.st));
+	c->band.on = guard.ok = true;
+	return TFREC_AMD_OK;
+}
+int tfrec_amd_read_burst_bands(tfrec_amd_ctx *c, tfrec_amd_band *out, size_t cap_runs, uint32_t *n_runs)
+{
+	return c ? read_run_records(c, c->band, kBandNames, out, cap_runs, n_runs) : TFREC_AMD_E_INVAL;
 }
 
 // ---- the track

@@ -102,6 +102,13 @@ struct BurstKeying : RunRecords<tfrec_amd_clock> {
 	uint32_t *d_n_work = nullptr;
 	int8_t *d_planes = nullptr;
 };
+// tfrec_amd_enable_burst_band: per set the records; once, the work list of the largest submit with its length, and
+// B's planes
+struct BurstBand : RunRecords<tfrec_amd_band> {
+	uint2 *d_work = nullptr;
+	uint32_t *d_n_work = nullptr;
+	int8_t *d_planes = nullptr;
+};
 // tfrec_amd_enable_burst_track: L; every stream's centre index as the next submit uses it; per set the records
 // (RunRecords), the bitmap (ceil(max_samples / 32) words) and the submit's centre indices with their page-locked
 // source; per stream the carried last 16 pairs and chain position (track_carry_kernel).  amplitude: the track's other mode
@@ -369,6 +376,7 @@ struct tfrec_amd_ctx {
 	RunRecords<tfrec_amd_envelope> env;
 	RunRecords<tfrec_amd_clock> clk;
 	BurstKeying key;
+	BurstBand band;
 	BurstTrack trk;
 	BurstSync syn;
 	BurstCode code;

@@ -445,6 +445,9 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		if (c->key.on)  // the envelope clock: behind the clock, on the table, the working set, the decimated samples and its own work list
 			HIPCHK(launch_burst_keying(c->cap.lane.st, out, b,
 						   { .recs = c->key.d_recs[set], .work = c->key.d_work, .n_work = c->key.d_n_work, .planes = c->key.d_planes }));
+		if (c->band.on)  // the burst band: behind the envelope clock, on the table, the working set, the decimated samples and its own work list
+			HIPCHK(launch_burst_band(c->cap.lane.st, out, b,
+						 { .recs = c->band.d_recs[set], .work = c->band.d_work, .n_work = c->band.d_n_work, .planes = c->band.d_planes }));
 		if (c->trk.on)  // the burst track: behind the clock, on the table, the working set, the samples, the final mask and its own carry
 			TRY(launch_track(c, set, out, b));
 		if (c->pls.on)  // the pulse slicer: behind the track's carry kernel, on the table, the working set, the track's bitmap and its own carry

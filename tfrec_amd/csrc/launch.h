@@ -60,6 +60,15 @@ struct KeyingBufs {
 	uint32_t *n_work;
 	const int8_t *planes;
 };
+// The burst band's buffers (band.h): the set's records, the work list ({ table entry, first sample } per whole segment, 16 x blocks x
+// streams of the largest submit) and its length, and B's planes (1 MB, built once)
+constexpr size_t kBandPlaneBytes = 1u << 20;
+struct BandBufs {
+	tfrec_amd_band *recs;
+	uint2 *work;
+	uint32_t *n_work;
+	const int8_t *planes;
+};
 // The burst sync's buffers and settings (sync.h): the set's records and match bitmap, the set's track bitmap, the carried 64 words
 // of track bits and H of every stream
 struct SyncBufs {
@@ -166,6 +175,8 @@ hipError_t launch_burst_envelope(hipStream_t st, const FrontOut &o, const Captur
 hipError_t launch_burst_clock(hipStream_t st, const FrontOut &o, const CaptureBufs &b, tfrec_amd_clock *out);
 hipError_t launch_keying_planes(hipStream_t st, int8_t *planes);  // (once, at enable)
 hipError_t launch_burst_keying(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const KeyingBufs &k);
+hipError_t launch_band_planes(hipStream_t st, int8_t *planes);  // (once, at enable)
+hipError_t launch_burst_band(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const BandBufs &k);
 hipError_t launch_burst_track(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);
 hipError_t launch_burst_track_amplitude(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);  // (k.centre: the levels)
 hipError_t launch_burst_track_auto(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);  // (k.centre: the set centres in Hz)

@@ -270,6 +270,10 @@ inline int device_worker::open_context()
 		call = "tfrec_amd_enable_burst_keying";
 		r = tfrec_amd_enable_burst_keying(ctx);
 	}
+	if (!r && job.band) {  // -I: the burst band on the recorder's table
+		call = "tfrec_amd_enable_burst_band";
+		r = tfrec_amd_enable_burst_band(ctx);
+	}
 	if (!r && job.amplitude()) {  // -G -O: the track in amplitude mode, every stream at the one level
 		call = "tfrec_amd_enable_burst_track_amplitude";
 		r = tfrec_amd_enable_burst_track_amplitude(ctx, job.track_smooth());
@@ -778,6 +782,8 @@ inline int device_worker::collect(size_t k, batch_result &b)
 		r = read_run_records(k, tfrec_amd_read_burst_clocks, "clock", true, b.clocks);
 	if (!r && job.keying)
 		r = read_run_records(k, tfrec_amd_read_burst_keyings, "keying", true, b.keyings);
+	if (!r && job.band)
+		r = read_run_records(k, tfrec_amd_read_burst_bands, "band", true, b.bands);
 	if (!r && job.tracking())
 		r = read_tracks(k, b);
 	if (!r && job.occupancy()) {  // -A: the detector's records in place of the spectrum's, 16 + N / 8 bytes each

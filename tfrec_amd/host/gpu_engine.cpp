@@ -460,6 +460,8 @@ int gpu_engine::run()
 	clocks.begin(n);
 	chain_report<tfrec_amd_clock> keyings(keying_line);
 	keyings.begin(n);
+	chain_report<tfrec_amd_band> bands(band_line);
+	bands.begin(n);
 	chain_merger<track_piece> tracks, codes;
 	std::vector<track_piece> said, coded;
 	tracks.begin(n);
@@ -531,6 +533,8 @@ int gpu_engine::run()
 				clocks.take(b.clocks, workers[d].plan[k], file_blocks, files, into);
 			if (job.keying)  // -a: likewise, behind -C's lines of the batch (never with a scan)
 				keyings.take(b.keyings, workers[d].plan[k], file_blocks, files, NULL);
+			if (job.band)  // -I: likewise, behind -a's lines of the batch (never with a scan)
+				bands.take(b.bands, workers[d].plan[k], file_blocks, files, NULL);
 			checked.clear();
 			if (job.checking())  // -V (with -Y): the check pieces of the sync's entries -- the same flags, so the chains end together, in one order
 				crcs.take(b.crcs, workers[d].plan[k], file_blocks, checked);

@@ -219,6 +219,11 @@ public:
 	//   keying <file> <start_sample> <n_samples> <n_segments> <keying_hz|-> <quality|->
 	// (job.h: spectrum_summary with kKeyingBand; keying_hz from quarter-Hz as %d.%02d).  Never with set_scan.
 	void set_keying() { job.keying = true; }
+	// -I: the burst band (tfrec_amd_enable_burst_band), with or without any of -M, -Q, -C, -a and -G.  Every context
+	// enables the recorder as for -M and the stage on it; run() merges the records' chains as -C's and prints
+	//   band <file> <start_sample> <n_samples> <n_segments> <peak_hz|-> <centre_hz|-> <bw_hz|-> <lo_hz|-> <hi_hz|->
+	// (job.h: band_summary).  Never with set_scan.
+	void set_band() { job.band = true; }
 	// -G: the burst track (tfrec_amd_enable_burst_track), with or without -M, -Q and -C.  Every context enables the
 	// recorder with a pool for every sample (the bitmap has the pool's size) and the track on it, L = half a symbol of `rate` held
 	// within 1 .. 16, every stream about centre_hz; run() merges the records' chains and their bits across the batches of a file

@@ -101,6 +101,7 @@ struct job_settings {
 	bool envelope = false;         // set_envelope
 	bool clock = false;            // set_clock
 	bool keying = false;           // set_keying
+	bool band = false;             // set_band
 	long track_rate = 0;           // set_track (0: none): the rate in bit/s, 1000 .. 96000
 	long track_centre = 0;         // ... and every stream's centre in Hz
 	long track_level = -1;         // set_track_level (-1: none): -O, the track is the amplitude's, every stream at this level, 0 .. 65535
@@ -135,7 +136,7 @@ struct job_settings {
 
 	bool resampled() const { return rate_p != 1 || rate_q != 1; }
 	bool occupancy() const { return spectrum && occ_ratio; }  // -A, pass 1
-	bool recorder() const { return capture || metering() || enveloping() || clocking() || keying || tracking(); }  // the contexts enable the recorder: for -S, or as the meter's, the envelope's, the clock's, the envelope clock's or the track's table
+	bool recorder() const { return capture || metering() || enveloping() || clocking() || keying || band || tracking(); }  // the contexts enable the recorder: for -S, or as the meter's, the envelope's, the clock's, the envelope clock's, the burst band's or the track's table
 	bool tracking() const { return track_rate != 0; }  // -G (never with -s or -A)
 	bool syncing() const { return sync_bits != 0; }  // -Y (only with -G)
 	bool coding() const { return code_taps != 0; }  // -U (only with -G)
@@ -405,6 +406,7 @@ inline std::vector<occ_channel> occupancy_channels(const std::vector<unsigned lo
 // -Q: the envelope records likewise; one that is cut at the file's end is OPEN (the input's end cut its tail)
 // -C: the clock records likewise
 // -a: the envelope clock's records likewise (the same record)
+// -I: the burst band's records likewise
 // -G: the track records likewise, each with its bits out of the batch's bitmap (track_piece; its functions are further down)
 constexpr uint64_t kTrackKeep = 1ull << 20;  // the samples of a chain's track that are kept
 
@@ -482,6 +484,7 @@ struct batch_result {
 	std::vector<tfrec_amd_envelope> envelopes;
 	std::vector<tfrec_amd_clock> clocks;
 	std::vector<tfrec_amd_clock> keyings;
+	std::vector<tfrec_amd_band> bands;
 	std::vector<tfrec_amd_event> ev;
 	std::vector<tfrec_amd_level> lv;
 	std::vector<tfrec_amd_run> runs;
@@ -699,6 +702,18 @@ struct spectrum_band {
 constexpr spectrum_band kClockBand = { 4, 12, 128, false, "clock" };   // -C: 4500 .. 48000 Hz in 375 Hz bins
 constexpr spectrum_band kKeyingBand = { 1, 3, 127, true, "keying" };   // -a: 281.25 .. 11906.25 Hz in 93.75 Hz bins (the header's "Envelope clock")
 
+// floor(a / b) for b > 0, toward minus infinity
+inline __int128 floor_div(__int128 a, __int128 b) { return a / b - ((a % b) < 0 ? 1 : 0); }
+
+// The parabola through a peak p0 and its neighbours pm, pp -> the peak's offset in units of which a bin holds 2 * half: num = pp - pm,
+// den = 2 p0 - pm - pp, floor((half num + den) / (2 den)) if den > 0 and neither neighbour exceeds p0, else 0
+inline long long spectrum_offset(uint64_t pm_, uint64_t p0_, uint64_t pp_, int half)
+{
+	const __int128 pm = pm_, p0 = p0_, pp = pp_;
+	const __int128 num = pp - pm, den = 2 * p0 - pm - pp;
+	return den > 0 && pm <= p0 && pp <= p0 ? (long long)floor_div(half * num + den, 2 * den) : 0;
+}
+
 // -> whether the summary is defined (n_segments > 0 and the band not empty); then rate = 375 jp + off and quality_c = floor(100 *
 // bins * P[jp] / tot), in 128-bit integers (P[j] = spec[j - bin0] may be saturated: 125 of them need 71 bits)
 inline bool spectrum_summary(const tfrec_amd_clock &r, const spectrum_band &k, long long &rate, unsigned long long &quality_c)
@@ -712,14 +727,8 @@ inline bool spectrum_summary(const tfrec_amd_clock &r, const spectrum_band &k, l
 	}
 	if (!r.n_segments || !tot)
 		return false;
-	const __int128 p0 = r.spec[jp - k.bin0], pm = r.spec[jp - k.bin0 - 1], pp = r.spec[jp - k.bin0 + 1];
-	const __int128 num = pp - pm, den = 2 * p0 - pm - pp;
-	__int128 off = 0;
-	if (den > 0 && pm <= p0 && pp <= p0) {
-		const __int128 a = 375 * num + den, b = 2 * den;  // floor(a / b), b > 0
-		off = a / b - ((a % b) < 0 ? 1 : 0);
-	}
-	rate = 375LL * jp + (long long)off;
+	const unsigned __int128 p0 = r.spec[jp - k.bin0];
+	rate = 375LL * jp + spectrum_offset(r.spec[jp - k.bin0 - 1], r.spec[jp - k.bin0], r.spec[jp - k.bin0 + 1], 375);
 	quality_c = (unsigned long long)((unsigned __int128)100 * (unsigned)(k.hi - k.lo + 1) * (unsigned __int128)p0 / tot);  // (<= 100 * bins)
 	return true;
 }
@@ -749,6 +758,75 @@ inline std::string spectrum_line(const std::string &file, const tfrec_amd_clock 
 inline std::string clock_line(const std::string &file, const tfrec_amd_clock &r) { return spectrum_line(file, r, kClockBand); }
 // -a: keying <file> <start_sample> <n_samples> <n_segments> <keying_hz as %d.%02d|-> <quality_c as %d.%02d|->
 inline std::string keying_line(const std::string &file, const tfrec_amd_clock &r) { return spectrum_line(file, r, kKeyingBand); }
+
+// ---- -I: the burst band's records (include/tfrec_amd.h: tfrec_amd_band, whose text is normative; tfrec_amd/band.py restates merge,
+// summary and the line)
+
+// piece p, which CONTINUES the chain c, merged into it: the clock's rule on 256 bins
+inline void band_add(tfrec_amd_band &c, const tfrec_amd_band &p)
+{
+	c.n_samples += p.n_samples;
+	c.n_segments += p.n_segments;
+	c.n_silent += p.n_silent;
+	for (int i = 0; i < 256; i++) {
+		const uint64_t v = c.spec[i] + p.spec[i];
+		c.spec[i] = v < p.spec[i] ? UINT64_MAX : v;
+	}
+	c.flags = (c.flags & TFREC_AMD_RUN_CONTINUES) | (p.flags & TFREC_AMD_RUN_OPEN);
+}
+
+struct band_figures {
+	long long peak_hz, centre_hz, bw_hz, lo_hz, hi_hz;
+};
+
+// -> whether the summary is defined (n_segments > 0 and the spectrum not empty); then the header's five figures, in 128-bit integers
+// (P[j] = spec[j + 128] may be saturated: 256 of them need 72 bits, 128 times that 79)
+inline bool band_summary(const tfrec_amd_band &r, band_figures &f)
+{
+	const uint64_t *P = r.spec + 128;  // P[j], j = -128 .. 127
+	unsigned __int128 tot = 0;
+	__int128 moment = 0;
+	int jp = -128;
+	for (int j = -128; j <= 127; j++) {
+		tot += P[j];
+		moment += (__int128)j * (__int128)P[j];
+		if (P[j] > P[jp])
+			jp = j;  // (the lowest j of the maximum)
+	}
+	if (!r.n_segments || !tot)
+		return false;
+	f.peak_hz = 750LL * jp + (jp > -128 && jp < 127 ? spectrum_offset(P[jp - 1], P[jp], P[jp + 1], 750) : 0);
+	f.centre_hz = (long long)floor_div(750 * moment, (__int128)tot);
+	int lo = -128, hi = 127;
+	for (unsigned __int128 below = 0; 200 * (below + P[lo]) <= tot; lo++)  // (ends below the top bin: tot > 0)
+		below += P[lo];
+	for (unsigned __int128 above = 0; 200 * (above + P[hi]) <= tot; hi--)
+		above += P[hi];
+	f.bw_hz = 750LL * (hi - lo + 1);
+	const int c = (int)std::min<long long>((long long)floor_div(f.centre_hz, 750), 126);
+	int jl = -128, jh = c + 1;
+	for (int j = -128; j <= c; j++)
+		if (P[j] > P[jl])
+			jl = j;
+	for (int j = c + 1; j <= 127; j++)
+		if (P[j] > P[jh])
+			jh = j;
+	f.lo_hz = 750LL * jl;
+	f.hi_hz = 750LL * jh;
+	return true;
+}
+
+// band <file> <start_sample> <n_samples> <n_segments> <peak_hz|-> <centre_hz|-> <bw_hz|-> <lo_hz|-> <hi_hz|->
+inline std::string band_line(const std::string &file, const tfrec_amd_band &r)
+{
+	band_figures f;
+	std::string s = "band " + file + " " + std::to_string((long long)r.start_sample) + " " + std::to_string(r.n_samples) + " " +
+			std::to_string(r.n_segments);
+	if (!band_summary(r, f))
+		return s + " - - - - -";
+	return s + " " + std::to_string(f.peak_hz) + " " + std::to_string(f.centre_hz) + " " + std::to_string(f.bw_hz) + " " + std::to_string(f.lo_hz) + " " +
+	       std::to_string(f.hi_hz);
+}
 
 // ---- -G: the burst track's records and bits (include/tfrec_amd.h: tfrec_amd_track, whose text is normative; tfrec_amd/track.py
 // restates merge, the slicer and the line)
@@ -1364,6 +1442,7 @@ inline void chain_add(crc_piece &c, const crc_piece &p) { crc_add(c, p); }
 inline void chain_add(sync_piece &c, const sync_piece &p) { sync_add(c, p); }
 inline void chain_add(track_piece &c, const track_piece &p) { track_add(c, p); }
 inline void chain_add(tfrec_amd_clock &c, const tfrec_amd_clock &p) { clock_add(c, p); }
+inline void chain_add(tfrec_amd_band &c, const tfrec_amd_band &p) { band_add(c, p); }
 inline void chain_add(tfrec_amd_envelope &c, const tfrec_amd_envelope &p) { envelope_add(c, p); }
 
 // The chains of pieces across a job's batches, per file (a record's stream is its file's index in the job).  A chain ends with a
@@ -1465,6 +1544,7 @@ struct scan_table {
 				clock_quality = q;
 			}
 		}
+		void note(const tfrec_amd_band &) {}  // (-I prints a line per burst and never runs with a scan)
 		// the median: of an even count the lower of the two in the middle
 		bool burst_snr(unsigned long long &ratio) const
 		{

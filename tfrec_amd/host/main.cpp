@@ -112,6 +112,17 @@
 // alternating pattern reads its pulse-pair rate, half the bit rate of NRZ 1010; a pulse-width code a mixture of its two symbol
 // periods; a square envelope has odd harmonics.  Works with -M, -Q, -C, -G, -O, -J, -S, -R, -n, -d and every input option; not with
 // -X, -k, -K, -s or -A.  No threshold is built in; nothing of it has been measured on real recordings.
+// -I (not in the reference): the burst band (tfrec_amd_enable_burst_band): for every trigger window of every file the power
+// spectrum of the burst's own IQ, 256 bins of 750 Hz over +-96 kHz, Hann-windowed -- where the transmitter's carrier lies to a
+// fraction of a bin (what tells two sensors of one type apart), how wide the burst is (what -W is chosen from) and, for an FSK burst,
+// its two tones.  The contexts enable the recorder as for -M and the stage; the pieces of a window are merged as -C's, and stdout
+// gets, as each window ends,
+//   band <file> <start_sample> <n_samples> <n_segments> <peak_hz|-> <centre_hz|-> <bw_hz|-> <lo_hz|-> <hi_hz|->
+// n_segments: the whole 512-sample segments of the window that entered the spectrum; peak_hz: the spectrum's peak, refined by its
+// neighbours; centre_hz: its centroid; bw_hz: the band that holds 99 % of the power; lo_hz, hi_hz: the strongest bin at or below the
+// centroid's bin and the strongest above it -- an FSK burst's two tones, meaningless for a single carrier or an on-off keyed burst
+// ("-": the window holds no whole segment -- one shorter than 1023 samples may not).  Works with everything -a works with, and -a;
+// not with -X, -k, -K, -s or -A.  No threshold is built in; nothing of it has been measured on real recordings.
 // -G rate[,centre_hz] (not in the reference): the burst track (tfrec_amd_enable_burst_track): for every trigger window
 // of every file, whether or not anything decoded in it, what the burst said when it is read at `rate` bit/s (1000 .. 96000: -C's
 // reading) about centre_hz (|centre_hz| <= 192000, default 0: -M's reading).  The contexts enable the recorder with a pool for every
@@ -365,6 +376,7 @@ struct cli {
 	bool envelope = false;  // -Q
 	bool clock = false;  // -C
 	bool keying = false;  // -a
+	bool band = false;  // -I
 	long track_rate = 0, track_centre = 0;  // -G (rate 0: not given)
 	bool track_centre_given = false;
 	bool track_auto = false;  // -G rate,auto
@@ -440,6 +452,10 @@ static void usage()
 			"              <quality|->' per trigger window (keying_hz: 93.75 Hz bins between 281.25 Hz and 11.9 kHz, two decimals; an\n"
 			"              alternating pattern reads its pulse-pair rate; -: no whole 4096-sample segment); also with -M, -Q, -C, -G, -O, -J,\n"
 			"              -S and -R; not with -X, -k, -K, -s or -A\n"
+			"  -I          measure every burst's IQ spectrum on the GPU, 256 bins of 750 Hz over +-96 kHz: a line 'band <file> <start_sample>\n"
+			"              <n_samples> <n_segments> <peak_hz|-> <centre_hz|-> <bw_hz|-> <lo_hz|-> <hi_hz|->' per trigger window (peak: the\n"
+			"              carrier to a fraction of a bin; centre: the centroid; bw: the 99 %% band; lo, hi: an FSK burst's two tones; -: no\n"
+			"              whole 512-sample segment); with everything -a works with; not with -X, -k, -K, -s or -A\n"
 			"  -G r[,c]    read every burst's bits on the GPU, decoded or not, at r bit/s (1000 .. 96000) about the centre c Hz (default 0): a\n"
 			"              line 'bits <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->' per trigger window, MSB-first,\n"
 			"              1 above the centre (+: longer than the 2^20 samples kept); also with -M, -Q, -C, -S and -R; not with -X, -k, -K,\n"
@@ -553,12 +569,13 @@ bool cli::parse_format(const char *arg)
 int cli::parse(int argc, char **argv)
 {
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCaG:O:Y:U:V:N:J:k:K:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCaIG:O:Y:U:V:N:J:k:K:h")) != -1) {
 		switch (c) {
 		case 'M': meter = true; break;
 		case 'Q': envelope = true; break;
 		case 'C': clock = true; break;
 		case 'a': keying = true; break;
+		case 'I': band = true; break;
 		case 'G': {
 			const char *comma = strchr(optarg, ',');
 			track_auto = comma && !strcmp(comma + 1, "auto");
@@ -782,6 +799,10 @@ int cli::check() const
 			fprintf(stderr, "tfrec_gpu: -k and -K do not carry a burst across runs: not with -a\n");
 			return 2;
 		}
+		if (band) {
+			fprintf(stderr, "tfrec_gpu: -k and -K do not carry a burst across runs: not with -I\n");
+			return 2;
+		}
 		if (track_rate) {
 			fprintf(stderr, "tfrec_gpu: -k and -K do not carry a burst across runs: not with -G\n");
 			return 2;
@@ -842,6 +863,10 @@ int cli::check() const
 	}
 	if (keying && (hexfile || have_scan || have_auto)) {
 		fprintf(stderr, "tfrec_gpu: -a measures the bursts of -L files or of a capture (-R), a line per burst: not with -X, -s or -A\n");
+		return 1;
+	}
+	if (band && (hexfile || have_scan || have_auto)) {
+		fprintf(stderr, "tfrec_gpu: -I measures the bursts of -L files or of a capture (-R), a line per burst: not with -X, -s or -A\n");
 		return 1;
 	}
 	if (track_level >= 0 && track_lag) {
@@ -1151,6 +1176,8 @@ int cli::run()
 		e.set_clock();
 	if (keying)
 		e.set_keying();
+	if (band)
+		e.set_band();
 	if (track_rate)
 		e.set_track(track_rate, track_centre);
 	if (track_level >= 0)
