@@ -1003,6 +1003,78 @@ int tfrec_amd_enable_burst_band(tfrec_amd_ctx *ctx);
  * and the TFREC_AMD_E_OVERFLOW prefix of tfrec_amd_read_burst_clocks. */
 int tfrec_amd_read_burst_bands(tfrec_amd_ctx *ctx, tfrec_amd_band *out, size_t cap_runs, uint32_t *n_runs);
 
+/* Burst correlator (tfrec_amd_enable_burst_corr): for every run of the recorder's table which of up to 16 known sync
+ * templates (a word at a rate) the burst carries -- a soft matched filter: the burst's per-sample instantaneous frequency, the burst
+ * meter's 6 kHz direction, correlated with every template at every sample, in one pass.  Per run and template: the largest and the
+ * smallest score, where each ends, and what tells a peak from the floor.  The burst sync compares one word at one rate on a
+ * hard-limited track; this stage tells transmitters apart that share a word and differ in rate.  One more sibling of the burst clock on
+ * the recorder, independent of every other burst stage.  There is no reference counterpart: this text is normative, tfrec_amd/corr.py
+ * restates it.  Exact integers only; no floating point.
+ *   Settings: n_templates, 1 .. 16; per template t a pattern (the low P = bits[t] bits of patterns[t], 8 <= P <= 64, the most significant
+ *             of them transmitted first: the burst sync's convention) and a rate R = rates[t], 1000 .. 96000 bit/s; one centre_hz, |hz| <=
+ *             192000, c = floor((hz + 3000) / 6000), a true floor (-3001 Hz gives -1).
+ *   Template: b(i) = floor(384000 i / R).  Symbol i (0 the first transmitted) covers the taps [b(i), b(i + 1)): T_t[j] = +1 there for a 1
+ *             bit, -1 for a 0 bit.  K_t = b(P) taps; K_t > 2048 is TFREC_AMD_E_INVAL.  Kp = the largest K_t rounded up to a multiple of
+ *             64; the device keeps the templates right-aligned in Kp taps, zero ahead.
+ *   Soft sample: for entry e of a submit's table (stream s, submit-relative start a, n = n_samples) and 0 <= k < n, u[k] = sb(j) - c,
+ *             j the burst meter's direction (tfrec_amd_burst's hist index) of the product of the pairs at a + k and a + k - 1 -- the
+ *             pair ahead of the submit's first sample for a + k = 0 --, sb(j) = j for j < 32, else j - 64.  u[k] = 0 for a zero
+ *             product, and for k = 0 of an entry without CONTINUES (the chain's first sample has no product).  -64 <= u <= 63.
+ *   History:  H soft samples of the same chain ahead of the piece are available, u[-H] .. u[-1]: H = 0 without CONTINUES, else min(2047,
+ *             H' + n') of the OPEN piece that ended the submit before (the burst sync's rule).
+ *   Score:    Y_t[k] = sum over i < K_t of u[k - K_t + 1 + i] T_t[i]: the window ends AT k.  Defined iff k + H >= K_t - 1.  |Y| <= 64 *
+ *             2048 = 2^17.
+ *   Record:   the entry's first 24 bytes, then per template t < 16: peak = the largest defined Y_t (INT32_MIN where none is defined),
+ *             peak_at = the first k that has it (0 where none), trough and trough_at = the smallest defined Y_t (INT32_MAX where none)
+ *             and the first k that has it, n_pos = the defined positions, sum_abs = the sum of |Y_t| over them.  A template at or
+ *             above n_templates has the none values and zeros.
+ *   Cutting:  merging adds n_samples, n_pos and sum_abs; takes the larger peak and the smaller trough, on a tie the earlier piece's,
+ *             with *_at offset by the n_samples of the pieces ahead; stream, start_sample, thresh and flags follow the burst sync's rule.
+ *             With the history the merged record is the uncut run's (claimed, as for the burst sync, for submits without
+ *             TFREC_AMD_E_OVERFLOW).  A run that does not fit max_samples is not looked at -- its record has the none values -- and
+ *             leaves H = 0; so does an OPEN run beyond max_runs.  A restart drops the chain.  A merged n_pos stays in 32 bits: a chain
+ *             of 2^32 samples, three hours of one burst, is the caller's to refuse, as for the other records' sums.  tfrec_amd_save_streams does not carry the
+ *             history, as for the burst track.
+ *   Summary (normative for tfrec_gpu -y and corr.py), per template with n_pos > 0: m = max(peak, -trough); polarity + iff peak >=
+ *             -trough; dev_hz = floor(6000 m / K_t), the mean deviation along the word; quality_c = floor(100 m n_pos / sum_abs),
+ *             undefined where sum_abs is 0.  The best template has the largest dev_hz, the lowest index on a tie; its word ends at
+ *             peak_at (+) or trough_at (-).  No threshold is built in.
+ *   Limits:   the direction is not circular: a burst near +-192 kHz wraps.  One centre per context.  A phase-keyed or on-off keyed
+ *             burst has no meaningful score.  The templates, the 6 kHz resolution and the summary rest on synthetic input: nothing of
+ *             it has been measured on real recordings.
+ * Turn it on after tfrec_amd_enable_capture and before the first submit.  Device memory, counted in tfrec_amd_get_memory: max_runs * 536
+ * bytes per FIFO set; once, max_samples bytes of soft samples, 16 * Kp bytes of templates, 2052 bytes per stream of carried history, and
+ * a work list of 8 * n_streams * (32 * max_blocks + R) bytes with its length, R = floor(max_blocks * 8192 / 356) + 3 the recorder's
+ * bound on a stream's runs in one submit.  Errors: a null argument, n_templates, a bits[t] or rates[t] or centre_hz outside its range, a
+ * K_t above 2048, no recorder, a second call, or a context of max_blocks >= 524288 (a piece's n_pos, at most 8192 * max_blocks, is
+ * summed on the device in 32 bits; sum_abs <= 2^17 * n_pos cannot overflow 64): TFREC_AMD_E_INVAL; after the first submit or a poisoned
+ * context: TFREC_AMD_E_STATE; TFREC_AMD_E_NOMEM as elsewhere; a call that fails leaves the context exactly as it was.  A context on which
+ * it was never called holds and launches what it did.  Independent of every other burst stage: any subset.  Its five kernels run on the
+ * recorder's low-priority stream behind the burst band's. */
+typedef struct {            /* 32 bytes */
+	int32_t  peak;          /* the largest defined Y; INT32_MIN: none */
+	uint32_t peak_at;       /* the first run-relative k that has it */
+	int32_t  trough;        /* the smallest defined Y; INT32_MAX: none */
+	uint32_t trough_at;
+	uint32_t n_pos;         /* defined positions */
+	uint32_t reserved;      /* 0 */
+	uint64_t sum_abs;       /* the sum of |Y| over them */
+} tfrec_amd_corr_score;
+typedef struct {            /* 536 bytes */
+	uint32_t stream;        /* these five: copied from the table entry */
+	uint32_t flags;
+	int64_t  start_sample;
+	uint32_t n_samples;
+	int32_t  thresh;
+	tfrec_amd_corr_score t[16];
+} tfrec_amd_corr;
+int tfrec_amd_enable_burst_corr(tfrec_amd_ctx *ctx, int32_t n_templates, const uint64_t *patterns, const int32_t *bits, const int32_t *rates,
+				int32_t centre_hz);
+/* out[i] = the burst correlator's record of entry i of the table tfrec_amd_read_captures returns for the same submit.  Conventions,
+ * errors and the TFREC_AMD_E_OVERFLOW prefix of tfrec_amd_read_burst_clocks; TFREC_AMD_E_OVERFLOW also, with every record delivered,
+ * where the submit's pairs did not fit max_samples: the runs behind the pool's end were not looked at. */
+int tfrec_amd_read_burst_corrs(tfrec_amd_ctx *ctx, tfrec_amd_corr *out, size_t cap_runs, uint32_t *n_runs);
+
 /* Burst track (tfrec_amd_enable_burst_track): for every run of the recorder's table what the burst SAID -- one bit per
  * captured sample, the sign of a quadrature discriminator about a centre frequency, boxcar-smoothed: 1 above the centre.  With the
  * rate from the burst clock and the centre from the burst meter a caller slices it into the burst's bits, at any rate, decoded or

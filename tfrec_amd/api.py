@@ -17,6 +17,7 @@ from .burst import BURST_DTYPE  # tfrec_amd_burst
 from .capture import RUN_DTYPE  # tfrec_amd_run
 from .band import BAND_DTYPE  # tfrec_amd_band
 from .clock import CLOCK_DTYPE  # tfrec_amd_clock
+from .corr import CORR_DTYPE  # tfrec_amd_corr
 from .crc import CRC_DTYPE  # tfrec_amd_burst_crc
 from .envelope import ENVELOPE_DTYPE  # tfrec_amd_envelope
 from .levels import LEVEL_DTYPE  # tfrec_amd_level
@@ -123,6 +124,7 @@ EXPORTS = (
     "tfrec_amd_enable_burst_clock", "tfrec_amd_read_burst_clocks",
     "tfrec_amd_enable_burst_keying", "tfrec_amd_read_burst_keyings",
     "tfrec_amd_enable_burst_band", "tfrec_amd_read_burst_bands",
+    "tfrec_amd_enable_burst_corr", "tfrec_amd_read_burst_corrs",
     "tfrec_amd_enable_burst_track", "tfrec_amd_set_burst_track_centre", "tfrec_amd_read_burst_tracks",
     "tfrec_amd_enable_burst_track_amplitude", "tfrec_amd_set_burst_track_level",
     "tfrec_amd_enable_burst_track_auto", "tfrec_amd_read_burst_track_centres", "tfrec_amd_enable_burst_track_phase",
@@ -238,6 +240,8 @@ def load_library(build: bool = True, experiments: bool = False, short_segments: 
     L.tfrec_amd_read_burst_keyings.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
     L.tfrec_amd_enable_burst_band.argtypes = [C.c_void_p]
     L.tfrec_amd_read_burst_bands.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+    L.tfrec_amd_enable_burst_corr.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    L.tfrec_amd_read_burst_corrs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
     L.tfrec_amd_enable_burst_track.argtypes = [C.c_void_p, C.c_int32]
     L.tfrec_amd_set_burst_track_centre.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tfrec_amd_enable_burst_track_amplitude.argtypes = [C.c_void_p, C.c_int32]
@@ -749,6 +753,25 @@ class Receiver:
         BAND_DTYPE array, one record per entry of that submit's run table (band.py).  allow_overflow: as read_burst_clocks;
         band_total holds the submit's true run count."""
         return self._read_run_records(self.L.tfrec_amd_read_burst_bands, BAND_DTYPE, "band_total", allow_overflow)
+
+    def enable_burst_corr(self, templates, centre_hz: int = 0):
+        """Turn the burst correlator on (tfrec_amd_enable_burst_corr; after enable_capture, before the first submit; with or without
+        any other burst stage): every run's soft direction track against the 1 .. 16 `templates`, (pattern, n_bits, rate) each --
+        the low n_bits (8 .. 64) of pattern, MSB first, at rate bit/s --, about `centre_hz`.  read_burst_corrs returns its records."""
+        tp = [tuple(int(v) for v in t) for t in templates]
+        for v in [centre_hz] + [x for t in tp for x in t[1:]]:
+            if not -2 ** 31 <= int(v) < 2 ** 31:  # (refused before ctypes could wrap a value into range)
+                raise TfrecAmdError(E_INVAL, "a template's bits or rate, or the centre, outside its type")
+        pat = np.array([t[0] & (2 ** 64 - 1) for t in tp], dtype=np.uint64)
+        bits = np.array([t[1] for t in tp], dtype=np.int32)
+        rates = np.array([t[2] for t in tp], dtype=np.int32)
+        _check(self.L, self.L.tfrec_amd_enable_burst_corr(self.h, len(tp), pat.ctypes.data, bits.ctypes.data, rates.ctypes.data, int(centre_hz)))
+
+    def read_burst_corrs(self, allow_overflow: bool = False) -> np.ndarray:
+        """The burst correlator's records of the OLDEST undrained submit (tfrec_amd_read_burst_corrs; read_burst_clocks' conventions)
+        -> a CORR_DTYPE array, one record per entry of that submit's run table (corr.py).  allow_overflow: as read_burst_clocks;
+        corr_total holds the submit's true run count."""
+        return self._read_run_records(self.L.tfrec_amd_read_burst_corrs, CORR_DTYPE, "corr_total", allow_overflow)
 
     def enable_burst_track(self, smooth: int):
         """Turn the burst track on (tfrec_amd_enable_burst_track; after enable_capture, before the first submit; with or without

@@ -1,5 +1,5 @@
 // tfrec_amd/csrc/capi_bursts.h -- the entry points of the five burst stages on the recorder's table: the meter, the
-// envelope (6r), the clock (6s), the envelope clock (6zc: the clock's record and reader), the burst band (6zd), the track (6t, with its centres; 6v, its amplitude mode, with its levels; 6w, its auto-centre mode, with its centre records; 6x, its phase mode; 6y, its line code; 6z, its frame check; 6za, its packet check; 6zb, its pulse slicer) and the sync (6u).  What they share comes first -- the enables'
+// envelope (6r), the clock (6s), the envelope clock (6zc: the clock's record and reader), the burst band (6zd), the burst correlator (6ze), the track (6t, with its centres; 6v, its amplitude mode, with its levels; 6w, its auto-centre mode, with its centre records; 6x, its phase mode; 6y, its line code; 6z, its frame check; 6za, its packet check; 6zb, its pulse slicer) and the sync (6u).  What they share comes first -- the enables'
 // preflight, the rebase of start_sample, the record-only reader and the record-plus-bitmap reader --, then each
 // stage's enable and read, which add their own argument checks and buffers.  Included by capi.hip, which lists what is where.
 #pragma once
@@ -13,6 +13,7 @@ constexpr StageNames kEnvelopeNames = { "burst envelope", "envelope", "tfrec_amd
 constexpr StageNames kClockNames = { "burst clock", "clock", "tfrec_amd_enable_burst_clock" };
 constexpr StageNames kKeyingNames = { "envelope clock", "keying", "tfrec_amd_enable_burst_keying" };
 constexpr StageNames kBandNames = { "burst band", "band", "tfrec_amd_enable_burst_band" };
+constexpr StageNames kCorrNames = { "burst correlator", "corr", "tfrec_amd_enable_burst_corr" };
 constexpr StageNames kTrackNames = { "burst track", "track", "tfrec_amd_enable_burst_track" };
 constexpr StageNames kCentreNames = { "auto-centre track", "centre", "tfrec_amd_enable_burst_track_auto" };
 constexpr StageNames kCodeNames = { "line code", "code", "tfrec_amd_enable_burst_code" };
@@ -222,6 +223,81 @@ int tfrec_amd_enable_burst_band(tfrec_amd_ctx *c)
 int tfrec_amd_read_burst_bands(tfrec_amd_ctx *c, tfrec_amd_band *out, size_t cap_runs, uint32_t *n_runs)
 {
 	return c ? read_run_records(c, c->band, kBandNames, out, cap_runs, n_runs) : TFREC_AMD_E_INVAL;
+}
+
+// The burst correlator: its own record, the clock's reader; beside the sets' records the soft bytes, the work list of the largest
+// submit, the carried history, and the bank, which is built here, once, in the B operand's layout: byte b of lane l of chunk q is
+// template l & 15 at tap 64 q + 16 (l >> 4) + b of its Kp right-aligned taps
+int tfrec_amd_enable_burst_corr(tfrec_amd_ctx *c, int32_t n_templates, const uint64_t *patterns, const int32_t *bits, const int32_t *rates,
+				int32_t centre_hz)
+{
+	if (!c || !patterns || !bits || !rates)
+		return TFREC_AMD_E_INVAL;
+	if (n_templates < 1 || n_templates > 16) {
+		snprintf(g_err, sizeof(g_err), "the burst correlator takes 1 .. 16 templates");
+		return TFREC_AMD_E_INVAL;
+	}
+	if (centre_hz < -192000 || centre_hz > 192000) {
+		snprintf(g_err, sizeof(g_err), "the burst correlator's centre is within +-192000 Hz");
+		return TFREC_AMD_E_INVAL;
+	}
+	BurstCorr set;
+	for (int t = 0; t < n_templates; t++) {
+		if (rates[t] < 1000 || rates[t] > 96000 || bits[t] < 8 || bits[t] > 64) {
+			snprintf(g_err, sizeof(g_err), "the burst correlator's template %d: the rate is within [1000, 96000] bit/s, the pattern has 8 .. 64 bits", t);
+			return TFREC_AMD_E_INVAL;
+		}
+		const long long k = 384000LL * bits[t] / rates[t];  // b(P)
+		if (k > kCorrMaxTaps) {
+			snprintf(g_err, sizeof(g_err), "the burst correlator's template %d spans %lld samples, more than %d", t, k, kCorrMaxTaps);
+			return TFREC_AMD_E_INVAL;
+		}
+		set.taps[t] = (int)k;
+		set.kp = std::max(set.kp, ((int)k + 63) / 64 * 64);
+	}
+	set.n_templates = n_templates;
+	set.centre_bin = (centre_hz + 3000 + 6000 * 64) / 6000 - 64;  // floor((hz + 3000) / 6000): the dividend is positive
+	// a piece's n_pos, at most 8192 max_blocks, is summed on the device in 32 bits
+	TRY(recorder_preflight(c, kCorrNames, c->corr.on, c->cfg.max_blocks >= 524288 ? "max_blocks < 524288" : nullptr));
+	std::vector<int8_t> bank((size_t)set.kp * 16, 0);
+	for (int t = 0; t < n_templates; t++) {
+		const int ahead = set.kp - set.taps[t];
+		for (int i = 0; i < bits[t]; i++) {
+			const int8_t v = ((patterns[t] >> (bits[t] - 1 - i)) & 1ull) ? 1 : -1;  // symbol 0: the most significant bit
+			for (long long j = 384000LL * i / rates[t]; j < 384000LL * (i + 1) / rates[t]; j++) {
+				const int tap = ahead + (int)j;
+				bank[((size_t)(tap >> 6) * 64 + (size_t)(16 * ((tap >> 4) & 3) + t)) * 16 + (tap & 15)] = v;
+			}
+		}
+	}
+	EnableGuard<BurstCorr> guard(c, c->corr);
+	BurstCorr &o = c->corr;
+	o = set;
+	const size_t n = (size_t)c->cfg.n_streams;
+	for (int k = 0; k < kSets; k++)
+		TRY(own_device(c, o.d_recs[k], (size_t)c->cap.max_runs * sizeof(tfrec_amd_corr)));
+	TRY(own_device(c, o.d_soft, (size_t)c->cap.max_samples));
+	TRY(own_device(c, o.d_work, n * ((size_t)32 * c->cfg.max_blocks + (size_t)c->cap.stage_cap) * sizeof(uint2)));
+	TRY(own_device(c, o.d_n_work, sizeof(uint32_t)));
+	TRY(own_device(c, o.d_bank, bank.size()));
+	TRY(own_device(c, o.d_carry, n * 2048));
+	TRY(own_device(c, o.d_hist, n * sizeof(uint32_t)));
+	HIPCHK(hipMemcpy(o.d_bank, bank.data(), bank.size(), hipMemcpyHostToDevice));
+	HIPCHK(hipMemset(o.d_carry, 0, n * 2048));  // (never used before a submit has written them: no first submit CONTINUES)
+	HIPCHK(hipMemset(o.d_hist, 0, n * sizeof(uint32_t)));
+	o.on = guard.ok = true;
+	return TFREC_AMD_OK;
+}
+int tfrec_amd_read_burst_corrs(tfrec_amd_ctx *c, tfrec_amd_corr *out, size_t cap_runs, uint32_t *n_runs)
+{
+	if (!c)
+		return TFREC_AMD_E_INVAL;
+	TRY(read_run_records(c, c->corr, kCorrNames, out, cap_runs, n_runs));  // (an overflow of the table, or an error: as the clock's)
+	// every record is delivered; the runs behind the pool's end were not looked at, so a submit whose pairs did not fit is an overflow too
+	int set = 0;
+	CaptureHeader hdr;
+	TRY(begin_records_read(c, c->corr, kCorrNames, &set, &hdr));
+	return hdr.n_pairs > c->cap.max_samples ? TFREC_AMD_E_OVERFLOW : TFREC_AMD_OK;
 }
 
 // ---- the track

@@ -109,6 +109,18 @@ struct BurstBand : RunRecords<tfrec_amd_band> {
 	uint32_t *d_n_work = nullptr;
 	int8_t *d_planes = nullptr;
 };
+// tfrec_amd_enable_burst_corr: per set the records; once, the soft bytes, the work list of the largest submit with its
+// length, the bank, per stream the carried soft bytes and H; the settings as the launcher takes them
+struct BurstCorr : RunRecords<tfrec_amd_corr> {
+	int8_t *d_soft = nullptr;
+	uint2 *d_work = nullptr;
+	uint32_t *d_n_work = nullptr;
+	int8_t *d_bank = nullptr;
+	int8_t *d_carry = nullptr;
+	uint32_t *d_hist = nullptr;
+	int taps[16] = {};
+	int n_templates = 0, kp = 0, centre_bin = 0;
+};
 // tfrec_amd_enable_burst_track: L; every stream's centre index as the next submit uses it; per set the records
 // (RunRecords), the bitmap (ceil(max_samples / 32) words) and the submit's centre indices with their page-locked
 // source; per stream the carried last 16 pairs and chain position (track_carry_kernel).  amplitude: the track's other mode
@@ -377,6 +389,7 @@ struct tfrec_amd_ctx {
 	RunRecords<tfrec_amd_clock> clk;
 	BurstKeying key;
 	BurstBand band;
+	BurstCorr corr;
 	BurstTrack trk;
 	BurstSync syn;
 	BurstCode code;

@@ -448,6 +448,11 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 		if (c->band.on)  // the burst band: behind the envelope clock, on the table, the working set, the decimated samples and its own work list
 			HIPCHK(launch_burst_band(c->cap.lane.st, out, b,
 						 { .recs = c->band.d_recs[set], .work = c->band.d_work, .n_work = c->band.d_n_work, .planes = c->band.d_planes }));
+		if (c->corr.on)  // the burst correlator: behind the burst band, on the table, the working set, the decimated samples, prevdec and its own soft bytes, work list and carry
+			HIPCHK(launch_burst_corr(c->cap.lane.st, out, b,
+						 { .recs = c->corr.d_recs[set], .soft = c->corr.d_soft, .work = c->corr.d_work, .n_work = c->corr.d_n_work,
+						   .bank = c->corr.d_bank, .carry = c->corr.d_carry, .hist = c->corr.d_hist, .taps = c->corr.taps,
+						   .n_templates = c->corr.n_templates, .kp = c->corr.kp, .centre_bin = c->corr.centre_bin }));
 		if (c->trk.on)  // the burst track: behind the clock, on the table, the working set, the samples, the final mask and its own carry
 			TRY(launch_track(c, set, out, b));
 		if (c->pls.on)  // the pulse slicer: behind the track's carry kernel, on the table, the working set, the track's bitmap and its own carry

@@ -69,6 +69,22 @@ struct BandBufs {
 	uint32_t *n_work;
 	const int8_t *planes;
 };
+// The burst correlator's buffers and settings (corr.h): the set's records; once, the soft byte of every captured sample (max_samples
+// bytes, where the sample's pair lies in the pool), the work list ({ table entry, first position } per tile of 256 positions) and its
+// length, the bank (Kp x 16 int8 in the B operand's layout, built at enable), per stream the carried 2048 soft bytes and H; every
+// template's taps K_t, their number, Kp and the centre's bin c
+constexpr int kCorrMaxTaps = 2048;
+struct CorrBufs {
+	tfrec_amd_corr *recs;
+	int8_t *soft;
+	uint2 *work;
+	uint32_t *n_work;
+	const int8_t *bank;
+	int8_t *carry;
+	uint32_t *hist;
+	const int *taps;
+	int n_templates, kp, centre_bin;
+};
 // The burst sync's buffers and settings (sync.h): the set's records and match bitmap, the set's track bitmap, the carried 64 words
 // of track bits and H of every stream
 struct SyncBufs {
@@ -177,6 +193,7 @@ hipError_t launch_keying_planes(hipStream_t st, int8_t *planes);  // (once, at e
 hipError_t launch_burst_keying(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const KeyingBufs &k);
 hipError_t launch_band_planes(hipStream_t st, int8_t *planes);  // (once, at enable)
 hipError_t launch_burst_band(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const BandBufs &k);
+hipError_t launch_burst_corr(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const CorrBufs &k);
 hipError_t launch_burst_track(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);
 hipError_t launch_burst_track_amplitude(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);  // (k.centre: the levels)
 hipError_t launch_burst_track_auto(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);  // (k.centre: the set centres in Hz)

@@ -246,9 +246,9 @@ inline int device_worker::open_context()
 		r = tfrec_amd_map_streams(ctx, all.data(), in_row.data(), (int)n);
 	}
 	if (!r && job.recorder()) {  // -S, sized so that no submit overflows: every sample, and a stream's runs are >= 356 samples long but two
-		call = "tfrec_amd_enable_capture";  // (-M, -Q or -C without -S: the table alone, a pool of one pair; -G: the bitmap has the pool's size)
+		call = "tfrec_amd_enable_capture";  // (-M, -Q or -C without -S: the table alone, a pool of one pair; -G: the bitmap has the pool's size, -y: the soft bytes)
 		r = tfrec_amd_enable_capture(ctx, (uint32_t)(n * ((size_t)bps * TFREC_AMD_BLOCK_DEC / 356 + 3)),
-					     job.capture || job.tracking() ? (uint64_t)n * (uint64_t)bps * TFREC_AMD_BLOCK_DEC : 1);
+					     job.capture || job.tracking() || job.corr.n ? (uint64_t)n * (uint64_t)bps * TFREC_AMD_BLOCK_DEC : 1);
 	}
 	if (!r && job.capture) {  // ... and the pair ahead of every run
 		call = "tfrec_amd_enable_capture_pre";
@@ -273,6 +273,17 @@ inline int device_worker::open_context()
 	if (!r && job.band) {  // -I: the burst band on the recorder's table
 		call = "tfrec_amd_enable_burst_band";
 		r = tfrec_amd_enable_burst_band(ctx);
+	}
+	if (!r && job.corr.n) {  // -y: the burst correlator on the recorder's table
+		call = "tfrec_amd_enable_burst_corr";
+		uint64_t pattern[16];
+		int32_t bits[16], rate[16];
+		for (int t = 0; t < job.corr.n; t++) {
+			pattern[t] = job.corr.pattern[t];
+			bits[t] = job.corr.bits[t];
+			rate[t] = job.corr.rate[t];
+		}
+		r = tfrec_amd_enable_burst_corr(ctx, job.corr.n, pattern, bits, rate, (int32_t)job.corr.centre);
 	}
 	if (!r && job.amplitude()) {  // -G -O: the track in amplitude mode, every stream at the one level
 		call = "tfrec_amd_enable_burst_track_amplitude";
@@ -784,6 +795,8 @@ inline int device_worker::collect(size_t k, batch_result &b)
 		r = read_run_records(k, tfrec_amd_read_burst_keyings, "keying", true, b.keyings);
 	if (!r && job.band)
 		r = read_run_records(k, tfrec_amd_read_burst_bands, "band", true, b.bands);
+	if (!r && job.corr.n)
+		r = read_run_records(k, tfrec_amd_read_burst_corrs, "corr", true, b.corrs);
 	if (!r && job.tracking())
 		r = read_tracks(k, b);
 	if (!r && job.occupancy()) {  // -A: the detector's records in place of the spectrum's, 16 + N / 8 bytes each

@@ -462,6 +462,9 @@ int gpu_engine::run()
 	keyings.begin(n);
 	chain_report<tfrec_amd_band> bands(band_line);
 	bands.begin(n);
+	chain_merger<tfrec_amd_corr> corrs;
+	std::vector<tfrec_amd_corr> correlated;
+	corrs.begin(n);
 	chain_merger<track_piece> tracks, codes;
 	std::vector<track_piece> said, coded;
 	tracks.begin(n);
@@ -535,6 +538,12 @@ int gpu_engine::run()
 				keyings.take(b.keyings, workers[d].plan[k], file_blocks, files, NULL);
 			if (job.band)  // -I: likewise, behind -a's lines of the batch (never with a scan)
 				bands.take(b.bands, workers[d].plan[k], file_blocks, files, NULL);
+			if (job.corr.n) {  // -y: likewise, behind -I's lines of the batch (never with a scan); its line takes the bank
+				correlated.clear();
+				corrs.take(b.corrs, workers[d].plan[k], file_blocks, correlated);
+				for (const tfrec_amd_corr &x : correlated)
+					printf("%s\n", corr_line(files[x.stream], x, job.corr).c_str());
+			}
 			checked.clear();
 			if (job.checking())  // -V (with -Y): the check pieces of the sync's entries -- the same flags, so the chains end together, in one order
 				crcs.take(b.crcs, workers[d].plan[k], file_blocks, checked);

@@ -224,6 +224,12 @@ public:
 	//   band <file> <start_sample> <n_samples> <n_segments> <peak_hz|-> <centre_hz|-> <bw_hz|-> <lo_hz|-> <hi_hz|->
 	// (job.h: band_summary).  Never with set_scan.
 	void set_band() { job.band = true; }
+	// -y: the burst correlator (tfrec_amd_enable_burst_corr), with or without any of -M, -Q, -C, -a, -I and -G.  Every
+	// context enables the recorder with a pool for every sample (the soft bytes have the pool's size) and the stage on it; run() merges
+	// the records' chains as -C's and prints
+	//   corr <file> <start_sample> <n_samples> <best|-> <end_sample|-> <+|-> <dev_hz|-> <quality_c|-> <dev_hz of every template>
+	// (job.h: corr_summary).  Never with set_scan.
+	void set_corr(const job_settings::corr_bank &bank) { job.corr = bank; }
 	// -G: the burst track (tfrec_amd_enable_burst_track), with or without -M, -Q and -C.  Every context enables the
 	// recorder with a pool for every sample (the bitmap has the pool's size) and the track on it, L = half a symbol of `rate` held
 	// within 1 .. 16, every stream about centre_hz; run() merges the records' chains and their bits across the batches of a file

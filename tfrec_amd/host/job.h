@@ -102,6 +102,13 @@ struct job_settings {
 	bool clock = false;            // set_clock
 	bool keying = false;           // set_keying
 	bool band = false;             // set_band
+	struct corr_bank {             // set_corr (n == 0: none): -y's templates, pattern's low bits[t] bits at rate[t] bit/s, and the one centre in Hz
+		int n = 0;
+		unsigned long long pattern[16] = {};
+		int bits[16] = {}, rate[16] = {};
+		long centre = 0;
+		long long taps(int t) const { return 384000LL * bits[t] / rate[t]; }  // K_t = b(P)
+	} corr;
 	long track_rate = 0;           // set_track (0: none): the rate in bit/s, 1000 .. 96000
 	long track_centre = 0;         // ... and every stream's centre in Hz
 	long track_level = -1;         // set_track_level (-1: none): -O, the track is the amplitude's, every stream at this level, 0 .. 65535
@@ -136,7 +143,7 @@ struct job_settings {
 
 	bool resampled() const { return rate_p != 1 || rate_q != 1; }
 	bool occupancy() const { return spectrum && occ_ratio; }  // -A, pass 1
-	bool recorder() const { return capture || metering() || enveloping() || clocking() || keying || band || tracking(); }  // the contexts enable the recorder: for -S, or as the meter's, the envelope's, the clock's, the envelope clock's, the burst band's or the track's table
+	bool recorder() const { return capture || metering() || enveloping() || clocking() || keying || band || corr.n || tracking(); }  // the contexts enable the recorder: for -S, or as the meter's, the envelope's, the clock's, the envelope clock's, the burst band's, the burst correlator's or the track's table
 	bool tracking() const { return track_rate != 0; }  // -G (never with -s or -A)
 	bool syncing() const { return sync_bits != 0; }  // -Y (only with -G)
 	bool coding() const { return code_taps != 0; }  // -U (only with -G)
@@ -407,6 +414,7 @@ inline std::vector<occ_channel> occupancy_channels(const std::vector<unsigned lo
 // -C: the clock records likewise
 // -a: the envelope clock's records likewise (the same record)
 // -I: the burst band's records likewise
+// -y: the burst correlator's records likewise
 // -G: the track records likewise, each with its bits out of the batch's bitmap (track_piece; its functions are further down)
 constexpr uint64_t kTrackKeep = 1ull << 20;  // the samples of a chain's track that are kept
 
@@ -485,6 +493,7 @@ struct batch_result {
 	std::vector<tfrec_amd_clock> clocks;
 	std::vector<tfrec_amd_clock> keyings;
 	std::vector<tfrec_amd_band> bands;
+	std::vector<tfrec_amd_corr> corrs;
 	std::vector<tfrec_amd_event> ev;
 	std::vector<tfrec_amd_level> lv;
 	std::vector<tfrec_amd_run> runs;
@@ -826,6 +835,108 @@ inline std::string band_line(const std::string &file, const tfrec_amd_band &r)
 		return s + " - - - - -";
 	return s + " " + std::to_string(f.peak_hz) + " " + std::to_string(f.centre_hz) + " " + std::to_string(f.bw_hz) + " " + std::to_string(f.lo_hz) + " " +
 	       std::to_string(f.hi_hz);
+}
+
+// ---- -y: the burst correlator's records (include/tfrec_amd.h: tfrec_amd_corr, whose text is normative; tfrec_amd/corr.py restates
+// merge, summary and the line)
+
+// piece p, which CONTINUES the chain c, merged into it: the sums added, the larger peak and the smaller trough -- on a tie the
+// earlier piece's -- with *_at offset by the samples ahead
+inline void corr_add(tfrec_amd_corr &c, const tfrec_amd_corr &p)
+{
+	for (int t = 0; t < 16; t++) {
+		tfrec_amd_corr_score &a = c.t[t];
+		const tfrec_amd_corr_score &b = p.t[t];
+		if (b.n_pos && (!a.n_pos || b.peak > a.peak)) {
+			a.peak = b.peak;
+			a.peak_at = c.n_samples + b.peak_at;
+		}
+		if (b.n_pos && (!a.n_pos || b.trough < a.trough)) {
+			a.trough = b.trough;
+			a.trough_at = c.n_samples + b.trough_at;
+		}
+		a.n_pos += b.n_pos;
+		a.sum_abs += b.sum_abs;
+	}
+	c.n_samples += p.n_samples;
+	c.flags = (c.flags & TFREC_AMD_RUN_CONTINUES) | (p.flags & TFREC_AMD_RUN_OPEN);
+}
+
+// -y's argument: <hex>@<rate>[,<hex>@<rate>...][,c=<hz>] -> the bank, or false: 1 .. 16 templates of 2 .. 16 hex digits at 1000 ..
+// 96000 bit/s and at most 2048 taps, |hz| <= 192000
+inline bool corr_parse(const char *arg, job_settings::corr_bank &k)
+{
+	k = job_settings::corr_bank{};
+	std::string a(arg);
+	for (size_t at = 0; at <= a.size();) {
+		const size_t comma = std::min(a.find(',', at), a.size());
+		const std::string part = a.substr(at, comma - at);
+		at = comma + 1;
+		char *end = NULL;
+		if (part.compare(0, 2, "c=") == 0) {
+			k.centre = strtol(part.c_str() + 2, &end, 10);
+			if (at <= a.size() || end == part.c_str() + 2 || *end || k.centre < -192000 || k.centre > 192000)
+				return false;  // (the last field only)
+			continue;
+		}
+		const size_t mark = part.find('@');
+		if (mark == std::string::npos || mark < 2 || mark > 16 || k.n == 16 || part.find_first_not_of("0123456789abcdefABCDEF") != mark)
+			return false;
+		const long rate = strtol(part.c_str() + mark + 1, &end, 10);
+		if (end == part.c_str() + mark + 1 || *end || rate < 1000 || rate > 96000)
+			return false;
+		k.pattern[k.n] = strtoull(part.substr(0, mark).c_str(), NULL, 16);
+		k.bits[k.n] = 4 * (int)mark;
+		k.rate[k.n] = (int)rate;
+		if (k.taps(k.n++) > 2048)
+			return false;
+	}
+	return k.n > 0;
+}
+
+struct corr_figures {
+	bool defined, plus, has_quality;
+	long long dev_hz, quality_c, end;  // end: the winning extreme's run-relative position
+};
+
+// -> the best template (-1: none has a position) and every template's figures: m = max(peak, -trough), + iff peak >= -trough, dev_hz
+// = floor(6000 m / K_t), quality_c = floor(100 m n_pos / sum_abs) in 128-bit integers; the best has the largest dev_hz, the lowest
+// index on a tie
+inline int corr_summary(const tfrec_amd_corr &r, const job_settings::corr_bank &k, corr_figures (&f)[16])
+{
+	int best = -1;
+	for (int t = 0; t < k.n; t++) {
+		const tfrec_amd_corr_score &x = r.t[t];
+		f[t] = corr_figures{};
+		if (!x.n_pos)
+			continue;
+		const long long peak = x.peak, fall = -(long long)x.trough;
+		const long long m = std::max(peak, fall);  // (>= 0: peak >= trough)
+		f[t].defined = true;
+		f[t].plus = peak >= fall;
+		f[t].dev_hz = (long long)floor_div((__int128)6000 * m, (__int128)k.taps(t));
+		f[t].has_quality = x.sum_abs != 0;
+		if (x.sum_abs)
+			f[t].quality_c = (long long)floor_div((__int128)100 * m * x.n_pos, (__int128)x.sum_abs);
+		f[t].end = f[t].plus ? x.peak_at : x.trough_at;
+		if (best < 0 || f[t].dev_hz > f[best].dev_hz)
+			best = t;
+	}
+	return best;
+}
+
+// corr <file> <start_sample> <n_samples> <best|-> <end_sample|-> <+|-> <dev_hz|-> <quality_c|-> <dev_hz of every template, comma separated, - where undefined>
+inline std::string corr_line(const std::string &file, const tfrec_amd_corr &r, const job_settings::corr_bank &k)
+{
+	corr_figures f[16];
+	const int best = corr_summary(r, k, f);
+	std::string s = "corr " + file + " " + std::to_string((long long)r.start_sample) + " " + std::to_string(r.n_samples), every;
+	for (int t = 0; t < k.n; t++)
+		every += std::string(t ? "," : "") + (f[t].defined ? std::to_string(f[t].dev_hz) : "-");
+	if (best < 0)
+		return s + " - - - - - " + every;
+	return s + " " + std::to_string(best) + " " + std::to_string((long long)r.start_sample + f[best].end) + (f[best].plus ? " + " : " - ") +
+	       std::to_string(f[best].dev_hz) + " " + (f[best].has_quality ? std::to_string(f[best].quality_c) : "-") + " " + every;
 }
 
 // ---- -G: the burst track's records and bits (include/tfrec_amd.h: tfrec_amd_track, whose text is normative; tfrec_amd/track.py
@@ -1443,6 +1554,7 @@ inline void chain_add(sync_piece &c, const sync_piece &p) { sync_add(c, p); }
 inline void chain_add(track_piece &c, const track_piece &p) { track_add(c, p); }
 inline void chain_add(tfrec_amd_clock &c, const tfrec_amd_clock &p) { clock_add(c, p); }
 inline void chain_add(tfrec_amd_band &c, const tfrec_amd_band &p) { band_add(c, p); }
+inline void chain_add(tfrec_amd_corr &c, const tfrec_amd_corr &p) { corr_add(c, p); }
 inline void chain_add(tfrec_amd_envelope &c, const tfrec_amd_envelope &p) { envelope_add(c, p); }
 
 // The chains of pieces across a job's batches, per file (a record's stream is its file's index in the job).  A chain ends with a

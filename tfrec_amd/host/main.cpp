@@ -123,6 +123,16 @@
 // centroid's bin and the strongest above it -- an FSK burst's two tones, meaningless for a single carrier or an on-off keyed burst
 // ("-": the window holds no whole segment -- one shorter than 1023 samples may not).  Works with everything -a works with, and -a;
 // not with -X, -k, -K, -s or -A.  No threshold is built in; nothing of it has been measured on real recordings.
+// -y word@rate[,word@rate...][,c=hz] (not in the reference): the burst correlator (tfrec_amd_enable_burst_corr): which of up
+// to 16 known sync templates every burst carries -- a soft matched filter of the burst's per-sample direction (the burst meter's 6 kHz
+// bin about c Hz, default 0) against every word (2 .. 16 hex digits, MSB first) at its rate (1000 .. 96000 bit/s), in one pass.  The
+// contexts enable the recorder with a pool for every sample, as for -G, and the stage; the pieces of a window are merged as -C's, and
+// stdout gets, as each window ends,
+//   corr <file> <start_sample> <n_samples> <best|-> <end_sample|-> <+|-> <dev_hz|-> <quality_c|-> <dev_hz of every template, comma separated>
+// best: the index of the template with the largest dev_hz; end_sample: where its word ends; +|-: the word or its complement; dev_hz:
+// the mean deviation along the word; quality_c: the peak against the mean |score|, in hundredths ("-": the window is shorter than
+// every template).  Works with everything -I works with, and -I; not with -X, -k, -K, -s or -A.  No threshold is built in; nothing of
+// it has been measured on real recordings.
 // -G rate[,centre_hz] (not in the reference): the burst track (tfrec_amd_enable_burst_track): for every trigger window
 // of every file, whether or not anything decoded in it, what the burst said when it is read at `rate` bit/s (1000 .. 96000: -C's
 // reading) about centre_hz (|centre_hz| <= 192000, default 0: -M's reading).  The contexts enable the recorder with a pool for every
@@ -377,6 +387,7 @@ struct cli {
 	bool clock = false;  // -C
 	bool keying = false;  // -a
 	bool band = false;  // -I
+	job_settings::corr_bank corr;  // -y (n == 0: not given)
 	long track_rate = 0, track_centre = 0;  // -G (rate 0: not given)
 	bool track_centre_given = false;
 	bool track_auto = false;  // -G rate,auto
@@ -456,6 +467,10 @@ static void usage()
 			"              <n_samples> <n_segments> <peak_hz|-> <centre_hz|-> <bw_hz|-> <lo_hz|-> <hi_hz|->' per trigger window (peak: the\n"
 			"              carrier to a fraction of a bin; centre: the centroid; bw: the 99 %% band; lo, hi: an FSK burst's two tones; -: no\n"
 			"              whole 512-sample segment); with everything -a works with; not with -X, -k, -K, -s or -A\n"
+			"  -y w@r[,..] tell every burst's transmitter by sync word and rate on the GPU: up to 16 templates, hex word w (2 .. 16 digits) at r\n"
+			"              bit/s (1000 .. 96000), an optional last field c=<hz> the centre: a line 'corr <file> <start_sample> <n_samples>\n"
+			"              <best|-> <end_sample|-> <+|-> <dev_hz|-> <quality_c|-> <dev_hz of every template>' per trigger window; with\n"
+			"              everything -I works with; not with -X, -k, -K, -s or -A\n"
 			"  -G r[,c]    read every burst's bits on the GPU, decoded or not, at r bit/s (1000 .. 96000) about the centre c Hz (default 0): a\n"
 			"              line 'bits <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->' per trigger window, MSB-first,\n"
 			"              1 above the centre (+: longer than the 2^20 samples kept); also with -M, -Q, -C, -S and -R; not with -X, -k, -K,\n"
@@ -569,13 +584,20 @@ bool cli::parse_format(const char *arg)
 int cli::parse(int argc, char **argv)
 {
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCaIG:O:Y:U:V:N:J:k:K:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCaIy:G:O:Y:U:V:N:J:k:K:h")) != -1) {
 		switch (c) {
 		case 'M': meter = true; break;
 		case 'Q': envelope = true; break;
 		case 'C': clock = true; break;
 		case 'a': keying = true; break;
 		case 'I': band = true; break;
+		case 'y':
+			if (!corr_parse(optarg, corr)) {
+				fprintf(stderr, "tfrec_gpu: bad -y '%s': want <hex>@<rate>[,<hex>@<rate>...][,c=<hz>]: 1 .. 16 templates, 2 .. 16 hex digits, rate within "
+						"1000 .. 96000 with at most 2048 samples a word, hz within +-192000\n", optarg);
+				return 1;
+			}
+			break;
 		case 'G': {
 			const char *comma = strchr(optarg, ',');
 			track_auto = comma && !strcmp(comma + 1, "auto");
@@ -803,6 +825,10 @@ int cli::check() const
 			fprintf(stderr, "tfrec_gpu: -k and -K do not carry a burst across runs: not with -I\n");
 			return 2;
 		}
+		if (corr.n) {
+			fprintf(stderr, "tfrec_gpu: -k and -K do not carry a burst across runs: not with -y\n");
+			return 2;
+		}
 		if (track_rate) {
 			fprintf(stderr, "tfrec_gpu: -k and -K do not carry a burst across runs: not with -G\n");
 			return 2;
@@ -867,6 +893,10 @@ int cli::check() const
 	}
 	if (band && (hexfile || have_scan || have_auto)) {
 		fprintf(stderr, "tfrec_gpu: -I measures the bursts of -L files or of a capture (-R), a line per burst: not with -X, -s or -A\n");
+		return 1;
+	}
+	if (corr.n && (hexfile || have_scan || have_auto)) {
+		fprintf(stderr, "tfrec_gpu: -y measures the bursts of -L files or of a capture (-R), a line per burst: not with -X, -s or -A\n");
 		return 1;
 	}
 	if (track_level >= 0 && track_lag) {
@@ -1178,6 +1208,8 @@ int cli::run()
 		e.set_keying();
 	if (band)
 		e.set_band();
+	if (corr.n)
+		e.set_corr(corr);
 	if (track_rate)
 		e.set_track(track_rate, track_centre);
 	if (track_level >= 0)
