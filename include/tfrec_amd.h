@@ -1075,6 +1075,85 @@ int tfrec_amd_enable_burst_corr(tfrec_amd_ctx *ctx, int32_t n_templates, const u
  * where the submit's pairs did not fit max_samples: the runs behind the pool's end were not looked at. */
 int tfrec_amd_read_burst_corrs(tfrec_amd_ctx *ctx, tfrec_amd_corr *out, size_t cap_runs, uint32_t *n_runs);
 
+/* Burst demodulator (tfrec_amd_enable_burst_demod): for every run of the recorder's table one soft decision per symbol
+ * -- a matched filter (the burst correlator's soft sample summed over each symbol) at a symbol timing recovered from the burst's own
+ * head, optionally with each Manchester bit decided as the difference of its two chips.  The piece between "measure and identify" and
+ * "check a frame": the burst track's bits come from a hard-limited track cut by a run-length slicer, where one misjudged run loses the
+ * word.  One more sibling of the burst clock on the recorder, independent of every other burst stage.  There is no reference
+ * counterpart: this text is normative, tfrec_amd/demod.py restates it.  Exact integers only; no floating point.
+ *   Settings: a rate R, 1000 .. 96000 bit/s; a code, TFREC_AMD_DEMOD_NRZ or TFREC_AMD_DEMOD_MAN (with it 2 R <= 96000); a centre_hz, |hz|
+ *             <= 192000, c = floor((hz + 3000) / 6000), a true floor.  One setting per context, fixed at enable.
+ *   Soft sample: u[k] of an entry is exactly the burst correlator's (tfrec_amd_corr, "Soft sample"), with this stage's c.  -64 <= u <= 63.
+ *   Chain:    the pieces of a run that submits cut (CONTINUES) form a chain; x counts the chain's samples from its first piece's first
+ *             sample, and a piece with A samples of the chain ahead of it holds x = A .. A + n_samples - 1.
+ *   Chips:    a chip is a symbol (NRZ) or half a bit (MAN): the chip rate Rc is R or 2 R, b(i) = floor(384000 i / Rc) in 64 bits.  With
+ *             the timing phase p, chip i covers the x in [p + b(i), p + b(i + 1)) and S_i is the sum of u over them.
+ *   Decisions: D_j = S_j (NRZ) or S_2j - S_2j+1 (MAN: a 1 bit is high, then low), j = 0, 1, ...; |D_j| <= 64 * 384 fits an int16.  Either
+ *             way decision j covers [p + g(j), p + g(j + 1)), g(j) = floor(384000 j / R), at most 384 samples.  The hard bit is D_j > 0.
+ *             A decision belongs to the piece that holds its last sample, x = p + g(j + 1) - 1; one whose span begins in an earlier
+ *             piece is summed over both (each stream carries its chain's last 384 soft samples).
+ *   Timing:   measured once per chain, on its first piece alone (the precedent of tfrec_amd_enable_burst_track_auto, which centres on
+ *             the burst's own head).  Pn = ceil(384000 / R) phases, one symbol (NRZ) or one bit (MAN), Pn <= 384.  Nt = the largest N <= 64
+ *             with g(N) <= 8192.  Ns = the number of j < Nt with Pn - 1 + g(j + 1) <= the piece's n_samples: every phase counts the same
+ *             Ns decisions.  E[p] = the sum over j < Ns of |D_j(p)|, 0 <= p < Pn; p* = the first p with the largest E[p].  Ns < 8: p* = 0,
+ *             the timing is TFREC_AMD_DEMOD_FLAGGED and e_best = e_sum = 0.  For MAN the bit-long range of phases lets the energy decide
+ *             the half-bit ambiguity: a pairing that straddles bit boundaries cancels wherever two equal bits meet.
+ *   Record:   the entry's first 24 bytes; phase = p*, timing (MEASURED or FLAGGED), n_timed = Ns, e_best = E[p*] and e_sum = the sum of
+ *             E[p] over all phases for a chain's first piece; for a piece that CONTINUES phase = the chain's p*, timing = INHERITED, n_timed
+ *             = 0, e_best = e_sum = 0 (phase 0 where the piece before left nothing: see Cutting).  first_symbol = the chain index j of
+ *             the piece's first decision = the number of decisions that end ahead of the piece: 0 for A < p, else floor(((A - p + 1) R -
+ *             1) / 384000); n_symbols = that number for A + n_samples less first_symbol; pool_offset = the entry's.
+ *   Pool:     int16, as long as the capture pool.  Decision q of a piece (chain index first_symbol + q) lies at pool_offset + q; n_symbols
+ *             <= n_samples because g(1) >= 4; the entries pool_offset + n_symbols .. pool_offset + n_samples - 1 are 0.
+ *   Cutting:  merging concatenates the decisions and adds n_samples and n_symbols; everything else is the first piece's; the flags follow
+ *             the burst sync's rule.  The merged record and decisions are the uncut run's whenever the first piece holds g(Nt) + Pn - 1
+ *             samples, 8575 at the most: then both time the same Ns = Nt decisions (as the auto-centre track's 1024 samples).  A shorter
+ *             first piece times fewer decisions than the uncut run would.  A run that does not fit max_samples, or lies beyond max_runs,
+ *             is not looked at (timing TFREC_AMD_DEMOD_NONE, no decisions) and, where it is OPEN, leaves nothing: the piece that
+ *             CONTINUES it is read with A = 0 and p = 0.  A restart drops the chain.  A chain of 2^47 samples is the caller's to refuse
+ *             (A R is formed in 64 bits).  tfrec_amd_save_streams does not carry the state, as for the burst track.
+ *   Summary (normative for tfrec_gpu -w and demod.py): quality_c = floor(100 e_best Pn / e_sum) of a MEASURED timing with e_sum > 0: the
+ *             best phase against the mean phase, in hundredths.  No threshold is built in.
+ *   Limits:   one rate, code and centre per context.  The timing comes from the burst's head only: clock drift along a long burst is
+ *             not tracked.  The direction is not circular: a burst near +-192 kHz wraps.  FSK only: a phase-keyed or on-off keyed burst
+ *             has no meaningful decisions.  Nothing of it has been measured on real recordings.
+ * Turn it on after tfrec_amd_enable_capture and before the first submit.  Device memory, counted in tfrec_amd_get_memory: per FIFO set
+ * max_runs * 72 bytes of records and 2 * max_samples bytes of decisions; once, max_samples bytes of soft samples, 396 bytes per stream
+ * of carried state (384 soft samples, A, p*), and two work lists with their lengths: 8 * n_streams * (2 * max_blocks + R) + 4 * n_streams *
+ * R + 8 bytes, R = floor(max_blocks * 8192 / 356) + 3 the recorder's bound on a stream's runs in one submit.  Errors: a null context, a
+ * rate, code or centre_hz outside its range, MAN above 48000 bit/s, no recorder, or a second call: TFREC_AMD_E_INVAL; after the first
+ * submit or a poisoned context: TFREC_AMD_E_STATE; TFREC_AMD_E_NOMEM as elsewhere; a call that fails leaves the context exactly as it
+ * was.  A context on which it was never called holds and launches what it did.  Its kernels run on the recorder's low-priority stream
+ * behind the burst correlator's. */
+#define TFREC_AMD_DEMOD_NRZ 0
+#define TFREC_AMD_DEMOD_MAN 1
+#define TFREC_AMD_DEMOD_NONE 0u       /* timing: the run was not looked at */
+#define TFREC_AMD_DEMOD_MEASURED 1u   /* m */
+#define TFREC_AMD_DEMOD_FLAGGED 2u    /* f */
+#define TFREC_AMD_DEMOD_INHERITED 3u  /* i */
+typedef struct {            /* 72 bytes */
+	uint32_t stream;        /* these five: copied from the table entry */
+	uint32_t flags;
+	int64_t  start_sample;
+	uint32_t n_samples;
+	int32_t  thresh;
+	uint32_t phase;         /* p* */
+	uint32_t timing;        /* TFREC_AMD_DEMOD_NONE, _MEASURED, _FLAGGED, _INHERITED */
+	uint32_t n_timed;       /* Ns */
+	uint32_t n_symbols;     /* the piece's decisions */
+	uint64_t e_best;        /* E[p*] */
+	uint64_t e_sum;         /* the sum of E[p] */
+	uint64_t first_symbol;  /* the chain index of the piece's first decision */
+	uint64_t pool_offset;   /* the entry's: decision q is pool[pool_offset + q] */
+} tfrec_amd_demod;
+int tfrec_amd_enable_burst_demod(tfrec_amd_ctx *ctx, int32_t rate, int32_t code, int32_t centre_hz);
+/* out[i] = the burst demodulator's record of entry i of the table tfrec_amd_read_captures returns for the same submit; pool = the
+ * decisions of the pairs tfrec_amd_read_captures delivers, cap_pool entries of room (null: the counts and the records alone), *n_pool
+ * their number.  tfrec_amd_read_burst_tracks' conventions and errors, an int16 per pair in place of a bit; TFREC_AMD_E_OVERFLOW, with
+ * the prefixes delivered, where the table or the pool overflowed: the runs behind the pool's end were not looked at. */
+int tfrec_amd_read_burst_demods(tfrec_amd_ctx *ctx, tfrec_amd_demod *out, size_t cap_runs, uint32_t *n_runs, int16_t *pool, size_t cap_pool,
+				uint64_t *n_pool);
+
 /* Burst track (tfrec_amd_enable_burst_track): for every run of the recorder's table what the burst SAID -- one bit per
  * captured sample, the sign of a quadrature discriminator about a centre frequency, boxcar-smoothed: 1 above the centre.  With the
  * rate from the burst clock and the centre from the burst meter a caller slices it into the burst's bits, at any rate, decoded or

@@ -19,6 +19,7 @@ from .band import BAND_DTYPE  # tfrec_amd_band
 from .clock import CLOCK_DTYPE  # tfrec_amd_clock
 from .corr import CORR_DTYPE  # tfrec_amd_corr
 from .crc import CRC_DTYPE  # tfrec_amd_burst_crc
+from .demod import DEMOD_DTYPE  # tfrec_amd_demod
 from .envelope import ENVELOPE_DTYPE  # tfrec_amd_envelope
 from .levels import LEVEL_DTYPE  # tfrec_amd_level
 from .occupancy import OCC_DTYPE  # tfrec_amd_occupancy
@@ -125,6 +126,7 @@ EXPORTS = (
     "tfrec_amd_enable_burst_keying", "tfrec_amd_read_burst_keyings",
     "tfrec_amd_enable_burst_band", "tfrec_amd_read_burst_bands",
     "tfrec_amd_enable_burst_corr", "tfrec_amd_read_burst_corrs",
+    "tfrec_amd_enable_burst_demod", "tfrec_amd_read_burst_demods",
     "tfrec_amd_enable_burst_track", "tfrec_amd_set_burst_track_centre", "tfrec_amd_read_burst_tracks",
     "tfrec_amd_enable_burst_track_amplitude", "tfrec_amd_set_burst_track_level",
     "tfrec_amd_enable_burst_track_auto", "tfrec_amd_read_burst_track_centres", "tfrec_amd_enable_burst_track_phase",
@@ -242,6 +244,9 @@ def load_library(build: bool = True, experiments: bool = False, short_segments: 
     L.tfrec_amd_read_burst_bands.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
     L.tfrec_amd_enable_burst_corr.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     L.tfrec_amd_read_burst_corrs.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+    L.tfrec_amd_enable_burst_demod.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+    L.tfrec_amd_read_burst_demods.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_size_t,
+                                              C.POINTER(C.c_uint64)]
     L.tfrec_amd_enable_burst_track.argtypes = [C.c_void_p, C.c_int32]
     L.tfrec_amd_set_burst_track_centre.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.tfrec_amd_enable_burst_track_amplitude.argtypes = [C.c_void_p, C.c_int32]
@@ -675,23 +680,23 @@ class Receiver:
             pre = pre[:len(self.read_captures(allow_overflow=True)[0])]
         return pre
 
-    def _read_run_records(self, fn, dtype, total_attr, allow_overflow, words=False):
+    def _read_run_records(self, fn, dtype, total_attr, allow_overflow, words=False, word_dtype=np.uint32):
         """What the reads of the five burst stages share: the records of the oldest undrained submit by `fn` -- the count first
-        (no room: E_INVAL), then the records, and with `words` the bitmap's uint32 words beside them.  `total_attr` is given the
+        (no room: E_INVAL), then the records, and with `words` the bitmap's uint32 words (or the pool's entries of `word_dtype`) beside them.  `total_attr` is given the
         submit's true run count; E_OVERFLOW raises unless allow_overflow."""
         ok = (E_OK, E_OVERFLOW) if allow_overflow else (E_OK,)
         nr, nw = C.c_uint32(0), C.c_uint64(0)
         counts = (None, 0, C.byref(nw)) if words else ()
         rc = fn(self.h, None, 0, C.byref(nr), *counts)  # the counts (no room: E_INVAL)
         setattr(self, total_attr, int(nr.value))
-        bits = np.zeros(0, dtype=np.uint32)
+        bits = np.zeros(0, dtype=word_dtype)
         if rc != E_INVAL or nr.value == 0:
             _check(self.L, rc, ok=ok)
             out = np.zeros(0, dtype=dtype)
             return (out, bits) if words else out
         out = np.zeros(min(nr.value, getattr(self, "_capture", (0, 0))[0]), dtype=dtype)
         if words:
-            bits = np.zeros(int(nw.value), dtype=np.uint32)
+            bits = np.zeros(int(nw.value), dtype=word_dtype)
             counts = (bits.ctypes.data if len(bits) else None, len(bits), C.byref(nw))
         _check(self.L, fn(self.h, out.ctypes.data, len(out), C.byref(nr), *counts), ok=ok)
         return (out, bits) if words else out
@@ -772,6 +777,25 @@ class Receiver:
         -> a CORR_DTYPE array, one record per entry of that submit's run table (corr.py).  allow_overflow: as read_burst_clocks;
         corr_total holds the submit's true run count."""
         return self._read_run_records(self.L.tfrec_amd_read_burst_corrs, CORR_DTYPE, "corr_total", allow_overflow)
+
+    def enable_burst_demod(self, rate: int, code: str = "nrz", centre_hz: int = 0):
+        """Turn the burst demodulator on (tfrec_amd_enable_burst_demod; after enable_capture, before the first submit; with or
+        without any other burst stage): one int16 soft decision per symbol of every run at `rate` bit/s, `code` "nrz" or "man", about
+        `centre_hz`, at a symbol timing measured on each chain's head.  read_burst_demods returns the records and the decisions."""
+        for v in (rate, centre_hz):
+            if not -2 ** 31 <= int(v) < 2 ** 31:  # (refused before ctypes could wrap a value into range)
+                raise TfrecAmdError(E_INVAL, "rate or centre outside its type")
+        if code not in ("nrz", "man"):
+            raise TfrecAmdError(E_INVAL, "the code is 'nrz' or 'man'")
+        _check(self.L, self.L.tfrec_amd_enable_burst_demod(self.h, int(rate), 1 if code == "man" else 0, int(centre_hz)))
+
+    def read_burst_demods(self, allow_overflow: bool = False):
+        """The burst demodulator's output of the OLDEST undrained submit (tfrec_amd_read_burst_demods; call it before the drain that
+        pops that submit) -> (a DEMOD_DTYPE array, one record per entry of that submit's run table; the int16 decision pool):
+        demod.decisions_of(rec, pool) is a record's decisions.  Overflow as for read_burst_tracks.  demod_total holds the submit's
+        true run count."""
+        return self._read_run_records(self.L.tfrec_amd_read_burst_demods, DEMOD_DTYPE, "demod_total", allow_overflow, words=True,
+                                      word_dtype=np.int16)
 
     def enable_burst_track(self, smooth: int):
         """Turn the burst track on (tfrec_amd_enable_burst_track; after enable_capture, before the first submit; with or without

@@ -1,5 +1,5 @@
 // tfrec_amd/csrc/capi_bursts.h -- the entry points of the five burst stages on the recorder's table: the meter, the
-// envelope (6r), the clock (6s), the envelope clock (6zc: the clock's record and reader), the burst band (6zd), the burst correlator (6ze), the track (6t, with its centres; 6v, its amplitude mode, with its levels; 6w, its auto-centre mode, with its centre records; 6x, its phase mode; 6y, its line code; 6z, its frame check; 6za, its packet check; 6zb, its pulse slicer) and the sync (6u).  What they share comes first -- the enables'
+// envelope (6r), the clock (6s), the envelope clock (6zc: the clock's record and reader), the burst band (6zd), the burst correlator (6ze), the burst demodulator (6zf), the track (6t, with its centres; 6v, its amplitude mode, with its levels; 6w, its auto-centre mode, with its centre records; 6x, its phase mode; 6y, its line code; 6z, its frame check; 6za, its packet check; 6zb, its pulse slicer) and the sync (6u).  What they share comes first -- the enables'
 // preflight, the rebase of start_sample, the record-only reader and the record-plus-bitmap reader --, then each
 // stage's enable and read, which add their own argument checks and buffers.  Included by capi.hip, which lists what is where.
 #pragma once
@@ -14,6 +14,7 @@ constexpr StageNames kClockNames = { "burst clock", "clock", "tfrec_amd_enable_b
 constexpr StageNames kKeyingNames = { "envelope clock", "keying", "tfrec_amd_enable_burst_keying" };
 constexpr StageNames kBandNames = { "burst band", "band", "tfrec_amd_enable_burst_band" };
 constexpr StageNames kCorrNames = { "burst correlator", "corr", "tfrec_amd_enable_burst_corr" };
+constexpr StageNames kDemodNames = { "burst demodulator", "demod", "tfrec_amd_enable_burst_demod" };
 constexpr StageNames kTrackNames = { "burst track", "track", "tfrec_amd_enable_burst_track" };
 constexpr StageNames kCentreNames = { "auto-centre track", "centre", "tfrec_amd_enable_burst_track_auto" };
 constexpr StageNames kCodeNames = { "line code", "code", "tfrec_amd_enable_burst_code" };
@@ -298,6 +299,83 @@ int tfrec_amd_read_burst_corrs(tfrec_amd_ctx *c, tfrec_amd_corr *out, size_t cap
 	CaptureHeader hdr;
 	TRY(begin_records_read(c, c->corr, kCorrNames, &set, &hdr));
 	return hdr.n_pairs > c->cap.max_samples ? TFREC_AMD_E_OVERFLOW : TFREC_AMD_OK;
+}
+
+// The burst demodulator: its own record and, per set, a decision pool of the capture pool's length; beside them the soft bytes,
+// the two work lists of the largest submit and the carried state
+int tfrec_amd_enable_burst_demod(tfrec_amd_ctx *c, int32_t rate, int32_t code, int32_t centre_hz)
+{
+	if (!c)
+		return TFREC_AMD_E_INVAL;
+	if (rate < 1000 || rate > 96000 || (code != TFREC_AMD_DEMOD_NRZ && code != TFREC_AMD_DEMOD_MAN) || (code == TFREC_AMD_DEMOD_MAN && rate > 48000)) {
+		snprintf(g_err, sizeof(g_err), "the burst demodulator's rate is within [1000, 96000] bit/s, [1000, 48000] with the Manchester code; the code is 0 or 1");
+		return TFREC_AMD_E_INVAL;
+	}
+	if (centre_hz < -192000 || centre_hz > 192000) {
+		snprintf(g_err, sizeof(g_err), "the burst demodulator's centre is within +-192000 Hz");
+		return TFREC_AMD_E_INVAL;
+	}
+	TRY(recorder_preflight(c, kDemodNames, c->dem.on));
+	EnableGuard<BurstDemod> guard(c, c->dem);
+	BurstDemod &o = c->dem;
+	o.rate = rate;
+	o.man = code == TFREC_AMD_DEMOD_MAN;
+	o.pn = (384000 + rate - 1) / rate;
+	for (o.nt = 0; o.nt < 64 && 384000LL * (o.nt + 1) / rate <= 8192; o.nt++)
+		;  // the largest N <= 64 with g(N) <= 8192
+	o.centre_bin = (centre_hz + 3000 + 6000 * 64) / 6000 - 64;  // floor((hz + 3000) / 6000): the dividend is positive
+	const size_t n = (size_t)c->cfg.n_streams;
+	for (int k = 0; k < kSets; k++) {
+		TRY(own_device(c, o.d_recs[k], (size_t)c->cap.max_runs * sizeof(tfrec_amd_demod)));
+		TRY(own_device(c, o.d_dec[k], (size_t)c->cap.max_samples * sizeof(int16_t)));
+	}
+	TRY(own_device(c, o.d_soft, (size_t)c->cap.max_samples));
+	TRY(own_device(c, o.d_work, n * ((size_t)2 * c->cfg.max_blocks + (size_t)c->cap.stage_cap) * sizeof(uint2)));
+	TRY(own_device(c, o.d_timed, n * (size_t)c->cap.stage_cap * sizeof(uint32_t)));
+	TRY(own_device(c, o.d_n_work, 2 * sizeof(uint32_t)));
+	TRY(own_device(c, o.d_carry, n * 384));
+	TRY(own_device(c, o.d_ahead, n * sizeof(unsigned long long)));
+	TRY(own_device(c, o.d_phase, n * sizeof(uint32_t)));
+	HIPCHK(hipMemset(o.d_carry, 0, n * 384));  // (never used before a submit has written them: no first submit CONTINUES)
+	HIPCHK(hipMemset(o.d_ahead, 0, n * sizeof(unsigned long long)));
+	HIPCHK(hipMemset(o.d_phase, 0, n * sizeof(uint32_t)));
+	o.on = guard.ok = true;
+	return TFREC_AMD_OK;
+}
+// The record-plus-pool read: read_run_bitmaps' shape with an int16 per pair in place of a bit
+int tfrec_amd_read_burst_demods(tfrec_amd_ctx *c, tfrec_amd_demod *out, size_t cap_runs, uint32_t *n_runs, int16_t *pool, size_t cap_pool,
+				uint64_t *n_pool)
+{
+	if (!c || !n_runs || !n_pool || (cap_runs > 0 && !out) || (cap_pool > 0 && !pool))
+		return TFREC_AMD_E_INVAL;
+	int set = 0;
+	CaptureHeader hdr;
+	TRY(begin_records_read(c, c->dem, kDemodNames, &set, &hdr));
+	const CaptureOut &o = c->cap;
+	const bool overflow = hdr.n_runs > o.max_runs || hdr.n_pairs > o.max_samples;
+	const size_t have = (size_t)std::min<unsigned long long>(hdr.n_runs, o.max_runs);
+	std::vector<tfrec_amd_demod> tmp(have);
+	if (have)
+		HIPCHK(hipMemcpy(tmp.data(), c->dem.d_recs[set], have * sizeof(tfrec_amd_demod), hipMemcpyDeviceToHost));
+	uint64_t pairs = hdr.n_pairs;
+	if (overflow) {
+		pairs = 0;
+		for (size_t k = 0; k < have && tmp[k].pool_offset + tmp[k].n_samples <= o.max_samples; k++)
+			pairs = tmp[k].pool_offset + tmp[k].n_samples;
+	}
+	*n_runs = (uint32_t)std::min<unsigned long long>(hdr.n_runs, 0xffffffffull);
+	*n_pool = pairs;
+	if (cap_runs < have || (pool && cap_pool < pairs)) {
+		snprintf(g_err, sizeof(g_err), "room for %zu demod records and %zu decisions, the submit delivers %zu and %llu", cap_runs, cap_pool, have,
+			 (unsigned long long)pairs);
+		return TFREC_AMD_E_INVAL;
+	}
+	rebase_start_samples(c, set, tmp.data(), have);
+	if (pool && pairs)
+		HIPCHK(hipMemcpy(pool, c->dem.d_dec[set], (size_t)pairs * sizeof(int16_t), hipMemcpyDeviceToHost));
+	if (have)
+		memcpy(out, tmp.data(), have * sizeof(tfrec_amd_demod));
+	return overflow ? TFREC_AMD_E_OVERFLOW : TFREC_AMD_OK;
 }
 
 // ---- the track

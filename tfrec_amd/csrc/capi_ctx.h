@@ -121,6 +121,19 @@ struct BurstCorr : RunRecords<tfrec_amd_corr> {
 	int taps[16] = {};
 	int n_templates = 0, kp = 0, centre_bin = 0;
 };
+// tfrec_amd_enable_burst_demod: per set the records and the decision pool; once, the soft bytes, the two work lists
+// of the largest submit with their lengths, per stream the carried soft bytes, A and p*; the settings as the launcher takes them
+struct BurstDemod : RunRecords<tfrec_amd_demod> {
+	int16_t *d_dec[kSets] = {};
+	int8_t *d_soft = nullptr;
+	uint2 *d_work = nullptr;
+	uint32_t *d_timed = nullptr;
+	uint32_t *d_n_work = nullptr;
+	int8_t *d_carry = nullptr;
+	unsigned long long *d_ahead = nullptr;
+	uint32_t *d_phase = nullptr;
+	int rate = 0, man = 0, pn = 0, nt = 0, centre_bin = 0;
+};
 // tfrec_amd_enable_burst_track: L; every stream's centre index as the next submit uses it; per set the records
 // (RunRecords), the bitmap (ceil(max_samples / 32) words) and the submit's centre indices with their page-locked
 // source; per stream the carried last 16 pairs and chain position (track_carry_kernel).  amplitude: the track's other mode
@@ -390,6 +403,7 @@ struct tfrec_amd_ctx {
 	BurstKeying key;
 	BurstBand band;
 	BurstCorr corr;
+	BurstDemod dem;
 	BurstTrack trk;
 	BurstSync syn;
 	BurstCode code;

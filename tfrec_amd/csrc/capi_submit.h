@@ -453,6 +453,12 @@ static int submit_common(tfrec_amd_ctx *c, const void *d_iq, size_t stride, int 
 						 { .recs = c->corr.d_recs[set], .soft = c->corr.d_soft, .work = c->corr.d_work, .n_work = c->corr.d_n_work,
 						   .bank = c->corr.d_bank, .carry = c->corr.d_carry, .hist = c->corr.d_hist, .taps = c->corr.taps,
 						   .n_templates = c->corr.n_templates, .kp = c->corr.kp, .centre_bin = c->corr.centre_bin }));
+		if (c->dem.on)  // the burst demodulator: behind the burst correlator, on the table, the working set, the decimated samples, prevdec and its own soft bytes, work lists and carry
+			HIPCHK(launch_burst_demod(c->cap.lane.st, out, b,
+						  { .recs = c->dem.d_recs[set], .dec = c->dem.d_dec[set], .soft = c->dem.d_soft, .work = c->dem.d_work,
+						    .timed = c->dem.d_timed, .n_work = c->dem.d_n_work, .carry = c->dem.d_carry, .ahead = c->dem.d_ahead,
+						    .cphase = c->dem.d_phase, .rate = c->dem.rate, .man = c->dem.man, .pn = c->dem.pn, .nt = c->dem.nt,
+						    .centre_bin = c->dem.centre_bin }));
 		if (c->trk.on)  // the burst track: behind the clock, on the table, the working set, the samples, the final mask and its own carry
 			TRY(launch_track(c, set, out, b));
 		if (c->pls.on)  // the pulse slicer: behind the track's carry kernel, on the table, the working set, the track's bitmap and its own carry

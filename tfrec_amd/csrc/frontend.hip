@@ -849,6 +849,7 @@ hipError_t launch_fmdev(hipStream_t st, const FrontOut &o, EventBuf *eb, int wma
 #include "keying.h"    // keying_planes_kernel, keying_list_kernel, keying_product_kernel, launch_burst_keying
 #include "band.h"      // band_planes_kernel, band_list_kernel, band_product_kernel, launch_burst_band
 #include "corr.h"      // corr_soft_kernel, corr_list_kernel, corr_product_kernel, corr_carry_kernel, launch_burst_corr
+#include "demod.h"     // demod_list_kernel, demod_timing_kernel, demod_symbol_kernel, demod_carry_kernel, launch_burst_demod
 #include "track.h"     // track_kernel, track_carry_kernel, launch_burst_track
 #include "amplitude.h"  // amplitude_kernel, launch_burst_track_amplitude
 #include "centre.h"    // centre_head_kernel, track_centre_kernel, centre_carry_kernel, launch_burst_track_auto

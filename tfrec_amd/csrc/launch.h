@@ -85,6 +85,21 @@ struct CorrBufs {
 	const int *taps;
 	int n_templates, kp, centre_bin;
 };
+// The burst demodulator's buffers and settings (demod.h): the set's records and decision pool (max_samples int16); once, the soft byte
+// of every captured sample, the tile list ({ table entry, first sample } per tile of 4096 samples), the list of the runs to time and
+// the two lengths, per stream the carried 384 soft bytes, the chain's samples ahead A and p*; R, the code, Pn, Nt and the centre's bin c
+struct DemodBufs {
+	tfrec_amd_demod *recs;
+	int16_t *dec;
+	int8_t *soft;
+	uint2 *work;
+	uint32_t *timed;
+	uint32_t *n_work;
+	int8_t *carry;
+	unsigned long long *ahead;
+	uint32_t *cphase;
+	int rate, man, pn, nt, centre_bin;
+};
 // The burst sync's buffers and settings (sync.h): the set's records and match bitmap, the set's track bitmap, the carried 64 words
 // of track bits and H of every stream
 struct SyncBufs {
@@ -194,6 +209,7 @@ hipError_t launch_burst_keying(hipStream_t st, const FrontOut &o, const CaptureB
 hipError_t launch_band_planes(hipStream_t st, int8_t *planes);  // (once, at enable)
 hipError_t launch_burst_band(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const BandBufs &k);
 hipError_t launch_burst_corr(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const CorrBufs &k);
+hipError_t launch_burst_demod(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const DemodBufs &k);
 hipError_t launch_burst_track(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);
 hipError_t launch_burst_track_amplitude(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);  // (k.centre: the levels)
 hipError_t launch_burst_track_auto(hipStream_t st, const FrontOut &o, const CaptureBufs &b, const TrackBufs &k);  // (k.centre: the set centres in Hz)

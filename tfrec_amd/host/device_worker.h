@@ -55,6 +55,7 @@ private:
 	template <class R>
 	int read_run_bitmaps(int (*reader)(tfrec_amd_ctx *, R *, size_t, uint32_t *, uint32_t *, size_t, uint64_t *), std::vector<R> &recs,
 			     std::vector<uint32_t> &words);
+	int read_demods(size_t k, batch_result &b);
 	int read_tracks(size_t k, batch_result &b);
 	typedef int (*estimate_reader)(tfrec_amd_ctx *, int32_t, int16_t *, size_t, int *);
 	int read_last_estimate(size_t k, estimate_reader reader, std::vector<int> &files, std::vector<int16_t> &last);
@@ -246,9 +247,9 @@ inline int device_worker::open_context()
 		r = tfrec_amd_map_streams(ctx, all.data(), in_row.data(), (int)n);
 	}
 	if (!r && job.recorder()) {  // -S, sized so that no submit overflows: every sample, and a stream's runs are >= 356 samples long but two
-		call = "tfrec_amd_enable_capture";  // (-M, -Q or -C without -S: the table alone, a pool of one pair; -G: the bitmap has the pool's size, -y: the soft bytes)
+		call = "tfrec_amd_enable_capture";  // (-M, -Q or -C without -S: the table alone, a pool of one pair; -G: the bitmap has the pool's size, -y: the soft bytes, -w: they and the decisions)
 		r = tfrec_amd_enable_capture(ctx, (uint32_t)(n * ((size_t)bps * TFREC_AMD_BLOCK_DEC / 356 + 3)),
-					     job.capture || job.tracking() || job.corr.n ? (uint64_t)n * (uint64_t)bps * TFREC_AMD_BLOCK_DEC : 1);
+					     job.capture || job.tracking() || job.corr.n || job.demod.rate ? (uint64_t)n * (uint64_t)bps * TFREC_AMD_BLOCK_DEC : 1);
 	}
 	if (!r && job.capture) {  // ... and the pair ahead of every run
 		call = "tfrec_amd_enable_capture_pre";
@@ -284,6 +285,10 @@ inline int device_worker::open_context()
 			rate[t] = job.corr.rate[t];
 		}
 		r = tfrec_amd_enable_burst_corr(ctx, job.corr.n, pattern, bits, rate, (int32_t)job.corr.centre);
+	}
+	if (!r && job.demod.rate) {  // -w: the burst demodulator on the recorder's table
+		call = "tfrec_amd_enable_burst_demod";
+		r = tfrec_amd_enable_burst_demod(ctx, (int32_t)job.demod.rate, job.demod.man ? TFREC_AMD_DEMOD_MAN : TFREC_AMD_DEMOD_NRZ, (int32_t)job.demod.centre);
 	}
 	if (!r && job.amplitude()) {  // -G -O: the track in amplitude mode, every stream at the one level
 		call = "tfrec_amd_enable_burst_track_amplitude";
@@ -634,6 +639,30 @@ inline int device_worker::read_run_bitmaps(int (*reader)(tfrec_amd_ctx *, R *, s
 	return r;
 }
 
+// -w: the batch's demodulator records, each with its first decisions out of the batch's pool (job.h: demod_take): the counts, then
+// both.  stream -> file and the file-end cut as above
+inline int device_worker::read_demods(size_t k, batch_result &b)
+{
+	std::vector<tfrec_amd_demod> recs;
+	std::vector<int16_t> pool;
+	uint32_t nr = 0;
+	uint64_t np = 0;
+	int r = tfrec_amd_read_burst_demods(ctx, NULL, 0, &nr, NULL, 0, &np);  // (the counts: E_INVAL for want of room)
+	if (r == TFREC_AMD_E_INVAL && nr) {
+		recs.resize(nr);
+		pool.resize((size_t)np + 1);
+		r = tfrec_amd_read_burst_demods(ctx, recs.data(), recs.size(), &nr, pool.data(), pool.size(), &np);
+	}
+	if (r == TFREC_AMD_E_OVERFLOW)  // (cannot happen: the table and the pool are sized for the worst case)
+		fprintf(stderr, "tfrec_amd: device %d batch %zu: more runs or pairs than the recorder holds, the decisions are incomplete\n", device, k);
+	if (r)
+		return r;
+	for (tfrec_amd_demod x : recs)
+		if (cut_at_file_end(x, plan[k].file, file_blocks, true))
+			b.demods.push_back(demod_take(x, pool.data()));
+	return 0;
+}
+
 // -G: the batch's track records, each with its bits out of the batch's bitmap.  stream -> file and the file-end cut as above; a
 // record that reaches over its file's end is cut there and is OPEN (job.h: track_take).  -Y: the sync records of the same entries
 // with them, each with its match track (job.h: sync_take), in b.syncs in place of b.tracks.  -G rate,auto: every track piece with
@@ -797,6 +826,8 @@ inline int device_worker::collect(size_t k, batch_result &b)
 		r = read_run_records(k, tfrec_amd_read_burst_bands, "band", true, b.bands);
 	if (!r && job.corr.n)
 		r = read_run_records(k, tfrec_amd_read_burst_corrs, "corr", true, b.corrs);
+	if (!r && job.demod.rate)
+		r = read_demods(k, b);
 	if (!r && job.tracking())
 		r = read_tracks(k, b);
 	if (!r && job.occupancy()) {  // -A: the detector's records in place of the spectrum's, 16 + N / 8 bytes each

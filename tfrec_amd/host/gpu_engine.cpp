@@ -465,6 +465,9 @@ int gpu_engine::run()
 	chain_merger<tfrec_amd_corr> corrs;
 	std::vector<tfrec_amd_corr> correlated;
 	corrs.begin(n);
+	chain_merger<demod_piece> demods;
+	std::vector<demod_piece> demodulated;
+	demods.begin(n);
 	chain_merger<track_piece> tracks, codes;
 	std::vector<track_piece> said, coded;
 	tracks.begin(n);
@@ -543,6 +546,12 @@ int gpu_engine::run()
 				corrs.take(b.corrs, workers[d].plan[k], file_blocks, correlated);
 				for (const tfrec_amd_corr &x : correlated)
 					printf("%s\n", corr_line(files[x.stream], x, job.corr).c_str());
+			}
+			if (job.demod.rate) {  // -w: likewise, behind -y's lines of the batch (never with a scan); its line takes the setting
+				demodulated.clear();
+				demods.take(b.demods, workers[d].plan[k], file_blocks, demodulated);
+				for (const demod_piece &x : demodulated)
+					printf("%s\n", demod_line(files[x.stream], x, job.demod).c_str());
 			}
 			checked.clear();
 			if (job.checking())  // -V (with -Y): the check pieces of the sync's entries -- the same flags, so the chains end together, in one order

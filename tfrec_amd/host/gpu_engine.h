@@ -230,6 +230,12 @@ public:
 	//   corr <file> <start_sample> <n_samples> <best|-> <end_sample|-> <+|-> <dev_hz|-> <quality_c|-> <dev_hz of every template>
 	// (job.h: corr_summary).  Never with set_scan.
 	void set_corr(const job_settings::corr_bank &bank) { job.corr = bank; }
+	// -w: the burst demodulator (tfrec_amd_enable_burst_demod), with or without any of -M, -Q, -C, -a, -I, -y and -G.  Every
+	// context enables the recorder with a pool for every sample (the soft bytes and the decisions have the pool's size) and the stage on
+	// it; run() merges the records' chains and their decisions and prints
+	//   demod <file> <start_sample> <n_samples> <phase> <m|f|i> <quality_c|-> <n_symbols>[+] <hex|->
+	// (job.h: demod_line).  Never with set_scan.
+	void set_demod(const job_settings::demod_setting &k) { job.demod = k; }
 	// -G: the burst track (tfrec_amd_enable_burst_track), with or without -M, -Q and -C.  Every context enables the
 	// recorder with a pool for every sample (the bitmap has the pool's size) and the track on it, L = half a symbol of `rate` held
 	// within 1 .. 16, every stream about centre_hz; run() merges the records' chains and their bits across the batches of a file

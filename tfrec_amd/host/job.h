@@ -109,6 +109,11 @@ struct job_settings {
 		long centre = 0;
 		long long taps(int t) const { return 384000LL * bits[t] / rate[t]; }  // K_t = b(P)
 	} corr;
+	struct demod_setting {         // set_demod (rate == 0: none): -w's rate in bit/s, code (man: Manchester) and centre in Hz
+		long rate = 0, centre = 0;
+		bool man = false;
+		long phases() const { return (384000 + rate - 1) / rate; }  // Pn
+	} demod;
 	long track_rate = 0;           // set_track (0: none): the rate in bit/s, 1000 .. 96000
 	long track_centre = 0;         // ... and every stream's centre in Hz
 	long track_level = -1;         // set_track_level (-1: none): -O, the track is the amplitude's, every stream at this level, 0 .. 65535
@@ -143,7 +148,7 @@ struct job_settings {
 
 	bool resampled() const { return rate_p != 1 || rate_q != 1; }
 	bool occupancy() const { return spectrum && occ_ratio; }  // -A, pass 1
-	bool recorder() const { return capture || metering() || enveloping() || clocking() || keying || band || corr.n || tracking(); }  // the contexts enable the recorder: for -S, or as the meter's, the envelope's, the clock's, the envelope clock's, the burst band's, the burst correlator's or the track's table
+	bool recorder() const { return capture || metering() || enveloping() || clocking() || keying || band || corr.n || demod.rate || tracking(); }  // the contexts enable the recorder: for -S, or as the meter's, the envelope's, the clock's, the envelope clock's, the burst band's, the burst correlator's, the burst demodulator's or the track's table
 	bool tracking() const { return track_rate != 0; }  // -G (never with -s or -A)
 	bool syncing() const { return sync_bits != 0; }  // -Y (only with -G)
 	bool coding() const { return code_taps != 0; }  // -U (only with -G)
@@ -415,6 +420,7 @@ inline std::vector<occ_channel> occupancy_channels(const std::vector<unsigned lo
 // -a: the envelope clock's records likewise (the same record)
 // -I: the burst band's records likewise
 // -y: the burst correlator's records likewise
+// -w: the burst demodulator's records likewise, each with its first decisions out of the batch's pool (demod_piece)
 // -G: the track records likewise, each with its bits out of the batch's bitmap (track_piece; its functions are further down)
 constexpr uint64_t kTrackKeep = 1ull << 20;  // the samples of a chain's track that are kept
 
@@ -441,6 +447,12 @@ inline bool cut_at_file_end(R &x, const std::vector<int> &file, const std::vecto
 	x.stream = (uint32_t)f;
 	return true;
 }
+
+// -w: a demodulator record with the first min(n_symbols, 2048) decisions of its piece, or, merged, of its chain
+constexpr uint32_t kDemodKeep = 2048;
+struct demod_piece : tfrec_amd_demod {
+	std::vector<int16_t> dec;
+};
 
 // A record with its track: bit k of the track is bit k & 31 of bits[k >> 5], for k < min(n_samples, 2^20).  -G rate,auto: with
 // the centre record of the same table entry (centred; centre_take)
@@ -494,6 +506,7 @@ struct batch_result {
 	std::vector<tfrec_amd_clock> keyings;
 	std::vector<tfrec_amd_band> bands;
 	std::vector<tfrec_amd_corr> corrs;
+	std::vector<demod_piece> demods;
 	std::vector<tfrec_amd_event> ev;
 	std::vector<tfrec_amd_level> lv;
 	std::vector<tfrec_amd_run> runs;
@@ -937,6 +950,73 @@ inline std::string corr_line(const std::string &file, const tfrec_amd_corr &r, c
 		return s + " - - - - - " + every;
 	return s + " " + std::to_string(best) + " " + std::to_string((long long)r.start_sample + f[best].end) + (f[best].plus ? " + " : " - ") +
 	       std::to_string(f[best].dev_hz) + " " + (f[best].has_quality ? std::to_string(f[best].quality_c) : "-") + " " + every;
+}
+
+// ---- -w: the burst demodulator's records and decisions (include/tfrec_amd.h: tfrec_amd_demod, whose text is normative;
+// tfrec_amd/demod.py restates merge and the line)
+
+// The entry's record with its decisions out of the batch's pool.  A file-end cut shortens n_samples alone: the decisions stay the
+// device's, as the other records' sums do -- the padding behind a file's end is silence, whose decisions are 0
+inline demod_piece demod_take(const tfrec_amd_demod &r, const int16_t *pool)
+{
+	demod_piece p;
+	static_cast<tfrec_amd_demod &>(p) = r;
+	p.dec.assign(pool + r.pool_offset, pool + r.pool_offset + std::min(r.n_symbols, kDemodKeep));
+	return p;
+}
+
+// piece p, which CONTINUES the chain c, merged into it: the decisions concatenated (the first 2048 kept), n_samples and n_symbols
+// added; the timing stays the first piece's
+inline void demod_add(demod_piece &c, const demod_piece &p)
+{
+	const size_t room = kDemodKeep - c.dec.size();
+	c.dec.insert(c.dec.end(), p.dec.begin(), p.dec.begin() + std::min(room, p.dec.size()));
+	c.n_samples += p.n_samples;
+	c.n_symbols += p.n_symbols;
+	c.flags = (c.flags & TFREC_AMD_RUN_CONTINUES) | (p.flags & TFREC_AMD_RUN_OPEN);
+}
+
+// -w's argument: <rate>[,nrz|man][,c=<hz>] -> the setting, or false: 1000 .. 96000 bit/s (man: 48000), |hz| <= 192000
+inline bool demod_parse(const char *arg, job_settings::demod_setting &k)
+{
+	k = job_settings::demod_setting{};
+	char *end = NULL;
+	k.rate = strtol(arg, &end, 10);
+	if (end == arg)
+		return false;
+	if (!strncmp(end, ",nrz", 4) || !strncmp(end, ",man", 4)) {
+		k.man = end[1] == 'm';
+		end += 4;
+	}
+	if (!strncmp(end, ",c=", 3)) {
+		const char *at = end + 3;
+		k.centre = strtol(at, &end, 10);
+		if (end == at)
+			return false;
+	}
+	return !*end && k.rate >= 1000 && k.rate <= (k.man ? 48000 : 96000) && k.centre >= -192000 && k.centre <= 192000;
+}
+
+// demod <file> <start_sample> <n_samples> <phase> <m|f|i> <quality_c|-> <n_symbols>[+] <hex|->: quality_c = floor(100 E[p*] Pn / sum of
+// E) of a measured timing; the first 2048 hard bits (D > 0), MSB first, the last nibble zero-padded; +: there are more
+inline std::string demod_line(const std::string &file, const demod_piece &c, const job_settings::demod_setting &k)
+{
+	std::string s = "demod " + file + " " + std::to_string((long long)c.start_sample) + " " + std::to_string(c.n_samples) + " " +
+			std::to_string(c.phase) + " " + "-mfi"[c.timing & 3u] + " ";
+	if (c.timing == TFREC_AMD_DEMOD_MEASURED && c.e_sum)
+		s += std::to_string(100ull * c.e_best * (unsigned long long)k.phases() / c.e_sum);  // (e_best < 2^21: below 2^37)
+	else
+		s += "-";
+	s += " " + std::to_string(c.n_symbols) + (c.n_symbols > kDemodKeep ? "+ " : " ");
+	if (c.dec.empty())
+		return s + "-";
+	for (size_t i = 0; i < c.dec.size(); i += 4) {
+		int nib = 0;
+		for (size_t j = 0; j < 4; j++)
+			nib = 2 * nib + (i + j < c.dec.size() && c.dec[i + j] > 0 ? 1 : 0);
+		s += "0123456789abcdef"[nib];
+	}
+	return s;
 }
 
 // ---- -G: the burst track's records and bits (include/tfrec_amd.h: tfrec_amd_track, whose text is normative; tfrec_amd/track.py
@@ -1555,6 +1635,7 @@ inline void chain_add(track_piece &c, const track_piece &p) { track_add(c, p); }
 inline void chain_add(tfrec_amd_clock &c, const tfrec_amd_clock &p) { clock_add(c, p); }
 inline void chain_add(tfrec_amd_band &c, const tfrec_amd_band &p) { band_add(c, p); }
 inline void chain_add(tfrec_amd_corr &c, const tfrec_amd_corr &p) { corr_add(c, p); }
+inline void chain_add(demod_piece &c, const demod_piece &p) { demod_add(c, p); }
 inline void chain_add(tfrec_amd_envelope &c, const tfrec_amd_envelope &p) { envelope_add(c, p); }
 
 // The chains of pieces across a job's batches, per file (a record's stream is its file's index in the job).  A chain ends with a

@@ -133,6 +133,16 @@
 // the mean deviation along the word; quality_c: the peak against the mean |score|, in hundredths ("-": the window is shorter than
 // every template).  Works with everything -I works with, and -I; not with -X, -k, -K, -s or -A.  No threshold is built in; nothing of
 // it has been measured on real recordings.
+// -w rate[,nrz|man][,c=hz] (not in the reference): the burst demodulator (tfrec_amd_enable_burst_demod): one soft decision
+// per symbol of every burst at `rate` bit/s (1000 .. 96000; man, the Manchester code: 48000) about c Hz (default 0) -- the per-sample
+// direction summed over each symbol at a symbol timing recovered from the burst's own head; man: each bit the difference of its two
+// chips.  The contexts enable the recorder with a pool for every sample, as for -G, and the stage; the pieces of a window are merged,
+// and stdout gets, as each window ends,
+//   demod <file> <start_sample> <n_samples> <phase> <m|f|i> <quality_c|-> <n_symbols>[+] <hex|->
+// phase: the timing in samples; m: measured, f: the window is too short for a timing (phase 0), i: the window's first piece is not in
+// the output; quality_c: the best phase's energy against the mean phase's, in hundredths; hex: the first 2048 hard bits, MSB first, 1
+// above the centre (+: there are more).  Works with everything -y works with, and -y; not with -X, -k, -K, -s or -A.  No threshold is
+// built in; nothing of it has been measured on real recordings.
 // -G rate[,centre_hz] (not in the reference): the burst track (tfrec_amd_enable_burst_track): for every trigger window
 // of every file, whether or not anything decoded in it, what the burst said when it is read at `rate` bit/s (1000 .. 96000: -C's
 // reading) about centre_hz (|centre_hz| <= 192000, default 0: -M's reading).  The contexts enable the recorder with a pool for every
@@ -388,6 +398,7 @@ struct cli {
 	bool keying = false;  // -a
 	bool band = false;  // -I
 	job_settings::corr_bank corr;  // -y (n == 0: not given)
+	job_settings::demod_setting demod;  // -w (rate 0: not given)
 	long track_rate = 0, track_centre = 0;  // -G (rate 0: not given)
 	bool track_centre_given = false;
 	bool track_auto = false;  // -G rate,auto
@@ -471,6 +482,10 @@ static void usage()
 			"              bit/s (1000 .. 96000), an optional last field c=<hz> the centre: a line 'corr <file> <start_sample> <n_samples>\n"
 			"              <best|-> <end_sample|-> <+|-> <dev_hz|-> <quality_c|-> <dev_hz of every template>' per trigger window; with\n"
 			"              everything -I works with; not with -X, -k, -K, -s or -A\n"
+			"  -w r[,code] demodulate every burst on the GPU at r bit/s (1000 .. 96000), code nrz (default) or man (Manchester, r <= 48000), an\n"
+			"              optional last field c=<hz> the centre: a matched filter at a symbol timing recovered from the burst's head; a line\n"
+			"              'demod <file> <start_sample> <n_samples> <phase> <m|f|i> <quality_c|-> <n_symbols>[+] <hex|->' per trigger window,\n"
+			"              MSB-first, 1 above the centre; with everything -y works with; not with -X, -k, -K, -s or -A\n"
 			"  -G r[,c]    read every burst's bits on the GPU, decoded or not, at r bit/s (1000 .. 96000) about the centre c Hz (default 0): a\n"
 			"              line 'bits <file> <start_sample> <n_samples> <burst_samples> <n_bits>[+] <hex|->' per trigger window, MSB-first,\n"
 			"              1 above the centre (+: longer than the 2^20 samples kept); also with -M, -Q, -C, -S and -R; not with -X, -k, -K,\n"
@@ -584,7 +599,7 @@ bool cli::parse_format(const char *arg)
 int cli::parse(int argc, char **argv)
 {
 	int c;
-	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCaIy:G:O:Y:U:V:N:J:k:K:h")) != -1) {
+	while ((c = getopt(argc, argv, "T:t:Wf:c:xr:F:qDBd:b:n:L:X:e:E:m:p:s:S:R:P:A::z::Z::MQCaIy:w:G:O:Y:U:V:N:J:k:K:h")) != -1) {
 		switch (c) {
 		case 'M': meter = true; break;
 		case 'Q': envelope = true; break;
@@ -595,6 +610,12 @@ int cli::parse(int argc, char **argv)
 			if (!corr_parse(optarg, corr)) {
 				fprintf(stderr, "tfrec_gpu: bad -y '%s': want <hex>@<rate>[,<hex>@<rate>...][,c=<hz>]: 1 .. 16 templates, 2 .. 16 hex digits, rate within "
 						"1000 .. 96000 with at most 2048 samples a word, hz within +-192000\n", optarg);
+				return 1;
+			}
+			break;
+		case 'w':
+			if (!demod_parse(optarg, demod)) {
+				fprintf(stderr, "tfrec_gpu: bad -w '%s': want <rate>[,nrz|man][,c=<hz>]: rate within 1000 .. 96000 (man: 48000), hz within +-192000\n", optarg);
 				return 1;
 			}
 			break;
@@ -829,6 +850,10 @@ int cli::check() const
 			fprintf(stderr, "tfrec_gpu: -k and -K do not carry a burst across runs: not with -y\n");
 			return 2;
 		}
+		if (demod.rate) {
+			fprintf(stderr, "tfrec_gpu: -k and -K do not carry a burst across runs: not with -w\n");
+			return 2;
+		}
 		if (track_rate) {
 			fprintf(stderr, "tfrec_gpu: -k and -K do not carry a burst across runs: not with -G\n");
 			return 2;
@@ -897,6 +922,10 @@ int cli::check() const
 	}
 	if (corr.n && (hexfile || have_scan || have_auto)) {
 		fprintf(stderr, "tfrec_gpu: -y measures the bursts of -L files or of a capture (-R), a line per burst: not with -X, -s or -A\n");
+		return 1;
+	}
+	if (demod.rate && (hexfile || have_scan || have_auto)) {
+		fprintf(stderr, "tfrec_gpu: -w demodulates the bursts of -L files or of a capture (-R), a line per burst: not with -X, -s or -A\n");
 		return 1;
 	}
 	if (track_level >= 0 && track_lag) {
@@ -1210,6 +1239,8 @@ int cli::run()
 		e.set_band();
 	if (corr.n)
 		e.set_corr(corr);
+	if (demod.rate)
+		e.set_demod(demod);
 	if (track_rate)
 		e.set_track(track_rate, track_centre);
 	if (track_level >= 0)
